@@ -16,10 +16,21 @@ Contract (driver): python bench.py --gpus N --steps K --warmup W.  N > 1: either
 (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* in the environment) or called plainly as ``python bench.py --gpus N ...``, in
 which case it re-launches itself under torch.distributed.run (one rank per GPU, RCCL).
 
-Output (rank 0): the LAST stdout line is ONE compact JSON object (< 4 KB: headline, `roofline`, `cpu_baseline`, a
-`{config: wall_s, collective_s}` calibration summary; benchlib/line.py).  Everything else -- the per-kernel table
-(benchlib/kernels.py), the calibration flows with their phases (benchlib/calibration_flows.py), the probe regions -- is
-printed BEFORE it as `detail <section> <json>` lines and written to bench_detail.json beside this file.
+A plain run does only what the headline needs: set-up, warm-up, the K timed steps (`--regions` consecutive K-step regions,
+default 1), the outputs of the last timed step if `--dump-outputs DIR` is given, and the result line.  `--full` adds
+everything else this benchmark measures, after the timed steps: the eager loop and the three-launch path of the same step,
+`roofline` (back-to-back and isolated launches of the step's kernel), the per-kernel table (benchlib/kernels.py), the
+calibration flows with their phases (benchlib/calibration_flows.py) and `cpu_baseline`.
+
+Every timed region starts from the same quantizer state (the fresh one), so with the same arguments the timed steps compute
+the same thing in every run, whichever way they are issued.  `--dump-outputs DIR` writes what the last timed step returned
+to its caller as DIR/<name>.npy (float32): a fixed, seeded sample of the fake-quantised tensor (`y_sample`, 4 Mi of its
+25 Mi elements) and the quantizer state the step left (`scale`, `zero_point`, `min_val`, `max_val`).
+
+Output (rank 0): the LAST stdout line is ONE compact JSON object (< 4 KB: headline, `roofline`, `cpu_baseline` -- null in a
+plain run --, a `{config: wall_s, collective_s}` calibration summary; benchlib/line.py).  Everything else -- the per-kernel
+table, the calibration flows with their phases, the probe regions -- is printed BEFORE it as `detail <section> <json>`
+lines and written to bench_detail.json beside this file.
 """
 import argparse
 import json
@@ -34,6 +45,23 @@ sys.path.insert(0, ROOT)
 
 from benchlib.common import SHAPE, HBM_PEAK_GBS, COPY_RATE_GBS, GIB, SHORT, make_inputs, make_quantizer, _ops_order, device_identity  # noqa: E402
 from benchlib import line as bench_line  # noqa: E402
+
+DUMP_SAMPLE = 1 << 22            # elements of the fake-quantised output written by --dump-outputs (16 MiB of float32)
+DUMP_SEED = 20261016
+
+
+def dump_outputs(dirname, y, q):
+    """What the last timed step handed its caller, as DIR/<name>.npy (float32): a seeded sample of y (the same indices in
+    every run) and the quantizer state the step left behind."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    flat = y.detach().reshape(-1)
+    g = torch.Generator(device="cpu").manual_seed(DUMP_SEED)
+    idx = torch.randint(0, flat.numel(), (min(DUMP_SAMPLE, flat.numel()),), generator=g).sort().values
+    arrays = {"y_sample": flat[idx.to(flat.device)], "scale": q.scale, "zero_point": q.zero_point,
+              "min_val": q.observer.min_val, "max_val": q.observer.max_val}
+    for name, t in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), t.detach().to(torch.float32).cpu().numpy().reshape(-1))
 
 
 def self_launch(n):
@@ -72,13 +100,18 @@ def main():
     ap.add_argument("--launch", default="auto", choices=["auto", "graph", "eager"],
                     help="how the K timed module calls are issued: one hipGraph replay, the eager loop, or (auto) whichever of the two "
                          "measures faster in untimed K-step regions directly before the timed one")
-    ap.add_argument("--regions", type=int, default=5, help="consecutive timed regions of exactly K steps each; ms_per_step is their median (min / max reported beside it)")
+    ap.add_argument("--regions", type=int, default=1, help="consecutive timed regions of exactly K steps each, each from the same starting state; "
+                                                           "ms_per_step is their median (min / max reported beside it)")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also measure everything beyond the headline: eager loop, "
+                                                        "three-launch path, roofline, per-kernel table, calibration flows, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (seeded sample of y, scale, zero_point, min_val, max_val) as DIR/<name>.npy")
     ap.add_argument("--kernel-launches", type=int, default=1000, help="launches of the step's kernel timed by HIP events on their dispatch packets for `roofline` (a sustained back-to-back run, the regime rocprofv3 --kernel-trace averages over)")
     ap.add_argument("--detail-file", default=os.path.join(ROOT, "bench_detail.json"))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--cpu-budget", type=float, default=20.0)
-    ap.add_argument("--no-calib", action="store_true", help="skip the 256-sample calibration wall-clock section")
-    ap.add_argument("--no-kernel-table", action="store_true", help="skip the per-kernel timing table")
+    ap.add_argument("--no-calib", action="store_true", help="--full: skip the 256-sample calibration wall-clock section")
+    ap.add_argument("--no-kernel-table", action="store_true", help="--full: skip the per-kernel timing table")
     ap.add_argument("--calib-search", default="cached", choices=["cached", "literal"])
     ap.add_argument("--calib-configs", default="0,1,2,3,4,5", help="BASELINE configs whose calibration wall-clock is measured (4 = configs[4] at the bart-LARGE dimensions BASELINE.json names, ~1 min; 5 = the same flow at bart-base dimensions, what the reference's shipped config uses)")
     args = ap.parse_args()
@@ -142,6 +175,16 @@ def main():
         from outlier_suppression_amd import ops as _ops
         _ops.set_tuning(kv.split("=")[0], int(kv.split("=")[1]))
     q = make_quantizer(dev)
+    # the quantizer's running state (statistic, step count, qparams): every timed region starts from this fresh state, so the
+    # K timed steps compute the same results in every run, however many untimed steps the time-based settle phase issued
+    state_bufs = (q.observer.min_val, q.observer.max_val, q.scale.data, q.zero_point.data)
+    fresh = [t.clone() for t in state_bufs]
+
+    def restore_state():
+        q.observer.cnt = 0
+        for dst, src in zip(state_bufs, fresh):
+            dst.copy_(src)
+
     xs, lengths = make_inputs(dev, args.buffers, seed=1234 + rank)
     lengths = lengths.to(dev)
     n_elem = xs[0].numel()
@@ -208,11 +251,14 @@ def main():
                     y = step(i)
             torch.cuda.current_stream().wait_stream(side)
             torch.cuda.synchronize()
+            restore_state()                                  # the step count is baked into the captured launches
+            torch.cuda.synchronize()
             graph = torch.cuda.CUDAGraph()
             with torch.no_grad(), torch.cuda.graph(graph, stream=side):
                 graph_ws = _hip.workspace(dev)
                 for i in range(args.steps):
                     y = step(i)
+            graph_y = y                                      # the last captured step's output: what a replay leaves there
             torch.cuda.synchronize()
             graph.replay()                                   # untimed: the first replay of a graph also uploads it (+4 us/step at K = 20)
             torch.cuda.synchronize()
@@ -287,14 +333,17 @@ def main():
         # idles AND when it has been busy for tens of milliseconds; a short run-up is the state the path's launches meet
         for _ in range(max(3, int(0.012 / (args.steps * 40e-6)))):
             y = issue(pick)
-    # ---- the timed regions: `--regions` CONSECUTIVE regions (default 5) of exactly K steps each, every one bracketed by barrier +
+    # ---- the timed regions: `--regions` CONSECUTIVE regions (default 1) of exactly K steps each, every one bracketed by barrier +
     # synchronize on both sides and (N > 1) closed by the path's exchange; per region the MAX over ranks; `ms_per_step` and
     # `value` are the MEDIAN region (min / max and every region's figure ride beside it: round 5 reported one region)
     region_s, gathered = [], None
     for _ in range(max(1, args.regions)):
+        restore_state()
         dt_r, host_dt, gathered, y = region(pick, exchange=True)
         region_s.append(dt_r)
     gc.enable()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, graph_y if pick == "graph" else y, q)
     if world > 1:
         t = torch.tensor(region_s, device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -351,114 +400,115 @@ def main():
 
     from outlier_suppression_amd import ops as ops_mod
     check_status()
-    # the same K steps as an eager loop (untimed region): GPU time per step and host enqueue time per step
-    with torch.no_grad():
-        eager_runs = []
-        for _ in range(5):                     # median of five K-step loops (a single 1 ms loop is at the mercy of its first call)
-            torch.cuda.synchronize()
-            te = time.perf_counter()
-            for i in range(args.steps):
-                y = step(i)
-            eh = time.perf_counter() - te
-            torch.cuda.synchronize()
-            eager_runs.append((time.perf_counter() - te, eh))
-        eager_runs.sort()
-        eager_dt, eager_host = eager_runs[len(eager_runs) // 2]
-    del y
-    check_status()
-
-    # ---- roofline of the step's kernel.  Two HIP-event clocks, both on the stream the kernel runs on:
-    #  (1) BACK TO BACK, the regime of the timed regions (and of most of a rocprofv3 --kernel-trace of this command): stream
-    #      events around R x K launches issued exactly as a timed region issues them (the picked mode), the first event recorded
-    #      while the GPU is still busy with earlier launches.  Elapsed / launches is the launch PERIOD, and back to back the
-    #      period IS the duration: the trace of this command (profiles/r06_bench_trace_phases.md) shows every graph-replayed or
-    #      eagerly queued launch starting where its predecessor ends (gap 0.00-0.25 us), durations 37.9-38.1 us.  `roofline`
-    #      is priced with THIS duration -- it reproduces from the committed trace.
-    #  (2) ISOLATED: events riding on the dispatch packet of each of --kernel-launches launches (hipExtLaunchKernelGGL inside
-    #      the library).  A launch that carries events is fenced off from its neighbours and meets a drained memory system: 36.9 us
-    #      in the same run, the same figure the trace gives for exactly these launches.  Rounds 1-5 priced `roofline` with this
-    #      one (5 % kinder than the trace average); it is reported as `isolated_launch_us`.
-    reps_b2b = max(1, -(-args.kernel_launches // args.steps))
-    b2b = []
-    with torch.no_grad():
-        for _ in range(3):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            for _ in range(2):
-                issue(pick)                                  # the queue is full when the first event is recorded
-            e0.record()
-            for _ in range(reps_b2b):
-                issue(pick)
-            e1.record()
-            torch.cuda.synchronize()
-            b2b.append(e0.elapsed_time(e1) / (reps_b2b * args.steps))      # ms per launch
-    b2b.sort()
-    b2b_ms = b2b[len(b2b) // 2]
-    check_status()
-    n_probe = max(args.steps, args.kernel_launches)
-    pairs = []
-    for _ in range(n_probe):
-        a, b = ctypes.c_void_p(), ctypes.c_void_p()
-        _hip.check(lib.osq_timing_events_create(ctypes.byref(a), ctypes.byref(b)), "timing_events_create")
-        pairs.append((a, b))
     fused_on = os.environ.get("OSQ_FUSED_STEP", "1") != "0"      # off: ranks sharing one GPU (test hook) run three launches
-    probe_family = _hip.TIME_FUSED_STEP if fused_on else _hip.TIME_FAKE_QUANT
-    with torch.no_grad():
-        for i in range(n_probe):
-            lib.osq_time_next_launch(probe_family, *pairs[i])
-            q(xs[i % len(xs)], lengths, 1)
-    torch.cuda.synchronize()
-    k_seq = []
-    for a, b in pairs:
-        us = ctypes.c_float()
-        _hip.check(lib.osq_timing_elapsed_us(a, b, ctypes.byref(us)), "timing_elapsed_us")
-        k_seq.append(us.value * 1e-3)
-        lib.osq_timing_events_destroy(a, b)
-    k_ms = sorted(k_seq)
-    iso_avg_ms = sum(k_ms) / len(k_ms)
-    probe_bytes = bytes_step if fused_on else 8 * n_elem
-    # one launch per step only with the one-launch step; the three-launch path (ranks sharing a GPU: test hook) is priced by its
-    # fake-quant launch's dispatch events as before
-    k_avg_ms = b2b_ms if fused_on else iso_avg_ms
-    achieved = probe_bytes / (k_avg_ms * 1e-3) / 1e9
-    # roofline.traffic: HBM bytes per launch of the dominant kernel from the PMC counters (FETCH_SIZE x 2 + WRITE_SIZE, separate
-    # rocprofv3 passes: tools/collect_profiles.sh).  Counters cannot be read from inside this process, so the figure comes
-    # from the committed profile -- but only while that profile was taken from the SAME kernel sources: the file carries the
-    # hash of the sources it measured, and a mismatch reports null with the reason instead of a number that went stale
-    traffic, traffic_source, rocprof_avg_us = None, None, None
-    tpath = os.path.join(ROOT, "profiles", "roofline_traffic.json")
-    if os.path.exists(tpath):
-        try:
-            sys.path.insert(0, os.path.join(ROOT, "tools"))
-            from summarize_profiles import kernel_sources_sha256
-            table_j = json.load(open(tpath))
-            now, then = kernel_sources_sha256(), table_j.get("_kernel_sources_sha256")
-            if then == now:
-                entry = next((v for k, v in table_j.items()
-                              if k.startswith("observe_fq_fused_kernel" if fused_on else "fq_tensor_vec_kernel") and isinstance(v, dict)), {})
-                traffic = entry.get("hbm_bytes_per_launch")
-                rocprof_avg_us = round(entry["avg_us_kernel_trace"], 2) if entry.get("avg_us_kernel_trace") else None
-                traffic_source = (f"profiles/roofline_traffic.json ({table_j.get('_profile_tag', '?')}: rocprofv3 --pmc FETCH_SIZE x2 + WRITE_SIZE, separate passes, "
-                                  f"same command; kernel sources sha256 {now[:12]} = the ones built here)")
-            else:
-                traffic_source = (f"none: profiles/roofline_traffic.json was measured on other kernel sources (sha256 {str(then)[:12]} vs {now[:12]} here); "
-                                  "re-run tools/collect_profiles.sh")
-        except Exception as e:
-            traffic, traffic_source = None, f"none: {type(e).__name__}: {e}"[:200]
+    if args.full:
+        # the same K steps as an eager loop (untimed region): GPU time per step and host enqueue time per step
+        with torch.no_grad():
+            eager_runs = []
+            for _ in range(5):                     # median of five K-step loops (a single 1 ms loop is at the mercy of its first call)
+                torch.cuda.synchronize()
+                te = time.perf_counter()
+                for i in range(args.steps):
+                    y = step(i)
+                eh = time.perf_counter() - te
+                torch.cuda.synchronize()
+                eager_runs.append((time.perf_counter() - te, eh))
+            eager_runs.sort()
+            eager_dt, eager_host = eager_runs[len(eager_runs) // 2]
+        del y
+        check_status()
 
-    # the same step as three launches (token_minmax, token_select, fake_quant), for reference
-    from outlier_suppression_amd import ops
-    ops.set_tuning("fused_step", 0)
-    q3 = make_quantizer(dev)
-    with torch.no_grad():
-        for i in range(20):
-            q3(xs[i % len(xs)], lengths, 1)
+        # ---- roofline of the step's kernel.  Two HIP-event clocks, both on the stream the kernel runs on:
+        #  (1) BACK TO BACK, the regime of the timed regions (and of most of a rocprofv3 --kernel-trace of this command): stream
+        #      events around R x K launches issued exactly as a timed region issues them (the picked mode), the first event recorded
+        #      while the GPU is still busy with earlier launches.  Elapsed / launches is the launch PERIOD, and back to back the
+        #      period IS the duration: the trace of this command (profiles/r06_bench_trace_phases.md) shows every graph-replayed or
+        #      eagerly queued launch starting where its predecessor ends (gap 0.00-0.25 us), durations 37.9-38.1 us.  `roofline`
+        #      is priced with THIS duration -- it reproduces from the committed trace.
+        #  (2) ISOLATED: events riding on the dispatch packet of each of --kernel-launches launches (hipExtLaunchKernelGGL inside
+        #      the library).  A launch that carries events is fenced off from its neighbours and meets a drained memory system: 36.9 us
+        #      in the same run, the same figure the trace gives for exactly these launches.  Rounds 1-5 priced `roofline` with this
+        #      one (5 % kinder than the trace average); it is reported as `isolated_launch_us`.
+        reps_b2b = max(1, -(-args.kernel_launches // args.steps))
+        b2b = []
+        with torch.no_grad():
+            for _ in range(3):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                for _ in range(2):
+                    issue(pick)                                  # the queue is full when the first event is recorded
+                e0.record()
+                for _ in range(reps_b2b):
+                    issue(pick)
+                e1.record()
+                torch.cuda.synchronize()
+                b2b.append(e0.elapsed_time(e1) / (reps_b2b * args.steps))      # ms per launch
+        b2b.sort()
+        b2b_ms = b2b[len(b2b) // 2]
+        check_status()
+        n_probe = max(args.steps, args.kernel_launches)
+        pairs = []
+        for _ in range(n_probe):
+            a, b = ctypes.c_void_p(), ctypes.c_void_p()
+            _hip.check(lib.osq_timing_events_create(ctypes.byref(a), ctypes.byref(b)), "timing_events_create")
+            pairs.append((a, b))
+        probe_family = _hip.TIME_FUSED_STEP if fused_on else _hip.TIME_FAKE_QUANT
+        with torch.no_grad():
+            for i in range(n_probe):
+                lib.osq_time_next_launch(probe_family, *pairs[i])
+                q(xs[i % len(xs)], lengths, 1)
         torch.cuda.synchronize()
-        t3 = time.perf_counter()
-        for i in range(max(args.steps, 50)):
-            q3(xs[i % len(xs)], lengths, 1)
-        torch.cuda.synchronize()
-        three_ms = (time.perf_counter() - t3) / max(args.steps, 50) * 1e3
-    ops.set_tuning("fused_step", 1)
+        k_seq = []
+        for a, b in pairs:
+            us = ctypes.c_float()
+            _hip.check(lib.osq_timing_elapsed_us(a, b, ctypes.byref(us)), "timing_elapsed_us")
+            k_seq.append(us.value * 1e-3)
+            lib.osq_timing_events_destroy(a, b)
+        k_ms = sorted(k_seq)
+        iso_avg_ms = sum(k_ms) / len(k_ms)
+        probe_bytes = bytes_step if fused_on else 8 * n_elem
+        # one launch per step only with the one-launch step; the three-launch path (ranks sharing a GPU: test hook) is priced by its
+        # fake-quant launch's dispatch events as before
+        k_avg_ms = b2b_ms if fused_on else iso_avg_ms
+        achieved = probe_bytes / (k_avg_ms * 1e-3) / 1e9
+        # roofline.traffic: HBM bytes per launch of the dominant kernel from the PMC counters (FETCH_SIZE x 2 + WRITE_SIZE, separate
+        # rocprofv3 passes: tools/collect_profiles.sh).  Counters cannot be read from inside this process, so the figure comes
+        # from the committed profile -- but only while that profile was taken from the SAME kernel sources: the file carries the
+        # hash of the sources it measured, and a mismatch reports null with the reason instead of a number that went stale
+        traffic, traffic_source, rocprof_avg_us = None, None, None
+        tpath = os.path.join(ROOT, "profiles", "roofline_traffic.json")
+        if os.path.exists(tpath):
+            try:
+                sys.path.insert(0, os.path.join(ROOT, "tools"))
+                from summarize_profiles import kernel_sources_sha256
+                table_j = json.load(open(tpath))
+                now, then = kernel_sources_sha256(), table_j.get("_kernel_sources_sha256")
+                if then == now:
+                    entry = next((v for k, v in table_j.items()
+                                  if k.startswith("observe_fq_fused_kernel" if fused_on else "fq_tensor_vec_kernel") and isinstance(v, dict)), {})
+                    traffic = entry.get("hbm_bytes_per_launch")
+                    rocprof_avg_us = round(entry["avg_us_kernel_trace"], 2) if entry.get("avg_us_kernel_trace") else None
+                    traffic_source = (f"profiles/roofline_traffic.json ({table_j.get('_profile_tag', '?')}: rocprofv3 --pmc FETCH_SIZE x2 + WRITE_SIZE, separate passes, "
+                                      f"same command; kernel sources sha256 {now[:12]} = the ones built here)")
+                else:
+                    traffic_source = (f"none: profiles/roofline_traffic.json was measured on other kernel sources (sha256 {str(then)[:12]} vs {now[:12]} here); "
+                                      "re-run tools/collect_profiles.sh")
+            except Exception as e:
+                traffic, traffic_source = None, f"none: {type(e).__name__}: {e}"[:200]
+
+        # the same step as three launches (token_minmax, token_select, fake_quant), for reference
+        from outlier_suppression_amd import ops
+        ops.set_tuning("fused_step", 0)
+        q3 = make_quantizer(dev)
+        with torch.no_grad():
+            for i in range(20):
+                q3(xs[i % len(xs)], lengths, 1)
+            torch.cuda.synchronize()
+            t3 = time.perf_counter()
+            for i in range(max(args.steps, 50)):
+                q3(xs[i % len(xs)], lengths, 1)
+            torch.cuda.synchronize()
+            three_ms = (time.perf_counter() - t3) / max(args.steps, 50) * 1e3
+        ops.set_tuning("fused_step", 1)
 
     value = bytes_step * args.steps * world / dt / GIB
     per_step_us = [round(r / args.steps * 1e6, 3) for r in region_s]
@@ -491,35 +541,37 @@ def main():
                    "probe_regions_us_per_step": probe_stats,
                    "sum_tier": ("package default: MSEFast losses in ATen's one-thread order, LSQ / LSQ+ parameter gradients order-free; the step "
                                 "itself holds no such sum" if _ops_order() else "order-free (OSQ_STRICT=0)"),
-                   "eager_ms_per_step": round(eager_dt / args.steps * 1e3, 5),
-                   "host_enqueue_ms_per_step": round(eager_host / args.steps * 1e3, 5),
-                   "three_launch_path_ms_per_step": round(three_ms, 5),
                    "pct_hbm_peak": round(100.0 * value * GIB / 1e9 / (HBM_PEAK_GBS * world), 2)},
-        "roofline": {"bound": "hbm", "kernel": ("observe_fq_fused_kernel<3>: per-token extrema + token-wise clipping + running mean + qparams + "
-                                                "fake-quant, ONE launch")
-                     if fused_on else "fq_tensor_vec_kernel (fake-quant forward of the three-launch path, 8 B per elem)",
-                     "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_source": traffic_source,
-                     "duration_source": (f"stream events around {reps_b2b * args.steps} back-to-back launches issued like the timed regions ({pick}), median of 3"
-                                         if fused_on else f"dispatch events of {len(k_ms)} launches"),
-                     "isolated_launch_us": round(iso_avg_ms * 1e3, 2),
-                     # the committed rocprofv3 --kernel-trace average of the same kernel (same sources, by hash): must agree with avg_launch_us
-                     "rocprof_avg_launch_us": rocprof_avg_us,
-                     # the same launch priced by the bytes that physically cross HBM (PMC): x is read once and y written
-                     # once because the tensor stays on chip between the reduction and the quantisation -- `frac` counts
-                     # the ALGORITHMIC 4 B per observed + 8 B per element of SURVEY 8d, `frac_physical` the 8 B that move
-                     "achieved_physical": round(traffic / (k_avg_ms * 1e-3) / 1e9, 1) if traffic else None,
-                     "frac_physical": round(traffic / (k_avg_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if traffic else None,
-                     # what a float4 copy kernel reaches on this part (MI355X_MICROARCH.md, chip-level parameters: 6.29 TB/s
-                     # measured = 79 % of the 8 TB/s specification): the physical rate as a fraction of THAT
-                     "copy_rate": COPY_RATE_GBS,
-                     "frac_physical_of_copy_rate": round(traffic / (k_avg_ms * 1e-3) / 1e9 / COPY_RATE_GBS, 4) if traffic else None,
-                     "avg_launch_us": round(k_avg_ms * 1e3, 2), "back_to_back_runs_us": [round(v * 1e3, 2) for v in b2b],
-                     "isolated_median_us": round(k_ms[len(k_ms) // 2] * 1e3, 2), "isolated_min_us": round(k_ms[0] * 1e3, 2),
-                     "isolated_max_us": round(k_ms[-1] * 1e3, 2),
-                     "launches_timed": reps_b2b * args.steps if fused_on else len(k_ms), "algorithmic_bytes_per_launch": probe_bytes},
+        "roofline": None,                      # --full
         "detail_file": os.path.basename(args.detail_file),
     }
+    if args.full:
+        out["config"].update({"eager_ms_per_step": round(eager_dt / args.steps * 1e3, 5),
+                              "host_enqueue_ms_per_step": round(eager_host / args.steps * 1e3, 5),
+                              "three_launch_path_ms_per_step": round(three_ms, 5)})
+        out["roofline"] = {"bound": "hbm", "kernel": ("observe_fq_fused_kernel<3>: per-token extrema + token-wise clipping + running mean + qparams + "
+                                                     "fake-quant, ONE launch")
+                          if fused_on else "fq_tensor_vec_kernel (fake-quant forward of the three-launch path, 8 B per elem)",
+                          "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                          "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_source": traffic_source,
+                          "duration_source": (f"stream events around {reps_b2b * args.steps} back-to-back launches issued like the timed regions ({pick}), median of 3"
+                                              if fused_on else f"dispatch events of {len(k_ms)} launches"),
+                          "isolated_launch_us": round(iso_avg_ms * 1e3, 2),
+                          # the committed rocprofv3 --kernel-trace average of the same kernel (same sources, by hash): must agree with avg_launch_us
+                          "rocprof_avg_launch_us": rocprof_avg_us,
+                          # the same launch priced by the bytes that physically cross HBM (PMC): x is read once and y written
+                          # once because the tensor stays on chip between the reduction and the quantisation -- `frac` counts
+                          # the ALGORITHMIC 4 B per observed + 8 B per element of SURVEY 8d, `frac_physical` the 8 B that move
+                          "achieved_physical": round(traffic / (k_avg_ms * 1e-3) / 1e9, 1) if traffic else None,
+                          "frac_physical": round(traffic / (k_avg_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if traffic else None,
+                          # what a float4 copy kernel reaches on this part (MI355X_MICROARCH.md, chip-level parameters: 6.29 TB/s
+                          # measured = 79 % of the 8 TB/s specification): the physical rate as a fraction of THAT
+                          "copy_rate": COPY_RATE_GBS,
+                          "frac_physical_of_copy_rate": round(traffic / (k_avg_ms * 1e-3) / 1e9 / COPY_RATE_GBS, 4) if traffic else None,
+                          "avg_launch_us": round(k_avg_ms * 1e3, 2), "back_to_back_runs_us": [round(v * 1e3, 2) for v in b2b],
+                          "isolated_median_us": round(k_ms[len(k_ms) // 2] * 1e3, 2), "isolated_min_us": round(k_ms[0] * 1e3, 2),
+                          "isolated_max_us": round(k_ms[-1] * 1e3, 2),
+                          "launches_timed": reps_b2b * args.steps if fused_on else len(k_ms), "algorithmic_bytes_per_launch": probe_bytes}
 
     def emit(final=False):
         """rank 0: the detail file (rewritten as sections arrive: a later crash keeps what was measured) and, at the end, the
@@ -539,14 +591,14 @@ def main():
             print(text, flush=True)
 
     emit()
-    if rank == 0 and not args.no_kernel_table:
+    if args.full and rank == 0 and not args.no_kernel_table:
         from benchlib.kernels import kernel_table
         try:          # a failure in the per-kernel table must not cost the headline line
             out["kernels"] = kernel_table(dev, xs, lengths)
         except Exception as e:
             out["kernels"] = {"error": f"{type(e).__name__}: {e}"[:300]}
         emit()
-    if not args.no_calib:
+    if args.full and not args.no_calib:
         from benchlib.calibration_flows import calibration_plain, calibration_wall_clock, calibration_extra, quantized_forward_times
         wanted = {int(c) for c in args.calib_configs.split(",") if c.strip()}
         if 0 in wanted:
@@ -587,7 +639,7 @@ def main():
                 out["quantized_forward"] = quantized_forward_times(dev)
             except Exception as e:
                 out["quantized_forward"] = {"error": f"{type(e).__name__}: {e}"[:300]}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         from benchlib.cpu import cpu_baseline
         try:
             out["cpu_baseline"] = cpu_baseline(1234, args.cpu_budget)

@@ -60,10 +60,12 @@ def compact_line(full):
     if "workload" in cfg:
         cfg["workload"] = _clip(cfg["workload"], 200)
     line["config"] = cfg
-    roof = _pick(full.get("roofline") or {}, _ROOFLINE_KEEP)
-    for k in ("kernel", "duration_source"):
-        if k in roof:
-            roof[k] = _clip(roof[k], 120)
+    roof = full.get("roofline")               # None: a plain run (bench.py --full measures it)
+    if isinstance(roof, dict):
+        roof = _pick(roof, _ROOFLINE_KEEP)
+        for k in ("kernel", "duration_source"):
+            if k in roof:
+                roof[k] = _clip(roof[k], 120)
     line["roofline"] = roof
     cpu = full.get("cpu_baseline")
     if isinstance(cpu, dict):
@@ -97,15 +99,16 @@ def dumps_line(full):
 
 def check_line(text):
     """What the driver needs of the line: one JSON object, under the cap, the contract's keys, roofline and cpu_baseline
-    shaped as the contract says.  Raises AssertionError naming the first thing that is wrong."""
+    shaped as the contract says (both null in a plain run, without --full).  Raises AssertionError naming the first thing that is wrong."""
     assert "\n" not in text, "the line must be one line"
     assert len(text) <= MAX_LINE_BYTES, f"line is {len(text)} bytes (cap {MAX_LINE_BYTES})"
     obj = json.loads(text)
     for k in REQUIRED_KEYS:
         assert k in obj, f"missing key {k!r}"
     assert isinstance(obj["config"], dict) and "workload" in obj["config"], "config.workload names the workload"
-    for k in ROOFLINE_KEYS:
-        assert k in obj["roofline"], f"roofline lacks {k!r}"
+    if obj["roofline"] is not None:
+        for k in ROOFLINE_KEYS:
+            assert k in obj["roofline"], f"roofline lacks {k!r}"
     if obj["cpu_baseline"] is not None and "error" not in obj["cpu_baseline"]:
         for k in CPU_KEYS:
             assert k in obj["cpu_baseline"], f"cpu_baseline lacks {k!r}"

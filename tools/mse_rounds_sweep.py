@@ -19,7 +19,7 @@ knobs = [a for a in sys.argv[1:] if "=" in a]
 for kv in knobs:
     k, v = kv.split("=")
     ops.set_tuning(k, int(v))
-sys.argv = ["bench.py", "--steps", "3", "--warmup", "1", "--settle", "0", "--preroll", "0.05", "--regions", "1", "--kernel-launches", "10",
+sys.argv = ["bench.py", "--full", "--steps", "3", "--warmup", "1", "--settle", "0", "--preroll", "0.05", "--regions", "1", "--kernel-launches", "10",
             "--no-cpu-baseline", "--no-kernel-table", "--calib-configs", "3", "--detail-file", "/tmp/mse_sweep_detail.json"]
 buf = io.StringIO()
 with redirect_stdout(buf):

@@ -62,7 +62,7 @@ def main(out, tag):
                   "pre-roll), the run of 1000 = the launches that carry dispatch events (`roofline.isolated_launch_us`).  `roofline.avg_launch_us` "
                   "of the bench line is the back-to-back figure:\n\n" + tail)
     open(os.path.join(out, f"{tag}_bench_kernel_stats.md"), "w").write(
-        f"# {tag}: rocprofv3 --kernel-trace --stats -- python bench.py --steps 50 --warmup 10 --settle 0 --no-cpu-baseline --no-calib --no-kernel-table\n\n" + stats + phases)
+        f"# {tag}: rocprofv3 --kernel-trace --stats -- python bench.py --full --steps 50 --warmup 10 --settle 0 --no-cpu-baseline --no-calib --no-kernel-table\n\n" + stats + phases)
     fetch = pmc_rows(find_db(os.path.join(out, "pmc_fetch")), "FETCH_SIZE")
     write = pmc_rows(find_db(os.path.join(out, "pmc_write")), "WRITE_SIZE")
     lines = [f"# {tag} PMC counters (rocprofv3 --pmc, separate passes), bench.py [256,128,768]", "",
@@ -87,7 +87,7 @@ def main(out, tag):
               "x read once, y written once); fake-quant "
               f"{8 * N_ELEM} (8 B x {N_ELEM}); token_minmax 4 B x valid elements; token_select 8 B x token slots."]
     open(os.path.join(out, f"{tag}_bench_pmc.md"), "w").write("\n".join(lines) + "\n")
-    traffic["_note"] = ("rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE (separate passes) on `python bench.py --steps 50 "
+    traffic["_note"] = ("rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE (separate passes) on `python bench.py --full --steps 50 "
                         "--warmup 10 --no-cpu-baseline --no-calib`; KB per dispatch; reads doubled per MI355X_MICROARCH.md")
     traffic["_kernel_sources_sha256"] = kernel_sources_sha256()
     traffic["_profile_tag"] = tag
