@@ -34,8 +34,9 @@ typedef void* osq_stream;
 
 /* Bumped whenever a signature or the workspace layout changes; the Python host refuses a library whose
  * osq_abi_version() differs from the number it was written against (a stale libosq_hip.so must be rebuilt).
- * 5: the LSQ / LSQ+ backward takes its summation order as an argument (`lanes` / `sum_lanes`). */
-#define OSQ_ABI_VERSION 7
+ * 5: the LSQ / LSQ+ backward takes its summation order as an argument (`lanes` / `sum_lanes`).
+ * 8: osq_attention_softmax_fake_quant, OSQ_TIME_ATTENTION_SOFTMAX. */
+#define OSQ_ABI_VERSION 8
 
 typedef enum osq_status {
     OSQ_OK = 0,
@@ -118,7 +119,7 @@ size_t      osq_workspace_bytes(void);
  *                        (0 = the default, ~2 s; n > 0 = n - 1 polls, so 1 makes every wait give up at once: tests force the
  *                        time-out path).
  * Performance A/B knobs -- "fq_unroll", "fq_max_blocks", "fq_nt", "fq_headsplit", "stream_wt", "bwd_blocks", "bwd_order_chunks",
- * "ln_blocks", "obs_blocks", "tok_nt", "fused_gate", "fused_grid", "select_hint", "mse_round_groups" (8), "mse_lean" (1),
+ * "ln_blocks", "attn_blocks", "obs_blocks", "tok_nt", "fused_gate", "fused_grid", "select_hint", "mse_round_groups" (8), "mse_lean" (1),
  * "mse_grid_all" -- are compile-time constants (the measured winners) in the release library, which answers
  * OSQ_ERR_INVALID_ARGUMENT for them; only the -DOSQ_TUNABLE development build (`make dbg`: libosq_hip_dbg.so) keeps them as
  * variables.  osq_build_flags(): bit 0 = that build, bit 1 = phase timestamps compiled in (-DOSQ_FINAL_TIMING). */
@@ -145,7 +146,8 @@ typedef enum osq_timed_kernel {
     OSQ_TIME_OBSERVE_CHANNELS = 10,   /* osq_observe_channels                                                */
     OSQ_TIME_TOKEN_MINMAX_MULTI = 11, /* osq_token_minmax_multi                                              */
     OSQ_TIME_MSEFAST_ROWS = 12,       /* osq_msefast_rows (the per-row search launch)                        */
-    OSQ_TIME_OBSERVE_TOKENS = 13      /* one-launch form of osq_observe_tokens                               */
+    OSQ_TIME_OBSERVE_TOKENS = 13,     /* one-launch form of osq_observe_tokens                               */
+    OSQ_TIME_ATTENTION_SOFTMAX = 14   /* osq_attention_softmax_fake_quant                                    */
 } osq_timed_kernel;
 int osq_timing_events_create(void** start, void** stop);
 int osq_timing_events_destroy(void* start, void* stop);
@@ -623,6 +625,32 @@ int osq_residual_layernorm_fake_quant(const float* x, const float* hidden, const
                                       float* scale, void* zero_point, int zp_type,
                                       int mode, float grad_factor, int quant_min, int quant_max,
                                       osq_stream stream);
+
+/* ------------------------------------------------------------------ attention probabilities: mask + softmax + fake-quant */
+
+/* One pass for what the attention-probabilities site of the quantized models runs as three eager steps
+ * (model/quant_bert.py:169-185, model/quant_bart.py:232-256), for every row (b, h, t) of a [batch, heads, tokens, cols]
+ * scores tensor:
+ *     v = pre(scores) + mask        alpha != 1:   mask + scores * alpha    (torch.add(mask, scores, alpha=...): exact
+ *                                                                          only for a power-of-two alpha, which callers pass)
+ *                                   divisor != 1: scores / divisor + mask  (IEEE division)
+ *                                   both 1:       scores + mask
+ *                                   (mask == NULL: no addition; at most one of alpha / divisor may differ from 1)
+ *     p = softmax(v) over cols      max-subtracted, accurate expf, fp32 sum, p = e * (1 / sum) as torch's CPU kernel;
+ *                                   a row with a NaN, a +inf or only -inf entries is NaN
+ *     y = fake_quantize(p)          scale == NULL: y = p (observer passes, disabled or per-channel quantizers)
+ * scores / y contiguous fp32 (y may be scores).  The mask is fp32 with a contiguous last axis; row (b, h, t) starts at
+ * b * mask_stride_b + h * mask_stride_h + t * mask_stride_t elements (0 = broadcast): BERT's [B,1,1,S], BART's [B,1,T,S].
+ * mode / grad_factor / zp_type as in osq_fake_quant_per_tensor, including OSQ_PARAM_SANITIZE: for a given p, y is
+ * word-equal to osq_fake_quant_per_tensor(p).  cols % 4 == 0, cols <= 2048 with 16-byte aligned scores / y / mask rows
+ * run the register-resident kernel (8 B per element); any other shape a generic kernel with the same arithmetic.
+ * Inference only: autograd passes use the eager sequence. */
+int osq_attention_softmax_fake_quant(const float* scores, const float* mask, int64_t batch, int64_t heads, int64_t tokens,
+                                     int64_t cols, int64_t mask_stride_b, int64_t mask_stride_h, int64_t mask_stride_t,
+                                     float alpha, float divisor, float* y,
+                                     float* scale, void* zero_point, int zp_type,
+                                     int mode, float grad_factor, int quant_min, int quant_max,
+                                     osq_stream stream);
 
 #ifdef __cplusplus
 }

@@ -52,10 +52,17 @@ def set_fast(on=True):
     util_layernorm.FUSE_LAYERNORM = bool(on)
 
 
+def set_fast_softmax(on=True):
+    """The one-launch attention-probabilities site (util_layernorm.FUSE_SOFTMAX: mask + softmax + fake-quant; default
+    OFF -- see there for how it compares with the eager sequence).  OSQ_FAST_SOFTMAX=1 turns it on at load."""
+    from . import util_layernorm
+    util_layernorm.FUSE_SOFTMAX = bool(on)
+
+
 def reset_tier(_lib=None):
     """The package's default tier, as the environment states it (applied when the library is first loaded): MSEFast sums in
     the reference's one-thread order, the backward's sums order-free; OSQ_STRICT=1 / 0 force both; OSQ_FAST=0 / 1 the
-    one-launch LayerNorm site."""
+    one-launch LayerNorm site; OSQ_FAST_SOFTMAX=1 the one-launch attention-probabilities site (unset: off)."""
     import os
     width = int(os.environ.get("OSQ_STRICT_SIMD", "8"))
     strict = os.environ.get("OSQ_STRICT", "")
@@ -65,6 +72,7 @@ def reset_tier(_lib=None):
         set_strict(strict != "0", width, _lib=_lib)
     # unset: the default (one-launch LayerNorm site ON) -- a set_fast(False) of an earlier caller or test does not leak
     set_fast(os.environ.get("OSQ_FAST", "") != "0")
+    set_fast_softmax(os.environ.get("OSQ_FAST_SOFTMAX", "") not in ("", "0"))
 
 
 _apply_environment = reset_tier

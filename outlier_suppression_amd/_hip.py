@@ -22,10 +22,10 @@ PARAM_MODE_MASK, PARAM_SANITIZE, PARAM_NO_PERSISTENT = 3, 16, 32
 TIME_FAKE_QUANT, TIME_LSQ_BACKWARD, TIME_OBSERVE_FLAT, TIME_TOKEN_MINMAX, TIME_TOKEN_SELECT = 1, 2, 3, 4, 5
 TIME_LAYERNORM, TIME_FUSED_STEP = 6, 7
 TIME_FAKE_QUANT_STRIDED, TIME_FAKE_QUANT_CHANNEL, TIME_OBSERVE_CHANNELS, TIME_TOKEN_MINMAX_MULTI, TIME_MSEFAST_ROWS = 8, 9, 10, 11, 12
-TIME_OBSERVE_TOKENS = 13
+TIME_OBSERVE_TOKENS, TIME_ATTENTION_SOFTMAX = 13, 14
 UPDATE_NONE, UPDATE_RUNNING, UPDATE_AVERAGE = 0, 1, 2
 ERR_UNSUPPORTED = -3          # OSQ_ERR_UNSUPPORTED: nothing was launched, the caller takes its other path
-ABI_VERSION = 7               # OSQ_ABI_VERSION of include/osq_hip.h this file was written against
+ABI_VERSION = 8               # OSQ_ABI_VERSION of include/osq_hip.h this file was written against
 
 _P = ctypes.c_void_p
 _I = ctypes.c_int
@@ -129,6 +129,7 @@ SIGNATURES = {
     "osq_gamma_split_bias": (_I, [_P, _P, _P, _L, _P]),
     "osq_gamma_residual": (_I, [_P, _P, _P, _P, _L, _L, _P]),
     "osq_residual_layernorm_fake_quant": (_I, [_P, _P, _P, _P, _P, _D, _P, _L, _L, _P, _P, _I, _I, _F, _I, _I, _P]),
+    "osq_attention_softmax_fake_quant": (_I, [_P, _P, _L, _L, _L, _L, _L, _L, _L, _F, _F, _P, _P, _P, _I, _I, _F, _I, _I, _P]),
 }
 
 _lib = None

@@ -1043,6 +1043,7 @@ extern "C" int osq_set_tuning(const char* key, int value) {
     else if (osq::set_observer_tuning(key, value)) { }
     else if (osq::set_msefast_tuning(key, value)) { }
     else if (osq::set_layernorm_tuning(key, value)) { }
+    else if (osq::set_attention_tuning(key, value)) { }
     else if (osq::set_extra_tuning(key, value)) { }
     else {
 #ifdef OSQ_TUNABLE

@@ -26,20 +26,6 @@ constexpr int kLnWaves = kLnThreads / OSQ_WAVE;
 OSQ_AB_KNOB(int, g_ln_blocks, 1024);      // grid cap (osq_set_tuning("ln_blocks", n)); rows are grid-strided above it.  tools/bwd_ab.py on MI355X,
                                     // [256,128,768]: one row per wave (8192 workgroups) 58.2 us, 2048: 51.6, 1024: 51.2, 768: 51.1, 512: 60.0; [32,384,768]: 23.6 -> 21.1
 
-template <int CTRL>
-__device__ __forceinline__ float dpp_add_f32(float v) {
-    return v + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, true));
-}
-// symmetric xor / mirror patterns: after each step both partners hold the same partial sum, so every
-// lane ends with the same value bit for bit
-__device__ __forceinline__ float wave_sum_f32(float v) {
-    v = dpp_add_f32<kDppQuadXor1>(v);
-    v = dpp_add_f32<kDppQuadXor2>(v);
-    v = dpp_add_f32<kDppRowHalfMirror>(v);
-    v = dpp_add_f32<kDppRowMirror>(v);
-    return (lane_value(v, 0) + lane_value(v, 16)) + (lane_value(v, 32) + lane_value(v, 48));
-}
-
 struct LnArgs {
     const float4* x;
     const float4* hidden;     // nullable: no residual

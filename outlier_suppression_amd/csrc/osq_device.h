@@ -296,6 +296,20 @@ __device__ __forceinline__ double wave_sum(double v) {
     return (lane_value_f64(v, 0) + lane_value_f64(v, 16)) + (lane_value_f64(v, 32) + lane_value_f64(v, 48));
 }
 __device__ __forceinline__ bool wave_any(bool p) { return __ballot(p) != 0ull; }
+// fp32 add-reduction (LayerNorm moments, softmax denominators)
+template <int CTRL>
+__device__ __forceinline__ float dpp_add_f32(float v) {
+    return v + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, true));
+}
+// symmetric xor / mirror patterns: after each step both partners hold the same partial sum, so every
+// lane ends with the same value bit for bit
+__device__ __forceinline__ float wave_sum_f32(float v) {
+    v = dpp_add_f32<kDppQuadXor1>(v);
+    v = dpp_add_f32<kDppQuadXor2>(v);
+    v = dpp_add_f32<kDppRowHalfMirror>(v);
+    v = dpp_add_f32<kDppRowMirror>(v);
+    return (lane_value(v, 0) + lane_value(v, 16)) + (lane_value(v, 32) + lane_value(v, 48));
+}
 
 // ---- ATen's CPU summation order (test modes: osq_set_tuning("mse_sum_order" / "bwd_sum_order", 8)) ----------------
 // torch's CPU `sum` of a contiguous vector adds in the order of cascade_sum / vectorized_inner_sum

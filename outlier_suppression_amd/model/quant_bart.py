@@ -23,8 +23,8 @@ from torch import nn
 
 from .losses import classification_loss, lm_loss, span_loss, with_loss
 from ..quantization import QuantizedModule, Quantizer
-from ..util_layernorm import (GammaResidual, QuantizedLayerNorm, activation_fake_quant, merge_heads_fake_quant,
-                              qkv_heads_fake_quant, residual_layernorm, split_heads_fake_quant)
+from ..util_layernorm import (GammaResidual, QuantizedLayerNorm, activation_fake_quant, attention_probs_fake_quant,
+                              merge_heads_fake_quant, qkv_heads_fake_quant, residual_layernorm, split_heads_fake_quant)
 
 
 def shift_tokens_right(input_ids, pad_token_id, decoder_start_token_id):
@@ -123,13 +123,12 @@ class QuantizedBartAttention(QuantizedModule):
             v = split_heads_fake_quant(self.value_post_act_fake_quantize, xv, heads, observation_mask)
         proj = (bsz * self.num_heads, -1, self.head_dim)
         q, k, v = q.view(*proj), k.view(*proj), v.view(*proj)
-        src_len = k.shape[1]
         w = torch.bmm(q, k.transpose(1, 2))
-        if attention_mask is not None:
-            w = (w.view(bsz, self.num_heads, tgt_len, src_len) + attention_mask).view(bsz * self.num_heads, tgt_len, src_len)
-        w = nn.functional.softmax(w, dim=-1)
-        probs = nn.functional.dropout(w, p=self.dropout, training=self.training)
-        probs = self.attention_probs_post_act_fake_quantize(probs, observation_mask, 2)
+        # [B*h, T, S] scores + [B, 1, T, S] mask -> softmax -> dropout -> probs quantizer (quant_bart.py:232-256); one
+        # launch under FUSE_SOFTMAX
+        probs = attention_probs_fake_quant(self.attention_probs_post_act_fake_quantize, w, attention_mask,
+                                           dropout=(self.dropout, self.training), observation_mask=observation_mask,
+                                           seq_pos=2, heads=self.num_heads)
         out = merge_heads_fake_quant(self.context_post_act_fake_quantize,
                                      torch.bmm(probs, v).view(bsz, self.num_heads, tgt_len, self.head_dim), observation_mask)
         out = self.out_proj(out)

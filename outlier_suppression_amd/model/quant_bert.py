@@ -21,8 +21,8 @@ from torch import nn
 from .losses import classification_loss, span_loss, with_loss
 
 from ..quantization import QuantizedModule, Quantizer
-from ..util_layernorm import (GammaResidual, QuantizedLayerNorm, activation_fake_quant, merge_heads_fake_quant,
-                              qkv_heads_fake_quant, residual_layernorm)
+from ..util_layernorm import (GammaResidual, QuantizedLayerNorm, activation_fake_quant, attention_probs_fake_quant,
+                              merge_heads_fake_quant, qkv_heads_fake_quant, residual_layernorm)
 
 
 class QuantizedBertEmbeddings(QuantizedModule):
@@ -87,13 +87,12 @@ class QuantizedBertSelfAttention(QuantizedModule):
         if attention_mask is not None and root == 2.0 ** round(math.log2(root)) and not torch.is_grad_enabled():
             # head sizes 16 / 64 / 256: dividing by sqrt(d) is an exact multiplication by a power of two, so
             # mask + scores * (1/sqrt(d)) in ONE stock kernel has the bits of the reference's two (quant_bert.py:172-176)
-            scores = torch.add(attention_mask, scores, alpha=1.0 / root)
+            scale = dict(alpha=1.0 / root)
         else:
-            scores = scores / root
-            if attention_mask is not None:
-                scores = scores + attention_mask
-        probs = self.dropout(nn.functional.softmax(scores, dim=-1))
-        probs = self.attention_probs_post_act_fake_quantize(probs, observation_mask, 2)
+            scale = dict(divisor=root)
+        # mask + scaling -> softmax -> dropout -> probs quantizer (quant_bert.py:169-185); one launch under FUSE_SOFTMAX
+        probs = attention_probs_fake_quant(self.attention_probs_post_act_fake_quantize, scores, attention_mask,
+                                           dropout=self.dropout, observation_mask=observation_mask, seq_pos=2, **scale)
         if fused is None:
             v = self.value_permute_post_act_fake_quantize(v, observation_mask, 2)
         return merge_heads_fake_quant(self.context_view_post_act_fake_quantize if self.qoutput else None,

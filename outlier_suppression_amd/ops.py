@@ -1224,3 +1224,62 @@ def gelu_fake_quant_per_tensor(x, scale, zero_point, quant_min, quant_max, mode=
                                                   float(grad_factor), int(quant_min), int(quant_max),
                                                   _hip.raw_stream(x.device)), "gelu_fake_quant_per_tensor")
     return y
+
+
+# ---------------------------------------------------------------------------------------
+# pre-softmax scaling + mask -> softmax -> fake-quant in one pass (the attention-probabilities site)
+# ---------------------------------------------------------------------------------------
+
+def _as_4d(x):
+    return (1,) * (4 - x.dim()) + tuple(x.shape)
+
+
+def attention_softmax_fusable(scores, mask=None):
+    """Layout rules of osq_attention_softmax_fake_quant: scores a contiguous fp32 [.., T, S] tensor of at most four dims
+    on the device; mask None, or fp32 on the same device, broadcastable to scores with a contiguous last axis (any
+    strides, 0 included, on the others).  Every row width is taken (cols % 4 == 0 and cols <= 2048 the fast kernel)."""
+    if not (scores.is_cuda and scores.dtype == torch.float32 and 1 <= scores.dim() <= 4 and scores.is_contiguous()
+            and scores.numel()):
+        return False
+    if mask is None:
+        return True
+    if not (mask.device == scores.device and mask.dtype == torch.float32 and mask.dim() <= 4):
+        return False
+    try:
+        m = mask.expand(scores.shape)
+    except RuntimeError:
+        return False
+    return scores.shape[-1] == 1 or m.stride(-1) == 1
+
+
+def attention_softmax_fake_quant(scores, mask=None, *, alpha=None, divisor=None, quant=None):
+    """probs = fake_quant(softmax(pre(scores) + mask, dim=-1)) in ONE launch on the current stream.
+    pre: ``scores * alpha`` (with a mask: the bits of ``torch.add(mask, scores, alpha=alpha)`` -- exact for the power-of-two
+    alpha callers pass), ``scores / divisor`` (IEEE division), or ``scores`` (neither given).  mask: None or broadcastable
+    to scores (see attention_softmax_fusable).  quant: None (softmax only) or (scale, zero_point, quant_min, quant_max,
+    mode, grad_factor) as for residual_layernorm_fake_quant."""
+    lib = _hip.load()
+    _hip.require_device(scores, mask)
+    if alpha is not None and divisor is not None:
+        raise ValueError("attention_softmax_fake_quant: give alpha or divisor, not both")
+    if not attention_softmax_fusable(scores, mask):
+        raise ValueError("attention_softmax_fake_quant: scores must be a contiguous fp32 tensor of <= 4 dims and mask "
+                         "an fp32 tensor broadcastable to it with a contiguous last axis")
+    b, h, t, s = _as_4d(scores)
+    sb = sh = st = 0
+    if mask is not None:
+        strides = (0,) * (4 - scores.dim()) + tuple(mask.expand(scores.shape).stride())
+        sb, sh, st = strides[0], strides[1], strides[2]
+    y = torch.empty_like(scores)
+    if quant is None:
+        s_ptr, z_ptr, z_type, mode, gf, qmin, qmax = None, None, ZP_INT32, PARAM_FIXED, 1.0, 0, 1
+    else:
+        scale, zero_point, qmin, qmax, mode, gf = quant
+        _hip.require_device(scale, zero_point)
+        s_ptr, z_ptr, z_type = scale.data_ptr(), zero_point.data_ptr(), _zp_type(zero_point)
+    _hip.check(lib.osq_attention_softmax_fake_quant(scores.data_ptr(), _hip.ptr(mask), b, h, t, s, sb, sh, st,
+                                                    1.0 if alpha is None else float(alpha),
+                                                    1.0 if divisor is None else float(divisor), y.data_ptr(), s_ptr,
+                                                    z_ptr, z_type, int(mode), float(gf), int(qmin), int(qmax),
+                                                    _hip.raw_stream(scores.device)), "attention_softmax_fake_quant")
+    return y

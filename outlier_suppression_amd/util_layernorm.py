@@ -1,7 +1,7 @@
 """LayerNorm wrappers used by Gamma Migration, with the reference's class names.
 
 Reference: quant_transformer/model/util_layernorm.py.  Under autograd the normalisation stays stock
-PyTorch-ROCm followed by the HIP quantizer (the eager sequence of the reference).  Three fusions exist for forwards without
+PyTorch-ROCm followed by the HIP quantizer (the eager sequence of the reference).  Four fusions exist for forwards without
 autograd (every calibration / evaluation forward):
 
 
@@ -18,6 +18,16 @@ autograd (every calibration / evaluation forward):
     136 (2e-7 relative; BASELINE.json's bar is 1e-5), and 0 / 0 / 0 integer entries of 3.1 M different from the
     reference's integer tensor against 0 / 1 / 0.  ``outlier_suppression_amd.set_fast(False)`` / ``OSQ_FAST=0`` /
     ``util_layernorm.FUSE_LAYERNORM = False`` keep the eager sequence.
+  * ``FUSE_SOFTMAX`` (default OFF): the attention-probabilities site -- pre-softmax scaling + additive mask, softmax,
+    fake-quant (quant_bert.py:169-185, quant_bart.py:232-256) -- as ONE launch (``ops.attention_softmax_fake_quant``,
+    csrc/attention.hip: 8 B per element instead of about 28 on the largest activation of the block).  Its exp is ocml's
+    expf, not the Sleef routine of the reference's CPU softmax: probabilities agree with the reference to a tolerance,
+    not bit for bit (tests/golden/attention_site.npz, tests/test_gpu_attention_site.py).  In the plain quantising state
+    the whole site is one launch; with the observer on, the quantizer disabled or per-channel, one launch computes the
+    probabilities and the quantizer then runs its own path.  Autograd passes and active dropout keep the eager sequence.
+    ``outlier_suppression_amd.set_fast_softmax(True)`` / ``OSQ_FAST_SOFTMAX=1`` turn it on.  Measured on MI355X
+    (profiles/attention_site_ab.txt): [32,12,384,384] 116 us against 220 us eager with fake-quant, 81 against 153 us
+    softmax only; [32,12,128,128] 26 against 32 us, and slower than eager softmax only (23 against 22 us).
 """
 import torch
 import torch.nn.functional as F
@@ -30,6 +40,7 @@ from .quantization.fake_quant import _LearnableFakeQuantize
 FUSE_LAYERNORM = True
 FUSE_ACTIVATION = True
 FUSE_QKV = True          # the query / key / value head-split sites of a self-attention block as one launch (bit-identical)
+FUSE_SOFTMAX = False     # the attention-probabilities site as one launch (tolerance-equal; set_fast_softmax / OSQ_FAST_SOFTMAX=1)
 
 
 def _fused_site(mod, x, hidden, gamma, weight, bias, eps, observation_mask):
@@ -232,3 +243,62 @@ def qkv_heads_fake_quant(quantizers, projections, heads):
         params.append((q.scale.data, q.zero_point.data, q.quant_min, q.quant_max, mode,
                        q._grad_factor(x) if q.param_mode != ops.PARAM_FIXED else 1.0))
     return ops.fake_quant_headsplit_multi(list(projections), params, heads)
+
+
+def _dropout_active(dropout):
+    if dropout is None:
+        return False
+    if isinstance(dropout, nn.Module):
+        return dropout.training and dropout.p > 0
+    p, training = dropout
+    return training and p > 0
+
+
+def _apply_dropout(dropout, x):
+    if dropout is None:
+        return x
+    if isinstance(dropout, nn.Module):
+        return dropout(x)
+    p, training = dropout
+    return F.dropout(x, p=p, training=training)
+
+
+def attention_probs_fake_quant(quantizer, scores, mask, alpha=None, divisor=None, dropout=None, observation_mask=None,
+                               seq_pos=2, heads=None):
+    """The attention-probabilities site: ``quantizer(dropout(softmax(pre(scores) + mask, -1)), observation_mask, seq_pos)``.
+
+    pre: ``alpha`` -- ``torch.add(mask, scores, alpha=alpha)``, one stock op (BERT, power-of-two 1/sqrt(d));
+    ``divisor`` -- ``scores / divisor`` then ``+ mask`` (BERT, other head sizes or no mask); neither -- ``scores + mask``
+    (BART, q scaled beforehand).  ``heads``: scores is BART's [B*h, T, S] view and mask broadcasts against its
+    [B, h, T, S] form (quant_bart.py:128-129); the result keeps the layout scores came in.  ``dropout``: an nn.Dropout, or
+    (p, training) for the functional form.
+
+    With FUSE_SOFTMAX on, autograd off, dropout inactive and a fusable layout, ONE launch computes the probabilities --
+    and, when the quantizer is in its plain quantising state, their fake-quant as well (the LSQ / LSQ+ parameter repair
+    riding along as in the other one-launch sites); otherwise the quantizer then runs its own path on them."""
+    scores4 = scores.view(scores.shape[0] // heads, heads, *scores.shape[1:]) if heads is not None else scores
+    if FUSE_SOFTMAX and not torch.is_grad_enabled() and not _dropout_active(dropout) and \
+            ops.attention_softmax_fusable(scores4, mask):
+        q = quantizer
+        quant = None
+        if _plain_quantizing(q, scores):
+            mode = q.param_mode
+            if isinstance(q, _LearnableFakeQuantize):
+                mode |= ops.PARAM_SANITIZE
+                q._touch_qparams()
+            quant = (q.scale.data, q.zero_point.data, q.quant_min, q.quant_max, mode,
+                     q._grad_factor(scores) if q.param_mode != ops.PARAM_FIXED else 1.0)
+        probs = ops.attention_softmax_fake_quant(scores4, mask, alpha=alpha, divisor=divisor, quant=quant).view(scores.shape)
+        if q is not None and quant is None:
+            probs = q(probs, observation_mask, seq_pos)
+        return probs
+    if alpha is not None:
+        v = torch.add(mask, scores, alpha=alpha) if mask is not None else scores * alpha
+    else:
+        v = scores if divisor is None else scores / divisor
+        if mask is not None:
+            v = (v.view(scores4.shape) + mask).view(scores.shape)
+    probs = _apply_dropout(dropout, F.softmax(v, dim=-1))
+    if quantizer is not None:
+        probs = quantizer(probs, observation_mask, seq_pos)
+    return probs
