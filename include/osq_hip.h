@@ -36,7 +36,7 @@ typedef void* osq_stream;
  * osq_abi_version() differs from the number it was written against (a stale libosq_hip.so must be rebuilt).
  * 5: the LSQ / LSQ+ backward takes its summation order as an argument (`lanes` / `sum_lanes`).
  * 8: osq_attention_softmax_fake_quant, OSQ_TIME_ATTENTION_SOFTMAX. */
-#define OSQ_ABI_VERSION 8
+#define OSQ_ABI_VERSION 9
 
 typedef enum osq_status {
     OSQ_OK = 0,
@@ -651,6 +651,48 @@ int osq_attention_softmax_fake_quant(const float* scores, const float* mask, int
                                      float* scale, void* zero_point, int zp_type,
                                      int mode, float grad_factor, int quant_min, int quant_max,
                                      osq_stream stream);
+
+/* ------------------------------------------------------------------ bf16 / fp16 inputs (lowp.hip) */
+
+/* Element type of the `const void*` / `void*` data of the entry points below; any other value is rejected (-1). */
+typedef enum osq_dtype { OSQ_DTYPE_BF16 = 1, OSQ_DTYPE_F16 = 2 } osq_dtype;
+
+/* FixedFakeQuantize per-tensor (util_quant.py:11-15 called with Python numbers or 0-dim tensors) in the input dtype:
+ * every op of the chain is rounded to x's dtype, as torch's CPU kernels do --
+ *     a = rd(x/s); r = rint(a); b = rd(rd(r - a) + a); c = clamp(rd(b + zp), qmin, qmax); y = rd(rd(c - zp) * s)
+ * (rd = round the fp32 result to the dtype, RNE).  scale: 1 fp32 on the device; zero_point: 1 int32 or fp32 (zp_type).
+ * x / y: n contiguous elements of `dtype` (16-byte accesses when both are 16-byte aligned, element accesses otherwise). */
+int osq_fake_quant_chain_lowp(int dtype, const void* x, void* y, int64_t n, const float* scale, const void* zero_point,
+                              int zp_type, int quant_min, int quant_max, osq_stream stream);
+
+/* The autograd backward of the chain above for x: x_int = rd(b + zp) recomputed,
+ *     dx = rd(where(qmin <= x_int <= qmax, rd(g * s), +0.0) / s)            (x, grad_out, grad_x: n elements of dtype) */
+int osq_fake_quant_chain_backward_lowp(int dtype, const void* x, const void* grad_out, void* grad_x, int64_t n,
+                                       const float* scale, const void* zero_point, int zp_type, int quant_min, int quant_max,
+                                       osq_stream stream);
+
+/* Per-tensor fake-quant of a bf16 / fp16 x with fp32 [1] parameters (Fixed / LSQ / LSQ+, util_quant.py with >= 1-dim
+ * tensors): torch promotes to fp32, so y is fp32 and word-equal to osq_fake_quant_per_tensor on x widened -- the same
+ * arguments, OSQ_PARAM_SANITIZE included.  One launch, 2 B read + 4 B written per element. */
+int osq_fake_quant_per_tensor_widen(int dtype, const void* x, float* y, int64_t n, float* scale, void* zero_point, int zp_type,
+                                    int mode, float grad_factor, int quant_min, int quant_max, osq_stream stream);
+
+/* Per-channel form of the above: x contiguous [outer, channels, inner] of dtype, y fp32, word-equal to
+ * osq_fake_quant_per_channel on x widened. */
+int osq_fake_quant_per_channel_widen(int dtype, const void* x, float* y, int64_t outer, int64_t channels, int64_t inner,
+                                     const float* scale, const void* zero_point, int zp_type, int mode, float grad_factor,
+                                     int quant_min, int quant_max, osq_stream stream);
+
+/* osq_observe_flat / osq_observe_channels / osq_token_minmax reading dtype elements: the statistics (fp32), scale and
+ * zero point are those of the fp32 entry point on x widened (the reference widens first: x_orig.to(min_val.dtype), observer.py:134). */
+int osq_observe_flat_lowp(int dtype, const void* x, int64_t n, int update_rule, int64_t cnt, float* min_val, float* max_val,
+                          float* cur_minmax, int quant_min, int quant_max, int symmetric, float* scale_out,
+                          void* zero_point_out, int zp_type, void* workspace, osq_stream stream);
+int osq_observe_channels_lowp(int dtype, const void* x, int64_t outer, int64_t channels, int64_t inner, int update_rule,
+                              int64_t cnt, float* min_val, float* max_val, int quant_min, int quant_max, int symmetric,
+                              float* scale_out, void* zero_point_out, int zp_type, osq_stream stream);
+int osq_token_minmax_lowp(int dtype, const void* x, const osq_token_view* view, const int64_t* lengths, float* token_min,
+                          float* token_max, osq_stream stream);
 
 #ifdef __cplusplus
 }

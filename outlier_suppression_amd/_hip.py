@@ -24,8 +24,9 @@ TIME_LAYERNORM, TIME_FUSED_STEP = 6, 7
 TIME_FAKE_QUANT_STRIDED, TIME_FAKE_QUANT_CHANNEL, TIME_OBSERVE_CHANNELS, TIME_TOKEN_MINMAX_MULTI, TIME_MSEFAST_ROWS = 8, 9, 10, 11, 12
 TIME_OBSERVE_TOKENS, TIME_ATTENTION_SOFTMAX = 13, 14
 UPDATE_NONE, UPDATE_RUNNING, UPDATE_AVERAGE = 0, 1, 2
+DTYPE_BF16, DTYPE_F16 = 1, 2   # osq_dtype: element type of the bf16 / fp16 entry points (lowp.hip)
 ERR_UNSUPPORTED = -3          # OSQ_ERR_UNSUPPORTED: nothing was launched, the caller takes its other path
-ABI_VERSION = 8               # OSQ_ABI_VERSION of include/osq_hip.h this file was written against
+ABI_VERSION = 9               # OSQ_ABI_VERSION of include/osq_hip.h this file was written against
 
 _P = ctypes.c_void_p
 _I = ctypes.c_int
@@ -130,6 +131,13 @@ SIGNATURES = {
     "osq_gamma_residual": (_I, [_P, _P, _P, _P, _L, _L, _P]),
     "osq_residual_layernorm_fake_quant": (_I, [_P, _P, _P, _P, _P, _D, _P, _L, _L, _P, _P, _I, _I, _F, _I, _I, _P]),
     "osq_attention_softmax_fake_quant": (_I, [_P, _P, _L, _L, _L, _L, _L, _L, _L, _F, _F, _P, _P, _P, _I, _I, _F, _I, _I, _P]),
+    "osq_fake_quant_chain_lowp": (_I, [_I, _P, _P, _L, _P, _P, _I, _I, _I, _P]),
+    "osq_fake_quant_chain_backward_lowp": (_I, [_I, _P, _P, _P, _L, _P, _P, _I, _I, _I, _P]),
+    "osq_fake_quant_per_tensor_widen": (_I, [_I, _P, _P, _L, _P, _P, _I, _I, _F, _I, _I, _P]),
+    "osq_fake_quant_per_channel_widen": (_I, [_I, _P, _P, _L, _L, _L, _P, _P, _I, _I, _F, _I, _I, _P]),
+    "osq_observe_flat_lowp": (_I, [_I, _P, _L, _I, _L, _P, _P, _P, _I, _I, _I, _P, _P, _I, _P, _P]),
+    "osq_observe_channels_lowp": (_I, [_I, _P, _L, _L, _L, _I, _L, _P, _P, _I, _I, _I, _P, _P, _I, _P]),
+    "osq_token_minmax_lowp": (_I, [_I, _P, ctypes.POINTER(TokenView), _P, _P, _P, _P]),
 }
 
 _lib = None

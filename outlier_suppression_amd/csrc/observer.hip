@@ -19,79 +19,6 @@ constexpr int kThreads = 256;
 constexpr int kWavesPerBlock = kThreads / OSQ_WAVE;
 constexpr int kFinalThreads = 1024;
 
-struct MinMax {
-    float mn, mx;
-    bool bad;   // a NaN was seen: torch's aminmax / max(dim) propagate it
-    __device__ __forceinline__ void init() { mn = __builtin_inff(); mx = -__builtin_inff(); bad = false; }
-    __device__ __forceinline__ void add(float v) {
-        mn = fminf(mn, v);
-        mx = fmaxf(mx, v);
-        bad |= (v != v);
-    }
-    __device__ __forceinline__ void add4(const float4& v) { add(v.x); add(v.y); add(v.z); add(v.w); }
-    __device__ __forceinline__ void wave_reduce() {
-        mn = wave_min(mn);
-        mx = wave_max(mx);
-        bad = wave_any(bad);
-    }
-    __device__ __forceinline__ void poison() {
-        if (bad) { mn = __builtin_nanf(""); mx = __builtin_nanf(""); }
-    }
-};
-
-// block-wide combine; valid in thread 0
-__device__ __forceinline__ MinMax block_reduce(MinMax v) {
-    __shared__ float s_mn[kFinalThreads / OSQ_WAVE], s_mx[kFinalThreads / OSQ_WAVE];
-    __shared__ int s_bad[kFinalThreads / OSQ_WAVE];
-    v.wave_reduce();
-    const int lane = threadIdx.x & (OSQ_WAVE - 1), w = threadIdx.x / OSQ_WAVE;
-    const int nw = (blockDim.x + OSQ_WAVE - 1) / OSQ_WAVE;
-    __syncthreads();
-    if (lane == 0) { s_mn[w] = v.mn; s_mx[w] = v.mx; s_bad[w] = v.bad; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int k = 1; k < nw; ++k) {
-            v.mn = fminf(v.mn, s_mn[k]);
-            v.mx = fmaxf(v.mx, s_mx[k]);
-            v.bad |= (s_bad[k] != 0);
-        }
-    }
-    return v;
-}
-
-struct Finish {   // what happens once a batch's (min, max) is known
-    int rule;
-    int64_t cnt;
-    float* min_val;
-    float* max_val;
-    float* cur;
-    int quant_min, quant_max, symmetric;
-    float* scale_out;
-    void* zp_out;
-    int zp_type;
-};
-
-// have_state: the caller already holds min_val[idx] / max_val[idx] in (st_min, st_max)
-__device__ __forceinline__ void finish_entry(const Finish& f, int64_t idx, float cur_min, float cur_max,
-                                             bool have_state = false, float st_min = 0.f, float st_max = 0.f) {
-    if (f.cur) { f.cur[2 * idx] = cur_min; f.cur[2 * idx + 1] = cur_max; }
-    float mn = cur_min, mx = cur_max;
-    if (f.rule != OSQ_UPDATE_NONE && f.min_val && f.max_val) {
-        if (!have_state) { st_min = f.min_val[idx]; st_max = f.max_val[idx]; }
-        mn = st_min;
-        mx = st_max;
-        apply_update(f.rule, f.cnt, cur_min, cur_max, &mn, &mx);
-        f.min_val[idx] = mn;
-        f.max_val[idx] = mx;
-    }
-    if (f.scale_out) {
-        float s, z;
-        qparams_from_range(mn, mx, f.quant_min, f.quant_max, f.symmetric, &s, &z);
-        f.scale_out[idx] = s;
-        if (f.zp_out) store_zp(f.zp_out, f.zp_type, idx, z);
-    }
-}
-
 // ---------------------------------------------------------------- calculate_qparams / update
 
 __global__ void qparams_kernel(const float* __restrict__ mn, const float* __restrict__ mx, int64_t n, int quant_min,

@@ -27,6 +27,21 @@ def _check_f32(*tensors):
             raise TypeError(f"outlier_suppression_amd kernels compute in float32, got {t.dtype}")
 
 
+# bf16 / fp16 inputs (lowp.hip): their own entry points below; the fp32 functions keep rejecting them
+LOWP_DTYPES = {torch.bfloat16: _hip.DTYPE_BF16, torch.float16: _hip.DTYPE_F16}
+
+
+def is_lowp(x):
+    return x.dtype in LOWP_DTYPES
+
+
+def _lowp_code(x):
+    code = LOWP_DTYPES.get(x.dtype)
+    if code is None:
+        raise TypeError(f"outlier_suppression_amd: expected a bfloat16 or float16 tensor, got {x.dtype}")
+    return code
+
+
 def is_dense(x):
     """True if x's elements occupy one gap-free block of memory (any dim order)."""
     if x.is_contiguous():
@@ -200,21 +215,117 @@ def lsq_sanitize_(scale, zero_point, eps, quant_min, quant_max):
                                     int(quant_max), _hip.stream_ptr(scale.device)), "lsq_sanitize")
 
 
+# ---------------------------------------------------------------------------------------
+# bf16 / fp16 fake-quant (README "Defaults": which call keeps x.dtype and which promotes to fp32)
+# ---------------------------------------------------------------------------------------
+
+def _lowp_flat(x):
+    """x itself when its elements form one gap-free block (any dim order), else a contiguous copy: one extra pass."""
+    return x if is_dense(x) else x.contiguous()
+
+
+def fake_quant_chain_lowp(x, scale, zero_point, quant_min, quant_max):
+    """FixedFakeQuantize per-tensor in x's dtype (bf16 / fp16): every op of util_quant.py:12-14 rounded to x.dtype, as the
+    reference computes it with Python-number parameters.  scale / zero_point: 1-element device tensors.  ONE launch."""
+    lib = _hip.load()
+    _hip.require_device(x, scale, zero_point)
+    _check_f32(scale)
+    x = _lowp_flat(x)
+    y = torch.empty_like(x)
+    _hip.check(lib.osq_fake_quant_chain_lowp(_lowp_code(x), _hip.ptr(x), _hip.ptr(y), x.numel(), _hip.ptr(scale),
+                                             _hip.ptr(zero_point), _zp_type(zero_point), int(quant_min), int(quant_max),
+                                             _hip.stream_ptr(x.device)), "fake_quant_chain_lowp")
+    return y
+
+
+def fake_quant_chain_backward_lowp(x, grad_out, scale, zero_point, quant_min, quant_max):
+    """d/dx of fake_quant_chain_lowp for an upstream gradient in x.dtype.  ONE launch."""
+    lib = _hip.load()
+    _hip.require_device(x, grad_out, scale, zero_point)
+    _check_f32(scale)
+    x = _lowp_flat(x)
+    g = _like_layout(grad_out, x) if grad_out.dtype == x.dtype else _like_layout(grad_out.to(x.dtype), x)
+    dx = torch.empty_like(x)
+    _hip.check(lib.osq_fake_quant_chain_backward_lowp(_lowp_code(x), _hip.ptr(x), _hip.ptr(g), _hip.ptr(dx), x.numel(),
+                                                      _hip.ptr(scale), _hip.ptr(zero_point), _zp_type(zero_point),
+                                                      int(quant_min), int(quant_max), _hip.stream_ptr(x.device)),
+               "fake_quant_chain_backward_lowp")
+    return dx
+
+
+def fake_quant_per_tensor_widen(x, scale, zero_point, quant_min, quant_max, mode=PARAM_FIXED, grad_factor=1.0):
+    """Per-tensor fake-quant of a bf16 / fp16 x with fp32 [1] parameters: fp32 result, word-equal to
+    fake_quant_per_tensor(x.float(), ...) (PARAM_SANITIZE included).  ONE launch, 2 B in + 4 B out per element."""
+    lib = _hip.load()
+    _hip.require_device(x, scale, zero_point)
+    _check_f32(scale)
+    x = _lowp_flat(x)
+    y = torch.empty_like(x, dtype=torch.float32)
+    _hip.check(lib.osq_fake_quant_per_tensor_widen(_lowp_code(x), _hip.ptr(x), _hip.ptr(y), x.numel(), _hip.ptr(scale),
+                                                   _hip.ptr(zero_point), _zp_type(zero_point), mode, float(grad_factor),
+                                                   int(quant_min), int(quant_max), _hip.stream_ptr(x.device)),
+               "fake_quant_per_tensor_widen")
+    return y
+
+
+def fake_quant_per_channel_widen(x, scale, zero_point, ch_axis, quant_min, quant_max, mode=PARAM_FIXED, grad_factor=1.0):
+    """Per-channel form of fake_quant_per_tensor_widen (fp32 result equal to fake_quant_per_channel(x.float(), ...))."""
+    lib = _hip.load()
+    _hip.require_device(x, scale, zero_point)
+    _check_f32(scale)
+    x = x.contiguous()
+    outer, channels, inner = _channel_split(x, ch_axis)
+    if scale.numel() != channels or zero_point.numel() != channels:
+        raise ValueError(f"per-channel fake-quant: {channels} channels but scale/zero_point have "
+                         f"{scale.numel()}/{zero_point.numel()} entries")
+    y = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+    _hip.check(lib.osq_fake_quant_per_channel_widen(_lowp_code(x), _hip.ptr(x), _hip.ptr(y), outer, channels, inner,
+                                                    _hip.ptr(scale), _hip.ptr(zero_point), _zp_type(zero_point),
+                                                    mode & PARAM_MODE_MASK, float(grad_factor), int(quant_min),
+                                                    int(quant_max), _hip.stream_ptr(x.device)), "fake_quant_per_channel_widen")
+    return y
+
+
+def _lowp_chain(x, ch_axis, mode, scalar_params):
+    """True when a bf16 / fp16 call keeps x.dtype: Fixed per-tensor with Python-number / 0-dim parameters."""
+    return scalar_params and ch_axis == -1 and (mode & PARAM_MODE_MASK) == PARAM_FIXED
+
+
+def _forward(x, scale, zero_point, ch_axis, quant_min, quant_max, mode, grad_factor, scalar_params):
+    if is_lowp(x):
+        if _lowp_chain(x, ch_axis, mode, scalar_params):
+            return fake_quant_chain_lowp(x, scale, zero_point, quant_min, quant_max)
+        if ch_axis == -1:
+            return fake_quant_per_tensor_widen(x, scale, zero_point, quant_min, quant_max, mode, grad_factor)
+        return fake_quant_per_channel_widen(x, scale, zero_point, ch_axis, quant_min, quant_max, mode, grad_factor)
+    if ch_axis == -1:
+        return fake_quant_per_tensor(x, scale, zero_point, quant_min, quant_max, mode, grad_factor)
+    return fake_quant_per_channel(x, scale, zero_point, ch_axis, quant_min, quant_max, mode, grad_factor)
+
+
 class _FakeQuantFn(torch.autograd.Function):
-    """Differentiable fake-quant: forward = one HIP launch, backward = one HIP launch."""
+    """Differentiable fake-quant: forward = one HIP launch, backward = one HIP launch (bf16 / fp16 rows that promote to
+    fp32: one more, the widening of x)."""
 
     @staticmethod
-    def forward(ctx, x, scale, zero_point, ch_axis, quant_min, quant_max, mode, grad_factor):
+    def forward(ctx, x, scale, zero_point, ch_axis, quant_min, quant_max, mode, grad_factor, scalar_params=False):
         ctx.cfg = (ch_axis, quant_min, quant_max, mode & PARAM_MODE_MASK, grad_factor)    # PARAM_SANITIZE is forward-only
+        ctx.chain = is_lowp(x) and _lowp_chain(x, ch_axis, mode, scalar_params)
         ctx.save_for_backward(x, scale, zero_point)
-        if ch_axis == -1:
-            return fake_quant_per_tensor(x, scale, zero_point, quant_min, quant_max, mode, grad_factor)
-        return fake_quant_per_channel(x, scale, zero_point, ch_axis, quant_min, quant_max, mode, grad_factor)
+        return _forward(x, scale, zero_point, ch_axis, quant_min, quant_max, mode, grad_factor, scalar_params)
 
     @staticmethod
     def backward(ctx, grad_out):
         x, scale, zero_point = ctx.saved_tensors
         ch_axis, quant_min, quant_max, mode, grad_factor = ctx.cfg
+        if ctx.chain:          # the parameters were numbers: x only (fake_quant refuses parameters that want a gradient)
+            dx = fake_quant_chain_backward_lowp(x, grad_out, scale, zero_point, quant_min, quant_max)
+            return (dx if ctx.needs_input_grad[0] else None), None, None, None, None, None, None, None, None
+        x_dtype = x.dtype
+        if is_lowp(x):
+            # the promoted rows: autograd's sums see the same fp32 numbers as for x.float(), so the fp32 kernels (every
+            # summation tier) apply to x widened once; dx is rounded to x.dtype once, as torch's to() backward does
+            x = x.float()
         need_s = ctx.needs_input_grad[1]
         need_z = ctx.needs_input_grad[2] and zero_point.dtype == torch.float32
         if ch_axis == -1:
@@ -227,19 +338,25 @@ class _FakeQuantFn(torch.autograd.Function):
             ds = ds.reshape(scale.shape)
         if dz is not None:
             dz = dz.reshape(zero_point.shape)
-        return (dx if ctx.needs_input_grad[0] else None), ds, dz, None, None, None, None, None
+        if dx.dtype != x_dtype:
+            dx = dx.to(x_dtype)
+        return (dx if ctx.needs_input_grad[0] else None), ds, dz, None, None, None, None, None, None
 
 
-def fake_quant(x, scale, zero_point, ch_axis, quant_min, quant_max, mode=PARAM_FIXED, grad_factor=1.0):
-    """Fake-quant with autograd when any input needs a gradient, a bare launch otherwise."""
+def fake_quant(x, scale, zero_point, ch_axis, quant_min, quant_max, mode=PARAM_FIXED, grad_factor=1.0, scalar_params=False):
+    """Fake-quant with autograd when any input needs a gradient, a bare launch otherwise.
+
+    scalar_params: the caller's parameters were Python numbers or 0-dim tensors (FixedFakeQuantize per-tensor passes
+    ``.item()`` values).  It matters for bf16 / fp16 x only: a Fixed per-tensor call then stays in x.dtype (the in-dtype
+    chain); every other bf16 / fp16 call meets fp32 [1] / [C] parameters and returns fp32, as torch's type promotion does."""
     needs = torch.is_grad_enabled() and (x.requires_grad or scale.requires_grad or
                                          (zero_point.is_floating_point() and zero_point.requires_grad))
     if needs:
-        return _FakeQuantFn.apply(x, scale, zero_point, ch_axis, quant_min, quant_max, mode, grad_factor)
-    sd, zd = scale.detach(), zero_point.detach()
-    if ch_axis == -1:
-        return fake_quant_per_tensor(x, sd, zd, quant_min, quant_max, mode, grad_factor)
-    return fake_quant_per_channel(x, sd, zd, ch_axis, quant_min, quant_max, mode, grad_factor)
+        if (is_lowp(x) and _lowp_chain(x, ch_axis, mode, scalar_params)
+                and (scale.requires_grad or (zero_point.is_floating_point() and zero_point.requires_grad))):
+            raise NotImplementedError("bf16 / fp16 fake-quant with number parameters: gradients flow to x only")
+        return _FakeQuantFn.apply(x, scale, zero_point, ch_axis, quant_min, quant_max, mode, grad_factor, scalar_params)
+    return _forward(x, scale.detach(), zero_point.detach(), ch_axis, quant_min, quant_max, mode, grad_factor, scalar_params)
 
 
 # ---------------------------------------------------------------------------------------
@@ -310,6 +427,35 @@ def observe_channels(x, ch_axis, rule, cnt, min_val, max_val, quant_min, quant_m
     _hip.check(lib.osq_observe_channels(_hip.ptr(x), outer, channels, inner, rule, int(cnt), _hip.ptr(min_val),
                                         _hip.ptr(max_val), int(quant_min), int(quant_max), int(bool(symmetric)), s_ptr,
                                         z_ptr, z_type, _hip.stream_ptr(x.device)), "observe_channels")
+
+
+def observe_flat_lowp(x, rule, cnt, min_val, max_val, quant_min, quant_max, symmetric, sink=None, cur=None):
+    """observe_flat reading a bf16 / fp16 tensor: the statistics of observe_flat(x.float(), ...) in ONE launch."""
+    lib = _hip.load()
+    _hip.require_device(x, min_val, max_val)
+    _check_f32(min_val, max_val)
+    x = _lowp_flat(x)
+    s_ptr, z_ptr, z_type = (sink or _NO_SINK).args()
+    _hip.check(lib.osq_observe_flat_lowp(_lowp_code(x), _hip.ptr(x), x.numel(), rule, int(cnt), _hip.ptr(min_val),
+                                         _hip.ptr(max_val), _hip.ptr(cur), int(quant_min), int(quant_max), int(bool(symmetric)),
+                                         s_ptr, z_ptr, z_type, _hip.ptr(_hip.workspace(x.device)), _hip.stream_ptr(x.device)),
+               "observe_flat_lowp")
+
+
+def observe_channels_lowp(x, ch_axis, rule, cnt, min_val, max_val, quant_min, quant_max, symmetric, sink=None):
+    """observe_channels reading a bf16 / fp16 tensor: ONE launch."""
+    lib = _hip.load()
+    _hip.require_device(x, min_val, max_val)
+    _check_f32(min_val, max_val)
+    x = x.contiguous()
+    outer, channels, inner = _channel_split(x, ch_axis)
+    if min_val.numel() != channels or max_val.numel() != channels:
+        raise ValueError("observe_channels: statistic buffers must have one entry per channel")
+    s_ptr, z_ptr, z_type = (sink or _NO_SINK).args()
+    _hip.check(lib.osq_observe_channels_lowp(_lowp_code(x), _hip.ptr(x), outer, channels, inner, rule, int(cnt),
+                                             _hip.ptr(min_val), _hip.ptr(max_val), int(quant_min), int(quant_max),
+                                             int(bool(symmetric)), s_ptr, z_ptr, z_type, _hip.stream_ptr(x.device)),
+               "observe_channels_lowp")
 
 
 _view_cache = {}
@@ -482,6 +628,33 @@ def token_minmax(x, seq_pos, lengths=None, out=None):
     _hip.check(lib.osq_token_minmax(_hip.ptr(x), ctypes.byref(view), _hip.ptr(lengths), _hip.ptr(tmin), _hip.ptr(tmax),
                                     _hip.stream_ptr(x.device)), "token_minmax")
     return tmin, tmax, view.batch, view.tokens, lengths
+
+
+def token_minmax_lowp(x, seq_pos, lengths=None, out=None):
+    """token_minmax reading a bf16 / fp16 tensor (any strides): the fp32 per-token extrema of x.float()."""
+    lib = _hip.load()
+    _hip.require_device(x, lengths)
+    code = _lowp_code(x)
+    if lengths is not None and lengths.dtype != torch.int64:
+        lengths = lengths.to(torch.int64)
+    view = token_view(x, seq_pos, None if lengths is None else lengths.numel())
+    n = view.batch * view.tokens
+    tmin, tmax = out if out is not None else _scratch(x.device, n)[:2]
+    if tmin.numel() < n or tmax.numel() < n:
+        raise ValueError(f"token_minmax: the output rows hold {tmin.numel()} slots, this tensor has {n} (batch x tokens)")
+    _hip.check(lib.osq_token_minmax_lowp(code, _hip.ptr(x), ctypes.byref(view), _hip.ptr(lengths), _hip.ptr(tmin),
+                                         _hip.ptr(tmax), _hip.stream_ptr(x.device)), "token_minmax_lowp")
+    return tmin, tmax, view.batch, view.tokens, lengths
+
+
+def observe_tokens_lowp(x, seq_pos, lengths, prune, percentile, rule, cnt, min_val, max_val, quant_min, quant_max,
+                        symmetric, sink=None, cur=None):
+    """observe_tokens for a bf16 / fp16 tensor: the per-token extrema read from the 2-byte data, then the unchanged fp32
+    finaliser -- TWO launches, no host synchronisation.  Returns (batch, tokens, lengths_int64)."""
+    tmin, tmax, batch, tokens, lengths = token_minmax_lowp(x, seq_pos, lengths)
+    token_range_finalize(tmin, tmax, batch, tokens, lengths, prune, percentile, rule, cnt, min_val, max_val, quant_min,
+                         quant_max, symmetric, sink, cur)
+    return batch, tokens, lengths
 
 
 def token_range_finalize(tmin, tmax, batch, tokens, lengths, prune, percentile, rule, cnt, min_val, max_val,

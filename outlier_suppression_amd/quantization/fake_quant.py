@@ -139,8 +139,11 @@ class QuantizeBase(nn.Module):
         return 1.0 / (numel * self.quant_max) ** 0.5
 
     def _quantize(self, X, flags=0):
+        # FixedFakeQuantize per-tensor hands the reference's util_quant .item() numbers (fake_quant.py:122-124): a bf16 /
+        # fp16 X stays in its dtype there; every other row meets fp32 tensors and returns fp32
         return ops.fake_quant(X, self.scale, self.zero_point, self.ch_axis, self.quant_min, self.quant_max,
-                              self.param_mode | flags, self._grad_factor(X) if self.param_mode != PARAM_FIXED else 1.0)
+                              self.param_mode | flags, self._grad_factor(X) if self.param_mode != PARAM_FIXED else 1.0,
+                              scalar_params=self.param_mode == PARAM_FIXED and self.ch_axis == -1)
 
     # ---- state dict: scale / zero_point change size on the first observation ----------
     def _save_to_state_dict(self, destination, prefix, keep_vars):

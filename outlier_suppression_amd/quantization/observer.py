@@ -10,6 +10,10 @@ Differences in mechanism, not in results:
   * per-token extrema, the two quantiles, the thresholded extrema, the running average
     and calculate_qparams run on the device without a host sync;
   * a whole observation is 1 launch (flat / per-channel) or 2 launches (masked).
+
+bf16 / fp16 input: the reference widens first (``x_orig.to(min_val.dtype)``).  MinMax, AvgMinMax and AvgPruneMinMax
+read the 2-byte data in their own kernels (ops.*_lowp: same statistics); MSEFast / AvgMSEFast, AvgQuantile, MSE / AvgMSE
+and LSQPlus widen once with ``x.float()`` at the boundary (``_widened``), which is that same conversion.
 """
 import torch
 import torch.nn as nn
@@ -22,6 +26,11 @@ def _quant_range(bit, symmetric):
     if symmetric:
         return -(1 << (bit - 1)), (1 << (bit - 1)) - 1
     return 0, (1 << bit) - 1
+
+
+def _widened(x):
+    """fp32 view of a bf16 / fp16 observation for the observers without a 2-byte kernel: the reference's own widening."""
+    return x.float() if ops.is_lowp(x) else x
 
 
 # quantization/deferred.py: while a DeferredSites object is installed here, masked activation observers record their
@@ -83,8 +92,10 @@ class ObserverBase(nn.Module):
             self.cnt += 1
 
     def _observe_tokens(self, x, lengths, seq_pos, prune, sink):
+        lowp = ops.is_lowp(x)
         if self._token_cache is not None:     # keep the per-token extrema; thresholds are applied later, per candidate
-            _, _, batch, tokens, lengths = ops.token_minmax(x, seq_pos, lengths, out=self._token_cache)
+            _, _, batch, tokens, lengths = (ops.token_minmax_lowp if lowp else ops.token_minmax)(x, seq_pos, lengths,
+                                                                                                out=self._token_cache)
             object.__setattr__(self, "_last_site", ("tokens", batch, tokens, lengths))   # nn.Module.__setattr__ costs microseconds
             return
         if (DEFERRED is not None and self._capture is None and self.__dict__.get("_defer_ok", False)
@@ -94,9 +105,11 @@ class ObserverBase(nn.Module):
         rule, cur = self.update_rule, None
         if self._capture is not None:      # record this batch only; calibration.replay() applies the rule later
             rule, cur, sink = ops.UPDATE_NONE, self._capture, None
-        batch, tokens, lengths = ops.observe_tokens(x, seq_pos, lengths, prune, getattr(self, "percentile", 1.0),
-                                                    rule, self._counter(), self.min_val, self.max_val,
-                                                    self.quant_min, self.quant_max, self.symmetric, sink, cur)
+        # a bf16 / fp16 site never reaches DeferredSites (its table is fp32): it runs here, two launches
+        observe = ops.observe_tokens_lowp if lowp else ops.observe_tokens
+        batch, tokens, lengths = observe(x, seq_pos, lengths, prune, getattr(self, "percentile", 1.0),
+                                         rule, self._counter(), self.min_val, self.max_val,
+                                         self.quant_min, self.quant_max, self.symmetric, sink, cur)
         object.__setattr__(self, "_last_site", ("tokens", batch, tokens, lengths))
 
     def token_path_prune(self):
@@ -109,13 +122,15 @@ class ObserverBase(nn.Module):
         rule, cur = self.update_rule, None
         if self._capture is not None:
             rule, cur, sink = ops.UPDATE_NONE, self._capture, None
-        ops.observe_flat(x, rule, self._counter(), self.min_val, self.max_val,
-                         self.quant_min, self.quant_max, self.symmetric, sink, cur)
+        (ops.observe_flat_lowp if ops.is_lowp(x) else ops.observe_flat)(x, rule, self._counter(), self.min_val, self.max_val,
+                                                                         self.quant_min, self.quant_max, self.symmetric, sink,
+                                                                         cur)
 
     def _observe_channels(self, x, sink):
         self._home(x.device, x.shape[self.ch_axis])
-        ops.observe_channels(x, self.ch_axis, self.update_rule, self._counter(), self.min_val, self.max_val,
-                             self.quant_min, self.quant_max, self.symmetric, sink)
+        (ops.observe_channels_lowp if ops.is_lowp(x) else ops.observe_channels)(
+            x, self.ch_axis, self.update_rule, self._counter(), self.min_val, self.max_val, self.quant_min, self.quant_max,
+            self.symmetric, sink)
 
     def observe_into(self, x, observation_mask=None, seq_pos=-1, sink=None):
         """Observe ``x`` and, if ``sink`` is given, also write calculate_qparams(min_val, max_val)
@@ -248,6 +263,7 @@ class MSEFastObserver(ObserverBase):
         return flags
 
     def observe_into(self, x, observation_mask=None, seq_pos=-1, sink=None):
+        x = _widened(x)
         if observation_mask is not None:
             assert self.ch_axis == -1
         cur = ops.batch_minmax(x, observation_mask, seq_pos)
@@ -323,6 +339,7 @@ class LSQPlusObserver(ObserverBase):
         self.std = None
 
     def observe_into(self, x, observation_mask=None, seq_pos=-1, sink=None):
+        x = _widened(x)
         self._home(x.device, None if self.ch_axis == -1 else x.shape[self.ch_axis])
         ops.observe_moments(x, self.ch_axis, self.min_val, self.max_val, self.quant_min, self.quant_max, self.symmetric,
                             sink)
@@ -344,6 +361,7 @@ class AvgQuantileObserver(ObserverBase):
         self._hist = None
 
     def observe_into(self, x, observation_mask=None, seq_pos=-1, sink=None):
+        x = _widened(x)
         if observation_mask is not None:
             assert self.ch_axis == -1
         cur = ops.batch_minmax(x, observation_mask, seq_pos)
@@ -369,6 +387,7 @@ class MSEObserver(ObserverBase):
         self.one_side_dist = None
 
     def observe_into(self, x, observation_mask=None, seq_pos=-1, sink=None):
+        x = _widened(x)
         if observation_mask is not None:
             assert self.ch_axis == -1
         cur = ops.batch_minmax(x, observation_mask, seq_pos)

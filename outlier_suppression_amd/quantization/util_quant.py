@@ -3,6 +3,10 @@
 Each function is ONE fused HIP launch (forward) and, under autograd, one launch for
 the backward.  ``scale`` / ``zero_point`` may be Python numbers or device tensors;
 numbers are uploaded (the reference passes ``.item()`` values at fake_quant.py:124).
+
+bf16 / fp16 ``x`` (README, "Defaults"): ``fake_quantize_per_tensor_affine`` with Python numbers or 0-dim tensors stays in
+x's dtype, every op rounded to it as in torch's eager chain; with >= 1-dim tensor parameters, and for every other function,
+torch's type promotion makes the result fp32, equal to the same call on ``x.float()``.
 """
 import torch
 
@@ -37,9 +41,21 @@ def grad_scale(t, scale):
     return (t - (t * scale)).detach() + (t * scale)
 
 
+def _scalar(v):
+    """A Python number or a 0-dim tensor: what keeps a bf16 / fp16 x in its dtype (decided before _as_scale reshapes it)."""
+    return not torch.is_tensor(v) or v.dim() == 0
+
+
+def _learnable_params(x, scale, zero_point):
+    if ops.is_lowp(x) and _scalar(scale) and _scalar(zero_point):
+        raise NotImplementedError("bf16 / fp16 learnable fake-quant takes [1] / [C] tensor parameters (the quantizers' own)")
+
+
 def fake_quantize_per_tensor_affine(x, scale, zero_point, quant_min, quant_max):
     """util_quant.py:11-15."""
-    return ops.fake_quant(x, _as_scale(scale, x), _as_zero_point(zero_point, x), -1, quant_min, quant_max, PARAM_FIXED)
+    scalar = _scalar(scale) and _scalar(zero_point)
+    return ops.fake_quant(x, _as_scale(scale, x), _as_zero_point(zero_point, x), -1, quant_min, quant_max, PARAM_FIXED,
+                          scalar_params=scalar)
 
 
 def fake_quantize_per_channel_affine(x, scale, zero_point, ch_axis, quant_min, quant_max):
@@ -49,18 +65,21 @@ def fake_quantize_per_channel_affine(x, scale, zero_point, ch_axis, quant_min, q
 
 def fake_quantize_learnable_per_tensor_affine_training(x, scale, zero_point, quant_min, quant_max, grad_factor):
     """util_quant.py:29-34 (LSQ)."""
+    _learnable_params(x, scale, zero_point)
     return ops.fake_quant(x, _as_scale(scale, x), _as_zero_point(zero_point, x), -1, quant_min, quant_max,
                           PARAM_LSQ, grad_factor)
 
 
 def fake_quantize_learnable_per_channel_affine_training(x, scale, zero_point, ch_axis, quant_min, quant_max, grad_factor):
     """util_quant.py:37-45 (LSQ)."""
+    _learnable_params(x, scale, zero_point)
     return ops.fake_quant(x, _as_scale(scale, x), _as_zero_point(zero_point, x), ch_axis, quant_min, quant_max,
                           PARAM_LSQ, grad_factor)
 
 
 def fake_quantize_learnableplus_per_tensor_affine_training(x, scale, zero_point, quant_min, quant_max, grad_factor):
     """util_quant.py:48-55 (LSQ+)."""
+    _learnable_params(x, scale, zero_point)
     return ops.fake_quant(x, _as_scale(scale, x), _as_zero_point(zero_point, x, True), -1, quant_min, quant_max,
                           PARAM_LSQPLUS, grad_factor)
 
@@ -68,5 +87,6 @@ def fake_quantize_learnableplus_per_tensor_affine_training(x, scale, zero_point,
 def fake_quantize_learnableplus_per_channel_affine_training(x, scale, zero_point, ch_axis, quant_min, quant_max,
                                                             grad_factor):
     """util_quant.py:58-67 (LSQ+)."""
+    _learnable_params(x, scale, zero_point)
     return ops.fake_quant(x, _as_scale(scale, x), _as_zero_point(zero_point, x, True), ch_axis, quant_min, quant_max,
                           PARAM_LSQPLUS, grad_factor)
