@@ -202,6 +202,32 @@ typedef struct osq_headsplit_site {
 int osq_fake_quant_headsplit_multi(const osq_headsplit_site* sites, int n_sites, int64_t batch, int64_t tokens,
                                    int64_t heads, int64_t head_dim, osq_stream stream);
 
+/* Incremental decoding (model/quant_bart.py, QuantizedBartCache): the attention sites of one decoder step as ONE launch.
+ * Site i reads the contiguous [batch, tokens, heads * head_dim] projection x and writes
+ *     y[b, head, offset + j, :] = fake_quant(x[b, j, head * head_dim:(head + 1) * head_dim])
+ * into y = a dense [batch, heads, cap, head_dim] buffer, with its own (scale, zero_point), zp_type, mode (incl.
+ * OSQ_PARAM_SANITIZE) and grad_factor: the arithmetic and bits of osq_fake_quant_headsplit_multi.  A query site is
+ * cap = tokens, offset = 0.  With src set (and offset > 0) the same launch also copies the first offset positions,
+ *     y[b, :, :offset, :] = src[src_rows[b], :, :offset, :]      (src_rows NULL: row b; src = [src_batch, heads, src_cap, head_dim])
+ * -- the beam reorder of a KV cache folded into the next append.  src == y without a row index copies nothing (an
+ * in-place append).  src_rows lives on the device (int64); a row outside [0, src_batch) yields NaN and reads nothing.
+ * OSQ_ERR_UNSUPPORTED, nothing launched: head_dim % 4, a tensor not 16-byte aligned, src overlapping y (src == y with a
+ * row index included), or a site of 2^31 float4s or more.  The caller then runs the eager form. */
+typedef struct osq_kv_append_site {
+    const float* x;
+    float* y;
+    const float* src;
+    const int64_t* src_rows;
+    float* scale;
+    void* zero_point;
+    int64_t tokens, cap, offset, src_batch, src_cap;
+    int32_t zp_type, mode;
+    float grad_factor;
+    int32_t quant_min, quant_max, pad;
+} osq_kv_append_site;
+int osq_fake_quant_kv_append(const osq_kv_append_site* sites, int n_sites, int64_t batch, int64_t heads,
+                             int64_t head_dim, osq_stream stream);
+
 /* util_quant.py:18-26 fake_quantize_per_channel_affine (and the per-channel learnable
  * forwards :37-45, :58-67).  x is contiguous and viewed as [outer, channels, inner]
  * with ch_axis in the middle; scale/zero_point have `channels` entries. */

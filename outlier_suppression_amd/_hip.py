@@ -54,6 +54,14 @@ class HeadSplitSite(ctypes.Structure):
                 ("grad_factor", _F), ("quant_min", ctypes.c_int32), ("quant_max", ctypes.c_int32), ("pad", ctypes.c_int32)]
 
 
+class KvAppendSite(ctypes.Structure):
+    """``osq_kv_append_site``: one entry of the table of osq_fake_quant_kv_append."""
+    _fields_ = [("x", _P), ("y", _P), ("src", _P), ("src_rows", _P), ("scale", _P), ("zero_point", _P), ("tokens", _L),
+                ("cap", _L), ("offset", _L), ("src_batch", _L), ("src_cap", _L), ("zp_type", ctypes.c_int32),
+                ("mode", ctypes.c_int32), ("grad_factor", _F), ("quant_min", ctypes.c_int32), ("quant_max", ctypes.c_int32),
+                ("pad", ctypes.c_int32)]
+
+
 class SiteDesc(ctypes.Structure):
     """``osq_site_desc``: one entry of the table of osq_token_minmax_multi."""
     _fields_ = [("x", _P), ("lengths", _P), ("token_min", _P), ("token_max", _P), ("view", TokenView),
@@ -76,6 +84,7 @@ SIGNATURES = {
     "osq_fake_quant_per_tensor_strided": (_I, [_P, _P, _P, ctypes.POINTER(_L), ctypes.POINTER(_L), ctypes.POINTER(_L),
                                                _P, _P, _I, _I, _F, _I, _I, _P]),
     "osq_fake_quant_headsplit_multi": (_I, [ctypes.POINTER(HeadSplitSite), _I, _L, _L, _L, _L, _P]),
+    "osq_fake_quant_kv_append": (_I, [ctypes.POINTER(KvAppendSite), _I, _L, _L, _L, _P]),
     "osq_fake_quant_per_channel": (_I, [_P, _P, _P, _L, _L, _L, _P, _P, _I, _I, _F, _I, _I, _P]),
     "osq_fake_quant_weights_multi": (_I, [_P, _P, _I, _L, _P]),
     "osq_lsq_backward_per_tensor": (_I, [_P, _P, _P, _L, _P, _P, _I, _I, _F, _I, _I, _P, _P, _P, _P]),
@@ -162,7 +171,12 @@ def load():
                 f"or `make -C {os.path.join(_HERE, 'csrc')}`.  outlier_suppression_amd has no CPU fallback.")
         lib = ctypes.CDLL(LIB_PATH)   # torch is already imported: its libamdhip64.so.7 satisfies the dependency
         for name, (res, args) in SIGNATURES.items():
-            fn = getattr(lib, name)   # AttributeError here = header and library disagree
+            try:
+                fn = getattr(lib, name)
+            except AttributeError:    # a library older than this package: an entry point added within one ABI version
+                raise HipLibraryMissing(
+                    f"{LIB_PATH} does not export {name}: it is older than this package, rebuild it "
+                    f"(`make -C {os.path.join(_HERE, 'csrc')}`).") from None
             fn.restype = res
             fn.argtypes = args
         built = int(lib.osq_abi_version())

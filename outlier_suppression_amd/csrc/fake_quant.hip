@@ -283,6 +283,62 @@ __global__ __launch_bounds__(kThreads) void fq_headsplit_multi_kernel(HeadSplitS
     }
 }
 
+// Incremental decoding (model/quant_bart.py, QuantizedBartCache): one step's query / key / value projections fake-quantised
+// and written at positions [offset, offset + tokens) of [B, h, cap, d] buffers, the first `offset` positions optionally
+// copied from a source buffer through a row index (the beam reorder of _reorder_cache folded into the append).  ONE
+// launch, blockIdx.y = site; every site has its own token count, capacity, offset and parameters.  The fake-quant
+// arithmetic is fq4 with tensor_params, as in fq_headsplit_multi_kernel: the same bits.  The per-step tensors are tiny:
+// the index maps use plain 32-bit divisions (the launcher keeps every site below 2^31 float4s).
+struct KvAppendSites {
+    const float4* x[kHeadSplitSites];
+    float4* y[kHeadSplitSites];
+    const float4* src[kHeadSplitSites];      // nullptr: nothing to copy
+    const int64_t* rows[kHeadSplitSites];    // nullptr: row b of src
+    float* scale[kHeadSplitSites];
+    void* zp[kHeadSplitSites];
+    int zp_type[kHeadSplitSites], mode[kHeadSplitSites];
+    float g[kHeadSplitSites], qmin[kHeadSplitSites], qmax[kHeadSplitSites];
+    unsigned int tokens[kHeadSplitSites], cap[kHeadSplitSites], offset[kHeadSplitSites];
+    unsigned int src_cap[kHeadSplitSites], src_batch[kHeadSplitSites];
+    unsigned int n_copy[kHeadSplitSites], n_total[kHeadSplitSites];   // float4s
+};
+
+__global__ __launch_bounds__(kThreads) void fq_kv_append_kernel(KvAppendSites s, unsigned int heads, unsigned int dv) {
+    const int site = blockIdx.y;
+    const float4* __restrict__ x = s.x[site];
+    float4* __restrict__ y = s.y[site];
+    const float qmin = s.qmin[site], qmax = s.qmax[site];
+    const QParams p = tensor_params(s.scale[site], s.zp[site], s.zp_type[site], s.mode[site], s.g[site], qmin, qmax);
+    const unsigned int cap = s.cap[site], offset = s.offset[site], tokens = s.tokens[site];
+    const unsigned int n_copy = s.n_copy[site], n_total = s.n_total[site];
+    const unsigned int stride = gridDim.x * kThreads;
+    const unsigned int head_row = heads * dv, past_row = offset * dv;
+    for (unsigned int i = blockIdx.x * kThreads + threadIdx.x; i < n_total; i += stride) {
+        if (i < n_copy) {
+            // y[b, head, :offset] = src[rows[b], head, :offset]
+            const unsigned int bh = i / past_row, r = i - bh * past_row;
+            const unsigned int b = bh / heads, head = bh - b * heads;
+            const int64_t row = s.rows[site] ? s.rows[site][b] : static_cast<int64_t>(b);
+            float4 v;
+            if (row >= 0 && row < static_cast<int64_t>(s.src_batch[site])) {
+                v = s.src[site][((static_cast<unsigned int>(row) * heads + head) * s.src_cap[site]) * dv + r];
+            } else {                                                     // an index out of range: NaN, no read
+                v.x = v.y = v.z = v.w = __builtin_nanf("");
+            }
+            y[bh * cap * dv + r] = v;
+        } else {
+            // y[b, head, offset + j, :] = fake_quant(x[b, j, head * d:(head + 1) * d])
+            const unsigned int e = i - n_copy;
+            const unsigned int bt = e / head_row, c = e - bt * head_row;
+            const unsigned int b = bt / tokens, j = bt - b * tokens;
+            const unsigned int head = c / dv, dd = c - head * dv;
+            float4 o, q;
+            fq4<false>(x[e], o, q, p.scale, p.zp, qmin, qmax);
+            y[((b * heads + head) * cap + offset + j) * dv + dd] = o;
+        }
+    }
+}
+
 // ---------------------------------------------------------------- per-channel
 
 // [rows = outer*channels, inner] with inner % 4 == 0: one wave walks whole rows, the
@@ -895,6 +951,63 @@ extern "C" int osq_fake_quant_headsplit_multi(const osq_headsplit_site* sites, i
     else OSQ_HEADSPLIT_M(1);
 #undef OSQ_HEADSPLIT_M
     return check_launch("fake_quant_headsplit_multi");
+}
+
+extern "C" int osq_fake_quant_kv_append(const osq_kv_append_site* sites, int n_sites, int64_t batch, int64_t heads,
+                                        int64_t head_dim, osq_stream stream) {
+    OSQ_REQUIRE(sites && n_sites >= 1 && n_sites <= kHeadSplitSites, "fake_quant_kv_append: 1..4 sites");
+    OSQ_REQUIRE(batch >= 0 && heads >= 1 && head_dim >= 1, "fake_quant_kv_append: bad geometry");
+    if (head_dim % 4 != 0) return OSQ_ERR_UNSUPPORTED;
+    const int64_t dv = head_dim / 4;
+    const int64_t kLimit = 1ll << 31;                  // every index of the kernel in 32 bits
+    KvAppendSites ks{};
+    int64_t most = 0;
+    for (int i = 0; i < n_sites; ++i) {
+        const osq_kv_append_site& t = sites[i];
+        OSQ_REQUIRE(t.scale && t.zero_point, "fake_quant_kv_append: null parameter pointer in a site");
+        OSQ_REQUIRE(t.tokens >= 0 && t.offset >= 0 && t.cap >= t.offset + t.tokens,
+                    "fake_quant_kv_append: need 0 <= offset, offset + tokens <= cap");
+        const int64_t n_app = batch * t.tokens * heads * dv;
+        OSQ_REQUIRE(n_app == 0 || (t.x && t.y), "fake_quant_kv_append: null tensor in a site");
+        const bool copy = t.src && t.offset > 0 && batch > 0 && !(t.src == t.y && !t.src_rows);
+        int64_t n_copy = 0;
+        if (copy) {
+            OSQ_REQUIRE(t.y && t.src_cap >= t.offset && t.src_batch >= 1, "fake_quant_kv_append: source smaller than offset");
+            OSQ_REQUIRE(t.src_rows || t.src_batch == batch, "fake_quant_kv_append: source batch differs, no row index");
+            n_copy = batch * heads * t.offset * dv;
+            // the copy must not read what the launch writes: the same buffer with a row index, or overlapping ranges
+            const char *s0 = reinterpret_cast<const char*>(t.src), *s1 = s0 + t.src_batch * heads * t.src_cap * head_dim * 4;
+            const char *y0 = reinterpret_cast<const char*>(t.y), *y1 = y0 + batch * heads * t.cap * head_dim * 4;
+            if (s0 < y1 && y0 < s1) return OSQ_ERR_UNSUPPORTED;
+            if (!aligned16(t.src) || t.src_batch * heads * t.src_cap * dv >= kLimit) return OSQ_ERR_UNSUPPORTED;
+        }
+        if ((t.x && !aligned16(t.x)) || (t.y && !aligned16(t.y))) return OSQ_ERR_UNSUPPORTED;
+        if (batch * heads * t.cap * dv >= kLimit || n_copy + n_app >= kLimit) return OSQ_ERR_UNSUPPORTED;
+        ks.x[i] = reinterpret_cast<const float4*>(t.x);
+        ks.y[i] = reinterpret_cast<float4*>(t.y);
+        ks.src[i] = copy ? reinterpret_cast<const float4*>(t.src) : nullptr;
+        ks.rows[i] = copy ? t.src_rows : nullptr;
+        ks.scale[i] = t.scale;
+        ks.zp[i] = t.zero_point;
+        ks.zp_type[i] = t.zp_type;
+        ks.mode[i] = t.mode;
+        ks.g[i] = t.grad_factor;
+        ks.qmin[i] = static_cast<float>(t.quant_min);
+        ks.qmax[i] = static_cast<float>(t.quant_max);
+        ks.tokens[i] = static_cast<unsigned int>(t.tokens);
+        ks.cap[i] = static_cast<unsigned int>(t.cap);
+        ks.offset[i] = static_cast<unsigned int>(t.offset);
+        ks.src_cap[i] = copy ? static_cast<unsigned int>(t.src_cap) : 0u;
+        ks.src_batch[i] = copy ? static_cast<unsigned int>(t.src_batch) : 0u;
+        ks.n_copy[i] = static_cast<unsigned int>(n_copy);
+        ks.n_total[i] = static_cast<unsigned int>(n_copy + n_app);
+        most = std::max(most, n_copy + n_app);
+    }
+    if (most == 0) return OSQ_OK;
+    const dim3 grid(static_cast<unsigned>(grid_for(most, kThreads, kMaxBlocks)), static_cast<unsigned>(n_sites));
+    hipLaunchKernelGGL(fq_kv_append_kernel, grid, dim3(kThreads), 0, static_cast<hipStream_t>(stream), ks,
+                       static_cast<unsigned int>(heads), static_cast<unsigned int>(dv));
+    return check_launch("fake_quant_kv_append");
 }
 
 extern "C" int osq_fake_quant_per_channel(const float* x, float* y, float* x_quant,

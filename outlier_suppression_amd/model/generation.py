@@ -1,0 +1,189 @@
+"""generate() for the quantized BART wrapper: greedy and beam search over a KV cache.
+
+The package's own loop, not transformers' GenerationMixin (whose cache contract does not fit the reference's tuples).
+It follows transformers' greedy decoding and its vectorised beam search step for step, so that with the quantizers
+disabled the tokens equal ``BartForConditionalGeneration.generate`` on the FP model.  The logits processors a BART
+configuration turns on -- no_repeat_ngram_size, min_length, forced_bos_token_id, forced_eos_token_id -- are
+transformers' own, applied in transformers' order.  Not covered: sampling, return_dict_in_generate, streaming.
+
+Each step feeds the last token with the cache (quant_bart.QuantizedBartCache: the step's k / v are fake-quantized and
+appended in one launch, a beam reorder rides in the next append); ``use_cache=False`` re-runs the whole prefix instead.
+"""
+import torch
+from torch import nn
+
+_DEFAULTS = {"max_length": 20, "min_length": 0, "num_beams": 1, "no_repeat_ngram_size": 0, "forced_bos_token_id": None,
+             "forced_eos_token_id": None, "length_penalty": 1.0, "early_stopping": False, "num_return_sequences": 1,
+             "pad_token_id": None, "eos_token_id": None, "decoder_start_token_id": None, "bos_token_id": None}
+_NOT_COVERED = ("do_sample", "return_dict_in_generate", "streamer", "output_scores", "num_beam_groups", "top_k", "top_p",
+                "temperature")
+
+
+def _setting(model, name, given):
+    """The explicit argument, else the wrapped model's generation_config, else its config, else transformers' default."""
+    if given is not None:
+        return given
+    for src in (getattr(model, "generation_config", None), model.config):
+        v = getattr(src, name, None) if src is not None else None
+        if v is not None:
+            return v
+    return _DEFAULTS[name]
+
+
+def _processors(min_length, eos, no_repeat, forced_bos, forced_eos, max_length, device):
+    from transformers.generation.logits_process import (ForcedBOSTokenLogitsProcessor, ForcedEOSTokenLogitsProcessor,
+                                                        LogitsProcessorList, MinLengthLogitsProcessor,
+                                                        NoRepeatNGramLogitsProcessor)
+    procs = LogitsProcessorList()                # transformers' _get_logits_processor order
+    if no_repeat and no_repeat > 0:
+        procs.append(NoRepeatNGramLogitsProcessor(no_repeat))
+    if min_length and min_length > 0 and eos is not None:
+        procs.append(MinLengthLogitsProcessor(min_length, eos, device=device))
+    if forced_bos is not None:
+        procs.append(ForcedBOSTokenLogitsProcessor(forced_bos))
+    if forced_eos is not None:
+        procs.append(ForcedEOSTokenLogitsProcessor(max_length, forced_eos, device=device))
+    return procs
+
+
+def _step_logits(model, seq, enc, attention_mask, cache):
+    """Logits of the last position: the last token through the cache, or the whole prefix without one."""
+    if cache is None:
+        return model(decoder_input_ids=seq, encoder_outputs=(enc,), attention_mask=attention_mask)[0][:, -1, :]
+    logits, cache_out, _ = model(decoder_input_ids=seq[:, -1:], encoder_outputs=(enc,), attention_mask=attention_mask,
+                                 past_key_values=cache, use_cache=True)
+    assert cache_out is cache
+    return logits[:, -1, :]
+
+
+def generate(model, input_ids, attention_mask=None, max_length=None, num_beams=None, use_cache=True, **kwargs):
+    if kwargs.pop("synced_gpus", False):      # Seq2SeqTrainer's predict_with_generate passes synced_gpus=False
+        raise NotImplementedError("generate(): synced_gpus=True is not supported")
+    for name in _NOT_COVERED:
+        if kwargs.get(name):
+            raise NotImplementedError(f"generate(): {name} is not supported (greedy and beam search only)")
+    unknown = set(kwargs) - set(_DEFAULTS) - set(_NOT_COVERED)
+    if unknown:
+        raise TypeError(f"generate(): unexpected arguments {sorted(unknown)}")
+    get = lambda name, given=None: _setting(model, name, kwargs.get(name, given))  # noqa: E731
+    max_length, num_beams = get("max_length", max_length), get("num_beams", num_beams)
+    pad, start = get("pad_token_id"), get("decoder_start_token_id")
+    if start is None:
+        start = get("bos_token_id")
+    eos = get("eos_token_id")
+    eos_t = None if eos is None else torch.tensor(eos if isinstance(eos, (list, tuple)) else [eos], device=input_ids.device)
+    procs = _processors(get("min_length"), eos_t, get("no_repeat_ngram_size"), get("forced_bos_token_id"),
+                        get("forced_eos_token_id"), max_length, input_ids.device)
+    n_return = get("num_return_sequences")
+    if attention_mask is None:
+        attention_mask = torch.ones_like(input_ids)
+    enc = model.get_encoder()(input_ids, attention_mask=attention_mask)
+    n_layers = len(model.model.decoder.layers)
+    if num_beams == 1:
+        if n_return != 1:
+            raise ValueError("greedy decoding returns one sequence per input (num_return_sequences must be 1)")
+        return _greedy(model, enc, attention_mask, start, pad, eos_t, procs, max_length, use_cache, n_layers)
+    if n_return > num_beams:
+        raise ValueError("num_return_sequences must not exceed num_beams")
+    return _beam_search(model, enc, attention_mask, start, pad, eos_t, procs, max_length, num_beams, n_return,
+                        get("length_penalty"), get("early_stopping"), use_cache, n_layers)
+
+
+def _greedy(model, enc, attention_mask, start, pad, eos, procs, max_length, use_cache, n_layers):
+    from .quant_bart import QuantizedBartCache
+    b = enc.shape[0]
+    seq = torch.full((b, 1), start, dtype=torch.long, device=enc.device)
+    cache = QuantizedBartCache(n_layers, capacity=max_length) if use_cache else None
+    unfinished = torch.ones(b, dtype=torch.long, device=enc.device)
+    while seq.shape[1] < max_length:
+        scores = procs(seq, _step_logits(model, seq, enc, attention_mask, cache).to(torch.float32))
+        nxt = torch.argmax(scores, dim=-1)
+        if eos is not None:
+            nxt = nxt * unfinished + pad * (1 - unfinished)
+        seq = torch.cat([seq, nxt[:, None]], dim=-1)
+        if eos is not None:
+            unfinished = unfinished & ~torch.isin(nxt, eos)
+            if unfinished.max() == 0:
+                break
+    return seq
+
+
+def _gather(t, idx):
+    """t[b, idx[b, k], ...] for a [B, N, ...] tensor and a [B, K] index."""
+    while idx.dim() < t.dim():
+        idx = idx.unsqueeze(-1)
+    return torch.gather(t, 1, idx.expand(*idx.shape[:2], *t.shape[2:]))
+
+
+def _beam_search(model, enc, attention_mask, start, pad, eos, procs, max_length, nb, n_return, length_penalty,
+                 early_stopping, use_cache, n_layers):
+    """transformers' vectorised beam search (GenerationMixin._beam_search, 5.x) with the prompt of one start token."""
+    from .quant_bart import QuantizedBartCache
+    dev = enc.device
+    bsz = enc.shape[0]
+    enc = enc.repeat_interleave(nb, dim=0)
+    attention_mask = attention_mask.repeat_interleave(nb, dim=0)
+    vocab = model.config.vocab_size
+    prompt = cur = 1
+    keep = max(2, 1 + (eos.shape[0] if eos is not None else 0)) * nb
+    top_mask = torch.cat((torch.ones(nb, dtype=torch.bool), torch.zeros(keep - nb, dtype=torch.bool))).to(dev)
+    fill = (pad if pad else int(eos[0])) if eos is not None else -1
+    running = torch.full((bsz, nb, max_length), fill, dtype=torch.long, device=dev)
+    running[:, :, 0] = start
+    finished = running.clone()
+    running_scores = torch.zeros((bsz, nb), dtype=torch.float, device=dev)
+    running_scores[:, 1:] = -1e9
+    scores = torch.full((bsz, nb), -1e9, dtype=torch.float, device=dev)
+    done = torch.zeros((bsz, nb), dtype=torch.bool, device=dev)
+    improvable = torch.ones((bsz, 1), dtype=torch.bool, device=dev)
+    finished_len = torch.zeros((bsz, nb), dtype=torch.long, device=dev)      # generated tokens of each finished beam
+    offsets = torch.arange(bsz, device=dev).view(-1, 1) * nb
+    cache = QuantizedBartCache(n_layers, capacity=max_length) if use_cache else None
+    while True:
+        flat = running[:, :, :cur].reshape(bsz * nb, cur)
+        logits = _step_logits(model, flat, enc, attention_mask, cache).to(torch.float32)
+        log_probs = procs(flat, nn.functional.log_softmax(logits, dim=-1))
+        log_probs = (log_probs.view(bsz, nb, vocab) + running_scores[:, :, None]).view(bsz, nb * vocab)
+        # c. top-K continuations over all beams
+        top_lp, top_idx = torch.topk(log_probs, k=keep)
+        beam = top_idx // vocab
+        top_seq = _gather(running, beam)
+        top_seq[:, :, cur] = top_idx % vocab
+        rows = beam + offsets
+        # d. which of them finished
+        hits = torch.full((bsz, keep), cur + 1 >= max_length, dtype=torch.bool, device=dev)
+        if eos is not None:
+            hits = hits | torch.isin(top_seq[:, :, cur], eos)
+        # e. the best num_beams unfinished continue
+        top_running_lp = top_lp + hits.to(torch.float32) * -1.0e9
+        nxt = torch.topk(top_running_lp, k=nb)[1]
+        running = _gather(top_seq, nxt)
+        running_scores = _gather(top_running_lp, nxt)
+        beam_idx = _gather(rows, nxt).view(-1)
+        # f. merge newly finished ones into the finished set
+        just = hits & top_mask[None, :]
+        cand = top_lp / ((cur + 1 - prompt) ** length_penalty)
+        full = torch.all(done, axis=-1, keepdims=True) & (early_stopping is True)
+        cand += full.to(torch.float32) * -1.0e9
+        cand += (~improvable).to(torch.float32) * -1.0e9
+        cand += (~just) * -1.0e9
+        merged = torch.topk(torch.cat((scores, cand), dim=1), k=nb)[1]
+        finished = _gather(torch.cat((finished, top_seq), dim=1), merged)
+        scores = _gather(torch.cat((scores, cand), dim=1), merged)
+        finished_len = _gather(torch.cat((finished_len, torch.full_like(top_idx, cur + 1 - prompt)), dim=1), merged)
+        done = _gather(torch.cat((done, just), dim=1), merged)
+        # g. next iteration: the cache follows the kept beams
+        if cache is not None:
+            cache = model._reorder_cache(cache, beam_idx)
+        cur += 1
+        # early-stop heuristic and stopping condition (transformers' _check_early_stop_heuristic / _has_unfinished)
+        best_len = (max_length - prompt) if (early_stopping == "never" and length_penalty > 0.0) else (cur - prompt)
+        best_running = running_scores[:, :1] / (best_len ** length_penalty)
+        worst_done = torch.where(done, torch.min(scores, dim=1, keepdim=True)[0], -1.0e9)
+        improvable = improvable & torch.any(best_running > worst_done, dim=-1, keepdim=True)
+        go_on = torch.any(improvable) & ~(torch.all(done) & (early_stopping is True)) & ~torch.all(hits)
+        if not bool(go_on):
+            break
+    seqs = finished[:, :n_return].reshape(bsz * n_return, max_length)
+    length = prompt + int(finished_len[:, :n_return].max())
+    return seqs[:, :length]

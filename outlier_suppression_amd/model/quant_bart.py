@@ -15,16 +15,20 @@ Placement table (reference: quant_transformer/model/quant_bart.py):
   model         shared / encoder.embed_tokens / decoder.embed_tokens are three separate QEmbedding copies
                 (:553,698,901); encoder qoutput=True, decoder qoutput = model's (:904-907)
   lm            model(qoutput=True) -> lm_head (QLinear) + final_logits_bias (:1020-1023,1101)
-Teacher-forced forward only (what calibration needs); generation stays with the FP HuggingFace model,
-as in the reference driver (ptq_summ_quant.py:137-153).
+  decoding      past_key_values / use_cache / encoder_outputs (:1036-1164): a step fake-quantizes only its own k / v and
+                appends them to the cache; cross-attention k / v are quantized once and reused.  QuantizedBartCache holds
+                the buffers and reads as the reference's tuple of (k, v, cross_k, cross_v) per layer; generate()
+                (model/generation.py) runs greedy and beam search on it.
 """
 import torch
 from torch import nn
 
+from . import generation
 from .losses import classification_loss, lm_loss, span_loss, with_loss
 from ..quantization import QuantizedModule, Quantizer
 from ..util_layernorm import (GammaResidual, QuantizedLayerNorm, activation_fake_quant, attention_probs_fake_quant,
-                              merge_heads_fake_quant, qkv_heads_fake_quant, residual_layernorm, split_heads_fake_quant)
+                              kv_append_fake_quant, merge_heads_fake_quant, qkv_heads_fake_quant, residual_layernorm,
+                              split_heads_fake_quant)
 
 
 def shift_tokens_right(input_ids, pad_token_id, decoder_start_token_id):
@@ -36,12 +40,15 @@ def shift_tokens_right(input_ids, pad_token_id, decoder_start_token_id):
     return shifted
 
 
-def _causal_mask(bsz, tgt_len, dtype, device):
-    """quant_bart.py:40-52: -inf above the diagonal."""
+def _causal_mask(bsz, tgt_len, dtype, device, past=0):
+    """quant_bart.py:40-52: -inf above the diagonal, preceded by `past` zero columns for the cached positions."""
     mask = torch.full((tgt_len, tgt_len), float("-inf"), device=device)
     cond = torch.arange(tgt_len, device=device)
     mask.masked_fill_(cond < (cond + 1).view(tgt_len, 1), 0)
-    return mask.to(dtype)[None, None, :, :].expand(bsz, 1, tgt_len, tgt_len)
+    mask = mask.to(dtype)
+    if past > 0:
+        mask = torch.cat([torch.zeros(tgt_len, past, dtype=dtype, device=device), mask], dim=-1)
+    return mask[None, None, :, :].expand(bsz, 1, tgt_len, tgt_len + past)
 
 
 def _expand_mask(mask, dtype, tgt_len=None):
@@ -67,6 +74,126 @@ def _embed_scale(stack):
     if hasattr(stack, "embed_scale"):
         return stack.embed_scale
     return getattr(stack.embed_tokens, "embed_scale", 1.0)
+
+
+class QuantizedBartCache:
+    """The decoder's KV cache for incremental decoding.
+
+    Per layer: the self-attention keys / values in [B, h, cap, d] buffers with room for `capacity` positions (a step
+    appends in place), a ping-pong partner buffer for beam reorders, and the cross-attention keys / values (quantized once,
+    at the first step).  ``reorder(beam_idx)`` (what ``_reorder_cache`` calls) only records the row index: the next step's
+    append copies the kept prefix through it into the partner buffer in the same launch (util_layernorm.
+    kv_append_fake_quant), so a step costs one cache copy when beams move and none for greedy decoding, with no torch.cat.
+
+    The object also reads as the reference's legacy tuple of tuples: ``cache[i] == (k, v, cross_k, cross_v)``, each a
+    [B, h, S, d] view, ``cache[0][0].shape[2]`` the past length (quant_bart.py:774).  Reading it applies a pending reorder.
+    A step extends the cache in place and returns the same object: views read from it stay valid until the next step."""
+
+    def __init__(self, num_layers, capacity=None):
+        self.capacity = capacity
+        self._k = [None] * num_layers
+        self._v = [None] * num_layers
+        self._spare = [None] * num_layers          # (k, v) partner buffers, or None
+        self._len = [0] * num_layers
+        self._rows = [None] * num_layers           # pending beam index per layer
+        self._cross = [None] * num_layers          # (k, v) of the cross-attention, or None
+
+    @classmethod
+    def wrap(cls, past, num_layers, capacity=None):
+        """``past``: None, a QuantizedBartCache (returned as it is), or the reference's tuple of per-layer (k, v[, cross_k,
+        cross_v]) tensors."""
+        if isinstance(past, cls):
+            return past
+        cache = cls(num_layers, capacity)
+        if past is not None:
+            if len(past) != num_layers:
+                raise ValueError(f"past_key_values has {len(past)} layers, the decoder {num_layers}")
+            for i, layer in enumerate(past):
+                cache._k[i], cache._v[i] = layer[0], layer[1]
+                cache._len[i] = layer[0].shape[2]
+                if len(layer) >= 4:
+                    cache._cross[i] = (layer[2], layer[3])
+        return cache
+
+    def get_seq_length(self, layer=0):
+        return self._len[layer]
+
+    def reorder(self, beam_idx):
+        """Select the rows ``beam_idx`` of every self-attention cache, lazily; returns self."""
+        for i in range(len(self._k)):
+            if self._k[i] is not None:
+                self._rows[i] = beam_idx if self._rows[i] is None else self._rows[i].index_select(0, beam_idx)
+        return self
+
+    def _materialise(self, i):
+        rows = self._rows[i]
+        if rows is not None:
+            n = self._len[i]
+            self._k[i] = self._k[i][:, :, :n].index_select(0, rows)
+            self._v[i] = self._v[i][:, :, :n].index_select(0, rows)
+            self._rows[i] = None
+
+    def __len__(self):
+        return len(self._k)
+
+    def __getitem__(self, i):
+        if self._k[i] is None:
+            raise IndexError(f"layer {i} of the cache holds nothing yet")
+        self._materialise(i)
+        n = self._len[i]
+        return (self._k[i][:, :, :n], self._v[i][:, :, :n]) + (self._cross[i] if self._cross[i] is not None else ())
+
+    def __iter__(self):
+        return (self[i] for i in range(len(self)))
+
+    def to_legacy(self):
+        return tuple(self)
+
+    # ---- what QuantizedBartAttention uses
+    def append_targets(self, i, bsz, heads, head_dim, t, like):
+        """Destination buffers for a step of t tokens at layer i: (k_dst, v_dst, k_src, v_src, rows).  In place when no
+        reorder is pending and the buffer has room, else the partner buffer (the kept prefix is copied through rows)."""
+        n, k, v, rows = self._len[i], self._k[i], self._v[i], self._rows[i]
+        want = n + t
+        if k is not None and rows is None and k.shape[2] >= want and k.shape[0] == bsz and k.is_contiguous():
+            return k, v, None, None, None
+        cap = max(want, self.capacity or 0, 2 * n)
+        spare = self._spare[i]
+        if spare is not None and spare[0].shape[0] == bsz and spare[0].shape[2] >= want:
+            kd, vd = spare
+        else:
+            shape = (bsz, heads, cap, head_dim)
+            kd, vd = like.new_empty(shape), like.new_empty(shape)
+        if k is None:
+            return kd, vd, None, None, None
+        return kd, vd, k[:, :, :n], v[:, :, :n], rows
+
+    def commit(self, i, k, v, length):
+        if k is not self._k[i]:
+            old = self._k[i]
+            if old is not None and old.is_contiguous() and old.dim() == 4:
+                self._spare[i] = (old, self._v[i])
+            self._k[i], self._v[i] = k, v
+        self._len[i] = length
+        self._rows[i] = None
+
+    def past(self, i):
+        """The self-attention (k, v) of layer i as [B, h, S, d] views, any pending reorder applied (eager form), or None."""
+        if self._k[i] is None:
+            return None
+        self._materialise(i)
+        n = self._len[i]
+        return self._k[i][:, :, :n], self._v[i][:, :, :n]
+
+    def slot(self, i):
+        return _CacheSlot(self, i)
+
+
+class _CacheSlot:
+    """One decoder layer's view of a QuantizedBartCache: the ``past_key_value`` a QuantizedBartAttention takes."""
+
+    def __init__(self, cache, layer):
+        self.cache, self.layer = cache, layer
 
 
 class QuantizedBartLearnedPositionalEmbedding(QuantizedModule):
@@ -106,10 +233,53 @@ class QuantizedBartAttention(QuantizedModule):
         if qoutput:
             self.out_proj_post_act_fake_quantize = Quantizer(None, a_qconfig)
 
-    def forward(self, hidden_states, key_value_states=None, attention_mask=None, observation_mask=None):
+    def _cached_qkv(self, slot, hidden_states, key_value_states, observation_mask):
+        """q / k / v of a decoding step (quant_bart.py:156-198): self-attention fake-quantizes the step's keys / values and
+        appends them to the cache, cross-attention quantizes the encoder's once and reuses them.  k / v come back as
+        [B, h, S, d] views of the cache buffers."""
+        cache, i, heads, d = slot.cache, slot.layer, self.num_heads, self.head_dim
+        bsz, t, _ = hidden_states.shape
+        xq = self.q_proj(hidden_states) * self.scaling
+        qs = (self.query_post_act_fake_quantize, self.key_post_act_fake_quantize, self.value_post_act_fake_quantize)
+        if key_value_states is not None:
+            if cache._cross[i] is not None:
+                return (split_heads_fake_quant(qs[0], xq, heads, observation_mask),) + tuple(cache._cross[i])
+            xk, xv = self.k_proj(key_value_states), self.v_proj(key_value_states)
+            s = xk.shape[1]
+            out = kv_append_fake_quant([(qs[0], xq, xq.new_empty((bsz, heads, t, d)), 0, None, None),
+                                        (qs[1], xk, xk.new_empty((bsz, heads, s, d)), 0, None, None),
+                                        (qs[2], xv, xv.new_empty((bsz, heads, s, d)), 0, None, None)], heads)
+            if out is None:
+                out = [split_heads_fake_quant(q, x, heads, observation_mask) for q, x in zip(qs, (xq, xk, xv))]
+            cache._cross[i] = (out[1], out[2])
+            return tuple(out)
+        xk, xv = self.k_proj(hidden_states), self.v_proj(hidden_states)
+        n = cache.get_seq_length(i)
+        kd, vd, ks, vs, rows = cache.append_targets(i, bsz, heads, d, t, xk)
+        out = kv_append_fake_quant([(qs[0], xq, xq.new_empty((bsz, heads, t, d)), 0, None, None),
+                                    (qs[1], xk, kd, n, ks, rows), (qs[2], xv, vd, n, vs, rows)], heads)
+        if out is not None:
+            cache.commit(i, kd, vd, n + t)
+            return out[0], kd[:, :, :n + t], vd[:, :, :n + t]
+        # the reference's eager form: quantizer, head split, then index_select (pending reorder) and torch.cat
+        q, k, v = [split_heads_fake_quant(q, x, heads, observation_mask) for q, x in zip(qs, (xq, xk, xv))]
+        past = cache.past(i)
+        if past is not None:
+            k, v = torch.cat([past[0], k], dim=2), torch.cat([past[1], v], dim=2)
+        cache.commit(i, k, v, n + t)
+        return q, k, v
+
+    def forward(self, hidden_states, key_value_states=None, attention_mask=None, observation_mask=None,
+                past_key_value=None):
+        """``past_key_value``: None (no cache; returns the output alone, as before) or a layer slot of a
+        QuantizedBartCache (QuantizedBartCache.slot(i)), which this call extends: returns (output, past_key_value)."""
         bsz, tgt_len, _ = hidden_states.shape
-        source = hidden_states if key_value_states is None else key_value_states
         heads = self.num_heads
+        if past_key_value is not None:
+            q, k, v = self._cached_qkv(past_key_value, hidden_states, key_value_states, observation_mask)
+            out = self._attend(q, k, v, bsz, tgt_len, attention_mask, observation_mask)
+            return out, past_key_value
+        source = hidden_states if key_value_states is None else key_value_states
         xq, xk, xv = self.q_proj(hidden_states) * self.scaling, self.k_proj(source), self.v_proj(source)
         # self-attention in the plain quantising state: the three head-split sites in one launch (same bits); cross-attention
         # (keys / values of another length) and every other state: site by site
@@ -121,6 +291,10 @@ class QuantizedBartAttention(QuantizedModule):
             q = split_heads_fake_quant(self.query_post_act_fake_quantize, xq, heads, observation_mask)
             k = split_heads_fake_quant(self.key_post_act_fake_quantize, xk, heads, observation_mask)
             v = split_heads_fake_quant(self.value_post_act_fake_quantize, xv, heads, observation_mask)
+        return self._attend(q, k, v, bsz, tgt_len, attention_mask, observation_mask)
+
+    def _attend(self, q, k, v, bsz, tgt_len, attention_mask, observation_mask):
+        """[B, h, T, d] q and [B, h, S, d] k / v (dense, or views of a cache buffer) -> the block's output."""
         proj = (bsz * self.num_heads, -1, self.head_dim)
         q, k, v = q.view(*proj), k.view(*proj), v.view(*proj)
         w = torch.bmm(q, k.transpose(1, 2))
@@ -202,16 +376,19 @@ class QuantizedBartDecoderLayer(QuantizedModule):
         return nn.functional.dropout(x, p=p, training=self.training)
 
     def forward(self, hidden_states, attention_mask=None, encoder_hidden_states=None, encoder_attention_mask=None,
-                observation_mask=None):
+                observation_mask=None, past_key_value=None):
+        """``past_key_value``: None, or this layer's slot of a QuantizedBartCache (extended in place)."""
+        def attn(module, x, **kw):
+            if past_key_value is None:
+                return module(x, observation_mask=observation_mask, **kw)
+            return module(x, observation_mask=observation_mask, past_key_value=past_key_value, **kw)[0]
         residual = hidden_states
-        h = self._drop(self.self_attn(hidden_states, attention_mask=attention_mask, observation_mask=observation_mask),
-                       self.dropout)
+        h = self._drop(attn(self.self_attn, hidden_states, attention_mask=attention_mask), self.dropout)
         h = residual_layernorm(self.before_self_attn_layer_norm_residual, self.self_attn_layer_norm, residual, h, observation_mask)
         if encoder_hidden_states is not None:
             residual = h
-            h = self._drop(self.encoder_attn(h, key_value_states=encoder_hidden_states,
-                                             attention_mask=encoder_attention_mask, observation_mask=observation_mask),
-                           self.dropout)
+            h = self._drop(attn(self.encoder_attn, h, key_value_states=encoder_hidden_states,
+                                attention_mask=encoder_attention_mask), self.dropout)
             h = residual_layernorm(self.before_encoder_attn_layer_norm_residual, self.encoder_attn_layer_norm, residual, h, observation_mask)
         residual = h
         if self.training and self.activation_dropout > 0:
@@ -246,8 +423,8 @@ class _BartStack(QuantizedModule):
             self.layer_cls(org_module.layers[i], w_qconfig, a_qconfig, qoutput=(True if i != n - 1 else qoutput),
                            backend=backend) for i in range(n))
 
-    def _embed(self, input_ids, observation_mask):
-        x = self.embed_tokens(input_ids) * self.embed_scale + self.embed_positions(input_ids.shape)
+    def _embed(self, input_ids, observation_mask, past=0):
+        x = self.embed_tokens(input_ids) * self.embed_scale + self.embed_positions(input_ids.shape, past)
         x = self.layernorm_embedding(x, observation_mask)
         return nn.functional.dropout(x, p=self.dropout, training=self.training)
 
@@ -267,20 +444,29 @@ class QuantizedBartDecoder(_BartStack):
     layer_cls = QuantizedBartDecoderLayer
 
     def forward(self, input_ids, attention_mask=None, encoder_hidden_states=None, encoder_attention_mask=None,
-                observation_mask=None):
+                observation_mask=None, past_key_values=None, use_cache=False):
+        """Without ``use_cache`` / ``past_key_values``: the hidden states.  With either: (hidden states, cache), the cache a
+        QuantizedBartCache (``past_key_values`` may also be the reference's tuple of per-layer tensors; positions and the
+        causal mask start after its length, quant_bart.py:774-787) extended by this step.  ``attention_mask`` then covers
+        past + new positions."""
         bsz, tgt_len = input_ids.shape
-        h = self._embed(input_ids, observation_mask)
-        mask = _causal_mask(bsz, tgt_len, h.dtype, h.device) if tgt_len > 1 else None
+        cache = None
+        if use_cache or past_key_values is not None:
+            cache = QuantizedBartCache.wrap(past_key_values, len(self.layers))
+        past = cache.get_seq_length() if cache is not None else 0
+        h = self._embed(input_ids, observation_mask, past)
+        mask = _causal_mask(bsz, tgt_len, h.dtype, h.device, past) if tgt_len > 1 else None
         if attention_mask is not None:
             pad = _expand_mask(attention_mask, h.dtype, tgt_len=tgt_len)
             mask = pad if mask is None else pad + mask
         enc_mask = None
         if encoder_hidden_states is not None and encoder_attention_mask is not None:
             enc_mask = _expand_mask(encoder_attention_mask, h.dtype, tgt_len=tgt_len)
-        for layer in self.layers:
+        for i, layer in enumerate(self.layers):
             h = layer(h, attention_mask=mask, encoder_hidden_states=encoder_hidden_states,
-                      encoder_attention_mask=enc_mask, observation_mask=observation_mask)
-        return h
+                      encoder_attention_mask=enc_mask, observation_mask=observation_mask,
+                      past_key_value=cache.slot(i) if cache is not None else None)
+        return h if cache is None else (h, cache)
 
 
 class QuantizedBartModel(QuantizedModule):
@@ -292,14 +478,29 @@ class QuantizedBartModel(QuantizedModule):
         self.encoder = QuantizedBartEncoder(org_module.encoder, w_qconfig, a_qconfig, qoutput=True, backend=backend)
         self.decoder = QuantizedBartDecoder(org_module.decoder, w_qconfig, a_qconfig, qoutput=qoutput, backend=backend)
 
+    def get_encoder(self):
+        return self.encoder
+
+    def get_decoder(self):
+        return self.decoder
+
     def forward(self, input_ids=None, attention_mask=None, decoder_input_ids=None, decoder_attention_mask=None,
-                observation_mask=None, decoder_observation_mask=None):
+                observation_mask=None, decoder_observation_mask=None, encoder_outputs=None, past_key_values=None,
+                use_cache=False):
+        """(decoder states, encoder states); with ``use_cache`` or ``past_key_values``: (decoder states, cache, encoder
+        states).  ``encoder_outputs``: the encoder states (a tensor, or a tuple / ModelOutput whose first entry they are),
+        which skips the encoder."""
         if decoder_input_ids is None:
             decoder_input_ids = shift_tokens_right(input_ids, self.config.pad_token_id, self.config.decoder_start_token_id)
-        enc = self.encoder(input_ids, attention_mask=attention_mask, observation_mask=observation_mask)
+        if encoder_outputs is None:
+            enc = self.encoder(input_ids, attention_mask=attention_mask, observation_mask=observation_mask)
+        else:
+            enc = encoder_outputs if isinstance(encoder_outputs, torch.Tensor) else encoder_outputs[0]
+        caching = use_cache or past_key_values is not None
         dec = self.decoder(decoder_input_ids, attention_mask=decoder_attention_mask, encoder_hidden_states=enc,
-                           encoder_attention_mask=attention_mask, observation_mask=decoder_observation_mask)
-        return dec, enc
+                           encoder_attention_mask=attention_mask, observation_mask=decoder_observation_mask,
+                           **(dict(past_key_values=past_key_values, use_cache=True) if caching else {}))
+        return (dec[0], dec[1], enc) if caching else (dec, enc)
 
 
 class QuantizedBartForConditionalGeneration(QuantizedModule):
@@ -311,19 +512,67 @@ class QuantizedBartForConditionalGeneration(QuantizedModule):
         self.model = QuantizedBartModel(org_module.model, w_qconfig, a_qconfig, qoutput=True, backend=backend)
         self.lm_head = Quantizer(org_module.lm_head, w_qconfig)
         self.register_buffer("final_logits_bias", org_module.final_logits_bias.clone())
+        self.main_input_name = getattr(org_module, "main_input_name", "input_ids")
+        self.generation_config = getattr(org_module, "generation_config", None)     # generate()'s defaults
+
+    def get_encoder(self):
+        return self.model.get_encoder()
+
+    def get_decoder(self):
+        return self.model.get_decoder()
 
     def forward(self, input_ids=None, attention_mask=None, decoder_input_ids=None, decoder_attention_mask=None,
-                labels=None, **unused):
+                labels=None, encoder_outputs=None, past_key_values=None, use_cache=None, **unused):
+        """(logits, encoder states) -- [loss first with labels].  With ``use_cache=True`` (or ``past_key_values`` given and
+        ``use_cache`` not False): (logits, past_key_values, encoder states), the reference's return_dict=False order; the
+        cache is a QuantizedBartCache.  ``labels`` turn the cache off (quant_bart.py:1076-1082).  Unlike the reference,
+        ``use_cache`` does not default to config.use_cache: a plain call returns what it always did."""
         obs = dec_obs = None
         if self.is_remove_padding:                      # quant_bart.py:1064-1072
             obs = attention_mask.sum(1)
             dec_obs = obs if decoder_attention_mask is None else decoder_attention_mask.sum(1)
-        if labels is not None and decoder_input_ids is None:
-            decoder_input_ids = shift_tokens_right(labels, self.config.pad_token_id, self.config.decoder_start_token_id)
-        dec, enc = self.model(input_ids, attention_mask, decoder_input_ids, decoder_attention_mask,
-                              observation_mask=obs, decoder_observation_mask=dec_obs)
-        logits = self.lm_head(dec) + self.final_logits_bias
-        return with_loss(lm_loss(logits, labels, self.config.vocab_size), (logits, enc))
+        if labels is not None:
+            use_cache = False
+            if decoder_input_ids is None:
+                decoder_input_ids = shift_tokens_right(labels, self.config.pad_token_id, self.config.decoder_start_token_id)
+        caching = use_cache if use_cache is not None else past_key_values is not None
+        out = self.model(input_ids, attention_mask, decoder_input_ids, decoder_attention_mask,
+                         observation_mask=obs, decoder_observation_mask=dec_obs, encoder_outputs=encoder_outputs,
+                         **(dict(past_key_values=past_key_values, use_cache=caching)
+                            if caching or past_key_values is not None else {}))
+        logits = self.lm_head(out[0]) + self.final_logits_bias
+        rest = (out[1], out[2]) if caching else (out[-1],)
+        return with_loss(lm_loss(logits, labels, self.config.vocab_size), (logits,) + rest)
+
+    def prepare_inputs_for_generation(self, decoder_input_ids, past=None, attention_mask=None, head_mask=None,
+                                      decoder_head_mask=None, cross_attn_head_mask=None, use_cache=None,
+                                      encoder_outputs=None, **kwargs):
+        """quant_bart.py:1125-1149: only the last token once a cache exists."""
+        if past is not None:
+            decoder_input_ids = decoder_input_ids[:, -1:]
+        return {"input_ids": None, "encoder_outputs": encoder_outputs, "past_key_values": past,
+                "decoder_input_ids": decoder_input_ids, "attention_mask": attention_mask, "head_mask": head_mask,
+                "decoder_head_mask": decoder_head_mask, "cross_attn_head_mask": cross_attn_head_mask,
+                "use_cache": use_cache}
+
+    def prepare_decoder_input_ids_from_labels(self, labels):
+        return shift_tokens_right(labels, self.config.pad_token_id, self.config.decoder_start_token_id)
+
+    @staticmethod
+    def _reorder_cache(past, beam_idx):
+        """quant_bart.py:1155-1164: the self-attention rows follow beam_idx, the cross-attention entries stay.  A
+        QuantizedBartCache records the index and applies it in its next append (returned as it is)."""
+        if isinstance(past, QuantizedBartCache):
+            return past.reorder(beam_idx)
+        return tuple(tuple(s.index_select(0, beam_idx) for s in layer[:2]) + tuple(layer[2:]) for layer in past)
+
+    @torch.no_grad()
+    def generate(self, input_ids, attention_mask=None, max_length=None, num_beams=None, **kwargs):
+        """Greedy or beam-search decoding with a KV cache (model/generation.py): token ids [B * num_return_sequences, L]
+        padded with pad_token_id, as transformers' generate returns them.  Defaults come from the wrapped model's
+        generation_config / config."""
+        return generation.generate(self, input_ids, attention_mask=attention_mask, max_length=max_length,
+                                   num_beams=num_beams, **kwargs)
 
 
 class QuantizedBartClassificationHead(QuantizedModule):

@@ -1382,6 +1382,64 @@ def fake_quant_headsplit_multi(xs, params, heads):
     return ys
 
 
+def fake_quant_kv_append(sites, heads):
+    """One decoder step's attention sites as ONE launch (osq_fake_quant_kv_append).  ``sites``: 1..4 tuples
+    ``(x, y, offset, params, src, src_rows)`` of one batch size B:
+
+    * x -- the step's contiguous [B, t, heads * d] fp32 projection (t may differ between sites);
+    * y -- a dense [B, heads, cap, d] buffer; ``y[:, :, offset:offset + t]`` receives the head-split fake-quant of x, the
+      bits of ``fake_quant_per_tensor`` on ``x.view(B, t, heads, d).transpose(1, 2)``;
+    * params -- (scale, zero_point, quant_min, quant_max, mode, grad_factor) of the site;
+    * src / src_rows -- None, or a [B', heads, S', d] tensor whose last two dimensions are dense (a ``[:, :, :S']`` view of
+      a cache buffer is) with S' >= offset, and None or an int64 device index of length B: ``y[:, :, :offset] =
+      src.index_select(0, src_rows)[:, :, :offset]`` in the same launch.  ``src`` being ``y`` without an index copies
+      nothing (in-place append).
+
+    Returns the list of y, or None when the kernel does not take the geometry (nothing was launched)."""
+    lib = _hip.load()
+    n = len(sites)
+    if not 1 <= n <= 4:
+        raise ValueError("fake_quant_kv_append: 1..4 sites")
+    b = sites[0][0].shape[0]
+    d = sites[0][1].shape[-1]
+    table = (_hip.KvAppendSite * n)()
+    for i, (x, y, offset, (scale, zero_point, quant_min, quant_max, mode, grad_factor), src, rows) in enumerate(sites):
+        _hip.require_device(x, y, scale, zero_point)
+        _check_f32(x, y, scale)
+        t = x.shape[1]
+        if (x.dim() != 3 or x.shape[0] != b or x.shape[2] != heads * d or not x.is_contiguous() or y.dim() != 4
+                or tuple(y.shape[:2]) != (b, heads) or y.shape[3] != d or not y.is_contiguous()):
+            raise ValueError("fake_quant_kv_append: x must be [B, t, heads*d] and y [B, heads, cap, d], both contiguous")
+        if not 0 <= offset or offset + t > y.shape[2]:
+            raise ValueError(f"fake_quant_kv_append: offset {offset} + {t} tokens exceeds the capacity {y.shape[2]}")
+        e = table[i]
+        e.x, e.y, e.scale, e.zero_point = x.data_ptr(), y.data_ptr(), scale.data_ptr(), zero_point.data_ptr()
+        e.tokens, e.cap, e.offset = t, y.shape[2], int(offset)
+        if src is not None and offset > 0:
+            _hip.require_device(src)
+            _check_f32(src)
+            if src.dim() != 4 or src.shape[1] != heads or src.shape[3] != d or src.shape[2] < offset:
+                raise ValueError("fake_quant_kv_append: src must be [B', heads, S' >= offset, d]")
+            st = src.stride()
+            if st[3] != 1 or st[2] != d or st[1] % d or st[1] // d < src.shape[2] or st[0] != heads * st[1]:
+                return None
+            e.src, e.src_batch, e.src_cap = src.data_ptr(), src.shape[0], st[1] // d
+            if rows is not None:
+                _hip.require_device(rows)
+                if rows.dtype != torch.int64 or rows.dim() != 1 or rows.shape[0] != b or not rows.is_contiguous():
+                    raise ValueError("fake_quant_kv_append: src_rows must be a contiguous int64 [B] device tensor")
+                e.src_rows = rows.data_ptr()
+            elif src.shape[0] != b:
+                raise ValueError("fake_quant_kv_append: src batch differs from B and no src_rows given")
+        e.zp_type, e.mode, e.grad_factor = _zp_type(zero_point), int(mode), float(grad_factor)
+        e.quant_min, e.quant_max = int(quant_min), int(quant_max)
+    rc = lib.osq_fake_quant_kv_append(table, n, b, heads, d, _hip.stream_ptr(sites[0][0].device))
+    if rc == _hip.ERR_UNSUPPORTED:
+        return None
+    _hip.check(rc, "fake_quant_kv_append")
+    return [site[1] for site in sites]
+
+
 def gelu_fake_quant_per_tensor(x, scale, zero_point, quant_min, quant_max, mode=PARAM_FIXED, grad_factor=1.0):
     """fake_quant(F.gelu(x)) in ONE launch; x dense fp32 on the device."""
     lib = _hip.load()

@@ -41,6 +41,7 @@ FUSE_LAYERNORM = True
 FUSE_ACTIVATION = True
 FUSE_QKV = True          # the query / key / value head-split sites of a self-attention block as one launch (bit-identical)
 FUSE_SOFTMAX = False     # the attention-probabilities site as one launch (tolerance-equal; set_fast_softmax / OSQ_FAST_SOFTMAX=1)
+FUSE_KV_APPEND = True    # incremental decoding: a step's q / k / v sites + KV-cache append (+ beam reorder) as one launch (bit-identical)
 
 
 def _fused_site(mod, x, hidden, gamma, weight, bias, eps, observation_mask):
@@ -243,6 +244,30 @@ def qkv_heads_fake_quant(quantizers, projections, heads):
         params.append((q.scale.data, q.zero_point.data, q.quant_min, q.quant_max, mode,
                        q._grad_factor(x) if q.param_mode != ops.PARAM_FIXED else 1.0))
     return ops.fake_quant_headsplit_multi(list(projections), params, heads)
+
+
+def kv_append_fake_quant(sites, heads):
+    """Incremental decoding (model/quant_bart.py, QuantizedBartCache): the activation quantizers of one attention block's
+    step, each site ``(quantizer, x, y, offset, src, src_rows)``, as ONE launch (ops.fake_quant_kv_append): site i writes
+    the head-split fake-quant of its [B, t, h*d] projection x at positions [offset, offset + t) of the [B, h, cap, d]
+    buffer y, after copying ``src.index_select(0, src_rows)[:, :, :offset]`` (or ``src[:, :, :offset]``) in front of it.
+    The cache contents are word for word what ``torch.cat([past.index_select(0, idx), split_heads(quantizer(x))], 2)``
+    gives.  Only when every quantizer is in its plain quantising state (as qkv_heads_fake_quant); returns the list of y,
+    or None (nothing launched): the caller then runs the eager form."""
+    if not FUSE_KV_APPEND:
+        return None
+    for q, x, *_ in sites:
+        if not (_plain_quantizing(q, x) and x.dim() == 3 and x.is_contiguous() and x.data_ptr() % 16 == 0):
+            return None
+    table = []
+    for q, x, y, offset, src, rows in sites:
+        mode = q.param_mode
+        if isinstance(q, _LearnableFakeQuantize):
+            mode |= ops.PARAM_SANITIZE
+            q._touch_qparams()
+        table.append((x, y, offset, (q.scale.data, q.zero_point.data, q.quant_min, q.quant_max, mode,
+                                     q._grad_factor(x) if q.param_mode != ops.PARAM_FIXED else 1.0), src, rows))
+    return ops.fake_quant_kv_append(table, heads)
 
 
 def _dropout_active(dropout):

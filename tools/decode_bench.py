@@ -1,0 +1,133 @@
+"""Decoder-step A/B of incremental decoding: the one-launch q/k/v + KV-cache append (util_layernorm.FUSE_KV_APPEND) against
+the eager form (quantizer, head split, index_select, torch.cat).
+
+BART-large shape, random init (d_model 1024, 12 + 12 layers, 16 heads, vocab 50265), W6A6 in the plain quantising state,
+batch 32 x 6 beams, source 512.  Times one decoder step (all 12 layers + lm_head, a beam reorder pending as in beam
+search) at past length S = 1, 31, 62, median and spread of --reps runs, and the whole generate(max_length=62, num_beams=6).
+--profile-steps N only runs N cached decode steps (for ``rocprofv3 --kernel-trace --stats``: launches per step).
+
+    python tools/decode_bench.py [--reps 7] [--out profiles/decode_step_ab.txt]
+"""
+import argparse
+import copy
+import os
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def build(batch, src_len, layers):
+    from types import SimpleNamespace as NS
+    from transformers import BartConfig, BartForConditionalGeneration
+    from outlier_suppression_amd import util_layernorm as UL
+    from outlier_suppression_amd.quant_model import quantize_model
+    from outlier_suppression_amd.quantization import disable_all, enable_calibration_woquantization, enable_quantization
+    torch.manual_seed(0)
+    cfg = BartConfig(vocab_size=50265, d_model=1024, encoder_layers=layers, decoder_layers=layers, encoder_attention_heads=16,
+                     decoder_attention_heads=16, encoder_ffn_dim=4096, decoder_ffn_dim=4096, max_position_embeddings=1024,
+                     dropout=0.0, attention_dropout=0.0, activation_dropout=0.0)
+    fp = BartForConditionalGeneration(cfg).eval()
+    w = NS(quantizer="FixedFakeQuantize", observer="MinMaxObserver", bit=6, symmetric=True, ch_axis=0)
+    a = NS(quantizer="LSQPlusFakeQuantize", observer="AvgMinMaxObserver", bit=6, symmetric=False, ch_axis=-1)
+    dev = torch.device("cuda:0")
+    q = quantize_model(copy.deepcopy(fp), w, a).to(dev).eval()
+    del fp
+    ids = torch.randint(3, 50265, (batch, src_len), device=dev)
+    mask = torch.ones_like(ids)
+    enable_calibration_woquantization(q)
+    with torch.no_grad():
+        q(ids[:2, :64], mask[:2, :64], decoder_input_ids=ids[:2, :8])
+    disable_all(q)
+    enable_quantization(q)
+    assert UL.FUSE_KV_APPEND
+    return q, ids, mask
+
+
+def step_times(q, ids, mask, beams, past, reps, fused):
+    """Median / min / max (ms) of one decoder step at past length `past` with a pending beam reorder."""
+    from outlier_suppression_amd import util_layernorm as UL
+    UL.FUSE_KV_APPEND = fused
+    dev = ids.device
+    bb = ids.shape[0] * beams
+    try:
+        with torch.no_grad():
+            enc = q.get_encoder()(ids, attention_mask=mask).repeat_interleave(beams, 0)
+            m = mask.repeat_interleave(beams, 0)
+            tok = torch.randint(3, 50265, (bb, past + 1), device=dev)
+            _, cache, _ = q(attention_mask=m, decoder_input_ids=tok[:, :past], encoder_outputs=(enc,), use_cache=True)
+            perm = torch.randperm(bb, device=dev)
+            lens = list(cache._len)
+            times = []
+            for r in range(reps + 2):
+                cache._len = list(lens)
+                cache.reorder(perm)
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                q(attention_mask=m, decoder_input_ids=tok[:, past:past + 1], encoder_outputs=(enc,), past_key_values=cache,
+                  use_cache=True)
+                torch.cuda.synchronize()
+                if r >= 2:
+                    times.append((time.perf_counter() - t0) * 1e3)
+    finally:
+        UL.FUSE_KV_APPEND = True
+    times.sort()
+    return times[len(times) // 2], times[0], times[-1]
+
+
+def generate_time(q, ids, mask, fused):
+    from outlier_suppression_amd import util_layernorm as UL
+    UL.FUSE_KV_APPEND = fused
+    try:
+        with torch.no_grad():
+            q.generate(ids[:2], attention_mask=mask[:2], max_length=4, num_beams=6, min_length=4)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            out = q.generate(ids, attention_mask=mask, max_length=62, num_beams=6, min_length=62)
+            torch.cuda.synchronize()
+            return time.perf_counter() - t0, tuple(out.shape)
+    finally:
+        UL.FUSE_KV_APPEND = True
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=32)
+    ap.add_argument("--beams", type=int, default=6)
+    ap.add_argument("--src", type=int, default=512)
+    ap.add_argument("--layers", type=int, default=12)
+    ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--profile-steps", type=int, default=0)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    q, ids, mask = build(args.batch, args.src, args.layers)
+    if args.profile_steps:
+        with torch.no_grad():
+            q.generate(ids, attention_mask=mask, max_length=args.profile_steps + 1, num_beams=args.beams,
+                       min_length=args.profile_steps + 1)
+        torch.cuda.synchronize()
+        return
+    lines = [f"decoder step, BART-large shape (random init, {args.layers}+{args.layers} layers), W6A6 LSQ+ plain quantising, "
+             f"batch {args.batch} x {args.beams} beams, source {args.src}; a beam reorder pending before every step; "
+             f"{args.reps} runs each, ms: median [min, max]"]
+    for past in (1, 31, 62):
+        row = []
+        for fused in (True, False):
+            med, lo, hi = step_times(q, ids, mask, args.beams, past, args.reps, fused)
+            row.append(f"{'one-launch' if fused else 'eager'} {med:.3f} [{lo:.3f}, {hi:.3f}]")
+        lines.append(f"S = {past:2d}: " + "   ".join(row))
+    for fused in (True, False):
+        secs, shape = generate_time(q, ids, mask, fused)
+        lines.append(f"generate(max_length=62, num_beams=6, min_length=62) {'one-launch' if fused else 'eager'}: "
+                     f"{secs:.2f} s, output {shape}")
+    text = "\n".join(lines)
+    print(text)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(text + "\n")
+
+
+if __name__ == "__main__":
+    main()
