@@ -11,7 +11,9 @@ autograd (every calibration / evaluation forward):
   * ``FUSE_LAYERNORM`` (default ON since round 5): a LayerNorm site -- residual (GammaResidual), normalisation, affine pair
     or beta/gamma shift, output fake-quant -- as ONE launch (``ops.residual_layernorm_fake_quant``: 52 us
     instead of 168 us on [256,128,768], 14-19 against 25-38 us at [32,128,768]).  Its row moments are two-pass sums in a
-    wave, torch-ROCm's LayerNorm kernel is Welford: the two agree to 2e-6, and NEITHER is bit-comparable with the
+    wave, torch-ROCm's LayerNorm kernel is Welford: against float64 both carry an error proportional to the row's
+    condition number kappa = 1 + |mean|/sigma (2-3e-7 x kappa of the output's magnitude, as torch's CPU kernel does:
+    tests/test_gpu_site_accuracy.py, profiles/site_accuracy.txt), and NEITHER is bit-comparable with the
     reference's CPU LayerNorm.  Against the reference's own run at BERT-base width (tests/golden/ln_site.npz,
     tests/test_gpu_ln_site.py, profiles/r05_ln_site_parity.txt) the one-launch site is no further away than the eager
     one: max |LayerNorm output - reference| 2.3e-5 / 5.7e-6 / 3.1e-5 against 2.3e-5 / 5.7e-6 / 2.3e-5 on values up to
