@@ -262,7 +262,8 @@ int osq_lsq_backward_per_tensor_ordered(const float* x, const float* grad_out, f
 
 /* Per-channel form (util_quant.py:58-67), x viewed as [outer, channels, inner].  sum_lanes 8 | 16: weights
  * (outer == 1, inner <= 3072) take every row's four reductions in torch's one-thread order on that many SIMD lanes (bit-equal to
- * the reference's autograd run); 0 (and every other layout): float64 sums rounded once. */
+ * the reference's autograd run); 0 (and every other layout): float64 sums rounded once.  An empty x (outer, channels or inner 0)
+ * launches nothing and sets the `channels` gradients to zero. */
 int osq_lsq_backward_per_channel(const float* x, const float* grad_out, float* grad_x,
                                  int64_t outer, int64_t channels, int64_t inner,
                                  const float* scale, const void* zero_point, int zp_type,

@@ -1101,10 +1101,18 @@ extern "C" int osq_lsq_backward_per_channel(const float* x, const float* grad_ou
                                             int sum_lanes, osq_stream stream) {
     OSQ_REQUIRE(outer >= 0 && channels >= 0 && inner >= 0 && scale && zero_point, "lsq_backward_per_channel: bad argument");
     OSQ_REQUIRE(sum_lanes == 0 || sum_lanes == 8 || sum_lanes == 16, "lsq_backward_per_channel: sum_lanes must be 0, 8 or 16");
-    if (outer * channels * inner == 0) return OSQ_OK;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (outer * channels * inner == 0) {                 // nothing to sum: every channel's gradients are zeros, not left unwritten
+        const size_t bytes = static_cast<size_t>(channels) * sizeof(float);
+        if (channels > 0 && ((grad_scale && hipMemsetAsync(grad_scale, 0, bytes, st) != hipSuccess) ||
+                             (grad_zero_point && hipMemsetAsync(grad_zero_point, 0, bytes, st) != hipSuccess))) {
+            osq::set_error("lsq_backward_per_channel: clearing the gradients of an empty tensor failed");
+            return OSQ_ERR_HIP;
+        }
+        return OSQ_OK;
+    }
     OSQ_REQUIRE(x && grad_out && grad_x, "lsq_backward_per_channel: null tensor");
     OSQ_REQUIRE(channels < (1ll << 31), "lsq_backward_per_channel: too many channels");
-    hipStream_t st = static_cast<hipStream_t>(stream);
     if (sum_lanes && outer == 1 && inner <= 3072) {      // strict switch: weight rows in the reference's order (4 x inner floats of LDS)
         static_assert(kThreads / OSQ_WAVE == 4, "one wave per term");
         hipLaunchKernelGGL(lsq_bwd_channel_ordered_kernel, dim3(static_cast<unsigned>(channels)), dim3(kThreads),

@@ -196,6 +196,11 @@ def lsq_backward_per_channel(x, grad_out, scale, zero_point, ch_axis, quant_min,
     g = grad_out.contiguous()
     outer, channels, inner = _channel_split(x, ch_axis)
     dx = torch.empty_like(x)
+    if x.numel() == 0:
+        # nothing to launch (and no channel may mean no parameter storage): the sums over no elements are zeros, as
+        # autograd's sum_to_size gives them -- not whatever an uninitialised allocation holds
+        zeros = lambda: torch.zeros(channels, dtype=torch.float32, device=x.device)   # noqa: E731
+        return dx, (zeros() if need_scale else None), (zeros() if need_zp else None)
     ds = torch.empty(channels, dtype=torch.float32, device=x.device) if need_scale else None
     dz = torch.empty(channels, dtype=torch.float32, device=x.device) if need_zp else None
     _hip.check(lib.osq_lsq_backward_per_channel(_hip.ptr(x), _hip.ptr(g), _hip.ptr(dx), outer, channels, inner,

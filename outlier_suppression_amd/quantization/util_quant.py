@@ -51,6 +51,15 @@ def _learnable_params(x, scale, zero_point):
         raise NotImplementedError("bf16 / fp16 learnable fake-quant takes [1] / [C] tensor parameters (the quantizers' own)")
 
 
+def _channel_axis(x, ch_axis):
+    """The reference indexes ``x.shape[ch_axis]`` (util_quant.py:20,39,61): a negative axis counts from the end.  ops.fake_quant
+    keeps -1 for "per-tensor", so the per-channel functions hand it the axis counted from the front."""
+    ch_axis = int(ch_axis)
+    if not -x.dim() <= ch_axis < x.dim():
+        raise IndexError(f"ch_axis {ch_axis} is out of range for a tensor of {x.dim()} dimensions")
+    return ch_axis % x.dim()
+
+
 def fake_quantize_per_tensor_affine(x, scale, zero_point, quant_min, quant_max):
     """util_quant.py:11-15."""
     scalar = _scalar(scale) and _scalar(zero_point)
@@ -60,7 +69,7 @@ def fake_quantize_per_tensor_affine(x, scale, zero_point, quant_min, quant_max):
 
 def fake_quantize_per_channel_affine(x, scale, zero_point, ch_axis, quant_min, quant_max):
     """util_quant.py:18-26."""
-    return ops.fake_quant(x, _as_scale(scale, x), _as_zero_point(zero_point, x), ch_axis, quant_min, quant_max, PARAM_FIXED)
+    return ops.fake_quant(x, _as_scale(scale, x), _as_zero_point(zero_point, x), _channel_axis(x, ch_axis), quant_min, quant_max, PARAM_FIXED)
 
 
 def fake_quantize_learnable_per_tensor_affine_training(x, scale, zero_point, quant_min, quant_max, grad_factor):
@@ -73,7 +82,7 @@ def fake_quantize_learnable_per_tensor_affine_training(x, scale, zero_point, qua
 def fake_quantize_learnable_per_channel_affine_training(x, scale, zero_point, ch_axis, quant_min, quant_max, grad_factor):
     """util_quant.py:37-45 (LSQ)."""
     _learnable_params(x, scale, zero_point)
-    return ops.fake_quant(x, _as_scale(scale, x), _as_zero_point(zero_point, x), ch_axis, quant_min, quant_max,
+    return ops.fake_quant(x, _as_scale(scale, x), _as_zero_point(zero_point, x), _channel_axis(x, ch_axis), quant_min, quant_max,
                           PARAM_LSQ, grad_factor)
 
 
@@ -88,5 +97,5 @@ def fake_quantize_learnableplus_per_channel_affine_training(x, scale, zero_point
                                                             grad_factor):
     """util_quant.py:58-67 (LSQ+)."""
     _learnable_params(x, scale, zero_point)
-    return ops.fake_quant(x, _as_scale(scale, x), _as_zero_point(zero_point, x, True), ch_axis, quant_min, quant_max,
+    return ops.fake_quant(x, _as_scale(scale, x), _as_zero_point(zero_point, x, True), _channel_axis(x, ch_axis), quant_min, quant_max,
                           PARAM_LSQPLUS, grad_factor)
