@@ -679,7 +679,7 @@ int osq_attention_softmax_fake_quant(const float* scores, const float* mask, int
                                      int mode, float grad_factor, int quant_min, int quant_max,
                                      osq_stream stream);
 
-/* ------------------------------------------------------------------ bf16 / fp16 inputs (lowp.hip) */
+/* ------------------------------------------------------------------ bf16 / fp16 inputs (lowp.hip, observer.hip, fake_quant.hip) */
 
 /* Element type of the `const void*` / `void*` data of the entry points below; any other value is rejected (-1). */
 typedef enum osq_dtype { OSQ_DTYPE_BF16 = 1, OSQ_DTYPE_F16 = 2 } osq_dtype;

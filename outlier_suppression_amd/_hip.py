@@ -24,7 +24,7 @@ TIME_LAYERNORM, TIME_FUSED_STEP = 6, 7
 TIME_FAKE_QUANT_STRIDED, TIME_FAKE_QUANT_CHANNEL, TIME_OBSERVE_CHANNELS, TIME_TOKEN_MINMAX_MULTI, TIME_MSEFAST_ROWS = 8, 9, 10, 11, 12
 TIME_OBSERVE_TOKENS, TIME_ATTENTION_SOFTMAX = 13, 14
 UPDATE_NONE, UPDATE_RUNNING, UPDATE_AVERAGE = 0, 1, 2
-DTYPE_BF16, DTYPE_F16 = 1, 2   # osq_dtype: element type of the bf16 / fp16 entry points (lowp.hip)
+DTYPE_BF16, DTYPE_F16 = 1, 2   # osq_dtype: element type of the bf16 / fp16 entry points (lowp.hip, observer.hip, fake_quant.hip)
 ERR_UNSUPPORTED = -3          # OSQ_ERR_UNSUPPORTED: nothing was launched, the caller takes its other path
 ABI_VERSION = 9               # OSQ_ABI_VERSION of include/osq_hip.h this file was written against
 

@@ -7,6 +7,7 @@
 // grid sized to a few waves per SIMD and grid-strided above that.
 #include <algorithm>
 #include <string>
+#include <type_traits>
 #include <hip/hip_ext.h>
 #include "osq_device.h"
 #include "aten_order.h"
@@ -15,7 +16,7 @@
 namespace osq {
 
 constexpr int kThreads = 256;
-constexpr int kUnroll = 4;   // float4 loads in flight per lane (per-channel kernel)
+constexpr int kUnroll = 4;   // float4 loads in flight per lane (the many-weights kernel; per-channel rows: Granule<T>::kRowLoads)
 
 // tuning knobs of the dense per-tensor kernel (osq_set_tuning): loads in flight per lane, grid cap, and
 // whether loads / stores carry the non-temporal hint
@@ -341,49 +342,53 @@ __global__ __launch_bounds__(kThreads) void fq_kv_append_kernel(KvAppendSites s,
 
 // ---------------------------------------------------------------- per-channel
 
-// [rows = outer*channels, inner] with inner % 4 == 0: one wave walks whole rows, the
-// row's (scale, zero_point) is wave-uniform.  Weights [C_out, C_in], ch_axis = 0.
-template <bool WRITE_Q>
+// [rows = outer*channels, inner] with inner a whole number of 16-byte granules of T: one wave walks whole rows, the
+// row's (scale, zero_point) is wave-uniform.  Weights [C_out, C_in], ch_axis = 0.  T = __bf16 / _Float16 is widened
+// exactly and then takes the fp32 arithmetic; the outputs are fp32 for every T (WRITE_Q: T = float only).
+template <typename T, bool WRITE_Q>
 __global__ __launch_bounds__(kThreads) void fq_channel_rows_kernel(
-    const float4* __restrict__ x, float4* __restrict__ y, float4* __restrict__ xq,
-    int64_t rows, int64_t channels, int inner4,
+    const typename Granule<T>::V* __restrict__ x, float4* __restrict__ y, float4* __restrict__ xq,
+    int64_t rows, int64_t channels, int inner_g,
     const float* __restrict__ scale_p, const void* __restrict__ zp_p, int zp_type, int mode, float g,
     float qmin, float qmax) {
+    typedef Granule<T> G;
     const int lane = threadIdx.x & (OSQ_WAVE - 1);
     const int64_t wave = (static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x) / OSQ_WAVE;
     const int64_t nwaves = static_cast<int64_t>(gridDim.x) * (kThreads / OSQ_WAVE);
     for (int64_t r = wave; r < rows; r += nwaves) {
         const int64_t c = r % channels;
         const QParams p = effective_params(scale_p[c], load_zp(zp_p, zp_type, c), mode, g);
-        const float4* xr = x + r * inner4;
-        float4* yr = y + r * inner4;
-        float4* qr = WRITE_Q ? xq + r * inner4 : nullptr;
-        int j = lane;
-        for (; j + (kUnroll - 1) * OSQ_WAVE < inner4; j += kUnroll * OSQ_WAVE) {
-            float4 v[kUnroll];
+        const typename G::V* xr = x + r * inner_g;
+        float4* yr = y + G::kWide * r * inner_g;
+        float4* qr = WRITE_Q ? xq + G::kWide * r * inner_g : nullptr;
+        // granule j of the row: its widened float4s through the chain, to float4s G::kWide * j ... of the outputs
+        const auto fq_granule = [&](const typename G::V& v, const int j) {
+            float4 w[G::kWide];
+            G::widen(v, w);
 #pragma unroll
-            for (int u = 0; u < kUnroll; ++u) v[u] = xr[j + u * OSQ_WAVE];
-#pragma unroll
-            for (int u = 0; u < kUnroll; ++u) {
+            for (int k = 0; k < G::kWide; ++k) {
                 float4 o, q;
-                fq4<WRITE_Q>(v[u], o, q, p.scale, p.zp, qmin, qmax);
-                yr[j + u * OSQ_WAVE] = o;
-                if (WRITE_Q) qr[j + u * OSQ_WAVE] = q;
+                fq4<WRITE_Q>(w[k], o, q, p.scale, p.zp, qmin, qmax);
+                yr[G::kWide * j + k] = o;
+                if (WRITE_Q) qr[G::kWide * j + k] = q;
             }
+        };
+        int j = lane;
+        for (; j + (G::kRowLoads - 1) * OSQ_WAVE < inner_g; j += G::kRowLoads * OSQ_WAVE) {
+            typename G::V v[G::kRowLoads];
+#pragma unroll
+            for (int u = 0; u < G::kRowLoads; ++u) v[u] = G::load(&xr[j + u * OSQ_WAVE]);
+#pragma unroll
+            for (int u = 0; u < G::kRowLoads; ++u) fq_granule(v[u], j + u * OSQ_WAVE);
         }
-        for (; j < inner4; j += OSQ_WAVE) {
-            float4 o, q;
-            fq4<WRITE_Q>(xr[j], o, q, p.scale, p.zp, qmin, qmax);
-            yr[j] = o;
-            if (WRITE_Q) qr[j] = q;
-        }
+        for (; j < inner_g; j += OSQ_WAVE) fq_granule(G::load(&xr[j]), j);
     }
 }
 
 // generic [outer, channels, inner]: channel = (i / inner) % channels per element
-template <bool WRITE_Q>
+template <typename T, bool WRITE_Q>
 __global__ __launch_bounds__(kThreads) void fq_channel_generic_kernel(
-    const float* __restrict__ x, float* __restrict__ y, float* __restrict__ xq, int64_t n,
+    const T* __restrict__ x, float* __restrict__ y, float* __restrict__ xq, int64_t n,
     int64_t channels, int64_t inner,
     const float* __restrict__ scale_p, const void* __restrict__ zp_p, int zp_type, int mode, float g,
     float qmin, float qmax) {
@@ -391,7 +396,7 @@ __global__ __launch_bounds__(kThreads) void fq_channel_generic_kernel(
     for (int64_t i = static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x; i < n; i += stride) {
         const int64_t c = (i / inner) % channels;
         const QParams p = effective_params(scale_p[c], load_zp(zp_p, zp_type, c), mode, g);
-        const float q = quantize_value(x[i], p.scale, p.zp, qmin, qmax);
+        const float q = quantize_value(static_cast<float>(x[i]), p.scale, p.zp, qmin, qmax);
         y[i] = dequantize_value(q, p.scale, p.zp);
         if (WRITE_Q) xq[i] = q;
     }
@@ -747,13 +752,6 @@ static inline MagicDiv make_magic(int64_t d) {       // 1 <= d < 2^31
     return v;
 }
 
-static inline int grid_for(int64_t work_items, int per_block, int max_blocks) {
-    int64_t b = (work_items + per_block - 1) / per_block;
-    if (b < 1) b = 1;
-    if (b > max_blocks) b = max_blocks;
-    return static_cast<int>(b);
-}
-
 }  // namespace osq
 
 using namespace osq;
@@ -1010,41 +1008,72 @@ extern "C" int osq_fake_quant_kv_append(const osq_kv_append_site* sites, int n_s
     return check_launch("fake_quant_kv_append");
 }
 
+// per-channel launch: T = float behind osq_fake_quant_per_channel (x_quant optional), __bf16 / _Float16 behind the
+// widening entry point (x_quant == nullptr); y is fp32 for every T
+template <typename T>
+static void launch_fq_channel(const T* x, float* y, float* x_quant, int64_t outer, int64_t channels, int64_t inner,
+                              const float* scale, const void* zero_point, int zp_type, int mode, float grad_factor, int quant_min,
+                              int quant_max, hipStream_t st) {
+    typedef Granule<T> G;
+    const float qmin = static_cast<float>(quant_min), qmax = static_cast<float>(quant_max);
+    const bool aligned = aligned16(x) && aligned16(y) && (!x_quant || aligned16(x_quant));
+    if (aligned && inner % G::kPer == 0 && inner >= 64 && inner / G::kPer < (1 << 30)) {
+        const int64_t rows = outer * channels;
+        const int grid = grid_for(rows, kThreads / OSQ_WAVE, kMaxBlocks * 2);
+        const typename G::V* xg = reinterpret_cast<const typename G::V*>(x);
+        float4* y4 = reinterpret_cast<float4*>(y);
+        float4* q4 = reinterpret_cast<float4*>(x_quant);
+        const int inner_g = static_cast<int>(inner / G::kPer);
+        const TimingHook th = take_timing_hook(OSQ_TIME_FAKE_QUANT_CHANNEL);
+        if constexpr (std::is_same<T, float>::value) {      // WRITE_Q is fp32-only
+            if (x_quant) {
+                hipExtLaunchKernelGGL((fq_channel_rows_kernel<T, true>), dim3(grid), dim3(kThreads), 0, st, th.start, th.stop, 0, xg,
+                                      y4, q4, rows, channels, inner_g, scale, zero_point, zp_type, mode, grad_factor, qmin, qmax);
+                return;
+            }
+        }
+        hipExtLaunchKernelGGL((fq_channel_rows_kernel<T, false>), dim3(grid), dim3(kThreads), 0, st, th.start, th.stop, 0, xg, y4,
+                              q4, rows, channels, inner_g, scale, zero_point, zp_type, mode, grad_factor, qmin, qmax);
+    } else {
+        const int64_t n = outer * channels * inner;
+        const int grid = grid_for(n, kThreads);
+        if constexpr (std::is_same<T, float>::value) {
+            if (x_quant) {
+                hipLaunchKernelGGL((fq_channel_generic_kernel<T, true>), dim3(grid), dim3(kThreads), 0, st, x, y, x_quant, n,
+                                   channels, inner, scale, zero_point, zp_type, mode, grad_factor, qmin, qmax);
+                return;
+            }
+        }
+        hipLaunchKernelGGL((fq_channel_generic_kernel<T, false>), dim3(grid), dim3(kThreads), 0, st, x, y, x_quant, n, channels,
+                           inner, scale, zero_point, zp_type, mode, grad_factor, qmin, qmax);
+    }
+}
+
 extern "C" int osq_fake_quant_per_channel(const float* x, float* y, float* x_quant,
                                           int64_t outer, int64_t channels, int64_t inner,
                                           const float* scale, const void* zero_point, int zp_type,
                                           int mode, float grad_factor, int quant_min, int quant_max,
                                           osq_stream stream) {
     OSQ_REQUIRE(outer >= 0 && channels >= 0 && inner >= 0 && scale && zero_point, "fake_quant_per_channel: bad argument");
-    const int64_t n = outer * channels * inner;
-    if (n == 0) return OSQ_OK;
+    if (outer * channels * inner == 0) return OSQ_OK;
     OSQ_REQUIRE(x && y, "fake_quant_per_channel: null tensor");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const float qmin = static_cast<float>(quant_min), qmax = static_cast<float>(quant_max);
-    const bool aligned = aligned16(x) && aligned16(y) && (!x_quant || aligned16(x_quant));
-    if (aligned && inner % 4 == 0 && inner >= 64 && inner / 4 < (1 << 30)) {
-        const int64_t rows = outer * channels;
-        const int grid = grid_for(rows, kThreads / OSQ_WAVE, kMaxBlocks * 2);
-        const float4* x4 = reinterpret_cast<const float4*>(x);
-        float4* y4 = reinterpret_cast<float4*>(y);
-        float4* q4 = reinterpret_cast<float4*>(x_quant);
-        const TimingHook th = take_timing_hook(OSQ_TIME_FAKE_QUANT_CHANNEL);
-        if (x_quant)
-            hipExtLaunchKernelGGL(fq_channel_rows_kernel<true>, dim3(grid), dim3(kThreads), 0, st, th.start, th.stop, 0, x4, y4, q4, rows,
-                                  channels, static_cast<int>(inner / 4), scale, zero_point, zp_type, mode, grad_factor, qmin, qmax);
-        else
-            hipExtLaunchKernelGGL(fq_channel_rows_kernel<false>, dim3(grid), dim3(kThreads), 0, st, th.start, th.stop, 0, x4, y4, q4, rows,
-                                  channels, static_cast<int>(inner / 4), scale, zero_point, zp_type, mode, grad_factor, qmin, qmax);
-    } else {
-        const int grid = grid_for(n, kThreads, kMaxBlocks);
-        if (x_quant)
-            hipLaunchKernelGGL(fq_channel_generic_kernel<true>, dim3(grid), dim3(kThreads), 0, st, x, y, x_quant, n, channels,
-                               inner, scale, zero_point, zp_type, mode, grad_factor, qmin, qmax);
-        else
-            hipLaunchKernelGGL(fq_channel_generic_kernel<false>, dim3(grid), dim3(kThreads), 0, st, x, y, x_quant, n, channels,
-                               inner, scale, zero_point, zp_type, mode, grad_factor, qmin, qmax);
-    }
+    launch_fq_channel(x, y, x_quant, outer, channels, inner, scale, zero_point, zp_type, mode, grad_factor, quant_min, quant_max,
+                      static_cast<hipStream_t>(stream));
     return check_launch("fake_quant_per_channel");
+}
+
+extern "C" int osq_fake_quant_per_channel_widen(int dtype, const void* x, float* y, int64_t outer, int64_t channels, int64_t inner,
+                                                const float* scale, const void* zero_point, int zp_type, int mode,
+                                                float grad_factor, int quant_min, int quant_max, osq_stream stream) {
+    OSQ_REQUIRE(known_dtype(dtype), "fake_quant_per_channel_widen: unknown dtype");
+    OSQ_REQUIRE(outer >= 0 && channels >= 0 && inner >= 0 && scale && zero_point, "fake_quant_per_channel_widen: bad argument");
+    OSQ_REQUIRE(zp_type == OSQ_ZP_INT32 || zp_type == OSQ_ZP_FLOAT32, "fake_quant_per_channel_widen: bad zp_type");
+    OSQ_REQUIRE(mode >= OSQ_PARAM_FIXED && mode <= OSQ_PARAM_LSQPLUS, "fake_quant_per_channel_widen: bad mode");
+    if (outer * channels * inner == 0) return OSQ_OK;
+    OSQ_REQUIRE(x && y, "fake_quant_per_channel_widen: null tensor");
+    OSQ_LOWP_DISPATCH(dtype, launch_fq_channel(static_cast<const T*>(x), y, nullptr, outer, channels, inner, scale, zero_point,
+                                               zp_type, mode, grad_factor, quant_min, quant_max, static_cast<hipStream_t>(stream)));
+    return check_launch("fake_quant_per_channel_widen");
 }
 
 extern "C" int osq_lsq_backward_per_tensor(const float* x, const float* grad_out, float* grad_x, int64_t n,

@@ -62,13 +62,6 @@ __global__ __launch_bounds__(kThreads) void gamma_residual_vec_kernel(const floa
     }
 }
 
-static inline int grid_for(int64_t items, int per_block) {
-    int64_t b = (items + per_block - 1) / per_block;
-    if (b < 1) b = 1;
-    if (b > kMaxBlocks) b = kMaxBlocks;
-    return static_cast<int>(b);
-}
-
 }  // namespace osq
 
 using namespace osq;

@@ -1612,13 +1612,6 @@ __global__ __launch_bounds__(kResThreads) void msefast_resident_multi_kernel(Res
     }
 }
 
-static inline int grid_for(int64_t items, int per_block, int max_blocks) {
-    int64_t b = (items + per_block - 1) / per_block;
-    if (b < 1) b = 1;
-    if (b > max_blocks) b = max_blocks;
-    return static_cast<int>(b);
-}
-
 }  // namespace osq
 
 using namespace osq;

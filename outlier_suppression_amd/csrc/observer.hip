@@ -83,14 +83,17 @@ __global__ void update_kernel(const float* __restrict__ cur_min, const float* __
 
 // ---------------------------------------------------------------- flat min/max (K4)
 
-__global__ __launch_bounds__(kThreads) void observe_flat_kernel(const float4* __restrict__ x, int64_t n4,
-                                                                const float* __restrict__ xt, int tail,
+// granules [0, ng) by 16-byte loads (x 16-byte aligned, else ng == 0), elements [ng * per, n) one by one over the whole grid
+template <typename T>
+__global__ __launch_bounds__(kThreads) void observe_flat_kernel(const T* __restrict__ x, int64_t ng, int64_t n,
                                                                 float* __restrict__ partials,
                                                                 unsigned int* __restrict__ counter, Finish fin) {
+    typedef Granule<T> G;
     MinMax acc;
     acc.init();
     const int64_t stride = static_cast<int64_t>(gridDim.x) * kThreads;
-    int64_t i = static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x;
+    const int64_t tid = static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x;
+    const typename G::V* xg = reinterpret_cast<const typename G::V*>(x);
     // running state for the finish step: fetched now by the thread that may need it, so that the last
     // workgroup's tail has no dependent load left (every serial memory round trip there costs ~1 us)
     float st_min = 0.f, st_max = 0.f;
@@ -98,13 +101,14 @@ __global__ __launch_bounds__(kThreads) void observe_flat_kernel(const float4* __
         st_min = fin.min_val[0];
         st_max = fin.max_val[0];
     }
-    for (; i + 3 * stride < n4; i += 4 * stride) {
-        const float4 a = load_stream(&x[i]), b = load_stream(&x[i + stride]), c = load_stream(&x[i + 2 * stride]),
-                     d = load_stream(&x[i + 3 * stride]);
-        acc.add4(a); acc.add4(b); acc.add4(c); acc.add4(d);
+    int64_t i = tid;
+    for (; i + 3 * stride < ng; i += 4 * stride) {
+        const typename G::V a = G::load_nt(&xg[i]), b = G::load_nt(&xg[i + stride]), c = G::load_nt(&xg[i + 2 * stride]),
+                            d = G::load_nt(&xg[i + 3 * stride]);
+        G::add(acc, a); G::add(acc, b); G::add(acc, c); G::add(acc, d);
     }
-    for (; i < n4; i += stride) acc.add4(x[i]);
-    if (blockIdx.x == 0 && static_cast<int>(threadIdx.x) < tail) acc.add(xt[threadIdx.x]);
+    for (; i < ng; i += stride) G::add(acc, G::load(&xg[i]));
+    for (int64_t j = ng * G::kPer + tid; j < n; j += stride) acc.add(static_cast<float>(x[j]));
     acc = block_reduce(acc);
     // ONE 8-byte partial per workgroup: {min, max}, a NaN minimum flags "NaN seen" (fminf never yields one)
     unsigned long long* part64 = reinterpret_cast<unsigned long long*>(partials);
@@ -145,22 +149,29 @@ __global__ __launch_bounds__(kThreads) void observe_flat_kernel(const float4* __
 
 // ---------------------------------------------------------------- per-channel min/max (K5)
 
-// rows = channels (outer == 1), inner % 4 == 0: one wave per row
-__global__ __launch_bounds__(kThreads) void observe_rows_kernel(const float4* __restrict__ x, int64_t rows, int inner4,
-                                                                Finish fin) {
+// rows = channels (outer == 1), inner a whole number of granules: one wave per row
+template <typename T>
+__global__ __launch_bounds__(kThreads) void observe_rows_kernel(const typename Granule<T>::V* __restrict__ x, int64_t rows,
+                                                                int inner_g, Finish fin) {
+    typedef Granule<T> G;
     const int lane = threadIdx.x & (OSQ_WAVE - 1);
     const int64_t wave = (static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x) / OSQ_WAVE;
     const int64_t nwaves = static_cast<int64_t>(gridDim.x) * kWavesPerBlock;
     for (int64_t r = wave; r < rows; r += nwaves) {
-        const float4* xr = x + r * inner4;
+        const typename G::V* xr = x + r * inner_g;
         MinMax acc;
         acc.init();
         int j = lane;
-        for (; j + 3 * OSQ_WAVE < inner4; j += 4 * OSQ_WAVE) {
-            const float4 a = xr[j], b = xr[j + OSQ_WAVE], c = xr[j + 2 * OSQ_WAVE], d = xr[j + 3 * OSQ_WAVE];
-            acc.add4(a); acc.add4(b); acc.add4(c); acc.add4(d);
+        for (; j + (G::kRowLoads - 1) * OSQ_WAVE < inner_g; j += G::kRowLoads * OSQ_WAVE) {
+            const typename G::V a = G::load(&xr[j]), b = G::load(&xr[j + OSQ_WAVE]);
+            if constexpr (G::kRowLoads == 4) {
+                const typename G::V c = G::load(&xr[j + 2 * OSQ_WAVE]), d = G::load(&xr[j + 3 * OSQ_WAVE]);
+                G::add(acc, a); G::add(acc, b); G::add(acc, c); G::add(acc, d);
+            } else {
+                G::add(acc, a); G::add(acc, b);
+            }
         }
-        for (; j < inner4; j += OSQ_WAVE) acc.add4(xr[j]);
+        for (; j < inner_g; j += OSQ_WAVE) G::add(acc, G::load(&xr[j]));
         acc.wave_reduce();
         if (lane == 0) {
             acc.poison();
@@ -170,14 +181,15 @@ __global__ __launch_bounds__(kThreads) void observe_rows_kernel(const float4* __
 }
 
 // generic [outer, channels, inner]: one workgroup per channel
-__global__ __launch_bounds__(kThreads) void observe_channels_kernel(const float* __restrict__ x, int64_t outer,
+template <typename T>
+__global__ __launch_bounds__(kThreads) void observe_channels_kernel(const T* __restrict__ x, int64_t outer,
                                                                     int64_t channels, int64_t inner, Finish fin) {
     const int64_t c = blockIdx.x;
     MinMax acc;
     acc.init();
     for (int64_t o = 0; o < outer; ++o) {
-        const float* p = x + (o * channels + c) * inner;
-        for (int64_t j = threadIdx.x; j < inner; j += kThreads) acc.add(p[j]);
+        const T* p = x + (o * channels + c) * inner;
+        for (int64_t j = threadIdx.x; j < inner; j += kThreads) acc.add(static_cast<float>(p[j]));
     }
     acc = block_reduce(acc);
     if (threadIdx.x == 0) {
@@ -191,65 +203,69 @@ __global__ __launch_bounds__(kThreads) void observe_channels_kernel(const float*
 constexpr int kTokPerWave = 4;                                  // tokens a wave keeps in flight together
 constexpr int kTokPerBlock = kTokPerWave * kWavesPerBlock;      // consecutive tokens of ONE sample per workgroup
 
-// Fast path: feat_inner contiguous (stride 1), everything 16-byte aligned.
+// Fast path: feat_inner contiguous (stride 1) and a whole number of granules, everything 16-byte aligned.
 // Workgroup = 16 consecutive tokens of one sample (blockIdx.y = sample); a workgroup that
 // starts beyond the sample's valid length exits at once, so padding is never read.
 // Each wave owns 4 tokens and issues all their 16-byte loads before reducing any.
 // Lane layout inside a token: the wave is split into 64/G groups of G lanes; group g walks
 // feature segments g, g + 64/G, ...; G = 64 for one long segment ([B,T,768]), G = 16 for
 // head_dim 64 ([B,h,T,64] and its views) so that no lane idles on short segments.
-template <bool NT>
-__device__ __forceinline__ float4 tok_load(const float4* p) { return NT ? load_stream(p) : *p; }
+template <typename T, bool NT>
+__device__ __forceinline__ typename Granule<T>::V tok_load(const T* p, int j) {
+    const typename Granule<T>::V* g = reinterpret_cast<const typename Granule<T>::V*>(p) + j;
+    return NT ? Granule<T>::load_nt(g) : Granule<T>::load(g);
+}
 
 // The per-token reduction of one wave: the extrema of its (up to) 4 tokens starting at `base`, NaN-poisoned, every
 // lane holding every token's result.
-template <bool SINGLE_SEGMENT, bool NT>
-__device__ __forceinline__ void token_extrema(const float* __restrict__ base, const osq_token_view& v, const int ntok,
-                                              const int lgG, const int inner4, const int lane, MinMax (&acc)[kTokPerWave]) {
+template <typename T, bool SINGLE_SEGMENT, bool NT>
+__device__ __forceinline__ void token_extrema(const T* __restrict__ base, const osq_token_view& v, const int ntok,
+                                              const int lgG, const int inner_g, const int lane, MinMax (&acc)[kTokPerWave]) {
+    typedef Granule<T> G;
 #pragma unroll
     for (int k = 0; k < kTokPerWave; ++k) acc[k].init();
     if (SINGLE_SEGMENT) {
         // three column steps at a time (768 columns = exactly one trip): 12 independent 16-byte loads per lane
         // are issued before the first is reduced; the short loop below takes what is left
         int j = lane;
-        for (; j + 2 * OSQ_WAVE < inner4; j += 3 * OSQ_WAVE) {
-            float4 val[3][kTokPerWave];
+        for (; j + 2 * OSQ_WAVE < inner_g; j += 3 * OSQ_WAVE) {
+            typename G::V val[3][kTokPerWave];
 #pragma unroll
             for (int u = 0; u < 3; ++u)
 #pragma unroll
                 for (int k = 0; k < kTokPerWave; ++k) {
                     const int kk = k < ntok ? k : 0;             // short tail: re-read token 0, result unused
-                    val[u][k] = tok_load<NT>(reinterpret_cast<const float4*>(base + kk * v.stride_token) + j + u * OSQ_WAVE);
+                    val[u][k] = tok_load<T, NT>(base + kk * v.stride_token, j + u * OSQ_WAVE);
                 }
 #pragma unroll
             for (int u = 0; u < 3; ++u)
 #pragma unroll
-                for (int k = 0; k < kTokPerWave; ++k) acc[k].add4(val[u][k]);
+                for (int k = 0; k < kTokPerWave; ++k) G::add(acc[k], val[u][k]);
         }
-        for (; j < inner4; j += OSQ_WAVE) {
-            float4 val[kTokPerWave];
+        for (; j < inner_g; j += OSQ_WAVE) {
+            typename G::V val[kTokPerWave];
 #pragma unroll
             for (int k = 0; k < kTokPerWave; ++k) {
                 const int kk = k < ntok ? k : 0;
-                val[k] = tok_load<NT>(reinterpret_cast<const float4*>(base + kk * v.stride_token) + j);
+                val[k] = tok_load<T, NT>(base + kk * v.stride_token, j);
             }
 #pragma unroll
-            for (int k = 0; k < kTokPerWave; ++k) acc[k].add4(val[k]);
+            for (int k = 0; k < kTokPerWave; ++k) G::add(acc[k], val[k]);
         }
     } else {
-        const int G = 1 << lgG;
-        const int grp = lane >> lgG, li = lane & (G - 1), ngrp = OSQ_WAVE >> lgG;
+        const int gl = 1 << lgG;
+        const int grp = lane >> lgG, li = lane & (gl - 1), ngrp = OSQ_WAVE >> lgG;
         for (int64_t o = grp; o < v.feat_outer; o += ngrp) {
-            const float* seg = base + o * v.stride_outer;
-            for (int j = li; j < inner4; j += G) {
-                float4 val[kTokPerWave];
+            const T* seg = base + o * v.stride_outer;
+            for (int j = li; j < inner_g; j += gl) {
+                typename G::V val[kTokPerWave];
 #pragma unroll
                 for (int k = 0; k < kTokPerWave; ++k) {
                     const int kk = k < ntok ? k : 0;
-                    val[k] = tok_load<NT>(reinterpret_cast<const float4*>(seg + kk * v.stride_token) + j);
+                    val[k] = tok_load<T, NT>(seg + kk * v.stride_token, j);
                 }
 #pragma unroll
-                for (int k = 0; k < kTokPerWave; ++k) acc[k].add4(val[k]);
+                for (int k = 0; k < kTokPerWave; ++k) G::add(acc[k], val[k]);
             }
         }
     }
@@ -260,11 +276,11 @@ __device__ __forceinline__ void token_extrema(const float* __restrict__ base, co
     }
 }
 
-template <bool SINGLE_SEGMENT, bool NT>
-__global__ __launch_bounds__(kThreads) void token_minmax_vec_kernel(const float* __restrict__ x, osq_token_view v,
+template <typename T, bool SINGLE_SEGMENT, bool NT>
+__global__ __launch_bounds__(kThreads) void token_minmax_vec_kernel(const T* __restrict__ x, osq_token_view v,
                                                                     const int64_t* __restrict__ lengths,
                                                                     float* __restrict__ tok_min,
-                                                                    float* __restrict__ tok_max, int lgG, int inner4) {
+                                                                    float* __restrict__ tok_max, int lgG, int inner_g) {
     const int64_t b = blockIdx.y;
     int64_t len = v.tokens;
     if (lengths) {
@@ -280,9 +296,9 @@ __global__ __launch_bounds__(kThreads) void token_minmax_vec_kernel(const float*
     const int64_t t0 = chunk * kTokPerBlock + w * kTokPerWave;
     if (t0 >= len) return;
     const int ntok = (len - t0) < kTokPerWave ? static_cast<int>(len - t0) : kTokPerWave;
-    const float* base = x + b * v.stride_batch + t0 * v.stride_token;
+    const T* base = x + b * v.stride_batch + t0 * v.stride_token;
     MinMax acc[kTokPerWave];
-    token_extrema<SINGLE_SEGMENT, NT>(base, v, ntok, lgG, inner4, lane, acc);
+    token_extrema<T, SINGLE_SEGMENT, NT>(base, v, ntok, lgG, inner_g, lane, acc);
     if (lane < ntok) {
         float mn = acc[0].mn, mx = acc[0].mx;
 #pragma unroll
@@ -295,7 +311,8 @@ __global__ __launch_bounds__(kThreads) void token_minmax_vec_kernel(const float*
 }
 
 // Any strides (scalar loads): correctness path for layouts the fast path rejects.
-__global__ __launch_bounds__(kThreads) void token_minmax_generic_kernel(const float* __restrict__ x, osq_token_view v,
+template <typename T>
+__global__ __launch_bounds__(kThreads) void token_minmax_generic_kernel(const T* __restrict__ x, osq_token_view v,
                                                                         const int64_t* __restrict__ lengths,
                                                                         float* __restrict__ tok_min,
                                                                         float* __restrict__ tok_max) {
@@ -307,12 +324,12 @@ __global__ __launch_bounds__(kThreads) void token_minmax_generic_kernel(const fl
     for (int64_t tok = wave0; tok < ntok; tok += nwaves) {
         const int64_t b = tok / v.tokens, t = tok - b * v.tokens;
         if (lengths && t >= lengths[b]) continue;
-        const float* base = x + b * v.stride_batch + t * v.stride_token;
+        const T* base = x + b * v.stride_batch + t * v.stride_token;
         MinMax acc;
         acc.init();
         for (int64_t j = lane; j < F; j += OSQ_WAVE) {
             const int64_t o = j / v.feat_inner, i = j - o * v.feat_inner;
-            acc.add(base[o * v.stride_outer + i * v.stride_inner]);
+            acc.add(static_cast<float>(base[o * v.stride_outer + i * v.stride_inner]));
         }
         acc.wave_reduce();
         if (lane == 0) {
@@ -1210,20 +1227,6 @@ __global__ __launch_bounds__(kWideThreads) void wide_select_kernel(WideArgs a, F
     }
 }
 
-static inline int grid_for(int64_t work_items, int per_block, int max_blocks) {
-    int64_t b = (work_items + per_block - 1) / per_block;
-    if (b < 1) b = 1;
-    if (b > max_blocks) b = max_blocks;
-    return static_cast<int>(b);
-}
-
-static inline int check_finish_args(int update_rule, const float* min_val, const float* max_val, const char** why) {
-    if (update_rule < OSQ_UPDATE_NONE || update_rule > OSQ_UPDATE_AVERAGE) { *why = "bad update rule"; return 0; }
-    if (update_rule != OSQ_UPDATE_NONE && (!min_val || !max_val)) { *why = "update rule needs min_val/max_val"; return 0; }
-    return 1;
-}
-
-
 // Layout rules of token_select_kernel: 16-byte groups (slot count and problem stride multiples of 4,
 // aligned arrays), T >= 4 so that a group straddles at most two samples, at most 32 values per thread
 // (64 would spill at 1024 threads per workgroup).
@@ -1311,90 +1314,146 @@ extern "C" int osq_replay_statistics(const float* table, int n_batches, int n_qu
     return check_launch("replay_statistics");
 }
 
-extern "C" int osq_observe_flat(const float* x, int64_t n,
-                                int update_rule, int64_t cnt, float* min_val, float* max_val,
-                                float* cur_minmax,
-                                int quant_min, int quant_max, int symmetric,
-                                float* scale_out, void* zero_point_out, int zp_type,
-                                void* workspace, osq_stream stream) {
+// ---- the min / max entry points: one body per pair, T = float behind the fp32 name, __bf16 / _Float16 behind `_lowp`;
+// `what` = the entry point's name, for osq_last_error()
+#define OSQ_REQUIRE_AT(cond, what, msg)                  \
+    do {                                                 \
+        if (!(cond)) {                                   \
+            ::osq::set_error("%s: %s", what, msg);       \
+            return OSQ_ERR_INVALID_ARGUMENT;             \
+        }                                                \
+    } while (0)
+
+template <typename T>
+static int observe_flat(const char* what, const T* x, int64_t n, int update_rule, int64_t cnt, float* min_val, float* max_val,
+                        float* cur_minmax,
+                        int quant_min, int quant_max, int symmetric, float* scale_out, void* zero_point_out, int zp_type,
+                        void* workspace, osq_stream stream) {
+    typedef Granule<T> G;
     const char* why = "";
-    OSQ_REQUIRE(n > 0 && x && workspace, "observe_flat: empty tensor or null pointer");
-    OSQ_REQUIRE(check_finish_args(update_rule, min_val, max_val, &why), why);
+    OSQ_REQUIRE_AT(n > 0 && x && workspace, what, "empty tensor or null pointer");
+    OSQ_REQUIRE_AT(check_finish_args(update_rule, min_val, max_val, &why), what, why);
     const Finish fin{update_rule, cnt, min_val, max_val, cur_minmax, quant_min, quant_max, symmetric, scale_out,
                      zero_point_out, zp_type};
-    Workspace ws(workspace);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (aligned16(x)) {
-        const int64_t n4 = n / 4;
-        const int grid = grid_for(n4, kThreads * 4, g_obs_blocks);
-        const TimingHook th = take_timing_hook(OSQ_TIME_OBSERVE_FLAT);
-        hipExtLaunchKernelGGL(observe_flat_kernel, dim3(grid), dim3(kThreads), 0, st, th.start, th.stop, 0,
-                              reinterpret_cast<const float4*>(x), n4,
-                           x + n4 * 4, static_cast<int>(n - n4 * 4), ws.floats(kFamObserveFlat), ws.counter(kFamObserveFlat), fin);
-    } else {
-        // misaligned base: peel to the next 16-byte boundary by treating the head as the "tail" is not
-        // possible with one pointer, so fall back to the per-channel kernel with a single channel.
-        hipLaunchKernelGGL(observe_channels_kernel, dim3(1), dim3(kThreads), 0, st, x, int64_t(1), int64_t(1), n, fin);
-    }
-    return check_launch("observe_flat");
+    const Workspace ws(workspace);
+    const int64_t ng = aligned16(x) ? n / G::kPer : 0;
+    const int grid = grid_for(ng ? ng : (n + G::kPer - 1) / G::kPer, kThreads * 4, g_obs_blocks);
+    const TimingHook th = take_timing_hook(OSQ_TIME_OBSERVE_FLAT);
+    hipExtLaunchKernelGGL(observe_flat_kernel<T>, dim3(grid), dim3(kThreads), 0, static_cast<hipStream_t>(stream), th.start, th.stop,
+                          0, x, ng, n, ws.floats(kFamObserveFlat), ws.counter(kFamObserveFlat), fin);
+    return check_launch(what);
 }
 
-extern "C" int osq_observe_channels(const float* x, int64_t outer, int64_t channels, int64_t inner,
-                                    int update_rule, int64_t cnt, float* min_val, float* max_val,
-                                    int quant_min, int quant_max, int symmetric,
-                                    float* scale_out, void* zero_point_out, int zp_type,
-                                    osq_stream stream) {
+extern "C" int osq_observe_flat(const float* x, int64_t n, int update_rule, int64_t cnt, float* min_val, float* max_val,
+                                float* cur_minmax, int quant_min, int quant_max, int symmetric, float* scale_out,
+                                void* zero_point_out, int zp_type, void* workspace, osq_stream stream) {
+    return observe_flat("observe_flat", x, n, update_rule, cnt, min_val, max_val, cur_minmax, quant_min, quant_max, symmetric, scale_out,
+                        zero_point_out, zp_type, workspace, stream);
+}
+
+extern "C" int osq_observe_flat_lowp(int dtype, const void* x, int64_t n, int update_rule, int64_t cnt, float* min_val,
+                                     float* max_val, float* cur_minmax, int quant_min, int quant_max, int symmetric,
+                                     float* scale_out, void* zero_point_out, int zp_type, void* workspace, osq_stream stream) {
+    OSQ_REQUIRE(known_dtype(dtype), "observe_flat_lowp: unknown dtype");
+    int rc;
+    OSQ_LOWP_DISPATCH(dtype, rc = observe_flat("observe_flat_lowp", static_cast<const T*>(x), n, update_rule, cnt, min_val, max_val,
+                                               cur_minmax, quant_min, quant_max, symmetric, scale_out, zero_point_out, zp_type,
+                                               workspace, stream));
+    return rc;
+}
+
+template <typename T>
+static int observe_channels(const char* what, const T* x, int64_t outer, int64_t channels, int64_t inner, int update_rule,
+                            int64_t cnt,
+                            float* min_val, float* max_val, int quant_min, int quant_max, int symmetric, float* scale_out,
+                            void* zero_point_out, int zp_type, osq_stream stream) {
+    typedef Granule<T> G;
     const char* why = "";
-    OSQ_REQUIRE(outer > 0 && channels > 0 && inner > 0 && x, "observe_channels: empty tensor or null pointer");
-    OSQ_REQUIRE(channels < (1ll << 31), "observe_channels: too many channels");
-    OSQ_REQUIRE(check_finish_args(update_rule, min_val, max_val, &why), why);
+    OSQ_REQUIRE_AT(outer > 0 && channels > 0 && inner > 0 && x, what, "empty tensor or null pointer");
+    OSQ_REQUIRE_AT(channels < (1ll << 31), what, "too many channels");
+    OSQ_REQUIRE_AT(check_finish_args(update_rule, min_val, max_val, &why), what, why);
     const Finish fin{update_rule, cnt, min_val, max_val, nullptr, quant_min, quant_max, symmetric, scale_out,
                      zero_point_out, zp_type};
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (outer == 1 && inner % 4 == 0 && aligned16(x) && inner / 4 < (1 << 30)) {
+    if (outer == 1 && inner % G::kPer == 0 && aligned16(x) && inner / G::kPer < (1 << 30)) {
         const int grid = grid_for(channels, kWavesPerBlock, kMaxBlocks * 4);
         const TimingHook th = take_timing_hook(OSQ_TIME_OBSERVE_CHANNELS);
-        hipExtLaunchKernelGGL(observe_rows_kernel, dim3(grid), dim3(kThreads), 0, st, th.start, th.stop, 0,
-                              reinterpret_cast<const float4*>(x), channels, static_cast<int>(inner / 4), fin);
+        hipExtLaunchKernelGGL(observe_rows_kernel<T>, dim3(grid), dim3(kThreads), 0, st, th.start, th.stop, 0,
+                              reinterpret_cast<const typename G::V*>(x), channels, static_cast<int>(inner / G::kPer), fin);
     } else {
-        hipLaunchKernelGGL(observe_channels_kernel, dim3(static_cast<unsigned>(channels)), dim3(kThreads), 0, st, x, outer,
+        hipLaunchKernelGGL(observe_channels_kernel<T>, dim3(static_cast<unsigned>(channels)), dim3(kThreads), 0, st, x, outer,
                            channels, inner, fin);
     }
-    return check_launch("observe_channels");
+    return check_launch(what);
 }
 
-extern "C" int osq_token_minmax(const float* x, const osq_token_view* view, const int64_t* lengths,
-                                float* token_min, float* token_max, osq_stream stream) {
-    OSQ_REQUIRE(x && view && token_min && token_max, "token_minmax: null pointer");
+extern "C" int osq_observe_channels(const float* x, int64_t outer, int64_t channels, int64_t inner, int update_rule, int64_t cnt,
+                                    float* min_val, float* max_val, int quant_min, int quant_max, int symmetric,
+                                    float* scale_out, void* zero_point_out, int zp_type, osq_stream stream) {
+    return observe_channels("observe_channels", x, outer, channels, inner, update_rule, cnt, min_val, max_val, quant_min, quant_max, symmetric,
+                            scale_out, zero_point_out, zp_type, stream);
+}
+
+extern "C" int osq_observe_channels_lowp(int dtype, const void* x, int64_t outer, int64_t channels, int64_t inner,
+                                         int update_rule, int64_t cnt, float* min_val, float* max_val, int quant_min,
+                                         int quant_max, int symmetric, float* scale_out, void* zero_point_out, int zp_type,
+                                         osq_stream stream) {
+    OSQ_REQUIRE(known_dtype(dtype), "observe_channels_lowp: unknown dtype");
+    int rc;
+    OSQ_LOWP_DISPATCH(dtype, rc = observe_channels("observe_channels_lowp", static_cast<const T*>(x), outer, channels, inner,
+                                                   update_rule, cnt, min_val, max_val, quant_min, quant_max, symmetric, scale_out,
+                                                   zero_point_out, zp_type, stream));
+    return rc;
+}
+
+template <typename T>
+static int token_minmax(const char* what, const T* x, const osq_token_view* view, const int64_t* lengths, float* token_min,
+                        float* token_max,
+                        osq_stream stream) {
+    constexpr int kPer = Granule<T>::kPer;
+    OSQ_REQUIRE_AT(x && view && token_min && token_max, what, "null pointer");
     const osq_token_view v = *view;
-    OSQ_REQUIRE(v.batch > 0 && v.tokens > 0 && v.feat_outer > 0 && v.feat_inner > 0, "token_minmax: empty view");
+    OSQ_REQUIRE_AT(v.batch > 0 && v.tokens > 0 && v.feat_outer > 0 && v.feat_inner > 0, what, "empty view");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const int64_t ntok = v.batch * v.tokens;
-    const int grid = grid_for(ntok, kWavesPerBlock, kMaxBlocks * 8);
-    const bool vec = v.stride_inner == 1 && v.feat_inner % 4 == 0 && aligned16(x) && v.stride_batch % 4 == 0 &&
-                     v.stride_token % 4 == 0 && (v.feat_outer == 1 || v.stride_outer % 4 == 0) &&
-                     v.feat_inner / 4 < (1 << 30);
+    // 16-byte path: whole granules and 16-byte aligned rows; the sample index is gridDim.y
+    const bool vec = v.stride_inner == 1 && v.feat_inner % kPer == 0 && aligned16(x) && v.stride_batch % kPer == 0 &&
+                     v.stride_token % kPer == 0 && (v.feat_outer == 1 || v.stride_outer % kPer == 0) &&
+                     v.feat_inner / kPer < (1 << 30) && v.batch <= 65535;
     if (vec) {
-        const int inner4 = static_cast<int>(v.feat_inner / 4);
+        const int inner_g = static_cast<int>(v.feat_inner / kPer);
         int lgG = 6;
         if (v.feat_outer > 1) {
             lgG = 0;
-            while ((1 << lgG) < inner4 && lgG < 6) ++lgG;
+            while ((1 << lgG) < inner_g && lgG < 6) ++lgG;
         }
-        OSQ_REQUIRE(v.batch <= 65535, "token_minmax: batch exceeds grid.y");
         const dim3 tgrid(static_cast<unsigned>((v.tokens + kTokPerBlock - 1) / kTokPerBlock), static_cast<unsigned>(v.batch));
         const TimingHook th = take_timing_hook(OSQ_TIME_TOKEN_MINMAX);
 #define OSQ_TOK(SEG, NT) \
-    hipExtLaunchKernelGGL((token_minmax_vec_kernel<SEG, NT>), tgrid, dim3(kThreads), 0, st, th.start, th.stop, 0, x, v, lengths, \
-                          token_min, token_max, lgG, inner4)
+    hipExtLaunchKernelGGL((token_minmax_vec_kernel<T, SEG, NT>), tgrid, dim3(kThreads), 0, st, th.start, th.stop, 0, x, v, lengths, \
+                          token_min, token_max, lgG, inner_g)
         if (v.feat_outer == 1) { if (g_tok_nt) OSQ_TOK(true, true); else OSQ_TOK(true, false); }
         else { if (g_tok_nt) OSQ_TOK(false, true); else OSQ_TOK(false, false); }
 #undef OSQ_TOK
     } else {
-        hipLaunchKernelGGL(token_minmax_generic_kernel, dim3(grid), dim3(kThreads), 0, st, x, v, lengths, token_min,
+        const int grid = grid_for(v.batch * v.tokens, kWavesPerBlock, kMaxBlocks * 8);
+        hipLaunchKernelGGL(token_minmax_generic_kernel<T>, dim3(grid), dim3(kThreads), 0, st, x, v, lengths, token_min,
                            token_max);
     }
-    return check_launch("token_minmax");
+    return check_launch(what);
+}
+
+extern "C" int osq_token_minmax(const float* x, const osq_token_view* view, const int64_t* lengths,
+                                float* token_min, float* token_max, osq_stream stream) {
+    return token_minmax("token_minmax", x, view, lengths, token_min, token_max, stream);
+}
+
+extern "C" int osq_token_minmax_lowp(int dtype, const void* x, const osq_token_view* view, const int64_t* lengths,
+                                     float* token_min, float* token_max, osq_stream stream) {
+    OSQ_REQUIRE(known_dtype(dtype), "token_minmax_lowp: unknown dtype");
+    int rc;
+    OSQ_LOWP_DISPATCH(dtype, rc = token_minmax("token_minmax_lowp", static_cast<const T*>(x), view, lengths, token_min, token_max,
+                                               stream));
+    return rc;
 }
 
 extern "C" int osq_token_minmax_multi(const osq_site_desc* descs, const int64_t* tok_end, int n_sites,

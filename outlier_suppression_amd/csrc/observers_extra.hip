@@ -577,13 +577,6 @@ __global__ __launch_bounds__(kThreads) void mse_grid_rows_kernel(const float* __
     if (lane == 0) { best_min[row] = bmin; best_max[row] = bmax; }
 }
 
-static inline int grid_for(int64_t items, int per_block, int max_blocks) {
-    int64_t b = (items + per_block - 1) / per_block;
-    if (b < 1) b = 1;
-    if (b > max_blocks) b = max_blocks;
-    return static_cast<int>(b);
-}
-
 static inline bool make_source(const float* x, int64_t n, const osq_token_view* view, const int64_t* lengths, ElemSource* s,
                                int* grid, int max_blocks) {
     s->x = x;

@@ -311,7 +311,7 @@ __device__ __forceinline__ float wave_sum_f32(float v) {
     return (lane_value(v, 0) + lane_value(v, 16)) + (lane_value(v, 32) + lane_value(v, 48));
 }
 
-// ---- (min, max) reductions and what follows them (observer.hip, lowp.hip) ---------------
+// ---- (min, max) reductions and what follows them (observer.hip) --------------------------
 constexpr int kMinMaxMaxThreads = 1024;     // largest workgroup block_reduce serves
 
 struct MinMax {
@@ -353,6 +353,39 @@ __device__ __forceinline__ MinMax block_reduce(MinMax v) {
     }
     return v;
 }
+
+// ---- one 16-byte granule of T: what a kernel that serves fp32, bf16 and fp16 says instead of float4 / load_stream / add4.
+// float: four elements, the float4 itself.  __bf16 / _Float16: eight elements, widened exactly (two float4s).
+template <typename T>
+struct Granule {
+    static constexpr int kPer = 8;          // elements
+    static constexpr int kWide = 2;         // float4s of the widened granule
+    static constexpr int kRowLoads = 2;     // loads in flight per lane where one wave walks a row: a row has half the fp32 granules
+    typedef T V __attribute__((ext_vector_type(8)));
+    __device__ static __forceinline__ V load(const V* p) { return __builtin_bit_cast(V, *reinterpret_cast<const osq_v4u32*>(p)); }
+    __device__ static __forceinline__ V load_nt(const V* p) {
+        return __builtin_bit_cast(V, __builtin_nontemporal_load(reinterpret_cast<const osq_v4u32*>(p)));
+    }
+    __device__ static __forceinline__ void add(MinMax& acc, const V& v) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) acc.add(static_cast<float>(v[e]));
+    }
+    __device__ static __forceinline__ void widen(const V& v, float4 (&w)[2]) {
+        w[0] = make_float4(static_cast<float>(v[0]), static_cast<float>(v[1]), static_cast<float>(v[2]), static_cast<float>(v[3]));
+        w[1] = make_float4(static_cast<float>(v[4]), static_cast<float>(v[5]), static_cast<float>(v[6]), static_cast<float>(v[7]));
+    }
+};
+template <>
+struct Granule<float> {
+    static constexpr int kPer = 4;
+    static constexpr int kWide = 1;
+    static constexpr int kRowLoads = 4;
+    typedef float4 V;
+    __device__ static __forceinline__ V load(const V* p) { return *p; }
+    __device__ static __forceinline__ V load_nt(const V* p) { return load_stream(p); }
+    __device__ static __forceinline__ void add(MinMax& acc, const V& v) { acc.add4(v); }
+    __device__ static __forceinline__ void widen(const V& v, float4 (&w)[1]) { w[0] = v; }
+};
 
 struct Finish {   // what happens once a batch's (min, max) is known
     int rule;

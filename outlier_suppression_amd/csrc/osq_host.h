@@ -81,6 +81,33 @@ static inline int check_launch(const char* what) {
     return OSQ_OK;
 }
 
+// workgroups for `work_items` items at `per_block` each: at least one, at most max_blocks
+static inline int grid_for(int64_t work_items, int per_block, int max_blocks = kMaxBlocks) {
+    int64_t b = (work_items + per_block - 1) / per_block;
+    if (b < 1) b = 1;
+    if (b > max_blocks) b = max_blocks;
+    return static_cast<int>(b);
+}
+
+static inline int check_finish_args(int update_rule, const float* min_val, const float* max_val, const char** why) {
+    if (update_rule < OSQ_UPDATE_NONE || update_rule > OSQ_UPDATE_AVERAGE) { *why = "bad update rule"; return 0; }
+    if (update_rule != OSQ_UPDATE_NONE && (!min_val || !max_val)) { *why = "update rule needs min_val/max_val"; return 0; }
+    return 1;
+}
+
+// the 16-bit entry points (`dtype` argument): CALL runs with T = __bf16 or _Float16
+static inline bool known_dtype(int dtype) { return dtype == OSQ_DTYPE_BF16 || dtype == OSQ_DTYPE_F16; }
+#define OSQ_LOWP_DISPATCH(dtype, CALL) \
+    do {                                 \
+        if ((dtype) == OSQ_DTYPE_BF16) { \
+            typedef __bf16 T;            \
+            CALL;                        \
+        } else {                         \
+            typedef _Float16 T;          \
+            CALL;                        \
+        }                                \
+    } while (0)
+
 // Caller-owned scratch: [8 x 4 KiB of ticket counters][8 x 64 KiB of partials][16 KiB + 64 B wide-finaliser state]
 // [64 KiB rendezvous words][2 KiB state of the fused observe + fake-quant launch][256.1 KiB state of the resident MSEFast search].  Counters are zero between
 // launches (each kernel's last workgroup resets the one it used).

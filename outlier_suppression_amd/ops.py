@@ -27,7 +27,7 @@ def _check_f32(*tensors):
             raise TypeError(f"outlier_suppression_amd kernels compute in float32, got {t.dtype}")
 
 
-# bf16 / fp16 inputs (lowp.hip): their own entry points below; the fp32 functions keep rejecting them
+# bf16 / fp16 inputs (lowp.hip; the observer and per-channel ones in observer.hip / fake_quant.hip): their own entry points below; the fp32 functions keep rejecting them
 LOWP_DTYPES = {torch.bfloat16: _hip.DTYPE_BF16, torch.float16: _hip.DTYPE_F16}
 
 

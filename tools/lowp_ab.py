@@ -5,6 +5,7 @@ Times with device events, after a warm-up, the median of --reps repetitions of -
   * the in-dtype chain (FixedFakeQuantize per-tensor, osq_fake_quant_chain_lowp), bf16 and fp16;
   * the widening LSQ+ forward (fp32 result, osq_fake_quant_per_tensor_widen);
   * the flat observe (osq_observe_flat_lowp) and the masked token-path observe (token extrema + the fp32 finaliser);
+  * the per-channel observe and the per-channel widening forward of a [3072, 768] weight, ch_axis = 0;
   * the same calls on fp32 data through the existing kernels;
   * ".float() -> fp32 kernel -> .to(dtype)": a cost baseline only (it is NOT bit-equal to the reference's chain).
 Bytes moved are computed from the shapes (compulsory HBM traffic of one call); share = bytes / time / 8 TB/s.
@@ -50,6 +51,12 @@ def main():
     dev = torch.device("cuda:0")
     gen = torch.Generator().manual_seed(0)
     rows = []
+
+    def add(shape, name, dtype, fn, nbytes):
+        us = timed(fn, args.iters, args.reps)
+        rows.append({"shape": list(shape), "call": name, "dtype": dtype, "us": round(us, 2), "MB": round(nbytes / 1e6, 1),
+                     "TB_s": round(nbytes / us / 1e6, 2), "share_8TBs": round(nbytes / us / 1e6 / 8.0, 3)})
+
     for shape in ((256, 128, 768), (32, 128, 3072)):
         B, T, H = shape
         n = B * T * H
@@ -63,28 +70,36 @@ def main():
         mn, mx = torch.full((), float("inf"), device=dev), torch.full((), float("-inf"), device=dev)
         sink = ops.QParamSink(torch.ones(1, device=dev), torch.zeros(1, device=dev))
 
-        def add(name, dtype, fn, nbytes):
-            us = timed(fn, args.iters, args.reps)
-            rows.append({"shape": list(shape), "call": name, "dtype": dtype, "us": round(us, 2), "MB": round(nbytes / 1e6, 1),
-                         "TB_s": round(nbytes / us / 1e6, 2), "share_8TBs": round(nbytes / us / 1e6 / 8.0, 3)})
-
-        add("fake_quant fixed (fp32 kernel)", "fp32", lambda: ops.fake_quant_per_tensor(x32, s, zi, 0, 255), 8 * n)
-        add("fake_quant lsq+ (fp32 kernel)", "fp32",
+        add(shape, "fake_quant fixed (fp32 kernel)", "fp32", lambda: ops.fake_quant_per_tensor(x32, s, zi, 0, 255), 8 * n)
+        add(shape, "fake_quant lsq+ (fp32 kernel)", "fp32",
             lambda: ops.fake_quant_per_tensor(x32, s, zf, 0, 255, ops.PARAM_LSQPLUS, 0.01), 8 * n)
-        add("observe flat (fp32 kernel)", "fp32", lambda: ops.observe_flat(x32, ops.UPDATE_AVERAGE, 0, mn, mx, 0, 255, False, sink), 4 * n)
-        add("observe tokens (fp32 kernels)", "fp32",
+        add(shape, "observe flat (fp32 kernel)", "fp32", lambda: ops.observe_flat(x32, ops.UPDATE_AVERAGE, 0, mn, mx, 0, 255, False, sink), 4 * n)
+        add(shape, "observe tokens (fp32 kernels)", "fp32",
             lambda: ops.observe_tokens(x32, 1, lens, True, 0.99, ops.UPDATE_AVERAGE, 0, mn, mx, 0, 255, False, sink), 4 * n * valid)
         for dn, dt in (("bf16", torch.bfloat16), ("f16", torch.float16)):
             xh = x32.to(dt)
-            add("chain (in-dtype)", dn, lambda: ops.fake_quant_chain_lowp(xh, s, zi, 0, 255), 4 * n)
-            add("widen lsq+ (fp32 out)", dn, lambda: ops.fake_quant_per_tensor_widen(xh, s, zf, 0, 255, ops.PARAM_LSQPLUS, 0.01), 6 * n)
-            add("observe flat", dn, lambda: ops.observe_flat_lowp(xh, ops.UPDATE_AVERAGE, 0, mn, mx, 0, 255, False, sink), 2 * n)
-            add("observe tokens", dn,
+            add(shape, "chain (in-dtype)", dn, lambda: ops.fake_quant_chain_lowp(xh, s, zi, 0, 255), 4 * n)
+            add(shape, "widen lsq+ (fp32 out)", dn, lambda: ops.fake_quant_per_tensor_widen(xh, s, zf, 0, 255, ops.PARAM_LSQPLUS, 0.01), 6 * n)
+            add(shape, "observe flat", dn, lambda: ops.observe_flat_lowp(xh, ops.UPDATE_AVERAGE, 0, mn, mx, 0, 255, False, sink), 2 * n)
+            add(shape, "observe tokens", dn,
                 lambda: ops.observe_tokens_lowp(xh, 1, lens, True, 0.99, ops.UPDATE_AVERAGE, 0, mn, mx, 0, 255, False, sink),
                 2 * n * valid)
-            add("baseline .float()->fp32 kernel->.to() (not bit-equal)", dn,
+            add(shape, "baseline .float()->fp32 kernel->.to() (not bit-equal)", dn,
                 lambda: ops.fake_quant_per_tensor(xh.float(), s, zi, 0, 255).to(dt), 20 * n)
         del x32
+    shape = (3072, 768)
+    w32 = torch.randn(shape, generator=gen).to(dev) * 0.05
+    cs = torch.full((shape[0],), 0.0007, device=dev)
+    cz = torch.zeros(shape[0], dtype=torch.int32, device=dev)
+    cmn, cmx = torch.full((shape[0],), float("inf"), device=dev), torch.full((shape[0],), float("-inf"), device=dev)
+    n = w32.numel()
+    add(shape, "observe channels (fp32 kernel)", "fp32",
+        lambda: ops.observe_channels(w32, 0, ops.UPDATE_RUNNING, 0, cmn, cmx, -128, 127, True), 4 * n)
+    add(shape, "fake_quant per-channel (fp32 kernel)", "fp32", lambda: ops.fake_quant_per_channel(w32, cs, cz, 0, -128, 127), 8 * n)
+    for dn, dt in (("bf16", torch.bfloat16), ("f16", torch.float16)):
+        wh = w32.to(dt)
+        add(shape, "observe channels", dn, lambda: ops.observe_channels_lowp(wh, 0, ops.UPDATE_RUNNING, 0, cmn, cmx, -128, 127, True), 2 * n)
+        add(shape, "widen per-channel (fp32 out)", dn, lambda: ops.fake_quant_per_channel_widen(wh, cs, cz, 0, -128, 127), 6 * n)
     for r in rows:
         print(json.dumps(r))
 
