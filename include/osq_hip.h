@@ -35,8 +35,10 @@ typedef void* osq_stream;
 /* Bumped whenever a signature or the workspace layout changes; the Python host refuses a library whose
  * osq_abi_version() differs from the number it was written against (a stale libosq_hip.so must be rebuilt).
  * 5: the LSQ / LSQ+ backward takes its summation order as an argument (`lanes` / `sum_lanes`).
- * 8: osq_attention_softmax_fake_quant, OSQ_TIME_ATTENTION_SOFTMAX. */
-#define OSQ_ABI_VERSION 9
+ * 8: osq_attention_softmax_fake_quant, OSQ_TIME_ATTENTION_SOFTMAX.
+ * 10: osq_observe_flat / _channels, osq_token_minmax, osq_observe_tokens and osq_fake_quant_per_channel take `dtype` first;
+ *     their separate 16-bit twins are gone. */
+#define OSQ_ABI_VERSION 10
 
 typedef enum osq_status {
     OSQ_OK = 0,
@@ -74,6 +76,12 @@ typedef enum osq_update_rule {
     OSQ_UPDATE_RUNNING = 1,  /* observer.py:143-144  min_val = min(min_val, cur) ...    */
     OSQ_UPDATE_AVERAGE = 2   /* observer.py:194-202  (m*cnt + cur) / (cnt+1)            */
 } osq_update_rule;
+
+/* Element type of the `const void*` / `void*` tensor data of the entry points with a `dtype` argument; any other value
+ * is rejected (-1) before anything else is looked at.  The 16-bit types are read as they lie and widened in registers
+ * (the reference widens first: x_orig.to(min_val.dtype), observer.py:134; torch promotes bf16 / fp16 x with fp32
+ * parameters to fp32): statistics, scale, zero point and fp32 outputs are word-equal to the fp32 call on x widened. */
+typedef enum osq_dtype { OSQ_DTYPE_F32 = 0, OSQ_DTYPE_BF16 = 1, OSQ_DTYPE_F16 = 2 } osq_dtype;
 
 /*
  * Logical [batch, tokens, feat_outer, feat_inner] view of an activation, i.e. the
@@ -229,9 +237,10 @@ int osq_fake_quant_kv_append(const osq_kv_append_site* sites, int n_sites, int64
                              int64_t head_dim, osq_stream stream);
 
 /* util_quant.py:18-26 fake_quantize_per_channel_affine (and the per-channel learnable
- * forwards :37-45, :58-67).  x is contiguous and viewed as [outer, channels, inner]
- * with ch_axis in the middle; scale/zero_point have `channels` entries. */
-int osq_fake_quant_per_channel(const float* x, float* y, float* x_quant,
+ * forwards :37-45, :58-67).  x is contiguous `dtype` data viewed as [outer, channels, inner]
+ * with ch_axis in the middle; scale/zero_point have `channels` entries; y is fp32.  x_quant (nullable, the
+ * integers before dequantisation) exists for fp32 x only: non-NULL with a 16-bit dtype is an invalid argument. */
+int osq_fake_quant_per_channel(int dtype, const void* x, float* y, float* x_quant,
                                int64_t outer, int64_t channels, int64_t inner,
                                const float* scale, const void* zero_point, int zp_type,
                                int mode, float grad_factor, int quant_min, int quant_max,
@@ -287,13 +296,13 @@ int osq_calculate_qparams(const float* min_val, const float* max_val, int64_t n,
                           float* scale_out, void* zero_point_out, int zp_type,
                           osq_stream stream);
 
-/* observer.py:139 torch._aminmax(x) over n contiguous values, followed by the
+/* observer.py:139 torch._aminmax(x) over n contiguous values of `dtype`, followed by the
  * running-statistic rule of the observer (MinMaxObserver :143-144, Avg* :194-202)
  * and, when scale_out != NULL, calculate_qparams (:101-119) -- what
  * QuantizeBase.forward does after observer(...) at fake_quant.py:108-116.
  * cur_minmax (nullable): the batch's own (min, max), 2 floats.  `cnt` is the
  * observer's batch counter BEFORE this call (host int, observer.py:198). */
-int osq_observe_flat(const float* x, int64_t n,
+int osq_observe_flat(int dtype, const void* x, int64_t n,
                      int update_rule, int64_t cnt, float* min_val, float* max_val,
                      float* cur_minmax,
                      int quant_min, int quant_max, int symmetric,
@@ -301,19 +310,19 @@ int osq_observe_flat(const float* x, int64_t n,
                      void* workspace, osq_stream stream);
 
 /* observer.py:141-144 per-channel min/max: _transform_to_ch_axis + _aminmax(y, 1) +
- * running min/max, x contiguous viewed as [outer, channels, inner]; optional
+ * running min/max, x contiguous `dtype` data viewed as [outer, channels, inner]; optional
  * qparams per channel.  min_val/max_val hold `channels` entries. */
-int osq_observe_channels(const float* x, int64_t outer, int64_t channels, int64_t inner,
+int osq_observe_channels(int dtype, const void* x, int64_t outer, int64_t channels, int64_t inner,
                          int update_rule, int64_t cnt, float* min_val, float* max_val,
                          int quant_min, int quant_max, int symmetric,
                          float* scale_out, void* zero_point_out, int zp_type,
                          osq_stream stream);
 
 /* observer.py:64-65 after observer.py:72-84: per-token min and max over the feature
- * axes, for the tokens t < lengths[b] only (lengths == NULL: every token,
+ * axes of `dtype` data, for the tokens t < lengths[b] only (lengths == NULL: every token,
  * observer.py:86-98).  token_min/token_max have batch*tokens slots, slot b*T+t;
  * slots of padded tokens are left untouched. */
-int osq_token_minmax(const float* x, const osq_token_view* view, const int64_t* lengths,
+int osq_token_minmax(int dtype, const void* x, const osq_token_view* view, const int64_t* lengths,
                      float* token_min, float* token_max, osq_stream stream);
 
 /* osq_token_minmax for MANY tensors in ONE launch (the observer passes of a calibration forward call ~100 sites of 6-50 MB
@@ -358,7 +367,7 @@ int osq_token_range_finalize(const float* token_min, const float* token_max,
  * observation (AvgPruneMinMaxObserver / AvgMinMaxObserver / MinMaxObserver.forward with a mask,
  * observer.py:130-145, 184-203, 214-237) behind one call of the host binding.  token_min/token_max:
  * caller-owned scratch of batch*tokens floats each (their contents are the per-token extrema afterwards). */
-int osq_observe_tokens(const float* x, const osq_token_view* view, const int64_t* lengths,
+int osq_observe_tokens(int dtype, const void* x, const osq_token_view* view, const int64_t* lengths,
                        float* token_min, float* token_max,
                        int prune, double percentile,
                        int update_rule, int64_t cnt, float* min_val, float* max_val,
@@ -679,10 +688,11 @@ int osq_attention_softmax_fake_quant(const float* scores, const float* mask, int
                                      int mode, float grad_factor, int quant_min, int quant_max,
                                      osq_stream stream);
 
-/* ------------------------------------------------------------------ bf16 / fp16 inputs (lowp.hip, observer.hip, fake_quant.hip) */
+/* ------------------------------------------------------------------ bf16 / fp16 only (lowp.hip) */
 
-/* Element type of the `const void*` / `void*` data of the entry points below; any other value is rejected (-1). */
-typedef enum osq_dtype { OSQ_DTYPE_BF16 = 1, OSQ_DTYPE_F16 = 2 } osq_dtype;
+/* The three entry points below take OSQ_DTYPE_BF16 / OSQ_DTYPE_F16 only (OSQ_DTYPE_F32 is rejected) and are not folded
+ * into the fp32 ones: the in-dtype chain and its backward have no fp32 counterpart (every op is rounded to x's dtype), and
+ * the per-tensor widening forward has its own kernel, access pattern and tuning constants. */
 
 /* FixedFakeQuantize per-tensor (util_quant.py:11-15 called with Python numbers or 0-dim tensors) in the input dtype:
  * every op of the chain is rounded to x's dtype, as torch's CPU kernels do --
@@ -703,23 +713,6 @@ int osq_fake_quant_chain_backward_lowp(int dtype, const void* x, const void* gra
  * arguments, OSQ_PARAM_SANITIZE included.  One launch, 2 B read + 4 B written per element. */
 int osq_fake_quant_per_tensor_widen(int dtype, const void* x, float* y, int64_t n, float* scale, void* zero_point, int zp_type,
                                     int mode, float grad_factor, int quant_min, int quant_max, osq_stream stream);
-
-/* Per-channel form of the above: x contiguous [outer, channels, inner] of dtype, y fp32, word-equal to
- * osq_fake_quant_per_channel on x widened. */
-int osq_fake_quant_per_channel_widen(int dtype, const void* x, float* y, int64_t outer, int64_t channels, int64_t inner,
-                                     const float* scale, const void* zero_point, int zp_type, int mode, float grad_factor,
-                                     int quant_min, int quant_max, osq_stream stream);
-
-/* osq_observe_flat / osq_observe_channels / osq_token_minmax reading dtype elements: the statistics (fp32), scale and
- * zero point are those of the fp32 entry point on x widened (the reference widens first: x_orig.to(min_val.dtype), observer.py:134). */
-int osq_observe_flat_lowp(int dtype, const void* x, int64_t n, int update_rule, int64_t cnt, float* min_val, float* max_val,
-                          float* cur_minmax, int quant_min, int quant_max, int symmetric, float* scale_out,
-                          void* zero_point_out, int zp_type, void* workspace, osq_stream stream);
-int osq_observe_channels_lowp(int dtype, const void* x, int64_t outer, int64_t channels, int64_t inner, int update_rule,
-                              int64_t cnt, float* min_val, float* max_val, int quant_min, int quant_max, int symmetric,
-                              float* scale_out, void* zero_point_out, int zp_type, osq_stream stream);
-int osq_token_minmax_lowp(int dtype, const void* x, const osq_token_view* view, const int64_t* lengths, float* token_min,
-                          float* token_max, osq_stream stream);
 
 #ifdef __cplusplus
 }

@@ -24,9 +24,9 @@ TIME_LAYERNORM, TIME_FUSED_STEP = 6, 7
 TIME_FAKE_QUANT_STRIDED, TIME_FAKE_QUANT_CHANNEL, TIME_OBSERVE_CHANNELS, TIME_TOKEN_MINMAX_MULTI, TIME_MSEFAST_ROWS = 8, 9, 10, 11, 12
 TIME_OBSERVE_TOKENS, TIME_ATTENTION_SOFTMAX = 13, 14
 UPDATE_NONE, UPDATE_RUNNING, UPDATE_AVERAGE = 0, 1, 2
-DTYPE_BF16, DTYPE_F16 = 1, 2   # osq_dtype: element type of the bf16 / fp16 entry points (lowp.hip, observer.hip, fake_quant.hip)
+DTYPE_F32, DTYPE_BF16, DTYPE_F16 = 0, 1, 2   # osq_dtype: element type of the data behind the entry points with a `dtype` argument
 ERR_UNSUPPORTED = -3          # OSQ_ERR_UNSUPPORTED: nothing was launched, the caller takes its other path
-ABI_VERSION = 9               # OSQ_ABI_VERSION of include/osq_hip.h this file was written against
+ABI_VERSION = 10              # OSQ_ABI_VERSION of include/osq_hip.h this file was written against
 
 _P = ctypes.c_void_p
 _I = ctypes.c_int
@@ -85,7 +85,7 @@ SIGNATURES = {
                                                _P, _P, _I, _I, _F, _I, _I, _P]),
     "osq_fake_quant_headsplit_multi": (_I, [ctypes.POINTER(HeadSplitSite), _I, _L, _L, _L, _L, _P]),
     "osq_fake_quant_kv_append": (_I, [ctypes.POINTER(KvAppendSite), _I, _L, _L, _L, _P]),
-    "osq_fake_quant_per_channel": (_I, [_P, _P, _P, _L, _L, _L, _P, _P, _I, _I, _F, _I, _I, _P]),
+    "osq_fake_quant_per_channel": (_I, [_I, _P, _P, _P, _L, _L, _L, _P, _P, _I, _I, _F, _I, _I, _P]),
     "osq_fake_quant_weights_multi": (_I, [_P, _P, _I, _L, _P]),
     "osq_lsq_backward_per_tensor": (_I, [_P, _P, _P, _L, _P, _P, _I, _I, _F, _I, _I, _P, _P, _P, _P]),
     "osq_ordered_sum_scratch_bytes": (ctypes.c_size_t, [_L, _I]),
@@ -93,12 +93,12 @@ SIGNATURES = {
     "osq_lsq_backward_per_channel": (_I, [_P, _P, _P, _L, _L, _L, _P, _P, _I, _I, _F, _I, _I, _P, _P, _I, _P]),
     "osq_lsq_sanitize": (_I, [_P, _P, _L, _F, _I, _I, _P]),
     "osq_calculate_qparams": (_I, [_P, _P, _L, _I, _I, _I, _P, _P, _I, _P]),
-    "osq_observe_flat": (_I, [_P, _L, _I, _L, _P, _P, _P, _I, _I, _I, _P, _P, _I, _P, _P]),
-    "osq_observe_channels": (_I, [_P, _L, _L, _L, _I, _L, _P, _P, _I, _I, _I, _P, _P, _I, _P]),
-    "osq_token_minmax": (_I, [_P, ctypes.POINTER(TokenView), _P, _P, _P, _P]),
+    "osq_observe_flat": (_I, [_I, _P, _L, _I, _L, _P, _P, _P, _I, _I, _I, _P, _P, _I, _P, _P]),
+    "osq_observe_channels": (_I, [_I, _P, _L, _L, _L, _I, _L, _P, _P, _I, _I, _I, _P, _P, _I, _P]),
+    "osq_token_minmax": (_I, [_I, _P, ctypes.POINTER(TokenView), _P, _P, _P, _P]),
     "osq_token_minmax_multi": (_I, [_P, _P, _I, _L, _P]),
     "osq_token_range_finalize": (_I, [_P, _P, _L, _L, _P, _I, _D, _I, _L, _P, _P, _P, _I, _I, _I, _P, _P, _I, _P, _P, _P]),
-    "osq_observe_tokens": (_I, [_P, ctypes.POINTER(TokenView), _P, _P, _P, _I, _D, _I, _L, _P, _P, _P, _I, _I, _I, _P, _P, _I, _P, _P, _P]),
+    "osq_observe_tokens": (_I, [_I, _P, ctypes.POINTER(TokenView), _P, _P, _P, _I, _D, _I, _L, _P, _P, _P, _I, _I, _I, _P, _P, _I, _P, _P, _P]),
     "osq_observe_tokens_fake_quant": (_I, [_P, ctypes.POINTER(TokenView), _P, _P, _P, _I, _D, _I, _L, _P, _P, _P, _I, _I, _I, _P, _P, _I,
                                            _P, _L, _I, _F, _P, _P, _P]),
     "osq_fused_step_status": (_I, [_P, ctypes.POINTER(_I), _P]),
@@ -143,10 +143,6 @@ SIGNATURES = {
     "osq_fake_quant_chain_lowp": (_I, [_I, _P, _P, _L, _P, _P, _I, _I, _I, _P]),
     "osq_fake_quant_chain_backward_lowp": (_I, [_I, _P, _P, _P, _L, _P, _P, _I, _I, _I, _P]),
     "osq_fake_quant_per_tensor_widen": (_I, [_I, _P, _P, _L, _P, _P, _I, _I, _F, _I, _I, _P]),
-    "osq_fake_quant_per_channel_widen": (_I, [_I, _P, _P, _L, _L, _L, _P, _P, _I, _I, _F, _I, _I, _P]),
-    "osq_observe_flat_lowp": (_I, [_I, _P, _L, _I, _L, _P, _P, _P, _I, _I, _I, _P, _P, _I, _P, _P]),
-    "osq_observe_channels_lowp": (_I, [_I, _P, _L, _L, _L, _I, _L, _P, _P, _I, _I, _I, _P, _P, _I, _P]),
-    "osq_token_minmax_lowp": (_I, [_I, _P, ctypes.POINTER(TokenView), _P, _P, _P, _P]),
 }
 
 _lib = None

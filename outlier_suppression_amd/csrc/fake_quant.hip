@@ -1008,8 +1008,7 @@ extern "C" int osq_fake_quant_kv_append(const osq_kv_append_site* sites, int n_s
     return check_launch("fake_quant_kv_append");
 }
 
-// per-channel launch: T = float behind osq_fake_quant_per_channel (x_quant optional), __bf16 / _Float16 behind the
-// widening entry point (x_quant == nullptr); y is fp32 for every T
+// per-channel launch: T = float (x_quant optional), __bf16 or _Float16 (x_quant == nullptr); y is fp32 for every T
 template <typename T>
 static void launch_fq_channel(const T* x, float* y, float* x_quant, int64_t outer, int64_t channels, int64_t inner,
                               const float* scale, const void* zero_point, int zp_type, int mode, float grad_factor, int quant_min,
@@ -1049,31 +1048,23 @@ static void launch_fq_channel(const T* x, float* y, float* x_quant, int64_t oute
     }
 }
 
-extern "C" int osq_fake_quant_per_channel(const float* x, float* y, float* x_quant,
+extern "C" int osq_fake_quant_per_channel(int dtype, const void* x, float* y, float* x_quant,
                                           int64_t outer, int64_t channels, int64_t inner,
                                           const float* scale, const void* zero_point, int zp_type,
                                           int mode, float grad_factor, int quant_min, int quant_max,
                                           osq_stream stream) {
+    OSQ_REQUIRE(known_dtype(dtype), "fake_quant_per_channel: unknown dtype");
     OSQ_REQUIRE(outer >= 0 && channels >= 0 && inner >= 0 && scale && zero_point, "fake_quant_per_channel: bad argument");
+    if (lowp_dtype(dtype)) {      // zp_type and mode are checked for 16-bit x only: the fp32 call never looked at them
+        OSQ_REQUIRE(!x_quant, "fake_quant_per_channel: x_quant needs fp32 x");
+        OSQ_REQUIRE(zp_type == OSQ_ZP_INT32 || zp_type == OSQ_ZP_FLOAT32, "fake_quant_per_channel: bad zp_type");
+        OSQ_REQUIRE(mode >= OSQ_PARAM_FIXED && mode <= OSQ_PARAM_LSQPLUS, "fake_quant_per_channel: bad mode");
+    }
     if (outer * channels * inner == 0) return OSQ_OK;
     OSQ_REQUIRE(x && y, "fake_quant_per_channel: null tensor");
-    launch_fq_channel(x, y, x_quant, outer, channels, inner, scale, zero_point, zp_type, mode, grad_factor, quant_min, quant_max,
-                      static_cast<hipStream_t>(stream));
+    OSQ_DTYPE_DISPATCH(dtype, launch_fq_channel(static_cast<const T*>(x), y, x_quant, outer, channels, inner, scale, zero_point,
+                                                zp_type, mode, grad_factor, quant_min, quant_max, static_cast<hipStream_t>(stream)));
     return check_launch("fake_quant_per_channel");
-}
-
-extern "C" int osq_fake_quant_per_channel_widen(int dtype, const void* x, float* y, int64_t outer, int64_t channels, int64_t inner,
-                                                const float* scale, const void* zero_point, int zp_type, int mode,
-                                                float grad_factor, int quant_min, int quant_max, osq_stream stream) {
-    OSQ_REQUIRE(known_dtype(dtype), "fake_quant_per_channel_widen: unknown dtype");
-    OSQ_REQUIRE(outer >= 0 && channels >= 0 && inner >= 0 && scale && zero_point, "fake_quant_per_channel_widen: bad argument");
-    OSQ_REQUIRE(zp_type == OSQ_ZP_INT32 || zp_type == OSQ_ZP_FLOAT32, "fake_quant_per_channel_widen: bad zp_type");
-    OSQ_REQUIRE(mode >= OSQ_PARAM_FIXED && mode <= OSQ_PARAM_LSQPLUS, "fake_quant_per_channel_widen: bad mode");
-    if (outer * channels * inner == 0) return OSQ_OK;
-    OSQ_REQUIRE(x && y, "fake_quant_per_channel_widen: null tensor");
-    OSQ_LOWP_DISPATCH(dtype, launch_fq_channel(static_cast<const T*>(x), y, nullptr, outer, channels, inner, scale, zero_point,
-                                               zp_type, mode, grad_factor, quant_min, quant_max, static_cast<hipStream_t>(stream)));
-    return check_launch("fake_quant_per_channel_widen");
 }
 
 extern "C" int osq_lsq_backward_per_tensor(const float* x, const float* grad_out, float* grad_x, int64_t n,

@@ -220,7 +220,7 @@ using namespace osq;
 
 extern "C" int osq_fake_quant_chain_lowp(int dtype, const void* x, void* y, int64_t n, const float* scale,
                                          const void* zero_point, int zp_type, int quant_min, int quant_max, osq_stream stream) {
-    OSQ_REQUIRE(known_dtype(dtype), "fake_quant_chain_lowp: unknown dtype");
+    OSQ_REQUIRE(lowp_dtype(dtype), "fake_quant_chain_lowp: unknown dtype");
     OSQ_REQUIRE(n >= 0 && (n == 0 || (x && y)) && scale && zero_point, "fake_quant_chain_lowp: null pointer or n < 0");
     OSQ_REQUIRE(zp_type == OSQ_ZP_INT32 || zp_type == OSQ_ZP_FLOAT32, "fake_quant_chain_lowp: bad zp_type");
     if (n == 0) return OSQ_OK;
@@ -232,7 +232,7 @@ extern "C" int osq_fake_quant_chain_lowp(int dtype, const void* x, void* y, int6
 extern "C" int osq_fake_quant_chain_backward_lowp(int dtype, const void* x, const void* grad_out, void* grad_x, int64_t n,
                                                   const float* scale, const void* zero_point, int zp_type, int quant_min,
                                                   int quant_max, osq_stream stream) {
-    OSQ_REQUIRE(known_dtype(dtype), "fake_quant_chain_backward_lowp: unknown dtype");
+    OSQ_REQUIRE(lowp_dtype(dtype), "fake_quant_chain_backward_lowp: unknown dtype");
     OSQ_REQUIRE(n >= 0 && (n == 0 || (x && grad_out && grad_x)) && scale && zero_point,
                 "fake_quant_chain_backward_lowp: null pointer or n < 0");
     OSQ_REQUIRE(zp_type == OSQ_ZP_INT32 || zp_type == OSQ_ZP_FLOAT32, "fake_quant_chain_backward_lowp: bad zp_type");
@@ -246,7 +246,7 @@ extern "C" int osq_fake_quant_chain_backward_lowp(int dtype, const void* x, cons
 extern "C" int osq_fake_quant_per_tensor_widen(int dtype, const void* x, float* y, int64_t n, float* scale, void* zero_point,
                                                int zp_type, int mode, float grad_factor, int quant_min, int quant_max,
                                                osq_stream stream) {
-    OSQ_REQUIRE(known_dtype(dtype), "fake_quant_per_tensor_widen: unknown dtype");
+    OSQ_REQUIRE(lowp_dtype(dtype), "fake_quant_per_tensor_widen: unknown dtype");
     OSQ_REQUIRE(n >= 0 && (n == 0 || (x && y)) && scale && zero_point, "fake_quant_per_tensor_widen: null pointer or n < 0");
     OSQ_REQUIRE(zp_type == OSQ_ZP_INT32 || zp_type == OSQ_ZP_FLOAT32, "fake_quant_per_tensor_widen: bad zp_type");
     OSQ_REQUIRE((mode & ~(OSQ_PARAM_MODE_MASK | OSQ_PARAM_SANITIZE)) == 0 && (mode & OSQ_PARAM_MODE_MASK) <= OSQ_PARAM_LSQPLUS,

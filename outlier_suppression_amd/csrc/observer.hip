@@ -1314,25 +1314,12 @@ extern "C" int osq_replay_statistics(const float* table, int n_batches, int n_qu
     return check_launch("replay_statistics");
 }
 
-// ---- the min / max entry points: one body per pair, T = float behind the fp32 name, __bf16 / _Float16 behind `_lowp`;
-// `what` = the entry point's name, for osq_last_error()
-#define OSQ_REQUIRE_AT(cond, what, msg)                  \
-    do {                                                 \
-        if (!(cond)) {                                   \
-            ::osq::set_error("%s: %s", what, msg);       \
-            return OSQ_ERR_INVALID_ARGUMENT;             \
-        }                                                \
-    } while (0)
-
+// ---- the min / max entry points: T = float, __bf16 or _Float16 as the call's `dtype` says (OSQ_DTYPE_DISPATCH)
 template <typename T>
-static int observe_flat(const char* what, const T* x, int64_t n, int update_rule, int64_t cnt, float* min_val, float* max_val,
-                        float* cur_minmax,
+static int observe_flat(const T* x, int64_t n, int update_rule, int64_t cnt, float* min_val, float* max_val, float* cur_minmax,
                         int quant_min, int quant_max, int symmetric, float* scale_out, void* zero_point_out, int zp_type,
                         void* workspace, osq_stream stream) {
     typedef Granule<T> G;
-    const char* why = "";
-    OSQ_REQUIRE_AT(n > 0 && x && workspace, what, "empty tensor or null pointer");
-    OSQ_REQUIRE_AT(check_finish_args(update_rule, min_val, max_val, &why), what, why);
     const Finish fin{update_rule, cnt, min_val, max_val, cur_minmax, quant_min, quant_max, symmetric, scale_out,
                      zero_point_out, zp_type};
     const Workspace ws(workspace);
@@ -1341,37 +1328,28 @@ static int observe_flat(const char* what, const T* x, int64_t n, int update_rule
     const TimingHook th = take_timing_hook(OSQ_TIME_OBSERVE_FLAT);
     hipExtLaunchKernelGGL(observe_flat_kernel<T>, dim3(grid), dim3(kThreads), 0, static_cast<hipStream_t>(stream), th.start, th.stop,
                           0, x, ng, n, ws.floats(kFamObserveFlat), ws.counter(kFamObserveFlat), fin);
-    return check_launch(what);
+    return check_launch("observe_flat");
 }
 
-extern "C" int osq_observe_flat(const float* x, int64_t n, int update_rule, int64_t cnt, float* min_val, float* max_val,
+extern "C" int osq_observe_flat(int dtype, const void* x, int64_t n, int update_rule, int64_t cnt, float* min_val, float* max_val,
                                 float* cur_minmax, int quant_min, int quant_max, int symmetric, float* scale_out,
                                 void* zero_point_out, int zp_type, void* workspace, osq_stream stream) {
-    return observe_flat("observe_flat", x, n, update_rule, cnt, min_val, max_val, cur_minmax, quant_min, quant_max, symmetric, scale_out,
-                        zero_point_out, zp_type, workspace, stream);
-}
-
-extern "C" int osq_observe_flat_lowp(int dtype, const void* x, int64_t n, int update_rule, int64_t cnt, float* min_val,
-                                     float* max_val, float* cur_minmax, int quant_min, int quant_max, int symmetric,
-                                     float* scale_out, void* zero_point_out, int zp_type, void* workspace, osq_stream stream) {
-    OSQ_REQUIRE(known_dtype(dtype), "observe_flat_lowp: unknown dtype");
+    const char* why = "";
+    OSQ_REQUIRE(known_dtype(dtype), "observe_flat: unknown dtype");
+    OSQ_REQUIRE(n > 0 && x && workspace, "observe_flat: empty tensor or null pointer");
+    OSQ_REQUIRE(check_finish_args(update_rule, min_val, max_val, &why), why);
     int rc;
-    OSQ_LOWP_DISPATCH(dtype, rc = observe_flat("observe_flat_lowp", static_cast<const T*>(x), n, update_rule, cnt, min_val, max_val,
-                                               cur_minmax, quant_min, quant_max, symmetric, scale_out, zero_point_out, zp_type,
-                                               workspace, stream));
+    OSQ_DTYPE_DISPATCH(dtype, rc = observe_flat(static_cast<const T*>(x), n, update_rule, cnt, min_val, max_val, cur_minmax,
+                                                quant_min, quant_max, symmetric, scale_out, zero_point_out, zp_type, workspace,
+                                                stream));
     return rc;
 }
 
 template <typename T>
-static int observe_channels(const char* what, const T* x, int64_t outer, int64_t channels, int64_t inner, int update_rule,
-                            int64_t cnt,
+static int observe_channels(const T* x, int64_t outer, int64_t channels, int64_t inner, int update_rule, int64_t cnt,
                             float* min_val, float* max_val, int quant_min, int quant_max, int symmetric, float* scale_out,
                             void* zero_point_out, int zp_type, osq_stream stream) {
     typedef Granule<T> G;
-    const char* why = "";
-    OSQ_REQUIRE_AT(outer > 0 && channels > 0 && inner > 0 && x, what, "empty tensor or null pointer");
-    OSQ_REQUIRE_AT(channels < (1ll << 31), what, "too many channels");
-    OSQ_REQUIRE_AT(check_finish_args(update_rule, min_val, max_val, &why), what, why);
     const Finish fin{update_rule, cnt, min_val, max_val, nullptr, quant_min, quant_max, symmetric, scale_out,
                      zero_point_out, zp_type};
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -1384,36 +1362,29 @@ static int observe_channels(const char* what, const T* x, int64_t outer, int64_t
         hipLaunchKernelGGL(observe_channels_kernel<T>, dim3(static_cast<unsigned>(channels)), dim3(kThreads), 0, st, x, outer,
                            channels, inner, fin);
     }
-    return check_launch(what);
+    return check_launch("observe_channels");
 }
 
-extern "C" int osq_observe_channels(const float* x, int64_t outer, int64_t channels, int64_t inner, int update_rule, int64_t cnt,
-                                    float* min_val, float* max_val, int quant_min, int quant_max, int symmetric,
+extern "C" int osq_observe_channels(int dtype, const void* x, int64_t outer, int64_t channels, int64_t inner, int update_rule,
+                                    int64_t cnt, float* min_val, float* max_val, int quant_min, int quant_max, int symmetric,
                                     float* scale_out, void* zero_point_out, int zp_type, osq_stream stream) {
-    return observe_channels("observe_channels", x, outer, channels, inner, update_rule, cnt, min_val, max_val, quant_min, quant_max, symmetric,
-                            scale_out, zero_point_out, zp_type, stream);
-}
-
-extern "C" int osq_observe_channels_lowp(int dtype, const void* x, int64_t outer, int64_t channels, int64_t inner,
-                                         int update_rule, int64_t cnt, float* min_val, float* max_val, int quant_min,
-                                         int quant_max, int symmetric, float* scale_out, void* zero_point_out, int zp_type,
-                                         osq_stream stream) {
-    OSQ_REQUIRE(known_dtype(dtype), "observe_channels_lowp: unknown dtype");
+    const char* why = "";
+    OSQ_REQUIRE(known_dtype(dtype), "observe_channels: unknown dtype");
+    OSQ_REQUIRE(outer > 0 && channels > 0 && inner > 0 && x, "observe_channels: empty tensor or null pointer");
+    OSQ_REQUIRE(channels < (1ll << 31), "observe_channels: too many channels");
+    OSQ_REQUIRE(check_finish_args(update_rule, min_val, max_val, &why), why);
     int rc;
-    OSQ_LOWP_DISPATCH(dtype, rc = observe_channels("observe_channels_lowp", static_cast<const T*>(x), outer, channels, inner,
-                                                   update_rule, cnt, min_val, max_val, quant_min, quant_max, symmetric, scale_out,
-                                                   zero_point_out, zp_type, stream));
+    OSQ_DTYPE_DISPATCH(dtype, rc = observe_channels(static_cast<const T*>(x), outer, channels, inner, update_rule, cnt, min_val,
+                                                    max_val, quant_min, quant_max, symmetric, scale_out, zero_point_out, zp_type,
+                                                    stream));
     return rc;
 }
 
 template <typename T>
-static int token_minmax(const char* what, const T* x, const osq_token_view* view, const int64_t* lengths, float* token_min,
-                        float* token_max,
+static int token_minmax(const T* x, const osq_token_view& v, const int64_t* lengths, float* token_min, float* token_max,
                         osq_stream stream) {
     constexpr int kPer = Granule<T>::kPer;
-    OSQ_REQUIRE_AT(x && view && token_min && token_max, what, "null pointer");
-    const osq_token_view v = *view;
-    OSQ_REQUIRE_AT(v.batch > 0 && v.tokens > 0 && v.feat_outer > 0 && v.feat_inner > 0, what, "empty view");
+    OSQ_REQUIRE(v.batch > 0 && v.tokens > 0 && v.feat_outer > 0 && v.feat_inner > 0, "token_minmax: empty view");
     hipStream_t st = static_cast<hipStream_t>(stream);
     // 16-byte path: whole granules and 16-byte aligned rows; the sample index is gridDim.y
     const bool vec = v.stride_inner == 1 && v.feat_inner % kPer == 0 && aligned16(x) && v.stride_batch % kPer == 0 &&
@@ -1439,20 +1410,15 @@ static int token_minmax(const char* what, const T* x, const osq_token_view* view
         hipLaunchKernelGGL(token_minmax_generic_kernel<T>, dim3(grid), dim3(kThreads), 0, st, x, v, lengths, token_min,
                            token_max);
     }
-    return check_launch(what);
+    return check_launch("token_minmax");
 }
 
-extern "C" int osq_token_minmax(const float* x, const osq_token_view* view, const int64_t* lengths,
+extern "C" int osq_token_minmax(int dtype, const void* x, const osq_token_view* view, const int64_t* lengths,
                                 float* token_min, float* token_max, osq_stream stream) {
-    return token_minmax("token_minmax", x, view, lengths, token_min, token_max, stream);
-}
-
-extern "C" int osq_token_minmax_lowp(int dtype, const void* x, const osq_token_view* view, const int64_t* lengths,
-                                     float* token_min, float* token_max, osq_stream stream) {
-    OSQ_REQUIRE(known_dtype(dtype), "token_minmax_lowp: unknown dtype");
+    OSQ_REQUIRE(known_dtype(dtype), "token_minmax: unknown dtype");
+    OSQ_REQUIRE(x && view && token_min && token_max, "token_minmax: null pointer");
     int rc;
-    OSQ_LOWP_DISPATCH(dtype, rc = token_minmax("token_minmax_lowp", static_cast<const T*>(x), view, lengths, token_min, token_max,
-                                               stream));
+    OSQ_DTYPE_DISPATCH(dtype, rc = token_minmax(static_cast<const T*>(x), *view, lengths, token_min, token_max, stream));
     return rc;
 }
 
@@ -1517,7 +1483,7 @@ extern "C" int osq_token_range_finalize(const float* token_min, const float* tok
     return check_launch("token_range_finalize");
 }
 
-extern "C" int osq_observe_tokens(const float* x, const osq_token_view* view, const int64_t* lengths,
+extern "C" int osq_observe_tokens(int dtype, const void* x, const osq_token_view* view, const int64_t* lengths,
                                   float* token_min, float* token_max,
                                   int prune, double percentile,
                                   int update_rule, int64_t cnt, float* min_val, float* max_val,
@@ -1525,8 +1491,10 @@ extern "C" int osq_observe_tokens(const float* x, const osq_token_view* view, co
                                   int quant_min, int quant_max, int symmetric,
                                   float* scale_out, void* zero_point_out, int zp_type,
                                   void* workspace, void* list_scratch, osq_stream stream) {
+    OSQ_REQUIRE(known_dtype(dtype), "observe_tokens: unknown dtype");
     OSQ_REQUIRE(x && view && token_min && token_max, "observe_tokens: null pointer");
-    const int rc = osq_token_minmax(x, view, lengths, token_min, token_max, stream);
+    int rc;
+    OSQ_DTYPE_DISPATCH(dtype, rc = token_minmax(static_cast<const T*>(x), *view, lengths, token_min, token_max, stream));
     if (rc != OSQ_OK) return rc;
     return osq_token_range_finalize(token_min, token_max, view->batch, view->tokens, lengths, prune, percentile,
                                     update_rule, cnt, min_val, max_val, cur_minmax, quant_min, quant_max, symmetric,
@@ -1653,9 +1621,9 @@ extern "C" int osq_observe_tokens_fake_quant(const float* x, const osq_token_vie
         }
         if (launched) return check_launch("observe_tokens_fake_quant(fused)");
     }
-    const int rc = osq_observe_tokens(x, view, lengths, token_min, token_max, prune, percentile, update_rule, cnt, min_val,
-                                      max_val, cur_minmax, quant_min, quant_max, symmetric, scale, zero_point, zp_type, workspace,
-                                      list_scratch, stream);
+    const int rc = osq_observe_tokens(OSQ_DTYPE_F32, x, view, lengths, token_min, token_max, prune, percentile, update_rule, cnt,
+                                      min_val, max_val, cur_minmax, quant_min, quant_max, symmetric, scale, zero_point, zp_type,
+                                      workspace, list_scratch, stream);
     if (rc != OSQ_OK) return rc;
     return osq_fake_quant_per_tensor(x, y, nullptr, n, scale, zero_point, zp_type, mode, grad_factor, quant_min, quant_max,
                                      stream);

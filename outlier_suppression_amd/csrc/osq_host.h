@@ -95,8 +95,10 @@ static inline int check_finish_args(int update_rule, const float* min_val, const
     return 1;
 }
 
-// the 16-bit entry points (`dtype` argument): CALL runs with T = __bf16 or _Float16
-static inline bool known_dtype(int dtype) { return dtype == OSQ_DTYPE_BF16 || dtype == OSQ_DTYPE_F16; }
+// the `dtype` argument (osq_dtype): CALL runs with T = float, __bf16 or _Float16.  Callers check known_dtype /
+// lowp_dtype first; the three 16-bit-only entry points (lowp.hip) use OSQ_LOWP_DISPATCH, which has no float branch.
+static inline bool lowp_dtype(int dtype) { return dtype == OSQ_DTYPE_BF16 || dtype == OSQ_DTYPE_F16; }
+static inline bool known_dtype(int dtype) { return dtype == OSQ_DTYPE_F32 || lowp_dtype(dtype); }
 #define OSQ_LOWP_DISPATCH(dtype, CALL) \
     do {                                 \
         if ((dtype) == OSQ_DTYPE_BF16) { \
@@ -106,6 +108,15 @@ static inline bool known_dtype(int dtype) { return dtype == OSQ_DTYPE_BF16 || dt
             typedef _Float16 T;          \
             CALL;                        \
         }                                \
+    } while (0)
+#define OSQ_DTYPE_DISPATCH(dtype, CALL) \
+    do {                                \
+        if ((dtype) == OSQ_DTYPE_F32) { \
+            typedef float T;            \
+            CALL;                       \
+        } else {                        \
+            OSQ_LOWP_DISPATCH(dtype, CALL); \
+        }                               \
     } while (0)
 
 // Caller-owned scratch: [8 x 4 KiB of ticket counters][8 x 64 KiB of partials][16 KiB + 64 B wide-finaliser state]

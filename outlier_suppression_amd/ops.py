@@ -27,8 +27,10 @@ def _check_f32(*tensors):
             raise TypeError(f"outlier_suppression_amd kernels compute in float32, got {t.dtype}")
 
 
-# bf16 / fp16 inputs (lowp.hip; the observer and per-channel ones in observer.hip / fake_quant.hip): their own entry points below; the fp32 functions keep rejecting them
+# bf16 / fp16 inputs: the min / max observers and per-channel fake-quant read all three element types (_elem_code); the in-dtype
+# chain and the per-tensor widening forward are 16-bit only (_lowp_code); every other function is fp32 only (_check_f32)
 LOWP_DTYPES = {torch.bfloat16: _hip.DTYPE_BF16, torch.float16: _hip.DTYPE_F16}
+_ELEM_CODES = {torch.float32: _hip.DTYPE_F32, **LOWP_DTYPES}
 
 
 def is_lowp(x):
@@ -39,6 +41,14 @@ def _lowp_code(x):
     code = LOWP_DTYPES.get(x.dtype)
     if code is None:
         raise TypeError(f"outlier_suppression_amd: expected a bfloat16 or float16 tensor, got {x.dtype}")
+    return code
+
+
+def _elem_code(x):
+    """osq_dtype of x's elements: read once, where the pointer is taken."""
+    code = _ELEM_CODES.get(x.dtype)
+    if code is None:
+        raise TypeError(f"outlier_suppression_amd kernels compute in float32, got {x.dtype}")
     return code
 
 
@@ -123,20 +133,29 @@ def _channel_split(x, ch_axis):
     return outer, x.shape[ch_axis], inner
 
 
+def _check_per_channel(what, channels, a, b):
+    if a.numel() != channels or b.numel() != channels:
+        raise ValueError(f"{what}: {channels} channels but the per-channel tensors have {a.numel()}/{b.numel()} entries")
+
+
 def fake_quant_per_channel(x, scale, zero_point, ch_axis, quant_min, quant_max, mode=PARAM_FIXED, grad_factor=1.0,
                            return_quantized=False):
-    """util_quant.py:18-26 / 37-45 / 58-67 (forward)."""
+    """util_quant.py:18-26 / 37-45 / 58-67 (forward).  x fp32, bf16 or fp16; the result is fp32 (torch promotes a 16-bit x
+    that meets fp32 [C] parameters) and word-equal to the call on x.float().  return_quantized: fp32 x only."""
     lib = _hip.load()
     _hip.require_device(x, scale, zero_point)
-    _check_f32(x, scale)
+    _check_f32(scale)
+    code = _elem_code(x)
+    if code != _hip.DTYPE_F32:
+        if return_quantized:
+            raise NotImplementedError("per-channel fake-quant of a bf16 / fp16 tensor has no return_quantized form")
+        mode &= PARAM_MODE_MASK
     x = x.contiguous()
     outer, channels, inner = _channel_split(x, ch_axis)
-    if scale.numel() != channels or zero_point.numel() != channels:
-        raise ValueError(f"per-channel fake-quant: {channels} channels but scale/zero_point have "
-                         f"{scale.numel()}/{zero_point.numel()} entries")
-    y = torch.empty_like(x)
+    _check_per_channel("per-channel fake-quant", channels, scale, zero_point)
+    y = torch.empty_like(x, dtype=torch.float32)
     xq = torch.empty_like(x) if return_quantized else None
-    _hip.check(lib.osq_fake_quant_per_channel(_hip.ptr(x), _hip.ptr(y), _hip.ptr(xq), outer, channels, inner,
+    _hip.check(lib.osq_fake_quant_per_channel(code, _hip.ptr(x), _hip.ptr(y), _hip.ptr(xq), outer, channels, inner,
                                               _hip.ptr(scale), _hip.ptr(zero_point), _zp_type(zero_point), mode,
                                               float(grad_factor), int(quant_min), int(quant_max),
                                               _hip.stream_ptr(x.device)), "fake_quant_per_channel")
@@ -273,39 +292,19 @@ def fake_quant_per_tensor_widen(x, scale, zero_point, quant_min, quant_max, mode
     return y
 
 
-def fake_quant_per_channel_widen(x, scale, zero_point, ch_axis, quant_min, quant_max, mode=PARAM_FIXED, grad_factor=1.0):
-    """Per-channel form of fake_quant_per_tensor_widen (fp32 result equal to fake_quant_per_channel(x.float(), ...))."""
-    lib = _hip.load()
-    _hip.require_device(x, scale, zero_point)
-    _check_f32(scale)
-    x = x.contiguous()
-    outer, channels, inner = _channel_split(x, ch_axis)
-    if scale.numel() != channels or zero_point.numel() != channels:
-        raise ValueError(f"per-channel fake-quant: {channels} channels but scale/zero_point have "
-                         f"{scale.numel()}/{zero_point.numel()} entries")
-    y = torch.empty(x.shape, dtype=torch.float32, device=x.device)
-    _hip.check(lib.osq_fake_quant_per_channel_widen(_lowp_code(x), _hip.ptr(x), _hip.ptr(y), outer, channels, inner,
-                                                    _hip.ptr(scale), _hip.ptr(zero_point), _zp_type(zero_point),
-                                                    mode & PARAM_MODE_MASK, float(grad_factor), int(quant_min),
-                                                    int(quant_max), _hip.stream_ptr(x.device)), "fake_quant_per_channel_widen")
-    return y
-
-
 def _lowp_chain(x, ch_axis, mode, scalar_params):
     """True when a bf16 / fp16 call keeps x.dtype: Fixed per-tensor with Python-number / 0-dim parameters."""
     return scalar_params and ch_axis == -1 and (mode & PARAM_MODE_MASK) == PARAM_FIXED
 
 
 def _forward(x, scale, zero_point, ch_axis, quant_min, quant_max, mode, grad_factor, scalar_params):
-    if is_lowp(x):
-        if _lowp_chain(x, ch_axis, mode, scalar_params):
-            return fake_quant_chain_lowp(x, scale, zero_point, quant_min, quant_max)
-        if ch_axis == -1:
-            return fake_quant_per_tensor_widen(x, scale, zero_point, quant_min, quant_max, mode, grad_factor)
-        return fake_quant_per_channel_widen(x, scale, zero_point, ch_axis, quant_min, quant_max, mode, grad_factor)
-    if ch_axis == -1:
+    if ch_axis != -1:
+        return fake_quant_per_channel(x, scale, zero_point, ch_axis, quant_min, quant_max, mode, grad_factor)
+    if not is_lowp(x):
         return fake_quant_per_tensor(x, scale, zero_point, quant_min, quant_max, mode, grad_factor)
-    return fake_quant_per_channel(x, scale, zero_point, ch_axis, quant_min, quant_max, mode, grad_factor)
+    if _lowp_chain(x, ch_axis, mode, scalar_params):
+        return fake_quant_chain_lowp(x, scale, zero_point, quant_min, quant_max)
+    return fake_quant_per_tensor_widen(x, scale, zero_point, quant_min, quant_max, mode, grad_factor)
 
 
 class _FakeQuantFn(torch.autograd.Function):
@@ -406,61 +405,34 @@ _NO_SINK = QParamSink()
 
 
 def observe_flat(x, rule, cnt, min_val, max_val, quant_min, quant_max, symmetric, sink=None, cur=None):
-    """Global min/max of a dense tensor + running statistic (+ qparams): ONE launch."""
+    """Global min/max of a dense fp32 / bf16 / fp16 tensor + running statistic (+ qparams): ONE launch.  The statistics of a
+    16-bit x are those of x.float()."""
     lib = _hip.load()
     _hip.require_device(x, min_val, max_val)
-    _check_f32(x, min_val, max_val)
+    _check_f32(min_val, max_val)
+    code = _elem_code(x)
     if not is_dense(x):
         x = x.contiguous()
-    s_ptr, z_ptr, z_type = (sink or QParamSink()).args()
+    s_ptr, z_ptr, z_type = (sink or _NO_SINK).args()
     ws = _hip.workspace(x.device)
-    _hip.check(lib.osq_observe_flat(_hip.ptr(x), x.numel(), rule, int(cnt), _hip.ptr(min_val), _hip.ptr(max_val),
+    _hip.check(lib.osq_observe_flat(code, _hip.ptr(x), x.numel(), rule, int(cnt), _hip.ptr(min_val), _hip.ptr(max_val),
                                     _hip.ptr(cur), int(quant_min), int(quant_max), int(bool(symmetric)), s_ptr, z_ptr,
                                     z_type, _hip.ptr(ws), _hip.stream_ptr(x.device)), "observe_flat")
 
 
 def observe_channels(x, ch_axis, rule, cnt, min_val, max_val, quant_min, quant_max, symmetric, sink=None):
-    """Per-channel min/max + running statistic (+ qparams): ONE launch."""
+    """Per-channel min/max of an fp32 / bf16 / fp16 tensor + running statistic (+ qparams): ONE launch."""
     lib = _hip.load()
     _hip.require_device(x, min_val, max_val)
-    _check_f32(x, min_val, max_val)
+    _check_f32(min_val, max_val)
+    code = _elem_code(x)
     x = x.contiguous()
     outer, channels, inner = _channel_split(x, ch_axis)
-    if min_val.numel() != channels or max_val.numel() != channels:
-        raise ValueError("observe_channels: statistic buffers must have one entry per channel")
-    s_ptr, z_ptr, z_type = (sink or QParamSink()).args()
-    _hip.check(lib.osq_observe_channels(_hip.ptr(x), outer, channels, inner, rule, int(cnt), _hip.ptr(min_val),
+    _check_per_channel("observe_channels", channels, min_val, max_val)
+    s_ptr, z_ptr, z_type = (sink or _NO_SINK).args()
+    _hip.check(lib.osq_observe_channels(code, _hip.ptr(x), outer, channels, inner, rule, int(cnt), _hip.ptr(min_val),
                                         _hip.ptr(max_val), int(quant_min), int(quant_max), int(bool(symmetric)), s_ptr,
                                         z_ptr, z_type, _hip.stream_ptr(x.device)), "observe_channels")
-
-
-def observe_flat_lowp(x, rule, cnt, min_val, max_val, quant_min, quant_max, symmetric, sink=None, cur=None):
-    """observe_flat reading a bf16 / fp16 tensor: the statistics of observe_flat(x.float(), ...) in ONE launch."""
-    lib = _hip.load()
-    _hip.require_device(x, min_val, max_val)
-    _check_f32(min_val, max_val)
-    x = _lowp_flat(x)
-    s_ptr, z_ptr, z_type = (sink or _NO_SINK).args()
-    _hip.check(lib.osq_observe_flat_lowp(_lowp_code(x), _hip.ptr(x), x.numel(), rule, int(cnt), _hip.ptr(min_val),
-                                         _hip.ptr(max_val), _hip.ptr(cur), int(quant_min), int(quant_max), int(bool(symmetric)),
-                                         s_ptr, z_ptr, z_type, _hip.ptr(_hip.workspace(x.device)), _hip.stream_ptr(x.device)),
-               "observe_flat_lowp")
-
-
-def observe_channels_lowp(x, ch_axis, rule, cnt, min_val, max_val, quant_min, quant_max, symmetric, sink=None):
-    """observe_channels reading a bf16 / fp16 tensor: ONE launch."""
-    lib = _hip.load()
-    _hip.require_device(x, min_val, max_val)
-    _check_f32(min_val, max_val)
-    x = x.contiguous()
-    outer, channels, inner = _channel_split(x, ch_axis)
-    if min_val.numel() != channels or max_val.numel() != channels:
-        raise ValueError("observe_channels: statistic buffers must have one entry per channel")
-    s_ptr, z_ptr, z_type = (sink or _NO_SINK).args()
-    _hip.check(lib.osq_observe_channels_lowp(_lowp_code(x), _hip.ptr(x), outer, channels, inner, rule, int(cnt),
-                                             _hip.ptr(min_val), _hip.ptr(max_val), int(quant_min), int(quant_max),
-                                             int(bool(symmetric)), s_ptr, z_ptr, z_type, _hip.stream_ptr(x.device)),
-               "observe_channels_lowp")
 
 
 _view_cache = {}
@@ -618,55 +590,32 @@ def _scratch(device, n):
     return views
 
 
+def _lengths_i64(lengths):
+    return lengths if lengths is None or lengths.dtype == torch.int64 else lengths.to(torch.int64)
+
+
 def token_minmax(x, seq_pos, lengths=None, out=None):
-    """Per-token (min, max) over features for tokens t < lengths[b]; padded slots untouched."""
+    """Per-token fp32 (min, max) over the features of an fp32 / bf16 / fp16 tensor (any strides) for tokens t < lengths[b];
+    padded slots untouched."""
     lib = _hip.load()
     _hip.require_device(x, lengths)
-    _check_f32(x)
-    if lengths is not None and lengths.dtype != torch.int64:
-        lengths = lengths.to(torch.int64)
+    code = _elem_code(x)
+    lengths = _lengths_i64(lengths)
     view = token_view(x, seq_pos, None if lengths is None else lengths.numel())
     n = view.batch * view.tokens
     tmin, tmax = out if out is not None else _scratch(x.device, n)[:2]
     if tmin.numel() < n or tmax.numel() < n:
         raise ValueError(f"token_minmax: the output rows hold {tmin.numel()} slots, this tensor has {n} (batch x tokens)")
-    _hip.check(lib.osq_token_minmax(_hip.ptr(x), ctypes.byref(view), _hip.ptr(lengths), _hip.ptr(tmin), _hip.ptr(tmax),
+    _hip.check(lib.osq_token_minmax(code, _hip.ptr(x), ctypes.byref(view), _hip.ptr(lengths), _hip.ptr(tmin), _hip.ptr(tmax),
                                     _hip.stream_ptr(x.device)), "token_minmax")
     return tmin, tmax, view.batch, view.tokens, lengths
-
-
-def token_minmax_lowp(x, seq_pos, lengths=None, out=None):
-    """token_minmax reading a bf16 / fp16 tensor (any strides): the fp32 per-token extrema of x.float()."""
-    lib = _hip.load()
-    _hip.require_device(x, lengths)
-    code = _lowp_code(x)
-    if lengths is not None and lengths.dtype != torch.int64:
-        lengths = lengths.to(torch.int64)
-    view = token_view(x, seq_pos, None if lengths is None else lengths.numel())
-    n = view.batch * view.tokens
-    tmin, tmax = out if out is not None else _scratch(x.device, n)[:2]
-    if tmin.numel() < n or tmax.numel() < n:
-        raise ValueError(f"token_minmax: the output rows hold {tmin.numel()} slots, this tensor has {n} (batch x tokens)")
-    _hip.check(lib.osq_token_minmax_lowp(code, _hip.ptr(x), ctypes.byref(view), _hip.ptr(lengths), _hip.ptr(tmin),
-                                         _hip.ptr(tmax), _hip.stream_ptr(x.device)), "token_minmax_lowp")
-    return tmin, tmax, view.batch, view.tokens, lengths
-
-
-def observe_tokens_lowp(x, seq_pos, lengths, prune, percentile, rule, cnt, min_val, max_val, quant_min, quant_max,
-                        symmetric, sink=None, cur=None):
-    """observe_tokens for a bf16 / fp16 tensor: the per-token extrema read from the 2-byte data, then the unchanged fp32
-    finaliser -- TWO launches, no host synchronisation.  Returns (batch, tokens, lengths_int64)."""
-    tmin, tmax, batch, tokens, lengths = token_minmax_lowp(x, seq_pos, lengths)
-    token_range_finalize(tmin, tmax, batch, tokens, lengths, prune, percentile, rule, cnt, min_val, max_val, quant_min,
-                         quant_max, symmetric, sink, cur)
-    return batch, tokens, lengths
 
 
 def token_range_finalize(tmin, tmax, batch, tokens, lengths, prune, percentile, rule, cnt, min_val, max_val,
                          quant_min, quant_max, symmetric, sink=None, cur=None):
     """Percentile pruning / plain extrema over valid tokens + running statistic (+ qparams): ONE launch."""
     lib = _hip.load()
-    s_ptr, z_ptr, z_type = (sink or QParamSink()).args()
+    s_ptr, z_ptr, z_type = (sink or _NO_SINK).args()
     dev = tmin.device
     lst = _scratch(dev, batch * tokens)[2] if batch * tokens >= _wide_min_slots else None
     _hip.check(lib.osq_token_range_finalize(_hip.ptr(tmin), _hip.ptr(tmax), batch, tokens, _hip.ptr(lengths),
@@ -681,18 +630,18 @@ def observe_tokens(x, seq_pos, lengths, prune, percentile, rule, cnt, min_val, m
                    symmetric, sink=None, cur=None):
     """token_minmax + token_range_finalize behind ONE call of the binding (the per-site hot path of a
     calibration forward: host time per quantizer call is of the order of the kernels' own run time).
+    x fp32, bf16 or fp16 (the extrema are read from the data as it lies; the finaliser is fp32 either way).
     Returns (batch, tokens, lengths_int64)."""
     lib = _hip.load()
     _hip.require_device(x, lengths)
-    _check_f32(x)
-    if lengths is not None and lengths.dtype != torch.int64:
-        lengths = lengths.to(torch.int64)
+    code = _elem_code(x)
+    lengths = _lengths_i64(lengths)
     view = token_view(x, seq_pos, None if lengths is None else lengths.numel())
     dev = x.device
     n = view.batch * view.tokens
     tmin, tmax, lst = _scratch(dev, n)
     s_ptr, z_ptr, z_type = (sink or _NO_SINK).args()
-    rc = lib.osq_observe_tokens(x.data_ptr(), ctypes.byref(view), _hip.ptr(lengths), tmin.data_ptr(), tmax.data_ptr(),
+    rc = lib.osq_observe_tokens(code, x.data_ptr(), ctypes.byref(view), _hip.ptr(lengths), tmin.data_ptr(), tmax.data_ptr(),
                                 1 if prune else 0, float(percentile) if prune else 1.0, rule, int(cnt),
                                 _hip.ptr(min_val), _hip.ptr(max_val), _hip.ptr(cur), int(quant_min), int(quant_max),
                                 1 if symmetric else 0, s_ptr, z_ptr, z_type, _hip.workspace(dev).data_ptr(),
@@ -1154,7 +1103,7 @@ def msefast_tensor_commit(r, rule, cnt, min_val, max_val, sink=None, ref_float64
     lib = _hip.load()
     dev = r.x.device
     quant_min, quant_max, symmetric = r.args
-    s_ptr, z_ptr, z_type = (sink or QParamSink()).args()
+    s_ptr, z_ptr, z_type = (sink or _NO_SINK).args()
     nfev = torch.empty(1, dtype=torch.int32, device=dev)
     _hip.check(lib.osq_msefast_tensor_commit(_hip.ptr(r.state), rule, int(cnt), _hip.ptr(min_val), _hip.ptr(max_val),
                                              quant_min, quant_max, symmetric, s_ptr, z_ptr, z_type,
@@ -1198,7 +1147,7 @@ def observe_moments(x, ch_axis, min_val, max_val, quant_min, quant_max, symmetri
     _check_f32(x, min_val, max_val)
     x = x.contiguous()
     outer, channels, inner = (1, 1, x.numel()) if ch_axis == -1 else _channel_split(x, ch_axis)
-    s_ptr, z_ptr, z_type = (sink or QParamSink()).args()
+    s_ptr, z_ptr, z_type = (sink or _NO_SINK).args()
     _hip.check(lib.osq_observe_moments(_hip.ptr(x), outer, channels, inner, _hip.ptr(min_val), _hip.ptr(max_val),
                                        int(quant_min), int(quant_max), int(bool(symmetric)), s_ptr, z_ptr, z_type,
                                        _hip.ptr(_hip.workspace(x.device)), _hip.stream_ptr(x.device)), "observe_moments")
@@ -1210,7 +1159,7 @@ def observe_quantile(x, observation_mask, seq_pos, cur, threshold, hist_scratch,
     _hip.require_device(x, cur, hist_scratch, min_val, max_val)
     _check_f32(x, min_val, max_val)
     x, n, view, lengths = _source(x, observation_mask, seq_pos)
-    s_ptr, z_ptr, z_type = (sink or QParamSink()).args()
+    s_ptr, z_ptr, z_type = (sink or _NO_SINK).args()
     _hip.check(lib.osq_observe_quantile(_hip.ptr(x), n, ctypes.byref(view) if view is not None else None, _hip.ptr(lengths),
                                         _hip.ptr(cur), float(threshold), _hip.ptr(hist_scratch), rule, int(cnt),
                                         _hip.ptr(min_val), _hip.ptr(max_val), int(quant_min), int(quant_max),
@@ -1228,7 +1177,7 @@ def mse_grid_tensor(x, observation_mask, seq_pos, cur, quant_min, quant_max, sym
     nbytes = int(lib.osq_mse_grid_scratch_bytes(int(quant_min), int(quant_max), int(bool(two_d))))
     scratch = torch.empty(nbytes, dtype=torch.uint8, device=x.device)      # losses + every workgroup's partial sums: the grid is one launch
     losses = scratch[:4 * n_cand].view(torch.float32)
-    s_ptr, z_ptr, z_type = (sink or QParamSink()).args()
+    s_ptr, z_ptr, z_type = (sink or _NO_SINK).args()
     _hip.check(lib.osq_mse_grid_tensor(_hip.ptr(x), n, ctypes.byref(view) if view is not None else None, _hip.ptr(lengths),
                                        _hip.ptr(cur), int(quant_min), int(quant_max), int(bool(symmetric)), SIDE[one_side],
                                        int(bool(two_d)), _hip.ptr(scratch), nbytes, rule, int(cnt), _hip.ptr(min_val),

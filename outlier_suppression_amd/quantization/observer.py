@@ -12,7 +12,8 @@ Differences in mechanism, not in results:
   * a whole observation is 1 launch (flat / per-channel) or 2 launches (masked).
 
 bf16 / fp16 input: the reference widens first (``x_orig.to(min_val.dtype)``).  MinMax, AvgMinMax and AvgPruneMinMax
-read the 2-byte data in their own kernels (ops.*_lowp: same statistics); MSEFast / AvgMSEFast, AvgQuantile, MSE / AvgMSE
+read the 2-byte data as it lies (ops.observe_flat / observe_channels / observe_tokens take all three element types: same
+statistics); MSEFast / AvgMSEFast, AvgQuantile, MSE / AvgMSE
 and LSQPlus widen once with ``x.float()`` at the boundary (``_widened``), which is that same conversion.
 """
 import torch
@@ -92,10 +93,8 @@ class ObserverBase(nn.Module):
             self.cnt += 1
 
     def _observe_tokens(self, x, lengths, seq_pos, prune, sink):
-        lowp = ops.is_lowp(x)
         if self._token_cache is not None:     # keep the per-token extrema; thresholds are applied later, per candidate
-            _, _, batch, tokens, lengths = (ops.token_minmax_lowp if lowp else ops.token_minmax)(x, seq_pos, lengths,
-                                                                                                out=self._token_cache)
+            _, _, batch, tokens, lengths = ops.token_minmax(x, seq_pos, lengths, out=self._token_cache)
             object.__setattr__(self, "_last_site", ("tokens", batch, tokens, lengths))   # nn.Module.__setattr__ costs microseconds
             return
         if (DEFERRED is not None and self._capture is None and self.__dict__.get("_defer_ok", False)
@@ -105,11 +104,10 @@ class ObserverBase(nn.Module):
         rule, cur = self.update_rule, None
         if self._capture is not None:      # record this batch only; calibration.replay() applies the rule later
             rule, cur, sink = ops.UPDATE_NONE, self._capture, None
-        # a bf16 / fp16 site never reaches DeferredSites (its table is fp32): it runs here, two launches
-        observe = ops.observe_tokens_lowp if lowp else ops.observe_tokens
-        batch, tokens, lengths = observe(x, seq_pos, lengths, prune, getattr(self, "percentile", 1.0),
-                                         rule, self._counter(), self.min_val, self.max_val,
-                                         self.quant_min, self.quant_max, self.symmetric, sink, cur)
+        # a bf16 / fp16 site never reaches DeferredSites (its table is fp32): it runs here, two launches behind one call
+        batch, tokens, lengths = ops.observe_tokens(x, seq_pos, lengths, prune, getattr(self, "percentile", 1.0),
+                                                    rule, self._counter(), self.min_val, self.max_val,
+                                                    self.quant_min, self.quant_max, self.symmetric, sink, cur)
         object.__setattr__(self, "_last_site", ("tokens", batch, tokens, lengths))
 
     def token_path_prune(self):
@@ -122,15 +120,13 @@ class ObserverBase(nn.Module):
         rule, cur = self.update_rule, None
         if self._capture is not None:
             rule, cur, sink = ops.UPDATE_NONE, self._capture, None
-        (ops.observe_flat_lowp if ops.is_lowp(x) else ops.observe_flat)(x, rule, self._counter(), self.min_val, self.max_val,
-                                                                         self.quant_min, self.quant_max, self.symmetric, sink,
-                                                                         cur)
+        ops.observe_flat(x, rule, self._counter(), self.min_val, self.max_val, self.quant_min, self.quant_max, self.symmetric,
+                         sink, cur)
 
     def _observe_channels(self, x, sink):
         self._home(x.device, x.shape[self.ch_axis])
-        (ops.observe_channels_lowp if ops.is_lowp(x) else ops.observe_channels)(
-            x, self.ch_axis, self.update_rule, self._counter(), self.min_val, self.max_val, self.quant_min, self.quant_max,
-            self.symmetric, sink)
+        ops.observe_channels(x, self.ch_axis, self.update_rule, self._counter(), self.min_val, self.max_val, self.quant_min,
+                             self.quant_max, self.symmetric, sink)
 
     def observe_into(self, x, observation_mask=None, seq_pos=-1, sink=None):
         """Observe ``x`` and, if ``sink`` is given, also write calculate_qparams(min_val, max_val)

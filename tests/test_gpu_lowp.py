@@ -252,7 +252,7 @@ def _check_chain(x, s, zp, qmin=0, qmax=255):
     if x.numel():
         st = [torch.full((), v, device=x.device) for v in (float("inf"), float("-inf"), float("inf"), float("-inf"))]
         cur = torch.empty(4, device=x.device)
-        ops.observe_flat_lowp(x, ops.UPDATE_RUNNING, 0, st[0], st[1], qmin, qmax, False, None, cur[:2])
+        ops.observe_flat(x, ops.UPDATE_RUNNING, 0, st[0], st[1], qmin, qmax, False, None, cur[:2])
         ops.observe_flat(x.float(), ops.UPDATE_RUNNING, 0, st[2], st[3], qmin, qmax, False, None, cur[2:])
         _same_f32(cur[:2], cur[2:])
 
@@ -278,17 +278,38 @@ def test_sizes_alignment_layouts(dev, dn):
     zc = torch.randint(0, 256, (48,), generator=gen, dtype=torch.int32).to(dev)
     for ww, ax in ((w, 0), (w.t(), 1), (w[:, 1:], 0)):
         _same_f32(ops.fake_quant(ww, sc, zc, ax, 0, 255), ops.fake_quant(ww.float(), sc, zc, ax, 0, 255))
+        # per-channel observation: (w, 0) takes the row kernel, the two views the generic one
+        got = []
+        for xx in (ww, ww.float()):
+            st = [torch.full((48,), float("inf"), device=dev), torch.full((48,), float("-inf"), device=dev),
+                  torch.empty(48, device=dev), torch.empty(48, dtype=torch.int32, device=dev)]
+            ops.observe_channels(xx, ax, ops.UPDATE_RUNNING, 0, st[0], st[1], 0, 255, False, ops.QParamSink(st[2], st[3]))
+            got.append(st)
+        for h, f in zip(*got):
+            _same_f32(h, f)
     a = (torch.randn(5, 9, 40, generator=gen) * 3).to(dt).to(dev)
     lens = torch.tensor([9, 3, 1, 7, 5], device=dev)
     for v, sp in ((a, 1), (a.permute(0, 2, 1), 2), (a[:, :, 1:], 1)):
         n = v.shape[0] * v.shape[sp]
         oh = (torch.empty(n, device=dev), torch.empty(n, device=dev))
         of = (torch.empty(n, device=dev), torch.empty(n, device=dev))
-        ops.token_minmax_lowp(v, sp, lens, out=oh)
+        ops.token_minmax(v, sp, lens, out=oh)
         ops.token_minmax(v.float(), sp, lens, out=of)
         valid = (torch.arange(v.shape[sp], device=dev)[None, :] < lens[:, None]).reshape(-1)
         _same_f32(oh[0][valid], of[0][valid])
         _same_f32(oh[1][valid], of[1][valid])
+        # masked token observation behind one call: inner width 40 takes the 16-byte path for both element sizes, the
+        # [:, :, 1:] view the generic one
+        for prune in (False, True):
+            got = []
+            for xx in (v, v.float()):
+                st = [torch.full((), float("inf"), device=dev), torch.full((), float("-inf"), device=dev),
+                      torch.empty(2, device=dev), torch.empty(1, device=dev), torch.empty(1, device=dev)]
+                ops.observe_tokens(xx, sp, lens, prune, 0.9, ops.UPDATE_AVERAGE, 0, st[0], st[1], 0, 255, False,
+                                   ops.QParamSink(st[3], st[4]), st[2])
+                got.append(st)
+            for h, f in zip(*got):
+                _same_f32(h, f)
 
 
 @pytest.mark.parametrize("dn", ["bf16"])

@@ -4,7 +4,7 @@
 Times with device events, after a warm-up, the median of --reps repetitions of --iters back-to-back calls:
   * the in-dtype chain (FixedFakeQuantize per-tensor, osq_fake_quant_chain_lowp), bf16 and fp16;
   * the widening LSQ+ forward (fp32 result, osq_fake_quant_per_tensor_widen);
-  * the flat observe (osq_observe_flat_lowp) and the masked token-path observe (token extrema + the fp32 finaliser);
+  * the flat observe (osq_observe_flat on 2-byte data) and the masked token-path observe (token extrema + the fp32 finaliser);
   * the per-channel observe and the per-channel widening forward of a [3072, 768] weight, ch_axis = 0;
   * the same calls on fp32 data through the existing kernels;
   * ".float() -> fp32 kernel -> .to(dtype)": a cost baseline only (it is NOT bit-equal to the reference's chain).
@@ -80,9 +80,9 @@ def main():
             xh = x32.to(dt)
             add(shape, "chain (in-dtype)", dn, lambda: ops.fake_quant_chain_lowp(xh, s, zi, 0, 255), 4 * n)
             add(shape, "widen lsq+ (fp32 out)", dn, lambda: ops.fake_quant_per_tensor_widen(xh, s, zf, 0, 255, ops.PARAM_LSQPLUS, 0.01), 6 * n)
-            add(shape, "observe flat", dn, lambda: ops.observe_flat_lowp(xh, ops.UPDATE_AVERAGE, 0, mn, mx, 0, 255, False, sink), 2 * n)
+            add(shape, "observe flat", dn, lambda: ops.observe_flat(xh, ops.UPDATE_AVERAGE, 0, mn, mx, 0, 255, False, sink), 2 * n)
             add(shape, "observe tokens", dn,
-                lambda: ops.observe_tokens_lowp(xh, 1, lens, True, 0.99, ops.UPDATE_AVERAGE, 0, mn, mx, 0, 255, False, sink),
+                lambda: ops.observe_tokens(xh, 1, lens, True, 0.99, ops.UPDATE_AVERAGE, 0, mn, mx, 0, 255, False, sink),
                 2 * n * valid)
             add(shape, "baseline .float()->fp32 kernel->.to() (not bit-equal)", dn,
                 lambda: ops.fake_quant_per_tensor(xh.float(), s, zi, 0, 255).to(dt), 20 * n)
@@ -98,8 +98,8 @@ def main():
     add(shape, "fake_quant per-channel (fp32 kernel)", "fp32", lambda: ops.fake_quant_per_channel(w32, cs, cz, 0, -128, 127), 8 * n)
     for dn, dt in (("bf16", torch.bfloat16), ("f16", torch.float16)):
         wh = w32.to(dt)
-        add(shape, "observe channels", dn, lambda: ops.observe_channels_lowp(wh, 0, ops.UPDATE_RUNNING, 0, cmn, cmx, -128, 127, True), 2 * n)
-        add(shape, "widen per-channel (fp32 out)", dn, lambda: ops.fake_quant_per_channel_widen(wh, cs, cz, 0, -128, 127), 6 * n)
+        add(shape, "observe channels", dn, lambda: ops.observe_channels(wh, 0, ops.UPDATE_RUNNING, 0, cmn, cmx, -128, 127, True), 2 * n)
+        add(shape, "widen per-channel (fp32 out)", dn, lambda: ops.fake_quant_per_channel(wh, cs, cz, 0, -128, 127), 6 * n)
     for r in rows:
         print(json.dumps(r))
 
