@@ -37,7 +37,8 @@ typedef void* osq_stream;
  * 5: the LSQ / LSQ+ backward takes its summation order as an argument (`lanes` / `sum_lanes`).
  * 8: osq_attention_softmax_fake_quant, OSQ_TIME_ATTENTION_SOFTMAX.
  * 10: osq_observe_flat / _channels, osq_token_minmax, osq_observe_tokens and osq_fake_quant_per_channel take `dtype` first;
- *     their separate 16-bit twins are gone. */
+ *     their separate 16-bit twins are gone.
+ *     Added within 10 (no existing signature changed): osq_quantize_codes, osq_dequantize_codes, osq_dequantize_codes_multi. */
 #define OSQ_ABI_VERSION 10
 
 typedef enum osq_status {
@@ -168,7 +169,8 @@ int osq_timing_elapsed_us(void* start, void* stop, float* us);
  * FixedFakeQuantize.forward fake_quant.py:123-125 (scale/zero_point stay on device
  * instead of .item()); with mode=LSQ/LSQPLUS also util_quant.py:29-34 / 48-55 forward
  * (LSQFakeQuantize / LSQPlusFakeQuantize.forward, fake_quant.py:159-167 / 199-208).
- * x, y: n contiguous fp32.  x_quant (nullable): the clamped integer tensor, fp32 storage. */
+ * x, y: n contiguous fp32.  x_quant (nullable): the clamped integer tensor, fp32 storage (as packed integers:
+ * osq_quantize_codes). */
 int osq_fake_quant_per_tensor(const float* x, float* y, float* x_quant, int64_t n,
                               float* scale, void* zero_point, int zp_type,
                               int mode, float grad_factor, int quant_min, int quant_max,
@@ -470,6 +472,61 @@ typedef struct osq_weight_desc {
 } osq_weight_desc;
 int osq_fake_quant_weights_multi(const osq_weight_desc* descs, const int64_t* row_end, int n_tensors,
                                  int64_t total_rows, osq_stream stream);
+
+/* ------------------------------------------------------------------ integer codes (csrc/codes.hip) */
+
+/* The result of PTQ as integers: what a W8 / W4 checkpoint stores instead of fp32 weights.
+ *
+ * Code format.  u = x_quant - quant_min, x_quant the clamped integer tensor of util_quant.py:12-13: an unsigned integer in
+ * [0, quant_max - quant_min].
+ *   code_bits 8: one byte per element, in x's contiguous order; n bytes.
+ *   code_bits 4: only when quant_max - quant_min <= 15.  Packed over the FLATTENED tensor: byte k holds element 2k in its low
+ *                nibble and element 2k + 1 in its high nibble; with an odd n the last high nibble is 0; ceil(n / 2) bytes.
+ *   A 6-bit quantizer uses code_bits 8 (no three-byte packing).
+ * (float(u + quant_min) - zp_eff) * scale_eff is the fake-quant y of the same call word for word.
+ *
+ * osq_quantize_codes: x is contiguous `dtype` data viewed as [outer, channels, inner] as in osq_fake_quant_per_channel
+ * (channels == 1: per-tensor; pass the tensor's rows as `outer`, a wave walks a row); scale / zero_point / zp_type / mode /
+ * grad_factor as there (no OSQ_PARAM_SANITIZE).  scale_eff / zp_eff (nullable, `channels` fp32 entries): the EFFECTIVE
+ * parameters that reached the quantiser, written once per channel -- in the LSQ modes grad_scale's value can differ from
+ * the stored parameter by an ulp, and the dequantiser must use what the quantiser used.  rejected (nullable, device int32,
+ * only ever added to -- the caller zeroes it): the number of elements whose x_quant is NaN or not an integer (a NaN or
+ * infinite x, a NaN parameter, a fractional zero point); such an element has no code and 0 is written for it.
+ * x and codes 16-byte aligned with inner a multiple of 4 elements (8 for bf16 / fp16, 8 at code_bits 4): 16-byte loads,
+ * codes stored 4 bytes per lane (16 where a row's code bytes are a multiple of 16).  Every other layout -- odd inner, a
+ * channel axis with inner 1, pointers off alignment, an odd n -- runs a generic kernel with the same results (never
+ * OSQ_ERR_UNSUPPORTED).  An empty x launches nothing and writes nothing.
+ *
+ * osq_dequantize_codes: y[outer, channels, inner] fp32 = (float(u + quant_min) - zp_eff[c]) * scale_eff[c], the operation
+ * order of util_quant.py:14.  y 16-byte aligned, inner % 4 == 0 and codes 4-byte (code_bits 4: 2-byte) aligned: one wave per
+ * row, float4 stores; otherwise the generic kernel. */
+int osq_quantize_codes(int dtype, const void* x, uint8_t* codes,
+                       int64_t outer, int64_t channels, int64_t inner,
+                       const float* scale, const void* zero_point, int zp_type,
+                       int mode, float grad_factor,
+                       int quant_min, int quant_max, int code_bits,
+                       float* scale_eff, float* zp_eff,
+                       int32_t* rejected, osq_stream stream);
+int osq_dequantize_codes(const uint8_t* codes, float* y,
+                         int64_t outer, int64_t channels, int64_t inner,
+                         const float* scale_eff, const float* zp_eff,
+                         int quant_min, int code_bits, osq_stream stream);
+
+/* Every coded weight of a checkpoint in ONE launch (load time), the table scheme of osq_fake_quant_weights_multi.  descs /
+ * row_end: DEVICE arrays of n_tensors entries; tensor i is codes -> y[rows, inner] (row-major, inner % 4 == 0, y 16-byte
+ * aligned, codes 4-byte aligned -- 2-byte at code_bits 4, where inner % 4 == 0 also makes every row start on a byte),
+ * row r dequantised with scale_eff[r % channels] / zp_eff[r % channels] (channels == 1: per-tensor); row_end[i] = rows of
+ * tensors 0..i.  Entries of both code widths may share a table.  Same arithmetic as osq_dequantize_codes: the same words. */
+typedef struct osq_codes_desc {
+    const uint8_t* codes;
+    float* y;
+    const float* scale_eff;
+    const float* zp_eff;
+    int64_t rows, channels, inner;
+    int32_t quant_min, code_bits;
+} osq_codes_desc;
+int osq_dequantize_codes_multi(const osq_codes_desc* descs, const int64_t* row_end, int n_tensors,
+                               int64_t total_rows, osq_stream stream);
 
 /* ------------------------------------------------------------------ MSEFast (observer.py:412-567) */
 

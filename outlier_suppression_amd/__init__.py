@@ -76,3 +76,11 @@ def reset_tier(_lib=None):
 
 
 _apply_environment = reset_tier
+
+
+def __getattr__(name):
+    """export_codes / load_codes (export.py), imported on first use: importing the package itself stays free of torch."""
+    if name in ("export_codes", "load_codes"):
+        from . import export
+        return getattr(export, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

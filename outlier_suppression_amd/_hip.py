@@ -48,6 +48,12 @@ class WeightDesc(ctypes.Structure):
                 ("quant_max", ctypes.c_int32), ("pad", ctypes.c_int32)]
 
 
+class CodesDesc(ctypes.Structure):
+    """``osq_codes_desc``: one entry of the table of osq_dequantize_codes_multi."""
+    _fields_ = [("codes", _P), ("y", _P), ("scale_eff", _P), ("zp_eff", _P), ("rows", _L), ("channels", _L), ("inner", _L),
+                ("quant_min", ctypes.c_int32), ("code_bits", ctypes.c_int32)]
+
+
 class HeadSplitSite(ctypes.Structure):
     """``osq_headsplit_site``: one entry of the table of osq_fake_quant_headsplit_multi."""
     _fields_ = [("x", _P), ("y", _P), ("scale", _P), ("zero_point", _P), ("zp_type", ctypes.c_int32), ("mode", ctypes.c_int32),
@@ -87,6 +93,9 @@ SIGNATURES = {
     "osq_fake_quant_kv_append": (_I, [ctypes.POINTER(KvAppendSite), _I, _L, _L, _L, _P]),
     "osq_fake_quant_per_channel": (_I, [_I, _P, _P, _P, _L, _L, _L, _P, _P, _I, _I, _F, _I, _I, _P]),
     "osq_fake_quant_weights_multi": (_I, [_P, _P, _I, _L, _P]),
+    "osq_quantize_codes": (_I, [_I, _P, _P, _L, _L, _L, _P, _P, _I, _I, _F, _I, _I, _I, _P, _P, _P, _P]),
+    "osq_dequantize_codes": (_I, [_P, _P, _L, _L, _L, _P, _P, _I, _I, _P]),
+    "osq_dequantize_codes_multi": (_I, [_P, _P, _I, _L, _P]),
     "osq_lsq_backward_per_tensor": (_I, [_P, _P, _P, _L, _P, _P, _I, _I, _F, _I, _I, _P, _P, _P, _P]),
     "osq_ordered_sum_scratch_bytes": (ctypes.c_size_t, [_L, _I]),
     "osq_lsq_backward_per_tensor_ordered": (_I, [_P, _P, _P, _L, _P, _P, _I, _I, _F, _I, _I, _P, _P, _I, _P, ctypes.c_size_t, _P, _P]),

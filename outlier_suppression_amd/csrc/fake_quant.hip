@@ -409,7 +409,6 @@ __global__ __launch_bounds__(kThreads) void fq_channel_generic_kernel(
 // bisection over the table's running row counts; per-row (scale, zero_point) as in fq_channel_rows_kernel
 // (channels == 1: the per-tensor form).  The host keeps the result while weight and parameters are unchanged
 // (quantization/weight_cache.py), so a frozen model pays this launch once, not per forward.
-constexpr int kMultiLdsWeights = 1024;         // running row counts of that many tensors are bisected in LDS
 __global__ __launch_bounds__(kThreads) void fq_weights_multi_kernel(const osq_weight_desc* __restrict__ descs,
                                                                     const int64_t* __restrict__ row_end, int n,
                                                                     int64_t total_rows) {

@@ -10,6 +10,7 @@
 namespace osq {
 
 constexpr int kMaxBlocks = 2048;          // 256 CUs x 8 workgroups of 256 threads
+constexpr int kMultiLdsWeights = 1024;    // table-driven weight launches (fake_quant.hip, codes.hip): running row counts of that many tensors are bisected in LDS
 // Every kernel family that finishes in its last workgroup owns a block of ticket counters and a block of partials:
 // two such kernels of DIFFERENT families may overlap on one stream (graph branches) without sharing either.
 enum WsFamily { kFamLsqBackward = 0, kFamObserveFlat = 1, kFamWideFinal = 2, kFamMseFlat = 3, kFamMseTokens = 4,

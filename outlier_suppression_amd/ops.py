@@ -5,6 +5,7 @@ host.  No arithmetic on tensor data happens in Python; torch only allocates.
 """
 import ctypes
 import os
+from typing import NamedTuple
 
 import torch
 
@@ -160,6 +161,98 @@ def fake_quant_per_channel(x, scale, zero_point, ch_axis, quant_min, quant_max, 
                                               float(grad_factor), int(quant_min), int(quant_max),
                                               _hip.stream_ptr(x.device)), "fake_quant_per_channel")
     return (y, xq) if return_quantized else y
+
+
+# ---------------------------------------------------------------------------------------
+# integer codes: the quantised tensor as packed unsigned integers, and back
+# ---------------------------------------------------------------------------------------
+
+class Codes(NamedTuple):
+    """A quantised tensor as integers (format: include/osq_hip.h, "integer codes").  codes: uint8, u = x_quant - quant_min,
+    one per byte (code_bits 8) or two per byte over the flattened tensor (code_bits 4); scale / zero_point: the fp32
+    EFFECTIVE parameters that reached the quantiser, [channels]; shape / ch_axis: of the tensor the codes came from."""
+    codes: torch.Tensor
+    scale: torch.Tensor
+    zero_point: torch.Tensor
+    quant_min: int
+    quant_max: int
+    code_bits: int
+    shape: tuple
+    ch_axis: int
+
+
+def _code_bits(quant_min, quant_max, code_bits):
+    if code_bits is None:
+        return 4 if quant_max - quant_min <= 15 else 8
+    return int(code_bits)
+
+
+def _codes_split(shape, ch_axis):
+    """[outer, channels, inner] of a coded tensor; per-tensor (ch_axis -1): the rows of the tensor as `outer`, one channel."""
+    shape = tuple(shape)
+    if ch_axis == -1:
+        rows = shape[0] if len(shape) >= 2 else 1
+        numel = 1
+        for s in shape:
+            numel *= s
+        return rows, 1, (numel // rows if rows else 0)
+    ch_axis = ch_axis % len(shape)
+    outer = inner = 1
+    for s in shape[:ch_axis]:
+        outer *= s
+    for s in shape[ch_axis + 1:]:
+        inner *= s
+    return outer, shape[ch_axis], inner
+
+
+def quantize_codes(x, scale, zero_point, ch_axis, quant_min, quant_max, mode=PARAM_FIXED, grad_factor=1.0, code_bits=None):
+    """The integer tensor of util_quant.py:12-13 as a ``Codes`` record.  x fp32, bf16 or fp16; ch_axis -1: per-tensor.
+    code_bits None: 4 when quant_max - quant_min <= 15, else 8.  Raises ValueError when some element has no integer code
+    (a NaN or infinite value, a fractional zero point): one host read of the launch's counter -- export is not a hot path."""
+    lib = _hip.load()
+    _hip.require_device(x, scale, zero_point)
+    _check_f32(scale)
+    code = _elem_code(x)
+    x = x.contiguous()
+    outer, channels, inner = _codes_split(x.shape, ch_axis)
+    _check_per_channel("quantize_codes", channels, scale, zero_point)
+    bits = _code_bits(quant_min, quant_max, code_bits)
+    n = x.numel()
+    codes = torch.empty((n * bits + 7) // 8, dtype=torch.uint8, device=x.device)
+    s_eff = torch.empty(channels, dtype=torch.float32, device=x.device)
+    z_eff = torch.empty(channels, dtype=torch.float32, device=x.device)
+    rejected = torch.zeros(1, dtype=torch.int32, device=x.device)
+    _hip.check(lib.osq_quantize_codes(code, _hip.ptr(x), _hip.ptr(codes), outer, channels, inner, _hip.ptr(scale),
+                                      _hip.ptr(zero_point), _zp_type(zero_point), mode & PARAM_MODE_MASK, float(grad_factor),
+                                      int(quant_min), int(quant_max), bits, _hip.ptr(s_eff), _hip.ptr(z_eff), _hip.ptr(rejected),
+                                      _hip.stream_ptr(x.device)), "quantize_codes")
+    bad = int(rejected.item())
+    if bad:
+        raise ValueError(f"quantize_codes: {bad} of {n} elements have no integer code (x_quant is NaN or not an integer: "
+                         "a NaN / infinite value or a non-integer zero point)")
+    return Codes(codes, s_eff, z_eff, int(quant_min), int(quant_max), bits, tuple(x.shape), int(ch_axis))
+
+
+def dequantize_codes(record, out=None):
+    """fp32 tensor of ``record.shape``: (float(u + quant_min) - zero_point) * scale, word-equal to the fake-quant of the
+    tensor the codes came from.  out: a contiguous fp32 tensor of that shape to write into."""
+    lib = _hip.load()
+    _hip.require_device(record.codes, record.scale, record.zero_point, out)
+    _check_f32(record.scale, record.zero_point, out)
+    shape = tuple(record.shape)
+    outer, channels, inner = _codes_split(shape, record.ch_axis)
+    n = outer * channels * inner
+    if record.codes.dtype != torch.uint8 or record.codes.numel() != (n * record.code_bits + 7) // 8 or not record.codes.is_contiguous():
+        raise ValueError(f"dequantize_codes: {record.codes.numel()} {record.codes.dtype} codes for shape {shape} at {record.code_bits} bits")
+    _check_per_channel("dequantize_codes", channels, record.scale, record.zero_point)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=record.codes.device)
+    elif tuple(out.shape) != shape or not out.is_contiguous():
+        raise ValueError(f"dequantize_codes: out must be a contiguous tensor of shape {shape}")
+    _hip.check(lib.osq_dequantize_codes(_hip.ptr(record.codes), _hip.ptr(out), outer, channels, inner, _hip.ptr(record.scale),
+                                        _hip.ptr(record.zero_point), int(record.quant_min), int(record.code_bits),
+                                        _hip.stream_ptr(out.device)), "dequantize_codes")
+    return out
 
 
 # ---------------------------------------------------------------------------------------

@@ -145,6 +145,19 @@ class QuantizeBase(nn.Module):
                               self.param_mode | flags, self._grad_factor(X) if self.param_mode != PARAM_FIXED else 1.0,
                               scalar_params=self.param_mode == PARAM_FIXED and self.ch_axis == -1)
 
+    # ---- integer codes (export.py) ------------------------------------------------------
+    def to_codes(self, x, code_bits=None):
+        """``ops.Codes`` of x under this quantizer's own parameters, mode and grad factor: the integers its fake-quant of x
+        stands for.  ValueError when some element has no integer code (ops.quantize_codes)."""
+        ops.check_persistent("to_codes")
+        return ops.quantize_codes(x, self.scale.detach(), self.zero_point.detach(), self.ch_axis, self.quant_min, self.quant_max,
+                                  self.param_mode, self._grad_factor(x) if self.param_mode != PARAM_FIXED else 1.0, code_bits)
+
+    @staticmethod
+    def from_codes(codes, out=None):
+        """The fp32 tensor the codes stand for: word-equal to this quantizer's fake-quant of the coded tensor."""
+        return ops.dequantize_codes(codes, out)
+
     # ---- state dict: scale / zero_point change size on the first observation ----------
     def _save_to_state_dict(self, destination, prefix, keep_vars):
         ops.check_persistent("state_dict")        # what is about to be saved must not come from a timed-out launch
