@@ -490,7 +490,9 @@ def observe_msefast(st, x, lengths=None, seq_pos=-1, average=False, counter=None
 def observe_lsqplus(st, x):
     """LSQPlusObserver.forward, observer.py:159-173: range = mean -+ 3 std (unbiased std), not accumulated.
     Moments are taken in float64 and rounded to fp32 (torch's own accumulation order is not part of
-    the reference); compare with a 1e-6 tolerance."""
+    the reference: its CPU std accumulates in double as well).  A result formed from moments that are accurate well
+    beyond fp32 lies within 4 ulp of |mean| + 3 std of this one (tests/_extra_observers.py::moment_range derives it);
+    the device kernels are held to that bound."""
     x = np.asarray(x, dtype=F32)
     if x.size == 0:
         return
@@ -569,10 +571,13 @@ def mse_grid_loss(x, new_min, new_max, quant_min, quant_max, symmetric):
     return F32((d * d).astype(np.float64).mean())
 
 
-def mse_grid_search(x, st, num=100):
-    """perform_1D_search / perform_2D_search (observer.py:314-364) for one tensor (or one channel row)."""
+def mse_grid_search(x, st, num=100, channel=False):
+    """perform_1D_search / perform_2D_search (observer.py:314-364) for one tensor (or, ``channel``, one channel row: the
+    per-channel 2-D search widens each row's extrema to include zero first, observer.py:319-320)."""
     x = np.asarray(x, dtype=F32)
     x_min, x_max = aminmax(x)
+    if channel and not (st.one_side_dist != "no" or st.symmetric):
+        x_min, x_max = F32(zminimum(x_min, F32(0))), F32(zmaximum(x_max, F32(0)))
     best_score, best_min, best_max = F32(1e10), x_min, x_max
     if st.one_side_dist != "no" or st.symmetric:
         xr = F32(max(abs(x_min), x_max))
@@ -610,7 +615,7 @@ def observe_mse(st, x, lengths=None, seq_pos=-1, average=False):
         best_min, best_max = mse_grid_search(x, st)
     else:
         rows = _to_channel_rows(x, st.ch_axis)
-        res = [mse_grid_search(r, st) for r in rows]
+        res = [mse_grid_search(r, st, channel=True) for r in rows]
         best_min = np.array([r[0] for r in res], dtype=F32)
         best_max = np.array([r[1] for r in res], dtype=F32)
     if average:

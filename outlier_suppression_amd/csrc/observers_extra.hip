@@ -121,10 +121,14 @@ struct QOut {
     int zp_type;
 };
 
-__device__ __forceinline__ void write_moment_range(double sum, double sumsq, double n, int64_t idx, float* min_val,
+// sum / sumsq: float64 sums of (x - shift) and (x - shift)^2.  The variance does not depend on the shift; with a shift near the
+// data (the kernels take the first element) sumsq - n mean^2 cancels nothing that matters even where |mean| >> std
+// (Chan, Golub & LeVeque 1983, "shifted data"), and constant data gives exactly zero.
+__device__ __forceinline__ void write_moment_range(double shift, double sum, double sumsq, double n, int64_t idx, float* min_val,
                                                    float* max_val, const QOut& q) {
-    const double mean_d = sum / n;
-    const double var_d = n > 1.0 ? (sumsq - n * mean_d * mean_d) / (n - 1.0) : __builtin_nan("");
+    const double mean_s = sum / n;
+    const double mean_d = shift + mean_s;
+    const double var_d = n > 1.0 ? (sumsq - n * mean_s * mean_s) / (n - 1.0) : __builtin_nan("");
     const float mean = static_cast<float>(mean_d);
     const float sd = static_cast<float>(sqrt(var_d > 0.0 ? var_d : (var_d == var_d ? 0.0 : var_d)));
     const float three = 3.0f * sd;                      // mean - 3*std / mean + 3*std in fp32 (observer.py:171-172)
@@ -143,16 +147,14 @@ __global__ __launch_bounds__(kThreads) void moments_flat_kernel(ElemSource src, 
                                                                 double* partials, unsigned int* tickets) {
     __shared__ double sums[2];
     double acc[2] = {0.0, 0.0};
-    float s1 = 0.f, s2 = 0.f;
-    int run = 0;
+    const double shift = src.x[0];                      // x - shift is exact in float64, and so is its square's product
     for_each_element(src, [&](float v) {
-        s1 += v; s2 += v * v;
-        if (++run == 32) { acc[0] += s1; acc[1] += s2; s1 = 0.f; s2 = 0.f; run = 0; }   // short fp32 runs, double totals
+        const double d = static_cast<double>(v) - shift;
+        acc[0] += d; acc[1] += d * d;                   // fp32 products and runs lost std to cancellation where |mean| >> std
     });
-    acc[0] += s1; acc[1] += s2;
     if (grid_sum<2>(acc, partials, tickets, sums)) {
         if (threadIdx.x == 0) {
-            write_moment_range(sums[0], sums[1], observed_count(src), 0, min_val, max_val, q);
+            write_moment_range(shift, sums[0], sums[1], observed_count(src), 0, min_val, max_val, q);
             grid_reset(tickets, gridDim.x);
         }
     }
@@ -165,9 +167,10 @@ __global__ __launch_bounds__(kThreads) void moments_channels_kernel(const float*
     __shared__ double sh[2][kWaves];
     const int64_t c = blockIdx.x;
     double a0 = 0.0, a1 = 0.0;
+    const double shift = x[c * inner];                  // the channel's first element
     for (int64_t o = 0; o < outer; ++o) {
         const float* p = x + (o * channels + c) * inner;
-        for (int64_t j = threadIdx.x; j < inner; j += kThreads) { const double v = p[j]; a0 += v; a1 += v * v; }
+        for (int64_t j = threadIdx.x; j < inner; j += kThreads) { const double v = static_cast<double>(p[j]) - shift; a0 += v; a1 += v * v; }
     }
     a0 = wave_sum(a0);
     a1 = wave_sum(a1);
@@ -177,7 +180,7 @@ __global__ __launch_bounds__(kThreads) void moments_channels_kernel(const float*
     if (threadIdx.x == 0) {
         double s = 0.0, ss = 0.0;
         for (int k = 0; k < kWaves; ++k) { s += sh[0][k]; ss += sh[1][k]; }
-        write_moment_range(s, ss, static_cast<double>(outer * inner), c, min_val, max_val, q);
+        write_moment_range(shift, s, ss, static_cast<double>(outer * inner), c, min_val, max_val, q);
     }
 }
 
@@ -329,7 +332,10 @@ __device__ __forceinline__ Cand make_candidate(int k, float x_min, float x_max, 
         const float xr = x_max - x_min;
         const float tmp_max = xr / static_cast<float>(num) * static_cast<float>(i);
         const float delta = (tmp_max - 0.0f) / static_cast<float>(qmax - qmin);
-        c.lo = fmaxf(0.0f - static_cast<float>(zp) * delta, x_min);
+        // 0 - zp * delta is +0.0 for zp == 0 (observer.py:334), but the instruction selector folds a subtraction from zero
+        // into a source negation of v_max_f32, which makes it -0.0: a zero lower end is set to +0.0 by its bits
+        const float lo = fmaxf(0.0f - static_cast<float>(zp) * delta, x_min);
+        c.lo = __float_as_uint(lo) == 0x80000000u ? 0.0f : lo;
         c.hi = fminf(tmp_max - static_cast<float>(zp) * delta, x_max);
     }
     qparams_from_range(c.lo, c.hi, qmin, qmax, sym, &c.scale, &c.zp);
