@@ -38,7 +38,8 @@ typedef void* osq_stream;
  * 8: osq_attention_softmax_fake_quant, OSQ_TIME_ATTENTION_SOFTMAX.
  * 10: osq_observe_flat / _channels, osq_token_minmax, osq_observe_tokens and osq_fake_quant_per_channel take `dtype` first;
  *     their separate 16-bit twins are gone.
- *     Added within 10 (no existing signature changed): osq_quantize_codes, osq_dequantize_codes, osq_dequantize_codes_multi. */
+ *     Added within 10 (no existing signature changed): osq_quantize_codes, osq_dequantize_codes, osq_dequantize_codes_multi,
+ *     osq_decode_attention_fake_quant. */
 #define OSQ_ABI_VERSION 10
 
 typedef enum osq_status {
@@ -744,6 +745,37 @@ int osq_attention_softmax_fake_quant(const float* scores, const float* mask, int
                                      float* scale, void* zero_point, int zp_type,
                                      int mode, float grad_factor, int quant_min, int quant_max,
                                      osq_stream stream);
+
+/* ------------------------------------------------------------------ one decoding step's attention over the KV cache */
+
+/* What QuantizedBartAttention._attend (model/quant_bart.py; the reference's quant_bart.py:232-268) runs for the single
+ * query token of a cached decoding step -- bmm, mask add, softmax, attention_probs quantizer, bmm, merge heads, context
+ * quantizer -- as ONE launch, one workgroup per (batch, head):
+ *     s[j] = dot(q, k[j]) + mask[j]      j < kv_len
+ *     p    = softmax(s)                  the arithmetic of osq_attention_softmax_fake_quant: max-subtracted, accurate expf,
+ *                                        p = e * (1 / sum)
+ *     p'   = fake_quantize(p)            the probs_* group
+ *     out  = fake_quantize(sum_j p'[j] * v[j])      the ctx_* group
+ * q: dense [batch, heads, 1, head_dim], the already fake-quantised and scaled query.  k / v: [batch, heads, cap, head_dim]
+ * buffers with their own cap (row stride cap * head_dim, cap >= kv_len) of which positions [0, kv_len) are read: the cache
+ * buffers as they are, or the cross-attention tensors with cap == kv_len.  mask: NULL, or additive dense
+ * [batch, 1, 1, kv_len], broadcast over heads.  out: dense [batch, 1, heads * head_dim] (the merged layout).  probs_out:
+ * NULL, or dense [batch, heads, 1, kv_len], receives p'.  All fp32.  Each parameter group is (scale, zero_point, zp_type,
+ * mode, grad_factor, quant_min, quant_max) as in osq_headsplit_site, OSQ_PARAM_SANITIZE included; a NULL scale means no
+ * quantizer: the values pass through.  For given p (given c) the outputs are word-equal to osq_fake_quant_per_tensor.
+ * The dot products are fp32 sums in an order fixed by (head_dim, kv_len) alone (csrc/decode_attention.hip) -- not
+ * rocBLAS's: against the eager sequence the result is equal to a tolerance, not bit for bit; the same inputs give the same
+ * words on every run, whatever the caps.
+ * OSQ_ERR_UNSUPPORTED, nothing launched (the caller runs the eager sequence): head_dim / 4 not a power of two <= 64, kv_len
+ * outside [1, 4096], a pointer not 16-byte aligned.  Inference only. */
+int osq_decode_attention_fake_quant(const float* q, const float* k, const float* v, const float* mask, float* out,
+                                    float* probs_out, int64_t batch, int64_t heads, int64_t head_dim, int64_t kv_len,
+                                    int64_t k_cap, int64_t v_cap,
+                                    float* probs_scale, void* probs_zero_point, int probs_zp_type, int probs_mode,
+                                    float probs_grad_factor, int probs_quant_min, int probs_quant_max,
+                                    float* ctx_scale, void* ctx_zero_point, int ctx_zp_type, int ctx_mode,
+                                    float ctx_grad_factor, int ctx_quant_min, int ctx_quant_max,
+                                    osq_stream stream);
 
 /* ------------------------------------------------------------------ bf16 / fp16 only (lowp.hip) */
 

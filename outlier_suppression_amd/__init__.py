@@ -59,10 +59,19 @@ def set_fast_softmax(on=True):
     util_layernorm.FUSE_SOFTMAX = bool(on)
 
 
+def set_fast_decode_attention(on=True):
+    """The one-launch attention of a cached decoding step (util_layernorm.FUSE_DECODE_ATTENTION: scores, mask, softmax,
+    probabilities quantizer, context, context quantizer over the KV cache; default OFF -- tolerance-equal to the eager
+    sequence, not bit-equal).  OSQ_FAST_DECODE_ATTENTION=1 turns it on at load."""
+    from . import util_layernorm
+    util_layernorm.FUSE_DECODE_ATTENTION = bool(on)
+
+
 def reset_tier(_lib=None):
     """The package's default tier, as the environment states it (applied when the library is first loaded): MSEFast sums in
     the reference's one-thread order, the backward's sums order-free; OSQ_STRICT=1 / 0 force both; OSQ_FAST=0 / 1 the
-    one-launch LayerNorm site; OSQ_FAST_SOFTMAX=1 the one-launch attention-probabilities site (unset: off)."""
+    one-launch LayerNorm site; OSQ_FAST_SOFTMAX=1 the one-launch attention-probabilities site and OSQ_FAST_DECODE_ATTENTION=1
+    the one-launch attention of a cached decoding step (unset: off)."""
     import os
     width = int(os.environ.get("OSQ_STRICT_SIMD", "8"))
     strict = os.environ.get("OSQ_STRICT", "")
@@ -73,6 +82,7 @@ def reset_tier(_lib=None):
     # unset: the default (one-launch LayerNorm site ON) -- a set_fast(False) of an earlier caller or test does not leak
     set_fast(os.environ.get("OSQ_FAST", "") != "0")
     set_fast_softmax(os.environ.get("OSQ_FAST_SOFTMAX", "") not in ("", "0"))
+    set_fast_decode_attention(os.environ.get("OSQ_FAST_DECODE_ATTENTION", "") not in ("", "0"))
 
 
 _apply_environment = reset_tier

@@ -149,6 +149,8 @@ SIGNATURES = {
     "osq_gamma_residual": (_I, [_P, _P, _P, _P, _L, _L, _P]),
     "osq_residual_layernorm_fake_quant": (_I, [_P, _P, _P, _P, _P, _D, _P, _L, _L, _P, _P, _I, _I, _F, _I, _I, _P]),
     "osq_attention_softmax_fake_quant": (_I, [_P, _P, _L, _L, _L, _L, _L, _L, _L, _F, _F, _P, _P, _P, _I, _I, _F, _I, _I, _P]),
+    "osq_decode_attention_fake_quant": (_I, [_P, _P, _P, _P, _P, _P, _L, _L, _L, _L, _L, _L,
+                                             _P, _P, _I, _I, _F, _I, _I, _P, _P, _I, _I, _F, _I, _I, _P]),
     "osq_fake_quant_chain_lowp": (_I, [_I, _P, _P, _L, _P, _P, _I, _I, _I, _P]),
     "osq_fake_quant_chain_backward_lowp": (_I, [_I, _P, _P, _P, _L, _P, _P, _I, _I, _I, _P]),
     "osq_fake_quant_per_tensor_widen": (_I, [_I, _P, _P, _L, _P, _P, _I, _I, _F, _I, _I, _P]),

@@ -27,8 +27,8 @@ from . import generation
 from .losses import classification_loss, lm_loss, span_loss, with_loss
 from ..quantization import QuantizedModule, Quantizer
 from ..util_layernorm import (GammaResidual, QuantizedLayerNorm, activation_fake_quant, attention_probs_fake_quant,
-                              kv_append_fake_quant, merge_heads_fake_quant, qkv_heads_fake_quant, residual_layernorm,
-                              split_heads_fake_quant)
+                              decode_attention_fake_quant, kv_append_fake_quant, merge_heads_fake_quant,
+                              qkv_heads_fake_quant, residual_layernorm, split_heads_fake_quant)
 
 
 def shift_tokens_right(input_ids, pad_token_id, decoder_start_token_id):
@@ -277,7 +277,7 @@ class QuantizedBartAttention(QuantizedModule):
         heads = self.num_heads
         if past_key_value is not None:
             q, k, v = self._cached_qkv(past_key_value, hidden_states, key_value_states, observation_mask)
-            out = self._attend(q, k, v, bsz, tgt_len, attention_mask, observation_mask)
+            out = self._attend(q, k, v, bsz, tgt_len, attention_mask, observation_mask, cached=True)
             return out, past_key_value
         source = hidden_states if key_value_states is None else key_value_states
         xq, xk, xv = self.q_proj(hidden_states) * self.scaling, self.k_proj(source), self.v_proj(source)
@@ -293,8 +293,14 @@ class QuantizedBartAttention(QuantizedModule):
             v = split_heads_fake_quant(self.value_post_act_fake_quantize, xv, heads, observation_mask)
         return self._attend(q, k, v, bsz, tgt_len, attention_mask, observation_mask)
 
-    def _attend(self, q, k, v, bsz, tgt_len, attention_mask, observation_mask):
-        """[B, h, T, d] q and [B, h, S, d] k / v (dense, or views of a cache buffer) -> the block's output."""
+    def _attend(self, q, k, v, bsz, tgt_len, attention_mask, observation_mask, cached=False):
+        """[B, h, T, d] q and [B, h, S, d] k / v (dense, or views of a cache buffer) -> the block's output.  ``cached``: a
+        call of the cached path, whose single-token steps have a one-launch form (util_layernorm.FUSE_DECODE_ATTENTION)."""
+        if cached and tgt_len == 1:
+            out = decode_attention_fake_quant(self.attention_probs_post_act_fake_quantize, self.context_post_act_fake_quantize,
+                                              q, k, v, attention_mask, dropout=(self.dropout, self.training))
+            if out is not None:
+                return self._project(out, observation_mask)
         proj = (bsz * self.num_heads, -1, self.head_dim)
         q, k, v = q.view(*proj), k.view(*proj), v.view(*proj)
         w = torch.bmm(q, k.transpose(1, 2))
@@ -305,6 +311,9 @@ class QuantizedBartAttention(QuantizedModule):
                                            seq_pos=2, heads=self.num_heads)
         out = merge_heads_fake_quant(self.context_post_act_fake_quantize,
                                      torch.bmm(probs, v).view(bsz, self.num_heads, tgt_len, self.head_dim), observation_mask)
+        return self._project(out, observation_mask)
+
+    def _project(self, out, observation_mask):
         out = self.out_proj(out)
         if self.qoutput:
             out = self.out_proj_post_act_fake_quantize(out, observation_mask, 1)

@@ -1561,3 +1561,67 @@ def attention_softmax_fake_quant(scores, mask=None, *, alpha=None, divisor=None,
                                                     z_ptr, z_type, int(mode), float(gf), int(qmin), int(qmax),
                                                     _hip.raw_stream(scores.device)), "attention_softmax_fake_quant")
     return y
+
+
+# ---------------------------------------------------------------------------------------
+# one decoding step's attention over the KV cache: scores, mask, softmax, two quantizers in one launch
+# ---------------------------------------------------------------------------------------
+
+def _kv_cap(x, b, h, s, d):
+    """cap of a [B, h, S, d] fp32 tensor laid out as the first S positions of a [B, h, cap, d] buffer (a ``[:, :, :S]`` view of
+    a cache buffer, or a dense tensor: cap == S), or None when it is laid out otherwise."""
+    if x.dim() != 4 or tuple(x.shape) != (b, h, s, d) or x.dtype != torch.float32:
+        return None
+    st = x.stride()
+    if st[3] != 1 or (s > 1 and st[2] != d):
+        return None
+    if h > 1:
+        row = st[1]
+    elif b > 1:
+        row = st[0]
+    else:
+        row = s * d
+    if row % d or row // d < s or (b > 1 and st[0] != h * row):
+        return None
+    return row // d
+
+
+def _quant_group(quant):
+    if quant is None:
+        return [None, None, ZP_INT32, PARAM_FIXED, 1.0, 0, 1]
+    scale, zero_point, qmin, qmax, mode, gf = quant
+    _hip.require_device(scale, zero_point)
+    _check_f32(scale)
+    return [scale.data_ptr(), zero_point.data_ptr(), _zp_type(zero_point), int(mode), float(gf), int(qmin), int(qmax)]
+
+
+def decode_attention_fake_quant(q, k, v, mask, probs_quant, ctx_quant, want_probs=False):
+    """``fq_ctx(merge_heads(fq_probs(softmax(q @ k^T + mask)) @ v))`` for ONE query token in ONE launch
+    (osq_decode_attention_fake_quant, csrc/decode_attention.hip).
+
+    q: dense [B, h, 1, d] fp32, the fake-quantised, scaled query.  k / v: [B, h, S, d] fp32, dense or ``[:, :, :S]`` views of
+    [B, h, cap, d] cache buffers (each with its own cap); nothing is copied.  mask: None or a dense additive [B, 1, 1, S].
+    probs_quant / ctx_quant: None (no quantizer) or (scale, zero_point, quant_min, quant_max, mode, grad_factor).
+    Returns the [B, 1, h * d] output -- with ``want_probs`` the pair (output, fake-quantised probabilities [B, h, 1, S]) --
+    or None when the library does not take the layout (nothing was launched): the caller runs the eager sequence."""
+    lib = _hip.load()
+    _hip.require_device(q, k, v, mask)
+    _check_f32(q)
+    if q.dim() != 4 or q.shape[2] != 1 or not q.is_contiguous() or k.dim() != 4:
+        return None
+    b, h, _, d = q.shape
+    s = k.shape[2]
+    k_cap, v_cap = _kv_cap(k, b, h, s, d), _kv_cap(v, b, h, s, d)
+    if k_cap is None or v_cap is None:
+        return None
+    if mask is not None and not (mask.dtype == torch.float32 and tuple(mask.shape) == (b, 1, 1, s) and mask.is_contiguous()):
+        return None
+    out = torch.empty((b, 1, h * d), dtype=torch.float32, device=q.device)
+    probs = torch.empty((b, h, 1, s), dtype=torch.float32, device=q.device) if want_probs else None
+    rc = lib.osq_decode_attention_fake_quant(q.data_ptr(), k.data_ptr(), v.data_ptr(), _hip.ptr(mask), out.data_ptr(),
+                                             _hip.ptr(probs), b, h, d, s, k_cap, v_cap, *_quant_group(probs_quant),
+                                             *_quant_group(ctx_quant), _hip.raw_stream(q.device))
+    if rc == _hip.ERR_UNSUPPORTED:
+        return None
+    _hip.check(rc, "decode_attention_fake_quant")
+    return (out, probs) if want_probs else out

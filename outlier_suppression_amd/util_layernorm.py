@@ -30,6 +30,13 @@ autograd (every calibration / evaluation forward):
     ``outlier_suppression_amd.set_fast_softmax(True)`` / ``OSQ_FAST_SOFTMAX=1`` turn it on.  Measured on MI355X
     (profiles/attention_site_ab.txt): [32,12,384,384] 116 us against 220 us eager with fake-quant, 81 against 153 us
     softmax only; [32,12,128,128] 26 against 32 us, and slower than eager softmax only (23 against 22 us).
+
+Incremental decoding has a fifth, ``FUSE_DECODE_ATTENTION`` (default OFF): everything a cached decoding step's attention
+block runs after its q / k / v + append launch -- bmm, mask add, softmax, probabilities quantizer, bmm, merge heads, context
+quantizer (quant_bart.py:232-268) -- as ONE launch for the step's single query token (``ops.decode_attention_fake_quant``,
+csrc/decode_attention.hip).  Its dot products are fp32 sums in the kernel's own fixed order, not rocBLAS's, and its exp is
+ocml's: the result is tolerance-equal to the eager sequence, not bit-equal, hence off by default.
+``outlier_suppression_amd.set_fast_decode_attention(True)`` / ``OSQ_FAST_DECODE_ATTENTION=1`` turn it on.
 """
 import torch
 import torch.nn.functional as F
@@ -43,6 +50,7 @@ FUSE_LAYERNORM = True
 FUSE_ACTIVATION = True
 FUSE_QKV = True          # the query / key / value head-split sites of a self-attention block as one launch (bit-identical)
 FUSE_SOFTMAX = False     # the attention-probabilities site as one launch (tolerance-equal; set_fast_softmax / OSQ_FAST_SOFTMAX=1)
+FUSE_DECODE_ATTENTION = False   # a cached decoding step's attention after the append as one launch (tolerance-equal; set_fast_decode_attention / OSQ_FAST_DECODE_ATTENTION=1)
 FUSE_KV_APPEND = True    # incremental decoding: a step's q / k / v sites + KV-cache append (+ beam reorder) as one launch (bit-identical)
 
 
@@ -270,6 +278,45 @@ def kv_append_fake_quant(sites, heads):
         table.append((x, y, offset, (q.scale.data, q.zero_point.data, q.quant_min, q.quant_max, mode,
                                      q._grad_factor(x) if q.param_mode != ops.PARAM_FIXED else 1.0), src, rows))
     return ops.fake_quant_kv_append(table, heads)
+
+
+class _Numel:
+    """Stands for a tensor of which a quantizer's grad factor needs the element count only."""
+
+    def __init__(self, n):
+        self.n = n
+
+    def numel(self):
+        return self.n
+
+
+def decode_attention_fake_quant(probs_quantizer, ctx_quantizer, q, k, v, mask=None, dropout=None):
+    """Incremental decoding: what follows the q / k / v + append launch of a step's attention block
+    (QuantizedBartAttention._attend: bmm, mask add, softmax, ``probs_quantizer``, bmm, merge heads, ``ctx_quantizer``) as ONE
+    launch (ops.decode_attention_fake_quant), for q = [B, h, 1, d] (one query token) and k / v = [B, h, S, d] views of the
+    cache buffers or the cross-attention tensors.  Only with FUSE_DECODE_ATTENTION on, autograd off, dropout inactive and
+    each quantizer either None or in its plain quantising state (the LSQ / LSQ+ parameter repair rides in the launch as in
+    the other one-launch sites).  Returns the [B, 1, h*d] context, or None (nothing launched): the caller runs the eager
+    sequence."""
+    if not FUSE_DECODE_ATTENTION or torch.is_grad_enabled() or _dropout_active(dropout):
+        return None
+    if q.dim() != 4 or q.shape[2] != 1 or k.dim() != 4:
+        return None
+    params = []
+    # a learnable quantizer's grad factor goes by the size of the tensor it would see: probabilities [B*h, 1, S], context [B, 1, h*d]
+    for quantizer, numel in ((probs_quantizer, q.shape[0] * q.shape[1] * k.shape[2]), (ctx_quantizer, q.numel())):
+        if quantizer is None:
+            params.append(None)
+            continue
+        if not _plain_quantizing(quantizer, q):
+            return None
+        mode = quantizer.param_mode
+        if isinstance(quantizer, _LearnableFakeQuantize):
+            mode |= ops.PARAM_SANITIZE
+            quantizer._touch_qparams()
+        params.append((quantizer.scale.data, quantizer.zero_point.data, quantizer.quant_min, quantizer.quant_max, mode,
+                       quantizer._grad_factor(_Numel(numel)) if quantizer.param_mode != ops.PARAM_FIXED else 1.0))
+    return ops.decode_attention_fake_quant(q, k, v, mask, params[0], params[1])
 
 
 def _dropout_active(dropout):

@@ -5,8 +5,12 @@ BART-large shape, random init (d_model 1024, 12 + 12 layers, 16 heads, vocab 502
 batch 32 x 6 beams, source 512.  Times one decoder step (all 12 layers + lm_head, a beam reorder pending as in beam
 search) at past length S = 1, 31, 62, median and spread of --reps runs, and the whole generate(max_length=62, num_beams=6).
 --profile-steps N only runs N cached decode steps (for ``rocprofv3 --kernel-trace --stats``: launches per step).
+--fast-decode-attention: the A/B is instead the one-launch attention of a decoding step (util_layernorm.
+FUSE_DECODE_ATTENTION, csrc/decode_attention.hip) off against on, the one-launch append on in both; with --profile-steps the
+profiled steps run with the switch on.
 
     python tools/decode_bench.py [--reps 7] [--out profiles/decode_step_ab.txt]
+    python tools/decode_bench.py --fast-decode-attention [--out profiles/decode_attention_ab.txt]
 """
 import argparse
 import copy
@@ -46,10 +50,11 @@ def build(batch, src_len, layers):
     return q, ids, mask
 
 
-def step_times(q, ids, mask, beams, past, reps, fused):
+def step_times(q, ids, mask, beams, past, reps, fused, attention=False):
     """Median / min / max (ms) of one decoder step at past length `past` with a pending beam reorder."""
     from outlier_suppression_amd import util_layernorm as UL
     UL.FUSE_KV_APPEND = fused
+    UL.FUSE_DECODE_ATTENTION = attention
     dev = ids.device
     bb = ids.shape[0] * beams
     try:
@@ -73,13 +78,15 @@ def step_times(q, ids, mask, beams, past, reps, fused):
                     times.append((time.perf_counter() - t0) * 1e3)
     finally:
         UL.FUSE_KV_APPEND = True
+        UL.FUSE_DECODE_ATTENTION = False
     times.sort()
     return times[len(times) // 2], times[0], times[-1]
 
 
-def generate_time(q, ids, mask, fused):
+def generate_time(q, ids, mask, fused, attention=False):
     from outlier_suppression_amd import util_layernorm as UL
     UL.FUSE_KV_APPEND = fused
+    UL.FUSE_DECODE_ATTENTION = attention
     try:
         with torch.no_grad():
             q.generate(ids[:2], attention_mask=mask[:2], max_length=4, num_beams=6, min_length=4)
@@ -90,6 +97,7 @@ def generate_time(q, ids, mask, fused):
             return time.perf_counter() - t0, tuple(out.shape)
     finally:
         UL.FUSE_KV_APPEND = True
+        UL.FUSE_DECODE_ATTENTION = False
 
 
 def main():
@@ -100,10 +108,13 @@ def main():
     ap.add_argument("--layers", type=int, default=12)
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--profile-steps", type=int, default=0)
+    ap.add_argument("--fast-decode-attention", action="store_true")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     q, ids, mask = build(args.batch, args.src, args.layers)
     if args.profile_steps:
+        from outlier_suppression_amd import util_layernorm as UL
+        UL.FUSE_DECODE_ATTENTION = args.fast_decode_attention
         with torch.no_grad():
             q.generate(ids, attention_mask=mask, max_length=args.profile_steps + 1, num_beams=args.beams,
                        min_length=args.profile_steps + 1)
@@ -112,16 +123,20 @@ def main():
     lines = [f"decoder step, BART-large shape (random init, {args.layers}+{args.layers} layers), W6A6 LSQ+ plain quantising, "
              f"batch {args.batch} x {args.beams} beams, source {args.src}; a beam reorder pending before every step; "
              f"{args.reps} runs each, ms: median [min, max]"]
+    # (label, FUSE_KV_APPEND, FUSE_DECODE_ATTENTION) of the two forms compared
+    forms = ([("attention one-launch", True, True), ("attention eager", True, False)] if args.fast_decode_attention
+             else [("one-launch", True, False), ("eager", False, False)])
+    if args.fast_decode_attention:
+        lines[0] += "; the q / k / v + append launch on in both"
     for past in (1, 31, 62):
         row = []
-        for fused in (True, False):
-            med, lo, hi = step_times(q, ids, mask, args.beams, past, args.reps, fused)
-            row.append(f"{'one-launch' if fused else 'eager'} {med:.3f} [{lo:.3f}, {hi:.3f}]")
+        for label, fused, attention in forms:
+            med, lo, hi = step_times(q, ids, mask, args.beams, past, args.reps, fused, attention)
+            row.append(f"{label} {med:.3f} [{lo:.3f}, {hi:.3f}]")
         lines.append(f"S = {past:2d}: " + "   ".join(row))
-    for fused in (True, False):
-        secs, shape = generate_time(q, ids, mask, fused)
-        lines.append(f"generate(max_length=62, num_beams=6, min_length=62) {'one-launch' if fused else 'eager'}: "
-                     f"{secs:.2f} s, output {shape}")
+    for label, fused, attention in forms:
+        secs, shape = generate_time(q, ids, mask, fused, attention)
+        lines.append(f"generate(max_length=62, num_beams=6, min_length=62) {label}: {secs:.2f} s, output {shape}")
     text = "\n".join(lines)
     print(text)
     if args.out:
