@@ -39,7 +39,7 @@ typedef void* osq_stream;
  * 10: osq_observe_flat / _channels, osq_token_minmax, osq_observe_tokens and osq_fake_quant_per_channel take `dtype` first;
  *     their separate 16-bit twins are gone.
  *     Added within 10 (no existing signature changed): osq_quantize_codes, osq_dequantize_codes, osq_dequantize_codes_multi,
- *     osq_decode_attention_fake_quant. */
+ *     osq_decode_attention_fake_quant, osq_fake_quant_kv_append_codes, osq_decode_attention_codes. */
 #define OSQ_ABI_VERSION 10
 
 typedef enum osq_status {
@@ -529,6 +529,45 @@ typedef struct osq_codes_desc {
 int osq_dequantize_codes_multi(const osq_codes_desc* descs, const int64_t* row_end, int n_tensors,
                                int64_t total_rows, osq_stream stream);
 
+/* ------------------------------------------------------------------ the KV cache as integer codes (csrc/kv_codes.hip) */
+
+/* A KV cache that holds codes instead of fp32 words: one byte per element, u = x_quant - quant_min (the code format above,
+ * code_bits 8; quant_max - quant_min <= 255), in the cache's [batch, heads, cap, head_dim] order.  Per cached tensor a
+ * RECORD of two device floats, scale_eff / zp_eff (the effective parameters that reached the quantiser), and one device
+ * int32 `rejected` shared by every tensor of a cache, only ever added to.  (float(u + quant_min) - zp_eff) * scale_eff is
+ * the word osq_fake_quant_kv_append writes for the same element; osq_dequantize_codes(codes, y, batch * heads * cap, 1,
+ * head_dim, scale_eff, zp_eff, quant_min, 8) turns a whole buffer into the fp32 buffer of the same geometry.
+ *
+ * osq_fake_quant_kv_append_codes is osq_fake_quant_kv_append (same geometry, same parameter handling, OSQ_PARAM_SANITIZE
+ * included, same overlap rules) with a destination kind per site:
+ *   coded == 0: y (and src) fp32, exactly the fp32 entry point's site -- the query site; scale_eff / zp_eff unused.
+ *   coded != 0: y and src are BYTE buffers.  x is quantised with the live parameters (tensor_params / quantize_value: the
+ *     x_quant of the fp32 form) and x_quant - quant_min stored, four codes per lane as one 32-bit store.  The kept prefix
+ *     is copied as bytes from src through src_rows (16 bytes per lane where prefix, caps and pointers allow, else 4).
+ *     write_record != 0: the launch writes the record.  Otherwise it compares its live effective pair with the record bit
+ *     for bit and adds 1 to `rejected` on a mismatch (parameters rewritten through raw pointers since the first append).
+ *     An element without a code (x_quant NaN or not an integer: a NaN or infinite x, NaN parameters, a fractional
+ *     effective zero point) gets code 0 and adds 1 to `rejected`.  A src_rows entry outside [0, src_batch) reads nothing:
+ *     the prefix of that batch row gets code 0 and every element of it adds 1 to `rejected` (a byte has no NaN).
+ * rejected: device int32, required when a site is coded.  OSQ_ERR_UNSUPPORTED as for the fp32 entry point, with 4-byte
+ * alignment asked of byte buffers. */
+typedef struct osq_kv_codes_site {
+    const float* x;
+    void* y;
+    const void* src;
+    const int64_t* src_rows;
+    float* scale;
+    void* zero_point;
+    float* scale_eff;
+    float* zp_eff;
+    int64_t tokens, cap, offset, src_batch, src_cap;
+    int32_t zp_type, mode;
+    float grad_factor;
+    int32_t quant_min, quant_max, coded, write_record, pad;
+} osq_kv_codes_site;
+int osq_fake_quant_kv_append_codes(const osq_kv_codes_site* sites, int n_sites, int64_t batch, int64_t heads,
+                                   int64_t head_dim, int32_t* rejected, osq_stream stream);
+
 /* ------------------------------------------------------------------ MSEFast (observer.py:412-567) */
 
 /* one_side: 0 = 'no', 1 = 'pos', 2 = 'neg' (observer.py:528-529, decided once by the caller on
@@ -763,8 +802,8 @@ int osq_attention_softmax_fake_quant(const float* scores, const float* mask, int
  * NULL, or dense [batch, heads, 1, kv_len], receives p'.  All fp32.  Each parameter group is (scale, zero_point, zp_type,
  * mode, grad_factor, quant_min, quant_max) as in osq_headsplit_site, OSQ_PARAM_SANITIZE included; a NULL scale means no
  * quantizer: the values pass through.  For given p (given c) the outputs are word-equal to osq_fake_quant_per_tensor.
- * The dot products are fp32 sums in an order fixed by (head_dim, kv_len) alone (csrc/decode_attention.hip) -- not
- * rocBLAS's: against the eager sequence the result is equal to a tolerance, not bit for bit; the same inputs give the same
+ * The dot products are fp32 sums in an order fixed by (head_dim, kv_len) alone (csrc/decode_attention.hip) -- not by cap,
+ * placement or the cache's storage format (osq_decode_attention_codes), and not rocBLAS's: against the eager sequence the result is equal to a tolerance, not bit for bit; the same inputs give the same
  * words on every run, whatever the caps.
  * OSQ_ERR_UNSUPPORTED, nothing launched (the caller runs the eager sequence): head_dim / 4 not a power of two <= 64, kv_len
  * outside [1, 4096], a pointer not 16-byte aligned.  Inference only. */
@@ -776,6 +815,23 @@ int osq_decode_attention_fake_quant(const float* q, const float* k, const float*
                                     float* ctx_scale, void* ctx_zero_point, int ctx_zp_type, int ctx_mode,
                                     float ctx_grad_factor, int ctx_quant_min, int ctx_quant_max,
                                     osq_stream stream);
+
+/* osq_decode_attention_fake_quant over a coded cache: k / v are byte buffers [batch, heads, cap, head_dim] of codes, each
+ * with its record (k_scale_eff / k_zp_eff, one device float each) and quant_min.  A lane reads four codes as one 32-bit
+ * load, forms float(u + quant_min), then (q - zp_eff) * scale_eff, and goes on as the fp32 form does: out and probs_out
+ * are word-equal to osq_decode_attention_fake_quant on the dequantised fp32 k / v, for every shape that takes.  rejected:
+ * the cache's counter (device int32, required); non-zero on entry -> every word of out and probs_out is NaN.  Limits and
+ * OSQ_ERR_UNSUPPORTED cases as the fp32 form, k / v 4-byte aligned. */
+int osq_decode_attention_codes(const float* q, const uint8_t* k, const uint8_t* v, const float* mask, float* out,
+                               float* probs_out, int64_t batch, int64_t heads, int64_t head_dim, int64_t kv_len,
+                               int64_t k_cap, int64_t v_cap,
+                               const float* k_scale_eff, const float* k_zp_eff, int k_quant_min,
+                               const float* v_scale_eff, const float* v_zp_eff, int v_quant_min, const int32_t* rejected,
+                               float* probs_scale, void* probs_zero_point, int probs_zp_type, int probs_mode,
+                               float probs_grad_factor, int probs_quant_min, int probs_quant_max,
+                               float* ctx_scale, void* ctx_zero_point, int ctx_zp_type, int ctx_mode,
+                               float ctx_grad_factor, int ctx_quant_min, int ctx_quant_max,
+                               osq_stream stream);
 
 /* ------------------------------------------------------------------ bf16 / fp16 only (lowp.hip) */
 

@@ -67,11 +67,26 @@ def set_fast_decode_attention(on=True):
     util_layernorm.FUSE_DECODE_ATTENTION = bool(on)
 
 
+def set_cache_codes(on=True):
+    """New KV caches of incremental decoding hold integer codes, one byte per element, instead of fp32 words
+    (util_layernorm.CACHE_CODES; model/quant_bart.py, QuantizedBartCache; default OFF).  What is read back from the cache,
+    and what attention computes over it, are the same words.  OSQ_CACHE_CODES=1 turns it on at load.  Independent of
+    set_fast_decode_attention."""
+    from . import util_layernorm
+    util_layernorm.CACHE_CODES = bool(on)
+
+
+def cache_codes_from_environment(environ=None):
+    """What OSQ_CACHE_CODES asks for: unset, empty or "0" -> False, anything else -> True."""
+    import os
+    return (os.environ if environ is None else environ).get("OSQ_CACHE_CODES", "") not in ("", "0")
+
+
 def reset_tier(_lib=None):
     """The package's default tier, as the environment states it (applied when the library is first loaded): MSEFast sums in
     the reference's one-thread order, the backward's sums order-free; OSQ_STRICT=1 / 0 force both; OSQ_FAST=0 / 1 the
     one-launch LayerNorm site; OSQ_FAST_SOFTMAX=1 the one-launch attention-probabilities site and OSQ_FAST_DECODE_ATTENTION=1
-    the one-launch attention of a cached decoding step (unset: off)."""
+    the one-launch attention of a cached decoding step (unset: off); OSQ_CACHE_CODES=1 KV caches as integer codes (unset: off)."""
     import os
     width = int(os.environ.get("OSQ_STRICT_SIMD", "8"))
     strict = os.environ.get("OSQ_STRICT", "")
@@ -83,6 +98,7 @@ def reset_tier(_lib=None):
     set_fast(os.environ.get("OSQ_FAST", "") != "0")
     set_fast_softmax(os.environ.get("OSQ_FAST_SOFTMAX", "") not in ("", "0"))
     set_fast_decode_attention(os.environ.get("OSQ_FAST_DECODE_ATTENTION", "") not in ("", "0"))
+    set_cache_codes(cache_codes_from_environment())
 
 
 _apply_environment = reset_tier

@@ -68,6 +68,15 @@ class KvAppendSite(ctypes.Structure):
                 ("pad", ctypes.c_int32)]
 
 
+class KvCodesSite(ctypes.Structure):
+    """``osq_kv_codes_site``: one entry of the table of osq_fake_quant_kv_append_codes."""
+    _fields_ = [("x", _P), ("y", _P), ("src", _P), ("src_rows", _P), ("scale", _P), ("zero_point", _P), ("scale_eff", _P),
+                ("zp_eff", _P), ("tokens", _L), ("cap", _L), ("offset", _L), ("src_batch", _L), ("src_cap", _L),
+                ("zp_type", ctypes.c_int32), ("mode", ctypes.c_int32), ("grad_factor", _F), ("quant_min", ctypes.c_int32),
+                ("quant_max", ctypes.c_int32), ("coded", ctypes.c_int32), ("write_record", ctypes.c_int32),
+                ("pad", ctypes.c_int32)]
+
+
 class SiteDesc(ctypes.Structure):
     """``osq_site_desc``: one entry of the table of osq_token_minmax_multi."""
     _fields_ = [("x", _P), ("lengths", _P), ("token_min", _P), ("token_max", _P), ("view", TokenView),
@@ -91,6 +100,7 @@ SIGNATURES = {
                                                _P, _P, _I, _I, _F, _I, _I, _P]),
     "osq_fake_quant_headsplit_multi": (_I, [ctypes.POINTER(HeadSplitSite), _I, _L, _L, _L, _L, _P]),
     "osq_fake_quant_kv_append": (_I, [ctypes.POINTER(KvAppendSite), _I, _L, _L, _L, _P]),
+    "osq_fake_quant_kv_append_codes": (_I, [ctypes.POINTER(KvCodesSite), _I, _L, _L, _L, _P, _P]),
     "osq_fake_quant_per_channel": (_I, [_I, _P, _P, _P, _L, _L, _L, _P, _P, _I, _I, _F, _I, _I, _P]),
     "osq_fake_quant_weights_multi": (_I, [_P, _P, _I, _L, _P]),
     "osq_quantize_codes": (_I, [_I, _P, _P, _L, _L, _L, _P, _P, _I, _I, _F, _I, _I, _I, _P, _P, _P, _P]),
@@ -151,6 +161,8 @@ SIGNATURES = {
     "osq_attention_softmax_fake_quant": (_I, [_P, _P, _L, _L, _L, _L, _L, _L, _L, _F, _F, _P, _P, _P, _I, _I, _F, _I, _I, _P]),
     "osq_decode_attention_fake_quant": (_I, [_P, _P, _P, _P, _P, _P, _L, _L, _L, _L, _L, _L,
                                              _P, _P, _I, _I, _F, _I, _I, _P, _P, _I, _I, _F, _I, _I, _P]),
+    "osq_decode_attention_codes": (_I, [_P, _P, _P, _P, _P, _P, _L, _L, _L, _L, _L, _L, _P, _P, _I, _P, _P, _I, _P,
+                                        _P, _P, _I, _I, _F, _I, _I, _P, _P, _I, _I, _F, _I, _I, _P]),
     "osq_fake_quant_chain_lowp": (_I, [_I, _P, _P, _L, _P, _P, _I, _I, _I, _P]),
     "osq_fake_quant_chain_backward_lowp": (_I, [_I, _P, _P, _P, _L, _P, _P, _I, _I, _I, _P]),
     "osq_fake_quant_per_tensor_widen": (_I, [_I, _P, _P, _L, _P, _P, _I, _I, _F, _I, _I, _P]),

@@ -20,7 +20,15 @@
 // partial vectors meet in LDS (4 x head_dim floats) and are added in wave order.  Traffic per (b, h): 2 * kv_len *
 // head_dim * 4 B of K and V, head_dim * 4 B of q, kv_len * 4 B of mask, head_dim * 4 B written.
 //
-// Summation order, fixed by (head_dim, kv_len) alone -- not by cap, alignment or placement; no float atomics:
+// K and V are the cache's fp32 buffers, or its byte buffers of integer codes (osq_decode_attention_codes; kv_codes.hip
+// writes them): the same kernel body with the same lane map, a lane then loading its four elements of a row as ONE 32-bit
+// word of four codes instead of a float4 and turning each into float(u + quant_min), then (q - zp_eff) * scale_eff
+// (dequantize_value) -- the word the fp32 cache holds -- before the arithmetic below.  A quarter of the bytes per load,
+// so four times the loads are issued before the first is reduced (KvCodes::kInFlight): the bytes in flight per CU stay.
+// Traffic per (b, h) over codes: 2 * kv_len * head_dim bytes of K and V.
+//
+// Summation order, fixed by (head_dim, kv_len) alone -- not by cap, alignment or placement, nor by the cache's storage
+// format (the loads in flight do not enter it: every position's products are formed and added as listed); no float atomics:
 //   a score      four products of a lane added left to right, then an xor butterfly over the row's LPR lanes
 //                (strides 1, 2, 4, ... : both partners of a step hold the same sum bit for bit);
 //   the softmax  denominator: thread t adds exps t, t + 256, ... in order, wave_sum_f32, then (w0 + w1) + (w2 + w3);
@@ -28,7 +36,7 @@
 //                butterfly over the wave's R row groups (strides LPR, 2 LPR, ... 32), then ((w0 + w1) + w2) + w3.
 #include <math.h>
 #include <hip/hip_runtime.h>
-#include "osq_device.h"
+#include "codes_device.h"
 #include "osq_host.h"
 
 namespace osq {
@@ -36,7 +44,35 @@ namespace osq {
 constexpr int kDecThreads = 256;
 constexpr int kDecWaves = kDecThreads / OSQ_WAVE;
 constexpr int kDecMaxKv = 4096;          // the row of scores / probabilities in LDS: 16 KB
-constexpr int kTripsInFlight = 4;        // loads issued per lane before the first reduction
+
+// How a lane reads its four elements of a row of K or V: the word it loads, how many such loads it issues before the first
+// reduction, and the four fp32 values of a word.
+struct DecCode {               // the record of a coded tensor; unused by the fp32 form
+    const float* scale_eff;
+    const float* zp_eff;
+    int quant_min;
+};
+struct KvWords {               // fp32 cache: a float4, 4 x 16 B in flight per lane
+    typedef float4 Word;
+    static constexpr int kInFlight = 4;
+    struct Params {};
+    __device__ __forceinline__ static Params params(const DecCode&) { return Params{}; }
+    __device__ __forceinline__ static Word load(const void* base, int64_t i) { return load_stream(static_cast<const float4*>(base) + i); }
+    __device__ __forceinline__ static float4 values(const Word& w, const Params&) { return w; }
+};
+struct KvCodes {               // coded cache: four codes in 32 bits, 16 x 4 B in flight per lane
+    typedef unsigned int Word;
+    static constexpr int kInFlight = 16;
+    struct Params { float s, z; int quant_min; };
+    __device__ __forceinline__ static Params params(const DecCode& d) { return Params{d.scale_eff[0], d.zp_eff[0], d.quant_min}; }
+    __device__ __forceinline__ static Word load(const void* base, int64_t i) {
+        return __builtin_nontemporal_load(static_cast<const unsigned int*>(base) + i);
+    }
+    __device__ __forceinline__ static float4 values(const Word& w, const Params& p) {
+        return make_float4(value_of(w & 255u, p.quant_min, p.s, p.z), value_of((w >> 8) & 255u, p.quant_min, p.s, p.z),
+                           value_of((w >> 16) & 255u, p.quant_min, p.s, p.z), value_of(w >> 24, p.quant_min, p.s, p.z));
+    }
+};
 
 struct DecQuant {              // one quantizer of the site; scale == nullptr: no quantizer, values pass through
     float* scale;              // written only under OSQ_PARAM_SANITIZE
@@ -47,14 +83,16 @@ struct DecQuant {              // one quantizer of the site; scale == nullptr: n
 
 struct DecArgs {
     const float* q;            // [batch, heads, 1, head_dim] dense
-    const float* k;            // [batch, heads, k_cap, head_dim], positions [0, kv_len) read
-    const float* v;            // [batch, heads, v_cap, head_dim]
+    const void* k;             // [batch, heads, k_cap, head_dim] fp32 words or code bytes, positions [0, kv_len) read
+    const void* v;             // [batch, heads, v_cap, head_dim]
     const float* mask;         // nullable, [batch, 1, 1, kv_len] dense, additive
     float* out;                // [batch, 1, heads * head_dim] dense
     float* probs_out;          // nullable, [batch, heads, 1, kv_len] dense
     int64_t heads, k_cap, v_cap;
     int kv_len;
     DecQuant probs, ctx;
+    DecCode kc, vc;            // coded form only
+    const int32_t* rejected;   // coded form only: the cache's counter; non-zero: the cache holds elements without a code
 };
 
 __device__ __forceinline__ QParams dec_params(const DecQuant& d) {
@@ -86,8 +124,9 @@ __device__ __forceinline__ float row_groups_sum(float v) {
     return v;
 }
 
-template <int LPR>
+template <int LPR, typename KV>
 __global__ __launch_bounds__(kDecThreads) void decode_attention_fq_kernel(DecArgs a) {
+    constexpr int kTripsInFlight = KV::kInFlight;
     constexpr int R = OSQ_WAVE / LPR;              // rows of K / V one wave load covers
     constexpr int kTrip = kDecWaves * R;           // positions one trip of the workgroup covers
     __shared__ float s_p[kDecMaxKv];               // scores -> exps -> fake-quantised probabilities
@@ -99,26 +138,36 @@ __global__ __launch_bounds__(kDecThreads) void decode_attention_fq_kernel(DecArg
     const int64_t bh = blockIdx.x;
     const int n = a.kv_len;
     const int trips = (n + kTrip - 1) / kTrip;
-    const QParams pq = dec_params(a.probs), cq = dec_params(a.ctx);
+    const QParams pq = dec_params(a.probs), cq = dec_params(a.ctx);      // first: the parameter repair rides here
+
+    if (a.rejected && *a.rejected != 0) {          // workgroup-uniform: a cache with an uncodable element never yields numbers
+        const float nan = __builtin_nanf("");
+        if (a.probs_out)
+            for (int j = threadIdx.x; j < n; j += kDecThreads) a.probs_out[bh * n + j] = nan;
+        if (threadIdx.x < LPR) reinterpret_cast<float4*>(a.out)[bh * LPR + c] = make_float4(nan, nan, nan, nan);
+        return;
+    }
+    const typename KV::Params kp = KV::params(a.kc), vp = KV::params(a.vc);
 
     // ---- scores
     const float4 q4 = reinterpret_cast<const float4*>(a.q)[bh * LPR + c];
-    const float4* kb = reinterpret_cast<const float4*>(a.k) + bh * a.k_cap * LPR + c;
+    const int64_t kb = bh * a.k_cap * LPR + c;           // in words of four elements
     const float* mrow = a.mask ? a.mask + (bh / a.heads) * n : nullptr;
     for (int t0 = 0; t0 < trips; t0 += kTripsInFlight) {
-        float4 kk[kTripsInFlight];
+        typename KV::Word kw[kTripsInFlight];
 #pragma unroll
         for (int u = 0; u < kTripsInFlight; ++u) {
             const int j = ((t0 + u) * kDecWaves + w) * R + r;
-            kk[u] = load_stream(kb + static_cast<int64_t>(j < n ? j : n - 1) * LPR);     // past the end: the last row again, unused
+            kw[u] = KV::load(a.k, kb + static_cast<int64_t>(j < n ? j : n - 1) * LPR);     // past the end: the last row again, unused
         }
 #pragma unroll
         for (int u = 0; u < kTripsInFlight; ++u) {
             const int j = ((t0 + u) * kDecWaves + w) * R + r;
-            float d = q4.x * kk[u].x;
-            d = d + q4.y * kk[u].y;
-            d = d + q4.z * kk[u].z;
-            d = d + q4.w * kk[u].w;
+            const float4 kk = KV::values(kw[u], kp);
+            float d = q4.x * kk.x;
+            d = d + q4.y * kk.y;
+            d = d + q4.z * kk.z;
+            d = d + q4.w * kk.w;
             d = row_lanes_sum<LPR>(d);
             if (c == 0 && j < n) s_p[j] = mrow ? d + mrow[j] : d;
         }
@@ -151,24 +200,25 @@ __global__ __launch_bounds__(kDecThreads) void decode_attention_fq_kernel(DecArg
     __syncthreads();
 
     // ---- context
-    const float4* vb = reinterpret_cast<const float4*>(a.v) + bh * a.v_cap * LPR + c;
+    const int64_t vb = bh * a.v_cap * LPR + c;
     float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
     for (int t0 = 0; t0 < trips; t0 += kTripsInFlight) {
-        float4 vv[kTripsInFlight];
+        typename KV::Word vw[kTripsInFlight];
 #pragma unroll
         for (int u = 0; u < kTripsInFlight; ++u) {
             const int j = ((t0 + u) * kDecWaves + w) * R + r;
-            vv[u] = load_stream(vb + static_cast<int64_t>(j < n ? j : n - 1) * LPR);
+            vw[u] = KV::load(a.v, vb + static_cast<int64_t>(j < n ? j : n - 1) * LPR);
         }
 #pragma unroll
         for (int u = 0; u < kTripsInFlight; ++u) {
             const int j = ((t0 + u) * kDecWaves + w) * R + r;
             if (j < n) {
                 const float p = s_p[j];
-                acc.x = acc.x + p * vv[u].x;
-                acc.y = acc.y + p * vv[u].y;
-                acc.z = acc.z + p * vv[u].z;
-                acc.w = acc.w + p * vv[u].w;
+                const float4 vv = KV::values(vw[u], vp);
+                acc.x = acc.x + p * vv.x;
+                acc.y = acc.y + p * vv.y;
+                acc.z = acc.z + p * vv.z;
+                acc.w = acc.w + p * vv.w;
             }
         }
     }
@@ -194,6 +244,46 @@ static bool dec_mode_ok(int mode) {
     return (mode & ~(OSQ_PARAM_MODE_MASK | OSQ_PARAM_SANITIZE)) == 0 && (mode & OSQ_PARAM_MODE_MASK) <= OSQ_PARAM_LSQPLUS;
 }
 
+// checks and launch shared by the two storage formats; kv_align: what K and V must be aligned to
+template <typename KV>
+static int launch_decode_attention(const char* what, const float* q, const void* k, const void* v, const float* mask, float* out,
+                                   float* probs_out, int64_t batch, int64_t heads, int64_t head_dim, int64_t kv_len,
+                                   int64_t k_cap, int64_t v_cap, const DecCode& kc, const DecCode& vc, const int32_t* rejected,
+                                   const DecQuant& probs, const DecQuant& ctx, uintptr_t kv_align, osq_stream stream) {
+    OSQ_REQUIRE(batch >= 0 && heads >= 0 && head_dim > 0 && batch * heads <= INT32_MAX, "decode_attention: bad shape");
+    OSQ_REQUIRE(!probs.scale || probs.zero_point, "decode_attention: probs scale without zero_point");
+    OSQ_REQUIRE(!ctx.scale || ctx.zero_point, "decode_attention: ctx scale without zero_point");
+    OSQ_REQUIRE(!probs.scale || dec_mode_ok(probs.mode), "decode_attention: bad probs mode");
+    OSQ_REQUIRE(!ctx.scale || dec_mode_ok(ctx.mode), "decode_attention: bad ctx mode");
+    if (kv_len < 1 || kv_len > kDecMaxKv) return OSQ_ERR_UNSUPPORTED;
+    const int64_t lpr = head_dim / 4;
+    if (head_dim % 4 || lpr > OSQ_WAVE || (lpr & (lpr - 1))) return OSQ_ERR_UNSUPPORTED;
+    OSQ_REQUIRE(k_cap >= kv_len && v_cap >= kv_len, "decode_attention: cap below kv_len");
+    if (batch * heads == 0) return OSQ_OK;
+    OSQ_REQUIRE(q && k && v && out, "decode_attention: null tensor");
+    if (!aligned16(q) || !aligned16(out) || !aligned16(mask) || !aligned16(probs_out)) return OSQ_ERR_UNSUPPORTED;
+    if ((reinterpret_cast<uintptr_t>(k) | reinterpret_cast<uintptr_t>(v)) & (kv_align - 1u)) return OSQ_ERR_UNSUPPORTED;
+    DecArgs a{q, k, v, mask, out, probs_out, heads, k_cap, v_cap, static_cast<int>(kv_len), probs, ctx, kc, vc, rejected};
+    const dim3 grid(static_cast<unsigned>(batch * heads));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+#define OSQ_DEC(LPR) hipLaunchKernelGGL((decode_attention_fq_kernel<LPR, KV>), grid, dim3(kDecThreads), 0, st, a)
+    switch (lpr) {
+        case 1: OSQ_DEC(1); break;
+        case 2: OSQ_DEC(2); break;
+        case 4: OSQ_DEC(4); break;
+        case 8: OSQ_DEC(8); break;
+        case 16: OSQ_DEC(16); break;
+        case 32: OSQ_DEC(32); break;
+        default: OSQ_DEC(64); break;
+    }
+#undef OSQ_DEC
+    return check_launch(what);
+}
+
+static DecQuant dec_quant(float* scale, void* zero_point, int zp_type, int mode, float grad_factor, int quant_min, int quant_max) {
+    return DecQuant{scale, zero_point, zp_type, mode, grad_factor, static_cast<float>(quant_min), static_cast<float>(quant_max)};
+}
+
 }  // namespace osq
 
 using namespace osq;
@@ -206,36 +296,26 @@ extern "C" int osq_decode_attention_fake_quant(const float* q, const float* k, c
                                                float* ctx_scale, void* ctx_zero_point, int ctx_zp_type, int ctx_mode,
                                                float ctx_grad_factor, int ctx_quant_min, int ctx_quant_max,
                                                osq_stream stream) {
-    OSQ_REQUIRE(batch >= 0 && heads >= 0 && head_dim > 0 && batch * heads <= INT32_MAX, "decode_attention_fake_quant: bad shape");
-    OSQ_REQUIRE(!probs_scale || probs_zero_point, "decode_attention_fake_quant: probs scale without zero_point");
-    OSQ_REQUIRE(!ctx_scale || ctx_zero_point, "decode_attention_fake_quant: ctx scale without zero_point");
-    OSQ_REQUIRE(!probs_scale || dec_mode_ok(probs_mode), "decode_attention_fake_quant: bad probs mode");
-    OSQ_REQUIRE(!ctx_scale || dec_mode_ok(ctx_mode), "decode_attention_fake_quant: bad ctx mode");
-    if (kv_len < 1 || kv_len > kDecMaxKv) return OSQ_ERR_UNSUPPORTED;
-    const int64_t lpr = head_dim / 4;
-    if (head_dim % 4 || lpr > OSQ_WAVE || (lpr & (lpr - 1))) return OSQ_ERR_UNSUPPORTED;
-    OSQ_REQUIRE(k_cap >= kv_len && v_cap >= kv_len, "decode_attention_fake_quant: cap below kv_len");
-    if (batch * heads == 0) return OSQ_OK;
-    OSQ_REQUIRE(q && k && v && out, "decode_attention_fake_quant: null tensor");
-    if (!aligned16(q) || !aligned16(k) || !aligned16(v) || !aligned16(out) || !aligned16(mask) || !aligned16(probs_out))
-        return OSQ_ERR_UNSUPPORTED;
-    DecArgs a{q, k, v, mask, out, probs_out, heads, k_cap, v_cap, static_cast<int>(kv_len),
-              DecQuant{probs_scale, probs_zero_point, probs_zp_type, probs_mode, probs_grad_factor,
-                       static_cast<float>(probs_quant_min), static_cast<float>(probs_quant_max)},
-              DecQuant{ctx_scale, ctx_zero_point, ctx_zp_type, ctx_mode, ctx_grad_factor,
-                       static_cast<float>(ctx_quant_min), static_cast<float>(ctx_quant_max)}};
-    const dim3 grid(static_cast<unsigned>(batch * heads));
-    hipStream_t st = static_cast<hipStream_t>(stream);
-#define OSQ_DEC(LPR) hipLaunchKernelGGL((decode_attention_fq_kernel<LPR>), grid, dim3(kDecThreads), 0, st, a)
-    switch (lpr) {
-        case 1: OSQ_DEC(1); break;
-        case 2: OSQ_DEC(2); break;
-        case 4: OSQ_DEC(4); break;
-        case 8: OSQ_DEC(8); break;
-        case 16: OSQ_DEC(16); break;
-        case 32: OSQ_DEC(32); break;
-        default: OSQ_DEC(64); break;
-    }
-#undef OSQ_DEC
-    return check_launch("decode_attention_fake_quant");
+    return launch_decode_attention<KvWords>(
+        "decode_attention_fake_quant", q, k, v, mask, out, probs_out, batch, heads, head_dim, kv_len, k_cap, v_cap, DecCode{}, DecCode{},
+        nullptr, dec_quant(probs_scale, probs_zero_point, probs_zp_type, probs_mode, probs_grad_factor, probs_quant_min, probs_quant_max),
+        dec_quant(ctx_scale, ctx_zero_point, ctx_zp_type, ctx_mode, ctx_grad_factor, ctx_quant_min, ctx_quant_max), 16u, stream);
+}
+
+extern "C" int osq_decode_attention_codes(const float* q, const uint8_t* k, const uint8_t* v, const float* mask, float* out,
+                                          float* probs_out, int64_t batch, int64_t heads, int64_t head_dim, int64_t kv_len,
+                                          int64_t k_cap, int64_t v_cap,
+                                          const float* k_scale_eff, const float* k_zp_eff, int k_quant_min,
+                                          const float* v_scale_eff, const float* v_zp_eff, int v_quant_min, const int32_t* rejected,
+                                          float* probs_scale, void* probs_zero_point, int probs_zp_type, int probs_mode,
+                                          float probs_grad_factor, int probs_quant_min, int probs_quant_max,
+                                          float* ctx_scale, void* ctx_zero_point, int ctx_zp_type, int ctx_mode,
+                                          float ctx_grad_factor, int ctx_quant_min, int ctx_quant_max,
+                                          osq_stream stream) {
+    OSQ_REQUIRE(k_scale_eff && k_zp_eff && v_scale_eff && v_zp_eff && rejected, "decode_attention_codes: null record or rejected counter");
+    return launch_decode_attention<KvCodes>(
+        "decode_attention_codes", q, k, v, mask, out, probs_out, batch, heads, head_dim, kv_len, k_cap, v_cap,
+        DecCode{k_scale_eff, k_zp_eff, k_quant_min}, DecCode{v_scale_eff, v_zp_eff, v_quant_min}, rejected,
+        dec_quant(probs_scale, probs_zero_point, probs_zp_type, probs_mode, probs_grad_factor, probs_quant_min, probs_quant_max),
+        dec_quant(ctx_scale, ctx_zero_point, ctx_zp_type, ctx_mode, ctx_grad_factor, ctx_quant_min, ctx_quant_max), 4u, stream);
 }

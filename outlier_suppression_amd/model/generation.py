@@ -56,7 +56,8 @@ def _step_logits(model, seq, enc, attention_mask, cache):
     return logits[:, -1, :]
 
 
-def generate(model, input_ids, attention_mask=None, max_length=None, num_beams=None, use_cache=True, **kwargs):
+def generate(model, input_ids, attention_mask=None, max_length=None, num_beams=None, use_cache=True, cache_codes=None,
+             **kwargs):
     if kwargs.pop("synced_gpus", False):      # Seq2SeqTrainer's predict_with_generate passes synced_gpus=False
         raise NotImplementedError("generate(): synced_gpus=True is not supported")
     for name in _NOT_COVERED:
@@ -79,21 +80,35 @@ def generate(model, input_ids, attention_mask=None, max_length=None, num_beams=N
         attention_mask = torch.ones_like(input_ids)
     enc = model.get_encoder()(input_ids, attention_mask=attention_mask)
     n_layers = len(model.model.decoder.layers)
+    from .. import util_layernorm
+    from .quant_bart import QuantizedBartCache
+    codes = util_layernorm.CACHE_CODES if cache_codes is None else bool(cache_codes)
+    cache = QuantizedBartCache(n_layers, capacity=max_length, codes=codes) if use_cache else None
     if num_beams == 1:
         if n_return != 1:
             raise ValueError("greedy decoding returns one sequence per input (num_return_sequences must be 1)")
-        return _greedy(model, enc, attention_mask, start, pad, eos_t, procs, max_length, use_cache, n_layers)
+        return _checked(cache, _greedy(model, enc, attention_mask, start, pad, eos_t, procs, max_length, cache))
     if n_return > num_beams:
         raise ValueError("num_return_sequences must not exceed num_beams")
-    return _beam_search(model, enc, attention_mask, start, pad, eos_t, procs, max_length, num_beams, n_return,
-                        get("length_penalty"), get("early_stopping"), use_cache, n_layers)
+    return _checked(cache, _beam_search(model, enc, attention_mask, start, pad, eos_t, procs, max_length, num_beams, n_return,
+                                        get("length_penalty"), get("early_stopping"), cache))
 
 
-def _greedy(model, enc, attention_mask, start, pad, eos, procs, max_length, use_cache, n_layers):
-    from .quant_bart import QuantizedBartCache
+def _checked(cache, tokens):
+    """After the last step on a cache of integer codes: one read of its counter (a host sync).  A cache that holds elements
+    without a code has produced NaN, not tokens."""
+    if cache is not None and cache.codes:
+        bad = cache.rejected()
+        if bad:
+            raise RuntimeError(f"generate(): the KV cache holds {bad} elements without an integer code (x_quant is NaN or not "
+                               "an integer: a NaN / infinite key or value, a non-integer zero point, or quantizer parameters "
+                               "rewritten during decoding); decode with cache_codes=False")
+    return tokens
+
+
+def _greedy(model, enc, attention_mask, start, pad, eos, procs, max_length, cache):
     b = enc.shape[0]
     seq = torch.full((b, 1), start, dtype=torch.long, device=enc.device)
-    cache = QuantizedBartCache(n_layers, capacity=max_length) if use_cache else None
     unfinished = torch.ones(b, dtype=torch.long, device=enc.device)
     while seq.shape[1] < max_length:
         scores = procs(seq, _step_logits(model, seq, enc, attention_mask, cache).to(torch.float32))
@@ -116,9 +131,8 @@ def _gather(t, idx):
 
 
 def _beam_search(model, enc, attention_mask, start, pad, eos, procs, max_length, nb, n_return, length_penalty,
-                 early_stopping, use_cache, n_layers):
+                 early_stopping, cache):
     """transformers' vectorised beam search (GenerationMixin._beam_search, 5.x) with the prompt of one start token."""
-    from .quant_bart import QuantizedBartCache
     dev = enc.device
     bsz = enc.shape[0]
     enc = enc.repeat_interleave(nb, dim=0)
@@ -138,7 +152,6 @@ def _beam_search(model, enc, attention_mask, start, pad, eos, procs, max_length,
     improvable = torch.ones((bsz, 1), dtype=torch.bool, device=dev)
     finished_len = torch.zeros((bsz, nb), dtype=torch.long, device=dev)      # generated tokens of each finished beam
     offsets = torch.arange(bsz, device=dev).view(-1, 1) * nb
-    cache = QuantizedBartCache(n_layers, capacity=max_length) if use_cache else None
     while True:
         flat = running[:, :, :cur].reshape(bsz * nb, cur)
         logits = _step_logits(model, flat, enc, attention_mask, cache).to(torch.float32)

@@ -25,10 +25,13 @@ from torch import nn
 
 from . import generation
 from .losses import classification_loss, lm_loss, span_loss, with_loss
+from .. import ops
+from .. import util_layernorm as _UL
 from ..quantization import QuantizedModule, Quantizer
 from ..util_layernorm import (GammaResidual, QuantizedLayerNorm, activation_fake_quant, attention_probs_fake_quant,
-                              decode_attention_fake_quant, kv_append_fake_quant, merge_heads_fake_quant,
-                              qkv_heads_fake_quant, residual_layernorm, split_heads_fake_quant)
+                              decode_attention_fake_quant, kv_append_codes_fake_quant, kv_append_fake_quant,
+                              kv_site_params, merge_heads_fake_quant, qkv_heads_fake_quant, residual_layernorm,
+                              split_heads_fake_quant)
 
 
 def shift_tokens_right(input_ids, pad_token_id, decoder_start_token_id):
@@ -76,6 +79,59 @@ def _embed_scale(stack):
     return getattr(stack.embed_tokens, "embed_scale", 1.0)
 
 
+class _CodedTensor:
+    """A cached tensor held as integer codes, as QuantizedBartAttention sees it: ``codes`` the uint8 [B, h, S, d] tensor (a
+    ``[:, :, :S]`` view of a cache buffer, or the whole cross-attention tensor), ``record`` its (scale_eff, zp_eff,
+    quant_min), ``rejected`` the cache's counter."""
+
+    __slots__ = ("codes", "record", "rejected")
+
+    def __init__(self, codes, record, rejected):
+        self.codes, self.record, self.rejected = codes, record, rejected
+
+    def float(self):
+        """The fp32 [B, h, S, d] tensor, a view of a buffer of the coded one's own geometry: the words and strides an fp32
+        cache hands out."""
+        c = self.codes
+        b, h, s, d = c.shape
+        row = c.stride(1) if h > 1 else (c.stride(0) if b > 1 else s * d)       # cap * d of the buffer c is a view of
+        buf = c if row == s * d else c.as_strided((b, h, row // d, d), (h * row, row, d, 1))
+        return ops.dequantize_kv_codes(buf, self.record)[:, :, :s]
+
+
+class _CodeRecord:
+    """What a coded cache tensor keeps besides its bytes: the device pair (scale_eff, zp_eff) its first append wrote, and
+    the host-side identity of that append's parameters."""
+
+    __slots__ = ("scale_eff", "zp_eff", "quant_min", "identity", "pinned", "fresh")
+
+    def __init__(self, pair, params):
+        self.scale_eff, self.zp_eff = pair[0:1], pair[1:2]
+        self.quant_min = params[2]
+        self.identity = _code_identity(params)
+        self.pinned = params[:2]                                    # keeps the ids in `identity` from being reused
+        self.fresh = True                                           # no launch has written the device pair yet
+
+    def triple(self):
+        return self.scale_eff, self.zp_eff, self.quant_min
+
+
+def _code_identity(params):
+    """Host-side identity of a site's parameters (util_layernorm.kv_site_params): equal identities give the same effective
+    (scale, zero point) words unless somebody wrote the parameters through raw pointers (the launch checks that)."""
+    scale, zp, quant_min, quant_max, mode, grad_factor = params
+    return (grad_factor, quant_min, quant_max, mode, id(scale), scale._version, id(zp), zp._version)
+
+
+def _takes_codes(params, x, heads):
+    """Whether a site takes codes: the one-launch append takes it (params), its codes fit a byte, the kernels take its head size."""
+    return (params is not None and params[3] - params[2] <= 255 and x.shape[2] % heads == 0
+            and (x.shape[2] // heads) % 4 == 0)
+
+
+_SELF, _CROSS = ("k", "v"), ("cross_k", "cross_v")
+
+
 class QuantizedBartCache:
     """The decoder's KV cache for incremental decoding.
 
@@ -87,24 +143,40 @@ class QuantizedBartCache:
 
     The object also reads as the reference's legacy tuple of tuples: ``cache[i] == (k, v, cross_k, cross_v)``, each a
     [B, h, S, d] view, ``cache[0][0].shape[2]`` the past length (quant_bart.py:774).  Reading it applies a pending reorder.
-    A step extends the cache in place and returns the same object: views read from it stay valid until the next step."""
+    A step extends the cache in place and returns the same object: views read from it stay valid until the next step.
 
-    def __init__(self, num_layers, capacity=None):
+    ``codes=True``: every tensor whose site qualifies (the one-launch append would take it -- util_layernorm.kv_site_params
+    -- and quant_max - quant_min <= 255) is held as integer codes, one byte per element (include/osq_hip.h, "the KV cache as
+    integer codes"), with a record of the effective parameters of its first append; the other tensors -- and everything on
+    the CPU or wrapped from a tuple -- stay fp32, tensor by tensor.  A later append whose parameters differ on the host
+    side (another grad factor, a parameter tensor replaced or written) first DEMOTES that tensor: one dequantise launch,
+    fp32 from then on.  Whatever is read from the cache -- ``cache[i]``, iteration, ``to_legacy()``, ``past(i)`` -- is
+    fp32, the words an fp32 cache holds.  Elements without a code (NaN, an infinite value, a fractional zero point) are
+    counted on the device: ``rejected()`` reads the counter, and attention over a cache with a non-zero counter yields
+    NaN."""
+
+    def __init__(self, num_layers, capacity=None, codes=False):
         self.capacity = capacity
+        self.codes = bool(codes)
         self._k = [None] * num_layers
         self._v = [None] * num_layers
-        self._spare = [None] * num_layers          # (k, v) partner buffers, or None
+        self._spare = [[None, None] for _ in range(num_layers)]     # partner buffers of k and v, or None
         self._len = [0] * num_layers
         self._rows = [None] * num_layers           # pending beam index per layer
         self._cross = [None] * num_layers          # (k, v) of the cross-attention, or None
+        self._records = [{} for _ in range(num_layers)]             # name -> _CodeRecord of the layer's coded tensors
+        self._record_pairs = None                  # [num_layers * 4, 2] fp32 on the device: every record's (scale_eff, zp_eff)
+        self._rejected = None                      # one int32 on the device
+        self._demoted = []
 
     @classmethod
-    def wrap(cls, past, num_layers, capacity=None):
+    def wrap(cls, past, num_layers, capacity=None, codes=None):
         """``past``: None, a QuantizedBartCache (returned as it is), or the reference's tuple of per-layer (k, v[, cross_k,
-        cross_v]) tensors."""
+        cross_v]) tensors, which stay fp32.  ``codes``: whether a new cache holds integer codes (None: the package switch,
+        set_cache_codes / OSQ_CACHE_CODES)."""
         if isinstance(past, cls):
             return past
-        cache = cls(num_layers, capacity)
+        cache = cls(num_layers, capacity, codes=_UL.CACHE_CODES if codes is None else codes)
         if past is not None:
             if len(past) != num_layers:
                 raise ValueError(f"past_key_values has {len(past)} layers, the decoder {num_layers}")
@@ -139,9 +211,8 @@ class QuantizedBartCache:
     def __getitem__(self, i):
         if self._k[i] is None:
             raise IndexError(f"layer {i} of the cache holds nothing yet")
-        self._materialise(i)
-        n = self._len[i]
-        return (self._k[i][:, :, :n], self._v[i][:, :, :n]) + (self._cross[i] if self._cross[i] is not None else ())
+        return self.past(i) + (tuple(self._fp32(i, name, t) for name, t in zip(_CROSS, self._cross[i]))
+                               if self._cross[i] is not None else ())
 
     def __iter__(self):
         return (self[i] for i in range(len(self)))
@@ -149,41 +220,138 @@ class QuantizedBartCache:
     def to_legacy(self):
         return tuple(self)
 
+    # ---- integer codes
+    def _operand(self, i, name, t):
+        """Tensor t of layer i as attention takes it: itself, or a _CodedTensor."""
+        rec = self._records[i].get(name)
+        return t if rec is None else _CodedTensor(t, rec.triple(), self._rejected)
+
+    def _fp32(self, i, name, t):
+        rec = self._records[i].get(name)
+        return t if rec is None else _CodedTensor(t, rec.triple(), self._rejected).float()
+
+    def _tensor(self, i, name):
+        if name in _SELF:
+            return (self._k[i], self._v[i])[_SELF.index(name)]
+        return None if self._cross[i] is None else self._cross[i][_CROSS.index(name)]
+
+    def plan(self, i, names, params, xs, heads):
+        """Before an append of the projections ``xs`` with the site parameters ``params`` (util_layernorm.kv_site_params, None
+        for a site the one-launch append does not take) to the tensors ``names`` of layer i: which of them take codes.  A tensor not yet held takes codes when the cache holds codes and its site qualifies; a coded one
+        goes on as such while its site qualifies with the parameters of its first append, and is demoted to fp32 first
+        otherwise.  Host decisions only, no sync."""
+        coded = []
+        for name, p, x in zip(names, params, xs):
+            rec, held = self._records[i].get(name), self._tensor(i, name)
+            if held is None:
+                if self.codes and _takes_codes(p, x, heads):
+                    if self._record_pairs is None:
+                        self._record_pairs = x.new_empty((len(self._k) * 4, 2))
+                        self._rejected = torch.zeros(1, dtype=torch.int32, device=x.device)
+                    slot = i * 4 + (_SELF + _CROSS).index(name)
+                    rec = self._records[i][name] = _CodeRecord(self._record_pairs[slot], p)
+            elif rec is not None and (p is None or _code_identity(p) != rec.identity):
+                self.demote(i, name)
+                rec = None
+            coded.append(rec is not None)
+        return coded
+
+    def record(self, i, name):
+        """(record pair, write_record) of a coded tensor for ops.fake_quant_kv_append_codes, or (None, False)."""
+        rec = self._records[i].get(name)
+        return (None, False) if rec is None else ((rec.scale_eff, rec.zp_eff), rec.fresh)
+
+    def appended(self, i, names):
+        for name in names:
+            rec = self._records[i].get(name)
+            if rec is not None:
+                rec.fresh = False
+
+    def demote(self, i, name):
+        """Turn a coded tensor into the fp32 tensor it stands for (one dequantise launch with its record); a tensor planned
+        but never written just loses its record.  The cache goes on as an fp32 cache for it."""
+        rec = self._records[i].pop(name, None)
+        held = self._tensor(i, name)
+        if rec is None or held is None or rec.fresh:
+            return
+        full = ops.dequantize_kv_codes(held, rec.triple())
+        if name in _SELF:
+            j = _SELF.index(name)
+            if j == 0:
+                self._k[i] = full
+            else:
+                self._v[i] = full
+            self._spare[i][j] = None
+        else:
+            pair = list(self._cross[i])
+            pair[_CROSS.index(name)] = full
+            self._cross[i] = tuple(pair)
+        self._demoted.append((i, name))
+
+    def coded(self):
+        """(layer, name) of every tensor held as codes, name one of k, v, cross_k, cross_v."""
+        return sorted((i, name) for i, recs in enumerate(self._records) for name, rec in recs.items() if not rec.fresh)
+
+    def demoted(self):
+        """(layer, name) of every tensor that was held as codes and has been demoted to fp32, in the order it happened."""
+        return list(self._demoted)
+
+    def rejected(self):
+        """Elements the cache holds no code for (plus record mismatches), read from the device counter: a host sync."""
+        return 0 if self._rejected is None else int(self._rejected.item())
+
+    def nbytes(self):
+        """Bytes of device (or host) memory the cache holds: buffers, partner buffers, cross-attention tensors, records and
+        the counter."""
+        held = [t for t in self._k + self._v if t is not None]
+        held += [t for pair in self._spare for t in pair if t is not None]
+        held += [t for pair in self._cross if pair is not None for t in pair]
+        held += [t for t in (self._record_pairs, self._rejected) if t is not None]
+        return sum(t.numel() * t.element_size() for t in held)
+
     # ---- what QuantizedBartAttention uses
-    def append_targets(self, i, bsz, heads, head_dim, t, like):
+    def append_targets(self, i, bsz, heads, head_dim, t, like, coded=(False, False)):
         """Destination buffers for a step of t tokens at layer i: (k_dst, v_dst, k_src, v_src, rows).  In place when no
-        reorder is pending and the buffer has room, else the partner buffer (the kept prefix is copied through rows)."""
+        reorder is pending and the buffer has room, else the partner buffer (the kept prefix is copied through rows).
+        ``coded``: whether a new buffer of k / of v holds codes (uint8) instead of fp32 words."""
         n, k, v, rows = self._len[i], self._k[i], self._v[i], self._rows[i]
         want = n + t
         if k is not None and rows is None and k.shape[2] >= want and k.shape[0] == bsz and k.is_contiguous():
             return k, v, None, None, None
         cap = max(want, self.capacity or 0, 2 * n)
-        spare = self._spare[i]
-        if spare is not None and spare[0].shape[0] == bsz and spare[0].shape[2] >= want:
-            kd, vd = spare
-        else:
-            shape = (bsz, heads, cap, head_dim)
-            kd, vd = like.new_empty(shape), like.new_empty(shape)
+        dst = []
+        for spare, as_codes in zip(self._spare[i], coded):
+            dtype = torch.uint8 if as_codes else like.dtype
+            if spare is None or spare.shape[0] != bsz or spare.shape[2] < want or spare.dtype != dtype:
+                spare = like.new_empty((bsz, heads, cap, head_dim), dtype=dtype)
+            dst.append(spare)
         if k is None:
-            return kd, vd, None, None, None
-        return kd, vd, k[:, :, :n], v[:, :, :n], rows
+            return dst[0], dst[1], None, None, None
+        return dst[0], dst[1], k[:, :, :n], v[:, :, :n], rows
 
     def commit(self, i, k, v, length):
         if k is not self._k[i]:
-            old = self._k[i]
-            if old is not None and old.is_contiguous() and old.dim() == 4:
-                self._spare[i] = (old, self._v[i])
+            for j, old in enumerate((self._k[i], self._v[i])):
+                if old is not None and old.is_contiguous() and old.dim() == 4:
+                    self._spare[i][j] = old
             self._k[i], self._v[i] = k, v
         self._len[i] = length
         self._rows[i] = None
 
     def past(self, i):
-        """The self-attention (k, v) of layer i as [B, h, S, d] views, any pending reorder applied (eager form), or None."""
+        """The self-attention (k, v) of layer i as fp32 [B, h, S, d] views, any pending reorder applied (eager form), or None."""
         if self._k[i] is None:
             return None
         self._materialise(i)
         n = self._len[i]
-        return self._k[i][:, :, :n], self._v[i][:, :, :n]
+        return self._fp32(i, "k", self._k[i][:, :, :n]), self._fp32(i, "v", self._v[i][:, :, :n])
+
+    def operands(self, i, n):
+        """The self-attention (k, v) of layer i over its first n positions as attention takes them."""
+        return self._operand(i, "k", self._k[i][:, :, :n]), self._operand(i, "v", self._v[i][:, :, :n])
+
+    def cross_operands(self, i):
+        return tuple(self._operand(i, name, t) for name, t in zip(_CROSS, self._cross[i]))
 
     def slot(self, i):
         return _CacheSlot(self, i)
@@ -236,16 +404,30 @@ class QuantizedBartAttention(QuantizedModule):
     def _cached_qkv(self, slot, hidden_states, key_value_states, observation_mask):
         """q / k / v of a decoding step (quant_bart.py:156-198): self-attention fake-quantizes the step's keys / values and
         appends them to the cache, cross-attention quantizes the encoder's once and reuses them.  k / v come back as
-        [B, h, S, d] views of the cache buffers."""
+        [B, h, S, d] views of the cache buffers -- as _CodedTensor where the cache holds them as integer codes."""
         cache, i, heads, d = slot.cache, slot.layer, self.num_heads, self.head_dim
         bsz, t, _ = hidden_states.shape
         xq = self.q_proj(hidden_states) * self.scaling
         qs = (self.query_post_act_fake_quantize, self.key_post_act_fake_quantize, self.value_post_act_fake_quantize)
         if key_value_states is not None:
             if cache._cross[i] is not None:
-                return (split_heads_fake_quant(qs[0], xq, heads, observation_mask),) + tuple(cache._cross[i])
+                return (split_heads_fake_quant(qs[0], xq, heads, observation_mask),) + cache.cross_operands(i)
             xk, xv = self.k_proj(key_value_states), self.v_proj(key_value_states)
             s = xk.shape[1]
+            ps = [kv_site_params(q, x) for q, x in zip(qs, (xq, xk, xv))] if cache.codes else None
+            coded = cache.plan(i, ("cross_k", "cross_v"), ps[1:], (xk, xv), heads) if cache.codes else ()
+            if any(coded):
+                ys = [x.new_empty((bsz, heads, s, d), dtype=torch.uint8 if c else x.dtype) for x, c in zip((xk, xv), coded)]
+                out = None if any(p is None for p in ps) else kv_append_codes_fake_quant(
+                    [(qs[0], ps[0], xq, xq.new_empty((bsz, heads, t, d)), 0, None, None, None, False),
+                     (qs[1], ps[1], xk, ys[0], 0, None, None) + cache.record(i, "cross_k"),
+                     (qs[2], ps[2], xv, ys[1], 0, None, None) + cache.record(i, "cross_v")], heads, cache._rejected)
+                if out is not None:
+                    cache._cross[i] = (out[1], out[2])
+                    cache.appended(i, ("cross_k", "cross_v"))
+                    return (out[0],) + cache.cross_operands(i)
+                cache.demote(i, "cross_k")
+                cache.demote(i, "cross_v")
             out = kv_append_fake_quant([(qs[0], xq, xq.new_empty((bsz, heads, t, d)), 0, None, None),
                                         (qs[1], xk, xk.new_empty((bsz, heads, s, d)), 0, None, None),
                                         (qs[2], xv, xv.new_empty((bsz, heads, s, d)), 0, None, None)], heads)
@@ -255,6 +437,20 @@ class QuantizedBartAttention(QuantizedModule):
             return tuple(out)
         xk, xv = self.k_proj(hidden_states), self.v_proj(hidden_states)
         n = cache.get_seq_length(i)
+        ps = [kv_site_params(q, x) for q, x in zip(qs, (xq, xk, xv))] if cache.codes else None
+        coded = cache.plan(i, ("k", "v"), ps[1:], (xk, xv), heads) if cache.codes else ()
+        if any(coded):
+            kd, vd, ks, vs, rows = cache.append_targets(i, bsz, heads, d, t, xk, coded)
+            out = None if any(p is None for p in ps) else kv_append_codes_fake_quant(
+                [(qs[0], ps[0], xq, xq.new_empty((bsz, heads, t, d)), 0, None, None, None, False),
+                 (qs[1], ps[1], xk, kd, n, ks, rows) + cache.record(i, "k"),
+                 (qs[2], ps[2], xv, vd, n, vs, rows) + cache.record(i, "v")], heads, cache._rejected)
+            if out is not None:
+                cache.commit(i, kd, vd, n + t)
+                cache.appended(i, ("k", "v"))
+                return (out[0],) + cache.operands(i, n + t)
+            cache.demote(i, "k")          # a geometry the coded append does not take: this layer goes on in fp32
+            cache.demote(i, "v")
         kd, vd, ks, vs, rows = cache.append_targets(i, bsz, heads, d, t, xk)
         out = kv_append_fake_quant([(qs[0], xq, xq.new_empty((bsz, heads, t, d)), 0, None, None),
                                     (qs[1], xk, kd, n, ks, rows), (qs[2], xv, vd, n, vs, rows)], heads)
@@ -295,12 +491,22 @@ class QuantizedBartAttention(QuantizedModule):
 
     def _attend(self, q, k, v, bsz, tgt_len, attention_mask, observation_mask, cached=False):
         """[B, h, T, d] q and [B, h, S, d] k / v (dense, or views of a cache buffer) -> the block's output.  ``cached``: a
-        call of the cached path, whose single-token steps have a one-launch form (util_layernorm.FUSE_DECODE_ATTENTION)."""
+        call of the cached path, whose single-token steps have a one-launch form (util_layernorm.FUSE_DECODE_ATTENTION).
+        k / v held as integer codes (_CodedTensor) go to that form as they are when both are; everything else -- one of the
+        two in fp32, the switch off, several tokens, dropout, a length the kernel does not take -- sees them dequantised."""
+        codes = None
+        if isinstance(k, _CodedTensor) and isinstance(v, _CodedTensor) and cached and tgt_len == 1:
+            codes = (k.record, v.record, k.rejected)
+        else:
+            k, v = (x.float() if isinstance(x, _CodedTensor) else x for x in (k, v))
         if cached and tgt_len == 1:
             out = decode_attention_fake_quant(self.attention_probs_post_act_fake_quantize, self.context_post_act_fake_quantize,
-                                              q, k, v, attention_mask, dropout=(self.dropout, self.training))
+                                              q, k.codes if codes else k, v.codes if codes else v, attention_mask,
+                                              dropout=(self.dropout, self.training), codes=codes)
             if out is not None:
                 return self._project(out, observation_mask)
+            if codes:
+                k, v = k.float(), v.float()
         proj = (bsz * self.num_heads, -1, self.head_dim)
         q, k, v = q.view(*proj), k.view(*proj), v.view(*proj)
         w = torch.bmm(q, k.transpose(1, 2))
@@ -579,7 +785,8 @@ class QuantizedBartForConditionalGeneration(QuantizedModule):
     def generate(self, input_ids, attention_mask=None, max_length=None, num_beams=None, **kwargs):
         """Greedy or beam-search decoding with a KV cache (model/generation.py): token ids [B * num_return_sequences, L]
         padded with pad_token_id, as transformers' generate returns them.  Defaults come from the wrapped model's
-        generation_config / config."""
+        generation_config / config.  ``cache_codes``: the cache holds integer codes (None: the package switch,
+        set_cache_codes); raises RuntimeError when the cache ended up with elements that have no code."""
         return generation.generate(self, input_ids, attention_mask=attention_mask, max_length=max_length,
                                    num_beams=num_beams, **kwargs)
 

@@ -1450,40 +1450,92 @@ def fake_quant_kv_append(sites, heads):
     b = sites[0][0].shape[0]
     d = sites[0][1].shape[-1]
     table = (_hip.KvAppendSite * n)()
-    for i, (x, y, offset, (scale, zero_point, quant_min, quant_max, mode, grad_factor), src, rows) in enumerate(sites):
-        _hip.require_device(x, y, scale, zero_point)
-        _check_f32(x, y, scale)
-        t = x.shape[1]
-        if (x.dim() != 3 or x.shape[0] != b or x.shape[2] != heads * d or not x.is_contiguous() or y.dim() != 4
-                or tuple(y.shape[:2]) != (b, heads) or y.shape[3] != d or not y.is_contiguous()):
-            raise ValueError("fake_quant_kv_append: x must be [B, t, heads*d] and y [B, heads, cap, d], both contiguous")
-        if not 0 <= offset or offset + t > y.shape[2]:
-            raise ValueError(f"fake_quant_kv_append: offset {offset} + {t} tokens exceeds the capacity {y.shape[2]}")
-        e = table[i]
-        e.x, e.y, e.scale, e.zero_point = x.data_ptr(), y.data_ptr(), scale.data_ptr(), zero_point.data_ptr()
-        e.tokens, e.cap, e.offset = t, y.shape[2], int(offset)
-        if src is not None and offset > 0:
-            _hip.require_device(src)
-            _check_f32(src)
-            if src.dim() != 4 or src.shape[1] != heads or src.shape[3] != d or src.shape[2] < offset:
-                raise ValueError("fake_quant_kv_append: src must be [B', heads, S' >= offset, d]")
-            st = src.stride()
-            if st[3] != 1 or st[2] != d or st[1] % d or st[1] // d < src.shape[2] or st[0] != heads * st[1]:
-                return None
-            e.src, e.src_batch, e.src_cap = src.data_ptr(), src.shape[0], st[1] // d
-            if rows is not None:
-                _hip.require_device(rows)
-                if rows.dtype != torch.int64 or rows.dim() != 1 or rows.shape[0] != b or not rows.is_contiguous():
-                    raise ValueError("fake_quant_kv_append: src_rows must be a contiguous int64 [B] device tensor")
-                e.src_rows = rows.data_ptr()
-            elif src.shape[0] != b:
-                raise ValueError("fake_quant_kv_append: src batch differs from B and no src_rows given")
-        e.zp_type, e.mode, e.grad_factor = _zp_type(zero_point), int(mode), float(grad_factor)
-        e.quant_min, e.quant_max = int(quant_min), int(quant_max)
+    for i, (x, y, offset, params, src, rows) in enumerate(sites):
+        if not _kv_site(table[i], "fake_quant_kv_append", x, y, offset, params, src, rows, b, heads, d, torch.float32):
+            return None
     rc = lib.osq_fake_quant_kv_append(table, n, b, heads, d, _hip.stream_ptr(sites[0][0].device))
     if rc == _hip.ERR_UNSUPPORTED:
         return None
     _hip.check(rc, "fake_quant_kv_append")
+    return [site[1] for site in sites]
+
+
+def _kv_site(e, what, x, y, offset, params, src, rows, b, heads, d, dtype):
+    """Fill one entry of a KV-append table (osq_kv_append_site / osq_kv_codes_site) after checking its tensors; y and src
+    hold ``dtype`` elements.  False: a source layout the kernel does not take."""
+    scale, zero_point, quant_min, quant_max, mode, grad_factor = params
+    _hip.require_device(x, y, scale, zero_point)
+    _check_f32(x, scale)
+    if y.dtype != dtype:
+        raise TypeError(f"{what}: y must be {dtype}, got {y.dtype}")
+    t = x.shape[1]
+    if (x.dim() != 3 or x.shape[0] != b or x.shape[2] != heads * d or not x.is_contiguous() or y.dim() != 4
+            or tuple(y.shape[:2]) != (b, heads) or y.shape[3] != d or not y.is_contiguous()):
+        raise ValueError(f"{what}: x must be [B, t, heads*d] and y [B, heads, cap, d], both contiguous")
+    if not 0 <= offset or offset + t > y.shape[2]:
+        raise ValueError(f"{what}: offset {offset} + {t} tokens exceeds the capacity {y.shape[2]}")
+    e.x, e.y, e.scale, e.zero_point = x.data_ptr(), y.data_ptr(), scale.data_ptr(), zero_point.data_ptr()
+    e.tokens, e.cap, e.offset = t, y.shape[2], int(offset)
+    if src is not None and offset > 0:
+        _hip.require_device(src)
+        if src.dtype != dtype:
+            raise TypeError(f"{what}: src must be {dtype}, got {src.dtype}")
+        if src.dim() != 4 or src.shape[1] != heads or src.shape[3] != d or src.shape[2] < offset:
+            raise ValueError(f"{what}: src must be [B', heads, S' >= offset, d]")
+        st = src.stride()
+        if st[3] != 1 or st[2] != d or st[1] % d or st[1] // d < src.shape[2] or st[0] != heads * st[1]:
+            return False
+        e.src, e.src_batch, e.src_cap = src.data_ptr(), src.shape[0], st[1] // d
+        if rows is not None:
+            _hip.require_device(rows)
+            if rows.dtype != torch.int64 or rows.dim() != 1 or rows.shape[0] != b or not rows.is_contiguous():
+                raise ValueError(f"{what}: src_rows must be a contiguous int64 [B] device tensor")
+            e.src_rows = rows.data_ptr()
+        elif src.shape[0] != b:
+            raise ValueError(f"{what}: src batch differs from B and no src_rows given")
+    e.zp_type, e.mode, e.grad_factor = _zp_type(zero_point), int(mode), float(grad_factor)
+    e.quant_min, e.quant_max = int(quant_min), int(quant_max)
+    return True
+
+
+def fake_quant_kv_append_codes(sites, heads, rejected):
+    """fake_quant_kv_append with a destination kind per site (osq_fake_quant_kv_append_codes, csrc/kv_codes.hip).
+    ``sites``: 1..4 tuples ``(x, y, offset, params, src, src_rows, record, write_record)``:
+
+    * record None -- an fp32 site, exactly fake_quant_kv_append's (the query site);
+    * record ``(scale_eff, zp_eff)``, two one-element fp32 device tensors -- y and src are uint8 buffers of the same
+      [B, heads, cap, d] geometry and receive the codes ``x_quant - quant_min`` (quant_max - quant_min <= 255), the bytes of
+      ``quantize_codes`` on the head-split view; the kept prefix is copied as bytes.  ``write_record``: this launch writes
+      the record (the tensor's first append); otherwise it compares its effective parameters with the record bit for bit.
+    * rejected -- the cache's int32 device counter: elements without a code (code 0 written), a record mismatch and the
+      elements behind a src_rows entry out of range are added to it.
+
+    Returns the list of y, or None when the kernel does not take the geometry (nothing was launched)."""
+    lib = _hip.load()
+    n = len(sites)
+    if not 1 <= n <= 4:
+        raise ValueError("fake_quant_kv_append_codes: 1..4 sites")
+    _hip.require_device(rejected)
+    if rejected.dtype != torch.int32 or rejected.numel() != 1:
+        raise TypeError("fake_quant_kv_append_codes: rejected must be one int32")
+    b = sites[0][0].shape[0]
+    d = sites[0][1].shape[-1]
+    table = (_hip.KvCodesSite * n)()
+    for i, (x, y, offset, params, src, rows, record, write_record) in enumerate(sites):
+        e = table[i]
+        if not _kv_site(e, "fake_quant_kv_append_codes", x, y, offset, params, src, rows, b, heads, d,
+                        torch.float32 if record is None else torch.uint8):
+            return None
+        if record is not None:
+            if params[3] - params[2] > 255:
+                raise ValueError("fake_quant_kv_append_codes: quant_max - quant_min does not fit a byte")
+            _hip.require_device(*record)
+            _check_f32(*record)
+            e.scale_eff, e.zp_eff, e.coded, e.write_record = record[0].data_ptr(), record[1].data_ptr(), 1, int(bool(write_record))
+    rc = lib.osq_fake_quant_kv_append_codes(table, n, b, heads, d, rejected.data_ptr(), _hip.stream_ptr(sites[0][0].device))
+    if rc == _hip.ERR_UNSUPPORTED:
+        return None
+    _hip.check(rc, "fake_quant_kv_append_codes")
     return [site[1] for site in sites]
 
 
@@ -1567,10 +1619,10 @@ def attention_softmax_fake_quant(scores, mask=None, *, alpha=None, divisor=None,
 # one decoding step's attention over the KV cache: scores, mask, softmax, two quantizers in one launch
 # ---------------------------------------------------------------------------------------
 
-def _kv_cap(x, b, h, s, d):
-    """cap of a [B, h, S, d] fp32 tensor laid out as the first S positions of a [B, h, cap, d] buffer (a ``[:, :, :S]`` view of
+def _kv_cap(x, b, h, s, d, dtype=torch.float32):
+    """cap of a [B, h, S, d] fp32 (``dtype``) tensor laid out as the first S positions of a [B, h, cap, d] buffer (a ``[:, :, :S]`` view of
     a cache buffer, or a dense tensor: cap == S), or None when it is laid out otherwise."""
-    if x.dim() != 4 or tuple(x.shape) != (b, h, s, d) or x.dtype != torch.float32:
+    if x.dim() != 4 or tuple(x.shape) != (b, h, s, d) or x.dtype != dtype:
         return None
     st = x.stride()
     if st[3] != 1 or (s > 1 and st[2] != d):
@@ -1625,3 +1677,43 @@ def decode_attention_fake_quant(q, k, v, mask, probs_quant, ctx_quant, want_prob
         return None
     _hip.check(rc, "decode_attention_fake_quant")
     return (out, probs) if want_probs else out
+
+
+def decode_attention_codes(q, k, v, mask, probs_quant, ctx_quant, k_record, v_record, rejected, want_probs=False):
+    """decode_attention_fake_quant over a coded cache (osq_decode_attention_codes): k / v are uint8 [B, h, S, d] code
+    tensors, dense or ``[:, :, :S]`` views of [B, h, cap, d] buffers; k_record / v_record ``(scale_eff, zp_eff, quant_min)``
+    with one-element fp32 device tensors; rejected the cache's int32 device counter -- non-zero: every output word is NaN.
+    The outputs are word-equal to decode_attention_fake_quant on the dequantised k / v.  Returns as that function does."""
+    lib = _hip.load()
+    _hip.require_device(q, k, v, mask, rejected, k_record[0], k_record[1], v_record[0], v_record[1])
+    _check_f32(q, k_record[0], k_record[1], v_record[0], v_record[1])
+    if rejected.dtype != torch.int32 or rejected.numel() != 1:
+        raise TypeError("decode_attention_codes: rejected must be one int32")
+    if q.dim() != 4 or q.shape[2] != 1 or not q.is_contiguous() or k.dim() != 4:
+        return None
+    b, h, _, d = q.shape
+    s = k.shape[2]
+    k_cap, v_cap = _kv_cap(k, b, h, s, d, torch.uint8), _kv_cap(v, b, h, s, d, torch.uint8)
+    if k_cap is None or v_cap is None:
+        return None
+    if mask is not None and not (mask.dtype == torch.float32 and tuple(mask.shape) == (b, 1, 1, s) and mask.is_contiguous()):
+        return None
+    out = torch.empty((b, 1, h * d), dtype=torch.float32, device=q.device)
+    probs = torch.empty((b, h, 1, s), dtype=torch.float32, device=q.device) if want_probs else None
+    rc = lib.osq_decode_attention_codes(q.data_ptr(), k.data_ptr(), v.data_ptr(), _hip.ptr(mask), out.data_ptr(),
+                                        _hip.ptr(probs), b, h, d, s, k_cap, v_cap,
+                                        k_record[0].data_ptr(), k_record[1].data_ptr(), int(k_record[2]),
+                                        v_record[0].data_ptr(), v_record[1].data_ptr(), int(v_record[2]), rejected.data_ptr(),
+                                        *_quant_group(probs_quant), *_quant_group(ctx_quant), _hip.raw_stream(q.device))
+    if rc == _hip.ERR_UNSUPPORTED:
+        return None
+    _hip.check(rc, "decode_attention_codes")
+    return (out, probs) if want_probs else out
+
+
+def dequantize_kv_codes(codes, record, out=None):
+    """The fp32 buffer of a coded cache buffer: ``codes`` a contiguous uint8 [B, h, cap, d] tensor, ``record`` its
+    (scale_eff, zp_eff, quant_min); the result has the same geometry and, position by position, the words the fp32 cache
+    holds (osq_dequantize_codes with one channel, reading the record)."""
+    scale_eff, zp_eff, quant_min = record
+    return dequantize_codes(Codes(codes, scale_eff, zp_eff, int(quant_min), int(quant_min) + 255, 8, tuple(codes.shape), -1), out)

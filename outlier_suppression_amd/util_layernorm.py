@@ -37,6 +37,11 @@ quantizer (quant_bart.py:232-268) -- as ONE launch for the step's single query t
 csrc/decode_attention.hip).  Its dot products are fp32 sums in the kernel's own fixed order, not rocBLAS's, and its exp is
 ocml's: the result is tolerance-equal to the eager sequence, not bit-equal, hence off by default.
 ``outlier_suppression_amd.set_fast_decode_attention(True)`` / ``OSQ_FAST_DECODE_ATTENTION=1`` turn it on.
+
+``CACHE_CODES`` (default OFF) is no fusion but a storage format: new KV caches (model/quant_bart.py, QuantizedBartCache) hold
+integer codes, one byte per element, written by ``ops.fake_quant_kv_append_codes`` and read as they are by
+``ops.decode_attention_codes`` (csrc/kv_codes.hip, csrc/decode_attention.hip); the words computed are those of the fp32 cache.
+``outlier_suppression_amd.set_cache_codes(True)`` / ``OSQ_CACHE_CODES=1`` turn it on; it is independent of the switch above.
 """
 import torch
 import torch.nn.functional as F
@@ -52,6 +57,7 @@ FUSE_QKV = True          # the query / key / value head-split sites of a self-at
 FUSE_SOFTMAX = False     # the attention-probabilities site as one launch (tolerance-equal; set_fast_softmax / OSQ_FAST_SOFTMAX=1)
 FUSE_DECODE_ATTENTION = False   # a cached decoding step's attention after the append as one launch (tolerance-equal; set_fast_decode_attention / OSQ_FAST_DECODE_ATTENTION=1)
 FUSE_KV_APPEND = True    # incremental decoding: a step's q / k / v sites + KV-cache append (+ beam reorder) as one launch (bit-identical)
+CACHE_CODES = False      # incremental decoding: new KV caches hold integer codes, one byte per element (same words read back; set_cache_codes / OSQ_CACHE_CODES=1)
 
 
 def _fused_site(mod, x, hidden, gamma, weight, bias, eps, observation_mask):
@@ -280,6 +286,32 @@ def kv_append_fake_quant(sites, heads):
     return ops.fake_quant_kv_append(table, heads)
 
 
+def kv_site_params(q, x):
+    """(scale, zero_point, quant_min, quant_max, mode, grad_factor) of quantizer q for the [B, t, h*d] projection x as a site
+    of a KV-append launch, or None when kv_append_fake_quant would not take the site (the quantizer not in its plain
+    quantising state, x not dense and 16-byte aligned, the one-launch append switched off)."""
+    if not (FUSE_KV_APPEND and _plain_quantizing(q, x) and x.dim() == 3 and x.is_contiguous() and x.data_ptr() % 16 == 0):
+        return None
+    mode = q.param_mode
+    if isinstance(q, _LearnableFakeQuantize):
+        mode |= ops.PARAM_SANITIZE
+    return (q.scale, q.zero_point, q.quant_min, q.quant_max, mode, q._grad_factor(x) if q.param_mode != ops.PARAM_FIXED else 1.0)
+
+
+def kv_append_codes_fake_quant(sites, heads, rejected):
+    """kv_append_fake_quant for a cache that holds integer codes (ops.fake_quant_kv_append_codes): each site
+    ``(quantizer, params, x, y, offset, src, src_rows, record, write_record)`` with ``params`` what kv_site_params gave for
+    it; record None is an fp32 site as there, record ``(scale_eff, zp_eff)`` a coded one whose y / src are uint8 buffers.
+    Dequantised with the record, the bytes are the words kv_append_fake_quant writes.  Returns the list of y, or None
+    (nothing launched)."""
+    table = []
+    for q, params, x, y, offset, src, rows, record, write_record in sites:
+        if params[4] & ops.PARAM_SANITIZE:
+            q._touch_qparams()
+        table.append((x, y, offset, params, src, rows, record, write_record))
+    return ops.fake_quant_kv_append_codes(table, heads, rejected)
+
+
 class _Numel:
     """Stands for a tensor of which a quantizer's grad factor needs the element count only."""
 
@@ -290,14 +322,15 @@ class _Numel:
         return self.n
 
 
-def decode_attention_fake_quant(probs_quantizer, ctx_quantizer, q, k, v, mask=None, dropout=None):
+def decode_attention_fake_quant(probs_quantizer, ctx_quantizer, q, k, v, mask=None, dropout=None, codes=None):
     """Incremental decoding: what follows the q / k / v + append launch of a step's attention block
     (QuantizedBartAttention._attend: bmm, mask add, softmax, ``probs_quantizer``, bmm, merge heads, ``ctx_quantizer``) as ONE
     launch (ops.decode_attention_fake_quant), for q = [B, h, 1, d] (one query token) and k / v = [B, h, S, d] views of the
     cache buffers or the cross-attention tensors.  Only with FUSE_DECODE_ATTENTION on, autograd off, dropout inactive and
     each quantizer either None or in its plain quantising state (the LSQ / LSQ+ parameter repair rides in the launch as in
-    the other one-launch sites).  Returns the [B, 1, h*d] context, or None (nothing launched): the caller runs the eager
-    sequence."""
+    the other one-launch sites).  ``codes``: None, or ``(k_record, v_record, rejected)`` of a coded cache -- k / v are then
+    its uint8 code tensors (ops.decode_attention_codes: the same words as on the dequantised tensors).  Returns the
+    [B, 1, h*d] context, or None (nothing launched): the caller runs the eager sequence."""
     if not FUSE_DECODE_ATTENTION or torch.is_grad_enabled() or _dropout_active(dropout):
         return None
     if q.dim() != 4 or q.shape[2] != 1 or k.dim() != 4:
@@ -316,6 +349,8 @@ def decode_attention_fake_quant(probs_quantizer, ctx_quantizer, q, k, v, mask=No
             quantizer._touch_qparams()
         params.append((quantizer.scale.data, quantizer.zero_point.data, quantizer.quant_min, quantizer.quant_max, mode,
                        quantizer._grad_factor(_Numel(numel)) if quantizer.param_mode != ops.PARAM_FIXED else 1.0))
+    if codes is not None:
+        return ops.decode_attention_codes(q, k, v, mask, params[0], params[1], *codes)
     return ops.decode_attention_fake_quant(q, k, v, mask, params[0], params[1])
 
 

@@ -8,9 +8,14 @@ search) at past length S = 1, 31, 62, median and spread of --reps runs, and the 
 --fast-decode-attention: the A/B is instead the one-launch attention of a decoding step (util_layernorm.
 FUSE_DECODE_ATTENTION, csrc/decode_attention.hip) off against on, the one-launch append on in both; with --profile-steps the
 profiled steps run with the switch on.
+--cache-codes: the A/B is the KV cache held as integer codes (util_layernorm.CACHE_CODES, csrc/kv_codes.hip) against the
+fp32 cache, the one-launch append and the one-launch attention on in both; the cache of a timed step is filled token by
+token, as generate() fills it (a first step of several tokens would demote the self-attention tensors of a coded cache),
+and ``cache.nbytes()`` is reported both ways; with --profile-steps the profiled steps run with codes on.
 
     python tools/decode_bench.py [--reps 7] [--out profiles/decode_step_ab.txt]
     python tools/decode_bench.py --fast-decode-attention [--out profiles/decode_attention_ab.txt]
+    python tools/decode_bench.py --cache-codes [--out profiles/kv_codes_ab.txt]
 """
 import argparse
 import copy
@@ -50,11 +55,14 @@ def build(batch, src_len, layers):
     return q, ids, mask
 
 
-def step_times(q, ids, mask, beams, past, reps, fused, attention=False):
-    """Median / min / max (ms) of one decoder step at past length `past` with a pending beam reorder."""
+def step_times(q, ids, mask, beams, past, reps, fused, attention=False, codes=None):
+    """Median / min / max (ms) of one decoder step at past length `past` with a pending beam reorder, and the bytes the
+    cache holds.  ``codes`` None: the cache filled by one call of `past` tokens; False / True: an fp32 / coded cache filled
+    token by token."""
     from outlier_suppression_amd import util_layernorm as UL
     UL.FUSE_KV_APPEND = fused
     UL.FUSE_DECODE_ATTENTION = attention
+    UL.CACHE_CODES = bool(codes)
     dev = ids.device
     bb = ids.shape[0] * beams
     try:
@@ -62,7 +70,14 @@ def step_times(q, ids, mask, beams, past, reps, fused, attention=False):
             enc = q.get_encoder()(ids, attention_mask=mask).repeat_interleave(beams, 0)
             m = mask.repeat_interleave(beams, 0)
             tok = torch.randint(3, 50265, (bb, past + 1), device=dev)
-            _, cache, _ = q(attention_mask=m, decoder_input_ids=tok[:, :past], encoder_outputs=(enc,), use_cache=True)
+            if codes is None:
+                _, cache, _ = q(attention_mask=m, decoder_input_ids=tok[:, :past], encoder_outputs=(enc,), use_cache=True)
+            else:
+                cache = None
+                for t in range(past):
+                    _, cache, _ = q(attention_mask=m, decoder_input_ids=tok[:, t:t + 1], encoder_outputs=(enc,),
+                                    past_key_values=cache, use_cache=True)
+                assert bool(cache.coded()) is codes and not cache.demoted()
             perm = torch.randperm(bb, device=dev)
             lens = list(cache._len)
             times = []
@@ -76,23 +91,28 @@ def step_times(q, ids, mask, beams, past, reps, fused, attention=False):
                 torch.cuda.synchronize()
                 if r >= 2:
                     times.append((time.perf_counter() - t0) * 1e3)
+            held = cache.nbytes()
+            if codes:
+                assert not cache.demoted() and cache.rejected() == 0
     finally:
         UL.FUSE_KV_APPEND = True
         UL.FUSE_DECODE_ATTENTION = False
+        UL.CACHE_CODES = False
     times.sort()
-    return times[len(times) // 2], times[0], times[-1]
+    return times[len(times) // 2], times[0], times[-1], held
 
 
-def generate_time(q, ids, mask, fused, attention=False):
+def generate_time(q, ids, mask, fused, attention=False, codes=None):
     from outlier_suppression_amd import util_layernorm as UL
     UL.FUSE_KV_APPEND = fused
     UL.FUSE_DECODE_ATTENTION = attention
+    codes = bool(codes)
     try:
         with torch.no_grad():
-            q.generate(ids[:2], attention_mask=mask[:2], max_length=4, num_beams=6, min_length=4)
+            q.generate(ids[:2], attention_mask=mask[:2], max_length=4, num_beams=6, min_length=4, cache_codes=codes)
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-            out = q.generate(ids, attention_mask=mask, max_length=62, num_beams=6, min_length=62)
+            out = q.generate(ids, attention_mask=mask, max_length=62, num_beams=6, min_length=62, cache_codes=codes)
             torch.cuda.synchronize()
             return time.perf_counter() - t0, tuple(out.shape)
     finally:
@@ -109,6 +129,7 @@ def main():
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--profile-steps", type=int, default=0)
     ap.add_argument("--fast-decode-attention", action="store_true")
+    ap.add_argument("--cache-codes", action="store_true")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     q, ids, mask = build(args.batch, args.src, args.layers)
@@ -117,25 +138,32 @@ def main():
         UL.FUSE_DECODE_ATTENTION = args.fast_decode_attention
         with torch.no_grad():
             q.generate(ids, attention_mask=mask, max_length=args.profile_steps + 1, num_beams=args.beams,
-                       min_length=args.profile_steps + 1)
+                       min_length=args.profile_steps + 1, cache_codes=args.cache_codes)
         torch.cuda.synchronize()
         return
     lines = [f"decoder step, BART-large shape (random init, {args.layers}+{args.layers} layers), W6A6 LSQ+ plain quantising, "
              f"batch {args.batch} x {args.beams} beams, source {args.src}; a beam reorder pending before every step; "
              f"{args.reps} runs each, ms: median [min, max]"]
-    # (label, FUSE_KV_APPEND, FUSE_DECODE_ATTENTION) of the two forms compared
-    forms = ([("attention one-launch", True, True), ("attention eager", True, False)] if args.fast_decode_attention
-             else [("one-launch", True, False), ("eager", False, False)])
-    if args.fast_decode_attention:
+    # (label, FUSE_KV_APPEND, FUSE_DECODE_ATTENTION, cache codes) of the two forms compared
+    if args.cache_codes:
+        forms = [("cache codes", True, True, True), ("cache fp32", True, True, False)]
+        lines[0] += "; the q / k / v + append launch and the one-launch attention on in both; caches filled token by token"
+    elif args.fast_decode_attention:
+        forms = [("attention one-launch", True, True, None), ("attention eager", True, False, None)]
         lines[0] += "; the q / k / v + append launch on in both"
+    else:
+        forms = [("one-launch", True, False, None), ("eager", False, False, None)]
     for past in (1, 31, 62):
-        row = []
-        for label, fused, attention in forms:
-            med, lo, hi = step_times(q, ids, mask, args.beams, past, args.reps, fused, attention)
+        row, held = [], []
+        for label, fused, attention, codes in forms:
+            med, lo, hi, nbytes = step_times(q, ids, mask, args.beams, past, args.reps, fused, attention, codes)
             row.append(f"{label} {med:.3f} [{lo:.3f}, {hi:.3f}]")
+            held.append(f"{label} {nbytes}")
         lines.append(f"S = {past:2d}: " + "   ".join(row))
-    for label, fused, attention in forms:
-        secs, shape = generate_time(q, ids, mask, fused, attention)
+        if args.cache_codes:
+            lines.append(f"        cache.nbytes() after the step: " + "   ".join(held))
+    for label, fused, attention, codes in forms:
+        secs, shape = generate_time(q, ids, mask, fused, attention, codes)
         lines.append(f"generate(max_length=62, num_beams=6, min_length=62) {label}: {secs:.2f} s, output {shape}")
     text = "\n".join(lines)
     print(text)
