@@ -39,7 +39,9 @@ typedef void* osq_stream;
  * 10: osq_observe_flat / _channels, osq_token_minmax, osq_observe_tokens and osq_fake_quant_per_channel take `dtype` first;
  *     their separate 16-bit twins are gone.
  *     Added within 10 (no existing signature changed): osq_quantize_codes, osq_dequantize_codes, osq_dequantize_codes_multi,
- *     osq_decode_attention_fake_quant, osq_fake_quant_kv_append_codes, osq_decode_attention_codes. */
+ *     osq_decode_attention_fake_quant, osq_fake_quant_kv_append_codes, osq_decode_attention_codes,
+ *     osq_fake_quant_kv_append_at, osq_fake_quant_kv_append_codes_at, osq_decode_attention_fake_quant_at,
+ *     osq_decode_attention_codes_at. */
 #define OSQ_ABI_VERSION 10
 
 typedef enum osq_status {
@@ -238,6 +240,18 @@ typedef struct osq_kv_append_site {
 } osq_kv_append_site;
 int osq_fake_quant_kv_append(const osq_kv_append_site* sites, int n_sites, int64_t batch, int64_t heads,
                              int64_t head_dim, osq_stream stream);
+
+/* osq_fake_quant_kv_append with the position read by the launch, so that a captured graph of a decoding step can be
+ * replayed at every position.  pos: one device int32.  site_at: n_sites host flags; site i with site_at[i] != 0 appends at
+ * [*pos, *pos + tokens) and copies [0, *pos) from src through src_rows (its `offset` field is not read); the other sites
+ * keep their own offset (a query site: 0).  src set means "copy the prefix", whatever *pos turns out to be (0: nothing);
+ * src == y without a row index still copies nothing.  The grid is sized from cap.  For every position the destination
+ * holds, byte for byte, what osq_fake_quant_kv_append writes when called with offset = that position.
+ * A position that fits no flagged site -- *pos < 0, *pos + tokens > cap, or, where a prefix is copied, *pos > src_cap --
+ * is refused by the launch itself: no address is formed from it and NO site writes anything (the parameter repair of
+ * OSQ_PARAM_SANITIZE included).  OSQ_ERR_UNSUPPORTED as for the static form, decided for the longest prefix cap admits. */
+int osq_fake_quant_kv_append_at(const osq_kv_append_site* sites, int n_sites, int64_t batch, int64_t heads,
+                                int64_t head_dim, const int32_t* pos, const int32_t* site_at, osq_stream stream);
 
 /* util_quant.py:18-26 fake_quantize_per_channel_affine (and the per-channel learnable
  * forwards :37-45, :58-67).  x is contiguous `dtype` data viewed as [outer, channels, inner]
@@ -568,6 +582,15 @@ typedef struct osq_kv_codes_site {
 int osq_fake_quant_kv_append_codes(const osq_kv_codes_site* sites, int n_sites, int64_t batch, int64_t heads,
                                    int64_t head_dim, int32_t* rejected, osq_stream stream);
 
+/* osq_fake_quant_kv_append_codes with the position read by the launch: pos / site_at and the refusal as in
+ * osq_fake_quant_kv_append_at.  Whether a coded prefix is copied 16 or 4 bytes per lane is decided by the launch for the
+ * position it reads (the bytes written are the same).  A refused position writes nothing -- no record either -- and, when
+ * any site is coded, adds exactly 1 to `rejected`.  For every other position the destinations, the records and `rejected`
+ * are byte-equal to osq_fake_quant_kv_append_codes called with offset = that position. */
+int osq_fake_quant_kv_append_codes_at(const osq_kv_codes_site* sites, int n_sites, int64_t batch, int64_t heads,
+                                      int64_t head_dim, int32_t* rejected, const int32_t* pos, const int32_t* site_at,
+                                      osq_stream stream);
+
 /* ------------------------------------------------------------------ MSEFast (observer.py:412-567) */
 
 /* one_side: 0 = 'no', 1 = 'pos', 2 = 'neg' (observer.py:528-529, decided once by the caller on
@@ -832,6 +855,40 @@ int osq_decode_attention_codes(const float* q, const uint8_t* k, const uint8_t* 
                                float* ctx_scale, void* ctx_zero_point, int ctx_zp_type, int ctx_mode,
                                float ctx_grad_factor, int ctx_quant_min, int ctx_quant_max,
                                osq_stream stream);
+
+/* The two entry points above with the length read by the launch: kv_len = *kv_len_dev + kv_len_add (kv_len_dev one device
+ * int32; self-attention passes the cache's position word and 1, the step's own token), so that one captured graph serves
+ * every step.  kv_max (1..4096, <= k_cap and v_cap) is the largest length the launch may meet; the host checks go by it.
+ * mask (nullable) is [batch, 1, 1, >= kv_max] with rows mask_stride floats apart, probs_out (nullable)
+ * [batch, heads, 1, >= kv_max] with rows probs_stride floats apart: columns [0, kv_len) are read / written, so buffers
+ * laid out for kv_max serve every step.  probs_grad_table: NULL (probs_grad_factor holds), or kv_max + 1 device floats,
+ * entry n the grad factor of the probabilities quantizer at kv_len == n as the HOST computed it (the launch reads the
+ * word, it does not re-derive it; entry 0 is not read).  For every kv_len in [1, kv_max], out and probs_out[..., :kv_len]
+ * are word-equal to the static entry point called with that kv_len; the summation order is fixed by (head_dim, kv_len)
+ * alone.  A kv_len outside [1, kv_max]: every word of out is NaN, and q, k, v, mask, the table and the parameters are not
+ * read.  OSQ_ERR_UNSUPPORTED as for the static forms, with kv_max in the place of kv_len. */
+int osq_decode_attention_fake_quant_at(const float* q, const float* k, const float* v, const float* mask,
+                                       int64_t mask_stride, float* out, float* probs_out, int64_t probs_stride,
+                                       int64_t batch, int64_t heads, int64_t head_dim,
+                                       const int32_t* kv_len_dev, int64_t kv_len_add, int64_t kv_max,
+                                       int64_t k_cap, int64_t v_cap, const float* probs_grad_table,
+                                       float* probs_scale, void* probs_zero_point, int probs_zp_type, int probs_mode,
+                                       float probs_grad_factor, int probs_quant_min, int probs_quant_max,
+                                       float* ctx_scale, void* ctx_zero_point, int ctx_zp_type, int ctx_mode,
+                                       float ctx_grad_factor, int ctx_quant_min, int ctx_quant_max,
+                                       osq_stream stream);
+int osq_decode_attention_codes_at(const float* q, const uint8_t* k, const uint8_t* v, const float* mask,
+                                  int64_t mask_stride, float* out, float* probs_out, int64_t probs_stride,
+                                  int64_t batch, int64_t heads, int64_t head_dim,
+                                  const int32_t* kv_len_dev, int64_t kv_len_add, int64_t kv_max,
+                                  int64_t k_cap, int64_t v_cap, const float* probs_grad_table,
+                                  const float* k_scale_eff, const float* k_zp_eff, int k_quant_min,
+                                  const float* v_scale_eff, const float* v_zp_eff, int v_quant_min, const int32_t* rejected,
+                                  float* probs_scale, void* probs_zero_point, int probs_zp_type, int probs_mode,
+                                  float probs_grad_factor, int probs_quant_min, int probs_quant_max,
+                                  float* ctx_scale, void* ctx_zero_point, int ctx_zp_type, int ctx_mode,
+                                  float ctx_grad_factor, int ctx_quant_min, int ctx_quant_max,
+                                  osq_stream stream);
 
 /* ------------------------------------------------------------------ bf16 / fp16 only (lowp.hip) */
 

@@ -76,6 +76,21 @@ def set_cache_codes(on=True):
     util_layernorm.CACHE_CODES = bool(on)
 
 
+def set_graph_decode(on=True):
+    """generate() captures a cached decoding step into a hipGraph and replays it instead of issuing its launches one by one
+    (util_layernorm.GRAPH_DECODE; model/graph_decode.py; default OFF).  A captured step uses the one-launch attention
+    whatever set_fast_decode_attention says; a step that cannot be captured is decoded as before.  OSQ_GRAPH_DECODE=1 turns
+    it on at load; ``generate(..., graph=True)`` asks for one call."""
+    from . import util_layernorm
+    util_layernorm.GRAPH_DECODE = bool(on)
+
+
+def graph_decode_from_environment(environ=None):
+    """What OSQ_GRAPH_DECODE asks for: unset, empty or "0" -> False, anything else -> True."""
+    import os
+    return (os.environ if environ is None else environ).get("OSQ_GRAPH_DECODE", "") not in ("", "0")
+
+
 def cache_codes_from_environment(environ=None):
     """What OSQ_CACHE_CODES asks for: unset, empty or "0" -> False, anything else -> True."""
     import os
@@ -86,7 +101,8 @@ def reset_tier(_lib=None):
     """The package's default tier, as the environment states it (applied when the library is first loaded): MSEFast sums in
     the reference's one-thread order, the backward's sums order-free; OSQ_STRICT=1 / 0 force both; OSQ_FAST=0 / 1 the
     one-launch LayerNorm site; OSQ_FAST_SOFTMAX=1 the one-launch attention-probabilities site and OSQ_FAST_DECODE_ATTENTION=1
-    the one-launch attention of a cached decoding step (unset: off); OSQ_CACHE_CODES=1 KV caches as integer codes (unset: off)."""
+    the one-launch attention of a cached decoding step (unset: off); OSQ_CACHE_CODES=1 KV caches as integer codes (unset: off);
+    OSQ_GRAPH_DECODE=1 generate() replays a captured decoding step (unset: off)."""
     import os
     width = int(os.environ.get("OSQ_STRICT_SIMD", "8"))
     strict = os.environ.get("OSQ_STRICT", "")
@@ -99,6 +115,7 @@ def reset_tier(_lib=None):
     set_fast_softmax(os.environ.get("OSQ_FAST_SOFTMAX", "") not in ("", "0"))
     set_fast_decode_attention(os.environ.get("OSQ_FAST_DECODE_ATTENTION", "") not in ("", "0"))
     set_cache_codes(cache_codes_from_environment())
+    set_graph_decode(graph_decode_from_environment())
 
 
 _apply_environment = reset_tier

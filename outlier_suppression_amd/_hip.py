@@ -101,6 +101,9 @@ SIGNATURES = {
     "osq_fake_quant_headsplit_multi": (_I, [ctypes.POINTER(HeadSplitSite), _I, _L, _L, _L, _L, _P]),
     "osq_fake_quant_kv_append": (_I, [ctypes.POINTER(KvAppendSite), _I, _L, _L, _L, _P]),
     "osq_fake_quant_kv_append_codes": (_I, [ctypes.POINTER(KvCodesSite), _I, _L, _L, _L, _P, _P]),
+    "osq_fake_quant_kv_append_at": (_I, [ctypes.POINTER(KvAppendSite), _I, _L, _L, _L, _P, ctypes.POINTER(ctypes.c_int32), _P]),
+    "osq_fake_quant_kv_append_codes_at": (_I, [ctypes.POINTER(KvCodesSite), _I, _L, _L, _L, _P, _P,
+                                               ctypes.POINTER(ctypes.c_int32), _P]),
     "osq_fake_quant_per_channel": (_I, [_I, _P, _P, _P, _L, _L, _L, _P, _P, _I, _I, _F, _I, _I, _P]),
     "osq_fake_quant_weights_multi": (_I, [_P, _P, _I, _L, _P]),
     "osq_quantize_codes": (_I, [_I, _P, _P, _L, _L, _L, _P, _P, _I, _I, _F, _I, _I, _I, _P, _P, _P, _P]),
@@ -163,6 +166,11 @@ SIGNATURES = {
                                              _P, _P, _I, _I, _F, _I, _I, _P, _P, _I, _I, _F, _I, _I, _P]),
     "osq_decode_attention_codes": (_I, [_P, _P, _P, _P, _P, _P, _L, _L, _L, _L, _L, _L, _P, _P, _I, _P, _P, _I, _P,
                                         _P, _P, _I, _I, _F, _I, _I, _P, _P, _I, _I, _F, _I, _I, _P]),
+    "osq_decode_attention_fake_quant_at": (_I, [_P, _P, _P, _P, _L, _P, _P, _L, _L, _L, _L, _P, _L, _L, _L, _L, _P,
+                                                _P, _P, _I, _I, _F, _I, _I, _P, _P, _I, _I, _F, _I, _I, _P]),
+    "osq_decode_attention_codes_at": (_I, [_P, _P, _P, _P, _L, _P, _P, _L, _L, _L, _L, _P, _L, _L, _L, _L, _P,
+                                           _P, _P, _I, _P, _P, _I, _P,
+                                           _P, _P, _I, _I, _F, _I, _I, _P, _P, _I, _I, _F, _I, _I, _P]),
     "osq_fake_quant_chain_lowp": (_I, [_I, _P, _P, _L, _P, _P, _I, _I, _I, _P]),
     "osq_fake_quant_chain_backward_lowp": (_I, [_I, _P, _P, _P, _L, _P, _P, _I, _I, _I, _P]),
     "osq_fake_quant_per_tensor_widen": (_I, [_I, _P, _P, _L, _P, _P, _I, _I, _F, _I, _I, _P]),

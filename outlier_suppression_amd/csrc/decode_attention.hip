@@ -34,6 +34,12 @@
 //   the softmax  denominator: thread t adds exps t, t + 256, ... in order, wave_sum_f32, then (w0 + w1) + (w2 + w3);
 //   a context    element: lane (wave w, row r) adds its positions (4 i + w) R + r for i = 0, 1, ... in order, an xor
 //                butterfly over the wave's R row groups (strides LPR, 2 LPR, ... 32), then ((w0 + w1) + w2) + w3.
+//
+// The _at forms (osq_decode_attention_fake_quant_at / _codes_at) are the same kernel with the length read by the launch:
+// kv_len = *kv_len_dev + kv_len_add, one scalar read per workgroup before anything else, so that a captured graph of a
+// decoding step serves every position.  What the host derived from the length either holds for every length up to kv_max
+// (caps, row strides of mask and probs_out) or comes from device memory indexed by it (the probabilities quantizer's grad
+// factor: a table of the host's own words).  The trip loops do not change: n is an SGPR either way.
 #include <math.h>
 #include <hip/hip_runtime.h>
 #include "codes_device.h"
@@ -85,11 +91,15 @@ struct DecArgs {
     const float* q;            // [batch, heads, 1, head_dim] dense
     const void* k;             // [batch, heads, k_cap, head_dim] fp32 words or code bytes, positions [0, kv_len) read
     const void* v;             // [batch, heads, v_cap, head_dim]
-    const float* mask;         // nullable, [batch, 1, 1, kv_len] dense, additive
+    const float* mask;         // nullable, [batch, 1, 1, :] additive, rows mask_stride floats apart (static form: kv_len)
     float* out;                // [batch, 1, heads * head_dim] dense
-    float* probs_out;          // nullable, [batch, heads, 1, kv_len] dense
-    int64_t heads, k_cap, v_cap;
+    float* probs_out;          // nullable, [batch, heads, 1, :], rows probs_stride floats apart (static form: kv_len)
+    int64_t heads, k_cap, v_cap, mask_stride, probs_stride;
     int kv_len;
+    // the _at forms: kv_len = *kv_len_dev + kv_len_add, read by the launch; outside [1, kv_max] -> out is NaN, nothing read
+    const int32_t* kv_len_dev; // nullptr: the static forms, kv_len above
+    int kv_len_add, kv_max;
+    const float* grad_table;   // nullable: probs.grad_factor = grad_table[kv_len], the host's own words
     DecQuant probs, ctx;
     DecCode kc, vc;            // coded form only
     const int32_t* rejected;   // coded form only: the cache's counter; non-zero: the cache holds elements without a code
@@ -136,14 +146,24 @@ __global__ __launch_bounds__(kDecThreads) void decode_attention_fq_kernel(DecArg
     const int lane = threadIdx.x & (OSQ_WAVE - 1), w = threadIdx.x / OSQ_WAVE;
     const int r = lane / LPR, c = lane % LPR;
     const int64_t bh = blockIdx.x;
-    const int n = a.kv_len;
+    int n = a.kv_len;
+    DecQuant probs = a.probs;
+    if (a.kv_len_dev) {                            // workgroup-uniform: the length is a device word, read once into an SGPR
+        n = __builtin_amdgcn_readfirstlane(*a.kv_len_dev) + a.kv_len_add;
+        if (n < 1 || n > a.kv_max) {               // a length no address may be formed from
+            const float nan = __builtin_nanf("");
+            if (threadIdx.x < LPR) reinterpret_cast<float4*>(a.out)[bh * LPR + c] = make_float4(nan, nan, nan, nan);
+            return;
+        }
+        if (a.grad_table) probs.grad_factor = a.grad_table[n];
+    }
     const int trips = (n + kTrip - 1) / kTrip;
-    const QParams pq = dec_params(a.probs), cq = dec_params(a.ctx);      // first: the parameter repair rides here
+    const QParams pq = dec_params(probs), cq = dec_params(a.ctx);      // first: the parameter repair rides here
 
     if (a.rejected && *a.rejected != 0) {          // workgroup-uniform: a cache with an uncodable element never yields numbers
         const float nan = __builtin_nanf("");
         if (a.probs_out)
-            for (int j = threadIdx.x; j < n; j += kDecThreads) a.probs_out[bh * n + j] = nan;
+            for (int j = threadIdx.x; j < n; j += kDecThreads) a.probs_out[bh * a.probs_stride + j] = nan;
         if (threadIdx.x < LPR) reinterpret_cast<float4*>(a.out)[bh * LPR + c] = make_float4(nan, nan, nan, nan);
         return;
     }
@@ -152,7 +172,7 @@ __global__ __launch_bounds__(kDecThreads) void decode_attention_fq_kernel(DecArg
     // ---- scores
     const float4 q4 = reinterpret_cast<const float4*>(a.q)[bh * LPR + c];
     const int64_t kb = bh * a.k_cap * LPR + c;           // in words of four elements
-    const float* mrow = a.mask ? a.mask + (bh / a.heads) * n : nullptr;
+    const float* mrow = a.mask ? a.mask + (bh / a.heads) * a.mask_stride : nullptr;
     for (int t0 = 0; t0 < trips; t0 += kTripsInFlight) {
         typename KV::Word kw[kTripsInFlight];
 #pragma unroll
@@ -191,9 +211,9 @@ __global__ __launch_bounds__(kDecThreads) void decode_attention_fq_kernel(DecArg
     if (lane == 0) s_red[1][w] = sum;
     __syncthreads();
     const float rcp = 1.0f / ((s_red[1][0] + s_red[1][1]) + (s_red[1][2] + s_red[1][3]));
-    float* prow = a.probs_out ? a.probs_out + bh * n : nullptr;
+    float* prow = a.probs_out ? a.probs_out + bh * a.probs_stride : nullptr;
     for (int j = threadIdx.x; j < n; j += kDecThreads) {
-        const float p = dec_fq(s_p[j] * rcp, a.probs, pq);
+        const float p = dec_fq(s_p[j] * rcp, probs, pq);
         s_p[j] = p;
         if (prow) prow[j] = p;
     }
@@ -244,12 +264,21 @@ static bool dec_mode_ok(int mode) {
     return (mode & ~(OSQ_PARAM_MODE_MASK | OSQ_PARAM_SANITIZE)) == 0 && (mode & OSQ_PARAM_MODE_MASK) <= OSQ_PARAM_LSQPLUS;
 }
 
-// checks and launch shared by the two storage formats; kv_align: what K and V must be aligned to
+// What the _at forms add: the device word of the length, the constant added to it, and the row strides of mask / probs_out.
+struct DecAt {
+    const int32_t* kv_len_dev;
+    int64_t kv_len_add, mask_stride, probs_stride;
+    const float* grad_table;
+};
+
+// checks and launch shared by the two storage formats; kv_align: what K and V must be aligned to.  at == nullptr: the static
+// forms.  Otherwise kv_len is kv_max, the largest length the launch may meet: every host check holds for all lengths up to it.
 template <typename KV>
 static int launch_decode_attention(const char* what, const float* q, const void* k, const void* v, const float* mask, float* out,
                                    float* probs_out, int64_t batch, int64_t heads, int64_t head_dim, int64_t kv_len,
                                    int64_t k_cap, int64_t v_cap, const DecCode& kc, const DecCode& vc, const int32_t* rejected,
-                                   const DecQuant& probs, const DecQuant& ctx, uintptr_t kv_align, osq_stream stream) {
+                                   const DecQuant& probs, const DecQuant& ctx, uintptr_t kv_align, osq_stream stream,
+                                   const DecAt* at = nullptr) {
     OSQ_REQUIRE(batch >= 0 && heads >= 0 && head_dim > 0 && batch * heads <= INT32_MAX, "decode_attention: bad shape");
     OSQ_REQUIRE(!probs.scale || probs.zero_point, "decode_attention: probs scale without zero_point");
     OSQ_REQUIRE(!ctx.scale || ctx.zero_point, "decode_attention: ctx scale without zero_point");
@@ -259,11 +288,19 @@ static int launch_decode_attention(const char* what, const float* q, const void*
     const int64_t lpr = head_dim / 4;
     if (head_dim % 4 || lpr > OSQ_WAVE || (lpr & (lpr - 1))) return OSQ_ERR_UNSUPPORTED;
     OSQ_REQUIRE(k_cap >= kv_len && v_cap >= kv_len, "decode_attention: cap below kv_len");
+    if (at) {
+        OSQ_REQUIRE(at->kv_len_dev, "decode_attention: null kv_len word");
+        OSQ_REQUIRE(at->kv_len_add >= 0 && at->kv_len_add <= kDecMaxKv, "decode_attention: bad kv_len_add");
+        OSQ_REQUIRE((!mask || at->mask_stride >= kv_len) && (!probs_out || at->probs_stride >= kv_len),
+                    "decode_attention: row stride below kv_max");
+    }
     if (batch * heads == 0) return OSQ_OK;
     OSQ_REQUIRE(q && k && v && out, "decode_attention: null tensor");
     if (!aligned16(q) || !aligned16(out) || !aligned16(mask) || !aligned16(probs_out)) return OSQ_ERR_UNSUPPORTED;
     if ((reinterpret_cast<uintptr_t>(k) | reinterpret_cast<uintptr_t>(v)) & (kv_align - 1u)) return OSQ_ERR_UNSUPPORTED;
-    DecArgs a{q, k, v, mask, out, probs_out, heads, k_cap, v_cap, static_cast<int>(kv_len), probs, ctx, kc, vc, rejected};
+    DecArgs a{q, k, v, mask, out, probs_out, heads, k_cap, v_cap, at ? at->mask_stride : kv_len, at ? at->probs_stride : kv_len,
+              static_cast<int>(kv_len), at ? at->kv_len_dev : nullptr, at ? static_cast<int>(at->kv_len_add) : 0,
+              static_cast<int>(kv_len), at ? at->grad_table : nullptr, probs, ctx, kc, vc, rejected};
     const dim3 grid(static_cast<unsigned>(batch * heads));
     hipStream_t st = static_cast<hipStream_t>(stream);
 #define OSQ_DEC(LPR) hipLaunchKernelGGL((decode_attention_fq_kernel<LPR, KV>), grid, dim3(kDecThreads), 0, st, a)
@@ -318,4 +355,42 @@ extern "C" int osq_decode_attention_codes(const float* q, const uint8_t* k, cons
         DecCode{k_scale_eff, k_zp_eff, k_quant_min}, DecCode{v_scale_eff, v_zp_eff, v_quant_min}, rejected,
         dec_quant(probs_scale, probs_zero_point, probs_zp_type, probs_mode, probs_grad_factor, probs_quant_min, probs_quant_max),
         dec_quant(ctx_scale, ctx_zero_point, ctx_zp_type, ctx_mode, ctx_grad_factor, ctx_quant_min, ctx_quant_max), 4u, stream);
+}
+
+extern "C" int osq_decode_attention_fake_quant_at(const float* q, const float* k, const float* v, const float* mask,
+                                                  int64_t mask_stride, float* out, float* probs_out, int64_t probs_stride,
+                                                  int64_t batch, int64_t heads, int64_t head_dim,
+                                                  const int32_t* kv_len_dev, int64_t kv_len_add, int64_t kv_max,
+                                                  int64_t k_cap, int64_t v_cap, const float* probs_grad_table,
+                                                  float* probs_scale, void* probs_zero_point, int probs_zp_type, int probs_mode,
+                                                  float probs_grad_factor, int probs_quant_min, int probs_quant_max,
+                                                  float* ctx_scale, void* ctx_zero_point, int ctx_zp_type, int ctx_mode,
+                                                  float ctx_grad_factor, int ctx_quant_min, int ctx_quant_max,
+                                                  osq_stream stream) {
+    const DecAt at{kv_len_dev, kv_len_add, mask_stride, probs_stride, probs_grad_table};
+    return launch_decode_attention<KvWords>(
+        "decode_attention_fake_quant_at", q, k, v, mask, out, probs_out, batch, heads, head_dim, kv_max, k_cap, v_cap, DecCode{},
+        DecCode{}, nullptr, dec_quant(probs_scale, probs_zero_point, probs_zp_type, probs_mode, probs_grad_factor, probs_quant_min, probs_quant_max),
+        dec_quant(ctx_scale, ctx_zero_point, ctx_zp_type, ctx_mode, ctx_grad_factor, ctx_quant_min, ctx_quant_max), 16u, stream, &at);
+}
+
+extern "C" int osq_decode_attention_codes_at(const float* q, const uint8_t* k, const uint8_t* v, const float* mask,
+                                             int64_t mask_stride, float* out, float* probs_out, int64_t probs_stride,
+                                             int64_t batch, int64_t heads, int64_t head_dim,
+                                             const int32_t* kv_len_dev, int64_t kv_len_add, int64_t kv_max,
+                                             int64_t k_cap, int64_t v_cap, const float* probs_grad_table,
+                                             const float* k_scale_eff, const float* k_zp_eff, int k_quant_min,
+                                             const float* v_scale_eff, const float* v_zp_eff, int v_quant_min, const int32_t* rejected,
+                                             float* probs_scale, void* probs_zero_point, int probs_zp_type, int probs_mode,
+                                             float probs_grad_factor, int probs_quant_min, int probs_quant_max,
+                                             float* ctx_scale, void* ctx_zero_point, int ctx_zp_type, int ctx_mode,
+                                             float ctx_grad_factor, int ctx_quant_min, int ctx_quant_max,
+                                             osq_stream stream) {
+    OSQ_REQUIRE(k_scale_eff && k_zp_eff && v_scale_eff && v_zp_eff && rejected, "decode_attention_codes_at: null record or rejected counter");
+    const DecAt at{kv_len_dev, kv_len_add, mask_stride, probs_stride, probs_grad_table};
+    return launch_decode_attention<KvCodes>(
+        "decode_attention_codes_at", q, k, v, mask, out, probs_out, batch, heads, head_dim, kv_max, k_cap, v_cap,
+        DecCode{k_scale_eff, k_zp_eff, k_quant_min}, DecCode{v_scale_eff, v_zp_eff, v_quant_min}, rejected,
+        dec_quant(probs_scale, probs_zero_point, probs_zp_type, probs_mode, probs_grad_factor, probs_quant_min, probs_quant_max),
+        dec_quant(ctx_scale, ctx_zero_point, ctx_zp_type, ctx_mode, ctx_grad_factor, ctx_quant_min, ctx_quant_max), 4u, stream, &at);
 }

@@ -302,6 +302,11 @@ struct KvAppendSites {
     unsigned int tokens[kHeadSplitSites], cap[kHeadSplitSites], offset[kHeadSplitSites];
     unsigned int src_cap[kHeadSplitSites], src_batch[kHeadSplitSites];
     unsigned int n_copy[kHeadSplitSites], n_total[kHeadSplitSites];   // float4s
+    // osq_fake_quant_kv_append_at: the offset of the sites flagged in `at` is the device word *pos, read by the launch; their
+    // n_copy is formed from it (src set: batch_heads * offset * dv) and n_total holds the appended float4s alone
+    const int32_t* pos;                      // nullptr: the static form, every offset above
+    int at[kHeadSplitSites];
+    unsigned int batch_heads;
 };
 
 __global__ __launch_bounds__(kThreads) void fq_kv_append_kernel(KvAppendSites s, unsigned int heads, unsigned int dv) {
@@ -309,9 +314,18 @@ __global__ __launch_bounds__(kThreads) void fq_kv_append_kernel(KvAppendSites s,
     const float4* __restrict__ x = s.x[site];
     float4* __restrict__ y = s.y[site];
     const float qmin = s.qmin[site], qmax = s.qmax[site];
+    const unsigned int cap = s.cap[site], tokens = s.tokens[site];
+    unsigned int offset = s.offset[site], n_copy = s.n_copy[site], n_total = s.n_total[site];
+    if (s.pos) {                                       // workgroup-uniform
+        const int pos = kv_append_position(s);
+        if (pos < 0) return;
+        if (s.at[site]) {
+            offset = static_cast<unsigned int>(pos);
+            n_copy = s.src[site] ? s.batch_heads * offset * dv : 0u;
+            n_total += n_copy;
+        }
+    }
     const QParams p = tensor_params(s.scale[site], s.zp[site], s.zp_type[site], s.mode[site], s.g[site], qmin, qmax);
-    const unsigned int cap = s.cap[site], offset = s.offset[site], tokens = s.tokens[site];
-    const unsigned int n_copy = s.n_copy[site], n_total = s.n_total[site];
     const unsigned int stride = gridDim.x * kThreads;
     const unsigned int head_row = heads * dv, past_row = offset * dv;
     for (unsigned int i = blockIdx.x * kThreads + threadIdx.x; i < n_total; i += stride) {
@@ -950,8 +964,10 @@ extern "C" int osq_fake_quant_headsplit_multi(const osq_headsplit_site* sites, i
     return check_launch("fake_quant_headsplit_multi");
 }
 
-extern "C" int osq_fake_quant_kv_append(const osq_kv_append_site* sites, int n_sites, int64_t batch, int64_t heads,
-                                        int64_t head_dim, osq_stream stream) {
+// pos == nullptr: the static form.  Otherwise site i with at[i] != 0 takes its offset from the device word *pos: whatever
+// the static form decides from the offset holds here for every offset the capacity admits, or is left to the launch.
+static int kv_append_launch(const osq_kv_append_site* sites, int n_sites, int64_t batch, int64_t heads, int64_t head_dim,
+                            const int32_t* pos, const int32_t* at, osq_stream stream) {
     OSQ_REQUIRE(sites && n_sites >= 1 && n_sites <= kHeadSplitSites, "fake_quant_kv_append: 1..4 sites");
     OSQ_REQUIRE(batch >= 0 && heads >= 1 && head_dim >= 1, "fake_quant_kv_append: bad geometry");
     if (head_dim % 4 != 0) return OSQ_ERR_UNSUPPORTED;
@@ -961,17 +977,19 @@ extern "C" int osq_fake_quant_kv_append(const osq_kv_append_site* sites, int n_s
     int64_t most = 0;
     for (int i = 0; i < n_sites; ++i) {
         const osq_kv_append_site& t = sites[i];
+        const bool from_pos = pos && at[i];
+        const int64_t offset = from_pos ? 0 : t.offset;
         OSQ_REQUIRE(t.scale && t.zero_point, "fake_quant_kv_append: null parameter pointer in a site");
-        OSQ_REQUIRE(t.tokens >= 0 && t.offset >= 0 && t.cap >= t.offset + t.tokens,
+        OSQ_REQUIRE(t.tokens >= 0 && offset >= 0 && t.cap >= offset + t.tokens,
                     "fake_quant_kv_append: need 0 <= offset, offset + tokens <= cap");
         const int64_t n_app = batch * t.tokens * heads * dv;
         OSQ_REQUIRE(n_app == 0 || (t.x && t.y), "fake_quant_kv_append: null tensor in a site");
-        const bool copy = t.src && t.offset > 0 && batch > 0 && !(t.src == t.y && !t.src_rows);
-        int64_t n_copy = 0;
+        const bool copy = t.src && (from_pos || offset > 0) && batch > 0 && !(t.src == t.y && !t.src_rows);
+        int64_t n_copy = 0;            // from_pos: the longest prefix the launch may copy; the grid and the 32-bit limit go by it
         if (copy) {
-            OSQ_REQUIRE(t.y && t.src_cap >= t.offset && t.src_batch >= 1, "fake_quant_kv_append: source smaller than offset");
+            OSQ_REQUIRE(t.y && t.src_cap >= offset && t.src_batch >= 1, "fake_quant_kv_append: source smaller than offset");
             OSQ_REQUIRE(t.src_rows || t.src_batch == batch, "fake_quant_kv_append: source batch differs, no row index");
-            n_copy = batch * heads * t.offset * dv;
+            n_copy = batch * heads * (from_pos ? std::min(t.cap - t.tokens, t.src_cap) : offset) * dv;
             // the copy must not read what the launch writes: the same buffer with a row index, or overlapping ranges
             const char *s0 = reinterpret_cast<const char*>(t.src), *s1 = s0 + t.src_batch * heads * t.src_cap * head_dim * 4;
             const char *y0 = reinterpret_cast<const char*>(t.y), *y1 = y0 + batch * heads * t.cap * head_dim * 4;
@@ -993,18 +1011,32 @@ extern "C" int osq_fake_quant_kv_append(const osq_kv_append_site* sites, int n_s
         ks.qmax[i] = static_cast<float>(t.quant_max);
         ks.tokens[i] = static_cast<unsigned int>(t.tokens);
         ks.cap[i] = static_cast<unsigned int>(t.cap);
-        ks.offset[i] = static_cast<unsigned int>(t.offset);
+        ks.offset[i] = static_cast<unsigned int>(offset);
         ks.src_cap[i] = copy ? static_cast<unsigned int>(t.src_cap) : 0u;
         ks.src_batch[i] = copy ? static_cast<unsigned int>(t.src_batch) : 0u;
-        ks.n_copy[i] = static_cast<unsigned int>(n_copy);
-        ks.n_total[i] = static_cast<unsigned int>(n_copy + n_app);
+        ks.n_copy[i] = from_pos ? 0u : static_cast<unsigned int>(n_copy);
+        ks.n_total[i] = static_cast<unsigned int>((from_pos ? 0 : n_copy) + n_app);
+        ks.at[i] = from_pos;
         most = std::max(most, n_copy + n_app);
     }
     if (most == 0) return OSQ_OK;
+    ks.pos = pos;
+    ks.batch_heads = static_cast<unsigned int>(batch * heads);
     const dim3 grid(static_cast<unsigned>(grid_for(most, kThreads, kMaxBlocks)), static_cast<unsigned>(n_sites));
     hipLaunchKernelGGL(fq_kv_append_kernel, grid, dim3(kThreads), 0, static_cast<hipStream_t>(stream), ks,
                        static_cast<unsigned int>(heads), static_cast<unsigned int>(dv));
-    return check_launch("fake_quant_kv_append");
+    return check_launch(pos ? "fake_quant_kv_append_at" : "fake_quant_kv_append");
+}
+
+extern "C" int osq_fake_quant_kv_append(const osq_kv_append_site* sites, int n_sites, int64_t batch, int64_t heads,
+                                        int64_t head_dim, osq_stream stream) {
+    return kv_append_launch(sites, n_sites, batch, heads, head_dim, nullptr, nullptr, stream);
+}
+
+extern "C" int osq_fake_quant_kv_append_at(const osq_kv_append_site* sites, int n_sites, int64_t batch, int64_t heads,
+                                           int64_t head_dim, const int32_t* pos, const int32_t* site_at, osq_stream stream) {
+    OSQ_REQUIRE(pos && site_at, "fake_quant_kv_append_at: null position word or site flags");
+    return kv_append_launch(sites, n_sites, batch, heads, head_dim, pos, site_at, stream);
 }
 
 // per-channel launch: T = float (x_quant optional), __bf16 or _Float16 (x_quant == nullptr); y is fp32 for every T

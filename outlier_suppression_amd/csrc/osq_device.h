@@ -559,4 +559,16 @@ __device__ __forceinline__ void grid_reset(unsigned int* counters, unsigned int 
         __hip_atomic_store(&counters[(1 + s) * kTicketStride], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// KV-cache appends whose offset is a device word (osq_fake_quant_kv_append_at / _codes_at; Sites: the kernel's site table).
+// The position of an _at append, or -1 when it fits no flagged site: *pos < 0, *pos + tokens > cap, or a prefix longer than
+// its source.  One scalar read; every workgroup of the launch takes the same decision, so a refused position writes nothing.
+template <typename Sites>
+__device__ __forceinline__ int kv_append_position(const Sites& s) {
+    const int p = __builtin_amdgcn_readfirstlane(*s.pos);
+    bool ok = p >= 0;
+    for (unsigned int k = 0; k < gridDim.y; ++k)
+        if (s.at[k]) ok = ok && static_cast<unsigned int>(p) + s.tokens[k] <= s.cap[k] && (!s.src[k] || static_cast<unsigned int>(p) <= s.src_cap[k]);
+    return ok ? p : -1;
+}
+
 }  // namespace osq

@@ -8,6 +8,8 @@ transformers' own, applied in transformers' order.  Not covered: sampling, retur
 
 Each step feeds the last token with the cache (quant_bart.QuantizedBartCache: the step's k / v are fake-quantized and
 appended in one launch, a beam reorder rides in the next append); ``use_cache=False`` re-runs the whole prefix instead.
+``graph=True`` (or the package switch, set_graph_decode) replays a captured graph of the step from the third step on
+(model/graph_decode.py); ``model.last_decode_graph`` tells what happened.
 """
 import torch
 from torch import nn
@@ -46,8 +48,11 @@ def _processors(min_length, eos, no_repeat, forced_bos, forced_eos, max_length, 
     return procs
 
 
-def _step_logits(model, seq, enc, attention_mask, cache):
-    """Logits of the last position: the last token through the cache, or the whole prefix without one."""
+def _step_logits(model, seq, enc, attention_mask, cache, stepper=None):
+    """Logits of the last position: the last token through the cache (``stepper``: by a captured graph where it can), or
+    the whole prefix without one."""
+    if stepper is not None:
+        return stepper.logits(seq, enc, attention_mask, cache)
     if cache is None:
         return model(decoder_input_ids=seq, encoder_outputs=(enc,), attention_mask=attention_mask)[0][:, -1, :]
     logits, cache_out, _ = model(decoder_input_ids=seq[:, -1:], encoder_outputs=(enc,), attention_mask=attention_mask,
@@ -57,7 +62,7 @@ def _step_logits(model, seq, enc, attention_mask, cache):
 
 
 def generate(model, input_ids, attention_mask=None, max_length=None, num_beams=None, use_cache=True, cache_codes=None,
-             **kwargs):
+             graph=None, **kwargs):
     if kwargs.pop("synced_gpus", False):      # Seq2SeqTrainer's predict_with_generate passes synced_gpus=False
         raise NotImplementedError("generate(): synced_gpus=True is not supported")
     for name in _NOT_COVERED:
@@ -84,14 +89,24 @@ def generate(model, input_ids, attention_mask=None, max_length=None, num_beams=N
     from .quant_bart import QuantizedBartCache
     codes = util_layernorm.CACHE_CODES if cache_codes is None else bool(cache_codes)
     cache = QuantizedBartCache(n_layers, capacity=max_length, codes=codes) if use_cache else None
+    # a captured decoding step (model/graph_decode.py), where asked for and possible; else the steps are issued as ever
+    from . import graph_decode
+    stepper = None
+    if util_layernorm.GRAPH_DECODE if graph is None else graph:
+        info = graph_decode.DecodeGraphInfo(graph_decode.why_not(model, enc.device, use_cache, max_length))
+        if info.reason is None:
+            stepper = graph_decode.GenerateStepper(model, info)
+    else:
+        info = graph_decode.DecodeGraphInfo("not asked for")
+    model.last_decode_graph = info
     if num_beams == 1:
         if n_return != 1:
             raise ValueError("greedy decoding returns one sequence per input (num_return_sequences must be 1)")
-        return _checked(cache, _greedy(model, enc, attention_mask, start, pad, eos_t, procs, max_length, cache))
+        return _checked(cache, _greedy(model, enc, attention_mask, start, pad, eos_t, procs, max_length, cache, stepper))
     if n_return > num_beams:
         raise ValueError("num_return_sequences must not exceed num_beams")
     return _checked(cache, _beam_search(model, enc, attention_mask, start, pad, eos_t, procs, max_length, num_beams, n_return,
-                                        get("length_penalty"), get("early_stopping"), cache))
+                                        get("length_penalty"), get("early_stopping"), cache, stepper))
 
 
 def _checked(cache, tokens):
@@ -106,12 +121,12 @@ def _checked(cache, tokens):
     return tokens
 
 
-def _greedy(model, enc, attention_mask, start, pad, eos, procs, max_length, cache):
+def _greedy(model, enc, attention_mask, start, pad, eos, procs, max_length, cache, stepper=None):
     b = enc.shape[0]
     seq = torch.full((b, 1), start, dtype=torch.long, device=enc.device)
     unfinished = torch.ones(b, dtype=torch.long, device=enc.device)
     while seq.shape[1] < max_length:
-        scores = procs(seq, _step_logits(model, seq, enc, attention_mask, cache).to(torch.float32))
+        scores = procs(seq, _step_logits(model, seq, enc, attention_mask, cache, stepper).to(torch.float32))
         nxt = torch.argmax(scores, dim=-1)
         if eos is not None:
             nxt = nxt * unfinished + pad * (1 - unfinished)
@@ -131,7 +146,7 @@ def _gather(t, idx):
 
 
 def _beam_search(model, enc, attention_mask, start, pad, eos, procs, max_length, nb, n_return, length_penalty,
-                 early_stopping, cache):
+                 early_stopping, cache, stepper=None):
     """transformers' vectorised beam search (GenerationMixin._beam_search, 5.x) with the prompt of one start token."""
     dev = enc.device
     bsz = enc.shape[0]
@@ -154,7 +169,7 @@ def _beam_search(model, enc, attention_mask, start, pad, eos, procs, max_length,
     offsets = torch.arange(bsz, device=dev).view(-1, 1) * nb
     while True:
         flat = running[:, :, :cur].reshape(bsz * nb, cur)
-        logits = _step_logits(model, flat, enc, attention_mask, cache).to(torch.float32)
+        logits = _step_logits(model, flat, enc, attention_mask, cache, stepper).to(torch.float32)
         log_probs = procs(flat, nn.functional.log_softmax(logits, dim=-1))
         log_probs = (log_probs.view(bsz, nb, vocab) + running_scores[:, :, None]).view(bsz, nb * vocab)
         # c. top-K continuations over all beams

@@ -1,0 +1,181 @@
+"""A cached BART decoding step as a captured graph, replayed once per token.
+
+A step over the KV cache is several hundred small launches, and the host issuing them is what bounds it (DESIGN.md,
+section 4).  Capturing the step into a hipGraph and replaying it takes the host out -- once nothing the host knows about
+the position is baked into a launch.  So the cache goes into device-position mode (quant_bart.QuantizedBartCache): the past
+length lives in one device int32, the append and the self-attention read it in their launches
+(ops.fake_quant_kv_append_at / _codes_at, ops.decode_attention_at), the position embedding is indexed by a tensor derived
+from it, and the decoder advances it after its last layer.  A captured step is then: position embedding, every layer, the
+LM head, the position increment -- a single chain on one stream.
+
+    step 0        eager: it computes the cross-attention keys / values and allocates the cache
+    step 1        eager on the capture stream, the cache now in device-position mode: per-stream workspaces come to exist
+    step 2, ...   captured on first need, replayed from then on
+
+Which graph a step needs goes by what the step does to the cache: appending in place (greedy decoding: one graph), or, with
+a beam reorder pending, copying the kept prefix from the current buffers into their partners through the row index, A -> B
+or B -> A (beam search: two graphs, replayed alternately).  Inputs are static buffers filled before a replay: the last token,
+the cache's row index (QuantizedBartCache.reorder) and the encoder mask; the logits are the graph's own output tensor, valid
+until its next replay.  Beam bookkeeping and logits processors stay outside.  The graphs live as long as the GraphDecoder:
+one generate() call.
+
+The words are those of issuing the same steps one by one with the one-launch attention on (util_layernorm.
+FUSE_DECODE_ATTENTION): a captured step always uses it, cross-attention included, whatever the switch says.
+"""
+import time
+
+import torch
+
+from .. import util_layernorm as _UL
+from ..quantization.fake_quant import QuantizeBase
+
+
+class DecodeGraphInfo:
+    """What a generate() call did with its decoding steps: ``captured`` graphs, ``replays`` of them, and, when no step was
+    captured, the ``reason``.  ``capture_seconds``: host time spent capturing and instantiating, the device idle."""
+
+    def __init__(self, reason=None):
+        self.captured, self.replays, self.reason, self.capture_seconds = 0, 0, reason, 0.0
+
+    def __repr__(self):
+        return f"DecodeGraphInfo(captured={self.captured}, replays={self.replays}, reason={self.reason!r})"
+
+
+def _plain(q):
+    return q.fake_quant_enabled == 1 and q.observer_enabled != 1 and q.ch_axis == -1 and q.scale.is_cuda
+
+
+def why_not(model, device, use_cache=True, max_length=None):
+    """None when a decoding step of ``model`` can be captured, else the reason it cannot (generate() then decodes as it
+    always did).  Everything here is known before the first step."""
+    if device.type != "cuda":
+        return "the tensors are on the CPU"
+    if not use_cache:
+        return "use_cache=False: there is no cached step"
+    if torch.is_grad_enabled():
+        return "autograd is on"
+    if not _UL.FUSE_KV_APPEND:
+        return "the one-launch KV append is off (util_layernorm.FUSE_KV_APPEND)"
+    decoder = model.model.decoder
+    if max_length is None or not 2 <= max_length <= 4096:
+        return "the one-launch attention takes lengths up to 4096"
+    if decoder.training:
+        rates = [decoder.dropout] + [p for layer in decoder.layers
+                                     for p in (layer.dropout, layer.activation_dropout, layer.self_attn.dropout,
+                                               layer.encoder_attn.dropout)]
+        if any(p > 0 for p in rates):
+            return "dropout is active"
+    for name, m in list(decoder.named_modules()) + list(model.lm_head.named_modules()):
+        if isinstance(m, QuantizeBase) and m.observer_enabled == 1:
+            return f"an observer is enabled ({name})"
+    for i, layer in enumerate(decoder.layers):
+        for attn, sites in ((layer.self_attn, ("query", "key", "value", "attention_probs", "context")),
+                            (layer.encoder_attn, ("query", "attention_probs", "context"))):
+            lpr = attn.head_dim // 4
+            if attn.head_dim % 4 or lpr > 64 or lpr & (lpr - 1) or attn.embed_dim != attn.num_heads * attn.head_dim:
+                return f"the one-launch append and attention do not take head_dim {attn.head_dim}"
+            for site in sites:
+                if not _plain(getattr(attn, site + "_post_act_fake_quantize")):
+                    return f"a quantizer is not in the plain quantising state (decoder layer {i}, {site})"
+    return None
+
+
+def _cache_fits(cache):
+    """After the first step: the reason the cache it left cannot go into device-position mode, or None."""
+    for i in range(len(cache)):
+        k, v, cross = cache._k[i], cache._v[i], cache._cross[i]
+        if k is None or cross is None:
+            return f"decoder layer {i} holds no keys / values after the first step"
+        if k.dim() != 4 or not (k.is_contiguous() and v.is_contiguous()) or k.shape[2] != cache.capacity or k.shape != v.shape:
+            return f"decoder layer {i} took the eager append: its cache is no [B, h, capacity, d] buffer"
+        if k.dtype != v.dtype:
+            return f"decoder layer {i} holds keys and values in different formats"
+        if cross[0].dtype != cross[1].dtype:
+            return f"decoder layer {i} holds its cross-attention keys and values in different formats"
+    return None
+
+
+class GraphDecoder:
+    """The decoding steps after the first, for one encoder batch and one cache: ``step(tokens)`` returns the logits
+    [B, vocab] of the next position, by a captured graph from the third step on.  ``enc`` / ``attention_mask`` are the
+    (beam-expanded) encoder states and mask the steps attend to; ``cache`` is the QuantizedBartCache the first step left."""
+
+    def __init__(self, model, enc, attention_mask, cache, info=None):
+        self.model, self.cache = model, cache
+        self.info = DecodeGraphInfo() if info is None else info
+        self.enc = enc
+        self.mask, self._mask_given = attention_mask.clone(), attention_mask
+        self.tokens = torch.zeros((enc.shape[0], 1), dtype=torch.long, device=enc.device)
+        self.stream = torch.cuda.Stream(device=enc.device)
+        self.graphs = {}
+        self.warm = False
+        cache.enter_device_position()
+
+    def _issue(self):
+        """One step's launches, as the model issues them; the one-launch attention on for the cross-attention as well."""
+        old = _UL.FUSE_DECODE_ATTENTION
+        _UL.FUSE_DECODE_ATTENTION = True
+        try:
+            logits, cache, _ = self.model(decoder_input_ids=self.tokens, encoder_outputs=(self.enc,), attention_mask=self.mask,
+                                          past_key_values=self.cache, use_cache=True)
+        finally:
+            _UL.FUSE_DECODE_ATTENTION = old
+        assert cache is self.cache
+        return logits[:, -1, :]
+
+    def step(self, tokens, attention_mask=None):
+        cache = self.cache
+        if not cache.positioned():
+            raise RuntimeError("GraphDecoder: the cache left device-position mode (it was read with a reorder pending)")
+        if cache.get_seq_length() + 1 > cache.capacity:
+            raise RuntimeError(f"GraphDecoder: the cache is full ({cache.capacity} positions)")
+        self.tokens.copy_(tokens)
+        if attention_mask is not None and attention_mask is not self._mask_given:      # another mask than the one held
+            self.mask.copy_(attention_mask)
+            self._mask_given = attention_mask
+        if not self.warm:
+            # issued, not captured: whatever a stream allocates on first use (workspaces) exists before a capture on it
+            current = torch.cuda.current_stream(self.enc.device)
+            self.stream.wait_stream(current)
+            with torch.cuda.stream(self.stream):
+                logits = self._issue()
+            current.wait_stream(self.stream)
+            logits.record_stream(current)
+            self.warm = True
+            return logits
+        # the graph this step needs: in place, or moving from the current buffers into their partners
+        key = (cache.reorder_pending(), cache._k[0].data_ptr())
+        entry = self.graphs.get(key)
+        if entry is None:
+            t0 = time.perf_counter()
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph, stream=self.stream):
+                logits = self._issue()                      # recorded, not run: the host side of the step is now done
+            entry = self.graphs[key] = (graph, logits)
+            self.info.captured += 1
+            self.info.capture_seconds += time.perf_counter() - t0
+        else:
+            cache.stepped()
+        entry[0].replay()
+        self.info.replays += 1
+        return entry[1]
+
+
+class GenerateStepper:
+    """generate()'s steps with ``graph=True``: the first through the model, the rest through a GraphDecoder -- or all of
+    them through the model when a step cannot be captured (``info.reason`` says why)."""
+
+    def __init__(self, model, info):
+        self.model, self.info, self.decoder = model, info, None
+
+    def logits(self, seq, enc, attention_mask, cache):
+        if self.decoder is not None:
+            return self.decoder.step(seq[:, -1:], attention_mask)
+        logits, cache_out, _ = self.model(decoder_input_ids=seq[:, -1:], encoder_outputs=(enc,), attention_mask=attention_mask,
+                                          past_key_values=cache, use_cache=True)
+        assert cache_out is cache
+        if self.info.reason is None and seq.shape[1] == 1:
+            self.info.reason = _cache_fits(cache)
+            if self.info.reason is None:
+                self.decoder = GraphDecoder(self.model, enc, attention_mask, cache, self.info)
+        return logits[:, -1, :]

@@ -29,7 +29,8 @@ from .. import ops
 from .. import util_layernorm as _UL
 from ..quantization import QuantizedModule, Quantizer
 from ..util_layernorm import (GammaResidual, QuantizedLayerNorm, activation_fake_quant, attention_probs_fake_quant,
-                              decode_attention_fake_quant, kv_append_codes_fake_quant, kv_append_fake_quant,
+                              decode_attention_at_fake_quant, decode_attention_fake_quant, decode_grad_table,
+                              kv_append_codes_fake_quant, kv_append_fake_quant,
                               kv_site_params, merge_heads_fake_quant, qkv_heads_fake_quant, residual_layernorm,
                               split_heads_fake_quant)
 
@@ -153,7 +154,14 @@ class QuantizedBartCache:
     fp32 from then on.  Whatever is read from the cache -- ``cache[i]``, iteration, ``to_legacy()``, ``past(i)`` -- is
     fp32, the words an fp32 cache holds.  Elements without a code (NaN, an infinite value, a fractional zero point) are
     counted on the device: ``rejected()`` reads the counter, and attention over a cache with a non-zero counter yields
-    NaN."""
+    NaN.
+
+    Device-position mode (``enter_device_position()``; model/graph_decode.py is its only user): the past length also lives
+    in ONE device int32 shared by all layers, which single-token steps read in their launches (the _at forms of the append
+    and of the attention) and the decoder advances after its last layer, so that a captured step can be replayed at every
+    position; ``_len`` mirrors it on the host.  ``reorder()`` then copies the index into a static int64 buffer, and both
+    buffers of every layer's ping-pong pair exist at ``capacity``.  Reading the cache while a reorder is pending leaves the
+    mode (the read re-packs the buffers)."""
 
     def __init__(self, num_layers, capacity=None, codes=False):
         self.capacity = capacity
@@ -168,6 +176,9 @@ class QuantizedBartCache:
         self._record_pairs = None                  # [num_layers * 4, 2] fp32 on the device: every record's (scale_eff, zp_eff)
         self._rejected = None                      # one int32 on the device
         self._demoted = []
+        self._pos = None                           # device-position mode: one int32 on the device, the past length
+        self._rows_buf = None                      # ... and the static int64 [B] row index reorder() copies into
+        self._tables = {}                          # ... grad-factor tables of the probabilities quantizers, on the device
 
     @classmethod
     def wrap(cls, past, num_layers, capacity=None, codes=None):
@@ -192,6 +203,11 @@ class QuantizedBartCache:
 
     def reorder(self, beam_idx):
         """Select the rows ``beam_idx`` of every self-attention cache, lazily; returns self."""
+        if self._pos is not None:
+            pending = self._rows[0] is not None
+            self._rows_buf.copy_(self._rows_buf.index_select(0, beam_idx) if pending else beam_idx)
+            self._rows = [self._rows_buf] * len(self._k)
+            return self
         for i in range(len(self._k)):
             if self._k[i] is not None:
                 self._rows[i] = beam_idx if self._rows[i] is None else self._rows[i].index_select(0, beam_idx)
@@ -200,6 +216,10 @@ class QuantizedBartCache:
     def _materialise(self, i):
         rows = self._rows[i]
         if rows is not None:
+            if self._pos is not None:              # the re-packed tensors are not the static buffers a captured step names
+                self._pos = None
+                self._rows = [None if r is None else r.clone() for r in self._rows]
+                rows = self._rows[i]
             n = self._len[i]
             self._k[i] = self._k[i][:, :, :n].index_select(0, rows)
             self._v[i] = self._v[i][:, :, :n].index_select(0, rows)
@@ -356,6 +376,85 @@ class QuantizedBartCache:
     def slot(self, i):
         return _CacheSlot(self, i)
 
+    # ---- device-position mode
+    def enter_device_position(self):
+        """After the first step: the position moves to a device word and every layer gets both buffers of its pair at
+        ``capacity``.  Needs every layer to hold contiguous [B, h, capacity, d] buffers of one length."""
+        n = self._len[0]
+        for i, (k, v) in enumerate(zip(self._k, self._v)):
+            if (k is None or self._len[i] != n or k.dim() != 4 or not (k.is_contiguous() and v.is_contiguous())
+                    or k.shape != v.shape or k.shape[2] != self.capacity):
+                raise ValueError(f"layer {i} of the cache does not hold [B, h, capacity, d] buffers of length {n}")
+            for j, t in enumerate((k, v)):
+                spare = self._spare[i][j]
+                if spare is None or spare.shape != t.shape or spare.dtype != t.dtype or not spare.is_contiguous():
+                    self._spare[i][j] = torch.empty_like(t)
+        k = self._k[0]
+        self._rows_buf = torch.arange(k.shape[0], dtype=torch.int64, device=k.device)
+        if self._rows[0] is not None:
+            self._rows_buf.copy_(self._rows[0])
+            self._rows = [self._rows_buf] * len(self._k)
+        self._pos = torch.tensor([n], dtype=torch.int32, device=k.device)
+        return self
+
+    def positioned(self):
+        return self._pos is not None
+
+    def position(self):
+        """The past length: an int, or in device-position mode the device word a step's launches read."""
+        return self._len[0] if self._pos is None else self._pos
+
+    def reorder_pending(self):
+        return self._rows[0] is not None
+
+    def at_targets(self, i):
+        """(k_dst, v_dst, k_src, v_src, rows) of a single-token step in device-position mode: in place, or into the partner
+        buffers with the prefix copied from the whole current buffers through the static row index."""
+        if self._rows[i] is None:
+            return self._k[i], self._v[i], None, None, None
+        return self._spare[i][0], self._spare[i][1], self._k[i], self._v[i], self._rows_buf
+
+    def commit_at(self, i, k, v, t=1):
+        """Host bookkeeping of a device-position step of layer i (also for a replayed one: ``stepped``)."""
+        if k is not self._k[i]:
+            self._spare[i] = [self._k[i], self._v[i]]
+            self._k[i], self._v[i] = k, v
+        self._len[i] += t
+        self._rows[i] = None
+
+    def advance(self, t):
+        """After the decoder's last layer: the device word follows (a launch of the step, so a captured step carries it)."""
+        if self._pos is not None:
+            self._pos.add_(t)
+
+    def stepped(self):
+        """A captured step was replayed: what its launches did, on the host side."""
+        for i in range(len(self._k)):
+            if self._rows[i] is None:
+                self.commit_at(i, self._k[i], self._v[i])
+            else:
+                self.commit_at(i, *self._spare[i])
+
+    def record_at(self, i, name, params):
+        """The record pair of a coded tensor for a device-position append (None: an fp32 tensor).  Such a step cannot demote:
+        parameters that differ from those of the first append are an error."""
+        rec = self._records[i].get(name)
+        if rec is None:
+            return None
+        if rec.fresh or _code_identity(params) != rec.identity:
+            raise RuntimeError(f"the quantizer parameters of cache tensor {name} of layer {i} changed while its position "
+                               "lives on the device")
+        return rec.scale_eff, rec.zp_eff
+
+    def grad_table(self, quantizer, rows):
+        """decode_grad_table of a probabilities quantizer on the device, built once per (quantizer settings, rows)."""
+        key = (rows, self.capacity, quantizer.param_mode, quantizer.quant_max, getattr(quantizer, "use_grad_scaling", False),
+               getattr(quantizer, "numel_multiplier", 1), quantizer.ch_axis)
+        table = self._tables.get(key)
+        if table is None:
+            table = self._tables[key] = decode_grad_table(quantizer, rows, self.capacity).to(self._pos.device)
+        return table
+
 
 class _CacheSlot:
     """One decoder layer's view of a QuantizedBartCache: the ``past_key_value`` a QuantizedBartAttention takes."""
@@ -376,6 +475,10 @@ class QuantizedBartLearnedPositionalEmbedding(QuantizedModule):
 
     def forward(self, input_ids_shape, past_key_values_length=0):
         seq_len = input_ids_shape[1]
+        if isinstance(past_key_values_length, torch.Tensor):        # a device word (QuantizedBartCache in device-position mode)
+            positions = past_key_values_length.to(torch.long) + torch.arange(seq_len, dtype=torch.long,
+                                                                             device=past_key_values_length.device)
+            return self.position_embeddings(positions + self.offset)
         positions = torch.arange(past_key_values_length, past_key_values_length + seq_len, dtype=torch.long,
                                  device=self.position_embeddings.weight.device)
         return self.position_embeddings(positions + self.offset)
@@ -472,6 +575,8 @@ class QuantizedBartAttention(QuantizedModule):
         bsz, tgt_len, _ = hidden_states.shape
         heads = self.num_heads
         if past_key_value is not None:
+            if key_value_states is None and past_key_value.cache.positioned():
+                return self._step_at(past_key_value, hidden_states, attention_mask, observation_mask), past_key_value
             q, k, v = self._cached_qkv(past_key_value, hidden_states, key_value_states, observation_mask)
             out = self._attend(q, k, v, bsz, tgt_len, attention_mask, observation_mask, cached=True)
             return out, past_key_value
@@ -488,6 +593,47 @@ class QuantizedBartAttention(QuantizedModule):
             k = split_heads_fake_quant(self.key_post_act_fake_quantize, xk, heads, observation_mask)
             v = split_heads_fake_quant(self.value_post_act_fake_quantize, xv, heads, observation_mask)
         return self._attend(q, k, v, bsz, tgt_len, attention_mask, observation_mask)
+
+    def _step_at(self, slot, hidden_states, attention_mask, observation_mask):
+        """Self-attention of a single-token step over a cache in device-position mode: the append and the attention read the
+        position in their launches (the _at forms), so the same two launches serve every step -- and a captured graph of
+        them.  They write and compute the words of _cached_qkv + _attend with the one-launch attention at that position.
+        There is no eager form to fall back to: a launch that refuses is an error."""
+        cache, i, heads, d = slot.cache, slot.layer, self.num_heads, self.head_dim
+        bsz, t, _ = hidden_states.shape
+        if t != 1 or attention_mask is not None:
+            raise RuntimeError("a cache in device-position mode takes single-token steps without a decoder mask")
+        xq = self.q_proj(hidden_states) * self.scaling
+        xk, xv = self.k_proj(hidden_states), self.v_proj(hidden_states)
+        qs = (self.query_post_act_fake_quantize, self.key_post_act_fake_quantize, self.value_post_act_fake_quantize)
+        ps = [kv_site_params(q, x) for q, x in zip(qs, (xq, xk, xv))]
+        if any(p is None for p in ps):
+            raise RuntimeError("device-position step: a q / k / v site does not take the one-launch append")
+        recs = [cache.record_at(i, name, p) for name, p in zip(_SELF, ps[1:])]
+        if (recs[0] is None) != (recs[1] is None):
+            raise RuntimeError("device-position step: keys and values must both be held as codes, or both as fp32 words")
+        kd, vd, ks, vs, rows = cache.at_targets(i)
+        qy = xq.new_empty((bsz, heads, t, d))
+        if recs[0] is not None:
+            out = kv_append_codes_fake_quant([(qs[0], ps[0], xq, qy, 0, None, None, None, False),
+                                              (qs[1], ps[1], xk, kd, None, ks, rows, recs[0], False),
+                                              (qs[2], ps[2], xv, vd, None, vs, rows, recs[1], False)], heads, cache._rejected,
+                                             pos=cache._pos)
+            codes = (cache._records[i]["k"].triple(), cache._records[i]["v"].triple(), cache._rejected)
+        else:
+            out = kv_append_fake_quant([(qs[0], xq, qy, 0, None, None), (qs[1], xk, kd, None, ks, rows),
+                                        (qs[2], xv, vd, None, vs, rows)], heads, pos=cache._pos)
+            codes = None
+        if out is None:
+            raise RuntimeError("device-position step: the one-launch append refused the step")
+        cache.commit_at(i, kd, vd, t)
+        probs_q = self.attention_probs_post_act_fake_quantize
+        ctx = decode_attention_at_fake_quant(probs_q, self.context_post_act_fake_quantize, out[0], kd, vd, cache._pos, t,
+                                             cache.capacity, cache.grad_table(probs_q, bsz * heads),
+                                             dropout=(self.dropout, self.training), codes=codes)
+        if ctx is None:
+            raise RuntimeError("device-position step: the one-launch attention refused the step")
+        return self._project(ctx, observation_mask)
 
     def _attend(self, q, k, v, bsz, tgt_len, attention_mask, observation_mask, cached=False):
         """[B, h, T, d] q and [B, h, S, d] k / v (dense, or views of a cache buffer) -> the block's output.  ``cached``: a
@@ -669,7 +815,7 @@ class QuantizedBartDecoder(_BartStack):
         if use_cache or past_key_values is not None:
             cache = QuantizedBartCache.wrap(past_key_values, len(self.layers))
         past = cache.get_seq_length() if cache is not None else 0
-        h = self._embed(input_ids, observation_mask, past)
+        h = self._embed(input_ids, observation_mask, cache.position() if cache is not None else 0)
         mask = _causal_mask(bsz, tgt_len, h.dtype, h.device, past) if tgt_len > 1 else None
         if attention_mask is not None:
             pad = _expand_mask(attention_mask, h.dtype, tgt_len=tgt_len)
@@ -681,6 +827,8 @@ class QuantizedBartDecoder(_BartStack):
             h = layer(h, attention_mask=mask, encoder_hidden_states=encoder_hidden_states,
                       encoder_attention_mask=enc_mask, observation_mask=observation_mask,
                       past_key_value=cache.slot(i) if cache is not None else None)
+        if cache is not None:
+            cache.advance(tgt_len)
         return h if cache is None else (h, cache)
 
 
@@ -786,7 +934,9 @@ class QuantizedBartForConditionalGeneration(QuantizedModule):
         """Greedy or beam-search decoding with a KV cache (model/generation.py): token ids [B * num_return_sequences, L]
         padded with pad_token_id, as transformers' generate returns them.  Defaults come from the wrapped model's
         generation_config / config.  ``cache_codes``: the cache holds integer codes (None: the package switch,
-        set_cache_codes); raises RuntimeError when the cache ended up with elements that have no code."""
+        set_cache_codes); raises RuntimeError when the cache ended up with elements that have no code.  ``graph``: capture
+        a decoding step into a hipGraph and replay it (None: the package switch, set_graph_decode; model/graph_decode.py);
+        ``self.last_decode_graph`` then says what happened (captured, replays, reason)."""
         return generation.generate(self, input_ids, attention_mask=attention_mask, max_length=max_length,
                                    num_beams=num_beams, **kwargs)
 

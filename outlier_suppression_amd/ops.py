@@ -1462,8 +1462,12 @@ def fake_quant_kv_append(sites, heads):
 
 def _kv_site(e, what, x, y, offset, params, src, rows, b, heads, d, dtype):
     """Fill one entry of a KV-append table (osq_kv_append_site / osq_kv_codes_site) after checking its tensors; y and src
-    hold ``dtype`` elements.  False: a source layout the kernel does not take."""
+    hold ``dtype`` elements.  ``offset`` None (the _at forms): the launch reads the position, and a src is the buffer the
+    prefix comes from, whatever its length.  False: a source layout the kernel does not take."""
     scale, zero_point, quant_min, quant_max, mode, grad_factor = params
+    from_pos = offset is None
+    if from_pos:
+        offset = 0
     _hip.require_device(x, y, scale, zero_point)
     _check_f32(x, scale)
     if y.dtype != dtype:
@@ -1476,7 +1480,7 @@ def _kv_site(e, what, x, y, offset, params, src, rows, b, heads, d, dtype):
         raise ValueError(f"{what}: offset {offset} + {t} tokens exceeds the capacity {y.shape[2]}")
     e.x, e.y, e.scale, e.zero_point = x.data_ptr(), y.data_ptr(), scale.data_ptr(), zero_point.data_ptr()
     e.tokens, e.cap, e.offset = t, y.shape[2], int(offset)
-    if src is not None and offset > 0:
+    if src is not None and (from_pos or offset > 0):
         _hip.require_device(src)
         if src.dtype != dtype:
             raise TypeError(f"{what}: src must be {dtype}, got {src.dtype}")
@@ -1498,6 +1502,44 @@ def _kv_site(e, what, x, y, offset, params, src, rows, b, heads, d, dtype):
     return True
 
 
+def _kv_position(what, sites, pos):
+    """The position word and the per-site flags of an _at append: a site whose offset is None appends at ``*pos``."""
+    _hip.require_device(pos)
+    if pos.dtype != torch.int32 or pos.numel() != 1:
+        raise TypeError(f"{what}: pos must be one int32")
+    return (ctypes.c_int32 * len(sites))(*[int(site[2] is None) for site in sites])
+
+
+def fake_quant_kv_append_at(sites, heads, pos):
+    """fake_quant_kv_append with the position read by the launch (osq_fake_quant_kv_append_at): ``pos`` is one int32 on
+    the device, and a site whose ``offset`` is None appends at ``[*pos, *pos + t)`` and copies ``[0, *pos)`` of its src (a
+    [B', heads, S', d] buffer, S' its capacity) through src_rows.  A captured graph of the call serves every position; the
+    buffers hold what fake_quant_kv_append writes for that offset.  A position that does not fit writes nothing."""
+    lib = _hip.load()
+    n = len(sites)
+    if not 1 <= n <= 4:
+        raise ValueError("fake_quant_kv_append_at: 1..4 sites")
+    at = _kv_position("fake_quant_kv_append_at", sites, pos)
+    b = sites[0][0].shape[0]
+    d = sites[0][1].shape[-1]
+    table = (_hip.KvAppendSite * n)()
+    for i, (x, y, offset, params, src, rows) in enumerate(sites):
+        if not _kv_site(table[i], "fake_quant_kv_append_at", x, y, offset, params, src, rows, b, heads, d, torch.float32):
+            return None
+    rc = lib.osq_fake_quant_kv_append_at(table, n, b, heads, d, pos.data_ptr(), at, _hip.stream_ptr(sites[0][0].device))
+    if rc == _hip.ERR_UNSUPPORTED:
+        return None
+    _hip.check(rc, "fake_quant_kv_append_at")
+    return [site[1] for site in sites]
+
+
+def fake_quant_kv_append_codes_at(sites, heads, rejected, pos):
+    """fake_quant_kv_append_codes with the position read by the launch (osq_fake_quant_kv_append_codes_at); sites, pos and
+    the None offset as in fake_quant_kv_append_at.  A position that does not fit writes nothing and adds 1 to ``rejected``
+    when a site is coded."""
+    return _kv_append_codes(sites, heads, rejected, pos)
+
+
 def fake_quant_kv_append_codes(sites, heads, rejected):
     """fake_quant_kv_append with a destination kind per site (osq_fake_quant_kv_append_codes, csrc/kv_codes.hip).
     ``sites``: 1..4 tuples ``(x, y, offset, params, src, src_rows, record, write_record)``:
@@ -1511,6 +1553,11 @@ def fake_quant_kv_append_codes(sites, heads, rejected):
       elements behind a src_rows entry out of range are added to it.
 
     Returns the list of y, or None when the kernel does not take the geometry (nothing was launched)."""
+    return _kv_append_codes(sites, heads, rejected, None)
+
+
+def _kv_append_codes(sites, heads, rejected, _pos):
+    """fake_quant_kv_append_codes (``_pos`` None) and fake_quant_kv_append_codes_at: one table, two entry points."""
     lib = _hip.load()
     n = len(sites)
     if not 1 <= n <= 4:
@@ -1518,6 +1565,8 @@ def fake_quant_kv_append_codes(sites, heads, rejected):
     _hip.require_device(rejected)
     if rejected.dtype != torch.int32 or rejected.numel() != 1:
         raise TypeError("fake_quant_kv_append_codes: rejected must be one int32")
+    what = "fake_quant_kv_append_codes" if _pos is None else "fake_quant_kv_append_codes_at"
+    at = None if _pos is None else _kv_position(what, sites, _pos)
     b = sites[0][0].shape[0]
     d = sites[0][1].shape[-1]
     table = (_hip.KvCodesSite * n)()
@@ -1532,10 +1581,14 @@ def fake_quant_kv_append_codes(sites, heads, rejected):
             _hip.require_device(*record)
             _check_f32(*record)
             e.scale_eff, e.zp_eff, e.coded, e.write_record = record[0].data_ptr(), record[1].data_ptr(), 1, int(bool(write_record))
-    rc = lib.osq_fake_quant_kv_append_codes(table, n, b, heads, d, rejected.data_ptr(), _hip.stream_ptr(sites[0][0].device))
+    if _pos is None:
+        rc = lib.osq_fake_quant_kv_append_codes(table, n, b, heads, d, rejected.data_ptr(), _hip.stream_ptr(sites[0][0].device))
+    else:
+        rc = lib.osq_fake_quant_kv_append_codes_at(table, n, b, heads, d, rejected.data_ptr(), _pos.data_ptr(), at,
+                                                   _hip.stream_ptr(sites[0][0].device))
     if rc == _hip.ERR_UNSUPPORTED:
         return None
-    _hip.check(rc, "fake_quant_kv_append_codes")
+    _hip.check(rc, what)
     return [site[1] for site in sites]
 
 
@@ -1709,6 +1762,72 @@ def decode_attention_codes(q, k, v, mask, probs_quant, ctx_quant, k_record, v_re
         return None
     _hip.check(rc, "decode_attention_codes")
     return (out, probs) if want_probs else out
+
+
+def decode_attention_at(q, k, v, kv_len, kv_len_add, kv_max, mask, probs_quant, ctx_quant, grad_table=None, codes=None,
+                        out=None, probs_out=None):
+    """decode_attention_fake_quant / decode_attention_codes with the length read by the launch
+    (osq_decode_attention_fake_quant_at / osq_decode_attention_codes_at): ``kv_len`` is one int32 on the device and the
+    launch attends over ``*kv_len + kv_len_add`` positions, so a captured graph of the call serves every step.
+
+    k / v: whole contiguous [B, h, cap, d] cache buffers (fp32, or uint8 with ``codes = (k_record, v_record, rejected)``),
+    cap >= kv_max.  mask: None or fp32 [B, 1, 1, W >= kv_max] with a dense last axis; probs_out: None or fp32
+    [B, h, 1, W >= kv_max] likewise: columns [0, length) are read / written.  grad_table: None or ``kv_max + 1`` device
+    floats, entry n the probabilities quantizer's grad factor at length n (util_layernorm.decode_grad_table).  out: the
+    [B, 1, h * d] tensor to write, or None for a new one.  A length outside [1, kv_max] gives NaN in every word of out.
+    Returns out, or None when the library does not take the layout (nothing was launched)."""
+    lib = _hip.load()
+    _hip.require_device(q, k, v, mask, kv_len, grad_table, out, probs_out)
+    _check_f32(q)
+    if kv_len.dtype != torch.int32 or kv_len.numel() != 1:
+        raise TypeError("decode_attention_at: kv_len must be one int32")
+    dtype = torch.float32 if codes is None else torch.uint8
+    if (q.dim() != 4 or q.shape[2] != 1 or not q.is_contiguous() or k.dim() != 4 or v.dim() != 4 or k.dtype != dtype
+            or v.dtype != dtype or not k.is_contiguous() or not v.is_contiguous()):
+        return None
+    b, h, _, d = q.shape
+    if tuple(k.shape[:2]) != (b, h) or tuple(v.shape[:2]) != (b, h) or k.shape[3] != d or v.shape[3] != d:
+        return None
+    kv_max = int(kv_max)
+    if k.shape[2] < kv_max or v.shape[2] < kv_max:
+        raise ValueError("decode_attention_at: kv_max exceeds the capacity of k / v")
+    strides = []
+    for t, heads_axis in ((mask, 1), (probs_out, h)):
+        if t is None:
+            strides.append(0)
+            continue
+        if (t.dtype != torch.float32 or t.dim() != 4 or tuple(t.shape[:3]) != (b, heads_axis, 1) or t.shape[3] < kv_max
+                or (t.shape[3] > 1 and t.stride(3) != 1)):
+            return None
+        row = t.stride(1) if heads_axis > 1 else (t.stride(0) if b > 1 else t.shape[3])
+        if row < t.shape[3] or (heads_axis > 1 and b > 1 and t.stride(0) != heads_axis * row):
+            return None
+        strides.append(row)
+    if grad_table is not None and (grad_table.dtype != torch.float32 or grad_table.numel() < kv_max + 1
+                                   or not grad_table.is_contiguous()):
+        raise ValueError("decode_attention_at: grad_table must hold kv_max + 1 contiguous floats")
+    if out is None:
+        out = torch.empty((b, 1, h * d), dtype=torch.float32, device=q.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (b, 1, h * d) or not out.is_contiguous():
+        raise ValueError("decode_attention_at: out must be a contiguous fp32 [B, 1, h * d] tensor")
+    head = (q.data_ptr(), k.data_ptr(), v.data_ptr(), _hip.ptr(mask), strides[0], out.data_ptr(), _hip.ptr(probs_out),
+            strides[1], b, h, d, kv_len.data_ptr(), int(kv_len_add), kv_max, k.shape[2], v.shape[2], _hip.ptr(grad_table))
+    tail = (*_quant_group(probs_quant), *_quant_group(ctx_quant), _hip.raw_stream(q.device))
+    if codes is None:
+        rc = lib.osq_decode_attention_fake_quant_at(*head, *tail)
+    else:
+        k_record, v_record, rejected = codes
+        _hip.require_device(rejected, k_record[0], k_record[1], v_record[0], v_record[1])
+        _check_f32(k_record[0], k_record[1], v_record[0], v_record[1])
+        if rejected.dtype != torch.int32 or rejected.numel() != 1:
+            raise TypeError("decode_attention_at: rejected must be one int32")
+        rc = lib.osq_decode_attention_codes_at(*head, k_record[0].data_ptr(), k_record[1].data_ptr(), int(k_record[2]),
+                                               v_record[0].data_ptr(), v_record[1].data_ptr(), int(v_record[2]),
+                                               rejected.data_ptr(), *tail)
+    if rc == _hip.ERR_UNSUPPORTED:
+        return None
+    _hip.check(rc, "decode_attention_at")
+    return out
 
 
 def dequantize_kv_codes(codes, record, out=None):

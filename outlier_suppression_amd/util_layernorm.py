@@ -42,6 +42,12 @@ ocml's: the result is tolerance-equal to the eager sequence, not bit-equal, henc
 integer codes, one byte per element, written by ``ops.fake_quant_kv_append_codes`` and read as they are by
 ``ops.decode_attention_codes`` (csrc/kv_codes.hip, csrc/decode_attention.hip); the words computed are those of the fp32 cache.
 ``outlier_suppression_amd.set_cache_codes(True)`` / ``OSQ_CACHE_CODES=1`` turn it on; it is independent of the switch above.
+
+``GRAPH_DECODE`` (default OFF) is neither: ``generate()`` captures a cached decoding step into a hipGraph and replays it
+(model/graph_decode.py).  The step's position then comes from a device word: the append and the self-attention take the
+position-from-device launches (``ops.fake_quant_kv_append_at`` / ``_codes_at``, ``ops.decode_attention_at``), which write and
+compute the words of the static launches at that position.  A captured step always uses the one-launch attention.
+``outlier_suppression_amd.set_graph_decode(True)`` / ``OSQ_GRAPH_DECODE=1`` / ``generate(..., graph=True)`` turn it on.
 """
 import torch
 import torch.nn.functional as F
@@ -57,6 +63,7 @@ FUSE_QKV = True          # the query / key / value head-split sites of a self-at
 FUSE_SOFTMAX = False     # the attention-probabilities site as one launch (tolerance-equal; set_fast_softmax / OSQ_FAST_SOFTMAX=1)
 FUSE_DECODE_ATTENTION = False   # a cached decoding step's attention after the append as one launch (tolerance-equal; set_fast_decode_attention / OSQ_FAST_DECODE_ATTENTION=1)
 FUSE_KV_APPEND = True    # incremental decoding: a step's q / k / v sites + KV-cache append (+ beam reorder) as one launch (bit-identical)
+GRAPH_DECODE = False     # generate(): capture a cached decoding step into a graph and replay it (set_graph_decode / OSQ_GRAPH_DECODE=1 / generate(graph=True))
 CACHE_CODES = False      # incremental decoding: new KV caches hold integer codes, one byte per element (same words read back; set_cache_codes / OSQ_CACHE_CODES=1)
 
 
@@ -262,14 +269,15 @@ def qkv_heads_fake_quant(quantizers, projections, heads):
     return ops.fake_quant_headsplit_multi(list(projections), params, heads)
 
 
-def kv_append_fake_quant(sites, heads):
+def kv_append_fake_quant(sites, heads, pos=None):
     """Incremental decoding (model/quant_bart.py, QuantizedBartCache): the activation quantizers of one attention block's
     step, each site ``(quantizer, x, y, offset, src, src_rows)``, as ONE launch (ops.fake_quant_kv_append): site i writes
     the head-split fake-quant of its [B, t, h*d] projection x at positions [offset, offset + t) of the [B, h, cap, d]
     buffer y, after copying ``src.index_select(0, src_rows)[:, :, :offset]`` (or ``src[:, :, :offset]``) in front of it.
     The cache contents are word for word what ``torch.cat([past.index_select(0, idx), split_heads(quantizer(x))], 2)``
     gives.  Only when every quantizer is in its plain quantising state (as qkv_heads_fake_quant); returns the list of y,
-    or None (nothing launched): the caller then runs the eager form."""
+    or None (nothing launched): the caller then runs the eager form.  ``pos``: None, or the device int32 a site whose
+    offset is None appends at (ops.fake_quant_kv_append_at: the position is read by the launch)."""
     if not FUSE_KV_APPEND:
         return None
     for q, x, *_ in sites:
@@ -283,7 +291,7 @@ def kv_append_fake_quant(sites, heads):
             q._touch_qparams()
         table.append((x, y, offset, (q.scale.data, q.zero_point.data, q.quant_min, q.quant_max, mode,
                                      q._grad_factor(x) if q.param_mode != ops.PARAM_FIXED else 1.0), src, rows))
-    return ops.fake_quant_kv_append(table, heads)
+    return ops.fake_quant_kv_append(table, heads) if pos is None else ops.fake_quant_kv_append_at(table, heads, pos)
 
 
 def kv_site_params(q, x):
@@ -298,17 +306,19 @@ def kv_site_params(q, x):
     return (q.scale, q.zero_point, q.quant_min, q.quant_max, mode, q._grad_factor(x) if q.param_mode != ops.PARAM_FIXED else 1.0)
 
 
-def kv_append_codes_fake_quant(sites, heads, rejected):
+def kv_append_codes_fake_quant(sites, heads, rejected, pos=None):
     """kv_append_fake_quant for a cache that holds integer codes (ops.fake_quant_kv_append_codes): each site
     ``(quantizer, params, x, y, offset, src, src_rows, record, write_record)`` with ``params`` what kv_site_params gave for
     it; record None is an fp32 site as there, record ``(scale_eff, zp_eff)`` a coded one whose y / src are uint8 buffers.
     Dequantised with the record, the bytes are the words kv_append_fake_quant writes.  Returns the list of y, or None
-    (nothing launched)."""
+    (nothing launched).  ``pos`` as in kv_append_fake_quant (ops.fake_quant_kv_append_codes_at)."""
     table = []
     for q, params, x, y, offset, src, rows, record, write_record in sites:
         if params[4] & ops.PARAM_SANITIZE:
             q._touch_qparams()
         table.append((x, y, offset, params, src, rows, record, write_record))
+    if pos is not None:
+        return ops.fake_quant_kv_append_codes_at(table, heads, rejected, pos)
     return ops.fake_quant_kv_append_codes(table, heads, rejected)
 
 
@@ -352,6 +362,42 @@ def decode_attention_fake_quant(probs_quantizer, ctx_quantizer, q, k, v, mask=No
     if codes is not None:
         return ops.decode_attention_codes(q, k, v, mask, params[0], params[1], *codes)
     return ops.decode_attention_fake_quant(q, k, v, mask, params[0], params[1])
+
+
+def decode_grad_table(quantizer, rows, kv_max):
+    """The grad factors of the probabilities quantizer of a decoding step for every length: a float32 CPU tensor of
+    ``kv_max + 1`` entries, entry n what decode_attention_fake_quant hands the launch at kv_len == n for ``rows`` = B * h
+    rows of probabilities -- the same expression (``quantizer._grad_factor``), rounded to fp32 as a launch argument is.
+    Entry 0 is not read.  ops.decode_attention_at reads the table on the device: a captured step holds no host number that
+    moves with the position."""
+    fixed = quantizer.param_mode == ops.PARAM_FIXED
+    return torch.tensor([0.0] + [1.0 if fixed else quantizer._grad_factor(_Numel(rows * n)) for n in range(1, kv_max + 1)],
+                        dtype=torch.float64).to(torch.float32)
+
+
+def decode_attention_at_fake_quant(probs_quantizer, ctx_quantizer, q, k, v, pos, add, kv_max, grad_table, dropout=None,
+                                   codes=None):
+    """decode_attention_fake_quant over the whole cache buffers k / v = [B, h, cap, d] with the length ``*pos + add`` read
+    by the launch (ops.decode_attention_at; self-attention: the cache's position word and the step's own token).
+    ``grad_table``: decode_grad_table of the probabilities quantizer on the device.  No mask: a single-token step of the
+    decoder's self-attention has none.  The switch FUSE_DECODE_ATTENTION is not asked: a step whose position lives on the
+    device has no eager form.  Returns the [B, 1, h*d] context, or None (nothing launched)."""
+    if torch.is_grad_enabled() or _dropout_active(dropout) or q.dim() != 4 or q.shape[2] != 1:
+        return None
+    params = []
+    for quantizer in (probs_quantizer, ctx_quantizer):
+        if quantizer is None:
+            params.append(None)
+            continue
+        if not _plain_quantizing(quantizer, q):
+            return None
+        mode = quantizer.param_mode
+        if isinstance(quantizer, _LearnableFakeQuantize):
+            mode |= ops.PARAM_SANITIZE
+            quantizer._touch_qparams()
+        params.append((quantizer.scale.data, quantizer.zero_point.data, quantizer.quant_min, quantizer.quant_max, mode,
+                       quantizer._grad_factor(_Numel(q.numel())) if quantizer.param_mode != ops.PARAM_FIXED else 1.0))
+    return ops.decode_attention_at(q, k, v, pos, add, kv_max, None, params[0], params[1], grad_table=grad_table, codes=codes)
 
 
 def _dropout_active(dropout):

@@ -12,10 +12,15 @@ profiled steps run with the switch on.
 fp32 cache, the one-launch append and the one-launch attention on in both; the cache of a timed step is filled token by
 token, as generate() fills it (a first step of several tokens would demote the self-attention tensors of a coded cache),
 and ``cache.nbytes()`` is reported both ways; with --profile-steps the profiled steps run with codes on.
+--graph: the A/B is a captured graph of the step, replayed (model/graph_decode.py, generate(graph=True)), against the step
+issued launch by launch -- with the default switches (the step as it was before graphs existed) and with the one-launch
+attention on (the very launches the graph holds) -- for the fp32 and the coded cache; every form is timed in turn within
+each of the --reps rounds, in one process; capture + instantiate time is reported apart.
 
     python tools/decode_bench.py [--reps 7] [--out profiles/decode_step_ab.txt]
     python tools/decode_bench.py --fast-decode-attention [--out profiles/decode_attention_ab.txt]
     python tools/decode_bench.py --cache-codes [--out profiles/kv_codes_ab.txt]
+    python tools/decode_bench.py --graph [--out profiles/graph_decode_ab.txt]
 """
 import argparse
 import copy
@@ -120,6 +125,117 @@ def generate_time(q, ids, mask, fused, attention=False, codes=None):
         UL.FUSE_DECODE_ATTENTION = False
 
 
+def _stats(times):
+    times = sorted(times)
+    return f"{times[len(times) // 2]:.3f} [{times[0]:.3f}, {times[-1]:.3f}]"
+
+
+# (label, FUSE_DECODE_ATTENTION, cache codes, graph) of the forms --graph compares
+GRAPH_FORMS = [("issued, default switches, fp32 cache", False, False, False),
+               ("issued, one-launch attention, fp32 cache", True, False, False),
+               ("graph, fp32 cache", True, False, True),
+               ("issued, one-launch attention, coded cache", True, True, False),
+               ("graph, coded cache", True, True, True)]
+
+
+def graph_step_ab(q, ids, mask, beams, past, reps):
+    """One decoder step at past length ``past`` with a beam reorder pending, every form of GRAPH_FORMS timed in turn in each
+    round.  Returns {label: [ms]} and {label: seconds of capture + instantiate}."""
+    from outlier_suppression_amd import util_layernorm as UL
+    from outlier_suppression_amd.model.graph_decode import GraphDecoder
+    from outlier_suppression_amd.model.quant_bart import QuantizedBartCache
+    dev = ids.device
+    bb = ids.shape[0] * beams
+    layers = len(q.model.decoder.layers)
+    runs, capture, caches = {}, {}, {}
+    with torch.no_grad():
+        enc = q.get_encoder()(ids, attention_mask=mask).repeat_interleave(beams, 0)
+        m = mask.repeat_interleave(beams, 0)
+        tok = torch.randint(3, 50265, (bb, past + 1), device=dev)
+        perm = torch.randperm(bb, device=dev)
+        last = tok[:, past:past + 1]
+        for label, attention, codes, graph in GRAPH_FORMS:
+            UL.FUSE_DECODE_ATTENTION = attention
+            cache = caches[label] = QuantizedBartCache(layers, capacity=past + 1, codes=codes)
+            for t in range(past):
+                q(attention_mask=m, decoder_input_ids=tok[:, t:t + 1], encoder_outputs=(enc,), past_key_values=cache, use_cache=True)
+            lens = list(cache._len)
+            decoder = GraphDecoder(q, enc, m, cache) if graph else None
+
+            def run(cache=cache, decoder=decoder, attention=attention, lens=lens):
+                UL.FUSE_DECODE_ATTENTION = attention
+                cache._len = list(lens)
+                if decoder is not None:
+                    cache._pos.fill_(past)
+                cache.reorder(perm)
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                if decoder is not None:
+                    decoder.step(last)
+                else:
+                    q(attention_mask=m, decoder_input_ids=last, encoder_outputs=(enc,), past_key_values=cache, use_cache=True)
+                torch.cuda.synchronize()
+                return (time.perf_counter() - t0) * 1e3
+            for _ in range(4):                      # lead-in: a graph form issues one step and captures its two graphs here
+                run()
+            if decoder is not None:
+                assert decoder.info.captured == 2, decoder.info
+                capture[label] = decoder.info.capture_seconds
+            runs[label] = (run, [])
+        for _ in range(reps):
+            for label, (run, times) in runs.items():
+                times.append(run())
+        for label, cache in caches.items():
+            assert cache.rejected() == 0 and bool(cache.coded()) is ("coded" in label) and not cache.demoted()
+    UL.FUSE_DECODE_ATTENTION = False
+    return {label: times for label, (run, times) in runs.items()}, capture
+
+
+def graph_generate_ab(q, ids, mask, reps):
+    from outlier_suppression_amd import util_layernorm as UL
+    times = {label: [] for label, *_ in GRAPH_FORMS}
+    capture = {}
+    kw = dict(attention_mask=mask, max_length=62, num_beams=6, min_length=62)
+    try:
+        with torch.no_grad():
+            for r in range(reps + 1):
+                for label, attention, codes, graph in GRAPH_FORMS:
+                    UL.FUSE_DECODE_ATTENTION = attention
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    q.generate(ids, cache_codes=codes, graph=graph, **kw)
+                    torch.cuda.synchronize()
+                    if r:                           # the first round warms every form up
+                        times[label].append(time.perf_counter() - t0)
+                        if graph:
+                            assert q.last_decode_graph.captured == 2, q.last_decode_graph
+                            capture.setdefault(label, []).append(q.last_decode_graph.capture_seconds)
+    finally:
+        UL.FUSE_DECODE_ATTENTION = False
+    return times, capture
+
+
+def graph_ab(q, ids, mask, args):
+    lines = [f"decoder step as a captured graph, BART-large shape (random init, {args.layers}+{args.layers} layers), W6A6 LSQ+ plain "
+             f"quantising, batch {args.batch} x {args.beams} beams, source {args.src}; a beam reorder pending before every step (the "
+             f"graph forms replay their A->B / B->A graphs alternately); caches filled token by token; every form timed in turn in each "
+             f"of {args.reps} rounds, one process; median [min, max]"]
+    print(lines[0], flush=True)
+    for past in (1, 31, 62):
+        times, capture = graph_step_ab(q, ids, mask, args.beams, past, args.reps)
+        lines.append(f"S = {past:2d}, one step, ms:")
+        lines += [f"    {label:45s} {_stats(t)}" for label, t in times.items()]
+        lines += [f"    capture + instantiate of the two graphs, {label}: {secs * 1e3:.0f} ms (not in the step times)"
+                  for label, secs in capture.items()]
+        print("\n".join(lines[-len(times) - len(capture) - 1:]), flush=True)         # as it comes: a run of minutes
+    times, capture = graph_generate_ab(q, ids, mask, args.reps)
+    lines.append("generate(max_length=62, num_beams=6, min_length=62), s, wall time of the call (a graph form: capture included):")
+    lines += [f"    {label:45s} {_stats(t)}" for label, t in times.items()]
+    lines += [f"    of which capture + instantiate, {label}: {_stats(t)}" for label, t in capture.items()]
+    print("\n".join(lines[-len(times) - len(capture) - 1:]), flush=True)
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=32)
@@ -130,15 +246,22 @@ def main():
     ap.add_argument("--profile-steps", type=int, default=0)
     ap.add_argument("--fast-decode-attention", action="store_true")
     ap.add_argument("--cache-codes", action="store_true")
+    ap.add_argument("--graph", action="store_true")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     q, ids, mask = build(args.batch, args.src, args.layers)
+    if args.graph and not args.profile_steps:
+        text = "\n".join(graph_ab(q, ids, mask, args))
+        if args.out:
+            with open(args.out, "w") as f:
+                f.write(text + "\n")
+        return
     if args.profile_steps:
         from outlier_suppression_amd import util_layernorm as UL
         UL.FUSE_DECODE_ATTENTION = args.fast_decode_attention
         with torch.no_grad():
             q.generate(ids, attention_mask=mask, max_length=args.profile_steps + 1, num_beams=args.beams,
-                       min_length=args.profile_steps + 1, cache_codes=args.cache_codes)
+                       min_length=args.profile_steps + 1, cache_codes=args.cache_codes, graph=args.graph)
         torch.cuda.synchronize()
         return
     lines = [f"decoder step, BART-large shape (random init, {args.layers}+{args.layers} layers), W6A6 LSQ+ plain quantising, "
