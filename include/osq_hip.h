@@ -41,7 +41,7 @@ typedef void* osq_stream;
  *     Added within 10 (no existing signature changed): osq_quantize_codes, osq_dequantize_codes, osq_dequantize_codes_multi,
  *     osq_decode_attention_fake_quant, osq_fake_quant_kv_append_codes, osq_decode_attention_codes,
  *     osq_fake_quant_kv_append_at, osq_fake_quant_kv_append_codes_at, osq_decode_attention_fake_quant_at,
- *     osq_decode_attention_codes_at. */
+ *     osq_decode_attention_codes_at, osq_beam_select_workspace_bytes, osq_beam_select. */
 #define OSQ_ABI_VERSION 10
 
 typedef enum osq_status {
@@ -889,6 +889,35 @@ int osq_decode_attention_codes_at(const float* q, const uint8_t* k, const uint8_
                                   float* ctx_scale, void* ctx_zero_point, int ctx_zp_type, int ctx_mode,
                                   float ctx_grad_factor, int ctx_quant_min, int ctx_quant_max,
                                   osq_stream stream);
+
+/* ------------------------------------------------------------------ beam search (beam_select.hip) */
+
+/* The continuations of one beam-search step: what log_softmax, the no-repeat-ngram and min-length logits processors, the add
+ * of the running beam scores and torch.topk over [bsz, nb * vocab] compute, without writing anything of the logits' size.
+ *     value(b, j, t) = ((x - m) - L) + running_scores[b, j]     x = logits[b * nb + j, t], m = max_t x,
+ *                                                               L = log(sum_t exp(x - m)) over the whole row;
+ *                      -inf + running_scores[b, j]              when t is banned in row r = b * nb + j
+ * each fp32 operation rounded on its own.  The row sum is taken in an order fixed by vocab alone (csrc/beam_select.hip): the
+ * same inputs give the same words on every run, wherever the row lies and whatever bsz and nb are.
+ * logits: rows = bsz * nb rows of vocab floats, unit stride in a row, rows logits_stride ELEMENTS apart (4-byte aligned is
+ * enough).  running_scores: dense [bsz, nb].  seq: int64 token history, rows of at least cur tokens, seq_stride elements
+ * apart; read only when ngram > 0 and cur >= ngram.  ban_ids: n_ban <= 16 int64 ids on the device.
+ * Banned in row r: every id of ban_ids; and, with n = ngram > 0 and cur >= n, token seq[r, i + n - 1] for every i in
+ * [0, cur - n] whose window seq[r, i : i + n - 1] equals the suffix seq[r, cur - n + 1 : cur] (n = 1: every token seen so
+ * far).  Ids outside [0, vocab) ban nothing.
+ * top_value [bsz, keep] fp32 and top_index [bsz, keep] int64 (the flat index j * vocab + t) receive each batch row's first
+ * keep elements in this order: larger value first; equal values by smaller flat index; NaN above every number, NaNs among
+ * themselves by flat index (a NaN comes out as the canonical quiet NaN).
+ * workspace: at least osq_beam_select_workspace_bytes(bsz, nb, vocab, keep) bytes of device memory, 8-byte aligned, contents
+ * arbitrary; one per stream in flight.  Three launches; no host synchronisation, no allocation, nothing read from the host:
+ * legal inside a stream capture.
+ * OSQ_ERR_INVALID_ARGUMENT, nothing launched: keep > 64, nb > 64, keep > vocab, cur > 4096, n_ban > 16, a workspace that is
+ * too small, a row stride below the row's length, a negative or zero extent. */
+size_t osq_beam_select_workspace_bytes(int64_t bsz, int64_t nb, int64_t vocab, int64_t keep);
+int osq_beam_select(const float* logits, int64_t logits_stride, const float* running_scores, const int64_t* seq,
+                    int64_t seq_stride, int64_t cur, int64_t ngram, const int64_t* ban_ids, int64_t n_ban,
+                    int64_t bsz, int64_t nb, int64_t vocab, int64_t keep, float* top_value, int64_t* top_index,
+                    void* workspace, size_t workspace_bytes, osq_stream stream);
 
 /* ------------------------------------------------------------------ bf16 / fp16 only (lowp.hip) */
 

@@ -85,6 +85,21 @@ def set_graph_decode(on=True):
     util_layernorm.GRAPH_DECODE = bool(on)
 
 
+def set_beam_select(on=True):
+    """generate()'s beam search selects a step's continuations with ops.beam_select -- log-softmax, the no-repeat-ngram and
+    min-length bans, the running scores and the top-k in one kernel call (util_layernorm.BEAM_SELECT; csrc/beam_select.hip;
+    default OFF) -- instead of the torch lines; a step it cannot take runs those.  OSQ_BEAM_SELECT=1 turns it on at load;
+    ``generate(..., beam_select=True)`` asks for one call."""
+    from . import util_layernorm
+    util_layernorm.BEAM_SELECT = bool(on)
+
+
+def beam_select_from_environment(environ=None):
+    """What OSQ_BEAM_SELECT asks for: unset, empty or "0" -> False, anything else -> True."""
+    import os
+    return (os.environ if environ is None else environ).get("OSQ_BEAM_SELECT", "") not in ("", "0")
+
+
 def graph_decode_from_environment(environ=None):
     """What OSQ_GRAPH_DECODE asks for: unset, empty or "0" -> False, anything else -> True."""
     import os
@@ -102,7 +117,8 @@ def reset_tier(_lib=None):
     the reference's one-thread order, the backward's sums order-free; OSQ_STRICT=1 / 0 force both; OSQ_FAST=0 / 1 the
     one-launch LayerNorm site; OSQ_FAST_SOFTMAX=1 the one-launch attention-probabilities site and OSQ_FAST_DECODE_ATTENTION=1
     the one-launch attention of a cached decoding step (unset: off); OSQ_CACHE_CODES=1 KV caches as integer codes (unset: off);
-    OSQ_GRAPH_DECODE=1 generate() replays a captured decoding step (unset: off)."""
+    OSQ_GRAPH_DECODE=1 generate() replays a captured decoding step (unset: off); OSQ_BEAM_SELECT=1 beam search selects a step's
+    continuations with one kernel call (unset: off)."""
     import os
     width = int(os.environ.get("OSQ_STRICT_SIMD", "8"))
     strict = os.environ.get("OSQ_STRICT", "")
@@ -116,6 +132,7 @@ def reset_tier(_lib=None):
     set_fast_decode_attention(os.environ.get("OSQ_FAST_DECODE_ATTENTION", "") not in ("", "0"))
     set_cache_codes(cache_codes_from_environment())
     set_graph_decode(graph_decode_from_environment())
+    set_beam_select(beam_select_from_environment())
 
 
 _apply_environment = reset_tier

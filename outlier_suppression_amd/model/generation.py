@@ -9,7 +9,9 @@ transformers' own, applied in transformers' order.  Not covered: sampling, retur
 Each step feeds the last token with the cache (quant_bart.QuantizedBartCache: the step's k / v are fake-quantized and
 appended in one launch, a beam reorder rides in the next append); ``use_cache=False`` re-runs the whole prefix instead.
 ``graph=True`` (or the package switch, set_graph_decode) replays a captured graph of the step from the third step on
-(model/graph_decode.py); ``model.last_decode_graph`` tells what happened.
+(model/graph_decode.py); ``model.last_decode_graph`` tells what happened.  ``beam_select=True`` (set_beam_select) hands a beam
+step's log-softmax, banned tokens, score add and top-k to one kernel call (ops.beam_select) where the step's processors are
+the no-repeat-ngram and min-length ones; ``model.last_beam_select`` tells how many steps took it.
 """
 import torch
 from torch import nn
@@ -61,8 +63,74 @@ def _step_logits(model, seq, enc, attention_mask, cache, stepper=None):
     return logits[:, -1, :]
 
 
+class BeamSelectInfo:
+    """What a generate() call did with its beam steps' continuations: ``selected`` steps through ops.beam_select, ``eager``
+    steps through the torch lines, and, when none was selected, the ``reason``."""
+
+    def __init__(self, reason=None):
+        self.selected, self.eager, self.reason = 0, 0, reason
+
+    def __repr__(self):
+        return f"BeamSelectInfo(selected={self.selected}, eager={self.eager}, reason={self.reason!r})"
+
+
+class _BeamSelectPlan:
+    """What ops.beam_select needs from the processor list, read once per call: the n-gram size, min_length with its eos ids
+    on the device, and the steps on which a forced token fires (those take the torch lines)."""
+
+    def __init__(self, procs, device, nb, vocab, keep, max_length):
+        from transformers.generation.logits_process import (ForcedBOSTokenLogitsProcessor, ForcedEOSTokenLogitsProcessor,
+                                                            MinLengthLogitsProcessor, NoRepeatNGramLogitsProcessor)
+        self.ngram, self.min_length, self.eos, self.forced_at = 0, 0, None, set()
+        self.reason = None
+        if device.type != "cuda":
+            self.reason = "the tensors are on the CPU"
+        elif torch.is_grad_enabled():
+            self.reason = "autograd is on"
+        elif keep > vocab or keep > 64 or nb > 64 or max_length > 4096:
+            self.reason = "the kernel takes keep <= min(vocab, 64), num_beams <= 64 and max_length <= 4096"
+        for proc in procs:
+            if self.reason is not None:
+                break
+            if type(proc) is NoRepeatNGramLogitsProcessor and self.ngram == 0:
+                self.ngram = int(proc.ngram_size)
+            elif type(proc) is MinLengthLogitsProcessor and self.eos is None:
+                self.min_length = int(proc.min_length)
+                self.eos = proc.eos_token_id.to(device=device, dtype=torch.int64).reshape(-1).contiguous()
+                if self.eos.numel() > 16:
+                    self.reason = "more than 16 eos ids"
+            elif type(proc) is ForcedBOSTokenLogitsProcessor:
+                self.forced_at.add(1)
+            elif type(proc) is ForcedEOSTokenLogitsProcessor:
+                self.forced_at.add(int(proc.max_length) - 1)
+            else:
+                self.reason = f"a logits processor the kernel does not restate ({type(proc).__name__})"
+
+    def takes(self, cur, logits):
+        return self.reason is None and cur not in self.forced_at and logits.is_cuda and logits.dtype == torch.float32
+
+
+def _select_continuations(logits, flat, running_scores, procs, bsz, nb, vocab, keep, plan=None, info=None):
+    """Steps a-c of a beam step: the log-probabilities of the [bsz * nb, vocab] logits, the logits processors on the token
+    history ``flat`` [bsz * nb, cur], the running beam scores, and the top ``keep`` continuations of every batch row over
+    all its beams: (top_lp [bsz, keep], top_idx [bsz, keep], the flat index beam * vocab + token).  The torch lines, or,
+    where ``plan`` takes the step, one call of ops.beam_select."""
+    if plan is not None and plan.takes(flat.shape[1], logits):
+        from .. import ops
+        cur = flat.shape[1]
+        if info is not None:
+            info.selected += 1
+        return ops.beam_select(logits, running_scores, keep, flat, cur, plan.ngram, plan.eos if cur < plan.min_length else None)
+    if info is not None:
+        info.eager += 1
+    log_probs = procs(flat, nn.functional.log_softmax(logits, dim=-1))
+    log_probs = (log_probs.view(bsz, nb, vocab) + running_scores[:, :, None]).view(bsz, nb * vocab)
+    # c. top-K continuations over all beams
+    return torch.topk(log_probs, k=keep)
+
+
 def generate(model, input_ids, attention_mask=None, max_length=None, num_beams=None, use_cache=True, cache_codes=None,
-             graph=None, **kwargs):
+             graph=None, beam_select=None, **kwargs):
     if kwargs.pop("synced_gpus", False):      # Seq2SeqTrainer's predict_with_generate passes synced_gpus=False
         raise NotImplementedError("generate(): synced_gpus=True is not supported")
     for name in _NOT_COVERED:
@@ -99,14 +167,18 @@ def generate(model, input_ids, attention_mask=None, max_length=None, num_beams=N
     else:
         info = graph_decode.DecodeGraphInfo("not asked for")
     model.last_decode_graph = info
+    select = BeamSelectInfo(None if (util_layernorm.BEAM_SELECT if beam_select is None else beam_select) else "not asked for")
+    model.last_beam_select = select
     if num_beams == 1:
+        if select.reason is None:
+            select.reason = "greedy decoding selects no beams"
         if n_return != 1:
             raise ValueError("greedy decoding returns one sequence per input (num_return_sequences must be 1)")
         return _checked(cache, _greedy(model, enc, attention_mask, start, pad, eos_t, procs, max_length, cache, stepper))
     if n_return > num_beams:
         raise ValueError("num_return_sequences must not exceed num_beams")
     return _checked(cache, _beam_search(model, enc, attention_mask, start, pad, eos_t, procs, max_length, num_beams, n_return,
-                                        get("length_penalty"), get("early_stopping"), cache, stepper))
+                                        get("length_penalty"), get("early_stopping"), cache, stepper, select))
 
 
 def _checked(cache, tokens):
@@ -146,7 +218,7 @@ def _gather(t, idx):
 
 
 def _beam_search(model, enc, attention_mask, start, pad, eos, procs, max_length, nb, n_return, length_penalty,
-                 early_stopping, cache, stepper=None):
+                 early_stopping, cache, stepper=None, select=None):
     """transformers' vectorised beam search (GenerationMixin._beam_search, 5.x) with the prompt of one start token."""
     dev = enc.device
     bsz = enc.shape[0]
@@ -167,13 +239,14 @@ def _beam_search(model, enc, attention_mask, start, pad, eos, procs, max_length,
     improvable = torch.ones((bsz, 1), dtype=torch.bool, device=dev)
     finished_len = torch.zeros((bsz, nb), dtype=torch.long, device=dev)      # generated tokens of each finished beam
     offsets = torch.arange(bsz, device=dev).view(-1, 1) * nb
+    plan = None
+    if select is not None and select.reason is None:
+        plan = _BeamSelectPlan(procs, dev, nb, vocab, keep, max_length)
+        select.reason = plan.reason
     while True:
         flat = running[:, :, :cur].reshape(bsz * nb, cur)
         logits = _step_logits(model, flat, enc, attention_mask, cache, stepper).to(torch.float32)
-        log_probs = procs(flat, nn.functional.log_softmax(logits, dim=-1))
-        log_probs = (log_probs.view(bsz, nb, vocab) + running_scores[:, :, None]).view(bsz, nb * vocab)
-        # c. top-K continuations over all beams
-        top_lp, top_idx = torch.topk(log_probs, k=keep)
+        top_lp, top_idx = _select_continuations(logits, flat, running_scores, procs, bsz, nb, vocab, keep, plan, select)
         beam = top_idx // vocab
         top_seq = _gather(running, beam)
         top_seq[:, :, cur] = top_idx % vocab
@@ -212,6 +285,8 @@ def _beam_search(model, enc, attention_mask, start, pad, eos, procs, max_length,
         go_on = torch.any(improvable) & ~(torch.all(done) & (early_stopping is True)) & ~torch.all(hits)
         if not bool(go_on):
             break
+    if select is not None and select.reason is None and select.selected == 0:
+        select.reason = "a forced token fired on every step"
     seqs = finished[:, :n_return].reshape(bsz * n_return, max_length)
     length = prompt + int(finished_len[:, :n_return].max())
     return seqs[:, :length]

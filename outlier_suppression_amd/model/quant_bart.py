@@ -936,7 +936,9 @@ class QuantizedBartForConditionalGeneration(QuantizedModule):
         generation_config / config.  ``cache_codes``: the cache holds integer codes (None: the package switch,
         set_cache_codes); raises RuntimeError when the cache ended up with elements that have no code.  ``graph``: capture
         a decoding step into a hipGraph and replay it (None: the package switch, set_graph_decode; model/graph_decode.py);
-        ``self.last_decode_graph`` then says what happened (captured, replays, reason)."""
+        ``self.last_decode_graph`` then says what happened (captured, replays, reason).  ``beam_select``: beam search
+        selects a step's continuations with one kernel call (None: the package switch, set_beam_select; ops.beam_select);
+        ``self.last_beam_select`` then says how many steps took it (selected, eager, reason)."""
         return generation.generate(self, input_ids, attention_mask=attention_mask, max_length=max_length,
                                    num_beams=num_beams, **kwargs)
 

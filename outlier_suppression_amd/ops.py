@@ -1836,3 +1836,50 @@ def dequantize_kv_codes(codes, record, out=None):
     holds (osq_dequantize_codes with one channel, reading the record)."""
     scale_eff, zp_eff, quant_min = record
     return dequantize_codes(Codes(codes, scale_eff, zp_eff, int(quant_min), int(quant_min) + 255, 8, tuple(codes.shape), -1), out)
+
+
+def beam_select(logits, running_scores, keep, seq=None, cur=0, ngram=0, ban_ids=None):
+    """The continuations of one beam-search step (osq_beam_select, csrc/beam_select.hip): per batch row the first ``keep`` of
+    ``log_softmax(logits)`` with the banned tokens at -inf plus the running beam scores, over all beams -- what
+    ``torch.topk((procs(seq, log_softmax(logits)).view(bsz, nb, vocab) + running_scores[:, :, None]).view(bsz, -1), keep)``
+    returns for the no-repeat-ngram and min-length processors, under a strict order: larger value first, equal values by
+    smaller index, NaN first.
+
+    logits: fp32 [bsz * nb, vocab] with a dense last axis and any row stride (a ``[:, -1, :]`` view is taken as it lies).
+    running_scores: fp32 [bsz, nb].  seq: int64 [bsz * nb, >= cur] token history with a dense last axis, needed when
+    ``ngram > 0``; ``cur`` its current length.  ban_ids: None or up to 16 int64 ids on the device, banned in every row.
+    Returns (top_lp [bsz, keep] fp32, top_idx [bsz, keep] int64, the flat index beam * vocab + token).  Three launches on the
+    current stream, no synchronisation; a shape the library does not take raises."""
+    lib = _hip.load()
+    _hip.require_device(logits, running_scores, seq, ban_ids)
+    _check_f32(logits, running_scores)
+    if running_scores.dim() != 2 or logits.dim() != 2:
+        raise ValueError("beam_select: logits must be [bsz * nb, vocab] and running_scores [bsz, nb]")
+    bsz, nb = running_scores.shape
+    rows, vocab = logits.shape
+    if rows != bsz * nb or (vocab > 1 and logits.stride(1) != 1) or (rows > 1 and logits.stride(0) < vocab):
+        raise ValueError("beam_select: logits must hold bsz * nb rows with a dense last axis")
+    running_scores = running_scores.contiguous()
+    seq_stride = 0
+    if seq is not None:
+        if (seq.dtype != torch.int64 or seq.dim() != 2 or seq.shape[0] != rows or seq.shape[1] < cur
+                or (seq.shape[1] > 1 and seq.stride(1) != 1)):
+            raise ValueError("beam_select: seq must be int64 [bsz * nb, >= cur] with a dense last axis")
+        seq_stride = seq.stride(0) if rows > 1 else seq.shape[1]
+    elif ngram > 0:
+        raise ValueError("beam_select: ngram > 0 needs seq")
+    n_ban = 0
+    if ban_ids is not None:
+        if ban_ids.dtype != torch.int64 or ban_ids.dim() != 1 or not ban_ids.is_contiguous():
+            raise ValueError("beam_select: ban_ids must be a contiguous 1-d int64 tensor")
+        n_ban = ban_ids.numel()
+    keep = int(keep)
+    top_lp = torch.empty((bsz, keep), dtype=torch.float32, device=logits.device)
+    top_idx = torch.empty((bsz, keep), dtype=torch.int64, device=logits.device)
+    nbytes = int(lib.osq_beam_select_workspace_bytes(bsz, nb, vocab, keep))
+    ws = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=logits.device)
+    rc = lib.osq_beam_select(logits.data_ptr(), logits.stride(0) if rows > 1 else vocab, running_scores.data_ptr(),
+                             _hip.ptr(seq), seq_stride, int(cur), int(ngram), _hip.ptr(ban_ids), n_ban, bsz, nb, vocab, keep,
+                             top_lp.data_ptr(), top_idx.data_ptr(), ws.data_ptr(), nbytes, _hip.raw_stream(logits.device))
+    _hip.check(rc, "beam_select")
+    return top_lp, top_idx

@@ -48,6 +48,11 @@ integer codes, one byte per element, written by ``ops.fake_quant_kv_append_codes
 position-from-device launches (``ops.fake_quant_kv_append_at`` / ``_codes_at``, ``ops.decode_attention_at``), which write and
 compute the words of the static launches at that position.  A captured step always uses the one-launch attention.
 ``outlier_suppression_amd.set_graph_decode(True)`` / ``OSQ_GRAPH_DECODE=1`` / ``generate(..., graph=True)`` turn it on.
+
+``BEAM_SELECT`` (default OFF) is tolerance-equal as well: beam search hands a step's log-softmax, banned tokens, score add and
+top-k to ``ops.beam_select`` (csrc/beam_select.hip) instead of the torch lines, on every step whose logits processors are the
+no-repeat-ngram and min-length ones; ties come out in a strict index order where torch.topk has none.
+``outlier_suppression_amd.set_beam_select(True)`` / ``OSQ_BEAM_SELECT=1`` / ``generate(..., beam_select=True)`` turn it on.
 """
 import torch
 import torch.nn.functional as F
@@ -64,6 +69,7 @@ FUSE_SOFTMAX = False     # the attention-probabilities site as one launch (toler
 FUSE_DECODE_ATTENTION = False   # a cached decoding step's attention after the append as one launch (tolerance-equal; set_fast_decode_attention / OSQ_FAST_DECODE_ATTENTION=1)
 FUSE_KV_APPEND = True    # incremental decoding: a step's q / k / v sites + KV-cache append (+ beam reorder) as one launch (bit-identical)
 GRAPH_DECODE = False     # generate(): capture a cached decoding step into a graph and replay it (set_graph_decode / OSQ_GRAPH_DECODE=1 / generate(graph=True))
+BEAM_SELECT = False      # generate(): a beam step's log-softmax + processors + score add + top-k as one kernel call (tolerance-equal; set_beam_select / OSQ_BEAM_SELECT=1 / generate(beam_select=True))
 CACHE_CODES = False      # incremental decoding: new KV caches hold integer codes, one byte per element (same words read back; set_cache_codes / OSQ_CACHE_CODES=1)
 
 

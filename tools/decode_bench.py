@@ -16,11 +16,17 @@ and ``cache.nbytes()`` is reported both ways; with --profile-steps the profiled 
 issued launch by launch -- with the default switches (the step as it was before graphs existed) and with the one-launch
 attention on (the very launches the graph holds) -- for the fp32 and the coded cache; every form is timed in turn within
 each of the --reps rounds, in one process; capture + instantiate time is reported apart.
+--beam-select: the A/B is what beam search does with a step's logits -- log-softmax, the logits processors, the score add and
+the top-k (generation._select_continuations) -- as the torch lines against ops.beam_select (csrc/beam_select.hip): those
+steps alone on [batch * beams, 50265] logits at length 31 with min_length active, no_repeat_ngram_size 0 and 3; then the whole
+generate() with the switch off and on, issued and with graph=True; and, once, the encoder pass alone.  Every form is timed
+in turn within each of the --reps rounds, in one process.
 
     python tools/decode_bench.py [--reps 7] [--out profiles/decode_step_ab.txt]
     python tools/decode_bench.py --fast-decode-attention [--out profiles/decode_attention_ab.txt]
     python tools/decode_bench.py --cache-codes [--out profiles/kv_codes_ab.txt]
     python tools/decode_bench.py --graph [--out profiles/graph_decode_ab.txt]
+    python tools/decode_bench.py --beam-select [--out profiles/beam_select_ab.txt]
 """
 import argparse
 import copy
@@ -236,6 +242,82 @@ def graph_ab(q, ids, mask, args):
     return lines
 
 
+def _timed(fn, unit=1e3):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    out = fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) * unit, out
+
+
+def beam_select_ab(q, ids, mask, args):
+    from outlier_suppression_amd.model import generation
+    dev = ids.device
+    bsz, nb, vocab, cur, max_length = args.batch, args.beams, q.config.vocab_size, 31, 62
+    keep = 2 * nb                                   # one eos id: generation._beam_search's keep
+    lines = [f"a beam step's continuations (log-softmax, logits processors, score add, top-{keep}), the torch lines of "
+             f"generation._select_continuations against ops.beam_select; logits [{bsz * nb}, {vocab}] fp32 (randn * 4), "
+             f"{bsz} x {nb} beams, length {cur}, min_length {max_length} active (one eos id banned), token history over 40 ids; "
+             f"every form timed in turn in each of {args.reps} rounds, one process; median [min, max]"]
+    print(lines[0], flush=True)
+    g = torch.Generator().manual_seed(0)
+    logits = (torch.randn(bsz * nb, vocab, generator=g) * 4).to(dev)
+    running = torch.randn(bsz, nb, generator=g).to(dev)
+    flat = torch.randint(3, 43, (bsz * nb, cur), generator=g).to(dev)
+    eos = torch.tensor([q.config.eos_token_id], device=dev)
+    with torch.no_grad():
+        forms = {}
+        for ngram in (0, 3):
+            procs = generation._processors(max_length, eos, ngram, None, None, max_length, dev)
+            plan = generation._BeamSelectPlan(procs, dev, nb, vocab, keep, max_length)
+            assert plan.reason is None, plan.reason
+            for label, p in (("torch lines", None), ("ops.beam_select", plan)):
+                forms[f"no_repeat_ngram_size {ngram}, {label}"] = (
+                    lambda procs=procs, p=p: generation._select_continuations(logits, flat, running, procs, bsz, nb, vocab, keep, p))
+        times = {label: [] for label in forms}
+        outs = {}
+        for r in range(args.reps + 3):              # three lead-in rounds
+            for label, fn in forms.items():
+                ms, outs[label] = _timed(fn)
+                if r >= 3:
+                    times[label].append(ms)
+        lines.append("steps a-c alone, ms:")
+        lines += [f"    {label:45s} {_stats(t)}" for label, t in times.items()]
+        for ngram in (0, 3):
+            a, b = outs[f"no_repeat_ngram_size {ngram}, torch lines"], outs[f"no_repeat_ngram_size {ngram}, ops.beam_select"]
+            lines.append(f"    no_repeat_ngram_size {ngram}: indices equal: {bool(torch.equal(a[1], b[1]))}, "
+                         f"max |value difference| {float((a[0] - b[0]).abs().max()):.3g}")
+        print("\n".join(lines[1:]), flush=True)
+
+        enc_ms = sorted(_timed(lambda: q.get_encoder()(ids, attention_mask=mask))[0] for _ in range(args.reps + 1))[:-1]
+        lines.append(f"encoder pass alone ({bsz} x {args.src}), ms: {_stats(enc_ms)}")
+        print(lines[-1], flush=True)
+
+        gen = [(f"no_repeat_ngram_size {ngram}, {'graph' if graph else 'issued'}, beam_select {'on' if on else 'off'}", ngram, graph, on)
+               for ngram in (0, 3) for graph in (False, True) for on in (False, True)]
+        times = {label: [] for label, *_ in gen}
+        tokens, selected = {}, {}
+        for r in range(args.reps + 1):              # the first round warms every form up
+            for label, ngram, graph, on in gen:
+                secs, tokens[label] = _timed(lambda: q.generate(ids, attention_mask=mask, max_length=max_length, num_beams=nb,
+                                                                min_length=max_length, no_repeat_ngram_size=ngram,
+                                                                graph=graph, beam_select=on), 1.0)
+                info = q.last_beam_select
+                selected[label] = (info.selected, info.eager)
+                if r:
+                    times[label].append(secs)
+        lines.append(f"generate(max_length={max_length}, num_beams={nb}, min_length={max_length}), s, wall time of the call "
+                     "(a graph form: capture included); (steps through the kernel, steps through torch):")
+        lines += [f"    {label:55s} {_stats(t)}   {selected[label]}" for label, t in times.items()]
+        for label, ngram, graph, on in gen:
+            if on:
+                off = label.replace("beam_select on", "beam_select off")
+                same = tokens[label].shape == tokens[off].shape and bool(torch.equal(tokens[label], tokens[off]))
+                lines.append(f"    {label}: tokens equal to beam_select off: {same}")
+        print("\n".join(lines[-len(gen) - len(gen) // 2 - 1:]), flush=True)
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=32)
@@ -247,9 +329,16 @@ def main():
     ap.add_argument("--fast-decode-attention", action="store_true")
     ap.add_argument("--cache-codes", action="store_true")
     ap.add_argument("--graph", action="store_true")
+    ap.add_argument("--beam-select", action="store_true")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     q, ids, mask = build(args.batch, args.src, args.layers)
+    if args.beam_select:
+        text = "\n".join(beam_select_ab(q, ids, mask, args))
+        if args.out:
+            with open(args.out, "w") as f:
+                f.write(text + "\n")
+        return
     if args.graph and not args.profile_steps:
         text = "\n".join(graph_ab(q, ids, mask, args))
         if args.out:
