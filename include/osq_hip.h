@@ -41,7 +41,7 @@ typedef void* osq_stream;
  *     Added within 10 (no existing signature changed): osq_quantize_codes, osq_dequantize_codes, osq_dequantize_codes_multi,
  *     osq_decode_attention_fake_quant, osq_fake_quant_kv_append_codes, osq_decode_attention_codes,
  *     osq_fake_quant_kv_append_at, osq_fake_quant_kv_append_codes_at, osq_decode_attention_fake_quant_at,
- *     osq_decode_attention_codes_at, osq_beam_select_workspace_bytes, osq_beam_select. */
+ *     osq_decode_attention_codes_at, osq_beam_select_workspace_bytes, osq_beam_select, osq_beam_advance. */
 #define OSQ_ABI_VERSION 10
 
 typedef enum osq_status {
@@ -918,6 +918,44 @@ int osq_beam_select(const float* logits, int64_t logits_stride, const float* run
                     int64_t seq_stride, int64_t cur, int64_t ngram, const int64_t* ban_ids, int64_t n_ban,
                     int64_t bsz, int64_t nb, int64_t vocab, int64_t keep, float* top_value, int64_t* top_index,
                     void* workspace, size_t workspace_bytes, osq_stream stream);
+
+/* ------------------------------------------------------------------ beam search (beam_advance.hip) */
+
+/* The bookkeeping of one beam-search step after the selection, at length cur with a prompt of one token: what
+ * model/generation.py::_advance_beams_torch computes from `beam = top_idx // vocab` to `go_on` -- which continuations
+ * finished, the nb that go on, the merge into the finished set, the cache rows of the kept beams, the early-stop heuristic
+ * and the stopping condition -- in two launches.
+ * In: top_value [bsz, keep] fp32 and top_index [bsz, keep] int64 (osq_beam_select's or torch.topk's outputs; an index
+ * outside [0, nb * vocab) is taken as the nearest beam: nothing outside the state is read), and the state: running
+ * [bsz, nb, max_length] int64, running_scores [bsz, nb] fp32, finished [bsz, nb, max_length] int64, scores [bsz, nb] fp32,
+ * finished_len [bsz, nb] int64, done [bsz, nb] bytes (0 / not 0), improvable [bsz] bytes; all dense.  eos_ids: n_eos <= 16
+ * int64 ids on the device, or NULL with n_eos = 0.
+ * early_stopping: 0 (False), 1 (True), 2 ("never").  len_div = (cur + 1 - 1) ** length_penalty and best_div =
+ * best_len ** length_penalty, computed by the host as the Python lines do and handed over as the doubles they are.
+ * reciprocal: when set, the division by those scalars is v * (float)(1.0 / div) -- the reciprocal taken in double and rounded
+ * to fp32 once: the words of torch's GPU kernel for a division by a host scalar, measured on MI355X; v * (1.0f / (float)div)
+ * is NOT that, e.g. for div = 7 ** 0.8 -- and when not set the correctly rounded v / (float)div (torch's CPU kernel).
+ * Out, all in buffers of their own (the gathers read the old state: no output may be its input; the host alternates between
+ * two sets): the seven state tensors; beam_idx [bsz * nb] int64, the cache row beam + b * nb of every kept beam; next_tokens
+ * [bsz * nb] int64 = running_out[:, :, cur]; go_on, one int32 word.  Written as 0 / 1: done_out, improvable_out, go_on.
+ * Arithmetic: the torch lines literally -- every fp32 operation rounded on its own, flags multiplied (float(false) * -1e9 is
+ * -0.0), the three += on the candidates' scores in the order of the source; hits = cur + 1 >= max_length, or the new token
+ * is one of eos_ids.  The two top-k follow osq_beam_select's order: larger value first, equal values by smaller index, NaN
+ * above every number.  Token rows are copied over all max_length positions.
+ * workspace: at least 4 * bsz bytes of device memory, 4-byte aligned, contents arbitrary; one per stream in flight.  One
+ * workgroup per batch row, then one workgroup for go_on; no workgroup waits for another; no host synchronisation, no
+ * allocation, nothing read from the host: legal inside a stream capture.
+ * OSQ_ERR_INVALID_ARGUMENT, nothing launched: keep > 64, nb > 64, nb > keep, n_eos > 16, max_length > 4096, cur < 1 or
+ * cur >= max_length, a non-positive extent, early_stopping outside 0..2, a null tensor, an output pointer equal to its input,
+ * a workspace that is too small. */
+int osq_beam_advance(const float* top_value, const int64_t* top_index, const int64_t* running, const float* running_scores,
+                     const int64_t* finished, const float* scores, const int64_t* finished_len, const uint8_t* done,
+                     const uint8_t* improvable, const int64_t* eos_ids, int64_t n_eos, int64_t bsz, int64_t nb, int64_t keep,
+                     int64_t vocab, int64_t max_length, int64_t cur, int early_stopping, double len_div, double best_div,
+                     int reciprocal, int64_t* running_out, float* running_scores_out, int64_t* finished_out,
+                     float* scores_out, int64_t* finished_len_out, uint8_t* done_out, uint8_t* improvable_out,
+                     int64_t* beam_idx, int64_t* next_tokens, int32_t* go_on, void* workspace, size_t workspace_bytes,
+                     osq_stream stream);
 
 /* ------------------------------------------------------------------ bf16 / fp16 only (lowp.hip) */
 

@@ -94,6 +94,22 @@ def set_beam_select(on=True):
     util_layernorm.BEAM_SELECT = bool(on)
 
 
+def set_beam_advance(on=True):
+    """generate()'s beam search advances its beams with ops.beam_advance -- the finished continuations, the beams that go on,
+    the merge into the finished set, the cache rows, the early-stop heuristic and the stopping word in one kernel call on two
+    alternating sets of state buffers (util_layernorm.BEAM_ADVANCE; csrc/beam_advance.hip; default OFF) -- instead of the
+    torch lines; a call it cannot take runs those.  OSQ_BEAM_ADVANCE=1 turns it on at load;
+    ``generate(..., beam_advance=True)`` asks for one call."""
+    from . import util_layernorm
+    util_layernorm.BEAM_ADVANCE = bool(on)
+
+
+def beam_advance_from_environment(environ=None):
+    """What OSQ_BEAM_ADVANCE asks for: unset, empty or "0" -> False, anything else -> True."""
+    import os
+    return (os.environ if environ is None else environ).get("OSQ_BEAM_ADVANCE", "") not in ("", "0")
+
+
 def beam_select_from_environment(environ=None):
     """What OSQ_BEAM_SELECT asks for: unset, empty or "0" -> False, anything else -> True."""
     import os
@@ -118,7 +134,8 @@ def reset_tier(_lib=None):
     one-launch LayerNorm site; OSQ_FAST_SOFTMAX=1 the one-launch attention-probabilities site and OSQ_FAST_DECODE_ATTENTION=1
     the one-launch attention of a cached decoding step (unset: off); OSQ_CACHE_CODES=1 KV caches as integer codes (unset: off);
     OSQ_GRAPH_DECODE=1 generate() replays a captured decoding step (unset: off); OSQ_BEAM_SELECT=1 beam search selects a step's
-    continuations with one kernel call (unset: off)."""
+    continuations with one kernel call (unset: off); OSQ_BEAM_ADVANCE=1 beam search advances its beams with one kernel call
+    (unset: off)."""
     import os
     width = int(os.environ.get("OSQ_STRICT_SIMD", "8"))
     strict = os.environ.get("OSQ_STRICT", "")
@@ -133,6 +150,7 @@ def reset_tier(_lib=None):
     set_cache_codes(cache_codes_from_environment())
     set_graph_decode(graph_decode_from_environment())
     set_beam_select(beam_select_from_environment())
+    set_beam_advance(beam_advance_from_environment())
 
 
 _apply_environment = reset_tier

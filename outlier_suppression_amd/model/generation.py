@@ -11,7 +11,10 @@ appended in one launch, a beam reorder rides in the next append); ``use_cache=Fa
 ``graph=True`` (or the package switch, set_graph_decode) replays a captured graph of the step from the third step on
 (model/graph_decode.py); ``model.last_decode_graph`` tells what happened.  ``beam_select=True`` (set_beam_select) hands a beam
 step's log-softmax, banned tokens, score add and top-k to one kernel call (ops.beam_select) where the step's processors are
-the no-repeat-ngram and min-length ones; ``model.last_beam_select`` tells how many steps took it.
+the no-repeat-ngram and min-length ones; ``model.last_beam_select`` tells how many steps took it.  ``beam_advance=True``
+(set_beam_advance) hands the bookkeeping after the selection -- which continuations finished, the beams that go on, the merge
+into the finished set, the early-stop heuristic -- to one kernel call (ops.beam_advance) on two alternating sets of state
+buffers; ``model.last_beam_advance`` tells how many steps took it.
 """
 import torch
 from torch import nn
@@ -129,8 +132,121 @@ def _select_continuations(logits, flat, running_scores, procs, bsz, nb, vocab, k
     return torch.topk(log_probs, k=keep)
 
 
+class BeamAdvanceInfo:
+    """What a generate() call did with its beam steps' bookkeeping: ``advanced`` steps through ops.beam_advance, ``eager``
+    steps through the torch lines, and, when none was advanced, the ``reason``."""
+
+    def __init__(self, reason=None):
+        self.advanced, self.eager, self.reason = 0, 0, reason
+
+    def __repr__(self):
+        return f"BeamAdvanceInfo(advanced={self.advanced}, eager={self.eager}, reason={self.reason!r})"
+
+
+# How ops.beam_advance divides by length ** length_penalty: as torch's GPU kernel divides by a host scalar, a multiplication
+# by float32(1 / div) with the reciprocal taken in double (tests/test_gpu_beam_advance.py compares the words with the torch
+# lines on the GPU under this flag; DESIGN.md, section 4).
+_ADVANCE_RECIPROCAL = True
+
+
+class _BeamState:
+    """The tensors a beam search carries from step to step.  ``buffers``: for the kernel path (``paired``), the two sets of
+    buffers a step alternates between -- ops.beam_advance reads one and writes the other."""
+    FIELDS = ("running", "running_scores", "finished", "scores", "finished_len", "done", "improvable")
+
+    def __init__(self, running, running_scores, finished, scores, finished_len, done, improvable):
+        self.running, self.running_scores, self.finished, self.scores = running, running_scores, finished, scores
+        self.finished_len, self.done, self.improvable = finished_len, done, improvable
+        self.buffers = None
+
+    @classmethod
+    def start(cls, bsz, nb, max_length, start, fill, dev):
+        running = torch.full((bsz, nb, max_length), fill, dtype=torch.long, device=dev)
+        running[:, :, 0] = start
+        finished = running.clone()
+        running_scores = torch.zeros((bsz, nb), dtype=torch.float, device=dev)
+        running_scores[:, 1:] = -1e9
+        scores = torch.full((bsz, nb), -1e9, dtype=torch.float, device=dev)
+        done = torch.zeros((bsz, nb), dtype=torch.bool, device=dev)
+        improvable = torch.ones((bsz, 1), dtype=torch.bool, device=dev)
+        finished_len = torch.zeros((bsz, nb), dtype=torch.long, device=dev)      # generated tokens of each finished beam
+        return cls(running, running_scores, finished, scores, finished_len, done, improvable)
+
+    def paired(self):
+        """This state in the first of two ops.BeamBuffers: (the current set, the one the next step writes)."""
+        from ..ops import BeamBuffers
+        bsz, nb, max_length = self.running.shape
+        self.buffers = [BeamBuffers(bsz, nb, max_length, self.running.device) for _ in range(2)]
+        for name in self.FIELDS:
+            getattr(self.buffers[0], name).copy_(getattr(self, name))
+        return self.buffers
+
+
+def _advance_why_not(device, nb, keep, max_length, eos):
+    """None when ops.beam_advance takes the steps of this call, else the reason the torch lines run."""
+    if device.type != "cuda":
+        return "the tensors are on the CPU"
+    if torch.is_grad_enabled():
+        return "autograd is on"
+    if keep > 64 or nb > 64 or not 2 <= max_length <= 4096:
+        return "the kernel takes keep <= 64, num_beams <= 64 and max_length in [2, 4096]"
+    if eos is not None and eos.numel() > 16:
+        return "more than 16 eos ids"
+    return None
+
+
+def _advance_beams_torch(state, top_lp, top_idx, cur, vocab, eos, top_mask, offsets, max_length, length_penalty, early_stopping,
+                         reorder=None, prompt=1):
+    """Steps c'-g of a beam step at length ``cur`` and the early-stop heuristic, as torch lines: from the top ``keep``
+    continuations (top_lp, top_idx [bsz, keep]) and the ``state`` to (the new state, beam_idx [bsz * nb] -- the cache rows
+    of the kept beams --, go_on, a 0-dim bool tensor).  ``reorder(beam_idx)`` is called at step g, where the cache follows
+    the kept beams."""
+    running, running_scores, finished, scores = state.running, state.running_scores, state.finished, state.scores
+    finished_len, done, improvable = state.finished_len, state.done, state.improvable
+    bsz, nb = running_scores.shape
+    keep = top_lp.shape[1]
+    dev = top_lp.device
+    beam = top_idx // vocab
+    top_seq = _gather(running, beam)
+    top_seq[:, :, cur] = top_idx % vocab
+    rows = beam + offsets
+    # d. which of them finished
+    hits = torch.full((bsz, keep), cur + 1 >= max_length, dtype=torch.bool, device=dev)
+    if eos is not None:
+        hits = hits | torch.isin(top_seq[:, :, cur], eos)
+    # e. the best num_beams unfinished continue
+    top_running_lp = top_lp + hits.to(torch.float32) * -1.0e9
+    nxt = torch.topk(top_running_lp, k=nb)[1]
+    running = _gather(top_seq, nxt)
+    running_scores = _gather(top_running_lp, nxt)
+    beam_idx = _gather(rows, nxt).view(-1)
+    # f. merge newly finished ones into the finished set
+    just = hits & top_mask[None, :]
+    cand = top_lp / ((cur + 1 - prompt) ** length_penalty)
+    full = torch.all(done, axis=-1, keepdims=True) & (early_stopping is True)
+    cand += full.to(torch.float32) * -1.0e9
+    cand += (~improvable).to(torch.float32) * -1.0e9
+    cand += (~just) * -1.0e9
+    merged = torch.topk(torch.cat((scores, cand), dim=1), k=nb)[1]
+    finished = _gather(torch.cat((finished, top_seq), dim=1), merged)
+    scores = _gather(torch.cat((scores, cand), dim=1), merged)
+    finished_len = _gather(torch.cat((finished_len, torch.full_like(top_idx, cur + 1 - prompt)), dim=1), merged)
+    done = _gather(torch.cat((done, just), dim=1), merged)
+    # g. next iteration: the cache follows the kept beams
+    if reorder is not None:
+        reorder(beam_idx)
+    cur += 1
+    # early-stop heuristic and stopping condition (transformers' _check_early_stop_heuristic / _has_unfinished)
+    best_len = (max_length - prompt) if (early_stopping == "never" and length_penalty > 0.0) else (cur - prompt)
+    best_running = running_scores[:, :1] / (best_len ** length_penalty)
+    worst_done = torch.where(done, torch.min(scores, dim=1, keepdim=True)[0], -1.0e9)
+    improvable = improvable & torch.any(best_running > worst_done, dim=-1, keepdim=True)
+    go_on = torch.any(improvable) & ~(torch.all(done) & (early_stopping is True)) & ~torch.all(hits)
+    return _BeamState(running, running_scores, finished, scores, finished_len, done, improvable), beam_idx, go_on
+
+
 def generate(model, input_ids, attention_mask=None, max_length=None, num_beams=None, use_cache=True, cache_codes=None,
-             graph=None, beam_select=None, **kwargs):
+             graph=None, beam_select=None, beam_advance=None, **kwargs):
     if kwargs.pop("synced_gpus", False):      # Seq2SeqTrainer's predict_with_generate passes synced_gpus=False
         raise NotImplementedError("generate(): synced_gpus=True is not supported")
     for name in _NOT_COVERED:
@@ -169,16 +285,21 @@ def generate(model, input_ids, attention_mask=None, max_length=None, num_beams=N
     model.last_decode_graph = info
     select = BeamSelectInfo(None if (util_layernorm.BEAM_SELECT if beam_select is None else beam_select) else "not asked for")
     model.last_beam_select = select
+    advance = BeamAdvanceInfo(None if (util_layernorm.BEAM_ADVANCE if beam_advance is None else beam_advance) else "not asked for")
+    model.last_beam_advance = advance
     if num_beams == 1:
         if select.reason is None:
             select.reason = "greedy decoding selects no beams"
+        if advance.reason is None:
+            advance.reason = "greedy decoding advances no beams"
         if n_return != 1:
             raise ValueError("greedy decoding returns one sequence per input (num_return_sequences must be 1)")
         return _checked(cache, _greedy(model, enc, attention_mask, start, pad, eos_t, procs, max_length, cache, stepper))
     if n_return > num_beams:
         raise ValueError("num_return_sequences must not exceed num_beams")
     return _checked(cache, _beam_search(model, enc, attention_mask, start, pad, eos_t, procs, max_length, num_beams, n_return,
-                                        get("length_penalty"), get("early_stopping"), cache, stepper, select))
+                                        get("length_penalty"), get("early_stopping"), cache, stepper, select,
+                                        advance))
 
 
 def _checked(cache, tokens):
@@ -218,7 +339,7 @@ def _gather(t, idx):
 
 
 def _beam_search(model, enc, attention_mask, start, pad, eos, procs, max_length, nb, n_return, length_penalty,
-                 early_stopping, cache, stepper=None, select=None):
+                 early_stopping, cache, stepper=None, select=None, advance=None):
     """transformers' vectorised beam search (GenerationMixin._beam_search, 5.x) with the prompt of one start token."""
     dev = enc.device
     bsz = enc.shape[0]
@@ -229,64 +350,69 @@ def _beam_search(model, enc, attention_mask, start, pad, eos, procs, max_length,
     keep = max(2, 1 + (eos.shape[0] if eos is not None else 0)) * nb
     top_mask = torch.cat((torch.ones(nb, dtype=torch.bool), torch.zeros(keep - nb, dtype=torch.bool))).to(dev)
     fill = (pad if pad else int(eos[0])) if eos is not None else -1
-    running = torch.full((bsz, nb, max_length), fill, dtype=torch.long, device=dev)
-    running[:, :, 0] = start
-    finished = running.clone()
-    running_scores = torch.zeros((bsz, nb), dtype=torch.float, device=dev)
-    running_scores[:, 1:] = -1e9
-    scores = torch.full((bsz, nb), -1e9, dtype=torch.float, device=dev)
-    done = torch.zeros((bsz, nb), dtype=torch.bool, device=dev)
-    improvable = torch.ones((bsz, 1), dtype=torch.bool, device=dev)
-    finished_len = torch.zeros((bsz, nb), dtype=torch.long, device=dev)      # generated tokens of each finished beam
+    state = _BeamState.start(bsz, nb, max_length, start, fill, dev)
     offsets = torch.arange(bsz, device=dev).view(-1, 1) * nb
     plan = None
     if select is not None and select.reason is None:
         plan = _BeamSelectPlan(procs, dev, nb, vocab, keep, max_length)
         select.reason = plan.reason
-    while True:
-        flat = running[:, :, :cur].reshape(bsz * nb, cur)
-        logits = _step_logits(model, flat, enc, attention_mask, cache, stepper).to(torch.float32)
-        top_lp, top_idx = _select_continuations(logits, flat, running_scores, procs, bsz, nb, vocab, keep, plan, select)
-        beam = top_idx // vocab
-        top_seq = _gather(running, beam)
-        top_seq[:, :, cur] = top_idx % vocab
-        rows = beam + offsets
-        # d. which of them finished
-        hits = torch.full((bsz, keep), cur + 1 >= max_length, dtype=torch.bool, device=dev)
-        if eos is not None:
-            hits = hits | torch.isin(top_seq[:, :, cur], eos)
-        # e. the best num_beams unfinished continue
-        top_running_lp = top_lp + hits.to(torch.float32) * -1.0e9
-        nxt = torch.topk(top_running_lp, k=nb)[1]
-        running = _gather(top_seq, nxt)
-        running_scores = _gather(top_running_lp, nxt)
-        beam_idx = _gather(rows, nxt).view(-1)
-        # f. merge newly finished ones into the finished set
-        just = hits & top_mask[None, :]
-        cand = top_lp / ((cur + 1 - prompt) ** length_penalty)
-        full = torch.all(done, axis=-1, keepdims=True) & (early_stopping is True)
-        cand += full.to(torch.float32) * -1.0e9
-        cand += (~improvable).to(torch.float32) * -1.0e9
-        cand += (~just) * -1.0e9
-        merged = torch.topk(torch.cat((scores, cand), dim=1), k=nb)[1]
-        finished = _gather(torch.cat((finished, top_seq), dim=1), merged)
-        scores = _gather(torch.cat((scores, cand), dim=1), merged)
-        finished_len = _gather(torch.cat((finished_len, torch.full_like(top_idx, cur + 1 - prompt)), dim=1), merged)
-        done = _gather(torch.cat((done, just), dim=1), merged)
-        # g. next iteration: the cache follows the kept beams
+    if advance is not None and advance.reason is None:
+        advance.reason = _advance_why_not(dev, nb, keep, max_length, eos)
+    if advance is not None and advance.reason is None:
+        return _beam_search_advanced(model, enc, attention_mask, eos, procs, max_length, nb, n_return, length_penalty,
+                                     early_stopping, cache, stepper, select, advance, state, plan, vocab, keep)
+
+    def reorder(beam_idx):
+        nonlocal cache
         if cache is not None:
             cache = model._reorder_cache(cache, beam_idx)
+    while True:
+        flat = state.running[:, :, :cur].reshape(bsz * nb, cur)
+        logits = _step_logits(model, flat, enc, attention_mask, cache, stepper).to(torch.float32)
+        top_lp, top_idx = _select_continuations(logits, flat, state.running_scores, procs, bsz, nb, vocab, keep, plan, select)
+        state, _, go_on = _advance_beams_torch(state, top_lp, top_idx, cur, vocab, eos, top_mask, offsets, max_length,
+                                               length_penalty, early_stopping, reorder, prompt)
         cur += 1
-        # early-stop heuristic and stopping condition (transformers' _check_early_stop_heuristic / _has_unfinished)
-        best_len = (max_length - prompt) if (early_stopping == "never" and length_penalty > 0.0) else (cur - prompt)
-        best_running = running_scores[:, :1] / (best_len ** length_penalty)
-        worst_done = torch.where(done, torch.min(scores, dim=1, keepdim=True)[0], -1.0e9)
-        improvable = improvable & torch.any(best_running > worst_done, dim=-1, keepdim=True)
-        go_on = torch.any(improvable) & ~(torch.all(done) & (early_stopping is True)) & ~torch.all(hits)
+        if advance is not None:
+            advance.eager += 1
         if not bool(go_on):
             break
+    return _beam_result(state, select, n_return, prompt)
+
+
+def _beam_search_advanced(model, enc, attention_mask, eos, procs, max_length, nb, n_return, length_penalty, early_stopping,
+                          cache, stepper, select, advance, state, plan, vocab, keep):
+    """The loop of _beam_search with the bookkeeping of every step as one call of ops.beam_advance: the state lives in two
+    sets of buffers, a step reads one and writes the other.  The token history goes to the selection as a row-strided view
+    of ``running``, the model is fed the kernel's next_tokens, the cache follows its beam_idx, and the go_on word is read
+    once per step (the one host sync of the torch lines)."""
+    from .. import ops
+    bsz = state.running.shape[0]
+    prompt = cur = 1
+    now, spare = state.paired()
+    eos_ids = None if eos is None else eos.to(torch.int64).reshape(-1).contiguous()
+    while True:
+        flat = now.running.view(bsz * nb, max_length)[:, :cur]
+        tokens = flat if cache is None or cur == prompt else now.next_tokens.view(-1, 1)
+        logits = _step_logits(model, tokens, enc, attention_mask, cache, stepper).to(torch.float32)
+        top_lp, top_idx = _select_continuations(logits, flat, now.running_scores, procs, bsz, nb, vocab, keep, plan, select)
+        best_len = (max_length - prompt) if (early_stopping == "never" and length_penalty > 0.0) else (cur + 1 - prompt)
+        ops.beam_advance(top_lp, top_idx, now, spare, cur, vocab, eos_ids, early_stopping,
+                         (cur + 1 - prompt) ** length_penalty, best_len ** length_penalty, _ADVANCE_RECIPROCAL)
+        now, spare = spare, now
+        if cache is not None:
+            cache = model._reorder_cache(cache, now.beam_idx)
+        cur += 1
+        advance.advanced += 1
+        if not int(now.go_on):
+            break
+    return _beam_result(now, select, n_return, prompt)
+
+
+def _beam_result(state, select, n_return, prompt):
+    bsz, _, max_length = state.finished.shape
     if select is not None and select.reason is None and select.selected == 0:
         select.reason = "a forced token fired on every step"
-    seqs = finished[:, :n_return].reshape(bsz * n_return, max_length)
-    length = prompt + int(finished_len[:, :n_return].max())
+    seqs = state.finished[:, :n_return].reshape(bsz * n_return, max_length)
+    length = prompt + int(state.finished_len[:, :n_return].max())
     return seqs[:, :length]

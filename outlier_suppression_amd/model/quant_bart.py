@@ -938,7 +938,9 @@ class QuantizedBartForConditionalGeneration(QuantizedModule):
         a decoding step into a hipGraph and replay it (None: the package switch, set_graph_decode; model/graph_decode.py);
         ``self.last_decode_graph`` then says what happened (captured, replays, reason).  ``beam_select``: beam search
         selects a step's continuations with one kernel call (None: the package switch, set_beam_select; ops.beam_select);
-        ``self.last_beam_select`` then says how many steps took it (selected, eager, reason)."""
+        ``self.last_beam_select`` then says how many steps took it (selected, eager, reason).  ``beam_advance``: beam search
+        advances its beams with one kernel call per step (None: the package switch, set_beam_advance; ops.beam_advance);
+        ``self.last_beam_advance`` then says how many steps took it (advanced, eager, reason)."""
         return generation.generate(self, input_ids, attention_mask=attention_mask, max_length=max_length,
                                    num_beams=num_beams, **kwargs)
 

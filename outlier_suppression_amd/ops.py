@@ -4,6 +4,7 @@ Everything here runs on the current HIP stream and never synchronises with the
 host.  No arithmetic on tensor data happens in Python; torch only allocates.
 """
 import ctypes
+import math
 import os
 from typing import NamedTuple
 
@@ -1883,3 +1884,88 @@ def beam_select(logits, running_scores, keep, seq=None, cur=0, ngram=0, ban_ids=
                              top_lp.data_ptr(), top_idx.data_ptr(), ws.data_ptr(), nbytes, _hip.raw_stream(logits.device))
     _hip.check(rc, "beam_select")
     return top_lp, top_idx
+
+
+class BeamBuffers:
+    """One set of beam-search state on a device, as osq_beam_advance reads and writes it: ``running`` /  ``finished``
+    [bsz, nb, max_length] int64, ``running_scores`` / ``scores`` [bsz, nb] fp32, ``finished_len`` [bsz, nb] int64, ``done``
+    [bsz, nb] bool, ``improvable`` [bsz, 1] bool; and what a step writes beside the state: ``beam_idx`` / ``next_tokens``
+    [bsz * nb] int64, the ``go_on`` int32 word and the call's ``workspace``."""
+    STATE = ("running", "running_scores", "finished", "scores", "finished_len", "done", "improvable")
+    _DTYPES = (torch.int64, torch.float32, torch.int64, torch.float32, torch.int64, torch.bool, torch.bool)
+
+    def __init__(self, bsz, nb, max_length, device):
+        shapes = ((bsz, nb, max_length), (bsz, nb), (bsz, nb, max_length), (bsz, nb), (bsz, nb), (bsz, nb), (bsz, 1))
+        for name, shape, dtype in zip(self.STATE, shapes, self._DTYPES):
+            setattr(self, name, torch.zeros(shape, dtype=dtype, device=device))
+        self.beam_idx = torch.zeros(bsz * nb, dtype=torch.int64, device=device)
+        self.next_tokens = torch.zeros(bsz * nb, dtype=torch.int64, device=device)
+        self.go_on = torch.zeros(1, dtype=torch.int32, device=device)
+        self.workspace = torch.zeros(4 * bsz, dtype=torch.uint8, device=device)
+
+
+def beam_advance(top_lp, top_idx, state, out, cur, vocab, eos_ids=None, early_stopping=False, len_div=1.0, best_div=1.0,
+                 reciprocal=True):
+    """The bookkeeping of one beam-search step after the selection (osq_beam_advance, csrc/beam_advance.hip): from ``top_lp``
+    / ``top_idx`` [bsz, keep] and the ``state`` at length ``cur`` (prompt of one token) into ``out`` -- the new state,
+    ``out.beam_idx`` (the cache rows of the kept beams), ``out.next_tokens`` (= out.running[:, :, cur]) and the ``out.go_on``
+    word -- what generation._advance_beams_torch computes, word for word, under a strict order of ties.
+
+    ``state`` / ``out``: two BeamBuffers (or objects with their attributes) of one geometry that share no memory: the gathers
+    read the old state.  eos_ids: None or up to 16 int64 ids on the device.  early_stopping: False, True or "never".
+    len_div / best_div: ``(cur + 1 - 1) ** length_penalty`` and ``best_len ** length_penalty`` as Python computes them.
+    reciprocal: divide as torch's GPU kernel does by a host scalar, v * float32(1 / div) with the reciprocal taken in
+    double; False: the correctly rounded v / float32(div), as torch's CPU kernel does.
+    Two launches on the current stream, no synchronisation, nothing allocated; returns ``out``."""
+    lib = _hip.load()
+    names = BeamBuffers.STATE
+    tensors = [getattr(state, n) for n in names]
+    outs = [getattr(out, n) for n in names]
+    extra = [out.beam_idx, out.next_tokens, out.go_on, out.workspace]
+    _hip.require_device(top_lp, top_idx, eos_ids, *tensors, *outs, *extra)
+    if top_lp.dim() != 2 or top_lp.shape != top_idx.shape or top_lp.dtype != torch.float32 or top_idx.dtype != torch.int64:
+        raise ValueError("beam_advance: top_lp must be fp32 [bsz, keep] and top_idx int64 [bsz, keep]")
+    bsz, keep = top_lp.shape
+    if state.running.dim() != 3 or state.running.shape[0] != bsz:
+        raise ValueError("beam_advance: running must be [bsz, nb, max_length]")
+    _, nb, max_length = state.running.shape
+    shapes = ((bsz, nb, max_length), (bsz, nb), (bsz, nb, max_length), (bsz, nb), (bsz, nb), (bsz, nb), (bsz,))
+    for group, what in ((tensors, "state"), (outs, "out")):
+        for name, t, shape, dtype in zip(names, group, shapes, BeamBuffers._DTYPES):
+            ok_dtype = t.dtype == dtype or (dtype == torch.bool and t.dtype == torch.uint8)
+            if not ok_dtype or t.numel() != math.prod(shape) or tuple(t.shape[:len(shape)]) != shape or not t.is_contiguous():
+                raise ValueError(f"beam_advance: {what}.{name} must be a contiguous {dtype} tensor of shape {shape}")
+    for name, t, n, dtype in (("beam_idx", out.beam_idx, bsz * nb, torch.int64), ("next_tokens", out.next_tokens, bsz * nb, torch.int64),
+                              ("go_on", out.go_on, 1, torch.int32)):
+        if t.dtype != dtype or t.numel() != n or not t.is_contiguous():
+            raise ValueError(f"beam_advance: out.{name} must be a contiguous {dtype} tensor of {n} elements")
+    if out.workspace.dtype != torch.uint8 or not out.workspace.is_contiguous():
+        raise ValueError("beam_advance: out.workspace must be a contiguous uint8 tensor")
+    device = top_lp.device
+    every = [top_lp, top_idx, *tensors, *outs, *extra] + ([] if eos_ids is None else [eos_ids])
+    if any(t.device != device for t in every):
+        raise ValueError("beam_advance: all tensors must be on one device")
+    reads = [top_lp, top_idx, *tensors] + ([] if eos_ids is None else [eos_ids])
+    writes = [*outs, *extra]
+    spans = lambda ts: [(t.data_ptr(), t.data_ptr() + t.numel() * t.element_size()) for t in ts if t.numel()]  # noqa: E731
+    w = spans(writes)
+    for i, (lo, hi) in enumerate(w):
+        if any(lo < h and l < hi for l, h in spans(reads) + w[:i]):
+            raise ValueError("beam_advance: an output shares memory with an input or another output (the gathers read the "
+                             "old state: state and out are two sets)")
+    n_eos = 0
+    if eos_ids is not None:
+        if eos_ids.dtype != torch.int64 or eos_ids.dim() != 1 or not eos_ids.is_contiguous():
+            raise ValueError("beam_advance: eos_ids must be a contiguous 1-d int64 tensor")
+        n_eos = eos_ids.numel()
+    if early_stopping not in (False, True, "never"):
+        raise ValueError('beam_advance: early_stopping is False, True or "never"')
+    mode = 2 if early_stopping == "never" else int(bool(early_stopping))
+    top_lp, top_idx = top_lp.contiguous(), top_idx.contiguous()
+    rc = lib.osq_beam_advance(top_lp.data_ptr(), top_idx.data_ptr(), *(t.data_ptr() for t in tensors),
+                              _hip.ptr(eos_ids) if n_eos else None, n_eos, bsz, nb, keep, int(vocab), max_length, int(cur), mode,
+                              float(len_div), float(best_div), int(bool(reciprocal)), *(t.data_ptr() for t in outs),
+                              out.beam_idx.data_ptr(), out.next_tokens.data_ptr(), out.go_on.data_ptr(),
+                              out.workspace.data_ptr(), out.workspace.numel(), _hip.raw_stream(device))
+    _hip.check(rc, "beam_advance")
+    return out

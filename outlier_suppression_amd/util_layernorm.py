@@ -53,6 +53,12 @@ compute the words of the static launches at that position.  A captured step alwa
 top-k to ``ops.beam_select`` (csrc/beam_select.hip) instead of the torch lines, on every step whose logits processors are the
 no-repeat-ngram and min-length ones; ties come out in a strict index order where torch.topk has none.
 ``outlier_suppression_amd.set_beam_select(True)`` / ``OSQ_BEAM_SELECT=1`` / ``generate(..., beam_select=True)`` turn it on.
+
+``BEAM_ADVANCE`` (default OFF): beam search hands the bookkeeping after the selection -- which continuations finished, the
+beams that go on, the merge into the finished set, the cache rows, the early-stop heuristic and the stopping word -- to
+``ops.beam_advance`` (csrc/beam_advance.hip) instead of about forty torch launches; the state then lives in two alternating
+sets of device buffers.  Word-equal to the torch lines where those have no ties; ties come out in the strict index order.
+``outlier_suppression_amd.set_beam_advance(True)`` / ``OSQ_BEAM_ADVANCE=1`` / ``generate(..., beam_advance=True)`` turn it on.
 """
 import torch
 import torch.nn.functional as F
@@ -70,6 +76,7 @@ FUSE_DECODE_ATTENTION = False   # a cached decoding step's attention after the a
 FUSE_KV_APPEND = True    # incremental decoding: a step's q / k / v sites + KV-cache append (+ beam reorder) as one launch (bit-identical)
 GRAPH_DECODE = False     # generate(): capture a cached decoding step into a graph and replay it (set_graph_decode / OSQ_GRAPH_DECODE=1 / generate(graph=True))
 BEAM_SELECT = False      # generate(): a beam step's log-softmax + processors + score add + top-k as one kernel call (tolerance-equal; set_beam_select / OSQ_BEAM_SELECT=1 / generate(beam_select=True))
+BEAM_ADVANCE = False     # generate(): a beam step's bookkeeping after the selection as one kernel call on alternating state buffers (set_beam_advance / OSQ_BEAM_ADVANCE=1 / generate(beam_advance=True))
 CACHE_CODES = False      # incremental decoding: new KV caches hold integer codes, one byte per element (same words read back; set_cache_codes / OSQ_CACHE_CODES=1)
 
 

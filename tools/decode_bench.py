@@ -21,12 +21,17 @@ the top-k (generation._select_continuations) -- as the torch lines against ops.b
 steps alone on [batch * beams, 50265] logits at length 31 with min_length active, no_repeat_ngram_size 0 and 3; then the whole
 generate() with the switch off and on, issued and with graph=True; and, once, the encoder pass alone.  Every form is timed
 in turn within each of the --reps rounds, in one process.
+--beam-advance: the A/B is the bookkeeping of a beam step after the selection (generation._advance_beams_torch) as the torch
+lines against ops.beam_advance (csrc/beam_advance.hip): that step alone on the state and the top_lp / top_idx recorded at
+length 31 of a generate() call; then generate(graph=True, beam_select=True) and the same issued launch by launch, with the
+switch off and on.  Every form is timed in turn within each of the --reps rounds, in one process.
 
     python tools/decode_bench.py [--reps 7] [--out profiles/decode_step_ab.txt]
     python tools/decode_bench.py --fast-decode-attention [--out profiles/decode_attention_ab.txt]
     python tools/decode_bench.py --cache-codes [--out profiles/kv_codes_ab.txt]
     python tools/decode_bench.py --graph [--out profiles/graph_decode_ab.txt]
     python tools/decode_bench.py --beam-select [--out profiles/beam_select_ab.txt]
+    python tools/decode_bench.py --beam-advance [--out profiles/beam_advance_ab.txt]
 """
 import argparse
 import copy
@@ -318,6 +323,96 @@ def beam_select_ab(q, ids, mask, args):
     return lines
 
 
+def beam_advance_ab(q, ids, mask, args):
+    from outlier_suppression_amd import ops
+    from outlier_suppression_amd.model import generation
+    dev = ids.device
+    bsz, nb, vocab, at, max_length = args.batch, args.beams, q.config.vocab_size, 31, 62
+    keep = 2 * nb                                   # one eos id: generation._beam_search's keep
+    lines = [f"a beam step's bookkeeping after the selection (finished continuations, the {nb} beams that go on, the merge "
+             f"into the finished set, cache rows, early-stop heuristic, go_on), the torch lines of "
+             f"generation._advance_beams_torch against ops.beam_advance; {bsz} x {nb} beams, top-{keep}, max_length "
+             f"{max_length}, the state and top_lp / top_idx recorded at length {at} of generate(min_length={max_length}); every "
+             f"form timed in turn in each of {args.reps} rounds, one process; median [min, max]"]
+    print(lines[0], flush=True)
+    recorded = {}
+    real = generation._advance_beams_torch
+
+    def recording(state, top_lp, top_idx, cur, *rest, **kw):
+        if cur == at:
+            recorded["args"] = (state, top_lp.clone(), top_idx.clone(), cur) + tuple(rest[:-2])   # without reorder, prompt
+        return real(state, top_lp, top_idx, cur, *rest, **kw)
+    generation._advance_beams_torch = recording
+    try:
+        with torch.no_grad():
+            q.generate(ids, attention_mask=mask, max_length=at + 2, num_beams=nb, min_length=max_length, beam_select=True)
+    finally:
+        generation._advance_beams_torch = real
+    state, top_lp, top_idx, cur, _, eos, top_mask, offsets, _, length_penalty, early_stopping = recorded["args"]
+    # the state as the max_length-62 call holds it: token rows of 62 positions
+    wide = {}
+    for name in generation._BeamState.FIELDS:
+        t = getattr(state, name)
+        if t.dim() == 3:
+            t = torch.cat((t, t[:, :, -1:].expand(-1, -1, max_length - t.shape[2])), dim=2).contiguous()
+        wide[name] = t
+    state = generation._BeamState(**wide)
+    now, spare = state.paired()
+    eos_ids = eos.to(torch.int64).reshape(-1).contiguous()
+    best_len = (max_length - 1) if (early_stopping == "never" and length_penalty > 0.0) else cur
+    len_div, best_div = cur ** length_penalty, best_len ** length_penalty
+    with torch.no_grad():
+        def torch_lines():
+            new, beam_idx, go_on = real(state, top_lp, top_idx, cur, vocab, eos, top_mask, offsets, max_length, length_penalty,
+                                        early_stopping)
+            return new, beam_idx, bool(go_on)
+
+        def kernel():
+            ops.beam_advance(top_lp, top_idx, now, spare, cur, vocab, eos_ids, early_stopping, len_div, best_div,
+                             generation._ADVANCE_RECIPROCAL)
+            return spare, spare.beam_idx, bool(int(spare.go_on))
+        forms = {"torch lines (with the read of go_on)": torch_lines, "ops.beam_advance (with the read of go_on)": kernel}
+        times = {label: [] for label in forms}
+        outs = {}
+        for r in range(args.reps + 3):              # three lead-in rounds
+            for label, fn in forms.items():
+                ms, outs[label] = _timed(fn)
+                if r >= 3:
+                    times[label].append(ms)
+        lines.append("the bookkeeping alone, ms:")
+        lines += [f"    {label:45s} {_stats(t)}" for label, t in times.items()]
+        (a, a_idx, a_go), (b, b_idx, b_go) = outs.values()
+        same = all(torch.equal(getattr(a, n).reshape(-1), getattr(b, n).reshape(-1))
+                   for n in ("running", "running_scores", "scores", "done", "improvable"))
+        lines.append(f"    running, running_scores, scores, done, improvable, beam_idx and go_on equal: "
+                     f"{bool(same and torch.equal(a_idx, b_idx) and a_go == b_go)}")
+        print("\n".join(lines[1:]), flush=True)
+
+        gen = [(f"{'graph' if graph else 'issued'}, beam_advance {'on' if on else 'off'}", graph, on)
+               for graph in (True, False) for on in (False, True)]
+        times = {label: [] for label, *_ in gen}
+        tokens, advanced = {}, {}
+        for r in range(args.reps + 1):              # the first round warms every form up
+            for label, graph, on in gen:
+                secs, tokens[label] = _timed(lambda: q.generate(ids, attention_mask=mask, max_length=max_length, num_beams=nb,
+                                                                min_length=max_length, graph=graph, beam_select=True,
+                                                                beam_advance=on), 1.0)
+                info = q.last_beam_advance
+                advanced[label] = (info.advanced, info.eager)
+                if r:
+                    times[label].append(secs)
+        lines.append(f"generate(max_length={max_length}, num_beams={nb}, min_length={max_length}, beam_select=True), s, wall time "
+                     "of the call (a graph form: capture included); (steps through the kernel, steps through torch):")
+        lines += [f"    {label:35s} {_stats(t)}   {advanced[label]}" for label, t in times.items()]
+        for label, graph, on in gen:
+            if on:
+                off = label.replace("beam_advance on", "beam_advance off")
+                same = tokens[label].shape == tokens[off].shape and bool(torch.equal(tokens[label], tokens[off]))
+                lines.append(f"    {label}: tokens equal to beam_advance off: {same}")
+        print("\n".join(lines[-len(gen) - len(gen) // 2 - 1:]), flush=True)
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=32)
@@ -330,9 +425,16 @@ def main():
     ap.add_argument("--cache-codes", action="store_true")
     ap.add_argument("--graph", action="store_true")
     ap.add_argument("--beam-select", action="store_true")
+    ap.add_argument("--beam-advance", action="store_true")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     q, ids, mask = build(args.batch, args.src, args.layers)
+    if args.beam_advance:
+        text = "\n".join(beam_advance_ab(q, ids, mask, args))
+        if args.out:
+            with open(args.out, "w") as f:
+                f.write(text + "\n")
+        return
     if args.beam_select:
         text = "\n".join(beam_select_ab(q, ids, mask, args))
         if args.out:
