@@ -41,7 +41,8 @@ typedef void* osq_stream;
  *     Added within 10 (no existing signature changed): osq_quantize_codes, osq_dequantize_codes, osq_dequantize_codes_multi,
  *     osq_decode_attention_fake_quant, osq_fake_quant_kv_append_codes, osq_decode_attention_codes,
  *     osq_fake_quant_kv_append_at, osq_fake_quant_kv_append_codes_at, osq_decode_attention_fake_quant_at,
- *     osq_decode_attention_codes_at, osq_beam_select_workspace_bytes, osq_beam_select, osq_beam_advance. */
+ *     osq_decode_attention_codes_at, osq_beam_select_workspace_bytes, osq_beam_select, osq_beam_advance,
+ *     osq_beam_select_at, osq_beam_advance_at. */
 #define OSQ_ABI_VERSION 10
 
 typedef enum osq_status {
@@ -919,6 +920,22 @@ int osq_beam_select(const float* logits, int64_t logits_stride, const float* run
                     int64_t bsz, int64_t nb, int64_t vocab, int64_t keep, float* top_value, int64_t* top_index,
                     void* workspace, size_t workspace_bytes, osq_stream stream);
 
+/* osq_beam_select with the position read by the launch: cur = *cur_dev + cur_add (cur_dev one device int32; a captured
+ * decoding step passes the KV cache's position word, which after the decoder's increment is the step's cur), so that one
+ * captured graph serves every step.  cur_max (0..4096) is the largest position the launch may meet; the host checks go by
+ * it: with ngram > 0 and cur_max >= ngram, seq rows hold at least cur_max tokens (seq_stride >= cur_max).  ban_ids apply
+ * while cur < ban_below -- the min-length rule, which the host decides for the static form -- and to no step otherwise.
+ * The same three kernels; only the second reads the word, once per workgroup.  For every cur in [0, cur_max], top_value
+ * and top_index are word-equal to osq_beam_select called with that cur, with ban_ids (cur < ban_below) or with n_ban = 0.
+ * A cur outside [0, cur_max]: every word of top_value is the canonical quiet NaN, every top_index is 0, and seq is not
+ * read -- no address is formed from a refused position.  Limits, workspace and OSQ_ERR_INVALID_ARGUMENT as for the static
+ * form, with cur_max in the place of cur; also a null cur_dev.  No host synchronisation, no allocation. */
+int osq_beam_select_at(const float* logits, int64_t logits_stride, const float* running_scores, const int64_t* seq,
+                       int64_t seq_stride, const int32_t* cur_dev, int64_t cur_add, int64_t cur_max, int64_t ngram,
+                       const int64_t* ban_ids, int64_t n_ban, int64_t ban_below, int64_t bsz, int64_t nb, int64_t vocab,
+                       int64_t keep, float* top_value, int64_t* top_index, void* workspace, size_t workspace_bytes,
+                       osq_stream stream);
+
 /* ------------------------------------------------------------------ beam search (beam_advance.hip) */
 
 /* The bookkeeping of one beam-search step after the selection, at length cur with a prompt of one token: what
@@ -956,6 +973,25 @@ int osq_beam_advance(const float* top_value, const int64_t* top_index, const int
                      float* scores_out, int64_t* finished_len_out, uint8_t* done_out, uint8_t* improvable_out,
                      int64_t* beam_idx, int64_t* next_tokens, int32_t* go_on, void* workspace, size_t workspace_bytes,
                      osq_stream stream);
+
+/* osq_beam_advance with the position read by the two launches: cur = *cur_dev + cur_add (cur_dev one device int32), and
+ * the two factors read from tables: len_table and best_table hold max_length device floats each, entry c the word the
+ * static form derives on the host from len_div / best_div at cur == c -- (float)(1.0 / div) with `reciprocal` set (the
+ * kernel multiplies), (float)div without (it divides).  The HOST fills them from the Python expressions of the search; the
+ * launch reads the word and re-derives no power.  Entries below 1 are not read.
+ * For every cur in [1, max_length), the seven state tensors, beam_idx, next_tokens and go_on are word-equal to
+ * osq_beam_advance called with that cur and those divisors.  A cur outside that range: go_on receives -1 and nothing else
+ * is written; no address is formed from a refused position.  Limits, workspace and OSQ_ERR_INVALID_ARGUMENT as for the
+ * static form (but for cur); also a null cur_dev or table.  No host synchronisation, no allocation. */
+int osq_beam_advance_at(const float* top_value, const int64_t* top_index, const int64_t* running,
+                        const float* running_scores, const int64_t* finished, const float* scores,
+                        const int64_t* finished_len, const uint8_t* done, const uint8_t* improvable, const int64_t* eos_ids,
+                        int64_t n_eos, int64_t bsz, int64_t nb, int64_t keep, int64_t vocab, int64_t max_length,
+                        const int32_t* cur_dev, int64_t cur_add, int early_stopping, const float* len_table,
+                        const float* best_table, int reciprocal, int64_t* running_out, float* running_scores_out,
+                        int64_t* finished_out, float* scores_out, int64_t* finished_len_out, uint8_t* done_out,
+                        uint8_t* improvable_out, int64_t* beam_idx, int64_t* next_tokens, int32_t* go_on, void* workspace,
+                        size_t workspace_bytes, osq_stream stream);
 
 /* ------------------------------------------------------------------ bf16 / fp16 only (lowp.hip) */
 

@@ -104,6 +104,24 @@ def set_beam_advance(on=True):
     util_layernorm.BEAM_ADVANCE = bool(on)
 
 
+def set_beam_graph(on=True):
+    """generate()'s beam search captures a whole step -- the token copy, the model step, ops.beam_select_at,
+    ops.beam_advance_at and the copy of the cache's row index -- into one hipGraph per direction of the alternating buffers
+    and replays it: per token the host issues one replay and reads one word (util_layernorm.BEAM_GRAPH;
+    model/graph_decode.py, BeamStepGraphs; default OFF).  For its call it implies set_graph_decode, set_beam_select and
+    set_beam_advance; a call it cannot take -- one of those says why, one of them is passed as False, greedy decoding --
+    decodes as without it (``model.last_beam_graph.reason``).  OSQ_BEAM_GRAPH=1 turns it on at load;
+    ``generate(..., beam_graph=True)`` asks for one call."""
+    from . import util_layernorm
+    util_layernorm.BEAM_GRAPH = bool(on)
+
+
+def beam_graph_from_environment(environ=None):
+    """What OSQ_BEAM_GRAPH asks for: unset, empty or "0" -> False, anything else -> True."""
+    import os
+    return (os.environ if environ is None else environ).get("OSQ_BEAM_GRAPH", "") not in ("", "0")
+
+
 def beam_advance_from_environment(environ=None):
     """What OSQ_BEAM_ADVANCE asks for: unset, empty or "0" -> False, anything else -> True."""
     import os
@@ -135,7 +153,7 @@ def reset_tier(_lib=None):
     the one-launch attention of a cached decoding step (unset: off); OSQ_CACHE_CODES=1 KV caches as integer codes (unset: off);
     OSQ_GRAPH_DECODE=1 generate() replays a captured decoding step (unset: off); OSQ_BEAM_SELECT=1 beam search selects a step's
     continuations with one kernel call (unset: off); OSQ_BEAM_ADVANCE=1 beam search advances its beams with one kernel call
-    (unset: off)."""
+    (unset: off); OSQ_BEAM_GRAPH=1 beam search replays a whole step, bookkeeping included, as one captured graph (unset: off)."""
     import os
     width = int(os.environ.get("OSQ_STRICT_SIMD", "8"))
     strict = os.environ.get("OSQ_STRICT", "")
@@ -151,6 +169,7 @@ def reset_tier(_lib=None):
     set_graph_decode(graph_decode_from_environment())
     set_beam_select(beam_select_from_environment())
     set_beam_advance(beam_advance_from_environment())
+    set_beam_graph(beam_graph_from_environment())
 
 
 _apply_environment = reset_tier

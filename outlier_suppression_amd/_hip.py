@@ -175,6 +175,9 @@ SIGNATURES = {
     "osq_beam_select": (_I, [_P, _L, _P, _P, _L, _L, _L, _P, _L, _L, _L, _L, _L, _P, _P, _P, ctypes.c_size_t, _P]),
     "osq_beam_advance": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _L, _L, _L, _L, _L, _L, _I, _D, _D, _I,
                               _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, ctypes.c_size_t, _P]),
+    "osq_beam_select_at": (_I, [_P, _L, _P, _P, _L, _P, _L, _L, _L, _P, _L, _L, _L, _L, _L, _L, _P, _P, _P, ctypes.c_size_t, _P]),
+    "osq_beam_advance_at": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _L, _L, _L, _L, _L, _P, _L, _I, _P, _P, _I,
+                                 _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, ctypes.c_size_t, _P]),
     "osq_fake_quant_chain_lowp": (_I, [_I, _P, _P, _L, _P, _P, _I, _I, _I, _P]),
     "osq_fake_quant_chain_backward_lowp": (_I, [_I, _P, _P, _P, _L, _P, _P, _I, _I, _I, _P]),
     "osq_fake_quant_per_tensor_widen": (_I, [_I, _P, _P, _L, _P, _P, _I, _I, _F, _I, _I, _P]),

@@ -27,6 +27,11 @@
 // among themselves by index -- osq_beam_select's rule.  An element's rank is the number of elements that precede it, counted
 // in LDS: nb + keep <= 128 elements.
 //
+// osq_beam_advance_at is the same two launches with the position read by them: cur = *cur_dev + cur_add, one scalar read per
+// workgroup, and the two factors read from tables indexed by cur -- entry c the word the static form derives on the host for
+// that cur, filled by the host: the launch re-derives no power.  A cur outside [1, max_length) is refused before any address
+// is formed from it: the first launch writes nothing, the second writes go_on = -1.
+//
 // Token rows are copied over all max_length positions, lanes striding over positions; position cur of a continuation is its
 // new token.  The gathers read the old state: no output may be its input.
 #include <hip/hip_runtime.h>
@@ -64,7 +69,18 @@ struct BeamAdvanceArgs {
     int64_t vocab;
     int bsz, nb, keep, max_length, cur, n_eos, early_stopping, reciprocal;
     float len_scale, best_scale;     // reciprocal: float(1.0 / div), the multiplier; else float(div), the divisor
+    // osq_beam_advance_at: cur = *cur_dev + cur_add, read by the launch; the scales are len_table[cur] / best_table[cur]
+    const int32_t* cur_dev;          // nullptr: the static form, cur and the scales above
+    int cur_add;
+    const float* len_table;          // [max_length]
+    const float* best_table;         // [max_length]
 };
+
+// The position of an _at launch, or -1 when it is refused (outside [1, max_length)): workgroup-uniform, in an SGPR.
+__device__ __forceinline__ int beam_advance_position(const BeamAdvanceArgs& a) {
+    const long long at = static_cast<long long>(__builtin_amdgcn_readfirstlane(*a.cur_dev)) + a.cur_add;
+    return at >= 1 && at < a.max_length ? static_cast<int>(at) : -1;
+}
 
 // a before b in the order of the top-k: (value a at index ia, value b at index ib), ia != ib
 __device__ __forceinline__ bool beam_before(float a, int ia, float b, int ib) {
@@ -88,7 +104,15 @@ __global__ __launch_bounds__(kBaThreads) void beam_advance_kernel(BeamAdvanceArg
     __shared__ unsigned char s_just[kBaMaxKeep];
     const int lane = threadIdx.x;
     const int64_t b = blockIdx.x;
-    const int nb = a.nb, keep = a.keep, cur = a.cur, L = a.max_length;
+    const int nb = a.nb, keep = a.keep, L = a.max_length;
+    int cur = a.cur;
+    float len_scale = a.len_scale, best_scale = a.best_scale;
+    if (a.cur_dev) {
+        cur = beam_advance_position(a);
+        if (cur < 0) return;                                    // refused: nothing written (beam_go_on_kernel says so)
+        len_scale = a.len_table[cur];
+        best_scale = a.best_table[cur];
+    }
 
     if (lane < a.n_eos) s_eos[lane] = a.eos_ids[lane];
     const bool was_done = lane < nb ? a.done[b * nb + lane] != 0 : true;
@@ -112,7 +136,7 @@ __global__ __launch_bounds__(kBaThreads) void beam_advance_kernel(BeamAdvanceArg
         s_token[lane] = token;
         s_just[lane] = just;
         s_trl[lane] = v + (hit ? 1.0f : 0.0f) * -1.0e9f;
-        float cand = beam_divide(v, a.len_scale, a.reciprocal);
+        float cand = beam_divide(v, len_scale, a.reciprocal);
         cand += (full ? 1.0f : 0.0f) * -1.0e9f;
         cand += (was_improvable ? 0.0f : 1.0f) * -1.0e9f;
         cand += (just ? 0.0f : 1.0f) * -1.0e9f;
@@ -156,7 +180,7 @@ __global__ __launch_bounds__(kBaThreads) void beam_advance_kernel(BeamAdvanceArg
     __syncthreads();
 
     // ---- the early-stop heuristic
-    const float best_running = beam_divide(s_trl[s_nxt[0]], a.best_scale, a.reciprocal);
+    const float best_running = beam_divide(s_trl[s_nxt[0]], best_scale, a.reciprocal);
     float worst = s_scores_out[0];                              // torch.min: a NaN wins
     for (int j = 1; j < nb; ++j) {
         const float v = s_scores_out[j];
@@ -190,6 +214,10 @@ __global__ __launch_bounds__(kBaThreads) void beam_advance_kernel(BeamAdvanceArg
 }
 
 __global__ __launch_bounds__(kBaThreads) void beam_go_on_kernel(BeamAdvanceArgs a) {
+    if (a.cur_dev && beam_advance_position(a) < 0) {            // refused: the row flags are not this step's
+        if (threadIdx.x == 0) *a.go_on = -1;
+        return;
+    }
     unsigned int any = 0u, all = kBaAllDone | kBaAllHits;
     for (int b = threadIdx.x; b < a.bsz; b += kBaThreads) {
         const unsigned int f = a.row_flags[b];
@@ -205,21 +233,24 @@ __global__ __launch_bounds__(kBaThreads) void beam_go_on_kernel(BeamAdvanceArgs 
 
 using namespace osq;
 
-extern "C" int osq_beam_advance(const float* top_value, const int64_t* top_index, const int64_t* running,
-                                const float* running_scores, const int64_t* finished, const float* scores,
-                                const int64_t* finished_len, const uint8_t* done, const uint8_t* improvable,
-                                const int64_t* eos_ids, int64_t n_eos, int64_t bsz, int64_t nb, int64_t keep, int64_t vocab,
-                                int64_t max_length, int64_t cur, int early_stopping, double len_div, double best_div,
-                                int reciprocal, int64_t* running_out, float* running_scores_out, int64_t* finished_out,
-                                float* scores_out, int64_t* finished_len_out, uint8_t* done_out, uint8_t* improvable_out,
-                                int64_t* beam_idx, int64_t* next_tokens, int32_t* go_on, void* workspace,
-                                size_t workspace_bytes, osq_stream stream) {
+// Both entry points.  cur_dev == nullptr: the static form at `cur` with the two divisors; else the position is the device word
+// and the factors come from the tables.
+static int beam_advance_launch(const float* top_value, const int64_t* top_index, const int64_t* running,
+                               const float* running_scores, const int64_t* finished, const float* scores,
+                               const int64_t* finished_len, const uint8_t* done, const uint8_t* improvable,
+                               const int64_t* eos_ids, int64_t n_eos, int64_t bsz, int64_t nb, int64_t keep, int64_t vocab,
+                               int64_t max_length, int64_t cur, const int32_t* cur_dev, int64_t cur_add, int early_stopping,
+                               double len_div, double best_div, const float* len_table, const float* best_table,
+                               int reciprocal, int64_t* running_out, float* running_scores_out, int64_t* finished_out,
+                               float* scores_out, int64_t* finished_len_out, uint8_t* done_out, uint8_t* improvable_out,
+                               int64_t* beam_idx, int64_t* next_tokens, int32_t* go_on, void* workspace,
+                               size_t workspace_bytes, osq_stream stream) {
     OSQ_REQUIRE(bsz >= 1 && nb >= 1 && keep >= 1 && vocab >= 1 && max_length >= 1, "beam_advance: a non-positive extent");
     OSQ_REQUIRE(keep <= kBaMaxKeep && nb <= kBaMaxBeams, "beam_advance: keep and nb go up to 64");
     OSQ_REQUIRE(nb <= keep, "beam_advance: nb exceeds keep");
     OSQ_REQUIRE(n_eos >= 0 && n_eos <= kBaMaxEos, "beam_advance: n_eos outside [0, 16]");
     OSQ_REQUIRE(max_length <= kBaMaxLength, "beam_advance: max_length above 4096");
-    OSQ_REQUIRE(cur >= 1 && cur < max_length, "beam_advance: cur outside [1, max_length)");
+    OSQ_REQUIRE(cur_dev || (cur >= 1 && cur < max_length), "beam_advance: cur outside [1, max_length)");
     OSQ_REQUIRE(early_stopping >= 0 && early_stopping <= 2, "beam_advance: early_stopping is 0, 1 or 2");
     OSQ_REQUIRE(bsz <= INT32_MAX / (kBaMaxBeams * 2), "beam_advance: too many batch rows");
     OSQ_REQUIRE(top_value && top_index && running && running_scores && finished && scores && finished_len && done &&
@@ -237,10 +268,46 @@ extern "C" int osq_beam_advance(const float* top_value, const int64_t* top_index
                       improvable_out, beam_idx, next_tokens, go_on, static_cast<unsigned int*>(workspace), vocab,
                       static_cast<int>(bsz), static_cast<int>(nb), static_cast<int>(keep), static_cast<int>(max_length),
                       static_cast<int>(cur), static_cast<int>(n_eos), early_stopping, reciprocal != 0,
-                      static_cast<float>(reciprocal ? 1.0 / len_div : len_div),
-                      static_cast<float>(reciprocal ? 1.0 / best_div : best_div)};
+                      cur_dev ? 0.f : static_cast<float>(reciprocal ? 1.0 / len_div : len_div),
+                      cur_dev ? 0.f : static_cast<float>(reciprocal ? 1.0 / best_div : best_div),
+                      cur_dev, static_cast<int>(cur_add), len_table, best_table};
     hipStream_t st = static_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(beam_advance_kernel, dim3(static_cast<unsigned>(bsz)), dim3(kBaThreads), 0, st, a);
     hipLaunchKernelGGL(beam_go_on_kernel, dim3(1), dim3(kBaThreads), 0, st, a);
-    return check_launch("beam_advance");
+    return check_launch(cur_dev ? "beam_advance_at" : "beam_advance");
+}
+
+extern "C" int osq_beam_advance(const float* top_value, const int64_t* top_index, const int64_t* running,
+                                const float* running_scores, const int64_t* finished, const float* scores,
+                                const int64_t* finished_len, const uint8_t* done, const uint8_t* improvable,
+                                const int64_t* eos_ids, int64_t n_eos, int64_t bsz, int64_t nb, int64_t keep, int64_t vocab,
+                                int64_t max_length, int64_t cur, int early_stopping, double len_div, double best_div,
+                                int reciprocal, int64_t* running_out, float* running_scores_out, int64_t* finished_out,
+                                float* scores_out, int64_t* finished_len_out, uint8_t* done_out, uint8_t* improvable_out,
+                                int64_t* beam_idx, int64_t* next_tokens, int32_t* go_on, void* workspace,
+                                size_t workspace_bytes, osq_stream stream) {
+    return beam_advance_launch(top_value, top_index, running, running_scores, finished, scores, finished_len, done, improvable,
+                               eos_ids, n_eos, bsz, nb, keep, vocab, max_length, cur, nullptr, 0, early_stopping, len_div,
+                               best_div, nullptr, nullptr, reciprocal, running_out, running_scores_out, finished_out,
+                               scores_out, finished_len_out, done_out, improvable_out, beam_idx, next_tokens, go_on,
+                               workspace, workspace_bytes, stream);
+}
+
+extern "C" int osq_beam_advance_at(const float* top_value, const int64_t* top_index, const int64_t* running,
+                                   const float* running_scores, const int64_t* finished, const float* scores,
+                                   const int64_t* finished_len, const uint8_t* done, const uint8_t* improvable,
+                                   const int64_t* eos_ids, int64_t n_eos, int64_t bsz, int64_t nb, int64_t keep,
+                                   int64_t vocab, int64_t max_length, const int32_t* cur_dev, int64_t cur_add,
+                                   int early_stopping, const float* len_table, const float* best_table, int reciprocal,
+                                   int64_t* running_out, float* running_scores_out, int64_t* finished_out, float* scores_out,
+                                   int64_t* finished_len_out, uint8_t* done_out, uint8_t* improvable_out, int64_t* beam_idx,
+                                   int64_t* next_tokens, int32_t* go_on, void* workspace, size_t workspace_bytes,
+                                   osq_stream stream) {
+    OSQ_REQUIRE(cur_dev && len_table && best_table, "beam_advance_at: null position word or table");
+    OSQ_REQUIRE(cur_add >= INT32_MIN && cur_add <= INT32_MAX, "beam_advance_at: cur_add does not fit 32 bits");
+    return beam_advance_launch(top_value, top_index, running, running_scores, finished, scores, finished_len, done, improvable,
+                               eos_ids, n_eos, bsz, nb, keep, vocab, max_length, 0, cur_dev, cur_add, early_stopping, 1.0, 1.0,
+                               len_table, best_table, reciprocal, running_out, running_scores_out, finished_out, scores_out,
+                               finished_len_out, done_out, improvable_out, beam_idx, next_tokens, go_on, workspace,
+                               workspace_bytes, stream);
 }

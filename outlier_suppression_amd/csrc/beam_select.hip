@@ -22,6 +22,12 @@
 // runs as the flat index does.  Key 0 is no value's (-inf has 0x007fffff): it marks a taken or absent candidate.
 // A value is never -0.0 ((x - m) - L is +0.0 where it vanishes, and a + (-a) is +0.0), so equal values have equal keys.
 //
+// osq_beam_select_at is the same three launches with the position read by the second: cur = *cur_dev + cur_add, one scalar
+// read per workgroup of beam_chunk_kernel (the only kernel that uses the position), so that a captured graph of the call
+// serves every step.  ban_ids then apply while cur < ban_below, the min-length rule the host decides for the static form.
+// A cur outside [0, cur_max] is refused before any address is formed from it: every candidate of the row becomes (NaN, token
+// 0), so the merge writes the canonical NaN and index 0 everywhere, and seq is not read.
+//
 // Summation order, fixed by (vocab) alone -- not by the row's alignment or place, bsz or nb; no float atomics: thread t of a
 // chunk's workgroup adds exp of elements t, t + 256, ... in order, wave_sum_f32, then (w0 + w1) + (w2 + w3); the row sum is
 // sum_c s_c * exp(m_c - m) in chunk order.  Elements are loaded one 32-bit word per lane (a row of an odd vocab is only
@@ -55,6 +61,9 @@ struct BeamArgs {
     int64_t* top_index;        // [bsz, keep]
     int64_t logits_stride, seq_stride;
     int nb, vocab, keep, chunks, cur, ngram, n_ban;
+    // osq_beam_select_at: cur = *cur_dev + cur_add, read by the launch; outside [0, cur_max] -> NaN candidates, seq not read
+    const int32_t* cur_dev;    // nullptr: the static form, cur above
+    int cur_add, cur_max, ban_below;
 };
 
 __device__ __forceinline__ unsigned int beam_key(float v) { return v != v ? 0xffffffffu : ordered_bits(v); }
@@ -129,18 +138,29 @@ __global__ __launch_bounds__(kBsThreads) void beam_chunk_kernel(BeamArgs a) {
         v[j] = i < len ? x[i] : 0.f;
     }
 
+    int cur = a.cur, n_ban = a.n_ban;
+    if (a.cur_dev) {                                                // workgroup-uniform: the position is a device word, read once into an SGPR
+        const long long at = static_cast<long long>(__builtin_amdgcn_readfirstlane(*a.cur_dev)) + a.cur_add;
+        if (at < 0 || at > a.cur_max) {                             // refused: NaN candidates with token 0, nothing else read
+            if (threadIdx.x < a.keep) a.cands[static_cast<int64_t>(blockIdx.x) * a.keep + threadIdx.x] = BeamCand{0xffffffffu, 0};
+            return;
+        }
+        cur = static_cast<int>(at);
+        if (cur >= a.ban_below) n_ban = 0;
+    }
+
     // ---- the chunk's banned tokens
     if (threadIdx.x < kBsChunk / 32) s_ban[threadIdx.x] = 0u;
     __syncthreads();
-    if (threadIdx.x < a.n_ban) {
+    if (threadIdx.x < n_ban) {
         const int64_t t = a.ban_ids[threadIdx.x] - c0;
         if (t >= 0 && t < len) atomicOr(&s_ban[t >> 5], 1u << (t & 31));
     }
     const int n = a.ngram;
-    if (n > 0 && a.cur >= n) {                                      // window i bans its last token when it starts with the suffix
+    if (n > 0 && cur >= n) {                                      // window i bans its last token when it starts with the suffix
         const int64_t* s = a.seq + row * a.seq_stride;
-        const int64_t* suffix = s + (a.cur - n + 1);
-        for (int i = threadIdx.x; i <= a.cur - n; i += kBsThreads) {
+        const int64_t* suffix = s + (cur - n + 1);
+        for (int i = threadIdx.x; i <= cur - n; i += kBsThreads) {
             bool same = true;
             for (int k = 0; k < n - 1 && same; ++k) same = s[i + k] == suffix[k];
             const int64_t t = s[i + n - 1] - c0;
@@ -238,10 +258,13 @@ extern "C" size_t osq_beam_select_workspace_bytes(int64_t bsz, int64_t nb, int64
     return beam_workspace_bytes(bsz, nb, vocab, keep);
 }
 
-extern "C" int osq_beam_select(const float* logits, int64_t logits_stride, const float* running_scores, const int64_t* seq,
-                               int64_t seq_stride, int64_t cur, int64_t ngram, const int64_t* ban_ids, int64_t n_ban,
-                               int64_t bsz, int64_t nb, int64_t vocab, int64_t keep, float* top_value, int64_t* top_index,
-                               void* workspace, size_t workspace_bytes, osq_stream stream) {
+// Both entry points.  cur_dev == nullptr: the static form at `cur`; else the position is the device word and `cur` is cur_max,
+// the largest position the launch may meet: the host checks go by it.
+static int beam_select_launch(const float* logits, int64_t logits_stride, const float* running_scores, const int64_t* seq,
+                              int64_t seq_stride, int64_t cur, const int32_t* cur_dev, int64_t cur_add, int64_t ban_below,
+                              int64_t ngram, const int64_t* ban_ids, int64_t n_ban, int64_t bsz, int64_t nb, int64_t vocab,
+                              int64_t keep, float* top_value, int64_t* top_index, void* workspace, size_t workspace_bytes,
+                              osq_stream stream) {
     OSQ_REQUIRE(bsz >= 0 && nb >= 1 && vocab >= 1 && keep >= 1, "beam_select: bad shape");
     OSQ_REQUIRE(keep <= kBsMaxKeep && nb <= kBsMaxBeams, "beam_select: keep and nb go up to 64");
     OSQ_REQUIRE(keep <= vocab, "beam_select: keep exceeds vocab");
@@ -264,11 +287,32 @@ extern "C" int osq_beam_select(const float* logits, int64_t logits_stride, const
     BeamArgs a{logits, running_scores, seq, ban_ids, partials, reinterpret_cast<BeamCand*>(partials + rows * chunks),
                top_value, top_index, logits_stride, seq_stride, static_cast<int>(nb), static_cast<int>(vocab),
                static_cast<int>(keep), static_cast<int>(chunks), static_cast<int>(cur),
-               static_cast<int>(ngram > kBsMaxCur ? kBsMaxCur + 1 : ngram), static_cast<int>(n_ban)};
+               static_cast<int>(ngram > kBsMaxCur ? kBsMaxCur + 1 : ngram), static_cast<int>(n_ban),
+               cur_dev, static_cast<int>(cur_add), static_cast<int>(cur),
+               static_cast<int>(ban_below < 0 ? 0 : (ban_below > kBsMaxCur ? kBsMaxCur + 1 : ban_below))};
     hipStream_t st = static_cast<hipStream_t>(stream);
     const dim3 grid(static_cast<unsigned>(rows * chunks));
     hipLaunchKernelGGL(beam_partials_kernel, grid, dim3(kBsThreads), 0, st, a);
     hipLaunchKernelGGL(beam_chunk_kernel, grid, dim3(kBsThreads), 0, st, a);
     hipLaunchKernelGGL(beam_merge_kernel, dim3(static_cast<unsigned>(bsz)), dim3(kBsThreads), 0, st, a);
-    return check_launch("beam_select");
+    return check_launch(cur_dev ? "beam_select_at" : "beam_select");
+}
+
+extern "C" int osq_beam_select(const float* logits, int64_t logits_stride, const float* running_scores, const int64_t* seq,
+                               int64_t seq_stride, int64_t cur, int64_t ngram, const int64_t* ban_ids, int64_t n_ban,
+                               int64_t bsz, int64_t nb, int64_t vocab, int64_t keep, float* top_value, int64_t* top_index,
+                               void* workspace, size_t workspace_bytes, osq_stream stream) {
+    return beam_select_launch(logits, logits_stride, running_scores, seq, seq_stride, cur, nullptr, 0, 0, ngram, ban_ids, n_ban,
+                              bsz, nb, vocab, keep, top_value, top_index, workspace, workspace_bytes, stream);
+}
+
+extern "C" int osq_beam_select_at(const float* logits, int64_t logits_stride, const float* running_scores, const int64_t* seq,
+                                  int64_t seq_stride, const int32_t* cur_dev, int64_t cur_add, int64_t cur_max, int64_t ngram,
+                                  const int64_t* ban_ids, int64_t n_ban, int64_t ban_below, int64_t bsz, int64_t nb,
+                                  int64_t vocab, int64_t keep, float* top_value, int64_t* top_index, void* workspace,
+                                  size_t workspace_bytes, osq_stream stream) {
+    OSQ_REQUIRE(cur_dev, "beam_select_at: null position word");
+    OSQ_REQUIRE(cur_add >= INT32_MIN && cur_add <= INT32_MAX, "beam_select_at: cur_add does not fit 32 bits");
+    return beam_select_launch(logits, logits_stride, running_scores, seq, seq_stride, cur_max, cur_dev, cur_add, ban_below, ngram,
+                              ban_ids, n_ban, bsz, nb, vocab, keep, top_value, top_index, workspace, workspace_bytes, stream);
 }

@@ -14,7 +14,10 @@ step's log-softmax, banned tokens, score add and top-k to one kernel call (ops.b
 the no-repeat-ngram and min-length ones; ``model.last_beam_select`` tells how many steps took it.  ``beam_advance=True``
 (set_beam_advance) hands the bookkeeping after the selection -- which continuations finished, the beams that go on, the merge
 into the finished set, the early-stop heuristic -- to one kernel call (ops.beam_advance) on two alternating sets of state
-buffers; ``model.last_beam_advance`` tells how many steps took it.
+buffers; ``model.last_beam_advance`` tells how many steps took it.  ``beam_graph=True`` (set_beam_graph) asks for all three
+and captures the whole step -- token copy, model, selection, bookkeeping, the cache's row index -- into one graph per
+direction of the alternating buffers (graph_decode.BeamStepGraphs): a token costs the host one replay and one read of the
+stopping word; ``model.last_beam_graph`` tells what happened.
 """
 import torch
 from torch import nn
@@ -246,7 +249,7 @@ def _advance_beams_torch(state, top_lp, top_idx, cur, vocab, eos, top_mask, offs
 
 
 def generate(model, input_ids, attention_mask=None, max_length=None, num_beams=None, use_cache=True, cache_codes=None,
-             graph=None, beam_select=None, beam_advance=None, **kwargs):
+             graph=None, beam_select=None, beam_advance=None, beam_graph=None, **kwargs):
     if kwargs.pop("synced_gpus", False):      # Seq2SeqTrainer's predict_with_generate passes synced_gpus=False
         raise NotImplementedError("generate(): synced_gpus=True is not supported")
     for name in _NOT_COVERED:
@@ -273,8 +276,17 @@ def generate(model, input_ids, attention_mask=None, max_length=None, num_beams=N
     from .quant_bart import QuantizedBartCache
     codes = util_layernorm.CACHE_CODES if cache_codes is None else bool(cache_codes)
     cache = QuantizedBartCache(n_layers, capacity=max_length, codes=codes) if use_cache else None
-    # a captured decoding step (model/graph_decode.py), where asked for and possible; else the steps are issued as ever
     from . import graph_decode
+    # a whole beam step as one captured graph: it implies the three switches below for this call, where nothing -- known
+    # before the first step -- stands against it; else the call decodes as without it
+    whole = graph_decode.BeamGraphInfo(None if (util_layernorm.BEAM_GRAPH if beam_graph is None else beam_graph) else "not asked for")
+    model.last_beam_graph = whole
+    if whole.reason is None:
+        whole.reason = _beam_graph_why_not(model, enc.device, use_cache, max_length, num_beams, eos_t, procs,
+                                           {"graph": graph, "beam_select": beam_select, "beam_advance": beam_advance})
+        if whole.reason is None:
+            graph = beam_select = beam_advance = True
+    # a captured decoding step (model/graph_decode.py), where asked for and possible; else the steps are issued as ever
     stepper = None
     if util_layernorm.GRAPH_DECODE if graph is None else graph:
         info = graph_decode.DecodeGraphInfo(graph_decode.why_not(model, enc.device, use_cache, max_length))
@@ -299,7 +311,27 @@ def generate(model, input_ids, attention_mask=None, max_length=None, num_beams=N
         raise ValueError("num_return_sequences must not exceed num_beams")
     return _checked(cache, _beam_search(model, enc, attention_mask, start, pad, eos_t, procs, max_length, num_beams, n_return,
                                         get("length_penalty"), get("early_stopping"), cache, stepper, select,
-                                        advance))
+                                        advance, whole if whole.reason is None else None))
+
+
+def _beam_keep(eos, nb):
+    """How many continuations of a batch row a beam step keeps: room for every beam to end on each eos id and go on."""
+    return max(2, 1 + (eos.shape[0] if eos is not None else 0)) * nb
+
+
+def _beam_graph_why_not(model, device, use_cache, max_length, nb, eos, procs, given):
+    """None when a generate() call can capture its beam steps whole, else the reason it decodes as without ``beam_graph``:
+    one of the three switches it implies was passed as False, decoding is greedy, or one of them would give a reason."""
+    from . import graph_decode
+    for name, value in given.items():
+        if value is not None and not value:
+            return f"{name}=False was passed"
+    if nb == 1:
+        return "greedy decoding has no beam step (beam_select at one beam is not argmax of the raw logits under ties)"
+    vocab, keep = model.config.vocab_size, _beam_keep(eos, nb)
+    return (graph_decode.why_not(model, device, use_cache, max_length)
+            or _BeamSelectPlan(procs, device, nb, vocab, keep, max_length).reason
+            or _advance_why_not(device, nb, keep, max_length, eos))
 
 
 def _checked(cache, tokens):
@@ -339,7 +371,7 @@ def _gather(t, idx):
 
 
 def _beam_search(model, enc, attention_mask, start, pad, eos, procs, max_length, nb, n_return, length_penalty,
-                 early_stopping, cache, stepper=None, select=None, advance=None):
+                 early_stopping, cache, stepper=None, select=None, advance=None, whole=None):
     """transformers' vectorised beam search (GenerationMixin._beam_search, 5.x) with the prompt of one start token."""
     dev = enc.device
     bsz = enc.shape[0]
@@ -347,7 +379,7 @@ def _beam_search(model, enc, attention_mask, start, pad, eos, procs, max_length,
     attention_mask = attention_mask.repeat_interleave(nb, dim=0)
     vocab = model.config.vocab_size
     prompt = cur = 1
-    keep = max(2, 1 + (eos.shape[0] if eos is not None else 0)) * nb
+    keep = _beam_keep(eos, nb)
     top_mask = torch.cat((torch.ones(nb, dtype=torch.bool), torch.zeros(keep - nb, dtype=torch.bool))).to(dev)
     fill = (pad if pad else int(eos[0])) if eos is not None else -1
     state = _BeamState.start(bsz, nb, max_length, start, fill, dev)
@@ -358,10 +390,11 @@ def _beam_search(model, enc, attention_mask, start, pad, eos, procs, max_length,
         select.reason = plan.reason
     if advance is not None and advance.reason is None:
         advance.reason = _advance_why_not(dev, nb, keep, max_length, eos)
+    if whole is not None and (select.reason or advance.reason):      # generate() asked the same questions before the first step
+        whole.reason, whole = select.reason or advance.reason, None
     if advance is not None and advance.reason is None:
         return _beam_search_advanced(model, enc, attention_mask, eos, procs, max_length, nb, n_return, length_penalty,
-                                     early_stopping, cache, stepper, select, advance, state, plan, vocab, keep)
-
+                                     early_stopping, cache, stepper, select, advance, state, plan, vocab, keep, whole)
     def reorder(beam_idx):
         nonlocal cache
         if cache is not None:
@@ -381,20 +414,47 @@ def _beam_search(model, enc, attention_mask, start, pad, eos, procs, max_length,
 
 
 def _beam_search_advanced(model, enc, attention_mask, eos, procs, max_length, nb, n_return, length_penalty, early_stopping,
-                          cache, stepper, select, advance, state, plan, vocab, keep):
+                          cache, stepper, select, advance, state, plan, vocab, keep, whole=None):
     """The loop of _beam_search with the bookkeeping of every step as one call of ops.beam_advance: the state lives in two
     sets of buffers, a step reads one and writes the other.  The token history goes to the selection as a row-strided view
     of ``running``, the model is fed the kernel's next_tokens, the cache follows its beam_idx, and the go_on word is read
-    once per step (the one host sync of the torch lines)."""
+    once per step (the one host sync of the torch lines).
+
+    ``whole`` (a graph_decode.BeamGraphInfo; generate(beam_graph=True)): from the third step on a step is one replay of a
+    captured graph that holds all of the above (graph_decode.BeamStepGraphs) -- but a step on which a forced token fires,
+    which is issued launch by launch on the capture stream and takes the lines below."""
     from .. import ops
+    from . import graph_decode
     bsz = state.running.shape[0]
     prompt = cur = 1
-    now, spare = state.paired()
+    now, spare = sets = state.paired()
     eos_ids = None if eos is None else eos.to(torch.int64).reshape(-1).contiguous()
+    graphs = None
     while True:
+        if whole is not None and graphs is None and cur == prompt + 2:
+            if stepper is None or stepper.decoder is None:          # the cache the first step left does not fit
+                whole.reason, whole = stepper.info.reason if stepper is not None else "no captured step", None
+            else:
+                graphs = graph_decode.BeamStepGraphs(stepper.decoder, whole, sets, plan, keep, vocab, eos_ids, early_stopping,
+                                                     length_penalty, _ADVANCE_RECIPROCAL)
+        if graphs is not None and cur not in plan.forced_at:
+            now, spare = graphs.step(0 if now is sets[0] else 1), now
+            cur += 1
+            select.selected += 1
+            advance.advanced += 1
+            go_on = int(now.go_on)
+            if go_on < 0:
+                raise RuntimeError(f"generate(): a captured beam step met the position {cur - 1}, outside [1, {max_length})")
+            if not go_on:
+                break
+            continue
         flat = now.running.view(bsz * nb, max_length)[:, :cur]
         tokens = flat if cache is None or cur == prompt else now.next_tokens.view(-1, 1)
-        logits = _step_logits(model, tokens, enc, attention_mask, cache, stepper).to(torch.float32)
+        if graphs is not None:
+            logits = stepper.decoder.issue(tokens, attention_mask).to(torch.float32)
+            whole.issued += 1
+        else:
+            logits = _step_logits(model, tokens, enc, attention_mask, cache, stepper).to(torch.float32)
         top_lp, top_idx = _select_continuations(logits, flat, now.running_scores, procs, bsz, nb, vocab, keep, plan, select)
         best_len = (max_length - prompt) if (early_stopping == "never" and length_penalty > 0.0) else (cur + 1 - prompt)
         ops.beam_advance(top_lp, top_idx, now, spare, cur, vocab, eos_ids, early_stopping,
@@ -406,6 +466,8 @@ def _beam_search_advanced(model, enc, attention_mask, eos, procs, max_length, nb
         advance.advanced += 1
         if not int(now.go_on):
             break
+    if whole is not None and whole.captured == 0:
+        whole.reason = "the search ended before a step could be captured"
     return _beam_result(now, select, n_return, prompt)
 
 

@@ -16,8 +16,16 @@ Which graph a step needs goes by what the step does to the cache: appending in p
 a beam reorder pending, copying the kept prefix from the current buffers into their partners through the row index, A -> B
 or B -> A (beam search: two graphs, replayed alternately).  Inputs are static buffers filled before a replay: the last token,
 the cache's row index (QuantizedBartCache.reorder) and the encoder mask; the logits are the graph's own output tensor, valid
-until its next replay.  Beam bookkeeping and logits processors stay outside.  The graphs live as long as the GraphDecoder:
-one generate() call.
+until its next replay.  Beam bookkeeping and logits processors stay outside these graphs.  The graphs live as long as the
+GraphDecoder: one generate() call.
+
+A whole beam-search step (BeamStepGraphs; generate(beam_graph=True)) goes one further: the selection and the bookkeeping
+read the position from the same device word -- after the decoder's increment it is the step's length ``cur`` -- through
+ops.beam_select_at / ops.beam_advance_at, so the captured chain is: the copy of the current beam set's next_tokens into the
+token buffer, the model step, the selection on the graph's own logits, the bookkeeping from the current set of state
+buffers into the other, the copy of the new beam_idx into the cache's row index.  Two graphs again, cache A -> B with beam
+set 0 -> 1 and the reverse; per token the host does the cache's bookkeeping, one replay and one read of go_on.  A step on
+which a forced token fires is issued launch by launch on the capture stream (GraphDecoder.issue), as step 1 is.
 
 The words are those of issuing the same steps one by one with the one-launch attention on (util_layernorm.
 FUSE_DECODE_ATTENTION): a captured step always uses it, cross-attention included, whatever the switch says.
@@ -123,26 +131,43 @@ class GraphDecoder:
         assert cache is self.cache
         return logits[:, -1, :]
 
-    def step(self, tokens, attention_mask=None):
+    def check_room(self):
         cache = self.cache
         if not cache.positioned():
             raise RuntimeError("GraphDecoder: the cache left device-position mode (it was read with a reorder pending)")
         if cache.get_seq_length() + 1 > cache.capacity:
             raise RuntimeError(f"GraphDecoder: the cache is full ({cache.capacity} positions)")
+
+    def _feed(self, tokens, attention_mask):
+        self.check_room()
         self.tokens.copy_(tokens)
         if attention_mask is not None and attention_mask is not self._mask_given:      # another mask than the one held
             self.mask.copy_(attention_mask)
             self._mask_given = attention_mask
+
+    def _issued(self):
+        """The step issued launch by launch on the capture stream, not captured; the current stream waits for it."""
+        current = torch.cuda.current_stream(self.enc.device)
+        self.stream.wait_stream(current)
+        with torch.cuda.stream(self.stream):
+            logits = self._issue()
+        current.wait_stream(self.stream)
+        logits.record_stream(current)
+        return logits
+
+    def issue(self, tokens, attention_mask=None):
+        """A step that is not to be captured (a forced token fires on it): its logits, issued as the second step is."""
+        self._feed(tokens, attention_mask)
+        self.warm = True
+        return self._issued()
+
+    def step(self, tokens, attention_mask=None):
+        cache = self.cache
+        self._feed(tokens, attention_mask)
         if not self.warm:
             # issued, not captured: whatever a stream allocates on first use (workspaces) exists before a capture on it
-            current = torch.cuda.current_stream(self.enc.device)
-            self.stream.wait_stream(current)
-            with torch.cuda.stream(self.stream):
-                logits = self._issue()
-            current.wait_stream(self.stream)
-            logits.record_stream(current)
             self.warm = True
-            return logits
+            return self._issued()
         # the graph this step needs: in place, or moving from the current buffers into their partners
         key = (cache.reorder_pending(), cache._k[0].data_ptr())
         entry = self.graphs.get(key)
@@ -159,6 +184,78 @@ class GraphDecoder:
         entry[0].replay()
         self.info.replays += 1
         return entry[1]
+
+
+class BeamGraphInfo:
+    """What a generate() call did with ``beam_graph``: ``captured`` whole-step graphs, ``replays`` of them, steps ``issued``
+    launch by launch because a forced token fired on them, and, when the call decoded as without the switch, the
+    ``reason``.  ``capture_seconds``: host time spent capturing and instantiating."""
+
+    def __init__(self, reason=None):
+        self.captured, self.replays, self.issued, self.reason, self.capture_seconds = 0, 0, 0, reason, 0.0
+
+    def __repr__(self):
+        return (f"BeamGraphInfo(captured={self.captured}, replays={self.replays}, issued={self.issued}, "
+                f"reason={self.reason!r})")
+
+
+class BeamStepGraphs:
+    """Whole beam-search steps of one generate() call as captured graphs, over a warm GraphDecoder and the two
+    ops.BeamBuffers ``sets`` of the search.  ``step(which)`` advances from ``sets[which]`` into the other set -- token copy,
+    model step, selection, bookkeeping, the cache's row index -- by one replay; the caller reads the new set's go_on."""
+
+    def __init__(self, decoder, info, sets, plan, keep, vocab, eos_ids, early_stopping, length_penalty, reciprocal):
+        from .. import ops
+        self.decoder, self.info, self.sets, self.plan = decoder, info, sets, plan
+        self.keep, self.vocab, self.eos_ids, self.early_stopping, self.reciprocal = keep, vocab, eos_ids, early_stopping, reciprocal
+        bsz, nb, self.max_length = sets[0].running.shape
+        dev = sets[0].running.device
+        self.top_lp = torch.empty((bsz, keep), dtype=torch.float32, device=dev)
+        self.top_idx = torch.empty((bsz, keep), dtype=torch.int64, device=dev)
+        self.workspace = torch.empty(ops.beam_select_workspace_bytes(bsz, nb, vocab, keep), dtype=torch.uint8, device=dev)
+        # the divisors of every step, from the search's own Python expressions: a launch reads its step's words
+        self.len_table, self.best_table = ops.beam_div_tables(self.max_length, length_penalty, early_stopping, reciprocal, dev)
+        self.graphs = {}
+
+    def _chain(self, now, spare):
+        """One step's launches, in order, on the current (capturing) stream."""
+        from .. import ops
+        decoder, cache, plan = self.decoder, self.decoder.cache, self.plan
+        decoder.tokens.copy_(now.next_tokens.view(-1, 1))
+        logits = decoder._issue().to(torch.float32)
+        cur = cache.position()                      # after the decoder's increment: the length of the history, this step's cur
+        rows = now.running.shape[0] * now.running.shape[1]
+        ops.beam_select_at(logits, now.running_scores, self.keep, cur, 0, self.max_length,
+                           seq=now.running.view(rows, self.max_length), ngram=plan.ngram, ban_ids=plan.eos,
+                           ban_below=plan.min_length, top_lp=self.top_lp, top_idx=self.top_idx, workspace=self.workspace)
+        ops.beam_advance_at(self.top_lp, self.top_idx, now, spare, cur, 0, self.vocab, self.len_table, self.best_table,
+                            self.eos_ids, self.early_stopping, self.reciprocal)
+        cache.reorder(spare.beam_idx)               # the copy into the static row index; pending, on the host side
+        return logits
+
+    def step(self, which):
+        decoder, cache = self.decoder, self.decoder.cache
+        decoder.check_room()
+        now, spare = self.sets[which], self.sets[1 - which]
+        key = (which, cache.reorder_pending(), cache._k[0].data_ptr())
+        entry = self.graphs.get(key)
+        if entry is None:
+            t0 = time.perf_counter()
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph, stream=decoder.stream):
+                logits = self._chain(now, spare)    # recorded, not run; the cache's host side of the step is now done
+            entry = self.graphs[key] = (graph, logits)
+            self.info.captured += 1
+            self.info.capture_seconds += time.perf_counter() - t0
+            decoder.info.captured += 1
+            decoder.info.capture_seconds += time.perf_counter() - t0
+        else:
+            cache.stepped()
+            cache.reorder_carried()
+        entry[0].replay()
+        self.info.replays += 1
+        decoder.info.replays += 1
+        return spare
 
 
 class GenerateStepper:

@@ -435,6 +435,11 @@ class QuantizedBartCache:
             else:
                 self.commit_at(i, *self._spare[i])
 
+    def reorder_carried(self):
+        """A captured step was replayed whose graph also carried the copy of the new row index into the static buffer
+        (what ``reorder`` launches): the reorder is pending, on the host side.  No launch."""
+        self._rows = [self._rows_buf] * len(self._k)
+
     def record_at(self, i, name, params):
         """The record pair of a coded tensor for a device-position append (None: an fp32 tensor).  Such a step cannot demote:
         parameters that differ from those of the first append are an error."""
@@ -940,7 +945,10 @@ class QuantizedBartForConditionalGeneration(QuantizedModule):
         selects a step's continuations with one kernel call (None: the package switch, set_beam_select; ops.beam_select);
         ``self.last_beam_select`` then says how many steps took it (selected, eager, reason).  ``beam_advance``: beam search
         advances its beams with one kernel call per step (None: the package switch, set_beam_advance; ops.beam_advance);
-        ``self.last_beam_advance`` then says how many steps took it (advanced, eager, reason)."""
+        ``self.last_beam_advance`` then says how many steps took it (advanced, eager, reason).  ``beam_graph``: beam search
+        captures a whole step -- model, selection, bookkeeping -- into one graph and replays it (None: the package switch,
+        set_beam_graph; it implies the three above for the call; model/graph_decode.py, BeamStepGraphs);
+        ``self.last_beam_graph`` then says what happened (captured, replays, issued, reason)."""
         return generation.generate(self, input_ids, attention_mask=attention_mask, max_length=max_length,
                                    num_beams=num_beams, **kwargs)
 

@@ -1886,6 +1886,70 @@ def beam_select(logits, running_scores, keep, seq=None, cur=0, ngram=0, ban_ids=
     return top_lp, top_idx
 
 
+def beam_select_workspace_bytes(bsz, nb, vocab, keep):
+    """Bytes of workspace a beam_select / beam_select_at call of this geometry needs (at least 8, for a tensor to exist)."""
+    return max(int(_hip.load().osq_beam_select_workspace_bytes(int(bsz), int(nb), int(vocab), int(keep))), 8)
+
+
+def beam_select_at(logits, running_scores, keep, cur, cur_add, cur_max, seq=None, ngram=0, ban_ids=None, ban_below=0,
+                   top_lp=None, top_idx=None, workspace=None):
+    """beam_select with the position read by the launch (osq_beam_select_at): ``cur`` is one int32 on the device and the call
+    selects at position ``*cur + cur_add``, so a captured graph of the call serves every step.  ``cur_max`` is the largest
+    position the call may meet: with ``ngram > 0``, seq rows hold at least that many tokens.  ``ban_ids`` apply while the
+    position is below ``ban_below`` (the min-length rule).  For a position in [0, cur_max] the result is word-equal to
+    ``beam_select`` at that position; outside it every word of top_lp is NaN and every top_idx 0.
+
+    running_scores must be contiguous (nothing is copied here).  top_lp / top_idx: the contiguous fp32 / int64 [bsz, keep]
+    tensors to write, workspace: a contiguous uint8 tensor of at least ``beam_select_workspace_bytes`` bytes -- a captured
+    step names static buffers; None: new ones.  Returns (top_lp, top_idx)."""
+    lib = _hip.load()
+    _hip.require_device(logits, running_scores, seq, ban_ids, cur, top_lp, top_idx, workspace)
+    _check_f32(logits, running_scores)
+    if running_scores.dim() != 2 or logits.dim() != 2 or not running_scores.is_contiguous():
+        raise ValueError("beam_select_at: logits must be [bsz * nb, vocab] and running_scores a contiguous [bsz, nb]")
+    if cur.dtype != torch.int32 or cur.numel() != 1 or cur.device != logits.device:
+        raise TypeError("beam_select_at: cur must be one int32 on the device of logits")
+    bsz, nb = running_scores.shape
+    rows, vocab = logits.shape
+    if rows != bsz * nb or (vocab > 1 and logits.stride(1) != 1) or (rows > 1 and logits.stride(0) < vocab):
+        raise ValueError("beam_select_at: logits must hold bsz * nb rows with a dense last axis")
+    cur_max = int(cur_max)
+    seq_stride = 0
+    if seq is not None:
+        if (seq.dtype != torch.int64 or seq.dim() != 2 or seq.shape[0] != rows or seq.shape[1] < cur_max
+                or (seq.shape[1] > 1 and seq.stride(1) != 1)):
+            raise ValueError("beam_select_at: seq must be int64 [bsz * nb, >= cur_max] with a dense last axis")
+        seq_stride = seq.stride(0) if rows > 1 else seq.shape[1]
+    elif ngram > 0:
+        raise ValueError("beam_select_at: ngram > 0 needs seq")
+    n_ban = 0
+    if ban_ids is not None:
+        if ban_ids.dtype != torch.int64 or ban_ids.dim() != 1 or not ban_ids.is_contiguous():
+            raise ValueError("beam_select_at: ban_ids must be a contiguous 1-d int64 tensor")
+        n_ban = ban_ids.numel()
+    keep = int(keep)
+    device = logits.device
+    if top_lp is None:
+        top_lp = torch.empty((bsz, keep), dtype=torch.float32, device=device)
+    if top_idx is None:
+        top_idx = torch.empty((bsz, keep), dtype=torch.int64, device=device)
+    for t, dtype, name in ((top_lp, torch.float32, "top_lp"), (top_idx, torch.int64, "top_idx")):
+        if t.dtype != dtype or tuple(t.shape) != (bsz, keep) or not t.is_contiguous() or t.device != device:
+            raise ValueError(f"beam_select_at: {name} must be a contiguous {dtype} [bsz, keep] tensor on the device of logits")
+    nbytes = int(lib.osq_beam_select_workspace_bytes(bsz, nb, vocab, keep))
+    if workspace is None:
+        workspace = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=device)
+    elif (workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.numel() < nbytes
+            or workspace.device != device):
+        raise ValueError(f"beam_select_at: workspace must be a contiguous uint8 tensor of at least {nbytes} bytes")
+    rc = lib.osq_beam_select_at(logits.data_ptr(), logits.stride(0) if rows > 1 else vocab, running_scores.data_ptr(),
+                                _hip.ptr(seq), seq_stride, cur.data_ptr(), int(cur_add), cur_max, int(ngram),
+                                _hip.ptr(ban_ids), n_ban, int(ban_below), bsz, nb, vocab, keep, top_lp.data_ptr(),
+                                top_idx.data_ptr(), workspace.data_ptr(), workspace.numel(), _hip.raw_stream(device))
+    _hip.check(rc, "beam_select_at")
+    return top_lp, top_idx
+
+
 class BeamBuffers:
     """One set of beam-search state on a device, as osq_beam_advance reads and writes it: ``running`` /  ``finished``
     [bsz, nb, max_length] int64, ``running_scores`` / ``scores`` [bsz, nb] fp32, ``finished_len`` [bsz, nb] int64, ``done``
@@ -1904,6 +1968,54 @@ class BeamBuffers:
         self.workspace = torch.zeros(4 * bsz, dtype=torch.uint8, device=device)
 
 
+def _beam_advance_operands(what, top_lp, top_idx, state, out, eos_ids, early_stopping):
+    """The checks beam_advance and beam_advance_at share; (tensors, outs, bsz, nb, keep, max_length, n_eos, mode, device)."""
+    names = BeamBuffers.STATE
+    tensors = [getattr(state, n) for n in names]
+    outs = [getattr(out, n) for n in names]
+    extra = [out.beam_idx, out.next_tokens, out.go_on, out.workspace]
+    _hip.require_device(top_lp, top_idx, eos_ids, *tensors, *outs, *extra)
+    if top_lp.dim() != 2 or top_lp.shape != top_idx.shape or top_lp.dtype != torch.float32 or top_idx.dtype != torch.int64:
+        raise ValueError(f"{what}: top_lp must be fp32 [bsz, keep] and top_idx int64 [bsz, keep]")
+    bsz, keep = top_lp.shape
+    if state.running.dim() != 3 or state.running.shape[0] != bsz:
+        raise ValueError(f"{what}: running must be [bsz, nb, max_length]")
+    _, nb, max_length = state.running.shape
+    shapes = ((bsz, nb, max_length), (bsz, nb), (bsz, nb, max_length), (bsz, nb), (bsz, nb), (bsz, nb), (bsz,))
+    for group, which in ((tensors, "state"), (outs, "out")):
+        for name, t, shape, dtype in zip(names, group, shapes, BeamBuffers._DTYPES):
+            ok_dtype = t.dtype == dtype or (dtype == torch.bool and t.dtype == torch.uint8)
+            if not ok_dtype or t.numel() != math.prod(shape) or tuple(t.shape[:len(shape)]) != shape or not t.is_contiguous():
+                raise ValueError(f"{what}: {which}.{name} must be a contiguous {dtype} tensor of shape {shape}")
+    for name, t, n, dtype in (("beam_idx", out.beam_idx, bsz * nb, torch.int64), ("next_tokens", out.next_tokens, bsz * nb, torch.int64),
+                              ("go_on", out.go_on, 1, torch.int32)):
+        if t.dtype != dtype or t.numel() != n or not t.is_contiguous():
+            raise ValueError(f"{what}: out.{name} must be a contiguous {dtype} tensor of {n} elements")
+    if out.workspace.dtype != torch.uint8 or not out.workspace.is_contiguous():
+        raise ValueError(f"{what}: out.workspace must be a contiguous uint8 tensor")
+    device = top_lp.device
+    every = [top_lp, top_idx, *tensors, *outs, *extra] + ([] if eos_ids is None else [eos_ids])
+    if any(t.device != device for t in every):
+        raise ValueError(f"{what}: all tensors must be on one device")
+    reads = [top_lp, top_idx, *tensors] + ([] if eos_ids is None else [eos_ids])
+    writes = [*outs, *extra]
+    spans = lambda ts: [(t.data_ptr(), t.data_ptr() + t.numel() * t.element_size()) for t in ts if t.numel()]  # noqa: E731
+    w = spans(writes)
+    for i, (lo, hi) in enumerate(w):
+        if any(lo < h and l < hi for l, h in spans(reads) + w[:i]):
+            raise ValueError(f"{what}: an output shares memory with an input or another output (the gathers read the "
+                             "old state: state and out are two sets)")
+    n_eos = 0
+    if eos_ids is not None:
+        if eos_ids.dtype != torch.int64 or eos_ids.dim() != 1 or not eos_ids.is_contiguous():
+            raise ValueError(f"{what}: eos_ids must be a contiguous 1-d int64 tensor")
+        n_eos = eos_ids.numel()
+    if early_stopping not in (False, True, "never"):
+        raise ValueError(f'{what}: early_stopping is False, True or "never"')
+    mode = 2 if early_stopping == "never" else int(bool(early_stopping))
+    return tensors, outs, bsz, nb, keep, max_length, n_eos, mode, device
+
+
 def beam_advance(top_lp, top_idx, state, out, cur, vocab, eos_ids=None, early_stopping=False, len_div=1.0, best_div=1.0,
                  reciprocal=True):
     """The bookkeeping of one beam-search step after the selection (osq_beam_advance, csrc/beam_advance.hip): from ``top_lp``
@@ -1918,49 +2030,8 @@ def beam_advance(top_lp, top_idx, state, out, cur, vocab, eos_ids=None, early_st
     double; False: the correctly rounded v / float32(div), as torch's CPU kernel does.
     Two launches on the current stream, no synchronisation, nothing allocated; returns ``out``."""
     lib = _hip.load()
-    names = BeamBuffers.STATE
-    tensors = [getattr(state, n) for n in names]
-    outs = [getattr(out, n) for n in names]
-    extra = [out.beam_idx, out.next_tokens, out.go_on, out.workspace]
-    _hip.require_device(top_lp, top_idx, eos_ids, *tensors, *outs, *extra)
-    if top_lp.dim() != 2 or top_lp.shape != top_idx.shape or top_lp.dtype != torch.float32 or top_idx.dtype != torch.int64:
-        raise ValueError("beam_advance: top_lp must be fp32 [bsz, keep] and top_idx int64 [bsz, keep]")
-    bsz, keep = top_lp.shape
-    if state.running.dim() != 3 or state.running.shape[0] != bsz:
-        raise ValueError("beam_advance: running must be [bsz, nb, max_length]")
-    _, nb, max_length = state.running.shape
-    shapes = ((bsz, nb, max_length), (bsz, nb), (bsz, nb, max_length), (bsz, nb), (bsz, nb), (bsz, nb), (bsz,))
-    for group, what in ((tensors, "state"), (outs, "out")):
-        for name, t, shape, dtype in zip(names, group, shapes, BeamBuffers._DTYPES):
-            ok_dtype = t.dtype == dtype or (dtype == torch.bool and t.dtype == torch.uint8)
-            if not ok_dtype or t.numel() != math.prod(shape) or tuple(t.shape[:len(shape)]) != shape or not t.is_contiguous():
-                raise ValueError(f"beam_advance: {what}.{name} must be a contiguous {dtype} tensor of shape {shape}")
-    for name, t, n, dtype in (("beam_idx", out.beam_idx, bsz * nb, torch.int64), ("next_tokens", out.next_tokens, bsz * nb, torch.int64),
-                              ("go_on", out.go_on, 1, torch.int32)):
-        if t.dtype != dtype or t.numel() != n or not t.is_contiguous():
-            raise ValueError(f"beam_advance: out.{name} must be a contiguous {dtype} tensor of {n} elements")
-    if out.workspace.dtype != torch.uint8 or not out.workspace.is_contiguous():
-        raise ValueError("beam_advance: out.workspace must be a contiguous uint8 tensor")
-    device = top_lp.device
-    every = [top_lp, top_idx, *tensors, *outs, *extra] + ([] if eos_ids is None else [eos_ids])
-    if any(t.device != device for t in every):
-        raise ValueError("beam_advance: all tensors must be on one device")
-    reads = [top_lp, top_idx, *tensors] + ([] if eos_ids is None else [eos_ids])
-    writes = [*outs, *extra]
-    spans = lambda ts: [(t.data_ptr(), t.data_ptr() + t.numel() * t.element_size()) for t in ts if t.numel()]  # noqa: E731
-    w = spans(writes)
-    for i, (lo, hi) in enumerate(w):
-        if any(lo < h and l < hi for l, h in spans(reads) + w[:i]):
-            raise ValueError("beam_advance: an output shares memory with an input or another output (the gathers read the "
-                             "old state: state and out are two sets)")
-    n_eos = 0
-    if eos_ids is not None:
-        if eos_ids.dtype != torch.int64 or eos_ids.dim() != 1 or not eos_ids.is_contiguous():
-            raise ValueError("beam_advance: eos_ids must be a contiguous 1-d int64 tensor")
-        n_eos = eos_ids.numel()
-    if early_stopping not in (False, True, "never"):
-        raise ValueError('beam_advance: early_stopping is False, True or "never"')
-    mode = 2 if early_stopping == "never" else int(bool(early_stopping))
+    tensors, outs, bsz, nb, keep, max_length, n_eos, mode, device = _beam_advance_operands(
+        "beam_advance", top_lp, top_idx, state, out, eos_ids, early_stopping)
     top_lp, top_idx = top_lp.contiguous(), top_idx.contiguous()
     rc = lib.osq_beam_advance(top_lp.data_ptr(), top_idx.data_ptr(), *(t.data_ptr() for t in tensors),
                               _hip.ptr(eos_ids) if n_eos else None, n_eos, bsz, nb, keep, int(vocab), max_length, int(cur), mode,
@@ -1968,4 +2039,58 @@ def beam_advance(top_lp, top_idx, state, out, cur, vocab, eos_ids=None, early_st
                               out.beam_idx.data_ptr(), out.next_tokens.data_ptr(), out.go_on.data_ptr(),
                               out.workspace.data_ptr(), out.workspace.numel(), _hip.raw_stream(device))
     _hip.check(rc, "beam_advance")
+    return out
+
+
+def beam_div_tables(max_length, length_penalty, early_stopping, reciprocal, device, prompt=1):
+    """The two factor tables of beam_advance_at for a search up to ``max_length``: (len_table, best_table), fp32
+    [max_length] on ``device``.  Entry ``cur`` is the word beam_advance derives at that length from the Python expressions of
+    the search (generation._beam_search_advanced),
+
+        len_div  = (cur + 1 - prompt) ** length_penalty
+        best_div = best_len ** length_penalty,   best_len = max_length - prompt with early_stopping == "never" and a positive
+                                                 penalty, else cur + 1 - prompt
+
+    as ``float32(1.0 / div)`` with ``reciprocal`` (the reciprocal in double, rounded once) and ``float32(div)`` without.
+    Entries below ``prompt`` belong to no step (a length of zero tokens has no divisor): they hold NaN."""
+    max_length, prompt = int(max_length), int(prompt)
+    nan = float("nan")
+    tables = ([], [])
+    for cur in range(max_length):
+        if cur < prompt:
+            divs = (nan, nan)
+        else:
+            best_len = (max_length - prompt) if (early_stopping == "never" and length_penalty > 0.0) else (cur + 1 - prompt)
+            divs = ((cur + 1 - prompt) ** length_penalty, best_len ** length_penalty)
+        for table, div in zip(tables, divs):
+            table.append(1.0 / div if reciprocal and div == div else div)
+    # float64 -> float32 rounds to nearest even, as the C cast of the static entry point does
+    return tuple(torch.tensor(t, dtype=torch.float64).to(torch.float32).to(device) for t in tables)
+
+
+def beam_advance_at(top_lp, top_idx, state, out, cur, cur_add, vocab, len_table, best_table, eos_ids=None,
+                    early_stopping=False, reciprocal=True):
+    """beam_advance with the position read by the launch (osq_beam_advance_at): ``cur`` is one int32 on the device and the
+    step is taken at length ``*cur + cur_add``, so a captured graph of the call serves every step.  len_table / best_table:
+    ``beam_div_tables`` of the search, built with the same ``reciprocal``.  For a length in [1, max_length) everything written
+    is word-equal to ``beam_advance`` at that length; outside it ``out.go_on`` receives -1 and nothing else is written.
+    top_lp / top_idx must be contiguous (nothing is copied here).  Returns ``out``."""
+    lib = _hip.load()
+    tensors, outs, bsz, nb, keep, max_length, n_eos, mode, device = _beam_advance_operands(
+        "beam_advance_at", top_lp, top_idx, state, out, eos_ids, early_stopping)
+    _hip.require_device(cur, len_table, best_table)
+    if not (top_lp.is_contiguous() and top_idx.is_contiguous()):
+        raise ValueError("beam_advance_at: top_lp and top_idx must be contiguous")
+    if cur.dtype != torch.int32 or cur.numel() != 1 or cur.device != device:
+        raise TypeError("beam_advance_at: cur must be one int32 on the device of top_lp")
+    for name, t in (("len_table", len_table), ("best_table", best_table)):
+        if t.dtype != torch.float32 or t.dim() != 1 or t.numel() < max_length or not t.is_contiguous() or t.device != device:
+            raise ValueError(f"beam_advance_at: {name} must hold max_length contiguous floats on the device of top_lp")
+    rc = lib.osq_beam_advance_at(top_lp.data_ptr(), top_idx.data_ptr(), *(t.data_ptr() for t in tensors),
+                                 _hip.ptr(eos_ids) if n_eos else None, n_eos, bsz, nb, keep, int(vocab), max_length,
+                                 cur.data_ptr(), int(cur_add), mode, len_table.data_ptr(), best_table.data_ptr(),
+                                 int(bool(reciprocal)), *(t.data_ptr() for t in outs), out.beam_idx.data_ptr(),
+                                 out.next_tokens.data_ptr(), out.go_on.data_ptr(), out.workspace.data_ptr(),
+                                 out.workspace.numel(), _hip.raw_stream(device))
+    _hip.check(rc, "beam_advance_at")
     return out

@@ -59,6 +59,12 @@ beams that go on, the merge into the finished set, the cache rows, the early-sto
 ``ops.beam_advance`` (csrc/beam_advance.hip) instead of about forty torch launches; the state then lives in two alternating
 sets of device buffers.  Word-equal to the torch lines where those have no ties; ties come out in the strict index order.
 ``outlier_suppression_amd.set_beam_advance(True)`` / ``OSQ_BEAM_ADVANCE=1`` / ``generate(..., beam_advance=True)`` turn it on.
+
+``BEAM_GRAPH`` (default OFF): beam search captures a WHOLE step -- the token copy, the model step, the selection
+(``ops.beam_select_at``), the bookkeeping (``ops.beam_advance_at``) and the copy of the cache's row index -- into one graph per
+direction of the alternating buffers and replays it (model/graph_decode.py, BeamStepGraphs); a token then costs the host one
+replay and one read of the stopping word.  For its call it implies the three switches above; the words are theirs.
+``outlier_suppression_amd.set_beam_graph(True)`` / ``OSQ_BEAM_GRAPH=1`` / ``generate(..., beam_graph=True)`` turn it on.
 """
 import torch
 import torch.nn.functional as F
@@ -77,6 +83,7 @@ FUSE_KV_APPEND = True    # incremental decoding: a step's q / k / v sites + KV-c
 GRAPH_DECODE = False     # generate(): capture a cached decoding step into a graph and replay it (set_graph_decode / OSQ_GRAPH_DECODE=1 / generate(graph=True))
 BEAM_SELECT = False      # generate(): a beam step's log-softmax + processors + score add + top-k as one kernel call (tolerance-equal; set_beam_select / OSQ_BEAM_SELECT=1 / generate(beam_select=True))
 BEAM_ADVANCE = False     # generate(): a beam step's bookkeeping after the selection as one kernel call on alternating state buffers (set_beam_advance / OSQ_BEAM_ADVANCE=1 / generate(beam_advance=True))
+BEAM_GRAPH = False       # generate(): capture a whole beam-search step -- model, selection, bookkeeping, cache row index -- into one graph (implies the three above for the call; set_beam_graph / OSQ_BEAM_GRAPH=1 / generate(beam_graph=True))
 CACHE_CODES = False      # incremental decoding: new KV caches hold integer codes, one byte per element (same words read back; set_cache_codes / OSQ_CACHE_CODES=1)
 
 

@@ -25,6 +25,10 @@ in turn within each of the --reps rounds, in one process.
 lines against ops.beam_advance (csrc/beam_advance.hip): that step alone on the state and the top_lp / top_idx recorded at
 length 31 of a generate() call; then generate(graph=True, beam_select=True) and the same issued launch by launch, with the
 switch off and on.  Every form is timed in turn within each of the --reps rounds, in one process.
+--beam-graph: the A/B is the whole beam step as one captured graph (generate(beam_graph=True); model/graph_decode.py,
+BeamStepGraphs) against generate(graph=True, beam_select=True, beam_advance=True), where the selection and the bookkeeping
+are issued between the replays: the whole call with no_repeat_ngram_size 0 and 3, the fp32 and the coded cache; every form
+is timed in turn within each of the --reps rounds, in one process; capture + instantiate time is reported apart.
 
     python tools/decode_bench.py [--reps 7] [--out profiles/decode_step_ab.txt]
     python tools/decode_bench.py --fast-decode-attention [--out profiles/decode_attention_ab.txt]
@@ -32,6 +36,7 @@ switch off and on.  Every form is timed in turn within each of the --reps rounds
     python tools/decode_bench.py --graph [--out profiles/graph_decode_ab.txt]
     python tools/decode_bench.py --beam-select [--out profiles/beam_select_ab.txt]
     python tools/decode_bench.py --beam-advance [--out profiles/beam_advance_ab.txt]
+    python tools/decode_bench.py --beam-graph [--out profiles/beam_graph_ab.txt]
 """
 import argparse
 import copy
@@ -413,6 +418,51 @@ def beam_advance_ab(q, ids, mask, args):
     return lines
 
 
+def beam_graph_ab(q, ids, mask, args):
+    bsz, nb, max_length = args.batch, args.beams, 62
+    parent = dict(graph=True, beam_select=True, beam_advance=True)
+    lines = [f"a whole beam step as one captured graph -- token copy, model step, ops.beam_select_at, ops.beam_advance_at, the "
+             f"cache's row index -- generate(beam_graph=True) against generate(graph=True, beam_select=True, beam_advance=True); "
+             f"{bsz} x {nb} beams, source {args.src}, max_length = min_length = {max_length} (BART's forced eos on: the last step is "
+             f"issued launch by launch); every form timed in turn in each of {args.reps} rounds, one process; median [min, max]"]
+    print(lines[0], flush=True)
+    m = q
+    gen = [(f"no_repeat_ngram_size {ngram}, {'coded' if codes else 'fp32'} cache, {'beam_graph' if whole else 'graph + select + advance'}",
+            ngram, codes, whole) for ngram in (0, 3) for codes in (False, True) for whole in (False, True)]
+    times = {label: [] for label, *_ in gen}
+    capture = {label: [] for label, *_ in gen}
+    tokens, did = {}, {}
+    with torch.no_grad():
+        for r in range(args.reps + 1):              # the first round warms every form up
+            for label, ngram, codes, whole in gen:
+                kw = dict(beam_graph=True) if whole else parent
+                secs, tokens[label] = _timed(lambda: m.generate(ids, attention_mask=mask, max_length=max_length, num_beams=nb,
+                                                                min_length=max_length, no_repeat_ngram_size=ngram,
+                                                                cache_codes=codes, **kw), 1.0)
+                info = m.last_beam_graph
+                assert (info.reason is None) == whole, info
+                did[label] = (m.last_decode_graph.captured, m.last_decode_graph.replays, info.issued)
+                if r:
+                    times[label].append(secs)
+                    capture[label].append(m.last_decode_graph.capture_seconds)
+    lines.append(f"generate(max_length={max_length}, num_beams={nb}, min_length={max_length}), s, wall time of the call (capture "
+                 "included); (graphs captured, replays, steps issued launch by launch):")
+    lines += [f"    {label:70s} {_stats(t)}   {did[label]}" for label, t in times.items()]
+    lines.append("of which capture + instantiate, s:")
+    lines += [f"    {label:70s} {_stats(t)}" for label, t in capture.items()]
+    for label, ngram, codes, whole in gen:
+        if whole:
+            off = label.replace("beam_graph", "graph + select + advance")
+            same = tokens[label].shape == tokens[off].shape and bool(torch.equal(tokens[label], tokens[off]))
+            a, b = sorted(times[off]), sorted(times[label])
+            gain = a[len(a) // 2] - b[len(b) // 2]
+            spread = a[-1] - a[0]
+            lines.append(f"    {label}: tokens equal to graph + select + advance: {same}; median gain {gain * 1e3:.1f} ms "
+                         f"({gain / (max_length - 1) * 1e3:.3f} ms per token), the parent form's own spread {spread * 1e3:.1f} ms")
+    print("\n".join(lines[1:]), flush=True)
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=32)
@@ -426,9 +476,16 @@ def main():
     ap.add_argument("--graph", action="store_true")
     ap.add_argument("--beam-select", action="store_true")
     ap.add_argument("--beam-advance", action="store_true")
+    ap.add_argument("--beam-graph", action="store_true")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     q, ids, mask = build(args.batch, args.src, args.layers)
+    if args.beam_graph:
+        text = "\n".join(beam_graph_ab(q, ids, mask, args))
+        if args.out:
+            with open(args.out, "w") as f:
+                f.write(text + "\n")
+        return
     if args.beam_advance:
         text = "\n".join(beam_advance_ab(q, ids, mask, args))
         if args.out:
