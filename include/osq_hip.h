@@ -42,7 +42,8 @@ typedef void* osq_stream;
  *     osq_decode_attention_fake_quant, osq_fake_quant_kv_append_codes, osq_decode_attention_codes,
  *     osq_fake_quant_kv_append_at, osq_fake_quant_kv_append_codes_at, osq_decode_attention_fake_quant_at,
  *     osq_decode_attention_codes_at, osq_beam_select_workspace_bytes, osq_beam_select, osq_beam_advance,
- *     osq_beam_select_at, osq_beam_advance_at. */
+ *     osq_beam_select_at, osq_beam_advance_at, osq_greedy_advance_workspace_bytes, osq_greedy_advance,
+ *     osq_greedy_advance_at. */
 #define OSQ_ABI_VERSION 10
 
 typedef enum osq_status {
@@ -992,6 +993,53 @@ int osq_beam_advance_at(const float* top_value, const int64_t* top_index, const 
                         int64_t* finished_out, float* scores_out, int64_t* finished_len_out, uint8_t* done_out,
                         uint8_t* improvable_out, int64_t* beam_idx, int64_t* next_tokens, int32_t* go_on, void* workspace,
                         size_t workspace_bytes, osq_stream stream);
+
+/* ------------------------------------------------------------------ greedy decoding (greedy_advance.hip) */
+
+/* One greedy decoding step after the model, at history length cur: what model/generation.py::_greedy does from
+ * `procs(seq, logits)` to its stopping test -- the banned tokens, argmax, the pad / eos lines, the new token into the
+ * sequence, the stopping condition -- in three launches that read the logits once.  For every batch row b:
+ *     banned (taken as -inf, a NaN included): every id of ban_ids; and the no-repeat-ngram tokens of seq[b, :cur] under
+ *         osq_beam_select's rule (window i bans its last token when its first ngram - 1 tokens equal the suffix; nothing when
+ *         cur < ngram).  Ids outside [0, vocab) ban nothing.
+ *     token = forced, when forced >= 0: every logit is then ignored, NaN included, and none is read
+ *             else the arg-max of the banned row: larger value first; equal values by smaller index; -0.0 and +0.0 are equal;
+ *             NaN above every number, NaNs among themselves by smaller index -- torch.argmax's and numpy's order.  A row that
+ *             is all -inf or all banned gives 0.
+ *     with n_eos > 0:  token = unfinished[b] ? token : pad;  unfinished[b] &= token not in eos_ids   (written as 0 / 1)
+ *     with n_eos == 0: unfinished is neither read nor written
+ *     seq[b, cur] = token (seq may be NULL with ngram == 0: it is then not written), next_tokens[b] = token
+ * and go_on (one int32) = (cur + 1 < max_length) && (n_eos == 0 || any row unfinished).  Nothing else of seq is written.
+ * logits: bsz rows of vocab floats, unit stride in a row, rows logits_stride ELEMENTS apart (4-byte aligned is enough).
+ * seq: int64, rows of max_length tokens, seq_stride elements apart.  ban_ids / eos_ids: n_ban / n_eos <= 16 int64 ids on the
+ * device; eos ids are compared, never stored.  unfinished: bsz bytes (0 / not 0).  next_tokens: bsz int64.
+ * workspace: at least osq_greedy_advance_workspace_bytes(bsz, vocab) bytes of device memory, 8-byte aligned, contents
+ * arbitrary; one per stream in flight.  One workgroup per (row, 4096-token chunk), one per row, one for go_on; no workgroup
+ * waits for another; no float atomics: the same inputs give the same words on every run.  No host synchronisation, no
+ * allocation, nothing read from the host: legal inside a stream capture.
+ * OSQ_ERR_INVALID_ARGUMENT, nothing launched: a non-positive extent, vocab >= 2^31, max_length > 4096, cur < 1 or
+ * cur >= max_length, n_ban > 16, n_eos > 16, n_eos > 0 with a null unfinished, forced >= vocab, pad outside [0, vocab) with
+ * n_eos > 0 (the tokens that are stored unchecked), a row stride below the row's length, ngram > 0 with a null seq, a
+ * workspace that is too small, a null tensor. */
+size_t osq_greedy_advance_workspace_bytes(int64_t bsz, int64_t vocab);
+int osq_greedy_advance(const float* logits, int64_t logits_stride, int64_t* seq, int64_t seq_stride, int64_t cur,
+                       int64_t ngram, const int64_t* ban_ids, int64_t n_ban, int64_t forced, const int64_t* eos_ids,
+                       int64_t n_eos, int64_t pad, uint8_t* unfinished, int64_t bsz, int64_t vocab, int64_t max_length,
+                       int64_t* next_tokens, int32_t* go_on, void* workspace, size_t workspace_bytes, osq_stream stream);
+
+/* osq_greedy_advance with the position read by the launches: cur = *cur_dev + cur_add (cur_dev one device int32; a captured
+ * decoding step passes the KV cache's position word, which after the decoder's increment is the step's cur), so that one
+ * captured graph serves every step, forced ones included.  ban_ids apply while cur < ban_below (the min-length rule);
+ * forced_bos >= 0 is the token at cur == 1 and forced_eos >= 0 the token at cur == max_length - 1; where both fire, eos wins
+ * (the later logits processor).  For every cur in [1, max_length) every output word equals osq_greedy_advance called with
+ * that cur and the n_ban / forced the host would have passed.  A cur outside that range: go_on receives -1 and nothing else
+ * is written; no address is formed from a refused position.  Limits, workspace and OSQ_ERR_INVALID_ARGUMENT as for the
+ * static form (but for cur; forced_bos and forced_eos as forced); also a null cur_dev. */
+int osq_greedy_advance_at(const float* logits, int64_t logits_stride, int64_t* seq, int64_t seq_stride,
+                          const int32_t* cur_dev, int64_t cur_add, int64_t ngram, const int64_t* ban_ids, int64_t n_ban,
+                          int64_t ban_below, int64_t forced_bos, int64_t forced_eos, const int64_t* eos_ids, int64_t n_eos,
+                          int64_t pad, uint8_t* unfinished, int64_t bsz, int64_t vocab, int64_t max_length,
+                          int64_t* next_tokens, int32_t* go_on, void* workspace, size_t workspace_bytes, osq_stream stream);
 
 /* ------------------------------------------------------------------ bf16 / fp16 only (lowp.hip) */
 

@@ -116,6 +116,39 @@ def set_beam_graph(on=True):
     util_layernorm.BEAM_GRAPH = bool(on)
 
 
+def set_greedy_advance(on=True):
+    """generate()'s greedy decoding takes a step with ops.greedy_advance -- the banned tokens of the logits processors, the
+    arg-max in torch.argmax's order, the pad / eos arithmetic, the new token into the sequence and the stopping word in one
+    kernel call on one set of state buffers (util_layernorm.GREEDY_ADVANCE; csrc/greedy_advance.hip; default OFF) -- instead
+    of the torch lines; a call it cannot take runs those (``model.last_greedy_advance.reason``).  OSQ_GREEDY_ADVANCE=1 turns
+    it on at load; ``generate(..., greedy_advance=True)`` asks for one call."""
+    from . import util_layernorm
+    util_layernorm.GREEDY_ADVANCE = bool(on)
+
+
+def set_greedy_graph(on=True):
+    """generate()'s greedy decoding captures a whole step -- the token copy, the model step and ops.greedy_advance_at -- into
+    one hipGraph and replays it, forced tokens included: per token the host issues one replay and reads one word
+    (util_layernorm.GREEDY_GRAPH; model/graph_decode.py, GreedyStepGraph; default OFF).  For its call it implies
+    set_graph_decode and set_greedy_advance; a call it cannot take -- one of those says why, one of them is passed as False,
+    beam search -- decodes as without it (``model.last_greedy_graph.reason``).  OSQ_GREEDY_GRAPH=1 turns it on at load;
+    ``generate(..., greedy_graph=True)`` asks for one call."""
+    from . import util_layernorm
+    util_layernorm.GREEDY_GRAPH = bool(on)
+
+
+def greedy_advance_from_environment(environ=None):
+    """What OSQ_GREEDY_ADVANCE asks for: unset, empty or "0" -> False, anything else -> True."""
+    import os
+    return (os.environ if environ is None else environ).get("OSQ_GREEDY_ADVANCE", "") not in ("", "0")
+
+
+def greedy_graph_from_environment(environ=None):
+    """What OSQ_GREEDY_GRAPH asks for: unset, empty or "0" -> False, anything else -> True."""
+    import os
+    return (os.environ if environ is None else environ).get("OSQ_GREEDY_GRAPH", "") not in ("", "0")
+
+
 def beam_graph_from_environment(environ=None):
     """What OSQ_BEAM_GRAPH asks for: unset, empty or "0" -> False, anything else -> True."""
     import os
@@ -153,7 +186,9 @@ def reset_tier(_lib=None):
     the one-launch attention of a cached decoding step (unset: off); OSQ_CACHE_CODES=1 KV caches as integer codes (unset: off);
     OSQ_GRAPH_DECODE=1 generate() replays a captured decoding step (unset: off); OSQ_BEAM_SELECT=1 beam search selects a step's
     continuations with one kernel call (unset: off); OSQ_BEAM_ADVANCE=1 beam search advances its beams with one kernel call
-    (unset: off); OSQ_BEAM_GRAPH=1 beam search replays a whole step, bookkeeping included, as one captured graph (unset: off)."""
+    (unset: off); OSQ_BEAM_GRAPH=1 beam search replays a whole step, bookkeeping included, as one captured graph (unset: off);
+    OSQ_GREEDY_ADVANCE=1 greedy decoding takes a step with one kernel call (unset: off); OSQ_GREEDY_GRAPH=1 greedy decoding
+    replays a whole step as one captured graph (unset: off)."""
     import os
     width = int(os.environ.get("OSQ_STRICT_SIMD", "8"))
     strict = os.environ.get("OSQ_STRICT", "")
@@ -170,6 +205,8 @@ def reset_tier(_lib=None):
     set_beam_select(beam_select_from_environment())
     set_beam_advance(beam_advance_from_environment())
     set_beam_graph(beam_graph_from_environment())
+    set_greedy_advance(greedy_advance_from_environment())
+    set_greedy_graph(greedy_graph_from_environment())
 
 
 _apply_environment = reset_tier

@@ -178,6 +178,10 @@ SIGNATURES = {
     "osq_beam_select_at": (_I, [_P, _L, _P, _P, _L, _P, _L, _L, _L, _P, _L, _L, _L, _L, _L, _L, _P, _P, _P, ctypes.c_size_t, _P]),
     "osq_beam_advance_at": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _L, _L, _L, _L, _L, _P, _L, _I, _P, _P, _I,
                                  _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, ctypes.c_size_t, _P]),
+    "osq_greedy_advance_workspace_bytes": (ctypes.c_size_t, [_L, _L]),
+    "osq_greedy_advance": (_I, [_P, _L, _P, _L, _L, _L, _P, _L, _L, _P, _L, _L, _P, _L, _L, _L, _P, _P, _P, ctypes.c_size_t, _P]),
+    "osq_greedy_advance_at": (_I, [_P, _L, _P, _L, _P, _L, _L, _P, _L, _L, _L, _L, _P, _L, _L, _P, _L, _L, _L, _P, _P, _P,
+                                   ctypes.c_size_t, _P]),
     "osq_fake_quant_chain_lowp": (_I, [_I, _P, _P, _L, _P, _P, _I, _I, _I, _P]),
     "osq_fake_quant_chain_backward_lowp": (_I, [_I, _P, _P, _P, _L, _P, _P, _I, _I, _I, _P]),
     "osq_fake_quant_per_tensor_widen": (_I, [_I, _P, _P, _L, _P, _P, _I, _I, _F, _I, _I, _P]),

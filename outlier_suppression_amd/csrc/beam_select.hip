@@ -36,19 +36,11 @@
 #include <hip/hip_runtime.h>
 #include "osq_device.h"
 #include "osq_host.h"
+#include "token_argmax.h"
 
 namespace osq {
 
-constexpr int kBsThreads = 256;
-constexpr int kBsWaves = kBsThreads / OSQ_WAVE;
-constexpr int kBsPer = 16;                          // elements of a chunk one thread holds
-constexpr int kBsChunk = kBsThreads * kBsPer;       // 4096 tokens
-constexpr int kBsMaxKeep = 64, kBsMaxBeams = 64, kBsMaxCur = 4096, kBsMaxBan = 16;
-
-struct BeamCand {              // one candidate in the workspace
-    unsigned int key;          // beam_key(value); 0: none
-    int token;
-};
+constexpr int kBsMaxKeep = 64, kBsMaxBeams = 64;
 
 struct BeamArgs {
     const float* logits;       // rows x vocab, rows logits_stride floats apart
@@ -65,28 +57,6 @@ struct BeamArgs {
     const int32_t* cur_dev;    // nullptr: the static form, cur above
     int cur_add, cur_max, ban_below;
 };
-
-__device__ __forceinline__ unsigned int beam_key(float v) { return v != v ? 0xffffffffu : ordered_bits(v); }
-__device__ __forceinline__ float beam_value(unsigned int key) {
-    return key == 0xffffffffu ? __builtin_nanf("") : from_ordered_bits(key);
-}
-
-// The largest (hi, lo) pair of the workgroup, lexicographically, in every thread.  s_red: [2][2 * kBsWaves] words, the two
-// halves used by alternate calls (`parity`), so one barrier per call is enough.
-__device__ __forceinline__ void block_argmax(unsigned int& hi, unsigned int& lo, unsigned int (*s_red)[2 * kBsWaves], int parity) {
-    const int lane = threadIdx.x & (OSQ_WAVE - 1), w = threadIdx.x / OSQ_WAVE;
-    const unsigned int wh = wave_max_u32(hi);
-    const unsigned int wl = wave_max_u32(hi == wh ? lo : 0u);
-    if (lane == 0) { s_red[parity][w] = wh; s_red[parity][kBsWaves + w] = wl; }
-    __syncthreads();
-    hi = s_red[parity][0];
-    lo = s_red[parity][kBsWaves];
-#pragma unroll
-    for (int k = 1; k < kBsWaves; ++k) {
-        const unsigned int h = s_red[parity][k], l = s_red[parity][kBsWaves + k];
-        if (h > hi || (h == hi && l > lo)) { hi = h; lo = l; }
-    }
-}
 
 __global__ __launch_bounds__(kBsThreads) void beam_partials_kernel(BeamArgs a) {
     __shared__ float s_red[2][kBsWaves];
@@ -150,23 +120,7 @@ __global__ __launch_bounds__(kBsThreads) void beam_chunk_kernel(BeamArgs a) {
     }
 
     // ---- the chunk's banned tokens
-    if (threadIdx.x < kBsChunk / 32) s_ban[threadIdx.x] = 0u;
-    __syncthreads();
-    if (threadIdx.x < n_ban) {
-        const int64_t t = a.ban_ids[threadIdx.x] - c0;
-        if (t >= 0 && t < len) atomicOr(&s_ban[t >> 5], 1u << (t & 31));
-    }
-    const int n = a.ngram;
-    if (n > 0 && cur >= n) {                                      // window i bans its last token when it starts with the suffix
-        const int64_t* s = a.seq + row * a.seq_stride;
-        const int64_t* suffix = s + (cur - n + 1);
-        for (int i = threadIdx.x; i <= cur - n; i += kBsThreads) {
-            bool same = true;
-            for (int k = 0; k < n - 1 && same; ++k) same = s[i + k] == suffix[k];
-            const int64_t t = s[i + n - 1] - c0;
-            if (same && t >= 0 && t < len) atomicOr(&s_ban[t >> 5], 1u << (t & 31));
-        }
-    }
+    chunk_bans(s_ban, a.ban_ids, n_ban, a.seq + row * a.seq_stride, cur, a.ngram, c0, len);
 
     // ---- m and L of the row: the same words in every workgroup of the row
     const float2* part = a.partials + row * a.chunks;

@@ -1,0 +1,69 @@
+// What beam_select.hip and greedy_advance.hip share: a row of logits cut into chunks of kBsChunk tokens, one 256-thread
+// workgroup per (row, chunk) holding 16 values per thread; the 64-bit candidate key; the workgroup arg-max over such keys; and
+// the chunk's bitmap of banned tokens (the min-length ids and the no-repeat-ngram rule).
+//
+// Order of a key: larger value first, NaN above every number; the low word carries ~position, so that among equal values the
+// smaller position wins and the arg-max is a max of (hi, lo) pairs.  Key 0 is no value's (-inf has 0x007fffff): it marks a
+// taken or absent candidate.  ordered_bits separates -0.0 from +0.0: a caller whose values can be -0.0 canonicalises first.
+#pragma once
+#include <hip/hip_runtime.h>
+#include "osq_device.h"
+
+namespace osq {
+
+constexpr int kBsThreads = 256;
+constexpr int kBsWaves = kBsThreads / OSQ_WAVE;
+constexpr int kBsPer = 16;                          // elements of a chunk one thread holds
+constexpr int kBsChunk = kBsThreads * kBsPer;       // 4096 tokens
+constexpr int kBsMaxCur = 4096, kBsMaxBan = 16;
+
+struct BeamCand {              // one candidate in the workspace
+    unsigned int key;          // beam_key(value); 0: none
+    int token;
+};
+
+__device__ __forceinline__ unsigned int beam_key(float v) { return v != v ? 0xffffffffu : ordered_bits(v); }
+__device__ __forceinline__ float beam_value(unsigned int key) {
+    return key == 0xffffffffu ? __builtin_nanf("") : from_ordered_bits(key);
+}
+
+// The largest (hi, lo) pair of the workgroup, lexicographically, in every thread.  s_red: [2][2 * kBsWaves] words, the two
+// halves used by alternate calls (`parity`), so one barrier per call is enough.
+__device__ __forceinline__ void block_argmax(unsigned int& hi, unsigned int& lo, unsigned int (*s_red)[2 * kBsWaves], int parity) {
+    const int lane = threadIdx.x & (OSQ_WAVE - 1), w = threadIdx.x / OSQ_WAVE;
+    const unsigned int wh = wave_max_u32(hi);
+    const unsigned int wl = wave_max_u32(hi == wh ? lo : 0u);
+    if (lane == 0) { s_red[parity][w] = wh; s_red[parity][kBsWaves + w] = wl; }
+    __syncthreads();
+    hi = s_red[parity][0];
+    lo = s_red[parity][kBsWaves];
+#pragma unroll
+    for (int k = 1; k < kBsWaves; ++k) {
+        const unsigned int h = s_red[parity][k], l = s_red[parity][kBsWaves + k];
+        if (h > hi || (h == hi && l > lo)) { hi = h; lo = l; }
+    }
+}
+
+// The banned tokens of the chunk [c0, c0 + len) of one row into s_ban (kBsChunk / 32 words, one bit per token): the n_ban ids
+// of ban_ids, and, with n = ngram > 0 and cur >= n, the last token of every window of s[0 : cur] that starts with the suffix
+// s[cur - n + 1 : cur].  s is read only then.  The caller's next barrier publishes the bitmap.
+__device__ __forceinline__ void chunk_bans(unsigned int* s_ban, const int64_t* ban_ids, int n_ban, const int64_t* s, int cur,
+                                           int n, int c0, int len) {
+    if (threadIdx.x < kBsChunk / 32) s_ban[threadIdx.x] = 0u;
+    __syncthreads();
+    if (threadIdx.x < n_ban) {
+        const int64_t t = ban_ids[threadIdx.x] - c0;
+        if (t >= 0 && t < len) atomicOr(&s_ban[t >> 5], 1u << (t & 31));
+    }
+    if (n > 0 && cur >= n) {                                      // window i bans its last token when it starts with the suffix
+        const int64_t* suffix = s + (cur - n + 1);
+        for (int i = threadIdx.x; i <= cur - n; i += kBsThreads) {
+            bool same = true;
+            for (int k = 0; k < n - 1 && same; ++k) same = s[i + k] == suffix[k];
+            const int64_t t = s[i + n - 1] - c0;
+            if (same && t >= 0 && t < len) atomicOr(&s_ban[t >> 5], 1u << (t & 31));
+        }
+    }
+}
+
+}  // namespace osq

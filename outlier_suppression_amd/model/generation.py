@@ -18,6 +18,15 @@ buffers; ``model.last_beam_advance`` tells how many steps took it.  ``beam_graph
 and captures the whole step -- token copy, model, selection, bookkeeping, the cache's row index -- into one graph per
 direction of the alternating buffers (graph_decode.BeamStepGraphs): a token costs the host one replay and one read of the
 stopping word; ``model.last_beam_graph`` tells what happened.
+
+Greedy decoding has the same two steps off the host.  ``greedy_advance=True`` (set_greedy_advance) hands everything after the
+model step -- the banned tokens of the logits processors, the arg-max, the pad / eos arithmetic, the new token into the
+sequence, the stopping word -- to one kernel call (ops.greedy_advance) on one set of state buffers (ops.GreedyBuffers): the
+model is fed the kernel's next_tokens and the host reads go_on once per token; ``model.last_greedy_advance`` tells how many
+steps took it.  The tokens are those of the torch lines with no tolerance: the kernel's order is torch.argmax's.
+``greedy_graph=True`` (set_greedy_graph) asks for ``graph`` and ``greedy_advance`` and captures the whole step -- token copy,
+model, ops.greedy_advance_at -- into one graph (graph_decode.GreedyStepGraph), forced tokens included: a token costs the host
+one replay and one read of the stopping word; ``model.last_greedy_graph`` tells what happened.
 """
 import torch
 from torch import nn
@@ -249,7 +258,7 @@ def _advance_beams_torch(state, top_lp, top_idx, cur, vocab, eos, top_mask, offs
 
 
 def generate(model, input_ids, attention_mask=None, max_length=None, num_beams=None, use_cache=True, cache_codes=None,
-             graph=None, beam_select=None, beam_advance=None, beam_graph=None, **kwargs):
+             graph=None, beam_select=None, beam_advance=None, beam_graph=None, greedy_advance=None, greedy_graph=None, **kwargs):
     if kwargs.pop("synced_gpus", False):      # Seq2SeqTrainer's predict_with_generate passes synced_gpus=False
         raise NotImplementedError("generate(): synced_gpus=True is not supported")
     for name in _NOT_COVERED:
@@ -286,6 +295,15 @@ def generate(model, input_ids, attention_mask=None, max_length=None, num_beams=N
                                            {"graph": graph, "beam_select": beam_select, "beam_advance": beam_advance})
         if whole.reason is None:
             graph = beam_select = beam_advance = True
+    # a whole greedy step as one captured graph: likewise, for the two switches it implies
+    gwhole = graph_decode.GreedyGraphInfo(None if (util_layernorm.GREEDY_GRAPH if greedy_graph is None else greedy_graph)
+                                          else "not asked for")
+    model.last_greedy_graph = gwhole
+    if gwhole.reason is None:
+        gwhole.reason = _greedy_graph_why_not(model, enc.device, use_cache, max_length, num_beams, eos_t, pad, procs,
+                                              {"graph": graph, "greedy_advance": greedy_advance})
+        if gwhole.reason is None:
+            graph = greedy_advance = True
     # a captured decoding step (model/graph_decode.py), where asked for and possible; else the steps are issued as ever
     stepper = None
     if util_layernorm.GRAPH_DECODE if graph is None else graph:
@@ -299,6 +317,11 @@ def generate(model, input_ids, attention_mask=None, max_length=None, num_beams=N
     model.last_beam_select = select
     advance = BeamAdvanceInfo(None if (util_layernorm.BEAM_ADVANCE if beam_advance is None else beam_advance) else "not asked for")
     model.last_beam_advance = advance
+    greedy = GreedyAdvanceInfo(None if (util_layernorm.GREEDY_ADVANCE if greedy_advance is None else greedy_advance)
+                               else "not asked for")
+    model.last_greedy_advance = greedy
+    if num_beams != 1 and greedy.reason is None:
+        greedy.reason = "beam search has no greedy step"
     if num_beams == 1:
         if select.reason is None:
             select.reason = "greedy decoding selects no beams"
@@ -306,7 +329,13 @@ def generate(model, input_ids, attention_mask=None, max_length=None, num_beams=N
             advance.reason = "greedy decoding advances no beams"
         if n_return != 1:
             raise ValueError("greedy decoding returns one sequence per input (num_return_sequences must be 1)")
-        return _checked(cache, _greedy(model, enc, attention_mask, start, pad, eos_t, procs, max_length, cache, stepper))
+        if greedy.reason is None:
+            plan = _GreedyPlan(procs, enc.device, model.config.vocab_size, max_length, eos_t, pad)
+            greedy.reason = plan.reason
+        if greedy.reason is None:
+            return _checked(cache, _greedy_advanced(model, enc, attention_mask, start, plan, max_length, cache, stepper, greedy,
+                                                    gwhole if gwhole.reason is None else None))
+        return _checked(cache, _greedy(model, enc, attention_mask, start, pad, eos_t, procs, max_length, cache, stepper, greedy))
     if n_return > num_beams:
         raise ValueError("num_return_sequences must not exceed num_beams")
     return _checked(cache, _beam_search(model, enc, attention_mask, start, pad, eos_t, procs, max_length, num_beams, n_return,
@@ -346,7 +375,7 @@ def _checked(cache, tokens):
     return tokens
 
 
-def _greedy(model, enc, attention_mask, start, pad, eos, procs, max_length, cache, stepper=None):
+def _greedy(model, enc, attention_mask, start, pad, eos, procs, max_length, cache, stepper=None, advance=None):
     b = enc.shape[0]
     seq = torch.full((b, 1), start, dtype=torch.long, device=enc.device)
     unfinished = torch.ones(b, dtype=torch.long, device=enc.device)
@@ -356,11 +385,128 @@ def _greedy(model, enc, attention_mask, start, pad, eos, procs, max_length, cach
         if eos is not None:
             nxt = nxt * unfinished + pad * (1 - unfinished)
         seq = torch.cat([seq, nxt[:, None]], dim=-1)
+        if advance is not None:
+            advance.eager += 1
         if eos is not None:
             unfinished = unfinished & ~torch.isin(nxt, eos)
             if unfinished.max() == 0:
                 break
     return seq
+
+
+class GreedyAdvanceInfo:
+    """What a generate() call did with its greedy steps: ``advanced`` steps through ops.greedy_advance, ``eager`` steps
+    through the torch lines, and, when none was advanced, the ``reason``."""
+
+    def __init__(self, reason=None):
+        self.advanced, self.eager, self.reason = 0, 0, reason
+
+    def __repr__(self):
+        return f"GreedyAdvanceInfo(advanced={self.advanced}, eager={self.eager}, reason={self.reason!r})"
+
+
+class _GreedyPlan:
+    """What ops.greedy_advance needs from a call's settings, read once: the n-gram size, min_length with its eos ids on the
+    device, the forced tokens, the eos ids and the pad -- or the ``reason`` the torch lines run instead."""
+
+    def __init__(self, procs, device, vocab, max_length, eos, pad):
+        from transformers.generation.logits_process import (ForcedBOSTokenLogitsProcessor, ForcedEOSTokenLogitsProcessor,
+                                                            MinLengthLogitsProcessor, NoRepeatNGramLogitsProcessor)
+        self.ngram, self.min_length, self.ban, self.forced_bos, self.forced_eos = 0, 0, None, None, None
+        self.eos = None if eos is None else eos.to(device=device, dtype=torch.int64).reshape(-1).contiguous()
+        self.pad = 0 if pad is None else int(pad)
+        self.max_length = max_length
+        self.reason = None
+        if device.type != "cuda":
+            self.reason = "the tensors are on the CPU"
+        elif torch.is_grad_enabled():
+            self.reason = "autograd is on"
+        elif not 2 <= max_length <= 4096:
+            self.reason = "the kernel takes max_length in [2, 4096]"
+        elif self.eos is not None and self.eos.numel() > 16:
+            self.reason = "more than 16 eos ids"
+        elif self.eos is not None and pad is None:
+            self.reason = "pad_token_id is missing and an eos is set"
+        elif self.eos is not None and not 0 <= self.pad < vocab:
+            self.reason = "pad_token_id is outside the vocabulary"
+        for proc in procs:
+            if self.reason is not None:
+                break
+            if type(proc) is NoRepeatNGramLogitsProcessor and self.ngram == 0:
+                self.ngram = int(proc.ngram_size)
+            elif type(proc) is MinLengthLogitsProcessor and self.ban is None:
+                self.min_length = int(proc.min_length)
+                self.ban = proc.eos_token_id.to(device=device, dtype=torch.int64).reshape(-1).contiguous()
+                if self.ban.numel() > 16:
+                    self.reason = "more than 16 eos ids"
+            elif type(proc) is ForcedBOSTokenLogitsProcessor and self.forced_bos is None:
+                self.forced_bos = int(proc.bos_token_id)
+            elif (type(proc) is ForcedEOSTokenLogitsProcessor and self.forced_eos is None and proc.eos_token_id.numel() == 1
+                  and int(proc.max_length) == max_length):
+                self.forced_eos = int(proc.eos_token_id.reshape(-1)[0])
+            else:
+                self.reason = f"a logits processor the kernel does not restate ({type(proc).__name__})"
+        if self.reason is None and any(t is not None and not 0 <= t < vocab for t in (self.forced_bos, self.forced_eos)):
+            self.reason = "a forced token is outside the vocabulary"
+
+    def forced(self, cur):
+        """The token the processors force at history length ``cur`` (the later processor wins), or None."""
+        if self.forced_eos is not None and cur == self.max_length - 1:
+            return self.forced_eos
+        return self.forced_bos if cur == 1 else None
+
+
+def _greedy_graph_why_not(model, device, use_cache, max_length, nb, eos, pad, procs, given):
+    """None when a generate() call can capture its greedy steps whole, else the reason it decodes as without
+    ``greedy_graph``: one of the two switches it implies was passed as False, the search has beams, or one of them would
+    give a reason."""
+    from . import graph_decode
+    for name, value in given.items():
+        if value is not None and not value:
+            return f"{name}=False was passed"
+    if nb != 1:
+        return "beam search has no greedy step"
+    return (graph_decode.why_not(model, device, use_cache, max_length)
+            or _GreedyPlan(procs, device, model.config.vocab_size, max_length, eos, pad).reason)
+
+
+def _greedy_advanced(model, enc, attention_mask, start, plan, max_length, cache, stepper, advance, whole=None):
+    """The loop of _greedy with everything after the model step as one call of ops.greedy_advance: the sequence, the
+    unfinished flags and the next tokens live in an ops.GreedyBuffers, the model is fed the kernel's next_tokens (without a
+    cache: the sequence so far, a view), and the go_on word is read once per token (the one host sync of the torch lines).
+
+    ``whole`` (a graph_decode.GreedyGraphInfo; generate(greedy_graph=True)): from the third step on a step is one replay of
+    a captured graph that holds all of the above (graph_decode.GreedyStepGraph), a step on which a forced token fires
+    included: the kernel takes the forced token itself."""
+    from .. import ops
+    from . import graph_decode
+    bufs = ops.GreedyBuffers(enc.shape[0], max_length, enc.device, model.config.vocab_size)
+    bufs.seq[:, 0] = start
+    cur = 1
+    captured = None
+    while True:
+        if whole is not None and captured is None and cur == 3:
+            if stepper is None or stepper.decoder is None:          # the cache the first step left does not fit
+                whole.reason, whole = stepper.info.reason if stepper is not None else "no captured step", None
+            else:
+                captured = graph_decode.GreedyStepGraph(stepper.decoder, whole, bufs, plan)
+        if captured is not None:
+            captured.step()
+        else:
+            tokens = bufs.seq[:, :cur] if cache is None or cur == 1 else bufs.next_tokens.view(-1, 1)
+            logits = _step_logits(model, tokens, enc, attention_mask, cache, stepper).to(torch.float32)
+            ops.greedy_advance(logits, bufs, cur, plan.ngram, plan.ban if cur < plan.min_length else None, plan.forced(cur),
+                               plan.eos, plan.pad)
+        cur += 1
+        advance.advanced += 1
+        go_on = int(bufs.go_on)
+        if go_on < 0:
+            raise RuntimeError(f"generate(): a captured greedy step met the position {cur - 1}, outside [1, {max_length})")
+        if not go_on:
+            break
+    if whole is not None and whole.captured == 0:
+        whole.reason = "the search ended before a step could be captured"
+    return bufs.seq[:, :cur]
 
 
 def _gather(t, idx):

@@ -27,6 +27,11 @@ buffers into the other, the copy of the new beam_idx into the cache's row index.
 set 0 -> 1 and the reverse; per token the host does the cache's bookkeeping, one replay and one read of go_on.  A step on
 which a forced token fires is issued launch by launch on the capture stream (GraphDecoder.issue), as step 1 is.
 
+A whole greedy step (GreedyStepGraph; generate(greedy_graph=True)) is the same idea with no beam state: the copy of the
+search's next_tokens into the token buffer, the model step, and ops.greedy_advance_at on the graph's own logits with the
+cache's position word -- bans, arg-max, pad / eos, the new token into the sequence, go_on.  One graph, keyed as the in-place
+graph above; the kernel takes a forced token itself at its position, so no step is issued launch by launch.
+
 The words are those of issuing the same steps one by one with the one-launch attention on (util_layernorm.
 FUSE_DECODE_ATTENTION): a captured step always uses it, cross-attention included, whatever the switch says.
 """
@@ -256,6 +261,59 @@ class BeamStepGraphs:
         self.info.replays += 1
         decoder.info.replays += 1
         return spare
+
+
+class GreedyGraphInfo:
+    """What a generate() call did with ``greedy_graph``: ``captured`` whole-step graphs, ``replays`` of them, and, when the
+    call decoded as without the switch, the ``reason``.  ``capture_seconds``: host time spent capturing and instantiating."""
+
+    def __init__(self, reason=None):
+        self.captured, self.replays, self.reason, self.capture_seconds = 0, 0, reason, 0.0
+
+    def __repr__(self):
+        return f"GreedyGraphInfo(captured={self.captured}, replays={self.replays}, reason={self.reason!r})"
+
+
+class GreedyStepGraph:
+    """Whole greedy steps of one generate() call as a captured graph, over a warm GraphDecoder, the ops.GreedyBuffers
+    ``buffers`` of the search and its ``plan`` (generation._GreedyPlan).  ``step()`` takes one step in place -- token copy,
+    model step, bans, arg-max, pad / eos, the new token into buffers.seq -- by one replay; the caller reads buffers.go_on."""
+
+    def __init__(self, decoder, info, buffers, plan):
+        self.decoder, self.info, self.buffers, self.plan = decoder, info, buffers, plan
+        self.graphs = {}
+
+    def _chain(self):
+        """One step's launches, in order, on the current (capturing) stream."""
+        from .. import ops
+        decoder, bufs, plan = self.decoder, self.buffers, self.plan
+        decoder.tokens.copy_(bufs.next_tokens.view(-1, 1))
+        logits = decoder._issue().to(torch.float32)
+        cur = decoder.cache.position()              # after the decoder's increment: the length of the history, this step's cur
+        ops.greedy_advance_at(logits, bufs, cur, 0, ngram=plan.ngram, ban_ids=plan.ban, ban_below=plan.min_length,
+                              forced_bos=plan.forced_bos, forced_eos=plan.forced_eos, eos_ids=plan.eos, pad=plan.pad)
+        return logits
+
+    def step(self):
+        decoder, cache = self.decoder, self.decoder.cache
+        decoder.check_room()
+        key = (cache.reorder_pending(), cache._k[0].data_ptr())
+        entry = self.graphs.get(key)
+        if entry is None:
+            t0 = time.perf_counter()
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph, stream=decoder.stream):
+                logits = self._chain()              # recorded, not run; the cache's host side of the step is now done
+            entry = self.graphs[key] = (graph, logits)
+            self.info.captured += 1
+            self.info.capture_seconds += time.perf_counter() - t0
+            decoder.info.captured += 1
+            decoder.info.capture_seconds += time.perf_counter() - t0
+        else:
+            cache.stepped()
+        entry[0].replay()
+        self.info.replays += 1
+        decoder.info.replays += 1
 
 
 class GenerateStepper:

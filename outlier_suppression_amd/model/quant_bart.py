@@ -948,7 +948,13 @@ class QuantizedBartForConditionalGeneration(QuantizedModule):
         ``self.last_beam_advance`` then says how many steps took it (advanced, eager, reason).  ``beam_graph``: beam search
         captures a whole step -- model, selection, bookkeeping -- into one graph and replays it (None: the package switch,
         set_beam_graph; it implies the three above for the call; model/graph_decode.py, BeamStepGraphs);
-        ``self.last_beam_graph`` then says what happened (captured, replays, issued, reason)."""
+        ``self.last_beam_graph`` then says what happened (captured, replays, issued, reason).  ``greedy_advance``: greedy
+        decoding takes everything after the model step -- processors, arg-max, pad / eos, the stopping word -- with one kernel
+        call per token (None: the package switch, set_greedy_advance; ops.greedy_advance); ``self.last_greedy_advance`` then
+        says how many steps took it (advanced, eager, reason).  ``greedy_graph``: greedy decoding captures a whole step into
+        one graph and replays it (None: the package switch, set_greedy_graph; it implies ``graph`` and ``greedy_advance`` for
+        the call; model/graph_decode.py, GreedyStepGraph); ``self.last_greedy_graph`` then says what happened (captured,
+        replays, reason)."""
         return generation.generate(self, input_ids, attention_mask=attention_mask, max_length=max_length,
                                    num_beams=num_beams, **kwargs)
 

@@ -2094,3 +2094,102 @@ def beam_advance_at(top_lp, top_idx, state, out, cur, cur_add, vocab, len_table,
                                  out.workspace.numel(), _hip.raw_stream(device))
     _hip.check(rc, "beam_advance_at")
     return out
+
+
+class GreedyBuffers:
+    """The state of a greedy search on a device, as osq_greedy_advance reads and writes it: ``seq`` [bsz, max_length] int64
+    (the token history, filled up to the current length), ``unfinished`` [bsz] uint8, and what a step writes beside them:
+    ``next_tokens`` [bsz] int64 (= seq[:, cur]), the ``go_on`` int32 word and the call's ``workspace`` (sized on first use:
+    it depends on the vocabulary -- or here, given ``vocab``)."""
+
+    def __init__(self, bsz, max_length, device, vocab=None):
+        self.seq = torch.zeros((bsz, max_length), dtype=torch.int64, device=device)
+        self.unfinished = torch.ones(bsz, dtype=torch.uint8, device=device)
+        self.next_tokens = torch.zeros(bsz, dtype=torch.int64, device=device)
+        self.go_on = torch.zeros(1, dtype=torch.int32, device=device)
+        self.workspace = None
+        if vocab is not None:
+            self.room(vocab)
+
+    def room(self, vocab):
+        """The workspace for rows of ``vocab`` logits (allocated once: a captured step names it)."""
+        nbytes = max(int(_hip.load().osq_greedy_advance_workspace_bytes(self.seq.shape[0], int(vocab))), 8)
+        if self.workspace is None or self.workspace.numel() < nbytes:
+            self.workspace = torch.empty(nbytes, dtype=torch.uint8, device=self.seq.device)
+        return self.workspace
+
+
+def _greedy_advance_operands(what, logits, buffers, ban_ids, eos_ids):
+    """The checks greedy_advance and greedy_advance_at share; (head, tail): the arguments before the position and from
+    eos_ids on."""
+    seq, unfinished, next_tokens, go_on = buffers.seq, buffers.unfinished, buffers.next_tokens, buffers.go_on
+    _hip.require_device(logits, seq, unfinished, next_tokens, go_on, ban_ids, eos_ids)
+    _check_f32(logits)
+    if logits.dim() != 2 or seq.dim() != 2 or seq.dtype != torch.int64:
+        raise ValueError(f"{what}: logits must be fp32 [bsz, vocab] and buffers.seq int64 [bsz, max_length]")
+    bsz, vocab = logits.shape
+    max_length = seq.shape[1]
+    if (vocab > 1 and logits.stride(1) != 1) or (bsz > 1 and logits.stride(0) < vocab):
+        raise ValueError(f"{what}: logits must have a dense last axis")
+    if seq.shape[0] != bsz or (max_length > 1 and seq.stride(1) != 1) or (bsz > 1 and seq.stride(0) < max_length):
+        raise ValueError(f"{what}: buffers.seq must hold bsz rows with a dense last axis")
+    for name, t, dtype in (("unfinished", unfinished, torch.uint8), ("next_tokens", next_tokens, torch.int64)):
+        if t.dtype != dtype or tuple(t.shape) != (bsz,) or not t.is_contiguous():
+            raise ValueError(f"{what}: buffers.{name} must be a contiguous {dtype} [bsz] tensor")
+    if go_on.dtype != torch.int32 or go_on.numel() != 1:
+        raise ValueError(f"{what}: buffers.go_on must be one int32")
+    counts = []
+    for name, ids in (("ban_ids", ban_ids), ("eos_ids", eos_ids)):
+        if ids is not None and (ids.dtype != torch.int64 or ids.dim() != 1 or not ids.is_contiguous()):
+            raise ValueError(f"{what}: {name} must be a contiguous 1-d int64 tensor")
+        counts.append(0 if ids is None else ids.numel())
+    device = logits.device
+    every = [seq, unfinished, next_tokens, go_on] + [t for t in (ban_ids, eos_ids) if t is not None]
+    if any(t.device != device for t in every):
+        raise ValueError(f"{what}: all tensors must be on one device")
+    ws = buffers.room(vocab)
+    head = (logits.data_ptr(), logits.stride(0) if bsz > 1 else vocab, seq.data_ptr(), seq.stride(0) if bsz > 1 else max_length)
+    return head, counts, (bsz, vocab, max_length, next_tokens.data_ptr(), go_on.data_ptr(), ws.data_ptr(), ws.numel(),
+                          _hip.raw_stream(device))
+
+
+def greedy_advance(logits, buffers, cur, ngram=0, ban_ids=None, forced=None, eos_ids=None, pad=0):
+    """One greedy decoding step after the model (osq_greedy_advance, csrc/greedy_advance.hip): from the fp32 ``logits``
+    [bsz, vocab] (a dense last axis, any row stride) and ``buffers`` (a GreedyBuffers) at history length ``cur`` -- the banned
+    tokens (``ban_ids``: None or up to 16 int64 ids on the device; ``ngram``: the no-repeat-ngram size), the arg-max of every
+    row in torch.argmax's order (or ``forced``, a token id, whatever the logits hold), with ``eos_ids`` (None or up to 16 int64
+    ids on the device) the ``pad`` of finished rows and the update of ``buffers.unfinished`` -- into ``buffers.seq[:, cur]``,
+    ``buffers.next_tokens`` and the ``buffers.go_on`` word: what generation._greedy computes, token for token.
+    Three launches on the current stream, no synchronisation; returns ``buffers``, or None when the library does not take
+    the call (the caller takes its other path)."""
+    lib = _hip.load()
+    head, (n_ban, n_eos), tail = _greedy_advance_operands("greedy_advance", logits, buffers, ban_ids, eos_ids)
+    rc = lib.osq_greedy_advance(*head, int(cur), int(ngram), _hip.ptr(ban_ids) if n_ban else None, n_ban,
+                                -1 if forced is None else int(forced), _hip.ptr(eos_ids) if n_eos else None, n_eos, int(pad),
+                                buffers.unfinished.data_ptr(), *tail)
+    if rc == _hip.ERR_UNSUPPORTED:
+        return None
+    _hip.check(rc, "greedy_advance")
+    return buffers
+
+
+def greedy_advance_at(logits, buffers, cur, cur_add=0, ngram=0, ban_ids=None, ban_below=0, forced_bos=None, forced_eos=None,
+                      eos_ids=None, pad=0):
+    """greedy_advance with the position read by the launches (osq_greedy_advance_at): ``cur`` is one int32 on the device and
+    the step is taken at length ``*cur + cur_add``, so a captured graph of the call serves every step.  ``ban_ids`` apply while
+    the length is below ``ban_below`` (the min-length rule), ``forced_bos`` is the token at length 1 and ``forced_eos`` the
+    token at length max_length - 1 (it wins where both fire).  For a length in [1, max_length) everything written is word-equal
+    to ``greedy_advance`` at that length; outside it ``buffers.go_on`` receives -1 and nothing else is written."""
+    lib = _hip.load()
+    head, (n_ban, n_eos), tail = _greedy_advance_operands("greedy_advance_at", logits, buffers, ban_ids, eos_ids)
+    _hip.require_device(cur)
+    if cur.dtype != torch.int32 or cur.numel() != 1 or cur.device != logits.device:
+        raise TypeError("greedy_advance_at: cur must be one int32 on the device of logits")
+    rc = lib.osq_greedy_advance_at(*head, cur.data_ptr(), int(cur_add), int(ngram), _hip.ptr(ban_ids) if n_ban else None, n_ban,
+                                   int(ban_below), -1 if forced_bos is None else int(forced_bos),
+                                   -1 if forced_eos is None else int(forced_eos), _hip.ptr(eos_ids) if n_eos else None, n_eos,
+                                   int(pad), buffers.unfinished.data_ptr(), *tail)
+    if rc == _hip.ERR_UNSUPPORTED:
+        return None
+    _hip.check(rc, "greedy_advance_at")
+    return buffers

@@ -65,6 +65,19 @@ sets of device buffers.  Word-equal to the torch lines where those have no ties;
 direction of the alternating buffers and replays it (model/graph_decode.py, BeamStepGraphs); a token then costs the host one
 replay and one read of the stopping word.  For its call it implies the three switches above; the words are theirs.
 ``outlier_suppression_amd.set_beam_graph(True)`` / ``OSQ_BEAM_GRAPH=1`` / ``generate(..., beam_graph=True)`` turn it on.
+
+``GREEDY_ADVANCE`` (default OFF): greedy decoding hands everything after the model step -- the banned tokens of the logits
+processors, the arg-max, the pad / eos arithmetic, the new token into the sequence and the stopping word -- to
+``ops.greedy_advance`` (csrc/greedy_advance.hip) instead of the torch lines; the state then lives in one set of device buffers.
+Token-for-token equal to the torch lines: the kernel's order is torch.argmax's (first maximum, NaN above every number).
+``outlier_suppression_amd.set_greedy_advance(True)`` / ``OSQ_GREEDY_ADVANCE=1`` / ``generate(..., greedy_advance=True)`` turn
+it on.
+
+``GREEDY_GRAPH`` (default OFF): greedy decoding captures a WHOLE step -- the token copy, the model step and
+``ops.greedy_advance_at`` on the graph's own logits -- into one graph and replays it (model/graph_decode.py, GreedyStepGraph),
+forced tokens included; a token then costs the host one replay and one read of the stopping word.  For its call it implies
+``GRAPH_DECODE`` and ``GREEDY_ADVANCE``.
+``outlier_suppression_amd.set_greedy_graph(True)`` / ``OSQ_GREEDY_GRAPH=1`` / ``generate(..., greedy_graph=True)`` turn it on.
 """
 import torch
 import torch.nn.functional as F
@@ -84,6 +97,8 @@ GRAPH_DECODE = False     # generate(): capture a cached decoding step into a gra
 BEAM_SELECT = False      # generate(): a beam step's log-softmax + processors + score add + top-k as one kernel call (tolerance-equal; set_beam_select / OSQ_BEAM_SELECT=1 / generate(beam_select=True))
 BEAM_ADVANCE = False     # generate(): a beam step's bookkeeping after the selection as one kernel call on alternating state buffers (set_beam_advance / OSQ_BEAM_ADVANCE=1 / generate(beam_advance=True))
 BEAM_GRAPH = False       # generate(): capture a whole beam-search step -- model, selection, bookkeeping, cache row index -- into one graph (implies the three above for the call; set_beam_graph / OSQ_BEAM_GRAPH=1 / generate(beam_graph=True))
+GREEDY_ADVANCE = False   # generate(): a greedy step's processors, arg-max, pad / eos lines, sequence append and stopping word as one kernel call (set_greedy_advance / OSQ_GREEDY_ADVANCE=1 / generate(greedy_advance=True))
+GREEDY_GRAPH = False     # generate(): capture a whole greedy step -- token copy, model, the kernel call above -- into one graph (implies GRAPH_DECODE and GREEDY_ADVANCE for the call; set_greedy_graph / OSQ_GREEDY_GRAPH=1 / generate(greedy_graph=True))
 CACHE_CODES = False      # incremental decoding: new KV caches hold integer codes, one byte per element (same words read back; set_cache_codes / OSQ_CACHE_CODES=1)
 
 

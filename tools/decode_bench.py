@@ -29,6 +29,14 @@ switch off and on.  Every form is timed in turn within each of the --reps rounds
 BeamStepGraphs) against generate(graph=True, beam_select=True, beam_advance=True), where the selection and the bookkeeping
 are issued between the replays: the whole call with no_repeat_ngram_size 0 and 3, the fp32 and the coded cache; every form
 is timed in turn within each of the --reps rounds, in one process; capture + instantiate time is reported apart.
+--greedy-advance: the A/B is greedy decoding with everything after the model step as one kernel call (ops.greedy_advance,
+csrc/greedy_advance.hip; generate(greedy_advance=True)) and with the whole step as one captured graph
+(generate(greedy_graph=True); graph_decode.GreedyStepGraph) against generate(graph=True), the best greedy form before them:
+generate(num_beams=1, max_length=62, min_length=62) at batch 32 with no_repeat_ngram_size 0 and 3, the three forms with graphs
+and the same three issued launch by launch (the one-launch attention on, so that every form computes the same words; asked
+with graph=False, greedy_graph decodes as without it); then the bookkeeping alone -- the torch lines of generation._greedy
+against the kernel call, each with its read of the stopping word -- on [32, 50265] logits at length 31.  The tokens of all
+forms are asserted equal before a time is printed; every form is timed in turn within each of the --reps rounds, in one process.
 
     python tools/decode_bench.py [--reps 7] [--out profiles/decode_step_ab.txt]
     python tools/decode_bench.py --fast-decode-attention [--out profiles/decode_attention_ab.txt]
@@ -37,6 +45,7 @@ is timed in turn within each of the --reps rounds, in one process; capture + ins
     python tools/decode_bench.py --beam-select [--out profiles/beam_select_ab.txt]
     python tools/decode_bench.py --beam-advance [--out profiles/beam_advance_ab.txt]
     python tools/decode_bench.py --beam-graph [--out profiles/beam_graph_ab.txt]
+    python tools/decode_bench.py --greedy-advance [--out profiles/greedy_advance_ab.txt]
 """
 import argparse
 import copy
@@ -463,6 +472,105 @@ def beam_graph_ab(q, ids, mask, args):
     return lines
 
 
+# (label, generate()'s switches) of the forms --greedy-advance compares; the first is the baseline of its group
+GREEDY_FORMS = [("graph", dict(graph=True)),
+                ("graph + greedy_advance", dict(graph=True, greedy_advance=True)),
+                ("greedy_graph", dict(greedy_graph=True)),
+                ("issued", dict(graph=False)),
+                ("issued + greedy_advance", dict(graph=False, greedy_advance=True)),
+                ("issued, greedy_graph asked (falls back)", dict(graph=False, greedy_graph=True))]
+
+
+def greedy_advance_ab(q, ids, mask, args):
+    from outlier_suppression_amd import ops, util_layernorm as UL
+    from outlier_suppression_amd.model import generation
+    dev = ids.device
+    bsz, vocab, at, max_length = args.batch, q.config.vocab_size, 31, 62
+    lines = [f"greedy decoding: everything after the model step as one kernel call (ops.greedy_advance) and the whole step as one "
+             f"captured graph (greedy_graph) against generate(graph=True); BART-large shape, batch {bsz}, source {args.src}, "
+             f"generate(num_beams=1, max_length={max_length}, min_length={max_length}) (BART's forced eos on the last step); the "
+             f"one-launch attention on in the issued forms as in the graphs; every form timed in turn in each of {args.reps} "
+             f"rounds, one process; median [min, max]"]
+    print(lines[0], flush=True)
+    old = UL.FUSE_DECODE_ATTENTION
+    UL.FUSE_DECODE_ATTENTION = True                 # the issued forms run the launches the graphs hold: the same words
+    try:
+        with torch.no_grad():
+            for ngram in (0, 3):
+                kw = dict(num_beams=1, max_length=max_length, min_length=max_length, no_repeat_ngram_size=ngram)
+                times = {label: [] for label, _ in GREEDY_FORMS}
+                tokens, did = {}, {}
+                for r in range(args.reps + 1):      # the first round warms every form up
+                    for label, switches in GREEDY_FORMS:
+                        secs, tokens[label] = _timed(lambda: q.generate(ids, attention_mask=mask, **kw, **switches), 1.0)
+                        did[label] = (q.last_greedy_advance.advanced, q.last_greedy_advance.eager, q.last_decode_graph.captured,
+                                      q.last_decode_graph.replays, q.last_greedy_graph.captured)
+                        if r:
+                            times[label].append(secs)
+                first = tokens[GREEDY_FORMS[0][0]]
+                for label, t in tokens.items():     # before a time is printed
+                    assert t.shape == first.shape and bool(torch.equal(t, first)), f"{label}: tokens differ from graph=True"
+                assert did["greedy_graph"][4] == 1 and did["graph + greedy_advance"][:2] == (max_length - 1, 0), did
+                block = [f"no_repeat_ngram_size {ngram}: tokens {tuple(first.shape)} equal in all {len(tokens)} forms; s, wall time "
+                         "of the call (a graph form: capture included); (steps through the kernel, through torch, graphs "
+                         "captured, replays, whole-step graphs):"]
+                block += [f"    {label:42s} {_stats(t)}   {did[label]}" for label, t in times.items()]
+                for group in (GREEDY_FORMS[:3], GREEDY_FORMS[3:5]):
+                    base = sorted(times[group[0][0]])
+                    spread = base[-1] - base[0]
+                    for label, _ in group[1:]:
+                        mine = sorted(times[label])
+                        gain = base[len(base) // 2] - mine[len(mine) // 2]
+                        block.append(f"    {label} against {group[0][0]}: median gain {gain * 1e3:.1f} ms "
+                                     f"({gain / (max_length - 1) * 1e3:.3f} ms per token, {gain / base[len(base) // 2] * 100:.1f} %), "
+                                     f"the baseline's own spread {spread * 1e3:.1f} ms: "
+                                     f"{'above' if gain > spread else 'within'} it")
+                print("\n".join(block), flush=True)
+                lines += block
+
+            # the bookkeeping alone at length `at`: min_length active, one eos id, every row unfinished
+            g = torch.Generator(device="cpu").manual_seed(3)
+            logits = (torch.randn(bsz, vocab, generator=g) * 4).to(dev)
+            history = torch.randint(3, 40, (bsz, at), generator=g).to(dev)
+            eos = torch.tensor([2], device=dev)
+            lines.append(f"the greedy bookkeeping alone (with the read of the stopping word), logits [{bsz}, {vocab}] fp32 (randn * 4), "
+                         f"history of {at} tokens, min_length {max_length} active, one eos id, ms:")
+            for ngram in (0, 3):
+                procs = generation._processors(max_length, eos, ngram, None, 2, max_length, dev)
+                plan = generation._GreedyPlan(procs, dev, vocab, max_length, eos, 1)
+                assert plan.reason is None, plan.reason
+                bufs = ops.GreedyBuffers(bsz, max_length, dev, vocab)
+                bufs.seq[:, :at] = history
+
+                def torch_lines():
+                    seq, unfinished = history, torch.ones(bsz, dtype=torch.long, device=dev)
+                    nxt = torch.argmax(procs(seq, logits), dim=-1)
+                    nxt = nxt * unfinished + 1 * (1 - unfinished)
+                    seq = torch.cat([seq, nxt[:, None]], dim=-1)
+                    unfinished = unfinished & ~torch.isin(nxt, eos)
+                    return nxt, bool(unfinished.max() == 0)
+
+                def kernel():
+                    bufs.unfinished.fill_(1)
+                    ops.greedy_advance(logits, bufs, at, plan.ngram, plan.ban, plan.forced(at), plan.eos, plan.pad)
+                    return bufs.next_tokens, not int(bufs.go_on)
+                forms = {"torch lines": torch_lines, "ops.greedy_advance": kernel}
+                times = {label: [] for label in forms}
+                outs = {}
+                for r in range(args.reps + 3):      # three lead-in rounds
+                    for label, fn in forms.items():
+                        ms, outs[label] = _timed(fn)
+                        if r >= 3:
+                            times[label].append(ms)
+                (a, a_stop), (b, b_stop) = outs.values()
+                assert bool(torch.equal(a, b)) and a_stop == b_stop, "the kernel's tokens differ from the torch lines'"
+                lines += [f"    no_repeat_ngram_size {ngram}, {label:20s} {_stats(t)}" for label, t in times.items()]
+            print("\n".join(lines[-5:]), flush=True)
+    finally:
+        UL.FUSE_DECODE_ATTENTION = old
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=32)
@@ -477,9 +585,16 @@ def main():
     ap.add_argument("--beam-select", action="store_true")
     ap.add_argument("--beam-advance", action="store_true")
     ap.add_argument("--beam-graph", action="store_true")
+    ap.add_argument("--greedy-advance", action="store_true")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     q, ids, mask = build(args.batch, args.src, args.layers)
+    if args.greedy_advance:
+        text = "\n".join(greedy_advance_ab(q, ids, mask, args))
+        if args.out:
+            with open(args.out, "w") as f:
+                f.write(text + "\n")
+        return
     if args.beam_graph:
         text = "\n".join(beam_graph_ab(q, ids, mask, args))
         if args.out:
