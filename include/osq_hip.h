@@ -43,7 +43,8 @@ typedef void* osq_stream;
  *     osq_fake_quant_kv_append_at, osq_fake_quant_kv_append_codes_at, osq_decode_attention_fake_quant_at,
  *     osq_decode_attention_codes_at, osq_beam_select_workspace_bytes, osq_beam_select, osq_beam_advance,
  *     osq_beam_select_at, osq_beam_advance_at, osq_greedy_advance_workspace_bytes, osq_greedy_advance,
- *     osq_greedy_advance_at. */
+ *     osq_greedy_advance_at, osq_sample_advance_workspace_bytes, osq_sample_advance, osq_sample_advance_at,
+ *     osq_sample_uniforms. */
 #define OSQ_ABI_VERSION 10
 
 typedef enum osq_status {
@@ -1040,6 +1041,53 @@ int osq_greedy_advance_at(const float* logits, int64_t logits_stride, int64_t* s
                           int64_t ban_below, int64_t forced_bos, int64_t forced_eos, const int64_t* eos_ids, int64_t n_eos,
                           int64_t pad, uint8_t* unfinished, int64_t bsz, int64_t vocab, int64_t max_length,
                           int64_t* next_tokens, int32_t* go_on, void* workspace, size_t workspace_bytes, osq_stream stream);
+
+/* ------------------------------------------------------------------ seeded sampling (sample_advance.hip) */
+
+/* One sampling step after the model, at history length cur: osq_greedy_advance with a seeded draw in the place of the
+ * arg-max.  Bans, the forced token, pad / eos, seq[b, cur], next_tokens, unfinished and go_on are osq_greedy_advance's, word
+ * for word; a forced step draws nothing and reads no logit.  Otherwise, for every batch row b:
+ *     z = x / temperature (one IEEE fp32 division).  A banned token, a NaN and -inf are out of the draw (weight 0).
+ *     top_k >= 1: the survivors are the min(top_k, vocab) largest z left, larger first, equal values by smaller token (-0.0
+ *         equals +0.0): exactly top_k of them, ties at the top_k-th value included.  This rank order is their order.
+ *     top_k == 0 (with top_p == 1): the survivors are all tokens left, in token order.
+ *     weights: m the largest surviving z, w_i = 1 where z_i == m (m = +inf included), else exp(z_i - m)
+ *     top_p < 1 (top_k >= 1 only): rank i stays iff sum_{j < i} w_j < top_p * sum_j w_j; rank 0 always stays
+ *     u = uniforms[b] when uniforms is given (bsz fp32 values in [0, 1) on the device), else
+ *         (word 0 of Philox4x32-10 with key (seed & 0xffffffff, seed >> 32) and counter (b, cur, 0, 0)) >> 8, times 2^-24
+ *     token = the first kept survivor with C_i > u * W (C_i the running sum of the kept weights in the survivors' order, W
+ *         their total; fp32), the last kept one when rounding leaves none; 0 for a row without a survivor.
+ * Every sum has an order fixed by (vocab, top_k) alone, not by the rows' alignment, stride or bsz (sample_advance.hip spells
+ * it out); no atomics on device memory: the same inputs give the same words on every run.  The logits are read once with
+ * top_k >= 1, once plus one 4096-token chunk per row with top_k == 0.
+ * workspace: at least osq_sample_advance_workspace_bytes(bsz, vocab, top_k) bytes of device memory, 8-byte aligned, contents
+ * arbitrary; one per stream in flight.  One workgroup per (row, 4096-token chunk), one per row, one for go_on; no workgroup
+ * waits for another.  No host synchronisation, no allocation, nothing read from the host: legal inside a stream capture.
+ * OSQ_ERR_INVALID_ARGUMENT, nothing launched: what osq_greedy_advance refuses, top_k outside [0, 64], top_p outside (0, 1],
+ * a temperature that is not positive and finite.  OSQ_ERR_UNSUPPORTED, nothing launched: top_k == 0 with top_p < 1 (a nucleus
+ * over the whole vocabulary: the caller runs its torch lines). */
+size_t osq_sample_advance_workspace_bytes(int64_t bsz, int64_t vocab, int64_t top_k);
+int osq_sample_advance(const float* logits, int64_t logits_stride, int64_t* seq, int64_t seq_stride, int64_t cur,
+                       int64_t ngram, const int64_t* ban_ids, int64_t n_ban, int64_t forced, const int64_t* eos_ids,
+                       int64_t n_eos, int64_t pad, uint8_t* unfinished, int64_t bsz, int64_t vocab, int64_t max_length,
+                       int64_t* next_tokens, int32_t* go_on, void* workspace, size_t workspace_bytes, uint64_t seed,
+                       float temperature, int64_t top_k, float top_p, const float* uniforms, osq_stream stream);
+
+/* osq_sample_advance with the position read by the launches: cur = *cur_dev + cur_add, with ban_below, forced_bos and
+ * forced_eos as in osq_greedy_advance_at; the seed is an argument, so one captured graph serves every step of a call.  For
+ * every cur in [1, max_length) every output word equals osq_sample_advance called with that cur and the n_ban / forced the
+ * host would have passed.  A cur outside that range: go_on receives -1 and nothing else is written; no address is formed
+ * from a refused position. */
+int osq_sample_advance_at(const float* logits, int64_t logits_stride, int64_t* seq, int64_t seq_stride,
+                          const int32_t* cur_dev, int64_t cur_add, int64_t ngram, const int64_t* ban_ids, int64_t n_ban,
+                          int64_t ban_below, int64_t forced_bos, int64_t forced_eos, const int64_t* eos_ids, int64_t n_eos,
+                          int64_t pad, uint8_t* unfinished, int64_t bsz, int64_t vocab, int64_t max_length,
+                          int64_t* next_tokens, int32_t* go_on, void* workspace, size_t workspace_bytes, uint64_t seed,
+                          float temperature, int64_t top_k, float top_p, const float* uniforms, osq_stream stream);
+
+/* out[b] = the u osq_sample_advance draws for row b at history length cur with this seed, b in [0, bsz): the same device
+ * function as the step's. */
+int osq_sample_uniforms(uint64_t seed, int64_t bsz, int64_t cur, float* out, osq_stream stream);
 
 /* ------------------------------------------------------------------ bf16 / fp16 only (lowp.hip) */
 

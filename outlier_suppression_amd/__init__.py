@@ -137,6 +137,38 @@ def set_greedy_graph(on=True):
     util_layernorm.GREEDY_GRAPH = bool(on)
 
 
+def set_sample_advance(on=True):
+    """sample() takes a step with ops.sample_advance -- the banned tokens of the logits processors, temperature, top-k / top-p,
+    the seeded draw, the pad / eos arithmetic, the new token into the sequence and the stopping word in one kernel call
+    (util_layernorm.SAMPLE_ADVANCE; csrc/sample_advance.hip; default OFF) -- instead of the torch lines; a call it cannot
+    take runs those (``model.last_sample_advance.reason``).  OSQ_SAMPLE_ADVANCE=1 turns it on at load;
+    ``sample(..., sample_advance=True)`` asks for one call."""
+    from . import util_layernorm
+    util_layernorm.SAMPLE_ADVANCE = bool(on)
+
+
+def set_sample_graph(on=True):
+    """sample() captures a whole step -- the token copy, the model step and ops.sample_advance_at -- into one hipGraph and
+    replays it (util_layernorm.SAMPLE_GRAPH; model/graph_decode.py, SampleStepGraph; default OFF).  For its call it implies
+    set_graph_decode and set_sample_advance; a call it cannot take decodes as without it
+    (``model.last_sample_graph.reason``).  OSQ_SAMPLE_GRAPH=1 turns it on at load; ``sample(..., sample_graph=True)`` asks
+    for one call."""
+    from . import util_layernorm
+    util_layernorm.SAMPLE_GRAPH = bool(on)
+
+
+def sample_advance_from_environment(environ=None):
+    """What OSQ_SAMPLE_ADVANCE asks for: unset, empty or "0" -> False, anything else -> True."""
+    import os
+    return (os.environ if environ is None else environ).get("OSQ_SAMPLE_ADVANCE", "") not in ("", "0")
+
+
+def sample_graph_from_environment(environ=None):
+    """What OSQ_SAMPLE_GRAPH asks for: unset, empty or "0" -> False, anything else -> True."""
+    import os
+    return (os.environ if environ is None else environ).get("OSQ_SAMPLE_GRAPH", "") not in ("", "0")
+
+
 def greedy_advance_from_environment(environ=None):
     """What OSQ_GREEDY_ADVANCE asks for: unset, empty or "0" -> False, anything else -> True."""
     import os
@@ -188,7 +220,8 @@ def reset_tier(_lib=None):
     continuations with one kernel call (unset: off); OSQ_BEAM_ADVANCE=1 beam search advances its beams with one kernel call
     (unset: off); OSQ_BEAM_GRAPH=1 beam search replays a whole step, bookkeeping included, as one captured graph (unset: off);
     OSQ_GREEDY_ADVANCE=1 greedy decoding takes a step with one kernel call (unset: off); OSQ_GREEDY_GRAPH=1 greedy decoding
-    replays a whole step as one captured graph (unset: off)."""
+    replays a whole step as one captured graph (unset: off); OSQ_SAMPLE_ADVANCE=1 sample() takes a step with one kernel call
+    (unset: off); OSQ_SAMPLE_GRAPH=1 sample() replays a whole step as one captured graph (unset: off)."""
     import os
     width = int(os.environ.get("OSQ_STRICT_SIMD", "8"))
     strict = os.environ.get("OSQ_STRICT", "")
@@ -207,6 +240,8 @@ def reset_tier(_lib=None):
     set_beam_graph(beam_graph_from_environment())
     set_greedy_advance(greedy_advance_from_environment())
     set_greedy_graph(greedy_graph_from_environment())
+    set_sample_advance(sample_advance_from_environment())
+    set_sample_graph(sample_graph_from_environment())
 
 
 _apply_environment = reset_tier

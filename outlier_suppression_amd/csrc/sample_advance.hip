@@ -1,0 +1,492 @@
+// ONE sampling step after the model: the banned tokens, temperature, top-k / top-p, a seeded draw from what is left, the pad /
+// eos arithmetic, the new token into the sequence and the stopping word, in three small launches.
+//
+// For a step at history length `cur`, a row cut into chunks of kBsChunk tokens (token_argmax.h), z = x / temperature (one IEEE
+// division), a banned token, a NaN and -inf out of the draw (weight 0):
+//
+//   launch 1   sample_chunk_kernel   one workgroup per (row, chunk): the chunk's ban bitmap in LDS, the chunk's z in registers
+//                                    (16 per thread).  top_k >= 1: top_k rounds of a workgroup arg-max, the chunk's first top_k
+//                                    candidates (value key, token) go to the workspace.  top_k == 0: the chunk's maximum m_c and
+//                                    s_c = sum exp(z - m_c) go there.  A forced step returns at once: it reads no logit
+//   launch 2   sample_row_kernel     one workgroup per row.  top_k >= 1: top_k rounds of the same arg-max over the row's
+//                                    candidates give the survivors in rank order (larger z first, equal z by smaller token);
+//                                    weights w_i = exp(z_i - z_0), the top-p cut, the draw.  top_k == 0: the row's total from the
+//                                    chunk sums in chunk order, the chunk the draw falls into, and that chunk read once more for
+//                                    the token.  Then the forced token in its place, pad / eos, seq[b, cur], next_tokens[b] and
+//                                    the row's unfinished flag into the workspace
+//   launch 3   sample_go_on_kernel   one wave: go_on = (cur + 1 < max_length) && (n_eos == 0 || any row unfinished)
+//
+// No workgroup waits for another: the launches follow each other on the stream.  No atomics on device memory.
+//
+// The draw: u = (word 0 of Philox4x32-10 with key (seed lo, seed hi) and counter (row, cur, 0, 0)) >> 8, times 2^-24 -- no
+// state to advance, so a captured graph of the call serves every step -- or uniforms[row] when given.  With C_i the running fp32
+// sum of the kept weights in the survivors' order and W their total, the token is the first kept survivor with C_i > u * W, the
+// last kept one when rounding leaves none.  A row without a survivor gives token 0.
+//
+// Summation order, fixed by (vocab, top_k) alone -- not by the row's alignment, stride or bsz.  top_k >= 1: ranks in order, one
+// thread.  top_k == 0: s_c as beam_partials_kernel forms it (thread t adds elements t, t + 256, ... in order, wave_sum_f32, then
+// (w0 + w1) + (w2 + w3)); the row total and the walk add s_c * exp(m_c - m) in chunk order; inside the chosen chunk thread t owns
+// tokens 16 t .. 16 t + 15 and adds them in order onto the sum of the threads before it (16 groups of 16 threads, each summed in
+// order).  Elements are loaded one 32-bit word per lane: a row of an odd vocab is only 4-byte aligned.
+//
+// osq_sample_advance_at is the same launches with the position read by them: cur = *cur_dev + cur_add, as osq_greedy_advance_at.
+#include <math.h>
+#include <hip/hip_runtime.h>
+#include "osq_device.h"
+#include "osq_host.h"
+#include "token_argmax.h"
+
+namespace osq {
+
+constexpr int kSaMaxLength = kBsMaxCur, kSaMaxEos = 16, kSaMaxTopK = 64;
+constexpr int kSaGoThreads = OSQ_WAVE;               // rows one trip of the go_on reduction covers
+constexpr int kSaGroup = 16;                         // threads whose sums one thread adds in order (the chosen chunk's scan)
+
+struct SampleArgs {
+    const float* logits;       // bsz x vocab, rows logits_stride floats apart
+    int64_t* seq;              // bsz x max_length, rows seq_stride apart: [0, cur) read with ngram > 0, [cur] written
+    const int64_t* ban_ids;    // n_ban ids banned in every row
+    const int64_t* eos_ids;    // n_eos ids that finish a row
+    uint8_t* unfinished;       // [bsz]; touched only with n_eos > 0
+    int64_t* next_tokens;      // [bsz]
+    int32_t* go_on;            // 1
+    const float* uniforms;     // nullptr: Philox; else [bsz] values in [0, 1) in the place of the draws
+    BeamCand* cands;           // [bsz, chunks, top_k]  workspace, top_k >= 1
+    float2* partials;          // [bsz, chunks] (m_c, s_c)  the same workspace, top_k == 0
+    unsigned int* row_flags;   // [bsz]          workspace: the row is unfinished after this step
+    int64_t logits_stride, seq_stride;
+    int64_t pad;
+    unsigned long long seed;
+    float temperature, top_p;
+    int top_k;
+    int bsz, vocab, chunks, max_length, cur, ngram, n_ban, n_eos;
+    int forced;                // static form: >= 0 is this step's token
+    // osq_sample_advance_at: cur = *cur_dev + cur_add, read by the launches
+    const int32_t* cur_dev;    // nullptr: the static form, cur / n_ban / forced above
+    int cur_add, ban_below, forced_bos, forced_eos;
+};
+
+struct SampleStep {            // what a launch knows of its step: workgroup-uniform
+    int cur;                   // -1: refused
+    int n_ban, forced;
+};
+
+__device__ __forceinline__ SampleStep sample_step(const SampleArgs& a) {
+    if (!a.cur_dev) return SampleStep{a.cur, a.n_ban, a.forced};
+    const long long at = static_cast<long long>(__builtin_amdgcn_readfirstlane(*a.cur_dev)) + a.cur_add;
+    if (at < 1 || at >= a.max_length) return SampleStep{-1, 0, -1};
+    const int cur = static_cast<int>(at);
+    int forced = cur == 1 ? a.forced_bos : -1;
+    if (cur == a.max_length - 1 && a.forced_eos >= 0) forced = a.forced_eos;
+    return SampleStep{cur, cur < a.ban_below ? a.n_ban : 0, forced};
+}
+
+// Word 0 of Philox4x32-10 (Salmon et al., SC'11) for the counter (c0, c1, 0, 0) and the key (k0, k1).
+__device__ __forceinline__ unsigned int philox_word0(unsigned int c0, unsigned int c1, unsigned int k0, unsigned int k1) {
+    unsigned int c2 = 0u, c3 = 0u;
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const unsigned long long p0 = 0xD2511F53ull * c0, p1 = 0xCD9E8D57ull * c2;
+        const unsigned int n0 = static_cast<unsigned int>(p1 >> 32) ^ c1 ^ k0, n2 = static_cast<unsigned int>(p0 >> 32) ^ c3 ^ k1;
+        c1 = static_cast<unsigned int>(p1);
+        c3 = static_cast<unsigned int>(p0);
+        c0 = n0;
+        c2 = n2;
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+    return c0;
+}
+
+// The draw of row b at history length cur: 24 bits, in [0, 1).
+__device__ __forceinline__ float sample_uniform(unsigned long long seed, unsigned int b, unsigned int cur) {
+    const unsigned int w = philox_word0(b, cur, static_cast<unsigned int>(seed), static_cast<unsigned int>(seed >> 32));
+    return static_cast<float>(w >> 8) * 0x1p-24f;
+}
+
+// z of one element: x / temperature with -0.0 as +0.0; -inf for what is out of the draw (banned, NaN, -inf, past the row)
+__device__ __forceinline__ float sample_z(float x, float temperature, bool out) {
+    const float z = x / temperature;
+    return (out || z != z) ? -INFINITY : z + 0.0f;
+}
+
+// what a survivor z weighs against the maximum m: 1 where equal (m = +inf included), else exp(z - m)
+__device__ __forceinline__ float sample_weight(float z, float m) { return z == m ? 1.f : expf(z - m); }
+
+__global__ __launch_bounds__(kBsThreads) void sample_chunk_kernel(SampleArgs a) {
+    __shared__ unsigned int s_ban[kBsChunk / 32];
+    __shared__ unsigned int s_red[2][2 * kBsWaves];
+    __shared__ float s_sum[2][kBsWaves];
+    const SampleStep step = sample_step(a);
+    if (step.cur < 0 || step.forced >= 0) return;                   // refused, or forced: every logit is ignored
+    const int lane = threadIdx.x & (OSQ_WAVE - 1), w = threadIdx.x / OSQ_WAVE;
+    const int64_t row = blockIdx.x / a.chunks;
+    const int c = blockIdx.x % a.chunks;
+    const int c0 = c * kBsChunk;
+    const int len = min(kBsChunk, a.vocab - c0);
+    const float* x = a.logits + row * a.logits_stride + c0;
+    float v[kBsPer];
+#pragma unroll
+    for (int j = 0; j < kBsPer; ++j) {                              // issued before the bans are found: the loads fly meanwhile
+        const int i = threadIdx.x + j * kBsThreads;
+        v[j] = i < len ? x[i] : 0.f;
+    }
+    chunk_bans(s_ban, a.ban_ids, step.n_ban, a.seq + row * a.seq_stride, step.cur, a.ngram, c0, len);
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < kBsPer; ++j) {
+        const int i = threadIdx.x + j * kBsThreads;
+        const bool banned = (s_ban[i >> 5] >> (i & 31)) & 1u;
+        v[j] = sample_z(v[j], a.temperature, banned || i >= len);
+    }
+
+    if (a.top_k == 0) {                                             // ---- the chunk's maximum and exp sum
+        float mx = -INFINITY;
+#pragma unroll
+        for (int j = 0; j < kBsPer; ++j) mx = fmaxf(mx, v[j]);
+        mx = wave_max(mx);
+        if (lane == 0) s_sum[0][w] = mx;
+        __syncthreads();
+        mx = fmaxf(fmaxf(s_sum[0][0], s_sum[0][1]), fmaxf(s_sum[0][2], s_sum[0][3]));
+        float sum = 0.f;
+#pragma unroll
+        for (int j = 0; j < kBsPer; ++j)
+            if (v[j] != -INFINITY) sum += sample_weight(v[j], mx);
+        sum = wave_sum_f32(sum);
+        if (lane == 0) s_sum[1][w] = sum;
+        __syncthreads();
+        if (threadIdx.x == 0)
+            a.partials[blockIdx.x] = make_float2(mx, (s_sum[1][0] + s_sum[1][1]) + (s_sum[1][2] + s_sum[1][3]));
+        return;
+    }
+
+    // ---- the chunk's first top_k candidates; key 0: none
+    unsigned int key[kBsPer];
+#pragma unroll
+    for (int j = 0; j < kBsPer; ++j) key[j] = v[j] == -INFINITY ? 0u : beam_key(v[j]);
+    BeamCand* out = a.cands + static_cast<int64_t>(blockIdx.x) * a.top_k;
+    unsigned int best = 0u, best_i = threadIdx.x;
+#pragma unroll
+    for (int j = 0; j < kBsPer; ++j)
+        if (key[j] > best) { best = key[j]; best_i = threadIdx.x + j * kBsThreads; }      // strict: the smaller index stays
+    for (int r = 0; r < a.top_k; ++r) {
+        unsigned int hi = best, lo = ~best_i;
+        block_argmax(hi, lo, s_red, r & 1);
+        const unsigned int i = ~lo;
+        if (threadIdx.x == 0) out[r] = BeamCand{hi, hi ? c0 + static_cast<int>(i) : -1};
+        if (hi && (i & (kBsThreads - 1)) == threadIdx.x) {          // the owner takes it out and looks again
+            best = 0u;
+            best_i = threadIdx.x;
+#pragma unroll
+            for (int j = 0; j < kBsPer; ++j) {
+                if (static_cast<unsigned int>(j) == i / kBsThreads) key[j] = 0u;
+                if (key[j] > best) { best = key[j]; best_i = threadIdx.x + j * kBsThreads; }
+            }
+        }
+    }
+}
+
+// The token of row b with top_k >= 1, in thread 0: the survivors by top_k rounds over the row's candidates, their weights, the
+// top-p cut and the draw u.  Every thread of the workgroup calls it.
+__device__ __forceinline__ int64_t sample_pick_top_k(const SampleArgs& a, int64_t b, float u, unsigned int (*s_red)[2 * kBsWaves],
+                                                     unsigned int* s_key, int* s_tok, float* s_w) {
+    const int n = a.chunks * a.top_k;                               // among equal values slots run as tokens do
+    BeamCand* cand = a.cands + b * n;
+    unsigned int best = 0u, best_p = threadIdx.x;
+    for (int p = threadIdx.x; p < n; p += kBsThreads) {
+        const unsigned int k = cand[p].key;
+        if (k > best) { best = k; best_p = p; }
+    }
+    int kept = 0;
+    for (; kept < a.top_k; ++kept) {
+        unsigned int hi = best, lo = ~best_p;
+        block_argmax(hi, lo, s_red, kept & 1);
+        if (!hi) break;                                             // workgroup-uniform: no candidate is left
+        const unsigned int p = ~lo;
+        if ((p & (kBsThreads - 1)) == threadIdx.x) {                // the owner notes it, takes it out and looks again
+            s_key[kept] = hi;
+            s_tok[kept] = cand[p].token;
+            cand[p].key = 0u;
+            best = 0u;
+            best_p = threadIdx.x;
+            for (int q = threadIdx.x; q < n; q += kBsThreads) {
+                const unsigned int k = cand[q].key;
+                if (k > best) { best = k; best_p = q; }
+            }
+        }
+    }
+    __syncthreads();
+    if (kept == 0) return 0;
+    if (threadIdx.x < kept) s_w[threadIdx.x] = sample_weight(beam_value(s_key[threadIdx.x]), beam_value(s_key[0]));
+    __syncthreads();
+    if (threadIdx.x != 0) return 0;
+    float total = 0.f;
+    for (int i = 0; i < kept; ++i) total += s_w[i];
+    if (a.top_p < 1.f) {                                            // rank i stays iff the weights above it sum below top_p * total
+        const float bound = a.top_p * total;
+        float above = s_w[0];
+        int i = 1;
+        for (; i < kept && above < bound; ++i) above += s_w[i];
+        kept = i;
+        total = above;
+    }
+    const float target = u * total;
+    float upto = 0.f;
+    int pick = kept - 1;
+    for (int i = 0; i < kept; ++i) {
+        upto += s_w[i];
+        if (upto > target) { pick = i; break; }
+    }
+    return s_tok[pick];
+}
+
+// The token of row b with top_k == 0, in every thread: the chunk the draw u falls into by the chunk sums, then that chunk's
+// tokens in order.  s_w: kBsChunk + kBsThreads floats; s_tot: kBsThreads; s_grp: kSaGroup.
+__device__ __forceinline__ int64_t sample_pick_full(const SampleArgs& a, const SampleStep& step, int64_t b, float u,
+                                                    unsigned int* s_ban, unsigned int (*s_red)[2 * kBsWaves], float* s_w,
+                                                    float* s_tot, float* s_grp) {
+    const float2* part = a.partials + b * a.chunks;
+    float m = -INFINITY;
+    for (int k = 0; k < a.chunks; ++k) m = fmaxf(m, part[k].x);
+    if (m == -INFINITY) return 0;                                   // no survivor in the row
+    float total = 0.f;
+    for (int k = 0; k < a.chunks; ++k) {
+        const float2 p = part[k];
+        total += p.y * sample_weight(p.x, m);
+    }
+    float target = u * total;
+    float before = 0.f;
+    int chosen = -1, last = 0;
+    for (int k = 0; k < a.chunks; ++k) {
+        const float2 p = part[k];
+        const float wc = p.y * sample_weight(p.x, m);
+        if (wc > 0.f) last = k;
+        if (before + wc > target) { chosen = k; break; }
+        before += wc;
+    }
+    if (chosen < 0) {                                               // rounding left none: the last survivor of the last chunk that has one
+        chosen = last;
+        target = INFINITY;
+    }
+
+    // ---- the chosen chunk once more: its weights in token order
+    const int c0 = chosen * kBsChunk;
+    const int len = min(kBsChunk, a.vocab - c0);
+    const float* x = a.logits + b * a.logits_stride + c0;
+    float v[kBsPer];
+#pragma unroll
+    for (int j = 0; j < kBsPer; ++j) {
+        const int i = threadIdx.x + j * kBsThreads;
+        v[j] = i < len ? x[i] : 0.f;
+    }
+    chunk_bans(s_ban, a.ban_ids, step.n_ban, a.seq + b * a.seq_stride, step.cur, a.ngram, c0, len);
+    __syncthreads();
+    const float mc = part[chosen].x;
+    const float scale = sample_weight(mc, m);
+#pragma unroll
+    for (int j = 0; j < kBsPer; ++j) {
+        const int i = threadIdx.x + j * kBsThreads;
+        const bool banned = (s_ban[i >> 5] >> (i & 31)) & 1u;
+        const float z = sample_z(v[j], a.temperature, banned || i >= len);
+        s_w[i + (i >> 4)] = z == -INFINITY ? 0.f : sample_weight(z, mc) * scale;      // one pad word per 16: thread t reads 17 t + j
+    }
+    __syncthreads();
+    float own = 0.f;
+#pragma unroll
+    for (int j = 0; j < kBsPer; ++j) {
+        v[j] = s_w[threadIdx.x * (kBsPer + 1) + j];
+        own += v[j];
+    }
+    s_tot[threadIdx.x] = own;
+    __syncthreads();
+    if (threadIdx.x < kBsThreads / kSaGroup) {                      // the sums before each thread of a group, and the group's
+        float run = 0.f;
+        for (int q = 0; q < kSaGroup; ++q) {
+            const float t = s_tot[threadIdx.x * kSaGroup + q];
+            s_tot[threadIdx.x * kSaGroup + q] = run;
+            run += t;
+        }
+        s_grp[threadIdx.x] = run;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float run = 0.f;
+        for (int q = 0; q < kBsThreads / kSaGroup; ++q) {
+            const float t = s_grp[q];
+            s_grp[q] = run;
+            run += t;
+        }
+    }
+    __syncthreads();
+    const float base = before + (s_grp[threadIdx.x / kSaGroup] + s_tot[threadIdx.x]);
+    unsigned int hit = 0u, hit_i = 0u, live = 0u, live_i = 0u;      // the first token past the target; the last with a weight
+    float upto = 0.f;
+#pragma unroll
+    for (int j = 0; j < kBsPer; ++j) {
+        upto += v[j];
+        if (v[j] > 0.f) {
+            const unsigned int i = threadIdx.x * kBsPer + j;
+            live = 1u;
+            live_i = i;
+            if (!hit && base + upto > target) { hit = 1u; hit_i = i; }
+        }
+    }
+    unsigned int lo = ~hit_i;
+    block_argmax(hit, lo, s_red, 0);                                // the largest ~i: the smallest token
+    block_argmax(live, live_i, s_red, 1);
+    return c0 + static_cast<int>(hit ? ~lo : live_i);               // live: the chunk's maximum weighs `scale` > 0
+}
+
+__global__ __launch_bounds__(kBsThreads) void sample_row_kernel(SampleArgs a) {
+    __shared__ unsigned int s_ban[kBsChunk / 32];
+    __shared__ unsigned int s_red[2][2 * kBsWaves];
+    __shared__ float s_w[kBsChunk + kBsThreads];
+    __shared__ float s_tot[kBsThreads], s_grp[kBsThreads / kSaGroup];
+    __shared__ unsigned int s_key[kSaMaxTopK];
+    __shared__ int s_tok[kSaMaxTopK];
+    const SampleStep step = sample_step(a);
+    if (step.cur < 0) return;                                       // refused: nothing written (sample_go_on_kernel says so)
+    const int64_t b = blockIdx.x;
+    int64_t token = step.forced;
+    if (step.forced < 0) {
+        const float u = a.uniforms ? a.uniforms[b] : sample_uniform(a.seed, static_cast<unsigned int>(b), static_cast<unsigned int>(step.cur));
+        token = a.top_k > 0 ? sample_pick_top_k(a, b, u, s_red, s_key, s_tok, s_w)
+                            : sample_pick_full(a, step, b, u, s_ban, s_red, s_w, s_tot, s_grp);
+    }
+    if (threadIdx.x != 0) return;
+    unsigned int unfinished = 1u;
+    if (a.n_eos > 0) {
+        unfinished = a.unfinished[b] != 0;
+        if (!unfinished) token = a.pad;
+        for (int e = 0; e < a.n_eos; ++e) unfinished &= token != a.eos_ids[e];
+        a.unfinished[b] = static_cast<uint8_t>(unfinished);
+    }
+    if (a.seq) a.seq[b * a.seq_stride + step.cur] = token;
+    a.next_tokens[b] = token;
+    a.row_flags[b] = unfinished;
+}
+
+__global__ __launch_bounds__(kSaGoThreads) void sample_go_on_kernel(SampleArgs a) {
+    const SampleStep step = sample_step(a);
+    if (step.cur < 0) {                                             // refused: the row flags are not this step's
+        if (threadIdx.x == 0) *a.go_on = -1;
+        return;
+    }
+    unsigned int any = a.n_eos == 0;
+    if (a.n_eos > 0)
+        for (int b = threadIdx.x; b < a.bsz; b += kSaGoThreads) any |= a.row_flags[b];
+    const bool some = __any(any != 0u);
+    if (threadIdx.x == 0) *a.go_on = step.cur + 1 < a.max_length && some;
+}
+
+__global__ __launch_bounds__(kBsThreads) void sample_uniforms_kernel(unsigned long long seed, int bsz, unsigned int cur, float* out) {
+    const int b = blockIdx.x * kBsThreads + threadIdx.x;
+    if (b < bsz) out[b] = sample_uniform(seed, static_cast<unsigned int>(b), cur);
+}
+
+static int64_t sample_chunks(int64_t vocab) { return (vocab + kBsChunk - 1) / kBsChunk; }
+
+static size_t sample_workspace_bytes(int64_t bsz, int64_t vocab, int64_t top_k) {
+    if (bsz < 1 || vocab < 1 || top_k < 0 || top_k > kSaMaxTopK) return 0;
+    static_assert(sizeof(BeamCand) == sizeof(float2), "one workspace slot holds a candidate or a chunk's (m_c, s_c)");
+    const int64_t slots = bsz * sample_chunks(vocab) * (top_k > 0 ? top_k : 1);
+    return static_cast<size_t>(slots) * sizeof(BeamCand) + static_cast<size_t>(bsz) * sizeof(unsigned int);
+}
+
+}  // namespace osq
+
+using namespace osq;
+
+extern "C" size_t osq_sample_advance_workspace_bytes(int64_t bsz, int64_t vocab, int64_t top_k) {
+    return sample_workspace_bytes(bsz, vocab, top_k);
+}
+
+// Both entry points.  cur_dev == nullptr: the static form at `cur` with n_ban ids and `forced`; else the position is the device
+// word, the ids apply below ban_below and the forced tokens fire at their positions.
+static int sample_advance_launch(const float* logits, int64_t logits_stride, int64_t* seq, int64_t seq_stride, int64_t cur,
+                                 const int32_t* cur_dev, int64_t cur_add, int64_t ngram, const int64_t* ban_ids, int64_t n_ban,
+                                 int64_t ban_below, int64_t forced, int64_t forced_bos, int64_t forced_eos,
+                                 const int64_t* eos_ids, int64_t n_eos, int64_t pad, uint8_t* unfinished, int64_t bsz,
+                                 int64_t vocab, int64_t max_length, int64_t* next_tokens, int32_t* go_on, void* workspace,
+                                 size_t workspace_bytes, uint64_t seed, float temperature, int64_t top_k, float top_p,
+                                 const float* uniforms, osq_stream stream) {
+    OSQ_REQUIRE(bsz >= 1 && vocab >= 1 && max_length >= 1, "sample_advance: a non-positive extent");
+    OSQ_REQUIRE(vocab <= INT32_MAX, "sample_advance: vocab does not fit 31 bits");
+    OSQ_REQUIRE(max_length <= kSaMaxLength, "sample_advance: max_length above 4096");
+    OSQ_REQUIRE(cur_dev || (cur >= 1 && cur < max_length), "sample_advance: cur outside [1, max_length)");
+    OSQ_REQUIRE(n_ban >= 0 && n_ban <= kBsMaxBan, "sample_advance: n_ban outside [0, 16]");
+    OSQ_REQUIRE(n_eos >= 0 && n_eos <= kSaMaxEos, "sample_advance: n_eos outside [0, 16]");
+    OSQ_REQUIRE(ngram >= 0, "sample_advance: negative ngram");
+    OSQ_REQUIRE(top_k >= 0 && top_k <= kSaMaxTopK, "sample_advance: top_k outside [0, 64]");
+    OSQ_REQUIRE(top_p > 0.f && top_p <= 1.f, "sample_advance: top_p outside (0, 1]");
+    OSQ_REQUIRE(temperature > 0.f && temperature <= 3.4028234663852886e38f, "sample_advance: temperature not positive and finite");
+    OSQ_REQUIRE(n_eos == 0 || unfinished, "sample_advance: n_eos without unfinished");
+    OSQ_REQUIRE(n_eos == 0 || eos_ids, "sample_advance: n_eos without eos_ids");
+    OSQ_REQUIRE(n_ban == 0 || ban_ids, "sample_advance: n_ban without ban_ids");
+    // a stored token is an index of the row: what is stored unchecked is checked here (a negative forced id: none)
+    OSQ_REQUIRE(forced < vocab && forced_bos < vocab && forced_eos < vocab, "sample_advance: a forced token outside [0, vocab)");
+    OSQ_REQUIRE(n_eos == 0 || (pad >= 0 && pad < vocab), "sample_advance: pad outside [0, vocab)");
+    OSQ_REQUIRE(logits_stride >= vocab, "sample_advance: logits row stride below vocab");
+    OSQ_REQUIRE(!seq || seq_stride >= max_length, "sample_advance: seq row stride below max_length");
+    OSQ_REQUIRE(ngram == 0 || seq, "sample_advance: ngram without seq");
+    const int64_t chunks = sample_chunks(vocab);
+    OSQ_REQUIRE(bsz <= INT32_MAX / (chunks * (top_k > 0 ? top_k : 1)), "sample_advance: too many elements");
+    OSQ_REQUIRE(workspace_bytes >= sample_workspace_bytes(bsz, vocab, top_k), "sample_advance: workspace too small");
+    OSQ_REQUIRE(logits && next_tokens && go_on && workspace, "sample_advance: null tensor");
+    OSQ_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 7u) == 0, "sample_advance: workspace not 8-byte aligned");
+    if (top_k == 0 && top_p < 1.f) {
+        set_error("%s", "sample_advance: top_p below 1 without top_k (a nucleus over the whole vocabulary) has no kernel");
+        return OSQ_ERR_UNSUPPORTED;
+    }
+    const auto id = [](int64_t t) { return static_cast<int>(t < 0 ? -1 : t); };
+    BeamCand* cands = static_cast<BeamCand*>(workspace);
+    const int64_t slots = bsz * chunks * (top_k > 0 ? top_k : 1);
+    SampleArgs a{logits, seq, ban_ids, eos_ids, unfinished, next_tokens, go_on, uniforms, cands,
+                 static_cast<float2*>(workspace), reinterpret_cast<unsigned int*>(cands + slots), logits_stride, seq_stride, pad,
+                 static_cast<unsigned long long>(seed), temperature, top_p, static_cast<int>(top_k),
+                 static_cast<int>(bsz), static_cast<int>(vocab), static_cast<int>(chunks), static_cast<int>(max_length),
+                 static_cast<int>(cur), static_cast<int>(ngram > kBsMaxCur ? kBsMaxCur + 1 : ngram), static_cast<int>(n_ban),
+                 static_cast<int>(n_eos), id(forced), cur_dev, static_cast<int>(cur_add),
+                 static_cast<int>(ban_below < 0 ? 0 : (ban_below > kBsMaxCur ? kBsMaxCur + 1 : ban_below)), id(forced_bos),
+                 id(forced_eos)};
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(sample_chunk_kernel, dim3(static_cast<unsigned>(bsz * chunks)), dim3(kBsThreads), 0, st, a);
+    hipLaunchKernelGGL(sample_row_kernel, dim3(static_cast<unsigned>(bsz)), dim3(kBsThreads), 0, st, a);
+    hipLaunchKernelGGL(sample_go_on_kernel, dim3(1), dim3(kSaGoThreads), 0, st, a);
+    return check_launch(cur_dev ? "sample_advance_at" : "sample_advance");
+}
+
+extern "C" int osq_sample_advance(const float* logits, int64_t logits_stride, int64_t* seq, int64_t seq_stride, int64_t cur,
+                                  int64_t ngram, const int64_t* ban_ids, int64_t n_ban, int64_t forced, const int64_t* eos_ids,
+                                  int64_t n_eos, int64_t pad, uint8_t* unfinished, int64_t bsz, int64_t vocab,
+                                  int64_t max_length, int64_t* next_tokens, int32_t* go_on, void* workspace,
+                                  size_t workspace_bytes, uint64_t seed, float temperature, int64_t top_k, float top_p,
+                                  const float* uniforms, osq_stream stream) {
+    return sample_advance_launch(logits, logits_stride, seq, seq_stride, cur, nullptr, 0, ngram, ban_ids, n_ban, 0, forced, -1,
+                                 -1, eos_ids, n_eos, pad, unfinished, bsz, vocab, max_length, next_tokens, go_on, workspace,
+                                 workspace_bytes, seed, temperature, top_k, top_p, uniforms, stream);
+}
+
+extern "C" int osq_sample_advance_at(const float* logits, int64_t logits_stride, int64_t* seq, int64_t seq_stride,
+                                     const int32_t* cur_dev, int64_t cur_add, int64_t ngram, const int64_t* ban_ids,
+                                     int64_t n_ban, int64_t ban_below, int64_t forced_bos, int64_t forced_eos,
+                                     const int64_t* eos_ids, int64_t n_eos, int64_t pad, uint8_t* unfinished, int64_t bsz,
+                                     int64_t vocab, int64_t max_length, int64_t* next_tokens, int32_t* go_on, void* workspace,
+                                     size_t workspace_bytes, uint64_t seed, float temperature, int64_t top_k, float top_p,
+                                     const float* uniforms, osq_stream stream) {
+    OSQ_REQUIRE(cur_dev, "sample_advance_at: null position word");
+    OSQ_REQUIRE(cur_add >= INT32_MIN && cur_add <= INT32_MAX, "sample_advance_at: cur_add does not fit 32 bits");
+    return sample_advance_launch(logits, logits_stride, seq, seq_stride, 0, cur_dev, cur_add, ngram, ban_ids, n_ban, ban_below,
+                                 -1, forced_bos, forced_eos, eos_ids, n_eos, pad, unfinished, bsz, vocab, max_length,
+                                 next_tokens, go_on, workspace, workspace_bytes, seed, temperature, top_k, top_p, uniforms, stream);
+}
+
+extern "C" int osq_sample_uniforms(uint64_t seed, int64_t bsz, int64_t cur, float* out, osq_stream stream) {
+    OSQ_REQUIRE(bsz >= 1 && bsz <= INT32_MAX - kBsThreads, "sample_uniforms: bsz outside [1, 2^31)");
+    OSQ_REQUIRE(cur >= 0 && cur <= 0xffffffffll, "sample_uniforms: cur does not fit 32 bits");
+    OSQ_REQUIRE(out, "sample_uniforms: null tensor");
+    hipLaunchKernelGGL(sample_uniforms_kernel, dim3(static_cast<unsigned>((bsz + kBsThreads - 1) / kBsThreads)), dim3(kBsThreads),
+                       0, static_cast<hipStream_t>(stream), static_cast<unsigned long long>(seed), static_cast<int>(bsz),
+                       static_cast<unsigned int>(cur), out);
+    return check_launch("sample_uniforms");
+}

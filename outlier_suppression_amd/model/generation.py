@@ -4,7 +4,8 @@ The package's own loop, not transformers' GenerationMixin (whose cache contract 
 It follows transformers' greedy decoding and its vectorised beam search step for step, so that with the quantizers
 disabled the tokens equal ``BartForConditionalGeneration.generate`` on the FP model.  The logits processors a BART
 configuration turns on -- no_repeat_ngram_size, min_length, forced_bos_token_id, forced_eos_token_id -- are
-transformers' own, applied in transformers' order.  Not covered: sampling, return_dict_in_generate, streaming.
+transformers' own, applied in transformers' order.  Not covered: sampling (generate() refuses it; ``sample()``, below, is
+the package's own), return_dict_in_generate, streaming.
 
 Each step feeds the last token with the cache (quant_bart.QuantizedBartCache: the step's k / v are fake-quantized and
 appended in one launch, a beam reorder rides in the next append); ``use_cache=False`` re-runs the whole prefix instead.
@@ -27,6 +28,10 @@ steps took it.  The tokens are those of the torch lines with no tolerance: the k
 ``greedy_graph=True`` (set_greedy_graph) asks for ``graph`` and ``greedy_advance`` and captures the whole step -- token copy,
 model, ops.greedy_advance_at -- into one graph (graph_decode.GreedyStepGraph), forced tokens included: a token costs the host
 one replay and one read of the stopping word; ``model.last_greedy_graph`` tells what happened.
+
+Sampling is ``sample()``, an entry point of its own (generate() promises transformers' tokens, a sampler with its own random
+stream cannot): the greedy loop with a seeded draw in the place of the arg-max (model/sampling.py), ``sample_advance=True``
+and ``sample_graph=True`` as the two greedy switches (ops.sample_advance, graph_decode.SampleStepGraph).
 """
 import torch
 from torch import nn
@@ -470,17 +475,21 @@ def _greedy_graph_why_not(model, device, use_cache, max_length, nb, eos, pad, pr
             or _GreedyPlan(procs, device, model.config.vocab_size, max_length, eos, pad).reason)
 
 
-def _greedy_advanced(model, enc, attention_mask, start, plan, max_length, cache, stepper, advance, whole=None):
+def _greedy_advanced(model, enc, attention_mask, start, plan, max_length, cache, stepper, advance, whole=None, draw=None):
     """The loop of _greedy with everything after the model step as one call of ops.greedy_advance: the sequence, the
     unfinished flags and the next tokens live in an ops.GreedyBuffers, the model is fed the kernel's next_tokens (without a
     cache: the sequence so far, a view), and the go_on word is read once per token (the one host sync of the torch lines).
+    ``draw`` (sample(): dict(seed, temperature, top_k, top_p)): the same loop on ops.sample_advance and an ops.SampleBuffers.
 
     ``whole`` (a graph_decode.GreedyGraphInfo; generate(greedy_graph=True)): from the third step on a step is one replay of
     a captured graph that holds all of the above (graph_decode.GreedyStepGraph), a step on which a forced token fires
     included: the kernel takes the forced token itself."""
     from .. import ops
     from . import graph_decode
-    bufs = ops.GreedyBuffers(enc.shape[0], max_length, enc.device, model.config.vocab_size)
+    if draw is None:
+        bufs = ops.GreedyBuffers(enc.shape[0], max_length, enc.device, model.config.vocab_size)
+    else:
+        bufs = ops.SampleBuffers(enc.shape[0], max_length, enc.device, model.config.vocab_size, draw["top_k"])
     bufs.seq[:, 0] = start
     cur = 1
     captured = None
@@ -489,24 +498,153 @@ def _greedy_advanced(model, enc, attention_mask, start, plan, max_length, cache,
             if stepper is None or stepper.decoder is None:          # the cache the first step left does not fit
                 whole.reason, whole = stepper.info.reason if stepper is not None else "no captured step", None
             else:
-                captured = graph_decode.GreedyStepGraph(stepper.decoder, whole, bufs, plan)
+                captured = (graph_decode.GreedyStepGraph(stepper.decoder, whole, bufs, plan) if draw is None else
+                            graph_decode.SampleStepGraph(stepper.decoder, whole, bufs, plan, draw))
         if captured is not None:
             captured.step()
         else:
             tokens = bufs.seq[:, :cur] if cache is None or cur == 1 else bufs.next_tokens.view(-1, 1)
             logits = _step_logits(model, tokens, enc, attention_mask, cache, stepper).to(torch.float32)
-            ops.greedy_advance(logits, bufs, cur, plan.ngram, plan.ban if cur < plan.min_length else None, plan.forced(cur),
-                               plan.eos, plan.pad)
+            if draw is None:
+                ops.greedy_advance(logits, bufs, cur, plan.ngram, plan.ban if cur < plan.min_length else None, plan.forced(cur),
+                                   plan.eos, plan.pad)
+            else:
+                ops.sample_advance(logits, bufs, cur, draw["seed"], draw["temperature"], draw["top_k"], draw["top_p"], plan.ngram,
+                                   plan.ban if cur < plan.min_length else None, plan.forced(cur), plan.eos, plan.pad)
         cur += 1
         advance.advanced += 1
         go_on = int(bufs.go_on)
         if go_on < 0:
-            raise RuntimeError(f"generate(): a captured greedy step met the position {cur - 1}, outside [1, {max_length})")
+            raise RuntimeError(f"{'generate' if draw is None else 'sample'}(): a captured {'greedy' if draw is None else 'sampling'} "
+                               f"step met the position {cur - 1}, outside [1, {max_length})")
         if not go_on:
             break
     if whole is not None and whole.captured == 0:
         whole.reason = "the search ended before a step could be captured"
     return bufs.seq[:, :cur]
+
+
+class SampleAdvanceInfo(GreedyAdvanceInfo):
+    """What a sample() call did with its steps: ``advanced`` steps through ops.sample_advance, ``eager`` steps through the
+    torch lines (sampling.select_torch), and, when none was advanced, the ``reason``."""
+
+    def __repr__(self):
+        return f"SampleAdvanceInfo(advanced={self.advanced}, eager={self.eager}, reason={self.reason!r})"
+
+
+def _sample_why_not(plan, top_k, top_p):
+    """None when ops.sample_advance takes the steps of this call, else the reason the torch lines run: those of _GreedyPlan
+    and the two forms the kernel does not have."""
+    if plan.reason is not None:
+        return plan.reason
+    if top_k == 0 and top_p < 1.0:
+        return "top_p below 1 without top_k"
+    if top_k > 64:
+        return "top_k above 64"
+    return None
+
+
+def _sample_eager(model, enc, attention_mask, start, pad, eos, procs, max_length, cache, stepper, advance, draw):
+    """_greedy with the arg-max replaced by sampling.select_torch on the host's uniforms of (seed, row, length)."""
+    from . import sampling
+    b = enc.shape[0]
+    seq = torch.full((b, 1), start, dtype=torch.long, device=enc.device)
+    unfinished = torch.ones(b, dtype=torch.long, device=enc.device)
+    while seq.shape[1] < max_length:
+        scores = procs(seq, _step_logits(model, seq, enc, attention_mask, cache, stepper).to(torch.float32))
+        u = sampling.uniforms(draw["seed"], b, seq.shape[1])
+        nxt = sampling.select_torch(scores, u, draw["temperature"], draw["top_k"], draw["top_p"])
+        if eos is not None:
+            nxt = nxt * unfinished + pad * (1 - unfinished)
+        seq = torch.cat([seq, nxt[:, None]], dim=-1)
+        advance.eager += 1
+        if eos is not None:
+            unfinished = unfinished & ~torch.isin(nxt, eos)
+            if unfinished.max() == 0:
+                break
+    return seq
+
+
+def sample(model, input_ids, attention_mask=None, max_length=None, seed=None, temperature=1.0, top_k=50, top_p=1.0,
+           use_cache=True, cache_codes=None, graph=None, sample_advance=None, sample_graph=None, **kwargs):
+    """Seeded sampling over a KV cache: generate()'s greedy loop with a draw in the place of the arg-max (model/sampling.py;
+    the rule is osq_sample_advance's, include/osq_hip.h).  The tokens are a function of the inputs and ``seed`` alone -- the
+    package's own random stream, not torch.multinomial's, so they are not transformers' tokens: hence an entry point of its
+    own beside generate(), which keeps refusing ``do_sample``.  ``seed=None`` draws a 63-bit seed from torch's default CPU
+    generator (torch.manual_seed makes the call reproducible).  ``top_k=0`` keeps every token, ``top_p=1.0`` cuts nothing.
+
+    Settings, logits processors, cache and ``graph`` as in greedy generate().  ``sample_advance=True`` (set_sample_advance)
+    hands everything after the model step to one kernel call (ops.sample_advance); ``model.last_sample_advance`` tells how
+    many steps took it.  ``sample_graph=True`` (set_sample_graph) asks for ``graph`` and ``sample_advance`` and captures the
+    whole step -- token copy, model, ops.sample_advance_at -- into one graph (graph_decode.SampleStepGraph);
+    ``model.last_sample_graph`` tells what happened."""
+    import math
+    if kwargs.pop("synced_gpus", False):
+        raise NotImplementedError("sample(): synced_gpus=True is not supported")
+    if kwargs.pop("num_beams", 1) not in (None, 1):
+        raise ValueError("sample(): beam sampling is not supported (num_beams must be 1)")
+    if kwargs.pop("num_return_sequences", 1) not in (None, 1):
+        raise ValueError("sample(): one sequence per input (num_return_sequences must be 1)")
+    kwargs.pop("do_sample", None)
+    unknown = set(kwargs) - set(_DEFAULTS)
+    if unknown:
+        raise TypeError(f"sample(): unexpected arguments {sorted(unknown)}")
+    temperature, top_k, top_p = float(temperature), int(top_k), float(top_p)
+    if not (temperature > 0.0 and math.isfinite(temperature)):
+        raise ValueError("sample(): temperature must be positive and finite")
+    if top_k < 0 or not 0.0 < top_p <= 1.0:
+        raise ValueError("sample(): top_k must not be negative and top_p must lie in (0, 1]")
+    if seed is None:
+        seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64))
+    draw = {"seed": int(seed) & 0xFFFFFFFFFFFFFFFF, "temperature": temperature, "top_k": top_k, "top_p": top_p}
+    get = lambda name, given=None: _setting(model, name, kwargs.get(name, given))  # noqa: E731
+    max_length = get("max_length", max_length)
+    pad, start = get("pad_token_id"), get("decoder_start_token_id")
+    if start is None:
+        start = get("bos_token_id")
+    eos = get("eos_token_id")
+    eos_t = None if eos is None else torch.tensor(eos if isinstance(eos, (list, tuple)) else [eos], device=input_ids.device)
+    procs = _processors(get("min_length"), eos_t, get("no_repeat_ngram_size"), get("forced_bos_token_id"),
+                        get("forced_eos_token_id"), max_length, input_ids.device)
+    if attention_mask is None:
+        attention_mask = torch.ones_like(input_ids)
+    enc = model.get_encoder()(input_ids, attention_mask=attention_mask)
+    from .. import util_layernorm
+    from . import graph_decode
+    from .quant_bart import QuantizedBartCache
+    codes = util_layernorm.CACHE_CODES if cache_codes is None else bool(cache_codes)
+    cache = QuantizedBartCache(len(model.model.decoder.layers), capacity=max_length, codes=codes) if use_cache else None
+    plan = _GreedyPlan(procs, enc.device, model.config.vocab_size, max_length, eos_t, pad)
+    # a whole step as one captured graph: it implies the two switches below for this call, where nothing stands against it
+    whole = graph_decode.SampleGraphInfo(None if (util_layernorm.SAMPLE_GRAPH if sample_graph is None else sample_graph)
+                                         else "not asked for")
+    model.last_sample_graph = whole
+    if whole.reason is None:
+        for name, value in (("graph", graph), ("sample_advance", sample_advance)):
+            if whole.reason is None and value is not None and not value:
+                whole.reason = f"{name}=False was passed"
+        whole.reason = (whole.reason or graph_decode.why_not(model, enc.device, use_cache, max_length)
+                        or _sample_why_not(plan, top_k, top_p))
+        if whole.reason is None:
+            graph = sample_advance = True
+    stepper = None
+    if util_layernorm.GRAPH_DECODE if graph is None else graph:
+        info = graph_decode.DecodeGraphInfo(graph_decode.why_not(model, enc.device, use_cache, max_length))
+        if info.reason is None:
+            stepper = graph_decode.GenerateStepper(model, info)
+    else:
+        info = graph_decode.DecodeGraphInfo("not asked for")
+    model.last_decode_graph = info
+    advance = SampleAdvanceInfo(None if (util_layernorm.SAMPLE_ADVANCE if sample_advance is None else sample_advance)
+                                else "not asked for")
+    model.last_sample_advance = advance
+    if advance.reason is None:
+        advance.reason = _sample_why_not(plan, top_k, top_p)
+    if advance.reason is None:
+        return _checked(cache, _greedy_advanced(model, enc, attention_mask, start, plan, max_length, cache, stepper, advance,
+                                                whole if whole.reason is None else None, draw))
+    return _checked(cache, _sample_eager(model, enc, attention_mask, start, pad, eos_t, procs, max_length, cache, stepper,
+                                         advance, draw))
 
 
 def _gather(t, idx):

@@ -290,9 +290,12 @@ class GreedyStepGraph:
         decoder.tokens.copy_(bufs.next_tokens.view(-1, 1))
         logits = decoder._issue().to(torch.float32)
         cur = decoder.cache.position()              # after the decoder's increment: the length of the history, this step's cur
-        ops.greedy_advance_at(logits, bufs, cur, 0, ngram=plan.ngram, ban_ids=plan.ban, ban_below=plan.min_length,
-                              forced_bos=plan.forced_bos, forced_eos=plan.forced_eos, eos_ids=plan.eos, pad=plan.pad)
+        self._advance(ops, logits, cur, dict(ngram=plan.ngram, ban_ids=plan.ban, ban_below=plan.min_length,
+                                             forced_bos=plan.forced_bos, forced_eos=plan.forced_eos, eos_ids=plan.eos, pad=plan.pad))
         return logits
+
+    def _advance(self, ops, logits, cur, settings):
+        ops.greedy_advance_at(logits, self.buffers, cur, 0, **settings)
 
     def step(self):
         decoder, cache = self.decoder, self.decoder.cache
@@ -314,6 +317,27 @@ class GreedyStepGraph:
         entry[0].replay()
         self.info.replays += 1
         decoder.info.replays += 1
+
+
+class SampleGraphInfo(GreedyGraphInfo):
+    """What a sample() call did with ``sample_graph``: as GreedyGraphInfo."""
+
+    def __repr__(self):
+        return f"SampleGraphInfo(captured={self.captured}, replays={self.replays}, reason={self.reason!r})"
+
+
+class SampleStepGraph(GreedyStepGraph):
+    """Whole sampling steps of one sample() call as a captured graph: GreedyStepGraph over an ops.SampleBuffers, with
+    ops.sample_advance_at in the place of the arg-max.  ``draw``: dict(seed, temperature, top_k, top_p), kernel arguments and
+    constant for the call; the generator is keyed by (seed, row, position) and has no state, so one graph serves every step."""
+
+    def __init__(self, decoder, info, buffers, plan, draw):
+        super().__init__(decoder, info, buffers, plan)
+        self.draw = draw
+
+    def _advance(self, ops, logits, cur, settings):
+        ops.sample_advance_at(logits, self.buffers, cur, self.draw["seed"], 0, self.draw["temperature"], self.draw["top_k"],
+                              self.draw["top_p"], **settings)
 
 
 class GenerateStepper:

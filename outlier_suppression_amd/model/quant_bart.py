@@ -958,6 +958,21 @@ class QuantizedBartForConditionalGeneration(QuantizedModule):
         return generation.generate(self, input_ids, attention_mask=attention_mask, max_length=max_length,
                                    num_beams=num_beams, **kwargs)
 
+    @torch.no_grad()
+    def sample(self, input_ids, attention_mask=None, max_length=None, seed=None, temperature=1.0, top_k=50, top_p=1.0, **kwargs):
+        """Seeded sampling with a KV cache (model/generation.py, sample; model/sampling.py): token ids [B, L] padded with
+        pad_token_id, a function of the inputs and ``seed`` alone (None: one drawn from torch's default CPU generator).  The
+        random stream is the package's own, so the tokens are not transformers'; generate() keeps refusing ``do_sample``.
+        ``temperature``, ``top_k`` (0: every token; exactly k survive, ties by smaller token) and ``top_p`` (over the
+        renormalised survivors) shape the distribution; settings, ``cache_codes`` and ``graph`` as in generate().
+        ``sample_advance``: everything after the model step in one kernel call per token (None: the package switch,
+        set_sample_advance; ops.sample_advance); ``self.last_sample_advance`` then says how many steps took it (advanced,
+        eager, reason).  ``sample_graph``: a whole step captured into one graph and replayed (None: the package switch,
+        set_sample_graph; it implies ``graph`` and ``sample_advance`` for the call); ``self.last_sample_graph`` then says
+        what happened (captured, replays, reason)."""
+        return generation.sample(self, input_ids, attention_mask=attention_mask, max_length=max_length, seed=seed,
+                                 temperature=temperature, top_k=top_k, top_p=top_p, **kwargs)
+
 
 class QuantizedBartClassificationHead(QuantizedModule):
     """quant_bart.py:505-529: the sentence representation, the tanh layer's output (and the logits) are quantizer sites;

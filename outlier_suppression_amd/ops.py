@@ -2193,3 +2193,92 @@ def greedy_advance_at(logits, buffers, cur, cur_add=0, ngram=0, ban_ids=None, ba
         return None
     _hip.check(rc, "greedy_advance_at")
     return buffers
+
+
+class SampleBuffers(GreedyBuffers):
+    """GreedyBuffers for osq_sample_advance: the same state, a workspace sized for (vocab, top_k)."""
+
+    def __init__(self, bsz, max_length, device, vocab=None, top_k=0):
+        self.top_k = int(top_k)
+        super().__init__(bsz, max_length, device, vocab)
+
+    def room(self, vocab):
+        nbytes = max(int(_hip.load().osq_sample_advance_workspace_bytes(self.seq.shape[0], int(vocab), self.top_k)), 8)
+        if self.workspace is None or self.workspace.numel() < nbytes:
+            self.workspace = torch.empty(nbytes, dtype=torch.uint8, device=self.seq.device)
+        return self.workspace
+
+
+def _sample_advance_operands(what, logits, buffers, ban_ids, eos_ids, seed, temperature, top_k, top_p, uniforms):
+    """_greedy_advance_operands, and the arguments after the workspace: (head, counts, tail) with the stream last."""
+    top_k = int(top_k)
+    if not 0 <= top_k <= 64:                         # the workspace's size follows it: refused before one is sized
+        raise ValueError(f"{what}: top_k must lie in [0, 64]")
+    if not isinstance(buffers, SampleBuffers):
+        raise TypeError(f"{what}: buffers must be an ops.SampleBuffers")
+    buffers.top_k = max(buffers.top_k, top_k)
+    head, counts, tail = _greedy_advance_operands(what, logits, buffers, ban_ids, eos_ids)
+    if uniforms is not None:
+        _hip.require_device(uniforms)
+        if (uniforms.dtype != torch.float32 or tuple(uniforms.shape) != (logits.shape[0],) or not uniforms.is_contiguous()
+                or uniforms.device != logits.device):
+            raise ValueError(f"{what}: uniforms must be a contiguous float32 [bsz] tensor on the device of logits")
+    draw = (int(seed) & 0xFFFFFFFFFFFFFFFF, float(temperature), top_k, float(top_p), _hip.ptr(uniforms))
+    return head, counts, tail[:-1] + draw + tail[-1:]
+
+
+def sample_advance(logits, buffers, cur, seed, temperature=1.0, top_k=0, top_p=1.0, ngram=0, ban_ids=None, forced=None,
+                   eos_ids=None, pad=0, uniforms=None):
+    """One sampling step after the model (osq_sample_advance, csrc/sample_advance.hip): ``greedy_advance`` with a seeded
+    draw in the place of the arg-max.  From the fp32 ``logits`` [bsz, vocab] and ``buffers`` (a SampleBuffers) at history
+    length ``cur``: the banned tokens, z = logits / ``temperature``, the ``top_k`` largest (0: all; up to 64; equal values by
+    smaller token, exactly top_k of them), the ``top_p`` cut over their renormalised weights (with top_k >= 1), and the token
+    the row's uniform u selects -- Philox4x32-10 keyed by ``seed`` at counter (row, cur), or ``uniforms`` [bsz] fp32 in [0, 1)
+    on the device -- then greedy_advance's pad / eos arithmetic, ``buffers.seq[:, cur]``, ``buffers.next_tokens`` and
+    ``buffers.go_on``.  Three launches on the current stream, no synchronisation; returns ``buffers``, or None when the
+    library does not take the call (top_k == 0 with top_p < 1: the caller takes its other path)."""
+    lib = _hip.load()
+    head, (n_ban, n_eos), tail = _sample_advance_operands("sample_advance", logits, buffers, ban_ids, eos_ids, seed,
+                                                          temperature, top_k, top_p, uniforms)
+    rc = lib.osq_sample_advance(*head, int(cur), int(ngram), _hip.ptr(ban_ids) if n_ban else None, n_ban,
+                                -1 if forced is None else int(forced), _hip.ptr(eos_ids) if n_eos else None, n_eos, int(pad),
+                                buffers.unfinished.data_ptr(), *tail)
+    if rc == _hip.ERR_UNSUPPORTED:
+        return None
+    _hip.check(rc, "sample_advance")
+    return buffers
+
+
+def sample_advance_at(logits, buffers, cur, seed, cur_add=0, temperature=1.0, top_k=0, top_p=1.0, ngram=0, ban_ids=None,
+                      ban_below=0, forced_bos=None, forced_eos=None, eos_ids=None, pad=0, uniforms=None):
+    """sample_advance with the position read by the launches (osq_sample_advance_at): ``cur`` is one int32 on the device and
+    the step is taken at length ``*cur + cur_add``; ``ban_below``, ``forced_bos`` and ``forced_eos`` as in greedy_advance_at.
+    The seed is an argument and the generator has no state, so a captured graph of the call serves every step.  For a length
+    in [1, max_length) everything written is word-equal to ``sample_advance`` at that length; outside it ``buffers.go_on``
+    receives -1 and nothing else is written."""
+    lib = _hip.load()
+    head, (n_ban, n_eos), tail = _sample_advance_operands("sample_advance_at", logits, buffers, ban_ids, eos_ids, seed,
+                                                          temperature, top_k, top_p, uniforms)
+    _hip.require_device(cur)
+    if cur.dtype != torch.int32 or cur.numel() != 1 or cur.device != logits.device:
+        raise TypeError("sample_advance_at: cur must be one int32 on the device of logits")
+    rc = lib.osq_sample_advance_at(*head, cur.data_ptr(), int(cur_add), int(ngram), _hip.ptr(ban_ids) if n_ban else None, n_ban,
+                                   int(ban_below), -1 if forced_bos is None else int(forced_bos),
+                                   -1 if forced_eos is None else int(forced_eos), _hip.ptr(eos_ids) if n_eos else None, n_eos,
+                                   int(pad), buffers.unfinished.data_ptr(), *tail)
+    if rc == _hip.ERR_UNSUPPORTED:
+        return None
+    _hip.check(rc, "sample_advance_at")
+    return buffers
+
+
+def sample_uniforms(seed, bsz, cur, device):
+    """The ``bsz`` uniforms sample_advance draws at history length ``cur`` with ``seed`` (osq_sample_uniforms): fp32 [bsz] on
+    ``device``, word-equal to model.sampling.uniforms on the host."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError(f"outlier_suppression_amd: tensors must live on a HIP device (got device={device}); there is no CPU path.")
+    out = torch.empty(int(bsz), dtype=torch.float32, device=device)
+    _hip.check(_hip.load().osq_sample_uniforms(int(seed) & 0xFFFFFFFFFFFFFFFF, int(bsz), int(cur), out.data_ptr(),
+                                               _hip.raw_stream(device)), "sample_uniforms")
+    return out

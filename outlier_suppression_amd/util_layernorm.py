@@ -78,6 +78,17 @@ it on.
 forced tokens included; a token then costs the host one replay and one read of the stopping word.  For its call it implies
 ``GRAPH_DECODE`` and ``GREEDY_ADVANCE``.
 ``outlier_suppression_amd.set_greedy_graph(True)`` / ``OSQ_GREEDY_GRAPH=1`` / ``generate(..., greedy_graph=True)`` turn it on.
+
+``SAMPLE_ADVANCE`` (default OFF): sample() hands everything after the model step -- the banned tokens, temperature, top-k /
+top-p, the seeded draw, the pad / eos arithmetic, the new token into the sequence and the stopping word -- to
+``ops.sample_advance`` (csrc/sample_advance.hip) instead of the torch lines (model/sampling.py).  The same rule and the same
+uniforms; the sums are fp32 in another order, so a draw within rounding of a boundary may select the neighbouring token.
+``outlier_suppression_amd.set_sample_advance(True)`` / ``OSQ_SAMPLE_ADVANCE=1`` / ``sample(..., sample_advance=True)`` turn it on.
+
+``SAMPLE_GRAPH`` (default OFF): sample() captures a WHOLE step -- the token copy, the model step and ``ops.sample_advance_at``
+-- into one graph and replays it (model/graph_decode.py, SampleStepGraph); the generator is keyed by (seed, row, position), so
+one graph serves every step.  For its call it implies ``GRAPH_DECODE`` and ``SAMPLE_ADVANCE``.
+``outlier_suppression_amd.set_sample_graph(True)`` / ``OSQ_SAMPLE_GRAPH=1`` / ``sample(..., sample_graph=True)`` turn it on.
 """
 import torch
 import torch.nn.functional as F
@@ -99,6 +110,8 @@ BEAM_ADVANCE = False     # generate(): a beam step's bookkeeping after the selec
 BEAM_GRAPH = False       # generate(): capture a whole beam-search step -- model, selection, bookkeeping, cache row index -- into one graph (implies the three above for the call; set_beam_graph / OSQ_BEAM_GRAPH=1 / generate(beam_graph=True))
 GREEDY_ADVANCE = False   # generate(): a greedy step's processors, arg-max, pad / eos lines, sequence append and stopping word as one kernel call (set_greedy_advance / OSQ_GREEDY_ADVANCE=1 / generate(greedy_advance=True))
 GREEDY_GRAPH = False     # generate(): capture a whole greedy step -- token copy, model, the kernel call above -- into one graph (implies GRAPH_DECODE and GREEDY_ADVANCE for the call; set_greedy_graph / OSQ_GREEDY_GRAPH=1 / generate(greedy_graph=True))
+SAMPLE_ADVANCE = False   # sample(): a sampling step's processors, temperature / top-k / top-p, seeded draw, pad / eos lines, sequence append and stopping word as one kernel call (set_sample_advance / OSQ_SAMPLE_ADVANCE=1 / sample(sample_advance=True))
+SAMPLE_GRAPH = False     # sample(): capture a whole sampling step -- token copy, model, the kernel call above -- into one graph (implies GRAPH_DECODE and SAMPLE_ADVANCE for the call; set_sample_graph / OSQ_SAMPLE_GRAPH=1 / sample(sample_graph=True))
 CACHE_CODES = False      # incremental decoding: new KV caches hold integer codes, one byte per element (same words read back; set_cache_codes / OSQ_CACHE_CODES=1)
 
 

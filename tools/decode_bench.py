@@ -46,6 +46,14 @@ forms are asserted equal before a time is printed; every form is timed in turn w
     python tools/decode_bench.py --beam-advance [--out profiles/beam_advance_ab.txt]
     python tools/decode_bench.py --beam-graph [--out profiles/beam_graph_ab.txt]
     python tools/decode_bench.py --greedy-advance [--out profiles/greedy_advance_ab.txt]
+
+--sample-advance: the A/B is seeded sampling (sample()) with everything after the model step as one kernel call
+(ops.sample_advance, csrc/sample_advance.hip; sample(sample_advance=True)) and with the whole step as one captured graph
+(sample(sample_graph=True); graph_decode.SampleStepGraph) against the torch lines of model/sampling.py, for top_k 50 with
+top_p 0.95 and for the whole vocabulary, the tokens asserted equal between the forms first; then the selection alone against
+transformers' own lines (warpers, softmax, torch.multinomial) and against sampling.select_torch.
+
+    python tools/decode_bench.py --sample-advance [--out profiles/sample_advance_ab.txt]
 """
 import argparse
 import copy
@@ -571,6 +579,133 @@ def greedy_advance_ab(q, ids, mask, args):
     return lines
 
 
+# (label, sample()'s switches) of the forms --sample-advance compares; the first is the baseline of its group
+SAMPLE_FORMS = [("graph", dict(graph=True)),
+                ("graph + sample_advance", dict(graph=True, sample_advance=True)),
+                ("sample_graph", dict(sample_graph=True)),
+                ("issued", dict(graph=False)),
+                ("issued + sample_advance", dict(graph=False, sample_advance=True))]
+
+
+def sample_advance_ab(q, ids, mask, args):
+    from transformers.generation.logits_process import TemperatureLogitsWarper, TopKLogitsWarper, TopPLogitsWarper
+    from outlier_suppression_amd import ops, util_layernorm as UL
+    from outlier_suppression_amd.model import generation, sampling
+    dev = ids.device
+    bsz, vocab, at, max_length, seed = args.batch, q.config.vocab_size, 31, 62, 20261019
+    draws = (("top_k 50, top_p 0.95, temperature 0.8", dict(top_k=50, top_p=0.95, temperature=0.8)),
+             ("the whole vocabulary, temperature 0.8", dict(top_k=0, top_p=1.0, temperature=0.8)))
+    lines = [f"seeded sampling: everything after the model step as one kernel call (ops.sample_advance) and the whole step as one "
+             f"captured graph (sample_graph) against the torch lines (model/sampling.py); BART-large shape, batch {bsz}, source "
+             f"{args.src}, sample(max_length={max_length}, min_length={max_length}, seed={seed}) (BART's forced eos on the last "
+             f"step); the one-launch attention on in the issued forms as in the graphs; every form timed in turn in each of "
+             f"{args.reps} rounds, one process; median [min, max]"]
+    print(lines[0], flush=True)
+    old = UL.FUSE_DECODE_ATTENTION
+    UL.FUSE_DECODE_ATTENTION = True                 # the issued forms run the launches the graphs hold: the same words
+    try:
+        with torch.no_grad():
+            for name, draw in draws:
+                kw = dict(max_length=max_length, min_length=max_length, seed=seed, **draw)
+                times = {label: [] for label, _ in SAMPLE_FORMS}
+                tokens, did = {}, {}
+                for r in range(args.reps + 1):      # the first round warms every form up
+                    for label, switches in SAMPLE_FORMS:
+                        secs, tokens[label] = _timed(lambda: q.sample(ids, attention_mask=mask, **kw, **switches), 1.0)
+                        did[label] = (q.last_sample_advance.advanced, q.last_sample_advance.eager, q.last_decode_graph.captured,
+                                      q.last_decode_graph.replays, q.last_sample_graph.captured)
+                        if r:
+                            times[label].append(secs)
+                first = tokens[SAMPLE_FORMS[0][0]]
+                assert did["sample_graph"][4] == 1 and did["graph + sample_advance"][:2] == (max_length - 1, 0), did
+                families = [[label for label in tokens if (did[label][0] > 0) == kernel] for kernel in (False, True)]
+                for family in families:             # before a time is printed
+                    for label in family:
+                        assert bool(torch.equal(tokens[label], tokens[family[0]])), f"{label}: tokens differ from {family[0]}"
+                parted = (tokens[families[0][0]] != tokens[families[1][0]]).any(dim=0).nonzero()
+                # with top_k the intervals of the running sums are wide and the two families must agree; over the whole
+                # vocabulary of a near-flat distribution an interval is about W / vocab, the size of the fp32 sums' own band
+                assert draw["top_k"] == 0 or parted.numel() == 0, f"{name}: the kernel's tokens part from the torch lines'"
+                agree = (f"equal in all {len(tokens)} forms" if parted.numel() == 0 else
+                         f"equal among the {len(families[0])} torch forms and among the {len(families[1])} kernel forms; the two "
+                         f"part at position {int(parted[0])} (the fp32 sums run in another order and an interval here is about "
+                         f"W / {vocab}: a draw within rounding of a boundary)")
+                block = [f"{name}: tokens {tuple(first.shape)} {agree}; s, wall time of the call (a graph "
+                         "form: capture included); (steps through the kernel, through torch, graphs captured, replays, "
+                         "whole-step graphs):"]
+                block += [f"    {label:42s} {_stats(t)}   {did[label]}" for label, t in times.items()]
+                for group in (SAMPLE_FORMS[:3], SAMPLE_FORMS[3:5]):
+                    base = sorted(times[group[0][0]])
+                    spread = base[-1] - base[0]
+                    for label, _ in group[1:]:
+                        mine = sorted(times[label])
+                        gain = base[len(base) // 2] - mine[len(mine) // 2]
+                        block.append(f"    {label} against {group[0][0]}: median gain {gain * 1e3:.1f} ms "
+                                     f"({gain / (max_length - 1) * 1e3:.3f} ms per token, {gain / base[len(base) // 2] * 100:.1f} %), "
+                                     f"the baseline's own spread {spread * 1e3:.1f} ms: "
+                                     f"{'above' if gain > spread else 'within'} it")
+                print("\n".join(block), flush=True)
+                lines += block
+
+            # the selection alone at length `at`: min_length active, one eos id, every row unfinished
+            g = torch.Generator(device="cpu").manual_seed(3)
+            logits = (torch.randn(bsz, vocab, generator=g) * 4).to(dev)
+            history = torch.randint(3, 40, (bsz, at), generator=g).to(dev)
+            eos = torch.tensor([2], device=dev)
+            procs = generation._processors(max_length, eos, 0, None, 2, max_length, dev)
+            plan = generation._GreedyPlan(procs, dev, vocab, max_length, eos, 1)
+            assert plan.reason is None, plan.reason
+            lines.append(f"the selection alone (with the read of the stopping word), logits [{bsz}, {vocab}] fp32 (randn * 4), history "
+                         f"of {at} tokens, min_length {max_length} active, one eos id, ms; transformers' lines: its temperature / "
+                         "top-k / top-p warpers, softmax and torch.multinomial (another random stream: its tokens are not compared):")
+            for name, draw in draws:
+                bufs = ops.SampleBuffers(bsz, max_length, dev, vocab, draw["top_k"])
+                bufs.seq[:, :at] = history
+                warpers = [TemperatureLogitsWarper(draw["temperature"])]
+                if draw["top_k"]:
+                    warpers.append(TopKLogitsWarper(draw["top_k"]))
+                if draw["top_p"] < 1.0:
+                    warpers.append(TopPLogitsWarper(draw["top_p"]))
+
+                def finish(nxt):
+                    unfinished = torch.ones(bsz, dtype=torch.long, device=dev)
+                    nxt = nxt * unfinished + 1 * (1 - unfinished)
+                    torch.cat([history, nxt[:, None]], dim=-1)
+                    unfinished = unfinished & ~torch.isin(nxt, eos)
+                    return nxt, bool(unfinished.max() == 0)
+
+                def transformers_lines():
+                    scores = procs(history, logits)
+                    for w in warpers:
+                        scores = w(history, scores)
+                    return finish(torch.multinomial(torch.softmax(scores, dim=-1), num_samples=1).squeeze(1))
+
+                def torch_lines():
+                    u = sampling.uniforms(seed, bsz, at)
+                    return finish(sampling.select_torch(procs(history, logits), u, **draw))
+
+                def kernel():
+                    bufs.unfinished.fill_(1)
+                    ops.sample_advance(logits, bufs, at, seed, ngram=plan.ngram, ban_ids=plan.ban, forced=plan.forced(at),
+                                       eos_ids=plan.eos, pad=plan.pad, **draw)
+                    return bufs.next_tokens, not int(bufs.go_on)
+                forms = {"transformers' lines": transformers_lines, "sampling.select_torch": torch_lines, "ops.sample_advance": kernel}
+                times = {label: [] for label in forms}
+                outs = {}
+                for r in range(args.reps + 3):      # three lead-in rounds
+                    for label, fn in forms.items():
+                        ms, outs[label] = _timed(fn)
+                        if r >= 3:
+                            times[label].append(ms)
+                (a, a_stop), (b, b_stop) = outs["sampling.select_torch"], outs["ops.sample_advance"]
+                assert bool(torch.equal(a, b)) and a_stop == b_stop, "the kernel's tokens differ from the torch lines'"
+                lines += [f"    {name}, {label:24s} {_stats(t)}" for label, t in times.items()]
+            print("\n".join(lines[-7:]), flush=True)
+    finally:
+        UL.FUSE_DECODE_ATTENTION = old
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=32)
@@ -586,9 +721,16 @@ def main():
     ap.add_argument("--beam-advance", action="store_true")
     ap.add_argument("--beam-graph", action="store_true")
     ap.add_argument("--greedy-advance", action="store_true")
+    ap.add_argument("--sample-advance", action="store_true")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     q, ids, mask = build(args.batch, args.src, args.layers)
+    if args.sample_advance:
+        text = "\n".join(sample_advance_ab(q, ids, mask, args))
+        if args.out:
+            with open(args.out, "w") as f:
+                f.write(text + "\n")
+        return
     if args.greedy_advance:
         text = "\n".join(greedy_advance_ab(q, ids, mask, args))
         if args.out:
