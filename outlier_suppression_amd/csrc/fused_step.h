@@ -101,8 +101,8 @@ __device__ __forceinline__ unsigned long long side_granule(unsigned int tag, con
 // a selection on -- happen while the streaming workgroups are still arriving.
 // One CU retires an instruction of a 16-wave workgroup in ~8 clocks, so the registers are packed: with CH = ceil(cmax/64),
 // a chunk's first 64 (CH - 1) values fill CH - 1 registers -- always full --, and the TAILS (cmax - 64 (CH - 1) values or
-// one less) of the four chunks of a group share 1, 2 or 4 registers (tpad = the tail length rounded up to a power of
-// two, 64 / tpad chunks per register): 20 registers per lane instead of 32 at the bench lengths.  noinline: one copy of the selection per CH for the four
+// one less) of the eight chunks of a group share 1, 2, 4 or 8 registers (tpad = the tail length rounded up to a power of
+// two, min(8, 64 / tpad) chunks per register): 18 registers per lane in use instead of 32 at the bench lengths.  noinline: one copy of the selection per CH for the four
 // kernel instantiations; the function publishes the side's granule itself, so that what the call costs at its end
 // (callee-saved registers coming back from scratch) is behind the hand-off, not in front of it.
 template <int CH>
@@ -144,9 +144,9 @@ __device__ __attribute__((noinline)) void fused_select(const float* src_, const 
     const unsigned int cmax = qv + (rv ? 1u : 0u);                   // V > 0: 64 (CH - 1) < cmax <= 64 CH
     const unsigned int tlen = cmax - static_cast<unsigned int>(OSQ_WAVE * (CH - 1));
     const unsigned int lt = tlen <= 1u ? 0u : 32u - static_cast<unsigned int>(__builtin_clz(tlen - 1u));   // tpad = 1 << lt >= tlen
-    const unsigned int cpr = (64u >> lt) >= static_cast<unsigned int>(GC) ? static_cast<unsigned int>(GC) : 64u >> lt;   // chunks per tail register: 4, 2, 1
-    const unsigned int ntg = static_cast<unsigned int>(GC) / cpr;                                          // tail registers per group: 1, 2, 4
-    // registers: [group j: 4 (CH - 1) full blocks][group j: 4 tail registers, ntg of them in use], j = 0..3
+    const unsigned int cpr = (64u >> lt) >= static_cast<unsigned int>(GC) ? static_cast<unsigned int>(GC) : 64u >> lt;   // chunks per tail register: 8, 4, 2, 1
+    const unsigned int ntg = static_cast<unsigned int>(GC) / cpr;                                          // tail registers per group: 1, 2, 4, 8
+    // registers: [group j: 8 (CH - 1) full blocks][group j: 8 tail registers, ntg of them in use], j = 0, 1
     constexpr int RG = GC * (CH - 1) + GC;                           // per group
     // this lane's place in a tail register: chunk ci of the register's cpr, tail position tl
     const unsigned int ci = static_cast<unsigned int>(lane) >> lt, tl = static_cast<unsigned int>(lane) & ((1u << lt) - 1u);

@@ -63,6 +63,23 @@ def test_minmax_knob_cases_pass_on_the_tunable_build():
     assert "6 passed" in r.stdout and "skipped" not in r.stdout.splitlines()[-1], tail
 
 
+def test_fused_select_knob_cases_pass_on_the_tunable_build():
+    """The test_knobs_* cases of tests/test_gpu_fused_select.py (fused_grid = 3 .. 132: all 21 chunk shapes of fused_select on
+    small grids, the row mapping with one streaming workgroup; fused_gate 0 / 1 / 2 x select_hint 0 / 1) against
+    libosq_hip_dbg.so: all run, none skipped."""
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    if not os.path.exists(DBG):
+        pytest.skip("libosq_hip_dbg.so not built (make -C outlier_suppression_amd/csrc dbg)")
+    env = dict(os.environ, OSQ_HIP_LIBRARY=DBG)
+    r = subprocess.run([sys.executable, "-m", "pytest", "-q", "-m", "gpu", "-x", "-p", "no:cacheprovider",
+                        os.path.join(ROOT, "tests", "test_gpu_fused_select.py"), "-k", "test_knobs"],
+                       env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
+    tail = r.stdout[-3000:] + r.stderr[-2000:]
+    assert r.returncode == 0, tail
+    assert "8 passed" in r.stdout and "skipped" not in r.stdout.splitlines()[-1], tail
+
+
 def test_tunable_build_accepts_what_the_release_library_refuses():
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
