@@ -44,7 +44,7 @@ typedef void* osq_stream;
  *     osq_decode_attention_codes_at, osq_beam_select_workspace_bytes, osq_beam_select, osq_beam_advance,
  *     osq_beam_select_at, osq_beam_advance_at, osq_greedy_advance_workspace_bytes, osq_greedy_advance,
  *     osq_greedy_advance_at, osq_sample_advance_workspace_bytes, osq_sample_advance, osq_sample_advance_at,
- *     osq_sample_uniforms. */
+ *     osq_sample_uniforms, osq_sample_nucleus_workspace_bytes, osq_sample_nucleus, osq_sample_nucleus_at. */
 #define OSQ_ABI_VERSION 10
 
 typedef enum osq_status {
@@ -1088,6 +1088,61 @@ int osq_sample_advance_at(const float* logits, int64_t logits_stride, int64_t* s
 /* out[b] = the u osq_sample_advance draws for row b at history length cur with this seed, b in [0, bsz): the same device
  * function as the step's. */
 int osq_sample_uniforms(uint64_t seed, int64_t bsz, int64_t cur, float* out, osq_stream stream);
+
+/* ------------------------------------------------------------------ a nucleus over the whole vocabulary (sample_nucleus.hip) */
+
+/* One sampling step after the model for top_k == 0 and top_p <= 1, the form osq_sample_advance refuses: every token left is
+ * ranked, the nucleus is cut from the ranking and the draw is taken from it -- without a sort.  Bans, the forced token, pad /
+ * eos, seq[b, cur], next_tokens, unfinished, go_on and the uniform u (Philox word 0 with key (seed lo, seed hi) and counter
+ * (b, cur, 0, 0), or uniforms[b]) are osq_sample_advance's, word for word; a forced step draws nothing and reads no logit.
+ * Otherwise, for every batch row b:
+ *     z = x / temperature (one IEEE fp32 division), -0.0 taken as +0.0.  A banned token, a NaN and -inf weigh 0.
+ *     the survivors rank by larger z first, equal z by smaller token; m the largest z, w_i = 1 where z_i == m (m = +inf
+ *         included), else exp(z_i - m)
+ *     rank i stays iff the weights ranked above it sum below top_p * total; rank 0 always stays; W = the kept ranks' total
+ *     token = the first kept rank whose running sum passes u * W, the last kept rank when rounding leaves none; 0 for a row
+ *         without a survivor.
+ * top_p == 1 is taken: the plain draw from every token IN RANK ORDER -- not word-equal to osq_sample_advance(top_k = 0,
+ * top_p = 1), which walks in token order.
+ * How the kernel decides (this fixes the fp32 words; tokens are tolerance-equal to any other summation order).  Let key(z) be
+ * the order-preserving 32-bit image of z and S(k) the fp32 sum, in ONE fixed order, of w_i over the tokens with key(z_i) > k;
+ * a token not above k adds 0.0f in the same position of the same tree.  Every fp32 add rounds monotonically, so S is
+ * non-increasing in k and both searches are bisections over k (at most 32 rounds each), no sort:
+ *     the cut:  total = S(0), bound = top_p * total.  k* = the smallest key with S(k*) < bound (a key that is present).  Of the
+ *         n tokens with that key, in token order, the j-th (0-based) stays iff S(k*) + float(j) * w(k*) < bound, one multiply
+ *         and one add; r >= 1 of them stay, and W = S(k*) + float(r) * w(k*).
+ *     the draw: target = u * W.  kv = the smallest key >= k* with S(kv) <= target (present too).  Inside its group the pick is
+ *         the first j with S(kv) + float(j + 1) * w(kv) > target, among the r kept ones when kv == k*; the token is the j-th
+ *         token with that key, in token order.  When rounding leaves no such j the pick is the group's last eligible token --
+ *         for kv == k* the last kept rank.  (key(m) always qualifies as kv: S(key(m)) = 0.)
+ * The order of S: the row in 1024 runs of 50 consecutive tokens; a run's tokens 0..24 in order, its tokens 25..49 in order,
+ * the two halves added; 64 consecutive runs by four symmetric lane-exchange steps (xor 1, xor 2, mirror of 8, mirror of 16) and
+ * then (r0 + r16) + (r32 + r48); the 16 results left to right.  It depends on vocab alone: not on bsz, the rows' stride or
+ * alignment.  No atomics on device memory: the same inputs give the same words on every run, and a row's token does not depend
+ * on bsz or on its row index but through the Philox counter.  The logits are read once.
+ * vocab <= 51200 (what one workgroup holds in registers: 1024 threads of 50 tokens); above it OSQ_ERR_UNSUPPORTED, nothing
+ * launched, and osq_sample_nucleus_workspace_bytes returns 0.
+ * workspace: at least osq_sample_nucleus_workspace_bytes(bsz, vocab) bytes (the rows' flags: 4 * bsz) of device memory, 8-byte
+ * aligned, contents arbitrary; one per stream in flight.  One workgroup per row, then one for go_on; no workgroup waits for
+ * another.  No host synchronisation, no allocation, nothing read from the host: legal inside a stream capture.
+ * OSQ_ERR_INVALID_ARGUMENT, nothing launched: what osq_sample_advance refuses but for top_k. */
+size_t osq_sample_nucleus_workspace_bytes(int64_t bsz, int64_t vocab);
+int osq_sample_nucleus(const float* logits, int64_t logits_stride, int64_t* seq, int64_t seq_stride, int64_t cur,
+                       int64_t ngram, const int64_t* ban_ids, int64_t n_ban, int64_t forced, const int64_t* eos_ids,
+                       int64_t n_eos, int64_t pad, uint8_t* unfinished, int64_t bsz, int64_t vocab, int64_t max_length,
+                       int64_t* next_tokens, int32_t* go_on, void* workspace, size_t workspace_bytes, uint64_t seed,
+                       float temperature, float top_p, const float* uniforms, osq_stream stream);
+
+/* osq_sample_nucleus with the position read by the launches: cur = *cur_dev + cur_add, with ban_below, forced_bos and
+ * forced_eos as in osq_greedy_advance_at.  For every cur in [1, max_length) every output word equals osq_sample_nucleus called
+ * with that cur and the n_ban / forced the host would have passed.  A cur outside that range: go_on receives -1 and nothing
+ * else is written; no address is formed from a refused position. */
+int osq_sample_nucleus_at(const float* logits, int64_t logits_stride, int64_t* seq, int64_t seq_stride,
+                          const int32_t* cur_dev, int64_t cur_add, int64_t ngram, const int64_t* ban_ids, int64_t n_ban,
+                          int64_t ban_below, int64_t forced_bos, int64_t forced_eos, const int64_t* eos_ids, int64_t n_eos,
+                          int64_t pad, uint8_t* unfinished, int64_t bsz, int64_t vocab, int64_t max_length,
+                          int64_t* next_tokens, int32_t* go_on, void* workspace, size_t workspace_bytes, uint64_t seed,
+                          float temperature, float top_p, const float* uniforms, osq_stream stream);
 
 /* ------------------------------------------------------------------ bf16 / fp16 only (lowp.hip) */
 

@@ -157,6 +157,22 @@ def set_sample_graph(on=True):
     util_layernorm.SAMPLE_GRAPH = bool(on)
 
 
+def set_sample_nucleus(on=True):
+    """Where sample() takes a step with one kernel call (set_sample_advance, set_sample_graph), a nucleus over the whole
+    vocabulary -- ``top_k=0, top_p<1``, the form ops.sample_advance does not have -- goes to ops.sample_nucleus
+    (util_layernorm.SAMPLE_NUCLEUS; csrc/sample_nucleus.hip; default OFF) instead of falling back to the torch lines with the
+    reason "top_p below 1 without top_k".  OSQ_SAMPLE_NUCLEUS=1 turns it on at load; ``sample(..., sample_nucleus=True)``
+    asks for one call."""
+    from . import util_layernorm
+    util_layernorm.SAMPLE_NUCLEUS = bool(on)
+
+
+def sample_nucleus_from_environment(environ=None):
+    """What OSQ_SAMPLE_NUCLEUS asks for: unset, empty or "0" -> False, anything else -> True."""
+    import os
+    return (os.environ if environ is None else environ).get("OSQ_SAMPLE_NUCLEUS", "") not in ("", "0")
+
+
 def sample_advance_from_environment(environ=None):
     """What OSQ_SAMPLE_ADVANCE asks for: unset, empty or "0" -> False, anything else -> True."""
     import os
@@ -221,7 +237,8 @@ def reset_tier(_lib=None):
     (unset: off); OSQ_BEAM_GRAPH=1 beam search replays a whole step, bookkeeping included, as one captured graph (unset: off);
     OSQ_GREEDY_ADVANCE=1 greedy decoding takes a step with one kernel call (unset: off); OSQ_GREEDY_GRAPH=1 greedy decoding
     replays a whole step as one captured graph (unset: off); OSQ_SAMPLE_ADVANCE=1 sample() takes a step with one kernel call
-    (unset: off); OSQ_SAMPLE_GRAPH=1 sample() replays a whole step as one captured graph (unset: off)."""
+    (unset: off); OSQ_SAMPLE_GRAPH=1 sample() replays a whole step as one captured graph (unset: off); OSQ_SAMPLE_NUCLEUS=1
+    that kernel call takes a nucleus over the whole vocabulary too (unset: off)."""
     import os
     width = int(os.environ.get("OSQ_STRICT_SIMD", "8"))
     strict = os.environ.get("OSQ_STRICT", "")
@@ -242,6 +259,7 @@ def reset_tier(_lib=None):
     set_greedy_graph(greedy_graph_from_environment())
     set_sample_advance(sample_advance_from_environment())
     set_sample_graph(sample_graph_from_environment())
+    set_sample_nucleus(sample_nucleus_from_environment())
 
 
 _apply_environment = reset_tier

@@ -44,12 +44,14 @@ __device__ __forceinline__ void block_argmax(unsigned int& hi, unsigned int& lo,
     }
 }
 
-// The banned tokens of the chunk [c0, c0 + len) of one row into s_ban (kBsChunk / 32 words, one bit per token): the n_ban ids
-// of ban_ids, and, with n = ngram > 0 and cur >= n, the last token of every window of s[0 : cur] that starts with the suffix
-// s[cur - n + 1 : cur].  s is read only then.  The caller's next barrier publishes the bitmap.
-__device__ __forceinline__ void chunk_bans(unsigned int* s_ban, const int64_t* ban_ids, int n_ban, const int64_t* s, int cur,
-                                           int n, int c0, int len) {
-    if (threadIdx.x < kBsChunk / 32) s_ban[threadIdx.x] = 0u;
+// The banned tokens of the span [c0, c0 + len) of one row into s_ban (kWords words, one bit per token, len <= 32 kWords), by a
+// workgroup of kThreads: the n_ban ids of ban_ids, and, with n = ngram > 0 and cur >= n, the last token of every window of
+// s[0 : cur] that starts with the suffix s[cur - n + 1 : cur].  s is read only then.  The caller's next barrier publishes the
+// bitmap.
+template <int kThreads, int kWords>
+__device__ __forceinline__ void span_bans(unsigned int* s_ban, const int64_t* ban_ids, int n_ban, const int64_t* s, int cur,
+                                          int n, int c0, int len) {
+    for (int i = threadIdx.x; i < kWords; i += kThreads) s_ban[i] = 0u;
     __syncthreads();
     if (threadIdx.x < n_ban) {
         const int64_t t = ban_ids[threadIdx.x] - c0;
@@ -57,13 +59,19 @@ __device__ __forceinline__ void chunk_bans(unsigned int* s_ban, const int64_t* b
     }
     if (n > 0 && cur >= n) {                                      // window i bans its last token when it starts with the suffix
         const int64_t* suffix = s + (cur - n + 1);
-        for (int i = threadIdx.x; i <= cur - n; i += kBsThreads) {
+        for (int i = threadIdx.x; i <= cur - n; i += kThreads) {
             bool same = true;
             for (int k = 0; k < n - 1 && same; ++k) same = s[i + k] == suffix[k];
             const int64_t t = s[i + n - 1] - c0;
             if (same && t >= 0 && t < len) atomicOr(&s_ban[t >> 5], 1u << (t & 31));
         }
     }
+}
+
+// The chunk [c0, c0 + len) of a kBsThreads workgroup: kBsChunk / 32 words.
+__device__ __forceinline__ void chunk_bans(unsigned int* s_ban, const int64_t* ban_ids, int n_ban, const int64_t* s, int cur,
+                                           int n, int c0, int len) {
+    span_bans<kBsThreads, kBsChunk / 32>(s_ban, ban_ids, n_ban, s, cur, n, c0, len);
 }
 
 }  // namespace osq

@@ -479,7 +479,8 @@ def _greedy_advanced(model, enc, attention_mask, start, plan, max_length, cache,
     """The loop of _greedy with everything after the model step as one call of ops.greedy_advance: the sequence, the
     unfinished flags and the next tokens live in an ops.GreedyBuffers, the model is fed the kernel's next_tokens (without a
     cache: the sequence so far, a view), and the go_on word is read once per token (the one host sync of the torch lines).
-    ``draw`` (sample(): dict(seed, temperature, top_k, top_p)): the same loop on ops.sample_advance and an ops.SampleBuffers.
+    ``draw`` (sample(): dict(seed, temperature, top_k, top_p)): the same loop on ops.sample_advance and an ops.SampleBuffers;
+    with ``nucleus`` set in it (top_k == 0 with top_p < 1 under sample_nucleus) on ops.sample_nucleus.
 
     ``whole`` (a graph_decode.GreedyGraphInfo; generate(greedy_graph=True)): from the third step on a step is one replay of
     a captured graph that holds all of the above (graph_decode.GreedyStepGraph), a step on which a forced token fires
@@ -489,7 +490,8 @@ def _greedy_advanced(model, enc, attention_mask, start, plan, max_length, cache,
     if draw is None:
         bufs = ops.GreedyBuffers(enc.shape[0], max_length, enc.device, model.config.vocab_size)
     else:
-        bufs = ops.SampleBuffers(enc.shape[0], max_length, enc.device, model.config.vocab_size, draw["top_k"])
+        bufs = ops.SampleBuffers(enc.shape[0], max_length, enc.device, model.config.vocab_size, draw["top_k"],
+                                 nucleus=bool(draw.get("nucleus")))
     bufs.seq[:, 0] = start
     cur = 1
     captured = None
@@ -508,6 +510,9 @@ def _greedy_advanced(model, enc, attention_mask, start, plan, max_length, cache,
             if draw is None:
                 ops.greedy_advance(logits, bufs, cur, plan.ngram, plan.ban if cur < plan.min_length else None, plan.forced(cur),
                                    plan.eos, plan.pad)
+            elif draw.get("nucleus"):
+                ops.sample_nucleus(logits, bufs, cur, draw["seed"], draw["temperature"], draw["top_p"], plan.ngram,
+                                   plan.ban if cur < plan.min_length else None, plan.forced(cur), plan.eos, plan.pad)
             else:
                 ops.sample_advance(logits, bufs, cur, draw["seed"], draw["temperature"], draw["top_k"], draw["top_p"], plan.ngram,
                                    plan.ban if cur < plan.min_length else None, plan.forced(cur), plan.eos, plan.pad)
@@ -532,11 +537,17 @@ class SampleAdvanceInfo(GreedyAdvanceInfo):
         return f"SampleAdvanceInfo(advanced={self.advanced}, eager={self.eager}, reason={self.reason!r})"
 
 
-def _sample_why_not(plan, top_k, top_p):
+NUCLEUS_MAX_VOCAB = 51200          # kSnMaxVocab of csrc/sample_nucleus.hip: what one workgroup holds in registers
+
+
+def _sample_why_not(plan, top_k, top_p, nucleus=False, vocab=0):
     """None when ops.sample_advance takes the steps of this call, else the reason the torch lines run: those of _GreedyPlan
-    and the two forms the kernel does not have."""
+    and the two forms the kernel does not have.  ``nucleus`` (sample_nucleus): top_k == 0 with top_p < 1 is
+    ops.sample_nucleus's, for a vocabulary it holds."""
     if plan.reason is not None:
         return plan.reason
+    if top_k == 0 and top_p < 1.0 and nucleus:
+        return f"vocab above {NUCLEUS_MAX_VOCAB}" if vocab > NUCLEUS_MAX_VOCAB else None
     if top_k == 0 and top_p < 1.0:
         return "top_p below 1 without top_k"
     if top_k > 64:
@@ -566,7 +577,7 @@ def _sample_eager(model, enc, attention_mask, start, pad, eos, procs, max_length
 
 
 def sample(model, input_ids, attention_mask=None, max_length=None, seed=None, temperature=1.0, top_k=50, top_p=1.0,
-           use_cache=True, cache_codes=None, graph=None, sample_advance=None, sample_graph=None, **kwargs):
+           use_cache=True, cache_codes=None, graph=None, sample_advance=None, sample_graph=None, sample_nucleus=None, **kwargs):
     """Seeded sampling over a KV cache: generate()'s greedy loop with a draw in the place of the arg-max (model/sampling.py;
     the rule is osq_sample_advance's, include/osq_hip.h).  The tokens are a function of the inputs and ``seed`` alone -- the
     package's own random stream, not torch.multinomial's, so they are not transformers' tokens: hence an entry point of its
@@ -577,7 +588,8 @@ def sample(model, input_ids, attention_mask=None, max_length=None, seed=None, te
     hands everything after the model step to one kernel call (ops.sample_advance); ``model.last_sample_advance`` tells how
     many steps took it.  ``sample_graph=True`` (set_sample_graph) asks for ``graph`` and ``sample_advance`` and captures the
     whole step -- token copy, model, ops.sample_advance_at -- into one graph (graph_decode.SampleStepGraph);
-    ``model.last_sample_graph`` tells what happened."""
+    ``model.last_sample_graph`` tells what happened.  ``sample_nucleus=True`` (set_sample_nucleus): under either switch,
+    ``top_k=0`` with ``top_p<1`` goes to ops.sample_nucleus(_at) instead of falling back to the torch lines."""
     import math
     if kwargs.pop("synced_gpus", False):
         raise NotImplementedError("sample(): synced_gpus=True is not supported")
@@ -615,6 +627,8 @@ def sample(model, input_ids, attention_mask=None, max_length=None, seed=None, te
     codes = util_layernorm.CACHE_CODES if cache_codes is None else bool(cache_codes)
     cache = QuantizedBartCache(len(model.model.decoder.layers), capacity=max_length, codes=codes) if use_cache else None
     plan = _GreedyPlan(procs, enc.device, model.config.vocab_size, max_length, eos_t, pad)
+    nucleus = bool(util_layernorm.SAMPLE_NUCLEUS if sample_nucleus is None else sample_nucleus)
+    draw["nucleus"] = nucleus and top_k == 0 and top_p < 1.0
     # a whole step as one captured graph: it implies the two switches below for this call, where nothing stands against it
     whole = graph_decode.SampleGraphInfo(None if (util_layernorm.SAMPLE_GRAPH if sample_graph is None else sample_graph)
                                          else "not asked for")
@@ -624,7 +638,7 @@ def sample(model, input_ids, attention_mask=None, max_length=None, seed=None, te
             if whole.reason is None and value is not None and not value:
                 whole.reason = f"{name}=False was passed"
         whole.reason = (whole.reason or graph_decode.why_not(model, enc.device, use_cache, max_length)
-                        or _sample_why_not(plan, top_k, top_p))
+                        or _sample_why_not(plan, top_k, top_p, nucleus, model.config.vocab_size))
         if whole.reason is None:
             graph = sample_advance = True
     stepper = None
@@ -639,7 +653,7 @@ def sample(model, input_ids, attention_mask=None, max_length=None, seed=None, te
                                 else "not asked for")
     model.last_sample_advance = advance
     if advance.reason is None:
-        advance.reason = _sample_why_not(plan, top_k, top_p)
+        advance.reason = _sample_why_not(plan, top_k, top_p, nucleus, model.config.vocab_size)
     if advance.reason is None:
         return _checked(cache, _greedy_advanced(model, enc, attention_mask, start, plan, max_length, cache, stepper, advance,
                                                 whole if whole.reason is None else None, draw))

@@ -328,14 +328,19 @@ class SampleGraphInfo(GreedyGraphInfo):
 
 class SampleStepGraph(GreedyStepGraph):
     """Whole sampling steps of one sample() call as a captured graph: GreedyStepGraph over an ops.SampleBuffers, with
-    ops.sample_advance_at in the place of the arg-max.  ``draw``: dict(seed, temperature, top_k, top_p), kernel arguments and
-    constant for the call; the generator is keyed by (seed, row, position) and has no state, so one graph serves every step."""
+    ops.sample_advance_at in the place of the arg-max -- ops.sample_nucleus_at where ``draw`` has ``nucleus`` set (top_k == 0
+    with top_p < 1 under sample_nucleus).  ``draw``: dict(seed, temperature, top_k, top_p), kernel arguments and constant for
+    the call; the generator is keyed by (seed, row, position) and has no state, so one graph serves every step."""
 
     def __init__(self, decoder, info, buffers, plan, draw):
         super().__init__(decoder, info, buffers, plan)
         self.draw = draw
 
     def _advance(self, ops, logits, cur, settings):
+        if self.draw.get("nucleus"):
+            ops.sample_nucleus_at(logits, self.buffers, cur, self.draw["seed"], 0, self.draw["temperature"], self.draw["top_p"],
+                                  **settings)
+            return
         ops.sample_advance_at(logits, self.buffers, cur, self.draw["seed"], 0, self.draw["temperature"], self.draw["top_k"],
                               self.draw["top_p"], **settings)
 

@@ -969,7 +969,8 @@ class QuantizedBartForConditionalGeneration(QuantizedModule):
         set_sample_advance; ops.sample_advance); ``self.last_sample_advance`` then says how many steps took it (advanced,
         eager, reason).  ``sample_graph``: a whole step captured into one graph and replayed (None: the package switch,
         set_sample_graph; it implies ``graph`` and ``sample_advance`` for the call); ``self.last_sample_graph`` then says
-        what happened (captured, replays, reason)."""
+        what happened (captured, replays, reason).  ``sample_nucleus`` (None: the package switch, set_sample_nucleus): under
+        either, ``top_k=0`` with ``top_p<1`` is one kernel call too (ops.sample_nucleus) instead of the torch lines."""
         return generation.sample(self, input_ids, attention_mask=attention_mask, max_length=max_length, seed=seed,
                                  temperature=temperature, top_k=top_k, top_p=top_p, **kwargs)
 

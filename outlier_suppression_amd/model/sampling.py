@@ -6,7 +6,8 @@ word 0 of Philox4x32-10 with the key (seed & 0xffffffff, seed >> 32) and the cou
 graph of a step serves every step.  ``philox4x32`` and ``uniforms`` restate it in integer arithmetic on the host;
 ``select_torch`` / ``sample_step_torch`` are the rule of include/osq_hip.h (osq_sample_advance) as torch lines in fp32, fed
 those uniforms: the eager form, which serves on the CPU, under autograd and wherever the kernel does not take a call
-(``top_k == 0`` with ``top_p < 1``, ``top_k > 64``).
+(``top_k > 64``; ``top_k == 0`` with ``top_p < 1`` unless ``sample_nucleus`` hands it to csrc/sample_nucleus.hip, whose rule
+these lines state too -- and then a vocabulary above 51200).
 
 Where the rule departs from transformers' warpers: exactly ``top_k`` survivors under ties at the k-th value (transformers keeps
 every tie), equal values by smaller token; a NaN logit counts as banned.

@@ -2196,14 +2196,19 @@ def greedy_advance_at(logits, buffers, cur, cur_add=0, ngram=0, ban_ids=None, ba
 
 
 class SampleBuffers(GreedyBuffers):
-    """GreedyBuffers for osq_sample_advance: the same state, a workspace sized for (vocab, top_k)."""
+    """GreedyBuffers for osq_sample_advance: the same state, a workspace sized for (vocab, top_k) -- and, with ``nucleus``,
+    for osq_sample_nucleus (osq_sample_nucleus_workspace_bytes) as well, so that one set of buffers serves both calls."""
 
-    def __init__(self, bsz, max_length, device, vocab=None, top_k=0):
+    def __init__(self, bsz, max_length, device, vocab=None, top_k=0, nucleus=False):
         self.top_k = int(top_k)
+        self.nucleus = bool(nucleus)
         super().__init__(bsz, max_length, device, vocab)
 
     def room(self, vocab):
-        nbytes = max(int(_hip.load().osq_sample_advance_workspace_bytes(self.seq.shape[0], int(vocab), self.top_k)), 8)
+        lib = _hip.load()
+        nbytes = max(int(lib.osq_sample_advance_workspace_bytes(self.seq.shape[0], int(vocab), self.top_k)), 8)
+        if self.nucleus:
+            nbytes = max(nbytes, int(lib.osq_sample_nucleus_workspace_bytes(self.seq.shape[0], int(vocab))))
         if self.workspace is None or self.workspace.numel() < nbytes:
             self.workspace = torch.empty(nbytes, dtype=torch.uint8, device=self.seq.device)
         return self.workspace
@@ -2236,7 +2241,8 @@ def sample_advance(logits, buffers, cur, seed, temperature=1.0, top_k=0, top_p=1
     the row's uniform u selects -- Philox4x32-10 keyed by ``seed`` at counter (row, cur), or ``uniforms`` [bsz] fp32 in [0, 1)
     on the device -- then greedy_advance's pad / eos arithmetic, ``buffers.seq[:, cur]``, ``buffers.next_tokens`` and
     ``buffers.go_on``.  Three launches on the current stream, no synchronisation; returns ``buffers``, or None when the
-    library does not take the call (top_k == 0 with top_p < 1: the caller takes its other path)."""
+    library does not take the call (top_k == 0 with top_p < 1: the caller takes its other path -- ``sample_nucleus`` below,
+    where it asked for that kernel, else its torch lines)."""
     lib = _hip.load()
     head, (n_ban, n_eos), tail = _sample_advance_operands("sample_advance", logits, buffers, ban_ids, eos_ids, seed,
                                                           temperature, top_k, top_p, uniforms)
@@ -2269,6 +2275,58 @@ def sample_advance_at(logits, buffers, cur, seed, cur_add=0, temperature=1.0, to
     if rc == _hip.ERR_UNSUPPORTED:
         return None
     _hip.check(rc, "sample_advance_at")
+    return buffers
+
+
+def _sample_nucleus_operands(what, logits, buffers, ban_ids, eos_ids, seed, temperature, top_p, uniforms):
+    """_sample_advance_operands without top_k, over a workspace sized by osq_sample_nucleus_workspace_bytes."""
+    if not isinstance(buffers, SampleBuffers):
+        raise TypeError(f"{what}: buffers must be an ops.SampleBuffers")
+    buffers.nucleus = True
+    head, counts, tail = _sample_advance_operands(what, logits, buffers, ban_ids, eos_ids, seed, temperature, 0, top_p, uniforms)
+    return head, counts, tail[:-4] + tail[-3:]
+
+
+def sample_nucleus(logits, buffers, cur, seed, temperature=1.0, top_p=1.0, ngram=0, ban_ids=None, forced=None, eos_ids=None,
+                   pad=0, uniforms=None):
+    """One sampling step after the model from a nucleus over the whole vocabulary (osq_sample_nucleus,
+    csrc/sample_nucleus.hip): ``sample_advance`` for top_k == 0 and any ``top_p`` in (0, 1].  Every token left is ranked
+    (larger z first, equal z by smaller token), rank i stays iff the weights ranked above it sum below top_p of the total,
+    and the row's uniform selects among the kept ranks -- found by two bisections over a fixed-order fp32 sum held in
+    registers, without a sort (the rule: include/osq_hip.h).  Bans, ``forced``, pad / eos, ``buffers.seq[:, cur]``,
+    ``buffers.next_tokens``, ``buffers.go_on`` and the uniforms are sample_advance's.  Two launches on the current stream, no
+    synchronisation; returns ``buffers``, or None when the library does not take the call (a vocabulary above 51200)."""
+    lib = _hip.load()
+    head, (n_ban, n_eos), tail = _sample_nucleus_operands("sample_nucleus", logits, buffers, ban_ids, eos_ids, seed,
+                                                          temperature, top_p, uniforms)
+    rc = lib.osq_sample_nucleus(*head, int(cur), int(ngram), _hip.ptr(ban_ids) if n_ban else None, n_ban,
+                                -1 if forced is None else int(forced), _hip.ptr(eos_ids) if n_eos else None, n_eos, int(pad),
+                                buffers.unfinished.data_ptr(), *tail)
+    if rc == _hip.ERR_UNSUPPORTED:
+        return None
+    _hip.check(rc, "sample_nucleus")
+    return buffers
+
+
+def sample_nucleus_at(logits, buffers, cur, seed, cur_add=0, temperature=1.0, top_p=1.0, ngram=0, ban_ids=None, ban_below=0,
+                      forced_bos=None, forced_eos=None, eos_ids=None, pad=0, uniforms=None):
+    """sample_nucleus with the position read by the launches (osq_sample_nucleus_at): ``cur`` is one int32 on the device and
+    the step is taken at length ``*cur + cur_add``; everything else as sample_advance_at.  For a length in [1, max_length)
+    everything written is word-equal to ``sample_nucleus`` at that length; outside it ``buffers.go_on`` receives -1 and
+    nothing else is written."""
+    lib = _hip.load()
+    head, (n_ban, n_eos), tail = _sample_nucleus_operands("sample_nucleus_at", logits, buffers, ban_ids, eos_ids, seed,
+                                                          temperature, top_p, uniforms)
+    _hip.require_device(cur)
+    if cur.dtype != torch.int32 or cur.numel() != 1 or cur.device != logits.device:
+        raise TypeError("sample_nucleus_at: cur must be one int32 on the device of logits")
+    rc = lib.osq_sample_nucleus_at(*head, cur.data_ptr(), int(cur_add), int(ngram), _hip.ptr(ban_ids) if n_ban else None, n_ban,
+                                   int(ban_below), -1 if forced_bos is None else int(forced_bos),
+                                   -1 if forced_eos is None else int(forced_eos), _hip.ptr(eos_ids) if n_eos else None, n_eos,
+                                   int(pad), buffers.unfinished.data_ptr(), *tail)
+    if rc == _hip.ERR_UNSUPPORTED:
+        return None
+    _hip.check(rc, "sample_nucleus_at")
     return buffers
 
 

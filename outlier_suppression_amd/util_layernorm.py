@@ -89,6 +89,12 @@ uniforms; the sums are fp32 in another order, so a draw within rounding of a bou
 -- into one graph and replays it (model/graph_decode.py, SampleStepGraph); the generator is keyed by (seed, row, position), so
 one graph serves every step.  For its call it implies ``GRAPH_DECODE`` and ``SAMPLE_ADVANCE``.
 ``outlier_suppression_amd.set_sample_graph(True)`` / ``OSQ_SAMPLE_GRAPH=1`` / ``sample(..., sample_graph=True)`` turn it on.
+
+``SAMPLE_NUCLEUS`` (default OFF): under the two switches above, ``top_k=0, top_p<1`` -- a nucleus over the whole vocabulary,
+which ``ops.sample_advance`` refuses -- goes to ``ops.sample_nucleus`` (csrc/sample_nucleus.hip: the row in registers, two
+bisections over a fixed-order sum, no sort) instead of falling back to the torch lines.  The same rule and uniforms, fp32 sums
+in another order.  Off, every path and every fallback reason is unchanged.
+``outlier_suppression_amd.set_sample_nucleus(True)`` / ``OSQ_SAMPLE_NUCLEUS=1`` / ``sample(..., sample_nucleus=True)`` turn it on.
 """
 import torch
 import torch.nn.functional as F
@@ -112,6 +118,7 @@ GREEDY_ADVANCE = False   # generate(): a greedy step's processors, arg-max, pad 
 GREEDY_GRAPH = False     # generate(): capture a whole greedy step -- token copy, model, the kernel call above -- into one graph (implies GRAPH_DECODE and GREEDY_ADVANCE for the call; set_greedy_graph / OSQ_GREEDY_GRAPH=1 / generate(greedy_graph=True))
 SAMPLE_ADVANCE = False   # sample(): a sampling step's processors, temperature / top-k / top-p, seeded draw, pad / eos lines, sequence append and stopping word as one kernel call (set_sample_advance / OSQ_SAMPLE_ADVANCE=1 / sample(sample_advance=True))
 SAMPLE_GRAPH = False     # sample(): capture a whole sampling step -- token copy, model, the kernel call above -- into one graph (implies GRAPH_DECODE and SAMPLE_ADVANCE for the call; set_sample_graph / OSQ_SAMPLE_GRAPH=1 / sample(sample_graph=True))
+SAMPLE_NUCLEUS = False   # sample(): under the two switches above, top_k=0 with top_p<1 (a nucleus over the whole vocabulary) goes to ops.sample_nucleus instead of the torch lines (set_sample_nucleus / OSQ_SAMPLE_NUCLEUS=1 / sample(sample_nucleus=True))
 CACHE_CODES = False      # incremental decoding: new KV caches hold integer codes, one byte per element (same words read back; set_cache_codes / OSQ_CACHE_CODES=1)
 
 

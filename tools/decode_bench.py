@@ -54,6 +54,11 @@ top_p 0.95 and for the whole vocabulary, the tokens asserted equal between the f
 transformers' own lines (warpers, softmax, torch.multinomial) and against sampling.select_torch.
 
     python tools/decode_bench.py --sample-advance [--out profiles/sample_advance_ab.txt]
+
+--sample-nucleus: the same comparison for top_k=0, top_p=0.9 -- a nucleus over the whole vocabulary, which goes to
+ops.sample_nucleus (csrc/sample_nucleus.hip) under sample(sample_nucleus=True) and to the torch lines without it:
+
+    python tools/decode_bench.py --sample-nucleus [--out profiles/sample_nucleus_ab.txt]
 """
 import argparse
 import copy
@@ -706,6 +711,128 @@ def sample_advance_ab(q, ids, mask, args):
     return lines
 
 
+# (label, sample()'s switches) of the forms --sample-nucleus compares; the first is the baseline of its group (the switch
+# off: the torch lines, what sample() did with top_k=0, top_p<1 before ops.sample_nucleus)
+NUCLEUS_FORMS = [("graph", dict(graph=True)),
+                 ("graph + sample_advance + sample_nucleus", dict(graph=True, sample_advance=True, sample_nucleus=True)),
+                 ("sample_graph + sample_nucleus", dict(sample_graph=True, sample_nucleus=True)),
+                 ("issued", dict(graph=False)),
+                 ("issued + sample_advance + sample_nucleus", dict(graph=False, sample_advance=True, sample_nucleus=True))]
+
+
+def sample_nucleus_ab(q, ids, mask, args):
+    from transformers.generation.logits_process import TemperatureLogitsWarper, TopPLogitsWarper
+    from outlier_suppression_amd import ops, util_layernorm as UL
+    from outlier_suppression_amd.model import generation, sampling
+    dev = ids.device
+    bsz, vocab, at, max_length, seed = args.batch, q.config.vocab_size, 31, 62, 20261020
+    draw = dict(top_k=0, top_p=0.9, temperature=1.0)
+    lines = [f"a nucleus over the whole vocabulary (top_k=0, top_p={draw['top_p']}): everything after the model step as one kernel "
+             f"call (ops.sample_nucleus, sample(sample_nucleus=True)) and the whole step as one captured graph against the torch "
+             f"lines (model/sampling.py: a stable sort of the row), which the switch off runs; BART-large shape, batch {bsz}, "
+             f"source {args.src}, sample(max_length={max_length}, min_length={max_length}, seed={seed}) (BART's forced eos on the "
+             f"last step); the one-launch attention on in the issued forms as in the graphs; every form timed in turn in each of "
+             f"{args.reps} rounds, one process; median [min, max]"]
+    print(lines[0], flush=True)
+    old = UL.FUSE_DECODE_ATTENTION
+    UL.FUSE_DECODE_ATTENTION = True                 # the issued forms run the launches the graphs hold: the same words
+    try:
+        with torch.no_grad():
+            kw = dict(max_length=max_length, min_length=max_length, seed=seed, **draw)
+            times = {label: [] for label, _ in NUCLEUS_FORMS}
+            tokens, did = {}, {}
+            for r in range(args.reps + 1):          # the first round warms every form up
+                for label, switches in NUCLEUS_FORMS:
+                    secs, tokens[label] = _timed(lambda: q.sample(ids, attention_mask=mask, **kw, **switches), 1.0)
+                    did[label] = (q.last_sample_advance.advanced, q.last_sample_advance.eager, q.last_decode_graph.captured,
+                                  q.last_decode_graph.replays, q.last_sample_graph.captured)
+                    if r:
+                        times[label].append(secs)
+            first = tokens[NUCLEUS_FORMS[0][0]]
+            assert did["sample_graph + sample_nucleus"][4] == 1, did
+            assert did["graph + sample_advance + sample_nucleus"][:2] == (max_length - 1, 0), did
+            assert did["graph"][:2] == (0, max_length - 1), did
+            families = [[label for label in tokens if (did[label][0] > 0) == kernel] for kernel in (False, True)]
+            for family in families:                 # before a time is printed
+                for label in family:
+                    assert bool(torch.equal(tokens[label], tokens[family[0]])), f"{label}: tokens differ from {family[0]}"
+            parted = (tokens[families[0][0]] != tokens[families[1][0]]).any(dim=0).nonzero()
+            agree = (f"equal in all {len(tokens)} forms" if parted.numel() == 0 else
+                     f"equal among the {len(families[0])} torch forms and among the {len(families[1])} kernel forms; the two "
+                     f"part at position {int(parted[0])} (the fp32 sums run in another order: a draw within rounding of a "
+                     f"boundary)")
+            block = [f"tokens {tuple(first.shape)} {agree}; s, wall time of the call (a graph form: capture included); (steps "
+                     "through the kernel, through torch, graphs captured, replays, whole-step graphs):"]
+            block += [f"    {label:42s} {_stats(t)}   {did[label]}" for label, t in times.items()]
+            for group in (NUCLEUS_FORMS[:3], NUCLEUS_FORMS[3:5]):
+                base = sorted(times[group[0][0]])
+                spread = base[-1] - base[0]
+                for label, _ in group[1:]:
+                    mine = sorted(times[label])
+                    gain = base[len(base) // 2] - mine[len(mine) // 2]
+                    block.append(f"    {label} against {group[0][0]}: median gain {gain * 1e3:.1f} ms "
+                                 f"({gain / (max_length - 1) * 1e3:.3f} ms per token, {gain / base[len(base) // 2] * 100:.1f} %), "
+                                 f"the baseline's own spread {spread * 1e3:.1f} ms: "
+                                 f"{'above' if gain > spread else 'within'} it")
+            print("\n".join(block), flush=True)
+            lines += block
+
+            # the selection alone at length `at`: min_length active, one eos id, every row unfinished
+            g = torch.Generator(device="cpu").manual_seed(3)
+            logits = (torch.randn(bsz, vocab, generator=g) * 4).to(dev)
+            history = torch.randint(3, 40, (bsz, at), generator=g).to(dev)
+            eos = torch.tensor([2], device=dev)
+            procs = generation._processors(max_length, eos, 0, None, 2, max_length, dev)
+            plan = generation._GreedyPlan(procs, dev, vocab, max_length, eos, 1)
+            assert plan.reason is None, plan.reason
+            bufs = ops.SampleBuffers(bsz, max_length, dev, vocab, 0, nucleus=True)
+            bufs.seq[:, :at] = history
+            warpers = [TemperatureLogitsWarper(draw["temperature"]), TopPLogitsWarper(draw["top_p"])]
+
+            def finish(nxt):
+                unfinished = torch.ones(bsz, dtype=torch.long, device=dev)
+                nxt = nxt * unfinished + 1 * (1 - unfinished)
+                torch.cat([history, nxt[:, None]], dim=-1)
+                unfinished = unfinished & ~torch.isin(nxt, eos)
+                return nxt, bool(unfinished.max() == 0)
+
+            def transformers_lines():
+                scores = procs(history, logits)
+                for w in warpers:
+                    scores = w(history, scores)
+                return finish(torch.multinomial(torch.softmax(scores, dim=-1), num_samples=1).squeeze(1))
+
+            def torch_lines():
+                u = sampling.uniforms(seed, bsz, at)
+                return finish(sampling.select_torch(procs(history, logits), u, **draw))
+
+            def kernel():
+                bufs.unfinished.fill_(1)
+                ops.sample_nucleus(logits, bufs, at, seed, draw["temperature"], draw["top_p"], ngram=plan.ngram, ban_ids=plan.ban,
+                                   forced=plan.forced(at), eos_ids=plan.eos, pad=plan.pad)
+                return bufs.next_tokens, not int(bufs.go_on)
+            forms = {"transformers' lines": transformers_lines, "sampling.select_torch": torch_lines, "ops.sample_nucleus": kernel}
+            times = {label: [] for label in forms}
+            outs = {}
+            for r in range(args.reps + 3):          # three lead-in rounds
+                for label, fn in forms.items():
+                    ms, outs[label] = _timed(fn)
+                    if r >= 3:
+                        times[label].append(ms)
+            (a, a_stop), (b, b_stop) = outs["sampling.select_torch"], outs["ops.sample_nucleus"]
+            same = int((a == b).sum())
+            assert a_stop == b_stop and same >= bsz - 1, "the kernel's tokens differ from the torch lines'"
+            lines.append(f"the selection alone (with the read of the stopping word), logits [{bsz}, {vocab}] fp32 (randn * 4), history "
+                         f"of {at} tokens, min_length {max_length} active, one eos id, ms; {same} of {bsz} tokens equal between "
+                         "sampling.select_torch and ops.sample_nucleus; transformers' lines: its temperature / top-p warpers, "
+                         "softmax and torch.multinomial (another random stream: its tokens are not compared):")
+            lines += [f"    {label:24s} {_stats(t)}" for label, t in times.items()]
+            print("\n".join(lines[-4:]), flush=True)
+    finally:
+        UL.FUSE_DECODE_ATTENTION = old
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=32)
@@ -722,9 +849,16 @@ def main():
     ap.add_argument("--beam-graph", action="store_true")
     ap.add_argument("--greedy-advance", action="store_true")
     ap.add_argument("--sample-advance", action="store_true")
+    ap.add_argument("--sample-nucleus", action="store_true")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     q, ids, mask = build(args.batch, args.src, args.layers)
+    if args.sample_nucleus:
+        text = "\n".join(sample_nucleus_ab(q, ids, mask, args))
+        if args.out:
+            with open(args.out, "w") as f:
+                f.write(text + "\n")
+        return
     if args.sample_advance:
         text = "\n".join(sample_advance_ab(q, ids, mask, args))
         if args.out:
