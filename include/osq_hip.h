@@ -44,7 +44,8 @@ typedef void* osq_stream;
  *     osq_decode_attention_codes_at, osq_beam_select_workspace_bytes, osq_beam_select, osq_beam_advance,
  *     osq_beam_select_at, osq_beam_advance_at, osq_greedy_advance_workspace_bytes, osq_greedy_advance,
  *     osq_greedy_advance_at, osq_sample_advance_workspace_bytes, osq_sample_advance, osq_sample_advance_at,
- *     osq_sample_uniforms, osq_sample_nucleus_workspace_bytes, osq_sample_nucleus, osq_sample_nucleus_at. */
+ *     osq_sample_uniforms, osq_sample_nucleus_workspace_bytes, osq_sample_nucleus, osq_sample_nucleus_at,
+ *     osq_decode_attention_shared, osq_decode_attention_shared_codes. */
 #define OSQ_ABI_VERSION 10
 
 typedef enum osq_status {
@@ -892,6 +893,39 @@ int osq_decode_attention_codes_at(const float* q, const uint8_t* k, const uint8_
                                   float* ctx_scale, void* ctx_zero_point, int ctx_zp_type, int ctx_mode,
                                   float ctx_grad_factor, int ctx_quant_min, int ctx_quant_max,
                                   osq_stream stream);
+
+/* osq_decode_attention_fake_quant / osq_decode_attention_codes for query rows that share their keys and values
+ * (csrc/decode_attention_shared.hip): beam search's cross-attention, where the `group` beams of a batch row attend to the same
+ * encoder keys / values.  q: dense [batch * group, heads, 1, head_dim]; query row b * group + g attends to row b of k / v
+ * ([batch, heads, cap, head_dim]) and of mask (NULL, or [batch, 1, 1, kv_len]).  out: dense [batch * group, 1, heads *
+ * head_dim]; probs_out: NULL, or dense [batch * group, heads, 1, kv_len].  One workgroup serves up to 8 query rows of a
+ * (batch row, head) from one pass over K and one over V: K and V are read ceil(group / 8) times, not group times.  For every
+ * query row each score, the softmax denominator and every context element are formed and added as
+ * osq_decode_attention_fake_quant forms them: out and probs_out are word-equal to that function (to
+ * osq_decode_attention_codes) called with k, v and mask repeated `group` times along the batch.  Parameter groups,
+ * OSQ_PARAM_SANITIZE, records and the rejected counter as there.  No atomics; no host synchronisation, no allocation: legal
+ * inside a stream capture.
+ * OSQ_ERR_UNSUPPORTED, nothing launched: group above 64, kv_len outside [1, 1024] (the score rows of 8 queries in 32 KiB of
+ * LDS; BART's source positions), head_dim / 4 not a power of two <= 64, a pointer not 16-byte aligned (k / v of the coded
+ * form: 4-byte).  group < 1: OSQ_ERR_INVALID_ARGUMENT.  Inference only. */
+int osq_decode_attention_shared(const float* q, const float* k, const float* v, const float* mask, float* out,
+                                float* probs_out, int64_t batch, int64_t group, int64_t heads, int64_t head_dim,
+                                int64_t kv_len, int64_t k_cap, int64_t v_cap,
+                                float* probs_scale, void* probs_zero_point, int probs_zp_type, int probs_mode,
+                                float probs_grad_factor, int probs_quant_min, int probs_quant_max,
+                                float* ctx_scale, void* ctx_zero_point, int ctx_zp_type, int ctx_mode,
+                                float ctx_grad_factor, int ctx_quant_min, int ctx_quant_max,
+                                osq_stream stream);
+int osq_decode_attention_shared_codes(const float* q, const uint8_t* k, const uint8_t* v, const float* mask, float* out,
+                                      float* probs_out, int64_t batch, int64_t group, int64_t heads, int64_t head_dim,
+                                      int64_t kv_len, int64_t k_cap, int64_t v_cap,
+                                      const float* k_scale_eff, const float* k_zp_eff, int k_quant_min,
+                                      const float* v_scale_eff, const float* v_zp_eff, int v_quant_min, const int32_t* rejected,
+                                      float* probs_scale, void* probs_zero_point, int probs_zp_type, int probs_mode,
+                                      float probs_grad_factor, int probs_quant_min, int probs_quant_max,
+                                      float* ctx_scale, void* ctx_zero_point, int ctx_zp_type, int ctx_mode,
+                                      float ctx_grad_factor, int ctx_quant_min, int ctx_quant_max,
+                                      osq_stream stream);
 
 /* ------------------------------------------------------------------ beam search (beam_select.hip) */
 

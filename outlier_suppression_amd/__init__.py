@@ -173,6 +173,23 @@ def sample_nucleus_from_environment(environ=None):
     return (os.environ if environ is None else environ).get("OSQ_SAMPLE_NUCLEUS", "") not in ("", "0")
 
 
+def set_share_cross_kv(on=True):
+    """Beam search holds the cross-attention keys / values once per batch row -- they are identical for the beams of a row --
+    and a step's cross-attention serves all beams of a (row, head) from one pass over them (util_layernorm.SHARE_CROSS_KV;
+    ops.decode_attention_shared, csrc/decode_attention_shared.hip; default OFF): the cross part of the cache shrinks by the
+    factor num_beams, the words computed are those of the one-launch attention on the repeated tensors.
+    OSQ_SHARE_CROSS_KV=1 turns it on at load; ``generate(..., share_cross_kv=True)`` asks for one call;
+    ``model.last_share_cross_kv`` tells what happened."""
+    from . import util_layernorm
+    util_layernorm.SHARE_CROSS_KV = bool(on)
+
+
+def share_cross_kv_from_environment(environ=None):
+    """What OSQ_SHARE_CROSS_KV asks for: unset, empty or "0" -> False, anything else -> True."""
+    import os
+    return (os.environ if environ is None else environ).get("OSQ_SHARE_CROSS_KV", "") not in ("", "0")
+
+
 def sample_advance_from_environment(environ=None):
     """What OSQ_SAMPLE_ADVANCE asks for: unset, empty or "0" -> False, anything else -> True."""
     import os
@@ -238,7 +255,8 @@ def reset_tier(_lib=None):
     OSQ_GREEDY_ADVANCE=1 greedy decoding takes a step with one kernel call (unset: off); OSQ_GREEDY_GRAPH=1 greedy decoding
     replays a whole step as one captured graph (unset: off); OSQ_SAMPLE_ADVANCE=1 sample() takes a step with one kernel call
     (unset: off); OSQ_SAMPLE_GRAPH=1 sample() replays a whole step as one captured graph (unset: off); OSQ_SAMPLE_NUCLEUS=1
-    that kernel call takes a nucleus over the whole vocabulary too (unset: off)."""
+    that kernel call takes a nucleus over the whole vocabulary too (unset: off); OSQ_SHARE_CROSS_KV=1 beam search holds the
+    cross-attention keys / values once per batch row (unset: off)."""
     import os
     width = int(os.environ.get("OSQ_STRICT_SIMD", "8"))
     strict = os.environ.get("OSQ_STRICT", "")
@@ -260,6 +278,7 @@ def reset_tier(_lib=None):
     set_sample_advance(sample_advance_from_environment())
     set_sample_graph(sample_graph_from_environment())
     set_sample_nucleus(sample_nucleus_from_environment())
+    set_share_cross_kv(share_cross_kv_from_environment())
 
 
 _apply_environment = reset_tier

@@ -18,7 +18,11 @@ into the finished set, the early-stop heuristic -- to one kernel call (ops.beam_
 buffers; ``model.last_beam_advance`` tells how many steps took it.  ``beam_graph=True`` (set_beam_graph) asks for all three
 and captures the whole step -- token copy, model, selection, bookkeeping, the cache's row index -- into one graph per
 direction of the alternating buffers (graph_decode.BeamStepGraphs): a token costs the host one replay and one read of the
-stopping word; ``model.last_beam_graph`` tells what happened.
+stopping word; ``model.last_beam_graph`` tells what happened.  ``share_cross_kv=True`` (set_share_cross_kv) keeps the encoder
+states and their mask at one row per input instead of one per beam: the cache holds the cross-attention keys / values once
+per batch row (QuantizedBartCache, ``cross_group``) and a step's cross-attention serves all beams of a row from one pass over
+them (ops.decode_attention_shared), launch by launch or inside any of the graphs above; ``model.last_share_cross_kv`` tells
+what happened.
 
 Greedy decoding has the same two steps off the host.  ``greedy_advance=True`` (set_greedy_advance) hands everything after the
 model step -- the banned tokens of the logits processors, the arg-max, the pad / eos arithmetic, the new token into the
@@ -149,6 +153,51 @@ def _select_continuations(logits, flat, running_scores, procs, bsz, nb, vocab, k
     return torch.topk(log_probs, k=keep)
 
 
+class ShareCrossKvInfo:
+    """What a generate() call did with ``share_cross_kv``: ``shared`` beam steps over one copy of the cross-attention keys /
+    values per batch row, ``eager`` beam steps over one copy per beam, and, when none was shared, the ``reason``."""
+
+    def __init__(self, reason=None):
+        self.shared, self.eager, self.reason = 0, 0, reason
+
+    def __repr__(self):
+        return f"ShareCrossKvInfo(shared={self.shared}, eager={self.eager}, reason={self.reason!r})"
+
+
+SHARE_MAX_SOURCE = 1024            # kShMaxKv of csrc/decode_attention_shared.hip: the score rows of 8 queries in LDS
+SHARE_MAX_BEAMS = 64               # kShMaxGroup
+
+
+def _share_why_not(model, device, use_cache, nb, source_len):
+    """None when a generate() call can hold the cross-attention keys / values once per batch row, else the reason it
+    decodes as without ``share_cross_kv``.  Everything here is known before the first step."""
+    from . import graph_decode
+    if nb == 1:
+        return "one beam per batch row (num_beams == 1): there is nothing to share"
+    if nb > SHARE_MAX_BEAMS:
+        return f"num_beams above {SHARE_MAX_BEAMS}"
+    if not use_cache:
+        return "use_cache=False: there is no cache"
+    if device.type != "cuda":
+        return "the tensors are on the CPU"
+    if torch.is_grad_enabled():
+        return "autograd is on"
+    decoder = model.model.decoder
+    if decoder.training and any(p > 0 for layer in decoder.layers for p in (layer.dropout, layer.encoder_attn.dropout)):
+        return "dropout is active"
+    if source_len > SHARE_MAX_SOURCE:
+        return f"the source is longer than {SHARE_MAX_SOURCE}"
+    for i, layer in enumerate(decoder.layers):
+        attn = layer.encoder_attn
+        lpr = attn.head_dim // 4
+        if attn.head_dim % 4 or lpr > 64 or lpr & (lpr - 1) or attn.embed_dim != attn.num_heads * attn.head_dim:
+            return f"the shared cross-attention does not take head_dim {attn.head_dim}"
+        for site in ("query", "key", "value", "attention_probs", "context"):
+            if not graph_decode._plain(getattr(attn, site + "_post_act_fake_quantize")):
+                return f"a cross-attention quantizer is not in the plain quantising state (decoder layer {i}, {site})"
+    return None
+
+
 class BeamAdvanceInfo:
     """What a generate() call did with its beam steps' bookkeeping: ``advanced`` steps through ops.beam_advance, ``eager``
     steps through the torch lines, and, when none was advanced, the ``reason``."""
@@ -263,7 +312,8 @@ def _advance_beams_torch(state, top_lp, top_idx, cur, vocab, eos, top_mask, offs
 
 
 def generate(model, input_ids, attention_mask=None, max_length=None, num_beams=None, use_cache=True, cache_codes=None,
-             graph=None, beam_select=None, beam_advance=None, beam_graph=None, greedy_advance=None, greedy_graph=None, **kwargs):
+             graph=None, beam_select=None, beam_advance=None, beam_graph=None, greedy_advance=None, greedy_graph=None,
+             share_cross_kv=None, **kwargs):
     if kwargs.pop("synced_gpus", False):      # Seq2SeqTrainer's predict_with_generate passes synced_gpus=False
         raise NotImplementedError("generate(): synced_gpus=True is not supported")
     for name in _NOT_COVERED:
@@ -289,7 +339,15 @@ def generate(model, input_ids, attention_mask=None, max_length=None, num_beams=N
     from .. import util_layernorm
     from .quant_bart import QuantizedBartCache
     codes = util_layernorm.CACHE_CODES if cache_codes is None else bool(cache_codes)
-    cache = QuantizedBartCache(n_layers, capacity=max_length, codes=codes) if use_cache else None
+    # one copy of the cross-attention keys / values per batch row, where asked for and possible: decided once, here
+    share = ShareCrossKvInfo(None if (util_layernorm.SHARE_CROSS_KV if share_cross_kv is None else share_cross_kv) else "not asked for")
+    model.last_share_cross_kv = share
+    if share.reason is None:
+        share.reason = _share_why_not(model, enc.device, use_cache, num_beams, enc.shape[1])
+    cache = None
+    if use_cache:
+        cache = QuantizedBartCache(n_layers, capacity=max_length, codes=codes, cross_group=num_beams if share.reason is None else 1)
+        cache.cross_one_launch = share.reason is None
     from . import graph_decode
     # a whole beam step as one captured graph: it implies the three switches below for this call, where nothing -- known
     # before the first step -- stands against it; else the call decodes as without it
@@ -345,7 +403,7 @@ def generate(model, input_ids, attention_mask=None, max_length=None, num_beams=N
         raise ValueError("num_return_sequences must not exceed num_beams")
     return _checked(cache, _beam_search(model, enc, attention_mask, start, pad, eos_t, procs, max_length, num_beams, n_return,
                                         get("length_penalty"), get("early_stopping"), cache, stepper, select,
-                                        advance, whole if whole.reason is None else None))
+                                        advance, whole if whole.reason is None else None, share))
 
 
 def _beam_keep(eos, nb):
@@ -577,7 +635,8 @@ def _sample_eager(model, enc, attention_mask, start, pad, eos, procs, max_length
 
 
 def sample(model, input_ids, attention_mask=None, max_length=None, seed=None, temperature=1.0, top_k=50, top_p=1.0,
-           use_cache=True, cache_codes=None, graph=None, sample_advance=None, sample_graph=None, sample_nucleus=None, **kwargs):
+           use_cache=True, cache_codes=None, graph=None, sample_advance=None, sample_graph=None, sample_nucleus=None,
+           share_cross_kv=None, **kwargs):
     """Seeded sampling over a KV cache: generate()'s greedy loop with a draw in the place of the arg-max (model/sampling.py;
     the rule is osq_sample_advance's, include/osq_hip.h).  The tokens are a function of the inputs and ``seed`` alone -- the
     package's own random stream, not torch.multinomial's, so they are not transformers' tokens: hence an entry point of its
@@ -589,7 +648,8 @@ def sample(model, input_ids, attention_mask=None, max_length=None, seed=None, te
     many steps took it.  ``sample_graph=True`` (set_sample_graph) asks for ``graph`` and ``sample_advance`` and captures the
     whole step -- token copy, model, ops.sample_advance_at -- into one graph (graph_decode.SampleStepGraph);
     ``model.last_sample_graph`` tells what happened.  ``sample_nucleus=True`` (set_sample_nucleus): under either switch,
-    ``top_k=0`` with ``top_p<1`` goes to ops.sample_nucleus(_at) instead of falling back to the torch lines."""
+    ``top_k=0`` with ``top_p<1`` goes to ops.sample_nucleus(_at) instead of falling back to the torch lines.
+    ``share_cross_kv`` is beam search's: sampling has one row per input, ``model.last_share_cross_kv`` says so."""
     import math
     if kwargs.pop("synced_gpus", False):
         raise NotImplementedError("sample(): synced_gpus=True is not supported")
@@ -626,6 +686,9 @@ def sample(model, input_ids, attention_mask=None, max_length=None, seed=None, te
     from .quant_bart import QuantizedBartCache
     codes = util_layernorm.CACHE_CODES if cache_codes is None else bool(cache_codes)
     cache = QuantizedBartCache(len(model.model.decoder.layers), capacity=max_length, codes=codes) if use_cache else None
+    model.last_share_cross_kv = ShareCrossKvInfo(
+        _share_why_not(model, enc.device, use_cache, 1, enc.shape[1])
+        if (util_layernorm.SHARE_CROSS_KV if share_cross_kv is None else share_cross_kv) else "not asked for")
     plan = _GreedyPlan(procs, enc.device, model.config.vocab_size, max_length, eos_t, pad)
     nucleus = bool(util_layernorm.SAMPLE_NUCLEUS if sample_nucleus is None else sample_nucleus)
     draw["nucleus"] = nucleus and top_k == 0 and top_p < 1.0
@@ -669,12 +732,17 @@ def _gather(t, idx):
 
 
 def _beam_search(model, enc, attention_mask, start, pad, eos, procs, max_length, nb, n_return, length_penalty,
-                 early_stopping, cache, stepper=None, select=None, advance=None, whole=None):
-    """transformers' vectorised beam search (GenerationMixin._beam_search, 5.x) with the prompt of one start token."""
+                 early_stopping, cache, stepper=None, select=None, advance=None, whole=None, share=None):
+    """transformers' vectorised beam search (GenerationMixin._beam_search, 5.x) with the prompt of one start token.
+    ``share`` (a ShareCrossKvInfo without a reason): the encoder states and their mask stay at one row per input -- the cache
+    was built with ``cross_group=nb`` and the cross-attention reads one copy of its keys / values per batch row."""
     dev = enc.device
     bsz = enc.shape[0]
-    enc = enc.repeat_interleave(nb, dim=0)
-    attention_mask = attention_mask.repeat_interleave(nb, dim=0)
+    if share is not None and share.reason is not None:
+        share = None
+    if share is None:
+        enc = enc.repeat_interleave(nb, dim=0)
+        attention_mask = attention_mask.repeat_interleave(nb, dim=0)
     vocab = model.config.vocab_size
     prompt = cur = 1
     keep = _beam_keep(eos, nb)
@@ -692,7 +760,7 @@ def _beam_search(model, enc, attention_mask, start, pad, eos, procs, max_length,
         whole.reason, whole = select.reason or advance.reason, None
     if advance is not None and advance.reason is None:
         return _beam_search_advanced(model, enc, attention_mask, eos, procs, max_length, nb, n_return, length_penalty,
-                                     early_stopping, cache, stepper, select, advance, state, plan, vocab, keep, whole)
+                                     early_stopping, cache, stepper, select, advance, state, plan, vocab, keep, whole, share)
     def reorder(beam_idx):
         nonlocal cache
         if cache is not None:
@@ -706,13 +774,22 @@ def _beam_search(model, enc, attention_mask, start, pad, eos, procs, max_length,
         cur += 1
         if advance is not None:
             advance.eager += 1
+        _count_share(model, share)
         if not bool(go_on):
             break
     return _beam_result(state, select, n_return, prompt)
 
 
+def _count_share(model, share):
+    """One beam step went by: over shared cross-attention keys / values (``share``), or over one copy per beam."""
+    if share is not None:
+        share.shared += 1
+    elif getattr(model, "last_share_cross_kv", None) is not None:
+        model.last_share_cross_kv.eager += 1
+
+
 def _beam_search_advanced(model, enc, attention_mask, eos, procs, max_length, nb, n_return, length_penalty, early_stopping,
-                          cache, stepper, select, advance, state, plan, vocab, keep, whole=None):
+                          cache, stepper, select, advance, state, plan, vocab, keep, whole=None, share=None):
     """The loop of _beam_search with the bookkeeping of every step as one call of ops.beam_advance: the state lives in two
     sets of buffers, a step reads one and writes the other.  The token history goes to the selection as a row-strided view
     of ``running``, the model is fed the kernel's next_tokens, the cache follows its beam_idx, and the go_on word is read
@@ -740,6 +817,7 @@ def _beam_search_advanced(model, enc, attention_mask, eos, procs, max_length, nb
             cur += 1
             select.selected += 1
             advance.advanced += 1
+            _count_share(model, share)
             go_on = int(now.go_on)
             if go_on < 0:
                 raise RuntimeError(f"generate(): a captured beam step met the position {cur - 1}, outside [1, {max_length})")
@@ -762,6 +840,7 @@ def _beam_search_advanced(model, enc, attention_mask, eos, procs, max_length, nb
             cache = model._reorder_cache(cache, now.beam_idx)
         cur += 1
         advance.advanced += 1
+        _count_share(model, share)
         if not int(now.go_on):
             break
     if whole is not None and whole.captured == 0:

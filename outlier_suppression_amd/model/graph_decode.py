@@ -111,14 +111,15 @@ def _cache_fits(cache):
 class GraphDecoder:
     """The decoding steps after the first, for one encoder batch and one cache: ``step(tokens)`` returns the logits
     [B, vocab] of the next position, by a captured graph from the third step on.  ``enc`` / ``attention_mask`` are the
-    (beam-expanded) encoder states and mask the steps attend to; ``cache`` is the QuantizedBartCache the first step left."""
+    encoder states and mask the steps attend to: beam-expanded, or -- over a cache that holds the cross-attention keys / values
+    once per batch row (``cross_group``) -- one row per input; ``cache`` is the QuantizedBartCache the first step left."""
 
     def __init__(self, model, enc, attention_mask, cache, info=None):
         self.model, self.cache = model, cache
         self.info = DecodeGraphInfo() if info is None else info
         self.enc = enc
         self.mask, self._mask_given = attention_mask.clone(), attention_mask
-        self.tokens = torch.zeros((enc.shape[0], 1), dtype=torch.long, device=enc.device)
+        self.tokens = torch.zeros((enc.shape[0] * cache.cross_group, 1), dtype=torch.long, device=enc.device)
         self.stream = torch.cuda.Stream(device=enc.device)
         self.graphs = {}
         self.warm = False

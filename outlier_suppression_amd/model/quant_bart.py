@@ -29,7 +29,8 @@ from .. import ops
 from .. import util_layernorm as _UL
 from ..quantization import QuantizedModule, Quantizer
 from ..util_layernorm import (GammaResidual, QuantizedLayerNorm, activation_fake_quant, attention_probs_fake_quant,
-                              decode_attention_at_fake_quant, decode_attention_fake_quant, decode_grad_table,
+                              decode_attention_at_fake_quant, decode_attention_fake_quant, decode_attention_shared_fake_quant,
+                              decode_grad_table,
                               kv_append_codes_fake_quant, kv_append_fake_quant,
                               kv_site_params, merge_heads_fake_quant, qkv_heads_fake_quant, residual_layernorm,
                               split_heads_fake_quant)
@@ -156,6 +157,14 @@ class QuantizedBartCache:
     counted on the device: ``rejected()`` reads the counter, and attention over a cache with a non-zero counter yields
     NaN.
 
+    ``cross_group=G`` (beam search, generate(share_cross_kv=True)): the decoder runs G rows -- the beams -- per encoder row,
+    and the cross-attention keys / values, identical for them, are held ONCE per encoder row: [B, h, S, d] beside
+    self-attention buffers of B * G rows.  QuantizedBartAttention projects and quantizes them on B rows (with the grad factor
+    of the B * G-row tensor they stand for: the words and records of the unshared cache) and attends to them from every beam
+    in one launch (util_layernorm.decode_attention_shared_fake_quant).  Reading the cache -- ``cache[i]``, iteration,
+    ``to_legacy()`` -- repeats them to the decoder's row count, materialised on read, so the legacy tuple keeps its shapes;
+    ``nbytes()`` counts what is held.  Reorders leave them alone, as ever: a beam never changes its batch row.
+
     Device-position mode (``enter_device_position()``; model/graph_decode.py is its only user): the past length also lives
     in ONE device int32 shared by all layers, which single-token steps read in their launches (the _at forms of the append
     and of the attention) and the decoder advances after its last layer, so that a captured step can be replayed at every
@@ -163,9 +172,13 @@ class QuantizedBartCache:
     buffers of every layer's ping-pong pair exist at ``capacity``.  Reading the cache while a reorder is pending leaves the
     mode (the read re-packs the buffers)."""
 
-    def __init__(self, num_layers, capacity=None, codes=False):
+    def __init__(self, num_layers, capacity=None, codes=False, cross_group=1):
+        if int(cross_group) < 1:
+            raise ValueError("cross_group must be at least 1")
         self.capacity = capacity
         self.codes = bool(codes)
+        self.cross_group = int(cross_group)        # decoder rows per row of the cross-attention keys / values
+        self.cross_one_launch = False              # the shared cross-attention launch whatever FUSE_DECODE_ATTENTION says
         self._k = [None] * num_layers
         self._v = [None] * num_layers
         self._spare = [[None, None] for _ in range(num_layers)]     # partner buffers of k and v, or None
@@ -231,8 +244,12 @@ class QuantizedBartCache:
     def __getitem__(self, i):
         if self._k[i] is None:
             raise IndexError(f"layer {i} of the cache holds nothing yet")
-        return self.past(i) + (tuple(self._fp32(i, name, t) for name, t in zip(_CROSS, self._cross[i]))
-                               if self._cross[i] is not None else ())
+        if self._cross[i] is None:
+            return self.past(i)
+        cross = tuple(self._fp32(i, name, t) for name, t in zip(_CROSS, self._cross[i]))
+        if self.cross_group > 1:                   # one copy per encoder row is held: the tuple shows the decoder's rows
+            cross = tuple(t.repeat_interleave(self.cross_group, dim=0) for t in cross)
+        return self.past(i) + cross
 
     def __iter__(self):
         return (self[i] for i in range(len(self)))
@@ -373,6 +390,11 @@ class QuantizedBartCache:
     def cross_operands(self, i):
         return tuple(self._operand(i, name, t) for name, t in zip(_CROSS, self._cross[i]))
 
+    def keep_cross_rows(self, i):
+        """The cross-attention tensors of layer i were computed on the expanded encoder rows (a form the shared launches do
+        not take): keep every cross_group-th row, the one copy per encoder row."""
+        self._cross[i] = tuple(t[::self.cross_group].contiguous() for t in self._cross[i])
+
     def slot(self, i):
         return _CacheSlot(self, i)
 
@@ -509,7 +531,7 @@ class QuantizedBartAttention(QuantizedModule):
         if qoutput:
             self.out_proj_post_act_fake_quantize = Quantizer(None, a_qconfig)
 
-    def _cached_qkv(self, slot, hidden_states, key_value_states, observation_mask):
+    def _cached_qkv(self, slot, hidden_states, key_value_states, observation_mask, expanded=False):
         """q / k / v of a decoding step (quant_bart.py:156-198): self-attention fake-quantizes the step's keys / values and
         appends them to the cache, cross-attention quantizes the encoder's once and reuses them.  k / v come back as
         [B, h, S, d] views of the cache buffers -- as _CodedTensor where the cache holds them as integer codes."""
@@ -520,6 +542,8 @@ class QuantizedBartAttention(QuantizedModule):
         if key_value_states is not None:
             if cache._cross[i] is not None:
                 return (split_heads_fake_quant(qs[0], xq, heads, observation_mask),) + cache.cross_operands(i)
+            if cache.cross_group > 1 and not expanded:
+                return self._shared_cross_qkv(slot, xq, hidden_states, key_value_states, observation_mask)
             xk, xv = self.k_proj(key_value_states), self.v_proj(key_value_states)
             s = xk.shape[1]
             ps = [kv_site_params(q, x) for q, x in zip(qs, (xq, xk, xv))] if cache.codes else None
@@ -573,6 +597,50 @@ class QuantizedBartAttention(QuantizedModule):
         cache.commit(i, k, v, n + t)
         return q, k, v
 
+    def _shared_cross_qkv(self, slot, xq, hidden_states, key_value_states, observation_mask):
+        """The first cross-attention step over a cache with cross_group = G > 1: ``key_value_states`` has B rows, the step B * G.
+        Keys / values are projected and quantized on the B rows, in a launch of their own beside the query's.  Their LSQ /
+        LSQ+ grad factor is that of the [B * G, S, h*d] tensor they stand for -- it enters the last bits of the effective
+        scale -- so the words, and under codes the bytes and records, are those the unshared form stores.  Where a launch
+        does not take the step, the unshared computation runs on the expanded rows and one copy per encoder row is kept."""
+        cache, i, heads, d = slot.cache, slot.layer, self.num_heads, self.head_dim
+        group = cache.cross_group
+        bsz, t, _ = xq.shape
+        b = key_value_states.shape[0]
+        if b * group != bsz:
+            raise ValueError(f"a cache with cross_group={group} takes encoder states of {bsz // group} rows for {bsz} decoder "
+                             f"rows, got {b}")
+        qs = (self.query_post_act_fake_quantize, self.key_post_act_fake_quantize, self.value_post_act_fake_quantize)
+        xk, xv = self.k_proj(key_value_states), self.v_proj(key_value_states)
+        s = xk.shape[1]
+        numel = xk.numel() * group
+        kv = None
+        ps = [kv_site_params(qs[1], xk, numel), kv_site_params(qs[2], xv, numel)]
+        coded = cache.plan(i, _CROSS, ps, (xk, xv), heads) if cache.codes else ()
+        if any(coded) and None not in ps:
+            ys = [x.new_empty((b, heads, s, d), dtype=torch.uint8 if c else x.dtype) for x, c in zip((xk, xv), coded)]
+            kv = kv_append_codes_fake_quant([(qs[1], ps[0], xk, ys[0], 0, None, None) + cache.record(i, "cross_k"),
+                                             (qs[2], ps[1], xv, ys[1], 0, None, None) + cache.record(i, "cross_v")],
+                                            heads, cache._rejected)
+            if kv is not None:
+                cache.appended(i, _CROSS)
+        if kv is None:
+            if any(coded):
+                cache.demote(i, "cross_k")
+                cache.demote(i, "cross_v")
+            kv = kv_append_fake_quant([(qs[1], xk, xk.new_empty((b, heads, s, d)), 0, None, None),
+                                       (qs[2], xv, xv.new_empty((b, heads, s, d)), 0, None, None)], heads, numels=(numel, numel))
+        if kv is None:
+            out = self._cached_qkv(slot, hidden_states, key_value_states.repeat_interleave(group, dim=0), observation_mask,
+                                   expanded=True)
+            cache.keep_cross_rows(i)
+            return (out[0],) + cache.cross_operands(i)
+        cache._cross[i] = (kv[0], kv[1])
+        q = kv_append_fake_quant([(qs[0], xq, xq.new_empty((bsz, heads, t, d)), 0, None, None)], heads)
+        if q is None:
+            q = [split_heads_fake_quant(qs[0], xq, heads, observation_mask)]
+        return (q[0],) + cache.cross_operands(i)
+
     def forward(self, hidden_states, key_value_states=None, attention_mask=None, observation_mask=None,
                 past_key_value=None):
         """``past_key_value``: None (no cache; returns the output alone, as before) or a layer slot of a
@@ -583,7 +651,12 @@ class QuantizedBartAttention(QuantizedModule):
             if key_value_states is None and past_key_value.cache.positioned():
                 return self._step_at(past_key_value, hidden_states, attention_mask, observation_mask), past_key_value
             q, k, v = self._cached_qkv(past_key_value, hidden_states, key_value_states, observation_mask)
-            out = self._attend(q, k, v, bsz, tgt_len, attention_mask, observation_mask, cached=True)
+            cache = past_key_value.cache
+            if key_value_states is not None and cache.cross_group > 1:
+                out = self._attend_shared(q, k, v, bsz, tgt_len, attention_mask, observation_mask, cache.cross_group,
+                                          cache.cross_one_launch)
+            else:
+                out = self._attend(q, k, v, bsz, tgt_len, attention_mask, observation_mask, cached=True)
             return out, past_key_value
         source = hidden_states if key_value_states is None else key_value_states
         xq, xk, xv = self.q_proj(hidden_states) * self.scaling, self.k_proj(source), self.v_proj(source)
@@ -639,6 +712,25 @@ class QuantizedBartAttention(QuantizedModule):
         if ctx is None:
             raise RuntimeError("device-position step: the one-launch attention refused the step")
         return self._project(ctx, observation_mask)
+
+    def _attend_shared(self, q, k, v, bsz, tgt_len, attention_mask, observation_mask, group, force):
+        """_attend for [B * G, h, T, d] q over [B, h, S, d] k / v and a [B, 1, T, S] mask that the G rows of an encoder row
+        share: a single-token step as ONE launch that reads K and V once for (up to 8 of) the rows that share them.  A call
+        that launch does not take -- several tokens, a refusal -- expands k, v and the mask and takes _attend."""
+        if tgt_len == 1:
+            both = isinstance(k, _CodedTensor) and isinstance(v, _CodedTensor)
+            kk, vv = ((k.codes, v.codes) if both else (x.float() if isinstance(x, _CodedTensor) else x for x in (k, v)))
+            out = decode_attention_shared_fake_quant(self.attention_probs_post_act_fake_quantize,
+                                                     self.context_post_act_fake_quantize, q, kk, vv, group, attention_mask,
+                                                     dropout=(self.dropout, self.training),
+                                                     codes=(k.record, v.record, k.rejected) if both else None, force=force)
+            if out is not None:
+                return self._project(out, observation_mask)
+        k, v = (x.float() if isinstance(x, _CodedTensor) else x for x in (k, v))
+        k, v = k.repeat_interleave(group, dim=0), v.repeat_interleave(group, dim=0)
+        if attention_mask is not None:
+            attention_mask = attention_mask.repeat_interleave(group, dim=0)
+        return self._attend(q, k, v, bsz, tgt_len, attention_mask, observation_mask, cached=True)
 
     def _attend(self, q, k, v, bsz, tgt_len, attention_mask, observation_mask, cached=False):
         """[B, h, T, d] q and [B, h, S, d] k / v (dense, or views of a cache buffer) -> the block's output.  ``cached``: a
@@ -899,6 +991,9 @@ class QuantizedBartForConditionalGeneration(QuantizedModule):
         if self.is_remove_padding:                      # quant_bart.py:1064-1072
             obs = attention_mask.sum(1)
             dec_obs = obs if decoder_attention_mask is None else decoder_attention_mask.sum(1)
+            rows = None if decoder_input_ids is None else decoder_input_ids.shape[0]
+            if decoder_attention_mask is None and rows and rows != obs.shape[0] and rows % obs.shape[0] == 0:
+                dec_obs = obs.repeat_interleave(rows // obs.shape[0])   # several decoder rows per encoder row (cross_group)
         if labels is not None:
             use_cache = False
             if decoder_input_ids is None:
@@ -954,7 +1049,9 @@ class QuantizedBartForConditionalGeneration(QuantizedModule):
         says how many steps took it (advanced, eager, reason).  ``greedy_graph``: greedy decoding captures a whole step into
         one graph and replays it (None: the package switch, set_greedy_graph; it implies ``graph`` and ``greedy_advance`` for
         the call; model/graph_decode.py, GreedyStepGraph); ``self.last_greedy_graph`` then says what happened (captured,
-        replays, reason)."""
+        replays, reason).  ``share_cross_kv``: beam search holds the cross-attention keys / values once per batch row and
+        attends to them from every beam of the row in one launch (None: the package switch, set_share_cross_kv;
+        ops.decode_attention_shared); ``self.last_share_cross_kv`` then says what happened (shared, eager, reason)."""
         return generation.generate(self, input_ids, attention_mask=attention_mask, max_length=max_length,
                                    num_beams=num_beams, **kwargs)
 

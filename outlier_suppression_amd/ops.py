@@ -1831,6 +1831,57 @@ def decode_attention_at(q, k, v, kv_len, kv_len_add, kv_max, mask, probs_quant, 
     return out
 
 
+def decode_attention_shared(q, k, v, mask, probs_quant, ctx_quant, group, codes=None, want_probs=False):
+    """decode_attention_fake_quant / decode_attention_codes for query rows that share their keys and values
+    (osq_decode_attention_shared / osq_decode_attention_shared_codes, csrc/decode_attention_shared.hip): beam search's
+    cross-attention, one copy of K / V per batch row.
+
+    q: dense [B * group, h, 1, d] fp32; query row ``b * group + g`` attends to row b of k / v ([B, h, S, d], fp32, or uint8
+    with ``codes = (k_record, v_record, rejected)``; dense or ``[:, :, :S]`` views of [B, h, cap, d] buffers) and of mask
+    (None or a dense additive [B, 1, 1, S]).  One workgroup serves up to 8 query rows from one pass over K and V.  The
+    outputs are word-equal to decode_attention_fake_quant (decode_attention_codes) on k / v / mask repeated ``group`` times
+    along the batch.  Returns the [B * group, 1, h * d] output -- with ``want_probs`` the pair (output, probabilities
+    [B * group, h, 1, S]) -- or None where the launch refuses (group above 64, S above 1024, a head_dim or layout the
+    library does not take; nothing was launched)."""
+    lib = _hip.load()
+    _hip.require_device(q, k, v, mask)
+    _check_f32(q)
+    group = int(group)
+    if group < 1:
+        raise ValueError("decode_attention_shared: group must be at least 1")
+    if q.dim() != 4 or q.shape[2] != 1 or not q.is_contiguous() or k.dim() != 4 or q.shape[0] % group:
+        return None
+    rows, h, _, d = q.shape
+    b = rows // group
+    s = k.shape[2]
+    dtype = torch.float32 if codes is None else torch.uint8
+    k_cap, v_cap = _kv_cap(k, b, h, s, d, dtype), _kv_cap(v, b, h, s, d, dtype)
+    if k_cap is None or v_cap is None:
+        return None
+    if mask is not None and not (mask.dtype == torch.float32 and tuple(mask.shape) == (b, 1, 1, s) and mask.is_contiguous()):
+        return None
+    out = torch.empty((rows, 1, h * d), dtype=torch.float32, device=q.device)
+    probs = torch.empty((rows, h, 1, s), dtype=torch.float32, device=q.device) if want_probs else None
+    head = (q.data_ptr(), k.data_ptr(), v.data_ptr(), _hip.ptr(mask), out.data_ptr(), _hip.ptr(probs), b, group, h, d, s,
+            k_cap, v_cap)
+    tail = (*_quant_group(probs_quant), *_quant_group(ctx_quant), _hip.raw_stream(q.device))
+    if codes is None:
+        rc = lib.osq_decode_attention_shared(*head, *tail)
+    else:
+        k_record, v_record, rejected = codes
+        _hip.require_device(rejected, k_record[0], k_record[1], v_record[0], v_record[1])
+        _check_f32(k_record[0], k_record[1], v_record[0], v_record[1])
+        if rejected.dtype != torch.int32 or rejected.numel() != 1:
+            raise TypeError("decode_attention_shared: rejected must be one int32")
+        rc = lib.osq_decode_attention_shared_codes(*head, k_record[0].data_ptr(), k_record[1].data_ptr(), int(k_record[2]),
+                                                   v_record[0].data_ptr(), v_record[1].data_ptr(), int(v_record[2]),
+                                                   rejected.data_ptr(), *tail)
+    if rc == _hip.ERR_UNSUPPORTED:
+        return None
+    _hip.check(rc, "decode_attention_shared")
+    return (out, probs) if want_probs else out
+
+
 def dequantize_kv_codes(codes, record, out=None):
     """The fp32 buffer of a coded cache buffer: ``codes`` a contiguous uint8 [B, h, cap, d] tensor, ``record`` its
     (scale_eff, zp_eff, quant_min); the result has the same geometry and, position by position, the words the fp32 cache

@@ -95,6 +95,13 @@ which ``ops.sample_advance`` refuses -- goes to ``ops.sample_nucleus`` (csrc/sam
 bisections over a fixed-order sum, no sort) instead of falling back to the torch lines.  The same rule and uniforms, fp32 sums
 in another order.  Off, every path and every fallback reason is unchanged.
 ``outlier_suppression_amd.set_sample_nucleus(True)`` / ``OSQ_SAMPLE_NUCLEUS=1`` / ``sample(..., sample_nucleus=True)`` turn it on.
+
+Beam search has ``SHARE_CROSS_KV`` (default OFF): the cross-attention keys / values, identical for the beams of a batch row,
+are projected, quantized and held once per batch row (``QuantizedBartCache(cross_group=num_beams)``), and a step's
+cross-attention is ONE launch in which a workgroup serves the beams of a (row, head) from a single pass over K and V
+(``ops.decode_attention_shared``, csrc/decode_attention_shared.hip): the words of the one-launch attention on the repeated
+tensors.  ``outlier_suppression_amd.set_share_cross_kv(True)`` / ``OSQ_SHARE_CROSS_KV=1`` / ``generate(..., share_cross_kv=True)``
+turn it on.
 """
 import torch
 import torch.nn.functional as F
@@ -119,6 +126,7 @@ GREEDY_GRAPH = False     # generate(): capture a whole greedy step -- token copy
 SAMPLE_ADVANCE = False   # sample(): a sampling step's processors, temperature / top-k / top-p, seeded draw, pad / eos lines, sequence append and stopping word as one kernel call (set_sample_advance / OSQ_SAMPLE_ADVANCE=1 / sample(sample_advance=True))
 SAMPLE_GRAPH = False     # sample(): capture a whole sampling step -- token copy, model, the kernel call above -- into one graph (implies GRAPH_DECODE and SAMPLE_ADVANCE for the call; set_sample_graph / OSQ_SAMPLE_GRAPH=1 / sample(sample_graph=True))
 SAMPLE_NUCLEUS = False   # sample(): under the two switches above, top_k=0 with top_p<1 (a nucleus over the whole vocabulary) goes to ops.sample_nucleus instead of the torch lines (set_sample_nucleus / OSQ_SAMPLE_NUCLEUS=1 / sample(sample_nucleus=True))
+SHARE_CROSS_KV = False   # generate(): beam search holds the cross-attention keys / values once per batch row and attends to them from every beam of the row in one launch (set_share_cross_kv / OSQ_SHARE_CROSS_KV=1 / generate(share_cross_kv=True))
 CACHE_CODES = False      # incremental decoding: new KV caches hold integer codes, one byte per element (same words read back; set_cache_codes / OSQ_CACHE_CODES=1)
 
 
@@ -324,7 +332,7 @@ def qkv_heads_fake_quant(quantizers, projections, heads):
     return ops.fake_quant_headsplit_multi(list(projections), params, heads)
 
 
-def kv_append_fake_quant(sites, heads, pos=None):
+def kv_append_fake_quant(sites, heads, pos=None, numels=None):
     """Incremental decoding (model/quant_bart.py, QuantizedBartCache): the activation quantizers of one attention block's
     step, each site ``(quantizer, x, y, offset, src, src_rows)``, as ONE launch (ops.fake_quant_kv_append): site i writes
     the head-split fake-quant of its [B, t, h*d] projection x at positions [offset, offset + t) of the [B, h, cap, d]
@@ -332,33 +340,38 @@ def kv_append_fake_quant(sites, heads, pos=None):
     The cache contents are word for word what ``torch.cat([past.index_select(0, idx), split_heads(quantizer(x))], 2)``
     gives.  Only when every quantizer is in its plain quantising state (as qkv_heads_fake_quant); returns the list of y,
     or None (nothing launched): the caller then runs the eager form.  ``pos``: None, or the device int32 a site whose
-    offset is None appends at (ops.fake_quant_kv_append_at: the position is read by the launch)."""
+    offset is None appends at (ops.fake_quant_kv_append_at: the position is read by the launch).  ``numels``: None, or per
+    site the element count a learnable quantizer's grad factor goes by (None: that of x) -- keys / values held once for
+    several rows take the factor of the tensor they stand for."""
     if not FUSE_KV_APPEND:
         return None
     for q, x, *_ in sites:
         if not (_plain_quantizing(q, x) and x.dim() == 3 and x.is_contiguous() and x.data_ptr() % 16 == 0):
             return None
     table = []
-    for q, x, y, offset, src, rows in sites:
+    for j, (q, x, y, offset, src, rows) in enumerate(sites):
         mode = q.param_mode
         if isinstance(q, _LearnableFakeQuantize):
             mode |= ops.PARAM_SANITIZE
             q._touch_qparams()
+        sized = x if numels is None or numels[j] is None else _Numel(numels[j])
         table.append((x, y, offset, (q.scale.data, q.zero_point.data, q.quant_min, q.quant_max, mode,
-                                     q._grad_factor(x) if q.param_mode != ops.PARAM_FIXED else 1.0), src, rows))
+                                     q._grad_factor(sized) if q.param_mode != ops.PARAM_FIXED else 1.0), src, rows))
     return ops.fake_quant_kv_append(table, heads) if pos is None else ops.fake_quant_kv_append_at(table, heads, pos)
 
 
-def kv_site_params(q, x):
+def kv_site_params(q, x, numel=None):
     """(scale, zero_point, quant_min, quant_max, mode, grad_factor) of quantizer q for the [B, t, h*d] projection x as a site
     of a KV-append launch, or None when kv_append_fake_quant would not take the site (the quantizer not in its plain
-    quantising state, x not dense and 16-byte aligned, the one-launch append switched off)."""
+    quantising state, x not dense and 16-byte aligned, the one-launch append switched off).  ``numel``: the element count
+    the grad factor goes by, where it is not x's (kv_append_fake_quant, ``numels``)."""
     if not (FUSE_KV_APPEND and _plain_quantizing(q, x) and x.dim() == 3 and x.is_contiguous() and x.data_ptr() % 16 == 0):
         return None
     mode = q.param_mode
     if isinstance(q, _LearnableFakeQuantize):
         mode |= ops.PARAM_SANITIZE
-    return (q.scale, q.zero_point, q.quant_min, q.quant_max, mode, q._grad_factor(x) if q.param_mode != ops.PARAM_FIXED else 1.0)
+    sized = x if numel is None else _Numel(numel)
+    return (q.scale, q.zero_point, q.quant_min, q.quant_max, mode, q._grad_factor(sized) if q.param_mode != ops.PARAM_FIXED else 1.0)
 
 
 def kv_append_codes_fake_quant(sites, heads, rejected, pos=None):
@@ -417,6 +430,35 @@ def decode_attention_fake_quant(probs_quantizer, ctx_quantizer, q, k, v, mask=No
     if codes is not None:
         return ops.decode_attention_codes(q, k, v, mask, params[0], params[1], *codes)
     return ops.decode_attention_fake_quant(q, k, v, mask, params[0], params[1])
+
+
+def decode_attention_shared_fake_quant(probs_quantizer, ctx_quantizer, q, k, v, group, mask=None, dropout=None, codes=None,
+                                       force=False):
+    """decode_attention_fake_quant for q = [B * group, h, 1, d] whose rows b * group .. b * group + group - 1 share row b of
+    k / v = [B, h, S, d] and of mask [B, 1, 1, S] (beam search's cross-attention over a QuantizedBartCache with
+    ``cross_group``): ONE launch, every word of K and V read once per 8 query rows (ops.decode_attention_shared).  Gated as
+    decode_attention_fake_quant is -- ``force``: the caller asked for the shared form whatever FUSE_DECODE_ATTENTION says
+    (generate(share_cross_kv=True)).  The grad factors go by the query rows, as in the unshared form: the words are those of
+    decode_attention_fake_quant on k / v / mask repeated ``group`` times.  Returns the [B * group, 1, h*d] context, or None
+    (nothing launched): the caller expands k / v / mask and takes the unshared path."""
+    if not (FUSE_DECODE_ATTENTION or force) or torch.is_grad_enabled() or _dropout_active(dropout):
+        return None
+    if q.dim() != 4 or q.shape[2] != 1 or k.dim() != 4:
+        return None
+    params = []
+    for quantizer, numel in ((probs_quantizer, q.shape[0] * q.shape[1] * k.shape[2]), (ctx_quantizer, q.numel())):
+        if quantizer is None:
+            params.append(None)
+            continue
+        if not _plain_quantizing(quantizer, q):
+            return None
+        mode = quantizer.param_mode
+        if isinstance(quantizer, _LearnableFakeQuantize):
+            mode |= ops.PARAM_SANITIZE
+            quantizer._touch_qparams()
+        params.append((quantizer.scale.data, quantizer.zero_point.data, quantizer.quant_min, quantizer.quant_max, mode,
+                       quantizer._grad_factor(_Numel(numel)) if quantizer.param_mode != ops.PARAM_FIXED else 1.0))
+    return ops.decode_attention_shared(q, k, v, mask, params[0], params[1], group, codes=codes)
 
 
 def decode_grad_table(quantizer, rows, kv_max):

@@ -59,6 +59,15 @@ transformers' own lines (warpers, softmax, torch.multinomial) and against sampli
 ops.sample_nucleus (csrc/sample_nucleus.hip) under sample(sample_nucleus=True) and to the torch lines without it:
 
     python tools/decode_bench.py --sample-nucleus [--out profiles/sample_nucleus_ab.txt]
+
+--share-cross-kv: the A/B is beam search over ONE copy of the cross-attention keys / values per batch row
+(generate(share_cross_kv=True); QuantizedBartCache(cross_group=beams); ops.decode_attention_shared,
+csrc/decode_attention_shared.hip) against one copy per beam, for the fp32 and the coded cache: the cross-attention launch alone
+(device events around 50 launches); one decoder step as a replayed graph at S = 1 / 31 / 62; generate(graph=True,
+beam_select=True, beam_advance=True); ``cache.nbytes()`` of both forms; and the largest logit difference over 12
+teacher-forced steps.  Every form is timed in turn within each of the --reps rounds, in one process.
+
+    python tools/decode_bench.py --share-cross-kv [--out profiles/share_cross_kv_ab.txt]
 """
 import argparse
 import copy
@@ -833,6 +842,186 @@ def sample_nucleus_ab(q, ids, mask, args):
     return lines
 
 
+# (label, cache codes, share_cross_kv) of the forms --share-cross-kv compares: the baseline of each pair first
+SHARE_FORMS = [("fp32 cache, one copy per beam", False, False), ("fp32 cache, shared", False, True),
+               ("coded cache, one copy per beam", True, False), ("coded cache, shared", True, True)]
+
+
+def share_launch_ab(q, ids, beams, reps, launches=50):
+    """The cross-attention launch of one layer alone at the model's shape: ops.decode_attention_fake_quant / _codes on K / V
+    of batch * beams rows against ops.decode_attention_shared on batch rows.  {label: [us per launch]}."""
+    from outlier_suppression_amd import ops
+    dev = ids.device
+    attn = q.model.decoder.layers[0].encoder_attn
+    b, s, h, d = ids.shape[0], ids.shape[1], attn.num_heads, attn.head_dim
+    query = torch.randn(b * beams, h, 1, d, device=dev) * d ** -0.5
+    mask = torch.zeros(b, 1, 1, s, device=dev)
+    quant = lambda scale, zp: (torch.tensor([scale], device=dev), torch.tensor([zp], dtype=torch.int32, device=dev), 0, 63, ops.PARAM_FIXED, 1.0)  # noqa: E731
+    pq, cq = quant(1.0 / 63, 0), quant(0.05, 31)
+    rejected = torch.zeros(1, dtype=torch.int32, device=dev)
+    rec = (torch.tensor([0.06], device=dev), torch.tensor([31.0], device=dev), 0)
+    runs = {}
+    for label, codes, share in SHARE_FORMS:
+        rows = b if share else b * beams
+        if codes:
+            k, v = (torch.randint(0, 64, (rows, h, s, d), device=dev).to(torch.uint8) for _ in range(2))
+        else:
+            k, v = (torch.randn(rows, h, s, d, device=dev) for _ in range(2))
+        m = mask if share else mask.repeat_interleave(beams, 0)
+        if share:
+            fn = lambda k=k, v=v, m=m, codes=codes: ops.decode_attention_shared(  # noqa: E731
+                query, k, v, m, pq, cq, beams, codes=(rec, rec, rejected) if codes else None)
+        elif codes:
+            fn = lambda k=k, v=v, m=m: ops.decode_attention_codes(query, k, v, m, pq, cq, rec, rec, rejected)  # noqa: E731
+        else:
+            fn = lambda k=k, v=v, m=m: ops.decode_attention_fake_quant(query, k, v, m, pq, cq)  # noqa: E731
+        assert fn() is not None, label
+        runs[label] = (fn, [])
+    start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    for r in range(reps + 1):
+        for label, (fn, times) in runs.items():
+            torch.cuda.synchronize()
+            start.record()
+            for _ in range(launches):
+                fn()
+            stop.record()
+            torch.cuda.synchronize()
+            if r:                                   # the first round warms every form up
+                times.append(start.elapsed_time(stop) * 1e3 / launches)
+    return {label: times for label, (fn, times) in runs.items()}
+
+
+def share_step_ab(q, ids, mask, beams, past, reps):
+    """One decoder step at past length ``past`` as a replayed graph with a beam reorder pending, every form of SHARE_FORMS
+    timed in turn in each round.  Returns {label: [ms]} and {label: cache.nbytes()}."""
+    from outlier_suppression_amd.model.graph_decode import GraphDecoder
+    from outlier_suppression_amd.model.quant_bart import QuantizedBartCache
+    dev = ids.device
+    bb = ids.shape[0] * beams
+    layers = len(q.model.decoder.layers)
+    runs, held = {}, {}
+    with torch.no_grad():
+        enc1 = q.get_encoder()(ids, attention_mask=mask)
+        tok = torch.randint(3, 50265, (bb, past + 1), device=dev)
+        perm = (torch.arange(bb, device=dev).view(-1, beams)[:, torch.randperm(beams, device=dev)]).reshape(-1)   # beams stay in their row
+        last = tok[:, past:past + 1]
+        for label, codes, share in SHARE_FORMS:
+            enc, m = (enc1, mask) if share else (enc1.repeat_interleave(beams, 0), mask.repeat_interleave(beams, 0))
+            cache = QuantizedBartCache(layers, capacity=past + 1, codes=codes, cross_group=beams if share else 1)
+            cache.cross_one_launch = share
+            for t in range(past):
+                q(attention_mask=m, decoder_input_ids=tok[:, t:t + 1], encoder_outputs=(enc,), past_key_values=cache, use_cache=True)
+            lens = list(cache._len)
+            decoder = GraphDecoder(q, enc, m, cache)
+
+            def run(cache=cache, decoder=decoder, lens=lens):
+                cache._len = list(lens)
+                cache._pos.fill_(past)
+                cache.reorder(perm)
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                decoder.step(last)
+                torch.cuda.synchronize()
+                return (time.perf_counter() - t0) * 1e3
+            for _ in range(4):                      # lead-in: one issued step, the two graphs captured
+                run()
+            assert decoder.info.captured == 2, decoder.info
+            runs[label] = (run, [])
+            held[label] = cache.nbytes()
+            assert cache.rejected() == 0 and bool(cache.coded()) is codes and not cache.demoted()
+            assert cache._cross[0][0].shape[0] == (ids.shape[0] if share else bb)
+        for _ in range(reps):
+            for label, (run, times) in runs.items():
+                times.append(run())
+    return {label: times for label, (run, times) in runs.items()}, held
+
+
+def share_logits_ab(q, ids, mask, beams, steps=12, rows=4):
+    """max |logit difference| over ``steps`` teacher-forced steps on the first ``rows`` inputs, shared against unshared, the
+    one-launch attention on in both, and how many stored cross-attention words of layer 0 differ between the two caches (the
+    shared form projects K / V on ``rows`` rows, the unshared one on ``rows * beams``): {"fp32": (d, words, of), "codes": ...}."""
+    from outlier_suppression_amd import util_layernorm as UL
+    from outlier_suppression_amd.model.quant_bart import QuantizedBartCache
+    layers = len(q.model.decoder.layers)
+    ids, mask = ids[:rows], mask[:rows]
+    out = {}
+    UL.FUSE_DECODE_ATTENTION = True
+    try:
+        with torch.no_grad():
+            enc1 = q.get_encoder()(ids, attention_mask=mask)
+            tok = torch.randint(3, 50265, (rows * beams, steps), device=ids.device)
+            for name, codes in (("fp32", False), ("codes", True)):
+                logits, held = [], []
+                for share in (False, True):
+                    enc, m = (enc1, mask) if share else (enc1.repeat_interleave(beams, 0), mask.repeat_interleave(beams, 0))
+                    cache = QuantizedBartCache(layers, capacity=steps, codes=codes, cross_group=beams if share else 1)
+                    logits.append(torch.stack([q(attention_mask=m, decoder_input_ids=tok[:, t:t + 1], encoder_outputs=(enc,),
+                                                 past_key_values=cache, use_cache=True)[0][:, -1] for t in range(steps)], 1))
+                    held.append(torch.cat([cache[0][2], cache[0][3]]))
+                out[name] = ((logits[0] - logits[1]).abs().max().item(), int((held[0] != held[1]).sum()), held[0].numel())
+    finally:
+        UL.FUSE_DECODE_ATTENTION = False
+    return out
+
+
+def share_cross_kv_ab(q, ids, mask, args):
+    lines = [f"cross-attention keys / values shared among the beams of a row, BART-large shape (random init, {args.layers}+{args.layers} "
+             f"layers), W6A6 LSQ+ plain quantising, batch {args.batch} x {args.beams} beams, source {args.src}; every form timed in "
+             f"turn in each of {args.reps} rounds, one process; median [min, max]"]
+    print(lines[0], flush=True)
+
+    def emit(new):
+        lines.extend(new)
+        print("\n".join(new), flush=True)
+    times = share_launch_ab(q, ids, args.beams, args.reps)
+    emit(["the cross-attention launch of one layer alone, us per launch (device events around 50 launches):"]
+         + [f"    {label:34s} {_stats(t)}" for label, t in times.items()])
+    held = {}
+    for past in (1, 31, 62):
+        times, held = share_step_ab(q, ids, mask, args.beams, past, args.reps)
+        emit([f"S = {past:2d}, one decoder step as a replayed graph, a beam reorder pending, ms:"]
+             + [f"    {label:34s} {_stats(t)}" for label, t in times.items()])
+    attn = q.model.decoder.layers[0].encoder_attn
+    for fmt, size in (("fp32", 4), ("coded", 1)):
+        cross = 2 * args.layers * args.batch * args.beams * attn.num_heads * args.src * attn.head_dim * size
+        a, b = held[f"{fmt} cache, one copy per beam"], held[f"{fmt} cache, shared"]
+        emit([f"cache.nbytes() at capacity 63, {fmt} cache: one copy per beam {a}, shared {b}; the difference {a - b} is the cross "
+              f"tensors' {cross} B * ({args.beams} - 1) / {args.beams} = {cross // args.beams * (args.beams - 1)}"])
+        assert a - b == cross // args.beams * (args.beams - 1), (a, b, cross)
+    gen = {label: [] for label, *_ in SHARE_FORMS}
+    tokens, did = {}, {}
+    kw = dict(attention_mask=mask, max_length=62, num_beams=args.beams, min_length=62, graph=True, beam_select=True, beam_advance=True)
+    from outlier_suppression_amd import util_layernorm as UL
+    UL.FUSE_DECODE_ATTENTION = True                 # the first step, issued by the model, computes the replayed steps' words in every form
+    try:
+        with torch.no_grad():
+            for r in range(args.reps + 1):
+                for label, codes, share in SHARE_FORMS:
+                    secs, out = _timed(lambda: q.generate(ids, cache_codes=codes, share_cross_kv=share, **kw), unit=1.0)
+                    tokens[label], did[label] = out, repr(q.last_share_cross_kv)
+                    assert (q.last_share_cross_kv.reason is None) is share and q.last_decode_graph.reason is None, (label, did[label])
+                    if r:                           # the first round warms every form up
+                        gen[label].append(secs)
+    finally:
+        UL.FUSE_DECODE_ATTENTION = False
+    emit([f"generate(max_length=62, num_beams={args.beams}, min_length=62, graph=True, beam_select=True, beam_advance=True), the "
+          f"one-launch attention on for the first step too, s, wall time of the call (capture included):"]
+         + [f"    {label:34s} {_stats(t)}   {did[label]}" for label, t in gen.items()])
+    for fmt in ("fp32", "coded"):
+        a, b = tokens[f"{fmt} cache, one copy per beam"], tokens[f"{fmt} cache, shared"]
+        same = a.shape == b.shape and bool(torch.equal(a, b))
+        emit([f"    tokens, {fmt} cache, shared against one copy per beam: " + ("equal" if same else
+              f"DIFFER in {int((a != b).sum()) if a.shape == b.shape else 'shape'} of {a.numel()} positions")])
+    for rows in sorted({min(4, args.batch), args.batch}):
+        d = share_logits_ab(q, ids, mask, args.beams, rows=rows)
+        emit([f"{rows} x {args.beams} rows, 12 teacher-forced steps, shared against one copy per beam, the one-launch attention on in "
+              f"both: max |logit difference| fp32 cache {d['fp32'][0]:.3g}, coded cache {d['codes'][0]:.3g}"
+              + (" -- 0: every word is the same" if d["fp32"][0] == 0 and d["codes"][0] == 0 else "")
+              + f"; stored cross K / V words of layer 0 that differ (K / V projected on {rows} rows against {rows * args.beams}): "
+              f"fp32 cache {d['fp32'][1]} of {d['fp32'][2]}, coded cache {d['codes'][1]} of {d['codes'][2]}"])
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=32)
@@ -850,9 +1039,16 @@ def main():
     ap.add_argument("--greedy-advance", action="store_true")
     ap.add_argument("--sample-advance", action="store_true")
     ap.add_argument("--sample-nucleus", action="store_true")
+    ap.add_argument("--share-cross-kv", action="store_true")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     q, ids, mask = build(args.batch, args.src, args.layers)
+    if args.share_cross_kv:
+        text = "\n".join(share_cross_kv_ab(q, ids, mask, args))
+        if args.out:
+            with open(args.out, "w") as f:
+                f.write(text + "\n")
+        return
     if args.sample_nucleus:
         text = "\n".join(sample_nucleus_ab(q, ids, mask, args))
         if args.out:
