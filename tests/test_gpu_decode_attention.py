@@ -5,8 +5,17 @@ integer codes (tests/test_oracle_decode_attention.py shows it for the eager CPU 
 ``out`` and ``probs_out`` are compared as WORDS with ``(code - zp) * scale``.
 
 All shapes are tiny: what can go wrong sits in the trip counts.  A wave covers R = 64 / (head_dim / 4) rows per load, the
-four waves 4 R positions per trip, four trips of loads are in flight; head_dim 16 / 64 / 128 give 64 / 16 / 8 positions per
-trip and kv_len runs over 1, 3, 4R - 1, 4R, 4R + 1, 8R + 5, 17R + 1, plus 4096 once."""
+four waves 4 R positions per trip, four trips of loads are in flight; the seven head sizes the kernel is instantiated for
+(4 .. 256: LPR 1 .. 64, R 64 .. 1) give 256 .. 4 positions per trip and kv_len runs over 1, 3, 4R - 1, 4R, 4R + 1, 8R + 5,
+17R + 1, plus the limit once per head size (4096; at head_dim 256 also 1024).
+
+osq_decode_attention_codes is held to the same float64 restatement on the helper's CODED cases: the values of the code bytes
+are formed in numpy from the record, so a misreading of the record that the library's own dequantize_kv_codes shared would
+show here.  NaN and infinity as data are compared with the patterns the eager sequence gives them.
+
+Measured on MI355X: profiles/decode_attention_head_sizes.txt (written when OSQ_DECODE_ATTENTION_HEAD_SIZES_OUT=<path> is set)."""
+import os
+
 import numpy as np
 import pytest
 import torch
@@ -62,25 +71,59 @@ class Params:
             assert np.float32(self.scale.item()) == self.g.scale_after and np.float32(self.zp.item()) == self.g.zp_after
 
 
+def _code_buffer(codes, cap, record, seed, dev):
+    """codes [B, h, S, d] as the first S positions of a [B, h, cap, d] byte buffer.  Under a 6-bit record the tail holds bytes
+    that are no code (64..255): a read past kv_len shows as a value no code has."""
+    b, h, s, d = codes.shape
+    g = torch.Generator().manual_seed(seed)
+    buf = torch.randint(64 if record[2] == 0 else 0, 256, (b, h, cap, d), generator=g).to(torch.uint8)
+    buf[:, :, :s] = torch.from_numpy(codes)
+    return buf.to(dev)
+
+
 def launch(ref, dev, cap="eq", probs_q=True, ctx_q=True, want_probs=True, head_dim=None, kv_len=None, k_offset=0):
-    """One call of the entry point on the case's tensors.  Returns (status, out, probs_out or None, Params, Params)."""
+    """One call of the entry point on the case's tensors: osq_decode_attention_fake_quant, or osq_decode_attention_codes on
+    the code bytes and records of a coded case (``rejected`` must stay 0).  Returns (status, out, probs_out or None, Params,
+    Params)."""
     from outlier_suppression_amd import _hip
     lib = _hip.load()
     case = ref["case"]
     b, h, d, s = case.batch, case.heads, case.head_dim, case.kv_len
     k_cap, v_cap = _caps(cap, s)
     q = torch.from_numpy(ref["q"]).to(dev)
-    k, v = _cap_buffer(ref["k"], k_cap, dev), _cap_buffer(ref["v"], v_cap, dev)
     mask = None if ref["mask"] is None else torch.from_numpy(ref["mask"]).to(dev)
     out = torch.full((b, 1, h * d), SENTINEL, dtype=torch.float32, device=dev)
     probs = torch.full((b, h, 1, s), SENTINEL, dtype=torch.float32, device=dev) if want_probs else None
     pp, cp = Params(ref["probs_q"] if probs_q else None, dev), Params(ref["ctx_q"] if ctx_q else None, dev)
-    rc = lib.osq_decode_attention_fake_quant(q.data_ptr(), k.data_ptr() + k_offset, v.data_ptr(), _hip.ptr(mask), out.data_ptr(),
-                                             _hip.ptr(probs), b, h, d if head_dim is None else head_dim,
-                                             s if kv_len is None else kv_len, k_cap, v_cap, *pp.args, *cp.args,
-                                             _hip.raw_stream(dev))
-    torch.cuda.synchronize()
+    shape = [b, h, d if head_dim is None else head_dim, s if kv_len is None else kv_len, k_cap, v_cap]
+    if case.coded:
+        k = _code_buffer(ref["k_codes"], k_cap, ref["k_record"], ref["seed"], dev)
+        v = _code_buffer(ref["v_codes"], v_cap, ref["v_record"], ref["seed"] + 1, dev)
+        rejected = torch.zeros(1, dtype=torch.int32, device=dev)
+        recs, keep = [], []
+        for scale_eff, zp_eff, quant_min in (ref["k_record"], ref["v_record"]):
+            keep += [torch.tensor([scale_eff], dtype=torch.float32, device=dev), torch.tensor([zp_eff], dtype=torch.float32, device=dev)]
+            recs += [keep[-2].data_ptr(), keep[-1].data_ptr(), quant_min]
+        rc = lib.osq_decode_attention_codes(q.data_ptr(), k.data_ptr() + k_offset, v.data_ptr(), _hip.ptr(mask), out.data_ptr(),
+                                            _hip.ptr(probs), *shape, *recs, rejected.data_ptr(), *pp.args, *cp.args,
+                                            _hip.raw_stream(dev))
+        torch.cuda.synchronize()
+        assert int(rejected.item()) == 0
+    else:
+        k, v = _cap_buffer(ref["k"], k_cap, dev), _cap_buffer(ref["v"], v_cap, dev)
+        rc = lib.osq_decode_attention_fake_quant(q.data_ptr(), k.data_ptr() + k_offset, v.data_ptr(), _hip.ptr(mask), out.data_ptr(),
+                                                 _hip.ptr(probs), *shape, *pp.args, *cp.args, _hip.raw_stream(dev))
+        torch.cuda.synchronize()
     return rc, out.cpu().numpy(), None if probs is None else probs.cpu().numpy(), pp, cp
+
+
+REPORT = {}        # case -> line of profiles/decode_attention_head_sizes.txt, filled as the cases pass
+
+
+def _report(ref, extra=""):
+    c = ref["case"]
+    REPORT[c] = (f"{c.head_dim:4d} {c.kv_len:5d} {'codes' if c.coded else 'fp32':5s} {c.batch}x{c.heads} {c.bits:5s} {c.mode:7s} {c.mask:4s} "
+                 f"{ref['seed']:7d} {ref['margin']:10.3e} {ref['worst_g']:9.3e}{extra}")
 
 
 def _check_case(case, dev, cap=None):
@@ -92,18 +135,53 @@ def _check_case(case, dev, cap=None):
     assert same_f32(probs, ref["probs"]) and same_f32(out, ref["out"]), (case, cap, ref["seed"], bad_p, bad_c)
     pp.check_repaired()
     cp.check_repaired()
+    _report(ref)
 
 
 @pytest.mark.parametrize("head_dim", DA.HEAD_DIMS)
 def test_cases_through_the_c_abi(dev, head_dim):
     """Asymmetric 6-bit and symmetric 8-bit, Fixed and LSQ+ (OSQ_PARAM_SANITIZE, on a negative scale and an out-of-range zero
-    point in half of them), every kv_len of the table, batch * heads 1 and 6, the mask and cap variants rotating."""
+    point in half of them), every kv_len of the table, batch * heads 1 and 6 (2 and 2 at head_dim 256), the mask and cap
+    variants rotating."""
     for case in DA.table(head_dim):
+        _check_case(case, dev)
+
+
+@pytest.mark.parametrize("head_dim", DA.HEAD_DIMS)
+def test_coded_cases_through_the_c_abi(dev, head_dim):
+    """osq_decode_attention_codes against the CODED float64 reference: K and V as 6-bit and 8-bit code bytes whose values
+    numpy forms as ((u + quant_min) as fp32 - zp_eff) * scale_eff, with fractional zp_eff -- not another kernel's reading of
+    the record.  The coded kv_lens (sixteen trips of loads in flight), bytes that are no code behind kv_len, rejected 0."""
+    for case in DA.table(head_dim, coded=True):
         _check_case(case, dev)
 
 
 def test_kv_limit(dev):
     _check_case(DA.LIMIT_CASE, dev)
+
+
+@pytest.mark.parametrize("case", DA.LIMIT_CASES[1:], ids=lambda c: f"{c.head_dim}-{c.kv_len}")
+def test_kv_limit_at_the_other_head_sizes(dev, case):
+    """kv_len 4096 at head_dim 4, 8 and 32 (16 to 128 trips); head_dim 256 at 1024 (256 trips of four positions)."""
+    _check_case(case, dev)
+
+
+def test_kv_limit_at_head_dim_256(dev):
+    """1024 trips of four positions.  The one case without a tie-free instance (DA.RELAXED_CASE): its probabilities are
+    tie-free and compared as words; the context as words wherever the float64 u is further than 4 g from a tie, and at most
+    one quantization step off elsewhere.  The share of sure entries (at least 0.9) is asserted on the reference alone in
+    tests/test_oracle_decode_attention.py.  No other case is compared this way."""
+    ref = DA.reference(DA.RELAXED_CASE)
+    sure, _ = DA.sure_entries(ref)
+    assert sure.mean() >= 0.9
+    rc, out, probs, pp, cp = launch(ref, dev, DA.RELAXED_CASE.cap)
+    assert rc == 0 and same_f32(probs, ref["probs"])
+    assert same_f32(out[sure], ref["out"][sure])
+    assert (np.abs(out - ref["out"]) <= float(ref["ctx_q"].scale_eff) * (1 + 1e-6)).all()
+    pp.check_repaired()
+    cp.check_repaired()
+    off = int((out.view(np.uint32) != ref["out"].view(np.uint32)).sum())
+    _report(ref, f"   sure share {sure.mean():.4f}, {off} of {out.size} entries one step off")
 
 
 @pytest.mark.parametrize("head_dim", DA.HEAD_DIMS)
@@ -173,13 +251,14 @@ def test_probs_quantizer_absent(dev):
     cp.check_repaired()
 
 
-@pytest.mark.parametrize("what", ["head_dim 12", "kv_len 0", "kv_len 4097", "misaligned k"])
+@pytest.mark.parametrize("what", ["head_dim 12", "kv_len 0", "kv_len 4097", "misaligned k", "head_dim 260", "head_dim 24"])
 def test_unsupported(dev, what):
-    """OSQ_ERR_UNSUPPORTED, nothing launched: out keeps its sentinel."""
+    """OSQ_ERR_UNSUPPORTED, nothing launched: out keeps its sentinel.  head_dim 260 is LPR 65, more lanes than a wave has;
+    24 is LPR 6, no power of two."""
     from outlier_suppression_amd import _hip
     ref = DA.reference(_plain_case(16))
     kw = {"head_dim 12": dict(head_dim=12), "kv_len 0": dict(kv_len=0), "kv_len 4097": dict(kv_len=4097),
-          "misaligned k": dict(k_offset=4)}[what]
+          "misaligned k": dict(k_offset=4), "head_dim 260": dict(head_dim=260), "head_dim 24": dict(head_dim=24)}[what]
     rc, out, probs, _, _ = launch(ref, dev, cap="plus7", **kw)
     assert rc == _hip.ERR_UNSUPPORTED
     assert (out == np.float32(SENTINEL)).all() and (probs == np.float32(SENTINEL)).all()
@@ -217,3 +296,46 @@ def test_host_wrapper_on_cache_views(dev):
     assert ops.decode_attention_fake_quant(q[..., :12].contiguous(), k[..., :12].contiguous(), v[..., :12].contiguous(),
                                            None, None, None) is None
     assert ops.decode_attention_fake_quant(q, k.transpose(1, 2).contiguous().transpose(1, 2), v, None, None, None) is None
+
+
+@pytest.mark.parametrize("kind", DA.NONFINITE_KINDS)
+def test_nan_and_infinity_as_data(dev, kind):
+    """NaN and infinity in q, K, V and the mask, at head_dim 4, 64 and 256 (LPR 1, 16, 64), batch x heads 2 x 3, kv_len 3 and
+    one position beyond a trip.  The patterns are DA.nonfinite()'s, which tests/test_oracle_decode_attention.py derives from
+    the eager sequence: exactly the stated words are NaN -- all probabilities and all head_dim columns of the touched
+    (b, h) for a NaN in K or q and a +inf in K, every head of a batch row whose mask is -inf throughout, one column for a NaN
+    in V under a zero probability -- and every other word is the clean run's, which is the float64 reference's.  -inf in part
+    of a mask row gives the words of finfo.min there."""
+    for case in DA.nonfinite_cases():
+        ref = DA.reference(case)
+        rc, clean_out, clean_probs, _, _ = launch(ref, dev, case.cap)
+        assert rc == 0 and same_f32(clean_out, ref["out"]) and same_f32(clean_probs, ref["probs"]), case
+        x = DA.nonfinite(ref, kind)
+        rc, out, probs, _, _ = launch(dict(ref, q=x["q"], k=x["k"], v=x["v"], mask=x["mask"]), dev, case.cap)
+        assert rc == 0, case
+        if x["twin_mask"] is not None:
+            rc, clean_out, clean_probs, _, _ = launch(dict(ref, mask=x["twin_mask"]), dev, case.cap)
+            assert rc == 0, case
+            assert (probs[0][..., np.isneginf(x["mask"][0, 0, 0])] == 0).all(), case
+        assert (np.isnan(probs) == x["nan_probs"]).all(), (case, kind, int(np.isnan(probs).sum()), int(x["nan_probs"].sum()))
+        assert (np.isnan(out) == x["nan_out"]).all(), (case, kind, int(np.isnan(out).sum()), int(x["nan_out"].sum()))
+        assert same_f32(probs[~x["nan_probs"]], clean_probs[~x["nan_probs"]]), (case, kind)
+        assert same_f32(out[~x["nan_out"]], clean_out[~x["nan_out"]]), (case, kind)
+
+
+def test_z_report():
+    """What this run compared, per case: profiles/decode_attention_head_sizes.txt (written when
+    OSQ_DECODE_ATTENTION_HEAD_SIZES_OUT=<path> is set)."""
+    if not REPORT:           # run on its own: nothing to report
+        return
+    lines = ["osq_decode_attention_fake_quant / osq_decode_attention_codes against the float64 restatement (tests/_decode_attention.py):",
+             "every case below gave the reference's words in out and probs_out (tests/test_gpu_decode_attention.py).",
+             "margin: min |u - nearest tie| - 4 g over both quantizers (positive: tie-free); worst g: the largest forward bound on a u.",
+             "",
+             "head kv_len form  BxH bits  mode    mask    seed     margin   worst g"]
+    lines += [REPORT[c] for c in sorted(REPORT, key=lambda c: (c.head_dim, c.coded, c.kv_len, c.batch, c.bits, c.mode, c.mask))]
+    lines += ["", f"{len(REPORT)} cases"]
+    out = os.environ.get("OSQ_DECODE_ATTENTION_HEAD_SIZES_OUT")
+    if out:
+        with open(out, "w") as f:
+            f.write("\n".join(lines) + "\n")

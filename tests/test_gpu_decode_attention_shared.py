@@ -9,7 +9,12 @@ as WORDS (torch.equal on the int32 view; NaN-aware where NaN is expected), for f
 K and V of batch row b come from the seeded cases of tests/_decode_attention.py; every beam gets a
 query of its own.  Masks are built so that batch rows differ: a kernel that indexed the mask by query row would read another
 row.  Shapes are tiny; what can go wrong sits in the trip counts (kv_lens of the helper, plus the limit 1024), the chunking of
-the group (8 queries per workgroup: 9 leaves a chunk of one, 17 three chunks) and the row arithmetic (batch 2, heads 3)."""
+the group (8 queries per workgroup: 9 leaves a chunk of one, 17 three chunks) and the row arithmetic (batch 2, heads 3).
+
+All seven head sizes the kernel is instantiated for are launched.  At head_dim 256 (LPR 64) the final loop over the
+chunk's gn * LPR output words takes a second trip from five queries on: groups 5 and 8 run it, the chunks of one that 9 and
+17 leave do not; with kv_len 1024 and a chunk of eight the score rows and the partial vectors that reuse them both fill
+the LDS to its limit."""
 import functools
 
 import numpy as np
@@ -22,7 +27,8 @@ from conftest import same_f32
 pytestmark = pytest.mark.gpu
 
 SENTINEL = -777.25
-GROUPS = (1, 2, 3, 6, 8, 9, 17)
+GROUPS = (1, 2, 3, 5, 6, 8, 9, 17)
+assert {1, 5, 8} <= {g % 8 or 8 for g in GROUPS} and any(g > 8 for g in GROUPS)      # ragged last chunks of 1 and 5, a full one
 KINDS = (None, "fixed", "lsqplus_bad")
 FMIN = torch.finfo(torch.float32).min
 
@@ -162,7 +168,7 @@ def test_words_of_the_unshared_launch(dev, head_dim, codes):
     """Every kv_len of the helper's table and 1024, batch x heads (1, 1) and (2, 3), every group; masks, caps and the two
     quantizers (absent, fixed, LSQ+ with bad raw parameters) rotate at different periods."""
     i = 0
-    for s in DA.kv_lens(head_dim) + (1024,):
+    for s in tuple(n for n in DA.kv_lens(head_dim) if n <= 1024) + (1024,):     # head_dim 4: 17 R + 1 = 1089 is past this kernel's limit
         for b, h in ((1, 1), (2, 3)):
             for group in GROUPS:
                 _check(dev, head_dim, s, b, h, group, DA.MASKS[i % 3], DA.CAPS[(i // 3) % 3], KINDS[(i // 9) % 3],
@@ -305,3 +311,37 @@ def test_captured_launch_replays(dev, codes):
         torch.cuda.synchronize()
         want = _unshared_op(x, k, v, pq, cq, cd, 9)
         assert torch.equal(words(out), words(want[0])) and torch.equal(words(probs), words(want[1])), step
+
+
+@pytest.mark.parametrize("where", ["q", "k"])
+@pytest.mark.parametrize("head_dim", [4, 64, 256])
+def test_nan_as_data(dev, head_dim, where):
+    """The shared twin of test_gpu_decode_attention.py::test_nan_and_infinity_as_data, batch x heads 2 x 3, nine beams (a chunk
+    of eight and a chunk of one), kv_len 3 and one position beyond a trip.  A NaN in ONE beam's query makes that beam's
+    probabilities and head_dim columns of that head NaN and nothing else: the seven beams that share its workgroup keep the
+    clean run's words.  A NaN in the shared K makes them NaN for every beam of that batch row and head, in both chunks.
+    Either way the words are the unshared launch's on the repeated tensors."""
+    b, h, group, b0, h0, beam = 2, 3, 9, 1, 1, 3
+    for s in (3, DA.kv_lens(head_dim)[4]):
+        x = _inputs(dev, head_dim, s, b, h, group, "pad", "plus7", False)
+        rc, clean, clean_probs, _, _ = _launch(x, dev, True, "fixed", "fixed")
+        assert rc == 0 and not bool(torch.isnan(clean).any()) and not bool(torch.isnan(clean_probs).any())
+        x = dict(x, q=x["q"].clone(), k=x["k"].clone())
+        nan_rows = torch.zeros(b * group, h, dtype=torch.bool, device=dev)
+        if where == "q":
+            x["q"][b0 * group + beam, h0, 0, head_dim - 1] = float("nan")
+            nan_rows[b0 * group + beam, h0] = True
+        else:
+            x["k"][b0, h0, 0, 0] = float("nan")
+            nan_rows[b0 * group:(b0 + 1) * group, h0] = True
+        rc, want, want_probs, _, _ = _launch(x, dev, False, "fixed", "fixed")
+        assert rc == 0
+        rc, got, got_probs, _, _ = _launch(x, dev, True, "fixed", "fixed")
+        assert rc == 0
+        what = (head_dim, s, where)
+        assert same_f32(got.cpu().numpy(), want.cpu().numpy()) and same_f32(got_probs.cpu().numpy(), want_probs.cpu().numpy()), what
+        nan_probs = nan_rows[:, :, None, None].expand(b * group, h, 1, s)
+        nan_out = nan_rows[:, None, :, None].expand(b * group, 1, h, head_dim).reshape(b * group, 1, h * head_dim)
+        assert torch.equal(torch.isnan(got_probs), nan_probs) and torch.equal(torch.isnan(got), nan_out), what
+        assert torch.equal(words(got_probs)[~nan_probs], words(clean_probs)[~nan_probs]), what
+        assert torch.equal(words(got)[~nan_out], words(clean)[~nan_out]), what

@@ -85,7 +85,7 @@ def _run(dev, kind, bit, symmetric, d, t, offset, row_kind, n_sites, gen):
             assert torch.equal(q.scale.data, s1) and torch.equal(q.zero_point.data, z1)
 
 
-@pytest.mark.parametrize("d", [16, 32, 64, 128])
+@pytest.mark.parametrize("d", [4, 8, 12, 16, 32, 64, 128, 256])      # any multiple of 4; 12: three float4s per row, no power of two
 @pytest.mark.parametrize("t", [1, 3])
 @pytest.mark.parametrize("offset", [0, 1, 61])
 @pytest.mark.parametrize("row_kind", ["none", "perm", "repeat"])

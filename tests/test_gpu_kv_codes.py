@@ -14,7 +14,9 @@ attention over such a cache returns NaN only.
 
 Attention (ops.decode_attention_codes): ``out`` and ``probs_out`` word-equal to ops.decode_attention_fake_quant on the
 dequantised fp32 K / V -- both kernels see the same on-grid values and add in the same order, so there is no tie filter and
-no tolerance.  (The fp32 kernel is itself pinned to float64 by tests/test_gpu_decode_attention.py.)"""
+no tolerance.  (The fp32 kernel is itself pinned to float64 by tests/test_gpu_decode_attention.py at every head size, and so is
+the coded form, on code bytes whose values numpy forms from the record; this comparison stays as the one that runs on what an
+append leaves behind, asym8 records included.)"""
 import math
 
 import pytest
@@ -24,7 +26,10 @@ pytestmark = pytest.mark.gpu
 
 RANGES = {"asym6": (0, 63, 31), "sym8": (-128, 127, 0), "asym8": (0, 255, 128)}
 QUANTS = [(bits, mode) for bits in RANGES for mode in ("fixed", "lsqplus")]
-HEAD_DIMS = (4, 16, 64, 128)
+HEAD_DIMS = (4, 8, 16, 32, 64, 128, 256)           # attention: every head size the kernel is instantiated for
+# append: any multiple of 4.  8 and 12 (two and three words per row) are the sizes at which the 16-byte copy decision --
+# (offset * dv) % 4, (cap * dv) % 4 -- depends on the offset and the cap in a way one word and whole units of four do not show
+APPEND_HEAD_DIMS = (4, 8, 12, 16, 64, 128)
 SENTINEL = 0xA5
 
 
@@ -168,7 +173,7 @@ def check_append(dev, g, bits, mode, d, b, h, t, offset, cap_kind, src_kind, bad
     assert int(rejected.item()) == 0
 
 
-@pytest.mark.parametrize("d", HEAD_DIMS)
+@pytest.mark.parametrize("d", APPEND_HEAD_DIMS)
 @pytest.mark.parametrize("bits, mode", QUANTS)
 def test_append(dev, bits, mode, d):
     g = torch.Generator(device=dev).manual_seed(1000 + d)
