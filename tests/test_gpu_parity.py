@@ -1322,8 +1322,9 @@ def test_select_shortcut_equals_full_pass(dev):
 
 
 def test_select_large_problems_match_oracle(dev):
-    """token_select_kernel at 4096 .. 32768 token slots (2 .. 8 sixteen-byte groups per thread) against the oracle,
-    bit for bit: i.i.d. values, outlier tokens, heavy duplicates, one constant, values sorted along the slots, all
+    """token_select_kernel at 4096 .. 32768 token slots against the oracle (the six geometries give 8, 2, 2, 2, 2 and 1
+    sixteen-byte groups per thread: token_select_kernel<8>, <2> and <1>; <4>, 8193 .. 16384 slots, runs in
+    tests/test_gpu_token_finalize.py), bit for bit: i.i.d. values, outlier tokens, heavy duplicates, one constant, values sorted along the slots, all
     negative, with and without masks, T % 4 != 0, percentiles from 0 to 1; the shortcut and the register pass agree."""
     from outlier_suppression_amd import ops
     from oracle import observer_oracle as OB
