@@ -30,6 +30,9 @@
 // order).  Elements are loaded one 32-bit word per lane: a row of an odd vocab is only 4-byte aligned.
 //
 // osq_sample_advance_at is the same launches with the position read by them: cur = *cur_dev + cur_add, as osq_greedy_advance_at.
+//
+// The step's arguments, the step read from the position word, the row's tail, the stopping word and the entry points' shared
+// requirements are advance_step.h's (greedy_advance.hip ends with them too); what is about the draw is sample_draw.h's.
 #include <math.h>
 #include <hip/hip_runtime.h>
 #include "osq_device.h"
@@ -45,28 +48,17 @@ __global__ __launch_bounds__(kBsThreads) void sample_chunk_kernel(SampleArgs a) 
     __shared__ unsigned int s_ban[kBsChunk / 32];
     __shared__ unsigned int s_red[2][2 * kBsWaves];
     __shared__ float s_sum[2][kBsWaves];
-    const SampleStep step = sample_step(a);
+    const Step step = step_of(a.s);
     if (step.cur < 0 || step.forced >= 0) return;                   // refused, or forced: every logit is ignored
     const int lane = threadIdx.x & (OSQ_WAVE - 1), w = threadIdx.x / OSQ_WAVE;
-    const int64_t row = blockIdx.x / a.chunks;
-    const int c = blockIdx.x % a.chunks;
+    const int64_t row = blockIdx.x / a.s.chunks;
+    const int c = blockIdx.x % a.s.chunks;
     const int c0 = c * kBsChunk;
-    const int len = min(kBsChunk, a.vocab - c0);
-    const float* x = a.logits + row * a.logits_stride + c0;
+    const int len = min(kBsChunk, a.s.vocab - c0);
     float v[kBsPer];
-#pragma unroll
-    for (int j = 0; j < kBsPer; ++j) {                              // issued before the bans are found: the loads fly meanwhile
-        const int i = threadIdx.x + j * kBsThreads;
-        v[j] = i < len ? x[i] : 0.f;
-    }
-    chunk_bans(s_ban, a.ban_ids, step.n_ban, a.seq + row * a.seq_stride, step.cur, a.ngram, c0, len);
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < kBsPer; ++j) {
-        const int i = threadIdx.x + j * kBsThreads;
-        const bool banned = (s_ban[i >> 5] >> (i & 31)) & 1u;
-        v[j] = sample_z(v[j], a.temperature, banned || i >= len);
-    }
+    chunk_each(a.s.logits + row * a.s.logits_stride + c0, s_ban, a.s.ban_ids, step.n_ban, a.s.seq + row * a.s.seq_stride,
+               step.cur, a.s.ngram, c0, len,
+               [&](int j, int, float x, bool banned, bool in) { v[j] = sample_z(x, a.temperature, banned || !in); });
 
     if (a.top_k == 0) {                                             // ---- the chunk's maximum and exp sum
         float mx = -INFINITY;
@@ -118,7 +110,7 @@ __global__ __launch_bounds__(kBsThreads) void sample_chunk_kernel(SampleArgs a) 
 // top-p cut and the draw u.  Every thread of the workgroup calls it.
 __device__ __forceinline__ int64_t sample_pick_top_k(const SampleArgs& a, int64_t b, float u, unsigned int (*s_red)[2 * kBsWaves],
                                                      unsigned int* s_key, int* s_tok, float* s_w) {
-    const int n = a.chunks * a.top_k;                               // among equal values slots run as tokens do
+    const int n = a.s.chunks * a.top_k;                             // among equal values slots run as tokens do
     BeamCand* cand = a.cands + b * n;
     unsigned int best = 0u, best_p = threadIdx.x;
     for (int p = threadIdx.x; p < n; p += kBsThreads) {
@@ -170,22 +162,22 @@ __device__ __forceinline__ int64_t sample_pick_top_k(const SampleArgs& a, int64_
 
 // The token of row b with top_k == 0, in every thread: the chunk the draw u falls into by the chunk sums, then that chunk's
 // tokens in order.  s_w: kBsChunk + kBsThreads floats; s_tot: kBsThreads; s_grp: kSaGroup.
-__device__ __forceinline__ int64_t sample_pick_full(const SampleArgs& a, const SampleStep& step, int64_t b, float u,
+__device__ __forceinline__ int64_t sample_pick_full(const SampleArgs& a, const Step& step, int64_t b, float u,
                                                     unsigned int* s_ban, unsigned int (*s_red)[2 * kBsWaves], float* s_w,
                                                     float* s_tot, float* s_grp) {
-    const float2* part = a.partials + b * a.chunks;
+    const float2* part = a.partials + b * a.s.chunks;
     float m = -INFINITY;
-    for (int k = 0; k < a.chunks; ++k) m = fmaxf(m, part[k].x);
+    for (int k = 0; k < a.s.chunks; ++k) m = fmaxf(m, part[k].x);
     if (m == -INFINITY) return 0;                                   // no survivor in the row
     float total = 0.f;
-    for (int k = 0; k < a.chunks; ++k) {
+    for (int k = 0; k < a.s.chunks; ++k) {
         const float2 p = part[k];
         total += p.y * sample_weight(p.x, m);
     }
     float target = u * total;
     float before = 0.f;
     int chosen = -1, last = 0;
-    for (int k = 0; k < a.chunks; ++k) {
+    for (int k = 0; k < a.s.chunks; ++k) {
         const float2 p = part[k];
         const float wc = p.y * sample_weight(p.x, m);
         if (wc > 0.f) last = k;
@@ -199,26 +191,16 @@ __device__ __forceinline__ int64_t sample_pick_full(const SampleArgs& a, const S
 
     // ---- the chosen chunk once more: its weights in token order
     const int c0 = chosen * kBsChunk;
-    const int len = min(kBsChunk, a.vocab - c0);
-    const float* x = a.logits + b * a.logits_stride + c0;
-    float v[kBsPer];
-#pragma unroll
-    for (int j = 0; j < kBsPer; ++j) {
-        const int i = threadIdx.x + j * kBsThreads;
-        v[j] = i < len ? x[i] : 0.f;
-    }
-    chunk_bans(s_ban, a.ban_ids, step.n_ban, a.seq + b * a.seq_stride, step.cur, a.ngram, c0, len);
-    __syncthreads();
+    const int len = min(kBsChunk, a.s.vocab - c0);
     const float mc = part[chosen].x;
     const float scale = sample_weight(mc, m);
-#pragma unroll
-    for (int j = 0; j < kBsPer; ++j) {
-        const int i = threadIdx.x + j * kBsThreads;
-        const bool banned = (s_ban[i >> 5] >> (i & 31)) & 1u;
-        const float z = sample_z(v[j], a.temperature, banned || i >= len);
-        s_w[i + (i >> 4)] = z == -INFINITY ? 0.f : sample_weight(z, mc) * scale;      // one pad word per 16: thread t reads 17 t + j
-    }
+    chunk_each(a.s.logits + b * a.s.logits_stride + c0, s_ban, a.s.ban_ids, step.n_ban, a.s.seq + b * a.s.seq_stride, step.cur,
+               a.s.ngram, c0, len, [&](int, int i, float x, bool banned, bool in) {
+                   const float z = sample_z(x, a.temperature, banned || !in);
+                   s_w[i + (i >> 4)] = z == -INFINITY ? 0.f : sample_weight(z, mc) * scale;   // one pad word per 16: thread t reads 17 t + j
+               });
     __syncthreads();
+    float v[kBsPer];
     float own = 0.f;
 #pragma unroll
     for (int j = 0; j < kBsPer; ++j) {
@@ -272,7 +254,7 @@ __global__ __launch_bounds__(kBsThreads) void sample_row_kernel(SampleArgs a) {
     __shared__ float s_tot[kBsThreads], s_grp[kBsThreads / kSaGroup];
     __shared__ unsigned int s_key[kSaMaxTopK];
     __shared__ int s_tok[kSaMaxTopK];
-    const SampleStep step = sample_step(a);
+    const Step step = step_of(a.s);
     if (step.cur < 0) return;                                       // refused: nothing written (sample_go_on_kernel says so)
     const int64_t b = blockIdx.x;
     int64_t token = step.forced;
@@ -281,22 +263,20 @@ __global__ __launch_bounds__(kBsThreads) void sample_row_kernel(SampleArgs a) {
         token = a.top_k > 0 ? sample_pick_top_k(a, b, u, s_red, s_key, s_tok, s_w)
                             : sample_pick_full(a, step, b, u, s_ban, s_red, s_w, s_tot, s_grp);
     }
-    if (threadIdx.x == 0) sample_finish_row(a, step, b, token);
+    if (threadIdx.x == 0) finish_row(a.s, step, b, token);
 }
 
-__global__ __launch_bounds__(kSaGoThreads) void sample_go_on_kernel(SampleArgs a) { sample_go_on(a); }
+__global__ __launch_bounds__(kStepGoThreads) void sample_go_on_kernel(SampleArgs a) { step_go_on(a.s); }
 
 __global__ __launch_bounds__(kBsThreads) void sample_uniforms_kernel(unsigned long long seed, int bsz, unsigned int cur, float* out) {
     const int b = blockIdx.x * kBsThreads + threadIdx.x;
     if (b < bsz) out[b] = sample_uniform(seed, static_cast<unsigned int>(b), cur);
 }
 
-static int64_t sample_chunks(int64_t vocab) { return (vocab + kBsChunk - 1) / kBsChunk; }
-
 static size_t sample_workspace_bytes(int64_t bsz, int64_t vocab, int64_t top_k) {
     if (bsz < 1 || vocab < 1 || top_k < 0 || top_k > kSaMaxTopK) return 0;
     static_assert(sizeof(BeamCand) == sizeof(float2), "one workspace slot holds a candidate or a chunk's (m_c, s_c)");
-    const int64_t slots = bsz * sample_chunks(vocab) * (top_k > 0 ? top_k : 1);
+    const int64_t slots = bsz * step_chunks(vocab) * (top_k > 0 ? top_k : 1);
     return static_cast<size_t>(slots) * sizeof(BeamCand) + static_cast<size_t>(bsz) * sizeof(unsigned int);
 }
 
@@ -308,59 +288,30 @@ extern "C" size_t osq_sample_advance_workspace_bytes(int64_t bsz, int64_t vocab,
     return sample_workspace_bytes(bsz, vocab, top_k);
 }
 
-// Both entry points.  cur_dev == nullptr: the static form at `cur` with n_ban ids and `forced`; else the position is the device
-// word, the ids apply below ban_below and the forced tokens fire at their positions.
-static int sample_advance_launch(const float* logits, int64_t logits_stride, int64_t* seq, int64_t seq_stride, int64_t cur,
-                                 const int32_t* cur_dev, int64_t cur_add, int64_t ngram, const int64_t* ban_ids, int64_t n_ban,
-                                 int64_t ban_below, int64_t forced, int64_t forced_bos, int64_t forced_eos,
-                                 const int64_t* eos_ids, int64_t n_eos, int64_t pad, uint8_t* unfinished, int64_t bsz,
-                                 int64_t vocab, int64_t max_length, int64_t* next_tokens, int32_t* go_on, void* workspace,
-                                 size_t workspace_bytes, uint64_t seed, float temperature, int64_t top_k, float top_p,
-                                 const float* uniforms, osq_stream stream) {
-    OSQ_REQUIRE(bsz >= 1 && vocab >= 1 && max_length >= 1, "sample_advance: a non-positive extent");
-    OSQ_REQUIRE(vocab <= INT32_MAX, "sample_advance: vocab does not fit 31 bits");
-    OSQ_REQUIRE(max_length <= kSaMaxLength, "sample_advance: max_length above 4096");
-    OSQ_REQUIRE(cur_dev || (cur >= 1 && cur < max_length), "sample_advance: cur outside [1, max_length)");
-    OSQ_REQUIRE(n_ban >= 0 && n_ban <= kBsMaxBan, "sample_advance: n_ban outside [0, 16]");
-    OSQ_REQUIRE(n_eos >= 0 && n_eos <= kSaMaxEos, "sample_advance: n_eos outside [0, 16]");
-    OSQ_REQUIRE(ngram >= 0, "sample_advance: negative ngram");
+// Both entry points: check, fill, launch.
+static int sample_advance_run(const StepCall& c, uint64_t seed, float temperature, int64_t top_k, float top_p,
+                              const float* uniforms, osq_stream stream) {
+    if (const int rc = step_check("sample_advance", c)) return rc;
     OSQ_REQUIRE(top_k >= 0 && top_k <= kSaMaxTopK, "sample_advance: top_k outside [0, 64]");
     OSQ_REQUIRE(top_p > 0.f && top_p <= 1.f, "sample_advance: top_p outside (0, 1]");
     OSQ_REQUIRE(temperature > 0.f && temperature <= 3.4028234663852886e38f, "sample_advance: temperature not positive and finite");
-    OSQ_REQUIRE(n_eos == 0 || unfinished, "sample_advance: n_eos without unfinished");
-    OSQ_REQUIRE(n_eos == 0 || eos_ids, "sample_advance: n_eos without eos_ids");
-    OSQ_REQUIRE(n_ban == 0 || ban_ids, "sample_advance: n_ban without ban_ids");
-    // a stored token is an index of the row: what is stored unchecked is checked here (a negative forced id: none)
-    OSQ_REQUIRE(forced < vocab && forced_bos < vocab && forced_eos < vocab, "sample_advance: a forced token outside [0, vocab)");
-    OSQ_REQUIRE(n_eos == 0 || (pad >= 0 && pad < vocab), "sample_advance: pad outside [0, vocab)");
-    OSQ_REQUIRE(logits_stride >= vocab, "sample_advance: logits row stride below vocab");
-    OSQ_REQUIRE(!seq || seq_stride >= max_length, "sample_advance: seq row stride below max_length");
-    OSQ_REQUIRE(ngram == 0 || seq, "sample_advance: ngram without seq");
-    const int64_t chunks = sample_chunks(vocab);
-    OSQ_REQUIRE(bsz <= INT32_MAX / (chunks * (top_k > 0 ? top_k : 1)), "sample_advance: too many elements");
-    OSQ_REQUIRE(workspace_bytes >= sample_workspace_bytes(bsz, vocab, top_k), "sample_advance: workspace too small");
-    OSQ_REQUIRE(logits && next_tokens && go_on && workspace, "sample_advance: null tensor");
-    OSQ_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 7u) == 0, "sample_advance: workspace not 8-byte aligned");
+    const int64_t chunks = step_chunks(c.vocab);
+    OSQ_REQUIRE(c.bsz <= INT32_MAX / (chunks * (top_k > 0 ? top_k : 1)), "sample_advance: too many elements");
+    OSQ_REQUIRE(c.workspace_bytes >= sample_workspace_bytes(c.bsz, c.vocab, top_k), "sample_advance: workspace too small");
     if (top_k == 0 && top_p < 1.f) {
         set_error("%s", "sample_advance: top_p below 1 without top_k (a nucleus over the whole vocabulary) has no kernel");
         return OSQ_ERR_UNSUPPORTED;
     }
-    const auto id = [](int64_t t) { return static_cast<int>(t < 0 ? -1 : t); };
-    BeamCand* cands = static_cast<BeamCand*>(workspace);
-    const int64_t slots = bsz * chunks * (top_k > 0 ? top_k : 1);
-    SampleArgs a{logits, seq, ban_ids, eos_ids, unfinished, next_tokens, go_on, uniforms, cands,
-                 static_cast<float2*>(workspace), reinterpret_cast<unsigned int*>(cands + slots), logits_stride, seq_stride, pad,
-                 static_cast<unsigned long long>(seed), temperature, top_p, static_cast<int>(top_k),
-                 static_cast<int>(bsz), static_cast<int>(vocab), static_cast<int>(chunks), static_cast<int>(max_length),
-                 static_cast<int>(cur), static_cast<int>(ngram > kBsMaxCur ? kBsMaxCur + 1 : ngram), static_cast<int>(n_ban),
-                 static_cast<int>(n_eos), id(forced), cur_dev, static_cast<int>(cur_add),
-                 static_cast<int>(ban_below < 0 ? 0 : (ban_below > kBsMaxCur ? kBsMaxCur + 1 : ban_below)), id(forced_bos),
-                 id(forced_eos)};
+    BeamCand* cands = static_cast<BeamCand*>(c.workspace);
+    const int64_t slots = c.bsz * chunks * (top_k > 0 ? top_k : 1);
+    const SampleArgs a{.s = step_args(c, chunks, reinterpret_cast<unsigned int*>(cands + slots)), .uniforms = uniforms,
+                       .cands = cands, .partials = static_cast<float2*>(c.workspace), .seed = seed, .temperature = temperature,
+                       .top_p = top_p, .top_k = static_cast<int>(top_k)};
     hipStream_t st = static_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(sample_chunk_kernel, dim3(static_cast<unsigned>(bsz * chunks)), dim3(kBsThreads), 0, st, a);
-    hipLaunchKernelGGL(sample_row_kernel, dim3(static_cast<unsigned>(bsz)), dim3(kBsThreads), 0, st, a);
-    hipLaunchKernelGGL(sample_go_on_kernel, dim3(1), dim3(kSaGoThreads), 0, st, a);
-    return check_launch(cur_dev ? "sample_advance_at" : "sample_advance");
+    hipLaunchKernelGGL(sample_chunk_kernel, dim3(static_cast<unsigned>(c.bsz * chunks)), dim3(kBsThreads), 0, st, a);
+    hipLaunchKernelGGL(sample_row_kernel, dim3(static_cast<unsigned>(c.bsz)), dim3(kBsThreads), 0, st, a);
+    hipLaunchKernelGGL(sample_go_on_kernel, dim3(1), dim3(kStepGoThreads), 0, st, a);
+    return check_launch(c.cur_dev ? "sample_advance_at" : "sample_advance");
 }
 
 extern "C" int osq_sample_advance(const float* logits, int64_t logits_stride, int64_t* seq, int64_t seq_stride, int64_t cur,
@@ -369,9 +320,11 @@ extern "C" int osq_sample_advance(const float* logits, int64_t logits_stride, in
                                   int64_t max_length, int64_t* next_tokens, int32_t* go_on, void* workspace,
                                   size_t workspace_bytes, uint64_t seed, float temperature, int64_t top_k, float top_p,
                                   const float* uniforms, osq_stream stream) {
-    return sample_advance_launch(logits, logits_stride, seq, seq_stride, cur, nullptr, 0, ngram, ban_ids, n_ban, 0, forced, -1,
-                                 -1, eos_ids, n_eos, pad, unfinished, bsz, vocab, max_length, next_tokens, go_on, workspace,
-                                 workspace_bytes, seed, temperature, top_k, top_p, uniforms, stream);
+    return sample_advance_run({.logits = logits, .logits_stride = logits_stride, .seq = seq, .seq_stride = seq_stride, .cur = cur,
+                               .ngram = ngram, .ban_ids = ban_ids, .n_ban = n_ban, .forced = forced, .eos_ids = eos_ids,
+                               .n_eos = n_eos, .pad = pad, .unfinished = unfinished, .bsz = bsz, .vocab = vocab,
+                               .max_length = max_length, .next_tokens = next_tokens, .go_on = go_on, .workspace = workspace,
+                               .workspace_bytes = workspace_bytes}, seed, temperature, top_k, top_p, uniforms, stream);
 }
 
 extern "C" int osq_sample_advance_at(const float* logits, int64_t logits_stride, int64_t* seq, int64_t seq_stride,
@@ -383,9 +336,12 @@ extern "C" int osq_sample_advance_at(const float* logits, int64_t logits_stride,
                                      const float* uniforms, osq_stream stream) {
     OSQ_REQUIRE(cur_dev, "sample_advance_at: null position word");
     OSQ_REQUIRE(cur_add >= INT32_MIN && cur_add <= INT32_MAX, "sample_advance_at: cur_add does not fit 32 bits");
-    return sample_advance_launch(logits, logits_stride, seq, seq_stride, 0, cur_dev, cur_add, ngram, ban_ids, n_ban, ban_below,
-                                 -1, forced_bos, forced_eos, eos_ids, n_eos, pad, unfinished, bsz, vocab, max_length,
-                                 next_tokens, go_on, workspace, workspace_bytes, seed, temperature, top_k, top_p, uniforms, stream);
+    return sample_advance_run({.logits = logits, .logits_stride = logits_stride, .seq = seq, .seq_stride = seq_stride,
+                               .cur_dev = cur_dev, .cur_add = cur_add, .ngram = ngram, .ban_ids = ban_ids, .n_ban = n_ban,
+                               .ban_below = ban_below, .forced_bos = forced_bos, .forced_eos = forced_eos, .eos_ids = eos_ids,
+                               .n_eos = n_eos, .pad = pad, .unfinished = unfinished, .bsz = bsz, .vocab = vocab,
+                               .max_length = max_length, .next_tokens = next_tokens, .go_on = go_on, .workspace = workspace,
+                               .workspace_bytes = workspace_bytes}, seed, temperature, top_k, top_p, uniforms, stream);
 }
 
 extern "C" int osq_sample_uniforms(uint64_t seed, int64_t bsz, int64_t cur, float* out, osq_stream stream) {

@@ -10,7 +10,8 @@
 //                                            draw; a prefix count numbers the tokens of a tie group.  Then the forced token in
 //                                            its place, pad / eos, seq[b, cur], next_tokens[b] and the row's unfinished flag
 //                                            into the workspace.  A forced step reads no logit
-//   launch 2   sample_nucleus_go_on_kernel   one wave: sample_advance.hip's stopping word (sample_draw.h)
+//   launch 2   sample_nucleus_go_on_kernel   one wave: the stopping word of every advance call (advance_step.h, as the
+//                                            step's arguments, the row's tail and the entry points' shared requirements)
 //
 // No workgroup waits for another; no atomics on device memory (the ban bitmap is built with LDS atomics, as chunk_bans does).
 //
@@ -149,10 +150,10 @@ __device__ __forceinline__ float sn_above(const unsigned int (&key)[kSnPer], con
 }
 
 // The token of row b, in every thread.
-__device__ __forceinline__ int64_t sn_pick(const SampleArgs& a, const SampleStep& step, int64_t b, float u, float* s_stage,
+__device__ __forceinline__ int64_t sn_pick(const SampleArgs& a, const Step& step, int64_t b, float u, float* s_stage,
                                            unsigned int* s_ban, unsigned int (*s_red)[kSnWaves]) {
     const int lane = threadIdx.x & (OSQ_WAVE - 1), w = threadIdx.x / OSQ_WAVE;
-    const float* x = a.logits + b * a.logits_stride;
+    const float* x = a.s.logits + b * a.s.logits_stride;
     unsigned int key[kSnPer];
     float wt[kSnPer];
     {
@@ -161,12 +162,12 @@ __device__ __forceinline__ int64_t sn_pick(const SampleArgs& a, const SampleStep
 #pragma unroll
             for (int k = 0; k < kSnPhaseLoads; ++k) {
                 const int i = w * kSnWaveTokens + h * kSnPhaseWords + k * OSQ_WAVE + lane;
-                r[k] = i < a.vocab ? x[i] : 0.f;
+                r[k] = i < a.s.vocab ? x[i] : 0.f;
             }
         };
         load(0);                                                    // issued before the bans are found: the loads fly meanwhile
-        span_bans<kSnThreads, kSnMaxVocab / 32>(s_ban, a.ban_ids, step.n_ban, a.seq + b * a.seq_stride, step.cur, a.ngram, 0,
-                                                a.vocab);
+        span_bans<kSnThreads, kSnMaxVocab / 32>(s_ban, a.s.ban_ids, step.n_ban, a.s.seq + b * a.s.seq_stride, step.cur,
+                                                a.s.ngram, 0, a.s.vocab);
         float* stage = s_stage + w * kSnPhaseWords;
 #pragma unroll
         for (int h = 0; h < kSnPhases; ++h) {
@@ -189,7 +190,7 @@ __device__ __forceinline__ int64_t sn_pick(const SampleArgs& a, const SampleStep
         for (int j = g * kSnBlock; j < (g + 1) * kSnBlock; ++j) {
             const int i = threadIdx.x * kSnPer + j;
             const bool banned = (s_ban[i >> 5] >> (i & 31)) & 1u;   // i < kSnMaxVocab: inside the bitmap
-            const float z = sample_z(wt[j], a.temperature, banned || i >= a.vocab);
+            const float z = sample_z(wt[j], a.temperature, banned || i >= a.s.vocab);
             key[j] = z == -INFINITY ? 0u : beam_key(z);
             top = max(top, key[j]);
         }
@@ -264,7 +265,7 @@ __global__ __launch_bounds__(kSnThreads) void sample_nucleus_row_kernel(SampleAr
     __shared__ float s_stage[kSnWaves * kSnPhaseWords];
     __shared__ unsigned int s_ban[kSnMaxVocab / 32];
     __shared__ unsigned int s_red[2][kSnWaves];
-    const SampleStep step = sample_step(a);
+    const Step step = step_of(a.s);
     if (step.cur < 0) return;                                       // refused: nothing written (the go_on launch says so)
     const int64_t b = blockIdx.x;
     int64_t token = step.forced;
@@ -272,10 +273,10 @@ __global__ __launch_bounds__(kSnThreads) void sample_nucleus_row_kernel(SampleAr
         const float u = a.uniforms ? a.uniforms[b] : sample_uniform(a.seed, static_cast<unsigned int>(b), static_cast<unsigned int>(step.cur));
         token = sn_pick(a, step, b, u, s_stage, s_ban, s_red);
     }
-    if (threadIdx.x == 0) sample_finish_row(a, step, b, token);
+    if (threadIdx.x == 0) finish_row(a.s, step, b, token);
 }
 
-__global__ __launch_bounds__(kSaGoThreads) void sample_nucleus_go_on_kernel(SampleArgs a) { sample_go_on(a); }
+__global__ __launch_bounds__(kStepGoThreads) void sample_nucleus_go_on_kernel(SampleArgs a) { step_go_on(a.s); }
 
 static size_t nucleus_workspace_bytes(int64_t bsz) { return static_cast<size_t>(bsz) * sizeof(unsigned int); }
 
@@ -287,53 +288,25 @@ extern "C" size_t osq_sample_nucleus_workspace_bytes(int64_t bsz, int64_t vocab)
     return (bsz < 1 || vocab < 1 || vocab > kSnMaxVocab) ? 0 : nucleus_workspace_bytes(bsz);
 }
 
-// Both entry points.  cur_dev == nullptr: the static form at `cur` with n_ban ids and `forced`; else the position is the device
-// word, the ids apply below ban_below and the forced tokens fire at their positions.  The checks are sample_advance_launch's.
-static int sample_nucleus_launch(const float* logits, int64_t logits_stride, int64_t* seq, int64_t seq_stride, int64_t cur,
-                                 const int32_t* cur_dev, int64_t cur_add, int64_t ngram, const int64_t* ban_ids, int64_t n_ban,
-                                 int64_t ban_below, int64_t forced, int64_t forced_bos, int64_t forced_eos,
-                                 const int64_t* eos_ids, int64_t n_eos, int64_t pad, uint8_t* unfinished, int64_t bsz,
-                                 int64_t vocab, int64_t max_length, int64_t* next_tokens, int32_t* go_on, void* workspace,
-                                 size_t workspace_bytes, uint64_t seed, float temperature, float top_p, const float* uniforms,
-                                 osq_stream stream) {
-    OSQ_REQUIRE(bsz >= 1 && vocab >= 1 && max_length >= 1, "sample_nucleus: a non-positive extent");
-    OSQ_REQUIRE(bsz <= INT32_MAX && vocab <= INT32_MAX, "sample_nucleus: bsz or vocab does not fit 31 bits");
-    OSQ_REQUIRE(max_length <= kSaMaxLength, "sample_nucleus: max_length above 4096");
-    OSQ_REQUIRE(cur_dev || (cur >= 1 && cur < max_length), "sample_nucleus: cur outside [1, max_length)");
-    OSQ_REQUIRE(n_ban >= 0 && n_ban <= kBsMaxBan, "sample_nucleus: n_ban outside [0, 16]");
-    OSQ_REQUIRE(n_eos >= 0 && n_eos <= kSaMaxEos, "sample_nucleus: n_eos outside [0, 16]");
-    OSQ_REQUIRE(ngram >= 0, "sample_nucleus: negative ngram");
+// Both entry points: check, fill, launch.
+static int sample_nucleus_run(const StepCall& c, uint64_t seed, float temperature, float top_p, const float* uniforms,
+                              osq_stream stream) {
+    if (const int rc = step_check("sample_nucleus", c)) return rc;
+    OSQ_REQUIRE(c.bsz <= INT32_MAX, "sample_nucleus: bsz does not fit 31 bits");
     OSQ_REQUIRE(top_p > 0.f && top_p <= 1.f, "sample_nucleus: top_p outside (0, 1]");
     OSQ_REQUIRE(temperature > 0.f && temperature <= 3.4028234663852886e38f, "sample_nucleus: temperature not positive and finite");
-    OSQ_REQUIRE(n_eos == 0 || unfinished, "sample_nucleus: n_eos without unfinished");
-    OSQ_REQUIRE(n_eos == 0 || eos_ids, "sample_nucleus: n_eos without eos_ids");
-    OSQ_REQUIRE(n_ban == 0 || ban_ids, "sample_nucleus: n_ban without ban_ids");
-    // a stored token is an index of the row: what is stored unchecked is checked here (a negative forced id: none)
-    OSQ_REQUIRE(forced < vocab && forced_bos < vocab && forced_eos < vocab, "sample_nucleus: a forced token outside [0, vocab)");
-    OSQ_REQUIRE(n_eos == 0 || (pad >= 0 && pad < vocab), "sample_nucleus: pad outside [0, vocab)");
-    OSQ_REQUIRE(logits_stride >= vocab, "sample_nucleus: logits row stride below vocab");
-    OSQ_REQUIRE(!seq || seq_stride >= max_length, "sample_nucleus: seq row stride below max_length");
-    OSQ_REQUIRE(ngram == 0 || seq, "sample_nucleus: ngram without seq");
-    OSQ_REQUIRE(workspace_bytes >= nucleus_workspace_bytes(bsz), "sample_nucleus: workspace too small");
-    OSQ_REQUIRE(logits && next_tokens && go_on && workspace, "sample_nucleus: null tensor");
-    OSQ_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 7u) == 0, "sample_nucleus: workspace not 8-byte aligned");
-    if (vocab > kSnMaxVocab) {
-        set_error("sample_nucleus: vocab %lld above %d, what one workgroup holds in registers", static_cast<long long>(vocab),
+    OSQ_REQUIRE(c.workspace_bytes >= nucleus_workspace_bytes(c.bsz), "sample_nucleus: workspace too small");
+    if (c.vocab > kSnMaxVocab) {
+        set_error("sample_nucleus: vocab %lld above %d, what one workgroup holds in registers", static_cast<long long>(c.vocab),
                   kSnMaxVocab);
         return OSQ_ERR_UNSUPPORTED;
     }
-    const auto id = [](int64_t t) { return static_cast<int>(t < 0 ? -1 : t); };
-    SampleArgs a{logits, seq, ban_ids, eos_ids, unfinished, next_tokens, go_on, uniforms, nullptr, nullptr,
-                 static_cast<unsigned int*>(workspace), logits_stride, seq_stride, pad, static_cast<unsigned long long>(seed),
-                 temperature, top_p, 0, static_cast<int>(bsz), static_cast<int>(vocab), 0, static_cast<int>(max_length),
-                 static_cast<int>(cur), static_cast<int>(ngram > kBsMaxCur ? kBsMaxCur + 1 : ngram), static_cast<int>(n_ban),
-                 static_cast<int>(n_eos), id(forced), cur_dev, static_cast<int>(cur_add),
-                 static_cast<int>(ban_below < 0 ? 0 : (ban_below > kBsMaxCur ? kBsMaxCur + 1 : ban_below)), id(forced_bos),
-                 id(forced_eos)};
+    const SampleArgs a{.s = step_args(c, 0, static_cast<unsigned int*>(c.workspace)), .uniforms = uniforms, .cands = nullptr,
+                       .partials = nullptr, .seed = seed, .temperature = temperature, .top_p = top_p, .top_k = 0};
     hipStream_t st = static_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(sample_nucleus_row_kernel, dim3(static_cast<unsigned>(bsz)), dim3(kSnThreads), 0, st, a);
-    hipLaunchKernelGGL(sample_nucleus_go_on_kernel, dim3(1), dim3(kSaGoThreads), 0, st, a);
-    return check_launch(cur_dev ? "sample_nucleus_at" : "sample_nucleus");
+    hipLaunchKernelGGL(sample_nucleus_row_kernel, dim3(static_cast<unsigned>(c.bsz)), dim3(kSnThreads), 0, st, a);
+    hipLaunchKernelGGL(sample_nucleus_go_on_kernel, dim3(1), dim3(kStepGoThreads), 0, st, a);
+    return check_launch(c.cur_dev ? "sample_nucleus_at" : "sample_nucleus");
 }
 
 extern "C" int osq_sample_nucleus(const float* logits, int64_t logits_stride, int64_t* seq, int64_t seq_stride, int64_t cur,
@@ -342,9 +315,11 @@ extern "C" int osq_sample_nucleus(const float* logits, int64_t logits_stride, in
                                   int64_t max_length, int64_t* next_tokens, int32_t* go_on, void* workspace,
                                   size_t workspace_bytes, uint64_t seed, float temperature, float top_p, const float* uniforms,
                                   osq_stream stream) {
-    return sample_nucleus_launch(logits, logits_stride, seq, seq_stride, cur, nullptr, 0, ngram, ban_ids, n_ban, 0, forced, -1,
-                                 -1, eos_ids, n_eos, pad, unfinished, bsz, vocab, max_length, next_tokens, go_on, workspace,
-                                 workspace_bytes, seed, temperature, top_p, uniforms, stream);
+    return sample_nucleus_run({.logits = logits, .logits_stride = logits_stride, .seq = seq, .seq_stride = seq_stride, .cur = cur,
+                               .ngram = ngram, .ban_ids = ban_ids, .n_ban = n_ban, .forced = forced, .eos_ids = eos_ids,
+                               .n_eos = n_eos, .pad = pad, .unfinished = unfinished, .bsz = bsz, .vocab = vocab,
+                               .max_length = max_length, .next_tokens = next_tokens, .go_on = go_on, .workspace = workspace,
+                               .workspace_bytes = workspace_bytes}, seed, temperature, top_p, uniforms, stream);
 }
 
 extern "C" int osq_sample_nucleus_at(const float* logits, int64_t logits_stride, int64_t* seq, int64_t seq_stride,
@@ -356,7 +331,10 @@ extern "C" int osq_sample_nucleus_at(const float* logits, int64_t logits_stride,
                                      const float* uniforms, osq_stream stream) {
     OSQ_REQUIRE(cur_dev, "sample_nucleus_at: null position word");
     OSQ_REQUIRE(cur_add >= INT32_MIN && cur_add <= INT32_MAX, "sample_nucleus_at: cur_add does not fit 32 bits");
-    return sample_nucleus_launch(logits, logits_stride, seq, seq_stride, 0, cur_dev, cur_add, ngram, ban_ids, n_ban, ban_below,
-                                 -1, forced_bos, forced_eos, eos_ids, n_eos, pad, unfinished, bsz, vocab, max_length,
-                                 next_tokens, go_on, workspace, workspace_bytes, seed, temperature, top_p, uniforms, stream);
+    return sample_nucleus_run({.logits = logits, .logits_stride = logits_stride, .seq = seq, .seq_stride = seq_stride,
+                               .cur_dev = cur_dev, .cur_add = cur_add, .ngram = ngram, .ban_ids = ban_ids, .n_ban = n_ban,
+                               .ban_below = ban_below, .forced_bos = forced_bos, .forced_eos = forced_eos, .eos_ids = eos_ids,
+                               .n_eos = n_eos, .pad = pad, .unfinished = unfinished, .bsz = bsz, .vocab = vocab,
+                               .max_length = max_length, .next_tokens = next_tokens, .go_on = go_on, .workspace = workspace,
+                               .workspace_bytes = workspace_bytes}, seed, temperature, top_p, uniforms, stream);
 }

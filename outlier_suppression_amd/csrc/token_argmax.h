@@ -1,6 +1,7 @@
-// What beam_select.hip and greedy_advance.hip share: a row of logits cut into chunks of kBsChunk tokens, one 256-thread
-// workgroup per (row, chunk) holding 16 values per thread; the 64-bit candidate key; the workgroup arg-max over such keys; and
-// the chunk's bitmap of banned tokens (the min-length ids and the no-repeat-ngram rule).
+// What beam_select.hip, greedy_advance.hip and the sampling files share: a row of logits cut into chunks of kBsChunk tokens, one
+// 256-thread workgroup per (row, chunk) holding 16 values per thread; the 64-bit candidate key; the workgroup arg-max over such
+// keys; the chunk's bitmap of banned tokens (the min-length ids and the no-repeat-ngram rule); and the load of a chunk's values
+// over the search for its bans (chunk_each).
 //
 // Order of a key: larger value first, NaN above every number; the low word carries ~position, so that among equal values the
 // smaller position wins and the arg-max is a max of (hi, lo) pairs.  Key 0 is no value's (-inf has 0x007fffff): it marks a
@@ -72,6 +73,28 @@ __device__ __forceinline__ void span_bans(unsigned int* s_ban, const int64_t* ba
 __device__ __forceinline__ void chunk_bans(unsigned int* s_ban, const int64_t* ban_ids, int n_ban, const int64_t* s, int cur,
                                            int n, int c0, int len) {
     span_bans<kBsThreads, kBsChunk / 32>(s_ban, ban_ids, n_ban, s, cur, n, c0, len);
+}
+
+// The chunk [c0, c0 + len) of a row, x at its first token, through a kBsThreads workgroup: kBsPer values per thread, one 32-bit
+// word per lane (a row of an odd vocab is only 4-byte aligned), issued before the bans are found -- the loads fly meanwhile
+// -- then chunk_bans, a barrier, and keep(j, i, value, banned, in range) for the thread's elements i = threadIdx.x + j *
+// kBsThreads in order; past the chunk the value is 0.f.
+template <typename Keep>
+__device__ __forceinline__ void chunk_each(const float* x, unsigned int* s_ban, const int64_t* ban_ids, int n_ban,
+                                           const int64_t* s, int cur, int n, int c0, int len, Keep keep) {
+    float v[kBsPer];
+#pragma unroll
+    for (int j = 0; j < kBsPer; ++j) {
+        const int i = threadIdx.x + j * kBsThreads;
+        v[j] = i < len ? x[i] : 0.f;
+    }
+    chunk_bans(s_ban, ban_ids, n_ban, s, cur, n, c0, len);
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < kBsPer; ++j) {
+        const int i = threadIdx.x + j * kBsThreads;
+        keep(j, i, v[j], ((s_ban[i >> 5] >> (i & 31)) & 1u) != 0u, i < len);
+    }
 }
 
 }  // namespace osq

@@ -2170,9 +2170,10 @@ class GreedyBuffers:
         return self.workspace
 
 
-def _greedy_advance_operands(what, logits, buffers, ban_ids, eos_ids):
-    """The checks greedy_advance and greedy_advance_at share; (head, tail): the arguments before the position and from
-    eos_ids on."""
+def _advance_operands(what, logits, buffers, ban_ids, eos_ids):
+    """The checks every advance call shares, and its arguments but the position, the settings and the draw: (head, (n_ban,
+    n_eos), state, outputs, stream) -- logits and seq with their strides; unfinished and the shape; next_tokens, go_on and
+    the workspace."""
     seq, unfinished, next_tokens, go_on = buffers.seq, buffers.unfinished, buffers.next_tokens, buffers.go_on
     _hip.require_device(logits, seq, unfinished, next_tokens, go_on, ban_ids, eos_ids)
     _check_f32(logits)
@@ -2200,8 +2201,52 @@ def _greedy_advance_operands(what, logits, buffers, ban_ids, eos_ids):
         raise ValueError(f"{what}: all tensors must be on one device")
     ws = buffers.room(vocab)
     head = (logits.data_ptr(), logits.stride(0) if bsz > 1 else vocab, seq.data_ptr(), seq.stride(0) if bsz > 1 else max_length)
-    return head, counts, (bsz, vocab, max_length, next_tokens.data_ptr(), go_on.data_ptr(), ws.data_ptr(), ws.numel(),
-                          _hip.raw_stream(device))
+    state = (unfinished.data_ptr(), bsz, vocab, max_length)
+    return head, counts, state, (next_tokens.data_ptr(), go_on.data_ptr(), ws.data_ptr(), ws.numel()), _hip.raw_stream(device)
+
+
+def _advance(family, at, logits, buffers, cur, cur_add, ngram, ban_ids, ban_below, forced, eos_ids, pad, draw=None):
+    """The call path of greedy_advance, sample_advance, sample_nucleus and (``at``) their _at forms: the checks, the arguments
+    in the C ABI's order, the call, and None for a call the library does not take.  ``cur`` is the position or, ``at``, the
+    device word, to which ``cur_add`` and ``ban_below`` belong; ``forced`` is the static form's token or the _at form's
+    (forced_bos, forced_eos); ``draw`` is a sampling family's (seed, temperature, top_k, top_p, uniforms), of which
+    sample_nucleus passes no top_k on."""
+    what = family + ("_at" if at else "")
+    lib = _hip.load()
+    if draw is not None:
+        seed, temperature, top_k, top_p, uniforms = draw
+        top_k = int(top_k)
+        if not 0 <= top_k <= 64:                     # the workspace's size follows it: refused before one is sized
+            raise ValueError(f"{what}: top_k must lie in [0, 64]")
+        if not isinstance(buffers, SampleBuffers):
+            raise TypeError(f"{what}: buffers must be an ops.SampleBuffers")
+        buffers.top_k = max(buffers.top_k, top_k)
+        buffers.nucleus = buffers.nucleus or family == "sample_nucleus"
+    head, (n_ban, n_eos), state, outputs, stream = _advance_operands(what, logits, buffers, ban_ids, eos_ids)
+    if draw is not None:
+        if uniforms is not None:
+            _hip.require_device(uniforms)
+            if (uniforms.dtype != torch.float32 or tuple(uniforms.shape) != (logits.shape[0],) or not uniforms.is_contiguous()
+                    or uniforms.device != logits.device):
+                raise ValueError(f"{what}: uniforms must be a contiguous float32 [bsz] tensor on the device of logits")
+        draw = (int(seed) & 0xFFFFFFFFFFFFFFFF, float(temperature), *((top_k,) if family == "sample_advance" else ()),
+                float(top_p), _hip.ptr(uniforms))
+    ban, eos = (_hip.ptr(ban_ids) if n_ban else None, n_ban), (_hip.ptr(eos_ids) if n_eos else None, n_eos)
+    token = lambda t: -1 if t is None else int(t)    # noqa: E731
+    if at:
+        _hip.require_device(cur)
+        if cur.dtype != torch.int32 or cur.numel() != 1 or cur.device != logits.device:
+            raise TypeError(f"{what}: cur must be one int32 on the device of logits")
+        position = (cur.data_ptr(), int(cur_add))
+        settings = (int(ngram), *ban, int(ban_below), token(forced[0]), token(forced[1]), *eos, int(pad))
+    else:
+        position = (int(cur),)
+        settings = (int(ngram), *ban, token(forced), *eos, int(pad))
+    rc = getattr(lib, "osq_" + what)(*head, *position, *settings, *state, *outputs, *(draw or ()), stream)
+    if rc == _hip.ERR_UNSUPPORTED:
+        return None
+    _hip.check(rc, what)
+    return buffers
 
 
 def greedy_advance(logits, buffers, cur, ngram=0, ban_ids=None, forced=None, eos_ids=None, pad=0):
@@ -2213,15 +2258,7 @@ def greedy_advance(logits, buffers, cur, ngram=0, ban_ids=None, forced=None, eos
     ``buffers.next_tokens`` and the ``buffers.go_on`` word: what generation._greedy computes, token for token.
     Three launches on the current stream, no synchronisation; returns ``buffers``, or None when the library does not take
     the call (the caller takes its other path)."""
-    lib = _hip.load()
-    head, (n_ban, n_eos), tail = _greedy_advance_operands("greedy_advance", logits, buffers, ban_ids, eos_ids)
-    rc = lib.osq_greedy_advance(*head, int(cur), int(ngram), _hip.ptr(ban_ids) if n_ban else None, n_ban,
-                                -1 if forced is None else int(forced), _hip.ptr(eos_ids) if n_eos else None, n_eos, int(pad),
-                                buffers.unfinished.data_ptr(), *tail)
-    if rc == _hip.ERR_UNSUPPORTED:
-        return None
-    _hip.check(rc, "greedy_advance")
-    return buffers
+    return _advance("greedy_advance", False, logits, buffers, cur, 0, ngram, ban_ids, 0, forced, eos_ids, pad)
 
 
 def greedy_advance_at(logits, buffers, cur, cur_add=0, ngram=0, ban_ids=None, ban_below=0, forced_bos=None, forced_eos=None,
@@ -2231,19 +2268,8 @@ def greedy_advance_at(logits, buffers, cur, cur_add=0, ngram=0, ban_ids=None, ba
     the length is below ``ban_below`` (the min-length rule), ``forced_bos`` is the token at length 1 and ``forced_eos`` the
     token at length max_length - 1 (it wins where both fire).  For a length in [1, max_length) everything written is word-equal
     to ``greedy_advance`` at that length; outside it ``buffers.go_on`` receives -1 and nothing else is written."""
-    lib = _hip.load()
-    head, (n_ban, n_eos), tail = _greedy_advance_operands("greedy_advance_at", logits, buffers, ban_ids, eos_ids)
-    _hip.require_device(cur)
-    if cur.dtype != torch.int32 or cur.numel() != 1 or cur.device != logits.device:
-        raise TypeError("greedy_advance_at: cur must be one int32 on the device of logits")
-    rc = lib.osq_greedy_advance_at(*head, cur.data_ptr(), int(cur_add), int(ngram), _hip.ptr(ban_ids) if n_ban else None, n_ban,
-                                   int(ban_below), -1 if forced_bos is None else int(forced_bos),
-                                   -1 if forced_eos is None else int(forced_eos), _hip.ptr(eos_ids) if n_eos else None, n_eos,
-                                   int(pad), buffers.unfinished.data_ptr(), *tail)
-    if rc == _hip.ERR_UNSUPPORTED:
-        return None
-    _hip.check(rc, "greedy_advance_at")
-    return buffers
+    return _advance("greedy_advance", True, logits, buffers, cur, cur_add, ngram, ban_ids, ban_below, (forced_bos, forced_eos),
+                    eos_ids, pad)
 
 
 class SampleBuffers(GreedyBuffers):
@@ -2265,24 +2291,6 @@ class SampleBuffers(GreedyBuffers):
         return self.workspace
 
 
-def _sample_advance_operands(what, logits, buffers, ban_ids, eos_ids, seed, temperature, top_k, top_p, uniforms):
-    """_greedy_advance_operands, and the arguments after the workspace: (head, counts, tail) with the stream last."""
-    top_k = int(top_k)
-    if not 0 <= top_k <= 64:                         # the workspace's size follows it: refused before one is sized
-        raise ValueError(f"{what}: top_k must lie in [0, 64]")
-    if not isinstance(buffers, SampleBuffers):
-        raise TypeError(f"{what}: buffers must be an ops.SampleBuffers")
-    buffers.top_k = max(buffers.top_k, top_k)
-    head, counts, tail = _greedy_advance_operands(what, logits, buffers, ban_ids, eos_ids)
-    if uniforms is not None:
-        _hip.require_device(uniforms)
-        if (uniforms.dtype != torch.float32 or tuple(uniforms.shape) != (logits.shape[0],) or not uniforms.is_contiguous()
-                or uniforms.device != logits.device):
-            raise ValueError(f"{what}: uniforms must be a contiguous float32 [bsz] tensor on the device of logits")
-    draw = (int(seed) & 0xFFFFFFFFFFFFFFFF, float(temperature), top_k, float(top_p), _hip.ptr(uniforms))
-    return head, counts, tail[:-1] + draw + tail[-1:]
-
-
 def sample_advance(logits, buffers, cur, seed, temperature=1.0, top_k=0, top_p=1.0, ngram=0, ban_ids=None, forced=None,
                    eos_ids=None, pad=0, uniforms=None):
     """One sampling step after the model (osq_sample_advance, csrc/sample_advance.hip): ``greedy_advance`` with a seeded
@@ -2294,16 +2302,8 @@ def sample_advance(logits, buffers, cur, seed, temperature=1.0, top_k=0, top_p=1
     ``buffers.go_on``.  Three launches on the current stream, no synchronisation; returns ``buffers``, or None when the
     library does not take the call (top_k == 0 with top_p < 1: the caller takes its other path -- ``sample_nucleus`` below,
     where it asked for that kernel, else its torch lines)."""
-    lib = _hip.load()
-    head, (n_ban, n_eos), tail = _sample_advance_operands("sample_advance", logits, buffers, ban_ids, eos_ids, seed,
-                                                          temperature, top_k, top_p, uniforms)
-    rc = lib.osq_sample_advance(*head, int(cur), int(ngram), _hip.ptr(ban_ids) if n_ban else None, n_ban,
-                                -1 if forced is None else int(forced), _hip.ptr(eos_ids) if n_eos else None, n_eos, int(pad),
-                                buffers.unfinished.data_ptr(), *tail)
-    if rc == _hip.ERR_UNSUPPORTED:
-        return None
-    _hip.check(rc, "sample_advance")
-    return buffers
+    return _advance("sample_advance", False, logits, buffers, cur, 0, ngram, ban_ids, 0, forced, eos_ids, pad,
+                    (seed, temperature, top_k, top_p, uniforms))
 
 
 def sample_advance_at(logits, buffers, cur, seed, cur_add=0, temperature=1.0, top_k=0, top_p=1.0, ngram=0, ban_ids=None,
@@ -2313,29 +2313,8 @@ def sample_advance_at(logits, buffers, cur, seed, cur_add=0, temperature=1.0, to
     The seed is an argument and the generator has no state, so a captured graph of the call serves every step.  For a length
     in [1, max_length) everything written is word-equal to ``sample_advance`` at that length; outside it ``buffers.go_on``
     receives -1 and nothing else is written."""
-    lib = _hip.load()
-    head, (n_ban, n_eos), tail = _sample_advance_operands("sample_advance_at", logits, buffers, ban_ids, eos_ids, seed,
-                                                          temperature, top_k, top_p, uniforms)
-    _hip.require_device(cur)
-    if cur.dtype != torch.int32 or cur.numel() != 1 or cur.device != logits.device:
-        raise TypeError("sample_advance_at: cur must be one int32 on the device of logits")
-    rc = lib.osq_sample_advance_at(*head, cur.data_ptr(), int(cur_add), int(ngram), _hip.ptr(ban_ids) if n_ban else None, n_ban,
-                                   int(ban_below), -1 if forced_bos is None else int(forced_bos),
-                                   -1 if forced_eos is None else int(forced_eos), _hip.ptr(eos_ids) if n_eos else None, n_eos,
-                                   int(pad), buffers.unfinished.data_ptr(), *tail)
-    if rc == _hip.ERR_UNSUPPORTED:
-        return None
-    _hip.check(rc, "sample_advance_at")
-    return buffers
-
-
-def _sample_nucleus_operands(what, logits, buffers, ban_ids, eos_ids, seed, temperature, top_p, uniforms):
-    """_sample_advance_operands without top_k, over a workspace sized by osq_sample_nucleus_workspace_bytes."""
-    if not isinstance(buffers, SampleBuffers):
-        raise TypeError(f"{what}: buffers must be an ops.SampleBuffers")
-    buffers.nucleus = True
-    head, counts, tail = _sample_advance_operands(what, logits, buffers, ban_ids, eos_ids, seed, temperature, 0, top_p, uniforms)
-    return head, counts, tail[:-4] + tail[-3:]
+    return _advance("sample_advance", True, logits, buffers, cur, cur_add, ngram, ban_ids, ban_below, (forced_bos, forced_eos),
+                    eos_ids, pad, (seed, temperature, top_k, top_p, uniforms))
 
 
 def sample_nucleus(logits, buffers, cur, seed, temperature=1.0, top_p=1.0, ngram=0, ban_ids=None, forced=None, eos_ids=None,
@@ -2347,16 +2326,8 @@ def sample_nucleus(logits, buffers, cur, seed, temperature=1.0, top_p=1.0, ngram
     registers, without a sort (the rule: include/osq_hip.h).  Bans, ``forced``, pad / eos, ``buffers.seq[:, cur]``,
     ``buffers.next_tokens``, ``buffers.go_on`` and the uniforms are sample_advance's.  Two launches on the current stream, no
     synchronisation; returns ``buffers``, or None when the library does not take the call (a vocabulary above 51200)."""
-    lib = _hip.load()
-    head, (n_ban, n_eos), tail = _sample_nucleus_operands("sample_nucleus", logits, buffers, ban_ids, eos_ids, seed,
-                                                          temperature, top_p, uniforms)
-    rc = lib.osq_sample_nucleus(*head, int(cur), int(ngram), _hip.ptr(ban_ids) if n_ban else None, n_ban,
-                                -1 if forced is None else int(forced), _hip.ptr(eos_ids) if n_eos else None, n_eos, int(pad),
-                                buffers.unfinished.data_ptr(), *tail)
-    if rc == _hip.ERR_UNSUPPORTED:
-        return None
-    _hip.check(rc, "sample_nucleus")
-    return buffers
+    return _advance("sample_nucleus", False, logits, buffers, cur, 0, ngram, ban_ids, 0, forced, eos_ids, pad,
+                    (seed, temperature, 0, top_p, uniforms))
 
 
 def sample_nucleus_at(logits, buffers, cur, seed, cur_add=0, temperature=1.0, top_p=1.0, ngram=0, ban_ids=None, ban_below=0,
@@ -2365,20 +2336,8 @@ def sample_nucleus_at(logits, buffers, cur, seed, cur_add=0, temperature=1.0, to
     the step is taken at length ``*cur + cur_add``; everything else as sample_advance_at.  For a length in [1, max_length)
     everything written is word-equal to ``sample_nucleus`` at that length; outside it ``buffers.go_on`` receives -1 and
     nothing else is written."""
-    lib = _hip.load()
-    head, (n_ban, n_eos), tail = _sample_nucleus_operands("sample_nucleus_at", logits, buffers, ban_ids, eos_ids, seed,
-                                                          temperature, top_p, uniforms)
-    _hip.require_device(cur)
-    if cur.dtype != torch.int32 or cur.numel() != 1 or cur.device != logits.device:
-        raise TypeError("sample_nucleus_at: cur must be one int32 on the device of logits")
-    rc = lib.osq_sample_nucleus_at(*head, cur.data_ptr(), int(cur_add), int(ngram), _hip.ptr(ban_ids) if n_ban else None, n_ban,
-                                   int(ban_below), -1 if forced_bos is None else int(forced_bos),
-                                   -1 if forced_eos is None else int(forced_eos), _hip.ptr(eos_ids) if n_eos else None, n_eos,
-                                   int(pad), buffers.unfinished.data_ptr(), *tail)
-    if rc == _hip.ERR_UNSUPPORTED:
-        return None
-    _hip.check(rc, "sample_nucleus_at")
-    return buffers
+    return _advance("sample_nucleus", True, logits, buffers, cur, cur_add, ngram, ban_ids, ban_below, (forced_bos, forced_eos),
+                    eos_ids, pad, (seed, temperature, 0, top_p, uniforms))
 
 
 def sample_uniforms(seed, bsz, cur, device):
