@@ -45,7 +45,8 @@ typedef void* osq_stream;
  *     osq_beam_select_at, osq_beam_advance_at, osq_greedy_advance_workspace_bytes, osq_greedy_advance,
  *     osq_greedy_advance_at, osq_sample_advance_workspace_bytes, osq_sample_advance, osq_sample_advance_at,
  *     osq_sample_uniforms, osq_sample_nucleus_workspace_bytes, osq_sample_nucleus, osq_sample_nucleus_at,
- *     osq_decode_attention_shared, osq_decode_attention_shared_codes. */
+ *     osq_decode_attention_shared, osq_decode_attention_shared_codes, osq_sample_advance_group, osq_sample_advance_group_at,
+ *     osq_sample_nucleus_group, osq_sample_nucleus_group_at, osq_sample_uniforms_group. */
 #define OSQ_ABI_VERSION 10
 
 typedef enum osq_status {
@@ -1123,6 +1124,43 @@ int osq_sample_advance_at(const float* logits, int64_t logits_stride, int64_t* s
  * function as the step's. */
 int osq_sample_uniforms(uint64_t seed, int64_t bsz, int64_t cur, float* out, osq_stream stream);
 
+/* Several sequences per input, and the log-probability of every drawn token.  The four _group entry points take the argument
+ * list of their namesakes (osq_sample_advance, _at, osq_sample_nucleus, _at) and, before the stream, `group`, `logprobs` and
+ * `logprobs_stride`; the namesakes are these with group = 1 and logprobs = NULL.
+ *     Rows and groups.  A launch serves bsz = B * G rows; row r is sequence j = r % G of input b = r / G.  G is `group`,
+ *         G >= 1 and bsz % G == 0.
+ *     The uniform of row r at history length cur is word 0 of Philox4x32-10 with key (seed lo, seed hi) and counter
+ *         (b, cur, j, 0), its top 24 bits times 2^-24 (or uniforms[r], bsz values, when given).  With G == 1 this is the
+ *         counter (b, cur, 0, 0) above, bit for bit.  A row's draws depend on (seed, b, j, cur) alone: not on G, B or the
+ *         launch shape.  Everything else of the step is the namesake's, word for word.
+ *     The log-probability: `logprobs` is NULL or fp32, bsz rows logprobs_stride floats apart.  The launch that ends row r
+ *         writes the word [r, cur] and no other word of the buffer:
+ *             a draw                    lp = (z_tok - m) - logf(W), the first term 0 where z_tok == m (m = +inf included); z, m
+ *                                       and W are the fp32 values named above, W the total of the KEPT survivors after top-k /
+ *                                       top-p in the kernel's fixed order: the log of the probability with which the rule
+ *                                       drew the token
+ *             a forced step             0
+ *             a row finished before     0 (its token is the pad)
+ *             a row without a survivor  -inf
+ *         With logprobs == NULL nothing is computed or stored for it; passing a buffer changes no other output word.
+ * OSQ_ERR_INVALID_ARGUMENT, nothing launched: what the namesake refuses, group < 1, bsz % group != 0, logprobs given with
+ * logprobs_stride < max_length.  osq_sample_uniforms_group: out[r] = the u of row r, r in [0, bsz), under this rule. */
+int osq_sample_advance_group(const float* logits, int64_t logits_stride, int64_t* seq, int64_t seq_stride, int64_t cur,
+                             int64_t ngram, const int64_t* ban_ids, int64_t n_ban, int64_t forced, const int64_t* eos_ids,
+                             int64_t n_eos, int64_t pad, uint8_t* unfinished, int64_t bsz, int64_t vocab, int64_t max_length,
+                             int64_t* next_tokens, int32_t* go_on, void* workspace, size_t workspace_bytes, uint64_t seed,
+                             float temperature, int64_t top_k, float top_p, const float* uniforms, int64_t group,
+                             float* logprobs, int64_t logprobs_stride, osq_stream stream);
+int osq_sample_advance_group_at(const float* logits, int64_t logits_stride, int64_t* seq, int64_t seq_stride,
+                                const int32_t* cur_dev, int64_t cur_add, int64_t ngram, const int64_t* ban_ids, int64_t n_ban,
+                                int64_t ban_below, int64_t forced_bos, int64_t forced_eos, const int64_t* eos_ids,
+                                int64_t n_eos, int64_t pad, uint8_t* unfinished, int64_t bsz, int64_t vocab,
+                                int64_t max_length, int64_t* next_tokens, int32_t* go_on, void* workspace,
+                                size_t workspace_bytes, uint64_t seed, float temperature, int64_t top_k, float top_p,
+                                const float* uniforms, int64_t group, float* logprobs, int64_t logprobs_stride,
+                                osq_stream stream);
+int osq_sample_uniforms_group(uint64_t seed, int64_t bsz, int64_t group, int64_t cur, float* out, osq_stream stream);
+
 /* ------------------------------------------------------------------ a nucleus over the whole vocabulary (sample_nucleus.hip) */
 
 /* One sampling step after the model for top_k == 0 and top_p <= 1, the form osq_sample_advance refuses: every token left is
@@ -1177,6 +1215,22 @@ int osq_sample_nucleus_at(const float* logits, int64_t logits_stride, int64_t* s
                           int64_t pad, uint8_t* unfinished, int64_t bsz, int64_t vocab, int64_t max_length,
                           int64_t* next_tokens, int32_t* go_on, void* workspace, size_t workspace_bytes, uint64_t seed,
                           float temperature, float top_p, const float* uniforms, osq_stream stream);
+
+/* osq_sample_nucleus and osq_sample_nucleus_at for several sequences per input and with the drawn token's log-probability:
+ * the rule is stated under "seeded sampling" above.  W is S(k*) + float(r) * w(k*), z_tok the value of the key kv. */
+int osq_sample_nucleus_group(const float* logits, int64_t logits_stride, int64_t* seq, int64_t seq_stride, int64_t cur,
+                             int64_t ngram, const int64_t* ban_ids, int64_t n_ban, int64_t forced, const int64_t* eos_ids,
+                             int64_t n_eos, int64_t pad, uint8_t* unfinished, int64_t bsz, int64_t vocab, int64_t max_length,
+                             int64_t* next_tokens, int32_t* go_on, void* workspace, size_t workspace_bytes, uint64_t seed,
+                             float temperature, float top_p, const float* uniforms, int64_t group, float* logprobs,
+                             int64_t logprobs_stride, osq_stream stream);
+int osq_sample_nucleus_group_at(const float* logits, int64_t logits_stride, int64_t* seq, int64_t seq_stride,
+                                const int32_t* cur_dev, int64_t cur_add, int64_t ngram, const int64_t* ban_ids, int64_t n_ban,
+                                int64_t ban_below, int64_t forced_bos, int64_t forced_eos, const int64_t* eos_ids,
+                                int64_t n_eos, int64_t pad, uint8_t* unfinished, int64_t bsz, int64_t vocab,
+                                int64_t max_length, int64_t* next_tokens, int32_t* go_on, void* workspace,
+                                size_t workspace_bytes, uint64_t seed, float temperature, float top_p, const float* uniforms,
+                                int64_t group, float* logprobs, int64_t logprobs_stride, osq_stream stream);
 
 /* ------------------------------------------------------------------ bf16 / fp16 only (lowp.hip) */
 

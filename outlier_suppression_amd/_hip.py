@@ -197,6 +197,15 @@ SIGNATURES = {
                                 ctypes.c_uint64, _F, _F, _P, _P]),
     "osq_sample_nucleus_at": (_I, [_P, _L, _P, _L, _P, _L, _L, _P, _L, _L, _L, _L, _P, _L, _L, _P, _L, _L, _L, _P, _P, _P,
                                    ctypes.c_size_t, ctypes.c_uint64, _F, _F, _P, _P]),
+    "osq_sample_advance_group": (_I, [_P, _L, _P, _L, _L, _L, _P, _L, _L, _P, _L, _L, _P, _L, _L, _L, _P, _P, _P,
+                                      ctypes.c_size_t, ctypes.c_uint64, _F, _L, _F, _P, _L, _P, _L, _P]),
+    "osq_sample_advance_group_at": (_I, [_P, _L, _P, _L, _P, _L, _L, _P, _L, _L, _L, _L, _P, _L, _L, _P, _L, _L, _L, _P, _P, _P,
+                                         ctypes.c_size_t, ctypes.c_uint64, _F, _L, _F, _P, _L, _P, _L, _P]),
+    "osq_sample_nucleus_group": (_I, [_P, _L, _P, _L, _L, _L, _P, _L, _L, _P, _L, _L, _P, _L, _L, _L, _P, _P, _P,
+                                      ctypes.c_size_t, ctypes.c_uint64, _F, _F, _P, _L, _P, _L, _P]),
+    "osq_sample_nucleus_group_at": (_I, [_P, _L, _P, _L, _P, _L, _L, _P, _L, _L, _L, _L, _P, _L, _L, _P, _L, _L, _L, _P, _P, _P,
+                                         ctypes.c_size_t, ctypes.c_uint64, _F, _F, _P, _L, _P, _L, _P]),
+    "osq_sample_uniforms_group": (_I, [ctypes.c_uint64, _L, _L, _L, _P, _P]),
     "osq_fake_quant_chain_lowp": (_I, [_I, _P, _P, _L, _P, _P, _I, _I, _I, _P]),
     "osq_fake_quant_chain_backward_lowp": (_I, [_I, _P, _P, _P, _L, _P, _P, _I, _I, _I, _P]),
     "osq_fake_quant_per_tensor_widen": (_I, [_I, _P, _P, _L, _P, _P, _I, _I, _F, _I, _I, _P]),

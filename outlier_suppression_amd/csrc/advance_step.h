@@ -47,10 +47,13 @@ __device__ __forceinline__ Step step_of(const StepArgs& a) {
 }
 
 // The end of row b in one thread: the pad of a finished row, the eos test, seq[b, cur], next_tokens[b] and the row's flag.
-__device__ __forceinline__ void finish_row(const StepArgs& a, const Step& step, int64_t b, int64_t token) {
+// True where the row was finished before this step: its token is the pad.
+__device__ __forceinline__ bool finish_row(const StepArgs& a, const Step& step, int64_t b, int64_t token) {
     unsigned int unfinished = 1u;
+    bool padded = false;
     if (a.n_eos > 0) {
         unfinished = a.unfinished[b] != 0;
+        padded = !unfinished;
         if (!unfinished) token = a.pad;
         for (int e = 0; e < a.n_eos; ++e) unfinished &= token != a.eos_ids[e];
         a.unfinished[b] = static_cast<uint8_t>(unfinished);
@@ -58,6 +61,7 @@ __device__ __forceinline__ void finish_row(const StepArgs& a, const Step& step, 
     if (a.seq) a.seq[b * a.seq_stride + step.cur] = token;
     a.next_tokens[b] = token;
     a.row_flags[b] = unfinished;
+    return padded;
 }
 
 // The stopping word, by one wave of kStepGoThreads: go_on = (cur + 1 < max_length) && (n_eos == 0 || any row unfinished); -1

@@ -31,6 +31,13 @@
 //
 // osq_sample_advance_at is the same launches with the position read by them: cur = *cur_dev + cur_add, as osq_greedy_advance_at.
 //
+// osq_sample_advance_group(_at): the rows come in groups of `group` sequences per input, row r drawing at the counter
+// (r / group, cur, r % group, 0), and -- with `logprobs` -- the thread that ends row r stores lp = (z_tok - m) - logf(W) into
+// logprobs[r, cur] from what the pick already holds (top_k >= 1: the picked key, rank 0's and the kept total; top_k == 0: the
+// row's m and total, and the token's logit read once more): 0 on a forced step and for a finished row, -inf without a
+// survivor.  No further pass over the logits, no workspace; with logprobs == nullptr nothing is computed for it.  The
+// ungrouped entry points are these with group 1 and no buffer.
+//
 // The step's arguments, the step read from the position word, the row's tail, the stopping word and the entry points' shared
 // requirements are advance_step.h's (greedy_advance.hip ends with them too); what is about the draw is sample_draw.h's.
 #include <math.h>
@@ -107,9 +114,11 @@ __global__ __launch_bounds__(kBsThreads) void sample_chunk_kernel(SampleArgs a) 
 }
 
 // The token of row b with top_k >= 1, in thread 0: the survivors by top_k rounds over the row's candidates, their weights, the
-// top-p cut and the draw u.  Every thread of the workgroup calls it.
+// top-p cut and the draw u; beside it, there too, its log-probability in `lp` (-inf for a row without a survivor).  Every
+// thread of the workgroup calls it.
 __device__ __forceinline__ int64_t sample_pick_top_k(const SampleArgs& a, int64_t b, float u, unsigned int (*s_red)[2 * kBsWaves],
-                                                     unsigned int* s_key, int* s_tok, float* s_w) {
+                                                     unsigned int* s_key, int* s_tok, float* s_w, float& lp) {
+    lp = -INFINITY;
     const int n = a.s.chunks * a.top_k;                             // among equal values slots run as tokens do
     BeamCand* cand = a.cands + b * n;
     unsigned int best = 0u, best_p = threadIdx.x;
@@ -157,15 +166,18 @@ __device__ __forceinline__ int64_t sample_pick_top_k(const SampleArgs& a, int64_
         upto += s_w[i];
         if (upto > target) { pick = i; break; }
     }
+    if (a.logprobs) lp = sample_logprob(beam_value(s_key[pick]), beam_value(s_key[0]), total);
     return s_tok[pick];
 }
 
 // The token of row b with top_k == 0, in every thread: the chunk the draw u falls into by the chunk sums, then that chunk's
-// tokens in order.  s_w: kBsChunk + kBsThreads floats; s_tot: kBsThreads; s_grp: kSaGroup.
+// tokens in order; beside it its log-probability in `lp` (-inf for a row without a survivor), from the token's own logit
+// read once more by the one thread that stores it.  s_w: kBsChunk + kBsThreads floats; s_tot: kBsThreads; s_grp: kSaGroup.
 __device__ __forceinline__ int64_t sample_pick_full(const SampleArgs& a, const Step& step, int64_t b, float u,
                                                     unsigned int* s_ban, unsigned int (*s_red)[2 * kBsWaves], float* s_w,
-                                                    float* s_tot, float* s_grp) {
+                                                    float* s_tot, float* s_grp, float& lp) {
     const float2* part = a.partials + b * a.s.chunks;
+    lp = -INFINITY;
     float m = -INFINITY;
     for (int k = 0; k < a.s.chunks; ++k) m = fmaxf(m, part[k].x);
     if (m == -INFINITY) return 0;                                   // no survivor in the row
@@ -244,7 +256,10 @@ __device__ __forceinline__ int64_t sample_pick_full(const SampleArgs& a, const S
     unsigned int lo = ~hit_i;
     block_argmax(hit, lo, s_red, 0);                                // the largest ~i: the smallest token
     block_argmax(live, live_i, s_red, 1);
-    return c0 + static_cast<int>(hit ? ~lo : live_i);               // live: the chunk's maximum weighs `scale` > 0
+    const int token = c0 + static_cast<int>(hit ? ~lo : live_i);    // live: the chunk's maximum weighs `scale` > 0
+    if (a.logprobs && threadIdx.x == 0)                             // a survivor: not banned, inside the row
+        lp = sample_logprob(sample_z(a.s.logits[b * a.s.logits_stride + token], a.temperature, false), m, total);
+    return token;
 }
 
 __global__ __launch_bounds__(kBsThreads) void sample_row_kernel(SampleArgs a) {
@@ -256,21 +271,23 @@ __global__ __launch_bounds__(kBsThreads) void sample_row_kernel(SampleArgs a) {
     __shared__ int s_tok[kSaMaxTopK];
     const Step step = step_of(a.s);
     if (step.cur < 0) return;                                       // refused: nothing written (sample_go_on_kernel says so)
-    const int64_t b = blockIdx.x;
+    const int64_t b = blockIdx.x;                                   // the row: sequence b % group of input b / group
     int64_t token = step.forced;
+    float lp = 0.f;
     if (step.forced < 0) {
-        const float u = a.uniforms ? a.uniforms[b] : sample_uniform(a.seed, static_cast<unsigned int>(b), static_cast<unsigned int>(step.cur));
-        token = a.top_k > 0 ? sample_pick_top_k(a, b, u, s_red, s_key, s_tok, s_w)
-                            : sample_pick_full(a, step, b, u, s_ban, s_red, s_w, s_tot, s_grp);
+        const float u = sample_row_uniform(a, blockIdx.x, step.cur);
+        token = a.top_k > 0 ? sample_pick_top_k(a, b, u, s_red, s_key, s_tok, s_w, lp)
+                            : sample_pick_full(a, step, b, u, s_ban, s_red, s_w, s_tot, s_grp, lp);
     }
-    if (threadIdx.x == 0) finish_row(a.s, step, b, token);
+    if (threadIdx.x == 0) sample_finish_row(a, step, b, token, lp);
 }
 
 __global__ __launch_bounds__(kStepGoThreads) void sample_go_on_kernel(SampleArgs a) { step_go_on(a.s); }
 
-__global__ __launch_bounds__(kBsThreads) void sample_uniforms_kernel(unsigned long long seed, int bsz, unsigned int cur, float* out) {
-    const int b = blockIdx.x * kBsThreads + threadIdx.x;
-    if (b < bsz) out[b] = sample_uniform(seed, static_cast<unsigned int>(b), cur);
+__global__ __launch_bounds__(kBsThreads) void sample_uniforms_kernel(unsigned long long seed, int bsz, unsigned int group,
+                                                                     unsigned int cur, float* out) {
+    const unsigned int r = blockIdx.x * kBsThreads + threadIdx.x;
+    if (r < static_cast<unsigned int>(bsz)) out[r] = sample_uniform(seed, r / group, cur, r % group);
 }
 
 static size_t sample_workspace_bytes(int64_t bsz, int64_t vocab, int64_t top_k) {
@@ -290,8 +307,10 @@ extern "C" size_t osq_sample_advance_workspace_bytes(int64_t bsz, int64_t vocab,
 
 // Both entry points: check, fill, launch.
 static int sample_advance_run(const StepCall& c, uint64_t seed, float temperature, int64_t top_k, float top_p,
-                              const float* uniforms, osq_stream stream) {
+                              const float* uniforms, osq_stream stream, int64_t group = 1, float* logprobs = nullptr,
+                              int64_t logprobs_stride = 0) {
     if (const int rc = step_check("sample_advance", c)) return rc;
+    if (const int rc = sample_group_check("sample_advance", c, group, logprobs, logprobs_stride)) return rc;
     OSQ_REQUIRE(top_k >= 0 && top_k <= kSaMaxTopK, "sample_advance: top_k outside [0, 64]");
     OSQ_REQUIRE(top_p > 0.f && top_p <= 1.f, "sample_advance: top_p outside (0, 1]");
     OSQ_REQUIRE(temperature > 0.f && temperature <= 3.4028234663852886e38f, "sample_advance: temperature not positive and finite");
@@ -306,7 +325,8 @@ static int sample_advance_run(const StepCall& c, uint64_t seed, float temperatur
     const int64_t slots = c.bsz * chunks * (top_k > 0 ? top_k : 1);
     const SampleArgs a{.s = step_args(c, chunks, reinterpret_cast<unsigned int*>(cands + slots)), .uniforms = uniforms,
                        .cands = cands, .partials = static_cast<float2*>(c.workspace), .seed = seed, .temperature = temperature,
-                       .top_p = top_p, .top_k = static_cast<int>(top_k)};
+                       .top_p = top_p, .top_k = static_cast<int>(top_k), .group = static_cast<int>(group), .logprobs = logprobs,
+                       .logprobs_stride = logprobs_stride};
     hipStream_t st = static_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(sample_chunk_kernel, dim3(static_cast<unsigned>(c.bsz * chunks)), dim3(kBsThreads), 0, st, a);
     hipLaunchKernelGGL(sample_row_kernel, dim3(static_cast<unsigned>(c.bsz)), dim3(kBsThreads), 0, st, a);
@@ -344,12 +364,51 @@ extern "C" int osq_sample_advance_at(const float* logits, int64_t logits_stride,
                                .workspace_bytes = workspace_bytes}, seed, temperature, top_k, top_p, uniforms, stream);
 }
 
-extern "C" int osq_sample_uniforms(uint64_t seed, int64_t bsz, int64_t cur, float* out, osq_stream stream) {
+extern "C" int osq_sample_advance_group(const float* logits, int64_t logits_stride, int64_t* seq, int64_t seq_stride,
+                                        int64_t cur, int64_t ngram, const int64_t* ban_ids, int64_t n_ban, int64_t forced,
+                                        const int64_t* eos_ids, int64_t n_eos, int64_t pad, uint8_t* unfinished, int64_t bsz,
+                                        int64_t vocab, int64_t max_length, int64_t* next_tokens, int32_t* go_on,
+                                        void* workspace, size_t workspace_bytes, uint64_t seed, float temperature,
+                                        int64_t top_k, float top_p, const float* uniforms, int64_t group, float* logprobs,
+                                        int64_t logprobs_stride, osq_stream stream) {
+    return sample_advance_run({.logits = logits, .logits_stride = logits_stride, .seq = seq, .seq_stride = seq_stride, .cur = cur,
+                               .ngram = ngram, .ban_ids = ban_ids, .n_ban = n_ban, .forced = forced, .eos_ids = eos_ids,
+                               .n_eos = n_eos, .pad = pad, .unfinished = unfinished, .bsz = bsz, .vocab = vocab,
+                               .max_length = max_length, .next_tokens = next_tokens, .go_on = go_on, .workspace = workspace,
+                               .workspace_bytes = workspace_bytes}, seed, temperature, top_k, top_p, uniforms, stream, group,
+                              logprobs, logprobs_stride);
+}
+
+extern "C" int osq_sample_advance_group_at(const float* logits, int64_t logits_stride, int64_t* seq, int64_t seq_stride,
+                                           const int32_t* cur_dev, int64_t cur_add, int64_t ngram, const int64_t* ban_ids,
+                                           int64_t n_ban, int64_t ban_below, int64_t forced_bos, int64_t forced_eos,
+                                           const int64_t* eos_ids, int64_t n_eos, int64_t pad, uint8_t* unfinished,
+                                           int64_t bsz, int64_t vocab, int64_t max_length, int64_t* next_tokens,
+                                           int32_t* go_on, void* workspace, size_t workspace_bytes, uint64_t seed,
+                                           float temperature, int64_t top_k, float top_p, const float* uniforms,
+                                           int64_t group, float* logprobs, int64_t logprobs_stride, osq_stream stream) {
+    OSQ_REQUIRE(cur_dev, "sample_advance_at: null position word");
+    OSQ_REQUIRE(cur_add >= INT32_MIN && cur_add <= INT32_MAX, "sample_advance_at: cur_add does not fit 32 bits");
+    return sample_advance_run({.logits = logits, .logits_stride = logits_stride, .seq = seq, .seq_stride = seq_stride,
+                               .cur_dev = cur_dev, .cur_add = cur_add, .ngram = ngram, .ban_ids = ban_ids, .n_ban = n_ban,
+                               .ban_below = ban_below, .forced_bos = forced_bos, .forced_eos = forced_eos, .eos_ids = eos_ids,
+                               .n_eos = n_eos, .pad = pad, .unfinished = unfinished, .bsz = bsz, .vocab = vocab,
+                               .max_length = max_length, .next_tokens = next_tokens, .go_on = go_on, .workspace = workspace,
+                               .workspace_bytes = workspace_bytes}, seed, temperature, top_k, top_p, uniforms, stream, group,
+                              logprobs, logprobs_stride);
+}
+
+extern "C" int osq_sample_uniforms_group(uint64_t seed, int64_t bsz, int64_t group, int64_t cur, float* out, osq_stream stream) {
     OSQ_REQUIRE(bsz >= 1 && bsz <= INT32_MAX - kBsThreads, "sample_uniforms: bsz outside [1, 2^31)");
+    OSQ_REQUIRE(group >= 1 && bsz % group == 0, "sample_uniforms: group must be at least 1 and divide bsz");
     OSQ_REQUIRE(cur >= 0 && cur <= 0xffffffffll, "sample_uniforms: cur does not fit 32 bits");
     OSQ_REQUIRE(out, "sample_uniforms: null tensor");
     hipLaunchKernelGGL(sample_uniforms_kernel, dim3(static_cast<unsigned>((bsz + kBsThreads - 1) / kBsThreads)), dim3(kBsThreads),
                        0, static_cast<hipStream_t>(stream), static_cast<unsigned long long>(seed), static_cast<int>(bsz),
-                       static_cast<unsigned int>(cur), out);
+                       static_cast<unsigned int>(group), static_cast<unsigned int>(cur), out);
     return check_launch("sample_uniforms");
+}
+
+extern "C" int osq_sample_uniforms(uint64_t seed, int64_t bsz, int64_t cur, float* out, osq_stream stream) {
+    return osq_sample_uniforms_group(seed, bsz, 1, cur, out, stream);
 }

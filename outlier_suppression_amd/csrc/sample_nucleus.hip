@@ -39,6 +39,10 @@
 // (-Rpass-analysis=kernel-resource-usage).  LDS: 102400 B of stage, 6400 B of bitmap, 128 B of reductions.
 //
 // osq_sample_nucleus_at is the same launches with the position read by them: cur = *cur_dev + cur_add, as osq_sample_advance_at.
+//
+// osq_sample_nucleus_group(_at): `group` sequences per input and the drawn token's log-probability, as
+// osq_sample_advance_group (sample_draw.h): lp = (value(kv) - m) - logf(W) with W = S(k*) + float(r) * w(k*), all of them
+// in registers when the draw ends; one more live value through the second bisection, still 128 VGPRs and no scratch.
 #include <math.h>
 #include <hip/hip_runtime.h>
 #include "osq_device.h"
@@ -149,9 +153,10 @@ __device__ __forceinline__ float sn_above(const unsigned int (&key)[kSnPer], con
     return sn_block_sum(q[0] + q[1], s_red, turn);
 }
 
-// The token of row b, in every thread.
+// The token of row b, in every thread, and its log-probability in `lp` (-inf for a row without a survivor).
 __device__ __forceinline__ int64_t sn_pick(const SampleArgs& a, const Step& step, int64_t b, float u, float* s_stage,
-                                           unsigned int* s_ban, unsigned int (*s_red)[kSnWaves]) {
+                                           unsigned int* s_ban, unsigned int (*s_red)[kSnWaves], float& lp) {
+    lp = -INFINITY;
     const int lane = threadIdx.x & (OSQ_WAVE - 1), w = threadIdx.x / OSQ_WAVE;
     const float* x = a.s.logits + b * a.s.logits_stride;
     unsigned int key[kSnPer];
@@ -225,7 +230,8 @@ __device__ __forceinline__ int64_t sn_pick(const SampleArgs& a, const Step& step
         if (s_cut + static_cast<float>(j) * w_cut < bound) yes = j; else no = j;
     }
     const unsigned int n_kept = yes + 1u;
-    const float target = u * (s_cut + static_cast<float>(n_kept) * w_cut);
+    const float kept = s_cut + static_cast<float>(n_kept) * w_cut;  // W
+    const float target = u * kept;
 
     // ---- the draw
     unsigned int hit = top;                                         // S(hit) <= target; lo: above it, or just below the cut
@@ -258,6 +264,7 @@ __device__ __forceinline__ int64_t sn_pick(const SampleArgs& a, const Step& step
         if (is && seen == want) token = threadIdx.x * kSnPer + j + 1u;
         seen += is;
     }
+    if (a.logprobs) lp = sample_logprob(beam_value(hit), m, kept);
     return sn_block_max(token, s_red, turn) - 1u;                   // one thread holds it (limit >= 1: the key is present)
 }
 
@@ -267,13 +274,14 @@ __global__ __launch_bounds__(kSnThreads) void sample_nucleus_row_kernel(SampleAr
     __shared__ unsigned int s_red[2][kSnWaves];
     const Step step = step_of(a.s);
     if (step.cur < 0) return;                                       // refused: nothing written (the go_on launch says so)
-    const int64_t b = blockIdx.x;
+    const int64_t b = blockIdx.x;                                   // the row: sequence b % group of input b / group
     int64_t token = step.forced;
+    float lp = 0.f;
     if (step.forced < 0) {                                          // a forced step reads no logit
-        const float u = a.uniforms ? a.uniforms[b] : sample_uniform(a.seed, static_cast<unsigned int>(b), static_cast<unsigned int>(step.cur));
-        token = sn_pick(a, step, b, u, s_stage, s_ban, s_red);
+        const float u = sample_row_uniform(a, blockIdx.x, step.cur);
+        token = sn_pick(a, step, b, u, s_stage, s_ban, s_red, lp);
     }
-    if (threadIdx.x == 0) finish_row(a.s, step, b, token);
+    if (threadIdx.x == 0) sample_finish_row(a, step, b, token, lp);
 }
 
 __global__ __launch_bounds__(kStepGoThreads) void sample_nucleus_go_on_kernel(SampleArgs a) { step_go_on(a.s); }
@@ -290,8 +298,9 @@ extern "C" size_t osq_sample_nucleus_workspace_bytes(int64_t bsz, int64_t vocab)
 
 // Both entry points: check, fill, launch.
 static int sample_nucleus_run(const StepCall& c, uint64_t seed, float temperature, float top_p, const float* uniforms,
-                              osq_stream stream) {
+                              osq_stream stream, int64_t group = 1, float* logprobs = nullptr, int64_t logprobs_stride = 0) {
     if (const int rc = step_check("sample_nucleus", c)) return rc;
+    if (const int rc = sample_group_check("sample_nucleus", c, group, logprobs, logprobs_stride)) return rc;
     OSQ_REQUIRE(c.bsz <= INT32_MAX, "sample_nucleus: bsz does not fit 31 bits");
     OSQ_REQUIRE(top_p > 0.f && top_p <= 1.f, "sample_nucleus: top_p outside (0, 1]");
     OSQ_REQUIRE(temperature > 0.f && temperature <= 3.4028234663852886e38f, "sample_nucleus: temperature not positive and finite");
@@ -302,7 +311,8 @@ static int sample_nucleus_run(const StepCall& c, uint64_t seed, float temperatur
         return OSQ_ERR_UNSUPPORTED;
     }
     const SampleArgs a{.s = step_args(c, 0, static_cast<unsigned int*>(c.workspace)), .uniforms = uniforms, .cands = nullptr,
-                       .partials = nullptr, .seed = seed, .temperature = temperature, .top_p = top_p, .top_k = 0};
+                       .partials = nullptr, .seed = seed, .temperature = temperature, .top_p = top_p, .top_k = 0,
+                       .group = static_cast<int>(group), .logprobs = logprobs, .logprobs_stride = logprobs_stride};
     hipStream_t st = static_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(sample_nucleus_row_kernel, dim3(static_cast<unsigned>(c.bsz)), dim3(kSnThreads), 0, st, a);
     hipLaunchKernelGGL(sample_nucleus_go_on_kernel, dim3(1), dim3(kStepGoThreads), 0, st, a);
@@ -337,4 +347,38 @@ extern "C" int osq_sample_nucleus_at(const float* logits, int64_t logits_stride,
                                .n_eos = n_eos, .pad = pad, .unfinished = unfinished, .bsz = bsz, .vocab = vocab,
                                .max_length = max_length, .next_tokens = next_tokens, .go_on = go_on, .workspace = workspace,
                                .workspace_bytes = workspace_bytes}, seed, temperature, top_p, uniforms, stream);
+}
+
+extern "C" int osq_sample_nucleus_group(const float* logits, int64_t logits_stride, int64_t* seq, int64_t seq_stride,
+                                        int64_t cur, int64_t ngram, const int64_t* ban_ids, int64_t n_ban, int64_t forced,
+                                        const int64_t* eos_ids, int64_t n_eos, int64_t pad, uint8_t* unfinished, int64_t bsz,
+                                        int64_t vocab, int64_t max_length, int64_t* next_tokens, int32_t* go_on,
+                                        void* workspace, size_t workspace_bytes, uint64_t seed, float temperature,
+                                        float top_p, const float* uniforms, int64_t group, float* logprobs,
+                                        int64_t logprobs_stride, osq_stream stream) {
+    return sample_nucleus_run({.logits = logits, .logits_stride = logits_stride, .seq = seq, .seq_stride = seq_stride, .cur = cur,
+                               .ngram = ngram, .ban_ids = ban_ids, .n_ban = n_ban, .forced = forced, .eos_ids = eos_ids,
+                               .n_eos = n_eos, .pad = pad, .unfinished = unfinished, .bsz = bsz, .vocab = vocab,
+                               .max_length = max_length, .next_tokens = next_tokens, .go_on = go_on, .workspace = workspace,
+                               .workspace_bytes = workspace_bytes}, seed, temperature, top_p, uniforms, stream, group, logprobs,
+                              logprobs_stride);
+}
+
+extern "C" int osq_sample_nucleus_group_at(const float* logits, int64_t logits_stride, int64_t* seq, int64_t seq_stride,
+                                           const int32_t* cur_dev, int64_t cur_add, int64_t ngram, const int64_t* ban_ids,
+                                           int64_t n_ban, int64_t ban_below, int64_t forced_bos, int64_t forced_eos,
+                                           const int64_t* eos_ids, int64_t n_eos, int64_t pad, uint8_t* unfinished,
+                                           int64_t bsz, int64_t vocab, int64_t max_length, int64_t* next_tokens,
+                                           int32_t* go_on, void* workspace, size_t workspace_bytes, uint64_t seed,
+                                           float temperature, float top_p, const float* uniforms, int64_t group,
+                                           float* logprobs, int64_t logprobs_stride, osq_stream stream) {
+    OSQ_REQUIRE(cur_dev, "sample_nucleus_at: null position word");
+    OSQ_REQUIRE(cur_add >= INT32_MIN && cur_add <= INT32_MAX, "sample_nucleus_at: cur_add does not fit 32 bits");
+    return sample_nucleus_run({.logits = logits, .logits_stride = logits_stride, .seq = seq, .seq_stride = seq_stride,
+                               .cur_dev = cur_dev, .cur_add = cur_add, .ngram = ngram, .ban_ids = ban_ids, .n_ban = n_ban,
+                               .ban_below = ban_below, .forced_bos = forced_bos, .forced_eos = forced_eos, .eos_ids = eos_ids,
+                               .n_eos = n_eos, .pad = pad, .unfinished = unfinished, .bsz = bsz, .vocab = vocab,
+                               .max_length = max_length, .next_tokens = next_tokens, .go_on = go_on, .workspace = workspace,
+                               .workspace_bytes = workspace_bytes}, seed, temperature, top_p, uniforms, stream, group, logprobs,
+                              logprobs_stride);
 }

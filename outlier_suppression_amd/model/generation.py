@@ -36,6 +36,9 @@ one replay and one read of the stopping word; ``model.last_greedy_graph`` tells 
 Sampling is ``sample()``, an entry point of its own (generate() promises transformers' tokens, a sampler with its own random
 stream cannot): the greedy loop with a seeded draw in the place of the arg-max (model/sampling.py), ``sample_advance=True``
 and ``sample_graph=True`` as the two greedy switches (ops.sample_advance, graph_decode.SampleStepGraph).
+``num_samples=n`` draws n sequences per input from one run of the encoder -- sequence j of input b at the Philox counter
+(b, length, j, 0) -- and, with ``share_cross_kv``, over one copy of the cross-attention keys / values per input;
+``return_logprobs=True`` returns the log of the probability with which each token was drawn beside the tokens.
 """
 import torch
 from torch import nn
@@ -538,7 +541,9 @@ def _greedy_advanced(model, enc, attention_mask, start, plan, max_length, cache,
     unfinished flags and the next tokens live in an ops.GreedyBuffers, the model is fed the kernel's next_tokens (without a
     cache: the sequence so far, a view), and the go_on word is read once per token (the one host sync of the torch lines).
     ``draw`` (sample(): dict(seed, temperature, top_k, top_p)): the same loop on ops.sample_advance and an ops.SampleBuffers;
-    with ``nucleus`` set in it (top_k == 0 with top_p < 1 under sample_nucleus) on ops.sample_nucleus.
+    with ``nucleus`` set in it (top_k == 0 with top_p < 1 under sample_nucleus) on ops.sample_nucleus.  Its ``group`` (n
+    sequences per input: the loop runs enc.shape[0] * n rows where the cache shares the cross-attention keys / values, else
+    ``enc`` came expanded) and ``logprobs`` (the steps fill the buffers' logprobs; returns (sequences, logprobs)) go to the step.
 
     ``whole`` (a graph_decode.GreedyGraphInfo; generate(greedy_graph=True)): from the third step on a step is one replay of
     a captured graph that holds all of the above (graph_decode.GreedyStepGraph), a step on which a forced token fires
@@ -548,8 +553,9 @@ def _greedy_advanced(model, enc, attention_mask, start, plan, max_length, cache,
     if draw is None:
         bufs = ops.GreedyBuffers(enc.shape[0], max_length, enc.device, model.config.vocab_size)
     else:
-        bufs = ops.SampleBuffers(enc.shape[0], max_length, enc.device, model.config.vocab_size, draw["top_k"],
-                                 nucleus=bool(draw.get("nucleus")))
+        bufs = ops.SampleBuffers(draw.get("rows", enc.shape[0]), max_length, enc.device, model.config.vocab_size, draw["top_k"],
+                                 nucleus=bool(draw.get("nucleus")), logprobs=bool(draw.get("logprobs")))
+        grouped = dict(group=draw.get("group", 1), logprobs=bufs.logprobs)
     bufs.seq[:, 0] = start
     cur = 1
     captured = None
@@ -570,10 +576,10 @@ def _greedy_advanced(model, enc, attention_mask, start, plan, max_length, cache,
                                    plan.eos, plan.pad)
             elif draw.get("nucleus"):
                 ops.sample_nucleus(logits, bufs, cur, draw["seed"], draw["temperature"], draw["top_p"], plan.ngram,
-                                   plan.ban if cur < plan.min_length else None, plan.forced(cur), plan.eos, plan.pad)
+                                   plan.ban if cur < plan.min_length else None, plan.forced(cur), plan.eos, plan.pad, **grouped)
             else:
                 ops.sample_advance(logits, bufs, cur, draw["seed"], draw["temperature"], draw["top_k"], draw["top_p"], plan.ngram,
-                                   plan.ban if cur < plan.min_length else None, plan.forced(cur), plan.eos, plan.pad)
+                                   plan.ban if cur < plan.min_length else None, plan.forced(cur), plan.eos, plan.pad, **grouped)
         cur += 1
         advance.advanced += 1
         go_on = int(bufs.go_on)
@@ -584,6 +590,8 @@ def _greedy_advanced(model, enc, attention_mask, start, plan, max_length, cache,
             break
     if whole is not None and whole.captured == 0:
         whole.reason = "the search ended before a step could be captured"
+    if draw is not None and draw.get("logprobs"):
+        return bufs.seq[:, :cur], bufs.logprobs[:, :cur]
     return bufs.seq[:, :cur]
 
 
@@ -614,15 +622,25 @@ def _sample_why_not(plan, top_k, top_p, nucleus=False, vocab=0):
 
 
 def _sample_eager(model, enc, attention_mask, start, pad, eos, procs, max_length, cache, stepper, advance, draw):
-    """_greedy with the arg-max replaced by sampling.select_torch on the host's uniforms of (seed, row, length)."""
+    """_greedy with the arg-max replaced by sampling.select_torch on the host's uniforms of (seed, input, sequence, length).
+    ``draw`` with ``logprobs``: returns (sequences, logprobs), sampling.token_logprob of every drawn token (a forced token
+    is a row's one survivor: 0), 0 for a finished row."""
     from . import sampling
-    b = enc.shape[0]
+    group = draw.get("group", 1)
+    b = draw.get("rows", enc.shape[0])
     seq = torch.full((b, 1), start, dtype=torch.long, device=enc.device)
+    lps = torch.zeros((b, 1), dtype=torch.float32, device=enc.device) if draw.get("logprobs") else None
     unfinished = torch.ones(b, dtype=torch.long, device=enc.device)
     while seq.shape[1] < max_length:
         scores = procs(seq, _step_logits(model, seq, enc, attention_mask, cache, stepper).to(torch.float32))
-        u = sampling.uniforms(draw["seed"], b, seq.shape[1])
+        u = (sampling.uniforms(draw["seed"], b // group, seq.shape[1], group) if group > 1 else
+             sampling.uniforms(draw["seed"], b, seq.shape[1]))
         nxt = sampling.select_torch(scores, u, draw["temperature"], draw["top_k"], draw["top_p"])
+        if lps is not None:
+            lp = sampling.token_logprob(scores, nxt, draw["temperature"], draw["top_k"], draw["top_p"])
+            if eos is not None:
+                lp = torch.where(unfinished.bool(), lp, torch.zeros_like(lp))
+            lps = torch.cat([lps, lp[:, None]], dim=-1)
         if eos is not None:
             nxt = nxt * unfinished + pad * (1 - unfinished)
         seq = torch.cat([seq, nxt[:, None]], dim=-1)
@@ -631,12 +649,12 @@ def _sample_eager(model, enc, attention_mask, start, pad, eos, procs, max_length
             unfinished = unfinished & ~torch.isin(nxt, eos)
             if unfinished.max() == 0:
                 break
-    return seq
+    return seq if lps is None else (seq, lps)
 
 
 def sample(model, input_ids, attention_mask=None, max_length=None, seed=None, temperature=1.0, top_k=50, top_p=1.0,
            use_cache=True, cache_codes=None, graph=None, sample_advance=None, sample_graph=None, sample_nucleus=None,
-           share_cross_kv=None, **kwargs):
+           share_cross_kv=None, num_samples=1, return_logprobs=False, **kwargs):
     """Seeded sampling over a KV cache: generate()'s greedy loop with a draw in the place of the arg-max (model/sampling.py;
     the rule is osq_sample_advance's, include/osq_hip.h).  The tokens are a function of the inputs and ``seed`` alone -- the
     package's own random stream, not torch.multinomial's, so they are not transformers' tokens: hence an entry point of its
@@ -649,14 +667,25 @@ def sample(model, input_ids, attention_mask=None, max_length=None, seed=None, te
     whole step -- token copy, model, ops.sample_advance_at -- into one graph (graph_decode.SampleStepGraph);
     ``model.last_sample_graph`` tells what happened.  ``sample_nucleus=True`` (set_sample_nucleus): under either switch,
     ``top_k=0`` with ``top_p<1`` goes to ops.sample_nucleus(_at) instead of falling back to the torch lines.
-    ``share_cross_kv`` is beam search's: sampling has one row per input, ``model.last_share_cross_kv`` says so."""
+
+    ``num_samples=n`` draws n sequences per input: [B * n, L], the rows of an input adjacent (b * n + j).  Sequence j of
+    input b draws at the Philox counter (b, length, j, 0), so a sequence depends on (seed, b, j) and the input alone, not on
+    n or the batch; the encoder runs once, on B rows.  ``share_cross_kv=True`` (set_share_cross_kv) then keeps the encoder
+    states at B rows and the cross-attention keys / values once per input (QuantizedBartCache(cross_group=n),
+    ops.decode_attention_shared), where _share_why_not has no objection (n <= 64, a cache, a source of at most 1024, ...);
+    else they are expanded and ``model.last_share_cross_kv.reason`` says why.  ``return_logprobs=True`` returns (sequences,
+    logprobs): fp32 [B * n, L], the log of the probability with which each token was drawn from its kept survivors
+    (include/osq_hip.h, "seeded sampling"); 0 at column 0, on forced steps and after an eos."""
     import math
     if kwargs.pop("synced_gpus", False):
         raise NotImplementedError("sample(): synced_gpus=True is not supported")
     if kwargs.pop("num_beams", 1) not in (None, 1):
         raise ValueError("sample(): beam sampling is not supported (num_beams must be 1)")
     if kwargs.pop("num_return_sequences", 1) not in (None, 1):
-        raise ValueError("sample(): one sequence per input (num_return_sequences must be 1)")
+        raise ValueError("sample(): num_return_sequences must be 1 -- several sequences per input are num_samples=n")
+    n = int(num_samples)
+    if n < 1:
+        raise ValueError("sample(): num_samples must be at least 1")
     kwargs.pop("do_sample", None)
     unknown = set(kwargs) - set(_DEFAULTS)
     if unknown:
@@ -685,10 +714,21 @@ def sample(model, input_ids, attention_mask=None, max_length=None, seed=None, te
     from . import graph_decode
     from .quant_bart import QuantizedBartCache
     codes = util_layernorm.CACHE_CODES if cache_codes is None else bool(cache_codes)
-    cache = QuantizedBartCache(len(model.model.decoder.layers), capacity=max_length, codes=codes) if use_cache else None
-    model.last_share_cross_kv = ShareCrossKvInfo(
-        _share_why_not(model, enc.device, use_cache, 1, enc.shape[1])
+    # one copy of the cross-attention keys / values per input, where asked for and possible: decided once, here
+    share = ShareCrossKvInfo(
+        _share_why_not(model, enc.device, use_cache, n, enc.shape[1])
         if (util_layernorm.SHARE_CROSS_KV if share_cross_kv is None else share_cross_kv) else "not asked for")
+    model.last_share_cross_kv = share
+    cache = None
+    if use_cache:
+        cache = QuantizedBartCache(len(model.model.decoder.layers), capacity=max_length, codes=codes,
+                                   cross_group=n if share.reason is None else 1)
+        cache.cross_one_launch = share.reason is None
+    if n > 1 or return_logprobs:
+        draw.update(group=n, rows=enc.shape[0] * n, logprobs=bool(return_logprobs))
+    if n > 1 and share.reason is not None:
+        enc = enc.repeat_interleave(n, dim=0)
+        attention_mask = attention_mask.repeat_interleave(n, dim=0)
     plan = _GreedyPlan(procs, enc.device, model.config.vocab_size, max_length, eos_t, pad)
     nucleus = bool(util_layernorm.SAMPLE_NUCLEUS if sample_nucleus is None else sample_nucleus)
     draw["nucleus"] = nucleus and top_k == 0 and top_p < 1.0
@@ -718,10 +758,14 @@ def sample(model, input_ids, attention_mask=None, max_length=None, seed=None, te
     if advance.reason is None:
         advance.reason = _sample_why_not(plan, top_k, top_p, nucleus, model.config.vocab_size)
     if advance.reason is None:
-        return _checked(cache, _greedy_advanced(model, enc, attention_mask, start, plan, max_length, cache, stepper, advance,
-                                                whole if whole.reason is None else None, draw))
-    return _checked(cache, _sample_eager(model, enc, attention_mask, start, pad, eos_t, procs, max_length, cache, stepper,
-                                         advance, draw))
+        out = _greedy_advanced(model, enc, attention_mask, start, plan, max_length, cache, stepper, advance,
+                               whole if whole.reason is None else None, draw)
+    else:
+        out = _sample_eager(model, enc, attention_mask, start, pad, eos_t, procs, max_length, cache, stepper, advance, draw)
+    if n > 1:                                        # every step went over one copy per input, or over one per sequence
+        steps = advance.advanced + advance.eager
+        share.shared, share.eager = (steps, 0) if share.reason is None else (0, steps)
+    return _checked(cache, out)
 
 
 def _gather(t, idx):

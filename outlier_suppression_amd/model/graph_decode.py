@@ -331,13 +331,15 @@ class SampleStepGraph(GreedyStepGraph):
     """Whole sampling steps of one sample() call as a captured graph: GreedyStepGraph over an ops.SampleBuffers, with
     ops.sample_advance_at in the place of the arg-max -- ops.sample_nucleus_at where ``draw`` has ``nucleus`` set (top_k == 0
     with top_p < 1 under sample_nucleus).  ``draw``: dict(seed, temperature, top_k, top_p), kernel arguments and constant for
-    the call; the generator is keyed by (seed, row, position) and has no state, so one graph serves every step."""
+    the call; the generator is keyed by (seed, input, sequence, position) and has no state, so one graph serves every step.
+    ``draw["group"]`` sequences per input and the buffers' ``logprobs`` go to the step as they are."""
 
     def __init__(self, decoder, info, buffers, plan, draw):
         super().__init__(decoder, info, buffers, plan)
         self.draw = draw
 
     def _advance(self, ops, logits, cur, settings):
+        settings = dict(settings, group=self.draw.get("group", 1), logprobs=self.buffers.logprobs)
         if self.draw.get("nucleus"):
             ops.sample_nucleus_at(logits, self.buffers, cur, self.draw["seed"], 0, self.draw["temperature"], self.draw["top_p"],
                                   **settings)

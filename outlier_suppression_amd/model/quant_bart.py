@@ -1067,7 +1067,11 @@ class QuantizedBartForConditionalGeneration(QuantizedModule):
         eager, reason).  ``sample_graph``: a whole step captured into one graph and replayed (None: the package switch,
         set_sample_graph; it implies ``graph`` and ``sample_advance`` for the call); ``self.last_sample_graph`` then says
         what happened (captured, replays, reason).  ``sample_nucleus`` (None: the package switch, set_sample_nucleus): under
-        either, ``top_k=0`` with ``top_p<1`` is one kernel call too (ops.sample_nucleus) instead of the torch lines."""
+        either, ``top_k=0`` with ``top_p<1`` is one kernel call too (ops.sample_nucleus) instead of the torch lines.
+        ``num_samples=n``: n sequences per input, [B * n, L] with an input's rows adjacent; the encoder runs once and, with
+        ``share_cross_kv`` (None: the package switch, set_share_cross_kv), the cross-attention keys / values are held once
+        per input (``self.last_share_cross_kv``: shared, eager, reason).  ``return_logprobs=True``: (sequences, logprobs),
+        the fp32 log-probability with which each token was drawn."""
         return generation.sample(self, input_ids, attention_mask=attention_mask, max_length=max_length, seed=seed,
                                  temperature=temperature, top_k=top_k, top_p=top_p, **kwargs)
 

@@ -2,8 +2,10 @@
 
 The random stream is the package's own, not torch.multinomial's: the uniform of batch row ``b`` at history length ``cur`` is
 word 0 of Philox4x32-10 with the key (seed & 0xffffffff, seed >> 32) and the counter (b, cur, 0, 0), its top 24 bits times
-2^-24.  The generator has no state to advance: a call is reproducible from its seed whatever the launch shape, and a captured
-graph of a step serves every step.  ``philox4x32`` and ``uniforms`` restate it in integer arithmetic on the host;
+2^-24; with several sequences per input (``group``), sequence ``j`` of input ``b`` draws at the counter (b, cur, j, 0).  The
+generator has no state to advance: a call is reproducible from its seed whatever the launch shape, and a captured graph of a
+step serves every step.  ``philox4x32`` and ``uniforms`` restate it in integer arithmetic on the host; ``token_logprob`` is
+the log of the probability with which the rule drew a token, for sample(return_logprobs=True) where the kernel does not run;
 ``select_torch`` / ``sample_step_torch`` are the rule of include/osq_hip.h (osq_sample_advance) as torch lines in fp32, fed
 those uniforms: the eager form, which serves on the CPU, under autograd and wherever the kernel does not take a call
 (``top_k > 64``; ``top_k == 0`` with ``top_p < 1`` unless ``sample_nucleus`` hands it to csrc/sample_nucleus.hip, whose rule
@@ -28,11 +30,12 @@ def philox4x32(counter, key, rounds=10):
     return c0, c1, c2, c3
 
 
-def uniforms(seed, bsz, cur):
-    """The draws of a step at history length ``cur``: fp32 [bsz] on the CPU, each (word 0 >> 8) * 2^-24, in [0, 1)."""
+def uniforms(seed, bsz, cur, group=1):
+    """The draws of a step at history length ``cur`` for ``bsz`` inputs of ``group`` sequences each: fp32 [bsz * group] on the
+    CPU, row b * group + j from the counter (b, cur, j, 0), each (word 0 >> 8) * 2^-24, in [0, 1)."""
     seed = int(seed) & 0xFFFFFFFFFFFFFFFF
     key = (seed & _MASK, seed >> 32)
-    words = [philox4x32((b, cur, 0, 0), key)[0] >> 8 for b in range(bsz)]
+    words = [philox4x32((b, cur, j, 0), key)[0] >> 8 for b in range(bsz) for j in range(group)]
     return torch.tensor(words, dtype=torch.float64).mul_(2.0 ** -24).to(torch.float32)      # 24 bits: exact in both formats
 
 
@@ -69,6 +72,36 @@ def select_torch(scores, u, temperature=1.0, top_k=0, top_p=1.0):
     pick = pick.clamp_(min=0)
     token = pick if tokens is None else tokens.gather(1, pick[:, None])[:, 0]
     return torch.where(none, 0, token)
+
+
+def token_logprob(scores, token, temperature=1.0, top_k=0, top_p=1.0):
+    """The log of the probability with which select_torch drew ``token`` [bsz] from ``scores`` [bsz, vocab]: over its kept
+    survivors, (z_tok - m) - log(W), the first term 0 where z_tok == m (m = +inf included), W the kept weights' fp32 total;
+    -inf for a row without a survivor (and for a token that is not kept).  fp32 [bsz]."""
+    vocab = scores.shape[-1]
+    neg = float("-inf")
+    z = scores / torch.full((1,), float(temperature), dtype=scores.dtype, device=scores.device)
+    z = torch.where(torch.isnan(z), neg, z)
+    tokens = torch.arange(vocab, device=scores.device)[None, :].expand_as(z)
+    if top_k > 0 or top_p < 1.0:
+        z, tokens = torch.sort(z, dim=-1, descending=True, stable=True)
+        keep = vocab if top_k == 0 else min(int(top_k), vocab)
+        z, tokens = z[:, :keep], tokens[:, :keep]
+    m = z.max(dim=-1, keepdim=True)[0]
+    alive = z > neg
+    w = torch.where(alive, torch.where(z == m, 1.0, torch.exp(z - m)), 0.0)
+    if top_p < 1.0:
+        upto = torch.cumsum(w, dim=-1)
+        stay = (upto - w) < top_p * upto[:, -1:]
+        stay[:, 0] = True
+        alive = alive & stay
+        w = torch.where(alive, w, 0.0)
+    total = torch.cumsum(w, dim=-1)[:, -1]
+    at = (tokens == token.to(scores.device)[:, None]) & alive
+    z_tok = torch.where(at, z, neg).max(dim=-1)[0]
+    m = m[:, 0]
+    lp = torch.where(z_tok == m, torch.zeros_like(m), z_tok - m) - torch.log(total)
+    return torch.where(at.any(dim=-1), lp, neg).to(torch.float32)
 
 
 def sample_step_torch(logits, seq, cur, max_length, u, temperature=1.0, top_k=0, top_p=1.0, ngram=0, ban_ids=None, forced=None,

@@ -2205,13 +2205,29 @@ def _advance_operands(what, logits, buffers, ban_ids, eos_ids):
     return head, counts, state, (next_tokens.data_ptr(), go_on.data_ptr(), ws.data_ptr(), ws.numel()), _hip.raw_stream(device)
 
 
-def _advance(family, at, logits, buffers, cur, cur_add, ngram, ban_ids, ban_below, forced, eos_ids, pad, draw=None):
+def _advance(family, at, logits, buffers, cur, cur_add, ngram, ban_ids, ban_below, forced, eos_ids, pad, draw=None, group=1,
+             logprobs=None):
     """The call path of greedy_advance, sample_advance, sample_nucleus and (``at``) their _at forms: the checks, the arguments
     in the C ABI's order, the call, and None for a call the library does not take.  ``cur`` is the position or, ``at``, the
     device word, to which ``cur_add`` and ``ban_below`` belong; ``forced`` is the static form's token or the _at form's
     (forced_bos, forced_eos); ``draw`` is a sampling family's (seed, temperature, top_k, top_p, uniforms), of which
-    sample_nucleus passes no top_k on."""
+    sample_nucleus passes no top_k on.  ``group`` / ``logprobs`` (the sampling families): anything but (1, None) goes to the
+    family's _group entry point, which takes them after the draw."""
     what = family + ("_at" if at else "")
+    grouped = ()
+    if int(group) != 1 or logprobs is not None:
+        if draw is None:
+            raise ValueError(f"{what}: group and logprobs belong to the sampling families")
+        bsz, max_length = logits.shape[0], buffers.seq.shape[1]
+        if int(group) < 1 or bsz % int(group):
+            raise ValueError(f"{what}: group must be at least 1 and divide bsz")
+        if logprobs is not None:
+            _hip.require_device(logprobs)
+            if (logprobs.dtype != torch.float32 or tuple(logprobs.shape) != (bsz, max_length) or logprobs.device != logits.device
+                    or (max_length > 1 and logprobs.stride(1) != 1) or (bsz > 1 and logprobs.stride(0) < max_length)):
+                raise ValueError(f"{what}: logprobs must be a float32 [bsz, max_length] tensor with a dense last axis on the "
+                                 "device of logits")
+        grouped = (int(group), _hip.ptr(logprobs), 0 if logprobs is None else (logprobs.stride(0) if bsz > 1 else max_length))
     lib = _hip.load()
     if draw is not None:
         seed, temperature, top_k, top_p, uniforms = draw
@@ -2242,7 +2258,8 @@ def _advance(family, at, logits, buffers, cur, cur_add, ngram, ban_ids, ban_belo
     else:
         position = (int(cur),)
         settings = (int(ngram), *ban, token(forced), *eos, int(pad))
-    rc = getattr(lib, "osq_" + what)(*head, *position, *settings, *state, *outputs, *(draw or ()), stream)
+    entry = "osq_" + (family + "_group" + ("_at" if at else "") if grouped else what)
+    rc = getattr(lib, entry)(*head, *position, *settings, *state, *outputs, *(draw or ()), *grouped, stream)
     if rc == _hip.ERR_UNSUPPORTED:
         return None
     _hip.check(rc, what)
@@ -2274,12 +2291,14 @@ def greedy_advance_at(logits, buffers, cur, cur_add=0, ngram=0, ban_ids=None, ba
 
 class SampleBuffers(GreedyBuffers):
     """GreedyBuffers for osq_sample_advance: the same state, a workspace sized for (vocab, top_k) -- and, with ``nucleus``,
-    for osq_sample_nucleus (osq_sample_nucleus_workspace_bytes) as well, so that one set of buffers serves both calls."""
+    for osq_sample_nucleus (osq_sample_nucleus_workspace_bytes) as well, so that one set of buffers serves both calls.
+    ``logprobs=True``: a zero-filled fp32 ``logprobs`` [bsz, max_length] for the steps' ``logprobs=`` (else None)."""
 
-    def __init__(self, bsz, max_length, device, vocab=None, top_k=0, nucleus=False):
+    def __init__(self, bsz, max_length, device, vocab=None, top_k=0, nucleus=False, logprobs=False):
         self.top_k = int(top_k)
         self.nucleus = bool(nucleus)
         super().__init__(bsz, max_length, device, vocab)
+        self.logprobs = torch.zeros((bsz, max_length), dtype=torch.float32, device=device) if logprobs else None
 
     def room(self, vocab):
         lib = _hip.load()
@@ -2292,7 +2311,7 @@ class SampleBuffers(GreedyBuffers):
 
 
 def sample_advance(logits, buffers, cur, seed, temperature=1.0, top_k=0, top_p=1.0, ngram=0, ban_ids=None, forced=None,
-                   eos_ids=None, pad=0, uniforms=None):
+                   eos_ids=None, pad=0, uniforms=None, *, group=1, logprobs=None):
     """One sampling step after the model (osq_sample_advance, csrc/sample_advance.hip): ``greedy_advance`` with a seeded
     draw in the place of the arg-max.  From the fp32 ``logits`` [bsz, vocab] and ``buffers`` (a SampleBuffers) at history
     length ``cur``: the banned tokens, z = logits / ``temperature``, the ``top_k`` largest (0: all; up to 64; equal values by
@@ -2301,24 +2320,30 @@ def sample_advance(logits, buffers, cur, seed, temperature=1.0, top_k=0, top_p=1
     on the device -- then greedy_advance's pad / eos arithmetic, ``buffers.seq[:, cur]``, ``buffers.next_tokens`` and
     ``buffers.go_on``.  Three launches on the current stream, no synchronisation; returns ``buffers``, or None when the
     library does not take the call (top_k == 0 with top_p < 1: the caller takes its other path -- ``sample_nucleus`` below,
-    where it asked for that kernel, else its torch lines)."""
+    where it asked for that kernel, else its torch lines).
+
+    ``group=G`` (osq_sample_advance_group; here and in the three calls below): row r is sequence r % G of input r // G and
+    draws at counter (r // G, cur, r % G), so that a sequence's draws do not depend on the launch shape.  ``logprobs``: a
+    float32 [bsz, max_length] tensor whose word [r, cur] receives the log of the probability with which the rule drew the
+    token (0 on a forced step and for a finished row, -inf for a row without a survivor); no other word of it is written."""
     return _advance("sample_advance", False, logits, buffers, cur, 0, ngram, ban_ids, 0, forced, eos_ids, pad,
-                    (seed, temperature, top_k, top_p, uniforms))
+                    (seed, temperature, top_k, top_p, uniforms), group, logprobs)
 
 
 def sample_advance_at(logits, buffers, cur, seed, cur_add=0, temperature=1.0, top_k=0, top_p=1.0, ngram=0, ban_ids=None,
-                      ban_below=0, forced_bos=None, forced_eos=None, eos_ids=None, pad=0, uniforms=None):
+                      ban_below=0, forced_bos=None, forced_eos=None, eos_ids=None, pad=0, uniforms=None, *, group=1,
+                      logprobs=None):
     """sample_advance with the position read by the launches (osq_sample_advance_at): ``cur`` is one int32 on the device and
     the step is taken at length ``*cur + cur_add``; ``ban_below``, ``forced_bos`` and ``forced_eos`` as in greedy_advance_at.
     The seed is an argument and the generator has no state, so a captured graph of the call serves every step.  For a length
     in [1, max_length) everything written is word-equal to ``sample_advance`` at that length; outside it ``buffers.go_on``
     receives -1 and nothing else is written."""
     return _advance("sample_advance", True, logits, buffers, cur, cur_add, ngram, ban_ids, ban_below, (forced_bos, forced_eos),
-                    eos_ids, pad, (seed, temperature, top_k, top_p, uniforms))
+                    eos_ids, pad, (seed, temperature, top_k, top_p, uniforms), group, logprobs)
 
 
 def sample_nucleus(logits, buffers, cur, seed, temperature=1.0, top_p=1.0, ngram=0, ban_ids=None, forced=None, eos_ids=None,
-                   pad=0, uniforms=None):
+                   pad=0, uniforms=None, *, group=1, logprobs=None):
     """One sampling step after the model from a nucleus over the whole vocabulary (osq_sample_nucleus,
     csrc/sample_nucleus.hip): ``sample_advance`` for top_k == 0 and any ``top_p`` in (0, 1].  Every token left is ranked
     (larger z first, equal z by smaller token), rank i stays iff the weights ranked above it sum below top_p of the total,
@@ -2327,26 +2352,28 @@ def sample_nucleus(logits, buffers, cur, seed, temperature=1.0, top_p=1.0, ngram
     ``buffers.next_tokens``, ``buffers.go_on`` and the uniforms are sample_advance's.  Two launches on the current stream, no
     synchronisation; returns ``buffers``, or None when the library does not take the call (a vocabulary above 51200)."""
     return _advance("sample_nucleus", False, logits, buffers, cur, 0, ngram, ban_ids, 0, forced, eos_ids, pad,
-                    (seed, temperature, 0, top_p, uniforms))
+                    (seed, temperature, 0, top_p, uniforms), group, logprobs)
 
 
 def sample_nucleus_at(logits, buffers, cur, seed, cur_add=0, temperature=1.0, top_p=1.0, ngram=0, ban_ids=None, ban_below=0,
-                      forced_bos=None, forced_eos=None, eos_ids=None, pad=0, uniforms=None):
+                      forced_bos=None, forced_eos=None, eos_ids=None, pad=0, uniforms=None, *, group=1, logprobs=None):
     """sample_nucleus with the position read by the launches (osq_sample_nucleus_at): ``cur`` is one int32 on the device and
     the step is taken at length ``*cur + cur_add``; everything else as sample_advance_at.  For a length in [1, max_length)
     everything written is word-equal to ``sample_nucleus`` at that length; outside it ``buffers.go_on`` receives -1 and
     nothing else is written."""
     return _advance("sample_nucleus", True, logits, buffers, cur, cur_add, ngram, ban_ids, ban_below, (forced_bos, forced_eos),
-                    eos_ids, pad, (seed, temperature, 0, top_p, uniforms))
+                    eos_ids, pad, (seed, temperature, 0, top_p, uniforms), group, logprobs)
 
 
-def sample_uniforms(seed, bsz, cur, device):
-    """The ``bsz`` uniforms sample_advance draws at history length ``cur`` with ``seed`` (osq_sample_uniforms): fp32 [bsz] on
-    ``device``, word-equal to model.sampling.uniforms on the host."""
+def sample_uniforms(seed, bsz, cur, device, group=1):
+    """The uniforms sample_advance draws at history length ``cur`` with ``seed`` for ``bsz`` inputs of ``group`` sequences each
+    (osq_sample_uniforms_group): fp32 [bsz * group] on ``device``, word-equal to model.sampling.uniforms on the host."""
     device = torch.device(device)
     if device.type != "cuda":
         raise RuntimeError(f"outlier_suppression_amd: tensors must live on a HIP device (got device={device}); there is no CPU path.")
-    out = torch.empty(int(bsz), dtype=torch.float32, device=device)
-    _hip.check(_hip.load().osq_sample_uniforms(int(seed) & 0xFFFFFFFFFFFFFFFF, int(bsz), int(cur), out.data_ptr(),
-                                               _hip.raw_stream(device)), "sample_uniforms")
+    if int(group) < 1:
+        raise ValueError("sample_uniforms: group must be at least 1")
+    out = torch.empty(int(bsz) * int(group), dtype=torch.float32, device=device)
+    _hip.check(_hip.load().osq_sample_uniforms_group(int(seed) & 0xFFFFFFFFFFFFFFFF, out.numel(), int(group), int(cur),
+                                                     out.data_ptr(), _hip.raw_stream(device)), "sample_uniforms")
     return out

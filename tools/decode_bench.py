@@ -68,6 +68,13 @@ beam_select=True, beam_advance=True); ``cache.nbytes()`` of both forms; and the 
 teacher-forced steps.  Every form is timed in turn within each of the --reps rounds, in one process.
 
     python tools/decode_bench.py --share-cross-kv [--out profiles/share_cross_kv_ab.txt]
+
+--sample-group: the A/B is sample(num_samples=--beams, sample_graph=True) over ONE copy of the cross-attention keys / values per
+input (share_cross_kv=True) against one copy per sequence -- what a hand-repeated batch costs --, for top_k=50 / top_p=0.95 and
+for the nucleus top_k=0 / top_p=0.9, with the fp32 and the coded cache; ``cache.nbytes()`` of both forms; and the step kernels
+alone at [batch * beams, 50265] with and without ``logprobs``.  Every form is timed in turn within each of the --reps rounds.
+
+    python tools/decode_bench.py --sample-group [--out profiles/sample_group_ab.txt]
 """
 import argparse
 import copy
@@ -1022,6 +1029,105 @@ def share_cross_kv_ab(q, ids, mask, args):
     return lines
 
 
+def sample_group_step_ab(rows, group, reps, dev, launches=50):
+    """The step kernels alone on [rows, 50265] logits, us per call (device events around ``launches`` calls), with and without
+    ``logprobs``: {label: [us]}."""
+    from outlier_suppression_amd import ops
+    vocab, max_length = 50265, 62
+    logits = torch.randn((rows, vocab), device=dev) * 3
+    forms = [("sample_advance, top_k=50 top_p=0.95", ops.sample_advance, dict(top_k=50, top_p=0.95)),
+             ("sample_nucleus, top_p=0.9", ops.sample_nucleus, dict(top_p=0.9))]
+    calls = {}
+    for label, fn, draw in forms:
+        for lp in (False, True):
+            bufs = ops.SampleBuffers(rows, max_length, dev, vocab, top_k=draw.get("top_k", 0), nucleus=True, logprobs=lp)
+            calls[f"{label}, group {group}" + (", logprobs" if lp else "")] = (
+                lambda fn=fn, bufs=bufs, draw=draw: fn(logits, bufs, 7, 12345, 1.0, **draw, group=group, logprobs=bufs.logprobs))
+    times = {label: [] for label in calls}
+    start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    for r in range(reps + 1):
+        for label, call in calls.items():
+            call()
+            start.record()
+            for _ in range(launches):
+                call()
+            stop.record()
+            torch.cuda.synchronize()
+            if r:                                   # the first round warms every form up
+                times[label].append(start.elapsed_time(stop) * 1e3 / launches)
+    return times
+
+
+def sample_group_ab(q, ids, mask, args):
+    from outlier_suppression_amd import util_layernorm as UL
+    from outlier_suppression_amd.model import quant_bart
+    n = args.beams
+    lines = [f"sample(num_samples={n}) with the cross-attention keys / values held once per input, BART-large shape (random init, "
+             f"{args.layers}+{args.layers} layers), W6A6 LSQ+ plain quantising, {args.batch} inputs x {n} samples, source {args.src}; "
+             f"every form timed in turn in each of {args.reps} rounds, one process; median [min, max]"]
+    print(lines[0], flush=True)
+
+    def emit(new):
+        lines.extend(new)
+        print("\n".join(new), flush=True)
+    draws = [("top_k=50, top_p=0.95", dict(top_k=50, top_p=0.95)), ("top_k=0, top_p=0.9 (sample_nucleus)", dict(top_k=0, top_p=0.9, sample_nucleus=True))]
+    forms = [(f"{d}, {fmt} cache, {'shared' if share else 'one copy per sequence'}", kw, codes, share)
+             for d, kw in draws for fmt, codes in (("fp32", False), ("coded", True)) for share in (False, True)]
+    made = []
+
+    class Recorded(quant_bart.QuantizedBartCache):
+        def __init__(self, *a, **k):
+            super().__init__(*a, **k)
+            del made[:]
+            made.append(self)
+    plain_cache, quant_bart.QuantizedBartCache = quant_bart.QuantizedBartCache, Recorded
+    gen = {label: [] for label, *_ in forms}
+    tokens, did, held = {}, {}, {}
+    kw = dict(attention_mask=mask, max_length=62, min_length=62, seed=2 ** 40 + 3, num_samples=n, sample_graph=True)
+    UL.FUSE_DECODE_ATTENTION = True                 # the first step, issued by the model, computes the replayed steps' words in every form
+    try:
+        with torch.no_grad():
+            for r in range(args.reps + 1):
+                for label, draw, codes, share in forms:
+                    secs, out = _timed(lambda: q.sample(ids, cache_codes=codes, share_cross_kv=share, **draw, **kw), unit=1.0)
+                    tokens[label], did[label], held[label] = out, repr(q.last_share_cross_kv), made[0].nbytes()
+                    assert (q.last_share_cross_kv.reason is None) is share and q.last_sample_graph.reason is None, (label, did[label])
+                    if r:                           # the first round warms every form up
+                        gen[label].append(secs)
+            del made[:]
+            lp_times = {}
+            for label, draw, codes, share in forms[1:4:2]:          # the shared forms of the first draw, with the log-probabilities
+                for want in (False, True):
+                    for r in range(args.reps + 1):
+                        secs, _ = _timed(lambda: q.sample(ids, cache_codes=codes, share_cross_kv=share, return_logprobs=want,
+                                                          **draw, **kw), unit=1.0)
+                        if r:
+                            lp_times.setdefault(label + (", return_logprobs" if want else ""), []).append(secs)
+            del made[:]
+    finally:
+        UL.FUSE_DECODE_ATTENTION = False
+        quant_bart.QuantizedBartCache = plain_cache
+    emit([f"sample(max_length=62, min_length=62, num_samples={n}, sample_graph=True), the one-launch attention on for the first step "
+          f"too, s, wall time of the call (encoder and capture included):"]
+         + [f"    {label:72s} {_stats(t)}   {did[label]}" for label, t in gen.items()])
+    for (a, *_), (b, *_) in zip(forms[0::2], forms[1::2]):
+        ta, tb = sorted(gen[a])[len(gen[a]) // 2], sorted(gen[b])[len(gen[b]) // 2]
+        same = tokens[a].shape == tokens[b].shape and bool(torch.equal(tokens[a], tokens[b]))
+        outside = min(gen[a]) > max(gen[b]) or max(gen[a]) < min(gen[b])
+        emit([f"    {b}: {100 * (ta - tb) / ta:.1f} % below the unshared call's time ("
+              + ("outside" if outside else "INSIDE") + " the baseline's own range); tokens " + ("equal" if same else "DIFFER")
+              + f"; cache.nbytes() {held[a]} -> {held[b]}"])
+    emit(["the same shared calls with and without return_logprobs, s:"] + [f"    {label:88s} {_stats(t)}" for label, t in lp_times.items()])
+    times = sample_group_step_ab(args.batch * n, n, args.reps, ids.device)
+    emit([f"the step kernels alone at [{args.batch * n}, 50265], us per call (device events around 50 calls):"]
+         + [f"    {label:60s} {_stats(t)}" for label, t in times.items()])
+    for label in list(times)[0::2]:
+        a, b = times[label], times[label + ", logprobs"]
+        ma, mb = sorted(a)[len(a) // 2], sorted(b)[len(b) // 2]
+        emit([f"    {label}: logprobs {mb - ma:+.3f} us, " + ("inside" if min(a) <= mb <= max(a) else "OUTSIDE") + " the baseline's own range"])
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=32)
@@ -1040,9 +1146,16 @@ def main():
     ap.add_argument("--sample-advance", action="store_true")
     ap.add_argument("--sample-nucleus", action="store_true")
     ap.add_argument("--share-cross-kv", action="store_true")
+    ap.add_argument("--sample-group", action="store_true")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     q, ids, mask = build(args.batch, args.src, args.layers)
+    if args.sample_group:
+        text = "\n".join(sample_group_ab(q, ids, mask, args))
+        if args.out:
+            with open(args.out, "w") as f:
+                f.write(text + "\n")
+        return
     if args.share_cross_kv:
         text = "\n".join(share_cross_kv_ab(q, ids, mask, args))
         if args.out:
