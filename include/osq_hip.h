@@ -46,7 +46,8 @@ typedef void* osq_stream;
  *     osq_greedy_advance_at, osq_sample_advance_workspace_bytes, osq_sample_advance, osq_sample_advance_at,
  *     osq_sample_uniforms, osq_sample_nucleus_workspace_bytes, osq_sample_nucleus, osq_sample_nucleus_at,
  *     osq_decode_attention_shared, osq_decode_attention_shared_codes, osq_sample_advance_group, osq_sample_advance_group_at,
- *     osq_sample_nucleus_group, osq_sample_nucleus_group_at, osq_sample_uniforms_group. */
+ *     osq_sample_nucleus_group, osq_sample_nucleus_group_at, osq_sample_uniforms_group, osq_token_logprob_workspace_bytes,
+ *     osq_token_logprob, osq_token_logprob_backward. */
 #define OSQ_ABI_VERSION 10
 
 typedef enum osq_status {
@@ -1231,6 +1232,59 @@ int osq_sample_nucleus_group_at(const float* logits, int64_t logits_stride, int6
                                 int64_t max_length, int64_t* next_tokens, int32_t* go_on, void* workspace,
                                 size_t workspace_bytes, uint64_t seed, float temperature, float top_p, const float* uniforms,
                                 int64_t group, float* logprobs, int64_t logprobs_stride, osq_stream stream);
+
+/* ------------------------------------------------------------------ teacher-forced scoring (token_logprob.hip) */
+
+/* The log-probability the model gives a GIVEN token, per row, and the language-model loss over the rows: what
+ * -F.cross_entropy(logits, labels, reduction='none' / 'mean', ignore_index) computes, without a tensor of the logits' size.
+ * logits: fp32, `rows` rows of `vocab` values `stride` elements apart (stride >= vocab, any parity: a row needs 4-byte
+ * alignment only).  labels: int64 [rows].  For row r with label t:
+ *     m          the row's maximum (a NaN is no maximum)
+ *     W          the sum of expf(z - m) over the row in fp32, -inf logits weighing 0, in an order fixed by vocab alone: the row
+ *                in chunks of 4096 tokens; in a chunk, with its own maximum m_c, thread i of 256 adds expf(z - m_c) of the
+ *                tokens 4 (i + 256 k) + e in the order k = 0..3, e = 0..3; 64 consecutive threads by four symmetric
+ *                lane-exchange steps (xor 1, xor 2, mirror of 8, mirror of 16) and then (r0 + r16) + (r32 + r48); the four
+ *                results as (w0 + w1) + (w2 + w3) = W_c; then W = sum over the chunks, in order, of W_c * expf(m_c - m)
+ *     lse[r]     = m + logf(W)
+ *     logprob[r] = (z_t - m) - logf(W), the first term exactly 0 where z_t == m
+ *     t == ignore_index                     logprob[r] = 0; lse[r] is written all the same; the row is not counted as scored
+ *     t outside [0, vocab), not ignored     logprob[r] = NaN and the row is counted as bad: no address is formed from such a
+ *                                           label, nothing outside the row is read and nothing traps
+ *     a row whose maximum is not finite, or that holds a NaN: what the IEEE arithmetic above gives (NaN).  A label on the one
+ *     finite value of a row otherwise -inf gives exactly 0, a label on one of its -inf values gives -inf.
+ * loss (may be NULL): one fp32, -(sum of the `rows` words of logprob) / scored, the sum in an order fixed by `rows` alone
+ *     (thread i of 256 adds the rows i, i + 256, ... in order, then the tree above): NaN where no row was scored, as torch
+ *     gives, and NaN where a label was bad.  counts (may be NULL): two int64, {rows scored, rows with a bad label}.
+ * A row's words do not depend on rows, on its position or on the grid: one workgroup per (row, chunk) holds the chunk in
+ * registers and writes (m_c, W_c) to the workspace; one thread per row merges them and reads z_t; one workgroup forms loss
+ * and counts (not launched when both are NULL).  Every logit is read from memory once, nothing of the logits' size is written.
+ * No atomics on device memory, no host synchronisation, no allocation: legal inside a stream capture.
+ * workspace: at least osq_token_logprob_workspace_bytes(rows, vocab) bytes (8 per row and chunk) of device memory, 8-byte
+ * aligned, contents arbitrary; one per stream in flight.  It may be NULL where that size is 0.
+ * rows == 0 launches the last kernel alone: loss = NaN, counts = {0, 0}.
+ * OSQ_ERR_INVALID_ARGUMENT, nothing launched: with rows > 0 a null logits / labels / logprob / lse / workspace; vocab < 1,
+ * vocab > 2^31 - 4097, stride < vocab, rows < 0, more than 2^31 - 1 (row, chunk) pairs (the workspace size is 0 for the last
+ * four). */
+size_t osq_token_logprob_workspace_bytes(int64_t rows, int64_t vocab);
+int osq_token_logprob(const float* logits, int64_t stride, const int64_t* labels, int64_t rows, int64_t vocab,
+                      int64_t ignore_index, float* logprob, float* lse, float* loss, int64_t* counts, void* workspace,
+                      osq_stream stream);
+
+/* The gradient of the above for the logits, from lse alone: one streaming launch,
+ *     dlogits[r, v] = coef_r * (p - [v == t]), p = expf(z - lse[r]),   0 for a row that is ignored or has a bad label
+ * and, where vocab <= 4096 (the row is one chunk, one workgroup holds it), p = expf(z - lse[r]) / S with S the fp32 sum of
+ * the row's expf(z - lse[r]) in the order of W_c above: S is 1 but for the rounding of lse to one fp32 word, which moves every
+ * exponent of the row alike; dividing by it takes that rounding out, so that the dlogits of such a row add up to zero within
+ * their own roundings (a short row is where lse's rounding would be large beside them).
+ * with coef_r = row_grad[r] where row_grad (fp32 [rows]) is given: the upstream gradient of the row's NEGATIVE log-probability
+ * (reduction='none'); else coef_r = scalar_grad[0] / float(counts[0]): the upstream gradient of `loss` over the scored rows
+ * the forward counted (reduction='mean'), both read on the device.  dlogits: fp32, rows `dstride` elements apart
+ * (dstride >= vocab); the words between the rows are not written.  logits are read once, dlogits written once.
+ * OSQ_ERR_INVALID_ARGUMENT, nothing launched: what osq_token_logprob refuses, a null lse / dlogits, dstride < vocab, neither
+ * row_grad nor both of scalar_grad and counts.  rows == 0 launches nothing. */
+int osq_token_logprob_backward(const float* logits, int64_t stride, const int64_t* labels, const float* lse,
+                               const float* row_grad, const float* scalar_grad, const int64_t* counts, int64_t rows,
+                               int64_t vocab, int64_t ignore_index, float* dlogits, int64_t dstride, osq_stream stream);
 
 /* ------------------------------------------------------------------ bf16 / fp16 only (lowp.hip) */
 

@@ -184,6 +184,23 @@ def set_share_cross_kv(on=True):
     util_layernorm.SHARE_CROSS_KV = bool(on)
 
 
+def set_fast_lm_loss(on=True):
+    """``forward(labels=...)`` of QuantizedBartForConditionalGeneration computes its loss through the scoring kernels --
+    ops.lm_loss: every logit read once, no tensor of the logits' size written, the backward one streaming launch from the
+    rows' log-sum-exp (util_layernorm.FAST_LM_LOSS; csrc/token_logprob.hip; model/losses.py, FusedLmLoss; default OFF) --
+    instead of F.cross_entropy, with autograd on or off; a call the kernels do not take runs F.cross_entropy
+    (``model.last_lm_loss``: fused, eager, reason).  Tolerance-equal, not bit-equal.  OSQ_FAST_LM_LOSS=1 turns it on at
+    load.  ``model.score()`` uses the kernels on the GPU whatever this says."""
+    from . import util_layernorm
+    util_layernorm.FAST_LM_LOSS = bool(on)
+
+
+def fast_lm_loss_from_environment(environ=None):
+    """What OSQ_FAST_LM_LOSS asks for: unset, empty or "0" -> False, anything else -> True."""
+    import os
+    return (os.environ if environ is None else environ).get("OSQ_FAST_LM_LOSS", "") not in ("", "0")
+
+
 def share_cross_kv_from_environment(environ=None):
     """What OSQ_SHARE_CROSS_KV asks for: unset, empty or "0" -> False, anything else -> True."""
     import os
@@ -256,7 +273,8 @@ def reset_tier(_lib=None):
     replays a whole step as one captured graph (unset: off); OSQ_SAMPLE_ADVANCE=1 sample() takes a step with one kernel call
     (unset: off); OSQ_SAMPLE_GRAPH=1 sample() replays a whole step as one captured graph (unset: off); OSQ_SAMPLE_NUCLEUS=1
     that kernel call takes a nucleus over the whole vocabulary too (unset: off); OSQ_SHARE_CROSS_KV=1 beam search holds the
-    cross-attention keys / values once per batch row (unset: off)."""
+    cross-attention keys / values once per batch row (unset: off); OSQ_FAST_LM_LOSS=1 the BART LM wrapper's loss through the
+    scoring kernels (unset: off)."""
     import os
     width = int(os.environ.get("OSQ_STRICT_SIMD", "8"))
     strict = os.environ.get("OSQ_STRICT", "")
@@ -279,6 +297,7 @@ def reset_tier(_lib=None):
     set_sample_graph(sample_graph_from_environment())
     set_sample_nucleus(sample_nucleus_from_environment())
     set_share_cross_kv(share_cross_kv_from_environment())
+    set_fast_lm_loss(fast_lm_loss_from_environment())
 
 
 _apply_environment = reset_tier

@@ -206,6 +206,9 @@ SIGNATURES = {
     "osq_sample_nucleus_group_at": (_I, [_P, _L, _P, _L, _P, _L, _L, _P, _L, _L, _L, _L, _P, _L, _L, _P, _L, _L, _L, _P, _P, _P,
                                          ctypes.c_size_t, ctypes.c_uint64, _F, _F, _P, _L, _P, _L, _P]),
     "osq_sample_uniforms_group": (_I, [ctypes.c_uint64, _L, _L, _L, _P, _P]),
+    "osq_token_logprob_workspace_bytes": (ctypes.c_size_t, [_L, _L]),
+    "osq_token_logprob": (_I, [_P, _L, _P, _L, _L, _L, _P, _P, _P, _P, _P, _P]),
+    "osq_token_logprob_backward": (_I, [_P, _L, _P, _P, _P, _P, _P, _L, _L, _L, _P, _L, _P]),
     "osq_fake_quant_chain_lowp": (_I, [_I, _P, _P, _L, _P, _P, _I, _I, _I, _P]),
     "osq_fake_quant_chain_backward_lowp": (_I, [_I, _P, _P, _P, _L, _P, _P, _I, _I, _I, _P]),
     "osq_fake_quant_per_tensor_widen": (_I, [_I, _P, _P, _L, _P, _P, _I, _I, _F, _I, _I, _P]),

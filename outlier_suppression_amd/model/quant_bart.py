@@ -24,7 +24,7 @@ import torch
 from torch import nn
 
 from . import generation
-from .losses import classification_loss, lm_loss, span_loss, with_loss
+from .losses import LmLossInfo, classification_loss, lm_loss, span_loss, token_logprob_torch, with_loss
 from .. import ops
 from .. import util_layernorm as _UL
 from ..quantization import QuantizedModule, Quantizer
@@ -1005,7 +1005,61 @@ class QuantizedBartForConditionalGeneration(QuantizedModule):
                             if caching or past_key_values is not None else {}))
         logits = self.lm_head(out[0]) + self.final_logits_bias
         rest = (out[1], out[2]) if caching else (out[-1],)
-        return with_loss(lm_loss(logits, labels, self.config.vocab_size), (logits,) + rest)
+        info = None
+        if labels is not None:
+            self.last_lm_loss = info = LmLossInfo()
+        return with_loss(lm_loss(logits, labels, self.config.vocab_size, info), (logits,) + rest)
+
+    @torch.no_grad()
+    def score(self, input_ids, labels, attention_mask=None, num_candidates=1, ignore_index=-100):
+        """How likely the model finds GIVEN target sequences, teacher-forced: (token_logprobs [B * n, T] fp32, the
+        log-probability of every label under the model's own distribution -- not the warped one of sample()'s
+        ``return_logprobs`` -- and 0 where the label is ``ignore_index``; sequence_logprob [B * n], their sum per row in
+        position order; lengths [B * n] int64, the scored positions per row).  ``labels``: int64 [B * n, T] with the
+        ``n = num_candidates`` candidates of input b at rows b * n .. b * n + n - 1, the layout of ``sample(num_samples=n)``.
+        The encoder runs once, on the B inputs; its states and the attention mask are expanded with repeat_interleave(n);
+        the decoder's inputs are shift_tokens_right(labels).  On the GPU the logits go through ops.token_logprob
+        (csrc/token_logprob.hip) whatever set_fast_lm_loss says, on the CPU through losses.token_logprob_torch.  Raises
+        ValueError for a label outside the vocabulary (the kernel counts them; the count is read once, at the end)."""
+        n = int(num_candidates)
+        if n < 1:
+            raise ValueError("score(): num_candidates must be at least 1")
+        if labels.dim() != 2 or labels.shape[0] != input_ids.shape[0] * n:
+            raise ValueError("score(): labels must be [B * num_candidates, T], the candidates of an input adjacent")
+        labels = labels.to(torch.int64)
+        if attention_mask is None:
+            attention_mask = torch.ones_like(input_ids)
+        enc = self.get_encoder()(input_ids, attention_mask=attention_mask)
+        if n > 1:
+            enc = enc.repeat_interleave(n, dim=0)
+            attention_mask = attention_mask.repeat_interleave(n, dim=0)
+        dec_in = shift_tokens_right(labels.masked_fill(labels == ignore_index, -100), self.config.pad_token_id,
+                                    self.config.decoder_start_token_id)
+        dec_in.clamp_(0, self.config.vocab_size - 1)    # a label outside the vocabulary is refused below, not looked up
+        logits = self.forward(attention_mask=attention_mask, decoder_input_ids=dec_in, encoder_outputs=(enc,))[0]
+        rows, steps = labels.shape
+        vocab = logits.shape[-1]
+        scored = labels != ignore_index
+        counts = None
+        if logits.is_cuda:
+            flat = logits.reshape(rows * steps, vocab).float()
+            _, logprob, _, counts = ops.lm_loss(flat, labels.reshape(-1), ignore_index)
+            token_logprobs = logprob.view(rows, steps)
+        else:
+            self._score_refuse(int((scored & ((labels < 0) | (labels >= vocab))).sum()), vocab)
+            token_logprobs = token_logprob_torch(logits.float(), labels, ignore_index)
+        sequence_logprob = torch.zeros(rows, dtype=torch.float32, device=logits.device)
+        for t in range(steps):                          # position order: a row's sum does not depend on the batch
+            sequence_logprob += token_logprobs[:, t]
+        lengths = scored.sum(1)
+        if counts is not None:
+            self._score_refuse(int(counts[1]), vocab)   # the call's one synchronisation
+        return token_logprobs, sequence_logprob, lengths
+
+    @staticmethod
+    def _score_refuse(bad, vocab):
+        if bad:
+            raise ValueError(f"score(): {bad} labels lie outside the vocabulary [0, {vocab}) and are not ignore_index")
 
     def prepare_inputs_for_generation(self, decoder_input_ids, past=None, attention_mask=None, head_mask=None,
                                       decoder_head_mask=None, cross_attn_head_mask=None, use_cache=None,

@@ -2377,3 +2377,126 @@ def sample_uniforms(seed, bsz, cur, device, group=1):
     _hip.check(_hip.load().osq_sample_uniforms_group(int(seed) & 0xFFFFFFFFFFFFFFFF, out.numel(), int(group), int(cur),
                                                      out.data_ptr(), _hip.raw_stream(device)), "sample_uniforms")
     return out
+
+
+# ---------------------------------------------------------------------------------------
+# teacher-forced scoring (csrc/token_logprob.hip)
+# ---------------------------------------------------------------------------------------
+_token_logprob_ws = {}          # (device, stream) -> [workspace, a capture has named it]
+_token_logprob_named = []       # outgrown workspaces that a captured graph names: kept alive for its replays
+
+
+def token_logprob_fits(rows, vocab):
+    """True where one launch indexes ``rows`` rows of ``vocab`` logits (at most 2^31 - 1 (row, 4096-token chunk) pairs)."""
+    rows, vocab = int(rows), int(vocab)
+    return rows >= 0 and 1 <= vocab <= 2 ** 31 - 4097 and rows * ((vocab + 4095) // 4096) <= 2 ** 31 - 1
+
+
+def _token_logprob_workspace(device, rows, vocab):
+    """The (device, stream) scratch of the scoring launches, grown on demand.  Call once with the shape before capturing:
+    a capture allocates nothing then, and the workspace it names outlives a later, larger call."""
+    nbytes = max(int(_hip.load().osq_token_logprob_workspace_bytes(rows, vocab)), 8)
+    key = (_hip._device_index(device), _hip.raw_stream(device))
+    entry = _token_logprob_ws.get(key)
+    if entry is None or entry[0].numel() < nbytes:
+        if entry is not None and entry[1]:
+            _token_logprob_named.append(entry[0])
+        entry = [torch.empty(nbytes, dtype=torch.uint8, device=device), False]
+        _token_logprob_ws[key] = entry
+    if not entry[1] and torch.cuda.is_current_stream_capturing():
+        entry[1] = True
+    return entry[0]
+
+
+def _token_logprob_operands(what, logits, labels):
+    _hip.require_device(logits, labels)
+    _check_f32(logits)
+    if logits.dim() != 2 or labels.dim() != 1 or labels.dtype != torch.int64 or labels.shape[0] != logits.shape[0]:
+        raise ValueError(f"{what}: logits must be fp32 [rows, vocab] and labels int64 [rows]")
+    rows, vocab = logits.shape
+    if vocab < 1 or (vocab > 1 and logits.stride(1) != 1) or (rows > 1 and logits.stride(0) < vocab):
+        raise ValueError(f"{what}: logits must have a dense last axis of at least one token")
+    if labels.device != logits.device or (rows > 1 and labels.stride(0) != 1):
+        raise ValueError(f"{what}: labels must be contiguous on the device of logits")
+    if not token_logprob_fits(rows, vocab):
+        raise ValueError(f"{what}: more (row, 4096-token chunk) pairs than one launch indexes")
+    return rows, vocab, logits.stride(0) if rows > 1 else vocab
+
+
+def _token_logprob_out(what, out, name, shape, dtype, device):
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    if out.dtype != dtype or tuple(out.shape) != tuple(shape) or out.device != device or not out.is_contiguous():
+        raise ValueError(f"{what}: {name} must be a contiguous {dtype} tensor of shape {tuple(shape)} on the device of logits")
+    return out
+
+
+def _token_logprob(what, logits, labels, ignore_index, out, reduce):
+    lib = _hip.load()
+    rows, vocab, stride = _token_logprob_operands(what, logits, labels)
+    dev, out = logits.device, tuple(out) if out is not None else ()
+    out = out + (None,) * ((4 if reduce else 2) - len(out))
+    logprob = _token_logprob_out(what, out[1 if reduce else 0], "logprob", (rows,), torch.float32, dev)
+    lse = _token_logprob_out(what, out[2 if reduce else 1], "lse", (rows,), torch.float32, dev)
+    loss = counts = None
+    if reduce:
+        loss = _token_logprob_out(what, out[0], "loss", (), torch.float32, dev)
+        counts = _token_logprob_out(what, out[3], "counts", (2,), torch.int64, dev)
+    ws = _token_logprob_workspace(dev, rows, vocab)
+    rc = lib.osq_token_logprob(logits.data_ptr(), stride, labels.data_ptr(), rows, vocab, int(ignore_index), logprob.data_ptr(),
+                               lse.data_ptr(), _hip.ptr(loss), _hip.ptr(counts), ws.data_ptr(), _hip.raw_stream(dev))
+    _hip.check(rc, what)
+    return (loss, logprob, lse, counts) if reduce else (logprob, lse)
+
+
+def token_logprob(logits, labels, ignore_index=-100, out=None):
+    """The log-probability the rows of ``logits`` give their ``labels`` (osq_token_logprob, csrc/token_logprob.hip; the rule:
+    include/osq_hip.h, "teacher-forced scoring"): (logprob, lse), fp32 [rows] each -- ``-F.cross_entropy(logits, labels,
+    reduction='none', ignore_index=...)`` and ``logsumexp(logits, -1)``, without a tensor of the logits' size.  logits: fp32
+    [rows, vocab] with a dense last axis and any row stride; labels: int64 [rows].  A row whose label is ``ignore_index``
+    gives 0 (its lse is written all the same); a label outside the vocabulary gives NaN -- nothing asserts on the device.
+    ``out=(logprob, lse)``: the tensors to write, so that a captured call allocates nothing (the workspace is kept per device
+    and stream).  Two launches on the current stream, no synchronisation."""
+    return _token_logprob("token_logprob", logits, labels, ignore_index, out, False)
+
+
+def lm_loss(logits, labels, ignore_index=-100, out=None):
+    """token_logprob and the loss over the rows in one call: (loss, logprob, lse, counts) -- ``loss`` one fp32,
+    ``F.cross_entropy(logits, labels, ignore_index=...)`` (NaN where every row is ignored, as torch gives, and NaN where a
+    label lies outside the vocabulary), ``counts`` int64 [2]: the rows scored and the rows with such a label.  Reading counts
+    is the caller's synchronisation; this call has none.  ``out=(loss, logprob, lse, counts)``.  Three launches."""
+    return _token_logprob("lm_loss", logits, labels, ignore_index, out, True)
+
+
+def token_logprob_backward(logits, labels, lse, row_grad=None, scalar_grad=None, counts=None, ignore_index=-100, out=None):
+    """The gradient of token_logprob / lm_loss for the logits from ``lse`` alone (osq_token_logprob_backward):
+    ``coef * (exp(logits - lse[:, None]) - onehot(labels))`` per row (a row of at most 4096 tokens renormalised by the
+    kernel's own sum of its exponentials, which takes the rounding of lse out), 0 for an ignored row and for a label outside
+    the vocabulary.  coef is ``row_grad`` [rows] fp32 -- the upstream gradient of the rows' NEGATIVE log-probabilities -- or,
+    without it, ``scalar_grad / counts[0]``: the upstream gradient of the mean loss (one fp32 on the device) over the rows
+    lm_loss counted (its ``counts``), divided on the device.  ``out``: the fp32 [rows, vocab] tensor to write (dense last
+    axis, any row stride), else a new contiguous one.  One launch, no synchronisation."""
+    lib = _hip.load()
+    what = "token_logprob_backward"
+    rows, vocab, stride = _token_logprob_operands(what, logits, labels)
+    dev = logits.device
+    _hip.require_device(lse, row_grad, scalar_grad, counts, out)
+    _check_f32(lse, row_grad, scalar_grad, out)
+    for name, t, n in (("lse", lse, rows), ("row_grad", row_grad, rows), ("scalar_grad", scalar_grad, 1)):
+        if t is not None and (t.numel() != n or t.device != dev or not t.is_contiguous()):
+            raise ValueError(f"{what}: {name} must be a contiguous fp32 tensor of {n} elements on the device of logits")
+    if row_grad is None and (scalar_grad is None or counts is None):
+        raise ValueError(f"{what}: give row_grad, or scalar_grad with the counts of lm_loss")
+    if counts is not None and (counts.dtype != torch.int64 or counts.numel() != 2 or counts.device != dev
+                               or not counts.is_contiguous()):
+        raise ValueError(f"{what}: counts must be the int64 [2] tensor of lm_loss")
+    if out is None:
+        out = torch.empty((rows, vocab), dtype=torch.float32, device=dev)
+    elif (tuple(out.shape) != (rows, vocab) or out.device != dev or (vocab > 1 and out.stride(1) != 1)
+          or (rows > 1 and out.stride(0) < vocab)):
+        raise ValueError(f"{what}: out must be fp32 [rows, vocab] with a dense last axis on the device of logits")
+    rc = lib.osq_token_logprob_backward(logits.data_ptr(), stride, labels.data_ptr(), lse.data_ptr(), _hip.ptr(row_grad),
+                                        _hip.ptr(scalar_grad), _hip.ptr(counts), rows, vocab, int(ignore_index), out.data_ptr(),
+                                        out.stride(0) if rows > 1 else vocab, _hip.raw_stream(dev))
+    _hip.check(rc, what)
+    return out

@@ -127,6 +127,7 @@ SAMPLE_ADVANCE = False   # sample(): a sampling step's processors, temperature /
 SAMPLE_GRAPH = False     # sample(): capture a whole sampling step -- token copy, model, the kernel call above -- into one graph (implies GRAPH_DECODE and SAMPLE_ADVANCE for the call; set_sample_graph / OSQ_SAMPLE_GRAPH=1 / sample(sample_graph=True))
 SAMPLE_NUCLEUS = False   # sample(): under the two switches above, top_k=0 with top_p<1 (a nucleus over the whole vocabulary) goes to ops.sample_nucleus instead of the torch lines (set_sample_nucleus / OSQ_SAMPLE_NUCLEUS=1 / sample(sample_nucleus=True))
 SHARE_CROSS_KV = False   # generate(): beam search holds the cross-attention keys / values once per batch row and attends to them from every beam of the row in one launch (set_share_cross_kv / OSQ_SHARE_CROSS_KV=1 / generate(share_cross_kv=True))
+FAST_LM_LOSS = False     # forward(labels=...) of the BART LM wrapper: the loss through the scoring kernels -- ops.lm_loss, backward from lse alone -- instead of F.cross_entropy (tolerance-equal; set_fast_lm_loss / OSQ_FAST_LM_LOSS=1); score() uses the kernels whatever this says
 CACHE_CODES = False      # incremental decoding: new KV caches hold integer codes, one byte per element (same words read back; set_cache_codes / OSQ_CACHE_CODES=1)
 
 
