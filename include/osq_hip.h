@@ -897,7 +897,7 @@ int osq_decode_attention_codes_at(const float* q, const uint8_t* k, const uint8_
                                   osq_stream stream);
 
 /* osq_decode_attention_fake_quant / osq_decode_attention_codes for query rows that share their keys and values
- * (csrc/decode_attention_shared.hip): beam search's cross-attention, where the `group` beams of a batch row attend to the same
+ * (csrc/decode_attention.hip): beam search's cross-attention, where the `group` beams of a batch row attend to the same
  * encoder keys / values.  q: dense [batch * group, heads, 1, head_dim]; query row b * group + g attends to row b of k / v
  * ([batch, heads, cap, head_dim]) and of mask (NULL, or [batch, 1, 1, kv_len]).  out: dense [batch * group, 1, heads *
  * head_dim]; probs_out: NULL, or dense [batch * group, heads, 1, kv_len].  One workgroup serves up to 8 query rows of a

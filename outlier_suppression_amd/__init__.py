@@ -176,7 +176,7 @@ def sample_nucleus_from_environment(environ=None):
 def set_share_cross_kv(on=True):
     """Beam search holds the cross-attention keys / values once per batch row -- they are identical for the beams of a row --
     and a step's cross-attention serves all beams of a (row, head) from one pass over them (util_layernorm.SHARE_CROSS_KV;
-    ops.decode_attention_shared, csrc/decode_attention_shared.hip; default OFF): the cross part of the cache shrinks by the
+    ops.decode_attention_shared, csrc/decode_attention.hip; default OFF): the cross part of the cache shrinks by the
     factor num_beams, the words computed are those of the one-launch attention on the repeated tensors.
     OSQ_SHARE_CROSS_KV=1 turns it on at load; ``generate(..., share_cross_kv=True)`` asks for one call;
     ``model.last_share_cross_kv`` tells what happened."""

@@ -167,8 +167,8 @@ class ShareCrossKvInfo:
         return f"ShareCrossKvInfo(shared={self.shared}, eager={self.eager}, reason={self.reason!r})"
 
 
-SHARE_MAX_SOURCE = 1024            # kShMaxKv of csrc/decode_attention_shared.hip: the score rows of 8 queries in LDS
-SHARE_MAX_BEAMS = 64               # kShMaxGroup
+SHARE_MAX_SOURCE = 1024            # kMaxKv<8> of csrc/decode_attention.hip: the score rows of 8 queries in LDS
+SHARE_MAX_BEAMS = 64               # kDecMaxGroup
 
 
 def _share_why_not(model, device, use_cache, nb, source_len):

@@ -1701,6 +1701,93 @@ def _quant_group(quant):
     return [scale.data_ptr(), zero_point.data_ptr(), _zp_type(zero_point), int(mode), float(gf), int(qmin), int(qmax)]
 
 
+def _codes_args(what, codes):
+    """The launch arguments of a coded cache, ``codes = (k_record, v_record, rejected)``: each record
+    ``(scale_eff, zp_eff, quant_min)`` with one-element fp32 device tensors, rejected the cache's int32 device counter."""
+    k_record, v_record, rejected = codes
+    _hip.require_device(rejected, k_record[0], k_record[1], v_record[0], v_record[1])
+    _check_f32(k_record[0], k_record[1], v_record[0], v_record[1])
+    if rejected.dtype != torch.int32 or rejected.numel() != 1:
+        raise TypeError(f"{what}: rejected must be one int32")
+    return (k_record[0].data_ptr(), k_record[1].data_ptr(), int(k_record[2]),
+            v_record[0].data_ptr(), v_record[1].data_ptr(), int(v_record[2]), rejected.data_ptr())
+
+
+def _strided_rows(t, b, heads_axis, width):
+    """Row stride of an fp32 [b, heads_axis, 1, W >= width] tensor with a dense last axis whose rows lie evenly apart, or
+    None when it is laid out otherwise."""
+    if (t.dtype != torch.float32 or t.dim() != 4 or tuple(t.shape[:3]) != (b, heads_axis, 1) or t.shape[3] < width
+            or (t.shape[3] > 1 and t.stride(3) != 1)):
+        return None
+    row = t.stride(1) if heads_axis > 1 else (t.stride(0) if b > 1 else t.shape[3])
+    if row < t.shape[3] or (heads_axis > 1 and b > 1 and t.stride(0) != heads_axis * row):
+        return None
+    return row
+
+
+def _decode_attention(what, q, k, v, mask, probs_quant, ctx_quant, *, group=None, codes=None, at=None, out=None, probs_out=None,
+                      want_probs=False):
+    """The body of the four decode_attention_* functions below (csrc/decode_attention.hip); ``what`` is the caller's name in
+    messages.  ``group``: None for the one-query entry points, else the shared ones with that many query rows per row of
+    k / v.  ``at``: None for the static forms, which take k / v as views and the length from their
+    shape, or ``(kv_len, kv_len_add, kv_max, grad_table)`` for the length read by the launch over whole buffers.  Returns
+    out -- with ``want_probs`` the pair (out, probabilities) -- or None when the library does not take the layout."""
+    lib = _hip.load()
+    kv_len, kv_len_add, kv_max, grad_table = at if at is not None else (None, 0, 0, None)
+    _hip.require_device(q, k, v, mask, kv_len, grad_table, out, probs_out)
+    _check_f32(q)
+    if at is not None and (kv_len.dtype != torch.int32 or kv_len.numel() != 1):
+        raise TypeError(f"{what}: kv_len must be one int32")
+    shared, group = group is not None, 1 if group is None else int(group)
+    if group < 1:
+        raise ValueError(f"{what}: group must be at least 1")
+    dtype = torch.float32 if codes is None else torch.uint8
+    if q.dim() != 4 or q.shape[2] != 1 or not q.is_contiguous() or k.dim() != 4 or v.dim() != 4 or q.shape[0] % group:
+        return None
+    rows, h, _, d = q.shape
+    b = rows // group
+    if at is None:
+        s = k.shape[2]
+        k_cap, v_cap = _kv_cap(k, b, h, s, d, dtype), _kv_cap(v, b, h, s, d, dtype)
+        if k_cap is None or v_cap is None:
+            return None
+        if mask is not None and not (mask.dtype == torch.float32 and tuple(mask.shape) == (b, 1, 1, s) and mask.is_contiguous()):
+            return None
+    else:
+        if (k.dtype != dtype or v.dtype != dtype or not k.is_contiguous() or not v.is_contiguous()
+                or tuple(k.shape[:2]) != (b, h) or tuple(v.shape[:2]) != (b, h) or k.shape[3] != d or v.shape[3] != d):
+            return None
+        s, k_cap, v_cap = int(kv_max), k.shape[2], v.shape[2]
+        if k_cap < s or v_cap < s:
+            raise ValueError(f"{what}: kv_max exceeds the capacity of k / v")
+        strides = [0 if t is None else _strided_rows(t, b, heads_axis, s) for t, heads_axis in ((mask, 1), (probs_out, h))]
+        if None in strides:
+            return None
+        if grad_table is not None and (grad_table.dtype != torch.float32 or grad_table.numel() < s + 1
+                                       or not grad_table.is_contiguous()):
+            raise ValueError(f"{what}: grad_table must hold kv_max + 1 contiguous floats")
+    if out is None:
+        out = torch.empty((rows, 1, h * d), dtype=torch.float32, device=q.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (rows, 1, h * d) or not out.is_contiguous():
+        raise ValueError(f"{what}: out must be a contiguous fp32 [B, 1, h * d] tensor")
+    if want_probs:
+        probs_out = torch.empty((rows, h, 1, s), dtype=torch.float32, device=q.device)
+    if at is None:
+        head = (q.data_ptr(), k.data_ptr(), v.data_ptr(), _hip.ptr(mask), out.data_ptr(), _hip.ptr(probs_out), b,
+                *((group,) if shared else ()), h, d, s, k_cap, v_cap)
+    else:
+        head = (q.data_ptr(), k.data_ptr(), v.data_ptr(), _hip.ptr(mask), strides[0], out.data_ptr(), _hip.ptr(probs_out),
+                strides[1], b, h, d, kv_len.data_ptr(), int(kv_len_add), s, k_cap, v_cap, _hip.ptr(grad_table))
+    name = ("shared_codes" if codes is not None else "shared") if shared else ("codes" if codes is not None else "fake_quant")
+    entry = getattr(lib, "osq_decode_attention_" + name + ("_at" if at is not None else ""))
+    record = () if codes is None else _codes_args(what, codes)
+    rc = entry(*head, *record, *_quant_group(probs_quant), *_quant_group(ctx_quant), _hip.raw_stream(q.device))
+    if rc == _hip.ERR_UNSUPPORTED:
+        return None
+    _hip.check(rc, what)
+    return (out, probs_out) if want_probs else out
+
+
 def decode_attention_fake_quant(q, k, v, mask, probs_quant, ctx_quant, want_probs=False):
     """``fq_ctx(merge_heads(fq_probs(softmax(q @ k^T + mask)) @ v))`` for ONE query token in ONE launch
     (osq_decode_attention_fake_quant, csrc/decode_attention.hip).
@@ -1710,27 +1797,7 @@ def decode_attention_fake_quant(q, k, v, mask, probs_quant, ctx_quant, want_prob
     probs_quant / ctx_quant: None (no quantizer) or (scale, zero_point, quant_min, quant_max, mode, grad_factor).
     Returns the [B, 1, h * d] output -- with ``want_probs`` the pair (output, fake-quantised probabilities [B, h, 1, S]) --
     or None when the library does not take the layout (nothing was launched): the caller runs the eager sequence."""
-    lib = _hip.load()
-    _hip.require_device(q, k, v, mask)
-    _check_f32(q)
-    if q.dim() != 4 or q.shape[2] != 1 or not q.is_contiguous() or k.dim() != 4:
-        return None
-    b, h, _, d = q.shape
-    s = k.shape[2]
-    k_cap, v_cap = _kv_cap(k, b, h, s, d), _kv_cap(v, b, h, s, d)
-    if k_cap is None or v_cap is None:
-        return None
-    if mask is not None and not (mask.dtype == torch.float32 and tuple(mask.shape) == (b, 1, 1, s) and mask.is_contiguous()):
-        return None
-    out = torch.empty((b, 1, h * d), dtype=torch.float32, device=q.device)
-    probs = torch.empty((b, h, 1, s), dtype=torch.float32, device=q.device) if want_probs else None
-    rc = lib.osq_decode_attention_fake_quant(q.data_ptr(), k.data_ptr(), v.data_ptr(), _hip.ptr(mask), out.data_ptr(),
-                                             _hip.ptr(probs), b, h, d, s, k_cap, v_cap, *_quant_group(probs_quant),
-                                             *_quant_group(ctx_quant), _hip.raw_stream(q.device))
-    if rc == _hip.ERR_UNSUPPORTED:
-        return None
-    _hip.check(rc, "decode_attention_fake_quant")
-    return (out, probs) if want_probs else out
+    return _decode_attention("decode_attention_fake_quant", q, k, v, mask, probs_quant, ctx_quant, want_probs=want_probs)
 
 
 def decode_attention_codes(q, k, v, mask, probs_quant, ctx_quant, k_record, v_record, rejected, want_probs=False):
@@ -1738,31 +1805,9 @@ def decode_attention_codes(q, k, v, mask, probs_quant, ctx_quant, k_record, v_re
     tensors, dense or ``[:, :, :S]`` views of [B, h, cap, d] buffers; k_record / v_record ``(scale_eff, zp_eff, quant_min)``
     with one-element fp32 device tensors; rejected the cache's int32 device counter -- non-zero: every output word is NaN.
     The outputs are word-equal to decode_attention_fake_quant on the dequantised k / v.  Returns as that function does."""
-    lib = _hip.load()
-    _hip.require_device(q, k, v, mask, rejected, k_record[0], k_record[1], v_record[0], v_record[1])
-    _check_f32(q, k_record[0], k_record[1], v_record[0], v_record[1])
-    if rejected.dtype != torch.int32 or rejected.numel() != 1:
-        raise TypeError("decode_attention_codes: rejected must be one int32")
-    if q.dim() != 4 or q.shape[2] != 1 or not q.is_contiguous() or k.dim() != 4:
-        return None
-    b, h, _, d = q.shape
-    s = k.shape[2]
-    k_cap, v_cap = _kv_cap(k, b, h, s, d, torch.uint8), _kv_cap(v, b, h, s, d, torch.uint8)
-    if k_cap is None or v_cap is None:
-        return None
-    if mask is not None and not (mask.dtype == torch.float32 and tuple(mask.shape) == (b, 1, 1, s) and mask.is_contiguous()):
-        return None
-    out = torch.empty((b, 1, h * d), dtype=torch.float32, device=q.device)
-    probs = torch.empty((b, h, 1, s), dtype=torch.float32, device=q.device) if want_probs else None
-    rc = lib.osq_decode_attention_codes(q.data_ptr(), k.data_ptr(), v.data_ptr(), _hip.ptr(mask), out.data_ptr(),
-                                        _hip.ptr(probs), b, h, d, s, k_cap, v_cap,
-                                        k_record[0].data_ptr(), k_record[1].data_ptr(), int(k_record[2]),
-                                        v_record[0].data_ptr(), v_record[1].data_ptr(), int(v_record[2]), rejected.data_ptr(),
-                                        *_quant_group(probs_quant), *_quant_group(ctx_quant), _hip.raw_stream(q.device))
-    if rc == _hip.ERR_UNSUPPORTED:
-        return None
-    _hip.check(rc, "decode_attention_codes")
-    return (out, probs) if want_probs else out
+    codes = (k_record, v_record, rejected)
+    _codes_args("decode_attention_codes", codes)        # this form has always checked the record before the layout
+    return _decode_attention("decode_attention_codes", q, k, v, mask, probs_quant, ctx_quant, codes=codes, want_probs=want_probs)
 
 
 def decode_attention_at(q, k, v, kv_len, kv_len_add, kv_max, mask, probs_quant, ctx_quant, grad_table=None, codes=None,
@@ -1777,63 +1822,13 @@ def decode_attention_at(q, k, v, kv_len, kv_len_add, kv_max, mask, probs_quant, 
     floats, entry n the probabilities quantizer's grad factor at length n (util_layernorm.decode_grad_table).  out: the
     [B, 1, h * d] tensor to write, or None for a new one.  A length outside [1, kv_max] gives NaN in every word of out.
     Returns out, or None when the library does not take the layout (nothing was launched)."""
-    lib = _hip.load()
-    _hip.require_device(q, k, v, mask, kv_len, grad_table, out, probs_out)
-    _check_f32(q)
-    if kv_len.dtype != torch.int32 or kv_len.numel() != 1:
-        raise TypeError("decode_attention_at: kv_len must be one int32")
-    dtype = torch.float32 if codes is None else torch.uint8
-    if (q.dim() != 4 or q.shape[2] != 1 or not q.is_contiguous() or k.dim() != 4 or v.dim() != 4 or k.dtype != dtype
-            or v.dtype != dtype or not k.is_contiguous() or not v.is_contiguous()):
-        return None
-    b, h, _, d = q.shape
-    if tuple(k.shape[:2]) != (b, h) or tuple(v.shape[:2]) != (b, h) or k.shape[3] != d or v.shape[3] != d:
-        return None
-    kv_max = int(kv_max)
-    if k.shape[2] < kv_max or v.shape[2] < kv_max:
-        raise ValueError("decode_attention_at: kv_max exceeds the capacity of k / v")
-    strides = []
-    for t, heads_axis in ((mask, 1), (probs_out, h)):
-        if t is None:
-            strides.append(0)
-            continue
-        if (t.dtype != torch.float32 or t.dim() != 4 or tuple(t.shape[:3]) != (b, heads_axis, 1) or t.shape[3] < kv_max
-                or (t.shape[3] > 1 and t.stride(3) != 1)):
-            return None
-        row = t.stride(1) if heads_axis > 1 else (t.stride(0) if b > 1 else t.shape[3])
-        if row < t.shape[3] or (heads_axis > 1 and b > 1 and t.stride(0) != heads_axis * row):
-            return None
-        strides.append(row)
-    if grad_table is not None and (grad_table.dtype != torch.float32 or grad_table.numel() < kv_max + 1
-                                   or not grad_table.is_contiguous()):
-        raise ValueError("decode_attention_at: grad_table must hold kv_max + 1 contiguous floats")
-    if out is None:
-        out = torch.empty((b, 1, h * d), dtype=torch.float32, device=q.device)
-    elif out.dtype != torch.float32 or tuple(out.shape) != (b, 1, h * d) or not out.is_contiguous():
-        raise ValueError("decode_attention_at: out must be a contiguous fp32 [B, 1, h * d] tensor")
-    head = (q.data_ptr(), k.data_ptr(), v.data_ptr(), _hip.ptr(mask), strides[0], out.data_ptr(), _hip.ptr(probs_out),
-            strides[1], b, h, d, kv_len.data_ptr(), int(kv_len_add), kv_max, k.shape[2], v.shape[2], _hip.ptr(grad_table))
-    tail = (*_quant_group(probs_quant), *_quant_group(ctx_quant), _hip.raw_stream(q.device))
-    if codes is None:
-        rc = lib.osq_decode_attention_fake_quant_at(*head, *tail)
-    else:
-        k_record, v_record, rejected = codes
-        _hip.require_device(rejected, k_record[0], k_record[1], v_record[0], v_record[1])
-        _check_f32(k_record[0], k_record[1], v_record[0], v_record[1])
-        if rejected.dtype != torch.int32 or rejected.numel() != 1:
-            raise TypeError("decode_attention_at: rejected must be one int32")
-        rc = lib.osq_decode_attention_codes_at(*head, k_record[0].data_ptr(), k_record[1].data_ptr(), int(k_record[2]),
-                                               v_record[0].data_ptr(), v_record[1].data_ptr(), int(v_record[2]),
-                                               rejected.data_ptr(), *tail)
-    if rc == _hip.ERR_UNSUPPORTED:
-        return None
-    _hip.check(rc, "decode_attention_at")
-    return out
+    return _decode_attention("decode_attention_at", q, k, v, mask, probs_quant, ctx_quant, codes=codes,
+                             at=(kv_len, kv_len_add, kv_max, grad_table), out=out, probs_out=probs_out)
 
 
 def decode_attention_shared(q, k, v, mask, probs_quant, ctx_quant, group, codes=None, want_probs=False):
     """decode_attention_fake_quant / decode_attention_codes for query rows that share their keys and values
-    (osq_decode_attention_shared / osq_decode_attention_shared_codes, csrc/decode_attention_shared.hip): beam search's
+    (osq_decode_attention_shared / osq_decode_attention_shared_codes, csrc/decode_attention.hip): beam search's
     cross-attention, one copy of K / V per batch row.
 
     q: dense [B * group, h, 1, d] fp32; query row ``b * group + g`` attends to row b of k / v ([B, h, S, d], fp32, or uint8
@@ -1843,43 +1838,8 @@ def decode_attention_shared(q, k, v, mask, probs_quant, ctx_quant, group, codes=
     along the batch.  Returns the [B * group, 1, h * d] output -- with ``want_probs`` the pair (output, probabilities
     [B * group, h, 1, S]) -- or None where the launch refuses (group above 64, S above 1024, a head_dim or layout the
     library does not take; nothing was launched)."""
-    lib = _hip.load()
-    _hip.require_device(q, k, v, mask)
-    _check_f32(q)
-    group = int(group)
-    if group < 1:
-        raise ValueError("decode_attention_shared: group must be at least 1")
-    if q.dim() != 4 or q.shape[2] != 1 or not q.is_contiguous() or k.dim() != 4 or q.shape[0] % group:
-        return None
-    rows, h, _, d = q.shape
-    b = rows // group
-    s = k.shape[2]
-    dtype = torch.float32 if codes is None else torch.uint8
-    k_cap, v_cap = _kv_cap(k, b, h, s, d, dtype), _kv_cap(v, b, h, s, d, dtype)
-    if k_cap is None or v_cap is None:
-        return None
-    if mask is not None and not (mask.dtype == torch.float32 and tuple(mask.shape) == (b, 1, 1, s) and mask.is_contiguous()):
-        return None
-    out = torch.empty((rows, 1, h * d), dtype=torch.float32, device=q.device)
-    probs = torch.empty((rows, h, 1, s), dtype=torch.float32, device=q.device) if want_probs else None
-    head = (q.data_ptr(), k.data_ptr(), v.data_ptr(), _hip.ptr(mask), out.data_ptr(), _hip.ptr(probs), b, group, h, d, s,
-            k_cap, v_cap)
-    tail = (*_quant_group(probs_quant), *_quant_group(ctx_quant), _hip.raw_stream(q.device))
-    if codes is None:
-        rc = lib.osq_decode_attention_shared(*head, *tail)
-    else:
-        k_record, v_record, rejected = codes
-        _hip.require_device(rejected, k_record[0], k_record[1], v_record[0], v_record[1])
-        _check_f32(k_record[0], k_record[1], v_record[0], v_record[1])
-        if rejected.dtype != torch.int32 or rejected.numel() != 1:
-            raise TypeError("decode_attention_shared: rejected must be one int32")
-        rc = lib.osq_decode_attention_shared_codes(*head, k_record[0].data_ptr(), k_record[1].data_ptr(), int(k_record[2]),
-                                                   v_record[0].data_ptr(), v_record[1].data_ptr(), int(v_record[2]),
-                                                   rejected.data_ptr(), *tail)
-    if rc == _hip.ERR_UNSUPPORTED:
-        return None
-    _hip.check(rc, "decode_attention_shared")
-    return (out, probs) if want_probs else out
+    return _decode_attention("decode_attention_shared", q, k, v, mask, probs_quant, ctx_quant, group=group, codes=codes,
+                             want_probs=want_probs)
 
 
 def dequantize_kv_codes(codes, record, out=None):

@@ -99,7 +99,7 @@ in another order.  Off, every path and every fallback reason is unchanged.
 Beam search has ``SHARE_CROSS_KV`` (default OFF): the cross-attention keys / values, identical for the beams of a batch row,
 are projected, quantized and held once per batch row (``QuantizedBartCache(cross_group=num_beams)``), and a step's
 cross-attention is ONE launch in which a workgroup serves the beams of a (row, head) from a single pass over K and V
-(``ops.decode_attention_shared``, csrc/decode_attention_shared.hip): the words of the one-launch attention on the repeated
+(``ops.decode_attention_shared``, csrc/decode_attention.hip): the words of the one-launch attention on the repeated
 tensors.  ``outlier_suppression_amd.set_share_cross_kv(True)`` / ``OSQ_SHARE_CROSS_KV=1`` / ``generate(..., share_cross_kv=True)``
 turn it on.
 """
@@ -401,6 +401,26 @@ class _Numel:
         return self.n
 
 
+def _decode_site_params(q, *sites):
+    """The launch parameters of a decoding step's quantizers, ``sites`` = (quantizer, numel) pairs: per site None (no
+    quantizer) or (scale, zero_point, quant_min, quant_max, mode, grad_factor), a learnable quantizer's grad factor by the
+    ``numel`` elements of the tensor it would see; or None when a quantizer is not in its plain quantising state."""
+    params = []
+    for quantizer, numel in sites:
+        if quantizer is None:
+            params.append(None)
+            continue
+        if not _plain_quantizing(quantizer, q):
+            return None
+        mode = quantizer.param_mode
+        if isinstance(quantizer, _LearnableFakeQuantize):
+            mode |= ops.PARAM_SANITIZE
+            quantizer._touch_qparams()
+        params.append((quantizer.scale.data, quantizer.zero_point.data, quantizer.quant_min, quantizer.quant_max, mode,
+                       quantizer._grad_factor(_Numel(numel)) if quantizer.param_mode != ops.PARAM_FIXED else 1.0))
+    return params
+
+
 def decode_attention_fake_quant(probs_quantizer, ctx_quantizer, q, k, v, mask=None, dropout=None, codes=None):
     """Incremental decoding: what follows the q / k / v + append launch of a step's attention block
     (QuantizedBartAttention._attend: bmm, mask add, softmax, ``probs_quantizer``, bmm, merge heads, ``ctx_quantizer``) as ONE
@@ -414,20 +434,10 @@ def decode_attention_fake_quant(probs_quantizer, ctx_quantizer, q, k, v, mask=No
         return None
     if q.dim() != 4 or q.shape[2] != 1 or k.dim() != 4:
         return None
-    params = []
-    # a learnable quantizer's grad factor goes by the size of the tensor it would see: probabilities [B*h, 1, S], context [B, 1, h*d]
-    for quantizer, numel in ((probs_quantizer, q.shape[0] * q.shape[1] * k.shape[2]), (ctx_quantizer, q.numel())):
-        if quantizer is None:
-            params.append(None)
-            continue
-        if not _plain_quantizing(quantizer, q):
-            return None
-        mode = quantizer.param_mode
-        if isinstance(quantizer, _LearnableFakeQuantize):
-            mode |= ops.PARAM_SANITIZE
-            quantizer._touch_qparams()
-        params.append((quantizer.scale.data, quantizer.zero_point.data, quantizer.quant_min, quantizer.quant_max, mode,
-                       quantizer._grad_factor(_Numel(numel)) if quantizer.param_mode != ops.PARAM_FIXED else 1.0))
+    # the grad factors go by the size of the tensor a quantizer would see: probabilities [B*h, 1, S], context [B, 1, h*d]
+    params = _decode_site_params(q, (probs_quantizer, q.shape[0] * q.shape[1] * k.shape[2]), (ctx_quantizer, q.numel()))
+    if params is None:
+        return None
     if codes is not None:
         return ops.decode_attention_codes(q, k, v, mask, params[0], params[1], *codes)
     return ops.decode_attention_fake_quant(q, k, v, mask, params[0], params[1])
@@ -446,19 +456,9 @@ def decode_attention_shared_fake_quant(probs_quantizer, ctx_quantizer, q, k, v, 
         return None
     if q.dim() != 4 or q.shape[2] != 1 or k.dim() != 4:
         return None
-    params = []
-    for quantizer, numel in ((probs_quantizer, q.shape[0] * q.shape[1] * k.shape[2]), (ctx_quantizer, q.numel())):
-        if quantizer is None:
-            params.append(None)
-            continue
-        if not _plain_quantizing(quantizer, q):
-            return None
-        mode = quantizer.param_mode
-        if isinstance(quantizer, _LearnableFakeQuantize):
-            mode |= ops.PARAM_SANITIZE
-            quantizer._touch_qparams()
-        params.append((quantizer.scale.data, quantizer.zero_point.data, quantizer.quant_min, quantizer.quant_max, mode,
-                       quantizer._grad_factor(_Numel(numel)) if quantizer.param_mode != ops.PARAM_FIXED else 1.0))
+    params = _decode_site_params(q, (probs_quantizer, q.shape[0] * q.shape[1] * k.shape[2]), (ctx_quantizer, q.numel()))
+    if params is None:
+        return None
     return ops.decode_attention_shared(q, k, v, mask, params[0], params[1], group, codes=codes)
 
 
@@ -482,19 +482,9 @@ def decode_attention_at_fake_quant(probs_quantizer, ctx_quantizer, q, k, v, pos,
     device has no eager form.  Returns the [B, 1, h*d] context, or None (nothing launched)."""
     if torch.is_grad_enabled() or _dropout_active(dropout) or q.dim() != 4 or q.shape[2] != 1:
         return None
-    params = []
-    for quantizer in (probs_quantizer, ctx_quantizer):
-        if quantizer is None:
-            params.append(None)
-            continue
-        if not _plain_quantizing(quantizer, q):
-            return None
-        mode = quantizer.param_mode
-        if isinstance(quantizer, _LearnableFakeQuantize):
-            mode |= ops.PARAM_SANITIZE
-            quantizer._touch_qparams()
-        params.append((quantizer.scale.data, quantizer.zero_point.data, quantizer.quant_min, quantizer.quant_max, mode,
-                       quantizer._grad_factor(_Numel(q.numel())) if quantizer.param_mode != ops.PARAM_FIXED else 1.0))
+    params = _decode_site_params(q, (probs_quantizer, q.numel()), (ctx_quantizer, q.numel()))    # probs: grad_table serves
+    if params is None:
+        return None
     return ops.decode_attention_at(q, k, v, pos, add, kv_max, None, params[0], params[1], grad_table=grad_table, codes=codes)
 
 

@@ -1,4 +1,4 @@
-"""osq_decode_attention_shared / osq_decode_attention_shared_codes (csrc/decode_attention_shared.hip): one decoding step's
+"""osq_decode_attention_shared / osq_decode_attention_shared_codes (csrc/decode_attention.hip): one decoding step's
 attention for `group` query rows per batch row that share that row's keys, values and mask -- beam search's cross-attention.
 
 The comparator is the one-query-per-workgroup launch (osq_decode_attention_fake_quant / osq_decode_attention_codes, pinned to

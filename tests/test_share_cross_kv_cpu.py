@@ -1,5 +1,5 @@
 """CPU: what sharing the cross-attention keys / values among the beams of a row (generate(share_cross_kv=True);
-csrc/decode_attention_shared.hip) needs where no GPU is involved: the two entry points in the header's "Added within 10" list
+csrc/decode_attention.hip) needs where no GPU is involved: the two entry points in the header's "Added within 10" list
 and in ``_hip.SIGNATURES``; the switch, its setter and its environment variable; the reasons generate() and sample() give
 where nothing can be shared -- CPU tensors, one beam -- with the tokens of the call without the switch; and the cache's
 ``cross_group`` on the CPU, where the shared launches do not run: the legacy tuple keeps its shapes, ``nbytes`` counts one copy.
@@ -31,8 +31,12 @@ def test_entry_points_are_listed_and_bound():
         assert a[0] is b[0] and a[1] == b[1][:7] + [b[1][6]] + b[1][7:], shared
         decl = re.search(r"^int " + shared + r"\((.*?)\);", header, re.M | re.S).group(1)
         assert len(decl.split(",")) == len(a[1]) and re.search(r"int64_t batch, int64_t group, int64_t heads", decl)
-    makefile = open(os.path.join(ROOT, "outlier_suppression_amd", "csrc", "Makefile")).read()
-    assert makefile.count("decode_attention_shared.hip") == 2              # the library and the development build
+    csrc = os.path.join(ROOT, "outlier_suppression_amd", "csrc")
+    makefile = open(os.path.join(csrc, "Makefile")).read()
+    assert len(re.findall(r"\bdecode_attention\.hip\b", makefile)) == 2    # the library's and the development build's sources
+    source = open(os.path.join(csrc, "decode_attention.hip")).read()
+    for name in SYMBOLS:
+        assert re.search(r'^extern "C" int ' + name + r"\(", source, re.M), f"{name} is not defined in decode_attention.hip"
 
 
 @pytest.fixture()

@@ -62,7 +62,7 @@ ops.sample_nucleus (csrc/sample_nucleus.hip) under sample(sample_nucleus=True) a
 
 --share-cross-kv: the A/B is beam search over ONE copy of the cross-attention keys / values per batch row
 (generate(share_cross_kv=True); QuantizedBartCache(cross_group=beams); ops.decode_attention_shared,
-csrc/decode_attention_shared.hip) against one copy per beam, for the fp32 and the coded cache: the cross-attention launch alone
+csrc/decode_attention.hip) against one copy per beam, for the fp32 and the coded cache: the cross-attention launch alone
 (device events around 50 launches); one decoder step as a replayed graph at S = 1 / 31 / 62; generate(graph=True,
 beam_select=True, beam_advance=True); ``cache.nbytes()`` of both forms; and the largest logit difference over 12
 teacher-forced steps.  Every form is timed in turn within each of the --reps rounds, in one process.
