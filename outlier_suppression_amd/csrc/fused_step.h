@@ -469,47 +469,68 @@ __global__ __launch_bounds__(kFusedThreads) void observe_fq_fused_kernel(FusedAr
     unsigned int row[S];
 #pragma unroll
     for (int k = 0; k < S; ++k) row[k] = uniform(rows[k * kFusedWaves + wv]);
+    // A wave's tokens go up with the slot, so its valid slots are the first nval and its slots with a token the first
+    // nall: two counts (`k < nval`) instead of a kept condition per slot and phase
+    int nval = 0, nall = 0;
+#pragma unroll
+    for (int k = 0; k < S; ++k) {
+        nval += OSQ_FUSED_TOKEN(k) < V ? 1 : 0;
+        nall += OSQ_FUSED_TOKEN(k) < total ? 1 : 0;
+    }
     OSQ_FSTAMP(1);
 
     // ---- phase A1: valid tokens -> registers (slots 0..SR-1) / LDS (slots SR..S-1), per-token extrema -> compact arrays
+    // hipcc's wait counts cannot see a load behind a branch: with each slot's loads behind their own `j < V`, slot 0 first,
+    // the wait in front of every reduction was vmcnt(0) -- no younger load can be ASSUMED issued -- and no reduction
+    // overlapped the stream.  So the slots go downwards, slot k inside the `k - 1 < nval` of the slot below it: whoever
+    // has issued slot k's loads goes on through slots k - 1 .. 0, on every path their loads are behind slot k's, and the
+    // wait in front of slot k's reduction is vmcnt(NV k + NV - 1) .. vmcnt(NV k): its own loads, with everything younger
+    // still in flight.  (Loads of ALL slots as straight-line code, through a descriptor of zero records for the slots
+    // without a valid token, were countable too, but an out-of-range load still takes its turn in the CU's address and
+    // return path: +1.0 us at the bench lengths, +2.1 us on [64,128,1024], tools/ab_step.py on one box.)
+    // The extrema stay in the wave -- the pair of the wave's n-th token in lane n % 64, slots and the tokens beyond them
+    // alike -- and leave in one masked store pair behind the last reduction (or when 64 are held): vmcnt counts stores
+    // too, a publish per token put a write-through round trip in front of the next token's wait.
+    static_assert(S <= 9, "OSQ_FUSED_A1_SLOTS lists nine slots");
     v4u32 hold[SR > 0 ? SR : 1][NV];
+    float pub_mn = 0.f, pub_mx = 0.f;
     {
         v4u32 tmp[SL > 0 ? SL : 1][NV];
-#pragma unroll
-        for (int k = 0; k < S; ++k) {
-            const unsigned int j = OSQ_FUSED_TOKEN(k);
-            if (j < V) {
-#pragma unroll
-                for (int u = 0; u < NV; ++u) {
-                    const v4u32 w = __builtin_amdgcn_raw_buffer_load_b128(xrs, lane_off, row[k] * kRowBytes + OSQ_FUSED_PIECE(u), kNt);
-                    if (k < SR) hold[k][u] = w; else tmp[k - SR][u] = w;
-                }
-            }
+#define OSQ_FUSED_A1_LOAD(k)                                                                                                       \
+        if constexpr ((k) < S) {                                                                                                   \
+            _Pragma("unroll") for (int u = 0; u < NV; ++u) {                                                                       \
+                const v4u32 w = __builtin_amdgcn_raw_buffer_load_b128(xrs, lane_off, row[k] * kRowBytes + OSQ_FUSED_PIECE(u), kNt); \
+                if ((k) < SR) hold[(k) < SR ? (k) : 0][u] = w; else tmp[(k) < SR ? 0 : (k) - SR][u] = w;                           \
+            }                                                                                                                      \
+            __builtin_amdgcn_sched_barrier(0);                /* issued in slot order */                                           \
         }
-#pragma unroll
-        for (int k = 0; k < S; ++k) {
-            const unsigned int j = OSQ_FUSED_TOKEN(k);
-            if (j < V) {
-                MinMax acc;
-                acc.init();
-#pragma unroll
-                for (int u = 0; u < NV; ++u) {
-                    const v4u32 w = k < SR ? hold[k][u] : tmp[k - SR][u];
-                    acc.add4(as_float4(w));
-                    if (k >= SR) keep_w[((k - SR) * NV + u) * OSQ_WAVE] = w;
-                }
-                acc.wave_reduce();
-                acc.poison();
-                if (lane == 0) {
-                    publish_f32(&a.tok_min[chunk0 + k * kFusedWaves + wv], acc.mn);
-                    publish_f32(&a.tok_max[chunk0 + k * kFusedWaves + wv], acc.mx);
-                }
-            }
-            __builtin_amdgcn_sched_barrier(0);                // one token's temporaries at a time: the registers hold data
+#define OSQ_FUSED_A1_REDUCE(k)                                                                                                     \
+        if constexpr ((k) < S) {                                                                                                   \
+            MinMax acc;                                                                                                            \
+            acc.init();                                                                                                            \
+            _Pragma("unroll") for (int u = 0; u < NV; ++u) {                                                                       \
+                const v4u32 w = (k) < SR ? hold[(k) < SR ? (k) : 0][u] : tmp[(k) < SR ? 0 : (k) - SR][u];                          \
+                acc.add4(as_float4(w));                                                                                            \
+                if ((k) >= SR) keep_w[(((k) - SR) * NV + u) * OSQ_WAVE] = w;                                                       \
+            }                                                                                                                      \
+            acc.wave_reduce();                                                                                                     \
+            acc.poison();                                                                                                          \
+            pub_mn = set_lane(pub_mn, acc.mn, (k));                                                                                \
+            pub_mx = set_lane(pub_mx, acc.mx, (k));                                                                                \
+            __builtin_amdgcn_sched_barrier(0);                /* one token's temporaries at a time: the registers hold data */     \
         }
+#define OSQ_FUSED_A1_SLOTS(DO)   /* slots nval - 1 .. 0; nested, not a switch: the structurizer turns a switch that falls through into flag variables */ \
+        if (0 < nval) { if (1 < nval) { if (2 < nval) { if (3 < nval) { if (4 < nval) { if (5 < nval) { if (6 < nval) { if (7 < nval) { if (8 < nval) { \
+        DO(8) } DO(7) } DO(6) } DO(5) } DO(4) } DO(3) } DO(2) } DO(1) } DO(0) }
+        OSQ_FUSED_A1_SLOTS(OSQ_FUSED_A1_LOAD)
+        OSQ_FUSED_A1_SLOTS(OSQ_FUSED_A1_REDUCE)
+#undef OSQ_FUSED_A1_SLOTS
+#undef OSQ_FUSED_A1_REDUCE
+#undef OSQ_FUSED_A1_LOAD
     }
     // valid tokens beyond the capacity: reduced now, read again in phase C
-    for (unsigned int j = gwi + static_cast<unsigned int>(S) * nwv, local = S * kFusedWaves + wv; j < V; j += nwv, local += kFusedWaves) {
+    unsigned int npub = static_cast<unsigned int>(nval), pub_local = static_cast<unsigned int>(wv);      // lanes in use; lane 0's place in the chunk
+    for (unsigned int j = gwi + static_cast<unsigned int>(S) * nwv; j < V; j += nwv) {
         unsigned int b = 0u;
         for (unsigned int c = 0; c < Bu; c += OSQ_WAVE) {
             const unsigned int i = c + static_cast<unsigned int>(lane) + 1u;
@@ -528,10 +549,18 @@ __global__ __launch_bounds__(kFusedThreads) void observe_fq_fused_kernel(FusedAr
         }
         acc.wave_reduce();
         acc.poison();
-        if (lane == 0) {
-            publish_f32(&a.tok_min[chunk0 + local], acc.mn);
-            publish_f32(&a.tok_max[chunk0 + local], acc.mx);
+        pub_mn = set_lane(pub_mn, acc.mn, static_cast<int>(npub));
+        pub_mx = set_lane(pub_mx, acc.mx, static_cast<int>(npub));
+        if (++npub == static_cast<unsigned int>(OSQ_WAVE)) {      // (the launcher's limit of 192 values per chunk keeps a wave at 12 today)
+            publish_f32(&a.tok_min[chunk0 + pub_local + static_cast<unsigned int>(lane * kFusedWaves)], pub_mn);
+            publish_f32(&a.tok_max[chunk0 + pub_local + static_cast<unsigned int>(lane * kFusedWaves)], pub_mx);
+            pub_local += OSQ_WAVE * kFusedWaves;
+            npub = 0u;
         }
+    }
+    if (static_cast<unsigned int>(lane) < npub) {
+        publish_f32(&a.tok_min[chunk0 + pub_local + static_cast<unsigned int>(lane * kFusedWaves)], pub_mn);
+        publish_f32(&a.tok_max[chunk0 + pub_local + static_cast<unsigned int>(lane * kFusedWaves)], pub_mx);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // every publishing wave: its extrema have left this CU
     OSQ_FSTAMP(2);
@@ -548,8 +577,7 @@ __global__ __launch_bounds__(kFusedThreads) void observe_fq_fused_kernel(FusedAr
     if (a.gate != 1) {
 #pragma unroll
         for (int k = 0; k < SR; ++k) {
-            const unsigned int j = OSQ_FUSED_TOKEN(k);
-            if (j >= V && j < total) {
+            if (k >= nval && k < nall) {
 #pragma unroll
                 for (int u = 0; u < NV; ++u)
                     hold[k][u] = __builtin_amdgcn_raw_buffer_load_b128(xrs, lane_off, row[k] * kRowBytes + OSQ_FUSED_PIECE(u), kNt);
@@ -569,8 +597,7 @@ __global__ __launch_bounds__(kFusedThreads) void observe_fq_fused_kernel(FusedAr
     if (a.gate == 1) {
 #pragma unroll
         for (int k = 0; k < SR; ++k) {
-            const unsigned int j = OSQ_FUSED_TOKEN(k);
-            if (j >= V && j < total) {
+            if (k >= nval && k < nall) {
 #pragma unroll
                 for (int u = 0; u < NV; ++u)
                     hold[k][u] = __builtin_amdgcn_raw_buffer_load_b128(xrs, lane_off, row[k] * kRowBytes + OSQ_FUSED_PIECE(u), kNt);
@@ -579,8 +606,7 @@ __global__ __launch_bounds__(kFusedThreads) void observe_fq_fused_kernel(FusedAr
     }
 #pragma unroll
     for (int k = SR; k < S; ++k) {
-        const unsigned int j = OSQ_FUSED_TOKEN(k);
-        if (j >= V && j < total) {
+        if (k >= nval && k < nall) {
             v4u32 w[NV];
 #pragma unroll
             for (int u = 0; u < NV; ++u) w[u] = __builtin_amdgcn_raw_buffer_load_b128(xrs, lane_off, row[k] * kRowBytes + OSQ_FUSED_PIECE(u), kNt);
@@ -645,8 +671,7 @@ __global__ __launch_bounds__(kFusedThreads) void observe_fq_fused_kernel(FusedAr
     // ---- phase C: quantise from the registers / LDS
 #pragma unroll
     for (int k = 0; k < S; ++k) {
-        const unsigned int j = OSQ_FUSED_TOKEN(k);
-        if (j < total) {
+        if (k < nall) {
 #pragma unroll
             for (int u = 0; u < NV; ++u) {
                 const v4u32 w = k < SR ? hold[k < SR ? k : 0][u] : keep_w[((k - SR) * NV + u) * OSQ_WAVE];

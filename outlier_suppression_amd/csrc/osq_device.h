@@ -209,6 +209,10 @@ __device__ __forceinline__ float dpp_move(float v) {
 __device__ __forceinline__ float lane_value(float v, int lane) {
     return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), lane));
 }
+// v with lane `lane` (wave-uniform) replaced by x
+__device__ __forceinline__ float set_lane(float v, float x, int lane) {
+    return static_cast<int>(threadIdx.x & (OSQ_WAVE - 1)) == lane ? x : v;
+}
 constexpr int kDppQuadXor1 = 0xB1;       // quad_perm:[1,0,3,2]
 constexpr int kDppQuadXor2 = 0x4E;       // quad_perm:[2,3,0,1]
 constexpr int kDppRowHalfMirror = 0x141;
