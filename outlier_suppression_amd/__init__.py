@@ -9,6 +9,12 @@ through the C ABI in ``include/osq_hip.h``.  There is no CPU path.
 __version__ = "0.1.0"
 
 
+def _env_on(name, environ=None):
+    """What an on / off environment variable asks for: unset, empty or "0" -> False, anything else -> True."""
+    import os
+    return (os.environ if environ is None else environ).get(name, "") not in ("", "0")
+
+
 def set_strict(on=True, simd_width=8, backward=None, _lib=None):
     """Which rounding of the path's two whole-tensor sums is returned: the REFERENCE's own order, or the correctly rounded sum.
 
@@ -169,8 +175,7 @@ def set_sample_nucleus(on=True):
 
 def sample_nucleus_from_environment(environ=None):
     """What OSQ_SAMPLE_NUCLEUS asks for: unset, empty or "0" -> False, anything else -> True."""
-    import os
-    return (os.environ if environ is None else environ).get("OSQ_SAMPLE_NUCLEUS", "") not in ("", "0")
+    return _env_on("OSQ_SAMPLE_NUCLEUS", environ)
 
 
 def set_share_cross_kv(on=True):
@@ -197,68 +202,57 @@ def set_fast_lm_loss(on=True):
 
 def fast_lm_loss_from_environment(environ=None):
     """What OSQ_FAST_LM_LOSS asks for: unset, empty or "0" -> False, anything else -> True."""
-    import os
-    return (os.environ if environ is None else environ).get("OSQ_FAST_LM_LOSS", "") not in ("", "0")
+    return _env_on("OSQ_FAST_LM_LOSS", environ)
 
 
 def share_cross_kv_from_environment(environ=None):
     """What OSQ_SHARE_CROSS_KV asks for: unset, empty or "0" -> False, anything else -> True."""
-    import os
-    return (os.environ if environ is None else environ).get("OSQ_SHARE_CROSS_KV", "") not in ("", "0")
+    return _env_on("OSQ_SHARE_CROSS_KV", environ)
 
 
 def sample_advance_from_environment(environ=None):
     """What OSQ_SAMPLE_ADVANCE asks for: unset, empty or "0" -> False, anything else -> True."""
-    import os
-    return (os.environ if environ is None else environ).get("OSQ_SAMPLE_ADVANCE", "") not in ("", "0")
+    return _env_on("OSQ_SAMPLE_ADVANCE", environ)
 
 
 def sample_graph_from_environment(environ=None):
     """What OSQ_SAMPLE_GRAPH asks for: unset, empty or "0" -> False, anything else -> True."""
-    import os
-    return (os.environ if environ is None else environ).get("OSQ_SAMPLE_GRAPH", "") not in ("", "0")
+    return _env_on("OSQ_SAMPLE_GRAPH", environ)
 
 
 def greedy_advance_from_environment(environ=None):
     """What OSQ_GREEDY_ADVANCE asks for: unset, empty or "0" -> False, anything else -> True."""
-    import os
-    return (os.environ if environ is None else environ).get("OSQ_GREEDY_ADVANCE", "") not in ("", "0")
+    return _env_on("OSQ_GREEDY_ADVANCE", environ)
 
 
 def greedy_graph_from_environment(environ=None):
     """What OSQ_GREEDY_GRAPH asks for: unset, empty or "0" -> False, anything else -> True."""
-    import os
-    return (os.environ if environ is None else environ).get("OSQ_GREEDY_GRAPH", "") not in ("", "0")
+    return _env_on("OSQ_GREEDY_GRAPH", environ)
 
 
 def beam_graph_from_environment(environ=None):
     """What OSQ_BEAM_GRAPH asks for: unset, empty or "0" -> False, anything else -> True."""
-    import os
-    return (os.environ if environ is None else environ).get("OSQ_BEAM_GRAPH", "") not in ("", "0")
+    return _env_on("OSQ_BEAM_GRAPH", environ)
 
 
 def beam_advance_from_environment(environ=None):
     """What OSQ_BEAM_ADVANCE asks for: unset, empty or "0" -> False, anything else -> True."""
-    import os
-    return (os.environ if environ is None else environ).get("OSQ_BEAM_ADVANCE", "") not in ("", "0")
+    return _env_on("OSQ_BEAM_ADVANCE", environ)
 
 
 def beam_select_from_environment(environ=None):
     """What OSQ_BEAM_SELECT asks for: unset, empty or "0" -> False, anything else -> True."""
-    import os
-    return (os.environ if environ is None else environ).get("OSQ_BEAM_SELECT", "") not in ("", "0")
+    return _env_on("OSQ_BEAM_SELECT", environ)
 
 
 def graph_decode_from_environment(environ=None):
     """What OSQ_GRAPH_DECODE asks for: unset, empty or "0" -> False, anything else -> True."""
-    import os
-    return (os.environ if environ is None else environ).get("OSQ_GRAPH_DECODE", "") not in ("", "0")
+    return _env_on("OSQ_GRAPH_DECODE", environ)
 
 
 def cache_codes_from_environment(environ=None):
     """What OSQ_CACHE_CODES asks for: unset, empty or "0" -> False, anything else -> True."""
-    import os
-    return (os.environ if environ is None else environ).get("OSQ_CACHE_CODES", "") not in ("", "0")
+    return _env_on("OSQ_CACHE_CODES", environ)
 
 
 def reset_tier(_lib=None):
@@ -284,22 +278,18 @@ def reset_tier(_lib=None):
         set_strict(strict != "0", width, _lib=_lib)
     # unset: the default (one-launch LayerNorm site ON) -- a set_fast(False) of an earlier caller or test does not leak
     set_fast(os.environ.get("OSQ_FAST", "") != "0")
-    set_fast_softmax(os.environ.get("OSQ_FAST_SOFTMAX", "") not in ("", "0"))
-    set_fast_decode_attention(os.environ.get("OSQ_FAST_DECODE_ATTENTION", "") not in ("", "0"))
-    set_cache_codes(cache_codes_from_environment())
-    set_graph_decode(graph_decode_from_environment())
-    set_beam_select(beam_select_from_environment())
-    set_beam_advance(beam_advance_from_environment())
-    set_beam_graph(beam_graph_from_environment())
-    set_greedy_advance(greedy_advance_from_environment())
-    set_greedy_graph(greedy_graph_from_environment())
-    set_sample_advance(sample_advance_from_environment())
-    set_sample_graph(sample_graph_from_environment())
-    set_sample_nucleus(sample_nucleus_from_environment())
-    set_share_cross_kv(share_cross_kv_from_environment())
-    set_fast_lm_loss(fast_lm_loss_from_environment())
+    set_fast_softmax(_env_on("OSQ_FAST_SOFTMAX"))
+    set_fast_decode_attention(_env_on("OSQ_FAST_DECODE_ATTENTION"))
+    for setter, name in _SWITCHES:
+        setter(_env_on(name))
 
 
+# the switches reset_tier sets to what their environment variable says, off when it is unset
+_SWITCHES = ((set_cache_codes, "OSQ_CACHE_CODES"), (set_graph_decode, "OSQ_GRAPH_DECODE"), (set_beam_select, "OSQ_BEAM_SELECT"),
+             (set_beam_advance, "OSQ_BEAM_ADVANCE"), (set_beam_graph, "OSQ_BEAM_GRAPH"), (set_greedy_advance, "OSQ_GREEDY_ADVANCE"),
+             (set_greedy_graph, "OSQ_GREEDY_GRAPH"), (set_sample_advance, "OSQ_SAMPLE_ADVANCE"),
+             (set_sample_graph, "OSQ_SAMPLE_GRAPH"), (set_sample_nucleus, "OSQ_SAMPLE_NUCLEUS"),
+             (set_share_cross_kv, "OSQ_SHARE_CROSS_KV"), (set_fast_lm_loss, "OSQ_FAST_LM_LOSS"))
 _apply_environment = reset_tier
 
 

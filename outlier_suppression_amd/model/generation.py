@@ -39,9 +39,24 @@ and ``sample_graph=True`` as the two greedy switches (ops.sample_advance, graph_
 ``num_samples=n`` draws n sequences per input from one run of the encoder -- sequence j of input b at the Philox counter
 (b, length, j, 0) -- and, with ``share_cross_kv``, over one copy of the cross-attention keys / values per input;
 ``return_logprobs=True`` returns the log of the probability with which each token was drawn beside the tokens.
+
+The host layer is written once.  Both entry points start from _call_setup (settings, processors, encoder pass, the share
+decision, the cache) and take their ``graph`` switch through _graph_stepper; every ``model.last_*`` record is a
+graph_decode.Outcome, made by ``Outcome.asked`` from the call's argument and the package switch; the processors are read by
+_read_processors and the device by graph_decode._device_why_not, for every kernel plan alike; graph_decode.why_not and each
+plan are computed at most once per call (_once) and handed on; _greedy and _sample_eager are one loop, _eager_loop.
 """
+import functools
+from types import SimpleNamespace
+
 import torch
 from torch import nn
+
+from . import graph_decode
+from .. import util_layernorm
+from .graph_decode import Outcome, _device_why_not
+
+_once = functools.lru_cache(maxsize=None)        # on a lambda without arguments: what a call asks once and hands on
 
 _DEFAULTS = {"max_length": 20, "min_length": 0, "num_beams": 1, "no_repeat_ngram_size": 0, "forced_bos_token_id": None,
              "forced_eos_token_id": None, "length_penalty": 1.0, "early_stopping": False, "num_return_sequences": 1,
@@ -90,15 +105,42 @@ def _step_logits(model, seq, enc, attention_mask, cache, stepper=None):
     return logits[:, -1, :]
 
 
-class BeamSelectInfo:
+class BeamSelectInfo(Outcome):
     """What a generate() call did with its beam steps' continuations: ``selected`` steps through ops.beam_select, ``eager``
     steps through the torch lines, and, when none was selected, the ``reason``."""
+    COUNTERS = ("selected", "eager")
 
-    def __init__(self, reason=None):
-        self.selected, self.eager, self.reason = 0, 0, reason
 
-    def __repr__(self):
-        return f"BeamSelectInfo(selected={self.selected}, eager={self.eager}, reason={self.reason!r})"
+def _not_restated(proc):
+    return f"a logits processor the kernel does not restate ({type(proc).__name__})"
+
+
+def _read_processors(procs, device):
+    """One walk over a call's logits processors for the kernels that restate them (_BeamSelectPlan, _GreedyPlan).  Yields, in
+    the list's order: ("ngram", size); ("min_length", (min_length, the ids it bans: int64 on ``device``)); ("forced_bos",
+    processor); ("forced_eos", processor) -- what a forced token needs is the plan's to judge -- and, as its last item,
+    ("reason", text) at what no kernel restates: another class, a second n-gram or min-length processor, above 16 ids."""
+    from transformers.generation.logits_process import (ForcedBOSTokenLogitsProcessor, ForcedEOSTokenLogitsProcessor,
+                                                        MinLengthLogitsProcessor, NoRepeatNGramLogitsProcessor)
+    kinds = {NoRepeatNGramLogitsProcessor: "ngram", MinLengthLogitsProcessor: "min_length",
+             ForcedBOSTokenLogitsProcessor: "forced_bos", ForcedEOSTokenLogitsProcessor: "forced_eos"}
+    seen = set()
+    for proc in procs:
+        kind = kinds.get(type(proc))
+        if kind is None or (kind in seen and kind in ("ngram", "min_length")):
+            yield "reason", _not_restated(proc)
+            return
+        seen.add(kind)
+        if kind == "ngram":
+            yield kind, int(proc.ngram_size)
+        elif kind == "min_length":
+            ban = proc.eos_token_id.to(device=device, dtype=torch.int64).reshape(-1).contiguous()
+            yield kind, (int(proc.min_length), ban)
+            if ban.numel() > 16:
+                yield "reason", "more than 16 eos ids"
+                return
+        else:
+            yield kind, proc
 
 
 class _BeamSelectPlan:
@@ -106,32 +148,21 @@ class _BeamSelectPlan:
     on the device, and the steps on which a forced token fires (those take the torch lines)."""
 
     def __init__(self, procs, device, nb, vocab, keep, max_length):
-        from transformers.generation.logits_process import (ForcedBOSTokenLogitsProcessor, ForcedEOSTokenLogitsProcessor,
-                                                            MinLengthLogitsProcessor, NoRepeatNGramLogitsProcessor)
         self.ngram, self.min_length, self.eos, self.forced_at = 0, 0, None, set()
-        self.reason = None
-        if device.type != "cuda":
-            self.reason = "the tensors are on the CPU"
-        elif torch.is_grad_enabled():
-            self.reason = "autograd is on"
-        elif keep > vocab or keep > 64 or nb > 64 or max_length > 4096:
+        self.reason = _device_why_not(device)
+        if self.reason is None and (keep > vocab or keep > 64 or nb > 64 or max_length > 4096):
             self.reason = "the kernel takes keep <= min(vocab, 64), num_beams <= 64 and max_length <= 4096"
-        for proc in procs:
-            if self.reason is not None:
-                break
-            if type(proc) is NoRepeatNGramLogitsProcessor and self.ngram == 0:
-                self.ngram = int(proc.ngram_size)
-            elif type(proc) is MinLengthLogitsProcessor and self.eos is None:
-                self.min_length = int(proc.min_length)
-                self.eos = proc.eos_token_id.to(device=device, dtype=torch.int64).reshape(-1).contiguous()
-                if self.eos.numel() > 16:
-                    self.reason = "more than 16 eos ids"
-            elif type(proc) is ForcedBOSTokenLogitsProcessor:
+        for kind, value in () if self.reason is not None else _read_processors(procs, device):
+            if kind == "ngram":
+                self.ngram = value
+            elif kind == "min_length":
+                self.min_length, self.eos = value
+            elif kind == "forced_bos":
                 self.forced_at.add(1)
-            elif type(proc) is ForcedEOSTokenLogitsProcessor:
-                self.forced_at.add(int(proc.max_length) - 1)
+            elif kind == "forced_eos":
+                self.forced_at.add(int(value.max_length) - 1)
             else:
-                self.reason = f"a logits processor the kernel does not restate ({type(proc).__name__})"
+                self.reason = value
 
     def takes(self, cur, logits):
         return self.reason is None and cur not in self.forced_at and logits.is_cuda and logits.dtype == torch.float32
@@ -156,15 +187,10 @@ def _select_continuations(logits, flat, running_scores, procs, bsz, nb, vocab, k
     return torch.topk(log_probs, k=keep)
 
 
-class ShareCrossKvInfo:
+class ShareCrossKvInfo(Outcome):
     """What a generate() call did with ``share_cross_kv``: ``shared`` beam steps over one copy of the cross-attention keys /
     values per batch row, ``eager`` beam steps over one copy per beam, and, when none was shared, the ``reason``."""
-
-    def __init__(self, reason=None):
-        self.shared, self.eager, self.reason = 0, 0, reason
-
-    def __repr__(self):
-        return f"ShareCrossKvInfo(shared={self.shared}, eager={self.eager}, reason={self.reason!r})"
+    COUNTERS = ("shared", "eager")
 
 
 SHARE_MAX_SOURCE = 1024            # kMaxKv<8> of csrc/decode_attention.hip: the score rows of 8 queries in LDS
@@ -174,17 +200,15 @@ SHARE_MAX_BEAMS = 64               # kDecMaxGroup
 def _share_why_not(model, device, use_cache, nb, source_len):
     """None when a generate() call can hold the cross-attention keys / values once per batch row, else the reason it
     decodes as without ``share_cross_kv``.  Everything here is known before the first step."""
-    from . import graph_decode
     if nb == 1:
         return "one beam per batch row (num_beams == 1): there is nothing to share"
     if nb > SHARE_MAX_BEAMS:
         return f"num_beams above {SHARE_MAX_BEAMS}"
     if not use_cache:
         return "use_cache=False: there is no cache"
-    if device.type != "cuda":
-        return "the tensors are on the CPU"
-    if torch.is_grad_enabled():
-        return "autograd is on"
+    reason = _device_why_not(device)
+    if reason is not None:
+        return reason
     decoder = model.model.decoder
     if decoder.training and any(p > 0 for layer in decoder.layers for p in (layer.dropout, layer.encoder_attn.dropout)):
         return "dropout is active"
@@ -201,15 +225,10 @@ def _share_why_not(model, device, use_cache, nb, source_len):
     return None
 
 
-class BeamAdvanceInfo:
+class BeamAdvanceInfo(Outcome):
     """What a generate() call did with its beam steps' bookkeeping: ``advanced`` steps through ops.beam_advance, ``eager``
     steps through the torch lines, and, when none was advanced, the ``reason``."""
-
-    def __init__(self, reason=None):
-        self.advanced, self.eager, self.reason = 0, 0, reason
-
-    def __repr__(self):
-        return f"BeamAdvanceInfo(advanced={self.advanced}, eager={self.eager}, reason={self.reason!r})"
+    COUNTERS = ("advanced", "eager")
 
 
 # How ops.beam_advance divides by length ** length_penalty: as torch's GPU kernel divides by a host scalar, a multiplication
@@ -253,10 +272,9 @@ class _BeamState:
 
 def _advance_why_not(device, nb, keep, max_length, eos):
     """None when ops.beam_advance takes the steps of this call, else the reason the torch lines run."""
-    if device.type != "cuda":
-        return "the tensors are on the CPU"
-    if torch.is_grad_enabled():
-        return "autograd is on"
+    reason = _device_why_not(device)
+    if reason is not None:
+        return reason
     if keep > 64 or nb > 64 or not 2 <= max_length <= 4096:
         return "the kernel takes keep <= 64, num_beams <= 64 and max_length in [2, 4096]"
     if eos is not None and eos.numel() > 16:
@@ -325,67 +343,38 @@ def generate(model, input_ids, attention_mask=None, max_length=None, num_beams=N
     unknown = set(kwargs) - set(_DEFAULTS) - set(_NOT_COVERED)
     if unknown:
         raise TypeError(f"generate(): unexpected arguments {sorted(unknown)}")
-    get = lambda name, given=None: _setting(model, name, kwargs.get(name, given))  # noqa: E731
-    max_length, num_beams = get("max_length", max_length), get("num_beams", num_beams)
-    pad, start = get("pad_token_id"), get("decoder_start_token_id")
-    if start is None:
-        start = get("bos_token_id")
-    eos = get("eos_token_id")
-    eos_t = None if eos is None else torch.tensor(eos if isinstance(eos, (list, tuple)) else [eos], device=input_ids.device)
-    procs = _processors(get("min_length"), eos_t, get("no_repeat_ngram_size"), get("forced_bos_token_id"),
-                        get("forced_eos_token_id"), max_length, input_ids.device)
+    num_beams = _setting(model, "num_beams", num_beams)
+    s = _call_setup(model, input_ids, attention_mask, max_length, kwargs, use_cache, cache_codes, share_cross_kv, num_beams)
+    get, max_length, start, pad, eos_t, procs = s.get, s.max_length, s.start, s.pad, s.eos_t, s.procs
+    enc, attention_mask, share, cache = s.enc, s.attention_mask, s.share, s.cache
     n_return = get("num_return_sequences")
-    if attention_mask is None:
-        attention_mask = torch.ones_like(input_ids)
-    enc = model.get_encoder()(input_ids, attention_mask=attention_mask)
-    n_layers = len(model.model.decoder.layers)
-    from .. import util_layernorm
-    from .quant_bart import QuantizedBartCache
-    codes = util_layernorm.CACHE_CODES if cache_codes is None else bool(cache_codes)
-    # one copy of the cross-attention keys / values per batch row, where asked for and possible: decided once, here
-    share = ShareCrossKvInfo(None if (util_layernorm.SHARE_CROSS_KV if share_cross_kv is None else share_cross_kv) else "not asked for")
-    model.last_share_cross_kv = share
-    if share.reason is None:
-        share.reason = _share_why_not(model, enc.device, use_cache, num_beams, enc.shape[1])
-    cache = None
-    if use_cache:
-        cache = QuantizedBartCache(n_layers, capacity=max_length, codes=codes, cross_group=num_beams if share.reason is None else 1)
-        cache.cross_one_launch = share.reason is None
-    from . import graph_decode
+    vocab, keep = model.config.vocab_size, _beam_keep(eos_t, num_beams)
+    # what more than one of the switches below asks: answered on first need, once
+    graph_why = _once(lambda: graph_decode.why_not(model, enc.device, use_cache, max_length))
+    beam_plan = _once(lambda: _BeamSelectPlan(procs, enc.device, num_beams, vocab, keep, max_length))
+    greedy_plan = _once(lambda: _GreedyPlan(procs, enc.device, vocab, max_length, eos_t, pad))
     # a whole beam step as one captured graph: it implies the three switches below for this call, where nothing -- known
-    # before the first step -- stands against it; else the call decodes as without it
-    whole = graph_decode.BeamGraphInfo(None if (util_layernorm.BEAM_GRAPH if beam_graph is None else beam_graph) else "not asked for")
-    model.last_beam_graph = whole
+    # before the first step -- stands against it (one of them passed as False, greedy decoding, a reason one of them would
+    # give); else the call decodes as without it
+    whole = model.last_beam_graph = graph_decode.BeamGraphInfo.asked(beam_graph, "BEAM_GRAPH")
     if whole.reason is None:
-        whole.reason = _beam_graph_why_not(model, enc.device, use_cache, max_length, num_beams, eos_t, procs,
-                                           {"graph": graph, "beam_select": beam_select, "beam_advance": beam_advance})
+        whole.reason = (_passed_false(graph=graph, beam_select=beam_select, beam_advance=beam_advance)
+                        or ("greedy decoding has no beam step (beam_select at one beam is not argmax of the raw logits under ties)"
+                            if num_beams == 1 else None)
+                        or graph_why() or beam_plan().reason or _advance_why_not(enc.device, num_beams, keep, max_length, eos_t))
         if whole.reason is None:
             graph = beam_select = beam_advance = True
     # a whole greedy step as one captured graph: likewise, for the two switches it implies
-    gwhole = graph_decode.GreedyGraphInfo(None if (util_layernorm.GREEDY_GRAPH if greedy_graph is None else greedy_graph)
-                                          else "not asked for")
-    model.last_greedy_graph = gwhole
+    gwhole = model.last_greedy_graph = graph_decode.GreedyGraphInfo.asked(greedy_graph, "GREEDY_GRAPH")
     if gwhole.reason is None:
-        gwhole.reason = _greedy_graph_why_not(model, enc.device, use_cache, max_length, num_beams, eos_t, pad, procs,
-                                              {"graph": graph, "greedy_advance": greedy_advance})
+        gwhole.reason = (_passed_false(graph=graph, greedy_advance=greedy_advance)
+                         or ("beam search has no greedy step" if num_beams != 1 else None) or graph_why() or greedy_plan().reason)
         if gwhole.reason is None:
             graph = greedy_advance = True
-    # a captured decoding step (model/graph_decode.py), where asked for and possible; else the steps are issued as ever
-    stepper = None
-    if util_layernorm.GRAPH_DECODE if graph is None else graph:
-        info = graph_decode.DecodeGraphInfo(graph_decode.why_not(model, enc.device, use_cache, max_length))
-        if info.reason is None:
-            stepper = graph_decode.GenerateStepper(model, info)
-    else:
-        info = graph_decode.DecodeGraphInfo("not asked for")
-    model.last_decode_graph = info
-    select = BeamSelectInfo(None if (util_layernorm.BEAM_SELECT if beam_select is None else beam_select) else "not asked for")
-    model.last_beam_select = select
-    advance = BeamAdvanceInfo(None if (util_layernorm.BEAM_ADVANCE if beam_advance is None else beam_advance) else "not asked for")
-    model.last_beam_advance = advance
-    greedy = GreedyAdvanceInfo(None if (util_layernorm.GREEDY_ADVANCE if greedy_advance is None else greedy_advance)
-                               else "not asked for")
-    model.last_greedy_advance = greedy
+    stepper, _ = _graph_stepper(model, graph, graph_why)
+    select = model.last_beam_select = BeamSelectInfo.asked(beam_select, "BEAM_SELECT")
+    advance = model.last_beam_advance = BeamAdvanceInfo.asked(beam_advance, "BEAM_ADVANCE")
+    greedy = model.last_greedy_advance = GreedyAdvanceInfo.asked(greedy_advance, "GREEDY_ADVANCE")
     if num_beams != 1 and greedy.reason is None:
         greedy.reason = "beam search has no greedy step"
     if num_beams == 1:
@@ -396,37 +385,69 @@ def generate(model, input_ids, attention_mask=None, max_length=None, num_beams=N
         if n_return != 1:
             raise ValueError("greedy decoding returns one sequence per input (num_return_sequences must be 1)")
         if greedy.reason is None:
-            plan = _GreedyPlan(procs, enc.device, model.config.vocab_size, max_length, eos_t, pad)
-            greedy.reason = plan.reason
+            greedy.reason = greedy_plan().reason
         if greedy.reason is None:
-            return _checked(cache, _greedy_advanced(model, enc, attention_mask, start, plan, max_length, cache, stepper, greedy,
-                                                    gwhole if gwhole.reason is None else None))
+            return _checked(cache, _greedy_advanced(model, enc, attention_mask, start, greedy_plan(), max_length, cache, stepper,
+                                                    greedy, gwhole if gwhole.reason is None else None))
         return _checked(cache, _greedy(model, enc, attention_mask, start, pad, eos_t, procs, max_length, cache, stepper, greedy))
     if n_return > num_beams:
         raise ValueError("num_return_sequences must not exceed num_beams")
     return _checked(cache, _beam_search(model, enc, attention_mask, start, pad, eos_t, procs, max_length, num_beams, n_return,
                                         get("length_penalty"), get("early_stopping"), cache, stepper, select,
-                                        advance, whole if whole.reason is None else None, share))
+                                        advance, whole if whole.reason is None else None, share,
+                                        beam_plan() if select.reason is None else None))
+
+
+def _call_setup(model, input_ids, attention_mask, max_length, kwargs, use_cache, cache_codes, share_cross_kv, group):
+    """What generate() and sample() both start from: the settings (``get``, max_length, start, pad, eos_t), the logits
+    processors, the default mask and the encoder pass, the share decision for ``group`` decoder rows per input -- decided
+    once, here, and set on ``model.last_share_cross_kv`` -- and the cache with its ``cross_group`` and ``cross_one_launch``."""
+    from .quant_bart import QuantizedBartCache
+    s = SimpleNamespace()
+    s.get = get = lambda name, given=None: _setting(model, name, kwargs.get(name, given))  # noqa: E731
+    s.max_length = get("max_length", max_length)
+    s.pad, s.start = get("pad_token_id"), get("decoder_start_token_id")
+    if s.start is None:
+        s.start = get("bos_token_id")
+    eos = get("eos_token_id")
+    s.eos_t = None if eos is None else torch.tensor(eos if isinstance(eos, (list, tuple)) else [eos], device=input_ids.device)
+    s.procs = _processors(get("min_length"), s.eos_t, get("no_repeat_ngram_size"), get("forced_bos_token_id"),
+                          get("forced_eos_token_id"), s.max_length, input_ids.device)
+    s.attention_mask = torch.ones_like(input_ids) if attention_mask is None else attention_mask
+    s.enc = model.get_encoder()(input_ids, attention_mask=s.attention_mask)
+    codes = util_layernorm.CACHE_CODES if cache_codes is None else bool(cache_codes)
+    s.share = model.last_share_cross_kv = ShareCrossKvInfo.asked(share_cross_kv, "SHARE_CROSS_KV")
+    if s.share.reason is None:
+        s.share.reason = _share_why_not(model, s.enc.device, use_cache, group, s.enc.shape[1])
+    s.cache = None
+    if use_cache:
+        s.cache = QuantizedBartCache(len(model.model.decoder.layers), capacity=s.max_length, codes=codes,
+                                     cross_group=group if s.share.reason is None else 1)
+        s.cache.cross_one_launch = s.share.reason is None
+    return s
+
+
+def _graph_stepper(model, graph, why_not):
+    """The ``graph`` switch of a call: (stepper, info) -- a graph_decode.GenerateStepper where a captured decoding step is
+    asked for and ``why_not()`` has no objection, else None and the steps are issued as ever -- with ``info`` set on
+    ``model.last_decode_graph``."""
+    info = model.last_decode_graph = graph_decode.DecodeGraphInfo.asked(graph, "GRAPH_DECODE")
+    if info.reason is None:
+        info.reason = why_not()
+    return (graph_decode.GenerateStepper(model, info) if info.reason is None else None), info
+
+
+def _passed_false(**given):
+    """The reason a whole-step switch does not hold when one of the switches it implies was passed as False, else None."""
+    for name, value in given.items():
+        if value is not None and not value:
+            return f"{name}=False was passed"
+    return None
 
 
 def _beam_keep(eos, nb):
     """How many continuations of a batch row a beam step keeps: room for every beam to end on each eos id and go on."""
     return max(2, 1 + (eos.shape[0] if eos is not None else 0)) * nb
-
-
-def _beam_graph_why_not(model, device, use_cache, max_length, nb, eos, procs, given):
-    """None when a generate() call can capture its beam steps whole, else the reason it decodes as without ``beam_graph``:
-    one of the three switches it implies was passed as False, decoding is greedy, or one of them would give a reason."""
-    from . import graph_decode
-    for name, value in given.items():
-        if value is not None and not value:
-            return f"{name}=False was passed"
-    if nb == 1:
-        return "greedy decoding has no beam step (beam_select at one beam is not argmax of the raw logits under ties)"
-    vocab, keep = model.config.vocab_size, _beam_keep(eos, nb)
-    return (graph_decode.why_not(model, device, use_cache, max_length)
-            or _BeamSelectPlan(procs, device, nb, vocab, keep, max_length).reason
-            or _advance_why_not(device, nb, keep, max_length, eos))
 
 
 def _checked(cache, tokens):
@@ -441,13 +462,22 @@ def _checked(cache, tokens):
     return tokens
 
 
-def _greedy(model, enc, attention_mask, start, pad, eos, procs, max_length, cache, stepper=None, advance=None):
-    b = enc.shape[0]
+def _eager_loop(model, enc, attention_mask, start, pad, eos, procs, max_length, cache, stepper, advance, pick, rows=None,
+                logprobs=False):
+    """Decoding by the torch lines, one token per row and step: ``pick(scores, cur)`` gives the next tokens [rows] from the
+    processed scores at history length ``cur`` and, with ``logprobs``, their log-probabilities (0 for a finished row, and at
+    column 0); returns the sequences, with ``logprobs`` (sequences, logprobs)."""
+    b = enc.shape[0] if rows is None else rows
     seq = torch.full((b, 1), start, dtype=torch.long, device=enc.device)
+    lps = torch.zeros((b, 1), dtype=torch.float32, device=enc.device) if logprobs else None
     unfinished = torch.ones(b, dtype=torch.long, device=enc.device)
     while seq.shape[1] < max_length:
         scores = procs(seq, _step_logits(model, seq, enc, attention_mask, cache, stepper).to(torch.float32))
-        nxt = torch.argmax(scores, dim=-1)
+        nxt, lp = pick(scores, seq.shape[1])
+        if lps is not None:
+            if eos is not None:
+                lp = torch.where(unfinished.bool(), lp, torch.zeros_like(lp))
+            lps = torch.cat([lps, lp[:, None]], dim=-1)
         if eos is not None:
             nxt = nxt * unfinished + pad * (1 - unfinished)
         seq = torch.cat([seq, nxt[:, None]], dim=-1)
@@ -457,18 +487,18 @@ def _greedy(model, enc, attention_mask, start, pad, eos, procs, max_length, cach
             unfinished = unfinished & ~torch.isin(nxt, eos)
             if unfinished.max() == 0:
                 break
-    return seq
+    return seq if lps is None else (seq, lps)
 
 
-class GreedyAdvanceInfo:
+def _greedy(model, enc, attention_mask, start, pad, eos, procs, max_length, cache, stepper=None, advance=None):
+    return _eager_loop(model, enc, attention_mask, start, pad, eos, procs, max_length, cache, stepper, advance,
+                       lambda scores, cur: (torch.argmax(scores, dim=-1), None))
+
+
+class GreedyAdvanceInfo(Outcome):
     """What a generate() call did with its greedy steps: ``advanced`` steps through ops.greedy_advance, ``eager`` steps
     through the torch lines, and, when none was advanced, the ``reason``."""
-
-    def __init__(self, reason=None):
-        self.advanced, self.eager, self.reason = 0, 0, reason
-
-    def __repr__(self):
-        return f"GreedyAdvanceInfo(advanced={self.advanced}, eager={self.eager}, reason={self.reason!r})"
+    COUNTERS = ("advanced", "eager")
 
 
 class _GreedyPlan:
@@ -476,42 +506,33 @@ class _GreedyPlan:
     device, the forced tokens, the eos ids and the pad -- or the ``reason`` the torch lines run instead."""
 
     def __init__(self, procs, device, vocab, max_length, eos, pad):
-        from transformers.generation.logits_process import (ForcedBOSTokenLogitsProcessor, ForcedEOSTokenLogitsProcessor,
-                                                            MinLengthLogitsProcessor, NoRepeatNGramLogitsProcessor)
         self.ngram, self.min_length, self.ban, self.forced_bos, self.forced_eos = 0, 0, None, None, None
         self.eos = None if eos is None else eos.to(device=device, dtype=torch.int64).reshape(-1).contiguous()
         self.pad = 0 if pad is None else int(pad)
         self.max_length = max_length
-        self.reason = None
-        if device.type != "cuda":
-            self.reason = "the tensors are on the CPU"
-        elif torch.is_grad_enabled():
-            self.reason = "autograd is on"
-        elif not 2 <= max_length <= 4096:
+        self.reason = _device_why_not(device)
+        if self.reason is None and not 2 <= max_length <= 4096:
             self.reason = "the kernel takes max_length in [2, 4096]"
-        elif self.eos is not None and self.eos.numel() > 16:
-            self.reason = "more than 16 eos ids"
-        elif self.eos is not None and pad is None:
-            self.reason = "pad_token_id is missing and an eos is set"
-        elif self.eos is not None and not 0 <= self.pad < vocab:
-            self.reason = "pad_token_id is outside the vocabulary"
-        for proc in procs:
-            if self.reason is not None:
+        elif self.reason is None and self.eos is not None:
+            if self.eos.numel() > 16:
+                self.reason = "more than 16 eos ids"
+            elif pad is None:
+                self.reason = "pad_token_id is missing and an eos is set"
+            elif not 0 <= self.pad < vocab:
+                self.reason = "pad_token_id is outside the vocabulary"
+        for kind, value in () if self.reason is not None else _read_processors(procs, device):
+            if kind == "ngram":
+                self.ngram = value
+            elif kind == "min_length":
+                self.min_length, self.ban = value
+            elif kind == "forced_bos" and self.forced_bos is None:
+                self.forced_bos = int(value.bos_token_id)
+            elif (kind == "forced_eos" and self.forced_eos is None and value.eos_token_id.numel() == 1
+                  and int(value.max_length) == max_length):
+                self.forced_eos = int(value.eos_token_id.reshape(-1)[0])
+            else:                                    # the reader's reason, or a forced token this kernel does not take
+                self.reason = value if kind == "reason" else _not_restated(value)
                 break
-            if type(proc) is NoRepeatNGramLogitsProcessor and self.ngram == 0:
-                self.ngram = int(proc.ngram_size)
-            elif type(proc) is MinLengthLogitsProcessor and self.ban is None:
-                self.min_length = int(proc.min_length)
-                self.ban = proc.eos_token_id.to(device=device, dtype=torch.int64).reshape(-1).contiguous()
-                if self.ban.numel() > 16:
-                    self.reason = "more than 16 eos ids"
-            elif type(proc) is ForcedBOSTokenLogitsProcessor and self.forced_bos is None:
-                self.forced_bos = int(proc.bos_token_id)
-            elif (type(proc) is ForcedEOSTokenLogitsProcessor and self.forced_eos is None and proc.eos_token_id.numel() == 1
-                  and int(proc.max_length) == max_length):
-                self.forced_eos = int(proc.eos_token_id.reshape(-1)[0])
-            else:
-                self.reason = f"a logits processor the kernel does not restate ({type(proc).__name__})"
         if self.reason is None and any(t is not None and not 0 <= t < vocab for t in (self.forced_bos, self.forced_eos)):
             self.reason = "a forced token is outside the vocabulary"
 
@@ -520,20 +541,6 @@ class _GreedyPlan:
         if self.forced_eos is not None and cur == self.max_length - 1:
             return self.forced_eos
         return self.forced_bos if cur == 1 else None
-
-
-def _greedy_graph_why_not(model, device, use_cache, max_length, nb, eos, pad, procs, given):
-    """None when a generate() call can capture its greedy steps whole, else the reason it decodes as without
-    ``greedy_graph``: one of the two switches it implies was passed as False, the search has beams, or one of them would
-    give a reason."""
-    from . import graph_decode
-    for name, value in given.items():
-        if value is not None and not value:
-            return f"{name}=False was passed"
-    if nb != 1:
-        return "beam search has no greedy step"
-    return (graph_decode.why_not(model, device, use_cache, max_length)
-            or _GreedyPlan(procs, device, model.config.vocab_size, max_length, eos, pad).reason)
 
 
 def _greedy_advanced(model, enc, attention_mask, start, plan, max_length, cache, stepper, advance, whole=None, draw=None):
@@ -549,7 +556,6 @@ def _greedy_advanced(model, enc, attention_mask, start, plan, max_length, cache,
     a captured graph that holds all of the above (graph_decode.GreedyStepGraph), a step on which a forced token fires
     included: the kernel takes the forced token itself."""
     from .. import ops
-    from . import graph_decode
     if draw is None:
         bufs = ops.GreedyBuffers(enc.shape[0], max_length, enc.device, model.config.vocab_size)
     else:
@@ -599,9 +605,6 @@ class SampleAdvanceInfo(GreedyAdvanceInfo):
     """What a sample() call did with its steps: ``advanced`` steps through ops.sample_advance, ``eager`` steps through the
     torch lines (sampling.select_torch), and, when none was advanced, the ``reason``."""
 
-    def __repr__(self):
-        return f"SampleAdvanceInfo(advanced={self.advanced}, eager={self.eager}, reason={self.reason!r})"
-
 
 NUCLEUS_MAX_VOCAB = 51200          # kSnMaxVocab of csrc/sample_nucleus.hip: what one workgroup holds in registers
 
@@ -626,30 +629,14 @@ def _sample_eager(model, enc, attention_mask, start, pad, eos, procs, max_length
     ``draw`` with ``logprobs``: returns (sequences, logprobs), sampling.token_logprob of every drawn token (a forced token
     is a row's one survivor: 0), 0 for a finished row."""
     from . import sampling
-    group = draw.get("group", 1)
-    b = draw.get("rows", enc.shape[0])
-    seq = torch.full((b, 1), start, dtype=torch.long, device=enc.device)
-    lps = torch.zeros((b, 1), dtype=torch.float32, device=enc.device) if draw.get("logprobs") else None
-    unfinished = torch.ones(b, dtype=torch.long, device=enc.device)
-    while seq.shape[1] < max_length:
-        scores = procs(seq, _step_logits(model, seq, enc, attention_mask, cache, stepper).to(torch.float32))
-        u = (sampling.uniforms(draw["seed"], b // group, seq.shape[1], group) if group > 1 else
-             sampling.uniforms(draw["seed"], b, seq.shape[1]))
-        nxt = sampling.select_torch(scores, u, draw["temperature"], draw["top_k"], draw["top_p"])
-        if lps is not None:
-            lp = sampling.token_logprob(scores, nxt, draw["temperature"], draw["top_k"], draw["top_p"])
-            if eos is not None:
-                lp = torch.where(unfinished.bool(), lp, torch.zeros_like(lp))
-            lps = torch.cat([lps, lp[:, None]], dim=-1)
-        if eos is not None:
-            nxt = nxt * unfinished + pad * (1 - unfinished)
-        seq = torch.cat([seq, nxt[:, None]], dim=-1)
-        advance.eager += 1
-        if eos is not None:
-            unfinished = unfinished & ~torch.isin(nxt, eos)
-            if unfinished.max() == 0:
-                break
-    return seq if lps is None else (seq, lps)
+    group, b, logprobs = draw.get("group", 1), draw.get("rows", enc.shape[0]), bool(draw.get("logprobs"))
+    knobs = (draw["temperature"], draw["top_k"], draw["top_p"])
+
+    def pick(scores, cur):
+        u = sampling.uniforms(draw["seed"], b // group, cur, group) if group > 1 else sampling.uniforms(draw["seed"], b, cur)
+        nxt = sampling.select_torch(scores, u, *knobs)
+        return nxt, sampling.token_logprob(scores, nxt, *knobs) if logprobs else None
+    return _eager_loop(model, enc, attention_mask, start, pad, eos, procs, max_length, cache, stepper, advance, pick, b, logprobs)
 
 
 def sample(model, input_ids, attention_mask=None, max_length=None, seed=None, temperature=1.0, top_k=50, top_p=1.0,
@@ -698,32 +685,9 @@ def sample(model, input_ids, attention_mask=None, max_length=None, seed=None, te
     if seed is None:
         seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64))
     draw = {"seed": int(seed) & 0xFFFFFFFFFFFFFFFF, "temperature": temperature, "top_k": top_k, "top_p": top_p}
-    get = lambda name, given=None: _setting(model, name, kwargs.get(name, given))  # noqa: E731
-    max_length = get("max_length", max_length)
-    pad, start = get("pad_token_id"), get("decoder_start_token_id")
-    if start is None:
-        start = get("bos_token_id")
-    eos = get("eos_token_id")
-    eos_t = None if eos is None else torch.tensor(eos if isinstance(eos, (list, tuple)) else [eos], device=input_ids.device)
-    procs = _processors(get("min_length"), eos_t, get("no_repeat_ngram_size"), get("forced_bos_token_id"),
-                        get("forced_eos_token_id"), max_length, input_ids.device)
-    if attention_mask is None:
-        attention_mask = torch.ones_like(input_ids)
-    enc = model.get_encoder()(input_ids, attention_mask=attention_mask)
-    from .. import util_layernorm
-    from . import graph_decode
-    from .quant_bart import QuantizedBartCache
-    codes = util_layernorm.CACHE_CODES if cache_codes is None else bool(cache_codes)
-    # one copy of the cross-attention keys / values per input, where asked for and possible: decided once, here
-    share = ShareCrossKvInfo(
-        _share_why_not(model, enc.device, use_cache, n, enc.shape[1])
-        if (util_layernorm.SHARE_CROSS_KV if share_cross_kv is None else share_cross_kv) else "not asked for")
-    model.last_share_cross_kv = share
-    cache = None
-    if use_cache:
-        cache = QuantizedBartCache(len(model.model.decoder.layers), capacity=max_length, codes=codes,
-                                   cross_group=n if share.reason is None else 1)
-        cache.cross_one_launch = share.reason is None
+    s = _call_setup(model, input_ids, attention_mask, max_length, kwargs, use_cache, cache_codes, share_cross_kv, n)
+    max_length, start, pad, eos_t, procs = s.max_length, s.start, s.pad, s.eos_t, s.procs
+    enc, attention_mask, share, cache = s.enc, s.attention_mask, s.share, s.cache
     if n > 1 or return_logprobs:
         draw.update(group=n, rows=enc.shape[0] * n, logprobs=bool(return_logprobs))
     if n > 1 and share.reason is not None:
@@ -732,31 +696,18 @@ def sample(model, input_ids, attention_mask=None, max_length=None, seed=None, te
     plan = _GreedyPlan(procs, enc.device, model.config.vocab_size, max_length, eos_t, pad)
     nucleus = bool(util_layernorm.SAMPLE_NUCLEUS if sample_nucleus is None else sample_nucleus)
     draw["nucleus"] = nucleus and top_k == 0 and top_p < 1.0
+    graph_why = _once(lambda: graph_decode.why_not(model, enc.device, use_cache, max_length))
+    kernel_why = _sample_why_not(plan, top_k, top_p, nucleus, model.config.vocab_size)
     # a whole step as one captured graph: it implies the two switches below for this call, where nothing stands against it
-    whole = graph_decode.SampleGraphInfo(None if (util_layernorm.SAMPLE_GRAPH if sample_graph is None else sample_graph)
-                                         else "not asked for")
-    model.last_sample_graph = whole
+    whole = model.last_sample_graph = graph_decode.SampleGraphInfo.asked(sample_graph, "SAMPLE_GRAPH")
     if whole.reason is None:
-        for name, value in (("graph", graph), ("sample_advance", sample_advance)):
-            if whole.reason is None and value is not None and not value:
-                whole.reason = f"{name}=False was passed"
-        whole.reason = (whole.reason or graph_decode.why_not(model, enc.device, use_cache, max_length)
-                        or _sample_why_not(plan, top_k, top_p, nucleus, model.config.vocab_size))
+        whole.reason = _passed_false(graph=graph, sample_advance=sample_advance) or graph_why() or kernel_why
         if whole.reason is None:
             graph = sample_advance = True
-    stepper = None
-    if util_layernorm.GRAPH_DECODE if graph is None else graph:
-        info = graph_decode.DecodeGraphInfo(graph_decode.why_not(model, enc.device, use_cache, max_length))
-        if info.reason is None:
-            stepper = graph_decode.GenerateStepper(model, info)
-    else:
-        info = graph_decode.DecodeGraphInfo("not asked for")
-    model.last_decode_graph = info
-    advance = SampleAdvanceInfo(None if (util_layernorm.SAMPLE_ADVANCE if sample_advance is None else sample_advance)
-                                else "not asked for")
-    model.last_sample_advance = advance
+    stepper, _ = _graph_stepper(model, graph, graph_why)
+    advance = model.last_sample_advance = SampleAdvanceInfo.asked(sample_advance, "SAMPLE_ADVANCE")
     if advance.reason is None:
-        advance.reason = _sample_why_not(plan, top_k, top_p, nucleus, model.config.vocab_size)
+        advance.reason = kernel_why
     if advance.reason is None:
         out = _greedy_advanced(model, enc, attention_mask, start, plan, max_length, cache, stepper, advance,
                                whole if whole.reason is None else None, draw)
@@ -776,10 +727,11 @@ def _gather(t, idx):
 
 
 def _beam_search(model, enc, attention_mask, start, pad, eos, procs, max_length, nb, n_return, length_penalty,
-                 early_stopping, cache, stepper=None, select=None, advance=None, whole=None, share=None):
+                 early_stopping, cache, stepper=None, select=None, advance=None, whole=None, share=None, plan=None):
     """transformers' vectorised beam search (GenerationMixin._beam_search, 5.x) with the prompt of one start token.
     ``share`` (a ShareCrossKvInfo without a reason): the encoder states and their mask stay at one row per input -- the cache
-    was built with ``cross_group=nb`` and the cross-attention reads one copy of its keys / values per batch row."""
+    was built with ``cross_group=nb`` and the cross-attention reads one copy of its keys / values per batch row.  ``plan``:
+    the call's _BeamSelectPlan where generate() has built it; None: it is built here, where ``select`` asks for one."""
     dev = enc.device
     bsz = enc.shape[0]
     if share is not None and share.reason is not None:
@@ -794,9 +746,10 @@ def _beam_search(model, enc, attention_mask, start, pad, eos, procs, max_length,
     fill = (pad if pad else int(eos[0])) if eos is not None else -1
     state = _BeamState.start(bsz, nb, max_length, start, fill, dev)
     offsets = torch.arange(bsz, device=dev).view(-1, 1) * nb
-    plan = None
-    if select is not None and select.reason is None:
-        plan = _BeamSelectPlan(procs, dev, nb, vocab, keep, max_length)
+    if select is None or select.reason is not None:
+        plan = None
+    else:
+        plan = _BeamSelectPlan(procs, dev, nb, vocab, keep, max_length) if plan is None else plan
         select.reason = plan.reason
     if advance is not None and advance.reason is None:
         advance.reason = _advance_why_not(dev, nb, keep, max_length, eos)
@@ -843,7 +796,6 @@ def _beam_search_advanced(model, enc, attention_mask, eos, procs, max_length, nb
     captured graph that holds all of the above (graph_decode.BeamStepGraphs) -- but a step on which a forced token fires,
     which is issued launch by launch on the capture stream and takes the lines below."""
     from .. import ops
-    from . import graph_decode
     bsz = state.running.shape[0]
     prompt = cur = 1
     now, spare = sets = state.paired()

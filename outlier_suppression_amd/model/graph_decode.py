@@ -34,6 +34,11 @@ graph above; the kernel takes a forced token itself at its position, so no step 
 
 The words are those of issuing the same steps one by one with the one-launch attention on (util_layernorm.
 FUSE_DECODE_ATTENTION): a captured step always uses it, cross-attention included, whatever the switch says.
+
+All three kinds of step look their graph up, capture it or replay it through one method, GraphDecoder.replay: they differ in
+the key, in the chain they issue while capturing, and in the records that count.  Those records -- and generation.py's -- are
+subclasses of Outcome, below; _device_why_not is the device / autograd pair of reasons that every kernel path of decoding
+starts from.
 """
 import time
 
@@ -43,30 +48,55 @@ from .. import util_layernorm as _UL
 from ..quantization.fake_quant import QuantizeBase
 
 
-class DecodeGraphInfo:
-    """What a generate() call did with its decoding steps: ``captured`` graphs, ``replays`` of them, and, when no step was
-    captured, the ``reason``.  ``capture_seconds``: host time spent capturing and instantiating, the device idle."""
+class Outcome:
+    """What a call did with one of its switches, as ``model.last_*`` holds it: the integer ``COUNTERS`` a subclass names,
+    its ``SECONDS`` (floats that stay out of the repr), and, when the call decoded as without the switch, the ``reason``."""
+    COUNTERS, SECONDS = (), ()
 
     def __init__(self, reason=None):
-        self.captured, self.replays, self.reason, self.capture_seconds = 0, 0, reason, 0.0
+        for name in self.COUNTERS:
+            setattr(self, name, 0)
+        for name in self.SECONDS:
+            setattr(self, name, 0.0)
+        self.reason = reason
 
     def __repr__(self):
-        return f"DecodeGraphInfo(captured={self.captured}, replays={self.replays}, reason={self.reason!r})"
+        counts = "".join(f"{name}={getattr(self, name)}, " for name in self.COUNTERS)
+        return f"{type(self).__name__}({counts}reason={self.reason!r})"
+
+    @classmethod
+    def asked(cls, given, flag):
+        """The record of a call that was passed ``given`` for a switch whose package-wide value is util_layernorm's
+        ``flag``, read now: without a reason where either asks for it, else "not asked for"."""
+        return cls(None if (getattr(_UL, flag) if given is None else given) else "not asked for")
+
+
+class DecodeGraphInfo(Outcome):
+    """What a generate() call did with its decoding steps: ``captured`` graphs, ``replays`` of them, and, when no step was
+    captured, the ``reason``.  ``capture_seconds``: host time spent capturing and instantiating, the device idle."""
+    COUNTERS, SECONDS = ("captured", "replays"), ("capture_seconds",)
 
 
 def _plain(q):
     return q.fake_quant_enabled == 1 and q.observer_enabled != 1 and q.ch_axis == -1 and q.scale.is_cuda
 
 
+def _device_why_not(device, between=None):
+    """The reason none of the decoding kernels runs for tensors on ``device`` under the present autograd mode, or None.
+    ``between``: a caller's own reason that ranks after the device and before autograd."""
+    if device.type != "cuda":
+        return "the tensors are on the CPU"
+    if between is not None:
+        return between
+    return "autograd is on" if torch.is_grad_enabled() else None
+
+
 def why_not(model, device, use_cache=True, max_length=None):
     """None when a decoding step of ``model`` can be captured, else the reason it cannot (generate() then decodes as it
     always did).  Everything here is known before the first step."""
-    if device.type != "cuda":
-        return "the tensors are on the CPU"
-    if not use_cache:
-        return "use_cache=False: there is no cached step"
-    if torch.is_grad_enabled():
-        return "autograd is on"
+    reason = _device_why_not(device, None if use_cache else "use_cache=False: there is no cached step")
+    if reason is not None:
+        return reason
     if not _UL.FUSE_KV_APPEND:
         return "the one-launch KV append is off (util_layernorm.FUSE_KV_APPEND)"
     decoder = model.model.decoder
@@ -175,34 +205,41 @@ class GraphDecoder:
             self.warm = True
             return self._issued()
         # the graph this step needs: in place, or moving from the current buffers into their partners
-        key = (cache.reorder_pending(), cache._k[0].data_ptr())
-        entry = self.graphs.get(key)
+        return self.replay(self.graphs, (cache.reorder_pending(), cache._k[0].data_ptr()), self._issue, (self.info,))
+
+    def replay(self, graphs, key, chain, infos, reorders=False):
+        """One step by a replay of ``graphs[key]``: the one capture-or-replay path of the model step and of the whole
+        steps below.  A missing graph is captured first -- ``chain()`` issues the step's launches on the capturing stream
+        and returns its logits -- which does the host side of the step as well: the cache's counters move as the model
+        and the chain run, recorded, not executed.  On a later replay nothing of that runs, so the host side is done
+        here: ``cache.stepped()`` and, where the chain ``reorders``, ``cache.reorder_carried()``.  Every record of
+        ``infos`` counts the capture, its seconds and the replay.  Returns the graph's logits tensor."""
+        entry = graphs.get(key)
         if entry is None:
             t0 = time.perf_counter()
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph, stream=self.stream):
-                logits = self._issue()                      # recorded, not run: the host side of the step is now done
-            entry = self.graphs[key] = (graph, logits)
-            self.info.captured += 1
-            self.info.capture_seconds += time.perf_counter() - t0
+                logits = chain()
+            entry = graphs[key] = (graph, logits)
+            seconds = time.perf_counter() - t0
+            for info in infos:
+                info.captured += 1
+                info.capture_seconds += seconds
         else:
-            cache.stepped()
+            self.cache.stepped()
+            if reorders:
+                self.cache.reorder_carried()
         entry[0].replay()
-        self.info.replays += 1
+        for info in infos:
+            info.replays += 1
         return entry[1]
 
 
-class BeamGraphInfo:
+class BeamGraphInfo(Outcome):
     """What a generate() call did with ``beam_graph``: ``captured`` whole-step graphs, ``replays`` of them, steps ``issued``
     launch by launch because a forced token fired on them, and, when the call decoded as without the switch, the
     ``reason``.  ``capture_seconds``: host time spent capturing and instantiating."""
-
-    def __init__(self, reason=None):
-        self.captured, self.replays, self.issued, self.reason, self.capture_seconds = 0, 0, 0, reason, 0.0
-
-    def __repr__(self):
-        return (f"BeamGraphInfo(captured={self.captured}, replays={self.replays}, issued={self.issued}, "
-                f"reason={self.reason!r})")
+    COUNTERS, SECONDS = ("captured", "replays", "issued"), ("capture_seconds",)
 
 
 class BeamStepGraphs:
@@ -243,36 +280,15 @@ class BeamStepGraphs:
         decoder, cache = self.decoder, self.decoder.cache
         decoder.check_room()
         now, spare = self.sets[which], self.sets[1 - which]
-        key = (which, cache.reorder_pending(), cache._k[0].data_ptr())
-        entry = self.graphs.get(key)
-        if entry is None:
-            t0 = time.perf_counter()
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph, stream=decoder.stream):
-                logits = self._chain(now, spare)    # recorded, not run; the cache's host side of the step is now done
-            entry = self.graphs[key] = (graph, logits)
-            self.info.captured += 1
-            self.info.capture_seconds += time.perf_counter() - t0
-            decoder.info.captured += 1
-            decoder.info.capture_seconds += time.perf_counter() - t0
-        else:
-            cache.stepped()
-            cache.reorder_carried()
-        entry[0].replay()
-        self.info.replays += 1
-        decoder.info.replays += 1
+        decoder.replay(self.graphs, (which, cache.reorder_pending(), cache._k[0].data_ptr()),
+                       lambda: self._chain(now, spare), (self.info, decoder.info), reorders=True)
         return spare
 
 
-class GreedyGraphInfo:
+class GreedyGraphInfo(Outcome):
     """What a generate() call did with ``greedy_graph``: ``captured`` whole-step graphs, ``replays`` of them, and, when the
     call decoded as without the switch, the ``reason``.  ``capture_seconds``: host time spent capturing and instantiating."""
-
-    def __init__(self, reason=None):
-        self.captured, self.replays, self.reason, self.capture_seconds = 0, 0, reason, 0.0
-
-    def __repr__(self):
-        return f"GreedyGraphInfo(captured={self.captured}, replays={self.replays}, reason={self.reason!r})"
+    COUNTERS, SECONDS = ("captured", "replays"), ("capture_seconds",)
 
 
 class GreedyStepGraph:
@@ -301,30 +317,11 @@ class GreedyStepGraph:
     def step(self):
         decoder, cache = self.decoder, self.decoder.cache
         decoder.check_room()
-        key = (cache.reorder_pending(), cache._k[0].data_ptr())
-        entry = self.graphs.get(key)
-        if entry is None:
-            t0 = time.perf_counter()
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph, stream=decoder.stream):
-                logits = self._chain()              # recorded, not run; the cache's host side of the step is now done
-            entry = self.graphs[key] = (graph, logits)
-            self.info.captured += 1
-            self.info.capture_seconds += time.perf_counter() - t0
-            decoder.info.captured += 1
-            decoder.info.capture_seconds += time.perf_counter() - t0
-        else:
-            cache.stepped()
-        entry[0].replay()
-        self.info.replays += 1
-        decoder.info.replays += 1
+        decoder.replay(self.graphs, (cache.reorder_pending(), cache._k[0].data_ptr()), self._chain, (self.info, decoder.info))
 
 
 class SampleGraphInfo(GreedyGraphInfo):
     """What a sample() call did with ``sample_graph``: as GreedyGraphInfo."""
-
-    def __repr__(self):
-        return f"SampleGraphInfo(captured={self.captured}, replays={self.replays}, reason={self.reason!r})"
 
 
 class SampleStepGraph(GreedyStepGraph):

@@ -1862,38 +1862,65 @@ def beam_select(logits, running_scores, keep, seq=None, cur=0, ngram=0, ban_ids=
     ``ngram > 0``; ``cur`` its current length.  ban_ids: None or up to 16 int64 ids on the device, banned in every row.
     Returns (top_lp [bsz, keep] fp32, top_idx [bsz, keep] int64, the flat index beam * vocab + token).  Three launches on the
     current stream, no synchronisation; a shape the library does not take raises."""
+    return _beam_select("beam_select", logits, running_scores, keep, seq, cur, ngram, ban_ids)
+
+
+def _beam_select(what, logits, running_scores, keep, seq, cur, ngram, ban_ids, at=None, outs=(None, None, None)):
+    """The one body of beam_select and beam_select_at (``what``, in front of every message).  ``at``: None -- ``cur`` is the
+    host's position and running_scores is made contiguous -- or (cur_add, cur_max, ban_below) with ``cur`` the device word
+    and a running_scores that must be contiguous already.  ``outs``: (top_lp, top_idx, workspace), None for a new one."""
     lib = _hip.load()
-    _hip.require_device(logits, running_scores, seq, ban_ids)
+    _hip.require_device(logits, running_scores, seq, ban_ids, None if at is None else cur, *outs)
     _check_f32(logits, running_scores)
-    if running_scores.dim() != 2 or logits.dim() != 2:
-        raise ValueError("beam_select: logits must be [bsz * nb, vocab] and running_scores [bsz, nb]")
+    if running_scores.dim() != 2 or logits.dim() != 2 or (at is not None and not running_scores.is_contiguous()):
+        raise ValueError(f"{what}: logits must be [bsz * nb, vocab] and running_scores "
+                         + ("[bsz, nb]" if at is None else "a contiguous [bsz, nb]"))
+    if at is not None and (cur.dtype != torch.int32 or cur.numel() != 1 or cur.device != logits.device):
+        raise TypeError(f"{what}: cur must be one int32 on the device of logits")
     bsz, nb = running_scores.shape
     rows, vocab = logits.shape
     if rows != bsz * nb or (vocab > 1 and logits.stride(1) != 1) or (rows > 1 and logits.stride(0) < vocab):
-        raise ValueError("beam_select: logits must hold bsz * nb rows with a dense last axis")
-    running_scores = running_scores.contiguous()
+        raise ValueError(f"{what}: logits must hold bsz * nb rows with a dense last axis")
+    running_scores = running_scores.contiguous()                 # with ``at`` it is: nothing is copied
+    cur_add, cur_max, ban_below = (0, cur, 0) if at is None else (int(at[0]), int(at[1]), int(at[2]))
     seq_stride = 0
     if seq is not None:
-        if (seq.dtype != torch.int64 or seq.dim() != 2 or seq.shape[0] != rows or seq.shape[1] < cur
+        if (seq.dtype != torch.int64 or seq.dim() != 2 or seq.shape[0] != rows or seq.shape[1] < cur_max
                 or (seq.shape[1] > 1 and seq.stride(1) != 1)):
-            raise ValueError("beam_select: seq must be int64 [bsz * nb, >= cur] with a dense last axis")
+            raise ValueError(f"{what}: seq must be int64 [bsz * nb, >= {'cur' if at is None else 'cur_max'}] with a dense last axis")
         seq_stride = seq.stride(0) if rows > 1 else seq.shape[1]
     elif ngram > 0:
-        raise ValueError("beam_select: ngram > 0 needs seq")
+        raise ValueError(f"{what}: ngram > 0 needs seq")
     n_ban = 0
     if ban_ids is not None:
         if ban_ids.dtype != torch.int64 or ban_ids.dim() != 1 or not ban_ids.is_contiguous():
-            raise ValueError("beam_select: ban_ids must be a contiguous 1-d int64 tensor")
+            raise ValueError(f"{what}: ban_ids must be a contiguous 1-d int64 tensor")
         n_ban = ban_ids.numel()
     keep = int(keep)
-    top_lp = torch.empty((bsz, keep), dtype=torch.float32, device=logits.device)
-    top_idx = torch.empty((bsz, keep), dtype=torch.int64, device=logits.device)
+    device = logits.device
+    top_lp, top_idx, workspace = outs
+    for t, dtype, name in ((top_lp, torch.float32, "top_lp"), (top_idx, torch.int64, "top_idx")):
+        if t is not None and (t.dtype != dtype or tuple(t.shape) != (bsz, keep) or not t.is_contiguous() or t.device != device):
+            raise ValueError(f"{what}: {name} must be a contiguous {dtype} [bsz, keep] tensor on the device of logits")
+    if top_lp is None:
+        top_lp = torch.empty((bsz, keep), dtype=torch.float32, device=device)
+    if top_idx is None:
+        top_idx = torch.empty((bsz, keep), dtype=torch.int64, device=device)
     nbytes = int(lib.osq_beam_select_workspace_bytes(bsz, nb, vocab, keep))
-    ws = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=logits.device)
-    rc = lib.osq_beam_select(logits.data_ptr(), logits.stride(0) if rows > 1 else vocab, running_scores.data_ptr(),
-                             _hip.ptr(seq), seq_stride, int(cur), int(ngram), _hip.ptr(ban_ids), n_ban, bsz, nb, vocab, keep,
-                             top_lp.data_ptr(), top_idx.data_ptr(), ws.data_ptr(), nbytes, _hip.raw_stream(logits.device))
-    _hip.check(rc, "beam_select")
+    if workspace is None:
+        workspace = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=device)
+    elif (workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.numel() < nbytes
+            or workspace.device != device):
+        raise ValueError(f"{what}: workspace must be a contiguous uint8 tensor of at least {nbytes} bytes")
+    operands = (logits.data_ptr(), logits.stride(0) if rows > 1 else vocab, running_scores.data_ptr(), _hip.ptr(seq), seq_stride)
+    results = (bsz, nb, vocab, keep, top_lp.data_ptr(), top_idx.data_ptr(), workspace.data_ptr())
+    if at is None:
+        rc = lib.osq_beam_select(*operands, int(cur), int(ngram), _hip.ptr(ban_ids), n_ban, *results, nbytes,
+                                 _hip.raw_stream(device))
+    else:
+        rc = lib.osq_beam_select_at(*operands, cur.data_ptr(), cur_add, cur_max, int(ngram), _hip.ptr(ban_ids), n_ban, ban_below,
+                                    *results, workspace.numel(), _hip.raw_stream(device))
+    _hip.check(rc, what)
     return top_lp, top_idx
 
 
@@ -1913,52 +1940,8 @@ def beam_select_at(logits, running_scores, keep, cur, cur_add, cur_max, seq=None
     running_scores must be contiguous (nothing is copied here).  top_lp / top_idx: the contiguous fp32 / int64 [bsz, keep]
     tensors to write, workspace: a contiguous uint8 tensor of at least ``beam_select_workspace_bytes`` bytes -- a captured
     step names static buffers; None: new ones.  Returns (top_lp, top_idx)."""
-    lib = _hip.load()
-    _hip.require_device(logits, running_scores, seq, ban_ids, cur, top_lp, top_idx, workspace)
-    _check_f32(logits, running_scores)
-    if running_scores.dim() != 2 or logits.dim() != 2 or not running_scores.is_contiguous():
-        raise ValueError("beam_select_at: logits must be [bsz * nb, vocab] and running_scores a contiguous [bsz, nb]")
-    if cur.dtype != torch.int32 or cur.numel() != 1 or cur.device != logits.device:
-        raise TypeError("beam_select_at: cur must be one int32 on the device of logits")
-    bsz, nb = running_scores.shape
-    rows, vocab = logits.shape
-    if rows != bsz * nb or (vocab > 1 and logits.stride(1) != 1) or (rows > 1 and logits.stride(0) < vocab):
-        raise ValueError("beam_select_at: logits must hold bsz * nb rows with a dense last axis")
-    cur_max = int(cur_max)
-    seq_stride = 0
-    if seq is not None:
-        if (seq.dtype != torch.int64 or seq.dim() != 2 or seq.shape[0] != rows or seq.shape[1] < cur_max
-                or (seq.shape[1] > 1 and seq.stride(1) != 1)):
-            raise ValueError("beam_select_at: seq must be int64 [bsz * nb, >= cur_max] with a dense last axis")
-        seq_stride = seq.stride(0) if rows > 1 else seq.shape[1]
-    elif ngram > 0:
-        raise ValueError("beam_select_at: ngram > 0 needs seq")
-    n_ban = 0
-    if ban_ids is not None:
-        if ban_ids.dtype != torch.int64 or ban_ids.dim() != 1 or not ban_ids.is_contiguous():
-            raise ValueError("beam_select_at: ban_ids must be a contiguous 1-d int64 tensor")
-        n_ban = ban_ids.numel()
-    keep = int(keep)
-    device = logits.device
-    if top_lp is None:
-        top_lp = torch.empty((bsz, keep), dtype=torch.float32, device=device)
-    if top_idx is None:
-        top_idx = torch.empty((bsz, keep), dtype=torch.int64, device=device)
-    for t, dtype, name in ((top_lp, torch.float32, "top_lp"), (top_idx, torch.int64, "top_idx")):
-        if t.dtype != dtype or tuple(t.shape) != (bsz, keep) or not t.is_contiguous() or t.device != device:
-            raise ValueError(f"beam_select_at: {name} must be a contiguous {dtype} [bsz, keep] tensor on the device of logits")
-    nbytes = int(lib.osq_beam_select_workspace_bytes(bsz, nb, vocab, keep))
-    if workspace is None:
-        workspace = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=device)
-    elif (workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.numel() < nbytes
-            or workspace.device != device):
-        raise ValueError(f"beam_select_at: workspace must be a contiguous uint8 tensor of at least {nbytes} bytes")
-    rc = lib.osq_beam_select_at(logits.data_ptr(), logits.stride(0) if rows > 1 else vocab, running_scores.data_ptr(),
-                                _hip.ptr(seq), seq_stride, cur.data_ptr(), int(cur_add), cur_max, int(ngram),
-                                _hip.ptr(ban_ids), n_ban, int(ban_below), bsz, nb, vocab, keep, top_lp.data_ptr(),
-                                top_idx.data_ptr(), workspace.data_ptr(), workspace.numel(), _hip.raw_stream(device))
-    _hip.check(rc, "beam_select_at")
-    return top_lp, top_idx
+    return _beam_select("beam_select_at", logits, running_scores, keep, seq, cur, ngram, ban_ids,
+                        at=(cur_add, cur_max, ban_below), outs=(top_lp, top_idx, workspace))
 
 
 class BeamBuffers:

@@ -81,6 +81,7 @@ def test_a_same_tokens_same_steps(setup, unforced, switches, monkeypatch, name):
     info = m.last_beam_graph
     assert got.shape == want.shape and torch.equal(got, want), (got, want)
     assert info.reason is None and info.captured == 2, info
+    assert info.capture_seconds > 0 and m.last_decode_graph.capture_seconds > 0      # the one capture path times into both
     assert info.replays + info.issued + 2 == steps, (info, steps)                    # it stopped on the same step
     forced = not plain and steps == kw["max_length"] - 1
     assert info.issued == (1 if forced else 0), info
@@ -104,6 +105,7 @@ def test_b_the_parent_form_is_what_it_was(setup, unforced, switches):
     info = unforced.last_beam_graph
     assert (info.captured, info.replays, info.issued, info.reason) == (0, 0, 0, "not asked for"), info
     assert unforced.last_decode_graph.captured == 2 and unforced.last_beam_select.eager == 0
+    assert unforced.last_decode_graph.capture_seconds > 0 and info.capture_seconds == 0
 
 
 def test_c_falls_back_and_says_why(setup, unforced, switches):
@@ -129,5 +131,6 @@ def test_c_falls_back_and_says_why(setup, unforced, switches):
         parent = unforced.generate(s.ids, attention_mask=s.mask, beam_graph=False, **PARENT, **KW)
         got = unforced.generate(s.ids, attention_mask=s.mask, **KW)
         assert torch.equal(got, parent) and unforced.last_beam_graph.captured == 2 and unforced.last_beam_graph.reason is None
+        assert unforced.last_beam_graph.capture_seconds > 0 and unforced.last_decode_graph.capture_seconds > 0
         off = unforced.generate(s.ids, attention_mask=s.mask, beam_graph=False, **KW)
         assert torch.equal(off, want) and unforced.last_beam_graph.reason == "not asked for" and _counts(unforced) == plain

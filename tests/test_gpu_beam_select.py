@@ -286,6 +286,64 @@ def test_f_ops_wrapper_and_capture(dev):
     _check("captured", cap_v.cpu(), cap_i.cpu(), other, other_running, keep, seq, cur, 3, (2,))
 
 
+AT = dict(bsz=2, nb=2, vocab=70, keep=4, ngram=2, cur_max=9)
+
+
+def _at_case(dev):
+    logits, running, seq = BS.case(24, AT["bsz"], AT["nb"], AT["vocab"], AT["cur_max"])
+    ban = torch.tensor([35], dtype=torch.int64, device=dev)         # this seed's best token; a 2-gram bans another winner
+    return logits.to(dev), running.to(dev), seq.to(dev), ban
+
+
+@pytest.mark.parametrize("own", [True, False], ids=["caller-owned", "new"])
+def test_g_select_at_gives_the_words_of_select(dev, own):
+    """ops.beam_select_at and ops.beam_select share one Python body: at the positions 0 and cur_max the words of
+    ops.beam_select at that position, one past cur_max NaN in every top_lp and 0 in every top_idx -- into the caller's
+    top_lp / top_idx / workspace, and with None for new ones."""
+    from outlier_suppression_amd import ops
+    bsz, nb, vocab, keep, ngram, cur_max = (AT[k] for k in ("bsz", "nb", "vocab", "keep", "ngram", "cur_max"))
+    logits, running, seq, ban = _at_case(dev)
+    word = torch.zeros(1, dtype=torch.int32, device=dev)
+    outs = {}
+    if own:
+        outs = dict(top_lp=torch.empty((bsz, keep), device=dev), top_idx=torch.empty((bsz, keep), dtype=torch.int64, device=dev),
+                    workspace=torch.empty(ops.beam_select_workspace_bytes(bsz, nb, vocab, keep), dtype=torch.uint8, device=dev))
+    for cur in (0, cur_max, cur_max + 1):
+        word.fill_(cur)
+        if own:
+            outs["top_lp"].fill_(5.0)
+            outs["top_idx"].fill_(-9)
+        got_v, got_i = ops.beam_select_at(logits, running, keep, word, 0, cur_max, seq=seq, ngram=ngram, ban_ids=ban,
+                                          ban_below=cur_max + 1, **outs)
+        assert (got_v is outs["top_lp"] and got_i is outs["top_idx"]) if own else got_v.shape == got_i.shape == (bsz, keep)
+        if cur > cur_max:
+            assert bool(torch.isnan(got_v).all()) and bool((got_i == 0).all()), (cur, got_v, got_i)
+            continue
+        want_v, want_i = ops.beam_select(logits, running, keep, seq, cur, ngram, ban)
+        assert torch.equal(_words(got_v), _words(want_v)) and torch.equal(got_i, want_i), (cur, got_v, want_v, got_i, want_i)
+        assert bool(torch.isfinite(got_v).all())
+    free = ops.beam_select(logits, running, keep, seq, cur_max, 0, None)
+    assert not torch.equal(free[1], want_i)                       # at cur_max the windows and the banned id did remove a winner
+
+
+def test_g_running_scores_with_a_stride(dev):
+    """A non-contiguous running_scores: ops.beam_select copies it and gives the words of the contiguous call;
+    ops.beam_select_at, which a captured step calls on static buffers, copies nothing and refuses."""
+    from outlier_suppression_amd import ops
+    bsz, nb, keep, ngram, cur_max = (AT[k] for k in ("bsz", "nb", "keep", "ngram", "cur_max"))
+    logits, running, seq, ban = _at_case(dev)
+    wide = torch.full((bsz, 2 * nb), float("nan"), device=dev)
+    wide[:, ::2] = running
+    strided = wide[:, ::2]
+    assert not strided.is_contiguous() and torch.equal(strided, running)
+    want_v, want_i = ops.beam_select(logits, running, keep, seq, cur_max, ngram, ban)
+    got_v, got_i = ops.beam_select(logits, strided, keep, seq, cur_max, ngram, ban)
+    assert torch.equal(_words(got_v), _words(want_v)) and torch.equal(got_i, want_i)
+    word = torch.full((1,), cur_max, dtype=torch.int32, device=dev)
+    with pytest.raises(ValueError, match=r"beam_select_at: logits must be \[bsz \* nb, vocab\] and running_scores a contiguous \[bsz, nb\]"):
+        ops.beam_select_at(logits, strided, keep, word, 0, cur_max, seq=seq, ngram=ngram, ban_ids=ban, ban_below=cur_max + 1)
+
+
 def test_z_report():
     """The largest error of this run, per group and overall (the bound is 2e-5)."""
     if not WORST:           # run on its own: nothing to report

@@ -66,6 +66,7 @@ def test_a_steps_word_equal_to_issued_steps(setup, switches, codes, moving):
     switches.FUSE_DECODE_ATTENTION = False            # a captured step uses the one-launch attention whatever the switch says
     got, got_cache, info = _steps(s.q, s, codes, perm, graph=True)
     assert info.captured == (2 if moving else 1) and info.replays == STEPS - 2 and info.reason is None, info
+    assert info.capture_seconds > 0
     assert not torch.isnan(want).any()
     for t in range(STEPS):
         assert _same_words(got[:, t], want[:, t]), f"step {t}"
@@ -106,6 +107,7 @@ def test_b_generate_same_tokens_and_graphs_used(setup, switches, monkeypatch, kw
     steps = len(calls)
     assert steps >= 7
     assert info.captured == (1 if kw["num_beams"] == 1 else 2) and info.reason is None, info
+    assert info.capture_seconds > 0
     assert info.replays >= steps - 3 and info.replays == steps - 2, (info, steps)
     assert switches.FUSE_DECODE_ATTENTION is attention
 
@@ -117,7 +119,7 @@ def test_b_switch_turns_it_on(setup, switches):
         want = s.q.generate(s.ids, attention_mask=s.mask, max_length=12, num_beams=1, min_length=8)
         osq.set_graph_decode(True)
         got = s.q.generate(s.ids, attention_mask=s.mask, max_length=12, num_beams=1, min_length=8)
-        assert s.q.last_decode_graph.captured == 1
+        assert s.q.last_decode_graph.captured == 1 and s.q.last_decode_graph.capture_seconds > 0
         off = s.q.generate(s.ids, attention_mask=s.mask, max_length=12, num_beams=1, min_length=8, graph=False)
         assert s.q.last_decode_graph.captured == 0
     assert torch.equal(got, want) and torch.equal(off, want)
@@ -179,12 +181,13 @@ def test_d_nan_key_makes_generate_raise(setup, switches):
     try:
         with torch.no_grad():
             s.q.generate(s.ids, cache_codes=False, graph=True, **kw)
-            assert s.q.last_decode_graph.captured == 1
+            assert s.q.last_decode_graph.captured == 1 and s.q.last_decode_graph.capture_seconds > 0
             with pytest.raises(RuntimeError, match=r"holds \d+ elements without an integer code"):
                 s.q.generate(s.ids, cache_codes=True, **kw)
             with pytest.raises(RuntimeError, match=r"holds \d+ elements without an integer code"):
                 s.q.generate(s.ids, cache_codes=True, graph=True, **kw)
             assert s.q.last_decode_graph.captured == 1 and s.q.last_decode_graph.replays >= 4
+            assert s.q.last_decode_graph.capture_seconds > 0
     finally:
         handle.remove()
 
@@ -197,4 +200,4 @@ def test_e_two_calls_of_different_length(setup, switches):
             want = s.q.generate(s.ids, **kw)
             got = s.q.generate(s.ids, graph=True, **kw)
             assert torch.equal(got, want), max_length
-            assert s.q.last_decode_graph.captured == 2, s.q.last_decode_graph
+            assert s.q.last_decode_graph.captured == 2 and s.q.last_decode_graph.capture_seconds > 0, s.q.last_decode_graph

@@ -127,6 +127,7 @@ def test_a_same_tokens_same_steps(setup, unforced, switches, apart, variant, nam
     assert m.last_greedy_graph.reason == "not asked for"
     if variant.get("graph"):
         assert m.last_decode_graph.captured == 1 and m.last_decode_graph.reason is None, m.last_decode_graph
+        assert m.last_decode_graph.capture_seconds > 0 and m.last_greedy_graph.capture_seconds == 0
     if name == "rows-finish-apart":                       # asserted on the torch result: rows end apart, pad is written after
         ends = _finish_steps(want.cpu(), kw["eos_token_id"])
         early = [e for e in ends if e is not None and e < want.shape[1] - 1]
@@ -149,6 +150,7 @@ def test_b_whole_step_as_one_graph(setup, unforced, switches, apart, codes, name
         steps = want.shape[1] - 1
         assert m.last_greedy_graph.reason == m.last_greedy_advance.reason == "not asked for"
         assert (m.last_decode_graph.captured, m.last_decode_graph.replays) == (1, steps - 2)
+        assert m.last_decode_graph.capture_seconds > 0
         got = m.generate(setup.ids, attention_mask=setup.mask, greedy_graph=True, **kw)
     info = m.last_greedy_graph
     assert got.shape == want.shape and torch.equal(got, want), (got, want)
@@ -157,6 +159,7 @@ def test_b_whole_step_as_one_graph(setup, unforced, switches, apart, codes, name
     assert info.replays == steps - 2, (info, steps)
     assert (m.last_greedy_advance.advanced, m.last_greedy_advance.eager) == (steps, 0)
     assert (m.last_decode_graph.captured, m.last_decode_graph.replays, m.last_decode_graph.reason) == (1, steps - 2, None)
+    assert info.capture_seconds > 0 and m.last_decode_graph.capture_seconds > 0      # the one capture path times into both
     if name == "forced-eos":
         assert steps == L - 1 and (want[:, -1] == 2).all()
 
@@ -204,6 +207,7 @@ def test_d_the_switches(setup, unforced, switches):
         assert unforced.last_greedy_graph.reason == "not asked for"
         got = unforced.generate(s.ids, attention_mask=s.mask, **kw)
         assert unforced.last_greedy_graph.captured == 1 and unforced.last_greedy_graph.reason is None
+        assert unforced.last_greedy_graph.capture_seconds > 0 and unforced.last_decode_graph.capture_seconds > 0
         off = unforced.generate(s.ids, attention_mask=s.mask, greedy_graph=False, **kw)
         assert torch.equal(off, want) and unforced.last_greedy_graph.reason == "not asked for"
         assert unforced.last_greedy_advance.advanced == 0 and unforced.last_decode_graph.reason == "not asked for"
