@@ -47,7 +47,7 @@ typedef void* osq_stream;
  *     osq_sample_uniforms, osq_sample_nucleus_workspace_bytes, osq_sample_nucleus, osq_sample_nucleus_at,
  *     osq_decode_attention_shared, osq_decode_attention_shared_codes, osq_sample_advance_group, osq_sample_advance_group_at,
  *     osq_sample_nucleus_group, osq_sample_nucleus_group_at, osq_sample_uniforms_group, osq_token_logprob_workspace_bytes,
- *     osq_token_logprob, osq_token_logprob_backward. */
+ *     osq_token_logprob, osq_token_logprob_backward, osq_attention_fake_quant. */
 #define OSQ_ABI_VERSION 10
 
 typedef enum osq_status {
@@ -928,6 +928,51 @@ int osq_decode_attention_shared_codes(const float* q, const uint8_t* k, const ui
                                       float* ctx_scale, void* ctx_zero_point, int ctx_zp_type, int ctx_mode,
                                       float ctx_grad_factor, int ctx_quant_min, int ctx_quant_max,
                                       osq_stream stream);
+
+/* ------------------------------------------------------------------ attention over a whole sequence (attention_block.hip) */
+
+/* What QuantizedBertSelfAttention.forward and QuantizedBartAttention._attend run between the q / k / v sites and the output
+ * projection -- bmm, (scale, mask add, softmax, attention_probs quantizer), bmm, merge heads + context quantizer -- as ONE
+ * launch that never writes the [batch, heads, tokens, kv_len] scores: one workgroup per (batch, head, tile of 32 queries),
+ * the tile's score rows in LDS, both products on the fp32-input matrix instruction (v_mfma_f32_32x32x2_f32: a k-ordered
+ * chain of fmaf, one rounding per product).  For every (b, h, t):
+ *     s[j] = dot(q[t], k[j])                    j < kv_len
+ *     v[j] = pre(s[j]) + mask[b, h, t, j]       pre / mask exactly as osq_attention_softmax_fake_quant: alpha != 1:
+ *                                               mask + s * alpha; divisor != 1: s / divisor + mask; mask == NULL: no addition
+ *     p    = softmax(v)                         max-subtracted, accurate expf, fp32 sum, p = e * (1 / sum); a row with a NaN,
+ *                                               a +inf or only -inf entries is NaN (that row only)
+ *     p'   = fake_quantize(p)                   the probs_* group
+ *     out  = fake_quantize(sum_j p'[j] * v[j])  the ctx_* group, written in the merged layout
+ * q: row (b, h, t) starts q_stride_b * b + q_stride_h * h + q_stride_t * t elements into q and holds head_dim contiguous
+ * floats; k and v likewise with kv_len rows: dense [B, h, T, d], BERT's permuted views of [B, T, H] and [:, :, :S] views of
+ * cache buffers are taken without a copy.  mask: NULL, or additive with a contiguous last axis and element strides
+ * mask_stride_b / _h / _t, 0 = broadcast, as in osq_attention_softmax_fake_quant ([B,1,1,S] for BERT, [B,1,T,S] for BART).
+ * out: dense [batch, tokens, heads * head_dim].  probs_out: NULL, or dense [batch, heads, tokens, kv_len], receives p'.
+ * All fp32.  Each parameter group is (scale, zero_point, zp_type, mode, grad_factor, quant_min, quant_max) as in
+ * osq_decode_attention_fake_quant, OSQ_PARAM_SANITIZE included (the repair rides in every workgroup); a NULL scale means no
+ * quantizer: the values pass through.  Given p, and given c, the outputs are word-equal to osq_fake_quant_per_tensor.
+ * Order contract (csrc/attention_block.hip lists the orders): every sum is in an order fixed by (head_dim, kv_len) alone;
+ * no float atomics; the words of a query row do not depend on tokens, on where the row sits in its tile, on batch or
+ * heads, or on strides; the columns and rows that pad a ragged tile contribute no term that can change a word, signed
+ * zeros included; memory beyond tokens or kv_len is never read.  The order is not rocBLAS's: against the eager sequence the
+ * result is equal to a tolerance, not bit for bit.
+ * No allocation, no host synchronisation, no workspace: legal inside a stream capture.  Inference only.
+ * OSQ_ERR_UNSUPPORTED, nothing launched (the caller runs the eager sequence): head_dim not in {16, 32, 64, 128}; kv_len
+ * outside [1, 1024] (32 score rows of 1024 floats are 128 KiB of the CU's 160 KiB of LDS); q / k / v / out not 16-byte
+ * aligned, a q / k / v stride that is not a multiple of 4 elements, mask / probs_out not 4-byte aligned.  Both alpha and
+ * divisor different from 1: OSQ_ERR_INVALID_ARGUMENT. */
+int osq_attention_fake_quant(const float* q, const float* k, const float* v, const float* mask, float* out,
+                             float* probs_out, int64_t batch, int64_t heads, int64_t tokens, int64_t kv_len, int64_t head_dim,
+                             int64_t q_stride_b, int64_t q_stride_h, int64_t q_stride_t,
+                             int64_t k_stride_b, int64_t k_stride_h, int64_t k_stride_t,
+                             int64_t v_stride_b, int64_t v_stride_h, int64_t v_stride_t,
+                             int64_t mask_stride_b, int64_t mask_stride_h, int64_t mask_stride_t,
+                             float alpha, float divisor,
+                             float* probs_scale, void* probs_zero_point, int probs_zp_type, int probs_mode,
+                             float probs_grad_factor, int probs_quant_min, int probs_quant_max,
+                             float* ctx_scale, void* ctx_zero_point, int ctx_zp_type, int ctx_mode,
+                             float ctx_grad_factor, int ctx_quant_min, int ctx_quant_max,
+                             osq_stream stream);
 
 /* ------------------------------------------------------------------ beam search (beam_select.hip) */
 

@@ -73,6 +73,15 @@ def set_fast_decode_attention(on=True):
     util_layernorm.FUSE_DECODE_ATTENTION = bool(on)
 
 
+def set_fast_attention(on=True):
+    """The one-launch attention over whole sequences (util_layernorm.FUSE_ATTENTION: both products, scaling, mask, softmax,
+    probabilities quantizer, merge heads and context quantizer of a BERT / RoBERTa / BART attention block with more than one
+    query token, csrc/attention_block.hip; default OFF -- tolerance-equal to the eager sequence, not bit-equal).
+    OSQ_FAST_ATTENTION=1 turns it on at load."""
+    from . import util_layernorm
+    util_layernorm.FUSE_ATTENTION = bool(on)
+
+
 def set_cache_codes(on=True):
     """New KV caches of incremental decoding hold integer codes, one byte per element, instead of fp32 words
     (util_layernorm.CACHE_CODES; model/quant_bart.py, QuantizedBartCache; default OFF).  What is read back from the cache,
@@ -259,7 +268,8 @@ def reset_tier(_lib=None):
     """The package's default tier, as the environment states it (applied when the library is first loaded): MSEFast sums in
     the reference's one-thread order, the backward's sums order-free; OSQ_STRICT=1 / 0 force both; OSQ_FAST=0 / 1 the
     one-launch LayerNorm site; OSQ_FAST_SOFTMAX=1 the one-launch attention-probabilities site and OSQ_FAST_DECODE_ATTENTION=1
-    the one-launch attention of a cached decoding step (unset: off); OSQ_CACHE_CODES=1 KV caches as integer codes (unset: off);
+    the one-launch attention of a cached decoding step (unset: off); OSQ_FAST_ATTENTION=1 the one-launch attention over whole
+    sequences (unset: off); OSQ_CACHE_CODES=1 KV caches as integer codes (unset: off);
     OSQ_GRAPH_DECODE=1 generate() replays a captured decoding step (unset: off); OSQ_BEAM_SELECT=1 beam search selects a step's
     continuations with one kernel call (unset: off); OSQ_BEAM_ADVANCE=1 beam search advances its beams with one kernel call
     (unset: off); OSQ_BEAM_GRAPH=1 beam search replays a whole step, bookkeeping included, as one captured graph (unset: off);
@@ -280,6 +290,7 @@ def reset_tier(_lib=None):
     set_fast(os.environ.get("OSQ_FAST", "") != "0")
     set_fast_softmax(_env_on("OSQ_FAST_SOFTMAX"))
     set_fast_decode_attention(_env_on("OSQ_FAST_DECODE_ATTENTION"))
+    set_fast_attention(_env_on("OSQ_FAST_ATTENTION"))
     for setter, name in _SWITCHES:
         setter(_env_on(name))
 

@@ -63,6 +63,7 @@
 // cross-attention's length does not change between steps, a captured step replays the same shared launch.
 #include <math.h>
 #include <hip/hip_runtime.h>
+#include "attention_quant.h"
 #include "codes_device.h"
 #include "osq_host.h"
 
@@ -102,22 +103,6 @@ struct KvCodes {               // coded cache: four codes in 32 bits, 16 x 4 B i
     }
 };
 
-struct DecQuant {              // one quantizer of the site; scale == nullptr: no quantizer, values pass through
-    float* scale;              // written only under OSQ_PARAM_SANITIZE
-    void* zero_point;
-    int zp_type, mode;
-    float grad_factor, qmin, qmax;
-};
-
-__device__ __forceinline__ QParams dec_params(const DecQuant& d) {
-    if (!d.scale) return QParams{1.f, 0.f};
-    return tensor_params(d.scale, d.zero_point, d.zp_type, d.mode, d.grad_factor, d.qmin, d.qmax);
-}
-
-__device__ __forceinline__ float dec_fq(float x, const DecQuant& d, const QParams& p) {
-    return d.scale ? dequantize_value(quantize_value(x, p.scale, p.zp, d.qmin, d.qmax), p.scale, p.zp) : x;
-}
-
 // sum over the LPR consecutive lanes that share a row; every lane of the group ends with the same word.  All 64 lanes active.
 template <int LPR>
 __device__ __forceinline__ float row_lanes_sum(float v) {
@@ -136,14 +121,6 @@ __device__ __forceinline__ float row_groups_sum(float v) {
 #pragma unroll
     for (int s = LPR; s < OSQ_WAVE; s <<= 1) v = v + __shfl_xor(v, s, OSQ_WAVE);
     return v;
-}
-
-static bool dec_mode_ok(int mode) {
-    return (mode & ~(OSQ_PARAM_MODE_MASK | OSQ_PARAM_SANITIZE)) == 0 && (mode & OSQ_PARAM_MODE_MASK) <= OSQ_PARAM_LSQPLUS;
-}
-
-static DecQuant dec_quant(float* scale, void* zero_point, int zp_type, int mode, float grad_factor, int quant_min, int quant_max) {
-    return DecQuant{scale, zero_point, zp_type, mode, grad_factor, static_cast<float>(quant_min), static_cast<float>(quant_max)};
 }
 
 struct DecArgs {
@@ -422,10 +399,6 @@ static int launch_decode_attention(const char* what, const float* q, const void*
 }  // namespace osq
 
 using namespace osq;
-
-// the seven arguments of the quantizer named `site` (probs or ctx), site_scale .. site_quant_max, as the launcher's record
-#define OSQ_DEC_QUANT(site) \
-    dec_quant(site##_scale, site##_zero_point, site##_zp_type, site##_mode, site##_grad_factor, site##_quant_min, site##_quant_max)
 
 extern "C" int osq_decode_attention_fake_quant(const float* q, const float* k, const float* v, const float* mask, float* out,
                                                float* probs_out, int64_t batch, int64_t heads, int64_t head_dim,

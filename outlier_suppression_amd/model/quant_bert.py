@@ -21,7 +21,8 @@ from torch import nn
 from .losses import classification_loss, span_loss, with_loss
 
 from ..quantization import QuantizedModule, Quantizer
-from ..util_layernorm import (GammaResidual, QuantizedLayerNorm, activation_fake_quant, attention_probs_fake_quant,
+from ..util_layernorm import (GammaResidual, QuantizedLayerNorm, activation_fake_quant, attention_block_fake_quant,
+                              attention_probs_fake_quant,
                               merge_heads_fake_quant, qkv_heads_fake_quant, residual_layernorm)
 
 
@@ -82,7 +83,6 @@ class QuantizedBertSelfAttention(QuantizedModule):
             q, k, v = self._heads(xq), self._heads(xk), self._heads(xv)
             q = self.query_permute_post_act_fake_quantize(q, observation_mask, 2)
             kt = self.key_transpose_post_act_fake_quantize(k.transpose(-1, -2), observation_mask, 3)
-        scores = torch.matmul(q, kt)
         root = math.sqrt(self.attention_head_size)
         if attention_mask is not None and root == 2.0 ** round(math.log2(root)) and not torch.is_grad_enabled():
             # head sizes 16 / 64 / 256: dividing by sqrt(d) is an exact multiplication by a power of two, so
@@ -90,6 +90,14 @@ class QuantizedBertSelfAttention(QuantizedModule):
             scale = dict(alpha=1.0 / root)
         else:
             scale = dict(divisor=root)
+        if fused is not None:
+            # everything from here to the merged context as one launch under FUSE_ATTENTION (q / k / v are quantised already)
+            out = attention_block_fake_quant(self.attention_probs_post_act_fake_quantize,
+                                             self.context_view_post_act_fake_quantize if self.qoutput else None,
+                                             q, fused[1], v, attention_mask, dropout=self.dropout, **scale)
+            if out is not None:
+                return out
+        scores = torch.matmul(q, kt)
         # mask + scaling -> softmax -> dropout -> probs quantizer (quant_bert.py:169-185); one launch under FUSE_SOFTMAX
         probs = attention_probs_fake_quant(self.attention_probs_post_act_fake_quantize, scores, attention_mask,
                                            dropout=self.dropout, observation_mask=observation_mask, seq_pos=2, **scale)

@@ -1670,6 +1670,84 @@ def attention_softmax_fake_quant(scores, mask=None, *, alpha=None, divisor=None,
 
 
 # ---------------------------------------------------------------------------------------
+# attention over a whole sequence: both products, mask, softmax, two quantizers in one launch
+# ---------------------------------------------------------------------------------------
+
+ATTENTION_TQ = 32          # kBlkTQ of csrc/attention_block.hip: the query rows of a workgroup
+ATTENTION_TK = 32          # kBlkTK: the key columns of a score tile
+ATTENTION_MAX_KV = 1024    # kBlkMaxS
+ATTENTION_HEAD_DIMS = (16, 32, 64, 128)
+
+
+def attention_fusable(q, k, v, mask=None):
+    """Layout rules of osq_attention_fake_quant: q [B, h, T, d], k / v [B, h, S, d], fp32 on one device, with a contiguous
+    last axis and any strides on the others (dense tensors, BERT's permuted views of [B, T, H], ``[:, :, :S]`` views of cache
+    buffers); mask None, or fp32 on that device, broadcastable to [B, h, T, S] with a contiguous last axis (any strides, 0
+    included, on the others).  What the library refuses on top (head_dim, S, alignment) it says itself."""
+    if not (q.dim() == 4 and k.dim() == 4 and v.dim() == 4 and q.is_cuda and q.numel() and k.numel()):
+        return False
+    b, h, t, d = q.shape
+    s = k.shape[2]
+    if tuple(k.shape) != (b, h, s, d) or tuple(v.shape) != (b, h, s, d):
+        return False
+    for x in (q, k, v):
+        if x.dtype != torch.float32 or x.device != q.device or (d > 1 and x.stride(3) != 1):
+            return False
+    if mask is None:
+        return True
+    if not (mask.device == q.device and mask.dtype == torch.float32 and mask.dim() <= 4):
+        return False
+    try:
+        m = mask.expand(b, h, t, s)
+    except RuntimeError:
+        return False
+    return s == 1 or m.stride(3) == 1
+
+
+def attention_fake_quant(q, k, v, mask, probs_quant, ctx_quant, alpha=None, divisor=None, want_probs=False, *, out=None,
+                         probs_out=None):
+    """``fq_ctx(merge_heads(fq_probs(softmax(pre(q @ k^T) + mask)) @ v))`` for whole sequences in ONE launch
+    (osq_attention_fake_quant, csrc/attention_block.hip): the [B, h, T, S] scores are never written.
+
+    q [B, h, T, d], k / v [B, h, S, d] and mask as attention_fusable states; nothing is copied.  pre: ``alpha`` / ``divisor``
+    as in attention_softmax_fake_quant (give one or neither).  probs_quant / ctx_quant: None (no quantizer) or
+    (scale, zero_point, quant_min, quant_max, mode, grad_factor).  ``out`` / ``probs_out``: contiguous fp32 [B, T, h * d] /
+    [B, h, T, S] tensors to write into (``probs_out`` implies ``want_probs``).  Returns the [B, T, h * d] output -- with
+    ``want_probs`` the pair (output, fake-quantised probabilities [B, h, T, S]) -- or None when the layout is not fusable or the library refuses
+    it (head_dim outside 16 / 32 / 64 / 128, S above 1024, a misaligned pointer or stride): nothing was launched, the
+    caller runs the eager sequence."""
+    lib = _hip.load()
+    _hip.require_device(q, k, v, mask)
+    if alpha is not None and divisor is not None:
+        raise ValueError("attention_fake_quant: give alpha or divisor, not both")
+    if not attention_fusable(q, k, v, mask):
+        return None
+    b, h, t, d = q.shape
+    s = k.shape[2]
+    msb = msh = mst = 0
+    if mask is not None:
+        msb, msh, mst = mask.expand(b, h, t, s).stride()[:3]
+    for given, shape, name in ((out, (b, t, h * d), "out"), (probs_out, (b, h, t, s), "probs_out")):
+        if given is not None and (given.dtype != torch.float32 or tuple(given.shape) != shape or not given.is_contiguous()
+                                  or given.device != q.device):
+            raise ValueError(f"attention_fake_quant: {name} must be a contiguous fp32 tensor of shape {shape}")
+    if out is None:
+        out = torch.empty((b, t, h * d), dtype=torch.float32, device=q.device)
+    want_probs = want_probs or probs_out is not None
+    probs = probs_out if probs_out is not None or not want_probs else torch.empty((b, h, t, s), dtype=torch.float32, device=q.device)
+    # the stride of an axis of one element is never multiplied by anything but 0
+    strides = [0 if x.shape[i] == 1 else x.stride(i) for x in (q, k, v) for i in range(3)]
+    rc = lib.osq_attention_fake_quant(q.data_ptr(), k.data_ptr(), v.data_ptr(), _hip.ptr(mask), out.data_ptr(), _hip.ptr(probs),
+                                      b, h, t, s, d, *strides, msb, msh, mst,
+                                      1.0 if alpha is None else float(alpha), 1.0 if divisor is None else float(divisor),
+                                      *_quant_group(probs_quant), *_quant_group(ctx_quant), _hip.raw_stream(q.device))
+    if rc == _hip.ERR_UNSUPPORTED:
+        return None
+    _hip.check(rc, "attention_fake_quant")
+    return (out, probs) if want_probs else out
+
+
+# ---------------------------------------------------------------------------------------
 # one decoding step's attention over the KV cache: scores, mask, softmax, two quantizers in one launch
 # ---------------------------------------------------------------------------------------
 

@@ -38,6 +38,16 @@ csrc/decode_attention.hip).  Its dot products are fp32 sums in the kernel's own 
 ocml's: the result is tolerance-equal to the eager sequence, not bit-equal, hence off by default.
 ``outlier_suppression_amd.set_fast_decode_attention(True)`` / ``OSQ_FAST_DECODE_ATTENTION=1`` turn it on.
 
+``FUSE_ATTENTION`` (default OFF) is its counterpart for more than one query token: BERT and RoBERTa as a whole, BART's encoder,
+the teacher-forced decoder and a multi-token prefill.  Everything between the q / k / v sites and the output projection -- bmm,
+scaling, mask add, softmax, probabilities quantizer, bmm, merge heads, context quantizer -- is ONE launch that keeps a tile of
+32 score rows in LDS and never writes the [B, h, T, S] scores (``ops.attention_fake_quant``, csrc/attention_block.hip; both
+products on the fp32-input matrix instruction).  Tolerance-equal to the eager sequence for the same reasons, hence off by
+default; head sizes 16 / 32 / 64 / 128 and S <= 1024, anything else keeps the eager sequence (or FUSE_SOFTMAX), as do autograd
+passes, active dropout and observer passes.  Measured on MI355X (profiles/attention_block_ab.txt), the block alone: 1.40x the
+eager sequence at [32,12,128,128,64] and 1.22x at [192,16,62,62,64], but 0.84x / 0.79x / 0.72x at 384 / 512 / 512 keys, where
+FUSE_SOFTMAX is the faster switch.  ``outlier_suppression_amd.set_fast_attention(True)`` / ``OSQ_FAST_ATTENTION=1`` turn it on.
+
 ``CACHE_CODES`` (default OFF) is no fusion but a storage format: new KV caches (model/quant_bart.py, QuantizedBartCache) hold
 integer codes, one byte per element, written by ``ops.fake_quant_kv_append_codes`` and read as they are by
 ``ops.decode_attention_codes`` (csrc/kv_codes.hip, csrc/decode_attention.hip); the words computed are those of the fp32 cache.
@@ -116,6 +126,7 @@ FUSE_ACTIVATION = True
 FUSE_QKV = True          # the query / key / value head-split sites of a self-attention block as one launch (bit-identical)
 FUSE_SOFTMAX = False     # the attention-probabilities site as one launch (tolerance-equal; set_fast_softmax / OSQ_FAST_SOFTMAX=1)
 FUSE_DECODE_ATTENTION = False   # a cached decoding step's attention after the append as one launch (tolerance-equal; set_fast_decode_attention / OSQ_FAST_DECODE_ATTENTION=1)
+FUSE_ATTENTION = False   # an attention block over a whole sequence as one launch (tolerance-equal; set_fast_attention / OSQ_FAST_ATTENTION=1)
 FUSE_KV_APPEND = True    # incremental decoding: a step's q / k / v sites + KV-cache append (+ beam reorder) as one launch (bit-identical)
 GRAPH_DECODE = False     # generate(): capture a cached decoding step into a graph and replay it (set_graph_decode / OSQ_GRAPH_DECODE=1 / generate(graph=True))
 BEAM_SELECT = False      # generate(): a beam step's log-softmax + processors + score add + top-k as one kernel call (tolerance-equal; set_beam_select / OSQ_BEAM_SELECT=1 / generate(beam_select=True))
@@ -441,6 +452,24 @@ def decode_attention_fake_quant(probs_quantizer, ctx_quantizer, q, k, v, mask=No
     if codes is not None:
         return ops.decode_attention_codes(q, k, v, mask, params[0], params[1], *codes)
     return ops.decode_attention_fake_quant(q, k, v, mask, params[0], params[1])
+
+
+def attention_block_fake_quant(probs_quantizer, ctx_quantizer, q, k, v, mask=None, alpha=None, divisor=None, dropout=None):
+    """An attention block over a whole sequence, from the fake-quantised q [B, h, T, d] and k / v [B, h, S, d] to the merged,
+    fake-quantised context [B, T, h*d] -- matmul, ``alpha`` / ``divisor`` and mask as attention_probs_fake_quant takes them,
+    softmax, ``probs_quantizer``, matmul, merge heads, ``ctx_quantizer`` -- as ONE launch (ops.attention_fake_quant).  Gated
+    as decode_attention_fake_quant is: only with FUSE_ATTENTION on, autograd off, dropout inactive and each quantizer either
+    None or in its plain quantising state.  The grad factors go by the tensors the eager quantizers would see:
+    probabilities [B, h, T, S], context [B, T, h*d].  Returns the context, or None (nothing launched): the caller goes on
+    with the eager sequence."""
+    if not FUSE_ATTENTION or torch.is_grad_enabled() or _dropout_active(dropout):
+        return None
+    if q.dim() != 4 or k.dim() != 4 or not ops.attention_fusable(q, k, v, mask):
+        return None
+    params = _decode_site_params(q, (probs_quantizer, q.shape[0] * q.shape[1] * q.shape[2] * k.shape[2]), (ctx_quantizer, q.numel()))
+    if params is None:
+        return None
+    return ops.attention_fake_quant(q, k, v, mask, params[0], params[1], alpha=alpha, divisor=divisor)
 
 
 def decode_attention_shared_fake_quant(probs_quantizer, ctx_quantizer, q, k, v, group, mask=None, dropout=None, codes=None,
