@@ -1,6 +1,7 @@
 """Float64 restatement of an attention block over a whole sequence (quant_bert.py:169-188, quant_bart.py:232-268 for T
-query tokens) with a per-entry error bound, and the case table that tests/test_oracle_attention_block.py (CPU) and
-tests/test_gpu_attention_block.py share.
+query tokens) with a per-entry error bound, and the case tables that tests/test_oracle_attention_block*.py (CPU) and
+tests/test_gpu_attention_block*.py share: ``table`` (the tile edges of T and S) and ``edge_table`` (the S classes of the
+kernel and the boundaries of its score and context loops, with masks of every stride pattern and finite mask values).
 
     s[j] = dot(q[t], k[j]);  v[j] = pre(s[j]) + mask[t, j];  p = softmax(v);  p' = fq_probs(p)
     c    = sum_j p'[j] * V[j];  out = fq_ctx(c) in the merged [B, T, h * d] layout
@@ -41,6 +42,20 @@ SELECT_CAP = 0.07           # what an instance is chosen under: the context is r
                             # entries may change sides between two evaluations
 SEED_BUDGET = 20
 
+# ---- the edge table: lengths chosen from the constants of csrc/attention_block.hip, not from the workload
+WAVES = 4                   # kBlkWaves: key tiles go round them; the context's steps are split among WAVES / chunks segments
+IN_FLIGHT = 16              # kBlkInFlight: steps of the context a lane loads at once, one batch ahead
+S_CLASSES = (128, 256, 512, 1024)          # floats of LDS per score row: one kernel instance each
+# 9: five steps, split 2 2 1 0 among four segments, 3 2 among two; 63..65 and 127..129: a segment of IN_FLIGHT steps and of
+# one more with two and with four segments (with fewer segments: of two batches and of one step more); 128/129, 256/257,
+# 512/513: the class switches, 129 and 257 also the first key tile past one and past two rounds of the waves; 127, 255, 511,
+# 1023: the odd tops of the classes, where position S (the +0 partner of the last step) is the last word of the score row
+EDGE_KV_LENS = (9, 63, 64, 65, 127, 128, 129, 255, 256, 257, 511, 512, 513, 1023)
+EDGE_TOKENS = (1, TQ + 1)
+# head: [1, h, T, S] (batch stride 0, head stride not); bias: [B, h, T, S] of finite values; neginf: [1, 1, T, S] with -inf
+EDGE_MASKS = ("head", "bias", "neginf", "none", "pad", "causal")
+EDGE_PRES = ("none", "alpha", "divisor", "alpha_d")           # alpha_d: float32(d ** -0.5) as it is, a power of two or not
+
 Case = namedtuple("Case", "head_dim tokens kv_len batch heads bits mode bad_params mask pre sites")
 
 
@@ -58,10 +73,60 @@ def table(head_dim):
     return out
 
 
+def segments(head_dim):
+    """Segments the context's steps are split into: a wave per 32-column chunk of the context and segment."""
+    return WAVES // max(head_dim // 32, 1)
+
+
+def steps_per_segment(head_dim, kv_len):
+    """``per`` of the kernel's context loop: ceil(S / 2) steps (the matrix instruction sums two positions), split evenly."""
+    return -(-(-(-kv_len // 2)) // segments(head_dim))
+
+
+def key_tiles(kv_len, tk=TK):
+    """``ktiles`` of the kernel's score loop."""
+    return -(-kv_len // tk)
+
+
+def s_class(kv_len):
+    """The kernel instance a length runs: the smallest class that holds its score row."""
+    return next(c for c in S_CLASSES if kv_len <= c)
+
+
+def edge_table(head_dim):
+    """EDGE_TOKENS x EDGE_KV_LENS of one head size.  Geometry, quantizers, bad parameters and sites rotate as in table(); the
+    six masks start at the head size's index and the four pre-scalings shift by one every six cases, so that over the
+    table every mask meets every pre-scaling."""
+    out = []
+    shift = HEAD_DIMS.index(head_dim)
+    for t in EDGE_TOKENS:
+        for s in EDGE_KV_LENS:
+            i = len(out)
+            bits, mode = QUANTS[i % 4]
+            batch, heads = GEOMETRIES[(i // len(EDGE_KV_LENS) + i % len(EDGE_KV_LENS)) % 2]
+            out.append(Case(head_dim, t, s, batch, heads, bits, mode, mode == "lsqplus" and (i // 4) % 2 == 1,
+                            EDGE_MASKS[(i + shift) % 6], EDGE_PRES[(i + i // 6) % 4], SITES[i % 5]))
+    return out
+
+
 def build_mask(case, rng):
-    b, t, s = case.batch, case.tokens, case.kv_len
+    b, h, t, s = case.batch, case.heads, case.tokens, case.kv_len
     if case.mask == "none":
         return None
+    if case.mask == "head":                                      # per head, about 30 % closed; position 0 stays open
+        m = np.where(rng.random((1, h, t, s)) < 0.3, F32(FMIN), F32(0.0))
+        m[..., 0] = 0.0
+        return m
+    if case.mask == "bias":                                      # a finite bias everywhere, and the -10000 of older BERT code
+        m = (0.5 * rng.standard_normal((b, h, t, s))).astype(F32)
+        for i in range(b):
+            keep = s if s < 2 else int(rng.integers(1, s))
+            m[i, :, :, keep:] = -10000.0
+        return m
+    if case.mask == "neginf":                                    # torch's causal mask: -inf ahead of the diagonal
+        m = np.zeros((1, 1, t, s), F32)
+        m[0, 0][np.arange(s)[None, :] > np.arange(t)[:, None] + max(s - t, 0)] = -np.inf
+        return m
     m = np.zeros((b, 1, t if case.mask == "causal" else 1, s), F32)
     for i in range(b):
         keep = s if s < 2 else int(rng.integers(1, s))           # a padding tail on every row; position 0 stays open
@@ -80,6 +145,8 @@ def pre_args(case):
         return alpha, None, d ** -0.5 / alpha
     if case.pre == "divisor":
         return None, float(F32(d ** 0.5)), 1.0
+    if case.pre == "alpha_d":                                    # the model's scaling as one fp32 factor: rounds unless d is 4 ** n
+        return float(F32(d ** -0.5)), None, 1.0
     return None, None, d ** -0.5
 
 
@@ -96,21 +163,31 @@ def _softmax_with_bound(dot, err_s, s):
 
 
 def probabilities64(q, k, mask, alpha, divisor):
-    """float64 probabilities [B, h, T, S] of fp32 inputs and their bound.  Masks hold 0 and finfo.min only."""
+    """float64 probabilities [B, h, T, S] of fp32 inputs and their bound.  ``mask``: fp32, broadcastable to [B, h, T, S].  An
+    entry <= finfo.min (-inf included) closes its position: ``dot + finfo.min`` is finfo.min in fp32 and float64 alike, the
+    score carries no error, and its probability is exactly 0 while the row has an open position.  Adding a zero entry is
+    exact.  Any other entry m gives dot + m, rounded once (or not at all where the add is fused into the scaling)."""
     d, s = q.shape[-1], k.shape[2]
     q64, k64 = q.astype(np.float64), k.astype(np.float64)
     dot = np.einsum("bhtd,bhsd->bhts", q64, k64)
     err_s = gamma(d) * np.einsum("bhtd,bhsd->bhts", np.abs(q64), np.abs(k64))
-    if alpha is not None:                                        # a power of two: exact
+    if alpha is not None:
         dot, err_s = dot * alpha, err_s * alpha
+        if np.frexp(alpha)[0] != 0.5:                            # a power of two is exact; any other factor rounds once
+            err_s = err_s + np.abs(dot) * U
     elif divisor is not None:
         dot, err_s = dot / divisor, err_s / divisor
         err_s = err_s + np.abs(dot) * U
     if mask is not None:
-        assert np.isin(mask, (0.0, F32(FMIN))).all()
-        masked = np.broadcast_to(mask != 0, dot.shape)
-        dot = np.where(masked, FMIN, dot)
-        err_s = np.where(masked, 0.0, err_s)
+        assert mask.dtype == F32 and not np.isnan(mask).any() and not (mask == np.inf).any()
+        m = np.broadcast_to(mask, dot.shape)
+        closed = m <= F32(FMIN)
+        finite = ~closed & (m != 0)
+        if finite.any():
+            added = dot + np.where(finite, m, 0.0).astype(np.float64)
+            dot, err_s = np.where(finite, added, dot), np.where(finite, err_s + np.abs(added) * U, err_s)
+        dot = np.where(closed, FMIN, dot)
+        err_s = np.where(closed, 0.0, err_s)
     return _softmax_with_bound(dot, err_s, s)
 
 
@@ -231,14 +308,13 @@ def reference(case):
 
 
 def report():
-    """The per-case unsure shares, as profiles/attention_block_accuracy.txt holds them."""
+    """The per-case unsure shares, as profiles/attention_block_accuracy.txt holds them: table(), then edge_table()."""
     lines = ["head_dim T S B h quant mask pre sites seed(+offset) | unsure share probs / ctx | largest 4 g among unsure probs / ctx"]
-    for d in HEAD_DIMS:
-        for case in table(d):
-            r = reference(case)
-            lines.append(f"{d} {case.tokens} {case.kv_len} {case.batch} {case.heads} {case.bits}-{case.mode}"
-                         f"{'-bad' if case.bad_params else ''} {case.mask} {case.pre} {case.sites} {r['seed']}(+{r['seed'] - first_seed(case)}) | "
-                         f"{r['probs'].share:.4f} {r['ctx'].share:.4f} | {r['probs'].worst:.3f} {r['ctx'].worst:.3f}")
+    for case in [c for cases in (table, edge_table) for d in HEAD_DIMS for c in cases(d)]:
+        r = reference(case)
+        lines.append(f"{case.head_dim} {case.tokens} {case.kv_len} {case.batch} {case.heads} {case.bits}-{case.mode}"
+                     f"{'-bad' if case.bad_params else ''} {case.mask} {case.pre} {case.sites} {r['seed']}(+{r['seed'] - first_seed(case)}) | "
+                     f"{r['probs'].share:.4f} {r['ctx'].share:.4f} | {r['probs'].worst:.3f} {r['ctx'].worst:.3f}")
     return "\n".join(lines)
 
 
