@@ -47,7 +47,7 @@ typedef void* osq_stream;
  *     osq_sample_uniforms, osq_sample_nucleus_workspace_bytes, osq_sample_nucleus, osq_sample_nucleus_at,
  *     osq_decode_attention_shared, osq_decode_attention_shared_codes, osq_sample_advance_group, osq_sample_advance_group_at,
  *     osq_sample_nucleus_group, osq_sample_nucleus_group_at, osq_sample_uniforms_group, osq_token_logprob_workspace_bytes,
- *     osq_token_logprob, osq_token_logprob_backward, osq_attention_fake_quant. */
+ *     osq_token_logprob, osq_token_logprob_backward, osq_attention_fake_quant, osq_attention_fake_quant_int. */
 #define OSQ_ABI_VERSION 10
 
 typedef enum osq_status {
@@ -973,6 +973,60 @@ int osq_attention_fake_quant(const float* q, const float* k, const float* v, con
                              float* ctx_scale, void* ctx_zero_point, int ctx_zp_type, int ctx_mode,
                              float ctx_grad_factor, int ctx_quant_min, int ctx_quant_max,
                              osq_stream stream);
+
+/* ------------------------------------------------------------------ whole-sequence attention on integer codes (attention_int.hip) */
+
+/* osq_attention_fake_quant on the INTEGERS of the q / k / v / probabilities quantizers, both products on the bf16 matrix
+ * instruction (v_mfma_f32_32x32x16_bf16) and exact: every operand is s * n with an integer |n| <= 255, exact in bf16; the
+ * products are exact in fp32 and fp32 sums below 2**24 are exact in any order.  Inputs, layouts, strides, mask broadcast,
+ * alpha / divisor, probs_out and the dense merged out are those of osq_attention_fake_quant; in addition the q_*, k_* and
+ * v_* groups are the per-tensor quantizers that produced q, k and v (OSQ_PARAM_SANITIZE included: the repair rides in every
+ * workgroup).  The q, k, v and probs groups are required; the ctx group is optional (NULL scale).  For every (b, h, t), with
+ * (s_x, zp_x, qmin_x, qmax_x) the repaired, effective parameters of site x:
+ *     n_q[t][i] = clamp(rint(q[t][i] / s_q) + zp_q, qmin_q, qmax_q) - zp_q     likewise n_k[j][i], n_v[j][i]: the site's
+ *                 quantizer applied once more; on the quantizer's own outputs this is their integer, exactly
+ *     N[j]   = sum_i n_q[t][i] * n_k[j][i]            EXACT integer
+ *     sc[j]  = float(N[j]) * (s_q * s_k)              s_q * s_k rounded once; |N| < 2**24, so float() is exact
+ *     x[j]   = pre(sc[j]) + mask[b, h, t, j]          pre / mask exactly as osq_attention_fake_quant: one rounding per
+ *                                                     operation, no contraction into an fma
+ *     p      = softmax(x)                             row max exact, ocml expf of x - max, fp32 denominator in an order fixed
+ *                                                     by kv_len alone (csrc/attention_int.hip states it), p = e * (1 / sum);
+ *                                                     a row with a NaN, a +inf or only -inf is NaN (that row only)
+ *     n_p[j] = clamp(rint(p[j] / s_p) + zp_p, qmin_p, qmax_p) - zp_p           probs_out gets float(n_p) * s_p, the word of
+ *                                                     osq_fake_quant_per_tensor on p
+ *     C[i]   = sum_j n_p[j] * n_v[j][i]               EXACT integer (up to 2**30): fp32 over at most 128 keys at a time, the
+ *                                                     chunks added as int32; the chunking is not part of the contract
+ *     c[i]   = float(C[i]) * (s_p * s_v)              int -> float round-to-nearest-even, one product
+ *     out    = fake_quantize(c) by the ctx group, or c without one; merged [batch, tokens, heads * head_dim]
+ * So out is a function of probs_out and v alone, word for word, and the words of a query row do not depend on tokens, on
+ * where the row lies, on batch or heads, or on strides.  Memory beyond tokens or kv_len is never read.
+ * What the host cannot see the launch checks itself: if the effective zero point of q, k, v or probs is not an integer inside
+ * [quant_min, quant_max] (|n| could exceed 255), ALL of out and probs_out is NaN.  A non-finite element of q, k or v makes
+ * every output it reaches in the eager sequence NaN and changes no other output.
+ * No allocation, no host synchronisation, no workspace, no atomics: legal inside a stream capture.  Inference only.
+ * OSQ_ERR_UNSUPPORTED, nothing launched (the caller goes on with osq_attention_fake_quant or the eager sequence): a missing
+ * q / k / v / probs group, or one with quant_max - quant_min > 255 or a mode other than FIXED / LSQ / LSQ+ (+ SANITIZE);
+ * head_dim not in {16, 32, 64, 128}; kv_len outside [1, 16384]; q / k / v / out not 16-byte aligned, a q / k / v stride
+ * that is not a multiple of 4 elements, mask / probs_out not 4-byte aligned.  Both alpha and divisor different from 1:
+ * OSQ_ERR_INVALID_ARGUMENT. */
+int osq_attention_fake_quant_int(const float* q, const float* k, const float* v, const float* mask, float* out,
+                                 float* probs_out, int64_t batch, int64_t heads, int64_t tokens, int64_t kv_len, int64_t head_dim,
+                                 int64_t q_stride_b, int64_t q_stride_h, int64_t q_stride_t,
+                                 int64_t k_stride_b, int64_t k_stride_h, int64_t k_stride_t,
+                                 int64_t v_stride_b, int64_t v_stride_h, int64_t v_stride_t,
+                                 int64_t mask_stride_b, int64_t mask_stride_h, int64_t mask_stride_t,
+                                 float alpha, float divisor,
+                                 float* q_scale, void* q_zero_point, int q_zp_type, int q_mode,
+                                 float q_grad_factor, int q_quant_min, int q_quant_max,
+                                 float* k_scale, void* k_zero_point, int k_zp_type, int k_mode,
+                                 float k_grad_factor, int k_quant_min, int k_quant_max,
+                                 float* v_scale, void* v_zero_point, int v_zp_type, int v_mode,
+                                 float v_grad_factor, int v_quant_min, int v_quant_max,
+                                 float* probs_scale, void* probs_zero_point, int probs_zp_type, int probs_mode,
+                                 float probs_grad_factor, int probs_quant_min, int probs_quant_max,
+                                 float* ctx_scale, void* ctx_zero_point, int ctx_zp_type, int ctx_mode,
+                                 float ctx_grad_factor, int ctx_quant_min, int ctx_quant_max,
+                                 osq_stream stream);
 
 /* ------------------------------------------------------------------ beam search (beam_select.hip) */
 

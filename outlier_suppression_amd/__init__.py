@@ -82,6 +82,16 @@ def set_fast_attention(on=True):
     util_layernorm.FUSE_ATTENTION = bool(on)
 
 
+def set_fast_attention_int(on=True):
+    """The one-launch attention over whole sequences on the quantizers' integer codes (util_layernorm.FUSE_ATTENTION_INT:
+    the block of set_fast_attention with both products exact on the bf16 matrix instruction, S up to 16384,
+    csrc/attention_int.hip; needs per-tensor q / k / v / probabilities quantizers of at most 256 codes; tried before the
+    fp32 form when both are on; default OFF -- tolerance-equal to the eager sequence, not bit-equal).
+    OSQ_FAST_ATTENTION_INT=1 turns it on at load."""
+    from . import util_layernorm
+    util_layernorm.FUSE_ATTENTION_INT = bool(on)
+
+
 def set_cache_codes(on=True):
     """New KV caches of incremental decoding hold integer codes, one byte per element, instead of fp32 words
     (util_layernorm.CACHE_CODES; model/quant_bart.py, QuantizedBartCache; default OFF).  What is read back from the cache,
@@ -269,7 +279,7 @@ def reset_tier(_lib=None):
     the reference's one-thread order, the backward's sums order-free; OSQ_STRICT=1 / 0 force both; OSQ_FAST=0 / 1 the
     one-launch LayerNorm site; OSQ_FAST_SOFTMAX=1 the one-launch attention-probabilities site and OSQ_FAST_DECODE_ATTENTION=1
     the one-launch attention of a cached decoding step (unset: off); OSQ_FAST_ATTENTION=1 the one-launch attention over whole
-    sequences (unset: off); OSQ_CACHE_CODES=1 KV caches as integer codes (unset: off);
+    sequences and OSQ_FAST_ATTENTION_INT=1 its form on integer codes (unset: off); OSQ_CACHE_CODES=1 KV caches as integer codes (unset: off);
     OSQ_GRAPH_DECODE=1 generate() replays a captured decoding step (unset: off); OSQ_BEAM_SELECT=1 beam search selects a step's
     continuations with one kernel call (unset: off); OSQ_BEAM_ADVANCE=1 beam search advances its beams with one kernel call
     (unset: off); OSQ_BEAM_GRAPH=1 beam search replays a whole step, bookkeeping included, as one captured graph (unset: off);
@@ -300,7 +310,8 @@ _SWITCHES = ((set_cache_codes, "OSQ_CACHE_CODES"), (set_graph_decode, "OSQ_GRAPH
              (set_beam_advance, "OSQ_BEAM_ADVANCE"), (set_beam_graph, "OSQ_BEAM_GRAPH"), (set_greedy_advance, "OSQ_GREEDY_ADVANCE"),
              (set_greedy_graph, "OSQ_GREEDY_GRAPH"), (set_sample_advance, "OSQ_SAMPLE_ADVANCE"),
              (set_sample_graph, "OSQ_SAMPLE_GRAPH"), (set_sample_nucleus, "OSQ_SAMPLE_NUCLEUS"),
-             (set_share_cross_kv, "OSQ_SHARE_CROSS_KV"), (set_fast_lm_loss, "OSQ_FAST_LM_LOSS"))
+             (set_share_cross_kv, "OSQ_SHARE_CROSS_KV"), (set_fast_lm_loss, "OSQ_FAST_LM_LOSS"),
+             (set_fast_attention_int, "OSQ_FAST_ATTENTION_INT"))
 _apply_environment = reset_tier
 
 

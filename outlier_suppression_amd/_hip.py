@@ -177,6 +177,9 @@ SIGNATURES = {
                                                _P, _P, _I, _I, _F, _I, _I, _P, _P, _I, _I, _F, _I, _I, _P]),
     "osq_attention_fake_quant": (_I, [_P, _P, _P, _P, _P, _P, _L, _L, _L, _L, _L, _L, _L, _L, _L, _L, _L, _L, _L, _L, _L, _L, _L,
                                       _F, _F, _P, _P, _I, _I, _F, _I, _I, _P, _P, _I, _I, _F, _I, _I, _P]),
+    "osq_attention_fake_quant_int": (_I, [_P, _P, _P, _P, _P, _P, _L, _L, _L, _L, _L, _L, _L, _L, _L, _L, _L, _L, _L, _L, _L, _L, _L,
+                                          _F, _F, _P, _P, _I, _I, _F, _I, _I, _P, _P, _I, _I, _F, _I, _I, _P, _P, _I, _I, _F, _I, _I,
+                                          _P, _P, _I, _I, _F, _I, _I, _P, _P, _I, _I, _F, _I, _I, _P]),
     "osq_beam_select_workspace_bytes": (ctypes.c_size_t, [_L, _L, _L, _L]),
     "osq_beam_select": (_I, [_P, _L, _P, _P, _L, _L, _L, _P, _L, _L, _L, _L, _L, _P, _P, _P, ctypes.c_size_t, _P]),
     "osq_beam_advance": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _L, _L, _L, _L, _L, _L, _I, _D, _D, _I,

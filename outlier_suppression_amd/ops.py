@@ -1747,6 +1747,69 @@ def attention_fake_quant(q, k, v, mask, probs_quant, ctx_quant, alpha=None, divi
     return (out, probs) if want_probs else out
 
 
+ATTENTION_INT_TQ = 128         # kIntTQ of csrc/attention_int.hip: the query rows of a workgroup
+ATTENTION_INT_TK = 32          # kIntTK: the keys of a tile
+ATTENTION_INT_CHUNK = 128      # kIntChunk: the keys whose context terms are summed in fp32 before they join the int32 sum
+ATTENTION_INT_MAX_KV = 16384   # kIntMaxS
+ATTENTION_INT_MAX_RANGE = 255  # quant_max - quant_min of the q / k / v / probabilities quantizers
+
+
+def _per_tensor_quant(quant, device):
+    """``quant`` is a (scale, zero_point, ...) record of ONE scale and ONE zero point on ``device``."""
+    return (quant is not None and quant[0].numel() == 1 and quant[1].numel() == 1 and quant[0].device == device
+            and quant[1].device == device)
+
+
+def attention_int_fake_quant(q, k, v, mask, q_quant, k_quant, v_quant, probs_quant, ctx_quant, alpha=None, divisor=None,
+                             want_probs=False, *, out=None, probs_out=None):
+    """attention_fake_quant on the INTEGER CODES of the quantizers that produced q, k and v and of the probabilities
+    quantizer (osq_attention_fake_quant_int, csrc/attention_int.hip): both products on the bf16 matrix instruction, exact --
+    the context is word for word ``fq_ctx(float(sum_j n_p[j] * n_v[j]) * (s_p * s_v))``; no limit at 1024 keys.
+
+    q, k, v, mask, ``alpha`` / ``divisor``, ``out`` / ``probs_out`` and the return convention are attention_fake_quant's.
+    q_quant / k_quant / v_quant / probs_quant: (scale, zero_point, quant_min, quant_max, mode, grad_factor), per-tensor, on
+    the device of q, ``quant_max - quant_min <= 255`` -- all four required; ctx_quant: such a record or None.  Returns None
+    when one of them is missing, per-channel, elsewhere or too wide, when the layout is not fusable or the library refuses
+    it (head_dim outside 16 / 32 / 64 / 128, S above 16384, a misaligned pointer or stride): nothing was launched."""
+    lib = _hip.load()
+    _hip.require_device(q, k, v, mask)
+    if alpha is not None and divisor is not None:
+        raise ValueError("attention_int_fake_quant: give alpha or divisor, not both")
+    if not attention_fusable(q, k, v, mask):
+        return None
+    if not all(_per_tensor_quant(x, q.device) for x in (q_quant, k_quant, v_quant, probs_quant)):
+        return None
+    if ctx_quant is not None and not _per_tensor_quant(ctx_quant, q.device):
+        return None
+    b, h, t, d = q.shape
+    s = k.shape[2]
+    msb = msh = mst = 0
+    if mask is not None:
+        msb, msh, mst = mask.expand(b, h, t, s).stride()[:3]
+    for given, shape, name in ((out, (b, t, h * d), "out"), (probs_out, (b, h, t, s), "probs_out")):
+        if given is not None and (given.dtype != torch.float32 or tuple(given.shape) != shape or not given.is_contiguous()
+                                  or given.device != q.device):
+            raise ValueError(f"attention_int_fake_quant: {name} must be a contiguous fp32 tensor of shape {shape}")
+    groups = [_quant_group(x) for x in (q_quant, k_quant, v_quant, probs_quant, ctx_quant)]
+    want_probs = want_probs or probs_out is not None
+    # the library would refuse these as well; asked here so that a refused call allocates nothing
+    if d not in ATTENTION_HEAD_DIMS or s > ATTENTION_INT_MAX_KV or any(g[6] - g[5] > ATTENTION_INT_MAX_RANGE for g in groups[:4]):
+        return None
+    fresh_out = out is None
+    if fresh_out:
+        out = torch.empty((b, t, h * d), dtype=torch.float32, device=q.device)
+    probs = probs_out if probs_out is not None or not want_probs else torch.empty((b, h, t, s), dtype=torch.float32, device=q.device)
+    strides = [0 if x.shape[i] == 1 else x.stride(i) for x in (q, k, v) for i in range(3)]
+    rc = lib.osq_attention_fake_quant_int(q.data_ptr(), k.data_ptr(), v.data_ptr(), _hip.ptr(mask), out.data_ptr(), _hip.ptr(probs),
+                                          b, h, t, s, d, *strides, msb, msh, mst,
+                                          1.0 if alpha is None else float(alpha), 1.0 if divisor is None else float(divisor),
+                                          *[x for g in groups for x in g], _hip.raw_stream(q.device))
+    if rc == _hip.ERR_UNSUPPORTED:
+        return None
+    _hip.check(rc, "attention_int_fake_quant")
+    return (out, probs) if want_probs else out
+
+
 # ---------------------------------------------------------------------------------------
 # one decoding step's attention over the KV cache: scores, mask, softmax, two quantizers in one launch
 # ---------------------------------------------------------------------------------------

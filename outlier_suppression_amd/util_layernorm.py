@@ -48,6 +48,14 @@ passes, active dropout and observer passes.  Measured on MI355X (profiles/attent
 eager sequence at [32,12,128,128,64] and 1.22x at [192,16,62,62,64], but 0.84x / 0.79x / 0.72x at 384 / 512 / 512 keys, where
 FUSE_SOFTMAX is the faster switch.  ``outlier_suppression_amd.set_fast_attention(True)`` / ``OSQ_FAST_ATTENTION=1`` turn it on.
 
+``FUSE_ATTENTION_INT`` (default OFF) is the same block on the INTEGER CODES of its q / k / v / probabilities quantizers
+(``ops.attention_int_fake_quant``, csrc/attention_int.hip): every operand of both products is ``s * n`` with an integer
+|n| <= 255, so both run exactly on the bf16 matrix instruction, the scales are applied once to the exact sums, nothing of
+S's size is kept on chip and S may reach 16384.  Tolerance-equal to the eager sequence (and closer to float64 than it), hence
+off by default; it needs all four quantizers per-tensor with at most 256 codes, and is tried before FUSE_ATTENTION when both
+are on.  ``outlier_suppression_amd.set_fast_attention_int(True)`` / ``OSQ_FAST_ATTENTION_INT=1`` turn it on; the measured
+outcome per shape is in profiles/attention_int_ab.txt and README.
+
 ``CACHE_CODES`` (default OFF) is no fusion but a storage format: new KV caches (model/quant_bart.py, QuantizedBartCache) hold
 integer codes, one byte per element, written by ``ops.fake_quant_kv_append_codes`` and read as they are by
 ``ops.decode_attention_codes`` (csrc/kv_codes.hip, csrc/decode_attention.hip); the words computed are those of the fp32 cache.
@@ -127,6 +135,7 @@ FUSE_QKV = True          # the query / key / value head-split sites of a self-at
 FUSE_SOFTMAX = False     # the attention-probabilities site as one launch (tolerance-equal; set_fast_softmax / OSQ_FAST_SOFTMAX=1)
 FUSE_DECODE_ATTENTION = False   # a cached decoding step's attention after the append as one launch (tolerance-equal; set_fast_decode_attention / OSQ_FAST_DECODE_ATTENTION=1)
 FUSE_ATTENTION = False   # an attention block over a whole sequence as one launch (tolerance-equal; set_fast_attention / OSQ_FAST_ATTENTION=1)
+FUSE_ATTENTION_INT = False   # an attention block over a whole sequence as one launch on the quantizers' integer codes, exact products on the bf16 matrix instruction, tried before FUSE_ATTENTION (tolerance-equal to eager; set_fast_attention_int / OSQ_FAST_ATTENTION_INT=1)
 FUSE_KV_APPEND = True    # incremental decoding: a step's q / k / v sites + KV-cache append (+ beam reorder) as one launch (bit-identical)
 GRAPH_DECODE = False     # generate(): capture a cached decoding step into a graph and replay it (set_graph_decode / OSQ_GRAPH_DECODE=1 / generate(graph=True))
 BEAM_SELECT = False      # generate(): a beam step's log-softmax + processors + score add + top-k as one kernel call (tolerance-equal; set_beam_select / OSQ_BEAM_SELECT=1 / generate(beam_select=True))
@@ -280,11 +289,24 @@ def activation_fake_quant(act_fn, quantizer, hidden_states, observation_mask=Non
     return hidden_states
 
 
+def _not_plain(q):
+    """Why quantizer ``q`` is not in its plain quantising state -- one phrase -- or None when it is: it only fake-quantises
+    (observer off) and is per-tensor.  The one statement of that state: _plain_quantizing and the reasons of
+    attention_int_refusal both read it."""
+    if q is None:
+        return "is missing"
+    if q.ch_axis != -1:
+        return "is per-channel"
+    if q.fake_quant_enabled != 1 or q.observer_enabled == 1:
+        return "is observing or disabled"
+    return None
+
+
 def _plain_quantizing(q, x):
     """The quantizer only fake-quantises (observer off), per tensor, on the device, and nobody wants a gradient: its
     result depends on the VALUES of x alone, so x may be handed over as any view of its memory."""
-    return (q is not None and not torch.is_grad_enabled() and q.fake_quant_enabled == 1 and q.observer_enabled != 1
-            and q.ch_axis == -1 and x.is_cuda and x.dtype == torch.float32 and x.numel() and q.scale.is_cuda)
+    return (_not_plain(q) is None and not torch.is_grad_enabled() and x.is_cuda and x.dtype == torch.float32
+            and bool(x.numel()) and q.scale.is_cuda)
 
 
 def merge_heads_fake_quant(quantizer, ctx, observation_mask=None):
@@ -470,6 +492,51 @@ def attention_block_fake_quant(probs_quantizer, ctx_quantizer, q, k, v, mask=Non
     if params is None:
         return None
     return ops.attention_fake_quant(q, k, v, mask, params[0], params[1], alpha=alpha, divisor=divisor)
+
+
+def attention_int_refusal(q_quantizer, k_quantizer, v_quantizer, probs_quantizer, ctx_quantizer, q, k, v, mask=None,
+                          dropout=None):
+    """Why attention_int_block_fake_quant would not hand this call to the integer kernel -- one line -- or None when it
+    would (the library may still refuse the shape: head size, length, alignment)."""
+    if not FUSE_ATTENTION_INT:
+        return "FUSE_ATTENTION_INT is off"
+    if torch.is_grad_enabled():
+        return "autograd is on"
+    if _dropout_active(dropout):
+        return "dropout is active"
+    # the four quantizers of the products are required (both operands of both products as codes), the context's is not
+    sites = [("q", q_quantizer), ("k", k_quantizer), ("v", v_quantizer), ("probabilities", probs_quantizer)]
+    for name, quantizer in sites + ([("context", ctx_quantizer)] if ctx_quantizer is not None else []):
+        state = _not_plain(quantizer)
+        if state:
+            return f"the {name} quantizer {state}"
+    for name, quantizer in sites:
+        if quantizer.quant_max - quantizer.quant_min > ops.ATTENTION_INT_MAX_RANGE:
+            return f"the {name} quantizer has more than 256 codes"
+    if not (q.is_cuda and k.is_cuda and v.is_cuda):
+        return "q / k / v are not on a GPU"
+    if q.dim() != 4 or k.dim() != 4 or not ops.attention_fusable(q, k, v, mask):
+        return "the layout of q / k / v / mask is not fusable"
+    return None            # where the parameters live is _decode_site_params' to see
+
+
+def attention_int_block_fake_quant(q_quantizer, k_quantizer, v_quantizer, probs_quantizer, ctx_quantizer, q, k, v, mask=None,
+                                   alpha=None, divisor=None, dropout=None):
+    """attention_block_fake_quant on the INTEGER CODES of the block's own quantizers (ops.attention_int_fake_quant,
+    csrc/attention_int.hip): ``q_quantizer`` / ``k_quantizer`` / ``v_quantizer`` are the quantizers that PRODUCED q, k and
+    v, so that both products run exactly, on the bf16 matrix instruction, over S up to 16384.  Gated as that function is,
+    with FUSE_ATTENTION_INT for FUSE_ATTENTION: autograd off, dropout inactive, every quantizer in its plain quantising state
+    and per-tensor; q, k, v and the probabilities quantizer are required, ``ctx_quantizer`` may be None
+    (attention_int_refusal names the reason of a refusal).  The grad factors go by the tensors the eager quantizers see.
+    Returns the context [B, T, h*d], or None (nothing launched): the caller goes on with attention_block_fake_quant and the
+    eager sequence."""
+    if attention_int_refusal(q_quantizer, k_quantizer, v_quantizer, probs_quantizer, ctx_quantizer, q, k, v, mask, dropout):
+        return None
+    params = _decode_site_params(q, (q_quantizer, q.numel()), (k_quantizer, k.numel()), (v_quantizer, v.numel()),
+                                 (probs_quantizer, q.shape[0] * q.shape[1] * q.shape[2] * k.shape[2]), (ctx_quantizer, q.numel()))
+    if params is None:
+        return None
+    return ops.attention_int_fake_quant(q, k, v, mask, *params, alpha=alpha, divisor=divisor)
 
 
 def decode_attention_shared_fake_quant(probs_quantizer, ctx_quantizer, q, k, v, group, mask=None, dropout=None, codes=None,

@@ -1,15 +1,17 @@
 #!/usr/bin/env python3
-"""A/B of the attention block over a whole sequence (csrc/attention_block.hip): the eager sequence, the eager sequence with
-the one-launch probabilities site (util_layernorm.FUSE_SOFTMAX) and the one-launch block (util_layernorm.FUSE_ATTENTION), in
+"""A/B of the attention block over a whole sequence (csrc/attention_block.hip, csrc/attention_int.hip): the eager sequence,
+the eager sequence with the one-launch probabilities site (util_layernorm.FUSE_SOFTMAX), the one-launch block in fp32
+(util_layernorm.FUSE_ATTENTION) and the one-launch block on integer codes (util_layernorm.FUSE_ATTENTION_INT), in
 one process, every form timed in turn within each of the --reps rounds; a time is the median of the rounds with [min, max],
-a device synchronisation at either end of a round's --inner calls.  Before a block is timed the outputs of its three forms
+a device synchronisation at either end of a round's --inner calls.  Before a block is timed the outputs of its four forms
 are asserted within one quantization step of each other, and the number of codes that differ is printed.
 
   the block alone   from the fake-quantised q / k / v [B, h, T | S, d] to the quantised merged context [B, T, h * d], what
                     QuantizedBartAttention._attend runs before its output projection (W6A6 LSQ+ quantizers in the plain
                     quantising state; BERT shapes with the padding mask [B, 1, 1, S], the decoder's self-attention with the
                     causal mask [B, 1, T, S]): [B, h, T, S, d] = [32,12,128,128,64], [32,12,384,384,64], BART-large's encoder
-                    [32,16,512,512,64], its decoder's self- [192,16,62,62,64] and cross-attention [192,16,62,512,64];
+                    [32,16,512,512,64], its decoder's self- [192,16,62,62,64] and cross-attention [192,16,62,512,64], and its
+                    encoder at 1024 tokens [8,16,1024,1024,64];
   models            (--no-models skips them) a random-init BERT-base forward at 32 x 128 and 32 x 384; on the random-init
                     BART-large shape of tools/decode_bench.py the encoder pass at 32 x 512, score(num_candidates=6) and
                     generate(max_length=62, num_beams=6).
@@ -29,25 +31,27 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-FORMS = (("eager", False, False), ("FUSE_SOFTMAX", True, False), ("FUSE_ATTENTION", False, True))
+FORMS = (("eager", False, False, False), ("FUSE_SOFTMAX", True, False, False), ("FUSE_ATTENTION", False, True, False),
+         ("FUSE_ATTENTION_INT", False, False, True))
+INT = "FUSE_ATTENTION_INT"
 BLOCKS = (("bert-base 32x128", (32, 12, 128, 128, 64), "pad"), ("bert-base 32x384", (32, 12, 384, 384, 64), "pad"),
           ("bart-large encoder", (32, 16, 512, 512, 64), "pad"), ("bart-large decoder self", (192, 16, 62, 62, 64), "causal"),
-          ("bart-large decoder cross", (192, 16, 62, 512, 64), "pad"))
+          ("bart-large decoder cross", (192, 16, 62, 512, 64), "pad"), ("bart-large encoder 8x1024", (8, 16, 1024, 1024, 64), "pad"))
 A_Q = NS(quantizer="LSQPlusFakeQuantize", observer="AvgMinMaxObserver", bit=6, symmetric=False, ch_axis=-1)
 W_Q = NS(quantizer="FixedFakeQuantize", observer="MinMaxObserver", bit=6, symmetric=True, ch_axis=0)
 
 
-def set_form(softmax, attention):
+def set_form(softmax, attention, attention_int=False):
     from outlier_suppression_amd import util_layernorm as UL
-    UL.FUSE_SOFTMAX, UL.FUSE_ATTENTION = softmax, attention
+    UL.FUSE_SOFTMAX, UL.FUSE_ATTENTION, UL.FUSE_ATTENTION_INT = softmax, attention, attention_int
 
 
 def timed(fn, reps, inner):
     """{form: [ms per call] * reps}: every form in turn within each round, two warm-up rounds first."""
-    times = {name: [] for name, _, _ in FORMS}
+    times = {name: [] for name, *_ in FORMS}
     for r in range(reps + 2):
-        for name, softmax, attention in FORMS:
-            set_form(softmax, attention)
+        for name, *switches in FORMS:
+            set_form(*switches)
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             for _ in range(inner):
@@ -63,21 +67,29 @@ def report(emit, times):
     base = times["eager"]
     mb = statistics.median(base)
     spread = (max(base) - min(base)) / mb
-    for name, _, _ in FORMS:
+    for name, *_ in FORMS:
         ts = times[name]
         m = statistics.median(ts)
-        line = f"    {name:<15} {m:9.4f} ms [{min(ts):.4f}, {max(ts):.4f}]"
+        line = f"    {name:<18} {m:9.4f} ms [{min(ts):.4f}, {max(ts):.4f}]"
         if name != "eager":
             gain = (mb - m) / mb
             line += (f"   {mb / m:5.2f}x eager; the difference ({gain * 100:+.1f} %) "
                      f"{'exceeds' if abs(gain) > spread else 'does NOT exceed'} eager's own spread ({spread * 100:.1f} %)")
         emit(line)
+    # the integer form against the other two switches, each difference held to that baseline's own spread
+    m = statistics.median(times[INT])
+    for name in ("FUSE_SOFTMAX", "FUSE_ATTENTION"):
+        ts = times[name]
+        mo = statistics.median(ts)
+        gain, spread = (mo - m) / mo, (max(ts) - min(ts)) / mo
+        emit(f"    {INT} {'wins against' if m < mo else 'LOSES to'} {name}: {mo / m:5.2f}x; the difference ({gain * 100:+.1f} %) "
+             f"{'exceeds' if abs(gain) > spread else 'does NOT exceed'} {name}'s own spread ({spread * 100:.1f} %)")
 
 
 def outputs(fn):
     outs = {}
-    for name, softmax, attention in FORMS:
-        set_form(softmax, attention)
+    for name, *switches in FORMS:
+        set_form(*switches)
         with torch.no_grad():
             outs[name] = fn()
     set_form(False, False)
@@ -97,9 +109,21 @@ def block_forms(emit, label, shape, mask_kind, reps, inner):
                                                              torch.finfo(torch.float32).min)
     if mask_kind == "causal":
         mask = torch.full((t, s), torch.finfo(torch.float32).min, device=dev).triu(1)[None, None].expand(b, 1, t, s).contiguous()
-    probs_q, ctx_q = (Quantizer(None, A_Q).to(dev) for _ in range(2))
+    probs_q, ctx_q, q_q, k_q, v_q = (Quantizer(None, A_Q).to(dev) for _ in range(5))
+    with torch.no_grad():                                # q / k / v as their sites hand them on: fake-quantised
+        for qz in (q_q, k_q, v_q):
+            qz.enable_observer()
+            qz.disable_fake_quant()
+        q_q(q), k_q(k), v_q(v)
+        for qz in (q_q, k_q, v_q):
+            qz.disable_observer()
+            qz.enable_fake_quant()
+        q, k, v = q_q(q), k_q(k), v_q(v)
 
     def block():
+        out = UL.attention_int_block_fake_quant(q_q, k_q, v_q, probs_q, ctx_q, q, k, v, mask, dropout=(0.0, False))
+        if out is not None:
+            return out
         out = UL.attention_block_fake_quant(probs_q, ctx_q, q, k, v, mask, dropout=(0.0, False))
         if out is not None:
             return out
@@ -118,7 +142,7 @@ def block_forms(emit, label, shape, mask_kind, reps, inner):
         step = float(ctx_q.scale.abs().max())
         emit(f"{label}: [B, h, T, S, d] = {list(shape)}, {mask_kind} mask; scores {b * h * t * s * 4 / 1e6:.0f} MB, "
              f"{4 * b * h * t * s * d / 1e9:.1f} GFLOP")
-        for name in ("FUSE_SOFTMAX", "FUSE_ATTENTION"):
+        for name in ("FUSE_SOFTMAX", "FUSE_ATTENTION", INT):
             diff = (outs[name] - outs["eager"]).abs()
             assert float(diff.max()) <= step * (1 + 1e-3), (name, float(diff.max()), step)
             emit(f"    {name} vs eager: {int((diff > 0.5 * step).sum())} of {diff.numel()} context codes differ (by one step)")
@@ -127,11 +151,11 @@ def block_forms(emit, label, shape, mask_kind, reps, inner):
 
 
 def model_forms(emit, label, fn, reps, inner):
-    """A model call in the three forms.  A random-init W6A6 model carries a code that flips in one block through every
+    """A model call in the four forms.  A random-init W6A6 model carries a code that flips in one block through every
     later layer, so its outputs are not held to a bar here (tests/test_gpu_attention_block_model.py holds calibrated models
     to the project's bars): they must be finite, and how far they lie apart is printed."""
     outs = outputs(fn)
-    for name in ("FUSE_SOFTMAX", "FUSE_ATTENTION"):
+    for name in ("FUSE_SOFTMAX", "FUSE_ATTENTION", INT):
         a, e = outs[name], outs["eager"]
         if a.dtype.is_floating_point:
             assert bool(torch.isfinite(a).all()), (label, name)
