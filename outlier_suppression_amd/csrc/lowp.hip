@@ -29,6 +29,16 @@ typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 template <typename T>
 __device__ __forceinline__ float rd(float v) { return static_cast<float>(static_cast<T>(v)); }
 
+// rd(a * b), the fp32 product held in a register before it is rounded.  Written as static_cast<T>(a * b), hipcc selects
+// v_fma_mixlo_f16 a, b, +0 for T = _Float16, and (-0) * b + (+0) is +0: the sign of an exactly zero product is lost, which the
+// reference keeps (an upstream gradient of -0.0 gives dx = -0.0; a product with a negative scale likewise).
+template <typename T>
+__device__ __forceinline__ float mul_rd(float a, float b) {
+    float p = a * b;
+    asm("" : "+v"(p));
+    return rd<T>(p);
+}
+
 // ---------------------------------------------------------------- the in-dtype chain (FixedFakeQuantize per-tensor)
 
 template <typename T>
@@ -47,13 +57,13 @@ struct Chain {
         c = (xi < qmin) ? qmin : c;
         c = (xi > qmax) ? qmax : c;
         c = rd<T>(c);
-        return static_cast<T>(rd<T>(c - z) * s);
+        return static_cast<T>(mul_rd<T>(rd<T>(c - z), s));
     }
     // clamp's backward keeps g where qmin <= x_int <= qmax, else +0.0 (torch.where with a zero tensor, not g * mask);
     // mul's backward g * s and div's backward g / s, each rounded to T
     __device__ __forceinline__ T backward(float x, float g) const {
         const float xi = x_int(x);
-        const float gs = rd<T>(g * s);
+        const float gs = mul_rd<T>(g, s);
         const float m = (xi >= qmin && xi <= qmax) ? gs : 0.0f;
         return static_cast<T>(m / s);
     }

@@ -54,6 +54,12 @@ def _x_int(x, dtype, s, zp):
     return _rd(b + zp, dtype)
 
 
+def x_int(words, dtype, scale, zero_point):
+    """fp32 values of the chain's x_int (the number its clamp and the backward's mask see) for uint16 words of x."""
+    with np.errstate(all="ignore"):
+        return _x_int(to_f32(words, dtype), dtype, np.float32(scale), np.float32(zero_point))
+
+
 def chain_forward(x_words, dtype, scale, zero_point, quant_min, quant_max):
     """y words of util_quant.fake_quantize_per_tensor_affine(x, scale, zero_point, ...) with Python-number parameters."""
     x = to_f32(x_words, dtype)
