@@ -7,10 +7,7 @@
 // on the largest activation of the block ([B, h, T, S]: 226 MB at [32,12,384,384]) = about 28 B per element.
 // Here: read scores, write y (the mask is a broadcast operand, read from cache): 8 B per element.
 //
-// Pre-softmax step, each in the bits of the eager code it stands for (-ffp-contract=off):
-//     kPrePlain    v = scores + mask                   BART (q is scaled before the product)
-//     kPreScale    v = mask + scores * alpha           BERT, torch.add(mask, scores, alpha=1/sqrt(d)), alpha a power of two
-//     kPreDivide   v = scores / divisor + mask         BERT, other head sizes (IEEE division, not a reciprocal)
+// Pre-softmax step: the rule of attention_seq.h, its form a template parameter here (a streaming kernel).
 // Softmax as torch's CPU kernel computes it (vec_softmax_lastdim): subtract the row max, exp, sum, then MULTIPLY by the
 // reciprocal of the sum (probed against torch.softmax on one thread: p == e * (1/sum) wherever the exps agree).  expf is
 // ocml's accurate routine, not __expf; it is not Sleef's, so results are within a few ulp of torch's, not bit-equal.
@@ -24,8 +21,7 @@
 #include <math.h>
 #include <string>
 #include <hip/hip_ext.h>
-#include "osq_device.h"
-#include "osq_host.h"
+#include "attention_seq.h"
 
 namespace osq {
 
@@ -33,8 +29,6 @@ constexpr int kAttnThreads = 256;
 constexpr int kAttnWaves = kAttnThreads / OSQ_WAVE;
 constexpr int kAttnMaxCols = 4 * 8 * OSQ_WAVE;     // 2048: eight float4 per lane
 OSQ_AB_KNOB(int, g_attn_blocks, 2048);             // grid cap (osq_set_tuning("attn_blocks", n)); rows are grid-strided above it
-
-enum { kPrePlain = 0, kPreScale = 1, kPreDivide = 2 };
 
 struct AttnArgs {
     const float* scores;      // [rows, cols] contiguous; rows = batch * heads * tokens
@@ -44,26 +38,12 @@ struct AttnArgs {
     int64_t heads, tokens, rows;
     int cols;
     float alpha, divisor;
-    float* scale;             // nullable: no fake-quant (written only under OSQ_PARAM_SANITIZE)
-    void* zero_point;
-    int zp_type, mode;
-    float grad_factor, qmin, qmax;
+    DecQuant quant;           // the probabilities quantizer; scale == nullptr: softmax only
 };
-
-template <int PRE>
-__device__ __forceinline__ float pre_softmax(float s, float alpha, float divisor) {
-    if (PRE == kPreScale) return s * alpha;
-    if (PRE == kPreDivide) return s / divisor;
-    return s;
-}
 
 __device__ __forceinline__ int64_t mask_row(const AttnArgs& a, int64_t row) {
     const int64_t t = row % a.tokens, bh = row / a.tokens;
     return (bh / a.heads) * a.mask_sb + (bh % a.heads) * a.mask_sh + t * a.mask_st;
-}
-
-__device__ __forceinline__ float fq_value(float p, const AttnArgs& a, const QParams& q) {
-    return a.scale ? dequantize_value(quantize_value(p, q.scale, q.zp, a.qmin, a.qmax), q.scale, q.zp) : p;
 }
 
 template <int R, bool MASK>
@@ -84,8 +64,7 @@ __global__ __launch_bounds__(kAttnThreads) void attention_softmax_fq_kernel(Attn
     const int64_t wave0 = (static_cast<int64_t>(blockIdx.x) * kAttnThreads + threadIdx.x) / OSQ_WAVE;
     const int64_t nwaves = static_cast<int64_t>(gridDim.x) * kAttnWaves;
     const int cols4 = a.cols >> 2;
-    QParams q{1.f, 0.f};
-    if (a.scale) q = tensor_params(a.scale, a.zero_point, a.zp_type, a.mode, a.grad_factor, a.qmin, a.qmax);
+    const QParams q = dec_params(a.quant);
     float4* y4 = reinterpret_cast<float4*>(a.y);
     const WtStore ywt(y4, WT ? a.rows * cols4 : 0);
     float4 v[R], m[R];
@@ -100,7 +79,7 @@ __global__ __launch_bounds__(kAttnThreads) void attention_softmax_fq_kernel(Attn
             const float mm[4] = {MASK ? m[k].x : 0.f, MASK ? m[k].y : 0.f, MASK ? m[k].z : 0.f, MASK ? m[k].w : 0.f};
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                t[e] = pre_softmax<PRE>(t[e], a.alpha, a.divisor);
+                t[e] = pre_softmax(PRE, t[e], a.alpha, a.divisor);
                 if (MASK) t[e] = t[e] + mm[e];
             }
             v[k] = make_float4(t[0], t[1], t[2], t[3]);
@@ -120,8 +99,8 @@ __global__ __launch_bounds__(kAttnThreads) void attention_softmax_fq_kernel(Attn
         for (int k = 0; k < R; ++k) {
             const int c = lane + k * OSQ_WAVE;
             if (c < cols4) {
-                const float4 o = make_float4(fq_value(v[k].x * r, a, q), fq_value(v[k].y * r, a, q),
-                                             fq_value(v[k].z * r, a, q), fq_value(v[k].w * r, a, q));
+                const float4 o = make_float4(dec_fq(v[k].x * r, a.quant, q), dec_fq(v[k].y * r, a.quant, q),
+                                             dec_fq(v[k].z * r, a.quant, q), dec_fq(v[k].w * r, a.quant, q));
                 if (WT) ywt.put(base + c, o); else store_stream(y4 + base + c, o);
             }
         }
@@ -139,30 +118,29 @@ __global__ __launch_bounds__(kAttnThreads) void attention_softmax_fq_generic_ker
     const int lane = threadIdx.x & (OSQ_WAVE - 1);
     const int64_t wave0 = (static_cast<int64_t>(blockIdx.x) * kAttnThreads + threadIdx.x) / OSQ_WAVE;
     const int64_t nwaves = static_cast<int64_t>(gridDim.x) * kAttnWaves;
-    QParams q{1.f, 0.f};
-    if (a.scale) q = tensor_params(a.scale, a.zero_point, a.zp_type, a.mode, a.grad_factor, a.qmin, a.qmax);
+    const QParams q = dec_params(a.quant);
     for (int64_t row = wave0; row < a.rows; row += nwaves) {
         const float* xr = a.scores + row * a.cols;
         const float* mr = MASK ? a.mask + mask_row(a, row) : nullptr;
         float* yr = a.y + row * a.cols;
         float mx = -INFINITY;
         for (int j = lane; j < a.cols; j += OSQ_WAVE) {
-            float t = pre_softmax<PRE>(xr[j], a.alpha, a.divisor);
+            float t = pre_softmax(PRE, xr[j], a.alpha, a.divisor);
             if (MASK) t = t + mr[j];
             mx = fmaxf(mx, t);
         }
         mx = wave_max(mx);
         float sum = 0.f;
         for (int j = lane; j < a.cols; j += OSQ_WAVE) {
-            float t = pre_softmax<PRE>(xr[j], a.alpha, a.divisor);
+            float t = pre_softmax(PRE, xr[j], a.alpha, a.divisor);
             if (MASK) t = t + mr[j];
             sum += expf(t - mx);
         }
         const float r = 1.0f / wave_sum_f32(sum);
         for (int j = lane; j < a.cols; j += OSQ_WAVE) {
-            float t = pre_softmax<PRE>(xr[j], a.alpha, a.divisor);
+            float t = pre_softmax(PRE, xr[j], a.alpha, a.divisor);
             if (MASK) t = t + mr[j];
-            yr[j] = fq_value(expf(t - mx) * r, a, q);
+            yr[j] = dec_fq(expf(t - mx) * r, a.quant, q);
         }
     }
 }
@@ -193,12 +171,10 @@ extern "C" int osq_attention_softmax_fake_quant(const float* scores, const float
                 "attention_softmax_fake_quant: negative mask stride");
     OSQ_REQUIRE(alpha == 1.0f || divisor == 1.0f, "attention_softmax_fake_quant: give alpha or divisor, not both");
     OSQ_REQUIRE(!scale || zero_point, "attention_softmax_fake_quant: scale without zero_point");
-    OSQ_REQUIRE(!scale || ((mode & ~(OSQ_PARAM_MODE_MASK | OSQ_PARAM_SANITIZE)) == 0 && (mode & OSQ_PARAM_MODE_MASK) <= OSQ_PARAM_LSQPLUS),
-                "attention_softmax_fake_quant: bad mode");
+    OSQ_REQUIRE(!scale || dec_mode_ok(mode), "attention_softmax_fake_quant: bad mode");
     AttnArgs a{scores, y, mask, mask_stride_b, mask_stride_h, mask_stride_t, heads, tokens, rows, static_cast<int>(cols),
-               alpha, divisor, scale, zero_point, zp_type, mode, grad_factor, static_cast<float>(quant_min),
-               static_cast<float>(quant_max)};
-    const int pre = divisor != 1.0f ? kPreDivide : (alpha != 1.0f ? kPreScale : kPrePlain);
+               alpha, divisor, dec_quant(scale, zero_point, zp_type, mode, grad_factor, quant_min, quant_max)};
+    const int pre = pre_of(alpha, divisor);
     int64_t blocks = (rows + kAttnWaves - 1) / kAttnWaves;
     if (blocks > g_attn_blocks) blocks = g_attn_blocks;
     const dim3 grid(static_cast<unsigned>(blocks));

@@ -7,8 +7,7 @@
 // LDS: it reads Q, K, V and the mask and writes the context.  For every (b, head, query t):
 //
 //     s[j] = dot(q[t], k[j])                    j < S
-//     v[j] = pre(s[j]) + mask[b, h, t, j]       pre / mask as osq_attention_softmax_fake_quant (attention.hip):
-//                                               alpha != 1: mask + s * alpha; divisor != 1: s / divisor + mask; no mask: no add
+//     v[j] = pre(s[j]) + mask[b, h, t, j]       the pre-softmax rule (attention_seq.h)
 //     p    = softmax(v)                         row max subtracted, ocml's accurate expf, fp32 sum, p = e * (1 / sum); a row
 //                                               with a NaN, a +inf or only -inf is NaN (that row only)
 //     p'   = fq(p)                              attention_probs quantizer (dec_fq, attention_quant.h)
@@ -46,7 +45,7 @@
 // OSQ_PARAM_SANITIZE rides in every workgroup (all compute the same repaired words).
 #include <math.h>
 #include <hip/hip_runtime.h>
-#include "attention_quant.h"
+#include "attention_seq.h"
 
 namespace osq {
 
@@ -57,27 +56,9 @@ constexpr int kBlkTK = 32;          // key columns of a score tile: its N
 constexpr int kBlkMaxS = 1024;
 constexpr int kBlkInFlight = 16;    // steps of the context a lane loads at once (a word of V, a probability), one batch ahead
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-enum { kBlkPlain = 0, kBlkScale = 1, kBlkDivide = 2 };
-
-struct BlkArgs {
-    const float* q;            // row (b, h, t) at b * q_sb + h * q_sh + t * q_st, head_dim contiguous floats
-    const float* k;
-    const float* v;
-    const float* mask;         // nullable; row (b, h, t) at b * m_sb + h * m_sh + t * m_st, S contiguous floats
-    float* out;                // dense [B, T, heads * head_dim]
-    float* probs_out;          // nullable, dense [B, heads, T, S]
-    int64_t q_sb, q_sh, q_st, k_sb, k_sh, k_st, v_sb, v_sh, v_st, m_sb, m_sh, m_st;
-    int64_t heads;
-    int tokens, kv_len, tiles; // T, S, ceil(T / kBlkTQ)
-    int pre;
-    float alpha, divisor;
+struct BlkArgs : SeqArgs {     // tiles of kBlkTQ queries
     DecQuant probs, ctx;
 };
-
-// row of a 32 x 32 result a lane holds in register r (its column is lane & 31)
-__device__ __forceinline__ int blk_row(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
 
 template <int D, int SMAX>
 __global__ __launch_bounds__(kBlkThreads) void attention_block_kernel(BlkArgs a) {
@@ -136,10 +117,8 @@ __global__ __launch_bounds__(kBlkThreads) void attention_block_kernel(BlkArgs a)
             if (col < S) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int row = blk_row(r, half);
-                    float x = acc[r];
-                    if (a.pre == kBlkScale) x = x * a.alpha;
-                    else if (a.pre == kBlkDivide) x = x / a.divisor;
+                    const int row = mfma32_row(r, half);
+                    float x = pre_softmax(a.pre, acc[r], a.alpha, a.divisor);
                     if (mbase) x = x + mbase[static_cast<int64_t>(min(t0 + row, T - 1)) * a.m_st + col];
                     s_p[row * SP + col] = x;
                 }
@@ -208,7 +187,7 @@ __global__ __launch_bounds__(kBlkThreads) void attention_block_kernel(BlkArgs a)
         }
         __syncthreads();
 #pragma unroll
-        for (int r = 0; r < 16; ++r) s_part[w][blk_row(r, half)][l31] = acc[r];
+        for (int r = 0; r < 16; ++r) s_part[w][mfma32_row(r, half)][l31] = acc[r];
     }
     __syncthreads();
     for (int i = threadIdx.x; i < nrows * D; i += kBlkThreads) {
@@ -246,39 +225,19 @@ extern "C" int osq_attention_fake_quant(const float* q, const float* k, const fl
                                         float* ctx_scale, void* ctx_zero_point, int ctx_zp_type, int ctx_mode,
                                         float ctx_grad_factor, int ctx_quant_min, int ctx_quant_max,
                                         osq_stream stream) {
-    OSQ_REQUIRE(batch >= 0 && heads >= 0 && tokens >= 0 && tokens <= INT32_MAX && head_dim > 0, "attention_fake_quant: bad shape");
-    OSQ_REQUIRE(q_stride_b >= 0 && q_stride_h >= 0 && q_stride_t >= 0 && k_stride_b >= 0 && k_stride_h >= 0 && k_stride_t >= 0 &&
-                v_stride_b >= 0 && v_stride_h >= 0 && v_stride_t >= 0, "attention_fake_quant: negative stride");
-    OSQ_REQUIRE(!mask || (mask_stride_b >= 0 && mask_stride_h >= 0 && mask_stride_t >= 0), "attention_fake_quant: negative mask stride");
-    OSQ_REQUIRE(alpha == 1.0f || divisor == 1.0f, "attention_fake_quant: give alpha or divisor, not both");
-    OSQ_REQUIRE(!probs_scale || probs_zero_point, "attention_fake_quant: probs scale without zero_point");
-    OSQ_REQUIRE(!ctx_scale || ctx_zero_point, "attention_fake_quant: ctx scale without zero_point");
-    OSQ_REQUIRE(!probs_scale || dec_mode_ok(probs_mode), "attention_fake_quant: bad probs mode");
-    OSQ_REQUIRE(!ctx_scale || dec_mode_ok(ctx_mode), "attention_fake_quant: bad ctx mode");
-    if (head_dim != 16 && head_dim != 32 && head_dim != 64 && head_dim != 128) return OSQ_ERR_UNSUPPORTED;
-    if (kv_len < 1 || kv_len > kBlkMaxS) return OSQ_ERR_UNSUPPORTED;
-    // float4 loads of half rows of q and k; v is read by the float, and held to the same rule
-    if ((q_stride_b | q_stride_h | q_stride_t | k_stride_b | k_stride_h | k_stride_t | v_stride_b | v_stride_h | v_stride_t) & 3)
-        return OSQ_ERR_UNSUPPORTED;
-    const int64_t tiles = (tokens + kBlkTQ - 1) / kBlkTQ;
-    OSQ_REQUIRE(batch <= INT32_MAX && heads <= INT32_MAX && batch * heads <= INT32_MAX / (tiles > 0 ? tiles : 1),
-                "attention_fake_quant: bad shape");
-    if (batch * heads * tokens == 0) return OSQ_OK;
-    OSQ_REQUIRE(q && k && v && out, "attention_fake_quant: null tensor");
-    if (!aligned16(q) || !aligned16(k) || !aligned16(v) || !aligned16(out)) return OSQ_ERR_UNSUPPORTED;
-    if ((reinterpret_cast<uintptr_t>(mask) | reinterpret_cast<uintptr_t>(probs_out)) & 3u) return OSQ_ERR_UNSUPPORTED;
-    BlkArgs a{q, k, v, mask, out, probs_out, q_stride_b, q_stride_h, q_stride_t, k_stride_b, k_stride_h, k_stride_t,
-              v_stride_b, v_stride_h, v_stride_t, mask_stride_b, mask_stride_h, mask_stride_t, heads,
-              static_cast<int>(tokens), static_cast<int>(kv_len), static_cast<int>(tiles),
-              divisor != 1.0f ? kBlkDivide : (alpha != 1.0f ? kBlkScale : kBlkPlain), alpha, divisor,
+    const char* what = "attention_fake_quant";
+    BlkArgs a{{q, k, v, mask, out, probs_out, q_stride_b, q_stride_h, q_stride_t, k_stride_b, k_stride_h, k_stride_t,
+               v_stride_b, v_stride_h, v_stride_t, mask_stride_b, mask_stride_h, mask_stride_t, heads, 0, 0, 0, 0, alpha, divisor},
               OSQ_DEC_QUANT(probs), OSQ_DEC_QUANT(ctx)};
-    const dim3 grid(static_cast<unsigned>(batch * heads * tiles));
+    if (const int rc = seq_check_shape(what, a, batch, tokens, head_dim)) return rc;
+    OSQ_SEQ_REQUIRE(!probs_scale || probs_zero_point, "probs scale without zero_point");
+    OSQ_SEQ_REQUIRE(!ctx_scale || ctx_zero_point, "ctx scale without zero_point");
+    OSQ_SEQ_REQUIRE(!probs_scale || dec_mode_ok(probs_mode), "bad probs mode");
+    OSQ_SEQ_REQUIRE(!ctx_scale || dec_mode_ok(ctx_mode), "bad ctx mode");
+    int64_t blocks;
+    if (const int rc = seq_check_launch(what, a, batch, tokens, kv_len, head_dim, kBlkTQ, kBlkMaxS, &blocks); rc || !blocks) return rc;
+    const dim3 grid(static_cast<unsigned>(blocks));
     hipStream_t st = static_cast<hipStream_t>(stream);
-    switch (head_dim) {
-        case 16: launch_block<16>(a, grid, st); break;
-        case 32: launch_block<32>(a, grid, st); break;
-        case 64: launch_block<64>(a, grid, st); break;
-        default: launch_block<128>(a, grid, st); break;
-    }
-    return check_launch("attention_fake_quant");
+    OSQ_HEAD_DIM_DISPATCH(head_dim, launch_block<D>(a, grid, st));
+    return check_launch(what);
 }

@@ -11,7 +11,7 @@
 //                 quantizer once more -- on the quantizers' own outputs this is their integer, exactly
 //     N[j]  = sum_i n_q[t][i] * n_k[j][i]                 EXACT integer, |N| < 2**24
 //     sc[j] = float(N[j]) * (s_q * s_k)                   s_q * s_k rounded once
-//     x[j]  = pre(sc[j]) + mask[b, h, t, j]               pre / mask as attention_block.hip: one rounding per operation
+//     x[j]  = pre(sc[j]) + mask[b, h, t, j]               the pre-softmax rule (attention_seq.h): one rounding per operation
 //     p     = softmax(x)                                  row max exact; e = expf(x - max) (ocml); the denominator: per half h
 //                                                         of a key tile's rows (below) the chain from +0 over the tiles in
 //                                                         order and the half's 16 keys of a tile in register order, then
@@ -47,7 +47,7 @@
 // Inference only; no allocation, no host sync, no workspace, no atomics: legal inside a stream capture.
 #include <math.h>
 #include <hip/hip_runtime.h>
-#include "attention_quant.h"
+#include "attention_seq.h"
 
 namespace osq {
 
@@ -59,30 +59,13 @@ constexpr int kIntChunk = 128;           // keys whose context terms are summed 
 constexpr int kIntMaxS = 16384;          // C <= 255 * 255 * S < 2**30
 constexpr int kIntVtStride = 36;         // bf16 per row of the V^T image: 72 B, 8-byte aligned reads, rows 18 banks apart
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned short u16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned short u16x4 __attribute__((ext_vector_type(4)));
 
-enum { kIntPlain = 0, kIntScale = 1, kIntDivide = 2 };
-
-struct IntArgs {
-    const float* q;            // row (b, h, t) at b * q_sb + h * q_sh + t * q_st, head_dim contiguous floats
-    const float* k;
-    const float* v;
-    const float* mask;         // nullable; row (b, h, t) at b * m_sb + h * m_sh + t * m_st, S contiguous floats
-    float* out;                // dense [B, T, heads * head_dim]
-    float* probs_out;          // nullable, dense [B, heads, T, S]
-    int64_t q_sb, q_sh, q_st, k_sb, k_sh, k_st, v_sb, v_sh, v_st, m_sb, m_sh, m_st;
-    int64_t heads;
-    int tokens, kv_len, tiles; // T, S, ceil(T / kIntTQ)
-    int pre;
-    float alpha, divisor;
+struct IntArgs : SeqArgs {     // tiles of kIntTQ queries
     DecQuant qq, kq, vq, probs, ctx;
 };
-
-// key row of a 32 x 32 result a lane holds in register r (its column, the query, is lane & 31)
-__device__ __forceinline__ int int_row(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
 
 // the bf16 word of an integer |n| <= 256 (exact: the low 16 bits are zero) or of a NaN
 __device__ __forceinline__ unsigned short int_bf16(float n) {
@@ -195,7 +178,7 @@ __global__ __launch_bounds__(kIntThreads) void attention_int_kernel(IntArgs a) {
             }
         }
     };
-    // x[r] of the rule for the tile in LDS: key jt * 32 + int_row(r, half), query tq (keys beyond S: whatever, never used)
+    // x[r] of the rule for the tile in LDS: key jt * 32 + mfma32_row(r, half), query tq (keys beyond S: whatever, never used)
     const auto score_tile = [&](int jt, float* x) {
         f32x16 acc = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -205,10 +188,8 @@ __global__ __launch_bounds__(kIntThreads) void attention_int_kernel(IntArgs a) {
         }
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            float y = acc[r] * sqk;
-            if (a.pre == kIntScale) y = y * a.alpha;
-            else if (a.pre == kIntDivide) y = y / a.divisor;
-            if (mbase) y = y + mbase[min(jt * kIntTK + int_row(r, half), S - 1)];
+            float y = pre_softmax(a.pre, acc[r] * sqk, a.alpha, a.divisor);
+            if (mbase) y = y + mbase[min(jt * kIntTK + mfma32_row(r, half), S - 1)];
             x[r] = y;
         }
     };
@@ -237,7 +218,7 @@ __global__ __launch_bounds__(kIntThreads) void attention_int_kernel(IntArgs a) {
         score_tile(jt, x);
 #pragma unroll
         for (int r = 0; r < 16; ++r)
-            if (jt * kIntTK + int_row(r, half) < S) mx = fmaxf(mx, x[r]);
+            if (jt * kIntTK + mfma32_row(r, half) < S) mx = fmaxf(mx, x[r]);
     });
     mx = fmaxf(mx, __shfl_xor(mx, 32, OSQ_WAVE));
 
@@ -248,7 +229,7 @@ __global__ __launch_bounds__(kIntThreads) void attention_int_kernel(IntArgs a) {
         score_tile(jt, x);
 #pragma unroll
         for (int r = 0; r < 16; ++r)
-            if (jt * kIntTK + int_row(r, half) < S) sum = sum + expf(x[r] - mx);
+            if (jt * kIntTK + mfma32_row(r, half) < S) sum = sum + expf(x[r] - mx);
     });
     {
         const float other = __shfl_xor(sum, 32, OSQ_WAVE);
@@ -285,7 +266,7 @@ __global__ __launch_bounds__(kIntThreads) void attention_int_kernel(IntArgs a) {
         u16x8 pf[2];
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int key = jt * kIntTK + int_row(r, half);
+            const int key = jt * kIntTK + mfma32_row(r, half);
             float n = 0.f;
             if (key < S) {
                 const float p = expf(x[r] - mx) * rcp;
@@ -358,43 +339,23 @@ extern "C" int osq_attention_fake_quant_int(const float* q, const float* k, cons
                                             float* ctx_scale, void* ctx_zero_point, int ctx_zp_type, int ctx_mode,
                                             float ctx_grad_factor, int ctx_quant_min, int ctx_quant_max,
                                             osq_stream stream) {
-    OSQ_REQUIRE(batch >= 0 && heads >= 0 && tokens >= 0 && tokens <= INT32_MAX && head_dim > 0, "attention_fake_quant_int: bad shape");
-    OSQ_REQUIRE(q_stride_b >= 0 && q_stride_h >= 0 && q_stride_t >= 0 && k_stride_b >= 0 && k_stride_h >= 0 && k_stride_t >= 0 &&
-                v_stride_b >= 0 && v_stride_h >= 0 && v_stride_t >= 0, "attention_fake_quant_int: negative stride");
-    OSQ_REQUIRE(!mask || (mask_stride_b >= 0 && mask_stride_h >= 0 && mask_stride_t >= 0), "attention_fake_quant_int: negative mask stride");
-    OSQ_REQUIRE(alpha == 1.0f || divisor == 1.0f, "attention_fake_quant_int: give alpha or divisor, not both");
-    OSQ_REQUIRE(!ctx_scale || ctx_zero_point, "attention_fake_quant_int: ctx scale without zero_point");
-    OSQ_REQUIRE(!ctx_scale || dec_mode_ok(ctx_mode), "attention_fake_quant_int: bad ctx mode");
+    const char* what = "attention_fake_quant_int";
+    IntArgs a{{q, k, v, mask, out, probs_out, q_stride_b, q_stride_h, q_stride_t, k_stride_b, k_stride_h, k_stride_t,
+               v_stride_b, v_stride_h, v_stride_t, mask_stride_b, mask_stride_h, mask_stride_t, heads, 0, 0, 0, 0, alpha, divisor},
+              OSQ_DEC_QUANT(q), OSQ_DEC_QUANT(k), OSQ_DEC_QUANT(v), OSQ_DEC_QUANT(probs), OSQ_DEC_QUANT(ctx)};
+    if (const int rc = seq_check_shape(what, a, batch, tokens, head_dim)) return rc;
+    OSQ_SEQ_REQUIRE(!ctx_scale || ctx_zero_point, "ctx scale without zero_point");
+    OSQ_SEQ_REQUIRE(!ctx_scale || dec_mode_ok(ctx_mode), "bad ctx mode");
     // the four quantizers of the products: all there, per-tensor records, at most 256 codes
     if (!int_site_ok(q_scale, q_zero_point, q_mode, q_quant_min, q_quant_max) ||
         !int_site_ok(k_scale, k_zero_point, k_mode, k_quant_min, k_quant_max) ||
         !int_site_ok(v_scale, v_zero_point, v_mode, v_quant_min, v_quant_max) ||
         !int_site_ok(probs_scale, probs_zero_point, probs_mode, probs_quant_min, probs_quant_max))
         return OSQ_ERR_UNSUPPORTED;
-    if (head_dim != 16 && head_dim != 32 && head_dim != 64 && head_dim != 128) return OSQ_ERR_UNSUPPORTED;
-    if (kv_len < 1 || kv_len > kIntMaxS) return OSQ_ERR_UNSUPPORTED;
-    // float4 loads of rows of q, k and v
-    if ((q_stride_b | q_stride_h | q_stride_t | k_stride_b | k_stride_h | k_stride_t | v_stride_b | v_stride_h | v_stride_t) & 3)
-        return OSQ_ERR_UNSUPPORTED;
-    const int64_t tiles = (tokens + kIntTQ - 1) / kIntTQ;
-    OSQ_REQUIRE(batch <= INT32_MAX && heads <= INT32_MAX && batch * heads <= INT32_MAX / (tiles > 0 ? tiles : 1),
-                "attention_fake_quant_int: bad shape");
-    if (batch * heads * tokens == 0) return OSQ_OK;
-    OSQ_REQUIRE(q && k && v && out, "attention_fake_quant_int: null tensor");
-    if (!aligned16(q) || !aligned16(k) || !aligned16(v) || !aligned16(out)) return OSQ_ERR_UNSUPPORTED;
-    if ((reinterpret_cast<uintptr_t>(mask) | reinterpret_cast<uintptr_t>(probs_out)) & 3u) return OSQ_ERR_UNSUPPORTED;
-    IntArgs a{q, k, v, mask, out, probs_out, q_stride_b, q_stride_h, q_stride_t, k_stride_b, k_stride_h, k_stride_t,
-              v_stride_b, v_stride_h, v_stride_t, mask_stride_b, mask_stride_h, mask_stride_t, heads,
-              static_cast<int>(tokens), static_cast<int>(kv_len), static_cast<int>(tiles),
-              divisor != 1.0f ? kIntDivide : (alpha != 1.0f ? kIntScale : kIntPlain), alpha, divisor,
-              OSQ_DEC_QUANT(q), OSQ_DEC_QUANT(k), OSQ_DEC_QUANT(v), OSQ_DEC_QUANT(probs), OSQ_DEC_QUANT(ctx)};
-    const dim3 grid(static_cast<unsigned>(batch * heads * tiles));
+    int64_t blocks;
+    if (const int rc = seq_check_launch(what, a, batch, tokens, kv_len, head_dim, kIntTQ, kIntMaxS, &blocks); rc || !blocks) return rc;
+    const dim3 grid(static_cast<unsigned>(blocks));
     hipStream_t st = static_cast<hipStream_t>(stream);
-    switch (head_dim) {
-        case 16: hipLaunchKernelGGL((attention_int_kernel<16>), grid, dim3(kIntThreads), 0, st, a); break;
-        case 32: hipLaunchKernelGGL((attention_int_kernel<32>), grid, dim3(kIntThreads), 0, st, a); break;
-        case 64: hipLaunchKernelGGL((attention_int_kernel<64>), grid, dim3(kIntThreads), 0, st, a); break;
-        default: hipLaunchKernelGGL((attention_int_kernel<128>), grid, dim3(kIntThreads), 0, st, a); break;
-    }
-    return check_launch("attention_fake_quant_int");
+    OSQ_HEAD_DIM_DISPATCH(head_dim, hipLaunchKernelGGL((attention_int_kernel<D>), grid, dim3(kIntThreads), 0, st, a));
+    return check_launch(what);
 }

@@ -1,6 +1,7 @@
-// The quantizer record of the one-launch attention kernels (decode_attention.hip: one query token over the KV cache;
-// attention_block.hip: whole sequences): a parameter group of the C ABI as the kernel holds it, the parameters that reach
-// the quantiser (the repair under OSQ_PARAM_SANITIZE rides in tensor_params) and the fake-quant of one value.
+// The quantizer record of every one-launch attention kernel (decode_attention.hip: one query token over the KV cache;
+// attention.hip, attention_block.hip, attention_int.hip: whole sequences, through attention_seq.h): a parameter group of the
+// C ABI as the kernel holds it, the parameters that reach the quantiser (the repair under OSQ_PARAM_SANITIZE rides in
+// tensor_params), the fake-quant of one value and the check of a group's mode.
 #pragma once
 #include "osq_device.h"
 #include "osq_host.h"

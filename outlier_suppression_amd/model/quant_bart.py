@@ -28,8 +28,8 @@ from .losses import LmLossInfo, classification_loss, lm_loss, span_loss, token_l
 from .. import ops
 from .. import util_layernorm as _UL
 from ..quantization import QuantizedModule, Quantizer
-from ..util_layernorm import (GammaResidual, QuantizedLayerNorm, activation_fake_quant, attention_block_fake_quant,
-                              attention_int_block_fake_quant, attention_probs_fake_quant,
+from ..util_layernorm import (GammaResidual, QuantizedLayerNorm, activation_fake_quant, attention_probs_fake_quant,
+                              attention_sequence_fake_quant,
                               decode_attention_at_fake_quant, decode_attention_fake_quant, decode_attention_shared_fake_quant,
                               decode_grad_table,
                               kv_append_codes_fake_quant, kv_append_fake_quant,
@@ -755,14 +755,10 @@ class QuantizedBartAttention(QuantizedModule):
             # several query tokens -- the encoder, a teacher-forced decoder, cross-attention, a prefill: one launch, on the
             # integer codes of q / k / v (keys and values from a cache included: they are their quantizers' outputs) under
             # FUSE_ATTENTION_INT, else in fp32 under FUSE_ATTENTION
-            out = attention_int_block_fake_quant(self.query_post_act_fake_quantize, self.key_post_act_fake_quantize,
-                                                 self.value_post_act_fake_quantize, self.attention_probs_post_act_fake_quantize,
-                                                 self.context_post_act_fake_quantize, q, k, v, attention_mask,
-                                                 dropout=(self.dropout, self.training))
-            if out is not None:
-                return self._project(out, observation_mask)
-            out = attention_block_fake_quant(self.attention_probs_post_act_fake_quantize, self.context_post_act_fake_quantize,
-                                             q, k, v, attention_mask, dropout=(self.dropout, self.training))
+            out = attention_sequence_fake_quant(self.query_post_act_fake_quantize, self.key_post_act_fake_quantize,
+                                                self.value_post_act_fake_quantize, self.attention_probs_post_act_fake_quantize,
+                                                self.context_post_act_fake_quantize, q, k, v, attention_mask,
+                                                dropout=(self.dropout, self.training))
             if out is not None:
                 return self._project(out, observation_mask)
         proj = (bsz * self.num_heads, -1, self.head_dim)

@@ -21,8 +21,8 @@ from torch import nn
 from .losses import classification_loss, span_loss, with_loss
 
 from ..quantization import QuantizedModule, Quantizer
-from ..util_layernorm import (GammaResidual, QuantizedLayerNorm, activation_fake_quant, attention_block_fake_quant,
-                              attention_int_block_fake_quant, attention_probs_fake_quant,
+from ..util_layernorm import (GammaResidual, QuantizedLayerNorm, activation_fake_quant, attention_probs_fake_quant,
+                              attention_sequence_fake_quant,
                               merge_heads_fake_quant, qkv_heads_fake_quant, residual_layernorm)
 
 
@@ -93,17 +93,12 @@ class QuantizedBertSelfAttention(QuantizedModule):
         if fused is not None:
             # everything from here to the merged context as one launch (q / k / v are quantised already): on their integer
             # codes under FUSE_ATTENTION_INT, else in fp32 under FUSE_ATTENTION
-            out = attention_int_block_fake_quant(self.query_permute_post_act_fake_quantize,
-                                                 self.key_transpose_post_act_fake_quantize,
-                                                 self.value_permute_post_act_fake_quantize,
-                                                 self.attention_probs_post_act_fake_quantize,
-                                                 self.context_view_post_act_fake_quantize if self.qoutput else None,
-                                                 q, fused[1], v, attention_mask, dropout=self.dropout, **scale)
-            if out is not None:
-                return out
-            out = attention_block_fake_quant(self.attention_probs_post_act_fake_quantize,
-                                             self.context_view_post_act_fake_quantize if self.qoutput else None,
-                                             q, fused[1], v, attention_mask, dropout=self.dropout, **scale)
+            out = attention_sequence_fake_quant(self.query_permute_post_act_fake_quantize,
+                                                self.key_transpose_post_act_fake_quantize,
+                                                self.value_permute_post_act_fake_quantize,
+                                                self.attention_probs_post_act_fake_quantize,
+                                                self.context_view_post_act_fake_quantize if self.qoutput else None,
+                                                q, fused[1], v, attention_mask, dropout=self.dropout, **scale)
             if out is not None:
                 return out
         scores = torch.matmul(q, kt)

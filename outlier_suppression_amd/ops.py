@@ -1618,6 +1618,20 @@ def _as_4d(x):
     return (1,) * (4 - x.dim()) + tuple(x.shape)
 
 
+def _mask_fusable(mask, shape, device):
+    """The mask rule of the attention sites over whole sequences: None, or fp32 on ``device``, of at most four dims,
+    broadcastable to ``shape`` with a contiguous last axis (any strides, 0 included, on the others)."""
+    if mask is None:
+        return True
+    if not (mask.device == device and mask.dtype == torch.float32 and mask.dim() <= 4):
+        return False
+    try:
+        m = mask.expand(shape)
+    except RuntimeError:
+        return False
+    return shape[-1] == 1 or m.stride(-1) == 1
+
+
 def attention_softmax_fusable(scores, mask=None):
     """Layout rules of osq_attention_softmax_fake_quant: scores a contiguous fp32 [.., T, S] tensor of at most four dims
     on the device; mask None, or fp32 on the same device, broadcastable to scores with a contiguous last axis (any
@@ -1625,15 +1639,7 @@ def attention_softmax_fusable(scores, mask=None):
     if not (scores.is_cuda and scores.dtype == torch.float32 and 1 <= scores.dim() <= 4 and scores.is_contiguous()
             and scores.numel()):
         return False
-    if mask is None:
-        return True
-    if not (mask.device == scores.device and mask.dtype == torch.float32 and mask.dim() <= 4):
-        return False
-    try:
-        m = mask.expand(scores.shape)
-    except RuntimeError:
-        return False
-    return scores.shape[-1] == 1 or m.stride(-1) == 1
+    return _mask_fusable(mask, scores.shape, scores.device)
 
 
 def attention_softmax_fake_quant(scores, mask=None, *, alpha=None, divisor=None, quant=None):
@@ -1655,17 +1661,11 @@ def attention_softmax_fake_quant(scores, mask=None, *, alpha=None, divisor=None,
         strides = (0,) * (4 - scores.dim()) + tuple(mask.expand(scores.shape).stride())
         sb, sh, st = strides[0], strides[1], strides[2]
     y = torch.empty_like(scores)
-    if quant is None:
-        s_ptr, z_ptr, z_type, mode, gf, qmin, qmax = None, None, ZP_INT32, PARAM_FIXED, 1.0, 0, 1
-    else:
-        scale, zero_point, qmin, qmax, mode, gf = quant
-        _hip.require_device(scale, zero_point)
-        s_ptr, z_ptr, z_type = scale.data_ptr(), zero_point.data_ptr(), _zp_type(zero_point)
     _hip.check(lib.osq_attention_softmax_fake_quant(scores.data_ptr(), _hip.ptr(mask), b, h, t, s, sb, sh, st,
                                                     1.0 if alpha is None else float(alpha),
-                                                    1.0 if divisor is None else float(divisor), y.data_ptr(), s_ptr,
-                                                    z_ptr, z_type, int(mode), float(gf), int(qmin), int(qmax),
-                                                    _hip.raw_stream(scores.device)), "attention_softmax_fake_quant")
+                                                    1.0 if divisor is None else float(divisor), y.data_ptr(),
+                                                    *_quant_group(quant), _hip.raw_stream(scores.device)),
+               "attention_softmax_fake_quant")
     return y
 
 
@@ -1693,15 +1693,52 @@ def attention_fusable(q, k, v, mask=None):
     for x in (q, k, v):
         if x.dtype != torch.float32 or x.device != q.device or (d > 1 and x.stride(3) != 1):
             return False
-    if mask is None:
-        return True
-    if not (mask.device == q.device and mask.dtype == torch.float32 and mask.dim() <= 4):
-        return False
-    try:
-        m = mask.expand(b, h, t, s)
-    except RuntimeError:
-        return False
-    return s == 1 or m.stride(3) == 1
+    return _mask_fusable(mask, (b, h, t, s), q.device)
+
+
+def _attention(what, entry, q, k, v, mask, quants, n_required, max_kv, alpha, divisor, want_probs, out, probs_out):
+    """The body of attention_fake_quant and attention_int_fake_quant below; ``what`` is the caller's name in messages, ``entry``
+    the library's function.  ``quants``: the quantizer records in the order of the entry's groups, the context's last.  The
+    first ``n_required`` of them are the operands of exact products: each must be there, per-tensor, on the device of q and
+    of at most 256 codes, and the context's, where given, per-tensor on that device.  ``max_kv``: the keys the kernel takes.
+    Returns out -- with ``want_probs`` or ``probs_out`` the pair (out, probabilities) -- or None when the call is not taken;
+    what the library would refuse by head size, length or code range is asked before anything is allocated."""
+    lib = _hip.load()
+    _hip.require_device(q, k, v, mask)
+    if alpha is not None and divisor is not None:
+        raise ValueError(f"{what}: give alpha or divisor, not both")
+    if not attention_fusable(q, k, v, mask):
+        return None
+    if n_required:
+        checked = list(quants[:n_required]) + [x for x in quants[n_required:] if x is not None]
+        if not all(_per_tensor_quant(x, q.device) for x in checked):
+            return None
+    b, h, t, d = q.shape
+    s = k.shape[2]
+    msb = msh = mst = 0
+    if mask is not None:
+        msb, msh, mst = mask.expand(b, h, t, s).stride()[:3]
+    for given, shape, name in ((out, (b, t, h * d), "out"), (probs_out, (b, h, t, s), "probs_out")):
+        if given is not None and (given.dtype != torch.float32 or tuple(given.shape) != shape or not given.is_contiguous()
+                                  or given.device != q.device):
+            raise ValueError(f"{what}: {name} must be a contiguous fp32 tensor of shape {shape}")
+    groups = [_quant_group(x) for x in quants]
+    if d not in ATTENTION_HEAD_DIMS or s > max_kv or any(g[6] - g[5] > ATTENTION_INT_MAX_RANGE for g in groups[:n_required]):
+        return None
+    if out is None:
+        out = torch.empty((b, t, h * d), dtype=torch.float32, device=q.device)
+    want_probs = want_probs or probs_out is not None
+    probs = probs_out if probs_out is not None or not want_probs else torch.empty((b, h, t, s), dtype=torch.float32, device=q.device)
+    # the stride of an axis of one element is never multiplied by anything but 0
+    strides = [0 if x.shape[i] == 1 else x.stride(i) for x in (q, k, v) for i in range(3)]
+    rc = getattr(lib, entry)(q.data_ptr(), k.data_ptr(), v.data_ptr(), _hip.ptr(mask), out.data_ptr(), _hip.ptr(probs),
+                             b, h, t, s, d, *strides, msb, msh, mst,
+                             1.0 if alpha is None else float(alpha), 1.0 if divisor is None else float(divisor),
+                             *[x for g in groups for x in g], _hip.raw_stream(q.device))
+    if rc == _hip.ERR_UNSUPPORTED:
+        return None
+    _hip.check(rc, what)
+    return (out, probs) if want_probs else out
 
 
 def attention_fake_quant(q, k, v, mask, probs_quant, ctx_quant, alpha=None, divisor=None, want_probs=False, *, out=None,
@@ -1716,35 +1753,8 @@ def attention_fake_quant(q, k, v, mask, probs_quant, ctx_quant, alpha=None, divi
     ``want_probs`` the pair (output, fake-quantised probabilities [B, h, T, S]) -- or None when the layout is not fusable or the library refuses
     it (head_dim outside 16 / 32 / 64 / 128, S above 1024, a misaligned pointer or stride): nothing was launched, the
     caller runs the eager sequence."""
-    lib = _hip.load()
-    _hip.require_device(q, k, v, mask)
-    if alpha is not None and divisor is not None:
-        raise ValueError("attention_fake_quant: give alpha or divisor, not both")
-    if not attention_fusable(q, k, v, mask):
-        return None
-    b, h, t, d = q.shape
-    s = k.shape[2]
-    msb = msh = mst = 0
-    if mask is not None:
-        msb, msh, mst = mask.expand(b, h, t, s).stride()[:3]
-    for given, shape, name in ((out, (b, t, h * d), "out"), (probs_out, (b, h, t, s), "probs_out")):
-        if given is not None and (given.dtype != torch.float32 or tuple(given.shape) != shape or not given.is_contiguous()
-                                  or given.device != q.device):
-            raise ValueError(f"attention_fake_quant: {name} must be a contiguous fp32 tensor of shape {shape}")
-    if out is None:
-        out = torch.empty((b, t, h * d), dtype=torch.float32, device=q.device)
-    want_probs = want_probs or probs_out is not None
-    probs = probs_out if probs_out is not None or not want_probs else torch.empty((b, h, t, s), dtype=torch.float32, device=q.device)
-    # the stride of an axis of one element is never multiplied by anything but 0
-    strides = [0 if x.shape[i] == 1 else x.stride(i) for x in (q, k, v) for i in range(3)]
-    rc = lib.osq_attention_fake_quant(q.data_ptr(), k.data_ptr(), v.data_ptr(), _hip.ptr(mask), out.data_ptr(), _hip.ptr(probs),
-                                      b, h, t, s, d, *strides, msb, msh, mst,
-                                      1.0 if alpha is None else float(alpha), 1.0 if divisor is None else float(divisor),
-                                      *_quant_group(probs_quant), *_quant_group(ctx_quant), _hip.raw_stream(q.device))
-    if rc == _hip.ERR_UNSUPPORTED:
-        return None
-    _hip.check(rc, "attention_fake_quant")
-    return (out, probs) if want_probs else out
+    return _attention("attention_fake_quant", "osq_attention_fake_quant", q, k, v, mask, (probs_quant, ctx_quant), 0,
+                      ATTENTION_MAX_KV, alpha, divisor, want_probs, out, probs_out)
 
 
 ATTENTION_INT_TQ = 128         # kIntTQ of csrc/attention_int.hip: the query rows of a workgroup
@@ -1771,43 +1781,9 @@ def attention_int_fake_quant(q, k, v, mask, q_quant, k_quant, v_quant, probs_qua
     the device of q, ``quant_max - quant_min <= 255`` -- all four required; ctx_quant: such a record or None.  Returns None
     when one of them is missing, per-channel, elsewhere or too wide, when the layout is not fusable or the library refuses
     it (head_dim outside 16 / 32 / 64 / 128, S above 16384, a misaligned pointer or stride): nothing was launched."""
-    lib = _hip.load()
-    _hip.require_device(q, k, v, mask)
-    if alpha is not None and divisor is not None:
-        raise ValueError("attention_int_fake_quant: give alpha or divisor, not both")
-    if not attention_fusable(q, k, v, mask):
-        return None
-    if not all(_per_tensor_quant(x, q.device) for x in (q_quant, k_quant, v_quant, probs_quant)):
-        return None
-    if ctx_quant is not None and not _per_tensor_quant(ctx_quant, q.device):
-        return None
-    b, h, t, d = q.shape
-    s = k.shape[2]
-    msb = msh = mst = 0
-    if mask is not None:
-        msb, msh, mst = mask.expand(b, h, t, s).stride()[:3]
-    for given, shape, name in ((out, (b, t, h * d), "out"), (probs_out, (b, h, t, s), "probs_out")):
-        if given is not None and (given.dtype != torch.float32 or tuple(given.shape) != shape or not given.is_contiguous()
-                                  or given.device != q.device):
-            raise ValueError(f"attention_int_fake_quant: {name} must be a contiguous fp32 tensor of shape {shape}")
-    groups = [_quant_group(x) for x in (q_quant, k_quant, v_quant, probs_quant, ctx_quant)]
-    want_probs = want_probs or probs_out is not None
-    # the library would refuse these as well; asked here so that a refused call allocates nothing
-    if d not in ATTENTION_HEAD_DIMS or s > ATTENTION_INT_MAX_KV or any(g[6] - g[5] > ATTENTION_INT_MAX_RANGE for g in groups[:4]):
-        return None
-    fresh_out = out is None
-    if fresh_out:
-        out = torch.empty((b, t, h * d), dtype=torch.float32, device=q.device)
-    probs = probs_out if probs_out is not None or not want_probs else torch.empty((b, h, t, s), dtype=torch.float32, device=q.device)
-    strides = [0 if x.shape[i] == 1 else x.stride(i) for x in (q, k, v) for i in range(3)]
-    rc = lib.osq_attention_fake_quant_int(q.data_ptr(), k.data_ptr(), v.data_ptr(), _hip.ptr(mask), out.data_ptr(), _hip.ptr(probs),
-                                          b, h, t, s, d, *strides, msb, msh, mst,
-                                          1.0 if alpha is None else float(alpha), 1.0 if divisor is None else float(divisor),
-                                          *[x for g in groups for x in g], _hip.raw_stream(q.device))
-    if rc == _hip.ERR_UNSUPPORTED:
-        return None
-    _hip.check(rc, "attention_int_fake_quant")
-    return (out, probs) if want_probs else out
+    return _attention("attention_int_fake_quant", "osq_attention_fake_quant_int", q, k, v, mask,
+                      (q_quant, k_quant, v_quant, probs_quant, ctx_quant), 4, ATTENTION_INT_MAX_KV, alpha, divisor, want_probs,
+                      out, probs_out)
 
 
 # ---------------------------------------------------------------------------------------

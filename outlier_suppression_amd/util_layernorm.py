@@ -151,16 +151,38 @@ FAST_LM_LOSS = False     # forward(labels=...) of the BART LM wrapper: the loss 
 CACHE_CODES = False      # incremental decoding: new KV caches hold integer codes, one byte per element (same words read back; set_cache_codes / OSQ_CACHE_CODES=1)
 
 
+class _Numel:
+    """Stands for a tensor of which a quantizer's grad factor needs the element count only."""
+
+    def __init__(self, n):
+        self.n = n
+
+    def numel(self):
+        return self.n
+
+
+def _site_record(q, numel):
+    """The launch record of quantizer ``q`` at a one-launch site, (scale, zero_point, quant_min, quant_max, mode, grad_factor)
+    as the ops functions take it -- the one statement of it; whether the site is fusable is each caller's own condition (a
+    per-tensor quantizer that only fake-quantises, in every one).  ``numel``: the elements of the tensor the quantizer would
+    see, which a learnable quantizer's grad factor goes by.  With the observer off a learnable quantizer's parameter repair
+    (fake_quant.py:188-191) rides in the launch under PARAM_SANITIZE: a kernel may then write scale / zero_point, so the
+    quantizer is told (_touch_qparams).  For the activation quantizers of these sites nobody observes that: _qparam_epoch is
+    read by quantization/weight_cache.py alone, for weight quantizers."""
+    mode = q.param_mode
+    if isinstance(q, _LearnableFakeQuantize):
+        mode |= ops.PARAM_SANITIZE
+        q._touch_qparams()
+    return (q.scale.data, q.zero_point.data, q.quant_min, q.quant_max, mode,
+            q._grad_factor(_Numel(numel)) if q.param_mode != ops.PARAM_FIXED else 1.0)
+
+
 def _fused_site(mod, x, hidden, gamma, weight, bias, eps, observation_mask):
     """One launch for residual + LayerNorm (+ fake-quant when the site's quantizer is in its plain quantising state)."""
     q = mod.layernorm_post_act_fake_quantize if mod.qoutput else None
     quant = None
     if q is not None and q.fake_quant_enabled == 1 and q.observer_enabled != 1 and q.ch_axis == -1 and q.scale.is_cuda:
-        mode = q.param_mode
-        if isinstance(q, _LearnableFakeQuantize):
-            mode |= ops.PARAM_SANITIZE            # observer off: the parameter repair of fake_quant.py:188-191 rides along
-        quant = (q.scale.data, q.zero_point.data, q.quant_min, q.quant_max, mode,
-                 q._grad_factor(x) if q.param_mode != ops.PARAM_FIXED else 1.0)
+        quant = _site_record(q, x.numel())
     y = ops.residual_layernorm_fake_quant(x, hidden, gamma, weight, bias, eps, quant)
     if q is not None and quant is None:           # observing, disabled, or per-channel: the quantizer's own path
         y = q(y, observation_mask, 1)
@@ -277,12 +299,7 @@ def activation_fake_quant(act_fn, quantizer, hidden_states, observation_mask=Non
             and q.observer_enabled != 1 and q.ch_axis == -1 and hidden_states.is_cuda and hidden_states.dtype == torch.float32
             and hidden_states.is_contiguous() and hidden_states.numel() and hidden_states.data_ptr() % 16 == 0
             and q.scale.is_cuda and ops.is_exact_gelu(act_fn)):
-        mode = q.param_mode
-        if isinstance(q, _LearnableFakeQuantize):
-            mode |= ops.PARAM_SANITIZE
-        gf = q._grad_factor(hidden_states) if q.param_mode != ops.PARAM_FIXED else 1.0
-        return ops.gelu_fake_quant_per_tensor(hidden_states, q.scale.data, q.zero_point.data, q.quant_min, q.quant_max,
-                                              mode, gf)
+        return ops.gelu_fake_quant_per_tensor(hidden_states, *_site_record(q, hidden_states.numel()))
     hidden_states = act_fn(hidden_states)
     if q is not None:
         hidden_states = q(hidden_states, observation_mask, 1)
@@ -357,12 +374,7 @@ def qkv_heads_fake_quant(quantizers, projections, heads):
     for q, x in zip(quantizers, projections):
         if not (_plain_quantizing(q, x) and x.is_contiguous() and x.shape == x0.shape and x.data_ptr() % 16 == 0):
             return None
-        mode = q.param_mode
-        if isinstance(q, _LearnableFakeQuantize):
-            mode |= ops.PARAM_SANITIZE
-            q._touch_qparams()
-        params.append((q.scale.data, q.zero_point.data, q.quant_min, q.quant_max, mode,
-                       q._grad_factor(x) if q.param_mode != ops.PARAM_FIXED else 1.0))
+        params.append(_site_record(q, x.numel()))
     return ops.fake_quant_headsplit_multi(list(projections), params, heads)
 
 
@@ -384,13 +396,8 @@ def kv_append_fake_quant(sites, heads, pos=None, numels=None):
             return None
     table = []
     for j, (q, x, y, offset, src, rows) in enumerate(sites):
-        mode = q.param_mode
-        if isinstance(q, _LearnableFakeQuantize):
-            mode |= ops.PARAM_SANITIZE
-            q._touch_qparams()
-        sized = x if numels is None or numels[j] is None else _Numel(numels[j])
-        table.append((x, y, offset, (q.scale.data, q.zero_point.data, q.quant_min, q.quant_max, mode,
-                                     q._grad_factor(sized) if q.param_mode != ops.PARAM_FIXED else 1.0), src, rows))
+        numel = x.numel() if numels is None or numels[j] is None else numels[j]
+        table.append((x, y, offset, _site_record(q, numel), src, rows))
     return ops.fake_quant_kv_append(table, heads) if pos is None else ops.fake_quant_kv_append_at(table, heads, pos)
 
 
@@ -398,14 +405,12 @@ def kv_site_params(q, x, numel=None):
     """(scale, zero_point, quant_min, quant_max, mode, grad_factor) of quantizer q for the [B, t, h*d] projection x as a site
     of a KV-append launch, or None when kv_append_fake_quant would not take the site (the quantizer not in its plain
     quantising state, x not dense and 16-byte aligned, the one-launch append switched off).  ``numel``: the element count
-    the grad factor goes by, where it is not x's (kv_append_fake_quant, ``numels``)."""
+    the grad factor goes by, where it is not x's (kv_append_fake_quant, ``numels``).  scale and zero_point are the quantizer's
+    own tensors here, not their ``.data``: a coded cache tells by their identity and version whether a site still has the
+    parameters of its first append (model/quant_bart.py, _code_identity)."""
     if not (FUSE_KV_APPEND and _plain_quantizing(q, x) and x.dim() == 3 and x.is_contiguous() and x.data_ptr() % 16 == 0):
         return None
-    mode = q.param_mode
-    if isinstance(q, _LearnableFakeQuantize):
-        mode |= ops.PARAM_SANITIZE
-    sized = x if numel is None else _Numel(numel)
-    return (q.scale, q.zero_point, q.quant_min, q.quant_max, mode, q._grad_factor(sized) if q.param_mode != ops.PARAM_FIXED else 1.0)
+    return (q.scale, q.zero_point) + _site_record(q, x.numel() if numel is None else numel)[2:]
 
 
 def kv_append_codes_fake_quant(sites, heads, rejected, pos=None):
@@ -416,22 +421,10 @@ def kv_append_codes_fake_quant(sites, heads, rejected, pos=None):
     (nothing launched).  ``pos`` as in kv_append_fake_quant (ops.fake_quant_kv_append_codes_at)."""
     table = []
     for q, params, x, y, offset, src, rows, record, write_record in sites:
-        if params[4] & ops.PARAM_SANITIZE:
-            q._touch_qparams()
         table.append((x, y, offset, params, src, rows, record, write_record))
     if pos is not None:
         return ops.fake_quant_kv_append_codes_at(table, heads, rejected, pos)
     return ops.fake_quant_kv_append_codes(table, heads, rejected)
-
-
-class _Numel:
-    """Stands for a tensor of which a quantizer's grad factor needs the element count only."""
-
-    def __init__(self, n):
-        self.n = n
-
-    def numel(self):
-        return self.n
 
 
 def _decode_site_params(q, *sites):
@@ -445,12 +438,7 @@ def _decode_site_params(q, *sites):
             continue
         if not _plain_quantizing(quantizer, q):
             return None
-        mode = quantizer.param_mode
-        if isinstance(quantizer, _LearnableFakeQuantize):
-            mode |= ops.PARAM_SANITIZE
-            quantizer._touch_qparams()
-        params.append((quantizer.scale.data, quantizer.zero_point.data, quantizer.quant_min, quantizer.quant_max, mode,
-                       quantizer._grad_factor(_Numel(numel)) if quantizer.param_mode != ops.PARAM_FIXED else 1.0))
+        params.append(_site_record(quantizer, numel))
     return params
 
 
@@ -539,6 +527,19 @@ def attention_int_block_fake_quant(q_quantizer, k_quantizer, v_quantizer, probs_
     return ops.attention_int_fake_quant(q, k, v, mask, *params, alpha=alpha, divisor=divisor)
 
 
+def attention_sequence_fake_quant(q_quantizer, k_quantizer, v_quantizer, probs_quantizer, ctx_quantizer, q, k, v, mask=None,
+                                  alpha=None, divisor=None, dropout=None):
+    """The one-launch attention block over a whole sequence as the models call it: on the integer codes of the block's
+    quantizers (attention_int_block_fake_quant, FUSE_ATTENTION_INT), else in fp32 (attention_block_fake_quant,
+    FUSE_ATTENTION).  Returns the context [B, T, h*d], or None when neither launched: the caller runs the eager sequence."""
+    out = attention_int_block_fake_quant(q_quantizer, k_quantizer, v_quantizer, probs_quantizer, ctx_quantizer, q, k, v, mask,
+                                         alpha=alpha, divisor=divisor, dropout=dropout)
+    if out is None:
+        out = attention_block_fake_quant(probs_quantizer, ctx_quantizer, q, k, v, mask, alpha=alpha, divisor=divisor,
+                                         dropout=dropout)
+    return out
+
+
 def decode_attention_shared_fake_quant(probs_quantizer, ctx_quantizer, q, k, v, group, mask=None, dropout=None, codes=None,
                                        force=False):
     """decode_attention_fake_quant for q = [B * group, h, 1, d] whose rows b * group .. b * group + group - 1 share row b of
@@ -621,12 +622,7 @@ def attention_probs_fake_quant(quantizer, scores, mask, alpha=None, divisor=None
         q = quantizer
         quant = None
         if _plain_quantizing(q, scores):
-            mode = q.param_mode
-            if isinstance(q, _LearnableFakeQuantize):
-                mode |= ops.PARAM_SANITIZE
-                q._touch_qparams()
-            quant = (q.scale.data, q.zero_point.data, q.quant_min, q.quant_max, mode,
-                     q._grad_factor(scores) if q.param_mode != ops.PARAM_FIXED else 1.0)
+            quant = _site_record(q, scores.numel())
         probs = ops.attention_softmax_fake_quant(scores4, mask, alpha=alpha, divisor=divisor, quant=quant).view(scores.shape)
         if q is not None and quant is None:
             probs = q(probs, observation_mask, seq_pos)
