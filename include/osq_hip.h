@@ -47,7 +47,8 @@ typedef void* osq_stream;
  *     osq_sample_uniforms, osq_sample_nucleus_workspace_bytes, osq_sample_nucleus, osq_sample_nucleus_at,
  *     osq_decode_attention_shared, osq_decode_attention_shared_codes, osq_sample_advance_group, osq_sample_advance_group_at,
  *     osq_sample_nucleus_group, osq_sample_nucleus_group_at, osq_sample_uniforms_group, osq_token_logprob_workspace_bytes,
- *     osq_token_logprob, osq_token_logprob_backward, osq_attention_fake_quant, osq_attention_fake_quant_int. */
+ *     osq_token_logprob, osq_token_logprob_backward, osq_attention_fake_quant, osq_attention_fake_quant_int,
+ *     osq_attention_fake_quant_shared, osq_attention_fake_quant_int_shared. */
 #define OSQ_ABI_VERSION 10
 
 typedef enum osq_status {
@@ -974,6 +975,31 @@ int osq_attention_fake_quant(const float* q, const float* k, const float* v, con
                              float ctx_grad_factor, int ctx_quant_min, int ctx_quant_max,
                              osq_stream stream);
 
+/* osq_attention_fake_quant for query rows that SHARE their keys and values: `group` = G decoder rows per row of k / v, the
+ * layout of osq_decode_attention_shared (several candidates scored against one input).  `batch` counts the rows of k and v.
+ * q: [batch * G, heads, tokens, head_dim] by its strides; k / v: [batch, heads, kv_len, head_dim] by theirs; mask: indexed by
+ * the SHARED row b (anything broadcastable to [batch, heads, tokens, kv_len]); out: dense [batch * G, tokens, heads *
+ * head_dim]; probs_out: NULL or dense [batch * G, heads, tokens, kv_len].  Decoder rows b * G .. b * G + G - 1 attend over
+ * row b of k, v and mask.  A workgroup serves one (b, head) and a tile of 32 of the G * tokens query rows of that pair, so
+ * every word of k and v is read once per tile of the group, not once per decoder row.
+ * CONTRACT: out and probs_out are word for word those of osq_attention_fake_quant on k, v and mask repeated G times along
+ * the batch (the words of a query row depend on that row of q alone); with group == 1 this IS osq_attention_fake_quant.
+ * Refusals as there, in the same order, with group < 1 "bad shape" (OSQ_ERR_INVALID_ARGUMENT); the INT32_MAX bounds apply
+ * to batch * group, to group * tokens and to batch * heads * ceil(group * tokens / 32).  Legal inside a stream capture. */
+int osq_attention_fake_quant_shared(const float* q, const float* k, const float* v, const float* mask, float* out,
+                                    float* probs_out, int64_t batch, int64_t group, int64_t heads, int64_t tokens,
+                                    int64_t kv_len, int64_t head_dim,
+                                    int64_t q_stride_b, int64_t q_stride_h, int64_t q_stride_t,
+                                    int64_t k_stride_b, int64_t k_stride_h, int64_t k_stride_t,
+                                    int64_t v_stride_b, int64_t v_stride_h, int64_t v_stride_t,
+                                    int64_t mask_stride_b, int64_t mask_stride_h, int64_t mask_stride_t,
+                                    float alpha, float divisor,
+                                    float* probs_scale, void* probs_zero_point, int probs_zp_type, int probs_mode,
+                                    float probs_grad_factor, int probs_quant_min, int probs_quant_max,
+                                    float* ctx_scale, void* ctx_zero_point, int ctx_zp_type, int ctx_mode,
+                                    float ctx_grad_factor, int ctx_quant_min, int ctx_quant_max,
+                                    osq_stream stream);
+
 /* ------------------------------------------------------------------ whole-sequence attention on integer codes (attention_int.hip) */
 
 /* osq_attention_fake_quant on the INTEGERS of the q / k / v / probabilities quantizers, both products on the bf16 matrix
@@ -1027,6 +1053,33 @@ int osq_attention_fake_quant_int(const float* q, const float* k, const float* v,
                                  float* ctx_scale, void* ctx_zero_point, int ctx_zp_type, int ctx_mode,
                                  float ctx_grad_factor, int ctx_quant_min, int ctx_quant_max,
                                  osq_stream stream);
+
+/* osq_attention_fake_quant_int for query rows that share their keys and values: `group`, `batch`, the layouts of q, k, v,
+ * mask, out and probs_out and the row sharing are those of osq_attention_fake_quant_shared; a workgroup serves a tile of 128
+ * of the G * tokens query rows of a (b, head).
+ * CONTRACT: out and probs_out are word for word those of osq_attention_fake_quant_int on k, v and mask repeated G times along
+ * the batch; with group == 1 this IS osq_attention_fake_quant_int.  A bad effective zero point makes ALL of out and
+ * probs_out NaN, as there.  Refusals as there, in the same order, with group < 1 "bad shape"; the INT32_MAX bounds apply to
+ * batch * group, to group * tokens and to batch * heads * ceil(group * tokens / 128).  Legal inside a stream capture. */
+int osq_attention_fake_quant_int_shared(const float* q, const float* k, const float* v, const float* mask, float* out,
+                                        float* probs_out, int64_t batch, int64_t group, int64_t heads, int64_t tokens,
+                                        int64_t kv_len, int64_t head_dim,
+                                        int64_t q_stride_b, int64_t q_stride_h, int64_t q_stride_t,
+                                        int64_t k_stride_b, int64_t k_stride_h, int64_t k_stride_t,
+                                        int64_t v_stride_b, int64_t v_stride_h, int64_t v_stride_t,
+                                        int64_t mask_stride_b, int64_t mask_stride_h, int64_t mask_stride_t,
+                                        float alpha, float divisor,
+                                        float* q_scale, void* q_zero_point, int q_zp_type, int q_mode,
+                                        float q_grad_factor, int q_quant_min, int q_quant_max,
+                                        float* k_scale, void* k_zero_point, int k_zp_type, int k_mode,
+                                        float k_grad_factor, int k_quant_min, int k_quant_max,
+                                        float* v_scale, void* v_zero_point, int v_zp_type, int v_mode,
+                                        float v_grad_factor, int v_quant_min, int v_quant_max,
+                                        float* probs_scale, void* probs_zero_point, int probs_zp_type, int probs_mode,
+                                        float probs_grad_factor, int probs_quant_min, int probs_quant_max,
+                                        float* ctx_scale, void* ctx_zero_point, int ctx_zp_type, int ctx_mode,
+                                        float ctx_grad_factor, int ctx_quant_min, int ctx_quant_max,
+                                        osq_stream stream);
 
 /* ------------------------------------------------------------------ beam search (beam_select.hip) */
 

@@ -203,7 +203,8 @@ def set_share_cross_kv(on=True):
     ops.decode_attention_shared, csrc/decode_attention.hip; default OFF): the cross part of the cache shrinks by the
     factor num_beams, the words computed are those of the one-launch attention on the repeated tensors.
     OSQ_SHARE_CROSS_KV=1 turns it on at load; ``generate(..., share_cross_kv=True)`` asks for one call;
-    ``model.last_share_cross_kv`` tells what happened."""
+    ``model.last_share_cross_kv`` tells what happened.  ``score(..., num_candidates=n)`` follows the switch as well: the
+    candidates of an input share one copy of its cross-attention keys / values in the teacher-forced pass."""
     from . import util_layernorm
     util_layernorm.SHARE_CROSS_KV = bool(on)
 

@@ -180,6 +180,12 @@ SIGNATURES = {
     "osq_attention_fake_quant_int": (_I, [_P, _P, _P, _P, _P, _P, _L, _L, _L, _L, _L, _L, _L, _L, _L, _L, _L, _L, _L, _L, _L, _L, _L,
                                           _F, _F, _P, _P, _I, _I, _F, _I, _I, _P, _P, _I, _I, _F, _I, _I, _P, _P, _I, _I, _F, _I, _I,
                                           _P, _P, _I, _I, _F, _I, _I, _P, _P, _I, _I, _F, _I, _I, _P]),
+    # the two above with `group` after `batch`
+    "osq_attention_fake_quant_shared": (_I, [_P, _P, _P, _P, _P, _P, _L, _L, _L, _L, _L, _L, _L, _L, _L, _L, _L, _L, _L, _L, _L, _L,
+                                             _L, _L, _F, _F, _P, _P, _I, _I, _F, _I, _I, _P, _P, _I, _I, _F, _I, _I, _P]),
+    "osq_attention_fake_quant_int_shared": (_I, [_P, _P, _P, _P, _P, _P, _L, _L, _L, _L, _L, _L, _L, _L, _L, _L, _L, _L, _L, _L, _L,
+                                                 _L, _L, _L, _F, _F, _P, _P, _I, _I, _F, _I, _I, _P, _P, _I, _I, _F, _I, _I,
+                                                 _P, _P, _I, _I, _F, _I, _I, _P, _P, _I, _I, _F, _I, _I, _P, _P, _I, _I, _F, _I, _I, _P]),
     "osq_beam_select_workspace_bytes": (ctypes.c_size_t, [_L, _L, _L, _L]),
     "osq_beam_select": (_I, [_P, _L, _P, _P, _L, _L, _L, _P, _L, _L, _L, _L, _L, _P, _P, _P, ctypes.c_size_t, _P]),
     "osq_beam_advance": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _L, _L, _L, _L, _L, _L, _I, _D, _D, _I,

@@ -40,6 +40,9 @@
 // row T - 1 (their results are dropped); key columns beyond S are neither stored nor reduced; a step beyond S (odd S) or
 // beyond a wave's segment multiplies +0 by +0 -- and a chain that starts at +0 never holds -0, so adding +0 changes no
 // word, signed zeros included.  Addresses are clamped to [0, T) and [0, S): memory beyond them is never read.
+// So a GROUP of G decoder rows that share one row of k, v and mask (osq_attention_fake_quant_shared) is the row map of
+// attention_seq.h and nothing else: a tile's 32 queries are virtual rows of [0, G * T), and out and probs_out are word for word
+// those of the unshared entry point on k, v and mask repeated G times.
 //
 // Inference only; no allocation, no host sync, no workspace: legal inside a stream capture.  The parameter repair under
 // OSQ_PARAM_SANITIZE rides in every workgroup (all compute the same repaired words).
@@ -77,22 +80,20 @@ __global__ __launch_bounds__(kBlkThreads) void attention_block_kernel(BlkArgs a)
     const int64_t bh = blockIdx.x / a.tiles;
     const int t0 = static_cast<int>(blockIdx.x % a.tiles) * kBlkTQ;
     const int64_t b = bh / a.heads, h = bh % a.heads;
-    const int T = a.tokens, S = a.kv_len;
-    const int nrows = min(kBlkTQ, T - t0);            // 1..32 query rows of this tile
+    const int R = a.rows, S = a.kv_len;               // virtual query rows of this (b, head): the row map of attention_seq.h
+    const int nrows = min(kBlkTQ, R - t0);            // 1..32 query rows of this tile
     const QParams pq = dec_params(a.probs), cq = dec_params(a.ctx);      // first: the parameter repair rides here
 
     // ---- scores
     {
         float qf[HALF];
-        const float4* qrow = reinterpret_cast<const float4*>(a.q + b * a.q_sb + h * a.q_sh +
-                                                            static_cast<int64_t>(min(t0 + l31, T - 1)) * a.q_st + half * HALF);
+        const float4* qrow = reinterpret_cast<const float4*>(seq_q_row(a, b, h, min(t0 + l31, R - 1)) + half * HALF);
 #pragma unroll
         for (int c = 0; c < HALF / 4; ++c) {
             const float4 x = qrow[c];
             qf[4 * c] = x.x; qf[4 * c + 1] = x.y; qf[4 * c + 2] = x.z; qf[4 * c + 3] = x.w;
         }
         const float* kbase = a.k + b * a.k_sb + h * a.k_sh + half * HALF;
-        const float* mbase = a.mask ? a.mask + b * a.m_sb + h * a.m_sh : nullptr;
         const int ktiles = (S + kBlkTK - 1) / kBlkTK;
         // half a row of K of key tile jt; the next tile's loads are issued before this tile's products
         const auto load_k = [&](int jt, float* kf) {
@@ -119,7 +120,7 @@ __global__ __launch_bounds__(kBlkThreads) void attention_block_kernel(BlkArgs a)
                 for (int r = 0; r < 16; ++r) {
                     const int row = mfma32_row(r, half);
                     float x = pre_softmax(a.pre, acc[r], a.alpha, a.divisor);
-                    if (mbase) x = x + mbase[static_cast<int64_t>(min(t0 + row, T - 1)) * a.m_st + col];
+                    if (a.mask) x = x + seq_mask_row(a, b, h, min(t0 + row, R - 1))[col];
                     s_p[row * SP + col] = x;
                 }
             }
@@ -144,7 +145,7 @@ __global__ __launch_bounds__(kBlkThreads) void attention_block_kernel(BlkArgs a)
             sum += e;
         }
         const float rcp = 1.0f / wave_sum_f32(sum);
-        float* prow = a.probs_out ? a.probs_out + ((bh * T + t0 + row) * static_cast<int64_t>(S)) : nullptr;
+        float* prow = a.probs_out ? seq_probs_row(a, b, h, t0 + row) : nullptr;
         for (int j = lane; j < S; j += OSQ_WAVE) {
             const float p = dec_fq(sp[j] * rcp, a.probs, pq);
             sp[j] = p;
@@ -196,7 +197,7 @@ __global__ __launch_bounds__(kBlkThreads) void attention_block_kernel(BlkArgs a)
         float o = s_part[chunk][row][cc];
 #pragma unroll
         for (int g = 1; g < NSEG; ++g) o = o + s_part[g * NCH + chunk][row][cc];
-        a.out[((b * T + t0 + row) * a.heads + h) * D + col] = dec_fq(o, a.ctx, cq);
+        seq_out_row<D>(a, b, h, t0 + row)[col] = dec_fq(o, a.ctx, cq);
     }
 }
 
@@ -212,6 +213,38 @@ static void launch_block(const BlkArgs& a, dim3 grid, hipStream_t st) {
 
 using namespace osq;
 
+// batch counts the rows of k / v; q, out and probs_out have batch * group
+extern "C" int osq_attention_fake_quant_shared(const float* q, const float* k, const float* v, const float* mask, float* out,
+                                        float* probs_out, int64_t batch, int64_t group, int64_t heads, int64_t tokens,
+                                        int64_t kv_len, int64_t head_dim,
+                                        int64_t q_stride_b, int64_t q_stride_h, int64_t q_stride_t,
+                                        int64_t k_stride_b, int64_t k_stride_h, int64_t k_stride_t,
+                                        int64_t v_stride_b, int64_t v_stride_h, int64_t v_stride_t,
+                                        int64_t mask_stride_b, int64_t mask_stride_h, int64_t mask_stride_t,
+                                        float alpha, float divisor,
+                                        float* probs_scale, void* probs_zero_point, int probs_zp_type, int probs_mode,
+                                        float probs_grad_factor, int probs_quant_min, int probs_quant_max,
+                                        float* ctx_scale, void* ctx_zero_point, int ctx_zp_type, int ctx_mode,
+                                        float ctx_grad_factor, int ctx_quant_min, int ctx_quant_max,
+                                        osq_stream stream) {
+    const char* what = "attention_fake_quant";
+    BlkArgs a{{q, k, v, mask, out, probs_out, q_stride_b, q_stride_h, q_stride_t, k_stride_b, k_stride_h, k_stride_t,
+               v_stride_b, v_stride_h, v_stride_t, mask_stride_b, mask_stride_h, mask_stride_t, heads, 0, 0, 0, 0, 0, 0, alpha,
+               divisor},
+              OSQ_DEC_QUANT(probs), OSQ_DEC_QUANT(ctx)};
+    if (const int rc = seq_check_shape(what, a, batch, group, tokens, head_dim)) return rc;
+    OSQ_SEQ_REQUIRE(!probs_scale || probs_zero_point, "probs scale without zero_point");
+    OSQ_SEQ_REQUIRE(!ctx_scale || ctx_zero_point, "ctx scale without zero_point");
+    OSQ_SEQ_REQUIRE(!probs_scale || dec_mode_ok(probs_mode), "bad probs mode");
+    OSQ_SEQ_REQUIRE(!ctx_scale || dec_mode_ok(ctx_mode), "bad ctx mode");
+    int64_t blocks;
+    if (const int rc = seq_check_launch(what, a, batch, tokens, kv_len, head_dim, kBlkTQ, kBlkMaxS, &blocks); rc || !blocks) return rc;
+    const dim3 grid(static_cast<unsigned>(blocks));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    OSQ_HEAD_DIM_DISPATCH(head_dim, launch_block<D>(a, grid, st));
+    return check_launch(what);
+}
+
 extern "C" int osq_attention_fake_quant(const float* q, const float* k, const float* v, const float* mask, float* out,
                                         float* probs_out, int64_t batch, int64_t heads, int64_t tokens, int64_t kv_len,
                                         int64_t head_dim,
@@ -225,19 +258,10 @@ extern "C" int osq_attention_fake_quant(const float* q, const float* k, const fl
                                         float* ctx_scale, void* ctx_zero_point, int ctx_zp_type, int ctx_mode,
                                         float ctx_grad_factor, int ctx_quant_min, int ctx_quant_max,
                                         osq_stream stream) {
-    const char* what = "attention_fake_quant";
-    BlkArgs a{{q, k, v, mask, out, probs_out, q_stride_b, q_stride_h, q_stride_t, k_stride_b, k_stride_h, k_stride_t,
-               v_stride_b, v_stride_h, v_stride_t, mask_stride_b, mask_stride_h, mask_stride_t, heads, 0, 0, 0, 0, alpha, divisor},
-              OSQ_DEC_QUANT(probs), OSQ_DEC_QUANT(ctx)};
-    if (const int rc = seq_check_shape(what, a, batch, tokens, head_dim)) return rc;
-    OSQ_SEQ_REQUIRE(!probs_scale || probs_zero_point, "probs scale without zero_point");
-    OSQ_SEQ_REQUIRE(!ctx_scale || ctx_zero_point, "ctx scale without zero_point");
-    OSQ_SEQ_REQUIRE(!probs_scale || dec_mode_ok(probs_mode), "bad probs mode");
-    OSQ_SEQ_REQUIRE(!ctx_scale || dec_mode_ok(ctx_mode), "bad ctx mode");
-    int64_t blocks;
-    if (const int rc = seq_check_launch(what, a, batch, tokens, kv_len, head_dim, kBlkTQ, kBlkMaxS, &blocks); rc || !blocks) return rc;
-    const dim3 grid(static_cast<unsigned>(blocks));
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    OSQ_HEAD_DIM_DISPATCH(head_dim, launch_block<D>(a, grid, st));
-    return check_launch(what);
+    return osq_attention_fake_quant_shared(q, k, v, mask, out, probs_out, batch, 1, heads, tokens, kv_len, head_dim,
+                                           q_stride_b, q_stride_h, q_stride_t, k_stride_b, k_stride_h, k_stride_t,
+                                           v_stride_b, v_stride_h, v_stride_t, mask_stride_b, mask_stride_h, mask_stride_t,
+                                           alpha, divisor, probs_scale, probs_zero_point, probs_zp_type, probs_mode,
+                                           probs_grad_factor, probs_quant_min, probs_quant_max, ctx_scale, ctx_zero_point,
+                                           ctx_zp_type, ctx_mode, ctx_grad_factor, ctx_quant_min, ctx_quant_max, stream);
 }

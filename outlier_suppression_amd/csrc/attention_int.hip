@@ -44,6 +44,9 @@
 // The words of a query row depend on that row of q alone (a column of an MFMA result depends on that column of B alone):
 // not on T, on where the row sits in its tile, on B or h, or on strides.  Rows beyond T repeat row T - 1 (dropped); keys
 // beyond S carry code 0 in P and V and are neither reduced nor stored.  Addresses are clamped to [0, T) and [0, S).
+// So a GROUP of G decoder rows that share one row of k, v and mask (osq_attention_fake_quant_int_shared) is the row map of
+// attention_seq.h and nothing else: a workgroup's 128 queries are virtual rows of [0, G * T), and out and probs_out are word for
+// word those of the unshared entry point on k, v and mask repeated G times.
 // Inference only; no allocation, no host sync, no workspace, no atomics: legal inside a stream capture.
 #include <math.h>
 #include <hip/hip_runtime.h>
@@ -97,30 +100,31 @@ __global__ __launch_bounds__(kIntThreads) void attention_int_kernel(IntArgs a) {
     const int64_t bh = blockIdx.x / a.tiles;
     const int t0 = static_cast<int>(blockIdx.x % a.tiles) * kIntTQ;
     const int64_t b = bh / a.heads, h = bh % a.heads;
-    const int T = a.tokens, S = a.kv_len;
-    const int nrows = min(kIntTQ, T - t0);            // 1..128 query rows of this workgroup
+    const int R = a.rows, S = a.kv_len;               // virtual query rows of this (b, head): the row map of attention_seq.h
+    const int nrows = min(kIntTQ, R - t0);            // 1..128 query rows of this workgroup
     const QParams qp = dec_params(a.qq), kp = dec_params(a.kq), vp = dec_params(a.vq);   // first: the parameter repair rides here
     const QParams pq = dec_params(a.probs), cq = dec_params(a.ctx);
 
     if (!(int_zp_ok(a.qq, qp) && int_zp_ok(a.kq, kp) && int_zp_ok(a.vq, vp) && int_zp_ok(a.probs, pq))) {   // uniform
         const float nan = __builtin_nanf("");
-        for (int i = threadIdx.x; i < nrows * D; i += kIntThreads)
-            a.out[((b * T + t0 + i / D) * a.heads + h) * D + i % D] = nan;
+        for (int i = threadIdx.x; i < nrows * D; i += kIntThreads) seq_out_row<D>(a, b, h, t0 + i / D)[i % D] = nan;
         if (a.probs_out) {
-            float* p = a.probs_out + (bh * T + t0) * static_cast<int64_t>(S);
-            for (int64_t i = threadIdx.x; i < static_cast<int64_t>(nrows) * S; i += kIntThreads) p[i] = nan;
+            for (int row = 0; row < nrows; ++row) {
+                float* p = seq_probs_row(a, b, h, t0 + row);
+                for (int i = threadIdx.x; i < S; i += kIntThreads) p[i] = nan;
+            }
         }
         return;
     }
 
-    const bool active = t0 + 32 * w < T;              // a wave whose 32 queries all lie beyond T only helps with the tiles
-    const int tq = min(t0 + 32 * w + l31, T - 1);     // this lane's query
+    const bool active = t0 + 32 * w < R;              // a wave whose 32 queries all lie beyond R only helps with the tiles
+    const int tq = min(t0 + 32 * w + l31, R - 1);     // this lane's query: a virtual row
     const float sqk = qp.scale * kp.scale, spv = pq.scale * vp.scale;
 
     // ---- this lane's share of Q as the B operand: k-step s holds q[tq][16 s + 8 half + 0..7]
     bf16x8 qf[KSTEPS];
     {
-        const float4* qrow = reinterpret_cast<const float4*>(a.q + b * a.q_sb + h * a.q_sh + static_cast<int64_t>(tq) * a.q_st);
+        const float4* qrow = reinterpret_cast<const float4*>(seq_q_row(a, b, h, tq));
 #pragma unroll
         for (int s = 0; s < KSTEPS; ++s) {
             const float4 x = qrow[4 * s + 2 * half], y = qrow[4 * s + 2 * half + 1];
@@ -138,7 +142,7 @@ __global__ __launch_bounds__(kIntThreads) void attention_int_kernel(IntArgs a) {
 
     const float* kbase = a.k + b * a.k_sb + h * a.k_sh;
     const float* vbase = a.v + b * a.v_sb + h * a.v_sh;
-    const float* mbase = a.mask ? a.mask + b * a.m_sb + h * a.m_sh + static_cast<int64_t>(tq) * a.m_st : nullptr;
+    const float* mbase = a.mask ? seq_mask_row(a, b, h, tq) : nullptr;
     const int ktiles = (S + kIntTK - 1) / kIntTK;
 
     // a thread's float4s of tile jt of K or V: float4 number threadIdx.x + 256 u is row idx / F4ROW, elements 4 (idx % F4ROW)..
@@ -258,8 +262,8 @@ __global__ __launch_bounds__(kIntThreads) void attention_int_kernel(IntArgs a) {
                 cacc[c][r] = 0.f;
             }
     };
-    float* prow = a.probs_out ? a.probs_out + (bh * T + tq) * static_cast<int64_t>(S) : nullptr;
-    const bool row_ok = t0 + 32 * w + l31 < T;
+    float* prow = a.probs_out ? seq_probs_row(a, b, h, tq) : nullptr;
+    const bool row_ok = t0 + 32 * w + l31 < R;
     for_tiles(true, [&](int jt) {
         float x[16];
         score_tile(jt, x);
@@ -291,7 +295,7 @@ __global__ __launch_bounds__(kIntThreads) void attention_int_kernel(IntArgs a) {
     flush();
 
     if (row_ok) {
-        float* orow = a.out + ((b * T + tq) * a.heads + h) * D;
+        float* orow = seq_out_row<D>(a, b, h, tq);
 #pragma unroll
         for (int c = 0; c < NCH; ++c)
 #pragma unroll
@@ -320,6 +324,48 @@ static bool int_site_ok(const float* scale, const void* zero_point, int mode, in
 
 using namespace osq;
 
+// batch counts the rows of k / v; q, out and probs_out have batch * group
+extern "C" int osq_attention_fake_quant_int_shared(const float* q, const float* k, const float* v, const float* mask, float* out,
+                                            float* probs_out, int64_t batch, int64_t group, int64_t heads, int64_t tokens,
+                                            int64_t kv_len, int64_t head_dim,
+                                            int64_t q_stride_b, int64_t q_stride_h, int64_t q_stride_t,
+                                            int64_t k_stride_b, int64_t k_stride_h, int64_t k_stride_t,
+                                            int64_t v_stride_b, int64_t v_stride_h, int64_t v_stride_t,
+                                            int64_t mask_stride_b, int64_t mask_stride_h, int64_t mask_stride_t,
+                                            float alpha, float divisor,
+                                            float* q_scale, void* q_zero_point, int q_zp_type, int q_mode,
+                                            float q_grad_factor, int q_quant_min, int q_quant_max,
+                                            float* k_scale, void* k_zero_point, int k_zp_type, int k_mode,
+                                            float k_grad_factor, int k_quant_min, int k_quant_max,
+                                            float* v_scale, void* v_zero_point, int v_zp_type, int v_mode,
+                                            float v_grad_factor, int v_quant_min, int v_quant_max,
+                                            float* probs_scale, void* probs_zero_point, int probs_zp_type, int probs_mode,
+                                            float probs_grad_factor, int probs_quant_min, int probs_quant_max,
+                                            float* ctx_scale, void* ctx_zero_point, int ctx_zp_type, int ctx_mode,
+                                            float ctx_grad_factor, int ctx_quant_min, int ctx_quant_max,
+                                            osq_stream stream) {
+    const char* what = "attention_fake_quant_int";
+    IntArgs a{{q, k, v, mask, out, probs_out, q_stride_b, q_stride_h, q_stride_t, k_stride_b, k_stride_h, k_stride_t,
+               v_stride_b, v_stride_h, v_stride_t, mask_stride_b, mask_stride_h, mask_stride_t, heads, 0, 0, 0, 0, 0, 0, alpha,
+               divisor},
+              OSQ_DEC_QUANT(q), OSQ_DEC_QUANT(k), OSQ_DEC_QUANT(v), OSQ_DEC_QUANT(probs), OSQ_DEC_QUANT(ctx)};
+    if (const int rc = seq_check_shape(what, a, batch, group, tokens, head_dim)) return rc;
+    OSQ_SEQ_REQUIRE(!ctx_scale || ctx_zero_point, "ctx scale without zero_point");
+    OSQ_SEQ_REQUIRE(!ctx_scale || dec_mode_ok(ctx_mode), "bad ctx mode");
+    // the four quantizers of the products: all there, per-tensor records, at most 256 codes
+    if (!int_site_ok(q_scale, q_zero_point, q_mode, q_quant_min, q_quant_max) ||
+        !int_site_ok(k_scale, k_zero_point, k_mode, k_quant_min, k_quant_max) ||
+        !int_site_ok(v_scale, v_zero_point, v_mode, v_quant_min, v_quant_max) ||
+        !int_site_ok(probs_scale, probs_zero_point, probs_mode, probs_quant_min, probs_quant_max))
+        return OSQ_ERR_UNSUPPORTED;
+    int64_t blocks;
+    if (const int rc = seq_check_launch(what, a, batch, tokens, kv_len, head_dim, kIntTQ, kIntMaxS, &blocks); rc || !blocks) return rc;
+    const dim3 grid(static_cast<unsigned>(blocks));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    OSQ_HEAD_DIM_DISPATCH(head_dim, hipLaunchKernelGGL((attention_int_kernel<D>), grid, dim3(kIntThreads), 0, st, a));
+    return check_launch(what);
+}
+
 extern "C" int osq_attention_fake_quant_int(const float* q, const float* k, const float* v, const float* mask, float* out,
                                             float* probs_out, int64_t batch, int64_t heads, int64_t tokens, int64_t kv_len,
                                             int64_t head_dim,
@@ -339,23 +385,13 @@ extern "C" int osq_attention_fake_quant_int(const float* q, const float* k, cons
                                             float* ctx_scale, void* ctx_zero_point, int ctx_zp_type, int ctx_mode,
                                             float ctx_grad_factor, int ctx_quant_min, int ctx_quant_max,
                                             osq_stream stream) {
-    const char* what = "attention_fake_quant_int";
-    IntArgs a{{q, k, v, mask, out, probs_out, q_stride_b, q_stride_h, q_stride_t, k_stride_b, k_stride_h, k_stride_t,
-               v_stride_b, v_stride_h, v_stride_t, mask_stride_b, mask_stride_h, mask_stride_t, heads, 0, 0, 0, 0, alpha, divisor},
-              OSQ_DEC_QUANT(q), OSQ_DEC_QUANT(k), OSQ_DEC_QUANT(v), OSQ_DEC_QUANT(probs), OSQ_DEC_QUANT(ctx)};
-    if (const int rc = seq_check_shape(what, a, batch, tokens, head_dim)) return rc;
-    OSQ_SEQ_REQUIRE(!ctx_scale || ctx_zero_point, "ctx scale without zero_point");
-    OSQ_SEQ_REQUIRE(!ctx_scale || dec_mode_ok(ctx_mode), "bad ctx mode");
-    // the four quantizers of the products: all there, per-tensor records, at most 256 codes
-    if (!int_site_ok(q_scale, q_zero_point, q_mode, q_quant_min, q_quant_max) ||
-        !int_site_ok(k_scale, k_zero_point, k_mode, k_quant_min, k_quant_max) ||
-        !int_site_ok(v_scale, v_zero_point, v_mode, v_quant_min, v_quant_max) ||
-        !int_site_ok(probs_scale, probs_zero_point, probs_mode, probs_quant_min, probs_quant_max))
-        return OSQ_ERR_UNSUPPORTED;
-    int64_t blocks;
-    if (const int rc = seq_check_launch(what, a, batch, tokens, kv_len, head_dim, kIntTQ, kIntMaxS, &blocks); rc || !blocks) return rc;
-    const dim3 grid(static_cast<unsigned>(blocks));
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    OSQ_HEAD_DIM_DISPATCH(head_dim, hipLaunchKernelGGL((attention_int_kernel<D>), grid, dim3(kIntThreads), 0, st, a));
-    return check_launch(what);
+    return osq_attention_fake_quant_int_shared(q, k, v, mask, out, probs_out, batch, 1, heads, tokens, kv_len, head_dim, q_stride_b,
+                                q_stride_h, q_stride_t, k_stride_b, k_stride_h, k_stride_t, v_stride_b, v_stride_h,
+                                v_stride_t, mask_stride_b, mask_stride_h, mask_stride_t, alpha, divisor, q_scale,
+                                q_zero_point, q_zp_type, q_mode, q_grad_factor, q_quant_min, q_quant_max, k_scale,
+                                k_zero_point, k_zp_type, k_mode, k_grad_factor, k_quant_min, k_quant_max, v_scale,
+                                v_zero_point, v_zp_type, v_mode, v_grad_factor, v_quant_min, v_quant_max, probs_scale,
+                                probs_zero_point, probs_zp_type, probs_mode, probs_grad_factor, probs_quant_min,
+                                probs_quant_max, ctx_scale, ctx_zero_point, ctx_zp_type, ctx_mode, ctx_grad_factor,
+                                ctx_quant_min, ctx_quant_max, stream);
 }

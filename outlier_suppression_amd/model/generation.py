@@ -189,7 +189,8 @@ def _select_continuations(logits, flat, running_scores, procs, bsz, nb, vocab, k
 
 class ShareCrossKvInfo(Outcome):
     """What a generate() call did with ``share_cross_kv``: ``shared`` beam steps over one copy of the cross-attention keys /
-    values per batch row, ``eager`` beam steps over one copy per beam, and, when none was shared, the ``reason``."""
+    values per batch row, ``eager`` beam steps over one copy per beam, and, when none was shared, the ``reason``.  Of a
+    score() call the two count decoder LAYERS: those whose cross-attention ran on one copy per input, and on expanded rows."""
     COUNTERS = ("shared", "eager")
 
 
@@ -210,7 +211,7 @@ def _share_why_not(model, device, use_cache, nb, source_len):
     if reason is not None:
         return reason
     decoder = model.model.decoder
-    if decoder.training and any(p > 0 for layer in decoder.layers for p in (layer.dropout, layer.encoder_attn.dropout)):
+    if _dropout_active(decoder):
         return "dropout is active"
     if source_len > SHARE_MAX_SOURCE:
         return f"the source is longer than {SHARE_MAX_SOURCE}"
@@ -219,9 +220,41 @@ def _share_why_not(model, device, use_cache, nb, source_len):
         lpr = attn.head_dim // 4
         if attn.head_dim % 4 or lpr > 64 or lpr & (lpr - 1) or attn.embed_dim != attn.num_heads * attn.head_dim:
             return f"the shared cross-attention does not take head_dim {attn.head_dim}"
-        for site in ("query", "key", "value", "attention_probs", "context"):
-            if not graph_decode._plain(getattr(attn, site + "_post_act_fake_quantize")):
-                return f"a cross-attention quantizer is not in the plain quantising state (decoder layer {i}, {site})"
+        reason = _cross_site_why_not(i, attn)
+        if reason is not None:
+            return reason
+    return None
+
+
+def _dropout_active(decoder):
+    return decoder.training and any(p > 0 for layer in decoder.layers for p in (layer.dropout, layer.encoder_attn.dropout))
+
+
+def _cross_site_why_not(i, attn):
+    """The cross-attention quantizer of decoder layer ``i`` that is not in its plain quantising state, as a reason, or None."""
+    for site in ("query", "key", "value", "attention_probs", "context"):
+        if not graph_decode._plain(getattr(attn, site + "_post_act_fake_quantize")):
+            return f"a cross-attention quantizer is not in the plain quantising state (decoder layer {i}, {site})"
+    return None
+
+
+def score_share_why_not(model, device, n):
+    """None when a score() call of ``n`` candidates per input can run every decoder layer's cross-attention on one copy of
+    the keys / values per input, else the reason it expands the encoder states as without ``share_cross_kv``.  Everything
+    here is known before the decoder runs; lengths and head sizes are no reason: a layer whose launch does not take them
+    runs on expanded rows, with the same words."""
+    if n == 1:
+        return "one candidate per input (num_candidates == 1): there is nothing to share"
+    reason = _device_why_not(device)
+    if reason is not None:
+        return reason
+    decoder = model.model.decoder
+    if _dropout_active(decoder):
+        return "dropout is active"
+    for i, layer in enumerate(decoder.layers):
+        reason = _cross_site_why_not(i, layer.encoder_attn)
+        if reason is not None:
+            return reason
     return None
 
 

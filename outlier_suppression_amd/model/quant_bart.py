@@ -643,11 +643,18 @@ class QuantizedBartAttention(QuantizedModule):
         return (q[0],) + cache.cross_operands(i)
 
     def forward(self, hidden_states, key_value_states=None, attention_mask=None, observation_mask=None,
-                past_key_value=None):
+                past_key_value=None, cross_group=1):
         """``past_key_value``: None (no cache; returns the output alone, as before) or a layer slot of a
-        QuantizedBartCache (QuantizedBartCache.slot(i)), which this call extends: returns (output, past_key_value)."""
+        QuantizedBartCache (QuantizedBartCache.slot(i)), which this call extends: returns (output, past_key_value).
+        ``cross_group`` = G > 1 (cross-attention without a cache; score()): ``key_value_states`` and ``attention_mask`` have
+        one row per G rows of ``hidden_states`` (_cross_shared); ``self.last_cross_shared`` then says whether the keys and
+        values were held once."""
         bsz, tgt_len, _ = hidden_states.shape
         heads = self.num_heads
+        if cross_group > 1:
+            if past_key_value is not None or key_value_states is None:
+                raise ValueError("cross_group is for cross-attention without a cache (a cache has a cross_group of its own)")
+            return self._cross_shared(hidden_states, key_value_states, attention_mask, observation_mask, cross_group)
         if past_key_value is not None:
             if key_value_states is None and past_key_value.cache.positioned():
                 return self._step_at(past_key_value, hidden_states, attention_mask, observation_mask), past_key_value
@@ -672,6 +679,32 @@ class QuantizedBartAttention(QuantizedModule):
             k = split_heads_fake_quant(self.key_post_act_fake_quantize, xk, heads, observation_mask)
             v = split_heads_fake_quant(self.value_post_act_fake_quantize, xv, heads, observation_mask)
         return self._attend(q, k, v, bsz, tgt_len, attention_mask, observation_mask)
+
+    def _cross_shared(self, hidden_states, key_value_states, attention_mask, observation_mask, group):
+        """Teacher-forced cross-attention of [B * G, T, H] decoder states over [B, S, H] encoder states and a [B, 1, T, S] mask
+        that the G rows of an input share.  Keys / values are projected on the B rows and their two sites run as one launch
+        into [B, h, S, d] tensors, with the LSQ / LSQ+ grad factor of the [B * G, S, h*d] tensor they stand for, as
+        _shared_cross_qkv does for a cache: the words are those the expanded form computes.  Where that launch does not take
+        the layer, the layer runs on expanded rows as without a group."""
+        bsz, tgt_len, _ = hidden_states.shape
+        heads, d = self.num_heads, self.head_dim
+        b = key_value_states.shape[0]
+        if b * group != bsz:
+            raise ValueError(f"cross_group={group} takes encoder states of {bsz // group} rows for {bsz} decoder rows, got {b}")
+        xk, xv = self.k_proj(key_value_states), self.v_proj(key_value_states)
+        s = xk.shape[1]
+        numel = xk.numel() * group
+        kv = kv_append_fake_quant([(self.key_post_act_fake_quantize, xk, xk.new_empty((b, heads, s, d)), 0, None, None),
+                                   (self.value_post_act_fake_quantize, xv, xv.new_empty((b, heads, s, d)), 0, None, None)],
+                                  heads, numels=(numel, numel))
+        self.last_cross_shared = kv is not None
+        if kv is None:
+            if attention_mask is not None:
+                attention_mask = attention_mask.repeat_interleave(group, dim=0)
+            return self.forward(hidden_states, key_value_states.repeat_interleave(group, dim=0), attention_mask, observation_mask)
+        q = split_heads_fake_quant(self.query_post_act_fake_quantize, self.q_proj(hidden_states) * self.scaling, heads,
+                                   observation_mask)
+        return self._attend(q, kv[0], kv[1], bsz, tgt_len, attention_mask, observation_mask, group=group)
 
     def _step_at(self, slot, hidden_states, attention_mask, observation_mask):
         """Self-attention of a single-token step over a cache in device-position mode: the append and the attention read the
@@ -717,7 +750,8 @@ class QuantizedBartAttention(QuantizedModule):
     def _attend_shared(self, q, k, v, bsz, tgt_len, attention_mask, observation_mask, group, force):
         """_attend for [B * G, h, T, d] q over [B, h, S, d] k / v and a [B, 1, T, S] mask that the G rows of an encoder row
         share: a single-token step as ONE launch that reads K and V once for (up to 8 of) the rows that share them.  A call
-        that launch does not take -- several tokens, a refusal -- expands k, v and the mask and takes _attend."""
+        that launch does not take -- several tokens (a prefill), a refusal -- goes to _attend with the group: the grouped
+        whole-sequence launch where it takes the call, else k, v and the mask expanded."""
         if tgt_len == 1:
             both = isinstance(k, _CodedTensor) and isinstance(v, _CodedTensor)
             kk, vv = ((k.codes, v.codes) if both else (x.float() if isinstance(x, _CodedTensor) else x for x in (k, v)))
@@ -727,17 +761,28 @@ class QuantizedBartAttention(QuantizedModule):
                                                      codes=(k.record, v.record, k.rejected) if both else None, force=force)
             if out is not None:
                 return self._project(out, observation_mask)
-        k, v = (x.float() if isinstance(x, _CodedTensor) else x for x in (k, v))
-        k, v = k.repeat_interleave(group, dim=0), v.repeat_interleave(group, dim=0)
-        if attention_mask is not None:
-            attention_mask = attention_mask.repeat_interleave(group, dim=0)
-        return self._attend(q, k, v, bsz, tgt_len, attention_mask, observation_mask, cached=True)
+        return self._attend(q, k, v, bsz, tgt_len, attention_mask, observation_mask, cached=True, group=group)
 
-    def _attend(self, q, k, v, bsz, tgt_len, attention_mask, observation_mask, cached=False):
+    def _attend(self, q, k, v, bsz, tgt_len, attention_mask, observation_mask, cached=False, group=1):
         """[B, h, T, d] q and [B, h, S, d] k / v (dense, or views of a cache buffer) -> the block's output.  ``cached``: a
         call of the cached path, whose single-token steps have a one-launch form (util_layernorm.FUSE_DECODE_ATTENTION).
         k / v held as integer codes (_CodedTensor) go to that form as they are when both are; everything else -- one of the
-        two in fp32, the switch off, several tokens, dropout, a length the kernel does not take -- sees them dequantised."""
+        two in fp32, the switch off, several tokens, dropout, a length the kernel does not take -- sees them dequantised.
+        ``group`` = G > 1: q has G rows per row of k, v and the mask.  Several tokens go to the one-launch forms with the
+        group (the words of the call on expanded k, v and mask, by the kernels' contract); what they do not take, and every
+        other form, runs on k, v and the mask expanded here."""
+        if group > 1:
+            k, v = (x.float() if isinstance(x, _CodedTensor) else x for x in (k, v))
+            if tgt_len > 1:
+                out = attention_sequence_fake_quant(self.query_post_act_fake_quantize, self.key_post_act_fake_quantize,
+                                                    self.value_post_act_fake_quantize, self.attention_probs_post_act_fake_quantize,
+                                                    self.context_post_act_fake_quantize, q, k, v, attention_mask,
+                                                    dropout=(self.dropout, self.training), group=group)
+                if out is not None:
+                    return self._project(out, observation_mask)
+            k, v = k.repeat_interleave(group, dim=0), v.repeat_interleave(group, dim=0)
+            if attention_mask is not None:
+                attention_mask = attention_mask.repeat_interleave(group, dim=0)
         codes = None
         if isinstance(k, _CodedTensor) and isinstance(v, _CodedTensor) and cached and tgt_len == 1:
             codes = (k.record, v.record, k.rejected)
@@ -845,8 +890,9 @@ class QuantizedBartDecoderLayer(QuantizedModule):
         return nn.functional.dropout(x, p=p, training=self.training)
 
     def forward(self, hidden_states, attention_mask=None, encoder_hidden_states=None, encoder_attention_mask=None,
-                observation_mask=None, past_key_value=None):
-        """``past_key_value``: None, or this layer's slot of a QuantizedBartCache (extended in place)."""
+                observation_mask=None, past_key_value=None, cross_group=1):
+        """``past_key_value``: None, or this layer's slot of a QuantizedBartCache (extended in place).  ``cross_group``: the
+        rows of ``hidden_states`` per row of the encoder's states and mask (QuantizedBartAttention.forward; no cache)."""
         def attn(module, x, **kw):
             if past_key_value is None:
                 return module(x, observation_mask=observation_mask, **kw)
@@ -857,7 +903,8 @@ class QuantizedBartDecoderLayer(QuantizedModule):
         if encoder_hidden_states is not None:
             residual = h
             h = self._drop(attn(self.encoder_attn, h, key_value_states=encoder_hidden_states,
-                                attention_mask=encoder_attention_mask), self.dropout)
+                                attention_mask=encoder_attention_mask,
+                                **(dict(cross_group=cross_group) if cross_group > 1 else {})), self.dropout)
             h = residual_layernorm(self.before_encoder_attn_layer_norm_residual, self.encoder_attn_layer_norm, residual, h, observation_mask)
         residual = h
         if self.training and self.activation_dropout > 0:
@@ -913,14 +960,18 @@ class QuantizedBartDecoder(_BartStack):
     layer_cls = QuantizedBartDecoderLayer
 
     def forward(self, input_ids, attention_mask=None, encoder_hidden_states=None, encoder_attention_mask=None,
-                observation_mask=None, past_key_values=None, use_cache=False):
+                observation_mask=None, past_key_values=None, use_cache=False, cross_group=1):
         """Without ``use_cache`` / ``past_key_values``: the hidden states.  With either: (hidden states, cache), the cache a
         QuantizedBartCache (``past_key_values`` may also be the reference's tuple of per-layer tensors; positions and the
         causal mask start after its length, quant_bart.py:774-787) extended by this step.  ``attention_mask`` then covers
-        past + new positions."""
+        past + new positions.  ``cross_group`` = G > 1, without a cache: ``input_ids`` has G rows per row of
+        ``encoder_hidden_states`` and ``encoder_attention_mask``, rows b * G .. b * G + G - 1 for encoder row b (a cache
+        says the same with its own ``cross_group``)."""
         bsz, tgt_len = input_ids.shape
         cache = None
         if use_cache or past_key_values is not None:
+            if cross_group != 1:
+                raise ValueError("cross_group is for a decoder without a cache; give the cache its cross_group")
             cache = QuantizedBartCache.wrap(past_key_values, len(self.layers))
         past = cache.get_seq_length() if cache is not None else 0
         h = self._embed(input_ids, observation_mask, cache.position() if cache is not None else 0)
@@ -934,7 +985,8 @@ class QuantizedBartDecoder(_BartStack):
         for i, layer in enumerate(self.layers):
             h = layer(h, attention_mask=mask, encoder_hidden_states=encoder_hidden_states,
                       encoder_attention_mask=enc_mask, observation_mask=observation_mask,
-                      past_key_value=cache.slot(i) if cache is not None else None)
+                      past_key_value=cache.slot(i) if cache is not None else None,
+                      **(dict(cross_group=cross_group) if cross_group > 1 else {}))
         if cache is not None:
             cache.advance(tgt_len)
         return h if cache is None else (h, cache)
@@ -957,10 +1009,10 @@ class QuantizedBartModel(QuantizedModule):
 
     def forward(self, input_ids=None, attention_mask=None, decoder_input_ids=None, decoder_attention_mask=None,
                 observation_mask=None, decoder_observation_mask=None, encoder_outputs=None, past_key_values=None,
-                use_cache=False):
+                use_cache=False, cross_group=1):
         """(decoder states, encoder states); with ``use_cache`` or ``past_key_values``: (decoder states, cache, encoder
         states).  ``encoder_outputs``: the encoder states (a tensor, or a tuple / ModelOutput whose first entry they are),
-        which skips the encoder."""
+        which skips the encoder.  ``cross_group``: QuantizedBartDecoder.forward's."""
         if decoder_input_ids is None:
             decoder_input_ids = shift_tokens_right(input_ids, self.config.pad_token_id, self.config.decoder_start_token_id)
         if encoder_outputs is None:
@@ -970,7 +1022,8 @@ class QuantizedBartModel(QuantizedModule):
         caching = use_cache or past_key_values is not None
         dec = self.decoder(decoder_input_ids, attention_mask=decoder_attention_mask, encoder_hidden_states=enc,
                            encoder_attention_mask=attention_mask, observation_mask=decoder_observation_mask,
-                           **(dict(past_key_values=past_key_values, use_cache=True) if caching else {}))
+                           **(dict(past_key_values=past_key_values, use_cache=True) if caching else {}),
+                           **(dict(cross_group=cross_group) if cross_group != 1 else {}))
         return (dec[0], dec[1], enc) if caching else (dec, enc)
 
 
@@ -993,11 +1046,13 @@ class QuantizedBartForConditionalGeneration(QuantizedModule):
         return self.model.get_decoder()
 
     def forward(self, input_ids=None, attention_mask=None, decoder_input_ids=None, decoder_attention_mask=None,
-                labels=None, encoder_outputs=None, past_key_values=None, use_cache=None, **unused):
+                labels=None, encoder_outputs=None, past_key_values=None, use_cache=None, cross_group=1, **unused):
         """(logits, encoder states) -- [loss first with labels].  With ``use_cache=True`` (or ``past_key_values`` given and
         ``use_cache`` not False): (logits, past_key_values, encoder states), the reference's return_dict=False order; the
         cache is a QuantizedBartCache.  ``labels`` turn the cache off (quant_bart.py:1076-1082).  Unlike the reference,
-        ``use_cache`` does not default to config.use_cache: a plain call returns what it always did."""
+        ``use_cache`` does not default to config.use_cache: a plain call returns what it always did.  ``cross_group`` = G > 1
+        (no cache): the decoder's inputs have G rows per row of the encoder's states and of ``attention_mask``
+        (QuantizedBartDecoder.forward)."""
         obs = dec_obs = None
         if self.is_remove_padding:                      # quant_bart.py:1064-1072
             obs = attention_mask.sum(1)
@@ -1013,7 +1068,8 @@ class QuantizedBartForConditionalGeneration(QuantizedModule):
         out = self.model(input_ids, attention_mask, decoder_input_ids, decoder_attention_mask,
                          observation_mask=obs, decoder_observation_mask=dec_obs, encoder_outputs=encoder_outputs,
                          **(dict(past_key_values=past_key_values, use_cache=caching)
-                            if caching or past_key_values is not None else {}))
+                            if caching or past_key_values is not None else {}),
+                         **(dict(cross_group=cross_group) if cross_group != 1 else {}))
         logits = self.lm_head(out[0]) + self.final_logits_bias
         rest = (out[1], out[2]) if caching else (out[-1],)
         info = None
@@ -1022,7 +1078,7 @@ class QuantizedBartForConditionalGeneration(QuantizedModule):
         return with_loss(lm_loss(logits, labels, self.config.vocab_size, info), (logits,) + rest)
 
     @torch.no_grad()
-    def score(self, input_ids, labels, attention_mask=None, num_candidates=1, ignore_index=-100):
+    def score(self, input_ids, labels, attention_mask=None, num_candidates=1, ignore_index=-100, share_cross_kv=None):
         """How likely the model finds GIVEN target sequences, teacher-forced: (token_logprobs [B * n, T] fp32, the
         log-probability of every label under the model's own distribution -- not the warped one of sample()'s
         ``return_logprobs`` -- and 0 where the label is ``ignore_index``; sequence_logprob [B * n], their sum per row in
@@ -1031,7 +1087,12 @@ class QuantizedBartForConditionalGeneration(QuantizedModule):
         The encoder runs once, on the B inputs; its states and the attention mask are expanded with repeat_interleave(n);
         the decoder's inputs are shift_tokens_right(labels).  On the GPU the logits go through ops.token_logprob
         (csrc/token_logprob.hip) whatever set_fast_lm_loss says, on the CPU through losses.token_logprob_torch.  Raises
-        ValueError for a label outside the vocabulary (the kernel counts them; the count is read once, at the end)."""
+        ValueError for a label outside the vocabulary (the kernel counts them; the count is read once, at the end).
+        ``share_cross_kv`` (None: the package switch, set_share_cross_kv): neither the encoder states nor the mask are
+        expanded; every decoder layer projects and quantizes the cross-attention keys / values once per input and its n
+        candidates attend to that one copy (``cross_group``; ops.attention_fake_quant with ``group``).
+        ``self.last_share_cross_kv`` then says what happened: ``shared`` / ``eager`` decoder layers, and the ``reason``
+        when nothing was shared (generation.score_share_why_not)."""
         n = int(num_candidates)
         if n < 1:
             raise ValueError("score(): num_candidates must be at least 1")
@@ -1041,13 +1102,23 @@ class QuantizedBartForConditionalGeneration(QuantizedModule):
         if attention_mask is None:
             attention_mask = torch.ones_like(input_ids)
         enc = self.get_encoder()(input_ids, attention_mask=attention_mask)
-        if n > 1:
+        share = self.last_share_cross_kv = generation.ShareCrossKvInfo.asked(share_cross_kv, "SHARE_CROSS_KV")
+        if share.reason is None:
+            share.reason = generation.score_share_why_not(self, enc.device, n)
+        group = n if share.reason is None else 1
+        if n > 1 and group == 1:
             enc = enc.repeat_interleave(n, dim=0)
             attention_mask = attention_mask.repeat_interleave(n, dim=0)
         dec_in = shift_tokens_right(labels.masked_fill(labels == ignore_index, -100), self.config.pad_token_id,
                                     self.config.decoder_start_token_id)
         dec_in.clamp_(0, self.config.vocab_size - 1)    # a label outside the vocabulary is refused below, not looked up
-        logits = self.forward(attention_mask=attention_mask, decoder_input_ids=dec_in, encoder_outputs=(enc,))[0]
+        logits = self.forward(attention_mask=attention_mask, decoder_input_ids=dec_in, encoder_outputs=(enc,),
+                              **(dict(cross_group=group) if group > 1 else {}))[0]
+        if group > 1:
+            took = [layer.encoder_attn.last_cross_shared for layer in self.model.decoder.layers]
+            share.shared, share.eager = sum(took), len(took) - sum(took)
+            if not share.shared:
+                share.reason = "no decoder layer's key / value sites took the one launch (util_layernorm.FUSE_KV_APPEND)"
         rows, steps = labels.shape
         vocab = logits.shape[-1]
         scored = labels != ignore_index

@@ -1679,14 +1679,18 @@ ATTENTION_MAX_KV = 1024    # kBlkMaxS
 ATTENTION_HEAD_DIMS = (16, 32, 64, 128)
 
 
-def attention_fusable(q, k, v, mask=None):
+def attention_fusable(q, k, v, mask=None, group=1):
     """Layout rules of osq_attention_fake_quant: q [B, h, T, d], k / v [B, h, S, d], fp32 on one device, with a contiguous
     last axis and any strides on the others (dense tensors, BERT's permuted views of [B, T, H], ``[:, :, :S]`` views of cache
     buffers); mask None, or fp32 on that device, broadcastable to [B, h, T, S] with a contiguous last axis (any strides, 0
-    included, on the others).  What the library refuses on top (head_dim, S, alignment) it says itself."""
+    included, on the others).  With ``group`` = G (osq_attention_fake_quant_shared) q is [B * G, h, T, d] and its rows
+    b * G .. b * G + G - 1 share row b of k, v and mask.  What the library refuses on top (head_dim, S, alignment) it says
+    itself."""
     if not (q.dim() == 4 and k.dim() == 4 and v.dim() == 4 and q.is_cuda and q.numel() and k.numel()):
         return False
-    b, h, t, d = q.shape
+    if group < 1 or q.shape[0] % group:
+        return False
+    b, (h, t, d) = q.shape[0] // group, q.shape[1:]
     s = k.shape[2]
     if tuple(k.shape) != (b, h, s, d) or tuple(v.shape) != (b, h, s, d):
         return False
@@ -1696,29 +1700,34 @@ def attention_fusable(q, k, v, mask=None):
     return _mask_fusable(mask, (b, h, t, s), q.device)
 
 
-def _attention(what, entry, q, k, v, mask, quants, n_required, max_kv, alpha, divisor, want_probs, out, probs_out):
+def _attention(what, entry, q, k, v, mask, quants, n_required, max_kv, alpha, divisor, want_probs, out, probs_out, group=1):
     """The body of attention_fake_quant and attention_int_fake_quant below; ``what`` is the caller's name in messages, ``entry``
     the library's function.  ``quants``: the quantizer records in the order of the entry's groups, the context's last.  The
     first ``n_required`` of them are the operands of exact products: each must be there, per-tensor, on the device of q and
     of at most 256 codes, and the context's, where given, per-tensor on that device.  ``max_kv``: the keys the kernel takes.
+    ``group``: the rows of q that share a row of k / v / mask (attention_fusable); the library's ``entry + "_shared"`` whatever
+    its value, so that there is one call below.
     Returns out -- with ``want_probs`` or ``probs_out`` the pair (out, probabilities) -- or None when the call is not taken;
     what the library would refuse by head size, length or code range is asked before anything is allocated."""
     lib = _hip.load()
     _hip.require_device(q, k, v, mask)
     if alpha is not None and divisor is not None:
         raise ValueError(f"{what}: give alpha or divisor, not both")
-    if not attention_fusable(q, k, v, mask):
+    group = int(group)
+    if group < 1:
+        raise ValueError(f"{what}: group must be at least 1")
+    if not attention_fusable(q, k, v, mask, group):
         return None
     if n_required:
         checked = list(quants[:n_required]) + [x for x in quants[n_required:] if x is not None]
         if not all(_per_tensor_quant(x, q.device) for x in checked):
             return None
-    b, h, t, d = q.shape
-    s = k.shape[2]
+    bq, h, t, d = q.shape              # bq = b * group rows of q, out and the probabilities over b rows of k, v and mask
+    b, s = k.shape[0], k.shape[2]
     msb = msh = mst = 0
     if mask is not None:
         msb, msh, mst = mask.expand(b, h, t, s).stride()[:3]
-    for given, shape, name in ((out, (b, t, h * d), "out"), (probs_out, (b, h, t, s), "probs_out")):
+    for given, shape, name in ((out, (bq, t, h * d), "out"), (probs_out, (bq, h, t, s), "probs_out")):
         if given is not None and (given.dtype != torch.float32 or tuple(given.shape) != shape or not given.is_contiguous()
                                   or given.device != q.device):
             raise ValueError(f"{what}: {name} must be a contiguous fp32 tensor of shape {shape}")
@@ -1726,15 +1735,15 @@ def _attention(what, entry, q, k, v, mask, quants, n_required, max_kv, alpha, di
     if d not in ATTENTION_HEAD_DIMS or s > max_kv or any(g[6] - g[5] > ATTENTION_INT_MAX_RANGE for g in groups[:n_required]):
         return None
     if out is None:
-        out = torch.empty((b, t, h * d), dtype=torch.float32, device=q.device)
+        out = torch.empty((bq, t, h * d), dtype=torch.float32, device=q.device)
     want_probs = want_probs or probs_out is not None
-    probs = probs_out if probs_out is not None or not want_probs else torch.empty((b, h, t, s), dtype=torch.float32, device=q.device)
+    probs = probs_out if probs_out is not None or not want_probs else torch.empty((bq, h, t, s), dtype=torch.float32, device=q.device)
     # the stride of an axis of one element is never multiplied by anything but 0
     strides = [0 if x.shape[i] == 1 else x.stride(i) for x in (q, k, v) for i in range(3)]
-    rc = getattr(lib, entry)(q.data_ptr(), k.data_ptr(), v.data_ptr(), _hip.ptr(mask), out.data_ptr(), _hip.ptr(probs),
-                             b, h, t, s, d, *strides, msb, msh, mst,
-                             1.0 if alpha is None else float(alpha), 1.0 if divisor is None else float(divisor),
-                             *[x for g in groups for x in g], _hip.raw_stream(q.device))
+    rc = getattr(lib, entry + "_shared")(q.data_ptr(), k.data_ptr(), v.data_ptr(), _hip.ptr(mask), out.data_ptr(),
+                                         _hip.ptr(probs), b, group, h, t, s, d, *strides, msb, msh, mst,
+                                         1.0 if alpha is None else float(alpha), 1.0 if divisor is None else float(divisor),
+                                         *[x for g in groups for x in g], _hip.raw_stream(q.device))
     if rc == _hip.ERR_UNSUPPORTED:
         return None
     _hip.check(rc, what)
@@ -1742,7 +1751,7 @@ def _attention(what, entry, q, k, v, mask, quants, n_required, max_kv, alpha, di
 
 
 def attention_fake_quant(q, k, v, mask, probs_quant, ctx_quant, alpha=None, divisor=None, want_probs=False, *, out=None,
-                         probs_out=None):
+                         probs_out=None, group=1):
     """``fq_ctx(merge_heads(fq_probs(softmax(pre(q @ k^T) + mask)) @ v))`` for whole sequences in ONE launch
     (osq_attention_fake_quant, csrc/attention_block.hip): the [B, h, T, S] scores are never written.
 
@@ -1752,9 +1761,13 @@ def attention_fake_quant(q, k, v, mask, probs_quant, ctx_quant, alpha=None, divi
     [B, h, T, S] tensors to write into (``probs_out`` implies ``want_probs``).  Returns the [B, T, h * d] output -- with
     ``want_probs`` the pair (output, fake-quantised probabilities [B, h, T, S]) -- or None when the layout is not fusable or the library refuses
     it (head_dim outside 16 / 32 / 64 / 128, S above 1024, a misaligned pointer or stride): nothing was launched, the
-    caller runs the eager sequence."""
+    caller runs the eager sequence.
+
+    ``group`` = G > 1 (osq_attention_fake_quant_shared): q is [B * G, h, T, d], k / v [B, h, S, d] and mask broadcastable to
+    [B, h, T, S]; rows b * G .. b * G + G - 1 of q attend over row b.  out [B * G, T, h * d] and the probabilities
+    [B * G, h, T, S] are word for word those of the call without a group on k, v and mask ``repeat_interleave``d G times."""
     return _attention("attention_fake_quant", "osq_attention_fake_quant", q, k, v, mask, (probs_quant, ctx_quant), 0,
-                      ATTENTION_MAX_KV, alpha, divisor, want_probs, out, probs_out)
+                      ATTENTION_MAX_KV, alpha, divisor, want_probs, out, probs_out, group)
 
 
 ATTENTION_INT_TQ = 128         # kIntTQ of csrc/attention_int.hip: the query rows of a workgroup
@@ -1771,19 +1784,20 @@ def _per_tensor_quant(quant, device):
 
 
 def attention_int_fake_quant(q, k, v, mask, q_quant, k_quant, v_quant, probs_quant, ctx_quant, alpha=None, divisor=None,
-                             want_probs=False, *, out=None, probs_out=None):
+                             want_probs=False, *, out=None, probs_out=None, group=1):
     """attention_fake_quant on the INTEGER CODES of the quantizers that produced q, k and v and of the probabilities
     quantizer (osq_attention_fake_quant_int, csrc/attention_int.hip): both products on the bf16 matrix instruction, exact --
     the context is word for word ``fq_ctx(float(sum_j n_p[j] * n_v[j]) * (s_p * s_v))``; no limit at 1024 keys.
 
-    q, k, v, mask, ``alpha`` / ``divisor``, ``out`` / ``probs_out`` and the return convention are attention_fake_quant's.
+    q, k, v, mask, ``alpha`` / ``divisor``, ``out`` / ``probs_out``, ``group`` (osq_attention_fake_quant_int_shared) and the
+    return convention are attention_fake_quant's.
     q_quant / k_quant / v_quant / probs_quant: (scale, zero_point, quant_min, quant_max, mode, grad_factor), per-tensor, on
     the device of q, ``quant_max - quant_min <= 255`` -- all four required; ctx_quant: such a record or None.  Returns None
     when one of them is missing, per-channel, elsewhere or too wide, when the layout is not fusable or the library refuses
     it (head_dim outside 16 / 32 / 64 / 128, S above 16384, a misaligned pointer or stride): nothing was launched."""
     return _attention("attention_int_fake_quant", "osq_attention_fake_quant_int", q, k, v, mask,
                       (q_quant, k_quant, v_quant, probs_quant, ctx_quant), 4, ATTENTION_INT_MAX_KV, alpha, divisor, want_probs,
-                      out, probs_out)
+                      out, probs_out, group)
 
 
 # ---------------------------------------------------------------------------------------

@@ -119,7 +119,9 @@ are projected, quantized and held once per batch row (``QuantizedBartCache(cross
 cross-attention is ONE launch in which a workgroup serves the beams of a (row, head) from a single pass over K and V
 (``ops.decode_attention_shared``, csrc/decode_attention.hip): the words of the one-launch attention on the repeated
 tensors.  ``outlier_suppression_amd.set_share_cross_kv(True)`` / ``OSQ_SHARE_CROSS_KV=1`` / ``generate(..., share_cross_kv=True)``
-turn it on.
+turn it on.  ``score(..., num_candidates=n)`` follows the same switch (``score(..., share_cross_kv=True)``): the candidates of an
+input attend to ONE copy of its keys / values, projected and quantized once per decoder layer, through the whole-sequence
+launches with ``group=n`` (``ops.attention_fake_quant`` / ``ops.attention_int_fake_quant``; the row map of csrc/attention_seq.h).
 """
 import torch
 import torch.nn.functional as F
@@ -464,26 +466,29 @@ def decode_attention_fake_quant(probs_quantizer, ctx_quantizer, q, k, v, mask=No
     return ops.decode_attention_fake_quant(q, k, v, mask, params[0], params[1])
 
 
-def attention_block_fake_quant(probs_quantizer, ctx_quantizer, q, k, v, mask=None, alpha=None, divisor=None, dropout=None):
+def attention_block_fake_quant(probs_quantizer, ctx_quantizer, q, k, v, mask=None, alpha=None, divisor=None, dropout=None,
+                               group=1):
     """An attention block over a whole sequence, from the fake-quantised q [B, h, T, d] and k / v [B, h, S, d] to the merged,
     fake-quantised context [B, T, h*d] -- matmul, ``alpha`` / ``divisor`` and mask as attention_probs_fake_quant takes them,
     softmax, ``probs_quantizer``, matmul, merge heads, ``ctx_quantizer`` -- as ONE launch (ops.attention_fake_quant).  Gated
     as decode_attention_fake_quant is: only with FUSE_ATTENTION on, autograd off, dropout inactive and each quantizer either
     None or in its plain quantising state.  The grad factors go by the tensors the eager quantizers would see:
-    probabilities [B, h, T, S], context [B, T, h*d].  Returns the context, or None (nothing launched): the caller goes on
-    with the eager sequence."""
+    probabilities [B, h, T, S], context [B, T, h*d].  ``group`` = G > 1: q is [B * G, h, T, d] and its rows b * G ..
+    b * G + G - 1 share row b of k, v and mask (ops.attention_fake_quant, ``group``); the grad factors go by q's rows, so the
+    words are those of this function on k, v and mask repeated G times.  Returns the context, or None (nothing launched):
+    the caller goes on with the eager sequence."""
     if not FUSE_ATTENTION or torch.is_grad_enabled() or _dropout_active(dropout):
         return None
-    if q.dim() != 4 or k.dim() != 4 or not ops.attention_fusable(q, k, v, mask):
+    if q.dim() != 4 or k.dim() != 4 or not ops.attention_fusable(q, k, v, mask, group):
         return None
     params = _decode_site_params(q, (probs_quantizer, q.shape[0] * q.shape[1] * q.shape[2] * k.shape[2]), (ctx_quantizer, q.numel()))
     if params is None:
         return None
-    return ops.attention_fake_quant(q, k, v, mask, params[0], params[1], alpha=alpha, divisor=divisor)
+    return ops.attention_fake_quant(q, k, v, mask, params[0], params[1], alpha=alpha, divisor=divisor, group=group)
 
 
 def attention_int_refusal(q_quantizer, k_quantizer, v_quantizer, probs_quantizer, ctx_quantizer, q, k, v, mask=None,
-                          dropout=None):
+                          dropout=None, group=1):
     """Why attention_int_block_fake_quant would not hand this call to the integer kernel -- one line -- or None when it
     would (the library may still refuse the shape: head size, length, alignment)."""
     if not FUSE_ATTENTION_INT:
@@ -503,40 +508,43 @@ def attention_int_refusal(q_quantizer, k_quantizer, v_quantizer, probs_quantizer
             return f"the {name} quantizer has more than 256 codes"
     if not (q.is_cuda and k.is_cuda and v.is_cuda):
         return "q / k / v are not on a GPU"
-    if q.dim() != 4 or k.dim() != 4 or not ops.attention_fusable(q, k, v, mask):
+    if q.dim() != 4 or k.dim() != 4 or not ops.attention_fusable(q, k, v, mask, group):
         return "the layout of q / k / v / mask is not fusable"
     return None            # where the parameters live is _decode_site_params' to see
 
 
 def attention_int_block_fake_quant(q_quantizer, k_quantizer, v_quantizer, probs_quantizer, ctx_quantizer, q, k, v, mask=None,
-                                   alpha=None, divisor=None, dropout=None):
+                                   alpha=None, divisor=None, dropout=None, group=1):
     """attention_block_fake_quant on the INTEGER CODES of the block's own quantizers (ops.attention_int_fake_quant,
     csrc/attention_int.hip): ``q_quantizer`` / ``k_quantizer`` / ``v_quantizer`` are the quantizers that PRODUCED q, k and
     v, so that both products run exactly, on the bf16 matrix instruction, over S up to 16384.  Gated as that function is,
     with FUSE_ATTENTION_INT for FUSE_ATTENTION: autograd off, dropout inactive, every quantizer in its plain quantising state
     and per-tensor; q, k, v and the probabilities quantizer are required, ``ctx_quantizer`` may be None
-    (attention_int_refusal names the reason of a refusal).  The grad factors go by the tensors the eager quantizers see.
+    (attention_int_refusal names the reason of a refusal).  The grad factors go by the tensors the eager quantizers see --
+    with ``group`` = G > 1 (as in attention_block_fake_quant) those of the unshared form: k and v by G times their elements.
     Returns the context [B, T, h*d], or None (nothing launched): the caller goes on with attention_block_fake_quant and the
     eager sequence."""
-    if attention_int_refusal(q_quantizer, k_quantizer, v_quantizer, probs_quantizer, ctx_quantizer, q, k, v, mask, dropout):
+    if attention_int_refusal(q_quantizer, k_quantizer, v_quantizer, probs_quantizer, ctx_quantizer, q, k, v, mask, dropout,
+                             group):
         return None
-    params = _decode_site_params(q, (q_quantizer, q.numel()), (k_quantizer, k.numel()), (v_quantizer, v.numel()),
+    params = _decode_site_params(q, (q_quantizer, q.numel()), (k_quantizer, k.numel() * group), (v_quantizer, v.numel() * group),
                                  (probs_quantizer, q.shape[0] * q.shape[1] * q.shape[2] * k.shape[2]), (ctx_quantizer, q.numel()))
     if params is None:
         return None
-    return ops.attention_int_fake_quant(q, k, v, mask, *params, alpha=alpha, divisor=divisor)
+    return ops.attention_int_fake_quant(q, k, v, mask, *params, alpha=alpha, divisor=divisor, group=group)
 
 
 def attention_sequence_fake_quant(q_quantizer, k_quantizer, v_quantizer, probs_quantizer, ctx_quantizer, q, k, v, mask=None,
-                                  alpha=None, divisor=None, dropout=None):
+                                  alpha=None, divisor=None, dropout=None, group=1):
     """The one-launch attention block over a whole sequence as the models call it: on the integer codes of the block's
     quantizers (attention_int_block_fake_quant, FUSE_ATTENTION_INT), else in fp32 (attention_block_fake_quant,
-    FUSE_ATTENTION).  Returns the context [B, T, h*d], or None when neither launched: the caller runs the eager sequence."""
+    FUSE_ATTENTION).  ``group``: the rows of q that share a row of k, v and mask, as both take it.  Returns the context
+    [B, T, h*d], or None when neither launched: the caller runs the eager sequence (on expanded k, v and mask, with a group)."""
     out = attention_int_block_fake_quant(q_quantizer, k_quantizer, v_quantizer, probs_quantizer, ctx_quantizer, q, k, v, mask,
-                                         alpha=alpha, divisor=divisor, dropout=dropout)
+                                         alpha=alpha, divisor=divisor, dropout=dropout, group=group)
     if out is None:
         out = attention_block_fake_quant(probs_quantizer, ctx_quantizer, q, k, v, mask, alpha=alpha, divisor=divisor,
-                                         dropout=dropout)
+                                         dropout=dropout, group=group)
     return out
 
 

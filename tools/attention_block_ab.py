@@ -12,6 +12,9 @@ are asserted within one quantization step of each other, and the number of codes
                     causal mask [B, 1, T, S]): [B, h, T, S, d] = [32,12,128,128,64], [32,12,384,384,64], BART-large's encoder
                     [32,16,512,512,64], its decoder's self- [192,16,62,62,64] and cross-attention [192,16,62,512,64], and its
                     encoder at 1024 tokens [8,16,1024,1024,64];
+  the shared row    (--shared runs it alone) both one-launch kernels on the cross-attention of score(num_candidates=6):
+                    [32 x 6, 16, 62, 512, 64] with ``group=6`` -- 6 x 62 query rows over ONE copy of each input's keys and
+                    values -- against [192, 16, 62, 512, 64] on the repeated copies; the outputs are asserted word-equal;
   models            (--no-models skips them) a random-init BERT-base forward at 32 x 128 and 32 x 384; on the random-init
                     BART-large shape of tools/decode_bench.py the encoder pass at 32 x 512, score(num_candidates=6) and
                     generate(max_length=62, num_beams=6).
@@ -150,6 +153,84 @@ def block_forms(emit, label, shape, mask_kind, reps, inner):
     emit("")
 
 
+def shared_block(emit, reps, inner):
+    """The cross-attention of score(num_candidates=6) on the BART-large shape in both one-launch kernels, grouped against
+    unshared, every form timed in turn within each round."""
+    from outlier_suppression_amd import _hip, util_layernorm as UL
+    from outlier_suppression_amd.quantization import Quantizer
+    b, n, h, t, s, d = 32, 6, 16, 62, 512, 64
+    dev = torch.device("cuda:0")
+    g = torch.Generator(device=dev).manual_seed(t * 1000 + s)
+    q = torch.randn((b * n, h, t, d), generator=g, device=dev) * (d ** -0.5 * 2.0)
+    k, v = (torch.randn((b, h, s, d), generator=g, device=dev) for _ in range(2))
+    lengths = torch.randint(s // 2, s + 1, (b,), generator=g, device=dev)
+    mask = torch.zeros((b, 1, 1, s), device=dev).masked_fill(torch.arange(s, device=dev)[None, None, None] >= lengths[:, None, None, None],
+                                                             torch.finfo(torch.float32).min)
+    probs_q, ctx_q, q_q, k_q, v_q = (Quantizer(None, A_Q).to(dev) for _ in range(5))
+    _hip.load()                                          # the first load applies the environment's tier, the switches included
+    set_form(False, True, True)
+    with torch.no_grad():
+        for qz in (q_q, k_q, v_q):
+            qz.enable_observer()
+            qz.disable_fake_quant()
+        q_q(q), k_q(k), v_q(v)
+        for qz in (q_q, k_q, v_q):
+            qz.disable_observer()
+            qz.enable_fake_quant()
+        q, k, v = q_q(q), k_q(k), v_q(v)
+        kr, vr, mr = (x.repeat_interleave(n, dim=0) for x in (k, v, mask))
+        for qz in (probs_q, ctx_q):                      # one observer pass through the eager lines, then the plain state
+            qz.enable_observer()
+            qz.disable_fake_quant()
+        w = torch.bmm(q.view(b * n * h, t, d), kr.view(b * n * h, s, d).transpose(1, 2))
+        probs = UL.attention_probs_fake_quant(probs_q, w, mr, dropout=(0.0, False), seq_pos=2, heads=h)
+        UL.merge_heads_fake_quant(ctx_q, torch.bmm(probs, vr.view(b * n * h, s, d)).view(b * n, h, t, d))
+        del w, probs
+        for qz in (probs_q, ctx_q):
+            qz.disable_observer()
+            qz.enable_fake_quant()
+        forms = {
+            "FUSE_ATTENTION_INT unshared": lambda: UL.attention_int_block_fake_quant(q_q, k_q, v_q, probs_q, ctx_q, q, kr, vr, mr, dropout=(0.0, False)),
+            "FUSE_ATTENTION_INT group=6": lambda: UL.attention_int_block_fake_quant(q_q, k_q, v_q, probs_q, ctx_q, q, k, v, mask, dropout=(0.0, False), group=n),
+            "FUSE_ATTENTION unshared": lambda: UL.attention_block_fake_quant(probs_q, ctx_q, q, kr, vr, mr, dropout=(0.0, False)),
+            "FUSE_ATTENTION group=6": lambda: UL.attention_block_fake_quant(probs_q, ctx_q, q, k, v, mask, dropout=(0.0, False), group=n),
+        }
+        outs = {name: fn() for name, fn in forms.items()}
+        for name, out in outs.items():                   # a form that did not launch is an error here, with its reason
+            if out is None:
+                grouped = name.endswith("group=6")
+                why = UL.attention_int_refusal(q_q, k_q, v_q, probs_q, ctx_q, q, k if grouped else kr, v if grouped else vr,
+                                               mask if grouped else mr, (0.0, False), n if grouped else 1)
+                raise RuntimeError(f"{name} did not launch (the integer form's own objection: {why}; last library error: "
+                                   f"{_hip.load().osq_last_error().decode()!r})")
+        emit(f"bart-large decoder cross, shared: [B x G, h, T, S, d] = [{b} x {n}, {h}, {t}, {s}, {d}] with group={n} against "
+             f"[{b * n}, {h}, {t}, {s}, {d}] unshared, pad mask")
+        for kernel in ("FUSE_ATTENTION_INT", "FUSE_ATTENTION"):
+            same = torch.equal(outs[f"{kernel} group=6"].view(torch.int32), outs[f"{kernel} unshared"].view(torch.int32))
+            assert same, kernel
+            emit(f"    {kernel}: the grouped launch's context is word-equal to the unshared launch's")
+        times = {name: [] for name in forms}
+        for r in range(reps + 2):
+            for name, fn in forms.items():
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(inner):
+                    fn()
+                torch.cuda.synchronize()
+                if r >= 2:
+                    times[name].append((time.perf_counter() - t0) * 1e3 / inner)
+    set_form(False, False)
+    for kernel in ("FUSE_ATTENTION_INT", "FUSE_ATTENTION"):
+        base, new = times[f"{kernel} unshared"], times[f"{kernel} group=6"]
+        mb, mn = statistics.median(base), statistics.median(new)
+        gain, spread = (mb - mn) / mb, (max(base) - min(base)) / mb
+        emit(f"    {kernel + ' unshared':<30} {mb:9.4f} ms [{min(base):.4f}, {max(base):.4f}]")
+        emit(f"    {kernel + ' group=6':<30} {mn:9.4f} ms [{min(new):.4f}, {max(new):.4f}]   {mb / mn:5.2f}x unshared; the difference "
+             f"({gain * 100:+.1f} %) {'exceeds' if abs(gain) > spread else 'does NOT exceed'} the unshared form's own spread "
+             f"({spread * 100:.1f} %)")
+    emit("")
+
+
 def model_forms(emit, label, fn, reps, inner):
     """A model call in the four forms.  A random-init W6A6 model carries a code that flips in one block through every
     later layer, so its outputs are not held to a bar here (tests/test_gpu_attention_block_model.py holds calibrated models
@@ -194,6 +275,7 @@ def main():
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--inner", type=int, default=5)
     ap.add_argument("--no-models", action="store_true")
+    ap.add_argument("--shared", action="store_true", help="the shared row alone")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     assert torch.cuda.is_available(), "attention_block_ab.py measures on a GPU"
@@ -205,10 +287,12 @@ def main():
     emit(f"tools/attention_block_ab.py on {torch.cuda.get_device_name(0)}: medians of {args.reps} rounds of --inner calls "
          "[min, max], every form in turn within each round")
     emit("")
-    for label, shape, mask_kind in BLOCKS:
+    for label, shape, mask_kind in () if args.shared else BLOCKS:
         block_forms(emit, label, shape, mask_kind, args.reps, args.inner)
         torch.cuda.empty_cache()
-    if not args.no_models:
+    shared_block(emit, args.reps, args.inner)
+    torch.cuda.empty_cache()
+    if not args.no_models and not args.shared:
         for length in (128, 384):
             q, ids, mask = bert_base(32, length)
             tt = torch.zeros_like(ids)

@@ -13,7 +13,14 @@ Then, on a random-init BART-large shape (d_model 1024, 12 + 12 layers, vocab 502
 --batch, source 512, targets of 62 tokens: score(num_candidates=6) -- the encoder once per input -- against score() of the six
 times repeated inputs.  --no-model skips it.
 
+--share measures only this, on that model and shape: score(num_candidates=6) unshared against share_cross_kv=True -- the
+cross-attention keys / values projected, quantized and attended once per input -- under each of: every one-launch attention
+switch off, FUSE_SOFTMAX, FUSE_ATTENTION_INT, FUSE_ATTENTION; every form timed in turn in one process, with the peak memory
+above the inputs and the largest difference of a token log-probability between the two forms (reported, not asserted:
+rocBLAS may pick another kernel for the projections of B * S rows than of B * 6 * S).
+
     python tools/score_bench.py [--reps 7] [--out profiles/token_logprob_ab.txt]
+    python tools/score_bench.py --share [--reps 7] [--out profiles/score_share_ab.txt]
 """
 import argparse
 import os
@@ -148,12 +155,55 @@ def score_forms(emit, batch, reps):
     emit("")
 
 
+SHARE_SWITCHES = ("all switches off", "FUSE_SOFTMAX", "FUSE_ATTENTION_INT", "FUSE_ATTENTION")
+
+
+def share_forms(emit, batch, reps):
+    from decode_bench import build
+    from outlier_suppression_amd import util_layernorm as UL
+    n, steps = 6, 62
+    q, ids, mask = build(batch, 512, 12)
+    labels = torch.randint(3, VOCAB, (batch * n, steps), device=ids.device)
+    names = ("FUSE_SOFTMAX", "FUSE_ATTENTION_INT", "FUSE_ATTENTION")
+    old = {name: getattr(UL, name) for name in names}
+
+    def form(switch, share):
+        def run():
+            for name in names:
+                setattr(UL, name, name == switch)
+            return q.score(ids, labels, attention_mask=mask, num_candidates=n, share_cross_kv=share)
+        return run
+    emit(f"score(num_candidates={n}) on the BART-large shape, W6A6: {batch} inputs of 512 tokens, {n} candidates of {steps} "
+         f"tokens each; unshared (the encoder states repeated {n} times) against share_cross_kv=True")
+    forms = {}
+    for switch in SHARE_SWITCHES:
+        forms[f"{switch}, unshared"], forms[f"{switch}, shared"] = form(switch, False), form(switch, True)
+    try:
+        for switch in SHARE_SWITCHES:
+            a, b = forms[f"{switch}, unshared"](), forms[f"{switch}, shared"]()
+            info = q.last_share_cross_kv
+            emit(f"  {switch}: {info}; largest |token log-prob difference| shared - unshared "
+                 f"{float((a[0] - b[0]).abs().max()):.3g} (largest |token log-prob| {float(a[0].abs().max()):.3g})")
+            del a, b
+        times = timed(forms, reps, 1)
+        for switch in SHARE_SWITCHES:
+            emit(f"  {switch}")
+            compare(emit, times, f"{switch}, unshared", f"{switch}, shared")
+            for name in (f"{switch}, unshared", f"{switch}, shared"):
+                emit(f"    {name:<34} peak memory above the inputs {peak_above(forms[name]) / 1e6:10.1f} MB")
+    finally:
+        for name, value in old.items():
+            setattr(UL, name, value)
+    emit("")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--inner", type=int, default=10)
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--no-model", action="store_true")
+    ap.add_argument("--share", action="store_true")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     assert torch.cuda.is_available(), "score_bench.py measures on a GPU"
@@ -162,13 +212,19 @@ def main():
     def emit(line):
         print(line, flush=True)
         lines.append(line)
-    emit(f"tools/score_bench.py on {torch.cuda.get_device_name(0)}: medians of {args.reps} windows of {args.inner} calls "
-         "[min, max], every form in turn within each round")
-    emit("")
-    for rows in (32 * 62, 32 * 128):
-        loss_forms(emit, rows, args.reps, args.inner)
-    if not args.no_model:
-        score_forms(emit, args.batch, args.reps)
+    if args.share:
+        emit(f"tools/score_bench.py --share on {torch.cuda.get_device_name(0)}: medians of {args.reps} calls [min, max], every "
+             "form in turn within each round")
+        emit("")
+        share_forms(emit, args.batch, args.reps)
+    else:
+        emit(f"tools/score_bench.py on {torch.cuda.get_device_name(0)}: medians of {args.reps} windows of {args.inner} calls "
+             "[min, max], every form in turn within each round")
+        emit("")
+        for rows in (32 * 62, 32 * 128):
+            loss_forms(emit, rows, args.reps, args.inner)
+        if not args.no_model:
+            score_forms(emit, args.batch, args.reps)
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as f:
