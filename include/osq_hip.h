@@ -48,7 +48,8 @@ typedef void* osq_stream;
  *     osq_decode_attention_shared, osq_decode_attention_shared_codes, osq_sample_advance_group, osq_sample_advance_group_at,
  *     osq_sample_nucleus_group, osq_sample_nucleus_group_at, osq_sample_uniforms_group, osq_token_logprob_workspace_bytes,
  *     osq_token_logprob, osq_token_logprob_backward, osq_attention_fake_quant, osq_attention_fake_quant_int,
- *     osq_attention_fake_quant_shared, osq_attention_fake_quant_int_shared. */
+ *     osq_attention_fake_quant_shared, osq_attention_fake_quant_int_shared, osq_gelu_fake_quant_backward,
+ *     osq_attention_softmax_fake_quant_backward. */
 #define OSQ_ABI_VERSION 10
 
 typedef enum osq_status {
@@ -189,7 +190,7 @@ int osq_fake_quant_per_tensor(const float* x, float* y, float* x_quant, int64_t 
 /* The intermediate-activation site of a transformer block in one pass (model/quant_bert.py:277-280,
  * quant_bart.py:347-348: fc1 / dense -> GELU -> *_act_fn_post_act_fake_quantize): y = fake_quantize(gelu(x))
  * with torch's exact (erf) GELU, bit-identical to F.gelu followed by osq_fake_quant_per_tensor.  x, y: n
- * contiguous fp32, 16-byte aligned (else OSQ_ERR_UNSUPPORTED).  Inference only. */
+ * contiguous fp32, 16-byte aligned (else OSQ_ERR_UNSUPPORTED).  Its backward: osq_gelu_fake_quant_backward. */
 int osq_gelu_fake_quant_per_tensor(const float* x, float* y, int64_t n,
                                    float* scale, void* zero_point, int zp_type,
                                    int mode, float grad_factor, int quant_min, int quant_max,
@@ -310,6 +311,46 @@ int osq_lsq_backward_per_channel(const float* x, const float* grad_out, float* g
  * n entries, in place, one launch.  zero_point may be NULL (LSQ keeps an int32 buffer). */
 int osq_lsq_sanitize(float* scale, float* zero_point, int64_t n, float eps,
                      int quant_min, int quant_max, osq_stream stream);
+
+/* ------------------------------------------------------------------ backward of the one-launch sites */
+
+/* Backward of osq_gelu_fake_quant_per_tensor, y = fake_quantize(gelu(x)), from the site's INPUT x, in one streaming launch.
+ * Per element:
+ *     g  = gelu(x)                           the forward's device function: the words the forward quantised
+ *     dg, the three sum terms                the per-element rule of osq_lsq_backward_per_tensor on (g, grad_out)
+ *     grad_x = dg * (Phi(x) + x phi(x))      fp32; Phi = 0.5 (1 + erff(x / sqrt 2)) as in the forward, phi = exp(-x^2 / 2) / sqrt(2 pi)
+ * grad_scale[1] / grad_zero_point[1] (each nullable): the launch takes the grid of osq_lsq_backward_per_tensor for n and adds
+ * the same terms in the same order, so both are WORD-EQUAL to that call on (gelu(x), grad_out); float64 sums rounded once, no
+ * atomics on floating-point data, the same words on every run.  mode: OSQ_PARAM_FIXED / _LSQ / _LSQPLUS without
+ * OSQ_PARAM_SANITIZE (the repair is the forward's).  x, grad_out, grad_x: n contiguous fp32, 16-byte aligned (else
+ * OSQ_ERR_UNSUPPORTED).  The order-free summation tier only.  Its partials live in a workspace family of their own: the
+ * launch may overlap an osq_lsq_backward_per_tensor on the same workspace. */
+int osq_gelu_fake_quant_backward(const float* x, const float* grad_out, float* grad_x, int64_t n,
+                                 const float* scale, const void* zero_point, int zp_type,
+                                 int mode, float grad_factor, int quant_min, int quant_max,
+                                 float* grad_scale, float* grad_zero_point,
+                                 void* workspace, osq_stream stream);
+
+/* Backward of osq_attention_softmax_fake_quant from the site's INPUT, in one launch, one wave per row with the row in
+ * registers.  scores / mask / strides / alpha / divisor as given to the forward; per row (b, h, t):
+ *     p  = softmax(pre(scores) + mask)               recomputed by the forward's own device code: its words
+ *     dp, the three sum terms                        the per-element rule of osq_lsq_backward_per_tensor on (p, grad_out)
+ *     dot = sum_j dp_j p_j                           float64 in the wave (exact products), rounded to fp32 once
+ *     grad_scores_j = pre' * (p_j * (dp_j - dot))    pre' = alpha | 1 / divisor (one fp32 division) | nothing
+ * The mask receives no gradient; a key masked with -inf gets grad_scores == 0.  grad_scale[1] / grad_zero_point[1] (each
+ * nullable): fp32 per lane over a row, float64 from there, workgroup partials combined in block order by the workgroup that
+ * arrives last -- no atomics on floating-point data, the same words on every run; workspace family as above.  mode as above.
+ * Takes the geometry of the forward's register-resident kernel only -- cols % 4 == 0, cols <= 2048, 16-byte aligned scores /
+ * grad_out / grad_scores and mask rows -- anything else is OSQ_ERR_UNSUPPORTED (nothing launched: the caller keeps the eager
+ * chain). */
+int osq_attention_softmax_fake_quant_backward(const float* scores, const float* mask, int64_t batch, int64_t heads,
+                                              int64_t tokens, int64_t cols, int64_t mask_stride_b, int64_t mask_stride_h,
+                                              int64_t mask_stride_t, float alpha, float divisor,
+                                              const float* grad_out, float* grad_scores,
+                                              const float* scale, const void* zero_point, int zp_type,
+                                              int mode, float grad_factor, int quant_min, int quant_max,
+                                              float* grad_scale, float* grad_zero_point,
+                                              void* workspace, osq_stream stream);
 
 /* ------------------------------------------------------------------ observers */
 
@@ -807,7 +848,7 @@ int osq_residual_layernorm_fake_quant(const float* x, const float* hidden, const
  * mode / grad_factor / zp_type as in osq_fake_quant_per_tensor, including OSQ_PARAM_SANITIZE: for a given p, y is
  * word-equal to osq_fake_quant_per_tensor(p).  cols % 4 == 0, cols <= 2048 with 16-byte aligned scores / y / mask rows
  * run the register-resident kernel (8 B per element); any other shape a generic kernel with the same arithmetic.
- * Inference only: autograd passes use the eager sequence. */
+ * Its backward, for the register-resident geometry: osq_attention_softmax_fake_quant_backward. */
 int osq_attention_softmax_fake_quant(const float* scores, const float* mask, int64_t batch, int64_t heads, int64_t tokens,
                                      int64_t cols, int64_t mask_stride_b, int64_t mask_stride_h, int64_t mask_stride_t,
                                      float alpha, float divisor, float* y,

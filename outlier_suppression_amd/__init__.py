@@ -220,6 +220,20 @@ def set_fast_lm_loss(on=True):
     util_layernorm.FAST_LM_LOSS = bool(on)
 
 
+def set_fast_backward(on=True):
+    """Autograd passes (learn_scale) keep the one-launch GELU site and, under set_fast_softmax, the one-launch
+    attention-probabilities site, each with a one-launch backward that recomputes the quantizer's input from the site's own
+    input (util_layernorm.FUSE_BACKWARD; csrc/site_backward.hip; default OFF).  A call the kernels do not take runs the eager
+    lines (``util_layernorm.site_backward``: gelu, softmax, eager, reason).  OSQ_FAST_BACKWARD=1 turns it on at load."""
+    from . import util_layernorm
+    util_layernorm.FUSE_BACKWARD = bool(on)
+
+
+def fast_backward_from_environment(environ=None):
+    """What OSQ_FAST_BACKWARD asks for: unset, empty or "0" -> False, anything else -> True."""
+    return _env_on("OSQ_FAST_BACKWARD", environ)
+
+
 def fast_lm_loss_from_environment(environ=None):
     """What OSQ_FAST_LM_LOSS asks for: unset, empty or "0" -> False, anything else -> True."""
     return _env_on("OSQ_FAST_LM_LOSS", environ)
@@ -289,7 +303,8 @@ def reset_tier(_lib=None):
     (unset: off); OSQ_SAMPLE_GRAPH=1 sample() replays a whole step as one captured graph (unset: off); OSQ_SAMPLE_NUCLEUS=1
     that kernel call takes a nucleus over the whole vocabulary too (unset: off); OSQ_SHARE_CROSS_KV=1 beam search holds the
     cross-attention keys / values once per batch row (unset: off); OSQ_FAST_LM_LOSS=1 the BART LM wrapper's loss through the
-    scoring kernels (unset: off)."""
+    scoring kernels (unset: off); OSQ_FAST_BACKWARD=1 autograd passes keep the one-launch GELU and attention-probabilities
+    sites, with one-launch backwards (unset: off)."""
     import os
     width = int(os.environ.get("OSQ_STRICT_SIMD", "8"))
     strict = os.environ.get("OSQ_STRICT", "")
@@ -312,7 +327,7 @@ _SWITCHES = ((set_cache_codes, "OSQ_CACHE_CODES"), (set_graph_decode, "OSQ_GRAPH
              (set_greedy_graph, "OSQ_GREEDY_GRAPH"), (set_sample_advance, "OSQ_SAMPLE_ADVANCE"),
              (set_sample_graph, "OSQ_SAMPLE_GRAPH"), (set_sample_nucleus, "OSQ_SAMPLE_NUCLEUS"),
              (set_share_cross_kv, "OSQ_SHARE_CROSS_KV"), (set_fast_lm_loss, "OSQ_FAST_LM_LOSS"),
-             (set_fast_attention_int, "OSQ_FAST_ATTENTION_INT"))
+             (set_fast_attention_int, "OSQ_FAST_ATTENTION_INT"), (set_fast_backward, "OSQ_FAST_BACKWARD"))
 _apply_environment = reset_tier
 
 

@@ -21,43 +21,13 @@
 #include <math.h>
 #include <string>
 #include <hip/hip_ext.h>
-#include "attention_seq.h"
+#include "attention_row.h"
 
 namespace osq {
 
-constexpr int kAttnThreads = 256;
-constexpr int kAttnWaves = kAttnThreads / OSQ_WAVE;
-constexpr int kAttnMaxCols = 4 * 8 * OSQ_WAVE;     // 2048: eight float4 per lane
 OSQ_AB_KNOB(int, g_attn_blocks, 2048);             // grid cap (osq_set_tuning("attn_blocks", n)); rows are grid-strided above it
 
-struct AttnArgs {
-    const float* scores;      // [rows, cols] contiguous; rows = batch * heads * tokens
-    float* y;
-    const float* mask;        // nullable; row (b, h, t) starts at b * mask_sb + h * mask_sh + t * mask_st
-    int64_t mask_sb, mask_sh, mask_st;
-    int64_t heads, tokens, rows;
-    int cols;
-    float alpha, divisor;
-    DecQuant quant;           // the probabilities quantizer; scale == nullptr: softmax only
-};
-
-__device__ __forceinline__ int64_t mask_row(const AttnArgs& a, int64_t row) {
-    const int64_t t = row % a.tokens, bh = row / a.tokens;
-    return (bh / a.heads) * a.mask_sb + (bh % a.heads) * a.mask_sh + t * a.mask_st;
-}
-
-template <int R, bool MASK>
-__device__ __forceinline__ void load_attn_row(const AttnArgs& a, int64_t row, int lane, int cols4, float4* v, float4* m) {
-    const float4* xr = reinterpret_cast<const float4*>(a.scores) + row * cols4;
-    const float4* mr = MASK ? reinterpret_cast<const float4*>(a.mask + mask_row(a, row)) : nullptr;
-#pragma unroll
-    for (int k = 0; k < R; ++k) {
-        const int c = lane + k * OSQ_WAVE, cc = c < cols4 ? c : cols4 - 1;
-        v[k] = load_stream(xr + cc);
-        if (MASK) m[k] = mr[cc];           // a broadcast operand: plain loads, it stays in cache across rows
-    }
-}
-
+// AttnArgs, the row's loads and its softmax: attention_row.h (shared with the site's backward, site_backward.hip)
 template <int R, int PRE, bool MASK, bool WT>
 __global__ __launch_bounds__(kAttnThreads) void attention_softmax_fq_kernel(AttnArgs a) {
     const int lane = threadIdx.x & (OSQ_WAVE - 1);
@@ -72,28 +42,7 @@ __global__ __launch_bounds__(kAttnThreads) void attention_softmax_fq_kernel(Attn
     for (int64_t row = wave0; row < a.rows; row += nwaves) {
         float4 vn[R], mn[R];
         if (row + nwaves < a.rows) load_attn_row<R, MASK>(a, row + nwaves, lane, cols4, vn, mn);
-        float mx = -INFINITY;
-#pragma unroll
-        for (int k = 0; k < R; ++k) {
-            float t[4] = {v[k].x, v[k].y, v[k].z, v[k].w};
-            const float mm[4] = {MASK ? m[k].x : 0.f, MASK ? m[k].y : 0.f, MASK ? m[k].z : 0.f, MASK ? m[k].w : 0.f};
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                t[e] = pre_softmax(PRE, t[e], a.alpha, a.divisor);
-                if (MASK) t[e] = t[e] + mm[e];
-            }
-            v[k] = make_float4(t[0], t[1], t[2], t[3]);
-            // fmaxf drops a NaN: harmless, a NaN entry makes its exp and so the row's sum NaN
-            if (lane + k * OSQ_WAVE < cols4) mx = fmaxf(mx, fmaxf(fmaxf(t[0], t[1]), fmaxf(t[2], t[3])));
-        }
-        mx = wave_max(mx);
-        float sum = 0.f;
-#pragma unroll
-        for (int k = 0; k < R; ++k) {
-            v[k] = make_float4(expf(v[k].x - mx), expf(v[k].y - mx), expf(v[k].z - mx), expf(v[k].w - mx));
-            if (lane + k * OSQ_WAVE < cols4) sum += (v[k].x + v[k].y) + (v[k].z + v[k].w);
-        }
-        const float r = 1.0f / wave_sum_f32(sum);
+        const float r = softmax_row<R, PRE, MASK>(a, lane, cols4, v, m);
         const int64_t base = row * cols4;
 #pragma unroll
         for (int k = 0; k < R; ++k) {
@@ -180,8 +129,7 @@ extern "C" int osq_attention_softmax_fake_quant(const float* scores, const float
     const dim3 grid(static_cast<unsigned>(blocks));
     hipStream_t st = static_cast<hipStream_t>(stream);
     const TimingHook th = take_timing_hook(OSQ_TIME_ATTENTION_SOFTMAX);
-    const bool fast = cols % 4 == 0 && cols <= kAttnMaxCols && aligned16(scores) && aligned16(y) &&
-                      (!mask || (aligned16(mask) && mask_stride_b % 4 == 0 && mask_stride_h % 4 == 0 && mask_stride_t % 4 == 0));
+    const bool fast = attn_row_geometry(scores, mask, cols, mask_stride_b, mask_stride_h, mask_stride_t) && aligned16(y);
     if (!fast) {
 #define OSQ_ATTN_G(PRE, MASK) \
     hipExtLaunchKernelGGL((attention_softmax_fq_generic_kernel<PRE, MASK>), grid, dim3(kAttnThreads), 0, st, th.start, th.stop, 0, a)

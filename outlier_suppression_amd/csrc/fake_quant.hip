@@ -12,6 +12,7 @@
 #include "osq_device.h"
 #include "aten_order.h"
 #include "osq_host.h"
+#include "lsq_backward.h"
 
 namespace osq {
 
@@ -44,14 +45,7 @@ __device__ __forceinline__ void fq4(const float4& v, float4& y, float4& q, float
 
 // ---------------------------------------------------------------- per-tensor, dense
 
-// torch's exact GELU (aten GeluCUDAKernelImpl, approximate='none'): x * 0.5 * (1 + erf(x * M_SQRT1_2)), fp32,
-// same operation order; erff is the ocml routine torch's HIP build calls too, so the fused activation is
-// bit-identical to F.gelu on the device (tests/test_gpu_parity.py::test_gelu_fake_quant_fused).
-__device__ __forceinline__ float gelu_erf(float x) {
-    constexpr float kAlpha = 0.70710678118654752440f;
-    return (x * 0.5f) * (1.0f + erff(x * kAlpha));
-}
-
+// GELU = true: y = fake_quantize(gelu_erf(x)) (lsq_backward.h: torch's exact GELU, bit-identical to F.gelu on the device)
 template <bool WRITE_Q, int UNROLL, int NT, bool GELU = false>
 __global__ __launch_bounds__(kThreads) void fq_tensor_vec_kernel(
     const float4* __restrict__ x, float4* __restrict__ y, float4* __restrict__ xq, int64_t n4,
@@ -481,118 +475,9 @@ __global__ __launch_bounds__(kThreads) void fq_weights_multi_kernel(const osq_we
 
 // ---------------------------------------------------------------- LSQ / LSQ+ backward
 
-// Per element (autograd of util_quant.py:48-55, see oracle/fake_quant_oracle.py):
-//   g_mul = gy * s ; g_in = inside ? g_mul : 0 ; dx = g_in / s
-//   ds  += gy * (xq - z)  +  (-g_in) * ((x / s) / s)
-//   dzp += g_in - g_mul
-// Sums: fp32 per lane over a short run, then double across lanes / blocks; block
-// partials are combined in block order by the last block (deterministic).
-struct BwdAcc {
-    float ds_mul, ds_div, dz;
-};
-
-__device__ __forceinline__ float bwd_elem(float x, float gy, float s, float z, float qmin, float qmax, BwdAcc& a) {
-    float x_int;
-    const float q = quantize_value(x, s, z, qmin, qmax, &x_int);
-    const bool inside = (x_int >= qmin) && (x_int <= qmax);
-    const float g_mul = gy * s;
-    const float g_in = inside ? g_mul : 0.0f;
-    a.ds_mul += gy * (q - z);
-    a.ds_div += (-g_in) * ((x / s) / s);
-    a.dz += g_in - g_mul;
-    return g_in / s;
-}
-
-__global__ __launch_bounds__(kThreads) void lsq_bwd_tensor_kernel(
-    const float4* __restrict__ x, const float4* __restrict__ gy, float4* __restrict__ dx, int64_t n4,
-    const float* __restrict__ xt, const float* __restrict__ gyt, float* __restrict__ dxt, int tail,
-    const float* __restrict__ scale_p, const void* __restrict__ zp_p, int zp_type, int mode, float g,
-    float qmin, float qmax, float* __restrict__ dscale, float* __restrict__ dzp,
-    double* __restrict__ partials, unsigned int* __restrict__ counter, int wt) {
-    const WtStore dwt(dx, wt ? n4 : 0);                   // wt: grad_x leaves through write-through stores (n4 < 2^28)
-    const QParams p = effective_params(scale_p[0], load_zp(zp_p, zp_type), mode, g);
-    const float s = p.scale, z = p.zp;
-    const int64_t stride = static_cast<int64_t>(gridDim.x) * kThreads;
-    double t_ds = 0.0, t_dz = 0.0;
-    for (int64_t i = static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x; i < n4; i += 2 * stride) {
-        const bool two = (i + stride) < n4;
-        const float4 a0 = load_stream(&x[i]);
-        const float4 b0 = load_stream(&gy[i]);
-        float4 a1 = a0, b1 = b0;
-        if (two) {
-            a1 = load_stream(&x[i + stride]);
-            b1 = load_stream(&gy[i + stride]);
-        }
-        BwdAcc acc = {0.f, 0.f, 0.f};
-        float4 o;
-        o.x = bwd_elem(a0.x, b0.x, s, z, qmin, qmax, acc);
-        o.y = bwd_elem(a0.y, b0.y, s, z, qmin, qmax, acc);
-        o.z = bwd_elem(a0.z, b0.z, s, z, qmin, qmax, acc);
-        o.w = bwd_elem(a0.w, b0.w, s, z, qmin, qmax, acc);
-        if (wt) dwt.put(i, o); else store_stream(&dx[i], o);
-        if (two) {
-            o.x = bwd_elem(a1.x, b1.x, s, z, qmin, qmax, acc);
-            o.y = bwd_elem(a1.y, b1.y, s, z, qmin, qmax, acc);
-            o.z = bwd_elem(a1.z, b1.z, s, z, qmin, qmax, acc);
-            o.w = bwd_elem(a1.w, b1.w, s, z, qmin, qmax, acc);
-            if (wt) dwt.put(i + stride, o); else store_stream(&dx[i + stride], o);
-        }
-        t_ds += static_cast<double>(acc.ds_mul) + static_cast<double>(acc.ds_div);
-        t_dz += static_cast<double>(acc.dz);
-    }
-    if (blockIdx.x == 0 && static_cast<int>(threadIdx.x) < tail) {
-        BwdAcc acc = {0.f, 0.f, 0.f};
-        dxt[threadIdx.x] = bwd_elem(xt[threadIdx.x], gyt[threadIdx.x], s, z, qmin, qmax, acc);
-        t_ds += static_cast<double>(acc.ds_mul) + static_cast<double>(acc.ds_div);
-        t_dz += static_cast<double>(acc.dz);
-    }
-    __shared__ double sh[2][kThreads / OSQ_WAVE];
-    t_ds = wave_sum(t_ds);
-    t_dz = wave_sum(t_dz);
-    const int lane = threadIdx.x & (OSQ_WAVE - 1), w = threadIdx.x / OSQ_WAVE;
-    if (lane == 0) { sh[0][w] = t_ds; sh[1][w] = t_dz; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double a = 0.0, b = 0.0;
-        for (int k = 0; k < kThreads / OSQ_WAVE; ++k) { a += sh[0][k]; b += sh[1][k]; }
-        publish_f64(&partials[2 * blockIdx.x], a);
-        publish_f64(&partials[2 * blockIdx.x + 1], b);
-    }
-    if (grid_last_block(counter, gridDim.x)) {
-        // all loads first (ordered agent-scope loads consumed one by one cost a memory round trip each),
-        // then the same lane-strided summation order as before
-        constexpr int kPer = kMaxBlocks / kThreads;
-        double pa[kPer], pb[kPer];
-#pragma unroll
-        for (int j = 0; j < kPer; ++j) {
-            const unsigned int k = threadIdx.x + j * kThreads, kc = k < gridDim.x ? k : gridDim.x - 1;
-            pa[j] = consume_f64(&partials[2 * kc]);
-            pb[j] = consume_f64(&partials[2 * kc + 1]);
-        }
-        double a = 0.0, b = 0.0;
-#pragma unroll
-        for (int j = 0; j < kPer; ++j) {
-            const bool in = threadIdx.x + j * kThreads < gridDim.x;
-            a += in ? pa[j] : 0.0;
-            b += in ? pb[j] : 0.0;
-        }
-        // fixed combination order: lane-strided partial sums, then wave tree, then waves in order
-        a = wave_sum(a);
-        b = wave_sum(b);
-        __syncthreads();
-        if (lane == 0) { sh[0][w] = a; sh[1][w] = b; }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            double sa = 0.0, sb = 0.0;
-            for (int k = 0; k < kThreads / OSQ_WAVE; ++k) { sa += sh[0][k]; sb += sh[1][k]; }
-            // grad_scale backward: d(t*g)/dt = g  (util_quant.py:70-71)
-            const double gs = (mode == OSQ_PARAM_FIXED) ? 1.0 : static_cast<double>(g);
-            if (dscale) dscale[0] = static_cast<float>(sa * gs);
-            if (dzp) dzp[0] = static_cast<float>(sb * ((mode == OSQ_PARAM_LSQPLUS) ? static_cast<double>(g) : 1.0));
-            grid_reset(counter, gridDim.x);
-        }
-    }
-}
+// The per-element rule (bwd_elem), the dense per-tensor kernel (lsq_bwd_tensor_kernel, launched here with PlainProducer: the
+// quantizer's input read as it is) and the float64 reduction that ends it are lsq_backward.h's.
+static_assert(kThreads == kBwdThreads, "lsq_bwd_tensor_kernel: one workgroup size");
 
 // osq_set_tuning("bwd_sum_order", 8) -- part of the package's strict switch: the two gradients summed the way autograd
 // sums them on the reference's CPU -- FOUR reductions, each torch's fp32 `sum` in ATen's one-thread order (aten_order.h):
@@ -754,6 +639,7 @@ __global__ void lsq_sanitize_kernel(float* __restrict__ scale, float* __restrict
 }
 
 bool stream_write_through() { return g_stream_wt != 0; }
+int lsq_backward_grid(int64_t n4) { return grid_for(n4, kThreads * 2, g_bwd_blocks); }
 
 static inline MagicDiv make_magic(int64_t d) {       // 1 <= d < 2^31
     MagicDiv v;
@@ -1110,10 +996,10 @@ extern "C" int osq_lsq_backward_per_tensor(const float* x, const float* grad_out
     const float qmin = static_cast<float>(quant_min), qmax = static_cast<float>(quant_max);
     const int64_t n4 = n / 4;
     const int tail = static_cast<int>(n - n4 * 4);
-    const int grid = grid_for(n4, kThreads * 2, g_bwd_blocks);
+    const int grid = lsq_backward_grid(n4);
     Workspace ws(workspace);
     const TimingHook th = take_timing_hook(OSQ_TIME_LSQ_BACKWARD);
-    hipExtLaunchKernelGGL(lsq_bwd_tensor_kernel, dim3(grid), dim3(kThreads), 0, st, th.start, th.stop, 0, reinterpret_cast<const float4*>(x),
+    hipExtLaunchKernelGGL(lsq_bwd_tensor_kernel<PlainProducer>, dim3(grid), dim3(kThreads), 0, st, th.start, th.stop, 0, reinterpret_cast<const float4*>(x),
                        reinterpret_cast<const float4*>(grad_out), reinterpret_cast<float4*>(grad_x), n4, x + n4 * 4,
                        grad_out + n4 * 4, grad_x + n4 * 4, tail, scale, zero_point, zp_type, mode, grad_factor, qmin, qmax,
                        grad_scale, grad_zero_point, ws.doubles(kFamLsqBackward), ws.counter(kFamLsqBackward),

@@ -14,7 +14,7 @@ constexpr int kMultiLdsWeights = 1024;    // table-driven weight launches (fake_
 // Every kernel family that finishes in its last workgroup owns a block of ticket counters and a block of partials:
 // two such kernels of DIFFERENT families may overlap on one stream (graph branches) without sharing either.
 enum WsFamily { kFamLsqBackward = 0, kFamObserveFlat = 1, kFamWideFinal = 2, kFamMseFlat = 3, kFamMseTokens = 4,
-                kFamMoments = 5, kFamHistogram = 6, kWsFamilies = 8 };
+                kFamMoments = 5, kFamHistogram = 6, kFamSiteBackward = 7, kWsFamilies = 8 };
 constexpr size_t kWsCounterBlock = 4096;                      // 33 counters used, one 64-byte line each
 constexpr size_t kWsHeaderBytes = kWsFamilies * kWsCounterBlock;
 constexpr size_t kWsScratchPerFamily = 64 * 1024;             // 2048 partials of 8 B + extras, or 256 x 32 partials (MSE grid)

@@ -1670,6 +1670,143 @@ def attention_softmax_fake_quant(scores, mask=None, *, alpha=None, divisor=None,
 
 
 # ---------------------------------------------------------------------------------------
+# the GELU and attention-probabilities sites under autograd: forward one launch, backward one launch (csrc/site_backward.hip)
+# ---------------------------------------------------------------------------------------
+
+def _grad_outputs(device, need_scale, need_zp):
+    return (torch.empty(1, dtype=torch.float32, device=device) if need_scale else None,
+            torch.empty(1, dtype=torch.float32, device=device) if need_zp else None)
+
+
+def gelu_fake_quant_backward(x, grad_out, scale, zero_point, quant_min, quant_max, mode, grad_factor,
+                             need_scale=True, need_zp=True):
+    """(dx, dscale, dzero_point) of fake_quant(F.gelu(x)) from x itself in ONE launch: gelu(x) is recomputed per element, so
+    dscale / dzero_point are word-equal to lsq_backward_per_tensor(F.gelu(x), grad_out, ...) in the order-free tier.
+    x: contiguous fp32 on the device, 16-byte aligned; mode without PARAM_SANITIZE."""
+    lib = _hip.load()
+    _hip.require_device(x, grad_out, scale, zero_point)
+    _check_f32(x, grad_out, scale)
+    if not x.is_contiguous() or x.data_ptr() % 16:
+        raise ValueError("gelu_fake_quant_backward: x must be contiguous and 16-byte aligned")
+    g = _like_layout(grad_out, x)
+    if g.data_ptr() % 16:
+        g = g.clone()
+    dx = torch.empty_like(x)
+    ds, dz = _grad_outputs(x.device, need_scale, need_zp)
+    _hip.check(lib.osq_gelu_fake_quant_backward(x.data_ptr(), g.data_ptr(), dx.data_ptr(), x.numel(), scale.data_ptr(),
+                                                zero_point.data_ptr(), _zp_type(zero_point), int(mode), float(grad_factor),
+                                                int(quant_min), int(quant_max), _hip.ptr(ds), _hip.ptr(dz),
+                                                _hip.ptr(_hip.workspace(x.device)), _hip.raw_stream(x.device)),
+               "gelu_fake_quant_backward")
+    return dx, ds, dz
+
+
+SOFTMAX_BACKWARD_MAX_COLS = 2048      # kAttnMaxCols of csrc/attention_row.h: the row in eight float4 per lane
+
+
+def attention_softmax_backward_fusable(scores, mask=None):
+    """attention_softmax_fusable and the geometry of the forward's register-resident kernel, which its backward takes
+    alone: whole float4s, at most 2048 columns, 16-byte aligned scores and mask rows."""
+    if not attention_softmax_fusable(scores, mask):
+        return False
+    if scores.shape[-1] % 4 or scores.shape[-1] > SOFTMAX_BACKWARD_MAX_COLS or scores.data_ptr() % 16:
+        return False
+    if mask is None:
+        return True
+    return mask.data_ptr() % 16 == 0 and all(s % 4 == 0 for s in mask.expand(scores.shape).stride()[:-1])
+
+
+def attention_softmax_fake_quant_backward(scores, mask, grad_out, quant, *, alpha=None, divisor=None, need_scale=True,
+                                          need_zp=True):
+    """(dscores, dscale, dzero_point) of attention_softmax_fake_quant(scores, mask, alpha=, divisor=, quant=) from its
+    inputs in ONE launch: the probabilities are recomputed in registers as the forward computes them.  quant: (scale,
+    zero_point, quant_min, quant_max, mode, grad_factor), mode without PARAM_SANITIZE.  The mask gets no gradient."""
+    lib = _hip.load()
+    _hip.require_device(scores, mask, grad_out)
+    _check_f32(grad_out)
+    if alpha is not None and divisor is not None:
+        raise ValueError("attention_softmax_fake_quant_backward: give alpha or divisor, not both")
+    if not attention_softmax_backward_fusable(scores, mask):
+        raise ValueError("attention_softmax_fake_quant_backward: needs the layout of attention_softmax_fake_quant with "
+                         "cols % 4 == 0, cols <= 2048 and 16-byte aligned scores and mask rows")
+    b, h, t, s = _as_4d(scores)
+    sb = sh = st = 0
+    if mask is not None:
+        strides = (0,) * (4 - scores.dim()) + tuple(mask.expand(scores.shape).stride())
+        sb, sh, st = strides[0], strides[1], strides[2]
+    g = _like_layout(grad_out, scores)
+    if g.data_ptr() % 16:
+        g = g.clone()
+    dscores = torch.empty_like(scores)
+    ds, dz = _grad_outputs(scores.device, need_scale, need_zp)
+    _hip.check(lib.osq_attention_softmax_fake_quant_backward(
+        scores.data_ptr(), _hip.ptr(mask), b, h, t, s, sb, sh, st, 1.0 if alpha is None else float(alpha),
+        1.0 if divisor is None else float(divisor), g.data_ptr(), dscores.data_ptr(), *_quant_group(quant),
+        _hip.ptr(ds), _hip.ptr(dz), _hip.ptr(_hip.workspace(scores.device)), _hip.raw_stream(scores.device)),
+        "attention_softmax_fake_quant_backward")
+    return dscores, ds, dz
+
+
+def _param_grads(scale, zero_point, ds, dz):
+    return (None if ds is None else ds.reshape(scale.shape)), (None if dz is None else dz.reshape(zero_point.shape))
+
+
+class _GeluFakeQuantFn(torch.autograd.Function):
+    """fake_quant(F.gelu(x)) with autograd: forward = the site's one launch, backward = one launch; only x is kept."""
+
+    @staticmethod
+    def forward(ctx, x, scale, zero_point, quant_min, quant_max, mode, grad_factor):
+        ctx.cfg = (quant_min, quant_max, mode & PARAM_MODE_MASK, grad_factor)     # PARAM_SANITIZE is forward-only
+        ctx.save_for_backward(x, scale, zero_point)
+        return gelu_fake_quant_per_tensor(x, scale, zero_point, quant_min, quant_max, mode, grad_factor)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        x, scale, zero_point = ctx.saved_tensors
+        need_s = ctx.needs_input_grad[1]
+        need_z = ctx.needs_input_grad[2] and zero_point.dtype == torch.float32
+        dx, ds, dz = gelu_fake_quant_backward(x, grad_out, scale, zero_point, *ctx.cfg, need_s, need_z)
+        return (dx if ctx.needs_input_grad[0] else None), *_param_grads(scale, zero_point, ds, dz), None, None, None, None
+
+
+class _SoftmaxFakeQuantFn(torch.autograd.Function):
+    """attention_softmax_fake_quant with autograd: forward = the site's one launch, backward = one launch; scores and the
+    mask are saved, the probabilities are not."""
+
+    @staticmethod
+    def forward(ctx, scores, mask, scale, zero_point, quant_min, quant_max, mode, grad_factor, alpha, divisor):
+        ctx.cfg = (quant_min, quant_max, mode & PARAM_MODE_MASK, grad_factor)     # PARAM_SANITIZE is forward-only
+        ctx.pre = (alpha, divisor)
+        ctx.save_for_backward(scores, mask, scale, zero_point)       # mask may be None
+        return attention_softmax_fake_quant(scores, mask, alpha=alpha, divisor=divisor,
+                                            quant=(scale, zero_point, quant_min, quant_max, mode, grad_factor))
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        scores, mask, scale, zero_point = ctx.saved_tensors
+        need_s = ctx.needs_input_grad[2]
+        need_z = ctx.needs_input_grad[3] and zero_point.dtype == torch.float32
+        dscores, ds, dz = attention_softmax_fake_quant_backward(
+            scores, mask, grad_out, (scale, zero_point) + ctx.cfg, alpha=ctx.pre[0], divisor=ctx.pre[1],
+            need_scale=need_s, need_zp=need_z)
+        return ((dscores if ctx.needs_input_grad[0] else None), None, *_param_grads(scale, zero_point, ds, dz),
+                None, None, None, None, None, None)
+
+
+def gelu_fake_quant(x, scale, zero_point, quant_min, quant_max, mode=PARAM_FIXED, grad_factor=1.0):
+    """fake_quant(F.gelu(x)) as one launch whose backward is one launch too (gelu_fake_quant_backward).  scale / zero_point:
+    the quantizer's own tensors, so that a learnable pair receives its gradients."""
+    return _GeluFakeQuantFn.apply(x, scale, zero_point, quant_min, quant_max, mode, grad_factor)
+
+
+def softmax_fake_quant(scores, mask, scale, zero_point, quant_min, quant_max, mode=PARAM_FIXED, grad_factor=1.0, *,
+                       alpha=None, divisor=None):
+    """attention_softmax_fake_quant as one launch whose backward is one launch too (attention_softmax_fake_quant_backward);
+    scores and mask as attention_softmax_backward_fusable asks.  mask must not want a gradient."""
+    return _SoftmaxFakeQuantFn.apply(scores, mask, scale, zero_point, quant_min, quant_max, mode, grad_factor, alpha, divisor)
+
+
+# ---------------------------------------------------------------------------------------
 # attention over a whole sequence: both products, mask, softmax, two quantizers in one launch
 # ---------------------------------------------------------------------------------------
 

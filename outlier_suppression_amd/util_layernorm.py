@@ -31,6 +31,14 @@ autograd (every calibration / evaluation forward):
     (profiles/attention_site_ab.txt): [32,12,384,384] 116 us against 220 us eager with fake-quant, 81 against 153 us
     softmax only; [32,12,128,128] 26 against 32 us, and slower than eager softmax only (23 against 22 us).
 
+``FUSE_BACKWARD`` (default OFF) is for the passes the four above leave alone, those with autograd on (learn_scale's Adam loop):
+the GELU site and, under ``FUSE_SOFTMAX``, the attention-probabilities site keep their one-launch forward and get a one-launch
+backward that recomputes the quantizer's input from the site's input (``ops.gelu_fake_quant`` / ``ops.softmax_fake_quant``,
+csrc/site_backward.hip): only the site's input is kept for the backward, and scale.grad / zero_point.grad of the GELU site are
+word-equal to the eager chain's.  Per-tensor quantizers in their plain quantising state, fp32, the order-free summation tier,
+no active dropout; anything else takes the eager lines and ``util_layernorm.site_backward`` says why.
+``outlier_suppression_amd.set_fast_backward(True)`` / ``OSQ_FAST_BACKWARD=1`` turn it on.
+
 Incremental decoding has a fifth, ``FUSE_DECODE_ATTENTION`` (default OFF): everything a cached decoding step's attention
 block runs after its q / k / v + append launch -- bmm, mask add, softmax, probabilities quantizer, bmm, merge heads, context
 quantizer (quant_bart.py:232-268) -- as ONE launch for the step's single query token (``ops.decode_attention_fake_quant``,
@@ -151,6 +159,79 @@ SAMPLE_NUCLEUS = False   # sample(): under the two switches above, top_k=0 with 
 SHARE_CROSS_KV = False   # generate(): beam search holds the cross-attention keys / values once per batch row and attends to them from every beam of the row in one launch (set_share_cross_kv / OSQ_SHARE_CROSS_KV=1 / generate(share_cross_kv=True))
 FAST_LM_LOSS = False     # forward(labels=...) of the BART LM wrapper: the loss through the scoring kernels -- ops.lm_loss, backward from lse alone -- instead of F.cross_entropy (tolerance-equal; set_fast_lm_loss / OSQ_FAST_LM_LOSS=1); score() uses the kernels whatever this says
 CACHE_CODES = False      # incremental decoding: new KV caches hold integer codes, one byte per element (same words read back; set_cache_codes / OSQ_CACHE_CODES=1)
+FUSE_BACKWARD = False    # autograd passes (learn_scale): the GELU site and, under FUSE_SOFTMAX, the attention-probabilities site keep their one launch and get a one-launch backward (csrc/site_backward.hip; set_fast_backward / OSQ_FAST_BACKWARD=1)
+
+
+class SiteBackwardInfo:
+    """What the one-launch sites did under autograd since ``reset()``: ``gelu`` / ``softmax`` calls that took the fused
+    function (one launch forward, one backward), ``eager`` calls that took the eager lines, and the ``reason`` of the last
+    of those -- one phrase, as the decoding switches keep theirs (``util_layernorm.site_backward``)."""
+
+    def __init__(self):
+        self.reset()
+
+    def reset(self):
+        self.gelu, self.softmax, self.eager, self.reason = 0, 0, 0, None
+
+    def __repr__(self):
+        return f"SiteBackwardInfo(gelu={self.gelu}, softmax={self.softmax}, eager={self.eager}, reason={self.reason!r})"
+
+
+site_backward = SiteBackwardInfo()
+
+
+def _site_backward_why_not(q, x, site_switch=None):
+    """What the two sites share of the reasons an autograd pass keeps the eager lines -- one phrase -- or None; ``x``: the
+    site's input.  Where the tensors live is asked last: everything before it holds for any tensor."""
+    if not FUSE_BACKWARD:
+        return "FUSE_BACKWARD is off"
+    if site_switch is not None:
+        return site_switch
+    state = _not_plain(q)
+    if state:
+        return f"the quantizer {state}"
+    if ops.reference_sum_order("bwd"):
+        return "the strict summation tier is defined on the eager tensors"
+    if x.dtype != torch.float32:
+        return "the input is not fp32"
+    if not (x.is_cuda and q.scale.is_cuda):
+        return "the input or the quantizer's parameters are not on a GPU"
+    return None
+
+
+def gelu_backward_why_not(act_fn, q, x):
+    """None when an autograd pass through the intermediate-activation site takes ops.gelu_fake_quant (one launch forward,
+    one launch backward), else the reason it takes ``q(act_fn(x))``."""
+    why = None if FUSE_ACTIVATION else "FUSE_ACTIVATION is off"
+    if why is None and FUSE_BACKWARD and not ops.is_exact_gelu(act_fn):
+        why = "the activation is not the exact GELU"
+    why = _site_backward_why_not(q, x, why)
+    if why is None and not (x.is_contiguous() and x.numel() and x.data_ptr() % 16 == 0):
+        why = "the input is not a dense, 16-byte aligned tensor"
+    return why
+
+
+def softmax_backward_why_not(q, scores4, mask, dropout=None):
+    """None when an autograd pass through the attention-probabilities site takes ops.softmax_fake_quant, else the reason
+    it takes the eager lines.  ``scores4``: the scores in their [B, h, T, S] form."""
+    why = None if FUSE_SOFTMAX else "FUSE_SOFTMAX is off"
+    if why is None and FUSE_BACKWARD:
+        if _dropout_active(dropout):
+            why = "dropout is active"
+        elif mask is not None and mask.requires_grad:
+            why = "the mask requires a gradient"
+        elif scores4.shape[-1] % 4 or scores4.shape[-1] > ops.SOFTMAX_BACKWARD_MAX_COLS:
+            why = "the row width is not a multiple of 4 up to 2048"
+    why = _site_backward_why_not(q, scores4, why)
+    if why is None and not ops.attention_softmax_backward_fusable(scores4, mask):
+        why = "the layout of scores / mask is not the register-resident kernel's"
+    return why
+
+
+def _learnable_site(q, numel):
+    """_site_record for a fused function under autograd: the quantizer's OWN scale / zero_point (a learnable pair receives its
+    gradients), then quant_min, quant_max, mode, grad_factor."""
+    return (q.scale, q.zero_point) + _site_record(q, numel)[2:]
 
 
 class _Numel:
@@ -302,6 +383,15 @@ def activation_fake_quant(act_fn, quantizer, hidden_states, observation_mask=Non
             and hidden_states.is_contiguous() and hidden_states.numel() and hidden_states.data_ptr() % 16 == 0
             and q.scale.is_cuda and ops.is_exact_gelu(act_fn)):
         return ops.gelu_fake_quant_per_tensor(hidden_states, *_site_record(q, hidden_states.numel()))
+    if torch.is_grad_enabled():
+        # FUSE_BACKWARD: the same launch under autograd, its backward one launch as well; anything it does not take
+        # keeps the two steps below, with the reason in site_backward
+        why = gelu_backward_why_not(act_fn, q, hidden_states)
+        if why is None:
+            site_backward.gelu += 1
+            return ops.gelu_fake_quant(hidden_states, *_learnable_site(q, hidden_states.numel()))
+        site_backward.eager += 1
+        site_backward.reason = why
     hidden_states = act_fn(hidden_states)
     if q is not None:
         hidden_states = q(hidden_states, observation_mask, 1)
@@ -635,6 +725,16 @@ def attention_probs_fake_quant(quantizer, scores, mask, alpha=None, divisor=None
         if q is not None and quant is None:
             probs = q(probs, observation_mask, seq_pos)
         return probs
+    if torch.is_grad_enabled():
+        # FUSE_BACKWARD (behind FUSE_SOFTMAX): the site's one launch under autograd, its backward one launch that
+        # recomputes the probabilities; anything it does not take keeps the lines below, with the reason in site_backward
+        why = softmax_backward_why_not(quantizer, scores4, mask, dropout)
+        if why is None:
+            site_backward.softmax += 1
+            return ops.softmax_fake_quant(scores4, mask, *_learnable_site(quantizer, scores.numel()), alpha=alpha,
+                                          divisor=divisor).view(scores.shape)
+        site_backward.eager += 1
+        site_backward.reason = why
     if alpha is not None:
         v = torch.add(mask, scores, alpha=alpha) if mask is not None else scores * alpha
     else:
