@@ -49,7 +49,7 @@ typedef void* osq_stream;
  *     osq_sample_nucleus_group, osq_sample_nucleus_group_at, osq_sample_uniforms_group, osq_token_logprob_workspace_bytes,
  *     osq_token_logprob, osq_token_logprob_backward, osq_attention_fake_quant, osq_attention_fake_quant_int,
  *     osq_attention_fake_quant_shared, osq_attention_fake_quant_int_shared, osq_gelu_fake_quant_backward,
- *     osq_attention_softmax_fake_quant_backward. */
+ *     osq_attention_softmax_fake_quant_backward, osq_residual_layernorm_fake_quant_backward. */
 #define OSQ_ABI_VERSION 10
 
 typedef enum osq_status {
@@ -351,6 +351,33 @@ int osq_attention_softmax_fake_quant_backward(const float* scores, const float* 
                                               int mode, float grad_factor, int quant_min, int quant_max,
                                               float* grad_scale, float* grad_zero_point,
                                               void* workspace, osq_stream stream);
+
+/* Backward of osq_residual_layernorm_fake_quant from the site's INPUTS, in one launch, one wave per row with the row in
+ * registers.  x / hidden / gamma / weight / bias / eps / rows / cols as given to the forward (each of hidden, gamma, weight,
+ * bias nullable, gamma read only with hidden); per row:
+ *     r, mean, rstd, xhat = (r - mean) * rstd, n = xhat * weight + bias      recomputed by the forward's own device code
+ *                                                                            (csrc/layernorm_row.h): the words it quantised
+ *     dn, the three sum terms              the per-element rule of osq_lsq_backward_per_tensor on (n, grad_out)
+ *     dxhat = dn * weight
+ *     c1 = sum_j dxhat_j ;  c2 = sum_j dxhat_j * xhat'_j ;  dr_j = rstd' * ((dxhat_j - c1 / cols) - xhat'_j * (c2 / cols))
+ *                                          float64, rounded to fp32 once, with xhat' / rstd' the float64 statistics of the fp32
+ *                                          row r -- one wave round of four float64 sums gives them together with c1 and c2
+ * grad_hidden = dr; grad_x = dr * gamma, or dr without gamma or without hidden.  Each of grad_x, grad_hidden, grad_scale[1],
+ * grad_zero_point[1] is nullable and skipped when null; grad_hidden needs hidden.  Without gamma the two tensor gradients are
+ * the same words: pass ONE pointer (as grad_x, or the same as both) and hand it to both inputs.  gamma, weight and bias receive
+ * no gradient.  scale == NULL (with zero_point, grad_scale and grad_zero_point NULL): the site has no fake-quant, dn = grad_out.
+ * The parameter sums: fp32 per lane over a row, float64 from there, workgroup partials combined in block order
+ * by the workgroup that arrives last -- no atomics on floating-point data, the same words on every run; workspace family and
+ * mode as above.  rows == 0 writes zero sums.  cols % 4 == 0, cols <= 2048, 16-byte aligned contiguous operands -- anything
+ * else is OSQ_ERR_UNSUPPORTED (nothing launched: the caller keeps the eager lines). */
+int osq_residual_layernorm_fake_quant_backward(const float* x, const float* hidden, const float* gamma,
+                                               const float* weight, const float* bias, double eps,
+                                               int64_t rows, int64_t cols, const float* grad_out,
+                                               float* grad_x, float* grad_hidden,
+                                               const float* scale, const void* zero_point, int zp_type,
+                                               int mode, float grad_factor, int quant_min, int quant_max,
+                                               float* grad_scale, float* grad_zero_point,
+                                               void* workspace, osq_stream stream);
 
 /* ------------------------------------------------------------------ observers */
 
@@ -822,7 +849,7 @@ int osq_gamma_residual(const float* input, const float* hidden, const float* gam
  * rows x cols contiguous fp32, cols % 4 == 0, cols <= 4096, 16-byte aligned operands (else
  * OSQ_ERR_UNSUPPORTED and the caller keeps the eager sequence).  mode / grad_factor / zp_type as in
  * osq_fake_quant_per_tensor, including OSQ_PARAM_SANITIZE.  8 B per element (12 with a residual)
- * instead of 24-32.  Inference only: autograd passes use the eager sequence. */
+ * instead of 24-32.  Its backward, for rows of up to 2048 columns: osq_residual_layernorm_fake_quant_backward. */
 int osq_residual_layernorm_fake_quant(const float* x, const float* hidden, const float* gamma,
                                       const float* weight, const float* bias, double eps,
                                       float* y, int64_t rows, int64_t cols,

@@ -229,6 +229,22 @@ def set_fast_backward(on=True):
     util_layernorm.FUSE_BACKWARD = bool(on)
 
 
+def set_fast_layernorm_backward(on=True):
+    """Autograd passes (learn_scale) keep the one-launch LayerNorm site -- residual, LayerNorm, affine pair or split shift,
+    output fake-quant -- with a one-launch backward that recomputes the row from the site's own inputs
+    (util_layernorm.FUSE_LAYERNORM_BACKWARD; csrc/layernorm_backward.hip; behind set_fast; default OFF).  A switch of its own,
+    not set_fast_backward's: this site's forward is tolerance-equal to torch's LayerNorm, not bit-equal.  A call the kernel
+    does not take runs the eager lines (``util_layernorm.layernorm_backward``: fused, eager, reason).
+    OSQ_FAST_LAYERNORM_BACKWARD=1 turns it on at load."""
+    from . import util_layernorm
+    util_layernorm.FUSE_LAYERNORM_BACKWARD = bool(on)
+
+
+def fast_layernorm_backward_from_environment(environ=None):
+    """What OSQ_FAST_LAYERNORM_BACKWARD asks for: unset, empty or "0" -> False, anything else -> True."""
+    return _env_on("OSQ_FAST_LAYERNORM_BACKWARD", environ)
+
+
 def fast_backward_from_environment(environ=None):
     """What OSQ_FAST_BACKWARD asks for: unset, empty or "0" -> False, anything else -> True."""
     return _env_on("OSQ_FAST_BACKWARD", environ)
@@ -304,7 +320,8 @@ def reset_tier(_lib=None):
     that kernel call takes a nucleus over the whole vocabulary too (unset: off); OSQ_SHARE_CROSS_KV=1 beam search holds the
     cross-attention keys / values once per batch row (unset: off); OSQ_FAST_LM_LOSS=1 the BART LM wrapper's loss through the
     scoring kernels (unset: off); OSQ_FAST_BACKWARD=1 autograd passes keep the one-launch GELU and attention-probabilities
-    sites, with one-launch backwards (unset: off)."""
+    sites, with one-launch backwards (unset: off); OSQ_FAST_LAYERNORM_BACKWARD=1 they keep the one-launch LayerNorm site too,
+    with its one-launch backward (unset: off)."""
     import os
     width = int(os.environ.get("OSQ_STRICT_SIMD", "8"))
     strict = os.environ.get("OSQ_STRICT", "")
@@ -327,7 +344,8 @@ _SWITCHES = ((set_cache_codes, "OSQ_CACHE_CODES"), (set_graph_decode, "OSQ_GRAPH
              (set_greedy_graph, "OSQ_GREEDY_GRAPH"), (set_sample_advance, "OSQ_SAMPLE_ADVANCE"),
              (set_sample_graph, "OSQ_SAMPLE_GRAPH"), (set_sample_nucleus, "OSQ_SAMPLE_NUCLEUS"),
              (set_share_cross_kv, "OSQ_SHARE_CROSS_KV"), (set_fast_lm_loss, "OSQ_FAST_LM_LOSS"),
-             (set_fast_attention_int, "OSQ_FAST_ATTENTION_INT"), (set_fast_backward, "OSQ_FAST_BACKWARD"))
+             (set_fast_attention_int, "OSQ_FAST_ATTENTION_INT"), (set_fast_backward, "OSQ_FAST_BACKWARD"),
+             (set_fast_layernorm_backward, "OSQ_FAST_LAYERNORM_BACKWARD"))
 _apply_environment = reset_tier
 
 

@@ -113,6 +113,8 @@ SIGNATURES = {
     "osq_gelu_fake_quant_backward": (_I, [_P, _P, _P, _L, _P, _P, _I, _I, _F, _I, _I, _P, _P, _P, _P]),
     "osq_attention_softmax_fake_quant_backward": (_I, [_P, _P, _L, _L, _L, _L, _L, _L, _L, _F, _F, _P, _P, _P, _P, _I, _I, _F, _I, _I,
                                                        _P, _P, _P, _P]),
+    "osq_residual_layernorm_fake_quant_backward": (_I, [_P, _P, _P, _P, _P, _D, _L, _L, _P, _P, _P, _P, _P, _I, _I, _F, _I, _I,
+                                                        _P, _P, _P, _P]),
     "osq_ordered_sum_scratch_bytes": (ctypes.c_size_t, [_L, _I]),
     "osq_lsq_backward_per_tensor_ordered": (_I, [_P, _P, _P, _L, _P, _P, _I, _I, _F, _I, _I, _P, _P, _I, _P, ctypes.c_size_t, _P, _P]),
     "osq_lsq_backward_per_channel": (_I, [_P, _P, _P, _L, _L, _L, _P, _P, _I, _I, _F, _I, _I, _P, _P, _I, _P]),

@@ -13,34 +13,16 @@
 // every arithmetic step is individually rounded (-ffp-contract=off) in the order of the eager ops:
 //     a = input*gamma; r = a + hidden; t = (r - mean) * rstd; t = t*w; t = t + b; then quantize_value.
 // The normalisation is not bit-comparable with torch's own kernel (Welford on the GPU, a different
-// blocked summation on the CPU): callers that need the eager sequence keep using it (autograd passes do).
+// blocked summation on the CPU): callers that need the eager sequence keep using it (autograd passes do, unless
+// FUSE_LAYERNORM_BACKWARD hands them this launch and layernorm_backward.hip's).
 #include <string>
 #include <hip/hip_ext.h>
-#include "osq_device.h"
-#include "osq_host.h"
+#include "layernorm_row.h"
 
 namespace osq {
 
-constexpr int kLnThreads = 256;
-constexpr int kLnWaves = kLnThreads / OSQ_WAVE;
 OSQ_AB_KNOB(int, g_ln_blocks, 1024);      // grid cap (osq_set_tuning("ln_blocks", n)); rows are grid-strided above it.  tools/bwd_ab.py on MI355X,
                                     // [256,128,768]: one row per wave (8192 workgroups) 58.2 us, 2048: 51.6, 1024: 51.2, 768: 51.1, 512: 60.0; [32,384,768]: 23.6 -> 21.1
-
-struct LnArgs {
-    const float4* x;
-    const float4* hidden;     // nullable: no residual
-    const float4* gamma;      // nullable: plain residual add (only read when hidden != NULL)
-    const float4* weight;     // nullable: no elementwise scale
-    const float4* bias;       // nullable
-    float4* y;
-    int64_t rows;
-    int cols4;
-    float inv_cols, eps;
-    float* scale;             // nullable: no fake-quant (written only under OSQ_PARAM_SANITIZE)
-    void* zero_point;
-    int zp_type, mode;
-    float grad_factor, qmin, qmax;
-};
 
 template <int R>
 __global__ __launch_bounds__(kLnThreads) void residual_layernorm_fq_kernel(LnArgs a) {
@@ -49,68 +31,27 @@ __global__ __launch_bounds__(kLnThreads) void residual_layernorm_fq_kernel(LnArg
     const int64_t nwaves = static_cast<int64_t>(gridDim.x) * kLnWaves;
     QParams p{1.f, 0.f};
     if (a.scale) p = tensor_params(a.scale, a.zero_point, a.zp_type, a.mode, a.grad_factor, a.qmin, a.qmax);
-    // per-column operands stay in registers across the rows of this wave while the row is short (<= 1024
-    // columns: every LayerNorm of BERT / RoBERTa / BART); longer rows re-read them (L1/L2 hits) per row
-    constexpr bool KEEP = R <= 4;
-    constexpr int RK = KEEP ? R : 1;
+    // the row's loads, residual, moments and per-element steps are layernorm_row.h's: the backward recomputes them word for word
+    constexpr int RK = LnKeep<R>::regs;
     float4 g[RK], w[RK], b[RK];
-    if (KEEP) {
-#pragma unroll
-        for (int k = 0; k < RK; ++k) {
-            const int c = lane + k * OSQ_WAVE, cc = c < a.cols4 ? c : a.cols4 - 1;
-            g[k] = (a.hidden && a.gamma) ? a.gamma[cc] : make_float4(1.f, 1.f, 1.f, 1.f);
-            w[k] = a.weight ? a.weight[cc] : make_float4(1.f, 1.f, 1.f, 1.f);
-            b[k] = a.bias ? a.bias[cc] : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-    }
+    ln_load_cols<R>(a, lane, g, w, b);
     for (int64_t row = wave0; row < a.rows; row += nwaves) {
-        const float4* xr = a.x + row * a.cols4;
-        const float4* hr = a.hidden ? a.hidden + row * a.cols4 : nullptr;
         float4 v[R], h[R];
-#pragma unroll
-        for (int k = 0; k < R; ++k) {
-            const int c = lane + k * OSQ_WAVE, cc = c < a.cols4 ? c : a.cols4 - 1;
-            v[k] = load_stream(xr + cc);
-            if (hr) h[k] = load_stream(hr + cc);
-        }
-        float sum = 0.f;
-#pragma unroll
-        for (int k = 0; k < R; ++k) {
-            if (hr) {
-                if (a.gamma) {
-                    const int c = lane + k * OSQ_WAVE;
-                    const float4 gk = KEEP ? g[KEEP ? k : 0] : a.gamma[c < a.cols4 ? c : a.cols4 - 1];
-                    v[k].x *= gk.x; v[k].y *= gk.y; v[k].z *= gk.z; v[k].w *= gk.w;
-                }
-                v[k].x += h[k].x; v[k].y += h[k].y; v[k].z += h[k].z; v[k].w += h[k].w;
-            }
-            if (lane + k * OSQ_WAVE < a.cols4) sum += (v[k].x + v[k].y) + (v[k].z + v[k].w);
-        }
-        const float mean = wave_sum_f32(sum) * a.inv_cols;
-        float sq = 0.f;
-#pragma unroll
-        for (int k = 0; k < R; ++k) {
-            if (lane + k * OSQ_WAVE < a.cols4) {
-                const float dx = v[k].x - mean, dy = v[k].y - mean, dz = v[k].z - mean, dw = v[k].w - mean;
-                sq += (dx * dx + dy * dy) + (dz * dz + dw * dw);
-            }
-        }
-        const float var = wave_sum_f32(sq) * a.inv_cols;
-        const float rstd = 1.0f / sqrtf(var + a.eps);
+        ln_load_row<R>(a, a.hidden != nullptr, row, lane, v, h);
+        float mean, rstd;
+        ln_row_moments<R>(a, a.hidden != nullptr, lane, v, h, g, mean, rstd);
         float4* yr = a.y + row * a.cols4;
 #pragma unroll
         for (int k = 0; k < R; ++k) {
             const int c = lane + k * OSQ_WAVE;
             if (c < a.cols4) {
                 float t[4] = {v[k].x, v[k].y, v[k].z, v[k].w};
-                const float4 wk = KEEP ? w[KEEP ? k : 0] : (a.weight ? a.weight[c] : make_float4(1.f, 1.f, 1.f, 1.f));
-                const float4 bk = KEEP ? b[KEEP ? k : 0] : (a.bias ? a.bias[c] : make_float4(0.f, 0.f, 0.f, 0.f));
+                const float4 wk = ln_row_weight<R>(a, w, k, c);
+                const float4 bk = ln_row_bias<R>(a, b, k, c);
                 const float ww[4] = {wk.x, wk.y, wk.z, wk.w}, bb[4] = {bk.x, bk.y, bk.z, bk.w};
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    float u = (t[e] - mean) * rstd;
-                    if (a.weight) u = u * ww[e];
-                    if (a.bias) u = u + bb[e];
+                    float u = ln_affine(a, ln_xhat(t[e], mean, rstd), ww[e], bb[e]);
                     if (a.scale) u = dequantize_value(quantize_value(u, p.scale, p.zp, a.qmin, a.qmax), p.scale, p.zp);
                     t[e] = u;
                 }

@@ -1807,6 +1807,89 @@ def softmax_fake_quant(scores, mask, scale, zero_point, quant_min, quant_max, mo
 
 
 # ---------------------------------------------------------------------------------------
+# the residual + LayerNorm + fake-quant site under autograd: forward one launch, backward one launch (csrc/layernorm_backward.hip)
+# ---------------------------------------------------------------------------------------
+
+LAYERNORM_BACKWARD_MAX_COLS = 2048      # kLnBwdMaxCols of csrc/layernorm_backward.hip: the row in eight float4 per lane
+LAYERNORM_BACKWARD_GRID_ROWS = 4096     # kLnBwdBlocks workgroups of four waves: the rows of one grid stride
+
+
+def layernorm_backward_fusable(x, *operands):
+    """layernorm_fusable and the 2048-column limit of the site's backward."""
+    return layernorm_fusable(x, *operands) and x.shape[-1] <= LAYERNORM_BACKWARD_MAX_COLS
+
+
+def residual_layernorm_fake_quant_backward(x, hidden, gamma, weight, bias, eps, grad_out, quant, need_x=True, need_hidden=True,
+                                           need_scale=True, need_zp=True):
+    """(dx, dhidden, dscale, dzero_point) of residual_layernorm_fake_quant(x, hidden, gamma, weight, bias, eps, quant) from
+    its inputs in ONE launch: r, the row moments and the quantizer's input are recomputed in registers as the forward
+    computes them.  quant: (scale, zero_point, quant_min, quant_max, mode, grad_factor), mode without PARAM_SANITIZE, or None
+    (a site without fake-quant: no parameter gradients).  A gradient that is not needed is None (dhidden also when hidden is None); without gamma dx and dhidden are ONE tensor.
+    gamma, weight and bias get no gradient."""
+    lib = _hip.load()
+    _hip.require_device(x, hidden, gamma, weight, bias, grad_out)
+    _check_f32(grad_out)
+    if hidden is not None and hidden.shape != x.shape:
+        raise ValueError("residual_layernorm_fake_quant_backward: hidden must have x's shape")
+    if not layernorm_backward_fusable(x, hidden, gamma, weight, bias):
+        raise ValueError("residual_layernorm_fake_quant_backward: needs contiguous fp32 operands, 16-byte aligned, with "
+                         "cols % 4 == 0 and cols <= 2048")
+    cols = x.shape[-1]
+    for name, t in (("gamma", gamma), ("weight", weight), ("bias", bias)):
+        if t is not None and t.numel() != cols:
+            raise ValueError(f"residual_layernorm_fake_quant_backward: {name} must have {cols} entries")
+    g = _like_layout(grad_out, x)
+    if g.data_ptr() % 16:
+        g = g.clone()
+    need_hidden = need_hidden and hidden is not None
+    dx = torch.empty_like(x) if need_x else None
+    if need_hidden and need_x and gamma is None:
+        dh = dx                                     # the same words: stored once
+    else:
+        dh = torch.empty_like(x) if need_hidden else None
+    ds, dz = _grad_outputs(x.device, need_scale and quant is not None, need_zp and quant is not None)
+    _hip.check(lib.osq_residual_layernorm_fake_quant_backward(
+        x.data_ptr(), _hip.ptr(hidden), _hip.ptr(gamma), _hip.ptr(weight), _hip.ptr(bias), float(eps), x.numel() // cols, cols,
+        g.data_ptr(), _hip.ptr(dx), _hip.ptr(dh), *_quant_group(quant), _hip.ptr(ds), _hip.ptr(dz),
+        _hip.ptr(_hip.workspace(x.device)), _hip.raw_stream(x.device)), "residual_layernorm_fake_quant_backward")
+    return dx, dh, ds, dz
+
+
+class _ResidualLayerNormFakeQuantFn(torch.autograd.Function):
+    """residual_layernorm_fake_quant with autograd: forward = the site's one launch, backward = one launch; the site's
+    operands are saved, r and the normalised tensor are not."""
+
+    @staticmethod
+    def forward(ctx, x, hidden, gamma, weight, bias, eps, scale, zero_point, quant_min, quant_max, mode, grad_factor):
+        ctx.cfg = (quant_min, quant_max, mode & PARAM_MODE_MASK, grad_factor)     # PARAM_SANITIZE is forward-only
+        ctx.eps = eps
+        ctx.save_for_backward(x, hidden, gamma, weight, bias, scale, zero_point)  # each but x may be None (scale: no fake-quant)
+        return residual_layernorm_fake_quant(x, hidden, gamma, weight, bias, eps,
+                                             None if scale is None else (scale, zero_point, quant_min, quant_max, mode, grad_factor))
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        x, hidden, gamma, weight, bias, scale, zero_point = ctx.saved_tensors
+        need_s = ctx.needs_input_grad[6]
+        need_z = ctx.needs_input_grad[7] and zero_point.dtype == torch.float32
+        dx, dh, ds, dz = residual_layernorm_fake_quant_backward(
+            x, hidden, gamma, weight, bias, ctx.eps, grad_out, None if scale is None else (scale, zero_point) + ctx.cfg,
+            need_x=ctx.needs_input_grad[0], need_hidden=ctx.needs_input_grad[1], need_scale=need_s, need_zp=need_z)
+        grads = (None, None) if scale is None else _param_grads(scale, zero_point, ds, dz)
+        return dx, dh, None, None, None, None, *grads, None, None, None, None
+
+
+def residual_layernorm_fake_quant_autograd(x, hidden, gamma, weight, bias, eps, scale=None, zero_point=None, quant_min=0,
+                                           quant_max=1, mode=PARAM_FIXED, grad_factor=1.0):
+    """residual_layernorm_fake_quant as one launch whose backward is one launch too
+    (residual_layernorm_fake_quant_backward); operands as layernorm_backward_fusable asks.  scale / zero_point: the
+    quantizer's own tensors, so that a learnable pair receives its gradients; scale None: a site without fake-quant.  gamma,
+    weight and bias must not want a gradient."""
+    return _ResidualLayerNormFakeQuantFn.apply(x, hidden, gamma, weight, bias, eps, scale, zero_point, quant_min, quant_max,
+                                               mode, grad_factor)
+
+
+# ---------------------------------------------------------------------------------------
 # attention over a whole sequence: both products, mask, softmax, two quantizers in one launch
 # ---------------------------------------------------------------------------------------
 

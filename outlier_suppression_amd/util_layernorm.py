@@ -39,6 +39,16 @@ word-equal to the eager chain's.  Per-tensor quantizers in their plain quantisin
 no active dropout; anything else takes the eager lines and ``util_layernorm.site_backward`` says why.
 ``outlier_suppression_amd.set_fast_backward(True)`` / ``OSQ_FAST_BACKWARD=1`` turn it on.
 
+``FUSE_LAYERNORM_BACKWARD`` (default OFF) does the same for the LayerNorm site, behind ``FUSE_LAYERNORM`` and with a switch of
+its own because this site's forward is tolerance-equal to torch's LayerNorm, not bit-equal (see above): with autograd on,
+``residual_layernorm``, ``QuantizedLayerNorm`` and ``QuantizedSplitLayerNorm`` keep the site's one launch and get a one-launch
+backward that recomputes the residual, the row moments and the quantizer's input from the site's inputs
+(``ops.residual_layernorm_fake_quant_autograd``, csrc/layernorm_backward.hip); neither r nor the normalised tensor is kept.
+gamma, the LayerNorm's weight / bias and the split form's bias must be frozen (learn_scale freezes them), rows are multiples
+of 4 up to 2048 columns; otherwise as ``FUSE_BACKWARD``.  Anything else takes the eager lines and
+``util_layernorm.layernorm_backward`` says why.  ``outlier_suppression_amd.set_fast_layernorm_backward(True)`` /
+``OSQ_FAST_LAYERNORM_BACKWARD=1`` turn it on; measured times are in profiles/layernorm_backward_ab.txt and README.
+
 Incremental decoding has a fifth, ``FUSE_DECODE_ATTENTION`` (default OFF): everything a cached decoding step's attention
 block runs after its q / k / v + append launch -- bmm, mask add, softmax, probabilities quantizer, bmm, merge heads, context
 quantizer (quant_bart.py:232-268) -- as ONE launch for the step's single query token (``ops.decode_attention_fake_quant``,
@@ -160,6 +170,7 @@ SHARE_CROSS_KV = False   # generate(): beam search holds the cross-attention key
 FAST_LM_LOSS = False     # forward(labels=...) of the BART LM wrapper: the loss through the scoring kernels -- ops.lm_loss, backward from lse alone -- instead of F.cross_entropy (tolerance-equal; set_fast_lm_loss / OSQ_FAST_LM_LOSS=1); score() uses the kernels whatever this says
 CACHE_CODES = False      # incremental decoding: new KV caches hold integer codes, one byte per element (same words read back; set_cache_codes / OSQ_CACHE_CODES=1)
 FUSE_BACKWARD = False    # autograd passes (learn_scale): the GELU site and, under FUSE_SOFTMAX, the attention-probabilities site keep their one launch and get a one-launch backward (csrc/site_backward.hip; set_fast_backward / OSQ_FAST_BACKWARD=1)
+FUSE_LAYERNORM_BACKWARD = False    # autograd passes (learn_scale): a LayerNorm site keeps its one launch and gets a one-launch backward (csrc/layernorm_backward.hip; behind FUSE_LAYERNORM; set_fast_layernorm_backward / OSQ_FAST_LAYERNORM_BACKWARD=1)
 
 
 class SiteBackwardInfo:
@@ -180,13 +191,29 @@ class SiteBackwardInfo:
 site_backward = SiteBackwardInfo()
 
 
-def _site_backward_why_not(q, x, site_switch=None):
-    """What the two sites share of the reasons an autograd pass keeps the eager lines -- one phrase -- or None; ``x``: the
-    site's input.  Where the tensors live is asked last: everything before it holds for any tensor."""
-    if not FUSE_BACKWARD:
-        return "FUSE_BACKWARD is off"
-    if site_switch is not None:
-        return site_switch
+class LayerNormBackwardInfo:
+    """What the LayerNorm sites did under autograd since ``reset()``: ``fused`` calls that took the autograd function (one
+    launch forward, one backward), ``eager`` calls that took the eager lines, and the ``reason`` of the last of those
+    (``util_layernorm.layernorm_backward``).  A record of its own: ``site_backward`` is not touched by this site."""
+
+    def __init__(self):
+        self.reset()
+
+    def reset(self):
+        self.fused, self.eager, self.reason = 0, 0, None
+
+    def __repr__(self):
+        return f"LayerNormBackwardInfo(fused={self.fused}, eager={self.eager}, reason={self.reason!r})"
+
+
+layernorm_backward = LayerNormBackwardInfo()
+
+
+def _autograd_site_why_not(q, x, first=None):
+    """What every one-launch site under autograd asks of its quantizer, the summation tier and its input ``x`` once its own
+    switches are on -- one phrase, or None.  ``first``: a reason the caller already has."""
+    if first is not None:
+        return first
     state = _not_plain(q)
     if state:
         return f"the quantizer {state}"
@@ -194,9 +221,63 @@ def _site_backward_why_not(q, x, site_switch=None):
         return "the strict summation tier is defined on the eager tensors"
     if x.dtype != torch.float32:
         return "the input is not fp32"
+    return None
+
+
+def _off_gpu(q, x):
+    """Where the tensors live is asked last: everything before it holds for any tensor."""
     if not (x.is_cuda and q.scale.is_cuda):
         return "the input or the quantizer's parameters are not on a GPU"
     return None
+
+
+def _site_backward_why_not(q, x, site_switch=None):
+    """What the two sites share of the reasons an autograd pass keeps the eager lines -- one phrase -- or None; ``x``: the
+    site's input."""
+    if not FUSE_BACKWARD:
+        return "FUSE_BACKWARD is off"
+    return _autograd_site_why_not(q, x, site_switch) or _off_gpu(q, x)
+
+
+class _NoQuantizer:
+    """Answers what the reasons ask of a quantizer for a site that has none by construction: plain, and wherever x is."""
+    ch_axis, fake_quant_enabled, observer_enabled = -1, 1, 0
+
+    class scale:
+        is_cuda = True
+
+
+_NO_QUANTIZER = _NoQuantizer()
+
+
+def _dense16(t):
+    return t.dtype == torch.float32 and t.is_contiguous() and t.data_ptr() % 16 == 0
+
+
+def layernorm_backward_why_not(q, x, hidden=None, gamma=None, weight=None, bias=None, quantized=True):
+    """None when an autograd pass through a LayerNorm site takes ops.residual_layernorm_fake_quant_autograd (one launch
+    forward, one launch backward), else the reason it takes the eager lines.  ``q``: the site's output quantizer; ``x`` /
+    ``hidden``: the shortcut and the residual's other input (None: a lone LayerNorm); ``gamma`` / ``weight`` / ``bias``: the
+    parameters themselves (each may be None), which get no gradient from the launch.  ``quantized`` False: the site has no
+    output quantizer by construction (qoutput=False) -- the launch then only normalises and ``q`` is not asked."""
+    if not quantized:
+        q = _NO_QUANTIZER
+    if not FUSE_LAYERNORM_BACKWARD:
+        return "FUSE_LAYERNORM_BACKWARD is off"
+    why = None if FUSE_LAYERNORM else "FUSE_LAYERNORM is off"
+    if why is None and any(p is not None and p.requires_grad for p in (gamma, weight, bias)):
+        why = "a LayerNorm parameter requires a gradient"
+    why = _autograd_site_why_not(q, x, why)
+    if why is None and (x.dim() < 2 or x.shape[-1] % 4 or x.shape[-1] > ops.LAYERNORM_BACKWARD_MAX_COLS):
+        why = "the row width is not a multiple of 4 up to 2048"
+    if why is None and not (x.numel() and (hidden is None or hidden.shape == x.shape)
+                            and all(_dense16(t) for t in (x, hidden, gamma, weight, bias) if t is not None)):
+        why = "the operands are not dense, 16-byte aligned fp32 tensors of the site's shape"
+    if why is None:
+        why = _off_gpu(q, x)
+    if why is None and not ops.layernorm_backward_fusable(x, hidden, gamma, weight, bias):
+        why = "the operands are not dense, 16-byte aligned fp32 tensors of the site's shape"
+    return why
 
 
 def gelu_backward_why_not(act_fn, q, x):
@@ -276,12 +357,32 @@ def _can_fuse(x, *operands):
     return (FUSE_LAYERNORM and not torch.is_grad_enabled() and x.dim() >= 2 and ops.layernorm_fusable(x, *operands))
 
 
+def _autograd_site(mod, x, hidden, gamma, weight, bias, eps):
+    """A LayerNorm site under autograd: the one-launch pair when layernorm_backward_why_not has no objection, else None with
+    the reason in ``layernorm_backward`` -- the caller then runs its eager lines.  gamma / weight / bias: the parameters."""
+    q = mod.layernorm_post_act_fake_quantize if mod.qoutput else None
+    why = layernorm_backward_why_not(q, x, hidden, gamma, weight, bias, quantized=mod.qoutput)
+    if why is not None:
+        layernorm_backward.eager += 1
+        layernorm_backward.reason = why
+        return None
+    layernorm_backward.fused += 1
+    return ops.residual_layernorm_fake_quant_autograd(x, hidden, gamma, weight, bias, eps,
+                                                      *(_learnable_site(q, x.numel()) if mod.qoutput else ()))
+
+
 def residual_layernorm(residual, layernorm, shortcut, hidden_states, observation_mask=None):
     """``layernorm(residual(shortcut, hidden_states), observation_mask)`` -- the pair every transformer block ends
-    its two halves with (quant_bert.py:211-216, 298-303; quant_bart.py:342-353) -- as one launch when possible."""
+    its two halves with (quant_bert.py:211-216, 298-303; quant_bart.py:342-353) -- as one launch when possible: with
+    autograd off under FUSE_LAYERNORM, with autograd on under FUSE_LAYERNORM_BACKWARD as well."""
     gamma = residual.gamma.data if residual.mul_gamma else None
     if shortcut.shape == hidden_states.shape and _can_fuse(shortcut, hidden_states, gamma):
         return layernorm.forward_fused(shortcut, hidden_states, gamma, observation_mask)
+    if torch.is_grad_enabled() and isinstance(layernorm, (QuantizedLayerNorm, QuantizedSplitLayerNorm)):
+        y = layernorm.forward_autograd(shortcut, hidden_states, residual.gamma if residual.mul_gamma else None)
+        if y is not None:
+            return y
+        return layernorm(residual(shortcut, hidden_states), observation_mask, _fused=False)     # the site is counted once
     return layernorm(residual(shortcut, hidden_states), observation_mask)
 
 
@@ -304,9 +405,20 @@ class QuantizedLayerNorm(QuantizedModule):
         return _fused_site(self, x, hidden, gamma, None if ln.weight is None else ln.weight.data,
                            None if ln.bias is None else ln.bias.data, ln.eps, observation_mask)
 
+    def forward_autograd(self, x, hidden=None, gamma=None):
+        """The site under autograd (FUSE_LAYERNORM_BACKWARD), or None: the caller runs the eager lines."""
+        ln = self.layernorm
+        if not (isinstance(ln, nn.LayerNorm) and tuple(ln.normalized_shape) == tuple(x.shape[-1:])):
+            return None
+        return _autograd_site(self, x, hidden, gamma, ln.weight, ln.bias, ln.eps)
+
     def forward(self, hidden_states, observation_mask=None, _fused=True):
         if _fused and isinstance(self.layernorm, nn.LayerNorm) and _can_fuse(hidden_states):
             return self.forward_fused(hidden_states, None, None, observation_mask)
+        if _fused and torch.is_grad_enabled():
+            y = self.forward_autograd(hidden_states)
+            if y is not None:
+                return y
         hidden_states = self.layernorm(hidden_states)
         if self.qoutput:
             hidden_states = self.layernorm_post_act_fake_quantize(hidden_states, observation_mask, 1)
@@ -341,9 +453,19 @@ class QuantizedSplitLayerNorm(QuantizedModule):
             return self.forward(x, observation_mask, _fused=False)
         return _fused_site(self, x, hidden, gamma, None, self.bias.data, self.layernorm.eps, observation_mask)
 
+    def forward_autograd(self, x, hidden=None, gamma=None):
+        """The site under autograd (FUSE_LAYERNORM_BACKWARD), or None: the caller runs the eager lines."""
+        if tuple(self.layernorm.normalized_shape) != tuple(x.shape[-1:]):
+            return None
+        return _autograd_site(self, x, hidden, gamma, None, self.bias, self.layernorm.eps)
+
     def forward(self, hidden_states, observation_mask=None, _fused=True):
         if _fused and _can_fuse(hidden_states):
             return self.forward_fused(hidden_states, None, None, observation_mask)
+        if _fused and torch.is_grad_enabled():
+            y = self.forward_autograd(hidden_states)
+            if y is not None:
+                return y
         hidden_states = F.layer_norm(hidden_states, self.layernorm.normalized_shape, None, None, self.layernorm.eps)
         hidden_states += self.bias
         if self.qoutput:

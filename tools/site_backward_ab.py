@@ -55,13 +55,17 @@ def alternate(forms):
     return res
 
 
-def report(label, res, unit=1.0, suffix="us"):
+def _site_calls():
+    took = UL.site_backward
+    return f"gelu {took.gelu}, softmax {took.softmax}, eager {took.eager}"
+
+
+def report(label, res, unit=1.0, suffix="us", calls=_site_calls):
     med = {k: statistics.median(v) for k, v in res.items()}
     text = "   ".join(f"{k} {med[k] / unit:9.2f} [{min(v) / unit:.2f} .. {max(v) / unit:.2f}] {suffix}" for k, v in res.items())
     lo, hi = min(res["eager"]), max(res["eager"])
     verdict = "inside eager's own range" if lo <= med["fused"] <= hi else f"x{med['eager'] / med['fused']:.2f}"
-    took = UL.site_backward
-    return f"{label:44s} {text}   fused vs eager: {verdict}   (site calls: gelu {took.gelu}, softmax {took.softmax}, eager {took.eager})"
+    return f"{label:44s} {text}   fused vs eager: {verdict}   (site calls: {calls()})"
 
 
 def quantizer(dev, x):
@@ -112,7 +116,13 @@ def sites(dev, lines):
         torch.cuda.empty_cache()
 
 
-def learn_scale_step(dev, lines, seq):
+def _site_switches(fused):
+    UL.FUSE_BACKWARD = UL.FUSE_SOFTMAX = fused
+
+
+def learn_scale_step(dev, lines, seq, switch=_site_switches, calls=_site_calls):
+    """``switch(fused)`` sets the switches of a form, ``calls()`` words what the sites did (tools/layernorm_backward_ab.py
+    times its own switch through this function)."""
     from transformers import BertConfig, BertForSequenceClassification
     from outlier_suppression_amd import token_wise_clipping as TWC
     from outlier_suppression_amd.quant_model import quantize_model
@@ -144,14 +154,14 @@ def learn_scale_step(dev, lines, seq):
 
     def step(fused):
         def fn():
-            UL.FUSE_BACKWARD = UL.FUSE_SOFTMAX = fused
+            switch(fused)
             for p in params:
                 p.grad = None
             TWC.batch_loss(model(**batch), batch, target, "glue").backward()
         return fn
     with TWC._only_these_learn(model, params):
         res = alternate({"eager": step(False), "fused": step(True)})
-    lines.append(report(f"learn_scale step, BERT-base 32 x {seq} (forward + backward)", res, 1000.0, "ms"))
+    lines.append(report(f"learn_scale step, BERT-base 32 x {seq} (forward + backward)", res, 1000.0, "ms", calls))
     print(lines[-1], flush=True)
     del model, fp
     torch.cuda.empty_cache()
