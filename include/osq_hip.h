@@ -49,7 +49,8 @@ typedef void* osq_stream;
  *     osq_sample_nucleus_group, osq_sample_nucleus_group_at, osq_sample_uniforms_group, osq_token_logprob_workspace_bytes,
  *     osq_token_logprob, osq_token_logprob_backward, osq_attention_fake_quant, osq_attention_fake_quant_int,
  *     osq_attention_fake_quant_shared, osq_attention_fake_quant_int_shared, osq_gelu_fake_quant_backward,
- *     osq_attention_softmax_fake_quant_backward, osq_residual_layernorm_fake_quant_backward. */
+ *     osq_attention_softmax_fake_quant_backward, osq_residual_layernorm_fake_quant_backward, osq_fake_quant_heads_backward
+ *     (with it osq_workspace_bytes() grew at its END: no earlier offset of the workspace moved). */
 #define OSQ_ABI_VERSION 10
 
 typedef enum osq_status {
@@ -222,6 +223,46 @@ typedef struct osq_headsplit_site {
 } osq_headsplit_site;
 int osq_fake_quant_headsplit_multi(const osq_headsplit_site* sites, int n_sites, int64_t batch, int64_t tokens,
                                    int64_t heads, int64_t head_dim, osq_stream stream);
+
+/* Backward of the head-split sites, 1..4 sites of ONE geometry in one launch (csrc/heads_backward.hip).  Two layouts of one
+ * tensor: token-major [batch, tokens, heads * head_dim] and head-major [batch, heads, tokens, head_dim], both contiguous.
+ *     direction OSQ_HEADS_SPLIT   backward of osq_fake_quant_headsplit_multi (query / key / value):
+ *                                 x and grad_x token-major, grad_out head-major
+ *     direction OSQ_HEADS_MERGE   backward of the context site (osq_fake_quant_per_tensor_strided on the permuted context):
+ *                                 x and grad_x head-major, grad_out token-major
+ * grad_out_transposed != 0 (OSQ_HEADS_SPLIT only): grad_out is the head-major gradient held as a dense [batch, heads,
+ * head_dim, tokens] tensor -- element (b, h, t, d) at ((b * heads + h) * head_dim + d) * tokens + t, what a matmul's backward
+ * returns for a key used as k^T.  It is read in [<= 64 of head_dim][OSQ_HEADS_TOKEN_TILE tokens] tiles, coalesced along
+ * tokens, and transposed through LDS; it needs no alignment beyond a float's and tokens may be any number.
+ * Per element, with x and grad_out taken at the two layouts' indices of the same (b, t, h, d):
+ *     g_mul = grad_out * s ;  g_in = inside ? g_mul : 0            inside: the unclamped integer lies in [quant_min, quant_max]
+ *     grad_x = g_in / s                                            the rule of osq_lsq_backward_per_tensor: the same word
+ *     ds += grad_out * (xq - z)  +  (-g_in) * ((x / s) / s)
+ *     dz += g_in - g_mul
+ * with (s, z) the effective parameters of (scale, zero_point, mode, grad_factor).  grad_x is nullable (the sums are still
+ * formed), grad_scale[1] / grad_zero_point[1] are nullable; a site without an incoming gradient is left out of the table.  The
+ * sums: fp32 per lane over two float4 (a tile: four), float64 from there, workgroup partials combined in block order by the
+ * workgroup of the SITE that arrives last, each site on partials and ticket counters of its own in the workspace -- no atomics
+ * on floating-point data, the same words on every run.  mode: OSQ_PARAM_FIXED / _LSQ / _LSQPLUS without OSQ_PARAM_SANITIZE (the
+ * repair is the forward's).  The order-free summation tier only.  OSQ_ERR_UNSUPPORTED, nothing launched: head_dim % 4,
+ * head_dim / 4 not a power of two <= 64, 2^30 float4s or more, x / grad_x / a dense grad_out not 16-byte aligned. */
+#define OSQ_HEADS_SPLIT 0
+#define OSQ_HEADS_MERGE 1
+#define OSQ_HEADS_TOKEN_TILE 64
+typedef struct osq_heads_backward_site {
+    const float* x;
+    const float* grad_out;
+    float* grad_x;
+    const float* scale;
+    const void* zero_point;
+    float* grad_scale;
+    float* grad_zero_point;
+    int32_t zp_type, mode;
+    float grad_factor;
+    int32_t quant_min, quant_max, grad_out_transposed;
+} osq_heads_backward_site;
+int osq_fake_quant_heads_backward(const osq_heads_backward_site* sites, int n_sites, int64_t batch, int64_t tokens,
+                                  int64_t heads, int64_t head_dim, int direction, void* workspace, osq_stream stream);
 
 /* Incremental decoding (model/quant_bart.py, QuantizedBartCache): the attention sites of one decoder step as ONE launch.
  * Site i reads the contiguous [batch, tokens, heads * head_dim] projection x and writes

@@ -240,6 +240,21 @@ def set_fast_layernorm_backward(on=True):
     util_layernorm.FUSE_LAYERNORM_BACKWARD = bool(on)
 
 
+def set_fast_heads_backward(on=True):
+    """Autograd passes (learn_scale) keep the one-launch query / key / value head-split sites and the context site, with a
+    one-launch backward that reads one layout and writes the other (util_layernorm.FUSE_HEADS_BACKWARD;
+    csrc/heads_backward.hip; behind FUSE_QKV; default OFF).  A switch of its own: the counts of set_fast_backward's record are
+    pinned by its tests.  A call the kernels do not take runs the eager lines (``util_layernorm.heads_backward``: split,
+    merge, eager, reason).  OSQ_FAST_HEADS_BACKWARD=1 turns it on at load."""
+    from . import util_layernorm
+    util_layernorm.FUSE_HEADS_BACKWARD = bool(on)
+
+
+def fast_heads_backward_from_environment(environ=None):
+    """What OSQ_FAST_HEADS_BACKWARD asks for: unset, empty or "0" -> False, anything else -> True."""
+    return _env_on("OSQ_FAST_HEADS_BACKWARD", environ)
+
+
 def fast_layernorm_backward_from_environment(environ=None):
     """What OSQ_FAST_LAYERNORM_BACKWARD asks for: unset, empty or "0" -> False, anything else -> True."""
     return _env_on("OSQ_FAST_LAYERNORM_BACKWARD", environ)
@@ -321,7 +336,8 @@ def reset_tier(_lib=None):
     cross-attention keys / values once per batch row (unset: off); OSQ_FAST_LM_LOSS=1 the BART LM wrapper's loss through the
     scoring kernels (unset: off); OSQ_FAST_BACKWARD=1 autograd passes keep the one-launch GELU and attention-probabilities
     sites, with one-launch backwards (unset: off); OSQ_FAST_LAYERNORM_BACKWARD=1 they keep the one-launch LayerNorm site too,
-    with its one-launch backward (unset: off)."""
+    with its one-launch backward (unset: off); OSQ_FAST_HEADS_BACKWARD=1 they keep the one-launch head-split and context
+    sites, with one-launch backwards between the two layouts (unset: off)."""
     import os
     width = int(os.environ.get("OSQ_STRICT_SIMD", "8"))
     strict = os.environ.get("OSQ_STRICT", "")
@@ -345,7 +361,7 @@ _SWITCHES = ((set_cache_codes, "OSQ_CACHE_CODES"), (set_graph_decode, "OSQ_GRAPH
              (set_sample_graph, "OSQ_SAMPLE_GRAPH"), (set_sample_nucleus, "OSQ_SAMPLE_NUCLEUS"),
              (set_share_cross_kv, "OSQ_SHARE_CROSS_KV"), (set_fast_lm_loss, "OSQ_FAST_LM_LOSS"),
              (set_fast_attention_int, "OSQ_FAST_ATTENTION_INT"), (set_fast_backward, "OSQ_FAST_BACKWARD"),
-             (set_fast_layernorm_backward, "OSQ_FAST_LAYERNORM_BACKWARD"))
+             (set_fast_layernorm_backward, "OSQ_FAST_LAYERNORM_BACKWARD"), (set_fast_heads_backward, "OSQ_FAST_HEADS_BACKWARD"))
 _apply_environment = reset_tier
 
 

@@ -25,6 +25,7 @@ TIME_FAKE_QUANT_STRIDED, TIME_FAKE_QUANT_CHANNEL, TIME_OBSERVE_CHANNELS, TIME_TO
 TIME_OBSERVE_TOKENS, TIME_ATTENTION_SOFTMAX = 13, 14
 UPDATE_NONE, UPDATE_RUNNING, UPDATE_AVERAGE = 0, 1, 2
 DTYPE_F32, DTYPE_BF16, DTYPE_F16 = 0, 1, 2   # osq_dtype: element type of the data behind the entry points with a `dtype` argument
+HEADS_SPLIT, HEADS_MERGE, HEADS_TOKEN_TILE = 0, 1, 64    # OSQ_HEADS_SPLIT / _MERGE / _TOKEN_TILE
 ERR_UNSUPPORTED = -3          # OSQ_ERR_UNSUPPORTED: nothing was launched, the caller takes its other path
 ABI_VERSION = 10              # OSQ_ABI_VERSION of include/osq_hip.h this file was written against
 
@@ -58,6 +59,13 @@ class HeadSplitSite(ctypes.Structure):
     """``osq_headsplit_site``: one entry of the table of osq_fake_quant_headsplit_multi."""
     _fields_ = [("x", _P), ("y", _P), ("scale", _P), ("zero_point", _P), ("zp_type", ctypes.c_int32), ("mode", ctypes.c_int32),
                 ("grad_factor", _F), ("quant_min", ctypes.c_int32), ("quant_max", ctypes.c_int32), ("pad", ctypes.c_int32)]
+
+
+class HeadsBackwardSite(ctypes.Structure):
+    """``osq_heads_backward_site``: one entry of the table of osq_fake_quant_heads_backward."""
+    _fields_ = [("x", _P), ("grad_out", _P), ("grad_x", _P), ("scale", _P), ("zero_point", _P), ("grad_scale", _P),
+                ("grad_zero_point", _P), ("zp_type", ctypes.c_int32), ("mode", ctypes.c_int32), ("grad_factor", _F),
+                ("quant_min", ctypes.c_int32), ("quant_max", ctypes.c_int32), ("grad_out_transposed", ctypes.c_int32)]
 
 
 class KvAppendSite(ctypes.Structure):
@@ -99,6 +107,7 @@ SIGNATURES = {
     "osq_fake_quant_per_tensor_strided": (_I, [_P, _P, _P, ctypes.POINTER(_L), ctypes.POINTER(_L), ctypes.POINTER(_L),
                                                _P, _P, _I, _I, _F, _I, _I, _P]),
     "osq_fake_quant_headsplit_multi": (_I, [ctypes.POINTER(HeadSplitSite), _I, _L, _L, _L, _L, _P]),
+    "osq_fake_quant_heads_backward": (_I, [ctypes.POINTER(HeadsBackwardSite), _I, _L, _L, _L, _L, _I, _P, _P]),
     "osq_fake_quant_kv_append": (_I, [ctypes.POINTER(KvAppendSite), _I, _L, _L, _L, _P]),
     "osq_fake_quant_kv_append_codes": (_I, [ctypes.POINTER(KvCodesSite), _I, _L, _L, _L, _P, _P]),
     "osq_fake_quant_kv_append_at": (_I, [ctypes.POINTER(KvAppendSite), _I, _L, _L, _L, _P, ctypes.POINTER(ctypes.c_int32), _P]),

@@ -132,12 +132,7 @@ __global__ __launch_bounds__(kThreads) void fq_tensor_strided_kernel(
 // other stride a multiple of 4, aligned bases): the head-split views of attention -- [B,h,T,d] seen through
 // [B,T,h,d] memory (model/quant_bert.py:128-150) -- read in 256-byte runs and written densely, so that the
 // fake-quant also delivers the contiguous operand the following batched matmul would otherwise copy out.
-struct MagicDiv {                           // n / d for n < 2^31: (n * m) >> k, exact (m = ceil(2^k / d), k = 31 + ceil(log2 d))
-    unsigned int d, m, k;
-};
-__device__ __forceinline__ unsigned int magic_div(unsigned int n, const MagicDiv& v) {
-    return static_cast<unsigned int>((static_cast<unsigned long long>(n) * v.m) >> v.k);
-}
+// (MagicDiv, magic_div, make_magic and HeadSplit: osq_device.h -- heads_backward.hip walks the same index maps)
 struct Strided4v {
     MagicDiv size1, size2, size3v;          // sizes of axes 1, 2 and axis 3 in float4 units (axis 0 is implied)
     unsigned int xs[3], ys[3];              // strides of axes 0..2 in float4 units (< 2^32, checked by the launcher)
@@ -190,12 +185,6 @@ __global__ __launch_bounds__(kThreads) void fq_tensor_strided_vec_kernel(
 // generic strided kernel above walks y and reads 256-byte runs 4 h d bytes apart), every wave-store is 64 / (d / 4) runs
 // of d floats, one per head, and the sixteen tokens a 256-thread workgroup covers in one trip land 16 d floats in a row
 // in each head's plane.  Two divisions by launch constants per float4 (h * d / 4, then T) instead of three.
-struct HeadSplit {
-    MagicDiv row;                 // h * dv float4 per token
-    MagicDiv tokens;              // T
-    unsigned int dv_shift;        // log2(d / 4): d / 4 is a power of two (64 -> 16)
-    unsigned int h, T;
-};
 
 template <int UNROLL, int NT>
 __global__ __launch_bounds__(kThreads) void fq_headsplit_kernel(
@@ -640,16 +629,6 @@ __global__ void lsq_sanitize_kernel(float* __restrict__ scale, float* __restrict
 
 bool stream_write_through() { return g_stream_wt != 0; }
 int lsq_backward_grid(int64_t n4) { return grid_for(n4, kThreads * 2, g_bwd_blocks); }
-
-static inline MagicDiv make_magic(int64_t d) {       // 1 <= d < 2^31
-    MagicDiv v;
-    unsigned int l = 0;
-    while ((1ull << l) < static_cast<unsigned long long>(d)) ++l;
-    v.d = static_cast<unsigned int>(d);
-    v.k = 31 + l;
-    v.m = static_cast<unsigned int>(((1ull << v.k) + d - 1) / d);   // <= 2^32 - 1 for d >= 2; d == 1: 2^31
-    return v;
-}
 
 }  // namespace osq
 

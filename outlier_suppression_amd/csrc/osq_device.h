@@ -575,4 +575,46 @@ __device__ __forceinline__ int kv_append_position(const Sites& s) {
     return ok ? p : -1;
 }
 
+// ---- divisions by launch constants, and the head-split index map (fake_quant.hip, heads_backward.hip) ----------------
+struct MagicDiv {                           // n / d for n < 2^31: (n * m) >> k, exact (m = ceil(2^k / d), k = 31 + ceil(log2 d))
+    unsigned int d, m, k;
+};
+__device__ __forceinline__ unsigned int magic_div(unsigned int n, const MagicDiv& v) {
+    return static_cast<unsigned int>((static_cast<unsigned long long>(n) * v.m) >> v.k);
+}
+static inline MagicDiv make_magic(int64_t d) {       // host; 1 <= d < 2^31
+    MagicDiv v;
+    unsigned int l = 0;
+    while ((1ull << l) < static_cast<unsigned long long>(d)) ++l;
+    v.d = static_cast<unsigned int>(d);
+    v.k = 31 + l;
+    v.m = static_cast<unsigned int>(((1ull << v.k) + d - 1) / d);   // <= 2^32 - 1 for d >= 2; d == 1: 2^31
+    return v;
+}
+
+// [B, T, h, d] memory (token-major) against the dense [B, h, T, d] tensor (head-major), both counted in float4s
+struct HeadSplit {
+    MagicDiv row;                 // h * dv float4 per token
+    MagicDiv tokens;              // T
+    unsigned int dv_shift;        // log2(d / 4): d / 4 is a power of two (64 -> 16)
+    unsigned int h, T;
+};
+static inline HeadSplit make_head_split(int64_t heads, int64_t dvv, int64_t tokens) {     // host
+    HeadSplit hs;
+    hs.row = make_magic(heads * dvv);
+    hs.tokens = make_magic(tokens);
+    hs.dv_shift = 0;
+    while ((1ll << hs.dv_shift) < dvv) ++hs.dv_shift;
+    hs.h = static_cast<unsigned int>(heads);
+    hs.T = static_cast<unsigned int>(tokens);
+    return hs;
+}
+// float4 e of the token-major tensor -> its index in the head-major one: two divisions by launch constants
+__device__ __forceinline__ unsigned int head_major_index(unsigned int e, const HeadSplit& d) {
+    const unsigned int bt = magic_div(e, d.row), c = e - bt * d.row.d;          // token b*T + t, float4 c of its h * dv
+    const unsigned int b = magic_div(bt, d.tokens), t = bt - b * d.tokens.d;
+    const unsigned int head = c >> d.dv_shift, dd = c & ((1u << d.dv_shift) - 1u);
+    return (((b * d.h + head) * d.T + t) << d.dv_shift) + dd;
+}
+
 }  // namespace osq

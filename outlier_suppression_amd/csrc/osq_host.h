@@ -25,6 +25,9 @@ constexpr size_t kWsFusedBytes = 2048;               // FusedState of the one-la
 constexpr int kResidentMaxBlocks = 512;              // workgroups of the resident MSEFast search (msefast.hip)
 constexpr int kResidentMaxSites = 16;                // searches one multi-site launch can hold (one polling wave each)
 constexpr size_t kWsResidentBytes = 128 + 2 * static_cast<size_t>(kResidentMaxSites) * kResidentMaxBlocks * 2 * 8;   // its epoch / status words + two buffers of partial-sum granules per site
+constexpr int kWsHeadsSites = 4;                     // sites of one head-split backward launch (heads_backward.hip): each finishes on its own
+constexpr size_t kWsHeadsSiteBytes = kWsCounterBlock + static_cast<size_t>(kMaxBlocks) * 2 * 8;   // a site's ticket counters + its (ds, dz) partials
+constexpr size_t kWsHeadsBytes = kWsHeadsSites * kWsHeadsSiteBytes;
 
 
 // Process-wide state behind osq_set_tuning comes in two kinds:
@@ -121,7 +124,8 @@ static inline bool known_dtype(int dtype) { return dtype == OSQ_DTYPE_F32 || low
     } while (0)
 
 // Caller-owned scratch: [8 x 4 KiB of ticket counters][8 x 64 KiB of partials][16 KiB + 64 B wide-finaliser state]
-// [64 KiB rendezvous words][2 KiB state of the fused observe + fake-quant launch][256.1 KiB state of the resident MSEFast search].  Counters are zero between
+// [64 KiB rendezvous words][2 KiB state of the fused observe + fake-quant launch][256.1 KiB state of the resident MSEFast search]
+// [4 x (4 KiB of ticket counters + 32 KiB of partials) of the head-split backward's sites].  Counters are zero between
 // launches (each kernel's last workgroup resets the one it used).
 struct Workspace {
     char* base;
@@ -135,6 +139,10 @@ struct Workspace {
     }
     void* fused() const { return base + kWsHeaderBytes + kWsScratchBytes + kWsWideBytes + kWsMeetBytes; }
     void* resident() const { return base + kWsHeaderBytes + kWsScratchBytes + kWsWideBytes + kWsMeetBytes + kWsFusedBytes; }
+    // appended behind everything above: no earlier offset moved
+    char* heads(int site) const { return static_cast<char*>(resident()) + kWsResidentBytes + site * kWsHeadsSiteBytes; }
+    unsigned int* heads_counter(int site) const { return reinterpret_cast<unsigned int*>(heads(site)); }
+    double* heads_partials(int site) const { return reinterpret_cast<double*>(heads(site) + kWsCounterBlock); }
 };
 
 }  // namespace osq

@@ -1890,6 +1890,179 @@ def residual_layernorm_fake_quant_autograd(x, hidden, gamma, weight, bias, eps, 
 
 
 # ---------------------------------------------------------------------------------------
+# the query / key / value head-split sites and the context site under autograd: forward one launch, backward one launch
+# (csrc/heads_backward.hip)
+# ---------------------------------------------------------------------------------------
+
+HEADS_SPLIT, HEADS_MERGE = _hip.HEADS_SPLIT, _hip.HEADS_MERGE      # x token-major, dy head-major | x head-major, dy token-major
+HEADS_BACKWARD_TOKEN_TILE = _hip.HEADS_TOKEN_TILE    # kHeadsTokTile of csrc/heads_backward.hip: the tokens of a tile of a transposed gradient
+HEADS_MAX_SITES = 4                                  # kWsHeadsSites of csrc/osq_host.h: the sites of one launch
+
+
+def heads_fusable(b, t, heads, d):
+    """The geometry the head-split kernels take, forward (fake_quant_headsplit_multi) and backward alike: d a multiple of 4
+    with d / 4 a power of two up to 64, a non-empty tensor of fewer than 2^30 float4s."""
+    if min(b, t, heads, d) < 1 or d % 4:
+        return False
+    dv = d // 4
+    return dv & (dv - 1) == 0 and dv <= 64 and t < 2 ** 31 and heads * dv < 2 ** 31 and b * t * heads * dv < 2 ** 30
+
+
+def _dense16_f32(t):
+    return t.dtype == torch.float32 and t.is_contiguous() and t.data_ptr() % 16 == 0
+
+
+def _heads_grad(g, shape, direction):
+    """(gradient as the launch reads it, transposed flag).  Dense in ``shape`` and 16-byte aligned: as it is.  The
+    head-major gradient of a key used as k^T -- a [B, h, T, d] view of a dense [B, h, d, T] tensor -- : as it is, flagged.
+    Anything else is copied once into the dense layout."""
+    if g.shape != shape:
+        raise ValueError(f"fake_quant_heads_backward: a gradient of shape {tuple(g.shape)} for a site output of shape {tuple(shape)}")
+    if g.is_contiguous() and g.data_ptr() % 16 == 0:
+        return g, 0
+    if direction == HEADS_SPLIT and g.transpose(-1, -2).is_contiguous():
+        return g, 1
+    out = torch.empty(shape, dtype=g.dtype, device=g.device)
+    out.copy_(g)
+    return out, 0
+
+
+def fake_quant_heads_backward(xs, grads, params, heads, direction, needs=None, dx_out=None):
+    """The LSQ / LSQ+ backward of 1..4 head-split sites of one geometry in ONE launch (osq_fake_quant_heads_backward).
+    HEADS_SPLIT: xs[i] the [B, T, heads * d] projection fake_quant_headsplit_multi read, grads[i] the gradient of its
+    [B, heads, T, d] output.  HEADS_MERGE: xs[i] the [B, heads, T, d] context, grads[i] the gradient of the merged
+    [B, T, heads * d] output.  xs: contiguous fp32, 16-byte aligned, one shape.  A gradient may come dense, as the transposed
+    view a matmul's backward returns for k^T (read as it is, through LDS), or in any other layout (copied once); None leaves
+    the site out of the launch.  params[i] = (scale, zero_point, quant_min, quant_max, mode, grad_factor), mode without
+    PARAM_SANITIZE; needs[i] = (need_x, need_scale, need_zp), default all; dx_out: None, or per site the tensor dx is written
+    to.  Returns per site (dx, dscale, dzero_point) -- dx in
+    xs[i]'s layout, word-equal to lsq_backward_per_tensor on the same elements -- with None for what was not asked."""
+    lib = _hip.load()
+    n = len(xs)
+    if not (1 <= n <= HEADS_MAX_SITES and len(grads) == n and len(params) == n):
+        raise ValueError("fake_quant_heads_backward: 1..4 sites, with a gradient (or None) and a parameter record each")
+    x0 = xs[0]
+    if direction == HEADS_SPLIT:
+        b, t, width = x0.shape
+        d = width // heads
+        out_shape = (b, heads, t, d)
+    elif direction == HEADS_MERGE:
+        b, h_, t, d = x0.shape
+        width = heads * d
+        out_shape = (b, t, width)
+        if h_ != heads:
+            raise ValueError("fake_quant_heads_backward: the context has another number of heads")
+    else:
+        raise ValueError("fake_quant_heads_backward: direction is HEADS_SPLIT or HEADS_MERGE")
+    if width != heads * d or not heads_fusable(b, t, heads, d):
+        raise ValueError("fake_quant_heads_backward: needs head_dim % 4 == 0, head_dim / 4 a power of two <= 64 and a "
+                         "non-empty tensor of fewer than 2^30 float4s")
+    needs = [(True, True, True)] * n if needs is None else needs
+    results = [(None, None, None)] * n
+    table = (_hip.HeadsBackwardSite * n)()
+    keep, k = [], 0
+    for i, (x, g, (scale, zero_point, quant_min, quant_max, mode, grad_factor)) in enumerate(zip(xs, grads, params)):
+        if g is None:
+            continue
+        _hip.require_device(x, g, scale, zero_point)
+        _check_f32(x, g, scale)
+        if x.shape != x0.shape or not x.is_contiguous() or x.data_ptr() % 16:
+            raise ValueError("fake_quant_heads_backward: xs must be contiguous, 16-byte aligned tensors of one shape")
+        g, flag = _heads_grad(g, out_shape, direction)
+        need_x, need_s, need_z = needs[i]
+        dx = (torch.empty_like(x) if dx_out is None else dx_out[i]) if need_x else None
+        if dx is not None and (dx.shape != x.shape or not _dense16_f32(dx)):
+            raise ValueError("fake_quant_heads_backward: dx_out must be contiguous, 16-byte aligned fp32 tensors of xs' shape")
+        ds, dz = _grad_outputs(x.device, need_s, need_z)
+        e = table[k]
+        e.x, e.grad_out, e.grad_x, e.scale, e.zero_point = x.data_ptr(), g.data_ptr(), _hip.ptr(dx), scale.data_ptr(), zero_point.data_ptr()
+        e.grad_scale, e.grad_zero_point = _hip.ptr(ds), _hip.ptr(dz)
+        e.zp_type, e.mode, e.grad_factor, e.quant_min, e.quant_max = _zp_type(zero_point), int(mode), float(grad_factor), int(quant_min), int(quant_max)
+        e.grad_out_transposed = flag
+        keep.append(g)                      # a copied gradient lives until the launch is enqueued
+        results[i] = (dx, ds, dz)
+        k += 1
+    if k:
+        _hip.check(lib.osq_fake_quant_heads_backward(table, k, b, t, heads, d, direction, _hip.ptr(_hip.workspace(x0.device)),
+                                                     _hip.raw_stream(x0.device)), "fake_quant_heads_backward")
+    return results
+
+
+def _heads_backward_results(ctx, xs, quants, grads, direction, first):
+    """The launch of an autograd function's backward and its return values after the ``first`` non-tensor slots: dx per
+    site, then (scale.grad, zero_point.grad) per site."""
+    n = len(xs)
+    needs = [(ctx.needs_input_grad[first + i], ctx.needs_input_grad[first + n + 2 * i],
+              ctx.needs_input_grad[first + n + 2 * i + 1] and quants[i][1].dtype == torch.float32) for i in range(n)]
+    res = fake_quant_heads_backward(xs, grads, [q + c for q, c in zip(quants, ctx.cfgs)], ctx.heads, direction, needs)
+    out = [r[0] for r in res]
+    for (scale, zero_point), (_, ds, dz) in zip(quants, res):
+        out.extend(_param_grads(scale, zero_point, ds, dz))
+    return (None,) * first + tuple(out)
+
+
+class _HeadSplitFakeQuantFn(torch.autograd.Function):
+    """fake_quant_headsplit_multi with autograd, n sites: forward = the sites' one launch, backward = one launch; only the
+    projections and the parameters are kept.  apply(heads, cfgs, x_1 .. x_n, scale_1, zero_point_1, .., scale_n,
+    zero_point_n) with cfgs[i] = (quant_min, quant_max, mode, grad_factor); returns the n head-major tensors."""
+
+    @staticmethod
+    def forward(ctx, heads, cfgs, *tensors):
+        n = len(cfgs)
+        xs, quants = tensors[:n], [tuple(tensors[n + 2 * i:n + 2 * i + 2]) for i in range(n)]
+        ctx.heads = heads
+        ctx.cfgs = [(c[0], c[1], c[2] & PARAM_MODE_MASK, c[3]) for c in cfgs]     # PARAM_SANITIZE is forward-only
+        ctx.set_materialize_grads(False)              # an output nobody used arrives as None: its site is left out
+        ctx.save_for_backward(*tensors)
+        ys = fake_quant_headsplit_multi(list(xs), [q + tuple(c) for q, c in zip(quants, cfgs)], heads)
+        if ys is None:
+            raise RuntimeError("headsplit_fake_quant: the library refused a geometry heads_fusable admits")
+        return tuple(ys)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        n = len(ctx.cfgs)
+        tensors = ctx.saved_tensors
+        quants = [tuple(tensors[n + 2 * i:n + 2 * i + 2]) for i in range(n)]
+        return _heads_backward_results(ctx, tensors[:n], quants, grads, HEADS_SPLIT, 2)
+
+
+class _MergeHeadsFakeQuantFn(torch.autograd.Function):
+    """The context site with autograd: forward = the strided fake-quant on the permuted context (one launch, writes the
+    merged layout), backward = one launch; the context and the parameters are kept."""
+
+    @staticmethod
+    def forward(ctx, cfg, x, scale, zero_point):
+        b, h, t, d = x.shape
+        ctx.heads = h
+        ctx.cfgs = [(cfg[0], cfg[1], cfg[2] & PARAM_MODE_MASK, cfg[3])]           # PARAM_SANITIZE is forward-only
+        ctx.save_for_backward(x, scale, zero_point)
+        y = fake_quant_per_tensor(x.permute(0, 2, 1, 3), scale, zero_point, *cfg)
+        return y.view(b, t, h * d)                    # the strided kernel wrote the dense [B, T, h, d] tensor
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        x, scale, zero_point = ctx.saved_tensors
+        return _heads_backward_results(ctx, (x,), [(scale, zero_point)], (grad_out,), HEADS_MERGE, 1)
+
+
+def headsplit_fake_quant(xs, params, heads):
+    """fake_quant_headsplit_multi as one launch whose backward is one launch too (fake_quant_heads_backward, HEADS_SPLIT).
+    xs: 1..4 contiguous, 16-byte aligned [B, T, heads * d] fp32 tensors of one shape with heads_fusable(B, T, heads, d);
+    params[i] = (scale, zero_point, quant_min, quant_max, mode, grad_factor) with the quantizer's OWN scale / zero_point, so
+    that a learnable pair receives its gradients.  Returns the list of dense [B, heads, T, d] tensors."""
+    flat = [p for q in params for p in q[:2]]
+    return list(_HeadSplitFakeQuantFn.apply(heads, tuple(tuple(q[2:]) for q in params), *xs, *flat))
+
+
+def merge_heads_fake_quant(ctx, scale, zero_point, quant_min, quant_max, mode=PARAM_FIXED, grad_factor=1.0):
+    """The context site -- fake_quant of the contiguous, 16-byte aligned [B, h, T, d] context written as the merged
+    [B, T, h * d] tensor -- as one launch whose backward is one launch too (fake_quant_heads_backward, HEADS_MERGE);
+    heads_fusable(B, T, h, d)."""
+    return _MergeHeadsFakeQuantFn.apply((quant_min, quant_max, mode, grad_factor), ctx, scale, zero_point)
+
+
+# ---------------------------------------------------------------------------------------
 # attention over a whole sequence: both products, mask, softmax, two quantizers in one launch
 # ---------------------------------------------------------------------------------------
 

@@ -49,6 +49,15 @@ of 4 up to 2048 columns; otherwise as ``FUSE_BACKWARD``.  Anything else takes th
 ``util_layernorm.layernorm_backward`` says why.  ``outlier_suppression_amd.set_fast_layernorm_backward(True)`` /
 ``OSQ_FAST_LAYERNORM_BACKWARD=1`` turn it on; measured times are in profiles/layernorm_backward_ab.txt and README.
 
+``FUSE_HEADS_BACKWARD`` (default OFF) does it for the sites ``FUSE_QKV`` serves without autograd and for the context site:
+with autograd on, ``qkv_heads_fake_quant``, ``split_heads_fake_quant`` and ``merge_heads_fake_quant`` keep their one launch
+and get a one-launch backward that reads one of the two layouts ([B, T, h*d], [B, h, T, d]) and writes the other
+(``ops.headsplit_fake_quant`` / ``ops.merge_heads_fake_quant``, csrc/heads_backward.hip); the key's gradient is taken as the
+transposed view a matmul's backward returns.  The forward is bit-identical, dx word-equal to the eager quantizer's.  Head
+sizes with d / 4 a power of two up to 64; otherwise as ``FUSE_BACKWARD``.  Anything else takes the eager lines and
+``util_layernorm.heads_backward`` says why.  ``outlier_suppression_amd.set_fast_heads_backward(True)`` /
+``OSQ_FAST_HEADS_BACKWARD=1`` turn it on; measured times are in profiles/heads_backward_ab.txt and README.
+
 Incremental decoding has a fifth, ``FUSE_DECODE_ATTENTION`` (default OFF): everything a cached decoding step's attention
 block runs after its q / k / v + append launch -- bmm, mask add, softmax, probabilities quantizer, bmm, merge heads, context
 quantizer (quant_bart.py:232-268) -- as ONE launch for the step's single query token (``ops.decode_attention_fake_quant``,
@@ -171,6 +180,7 @@ FAST_LM_LOSS = False     # forward(labels=...) of the BART LM wrapper: the loss 
 CACHE_CODES = False      # incremental decoding: new KV caches hold integer codes, one byte per element (same words read back; set_cache_codes / OSQ_CACHE_CODES=1)
 FUSE_BACKWARD = False    # autograd passes (learn_scale): the GELU site and, under FUSE_SOFTMAX, the attention-probabilities site keep their one launch and get a one-launch backward (csrc/site_backward.hip; set_fast_backward / OSQ_FAST_BACKWARD=1)
 FUSE_LAYERNORM_BACKWARD = False    # autograd passes (learn_scale): a LayerNorm site keeps its one launch and gets a one-launch backward (csrc/layernorm_backward.hip; behind FUSE_LAYERNORM; set_fast_layernorm_backward / OSQ_FAST_LAYERNORM_BACKWARD=1)
+FUSE_HEADS_BACKWARD = False    # autograd passes (learn_scale): the query / key / value head-split sites and the context site keep their one launch and get a one-launch backward between the two layouts (csrc/heads_backward.hip; behind FUSE_QKV; set_fast_heads_backward / OSQ_FAST_HEADS_BACKWARD=1)
 
 
 class SiteBackwardInfo:
@@ -207,6 +217,25 @@ class LayerNormBackwardInfo:
 
 
 layernorm_backward = LayerNormBackwardInfo()
+
+
+class HeadsBackwardInfo:
+    """What the head-split sites did under autograd since ``reset()``: ``split`` (query / key / value: one call serves up to
+    four sites) and ``merge`` (context) calls that took the autograd functions (one launch forward, one backward), ``eager``
+    calls that took the eager lines, and the ``reason`` of the last of those (``util_layernorm.heads_backward``).  A record
+    of its own, as ``layernorm_backward`` is."""
+
+    def __init__(self):
+        self.reset()
+
+    def reset(self):
+        self.split, self.merge, self.eager, self.reason = 0, 0, 0, None
+
+    def __repr__(self):
+        return f"HeadsBackwardInfo(split={self.split}, merge={self.merge}, eager={self.eager}, reason={self.reason!r})"
+
+
+heads_backward = HeadsBackwardInfo()
 
 
 def _autograd_site_why_not(q, x, first=None):
@@ -307,6 +336,45 @@ def softmax_backward_why_not(q, scores4, mask, dropout=None):
     if why is None and not ops.attention_softmax_backward_fusable(scores4, mask):
         why = "the layout of scores / mask is not the register-resident kernel's"
     return why
+
+
+def heads_backward_why_not(quantizers, xs, heads, direction=ops.HEADS_SPLIT):
+    """None when an autograd pass through head-split sites takes ops.headsplit_fake_quant / ops.merge_heads_fake_quant (one
+    launch forward, one launch backward), else the reason it takes the eager lines -- one phrase.  ``quantizers`` / ``xs``:
+    the sites of one launch and their inputs, [B, T, heads * d] projections (HEADS_SPLIT) or the [B, heads, T, d] context
+    (HEADS_MERGE)."""
+    if not FUSE_HEADS_BACKWARD:
+        return "FUSE_HEADS_BACKWARD is off"
+    why = None if FUSE_QKV else "FUSE_QKV is off"
+    for q, x in zip(quantizers, xs):
+        why = _autograd_site_why_not(q, x, why)
+    x0 = xs[0]
+    if why is None:
+        if x0.dim() != (3 if direction == ops.HEADS_SPLIT else 4) or any(x.shape != x0.shape for x in xs):
+            why = "the geometry is refused by heads_fusable"
+        else:
+            b, t, h, d = ((x0.shape[0], x0.shape[1], heads, x0.shape[2] // heads) if direction == ops.HEADS_SPLIT
+                          else (x0.shape[0], x0.shape[2], x0.shape[1], x0.shape[3]))
+            if h != heads or (direction == ops.HEADS_SPLIT and x0.shape[2] != heads * d) or not ops.heads_fusable(b, t, h, d):
+                why = "the geometry is refused by heads_fusable"
+    if why is None and not all(_dense16(x) for x in xs):
+        why = "the input is not a dense, 16-byte aligned tensor"
+    for q, x in zip(quantizers, xs):
+        why = why or _off_gpu(q, x)
+    return why
+
+
+def _heads_site(direction, why):
+    """Counts a head-split call under autograd in ``heads_backward``; True when it takes the one-launch pair."""
+    if why is None:
+        if direction == ops.HEADS_SPLIT:
+            heads_backward.split += 1
+        else:
+            heads_backward.merge += 1
+        return True
+    heads_backward.eager += 1
+    heads_backward.reason = why
+    return False
 
 
 def _learnable_site(q, numel):
@@ -545,6 +613,10 @@ def merge_heads_fake_quant(quantizer, ctx, observation_mask=None):
     context site (quant_bert.py:184-188, quant_bart.py:262-268).  In the plain quantising state the permuted VIEW goes to
     the strided fake-quant kernel, which writes the merged layout itself: one pass instead of copy + fake-quant, same bits."""
     b, h, t, d = ctx.shape
+    if torch.is_grad_enabled() and _heads_site(ops.HEADS_MERGE, heads_backward_why_not((quantizer,), (ctx,), h, ops.HEADS_MERGE)):
+        # FUSE_HEADS_BACKWARD: the same launch under autograd, its backward one launch from the head-major context and the
+        # token-major gradient; anything it does not take keeps the lines below, with the reason in heads_backward
+        return ops.merge_heads_fake_quant(ctx, *_learnable_site(quantizer, ctx.numel()))
     if _plain_quantizing(quantizer, ctx) and ctx.is_contiguous() and d % 4 == 0:
         y = quantizer(ctx.permute(0, 2, 1, 3))
         if y.is_contiguous():
@@ -561,6 +633,8 @@ def split_heads_fake_quant(quantizer, x, heads, observation_mask=None):
     [B,h,T,d] layout (one pass, same bits)."""
     b, t, width = x.shape
     d = width // heads
+    if torch.is_grad_enabled() and _heads_site(ops.HEADS_SPLIT, heads_backward_why_not((quantizer,), (x,), heads)):
+        return ops.headsplit_fake_quant([x], [_learnable_site(quantizer, x.numel())], heads)[0]      # FUSE_HEADS_BACKWARD, as below
     if _plain_quantizing(quantizer, x) and x.is_contiguous() and d % 4 == 0:
         y = quantizer(x.view(b, t, heads, d).transpose(1, 2))
         if y.is_contiguous():
@@ -579,6 +653,12 @@ def qkv_heads_fake_quant(quantizers, projections, heads):
     [B, h, T, d] tensors (the caller transposes k), or None: the caller then runs the three sites one by one.  A site's
     result depends on its own tensor and parameters only, so the order of the three calls does not matter; every site's
     LSQ / LSQ+ parameter repair (fake_quant.py:188-191) rides in the launch as it does in the per-site form."""
+    if torch.is_grad_enabled() and _heads_site(ops.HEADS_SPLIT, heads_backward_why_not(quantizers, projections, heads)):
+        # FUSE_HEADS_BACKWARD: the same launch under autograd, its backward one launch that reads each projection token-major
+        # and its gradient head-major (the key's as the transposed view a matmul's backward returns); anything it does not
+        # take keeps the lines below -- which refuse under autograd -- with the reason in heads_backward
+        return ops.headsplit_fake_quant(list(projections), [_learnable_site(q, x.numel()) for q, x in zip(quantizers, projections)],
+                                        heads)
     if not FUSE_QKV:
         return None
     x0 = projections[0]
