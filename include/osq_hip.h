@@ -50,7 +50,8 @@ typedef void* osq_stream;
  *     osq_token_logprob, osq_token_logprob_backward, osq_attention_fake_quant, osq_attention_fake_quant_int,
  *     osq_attention_fake_quant_shared, osq_attention_fake_quant_int_shared, osq_gelu_fake_quant_backward,
  *     osq_attention_softmax_fake_quant_backward, osq_residual_layernorm_fake_quant_backward, osq_fake_quant_heads_backward
- *     (with it osq_workspace_bytes() grew at its END: no earlier offset of the workspace moved). */
+ *     (with it osq_workspace_bytes() grew at its END: no earlier offset of the workspace moved), osq_activation_codes,
+ *     osq_weight_codes_sums, osq_linear_int. */
 #define OSQ_ABI_VERSION 10
 
 typedef enum osq_status {
@@ -1189,6 +1190,50 @@ int osq_attention_fake_quant_int_shared(const float* q, const float* k, const fl
                                         float* ctx_scale, void* ctx_zero_point, int ctx_zp_type, int ctx_mode,
                                         float ctx_grad_factor, int ctx_quant_min, int ctx_quant_max,
                                         osq_stream stream);
+
+/* ------------------------------------------------------------------ integer linear (linear_int.hip) */
+
+/* out [rows, channels] = x . W^T + bias of a frozen model's linear layer on the INTEGER CODES of both operands, the products on
+ * the int8 matrix instruction (v_mfma_i32_32x32x32_i8: int32 accumulation, exact).  The weight is its quantizer's output
+ * (per-channel along axis 0, or per-tensor), the input the output of a per-tensor activation quantizer, the x_* group (the
+ * effective parameters are those of every one-launch site: OSQ_PARAM_SANITIZE included, the repair rides in the launch).
+ * For input row r, output channel c, reduction length K = cols:
+ *     ux = clamp(rint(x[r,k] / s_x) + zp_x, qmin_x, qmax_x) - qmin_x     the producer's quantizer once more: exact on its own outputs
+ *     uw = the weight's code byte, osq_quantize_codes' u                  (per-channel or per-tensor record, ch_axis 0 or -1)
+ *     a = ux - 128, b = uw - 128                                          int8
+ *     zx = (zp_x - qmin_x) - 128,  zw[c] = (zp_w[c] - qmin_w) - 128       integers, or the launch writes NaN everywhere
+ *     N[r,c] = sum_k a*b  - zw[c] * sum_k a[r,k]  - zx * sum_k b[c,k]  + K * zx * zw[c]      int32, exact: |N| <= 255*255*K
+ *     out[r,c] = (float)N[r,c] * (s_x * s_w[c]) + bias[c]                 one fp32 rounding per operation, in this order
+ *                                                                         (int -> float to nearest even); no bias: no add
+ * Limits: K % 16 == 0, 16 <= K <= 16384 (every term fits int32), at most 256 codes per quantizer.
+ *
+ * osq_activation_codes: x [rows, cols] fp32, rows `row_stride` elements apart (a multiple of 4, x 16-byte aligned) ->
+ * codes [rows, cols] bytes holding a (= ux ^ 0x80), dense, and rowsum[r] = sum_k a[r,k].  An element without a code (a NaN,
+ * an infinity, a parameter that makes x_quant no integer) makes rowsum[r] = INT32_MIN: osq_linear_int then writes NaN to
+ * exactly row r of out.  Once per producer output: every consumer of that tensor reads the same bytes.
+ *
+ * osq_weight_codes_sums: w [rows = output channels, cols] dense fp32 with `channels` (rows, or 1) raw scale / zero_point
+ * entries and mode / grad_factor as osq_quantize_codes takes them -> codes [rows, cols] bytes holding b, colsum[c] = sum_k
+ * b[c,k], scale_eff[c] = s_w[c], zw[c], all of `rows` entries, and *bad (zeroed by the caller) set to 1 when some zero point
+ * is not an integer inside [quant_min, quant_max] or some element has no code.  Once per frozen weight.
+ *
+ * osq_linear_int: the rule above from the two sets of codes; bias may be NULL; out dense.  If *w_bad is set or zp_x is not
+ * an integer inside [quant_min, quant_max], ALL of out is NaN.  rows <= 32 take a kernel that splits the channels over many
+ * workgroups and K over a workgroup's waves (the words are the same: the sum is an integer).  16-byte aligned codes, 4-byte
+ * aligned everything else.
+ * All three: no allocation, no host synchronisation, no workspace, no floating-point atomics: legal inside a stream
+ * capture.  Inference only.  OSQ_ERR_INVALID_ARGUMENT, nothing launched: a limit above exceeded, a null or misaligned tensor,
+ * a mode other than FIXED / LSQ / LSQ+ (+ SANITIZE for x). */
+int osq_activation_codes(const float* x, int64_t rows, int64_t cols, int64_t row_stride, uint8_t* codes, int32_t* rowsum,
+                         float* x_scale, void* x_zero_point, int x_zp_type, int x_mode, float x_grad_factor,
+                         int x_quant_min, int x_quant_max, osq_stream stream);
+int osq_weight_codes_sums(const float* w, int64_t rows, int64_t cols, int64_t channels, uint8_t* codes, int32_t* colsum,
+                          float* scale_eff, int32_t* zw, int32_t* bad, const float* scale, const void* zero_point,
+                          int zp_type, int mode, float grad_factor, int quant_min, int quant_max, osq_stream stream);
+int osq_linear_int(const uint8_t* x_codes, const int32_t* x_rowsum, const uint8_t* w_codes, const int32_t* w_colsum,
+                   const float* w_scale, const int32_t* w_zw, const int32_t* w_bad, const float* bias, float* out,
+                   int64_t rows, int64_t channels, int64_t cols, float* x_scale, void* x_zero_point, int x_zp_type,
+                   int x_mode, float x_grad_factor, int x_quant_min, int x_quant_max, osq_stream stream);
 
 /* ------------------------------------------------------------------ beam search (beam_select.hip) */
 

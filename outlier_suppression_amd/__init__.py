@@ -92,6 +92,17 @@ def set_fast_attention_int(on=True):
     util_layernorm.FUSE_ATTENTION_INT = bool(on)
 
 
+def set_fast_linear_int(on=True):
+    """A frozen model's QLinear layers on the integer codes of their weight and of the activation quantizer that produced their
+    input (util_layernorm.FUSE_LINEAR_INT: exact int32 sums on the int8 matrix instruction, the scales applied once,
+    csrc/linear_int.hip; needs autograd off, both quantizers plainly quantising with at most 256 codes, K a multiple of 16 up to
+    16384 and a linear that quantize_model bound to its producer; default OFF -- tolerance-equal to F.linear, not bit-equal).
+    A call the kernels do not take runs F.linear (``util_layernorm.linear_int``: fused, eager, reason).
+    OSQ_FAST_LINEAR_INT=1 turns it on at load."""
+    from . import util_layernorm
+    util_layernorm.FUSE_LINEAR_INT = bool(on)
+
+
 def set_cache_codes(on=True):
     """New KV caches of incremental decoding hold integer codes, one byte per element, instead of fp32 words
     (util_layernorm.CACHE_CODES; model/quant_bart.py, QuantizedBartCache; default OFF).  What is read back from the cache,
@@ -325,7 +336,8 @@ def reset_tier(_lib=None):
     the reference's one-thread order, the backward's sums order-free; OSQ_STRICT=1 / 0 force both; OSQ_FAST=0 / 1 the
     one-launch LayerNorm site; OSQ_FAST_SOFTMAX=1 the one-launch attention-probabilities site and OSQ_FAST_DECODE_ATTENTION=1
     the one-launch attention of a cached decoding step (unset: off); OSQ_FAST_ATTENTION=1 the one-launch attention over whole
-    sequences and OSQ_FAST_ATTENTION_INT=1 its form on integer codes (unset: off); OSQ_CACHE_CODES=1 KV caches as integer codes (unset: off);
+    sequences and OSQ_FAST_ATTENTION_INT=1 its form on integer codes (unset: off);
+    OSQ_FAST_LINEAR_INT=1 the linear layers of a frozen model on integer codes (unset: off); OSQ_CACHE_CODES=1 KV caches as integer codes (unset: off);
     OSQ_GRAPH_DECODE=1 generate() replays a captured decoding step (unset: off); OSQ_BEAM_SELECT=1 beam search selects a step's
     continuations with one kernel call (unset: off); OSQ_BEAM_ADVANCE=1 beam search advances its beams with one kernel call
     (unset: off); OSQ_BEAM_GRAPH=1 beam search replays a whole step, bookkeeping included, as one captured graph (unset: off);
@@ -360,7 +372,8 @@ _SWITCHES = ((set_cache_codes, "OSQ_CACHE_CODES"), (set_graph_decode, "OSQ_GRAPH
              (set_greedy_graph, "OSQ_GREEDY_GRAPH"), (set_sample_advance, "OSQ_SAMPLE_ADVANCE"),
              (set_sample_graph, "OSQ_SAMPLE_GRAPH"), (set_sample_nucleus, "OSQ_SAMPLE_NUCLEUS"),
              (set_share_cross_kv, "OSQ_SHARE_CROSS_KV"), (set_fast_lm_loss, "OSQ_FAST_LM_LOSS"),
-             (set_fast_attention_int, "OSQ_FAST_ATTENTION_INT"), (set_fast_backward, "OSQ_FAST_BACKWARD"),
+             (set_fast_attention_int, "OSQ_FAST_ATTENTION_INT"), (set_fast_linear_int, "OSQ_FAST_LINEAR_INT"),
+             (set_fast_backward, "OSQ_FAST_BACKWARD"),
              (set_fast_layernorm_backward, "OSQ_FAST_LAYERNORM_BACKWARD"), (set_fast_heads_backward, "OSQ_FAST_HEADS_BACKWARD"))
 _apply_environment = reset_tier
 

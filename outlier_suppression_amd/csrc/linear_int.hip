@@ -1,0 +1,398 @@
+// Linear layers of a frozen model on the quantizers' INTEGER CODES: out = x . W^T + bias on the int8 matrix instruction
+// v_mfma_i32_32x32x32_i8 -- int32 accumulation, exact by construction.
+//
+// In a frozen model both operands of a QLinear are codes times a scale: the weight is its quantizer's output (the bytes
+// export_codes stores), the input is the output of a per-tensor activation quantizer.  For input row r, output channel c
+// and reduction length K (include/osq_hip.h, "integer linear"):
+//
+//     ux = clamp(rint(x[r,k] / s_x) + zp_x, qmin_x, qmax_x) - qmin_x      the producer's quantizer once more: exact on its own outputs
+//     uw = clamp(rint(w[c,k] / s_w[c]) + zp_w[c], qmin_w, qmax_w) - qmin_w the weight's exported code byte
+//     a = ux - 128, b = uw - 128                                           int8
+//     zx = (zp_x - qmin_x) - 128,  zw[c] = (zp_w[c] - qmin_w) - 128        integers, or the launch writes NaN everywhere
+//     N[r,c] = sum_k a*b - zw[c] * sum_k a[r,k] - zx * sum_k b[c,k] + K * zx * zw[c]        int32, exact: |N| <= 255*255*K
+//     out[r,c] = (float)N[r,c] * (s_x * s_w[c]) + bias[c]                  one rounding per operation, in this order
+//
+// Three launches:
+//   activation_codes_kernel  x [M,K] fp32 -> a [M,K] bytes + rowsum [M] int32: once per producer output, shared by its consumers.
+//                            A wave per row, 16-byte loads, four codes to a 4-byte store, the row sum by wave shuffles.  A row
+//                            with a non-finite element has no codes: its row sum is kLinNoRow and exactly that row of out is NaN.
+//   weight_codes_kernel      w [N,K] fp32 -> b [N,K] bytes + colsum, s_w, zw [N] + one `bad` word: once per frozen weight.
+//   linear_int_kernel        one 256-thread workgroup per 128 x 128 tile of out, a wave per 64 x 64 part: 2 x 2 tiles of the
+//                            32 x 32 x 32 instruction, 64 accumulator registers.  K goes by in steps of 64 bytes: the code tiles
+//                            of W and X (128 rows each) are fetched with 16-byte loads into double-buffered LDS, the next step's
+//                            loads issued before this step's products, one barrier per step.  A row of a tile is 64 + 16 bytes:
+//                            row i starts at bank 20 i mod 64, so the 16 lanes of a 16-byte read phase hit 16 disjoint groups of
+//                            four banks.  LDS: 2 x 2 x 128 x 80 B = 40 KiB.
+//   linear_int_rows_kernel   M <= 32 (a decoding step, the pooler, the classifier): a 128-row tile would leave all but N / 128
+//                            CUs idle.  One workgroup per 32 channels, its four waves split K in chunks of 128 bytes per row and
+//                            read their operands straight from memory (every weight byte once, by one wave; x stays in cache);
+//                            the four partial tiles are added through LDS (int32: any order) and wave 0 finishes.
+// A = W, B = X in both: a lane holds ONE row of x (lane & 31) and, in register r of a 32 x 32 result, channel
+// (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5) -- the map csrc/attention_int.hip documents -- so registers 4 g .. 4 g + 3 are four
+// consecutive channels: their colsum / zw / s_w / bias come with one 16-byte load each and leave as one 16-byte store where
+// N % 4 == 0.  Both operands read their 16 bytes of a k-step from the same place of their row, so the k order inside the
+// instruction does not matter.  Rows beyond M and channels beyond N are clamped at the load and dropped at the store; bytes
+// beyond K (K % 64 != 0) are zero in both operands.
+// No allocation, no host sync, no workspace, no atomics: legal inside a stream capture.  Inference only.
+#include <math.h>
+#include <hip/hip_runtime.h>
+#include "attention_quant.h"
+#include "codes_device.h"
+
+namespace osq {
+
+constexpr int kLinThreads = 256;
+constexpr int kLinTile = 128;            // rows of x and channels of a workgroup's tile
+constexpr int kLinKStep = 64;            // code bytes of a row per step: two k-steps of the instruction
+constexpr int kLinPitch = kLinKStep + 16;    // bytes of a tile row in LDS
+constexpr int kLinMaxK = 16384;          // |N| <= 255 * 255 * K < 2**30
+constexpr int kLinRowsM = 32;            // up to here: linear_int_rows_kernel
+constexpr int kLinRowsChunk = 128;       // bytes of a row a wave of linear_int_rows_kernel takes at a time
+constexpr int kLinNoRow = INT32_MIN;     // rowsum of a row without codes (a real one is at most 128 * K = 2**21)
+
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+typedef int i32x16 __attribute__((ext_vector_type(16)));
+
+__device__ __forceinline__ int wave_sum_i32(int v) {
+#pragma unroll
+    for (int d = OSQ_WAVE / 2; d; d >>= 1) v += __shfl_xor(v, d, OSQ_WAVE);
+    return v;
+}
+
+// One wave, one row of n4 float4: the bytes (u ^ 0x80 = u - 128 as int8) four to a word.  Returns the row's sum of u - 128 in
+// every lane; `rej` counts this lane's elements without a code (code_of).
+__device__ __forceinline__ int encode_row(const float4* __restrict__ xr, unsigned int* __restrict__ cr, int n4, int lane,
+                                          const QParams& p, float qmin, float qmax, unsigned int& rej) {
+    constexpr int kTrip = 4;             // 16-byte loads in flight per lane
+    int sum = 0;
+    for (int j0 = lane; j0 < n4; j0 += kTrip * OSQ_WAVE) {
+        float4 v[kTrip];
+#pragma unroll
+        for (int u = 0; u < kTrip; ++u)
+            if (j0 + u * OSQ_WAVE < n4) v[u] = xr[j0 + u * OSQ_WAVE];
+#pragma unroll
+        for (int u = 0; u < kTrip; ++u)
+            if (j0 + u * OSQ_WAVE < n4) {
+                const unsigned int u0 = code_of(v[u].x, p, qmin, qmax, rej), u1 = code_of(v[u].y, p, qmin, qmax, rej);
+                const unsigned int u2 = code_of(v[u].z, p, qmin, qmax, rej), u3 = code_of(v[u].w, p, qmin, qmax, rej);
+                sum += static_cast<int>(u0 + u1 + u2 + u3) - 512;
+                cr[j0 + u * OSQ_WAVE] = (u0 | (u1 << 8) | (u2 << 16) | (u3 << 24)) ^ 0x80808080u;
+            }
+    }
+    return wave_sum_i32(sum);
+}
+
+__device__ __forceinline__ bool lin_zp_ok(float zp, float qmin, float qmax) {
+    return zp >= qmin && zp <= qmax && rintf(zp) == zp;       // false for a NaN
+}
+
+__global__ __launch_bounds__(kLinThreads) void activation_codes_kernel(const float* __restrict__ x, int64_t ldx,
+                                                                       uint8_t* __restrict__ codes, int32_t* __restrict__ rowsum,
+                                                                       int64_t rows, int cols, DecQuant q) {
+    const QParams p = dec_params(q);                  // first: the parameter repair rides here
+    const int lane = threadIdx.x & (OSQ_WAVE - 1);
+    const int64_t wave = (static_cast<int64_t>(blockIdx.x) * kLinThreads + threadIdx.x) / OSQ_WAVE;
+    const int64_t nwaves = static_cast<int64_t>(gridDim.x) * (kLinThreads / OSQ_WAVE);
+    for (int64_t r = wave; r < rows; r += nwaves) {
+        unsigned int rej = 0;
+        const int sum = encode_row(reinterpret_cast<const float4*>(x + r * ldx), reinterpret_cast<unsigned int*>(codes + r * cols),
+                                   cols / 4, lane, p, q.qmin, q.qmax, rej);
+        const int bad = wave_sum_i32(static_cast<int>(rej));
+        if (lane == 0) rowsum[r] = bad ? kLinNoRow : sum;
+    }
+}
+
+// rows = output channels; channels: rows (a scale per row) or 1
+__global__ __launch_bounds__(kLinThreads) void weight_codes_kernel(const float* __restrict__ w, uint8_t* __restrict__ codes,
+                                                                   int32_t* __restrict__ colsum, float* __restrict__ scale_eff,
+                                                                   int32_t* __restrict__ zw, int32_t* __restrict__ bad,
+                                                                   int64_t rows, int64_t channels, int cols,
+                                                                   const float* __restrict__ scale_p, const void* __restrict__ zp_p,
+                                                                   int zp_type, int mode, float g, float qmin, float qmax) {
+    const int lane = threadIdx.x & (OSQ_WAVE - 1);
+    const int64_t wave = (static_cast<int64_t>(blockIdx.x) * kLinThreads + threadIdx.x) / OSQ_WAVE;
+    const int64_t nwaves = static_cast<int64_t>(gridDim.x) * (kLinThreads / OSQ_WAVE);
+    for (int64_t r = wave; r < rows; r += nwaves) {
+        const int64_t c = channels == 1 ? 0 : r;
+        const QParams p = effective_params(scale_p[c], load_zp(zp_p, zp_type, c), mode, g);
+        unsigned int rej = 0;
+        const int sum = encode_row(reinterpret_cast<const float4*>(w + r * cols), reinterpret_cast<unsigned int*>(codes + r * cols),
+                                   cols / 4, lane, p, qmin, qmax, rej);
+        const int nbad = wave_sum_i32(static_cast<int>(rej));
+        if (lane == 0) {
+            const bool ok = lin_zp_ok(p.zp, qmin, qmax);
+            colsum[r] = sum;
+            scale_eff[r] = p.scale;
+            zw[r] = ok ? static_cast<int>(p.zp - qmin) - 128 : 0;
+            if (!ok || nbad) *bad = 1;                // every writer writes the same word
+        }
+    }
+}
+
+struct LinArgs {
+    const uint8_t *xc, *wc;            // a [M, K], b [N, K]
+    const int32_t *xrs, *wcs, *wz, *wbad;
+    const float *ws, *bias;
+    float* out;                        // [M, N]
+    int M, N, K;
+    int vec;                           // N % 4 == 0 and out, wcs, wz, ws, bias 16-byte aligned: 16-byte epilogue accesses
+    DecQuant xq;
+};
+
+// zx and s_x of the launch; false (uniform): the launch writes NaN everywhere
+__device__ __forceinline__ bool lin_prologue(const LinArgs& a, int& zx, float& sx) {
+    const QParams xp = dec_params(a.xq);
+    sx = xp.scale;
+    const bool ok = lin_zp_ok(xp.zp, a.xq.qmin, a.xq.qmax) && *a.wbad == 0;
+    zx = ok ? static_cast<int>(xp.zp - a.xq.qmin) - 128 : 0;
+    return ok;
+}
+
+__device__ __forceinline__ void lin_fill_nan(const LinArgs& a, int m0, int n0, int tm, int tn) {
+    const float nan = __builtin_nanf("");
+    for (int i = threadIdx.x; i < tm * tn; i += kLinThreads) {
+        const int r = m0 + i / tn, c = n0 + i % tn;
+        if (r < a.M && c < a.N) a.out[static_cast<int64_t>(r) * a.N + c] = nan;
+    }
+}
+
+__device__ __forceinline__ float lin_value(int acc, int rs, int cs, int zw, int zx, int kzx, float sx, float sw, bool has_bias,
+                                           float bias, bool row_nan) {
+    const int n = acc - zw * rs - zx * cs + kzx * zw;
+    float y = static_cast<float>(n) * (sx * sw);
+    if (has_bias) y = y + bias;
+    return row_nan ? __builtin_nanf("") : y;
+}
+
+// the 16 registers of one 32 x 32 result: row `row` of x, channels c0 + (r & 3) + 8 * (r >> 2) + 4 * half
+__device__ __forceinline__ void lin_store_tile(const LinArgs& a, const i32x16& acc, int row, int c0, int half, int zx, float sx) {
+    if (row >= a.M) return;
+    const int rs_raw = a.xrs[row];
+    const bool row_nan = rs_raw == kLinNoRow;
+    const int rs = row_nan ? 0 : rs_raw, kzx = a.K * zx;
+    const bool has_bias = a.bias != nullptr;
+    float* orow = a.out + static_cast<int64_t>(row) * a.N;
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        const int c = c0 + 8 * g + 4 * half;
+        if (c >= a.N) continue;
+        if (a.vec) {
+            const i32x4 cs = *reinterpret_cast<const i32x4*>(a.wcs + c), zw = *reinterpret_cast<const i32x4*>(a.wz + c);
+            const float4 sw = *reinterpret_cast<const float4*>(a.ws + c);
+            const float4 b = has_bias ? *reinterpret_cast<const float4*>(a.bias + c) : make_float4(0.f, 0.f, 0.f, 0.f);
+            *reinterpret_cast<float4*>(orow + c) =
+                make_float4(lin_value(acc[4 * g + 0], rs, cs.x, zw.x, zx, kzx, sx, sw.x, has_bias, b.x, row_nan),
+                            lin_value(acc[4 * g + 1], rs, cs.y, zw.y, zx, kzx, sx, sw.y, has_bias, b.y, row_nan),
+                            lin_value(acc[4 * g + 2], rs, cs.z, zw.z, zx, kzx, sx, sw.z, has_bias, b.z, row_nan),
+                            lin_value(acc[4 * g + 3], rs, cs.w, zw.w, zx, kzx, sx, sw.w, has_bias, b.w, row_nan));
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if (c + e < a.N)
+                    orow[c + e] = lin_value(acc[4 * g + e], rs, a.wcs[c + e], a.wz[c + e], zx, kzx, sx, a.ws[c + e], has_bias,
+                                            has_bias ? a.bias[c + e] : 0.f, row_nan);
+        }
+    }
+}
+
+__global__ __launch_bounds__(kLinThreads) void linear_int_kernel(LinArgs a) {
+    __shared__ __attribute__((aligned(16))) uint8_t s_w[2][kLinTile * kLinPitch];
+    __shared__ __attribute__((aligned(16))) uint8_t s_x[2][kLinTile * kLinPitch];
+    const int lane = threadIdx.x & (OSQ_WAVE - 1), w = threadIdx.x / OSQ_WAVE;
+    const int l31 = lane & 31, half = lane >> 5;
+    const int mtiles = (a.M + kLinTile - 1) / kLinTile;
+    const int m0 = static_cast<int>(blockIdx.x % mtiles) * kLinTile, n0 = static_cast<int>(blockIdx.x / mtiles) * kLinTile;
+    int zx;
+    float sx;
+    if (!lin_prologue(a, zx, sx)) {                   // uniform
+        lin_fill_nan(a, m0, n0, kLinTile, kLinTile);
+        return;
+    }
+    const int wm = w & 1, wn = w >> 1;                // this wave's 64 x 64 part
+
+    // a thread's two 16-byte granules of each tile: granule threadIdx.x + 256 u is row idx / 4, bytes 16 (idx % 4) ..
+    osq_v4u32 gw[2], gx[2];
+    const auto load = [&](int k0) {
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const int idx = threadIdx.x + kLinThreads * u, row = idx >> 2, k = k0 + 16 * (idx & 3);
+            const osq_v4u32 zero = {0u, 0u, 0u, 0u};
+            gw[u] = gx[u] = zero;
+            if (k < a.K) {
+                gw[u] = *reinterpret_cast<const osq_v4u32*>(a.wc + static_cast<int64_t>(min(n0 + row, a.N - 1)) * a.K + k);
+                gx[u] = *reinterpret_cast<const osq_v4u32*>(a.xc + static_cast<int64_t>(min(m0 + row, a.M - 1)) * a.K + k);
+            }
+        }
+    };
+    const auto stash = [&](int buf) {
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const int idx = threadIdx.x + kLinThreads * u, at = (idx >> 2) * kLinPitch + 16 * (idx & 3);
+            *reinterpret_cast<osq_v4u32*>(&s_w[buf][at]) = gw[u];
+            *reinterpret_cast<osq_v4u32*>(&s_x[buf][at]) = gx[u];
+        }
+    };
+
+    i32x16 acc[2][2];                                 // [x part][channel part]
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0;
+
+    load(0);
+    stash(0);
+    __syncthreads();
+    const int steps = (a.K + kLinKStep - 1) / kLinKStep;
+    for (int s = 0; s < steps; ++s) {
+        const int buf = s & 1, k0 = s * kLinKStep;
+        if (s + 1 < steps) load(k0 + kLinKStep);      // in flight during this step's products
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) {
+            if (k0 + 32 * ks >= a.K) break;           // uniform: the half step beyond K is zeros
+            i32x4 fw[2], fx[2];
+#pragma unroll
+            for (int t = 0; t < 2; ++t) {
+                fw[t] = *reinterpret_cast<const i32x4*>(&s_w[buf][(64 * wn + 32 * t + l31) * kLinPitch + 32 * ks + 16 * half]);
+                fx[t] = *reinterpret_cast<const i32x4*>(&s_x[buf][(64 * wm + 32 * t + l31) * kLinPitch + 32 * ks + 16 * half]);
+            }
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_i32_32x32x32_i8(fw[j], fx[i], acc[i][j], 0, 0, 0);
+        }
+        if (s + 1 < steps) stash(buf ^ 1);            // last read in step s - 1: every wave has passed that step's barrier
+        __syncthreads();
+    }
+
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+            lin_store_tile(a, acc[i][j], m0 + 64 * wm + 32 * i + l31, n0 + 64 * wn + 32 * j, half, zx, sx);
+}
+
+__global__ __launch_bounds__(kLinThreads) void linear_int_rows_kernel(LinArgs a) {
+    constexpr int kWaves = kLinThreads / OSQ_WAVE;
+    __shared__ int s_part[kWaves - 1][16][OSQ_WAVE];
+    const int lane = threadIdx.x & (OSQ_WAVE - 1), w = threadIdx.x / OSQ_WAVE;
+    const int l31 = lane & 31, half = lane >> 5;
+    const int n0 = static_cast<int>(blockIdx.x) * 32;
+    int zx;
+    float sx;
+    if (!lin_prologue(a, zx, sx)) {                   // uniform
+        lin_fill_nan(a, 0, n0, kLinRowsM, 32);
+        return;
+    }
+    const uint8_t* wrow = a.wc + static_cast<int64_t>(min(n0 + l31, a.N - 1)) * a.K + 16 * half;
+    const uint8_t* xrow = a.xc + static_cast<int64_t>(min(l31, a.M - 1)) * a.K + 16 * half;
+    i32x16 acc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0;
+    for (int k0 = kLinRowsChunk * w; k0 < a.K; k0 += kLinRowsChunk * kWaves) {
+        i32x4 fw[4], fx[4];
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {                 // all eight loads leave before the first product
+            const i32x4 zero = {0, 0, 0, 0};
+            fw[s] = fx[s] = zero;
+            if (k0 + 32 * s + 16 * half < a.K) {
+                fw[s] = *reinterpret_cast<const i32x4*>(wrow + k0 + 32 * s);
+                fx[s] = *reinterpret_cast<const i32x4*>(xrow + k0 + 32 * s);
+            }
+        }
+#pragma unroll
+        for (int s = 0; s < 4; ++s)
+            if (k0 + 32 * s < a.K) acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(fw[s], fx[s], acc, 0, 0, 0);      // uniform
+    }
+    if (w) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) s_part[w - 1][r][lane] = acc[r];
+    }
+    __syncthreads();
+    if (w) return;
+#pragma unroll
+    for (int v = 0; v < kWaves - 1; ++v)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[r] += s_part[v][r][lane];
+    lin_store_tile(a, acc, l31, n0, half, zx, sx);
+}
+
+static bool lin_quant_ok(int mode, int quant_min, int quant_max) {
+    return dec_mode_ok(mode) && quant_min <= quant_max && static_cast<int64_t>(quant_max) - quant_min <= 255;
+}
+
+static bool lin_k_ok(int64_t cols) { return cols >= 16 && cols <= kLinMaxK && cols % 16 == 0; }
+
+}  // namespace osq
+
+using namespace osq;
+
+extern "C" int osq_activation_codes(const float* x, int64_t rows, int64_t cols, int64_t row_stride, uint8_t* codes,
+                                    int32_t* rowsum, float* x_scale, void* x_zero_point, int x_zp_type, int x_mode,
+                                    float x_grad_factor, int x_quant_min, int x_quant_max, osq_stream stream) {
+    OSQ_REQUIRE(rows >= 0 && rows <= INT32_MAX, "activation_codes: bad row count");
+    OSQ_REQUIRE(lin_k_ok(cols), "activation_codes: the row length must be a multiple of 16 in [16, 16384]");
+    OSQ_REQUIRE(x_scale && x_zero_point, "activation_codes: null scale or zero_point");
+    OSQ_REQUIRE(x_zp_type == OSQ_ZP_INT32 || x_zp_type == OSQ_ZP_FLOAT32, "activation_codes: bad zp_type");
+    OSQ_REQUIRE(lin_quant_ok(x_mode, x_quant_min, x_quant_max), "activation_codes: bad mode, or more than 256 codes");
+    if (rows == 0) return OSQ_OK;
+    OSQ_REQUIRE(x && codes && rowsum, "activation_codes: null tensor");
+    OSQ_REQUIRE(row_stride >= cols && row_stride % 4 == 0 && aligned16(x), "activation_codes: x rows are not 16-byte aligned");
+    OSQ_REQUIRE((reinterpret_cast<uintptr_t>(codes) & 3u) == 0 && (reinterpret_cast<uintptr_t>(rowsum) & 3u) == 0,
+                "activation_codes: codes / rowsum not 4-byte aligned");
+    const int grid = grid_for(rows, kLinThreads / OSQ_WAVE, kMaxBlocks * 2);
+    hipLaunchKernelGGL(activation_codes_kernel, dim3(grid), dim3(kLinThreads), 0, static_cast<hipStream_t>(stream), x, row_stride,
+                       codes, rowsum, rows, static_cast<int>(cols), OSQ_DEC_QUANT(x));
+    return check_launch("activation_codes");
+}
+
+extern "C" int osq_weight_codes_sums(const float* w, int64_t rows, int64_t cols, int64_t channels, uint8_t* codes,
+                                     int32_t* colsum, float* scale_eff, int32_t* zw, int32_t* bad, const float* scale,
+                                     const void* zero_point, int zp_type, int mode, float grad_factor, int quant_min,
+                                     int quant_max, osq_stream stream) {
+    OSQ_REQUIRE(rows >= 0 && rows <= INT32_MAX, "weight_codes_sums: bad row count");
+    OSQ_REQUIRE(lin_k_ok(cols), "weight_codes_sums: the row length must be a multiple of 16 in [16, 16384]");
+    OSQ_REQUIRE(channels == 1 || channels == rows, "weight_codes_sums: one scale, or one per row");
+    OSQ_REQUIRE(scale && zero_point, "weight_codes_sums: null scale or zero_point");
+    OSQ_REQUIRE(zp_type == OSQ_ZP_INT32 || zp_type == OSQ_ZP_FLOAT32, "weight_codes_sums: bad zp_type");
+    OSQ_REQUIRE(mode >= OSQ_PARAM_FIXED && mode <= OSQ_PARAM_LSQPLUS, "weight_codes_sums: bad mode");
+    OSQ_REQUIRE(quant_min <= quant_max && static_cast<int64_t>(quant_max) - quant_min <= 255, "weight_codes_sums: more than 256 codes");
+    if (rows == 0) return OSQ_OK;
+    OSQ_REQUIRE(w && codes && colsum && scale_eff && zw && bad, "weight_codes_sums: null tensor");
+    OSQ_REQUIRE(aligned16(w) && (reinterpret_cast<uintptr_t>(codes) & 3u) == 0, "weight_codes_sums: w not 16-byte or codes not 4-byte aligned");
+    const int grid = grid_for(rows, kLinThreads / OSQ_WAVE, kMaxBlocks * 2);
+    hipLaunchKernelGGL(weight_codes_kernel, dim3(grid), dim3(kLinThreads), 0, static_cast<hipStream_t>(stream), w, codes, colsum,
+                       scale_eff, zw, bad, rows, channels, static_cast<int>(cols), scale, zero_point, zp_type, mode, grad_factor,
+                       static_cast<float>(quant_min), static_cast<float>(quant_max));
+    return check_launch("weight_codes_sums");
+}
+
+extern "C" int osq_linear_int(const uint8_t* x_codes, const int32_t* x_rowsum, const uint8_t* w_codes, const int32_t* w_colsum,
+                              const float* w_scale, const int32_t* w_zw, const int32_t* w_bad, const float* bias, float* out,
+                              int64_t rows, int64_t channels, int64_t cols, float* x_scale, void* x_zero_point, int x_zp_type,
+                              int x_mode, float x_grad_factor, int x_quant_min, int x_quant_max, osq_stream stream) {
+    OSQ_REQUIRE(rows >= 0 && rows <= INT32_MAX && channels >= 0 && channels <= INT32_MAX, "linear_int: bad shape");
+    OSQ_REQUIRE(lin_k_ok(cols), "linear_int: K must be a multiple of 16 in [16, 16384]");
+    OSQ_REQUIRE(x_scale && x_zero_point, "linear_int: null scale or zero_point");
+    OSQ_REQUIRE(x_zp_type == OSQ_ZP_INT32 || x_zp_type == OSQ_ZP_FLOAT32, "linear_int: bad zp_type");
+    OSQ_REQUIRE(lin_quant_ok(x_mode, x_quant_min, x_quant_max), "linear_int: bad mode, or more than 256 codes");
+    if (rows == 0 || channels == 0) return OSQ_OK;
+    OSQ_REQUIRE(x_codes && x_rowsum && w_codes && w_colsum && w_scale && w_zw && w_bad && out, "linear_int: null tensor");
+    OSQ_REQUIRE(aligned16(x_codes) && aligned16(w_codes), "linear_int: codes not 16-byte aligned");
+    OSQ_REQUIRE(((reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(bias) | reinterpret_cast<uintptr_t>(x_rowsum) |
+                  reinterpret_cast<uintptr_t>(w_colsum) | reinterpret_cast<uintptr_t>(w_scale) | reinterpret_cast<uintptr_t>(w_zw)) & 3u) == 0,
+                "linear_int: a tensor is not 4-byte aligned");
+    const int vec = channels % 4 == 0 && aligned16(out) && aligned16(w_colsum) && aligned16(w_scale) && aligned16(w_zw) && aligned16(bias);
+    const LinArgs a{x_codes, w_codes, x_rowsum, w_colsum, w_zw, w_bad, w_scale, bias, out, static_cast<int>(rows),
+                    static_cast<int>(channels), static_cast<int>(cols), vec, OSQ_DEC_QUANT(x)};
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (rows <= kLinRowsM) {
+        hipLaunchKernelGGL(linear_int_rows_kernel, dim3(static_cast<unsigned>((channels + 31) / 32)), dim3(kLinThreads), 0, st, a);
+    } else {
+        const int64_t blocks = ((rows + kLinTile - 1) / kLinTile) * ((channels + kLinTile - 1) / kLinTile);
+        OSQ_REQUIRE(blocks <= INT32_MAX, "linear_int: too many tiles");
+        hipLaunchKernelGGL(linear_int_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kLinThreads), 0, st, a);
+    }
+    return check_launch("linear_int");
+}

@@ -28,6 +28,7 @@ from .losses import LmLossInfo, classification_loss, lm_loss, span_loss, token_l
 from .. import ops
 from .. import util_layernorm as _UL
 from ..quantization import QuantizedModule, Quantizer
+from ..quantization.linear_int import shared_codes
 from ..util_layernorm import (GammaResidual, QuantizedLayerNorm, activation_fake_quant, attention_probs_fake_quant,
                               attention_sequence_fake_quant,
                               decode_attention_at_fake_quant, decode_attention_fake_quant, decode_attention_shared_fake_quant,
@@ -848,6 +849,10 @@ class QuantizedBartEncoderLayer(QuantizedModule):
         return nn.functional.dropout(x, p=p, training=self.training)
 
     def forward(self, hidden_states, attention_mask, observation_mask=None):
+        with shared_codes():       # FUSE_LINEAR_INT: q_proj / k_proj / v_proj read one set of activation codes
+            return self._forward(hidden_states, attention_mask, observation_mask)
+
+    def _forward(self, hidden_states, attention_mask, observation_mask):
         residual = hidden_states
         h = self._drop(self.self_attn(hidden_states, attention_mask=attention_mask, observation_mask=observation_mask),
                        self.dropout)
@@ -893,6 +898,12 @@ class QuantizedBartDecoderLayer(QuantizedModule):
                 observation_mask=None, past_key_value=None, cross_group=1):
         """``past_key_value``: None, or this layer's slot of a QuantizedBartCache (extended in place).  ``cross_group``: the
         rows of ``hidden_states`` per row of the encoder's states and mask (QuantizedBartAttention.forward; no cache)."""
+        with shared_codes():       # FUSE_LINEAR_INT: the projections that read one tensor read one set of activation codes
+            return self._forward(hidden_states, attention_mask, encoder_hidden_states, encoder_attention_mask, observation_mask,
+                                 past_key_value, cross_group)
+
+    def _forward(self, hidden_states, attention_mask, encoder_hidden_states, encoder_attention_mask, observation_mask,
+                 past_key_value, cross_group):
         def attn(module, x, **kw):
             if past_key_value is None:
                 return module(x, observation_mask=observation_mask, **kw)

@@ -21,6 +21,7 @@ from torch import nn
 from .losses import classification_loss, span_loss, with_loss
 
 from ..quantization import QuantizedModule, Quantizer
+from ..quantization.linear_int import shared_codes
 from ..util_layernorm import (GammaResidual, QuantizedLayerNorm, activation_fake_quant, attention_probs_fake_quant,
                               attention_sequence_fake_quant,
                               merge_heads_fake_quant, qkv_heads_fake_quant, residual_layernorm)
@@ -172,9 +173,10 @@ class QuantizedBertLayer(QuantizedModule):
         self.output = QuantizedBertOutput(org_module.output, w_qconfig, a_qconfig, qoutput=qoutput, backend=backend)
 
     def forward(self, hidden_states, attention_mask=None, observation_mask=None):
-        att = self.attention(hidden_states, attention_mask, observation_mask=observation_mask)
-        inter = self.intermediate(att, observation_mask=observation_mask)
-        return self.output(inter, att, observation_mask=observation_mask)
+        with shared_codes():       # FUSE_LINEAR_INT: query / key / value read one set of activation codes
+            att = self.attention(hidden_states, attention_mask, observation_mask=observation_mask)
+            inter = self.intermediate(att, observation_mask=observation_mask)
+            return self.output(inter, att, observation_mask=observation_mask)
 
 
 class QuantizedBertEncoder(QuantizedModule):

@@ -88,9 +88,10 @@ class QuantizedRobertaLayer(QuantizedModule):
         self.output = QuantizedRobertaOutput(org_module.output, w_qconfig, a_qconfig, qoutput=qoutput, backend=backend)
 
     def forward(self, hidden_states, attention_mask=None, observation_mask=None):
-        att = self.attention(hidden_states, attention_mask, observation_mask=observation_mask)
-        inter = self.intermediate(att, observation_mask=observation_mask)
-        return self.output(inter, att, observation_mask=observation_mask)
+        with B.shared_codes():     # FUSE_LINEAR_INT: query / key / value read one set of activation codes
+            att = self.attention(hidden_states, attention_mask, observation_mask=observation_mask)
+            inter = self.intermediate(att, observation_mask=observation_mask)
+            return self.output(inter, att, observation_mask=observation_mask)
 
 
 class QuantizedRobertaEncoder(QuantizedModule):

@@ -2194,6 +2194,131 @@ def attention_int_fake_quant(q, k, v, mask, q_quant, k_quant, v_quant, probs_qua
 
 
 # ---------------------------------------------------------------------------------------
+# integer linear: a frozen model's linear layers on the integer codes of both operands (csrc/linear_int.hip)
+# ---------------------------------------------------------------------------------------
+
+LINEAR_INT_TILE = 128          # kLinTile of csrc/linear_int.hip: rows of x and channels of a workgroup's tile (a wave: 64 x 64)
+LINEAR_INT_KSTEP = 64          # kLinKStep: code bytes of a row per step, two k-steps of v_mfma_i32_32x32x32_i8
+LINEAR_INT_ROWS_M = 32         # kLinRowsM: up to here the kernel that splits channels over workgroups and K over waves
+LINEAR_INT_MAX_K = 16384       # kLinMaxK
+LINEAR_INT_MAX_RANGE = 255     # quant_max - quant_min of both quantizers
+LINEAR_INT_NO_ROW = -2 ** 31   # kLinNoRow: the row sum of a row with an element that has no code
+
+
+class WeightCodes(NamedTuple):
+    """A frozen [N, K] weight as the integer linear launch reads it (include/osq_hip.h, "integer linear"): codes uint8 [N, K]
+    holding b = u - 128 as int8; colsum int32 [N] = sum_k b; scale fp32 [N], the effective s_w; zw int32 [N]; bad int32 [1],
+    set when a zero point is no integer inside the range or an element has no code (the launch then writes NaN everywhere)."""
+    codes: torch.Tensor
+    colsum: torch.Tensor
+    scale: torch.Tensor
+    zw: torch.Tensor
+    bad: torch.Tensor
+
+
+def linear_int_refusal(k, record, *tensors, fp32=(), last_dim=()):
+    """Why the integer linear launches do not take reduction length ``k``, activation record ``record`` = (scale, zero_point,
+    quant_min, quant_max, ...) and ``tensors`` -- one phrase -- or None.  ``fp32``: tensors that must be float32; ``last_dim``:
+    tensors whose last dimension must be contiguous.  Where the tensors live is asked last."""
+    scale, zero_point, quant_min, quant_max = record[:4]
+    if scale.numel() != 1 or zero_point.numel() != 1:
+        return "the activation record is per-channel"
+    if int(quant_max) - int(quant_min) > LINEAR_INT_MAX_RANGE:
+        return "a quantizer has more than 256 codes"
+    if k % 16:
+        return "K is not a multiple of 16"
+    if k > LINEAR_INT_MAX_K:
+        return "K exceeds 16384"
+    if any(t is not None and t.dtype != torch.float32 for t in (scale,) + tuple(fp32)):
+        return "an input is not fp32"
+    if any(t.dim() == 0 or t.stride(-1) != 1 for t in last_dim if t.numel()):
+        return "the last dimension is not contiguous"
+    if not all(t.is_cuda for t in (scale, zero_point) + tuple(tensors) + tuple(fp32) + tuple(last_dim) if t is not None):
+        return "a tensor is not on a GPU"
+    return None
+
+
+def activation_codes(x, record):
+    """(codes, rowsum) of x [..., K] fp32, the output of the per-tensor quantizer ``record`` = (scale, zero_point, quant_min,
+    quant_max, mode, grad_factor): codes uint8 of x's shape holding a = u - 128 as int8, rowsum int32 [...] = sum_k a
+    (LINEAR_INT_NO_ROW for a row with a non-finite element).  One launch, no host sync.  ValueError, nothing launched or
+    allocated: what linear_int_refusal names."""
+    k = x.shape[-1] if x.dim() else 0
+    why = linear_int_refusal(k, record, fp32=(x,), last_dim=(x,))
+    if why:
+        raise ValueError(f"activation_codes: {why}")
+    lib = _hip.load()
+    scale, zero_point, quant_min, quant_max, mode, grad_factor = record
+    lead = tuple(x.shape[:-1])
+    if x.is_contiguous() and x.data_ptr() % 16 == 0:
+        x2, ldx = x, k
+    elif x.dim() == 2 and x.stride(0) % 4 == 0 and x.stride(0) >= k and x.data_ptr() % 16 == 0:
+        x2, ldx = x, x.stride(0)
+    else:
+        x2, ldx = x.contiguous(), k
+        if x2.data_ptr() % 16:
+            x2 = x2.clone()
+    rows = x.numel() // k if k else 0
+    codes = torch.empty(lead + (k,), dtype=torch.uint8, device=x.device)
+    rowsum = torch.empty(lead, dtype=torch.int32, device=x.device)
+    _hip.check(lib.osq_activation_codes(_hip.ptr(x2), rows, k, ldx, _hip.ptr(codes), _hip.ptr(rowsum), _hip.ptr(scale),
+                                        _hip.ptr(zero_point), _zp_type(zero_point), int(mode), float(grad_factor), int(quant_min),
+                                        int(quant_max), _hip.stream_ptr(x.device)), "activation_codes")
+    return codes, rowsum
+
+
+def weight_codes(weight, scale, zero_point, ch_axis, quant_min, quant_max, mode=PARAM_FIXED, grad_factor=1.0):
+    """``WeightCodes`` of a dense fp32 [N, K] weight under its quantizer's raw parameters (ch_axis 0: one per row; -1: one),
+    mode and grad factor as quantize_codes takes them: the bytes are quantize_codes' u minus 128.  One launch."""
+    if ch_axis not in (0, -1) or weight.dim() != 2:
+        raise ValueError("weight_codes: a [N, K] weight quantized per row (ch_axis 0) or per tensor (ch_axis -1)")
+    n, k = weight.shape
+    why = linear_int_refusal(k, (scale[:1], zero_point[:1], quant_min, quant_max), zero_point, fp32=(weight, scale))
+    if why is None and not weight.is_contiguous():
+        why = "the weight is not dense"
+    if why:
+        raise ValueError(f"weight_codes: {why}")
+    lib = _hip.load()
+    channels = n if ch_axis == 0 else 1
+    _check_per_channel("weight_codes", channels, scale, zero_point)
+    dev = weight.device
+    codes = torch.empty((n, k), dtype=torch.uint8, device=dev)
+    colsum, zw = torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.int32, device=dev)
+    s_eff = torch.empty(n, dtype=torch.float32, device=dev)
+    bad = torch.zeros(1, dtype=torch.int32, device=dev)
+    _hip.check(lib.osq_weight_codes_sums(_hip.ptr(weight), n, k, channels, _hip.ptr(codes), _hip.ptr(colsum), _hip.ptr(s_eff),
+                                         _hip.ptr(zw), _hip.ptr(bad), _hip.ptr(scale), _hip.ptr(zero_point), _zp_type(zero_point),
+                                         mode & PARAM_MODE_MASK, float(grad_factor), int(quant_min), int(quant_max),
+                                         _hip.stream_ptr(dev)), "weight_codes_sums")
+    return WeightCodes(codes, colsum, s_eff, zw, bad)
+
+
+def linear_int(x_codes, x_rowsum, x_record, w_entry, bias=None):
+    """out [..., N] fp32 of the rule "integer linear" of include/osq_hip.h from ``activation_codes``' (x_codes [..., K],
+    x_rowsum [...]) under the record they were made with and a ``WeightCodes`` entry: exact int32 sums on the int8 matrix
+    instruction, then (float)N * (s_x * s_w[c]) + bias[c].  One launch, no host sync, legal inside a stream capture.
+    ValueError, nothing launched or allocated: a per-channel activation record, more than 256 codes, K % 16 != 0, K > 16384, a
+    bias that is not fp32, CPU tensors, codes whose last dimension is not contiguous, operands of other shapes than these."""
+    k = x_codes.shape[-1] if x_codes.dim() else 0
+    why = linear_int_refusal(k, x_record, x_rowsum, *w_entry, fp32=(bias,), last_dim=(x_codes,))
+    n = w_entry.codes.shape[0]
+    if why is None and (x_codes.dtype != torch.uint8 or not x_codes.is_contiguous() or tuple(w_entry.codes.shape) != (n, k)
+                        or tuple(x_rowsum.shape) != tuple(x_codes.shape[:-1]) or not x_rowsum.is_contiguous()
+                        or (bias is not None and (tuple(bias.shape) != (n,) or not bias.is_contiguous()))):
+        why = "the operands are not dense codes [..., K], row sums [...], a WeightCodes [N, K] and a bias [N]"
+    if why:
+        raise ValueError(f"linear_int: {why}")
+    lib = _hip.load()
+    scale, zero_point, quant_min, quant_max, mode, grad_factor = x_record
+    out = torch.empty(tuple(x_codes.shape[:-1]) + (n,), dtype=torch.float32, device=x_codes.device)
+    _hip.check(lib.osq_linear_int(_hip.ptr(x_codes), _hip.ptr(x_rowsum), _hip.ptr(w_entry.codes), _hip.ptr(w_entry.colsum),
+                                  _hip.ptr(w_entry.scale), _hip.ptr(w_entry.zw), _hip.ptr(w_entry.bad), _hip.ptr(bias), _hip.ptr(out),
+                                  x_rowsum.numel(), n, k, _hip.ptr(scale), _hip.ptr(zero_point), _zp_type(zero_point), int(mode),
+                                  float(grad_factor), int(quant_min), int(quant_max), _hip.stream_ptr(out.device)), "linear_int")
+    return out
+
+
+# ---------------------------------------------------------------------------------------
 # one decoding step's attention over the KV cache: scores, mask, softmax, two quantizers in one launch
 # ---------------------------------------------------------------------------------------
 

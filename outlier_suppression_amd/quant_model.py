@@ -83,5 +83,6 @@ def quantize_model(fp_model, w_qconfig, a_qconfig=None, backend="academic", is_r
     fp_model.eval()
     model = _WRAPPERS[cls](copy.deepcopy(fp_model), w_qconfig, a_qconfig, qoutput=False, backend=backend,
                            is_remove_padding=is_remove_padding)
+    from .quantization.linear_int import bind_linear_producers
     from .quantization.weight_cache import adopt
-    return adopt(model.eval())
+    return adopt(bind_linear_producers(model.eval()))

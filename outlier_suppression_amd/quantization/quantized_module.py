@@ -6,6 +6,8 @@ new module of the Q-type with cloned parameters and a child named ``weight_fake_
 that fake-quantises the weight on every forward (quantized_module.py:56,72,98); any other
 module is returned unchanged.
 """
+import sys
+
 import torch.nn.functional as F
 from torch import nn
 
@@ -64,12 +66,25 @@ def WeightQuantizer(w_qconfig):
     return _build_quantizer(w_qconfig)
 
 
+def _linear_int_on():
+    """util_layernorm.FUSE_LINEAR_INT, read where it lives (that module imports this package: it is looked up, not imported)."""
+    ul = sys.modules.get("outlier_suppression_amd.util_layernorm")
+    return ul is not None and ul.FUSE_LINEAR_INT
+
+
 class QLinear(QuantizedOperator, nn.Linear):
     def __init__(self, in_features, out_features, bias, w_qconfig):
         super().__init__(in_features=in_features, out_features=out_features, bias=bias)
         self.weight_fake_quant = WeightQuantizer(w_qconfig)
 
     def forward(self, input):
+        if _linear_int_on():
+            # FUSE_LINEAR_INT: a frozen model's product on the integer codes of both operands (quantization/linear_int.py);
+            # anything it does not take keeps the line below, with the reason in util_layernorm.linear_int
+            from . import linear_int
+            out = linear_int.forward(self, input)
+            if out is not None:
+                return out
         return F.linear(input, self._quantized_weight(), self.bias)
 
 

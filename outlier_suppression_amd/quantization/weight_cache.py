@@ -34,6 +34,7 @@ enabled = True        # False: every forward fake-quantises every weight in its 
 # Kept beside the modules, not inside them: nothing here is state of the model (state_dict, deepcopy and pickling see
 # the reference's attributes only), and entries die with their module.
 _CACHE = weakref.WeakKeyDictionary()     # operator -> (key, fake-quantised weight)
+_CODES = weakref.WeakKeyDictionary()     # operator -> (key, ops.WeightCodes of its weight): the integer linear launch's operand
 _OWNER = weakref.WeakKeyDictionary()     # operator -> weakref(model it was adopted by)
 _PLAN = weakref.WeakKeyDictionary()      # model -> (pointer key, device table, row ends, output views, total rows)
 
@@ -75,6 +76,26 @@ def quantized_weight(op):
     return y
 
 
+def weight_codes(op):
+    """The ``ops.WeightCodes`` of ``op``'s frozen weight for the integer linear launch (quantization/linear_int.py), kept
+    beside the fake-quantised weight under the same key: whatever invalidates that entry invalidates this one.  The caller
+    has checked ``cacheable``.  None while a stream capture is open and there is no valid entry: the codes are made
+    outside a graph's memory pool."""
+    fq = op.weight_fake_quant
+    entry = _CODES.get(op)
+    if entry is not None and entry[0] == _key(op, fq):
+        return entry[1]
+    if torch.cuda.is_current_stream_capturing():
+        return None
+    if fq.param_mode != ops.PARAM_FIXED:
+        quantized_weight(op)          # a learnable quantizer repairs its parameters in place on its first call: before the key
+    w = op.weight.detach()
+    rec = ops.weight_codes(w, fq.scale.detach(), fq.zero_point.detach(), fq.ch_axis, fq.quant_min, fq.quant_max, fq.param_mode,
+                           fq._grad_factor(w) if fq.param_mode != ops.PARAM_FIXED else 1.0)
+    _CODES[op] = (_key(op, fq), rec)
+    return rec
+
+
 def adopt(model):
     """Tell every weight-quantized operator of ``model`` which model it belongs to, so that the first stale entry met in
     a forward refreshes all of them in one launch (without it every operator refreshes its own)."""
@@ -88,6 +109,7 @@ def adopt(model):
 def invalidate(model):
     for m in model.modules():
         _CACHE.pop(m, None)
+        _CODES.pop(m, None)
     _PLAN.pop(model, None)
 
 

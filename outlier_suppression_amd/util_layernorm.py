@@ -83,6 +83,17 @@ off by default; it needs all four quantizers per-tensor with at most 256 codes, 
 are on.  ``outlier_suppression_amd.set_fast_attention_int(True)`` / ``OSQ_FAST_ATTENTION_INT=1`` turn it on; the measured
 outcome per shape is in profiles/attention_int_ab.txt and README.
 
+``FUSE_LINEAR_INT`` (default OFF) takes the same observation to the linear layers, the one large cost left outside this
+package's kernels: in a frozen model a ``QLinear`` multiplies its weight quantizer's codes by the codes of the per-tensor
+activation quantizer that produced its input, so the product runs exactly on the int8 matrix instruction
+(``ops.activation_codes`` + ``ops.linear_int``, csrc/linear_int.hip; the rule is in include/osq_hip.h, "integer linear") and
+the scales are applied once to the int32 sum.  ``quantize_model`` tells each linear its producer (quantization/linear_int.py,
+``bind_linear_producers``; the binding survives gamma migration); the codes of one producer output are made once per block
+and shared by its consumers.  Autograd off, evaluation mode, both quantizers in the plain quantising state, at most 256 codes, K a multiple of 16 up to 16384; anything else runs
+``F.linear`` and ``util_layernorm.linear_int`` (fused, eager, reason) says why.  Tolerance-equal to ``F.linear`` (closer to
+float64 than it), hence off by default.  ``outlier_suppression_amd.set_fast_linear_int(True)`` / ``OSQ_FAST_LINEAR_INT=1``
+turn it on; the measured outcome per shape is in profiles/linear_int_ab.txt and README.
+
 ``CACHE_CODES`` (default OFF) is no fusion but a storage format: new KV caches (model/quant_bart.py, QuantizedBartCache) hold
 integer codes, one byte per element, written by ``ops.fake_quant_kv_append_codes`` and read as they are by
 ``ops.decode_attention_codes`` (csrc/kv_codes.hip, csrc/decode_attention.hip); the words computed are those of the fp32 cache.
@@ -165,6 +176,7 @@ FUSE_SOFTMAX = False     # the attention-probabilities site as one launch (toler
 FUSE_DECODE_ATTENTION = False   # a cached decoding step's attention after the append as one launch (tolerance-equal; set_fast_decode_attention / OSQ_FAST_DECODE_ATTENTION=1)
 FUSE_ATTENTION = False   # an attention block over a whole sequence as one launch (tolerance-equal; set_fast_attention / OSQ_FAST_ATTENTION=1)
 FUSE_ATTENTION_INT = False   # an attention block over a whole sequence as one launch on the quantizers' integer codes, exact products on the bf16 matrix instruction, tried before FUSE_ATTENTION (tolerance-equal to eager; set_fast_attention_int / OSQ_FAST_ATTENTION_INT=1)
+FUSE_LINEAR_INT = False  # a frozen model's QLinear on the integer codes of its weight and of the quantizer that produced its input, exact products on the int8 matrix instruction (tolerance-equal to F.linear; set_fast_linear_int / OSQ_FAST_LINEAR_INT=1)
 FUSE_KV_APPEND = True    # incremental decoding: a step's q / k / v sites + KV-cache append (+ beam reorder) as one launch (bit-identical)
 GRAPH_DECODE = False     # generate(): capture a cached decoding step into a graph and replay it (set_graph_decode / OSQ_GRAPH_DECODE=1 / generate(graph=True))
 BEAM_SELECT = False      # generate(): a beam step's log-softmax + processors + score add + top-k as one kernel call (tolerance-equal; set_beam_select / OSQ_BEAM_SELECT=1 / generate(beam_select=True))
@@ -236,6 +248,24 @@ class HeadsBackwardInfo:
 
 
 heads_backward = HeadsBackwardInfo()
+
+
+class LinearIntInfo:
+    """What the ``QLinear`` calls did under FUSE_LINEAR_INT since ``reset()``: ``fused`` calls that took the integer launches,
+    ``eager`` calls that ran ``F.linear``, and the ``reason`` of the last of those (``util_layernorm.linear_int``).  With the
+    switch off nothing is counted."""
+
+    def __init__(self):
+        self.reset()
+
+    def reset(self):
+        self.fused, self.eager, self.reason = 0, 0, None
+
+    def __repr__(self):
+        return f"LinearIntInfo(fused={self.fused}, eager={self.eager}, reason={self.reason!r})"
+
+
+linear_int = LinearIntInfo()
 
 
 def _autograd_site_why_not(q, x, first=None):
