@@ -2273,19 +2273,23 @@ def weight_codes(weight, scale, zero_point, ch_axis, quant_min, quant_max, mode=
     if ch_axis not in (0, -1) or weight.dim() != 2:
         raise ValueError("weight_codes: a [N, K] weight quantized per row (ch_axis 0) or per tensor (ch_axis -1)")
     n, k = weight.shape
-    why = linear_int_refusal(k, (scale[:1], zero_point[:1], quant_min, quant_max), zero_point, fp32=(weight, scale))
+    channels = n if ch_axis == 0 else 1
+    # the refusals go by the first channel's parameters; a [0, K] weight quantized per row has none, and nothing to encode
+    first = (scale[:1], zero_point[:1]) if channels else (weight.new_ones(1), weight.new_zeros(1))
+    why = linear_int_refusal(k, first + (quant_min, quant_max), zero_point, fp32=(weight, scale))
     if why is None and not weight.is_contiguous():
         why = "the weight is not dense"
     if why:
         raise ValueError(f"weight_codes: {why}")
     lib = _hip.load()
-    channels = n if ch_axis == 0 else 1
     _check_per_channel("weight_codes", channels, scale, zero_point)
     dev = weight.device
     codes = torch.empty((n, k), dtype=torch.uint8, device=dev)
     colsum, zw = torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.int32, device=dev)
     s_eff = torch.empty(n, dtype=torch.float32, device=dev)
     bad = torch.zeros(1, dtype=torch.int32, device=dev)
+    if n == 0:
+        return WeightCodes(codes, colsum, s_eff, zw, bad)
     _hip.check(lib.osq_weight_codes_sums(_hip.ptr(weight), n, k, channels, _hip.ptr(codes), _hip.ptr(colsum), _hip.ptr(s_eff),
                                          _hip.ptr(zw), _hip.ptr(bad), _hip.ptr(scale), _hip.ptr(zero_point), _zp_type(zero_point),
                                          mode & PARAM_MODE_MASK, float(grad_factor), int(quant_min), int(quant_max),

@@ -28,19 +28,23 @@ def reference(m, n, k):
     return case, LI.rule(*case)
 
 
-def operands(case, dev, zp_int=True):
+def operands(case, dev, zp_int=True, x_mode=0, x_g=1.0, w_mode=0, w_g=1.0, w_zp_int=None):
+    """The launches' operands from a case whose parameters are the RAW words of both quantizers: under the default mode,
+    PARAM_FIXED, they are the effective ones LI.rule takes; under another (x_mode may carry PARAM_SANITIZE) LI.effective_case
+    says what the rule takes.  Zero points are int32 (zp_int / w_zp_int; the weight's follows the input's unless given) or
+    float32."""
     from outlier_suppression_amd import ops
     x, xq, w, wq, bias = case
-    (xs, xz), (ws, wz) = ((torch.from_numpy(q.scale).to(dev), torch.from_numpy(q.zero_point).to(dev).to(torch.int32 if zp_int else torch.float32))
-                          for q in (xq, wq))
-    entry = ops.weight_codes(torch.from_numpy(w).to(dev), ws, wz, 0 if ws.numel() > 1 else -1, wq.qmin, wq.qmax)
-    return (torch.from_numpy(x).to(dev), (xs, xz, xq.qmin, xq.qmax, ops.PARAM_FIXED, 1.0), entry,
+    (xs, xz), (ws, wz) = ((torch.from_numpy(q.scale).to(dev), torch.from_numpy(q.zero_point).to(dev).to(torch.int32 if as_int else torch.float32))
+                          for q, as_int in ((xq, zp_int), (wq, zp_int if w_zp_int is None else w_zp_int)))
+    entry = ops.weight_codes(torch.from_numpy(w).to(dev), ws, wz, 0 if ws.numel() > 1 else -1, wq.qmin, wq.qmax, w_mode, w_g)
+    return (torch.from_numpy(x).to(dev), (xs, xz, xq.qmin, xq.qmax, x_mode, x_g), entry,
             None if bias is None else torch.from_numpy(bias).to(dev))
 
 
-def run(case, dev, zp_int=True):
+def run(case, dev, zp_int=True, **modes):
     from outlier_suppression_amd import ops
-    x, record, entry, bias = operands(case, dev, zp_int)
+    x, record, entry, bias = operands(case, dev, zp_int, **modes)
     codes, rowsum = ops.activation_codes(x, record)
     return tuple(t.cpu().numpy() for t in (ops.linear_int(codes, rowsum, record, entry, bias), codes, rowsum))
 

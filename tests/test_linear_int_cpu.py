@@ -103,3 +103,77 @@ def test_routing_falls_back_with_a_reason_and_binding_adds_no_state(tiny):
     assert names() == bound and len(linears) == 2 * 6 + 2
     linear_int.bind_linear_producers(tiny)
     assert names() == bound and all(linear_int.producer_of(m) is not None for m in linears)
+
+
+# ---- the helpers and cases of tests/test_gpu_linear_int_edges.py, without a GPU ---------------------------------------------
+
+@pytest.mark.parametrize("g_kind", LI.GRAD_FACTORS, ids=str)
+@pytest.mark.parametrize("what", ("good",) + LI.REPAIRS + ("NaN scale",))
+@pytest.mark.parametrize("mode", ("lsq", "lsqplus"))
+def test_helpers_against_the_modules_torch_arithmetic(mode, what, g_kind):
+    """LI.repaired and LI.effective against the arithmetic of LSQFakeQuantize / LSQPlusFakeQuantize.forward with the observer
+    off, in torch on the CPU: the in-place repair (fake_quant.py:152-153 / 188-191: scale.abs_(), scale.clamp_(min=eps),
+    zero_point.clamp_(qmin, qmax) for LSQ+), then util_quant.py:29-34 / 48-55 with this package's round_ste and grad_scale.
+    The modules themselves take GPU tensors only; tests/test_gpu_linear_int_edges.py runs them.  Compared word for word: the
+    parameters left behind and the fake-quantised output."""
+    from outlier_suppression_amd.quantization.util_quant import grad_scale, round_ste
+    m = 2
+    (x, xq, *_), g, zp_int = LI.repair_case(m, mode, what if what in LI.REPAIRS else LI.REPAIRS[0])
+    if what not in LI.REPAIRS:
+        xq = xq._replace(scale=np.abs(xq.scale) if what == "good" else np.full(1, np.nan, np.float32))
+    g = LI.grad_factor(g_kind, m, x.shape[1], xq.qmax)
+    scale, zp = torch.from_numpy(xq.scale.copy()), torch.from_numpy(xq.zero_point.copy()).to(torch.int32 if zp_int else torch.float32)
+    scale.abs_()
+    scale.clamp_(min=torch.tensor([torch.finfo(torch.float32).eps]))
+    if mode == "lsqplus":
+        zp.clamp_(xq.qmin, xq.qmax)
+    left = LI.repaired(xq.scale, xq.zero_point, mode, not zp_int, xq.qmin, xq.qmax)
+    assert LI.words(scale.numpy()) == LI.words(left[0]) or (what == "NaN scale" and np.isnan(left[0]).all() and scale.isnan().all())
+    assert LI.words(zp.float().numpy()) == LI.words(left[1])
+    s, z = grad_scale(scale, g), (grad_scale(round_ste(zp), g) if mode == "lsqplus" else zp)
+    xt = torch.from_numpy(x)
+    x_quant = torch.clamp(round_ste(xt / s) + z, xq.qmin, xq.qmax)
+    y = ((x_quant - z) * s).numpy()
+    es, ez = LI.effective(*left, mode, g)
+    if what == "NaN scale":
+        assert np.isnan(es).all() and np.isnan(y).all()
+        return
+    assert LI.words(s.numpy()) == LI.words(es) and LI.words(z.float().numpy()) == LI.words(ez)
+    u = LI.units(x, xq._replace(scale=es, zero_point=ez))
+    assert not np.isnan(u).any() and y.dtype == np.float32
+    assert LI.words(y) == LI.words(((u.astype(np.float32) + np.float32(xq.qmin) - ez) * es).astype(np.float32))
+    assert LI.words(x_quant.numpy() - np.float32(xq.qmin)) == LI.words(u.astype(np.float32))
+
+
+@pytest.mark.parametrize("g_kind", LI.GRAD_FACTORS, ids=str)
+@pytest.mark.parametrize("x_mode", LI.MODES)
+@pytest.mark.parametrize("m", (2, 33))
+def test_mode_cases_have_teeth(m, x_mode, g_kind):
+    """The conditions the GPU test of the parameter modes states before it asks the GPU, here where a bad seed costs nothing:
+    the launch is good, the effective input scale is not the raw word, and the rule on the raw words of either quantizer
+    gives other words of out -- all NaN for the weight's fractional zero points."""
+    for w_mode in LI.W_MODES:
+        raw, g, want = LI.mode_reference(m, x_mode, g_kind, w_mode)
+        assert g == (0.3 if g_kind == 0.3 else 1.0 / (m * 144 * 255) ** 0.5) and want[0].shape == (m, LI.EDGE_N)
+        assert (x_mode == "lsqplus") == bool(raw[1].zero_point[0] % 1) and (w_mode == "lsqplus") == bool((raw[3].zero_point % 1).all())
+
+
+@pytest.mark.parametrize("mode", ("fixed", "lsq", "lsqplus"))
+@pytest.mark.parametrize("m", (2, 33))
+def test_repair_cases_are_what_they_say(m, mode):
+    """With the repair only an int32 zero point stays outside its range (all of out NaN); without it every zero point does,
+    and a negative or tiny scale alone leaves a good launch."""
+    for what in LI.REPAIRS:
+        for sanitize in (True, False):
+            raw, g, zp_int, left, want = LI.repair_reference(m, mode, what, sanitize and mode != "fixed")
+            outside = "zero point" in what and (zp_int or not sanitize or mode == "fixed")
+            assert np.isnan(want[0]).all() == outside and np.isfinite(want[0]).all() == (not outside)
+            assert zp_int == (mode != "lsqplus") and (want[2] != -2 ** 31).all()
+
+
+@pytest.mark.parametrize("k", LI.EDGE_KS)
+def test_edge_cases_stay_inside_the_rule(k):
+    """Every K of the GPU file's section A: |N| <= 255 * 255 * K (the rule's own assertion), no row without codes."""
+    for m in LI.EDGE_MS:
+        out, codes, rowsum = LI.rule(*LI.edge_case(m, k))
+        assert np.isfinite(out).all() and (rowsum != -2 ** 31).all() and codes.shape == (m, k)
