@@ -51,7 +51,7 @@ typedef void* osq_stream;
  *     osq_attention_fake_quant_shared, osq_attention_fake_quant_int_shared, osq_gelu_fake_quant_backward,
  *     osq_attention_softmax_fake_quant_backward, osq_residual_layernorm_fake_quant_backward, osq_fake_quant_heads_backward
  *     (with it osq_workspace_bytes() grew at its END: no earlier offset of the workspace moved), osq_activation_codes,
- *     osq_weight_codes_sums, osq_linear_int. */
+ *     osq_weight_codes_sums, osq_linear_int, osq_weight_codes_sums_w4, osq_linear_int_w4. */
 #define OSQ_ABI_VERSION 10
 
 typedef enum osq_status {
@@ -1221,7 +1221,18 @@ int osq_attention_fake_quant_int_shared(const float* q, const float* k, const fl
  * an integer inside [quant_min, quant_max], ALL of out is NaN.  rows <= 32 take a kernel that splits the channels over many
  * workgroups and K over a workgroup's waves (the words are the same: the sum is an integer).  16-byte aligned codes, 4-byte
  * aligned everything else.
- * All three: no allocation, no host synchronisation, no workspace, no floating-point atomics: legal inside a stream
+ *
+ * Packed 4-bit weights (a weight quantizer with quant_max - quant_min <= 15).  N[r,c] does not depend on the offset taken
+ * off the codes, so the packed pair takes none off the weight's:
+ *     b = uw (0 .. 15),  zw[c] = zp_w[c] - qmin_w,  colsum[c] = sum_k uw[c,k];  a, zx, rowsum as above
+ *     N[r,c] = sum_k a*b  - zw[c] * rowsum[r]  - zx * colsum[c]  + K * zx * zw[c]        the same integer, every term < 2**31
+ * and out is word-equal to the 8-bit pair's.  osq_weight_codes_sums_w4 takes osq_weight_codes_sums' arguments and writes
+ * codes [rows, cols / 2] bytes in the `code_bits 4` layout of "integer codes" (cols % 16 == 0: the flattened packing never
+ * crosses a row, so row r is cols / 2 contiguous bytes and codes is osq_quantize_codes' output byte for byte) with colsum,
+ * scale_eff, zw and *bad as defined here; it refuses quant_max - quant_min > 15.  osq_linear_int_w4 takes osq_linear_int's
+ * arguments with w_codes [channels, cols / 2] and the sums of osq_weight_codes_sums_w4; x_codes / x_rowsum are the same
+ * osq_activation_codes output either product reads.  NaN rows, *w_bad and the parameter repair are those of osq_linear_int.
+ * All five: no allocation, no host synchronisation, no workspace, no floating-point atomics: legal inside a stream
  * capture.  Inference only.  OSQ_ERR_INVALID_ARGUMENT, nothing launched: a limit above exceeded, a null or misaligned tensor,
  * a mode other than FIXED / LSQ / LSQ+ (+ SANITIZE for x). */
 int osq_activation_codes(const float* x, int64_t rows, int64_t cols, int64_t row_stride, uint8_t* codes, int32_t* rowsum,
@@ -1234,6 +1245,13 @@ int osq_linear_int(const uint8_t* x_codes, const int32_t* x_rowsum, const uint8_
                    const float* w_scale, const int32_t* w_zw, const int32_t* w_bad, const float* bias, float* out,
                    int64_t rows, int64_t channels, int64_t cols, float* x_scale, void* x_zero_point, int x_zp_type,
                    int x_mode, float x_grad_factor, int x_quant_min, int x_quant_max, osq_stream stream);
+int osq_weight_codes_sums_w4(const float* w, int64_t rows, int64_t cols, int64_t channels, uint8_t* codes, int32_t* colsum,
+                             float* scale_eff, int32_t* zw, int32_t* bad, const float* scale, const void* zero_point,
+                             int zp_type, int mode, float grad_factor, int quant_min, int quant_max, osq_stream stream);
+int osq_linear_int_w4(const uint8_t* x_codes, const int32_t* x_rowsum, const uint8_t* w_codes, const int32_t* w_colsum,
+                      const float* w_scale, const int32_t* w_zw, const int32_t* w_bad, const float* bias, float* out,
+                      int64_t rows, int64_t channels, int64_t cols, float* x_scale, void* x_zero_point, int x_zp_type,
+                      int x_mode, float x_grad_factor, int x_quant_min, int x_quant_max, osq_stream stream);
 
 /* ------------------------------------------------------------------ beam search (beam_select.hip) */
 

@@ -33,6 +33,28 @@
 // N % 4 == 0.  Both operands read their 16 bytes of a k-step from the same place of their row, so the k order inside the
 // instruction does not matter.  Rows beyond M and channels beyond N are clamped at the load and dropped at the store; bytes
 // beyond K (K % 64 != 0) are zero in both operands.
+//
+// PACKED 4-BIT WEIGHTS (osq_weight_codes_sums_w4, osq_linear_int_w4; a weight quantizer of at most 16 codes).  N[r,c] does not
+// depend on the offset taken off the codes, so the packed path takes none: b = uw in 0..15, zw[c] = zp_w[c] - qmin_w, colsum[c]
+// = sum_k uw -- the same integer, every term below 2**31 at K = 16384, the same epilogue.  W is [N, K / 2] bytes in the
+// `code_bits 4` layout of include/osq_hip.h (byte j: element 2 j low, 2 j + 1 high); K % 16 == 0 keeps a row whole bytes, 8-byte
+// aligned.  x is the shared, unpermuted activation_codes output.
+//   weight_codes_w4_kernel   encode_row's loop with two 16-byte loads per lane and trip: eight codes to one 4-byte store.
+//   linear_int_rows_kernel_w4  the weight stream is half as long, so a lane's 16-byte weight load now spans 32 k: in a step of
+//                            64 k half h of the wave holds packed bytes for k0 + 64 s + 32 h .. + 31 of its channel, unpacks them
+//                            in registers (p & 0x0F0F0F0F: even elements, (p >> 4) & 0x0F0F0F0F: odd ones, two v_perm_b32 put
+//                            them back in k order) and feeds k .. + 15 to one instruction and k + 16 .. + 31 to the next, x loaded
+//                            at the same two places.  A wave's chunk is 128 k = 64 packed bytes of a row; the NEXT chunk's six
+//                            loads leave before this chunk's four products (two register sets), so a wave with two or more
+//                            chunks always has weight bytes in flight.  The loop over whole chunks has no branch in it -- the
+//                            wait before a product then counts exactly the six younger loads -- and K's partial last chunk, which
+//                            one wave has, is read after it with predicated loads.  K split over four waves and the LDS add as above.
+//                            K % 32 == 16: rows are 8-byte, not 16-byte aligned -- the 16-byte load is typed 8-byte aligned --
+//                            and the row's last 16 k are 8 packed bytes: the half that owns them issues ONE 8-byte load and
+//                            zeroes the rest, so no lane reads past its row and the last row's reads end with the tensor.
+//   linear_int_kernel<true>  the tile kernel's body with one change: a granule of W is fetched as 8 packed bytes (8-byte
+//                            aligned) and unpacked into its 16 bytes just before the stash, so LDS holds what the 8-bit kernel's
+//                            does: same layout, bank note, product loop and epilogue, four registers fewer in flight.
 // No allocation, no host sync, no workspace, no atomics: legal inside a stream capture.  Inference only.
 #include <math.h>
 #include <hip/hip_runtime.h>
@@ -48,10 +70,26 @@ constexpr int kLinPitch = kLinKStep + 16;    // bytes of a tile row in LDS
 constexpr int kLinMaxK = 16384;          // |N| <= 255 * 255 * K < 2**30
 constexpr int kLinRowsM = 32;            // up to here: linear_int_rows_kernel
 constexpr int kLinRowsChunk = 128;       // bytes of a row a wave of linear_int_rows_kernel takes at a time
+constexpr int kLinW4Chunk = 128;         // k of a row a wave of linear_int_rows_kernel_w4 takes at a time: 64 packed bytes
 constexpr int kLinNoRow = INT32_MIN;     // rowsum of a row without codes (a real one is at most 128 * K = 2**21)
 
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 typedef int i32x16 __attribute__((ext_vector_type(16)));
+typedef int i32x2 __attribute__((ext_vector_type(2)));
+typedef int i32x4_a8 __attribute__((ext_vector_type(4), aligned(8)));       // a packed row starts on 8 bytes where K % 32 == 16
+
+// Eight 4-bit codes of one word, element 2 j in the low nibble of byte j, as two words of bytes in element order.
+__device__ __forceinline__ i32x2 unpack_w4(int p) {
+    const unsigned int even = static_cast<unsigned int>(p) & 0x0F0F0F0Fu, odd = (static_cast<unsigned int>(p) >> 4) & 0x0F0F0F0Fu;
+    return i32x2{static_cast<int>(__builtin_amdgcn_perm(odd, even, 0x05010400u)),       // e0 o0 e1 o1
+                 static_cast<int>(__builtin_amdgcn_perm(odd, even, 0x07030602u))};      // e2 o2 e3 o3
+}
+
+// sixteen codes of two words
+__device__ __forceinline__ i32x4 unpack_w4(int p0, int p1) {
+    const i32x2 a = unpack_w4(p0), b = unpack_w4(p1);
+    return i32x4{a.x, a.y, b.x, b.y};
+}
 
 __device__ __forceinline__ int wave_sum_i32(int v) {
 #pragma unroll
@@ -82,6 +120,37 @@ __device__ __forceinline__ int encode_row(const float4* __restrict__ xr, unsigne
     return wave_sum_i32(sum);
 }
 
+// The packed twin: n8 pairs of float4, eight codes u (no offset: 0 .. 15) to a word in the `code_bits 4` layout.  Returns the
+// row's sum of u.
+__device__ __forceinline__ int encode_row_w4(const float4* __restrict__ xr, unsigned int* __restrict__ cr, int n8, int lane,
+                                             const QParams& p, float qmin, float qmax, unsigned int& rej) {
+    constexpr int kTrip = 2;             // pairs of 16-byte loads in flight per lane
+    int sum = 0;
+    for (int j0 = lane; j0 < n8; j0 += kTrip * OSQ_WAVE) {
+        float4 v[kTrip][2];
+#pragma unroll
+        for (int u = 0; u < kTrip; ++u)
+            if (j0 + u * OSQ_WAVE < n8) {
+                v[u][0] = xr[2 * (j0 + u * OSQ_WAVE)];
+                v[u][1] = xr[2 * (j0 + u * OSQ_WAVE) + 1];
+            }
+#pragma unroll
+        for (int u = 0; u < kTrip; ++u)
+            if (j0 + u * OSQ_WAVE < n8) {
+                unsigned int word = 0;
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+                    const unsigned int u0 = code_of(v[u][h].x, p, qmin, qmax, rej), u1 = code_of(v[u][h].y, p, qmin, qmax, rej);
+                    const unsigned int u2 = code_of(v[u][h].z, p, qmin, qmax, rej), u3 = code_of(v[u][h].w, p, qmin, qmax, rej);
+                    sum += static_cast<int>(u0 + u1 + u2 + u3);
+                    word |= (u0 | (u1 << 4) | (u2 << 8) | (u3 << 12)) << (16 * h);
+                }
+                cr[j0 + u * OSQ_WAVE] = word;
+            }
+    }
+    return wave_sum_i32(sum);
+}
+
 __device__ __forceinline__ bool lin_zp_ok(float zp, float qmin, float qmax) {
     return zp >= qmin && zp <= qmax && rintf(zp) == zp;       // false for a NaN
 }
@@ -102,7 +171,8 @@ __global__ __launch_bounds__(kLinThreads) void activation_codes_kernel(const flo
     }
 }
 
-// rows = output channels; channels: rows (a scale per row) or 1
+// rows = output channels; channels: rows (a scale per row) or 1.  kW4: packed codes [rows, cols / 2] without the offset of 128
+template <bool kW4>
 __global__ __launch_bounds__(kLinThreads) void weight_codes_kernel(const float* __restrict__ w, uint8_t* __restrict__ codes,
                                                                    int32_t* __restrict__ colsum, float* __restrict__ scale_eff,
                                                                    int32_t* __restrict__ zw, int32_t* __restrict__ bad,
@@ -116,21 +186,22 @@ __global__ __launch_bounds__(kLinThreads) void weight_codes_kernel(const float* 
         const int64_t c = channels == 1 ? 0 : r;
         const QParams p = effective_params(scale_p[c], load_zp(zp_p, zp_type, c), mode, g);
         unsigned int rej = 0;
-        const int sum = encode_row(reinterpret_cast<const float4*>(w + r * cols), reinterpret_cast<unsigned int*>(codes + r * cols),
-                                   cols / 4, lane, p, qmin, qmax, rej);
+        const float4* wr = reinterpret_cast<const float4*>(w + r * cols);
+        const int sum = kW4 ? encode_row_w4(wr, reinterpret_cast<unsigned int*>(codes + r * (cols / 2)), cols / 8, lane, p, qmin, qmax, rej)
+                            : encode_row(wr, reinterpret_cast<unsigned int*>(codes + r * cols), cols / 4, lane, p, qmin, qmax, rej);
         const int nbad = wave_sum_i32(static_cast<int>(rej));
         if (lane == 0) {
             const bool ok = lin_zp_ok(p.zp, qmin, qmax);
             colsum[r] = sum;
             scale_eff[r] = p.scale;
-            zw[r] = ok ? static_cast<int>(p.zp - qmin) - 128 : 0;
+            zw[r] = ok ? static_cast<int>(p.zp - qmin) - (kW4 ? 0 : 128) : 0;
             if (!ok || nbad) *bad = 1;                // every writer writes the same word
         }
     }
 }
 
 struct LinArgs {
-    const uint8_t *xc, *wc;            // a [M, K], b [N, K]
+    const uint8_t *xc, *wc;            // a [M, K], b [N, K] (packed: [N, K / 2])
     const int32_t *xrs, *wcs, *wz, *wbad;
     const float *ws, *bias;
     float* out;                        // [M, N]
@@ -195,6 +266,8 @@ __device__ __forceinline__ void lin_store_tile(const LinArgs& a, const i32x16& a
     }
 }
 
+// kW4: a.wc is packed [N, K / 2]; a granule of W is in flight as its 8 packed bytes (gw[u].x, .y) and unpacked at the stash
+template <bool kW4>
 __global__ __launch_bounds__(kLinThreads) void linear_int_kernel(LinArgs a) {
     __shared__ __attribute__((aligned(16))) uint8_t s_w[2][kLinTile * kLinPitch];
     __shared__ __attribute__((aligned(16))) uint8_t s_x[2][kLinTile * kLinPitch];
@@ -219,7 +292,14 @@ __global__ __launch_bounds__(kLinThreads) void linear_int_kernel(LinArgs a) {
             const osq_v4u32 zero = {0u, 0u, 0u, 0u};
             gw[u] = gx[u] = zero;
             if (k < a.K) {
-                gw[u] = *reinterpret_cast<const osq_v4u32*>(a.wc + static_cast<int64_t>(min(n0 + row, a.N - 1)) * a.K + k);
+                const int64_t wrow = min(n0 + row, a.N - 1);
+                if constexpr (kW4) {
+                    const i32x2 p = *reinterpret_cast<const i32x2*>(a.wc + wrow * (a.K / 2) + k / 2);
+                    gw[u].x = static_cast<unsigned int>(p.x);
+                    gw[u].y = static_cast<unsigned int>(p.y);
+                } else {
+                    gw[u] = *reinterpret_cast<const osq_v4u32*>(a.wc + wrow * a.K + k);
+                }
                 gx[u] = *reinterpret_cast<const osq_v4u32*>(a.xc + static_cast<int64_t>(min(m0 + row, a.M - 1)) * a.K + k);
             }
         }
@@ -228,7 +308,11 @@ __global__ __launch_bounds__(kLinThreads) void linear_int_kernel(LinArgs a) {
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
             const int idx = threadIdx.x + kLinThreads * u, at = (idx >> 2) * kLinPitch + 16 * (idx & 3);
-            *reinterpret_cast<osq_v4u32*>(&s_w[buf][at]) = gw[u];
+            if constexpr (kW4) {
+                *reinterpret_cast<i32x4*>(&s_w[buf][at]) = unpack_w4(static_cast<int>(gw[u].x), static_cast<int>(gw[u].y));
+            } else {
+                *reinterpret_cast<osq_v4u32*>(&s_w[buf][at]) = gw[u];
+            }
             *reinterpret_cast<osq_v4u32*>(&s_x[buf][at]) = gx[u];
         }
     };
@@ -318,6 +402,111 @@ __global__ __launch_bounds__(kLinThreads) void linear_int_rows_kernel(LinArgs a)
     lin_store_tile(a, acc, l31, n0, half, zx, sx);
 }
 
+// One chunk of a lane of linear_int_rows_kernel_w4: per 64-k step its channel's 16 packed bytes (32 k) and its x row's 2 x 16.
+struct W4Chunk {
+    i32x4 w[2], x[2][2];
+};
+
+__global__ __launch_bounds__(kLinThreads) void linear_int_rows_kernel_w4(LinArgs a) {
+    constexpr int kWaves = kLinThreads / OSQ_WAVE;
+    __shared__ int s_part[kWaves - 1][16][OSQ_WAVE];
+    const int lane = threadIdx.x & (OSQ_WAVE - 1);
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x / OSQ_WAVE);      // a scalar: the K loop's branches are the wave's
+    const int l31 = lane & 31, half = lane >> 5;
+    const int n0 = static_cast<int>(blockIdx.x) * 32;
+    int zx;
+    float sx;
+    if (!lin_prologue(a, zx, sx)) {                   // uniform
+        lin_fill_nan(a, 0, n0, kLinRowsM, 32);
+        return;
+    }
+    const uint8_t* wrow = a.wc + static_cast<int64_t>(min(n0 + l31, a.N - 1)) * (a.K / 2);
+    const uint8_t* xrow = a.xc + static_cast<int64_t>(min(l31, a.M - 1)) * a.K;
+
+    // A whole chunk (k0 + 128 <= K): six loads and no branch, so the wait before a product counts exactly the loads behind it.
+    const auto load_whole = [&](int k0, W4Chunk& c) {
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            const int k = k0 + 64 * s + 32 * half;
+            c.w[s] = *reinterpret_cast<const i32x4_a8*>(wrow + k / 2);
+            c.x[s][0] = *reinterpret_cast<const i32x4*>(xrow + k);
+            c.x[s][1] = *reinterpret_cast<const i32x4*>(xrow + k + 16);
+        }
+    };
+    // K's last, partial chunk (one wave has it): nothing is read at or beyond K, what is not read is zero.
+    const auto load_part = [&](int k0, W4Chunk& c) {
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            const i32x4 zero = {0, 0, 0, 0};
+            c.w[s] = c.x[s][0] = c.x[s][1] = zero;
+            const int k = k0 + 64 * s + 32 * half, left = a.K - k;      // a multiple of 16
+            if (left >= 32) {
+                c.w[s] = *reinterpret_cast<const i32x4_a8*>(wrow + k / 2);
+                c.x[s][0] = *reinterpret_cast<const i32x4*>(xrow + k);
+                c.x[s][1] = *reinterpret_cast<const i32x4*>(xrow + k + 16);
+            } else if (left == 16) {                  // the row's last 8 packed bytes
+                const i32x2 p = *reinterpret_cast<const i32x2*>(wrow + k / 2);
+                c.w[s].x = p.x;
+                c.w[s].y = p.y;
+                c.x[s][0] = *reinterpret_cast<const i32x4*>(xrow + k);
+            }
+        }
+    };
+
+    i32x16 acc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0;
+    // the products of a chunk of which `left` k exist (uniform; 128: folded)
+    const auto products = [&](const W4Chunk& c, int left) {
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            if (64 * s >= left) break;
+            // k .. + 15 and k + 16 .. + 31 of this half's 32
+            const i32x4 lo = unpack_w4(c.w[s].x, c.w[s].y), hi = unpack_w4(c.w[s].z, c.w[s].w);
+            acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(lo, c.x[s][0], acc, 0, 0, 0);
+            if (64 * s + 16 < left) acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(hi, c.x[s][1], acc, 0, 0, 0);
+        }
+    };
+    // This wave's whole chunks are k0 + kRound * i, i < n; two register sets take them in turn, each loaded while the other's
+    // products run.
+    constexpr int kRound = kLinW4Chunk * kWaves;
+    const int k0 = kLinW4Chunk * w;
+    const int n = a.K - k0 >= kLinW4Chunk ? (a.K - k0 - kLinW4Chunk) / kRound + 1 : 0;
+    W4Chunk ca, cb;
+    if (n) {
+        load_whole(k0, ca);
+        int i = 1;
+        for (; i + 1 < n; i += 2) {
+            load_whole(k0 + kRound * i, cb);
+            products(ca, kLinW4Chunk);
+            load_whole(k0 + kRound * (i + 1), ca);
+            products(cb, kLinW4Chunk);
+        }
+        if (i < n) {                                  // K = 1024: every wave's two chunks
+            load_whole(k0 + kRound * i, cb);
+            products(ca, kLinW4Chunk);
+            products(cb, kLinW4Chunk);
+        } else {
+            products(ca, kLinW4Chunk);
+        }
+    }
+    if (k0 + kRound * n < a.K) {
+        load_part(k0 + kRound * n, ca);
+        products(ca, a.K - (k0 + kRound * n));
+    }
+    if (w) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) s_part[w - 1][r][lane] = acc[r];
+    }
+    __syncthreads();
+    if (w) return;
+#pragma unroll
+    for (int v = 0; v < kWaves - 1; ++v)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[r] += s_part[v][r][lane];
+    lin_store_tile(a, acc, l31, n0, half, zx, sx);
+}
+
 static bool lin_quant_ok(int mode, int quant_min, int quant_max) {
     return dec_mode_ok(mode) && quant_min <= quant_max && static_cast<int64_t>(quant_max) - quant_min <= 255;
 }
@@ -347,10 +536,11 @@ extern "C" int osq_activation_codes(const float* x, int64_t rows, int64_t cols, 
     return check_launch("activation_codes");
 }
 
-extern "C" int osq_weight_codes_sums(const float* w, int64_t rows, int64_t cols, int64_t channels, uint8_t* codes,
-                                     int32_t* colsum, float* scale_eff, int32_t* zw, int32_t* bad, const float* scale,
-                                     const void* zero_point, int zp_type, int mode, float grad_factor, int quant_min,
-                                     int quant_max, osq_stream stream) {
+// osq_weight_codes_sums and its packed twin
+static int lin_weight_codes(bool w4, const float* w, int64_t rows, int64_t cols, int64_t channels, uint8_t* codes,
+                            int32_t* colsum, float* scale_eff, int32_t* zw, int32_t* bad, const float* scale,
+                            const void* zero_point, int zp_type, int mode, float grad_factor, int quant_min,
+                            int quant_max, osq_stream stream) {
     OSQ_REQUIRE(rows >= 0 && rows <= INT32_MAX, "weight_codes_sums: bad row count");
     OSQ_REQUIRE(lin_k_ok(cols), "weight_codes_sums: the row length must be a multiple of 16 in [16, 16384]");
     OSQ_REQUIRE(channels == 1 || channels == rows, "weight_codes_sums: one scale, or one per row");
@@ -358,20 +548,38 @@ extern "C" int osq_weight_codes_sums(const float* w, int64_t rows, int64_t cols,
     OSQ_REQUIRE(zp_type == OSQ_ZP_INT32 || zp_type == OSQ_ZP_FLOAT32, "weight_codes_sums: bad zp_type");
     OSQ_REQUIRE(mode >= OSQ_PARAM_FIXED && mode <= OSQ_PARAM_LSQPLUS, "weight_codes_sums: bad mode");
     OSQ_REQUIRE(quant_min <= quant_max && static_cast<int64_t>(quant_max) - quant_min <= 255, "weight_codes_sums: more than 256 codes");
+    OSQ_REQUIRE(!w4 || quant_max - quant_min <= 15, "weight_codes_sums_w4: more than 16 codes");
     if (rows == 0) return OSQ_OK;
     OSQ_REQUIRE(w && codes && colsum && scale_eff && zw && bad, "weight_codes_sums: null tensor");
     OSQ_REQUIRE(aligned16(w) && (reinterpret_cast<uintptr_t>(codes) & 3u) == 0, "weight_codes_sums: w not 16-byte or codes not 4-byte aligned");
     const int grid = grid_for(rows, kLinThreads / OSQ_WAVE, kMaxBlocks * 2);
-    hipLaunchKernelGGL(weight_codes_kernel, dim3(grid), dim3(kLinThreads), 0, static_cast<hipStream_t>(stream), w, codes, colsum,
-                       scale_eff, zw, bad, rows, channels, static_cast<int>(cols), scale, zero_point, zp_type, mode, grad_factor,
-                       static_cast<float>(quant_min), static_cast<float>(quant_max));
-    return check_launch("weight_codes_sums");
+    hipLaunchKernelGGL(w4 ? weight_codes_kernel<true> : weight_codes_kernel<false>, dim3(grid), dim3(kLinThreads), 0,
+                       static_cast<hipStream_t>(stream), w, codes, colsum, scale_eff, zw, bad, rows, channels, static_cast<int>(cols),
+                       scale, zero_point, zp_type, mode, grad_factor, static_cast<float>(quant_min), static_cast<float>(quant_max));
+    return check_launch(w4 ? "weight_codes_sums_w4" : "weight_codes_sums");
 }
 
-extern "C" int osq_linear_int(const uint8_t* x_codes, const int32_t* x_rowsum, const uint8_t* w_codes, const int32_t* w_colsum,
-                              const float* w_scale, const int32_t* w_zw, const int32_t* w_bad, const float* bias, float* out,
-                              int64_t rows, int64_t channels, int64_t cols, float* x_scale, void* x_zero_point, int x_zp_type,
-                              int x_mode, float x_grad_factor, int x_quant_min, int x_quant_max, osq_stream stream) {
+extern "C" int osq_weight_codes_sums(const float* w, int64_t rows, int64_t cols, int64_t channels, uint8_t* codes,
+                                     int32_t* colsum, float* scale_eff, int32_t* zw, int32_t* bad, const float* scale,
+                                     const void* zero_point, int zp_type, int mode, float grad_factor, int quant_min,
+                                     int quant_max, osq_stream stream) {
+    return lin_weight_codes(false, w, rows, cols, channels, codes, colsum, scale_eff, zw, bad, scale, zero_point, zp_type, mode,
+                            grad_factor, quant_min, quant_max, stream);
+}
+
+extern "C" int osq_weight_codes_sums_w4(const float* w, int64_t rows, int64_t cols, int64_t channels, uint8_t* codes,
+                                        int32_t* colsum, float* scale_eff, int32_t* zw, int32_t* bad, const float* scale,
+                                        const void* zero_point, int zp_type, int mode, float grad_factor, int quant_min,
+                                        int quant_max, osq_stream stream) {
+    return lin_weight_codes(true, w, rows, cols, channels, codes, colsum, scale_eff, zw, bad, scale, zero_point, zp_type, mode,
+                            grad_factor, quant_min, quant_max, stream);
+}
+
+// osq_linear_int and its packed twin: w_codes [channels, cols] or [channels, cols / 2]
+static int lin_launch(bool w4, const uint8_t* x_codes, const int32_t* x_rowsum, const uint8_t* w_codes, const int32_t* w_colsum,
+                      const float* w_scale, const int32_t* w_zw, const int32_t* w_bad, const float* bias, float* out,
+                      int64_t rows, int64_t channels, int64_t cols, float* x_scale, void* x_zero_point, int x_zp_type,
+                      int x_mode, float x_grad_factor, int x_quant_min, int x_quant_max, osq_stream stream) {
     OSQ_REQUIRE(rows >= 0 && rows <= INT32_MAX && channels >= 0 && channels <= INT32_MAX, "linear_int: bad shape");
     OSQ_REQUIRE(lin_k_ok(cols), "linear_int: K must be a multiple of 16 in [16, 16384]");
     OSQ_REQUIRE(x_scale && x_zero_point, "linear_int: null scale or zero_point");
@@ -388,11 +596,29 @@ extern "C" int osq_linear_int(const uint8_t* x_codes, const int32_t* x_rowsum, c
                     static_cast<int>(channels), static_cast<int>(cols), vec, OSQ_DEC_QUANT(x)};
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (rows <= kLinRowsM) {
-        hipLaunchKernelGGL(linear_int_rows_kernel, dim3(static_cast<unsigned>((channels + 31) / 32)), dim3(kLinThreads), 0, st, a);
+        hipLaunchKernelGGL(w4 ? linear_int_rows_kernel_w4 : linear_int_rows_kernel, dim3(static_cast<unsigned>((channels + 31) / 32)),
+                           dim3(kLinThreads), 0, st, a);
     } else {
         const int64_t blocks = ((rows + kLinTile - 1) / kLinTile) * ((channels + kLinTile - 1) / kLinTile);
         OSQ_REQUIRE(blocks <= INT32_MAX, "linear_int: too many tiles");
-        hipLaunchKernelGGL(linear_int_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kLinThreads), 0, st, a);
+        hipLaunchKernelGGL(w4 ? linear_int_kernel<true> : linear_int_kernel<false>, dim3(static_cast<unsigned>(blocks)),
+                           dim3(kLinThreads), 0, st, a);
     }
-    return check_launch("linear_int");
+    return check_launch(w4 ? "linear_int_w4" : "linear_int");
+}
+
+extern "C" int osq_linear_int(const uint8_t* x_codes, const int32_t* x_rowsum, const uint8_t* w_codes, const int32_t* w_colsum,
+                              const float* w_scale, const int32_t* w_zw, const int32_t* w_bad, const float* bias, float* out,
+                              int64_t rows, int64_t channels, int64_t cols, float* x_scale, void* x_zero_point, int x_zp_type,
+                              int x_mode, float x_grad_factor, int x_quant_min, int x_quant_max, osq_stream stream) {
+    return lin_launch(false, x_codes, x_rowsum, w_codes, w_colsum, w_scale, w_zw, w_bad, bias, out, rows, channels, cols, x_scale,
+                      x_zero_point, x_zp_type, x_mode, x_grad_factor, x_quant_min, x_quant_max, stream);
+}
+
+extern "C" int osq_linear_int_w4(const uint8_t* x_codes, const int32_t* x_rowsum, const uint8_t* w_codes, const int32_t* w_colsum,
+                                 const float* w_scale, const int32_t* w_zw, const int32_t* w_bad, const float* bias, float* out,
+                                 int64_t rows, int64_t channels, int64_t cols, float* x_scale, void* x_zero_point, int x_zp_type,
+                                 int x_mode, float x_grad_factor, int x_quant_min, int x_quant_max, osq_stream stream) {
+    return lin_launch(true, x_codes, x_rowsum, w_codes, w_colsum, w_scale, w_zw, w_bad, bias, out, rows, channels, cols, x_scale,
+                      x_zero_point, x_zp_type, x_mode, x_grad_factor, x_quant_min, x_quant_max, stream);
 }

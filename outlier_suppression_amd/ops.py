@@ -2202,13 +2202,16 @@ LINEAR_INT_KSTEP = 64          # kLinKStep: code bytes of a row per step, two k-
 LINEAR_INT_ROWS_M = 32         # kLinRowsM: up to here the kernel that splits channels over workgroups and K over waves
 LINEAR_INT_MAX_K = 16384       # kLinMaxK
 LINEAR_INT_MAX_RANGE = 255     # quant_max - quant_min of both quantizers
+LINEAR_INT_W4_MAX_RANGE = 15   # quant_max - quant_min of a weight quantizer whose codes go two to a byte
 LINEAR_INT_NO_ROW = -2 ** 31   # kLinNoRow: the row sum of a row with an element that has no code
 
 
 class WeightCodes(NamedTuple):
     """A frozen [N, K] weight as the integer linear launch reads it (include/osq_hip.h, "integer linear"): codes uint8 [N, K]
     holding b = u - 128 as int8; colsum int32 [N] = sum_k b; scale fp32 [N], the effective s_w; zw int32 [N]; bad int32 [1],
-    set when a zero point is no integer inside the range or an element has no code (the launch then writes NaN everywhere)."""
+    set when a zero point is no integer inside the range or an element has no code (the launch then writes NaN everywhere).
+    A packed entry (``weight_codes(bits=4)``, at most 16 codes): codes uint8 [N, K // 2], two codes u per byte in the ``code_bits
+    4`` layout with nothing taken off, colsum = sum_k u and zw = zp_w - quant_min: the same N, the same words of out."""
     codes: torch.Tensor
     colsum: torch.Tensor
     scale: torch.Tensor
@@ -2216,15 +2219,18 @@ class WeightCodes(NamedTuple):
     bad: torch.Tensor
 
 
-def linear_int_refusal(k, record, *tensors, fp32=(), last_dim=()):
+def linear_int_refusal(k, record, *tensors, fp32=(), last_dim=(), packed=False):
     """Why the integer linear launches do not take reduction length ``k``, activation record ``record`` = (scale, zero_point,
     quant_min, quant_max, ...) and ``tensors`` -- one phrase -- or None.  ``fp32``: tensors that must be float32; ``last_dim``:
-    tensors whose last dimension must be contiguous.  Where the tensors live is asked last."""
+    tensors whose last dimension must be contiguous; ``packed``: the record is that of a weight to pack two codes to a byte.
+    Where the tensors live is asked last."""
     scale, zero_point, quant_min, quant_max = record[:4]
     if scale.numel() != 1 or zero_point.numel() != 1:
         return "the activation record is per-channel"
     if int(quant_max) - int(quant_min) > LINEAR_INT_MAX_RANGE:
         return "a quantizer has more than 256 codes"
+    if packed and int(quant_max) - int(quant_min) > LINEAR_INT_W4_MAX_RANGE:
+        return "a packed weight has more than 16 codes"
     if k % 16:
         return "K is not a multiple of 16"
     if k > LINEAR_INT_MAX_K:
@@ -2267,16 +2273,17 @@ def activation_codes(x, record):
     return codes, rowsum
 
 
-def weight_codes(weight, scale, zero_point, ch_axis, quant_min, quant_max, mode=PARAM_FIXED, grad_factor=1.0):
+def weight_codes(weight, scale, zero_point, ch_axis, quant_min, quant_max, mode=PARAM_FIXED, grad_factor=1.0, bits=8):
     """``WeightCodes`` of a dense fp32 [N, K] weight under its quantizer's raw parameters (ch_axis 0: one per row; -1: one),
-    mode and grad factor as quantize_codes takes them: the bytes are quantize_codes' u minus 128.  One launch."""
-    if ch_axis not in (0, -1) or weight.dim() != 2:
-        raise ValueError("weight_codes: a [N, K] weight quantized per row (ch_axis 0) or per tensor (ch_axis -1)")
+    mode and grad factor as quantize_codes takes them: the bytes are quantize_codes' u minus 128.  bits=4 (a quantizer of at
+    most 16 codes): the packed entry, codes [N, K // 2], byte for byte quantize_codes' at code_bits 4.  One launch."""
+    if ch_axis not in (0, -1) or weight.dim() != 2 or bits not in (4, 8):
+        raise ValueError("weight_codes: a [N, K] weight quantized per row (ch_axis 0) or per tensor (ch_axis -1), bits 4 or 8")
     n, k = weight.shape
     channels = n if ch_axis == 0 else 1
     # the refusals go by the first channel's parameters; a [0, K] weight quantized per row has none, and nothing to encode
     first = (scale[:1], zero_point[:1]) if channels else (weight.new_ones(1), weight.new_zeros(1))
-    why = linear_int_refusal(k, first + (quant_min, quant_max), zero_point, fp32=(weight, scale))
+    why = linear_int_refusal(k, first + (quant_min, quant_max), zero_point, fp32=(weight, scale), packed=bits == 4)
     if why is None and not weight.is_contiguous():
         why = "the weight is not dense"
     if why:
@@ -2284,16 +2291,16 @@ def weight_codes(weight, scale, zero_point, ch_axis, quant_min, quant_max, mode=
     lib = _hip.load()
     _check_per_channel("weight_codes", channels, scale, zero_point)
     dev = weight.device
-    codes = torch.empty((n, k), dtype=torch.uint8, device=dev)
+    codes = torch.empty((n, k // 2 if bits == 4 else k), dtype=torch.uint8, device=dev)
     colsum, zw = torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.int32, device=dev)
     s_eff = torch.empty(n, dtype=torch.float32, device=dev)
     bad = torch.zeros(1, dtype=torch.int32, device=dev)
     if n == 0:
         return WeightCodes(codes, colsum, s_eff, zw, bad)
-    _hip.check(lib.osq_weight_codes_sums(_hip.ptr(weight), n, k, channels, _hip.ptr(codes), _hip.ptr(colsum), _hip.ptr(s_eff),
-                                         _hip.ptr(zw), _hip.ptr(bad), _hip.ptr(scale), _hip.ptr(zero_point), _zp_type(zero_point),
-                                         mode & PARAM_MODE_MASK, float(grad_factor), int(quant_min), int(quant_max),
-                                         _hip.stream_ptr(dev)), "weight_codes_sums")
+    encode = lib.osq_weight_codes_sums_w4 if bits == 4 else lib.osq_weight_codes_sums
+    _hip.check(encode(_hip.ptr(weight), n, k, channels, _hip.ptr(codes), _hip.ptr(colsum), _hip.ptr(s_eff), _hip.ptr(zw),
+                      _hip.ptr(bad), _hip.ptr(scale), _hip.ptr(zero_point), _zp_type(zero_point), mode & PARAM_MODE_MASK,
+                      float(grad_factor), int(quant_min), int(quant_max), _hip.stream_ptr(dev)), "weight_codes_sums")
     return WeightCodes(codes, colsum, s_eff, zw, bad)
 
 
@@ -2302,11 +2309,13 @@ def linear_int(x_codes, x_rowsum, x_record, w_entry, bias=None):
     x_rowsum [...]) under the record they were made with and a ``WeightCodes`` entry: exact int32 sums on the int8 matrix
     instruction, then (float)N * (s_x * s_w[c]) + bias[c].  One launch, no host sync, legal inside a stream capture.
     ValueError, nothing launched or allocated: a per-channel activation record, more than 256 codes, K % 16 != 0, K > 16384, a
-    bias that is not fp32, CPU tensors, codes whose last dimension is not contiguous, operands of other shapes than these."""
+    bias that is not fp32, CPU tensors, codes whose last dimension is not contiguous, operands of other shapes than these.
+    A packed entry (codes [N, K // 2]; K is x_codes') takes the packed kernels and gives the same words."""
     k = x_codes.shape[-1] if x_codes.dim() else 0
     why = linear_int_refusal(k, x_record, x_rowsum, *w_entry, fp32=(bias,), last_dim=(x_codes,))
     n = w_entry.codes.shape[0]
-    if why is None and (x_codes.dtype != torch.uint8 or not x_codes.is_contiguous() or tuple(w_entry.codes.shape) != (n, k)
+    packed = k > 0 and tuple(w_entry.codes.shape) == (n, k // 2)
+    if why is None and (x_codes.dtype != torch.uint8 or not x_codes.is_contiguous() or tuple(w_entry.codes.shape) not in ((n, k), (n, k // 2))
                         or tuple(x_rowsum.shape) != tuple(x_codes.shape[:-1]) or not x_rowsum.is_contiguous()
                         or (bias is not None and (tuple(bias.shape) != (n,) or not bias.is_contiguous()))):
         why = "the operands are not dense codes [..., K], row sums [...], a WeightCodes [N, K] and a bias [N]"
@@ -2315,10 +2324,11 @@ def linear_int(x_codes, x_rowsum, x_record, w_entry, bias=None):
     lib = _hip.load()
     scale, zero_point, quant_min, quant_max, mode, grad_factor = x_record
     out = torch.empty(tuple(x_codes.shape[:-1]) + (n,), dtype=torch.float32, device=x_codes.device)
-    _hip.check(lib.osq_linear_int(_hip.ptr(x_codes), _hip.ptr(x_rowsum), _hip.ptr(w_entry.codes), _hip.ptr(w_entry.colsum),
-                                  _hip.ptr(w_entry.scale), _hip.ptr(w_entry.zw), _hip.ptr(w_entry.bad), _hip.ptr(bias), _hip.ptr(out),
-                                  x_rowsum.numel(), n, k, _hip.ptr(scale), _hip.ptr(zero_point), _zp_type(zero_point), int(mode),
-                                  float(grad_factor), int(quant_min), int(quant_max), _hip.stream_ptr(out.device)), "linear_int")
+    launch = lib.osq_linear_int_w4 if packed else lib.osq_linear_int
+    _hip.check(launch(_hip.ptr(x_codes), _hip.ptr(x_rowsum), _hip.ptr(w_entry.codes), _hip.ptr(w_entry.colsum),
+                      _hip.ptr(w_entry.scale), _hip.ptr(w_entry.zw), _hip.ptr(w_entry.bad), _hip.ptr(bias), _hip.ptr(out),
+                      x_rowsum.numel(), n, k, _hip.ptr(scale), _hip.ptr(zero_point), _zp_type(zero_point), int(mode),
+                      float(grad_factor), int(quant_min), int(quant_max), _hip.stream_ptr(out.device)), "linear_int")
     return out
 
 

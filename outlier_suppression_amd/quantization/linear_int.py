@@ -23,7 +23,11 @@ import torch
 from .. import ops
 from . import weight_cache
 
-_SHARED = []          # the open shared_codes() scopes: {(id(x), version, id(producer)): (x, codes, rowsum)}
+# A weight quantizer of at most 16 codes has its codes cached two to a byte (ops.weight_codes(bits=4)) and multiplied by the
+# packed kernels.  The words of the result are the same either way; on by default because no shape measured in
+# profiles/linear_int_w4_ab.txt loses beyond the 8-bit form's own range and the lm_head shapes gain 23 - 29 %.
+PACK_W4 = True
+_SHARED = []        # the open shared_codes() scopes: {(id(x), version, id(producer)): (x, codes, rowsum)}
 
 
 class shared_codes:

@@ -81,9 +81,12 @@ def weight_codes(op):
     beside the fake-quantised weight under the same key: whatever invalidates that entry invalidates this one.  The caller
     has checked ``cacheable``.  None while a stream capture is open and there is no valid entry: the codes are made
     outside a graph's memory pool."""
+    from . import linear_int
     fq = op.weight_fake_quant
+    # a weight of at most 16 codes goes two codes to a byte under linear_int.PACK_W4: an entry of the other layout is stale
+    bits = 4 if linear_int.PACK_W4 and fq.quant_max - fq.quant_min <= ops.LINEAR_INT_W4_MAX_RANGE else 8
     entry = _CODES.get(op)
-    if entry is not None and entry[0] == _key(op, fq):
+    if entry is not None and entry[0] == _key(op, fq) and entry[1].codes.shape[1] == op.weight.shape[1] * bits // 8:
         return entry[1]
     if torch.cuda.is_current_stream_capturing():
         return None
@@ -91,7 +94,7 @@ def weight_codes(op):
         quantized_weight(op)          # a learnable quantizer repairs its parameters in place on its first call: before the key
     w = op.weight.detach()
     rec = ops.weight_codes(w, fq.scale.detach(), fq.zero_point.detach(), fq.ch_axis, fq.quant_min, fq.quant_max, fq.param_mode,
-                           fq._grad_factor(w) if fq.param_mode != ops.PARAM_FIXED else 1.0)
+                           fq._grad_factor(w) if fq.param_mode != ops.PARAM_FIXED else 1.0, bits=bits)
     _CODES[op] = (_key(op, fq), rec)
     return rec
 

@@ -12,7 +12,14 @@ exceeds the baseline's own range.
   models   (--no-models skips them) the calls tools/attention_block_ab.py reports: a random-init BERT-base forward at 32 x 128
            and 32 x 384, the BART-large encoder pass at 32 x 512 and score(num_candidates=6).
 
+  w4       (--w4: these rows alone) a weight quantizer of 16 codes: ops.linear_int on the packed entry, ops.weight_codes(bits=4),
+           against the SAME call on the 8-bit entry of the same weight -- the baseline is the 8-bit form -- one activation_codes
+           output shared by both and made outside the timed calls.  The two outputs are held word-equal first.  The rows kernel:
+           BART's lm_head at 1 and 32 rows, the pooler, 1024 -> 4096 at 32 rows; the tile kernel: 768 -> 3072 at 4096 rows,
+           4096 -> 1024 at 16384, 1024 -> 1024 at 192.
+
     python tools/linear_int_ab.py [--reps 7] [--out profiles/linear_int_ab.txt]
+    python tools/linear_int_ab.py --w4 --inner 100 --out profiles/linear_int_w4_ab.txt
 """
 import argparse
 import os
@@ -31,6 +38,10 @@ LAYERS = (("bert-base 32x128", 32 * 128, ((768, 768, 1), (768, 768, 3), (768, 30
           ("bart-large 32x512", 32 * 512, ((1024, 4096, 1), (4096, 1024, 1))),
           ("bart-large decoding step", 192, ((1024, 1024, 1), (1024, 4096, 1))),
           ("bert-base pooler", 32, ((768, 768, 1),)))
+
+
+W4_LAYERS = ((1, 1024, 50265), (32, 1024, 50265), (32, 768, 768), (32, 1024, 4096), (4096, 768, 3072), (16384, 4096, 1024),
+             (192, 1024, 1024))
 
 
 def timed(forms, reps, inner):
@@ -85,6 +96,25 @@ def layer(emit, m, k, n, count, reps, inner):
     report(emit, timed({"F.linear": eager, "linear_int": integer}, reps, inner))
 
 
+def layer_w4(emit, m, k, n, reps, inner):
+    from outlier_suppression_amd import ops
+    dev = torch.device("cuda:0")
+    g = torch.Generator(device=dev).manual_seed(m + k + n)
+    s_x = torch.tensor([0.05], device=dev)
+    zp_x = torch.tensor([127], dtype=torch.int32, device=dev)
+    record = (s_x, zp_x, 0, 255, ops.PARAM_FIXED, 1.0)
+    w = torch.randn((n, k), generator=g, device=dev) * 0.03
+    scale, zps = w.abs().amax(1) / 7, torch.zeros(n, dtype=torch.int32, device=dev)
+    bias = torch.randn(n, generator=g, device=dev)
+    codes, rowsum = ops.activation_codes(torch.randn((m, k), generator=g, device=dev), record)
+    entries = {bits: ops.weight_codes(w, scale, zps, 0, -8, 7, bits=bits) for bits in (8, 4)}
+    forms = {"linear_int": lambda: ops.linear_int(codes, rowsum, record, entries[8], bias),
+             "linear_int_w4": lambda: ops.linear_int(codes, rowsum, record, entries[4], bias)}
+    assert torch.equal(forms["linear_int"](), forms["linear_int_w4"]()) and tuple(entries[4].codes.shape) == (n, k // 2)
+    emit(f"  [{m}, {k}] -> {n}: {entries[8].codes.numel()} and {entries[4].codes.numel()} weight bytes, the same words")
+    report(emit, timed(forms, reps, inner), "linear_int", "linear_int_w4")
+
+
 def model(emit, label, fn, reps, inner):
     import outlier_suppression_amd as osq
     from outlier_suppression_amd import util_layernorm as UL
@@ -110,6 +140,7 @@ def main():
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--inner", type=int, default=10)
     ap.add_argument("--no-models", action="store_true")
+    ap.add_argument("--w4", action="store_true", help="the packed 4-bit weight rows alone")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     assert torch.cuda.is_available(), "linear_int_ab.py measures on a GPU"
@@ -119,15 +150,21 @@ def main():
         print(line, flush=True)
         lines.append(line)
     emit(f"tools/linear_int_ab.py on {torch.cuda.get_device_name(0)}: medians of {args.reps} rounds of --inner calls [min, max], "
-         "both forms in turn within each round; linear_int includes its activation_codes launch")
+         "both forms in turn within each round" + ("" if args.w4 else "; linear_int includes its activation_codes launch"))
     emit("")
-    for label, m, shapes in LAYERS:
+    if args.w4:
+        emit("packed 4-bit weights against the 8-bit entry of the same weight (W4A8), ops.linear_int alone, "
+             f"{args.inner} calls to a round")
+        for m, k, n in W4_LAYERS:
+            layer_w4(emit, m, k, n, args.reps, args.inner)
+            torch.cuda.empty_cache()
+    for label, m, shapes in ((), LAYERS)[not args.w4]:
         emit(f"{label}: M = {m}")
         for k, n, count in shapes:
             layer(emit, m, k, n, count, args.reps, args.inner)
         emit("")
         torch.cuda.empty_cache()
-    if not args.no_models:
+    if not args.no_models and not args.w4:
         from attention_block_ab import bert_base
         for length in (128, 384):
             q, ids, mask = bert_base(32, length)
