@@ -51,7 +51,7 @@ typedef void* osq_stream;
  *     osq_attention_fake_quant_shared, osq_attention_fake_quant_int_shared, osq_gelu_fake_quant_backward,
  *     osq_attention_softmax_fake_quant_backward, osq_residual_layernorm_fake_quant_backward, osq_fake_quant_heads_backward
  *     (with it osq_workspace_bytes() grew at its END: no earlier offset of the workspace moved), osq_activation_codes,
- *     osq_weight_codes_sums, osq_linear_int, osq_weight_codes_sums_w4, osq_linear_int_w4. */
+ *     osq_weight_codes_sums, osq_linear_int, osq_weight_codes_sums_w4, osq_linear_int_w4, osq_linear_int_codes. */
 #define OSQ_ABI_VERSION 10
 
 typedef enum osq_status {
@@ -1234,7 +1234,22 @@ int osq_attention_fake_quant_int_shared(const float* q, const float* k, const fl
  * osq_activation_codes output either product reads.  NaN rows, *w_bad and the parameter repair are those of osq_linear_int.
  * All five: no allocation, no host synchronisation, no workspace, no floating-point atomics: legal inside a stream
  * capture.  Inference only.  OSQ_ERR_INVALID_ARGUMENT, nothing launched: a limit above exceeded, a null or misaligned tensor,
- * a mode other than FIXED / LSQ / LSQ+ (+ SANITIZE for x). */
+ * a mode other than FIXED / LSQ / LSQ+ (+ SANITIZE for x).
+ *
+ * Codes for the next linear (osq_linear_int_codes): the product above, 8-bit (w_bits 8) or packed (w_bits 4), whose epilogue
+ * writes no out but what osq_activation_codes would make of it under the per-tensor out_* quantizer (at most 256 codes, the
+ * x_* group's rules, OSQ_PARAM_SANITIZE included) of the linear that reads it.  Per element, in this order:
+ *     v = out[r,c] of the rule above                                      the fp32 word osq_linear_int would have stored
+ *     g = activation == 1 ? v * 0.5 * (1 + erf(v * sqrt(1/2))) : v        osq_gelu_fake_quant_per_tensor's GELU, bit for bit
+ *     u = clamp(rint(g / s_out) + zp_out, qmin_out, qmax_out) - qmin_out  codes[r,c] = u - 128 as int8
+ * and rowsum[r] = sum_c (u - 128): word for word osq_activation_codes of osq_gelu_fake_quant_per_tensor (activation 0:
+ * osq_fake_quant_per_tensor) of osq_linear_int's out, because re-encoding a fake-quantised value gives back its code.
+ * channels is the next reduction length: channels % 16 == 0, 16 <= channels <= 16384; codes 16-byte aligned, dense.
+ * rowsum[r] = INT32_MIN when an element of row r has no code or x_rowsum[r] was INT32_MIN (the bytes of such a row are
+ * unspecified), and for EVERY row when *w_bad is set or zp_x or zp_out is not an integer inside its range.  The caller zeroes
+ * rowsum [rows] and scratch [rows + ceil(rows / 128)] int32 (flags and arrival tickets; one buffer, one clear) before each
+ * launch.  Row sums are combined with int32 atomic adds (order-free: deterministic); no workgroup waits for another.  No
+ * allocation, no host synchronisation: legal inside a stream capture. */
 int osq_activation_codes(const float* x, int64_t rows, int64_t cols, int64_t row_stride, uint8_t* codes, int32_t* rowsum,
                          float* x_scale, void* x_zero_point, int x_zp_type, int x_mode, float x_grad_factor,
                          int x_quant_min, int x_quant_max, osq_stream stream);
@@ -1252,6 +1267,13 @@ int osq_linear_int_w4(const uint8_t* x_codes, const int32_t* x_rowsum, const uin
                       const float* w_scale, const int32_t* w_zw, const int32_t* w_bad, const float* bias, float* out,
                       int64_t rows, int64_t channels, int64_t cols, float* x_scale, void* x_zero_point, int x_zp_type,
                       int x_mode, float x_grad_factor, int x_quant_min, int x_quant_max, osq_stream stream);
+
+int osq_linear_int_codes(const uint8_t* x_codes, const int32_t* x_rowsum, const uint8_t* w_codes, const int32_t* w_colsum,
+                         const float* w_scale, const int32_t* w_zw, const int32_t* w_bad, const float* bias, uint8_t* codes,
+                         int32_t* rowsum, int32_t* scratch, int64_t rows, int64_t channels, int64_t cols, float* x_scale,
+                         void* x_zero_point, int x_zp_type, int x_mode, float x_grad_factor, int x_quant_min, int x_quant_max,
+                         float* out_scale, void* out_zero_point, int out_zp_type, int out_mode, float out_grad_factor,
+                         int out_quant_min, int out_quant_max, int activation, int w_bits, osq_stream stream);
 
 /* ------------------------------------------------------------------ beam search (beam_select.hip) */
 

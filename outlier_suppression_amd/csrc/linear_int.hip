@@ -56,10 +56,31 @@
 //                            aligned) and unpacked into its 16 bytes just before the stash, so LDS holds what the 8-bit kernel's
 //                            does: same layout, bank note, product loop and epilogue, four registers fewer in flight.
 // No allocation, no host sync, no workspace, no atomics: legal inside a stream capture.  Inference only.
+//
+// CODES FOR THE NEXT LINEAR (osq_linear_int_codes; a feed-forward block's fc1).  The three product kernels take one more
+// template argument, kCodes: same K loop, another epilogue.  It writes no out; per element u = code_of(gelu_erf(lin_value(..)))
+// under the NEXT linear's quantizer (gelu_erf only where the launch asks for it), codes [M, N] bytes u - 128 and rowsum [M] =
+// sum_c (u - 128): what activation_codes would make of the fake-quantised out -- re-encoding a fake-quantised value gives
+// back its code -- word for word.  N % 16 == 0.
+//   a lane's granule         per row the 32 bytes of a 32 x 32 result are A0 B0 A1 B1 A2 B2 A3 B3, A in lanes 0..31 and B in their
+//                            partners (lane ^ 32): each lane sends the two words its partner needs and keeps its own two, and
+//                            holds 16 contiguous bytes of its row (lin_code_granule).
+//   tile kernel              the 128 x 128 code bytes are staged in the operand LDS, free after the K loop, at a pitch of 144
+//                            (the bank note is at the code) and leave 16 bytes per lane, 8 consecutive lanes to a 128-byte line.
+//   rows kernels             a workgroup owns 32 bytes of a row, two lanes' granules: wave 0 stores them from registers.
+//   row sums                 a workgroup's partial per row comes from the granules and is added into the ZEROED rowsum with one
+//                            vector int32 atomic add per row (order-free: deterministic).  kLinNoRow cannot be made by adding:
+//                            a lane that meets an element without a code ORs its row's flag; every workgroup fences and takes a
+//                            ticket of its row tile, and whoever draws the last one exchanges kLinNoRow into the flagged rows
+//                            and into those that came in without codes.  Nobody waits.  A bad launch (*w_bad, zp_x or the out
+//                            zero point no integer in range) is uniform: the first channel tile's workgroups store kLinNoRow
+//                            into every row and nobody adds.  The caller zeroes rowsum, flags [M] and tickets [row tiles]: one
+//                            buffer, one clear, before every launch.
 #include <math.h>
 #include <hip/hip_runtime.h>
 #include "attention_quant.h"
 #include "codes_device.h"
+#include "lsq_backward.h"
 
 namespace osq {
 
@@ -208,6 +229,11 @@ struct LinArgs {
     int M, N, K;
     int vec;                           // N % 4 == 0 and out, wcs, wz, ws, bias 16-byte aligned: 16-byte epilogue accesses
     DecQuant xq;
+    // the kCodes epilogue only (out is null): codes [M, N] bytes, rowsum [M] zeroed, flags [M] and tickets [row tiles] zeroed
+    uint8_t* codes;
+    int32_t *rowsum, *flags, *tickets;
+    DecQuant oq;                       // the quantizer of the NEXT linear's input
+    int gelu;                          // 1: gelu_erf between the linear's word and the code
 };
 
 // zx and s_x of the launch; false (uniform): the launch writes NaN everywhere
@@ -266,8 +292,135 @@ __device__ __forceinline__ void lin_store_tile(const LinArgs& a, const i32x16& a
     }
 }
 
-// kW4: a.wc is packed [N, K / 2]; a granule of W is in flight as its 8 packed bytes (gw[u].x, .y) and unpacked at the stash
-template <bool kW4>
+// ---- the kCodes epilogue: the next linear's activation codes instead of out (header, "CODES FOR THE NEXT LINEAR") ----------
+
+// out quantizer's parameters; false (uniform): its zero point is no integer in range, the launch is bad
+__device__ __forceinline__ bool lin_out_params(const LinArgs& a, QParams& op) {
+    op = dec_params(a.oq);
+    return lin_zp_ok(op.zp, a.oq.qmin, a.oq.qmax);
+}
+
+// a bad launch: every row sum is kLinNoRow, written by the workgroups of the first channel tile; nobody adds
+__device__ __forceinline__ void lin_poison_rows(const LinArgs& a, int m0, int tm, bool first_channel_tile) {
+    if (!first_channel_tile) return;
+    for (int r = threadIdx.x; r < tm; r += kLinThreads)
+        if (m0 + r < a.M) a.rowsum[m0 + r] = kLinNoRow;
+}
+
+// The 16 registers of one 32 x 32 result as this lane's 16 CONTIGUOUS code bytes of row `row`: channels c0 + 16 * half .. + 15.
+// In the register map the lane owns 4 g .. 4 g + 3 -> channels 8 g + 4 half ..: words A0..A3 in half 0 and B0..B3 in half 1
+// of a row whose 32 bytes are A0 B0 A1 B1 A2 B2 A3 B3.  Each lane sends the two words its partner (lane ^ 32) needs and keeps
+// the two it needs itself: half 0 ends with A0 B0 A1 B1, half 1 with A2 B2 A3 B3.  Every lane of the wave calls (the exchange
+// is wave-wide); a row beyond M or a granule beyond N gives zero words.  `rej`: elements of this lane without a code.
+__device__ __forceinline__ i32x4 lin_code_granule(const LinArgs& a, const i32x16& acc, int row, int c0, int half, int zx, float sx,
+                                                  const QParams& op, unsigned int& rej) {
+    const bool live = row < a.M;
+    const int rs_raw = a.xrs[min(row, a.M - 1)];
+    const bool row_nan = rs_raw == kLinNoRow;
+    const int rs = row_nan ? 0 : rs_raw, kzx = a.K * zx;
+    const bool has_bias = a.bias != nullptr;
+    unsigned int w[4], bad = 0;
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        const int c = c0 + 8 * g + 4 * half;           // N % 16 == 0: c < N takes c .. c + 3 with it
+        w[g] = 0;
+        if (!live || c >= a.N) continue;
+        i32x4 cs, zw;
+        float sw[4], b[4] = {0.f, 0.f, 0.f, 0.f};
+        if (a.vec) {
+            cs = *reinterpret_cast<const i32x4*>(a.wcs + c);
+            zw = *reinterpret_cast<const i32x4*>(a.wz + c);
+            const float4 s4 = *reinterpret_cast<const float4*>(a.ws + c);
+            sw[0] = s4.x, sw[1] = s4.y, sw[2] = s4.z, sw[3] = s4.w;
+            if (has_bias) {
+                const float4 b4 = *reinterpret_cast<const float4*>(a.bias + c);
+                b[0] = b4.x, b[1] = b4.y, b[2] = b4.z, b[3] = b4.w;
+            }
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                cs[e] = a.wcs[c + e];
+                zw[e] = a.wz[c + e];
+                sw[e] = a.ws[c + e];
+                if (has_bias) b[e] = a.bias[c + e];
+            }
+        }
+        unsigned int u[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const float v = lin_value(acc[4 * g + e], rs, cs[e], zw[e], zx, kzx, sx, sw[e], has_bias, b[e], row_nan);
+            u[e] = code_of(a.gelu ? gelu_erf(v) : v, op, a.oq.qmin, a.oq.qmax, bad);
+        }
+        w[g] = (u[0] | (u[1] << 8) | (u[2] << 16) | (u[3] << 24)) ^ 0x80808080u;
+    }
+    rej += bad;
+    const int r0 = __shfl_xor(static_cast<int>(half ? w[0] : w[2]), 32, OSQ_WAVE);
+    const int r1 = __shfl_xor(static_cast<int>(half ? w[1] : w[3]), 32, OSQ_WAVE);
+    return half ? i32x4{r0, static_cast<int>(w[2]), r1, static_cast<int>(w[3])}
+                : i32x4{static_cast<int>(w[0]), r0, static_cast<int>(w[1]), r1};
+}
+
+// sum of the 16 bytes of a granule as int8
+__device__ __forceinline__ int lin_granule_sum(const i32x4& v) {
+    int s = 0;
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+#pragma unroll
+        for (int b = 0; b < 4; ++b) s += static_cast<int>(static_cast<int8_t>(static_cast<unsigned int>(v[e]) >> (8 * b)));
+    return s;
+}
+
+// The end of a kCodes workgroup, after its adds and flags: take a ticket of row tile `tile`; whoever draws the last of `total`
+// sees every other workgroup's adds and flags (their fence came before their ticket) and overwrites the flagged rows, and the
+// rows that came in without codes, with kLinNoRow.  Nobody waits.  `s_last`: one word of LDS.
+__device__ __forceinline__ void lin_finish_rows(const LinArgs& a, int tile, int total, int m0, int tm, int* s_last) {
+    __threadfence();
+    __syncthreads();
+    if (threadIdx.x == 0) *s_last = atomicAdd(a.tickets + tile, 1) == total - 1;
+    __syncthreads();
+    if (!*s_last) return;
+    __threadfence();
+    for (int r = threadIdx.x; r < tm; r += kLinThreads) {
+        const int row = m0 + r;
+        if (row < a.M && (a.xrs[row] == kLinNoRow || __hip_atomic_load(a.flags + row, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)))
+            atomicExch(a.rowsum + row, kLinNoRow);
+    }
+}
+
+// a row's flag: some element of it has no code (a row that came in without codes needs none: everyone reads that from xrs)
+__device__ __forceinline__ void lin_flag_row(const LinArgs& a, int row, unsigned int rej) {
+    if (rej && row < a.M && a.xrs[row] != kLinNoRow) atomicOr(a.flags + row, 1);
+}
+
+// The rows kernels' end, wave 0 alone (the workgroup's other waves have left: no barrier from here on): a lane's granule goes
+// straight to memory -- a workgroup owns 32 bytes of a row, two lanes' worth, there is nothing to gather -- the row's partial
+// sum is the two lanes', one add per row.
+__device__ __forceinline__ void lin_codes_rows(const LinArgs& a, const i32x16& acc, int l31, int n0, int half, int zx, float sx,
+                                               const QParams& op) {
+    unsigned int rej = 0;
+    const i32x4 v = lin_code_granule(a, acc, l31, n0, half, zx, sx, op, rej);
+    const int c = n0 + 16 * half;
+    const bool live = l31 < a.M && c < a.N;
+    if (live) *reinterpret_cast<i32x4*>(a.codes + static_cast<int64_t>(l31) * a.N + c) = v;
+    int sum = lin_granule_sum(v);                     // zero words where the granule is not there
+    sum += __shfl_xor(sum, 32, OSQ_WAVE);
+    if (half == 0 && l31 < a.M && a.xrs[l31] != kLinNoRow) atomicAdd(a.rowsum + l31, sum);
+    lin_flag_row(a, l31, rej);
+    __threadfence();                                  // the wave's adds and flags, then lane 0's ticket
+    int last = 0;
+    if (threadIdx.x == 0) last = atomicAdd(a.tickets, 1) == static_cast<int>(gridDim.x) - 1;
+    if (!__shfl(last, 0, OSQ_WAVE)) return;
+    __threadfence();
+    if (threadIdx.x < a.M && (a.xrs[threadIdx.x] == kLinNoRow ||
+                              __hip_atomic_load(a.flags + threadIdx.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)))
+        atomicExch(a.rowsum + threadIdx.x, kLinNoRow);
+}
+
+constexpr int kLinCodePitch = kLinTile + 16;          // bytes of a staged row of codes: 9 granules, see linear_int_kernel
+
+// kW4: a.wc is packed [N, K / 2]; a granule of W is in flight as its 8 packed bytes (gw[u].x, .y) and unpacked at the stash.
+// kCodes: the epilogue writes the next linear's codes and row sums instead of out.
+template <bool kW4, bool kCodes = false>
 __global__ __launch_bounds__(kLinThreads) void linear_int_kernel(LinArgs a) {
     __shared__ __attribute__((aligned(16))) uint8_t s_w[2][kLinTile * kLinPitch];
     __shared__ __attribute__((aligned(16))) uint8_t s_x[2][kLinTile * kLinPitch];
@@ -277,8 +430,12 @@ __global__ __launch_bounds__(kLinThreads) void linear_int_kernel(LinArgs a) {
     const int m0 = static_cast<int>(blockIdx.x % mtiles) * kLinTile, n0 = static_cast<int>(blockIdx.x / mtiles) * kLinTile;
     int zx;
     float sx;
-    if (!lin_prologue(a, zx, sx)) {                   // uniform
-        lin_fill_nan(a, m0, n0, kLinTile, kLinTile);
+    QParams op{1.f, 0.f};
+    bool ok = lin_prologue(a, zx, sx);
+    if constexpr (kCodes) ok = lin_out_params(a, op) && ok;      // both repairs ride, whatever the other says
+    if (!ok) {                                        // uniform
+        if constexpr (kCodes) lin_poison_rows(a, m0, kLinTile, n0 == 0);
+        else lin_fill_nan(a, m0, n0, kLinTile, kLinTile);
         return;
     }
     const int wm = w & 1, wn = w >> 1;                // this wave's 64 x 64 part
@@ -350,13 +507,56 @@ __global__ __launch_bounds__(kLinThreads) void linear_int_kernel(LinArgs a) {
         __syncthreads();
     }
 
+    if constexpr (!kCodes) {
 #pragma unroll
-    for (int i = 0; i < 2; ++i)
+        for (int i = 0; i < 2; ++i)
 #pragma unroll
-        for (int j = 0; j < 2; ++j)
-            lin_store_tile(a, acc[i][j], m0 + 64 * wm + 32 * i + l31, n0 + 64 * wn + 32 * j, half, zx, sx);
+            for (int j = 0; j < 2; ++j)
+                lin_store_tile(a, acc[i][j], m0 + 64 * wm + 32 * i + l31, n0 + 64 * wn + 32 * j, half, zx, sx);
+    } else {
+        // The operand LDS is free (every wave is past the last step's barrier): the tile's 128 x 128 code bytes are staged in
+        // s_w at a pitch of 128 + 16 bytes, so that a row leaves as whole 128-byte lines.  Both sides move 16 bytes per lane, 16
+        // lanes to a phase over 16 groups of four banks; a granule at (row, g) lies in group (9 row + g) mod 16.  Staging: the
+        // 16 lanes of a phase hold 16 consecutive rows at one g -- 9 is odd, 16 groups.  Read-out: a phase takes the 8 granules
+        // of row R and of row R + 8 -- groups 9 R + 0 .. 7 and 9 R + 72 + 0 .. 7 = 9 R + 8 .. 15 -- and 8 consecutive lanes write
+        // one 128-byte line of a row to memory.
+        uint8_t* s_c = &s_w[0][0];                    // 128 x 144 B = 18 KiB of its 20
+        int* s_last = reinterpret_cast<int*>(&s_x[0][0]);
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const int rl = 64 * wm + 32 * i + l31;
+            unsigned int rej = 0;
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const int cl = 64 * wn + 32 * j;
+                *reinterpret_cast<i32x4*>(&s_c[rl * kLinCodePitch + cl + 16 * half]) =
+                    lin_code_granule(a, acc[i][j], m0 + rl, n0 + cl, half, zx, sx, op, rej);
+            }
+            lin_flag_row(a, m0 + rl, rej);
+        }
+        __syncthreads();
+        const int g = threadIdx.x & 7, c = n0 + 16 * g;
+#pragma unroll
+        for (int p = 0; p < kLinTile / 32; ++p) {
+            const int rl = 32 * p + 16 * (threadIdx.x >> 7) + 8 * ((threadIdx.x >> 3) & 1) + ((threadIdx.x >> 4) & 7);
+            const int row = m0 + rl;
+            const bool live = row < a.M && c < a.N;
+            i32x4 v = {0, 0, 0, 0};
+            if (live) {
+                v = *reinterpret_cast<const i32x4*>(&s_c[rl * kLinCodePitch + 16 * g]);
+                *reinterpret_cast<i32x4*>(a.codes + static_cast<int64_t>(row) * a.N + c) = v;
+            }
+            int sum = lin_granule_sum(v);             // the row's 8 granules are 8 consecutive lanes
+            sum += __shfl_xor(sum, 1, OSQ_WAVE);
+            sum += __shfl_xor(sum, 2, OSQ_WAVE);
+            sum += __shfl_xor(sum, 4, OSQ_WAVE);
+            if (g == 0 && row < a.M && a.xrs[row] != kLinNoRow) atomicAdd(a.rowsum + row, sum);
+        }
+        lin_finish_rows(a, m0 / kLinTile, (a.N + kLinTile - 1) / kLinTile, m0, kLinTile, s_last);
+    }
 }
 
+template <bool kCodes>
 __global__ __launch_bounds__(kLinThreads) void linear_int_rows_kernel(LinArgs a) {
     constexpr int kWaves = kLinThreads / OSQ_WAVE;
     __shared__ int s_part[kWaves - 1][16][OSQ_WAVE];
@@ -365,8 +565,12 @@ __global__ __launch_bounds__(kLinThreads) void linear_int_rows_kernel(LinArgs a)
     const int n0 = static_cast<int>(blockIdx.x) * 32;
     int zx;
     float sx;
-    if (!lin_prologue(a, zx, sx)) {                   // uniform
-        lin_fill_nan(a, 0, n0, kLinRowsM, 32);
+    QParams op{1.f, 0.f};
+    bool ok = lin_prologue(a, zx, sx);
+    if constexpr (kCodes) ok = lin_out_params(a, op) && ok;
+    if (!ok) {                                        // uniform
+        if constexpr (kCodes) lin_poison_rows(a, 0, kLinRowsM, n0 == 0);
+        else lin_fill_nan(a, 0, n0, kLinRowsM, 32);
         return;
     }
     const uint8_t* wrow = a.wc + static_cast<int64_t>(min(n0 + l31, a.N - 1)) * a.K + 16 * half;
@@ -399,7 +603,8 @@ __global__ __launch_bounds__(kLinThreads) void linear_int_rows_kernel(LinArgs a)
     for (int v = 0; v < kWaves - 1; ++v)
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[r] += s_part[v][r][lane];
-    lin_store_tile(a, acc, l31, n0, half, zx, sx);
+    if constexpr (kCodes) lin_codes_rows(a, acc, l31, n0, half, zx, sx, op);
+    else lin_store_tile(a, acc, l31, n0, half, zx, sx);
 }
 
 // One chunk of a lane of linear_int_rows_kernel_w4: per 64-k step its channel's 16 packed bytes (32 k) and its x row's 2 x 16.
@@ -407,6 +612,7 @@ struct W4Chunk {
     i32x4 w[2], x[2][2];
 };
 
+template <bool kCodes>
 __global__ __launch_bounds__(kLinThreads) void linear_int_rows_kernel_w4(LinArgs a) {
     constexpr int kWaves = kLinThreads / OSQ_WAVE;
     __shared__ int s_part[kWaves - 1][16][OSQ_WAVE];
@@ -416,8 +622,12 @@ __global__ __launch_bounds__(kLinThreads) void linear_int_rows_kernel_w4(LinArgs
     const int n0 = static_cast<int>(blockIdx.x) * 32;
     int zx;
     float sx;
-    if (!lin_prologue(a, zx, sx)) {                   // uniform
-        lin_fill_nan(a, 0, n0, kLinRowsM, 32);
+    QParams op{1.f, 0.f};
+    bool ok = lin_prologue(a, zx, sx);
+    if constexpr (kCodes) ok = lin_out_params(a, op) && ok;
+    if (!ok) {                                        // uniform
+        if constexpr (kCodes) lin_poison_rows(a, 0, kLinRowsM, n0 == 0);
+        else lin_fill_nan(a, 0, n0, kLinRowsM, 32);
         return;
     }
     const uint8_t* wrow = a.wc + static_cast<int64_t>(min(n0 + l31, a.N - 1)) * (a.K / 2);
@@ -504,7 +714,8 @@ __global__ __launch_bounds__(kLinThreads) void linear_int_rows_kernel_w4(LinArgs
     for (int v = 0; v < kWaves - 1; ++v)
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[r] += s_part[v][r][lane];
-    lin_store_tile(a, acc, l31, n0, half, zx, sx);
+    if constexpr (kCodes) lin_codes_rows(a, acc, l31, n0, half, zx, sx, op);
+    else lin_store_tile(a, acc, l31, n0, half, zx, sx);
 }
 
 static bool lin_quant_ok(int mode, int quant_min, int quant_max) {
@@ -575,36 +786,58 @@ extern "C" int osq_weight_codes_sums_w4(const float* w, int64_t rows, int64_t co
                             grad_factor, quant_min, quant_max, stream);
 }
 
-// osq_linear_int and its packed twin: w_codes [channels, cols] or [channels, cols / 2]
+// what osq_linear_int_codes writes instead of out, and how: null for osq_linear_int and its packed twin
+struct LinCodesOut {
+    uint8_t* codes;
+    int32_t *rowsum, *scratch;
+    DecQuant oq;
+    int gelu;
+};
+
+// osq_linear_int, its packed twin and osq_linear_int_codes: w_codes [channels, cols] or [channels, cols / 2]
 static int lin_launch(bool w4, const uint8_t* x_codes, const int32_t* x_rowsum, const uint8_t* w_codes, const int32_t* w_colsum,
                       const float* w_scale, const int32_t* w_zw, const int32_t* w_bad, const float* bias, float* out,
                       int64_t rows, int64_t channels, int64_t cols, float* x_scale, void* x_zero_point, int x_zp_type,
-                      int x_mode, float x_grad_factor, int x_quant_min, int x_quant_max, osq_stream stream) {
+                      int x_mode, float x_grad_factor, int x_quant_min, int x_quant_max, osq_stream stream,
+                      const LinCodesOut* co = nullptr) {
     OSQ_REQUIRE(rows >= 0 && rows <= INT32_MAX && channels >= 0 && channels <= INT32_MAX, "linear_int: bad shape");
     OSQ_REQUIRE(lin_k_ok(cols), "linear_int: K must be a multiple of 16 in [16, 16384]");
     OSQ_REQUIRE(x_scale && x_zero_point, "linear_int: null scale or zero_point");
     OSQ_REQUIRE(x_zp_type == OSQ_ZP_INT32 || x_zp_type == OSQ_ZP_FLOAT32, "linear_int: bad zp_type");
     OSQ_REQUIRE(lin_quant_ok(x_mode, x_quant_min, x_quant_max), "linear_int: bad mode, or more than 256 codes");
+    OSQ_REQUIRE(!co || channels == 0 || lin_k_ok(channels), "linear_int_codes: N must be a multiple of 16 in [16, 16384]");
     if (rows == 0 || channels == 0) return OSQ_OK;
-    OSQ_REQUIRE(x_codes && x_rowsum && w_codes && w_colsum && w_scale && w_zw && w_bad && out, "linear_int: null tensor");
-    OSQ_REQUIRE(aligned16(x_codes) && aligned16(w_codes), "linear_int: codes not 16-byte aligned");
+    OSQ_REQUIRE(x_codes && x_rowsum && w_codes && w_colsum && w_scale && w_zw && w_bad && (co ? co->codes && co->rowsum && co->scratch : out != nullptr),
+                "linear_int: null tensor");
+    OSQ_REQUIRE(aligned16(x_codes) && aligned16(w_codes) && (!co || aligned16(co->codes)), "linear_int: codes not 16-byte aligned");
     OSQ_REQUIRE(((reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(bias) | reinterpret_cast<uintptr_t>(x_rowsum) |
-                  reinterpret_cast<uintptr_t>(w_colsum) | reinterpret_cast<uintptr_t>(w_scale) | reinterpret_cast<uintptr_t>(w_zw)) & 3u) == 0,
+                  reinterpret_cast<uintptr_t>(w_colsum) | reinterpret_cast<uintptr_t>(w_scale) | reinterpret_cast<uintptr_t>(w_zw) |
+                  reinterpret_cast<uintptr_t>(co ? co->rowsum : nullptr) | reinterpret_cast<uintptr_t>(co ? co->scratch : nullptr)) & 3u) == 0,
                 "linear_int: a tensor is not 4-byte aligned");
     const int vec = channels % 4 == 0 && aligned16(out) && aligned16(w_colsum) && aligned16(w_scale) && aligned16(w_zw) && aligned16(bias);
-    const LinArgs a{x_codes, w_codes, x_rowsum, w_colsum, w_zw, w_bad, w_scale, bias, out, static_cast<int>(rows),
-                    static_cast<int>(channels), static_cast<int>(cols), vec, OSQ_DEC_QUANT(x)};
+    LinArgs a{x_codes, w_codes, x_rowsum, w_colsum, w_zw, w_bad, w_scale, bias, out, static_cast<int>(rows),
+              static_cast<int>(channels), static_cast<int>(cols), vec, OSQ_DEC_QUANT(x)};
+    if (co) {                                         // scratch: a flag per row, then a ticket per row tile
+        a.codes = co->codes;
+        a.rowsum = co->rowsum;
+        a.flags = co->scratch;
+        a.tickets = co->scratch + rows;
+        a.oq = co->oq;
+        a.gelu = co->gelu;
+    }
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (rows <= kLinRowsM) {
-        hipLaunchKernelGGL(w4 ? linear_int_rows_kernel_w4 : linear_int_rows_kernel, dim3(static_cast<unsigned>((channels + 31) / 32)),
-                           dim3(kLinThreads), 0, st, a);
+        const auto kernel = co ? (w4 ? linear_int_rows_kernel_w4<true> : linear_int_rows_kernel<true>)
+                               : (w4 ? linear_int_rows_kernel_w4<false> : linear_int_rows_kernel<false>);
+        hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>((channels + 31) / 32)), dim3(kLinThreads), 0, st, a);
     } else {
         const int64_t blocks = ((rows + kLinTile - 1) / kLinTile) * ((channels + kLinTile - 1) / kLinTile);
         OSQ_REQUIRE(blocks <= INT32_MAX, "linear_int: too many tiles");
-        hipLaunchKernelGGL(w4 ? linear_int_kernel<true> : linear_int_kernel<false>, dim3(static_cast<unsigned>(blocks)),
-                           dim3(kLinThreads), 0, st, a);
+        const auto kernel = co ? (w4 ? linear_int_kernel<true, true> : linear_int_kernel<false, true>)
+                               : (w4 ? linear_int_kernel<true, false> : linear_int_kernel<false, false>);
+        hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>(blocks)), dim3(kLinThreads), 0, st, a);
     }
-    return check_launch(w4 ? "linear_int_w4" : "linear_int");
+    return check_launch(co ? "linear_int_codes" : w4 ? "linear_int_w4" : "linear_int");
 }
 
 extern "C" int osq_linear_int(const uint8_t* x_codes, const int32_t* x_rowsum, const uint8_t* w_codes, const int32_t* w_colsum,
@@ -621,4 +854,21 @@ extern "C" int osq_linear_int_w4(const uint8_t* x_codes, const int32_t* x_rowsum
                                  int x_mode, float x_grad_factor, int x_quant_min, int x_quant_max, osq_stream stream) {
     return lin_launch(true, x_codes, x_rowsum, w_codes, w_colsum, w_scale, w_zw, w_bad, bias, out, rows, channels, cols, x_scale,
                       x_zero_point, x_zp_type, x_mode, x_grad_factor, x_quant_min, x_quant_max, stream);
+}
+
+extern "C" int osq_linear_int_codes(const uint8_t* x_codes, const int32_t* x_rowsum, const uint8_t* w_codes, const int32_t* w_colsum,
+                                    const float* w_scale, const int32_t* w_zw, const int32_t* w_bad, const float* bias,
+                                    uint8_t* codes, int32_t* rowsum, int32_t* scratch, int64_t rows, int64_t channels, int64_t cols,
+                                    float* x_scale, void* x_zero_point, int x_zp_type, int x_mode, float x_grad_factor,
+                                    int x_quant_min, int x_quant_max, float* out_scale, void* out_zero_point, int out_zp_type,
+                                    int out_mode, float out_grad_factor, int out_quant_min, int out_quant_max, int activation,
+                                    int w_bits, osq_stream stream) {
+    OSQ_REQUIRE(w_bits == 8 || w_bits == 4, "linear_int_codes: w_bits is 8 or 4");
+    OSQ_REQUIRE(activation == 0 || activation == 1, "linear_int_codes: activation is 0 (none) or 1 (exact GELU)");
+    OSQ_REQUIRE(out_scale && out_zero_point, "linear_int_codes: null out scale or zero_point");
+    OSQ_REQUIRE(out_zp_type == OSQ_ZP_INT32 || out_zp_type == OSQ_ZP_FLOAT32, "linear_int_codes: bad out zp_type");
+    OSQ_REQUIRE(lin_quant_ok(out_mode, out_quant_min, out_quant_max), "linear_int_codes: bad out mode, or more than 256 codes");
+    const LinCodesOut co{codes, rowsum, scratch, OSQ_DEC_QUANT(out), activation};
+    return lin_launch(w_bits == 4, x_codes, x_rowsum, w_codes, w_colsum, w_scale, w_zw, w_bad, bias, nullptr, rows, channels, cols,
+                      x_scale, x_zero_point, x_zp_type, x_mode, x_grad_factor, x_quant_min, x_quant_max, stream, &co);
 }

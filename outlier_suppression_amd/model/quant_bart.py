@@ -28,6 +28,7 @@ from .losses import LmLossInfo, classification_loss, lm_loss, span_loss, token_l
 from .. import ops
 from .. import util_layernorm as _UL
 from ..quantization import QuantizedModule, Quantizer
+from ..quantization import linear_int
 from ..quantization.linear_int import shared_codes
 from ..util_layernorm import (GammaResidual, QuantizedLayerNorm, activation_fake_quant, attention_probs_fake_quant,
                               attention_sequence_fake_quant,
@@ -826,6 +827,17 @@ class QuantizedBartAttention(QuantizedModule):
         return out
 
 
+def _ffn(layer, h, observation_mask):
+    """fc1 -> activation -> quantizer -> fc2 of an encoder or decoder layer without activation dropout.  FUSE_LINEAR_INT:
+    fc1's launch writes fc2's codes (quantization/linear_int.py, ``ffn``) where both linears take the integer launches."""
+    q = layer.fc1_act_fn_post_act_fake_quantize
+    if _UL.FUSE_LINEAR_INT:
+        out = linear_int.ffn(layer.fc1, layer.activation_fn, q, layer.fc2, h)
+        if out is not None:
+            return out
+    return layer.fc2(activation_fake_quant(layer.activation_fn, q, layer.fc1(h), observation_mask))
+
+
 class QuantizedBartEncoderLayer(QuantizedModule):
     def __init__(self, org_module, w_qconfig, a_qconfig, qoutput=True, backend="academic"):
         super().__init__(backend)
@@ -861,9 +873,10 @@ class QuantizedBartEncoderLayer(QuantizedModule):
         if self.training and self.activation_dropout > 0:
             h = self._drop(self.activation_fn(self.fc1(h)), self.activation_dropout)
             h = self.fc1_act_fn_post_act_fake_quantize(h, observation_mask, 1)
+            h = self.fc2(h)
         else:
-            h = activation_fake_quant(self.activation_fn, self.fc1_act_fn_post_act_fake_quantize, self.fc1(h), observation_mask)
-        h = self._drop(self.fc2(h), self.dropout)
+            h = _ffn(self, h, observation_mask)
+        h = self._drop(h, self.dropout)
         return residual_layernorm(self.before_final_layer_norm_residual, self.final_layer_norm, residual, h, observation_mask)
 
 
@@ -921,9 +934,10 @@ class QuantizedBartDecoderLayer(QuantizedModule):
         if self.training and self.activation_dropout > 0:
             h = self._drop(self.activation_fn(self.fc1(h)), self.activation_dropout)
             h = self.fc1_act_fn_post_act_fake_quantize(h, observation_mask, 1)
+            h = self.fc2(h)
         else:
-            h = activation_fake_quant(self.activation_fn, self.fc1_act_fn_post_act_fake_quantize, self.fc1(h), observation_mask)
-        h = self._drop(self.fc2(h), self.dropout)
+            h = _ffn(self, h, observation_mask)
+        h = self._drop(h, self.dropout)
         return residual_layernorm(self.before_final_layer_norm_residual, self.final_layer_norm, residual, h, observation_mask)
 
 

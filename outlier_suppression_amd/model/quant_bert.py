@@ -21,6 +21,8 @@ from torch import nn
 from .losses import classification_loss, span_loss, with_loss
 
 from ..quantization import QuantizedModule, Quantizer
+from .. import util_layernorm
+from ..quantization import linear_int
 from ..quantization.linear_int import shared_codes
 from ..util_layernorm import (GammaResidual, QuantizedLayerNorm, activation_fake_quant, attention_probs_fake_quant,
                               attention_sequence_fake_quant,
@@ -124,7 +126,11 @@ class _DenseResidualNorm(QuantizedModule):
         self.LayerNorm = QuantizedLayerNorm(org_module.LayerNorm, w_qconfig, a_qconfig, qoutput=qoutput, backend=backend)
 
     def forward(self, hidden_states, input_tensor, observation_mask=None):
-        hidden_states = self.dropout(self.dense(hidden_states))
+        return self.after_dense(self.dense(hidden_states), input_tensor, observation_mask)
+
+    def after_dense(self, hidden_states, input_tensor, observation_mask=None):
+        """forward from ``dense``'s result on: QuantizedBertLayer hands over what its feed-forward launches computed"""
+        hidden_states = self.dropout(hidden_states)
         return residual_layernorm(self.before_LayerNorm_residual, self.LayerNorm, input_tensor, hidden_states, observation_mask)
 
 
@@ -175,6 +181,12 @@ class QuantizedBertLayer(QuantizedModule):
     def forward(self, hidden_states, attention_mask=None, observation_mask=None):
         with shared_codes():       # FUSE_LINEAR_INT: query / key / value read one set of activation codes
             att = self.attention(hidden_states, attention_mask, observation_mask=observation_mask)
+            if util_layernorm.FUSE_LINEAR_INT and self.intermediate.qoutput:
+                # fc1's launch writes fc2's codes (quantization/linear_int.py, ``ffn``); anything it does not take: the lines below
+                out = linear_int.ffn(self.intermediate.dense, self.intermediate.intermediate_act_fn,
+                                     self.intermediate.intermediate_act_fn_post_act_fake_quantize, self.output.dense, att)
+                if out is not None:
+                    return self.output.after_dense(out, att, observation_mask)
             inter = self.intermediate(att, observation_mask=observation_mask)
             return self.output(inter, att, observation_mask=observation_mask)
 

@@ -2332,6 +2332,46 @@ def linear_int(x_codes, x_rowsum, x_record, w_entry, bias=None):
     return out
 
 
+def linear_int_codes(x_codes, x_rowsum, x_record, w_entry, bias, out_record, activation="gelu"):
+    """(codes [..., N] uint8, rowsum [...] int32): ``activation_codes`` of the fake-quantised (``activation="gelu"``: GELU, then
+    fake-quantised) ``linear_int(x_codes, x_rowsum, x_record, w_entry, bias)`` under ``out_record``, the per-tensor quantizer
+    of the linear that reads them -- word for word, without the fp32 tensor ever being written (include/osq_hip.h, "Codes for
+    the next linear").  A row without codes, coming in or made here, has rowsum LINEAR_INT_NO_ROW.  One zeroing launch and
+    one kernel, no host sync, legal inside a stream capture.  ValueError, nothing launched or allocated: what ``linear_int``
+    refuses, an ``activation`` other than "gelu" / None, N % 16 != 0, N > 16384, an out record ``linear_int_refusal`` names."""
+    if activation not in ("gelu", None):
+        raise ValueError(f"linear_int_codes: activation {activation!r} is not 'gelu' or None")
+    k = x_codes.shape[-1] if x_codes.dim() else 0
+    n = w_entry.codes.shape[0]
+    why = "N is not a multiple of 16" if n % 16 else "N exceeds 16384" if n > LINEAR_INT_MAX_K else None
+    if why is None:
+        why = linear_int_refusal(k, x_record, x_rowsum, *w_entry, fp32=(bias,), last_dim=(x_codes,))
+    if why is None:
+        why = linear_int_refusal(n, out_record)
+    packed = k > 0 and tuple(w_entry.codes.shape) == (n, k // 2)
+    if why is None and (x_codes.dtype != torch.uint8 or not x_codes.is_contiguous() or tuple(w_entry.codes.shape) not in ((n, k), (n, k // 2))
+                        or tuple(x_rowsum.shape) != tuple(x_codes.shape[:-1]) or not x_rowsum.is_contiguous()
+                        or (bias is not None and (tuple(bias.shape) != (n,) or not bias.is_contiguous()))):
+        why = "the operands are not dense codes [..., K], row sums [...], a WeightCodes [N, K] and a bias [N]"
+    if why:
+        raise ValueError(f"linear_int_codes: {why}")
+    lib = _hip.load()
+    lead, rows, dev = tuple(x_codes.shape[:-1]), x_rowsum.numel(), x_codes.device
+    codes = torch.empty(lead + (n,), dtype=torch.uint8, device=dev)
+    # one clear: the row sums, then the scratch tail nobody sees -- a flag per row, a ticket per tile of 128 rows
+    words = torch.zeros(2 * rows + (rows + LINEAR_INT_TILE - 1) // LINEAR_INT_TILE, dtype=torch.int32, device=dev)
+    rowsum = words[:rows].view(lead)
+    if rows and n:
+        (xs, xz, xlo, xhi, xmode, xg), (os_, oz, olo, ohi, omode, og) = x_record, out_record
+        _hip.check(lib.osq_linear_int_codes(
+            _hip.ptr(x_codes), _hip.ptr(x_rowsum), _hip.ptr(w_entry.codes), _hip.ptr(w_entry.colsum), _hip.ptr(w_entry.scale),
+            _hip.ptr(w_entry.zw), _hip.ptr(w_entry.bad), _hip.ptr(bias), _hip.ptr(codes), _hip.ptr(words), _hip.ptr(words[rows:]),
+            rows, n, k, _hip.ptr(xs), _hip.ptr(xz), _zp_type(xz), int(xmode), float(xg), int(xlo), int(xhi),
+            _hip.ptr(os_), _hip.ptr(oz), _zp_type(oz), int(omode), float(og), int(olo), int(ohi), 1 if activation == "gelu" else 0,
+            4 if packed else 8, _hip.stream_ptr(dev)), "linear_int_codes")
+    return codes, rowsum
+
+
 # ---------------------------------------------------------------------------------------
 # one decoding step's attention over the KV cache: scores, mask, softmax, two quantizers in one launch
 # ---------------------------------------------------------------------------------------

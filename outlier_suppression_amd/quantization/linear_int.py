@@ -27,6 +27,13 @@ from . import weight_cache
 # packed kernels.  The words of the result are the same either way; on by default because no shape measured in
 # profiles/linear_int_w4_ab.txt loses beyond the 8-bit form's own range and the lm_head shapes gain 23 - 29 %.
 PACK_W4 = True
+# A feed-forward block (fc1 -> GELU -> quantizer -> fc2) whose two linears take the integer launches has fc1's launch write
+# fc2's activation codes (ffn below): the block's largest tensor is never written as fp32.  The words are the chain's.
+# On by default for the shapes that gain: up to FFN_MAX_ROWS rows (the rows kernels: a decoding step, +15 - 18 % on the block's
+# launches) the path is taken; above it the tile kernel's epilogue LOSES 31 - 45 % to the chain it replaces
+# (profiles/linear_int_codes_ab.txt), so those calls keep the chain.  FFN_MAX_ROWS = None lifts the limit (A/B, tests).
+FUSE_FFN = True
+FFN_MAX_ROWS = ops.LINEAR_INT_ROWS_M
 _SHARED = []        # the open shared_codes() scopes: {(id(x), version, id(producer)): (x, codes, rowsum)}
 
 
@@ -146,6 +153,16 @@ def bind_linear_producers(model):
 
 def why_not(op, x):
     """None when ``op(x)`` takes the integer launches, else the reason -- one phrase -- it runs ``F.linear``."""
+    return _why_not(op, x)
+
+
+def weight_why_not(op):
+    """``why_not`` without an input tensor: the producer, the module's and the weight quantizer's state, K, the weight side's
+    tensors -- what can be asked of a linear whose input does not exist yet (``ffn`` asks it of fc2)."""
+    return _why_not(op, None)
+
+
+def _why_not(op, x):
     from .. import util_layernorm as UL
     q = producer_of(op)
     if q is None:
@@ -161,10 +178,11 @@ def why_not(op, x):
     if fq.fake_quant_enabled != 1 or fq.observer_enabled == 1 or fq.ch_axis not in (0, -1):
         return "the weight quantizer is not plainly quantising and cacheable"
     record = (q.scale, q.zero_point, q.quant_min, q.quant_max)
-    why = ops.linear_int_refusal(op.in_features, record, fp32=(x, op.weight, fq.scale, op.bias), last_dim=(x,))
+    given = () if x is None else (x,)
+    why = ops.linear_int_refusal(op.in_features, record, fp32=given + (op.weight, fq.scale, op.bias), last_dim=given)
     if why is None and fq.quant_max - fq.quant_min > ops.LINEAR_INT_MAX_RANGE:
         why = "a quantizer has more than 256 codes"
-    if why is None and not (x.numel() and op.weight.is_contiguous() and op.weight.data_ptr() % 16 == 0
+    if why is None and not ((x is None or x.numel()) and op.weight.is_contiguous() and op.weight.data_ptr() % 16 == 0
                             and (op.bias is None or op.bias.is_contiguous())):
         why = "the operands are not dense, 16-byte aligned tensors"
     if why is None and not (fq.scale.numel() == fq.zero_point.numel() == (op.out_features if fq.ch_axis == 0 else 1)):
@@ -172,6 +190,27 @@ def why_not(op, x):
     if why is None and not (weight_cache.enabled and weight_cache.cacheable(op, fq)):      # last: it asks where the weight lives
         why = "the weight quantizer is not plainly quantising and cacheable"
     return why
+
+
+def _input_codes(op, x):
+    """(codes, rowsum, record) of ``op``'s input under its producer: one ``ops.activation_codes`` launch per (tensor, version,
+    producer) of the open ``shared_codes()`` scope."""
+    from .. import util_layernorm as UL
+    q = producer_of(op)
+    record = UL._site_record(q, x.numel())
+    key = (id(x), x._version, id(q))
+    held = _SHARED[-1].get(key) if _SHARED else None
+    if held is None:
+        codes, rowsum = ops.activation_codes(x, record)
+        if _SHARED:
+            _SHARED[-1][key] = (x, codes, rowsum)      # x itself: its id stays its own while the entry lives
+    else:
+        _, codes, rowsum = held
+    return codes, rowsum, record
+
+
+def _bias(op):
+    return None if op.bias is None else op.bias.detach()
 
 
 def forward(op, x):
@@ -188,15 +227,34 @@ def forward(op, x):
         info.eager += 1
         info.reason = why
         return None
-    q = producer_of(op)
-    record = UL._site_record(q, x.numel())
-    key = (id(x), x._version, id(q))
-    held = _SHARED[-1].get(key) if _SHARED else None
-    if held is None:
-        codes, rowsum = ops.activation_codes(x, record)
-        if _SHARED:
-            _SHARED[-1][key] = (x, codes, rowsum)      # x itself: its id stays its own while the entry lives
-    else:
-        _, codes, rowsum = held
+    codes, rowsum, record = _input_codes(op, x)
     info.fused += 1
-    return ops.linear_int(codes, rowsum, record, entry, None if op.bias is None else op.bias.detach())
+    return ops.linear_int(codes, rowsum, record, entry, _bias(op))
+
+
+def ffn(fc1, act_fn, q, fc2, x):
+    """``fc2(q(act_fn(fc1(x))))`` of a feed-forward block under FUSE_LINEAR_INT and FUSE_FFN: fc1's launch writes the codes
+    fc2 reads (``ops.linear_int_codes``), the [..., 4H] fp32 tensor is never made -- or None, nothing launched and nothing
+    counted, when the chain must run: the caller's lines then do, and count, what they did before.  The words of the result
+    are the chain's.  Everything is asked BEFORE anything is launched: both linears take the integer launches (fc2's input
+    side is fc1's output side: N % 16 == 0, N <= 16384), the site is the one ``util_layernorm.activation_fake_quant`` gives
+    one launch (FUSE_ACTIVATION, an exact GELU, ``q`` plainly quantising per tensor), ``q`` is fc2's producer, both weights'
+    codes exist (they are not made inside a stream capture), and the call has at most FFN_MAX_ROWS rows."""
+    from .. import util_layernorm as UL
+    if not (FUSE_FFN and UL.FUSE_ACTIVATION and q is not None and producer_of(fc2) is q and ops.is_exact_gelu(act_fn)):
+        return None
+    if UL._not_plain(q) or not q.scale.is_cuda or why_not(fc1, x) is not None or weight_why_not(fc2) is not None:
+        return None
+    if not (x.is_contiguous() and fc1.out_features == fc2.in_features):
+        return None
+    if FFN_MAX_ROWS is not None and x.numel() // x.shape[-1] > FFN_MAX_ROWS:      # the measured loss: the chain is faster
+        return None
+    entries = weight_cache.weight_codes(fc1), weight_cache.weight_codes(fc2)
+    if entries[0] is None or entries[1] is None:
+        return None
+    codes, rowsum, record = _input_codes(fc1, x)
+    mid = UL._site_record(q, codes.numel() // codes.shape[-1] * fc1.out_features)
+    codes, rowsum = ops.linear_int_codes(codes, rowsum, record, entries[0], _bias(fc1), mid, "gelu")
+    UL.linear_int.fused += 2
+    UL.linear_int.ffn += 1
+    return ops.linear_int(codes, rowsum, mid, entries[1], _bias(fc2))

@@ -89,7 +89,8 @@ activation quantizer that produced its input, so the product runs exactly on the
 (``ops.activation_codes`` + ``ops.linear_int``, csrc/linear_int.hip; the rule is in include/osq_hip.h, "integer linear") and
 the scales are applied once to the int32 sum.  ``quantize_model`` tells each linear its producer (quantization/linear_int.py,
 ``bind_linear_producers``; the binding survives gamma migration); the codes of one producer output are made once per block
-and shared by its consumers.  Autograd off, evaluation mode, both quantizers in the plain quantising state, at most 256 codes, K a multiple of 16 up to 16384; anything else runs
+and shared by its consumers; in a feed-forward block fc1's launch writes fc2's codes itself (``ops.linear_int_codes``,
+``linear_int.ffn`` / ``FUSE_FFN``: the words are the chain's, the [M, 4H] fp32 tensor is never made).  Autograd off, evaluation mode, both quantizers in the plain quantising state, at most 256 codes, K a multiple of 16 up to 16384; anything else runs
 ``F.linear`` and ``util_layernorm.linear_int`` (fused, eager, reason) says why.  Tolerance-equal to ``F.linear`` (closer to
 float64 than it), hence off by default.  ``outlier_suppression_amd.set_fast_linear_int(True)`` / ``OSQ_FAST_LINEAR_INT=1``
 turn it on; the measured outcome per shape is in profiles/linear_int_ab.txt and README.
@@ -252,17 +253,18 @@ heads_backward = HeadsBackwardInfo()
 
 class LinearIntInfo:
     """What the ``QLinear`` calls did under FUSE_LINEAR_INT since ``reset()``: ``fused`` calls that took the integer launches,
-    ``eager`` calls that ran ``F.linear``, and the ``reason`` of the last of those (``util_layernorm.linear_int``).  With the
-    switch off nothing is counted."""
+    ``eager`` calls that ran ``F.linear``, and the ``reason`` of the last of those (``util_layernorm.linear_int``); ``ffn``
+    feed-forward blocks whose fc1 launch wrote fc2's codes (quantization/linear_int.py, ``ffn``: two of ``fused`` each).  With
+    the switch off nothing is counted."""
 
     def __init__(self):
         self.reset()
 
     def reset(self):
-        self.fused, self.eager, self.reason = 0, 0, None
+        self.fused, self.eager, self.reason, self.ffn = 0, 0, None, 0
 
     def __repr__(self):
-        return f"LinearIntInfo(fused={self.fused}, eager={self.eager}, reason={self.reason!r})"
+        return f"LinearIntInfo(fused={self.fused}, eager={self.eager}, reason={self.reason!r}, ffn={self.ffn})"
 
 
 linear_int = LinearIntInfo()

@@ -18,7 +18,14 @@ exceeds the baseline's own range.
            BART's lm_head at 1 and 32 rows, the pooler, 1024 -> 4096 at 32 rows; the tile kernel: 768 -> 3072 at 4096 rows,
            4096 -> 1024 at 16384, 1024 -> 1024 at 192.
 
+  ffn      (--ffn: these rows alone) a feed-forward block's integer launches from fc1's activation codes on (made outside the
+           timed calls): the chain ops.linear_int -> ops.gelu_fake_quant_per_tensor -> ops.activation_codes -> ops.linear_int
+           against ops.linear_int_codes -> ops.linear_int on the same operands, 8-bit and packed weights; the two results are
+           held word-equal first.  Then BERT-base at 32 x 128 and the BART-large encoder pass with linear_int.FUSE_FFN off and
+           on (FFN_MAX_ROWS lifted: the path at every M), both under set_fast_linear_int(True).  The baseline is the chain.
+
     python tools/linear_int_ab.py [--reps 7] [--out profiles/linear_int_ab.txt]
+    python tools/linear_int_ab.py --ffn --inner 20 --out profiles/linear_int_codes_ab.txt
     python tools/linear_int_ab.py --w4 --inner 100 --out profiles/linear_int_w4_ab.txt
 """
 import argparse
@@ -115,6 +122,60 @@ def layer_w4(emit, m, k, n, reps, inner):
     report(emit, timed(forms, reps, inner), "linear_int", "linear_int_w4")
 
 
+FFN_LAYERS = ((4096, 768, 3072), (16384, 1024, 4096), (192, 1024, 4096), (32, 1024, 4096), (1, 1024, 4096))
+
+
+def layer_ffn(emit, m, h, f, bits, reps, inner):
+    """[m, h] -> f -> h: W8A8, or W4A8 on packed entries."""
+    from outlier_suppression_amd import ops
+    dev = torch.device("cuda:0")
+    g = torch.Generator(device=dev).manual_seed(m + h + f)
+    zp = torch.tensor([127], dtype=torch.int32, device=dev)
+    record = (torch.tensor([0.05], device=dev), zp, 0, 255, ops.PARAM_FIXED, 1.0)
+    mid = (torch.tensor([0.02], device=dev), torch.tensor([9], dtype=torch.int32, device=dev), 0, 255, ops.PARAM_FIXED, 1.0)
+    top = 2 ** (bits - 1) - 1
+    entries, biases = [], []
+    for n, k in ((f, h), (h, f)):
+        w = torch.randn((n, k), generator=g, device=dev) * 0.03
+        entries.append(ops.weight_codes(w, w.abs().amax(1) / top, torch.zeros(n, dtype=torch.int32, device=dev), 0, -top - 1, top, bits=bits))
+        biases.append(torch.randn(n, generator=g, device=dev))
+    codes, rowsum = ops.activation_codes(torch.randn((m, h), generator=g, device=dev), record)
+
+    def chain():
+        y = ops.gelu_fake_quant_per_tensor(ops.linear_int(codes, rowsum, record, entries[0], biases[0]), *mid)
+        return ops.linear_int(*ops.activation_codes(y, mid), mid, entries[1], biases[1])
+
+    def fused():
+        return ops.linear_int(*ops.linear_int_codes(codes, rowsum, record, entries[0], biases[0], mid), mid, entries[1], biases[1])
+    want = chain()
+    assert torch.equal(fused(), want) and bool(torch.isfinite(want).all())
+    emit(f"  [{m}, {h}] -> {f} -> {h}, W{bits}A8: the same words")
+    report(emit, timed({"chain": chain, "ffn": fused}, reps, inner), "chain", "ffn")
+
+
+def model_ffn(emit, label, fn, reps, inner):
+    import outlier_suppression_amd as osq
+    from outlier_suppression_amd import util_layernorm as UL
+    from outlier_suppression_amd.quantization import linear_int
+
+    def form(on):
+        def call():
+            linear_int.FUSE_FFN = on
+            with torch.no_grad():
+                return fn()
+        return call
+    old = linear_int.FUSE_FFN, linear_int.FFN_MAX_ROWS
+    linear_int.FFN_MAX_ROWS = None                       # the path at every M: what ffn's routing by rows is decided from
+    osq.set_fast_linear_int(True)
+    UL.linear_int.reset()
+    on = form(True)()
+    emit(f"{label}: {UL.linear_int}; the same words: {bool(torch.equal(on, form(False)()))}")
+    report(emit, timed({"chain": form(False), "ffn": form(True)}, reps, inner), "chain", "ffn")
+    osq.set_fast_linear_int(False)
+    linear_int.FUSE_FFN, linear_int.FFN_MAX_ROWS = old
+    emit("")
+
+
 def model(emit, label, fn, reps, inner):
     import outlier_suppression_amd as osq
     from outlier_suppression_amd import util_layernorm as UL
@@ -141,6 +202,7 @@ def main():
     ap.add_argument("--inner", type=int, default=10)
     ap.add_argument("--no-models", action="store_true")
     ap.add_argument("--w4", action="store_true", help="the packed 4-bit weight rows alone")
+    ap.add_argument("--ffn", action="store_true", help="the feed-forward rows alone: fc1 writing fc2's codes against the chain")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     assert torch.cuda.is_available(), "linear_int_ab.py measures on a GPU"
@@ -150,7 +212,7 @@ def main():
         print(line, flush=True)
         lines.append(line)
     emit(f"tools/linear_int_ab.py on {torch.cuda.get_device_name(0)}: medians of {args.reps} rounds of --inner calls [min, max], "
-         "both forms in turn within each round" + ("" if args.w4 else "; linear_int includes its activation_codes launch"))
+         "both forms in turn within each round" + ("" if args.w4 or args.ffn else "; linear_int includes its activation_codes launch"))
     emit("")
     if args.w4:
         emit("packed 4-bit weights against the 8-bit entry of the same weight (W4A8), ops.linear_int alone, "
@@ -158,13 +220,30 @@ def main():
         for m, k, n in W4_LAYERS:
             layer_w4(emit, m, k, n, args.reps, args.inner)
             torch.cuda.empty_cache()
-    for label, m, shapes in ((), LAYERS)[not args.w4]:
+    if args.ffn:
+        emit(f"fc1 writing fc2's codes (ops.linear_int_codes) against the chain of launches it replaces, {args.inner} calls to a round")
+        for m, h, f in FFN_LAYERS:
+            for bits in (8, 4):
+                layer_ffn(emit, m, h, f, bits, args.reps, args.inner)
+            torch.cuda.empty_cache()
+        emit("")
+        if not args.no_models:
+            from attention_block_ab import bert_base
+            q, ids, mask = bert_base(32, 128)
+            tt = torch.zeros_like(ids)
+            model_ffn(emit, "BERT-base forward 32 x 128, W6A6", lambda: q(input_ids=ids, attention_mask=mask, token_type_ids=tt)[0], args.reps, 2)
+            del q
+            torch.cuda.empty_cache()
+            from decode_bench import build
+            q, ids, mask = build(32, 512, 12)
+            model_ffn(emit, "BART-large shape, encoder pass 32 x 512", lambda: q.get_encoder()(ids, attention_mask=mask)[0], args.reps, 1)
+    for label, m, shapes in ((), LAYERS)[not (args.w4 or args.ffn)]:
         emit(f"{label}: M = {m}")
         for k, n, count in shapes:
             layer(emit, m, k, n, count, args.reps, args.inner)
         emit("")
         torch.cuda.empty_cache()
-    if not args.no_models and not args.w4:
+    if not args.no_models and not args.w4 and not args.ffn:
         from attention_block_ab import bert_base
         for length in (128, 384):
             q, ids, mask = bert_base(32, length)
